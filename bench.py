@@ -20,6 +20,10 @@ sources it was taken from and marked stale when that is not the running library)
 this run with HIP events on the stream it runs on; peak = SIMDs x clock / 2 (one fp32 add / mul / fma wave-instruction per
 2 cycles per SIMD, tools/bench_valu_issue.hip); frac <= 1.  `cpu_baseline` times the oracle (a CPU port of the loop — the
 reference has no CPU renderer) on the host cores, on a bounded spp.
+
+A plain run sets up, warms up, times the steps, writes the last timed frame if --dump-outputs is given, and prints the line.
+Everything else — `roofline`, `cpu_baseline`, `parity`, `parity_timed_frame`, the N > 1 `assembly_verified` check and the
+--pipeline 2 `serial_render_ms_rank0` — runs only with --full, after the timed region.
 """
 import argparse
 import json
@@ -96,9 +100,16 @@ def parse():
                          "and the tail of the draining frame.  Not the default: the per-kernel durations the roofline is priced with are those of "
                          "kernels that share the GPU (the line then carries serial_render_ms_rank0 too), and no multi-GPU run has exercised it")
     ap.add_argument("--verify-assembly", dest="verify_assembly", action="store_true", default=True,
-                    help="N > 1 (default on): after the timed region rank 0 renders the frame alone and requires the assembled image to be the "
-                         "same bits; the JSON line carries assembly_verified")
+                    help="N > 1 with --full (default on): after the timed region rank 0 renders the frame alone and requires the assembled image "
+                         "to be the same bits; the JSON line carries assembly_verified")
     ap.add_argument("--no-verify-assembly", dest="verify_assembly", action="store_false")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the legs beyond the headline figure: roofline, cpu_baseline, parity, "
+                         "parity_timed_frame, assembly_verified (N > 1), serial_render_ms_rank0 (--pipeline 2)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="rank 0 writes the framebuffer of the last timed step (what DownloadRenderbuffer returns) as DIR/framebuffer.npy "
+                         "(float32, H x W x 4, non-finite values set to 0) and DIR/framebuffer_nonfinite.npy (where they were: 1 NaN, "
+                         "2 +inf, 3 -inf); a frame above 64 MB is written as a fixed, seeded sample of its pixels instead")
     a = ap.parse_args()
     wl = WORKLOADS[a.workload]
     a.width = a.width or wl[4]
@@ -253,6 +264,40 @@ def sparse_leg(args, frame_rgba, tolerance_only=False):
     return res
 
 
+DUMP_CAP_BYTES = 64 << 20
+DUMP_SAMPLE_PIXELS = 1_000_000   # 16 B of RGBA + 16 B of non-finite classes + 8 B of pixel index each: 40 MB
+
+
+def split_nonfinite(a):
+    """(a with every NaN / inf replaced by 0, the class of each element as float32: 0 finite, 1 NaN, 2 +inf, 3 -inf).  The frame is finite
+    but for a few pixels where the path's arithmetic yields NaN — the CPU oracle's frame has NaN at the same pixels (`parity.nan_pixels_both`)."""
+    cls = np.zeros(a.shape, dtype=np.float32)
+    cls[np.isnan(a)] = 1
+    cls[np.isposinf(a)] = 2
+    cls[np.isneginf(a)] = 3
+    return np.where(cls == 0, a, np.float32(0)).astype(np.float32), cls
+
+
+def dump_outputs(out_dir, frame_rgba, W, H):
+    """--dump-outputs: the framebuffer of the last timed step as a caller of Render() + DownloadRenderbuffer() receives it (float32, H x W x 4),
+    every array finite: framebuffer.npy holds the frame with its non-finite values set to 0, framebuffer_nonfinite.npy (same shape) the
+    class of each value (split_nonfinite), so that the pair restores the frame.  A frame above DUMP_CAP_BYTES is written as a sample instead:
+    DUMP_SAMPLE_PIXELS pixels drawn with a fixed seed, in row-major order (framebuffer_sample.npy and framebuffer_sample_nonfinite.npy, n x 4)
+    next to their row-major indices (framebuffer_sample_pixels.npy, float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    img = np.ascontiguousarray(frame_rgba, dtype=np.float32).reshape(H, W, 4)
+    name, idx = "framebuffer", None
+    if 2 * img.nbytes > DUMP_CAP_BYTES:
+        name = "framebuffer_sample"
+        idx = np.sort(np.random.default_rng(0).choice(W * H, DUMP_SAMPLE_PIXELS, replace=False))
+        img = img.reshape(-1, 4)[idx]
+    vals, cls = split_nonfinite(img)
+    np.save(os.path.join(out_dir, f"{name}.npy"), vals)
+    np.save(os.path.join(out_dir, f"{name}_nonfinite.npy"), cls)
+    if idx is not None:
+        np.save(os.path.join(out_dir, "framebuffer_sample_pixels.npy"), idx.astype(np.float64))
+
+
 def self_launch(args):
     """`python bench.py --gpus N` (N > 1) without a launcher: start `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py
     <same arguments>` as a CHILD process — one rank per GPU — relay its output and return its exit code.  Nothing in THIS process has touched
@@ -377,8 +422,10 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        dump_outputs(args.dump_outputs, images[(frame[0] - 1) % depth].cpu().numpy(), W, H)
     serial_ms = None
-    if depth > 1:   # for the record: the same frame strictly one at a time (rank-local render, no gather), after the timed region
+    if depth > 1 and args.full:   # for the record: the same frame strictly one at a time (rank-local render, no gather), after the timed region
         fence()
         ts = time.perf_counter()
         for _ in range(3):
@@ -414,7 +461,7 @@ def main():
     out = None
     if rank == 0:
         base = counts = parity = None
-        if world_size == 1 and args.cpu_seconds > 0:
+        if args.full and world_size == 1 and args.cpu_seconds > 0:
             def gpu_image(spp_small):
                 rr = pkg.Renderer.MakeRenderer(W, H, spp_small, args.depth, cam, world, seed=args.seed, device=local_rank,
                                                variant=args.variant)
@@ -436,7 +483,7 @@ def main():
                        "kernel_variant": args.variant},
             "kernel_ms_per_step_rank0": round(kernel_ms, 3), "kernel_ms_source": kernel_ms_source + " (all kernels of a step)",
         }
-        if counts is None:
+        if args.full and counts is None:
             counts = count_leg(args)
         if counts is not None:
             bytes_per_sample = 32.0 * counts["box_tests"] + 16.0 * counts["leaf_tests"] + 16.0 * counts["shaded_hits"] + 16.0 / spp
@@ -496,24 +543,6 @@ def main():
                         "peak_GBps": HBM_PEAK_GBS,
                         "measured_frac_of_peak": None if traffic is None else round(traffic / (stream_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}}
             if per_rank is not None:
-                # N > 1: what a scaling curve needs to be read.  Row r = rank r's own measurement.
-                rms = per_rank[:, 0]
-                out["ranks_seen"] = int(dist.get_world_size())
-                out["backend"] = str(dist.get_backend())
-                out["per_rank"] = {
-                    "render_ms": [round(float(x), 3) for x in rms],
-                    "render_ms_min": round(float(rms.min()), 3), "render_ms_max": round(float(rms.max()), 3),
-                    "render_imbalance": round(float(rms.max() / rms.min() - 1.0), 4),
-                    "primary_rays_kernel_ms": [round(float(x), 3) for x in per_rank[:, 1]],
-                    "dominant_kernel_ms": [round(float(x), 3) for x in per_rank[:, 2]],
-                    "resolve_kernel_ms": [round(float(x), 3) for x in per_rank[:, 3]],
-                    "exchange_ms": [round(float(x), 3) for x in per_rank[:, 4]],
-                    "device": [int(x) for x in per_rank[:, 6]],
-                    "note": "HIP events on each rank's own streams, mean over the timed steps; exchange_ms = from 'this rank's render is done' to 'the "
-                            "gather (+ assemble_kernel on rank 0) is done' on the collectives' stream: rank 0's contains the wait for the slowest peer"}
-                out["gather_assemble_ms_rank0"] = round(float(per_rank[0, 4]), 3)
-                out["step_ms_breakdown_rank0"] = {"render": round(float(per_rank[0, 0]), 3), "exchange_and_assemble": round(float(per_rank[0, 4]), 3),
-                                                  "host_and_launch_gaps": round(elapsed / args.steps * 1e3 - float(per_rank[0, 0]) - float(per_rank[0, 4]), 3)}
                 out["roofline"]["kernel_ms_per_rank"] = [round(float(x), 3) for x in per_rank[:, 2]]
                 out["roofline"]["counters_scaled_by"] = f"1/{world_size} of the whole-frame counter summary (a rank's launch traces 1/{world_size} of the samples)"
             if base is not None:
@@ -522,7 +551,26 @@ def main():
                 out["parity"] = parity
             if world_size == 1 and args.sparse_parity > 0 and not args.no_parity and args.steps > 0:
                 out["parity_timed_frame"] = sparse_leg(args, images[(frame[0] - 1) % depth].cpu().numpy(), tolerance_only=not is_bit_exact_variant(kinfo["variant"]))
-        if args.verify_assembly and world_size > 1:
+        if per_rank is not None:
+            # N > 1: what a scaling curve needs to be read.  Row r = rank r's own measurement.
+            rms = per_rank[:, 0]
+            out["ranks_seen"] = int(dist.get_world_size())
+            out["backend"] = str(dist.get_backend())
+            out["per_rank"] = {
+                "render_ms": [round(float(x), 3) for x in rms],
+                "render_ms_min": round(float(rms.min()), 3), "render_ms_max": round(float(rms.max()), 3),
+                "render_imbalance": round(float(rms.max() / rms.min() - 1.0), 4),
+                "primary_rays_kernel_ms": [round(float(x), 3) for x in per_rank[:, 1]],
+                "dominant_kernel_ms": [round(float(x), 3) for x in per_rank[:, 2]],
+                "resolve_kernel_ms": [round(float(x), 3) for x in per_rank[:, 3]],
+                "exchange_ms": [round(float(x), 3) for x in per_rank[:, 4]],
+                "device": [int(x) for x in per_rank[:, 6]],
+                "note": "HIP events on each rank's own streams, mean over the timed steps; exchange_ms = from 'this rank's render is done' to 'the "
+                        "gather (+ assemble_kernel on rank 0) is done' on the collectives' stream: rank 0's contains the wait for the slowest peer"}
+            out["gather_assemble_ms_rank0"] = round(float(per_rank[0, 4]), 3)
+            out["step_ms_breakdown_rank0"] = {"render": round(float(per_rank[0, 0]), 3), "exchange_and_assemble": round(float(per_rank[0, 4]), 3),
+                                              "host_and_launch_gaps": round(elapsed / args.steps * 1e3 - float(per_rank[0, 0]) - float(per_rank[0, 4]), 3)}
+        if args.full and args.verify_assembly and world_size > 1:
             solo = pkg.Renderer.MakeRenderer(W, H, spp, args.depth, cam, world, seed=args.seed, device=local_rank, variant=args.variant)
             solo.Render()
             ref = solo.DownloadRenderbuffer()

@@ -5,6 +5,7 @@ builds (flat arrays bit-identical), and its rendered framebuffer must be bit-ide
 import os
 import re
 import subprocess
+import warnings
 
 import numpy as np
 import pytest
@@ -174,17 +175,19 @@ def test_header_is_plain_c_and_the_library_links_from_c():
     assert "C ABI ok" in out
 
 
-REF_GLM = "/root/reference/Libraries/include"
+GLM_APP = os.path.join(ROOT, "oracle", "_ref", "first_app_glm")   # built by `make -C oracle ref` (build() does it where the reference tree is)
+GLM_FLATTEN = os.path.join(ROOT, "tests", "golden", "first_app_glm_flatten.txt")
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF_GLM, "glm")), reason="build container only: needs the reference's vendored GLM (absent on the GPU box)")
-def test_cpp_api_compiles_against_the_references_own_glm_and_flattens_to_the_same_world(tmp_path):
+def test_cpp_api_compiles_against_the_references_own_glm_and_flattens_to_the_same_world():
     """INTEGRATION.md §2 tells a maintainer to build with -DRT06_USE_GLM so that glm::vec3 IS the reference's vendored GLM 0.9.9.7:
-    the FirstApp caller must compile that way and build byte-identical flat arrays."""
+    the FirstApp caller must compile that way and build byte-identical flat arrays.  tests/golden/first_app_glm_flatten.txt records what
+    that build printed; the build itself (oracle/_ref/first_app_glm) is run as well wherever build() could make it."""
     build_app()
-    exe = str(tmp_path / "first_app_glm")
-    libdir = os.path.join(ROOT, "ray-tracing-v06_amd", "csrc")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wno-volatile", "-Wno-deprecated-volatile", "-DRT06_USE_GLM", "-DGLM_ENABLE_EXPERIMENTAL",
-                           f"-I{REF_GLM}", f"-I{os.path.join(ROOT, 'include')}", "-o", exe, os.path.join(ROOT, "tests", "cpp", "first_app.cpp"),
-                           f"-L{libdir}", "-lrt06", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"])
-    assert subprocess.check_output([exe, "flatten"], text=True) == subprocess.check_output([APP, "flatten"], text=True)
+    got = subprocess.check_output([APP, "flatten"], text=True)
+    assert got == open(GLM_FLATTEN).read()
+    if os.path.exists(GLM_APP):
+        assert subprocess.check_output([GLM_APP, "flatten"], text=True) == got
+    else:   # the recorded output above is the whole check here; say so in the run's warnings summary
+        warnings.warn(f"{os.path.relpath(GLM_APP, ROOT)} not built (build() makes it only where the reference tree is): "
+                      "checked against the recorded output only")

@@ -270,6 +270,47 @@ def test_bench_workload_table_builds_matching_product_and_oracle_scenes():
         assert bytes(cam) == bytes(ocam), name
 
 
+def test_bench_dump_outputs_writes_the_frame_or_a_fixed_sample_of_it(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every array it writes is finite; a frame within the size cap is written whole (float32, H x W x 4) with its
+    NaN / inf values set to 0 and their classes next to it, so that the pair restores the frame bit for bit but for NaN payloads; a larger
+    frame as a sample of its pixels drawn with a fixed seed, in row-major order, next to their indices (float64), the same pixels on every run"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_dump", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    W, H = 32, 16
+    frame = np.random.default_rng(5).random(H * W * 4, dtype=np.float32)
+    frame[[3, 17, 18, 600]] = (np.nan, np.inf, -np.inf, np.nan)
+
+    def restore(vals, cls):
+        return np.where(cls == 1, np.float32(np.nan), np.where(cls == 2, np.float32(np.inf), np.where(cls == 3, np.float32(-np.inf), vals)))
+
+    def load_all(d):
+        out = {f: np.load(d / f) for f in os.listdir(d)}
+        for f, v in out.items():
+            assert v.dtype in (np.float32, np.float64) and np.isfinite(v).all(), f
+        return out
+
+    bench.dump_outputs(str(tmp_path / "whole"), frame, W, H)
+    whole = load_all(tmp_path / "whole")
+    assert sorted(whole) == ["framebuffer.npy", "framebuffer_nonfinite.npy"]
+    img, cls = whole["framebuffer.npy"], whole["framebuffer_nonfinite.npy"]
+    assert img.shape == cls.shape == (H, W, 4) and img.dtype == cls.dtype == np.float32
+    assert sorted(np.flatnonzero(cls)) == [3, 17, 18, 600] and cls.reshape(-1)[[3, 17, 18, 600]].tolist() == [1, 2, 3, 1]
+    assert bits_equal(restore(img, cls).reshape(-1), frame)
+    monkeypatch.setattr(bench, "DUMP_CAP_BYTES", frame.nbytes)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_PIXELS", 100)
+    for run in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / run), frame, W, H)
+    s1, s2 = load_all(tmp_path / "s1"), load_all(tmp_path / "s2")
+    assert sorted(s1) == ["framebuffer_sample.npy", "framebuffer_sample_nonfinite.npy", "framebuffer_sample_pixels.npy"]
+    smp, scls, idx = s1["framebuffer_sample.npy"], s1["framebuffer_sample_nonfinite.npy"], s1["framebuffer_sample_pixels.npy"]
+    assert smp.shape == scls.shape == (100, 4) and idx.shape == (100,)
+    assert np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < W * H
+    assert bits_equal(restore(smp, scls), frame.reshape(-1, 4)[idx.astype(np.int64)])
+    assert all(s1[f].tobytes() == s2[f].tobytes() for f in s1)
+
+
 def test_bench_roofline_is_recomputable_from_the_committed_counter_summary():
     """bench.py's `roofline` = SQ_INSTS_VALU of the newest profiles/rNN_bench_pmc_summary.csv / the live kernel time against
     SIMDs x clock / 2: recompute it here from the committed files alone and require frac <= 1 and a source-hash stamp."""

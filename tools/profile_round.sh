@@ -22,5 +22,5 @@ rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_V
 rocprofv3 --kernel-trace --pmc SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE --output-format csv -d $D/pmcB -- $BENCH > $D/pmcB.log 2>&1
 echo "sq counters done"
 python tools/summarize_profiles.py $TAG $NAME > /dev/null     # on the box: profiles/${TAG}_bench_pmc_summary.csv of THIS library, for the line below
-python bench.py $VARG --steps 20 --warmup 5 > $D/bench.json 2> $D/bench.err
+python bench.py --full $VARG --steps 20 --warmup 5 > $D/bench.json 2> $D/bench.err
 cat $D/bench.json

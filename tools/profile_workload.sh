@@ -23,5 +23,5 @@ rocprofv3 --kernel-trace --pmc SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAIT_ANY SQ_
 rocprofv3 --kernel-trace --pmc TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum TCP_PENDING_STALL_CYCLES_sum TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum --output-format csv -d $D/pmcC -- $BENCH > $D/pmcC.log 2>&1
 echo "counters done"
 python tools/summarize_profiles.py $TAG $WL > /dev/null     # on the box: profiles/${TAG}_${WL}_pmc_summary.csv of THIS library, for the line below
-python bench.py $ARGS --steps 5 --warmup 1 > $D/bench.json 2> $D/bench.err
+python bench.py --full $ARGS --steps 5 --warmup 1 > $D/bench.json 2> $D/bench.err
 cat $D/bench.json

@@ -2,7 +2,7 @@
 """Read the scaling curve out of bench.py's lines: one JSON line per GPU count (files, or stdin) -> a table with, per N, the whole-job rate, the
 speed-up over the N = 1 line, where a step's time goes on rank 0 (render / exchange + assembly / host gaps) and how evenly the ranks finished.
 
-    for n in 1 2 4 8; do python bench.py --gpus $n --steps 20 --warmup 5 > scale_n$n.json; done
+    for n in 1 2 4 8; do python bench.py --full --gpus $n --steps 20 --warmup 5 > scale_n$n.json; done
     python tools/scale_report.py scale_n*.json
 
 Everything it prints is in the lines themselves (`per_rank`, `gather_assemble_ms_rank0`, `step_ms_breakdown_rank0`, `roofline.kernel_ms_per_rank`);
