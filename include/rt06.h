@@ -378,6 +378,11 @@ int rt_probe_sphere(int device, size_t n, const float* rays, const float* sphere
  * hit n, t n, prim n, normal n*3                                             */
 int rt_probe_trace(int device, const rt_world_flat* world, size_t n, const float* rays,
                    int32_t* out_hit, float* out_t, int32_t* out_prim, float* out_normal);
+/* SphereHittable / MovingSphereHittable::ClosestIntersection (SphereHittable.cu:56-66, :91-102): sphere
+ * prims[i] (material ignored, RT_PRIM_MOVING kept) against ray i (o,d,time) with rec.distance preset[i]
+ * -> hit n, rec.distance n, normal n*3 (0 when not hit)                      */
+int rt_probe_sphere_hit(int device, size_t n, const rt_prim* prims, const float* rays, const float* preset,
+                        int32_t* out_hit, float* out_dist, float* out_normal);
 /* Material::Scatter (cu_materials.cuh:52,77,115,27): per case a material,
  * in-ray n*7, hit distance n, outward normal n*3, RNG key (pixel,sample) n*2
  * -> scattered n (0/1), out ray n*7, attenuation n*3, RNG blocks consumed n  */
@@ -387,6 +392,14 @@ int rt_probe_scatter(int device, uint64_t seed, size_t n, const rt_material* mat
 /* camera sample_ray (cu_Cameras.cuh:27,54,87): st n*2, keys n*2 -> ray n*7, RNG blocks consumed n */
 int rt_probe_camera(int device, uint64_t seed, const rt_camera* cam, size_t n, const float* st,
                     const uint32_t* keys, float* out_rays, uint32_t* out_draws);
+/* the same two on caller tapes of k in [1, 2^24] (u = k * 2^-24) instead of the generator: case i draws
+ * tape[offsets[2i] ..] for offsets[2i+1] uniforms; a case that wants more gets k = 2^23 + 1 and reports
+ * draws > its length                                                         */
+int rt_probe_scatter_tape(int device, size_t n, const rt_material* mats, const float* rays, const float* dist,
+                          const float* normals, const uint32_t* tape, size_t tape_len, const uint32_t* offsets,
+                          int32_t* out_scattered, float* out_rays, float* out_atten, uint32_t* out_draws);
+int rt_probe_camera_tape(int device, const rt_camera* cam, size_t n, const float* st, const uint32_t* tape,
+                         size_t tape_len, const uint32_t* offsets, float* out_rays, uint32_t* out_draws);
 /* one full sample (render_kernel body for one s + sample_world,
  * Renderer.cu:139-181,198-204): keys n*2 (pixel gid, sample) -> radiance n*3 */
 int rt_probe_radiance(const rt_render_config* cfg, const rt_camera* cam, const rt_world_flat* world,

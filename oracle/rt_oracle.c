@@ -238,25 +238,6 @@ void orc_rng_uniforms(uint64_t seed, uint32_t pixel, uint32_t sample, uint32_t s
     rng_t g; rng_init(&g, seed, pixel, sample, stream);
     for (uint32_t i = 0; i < n; i++) out[i] = rng_next(&g);
 }
-/* glm::cuRandomInUnit<2>, utilities/glm_utils.h:84-90 */
-static inline void rng_in_unit2(rng_t* g, float* ox, float* oy) {
-    for (;;) {
-        float x = rng_next(g) * 2.0f - 1.0f;
-        float y = rng_next(g) * 2.0f - 1.0f;
-        if (length2_2(x, y) < 1.0f) { *ox = x; *oy = y; return; }
-    }
-}
-/* glm::cuRandomOnUnit<3>, utilities/glm_utils.h:92-98 */
-static inline v3 rng_on_unit3(rng_t* g) {
-    for (;;) {
-        v3 v;
-        v.x = rng_next(g) * 2.0f - 1.0f;
-        v.y = rng_next(g) * 2.0f - 1.0f;
-        v.z = rng_next(g) * 2.0f - 1.0f;
-        if (!near_zero(v) && length2_3(v) < 1.0f) return normalize(v);
-    }
-}
-
 /* ------------------------------------------------------------------ */
 /* rays, boxes, spheres                                                */
 /* ------------------------------------------------------------------ */
@@ -296,6 +277,11 @@ static inline float sphere_closest_intersection(const ray_t* ray, v3 center, flo
     return t;
 }
 
+/* Leaf visiting order for orc_trace_order (test infrastructure): while it traces, the first leaf_log_cap spheres tested are
+ * written here in order.  NULL otherwise; set and cleared by orc_trace_order only, which no render runs alongside. */
+static int32_t* leaf_log = NULL;
+static uint32_t leaf_log_cap = 0;
+
 /* SphereHittable::ClosestIntersection (…/geometry/SphereHittable.cu:56-66) and
  * MovingSphereHittable::ClosestIntersection (:91-102) */
 static inline int prim_closest_intersection(const orc_world* w, int32_t idx, const ray_t* ray, rec_t* rec,
@@ -303,6 +289,7 @@ static inline int prim_closest_intersection(const orc_world* w, int32_t idx, con
     const orc_prim* p = &w->prims[idx];
     v3 center = ld3(p->c0);
     if (p->mat & ORC_PRIM_MOVING) center = mix3(ld3(p->c0), ld3(p->c1), ray->time);
+    if (leaf_log && cnt->leaf_tests < leaf_log_cap) leaf_log[cnt->leaf_tests] = idx;
     cnt->leaf_tests++;
     const orc_material* pm = &w->materials[p->mat & ~ORC_PRIM_MOVING];
     if (pm->type == 5) { /* RT_MAT_ISOTROPIC */
@@ -622,65 +609,6 @@ static v3 image_texel(const uint8_t* image, uint32_t width, uint32_t height, flo
     return V((float)px[0] * 0x1.010102p-8f, (float)px[1] * 0x1.010102p-8f, (float)px[2] * 0x1.010102p-8f);
 }
 
-/* Material::Scatter for the four material classes:
- *  LambertianAbstract  …/shaders/cu_materials.cuh:52-64
- *  MetalAbstract       :77-95
- *  DielectricAbstract  :115-143
- *  LambertianTexture   :27-40 */
-static int material_scatter(const orc_material* m, const ray_t* in_ray, const rec_t* rec, rng_t* g,
-                            ray_t* out, v3* attenuation, const orc_world* w) {
-    v3 normal = rec->normal;
-    if (m->type == 4) return 0; /* diffuse_light of "The Next Week": emits (material_emitted), never scatters */
-    switch (m->type) {
-    case 0:
-    case 3:
-    case 6:   /* lambertian(noise_texture) */
-    case 7: { /* lambertian(image_texture) */
-        v3 ray_dir = add(normal, rng_on_unit3(g));
-        if (near_zero(ray_dir)) return 0;
-        out->o = ray_at(in_ray, rec->distance); out->d = ray_dir; out->time = in_ray->time;
-        if (m->type == 0) *attenuation = ld3(m->albedo);
-        else if (m->type == 3) *attenuation = checker_value(m, ray_at(in_ray, rec->distance));
-        else if (m->type == 6) *attenuation = noise_value(w->perlin, ld3(m->albedo), m->param, ray_at(in_ray, rec->distance));
-        else if (rec->prim >= 0 && (uint32_t)rec->prim >= w->n_prims)
-            *attenuation = image_value_quad(w->image, w->image_width, w->image_height, &w->quads[(uint32_t)rec->prim - w->n_prims], ray_at(in_ray, rec->distance));
-        else *attenuation = image_value(w->image, w->image_width, w->image_height, normal);
-        return 1;
-    }
-    case 1: {
-        v3 refl = reflect(in_ray->d, normal);
-        v3 scatter_dir = add(refl, muls(rng_on_unit3(g), m->param));
-        if (dot(scatter_dir, normal) < 0 || near_zero(scatter_dir)) return 0;
-        out->o = ray_at(in_ray, rec->distance); out->d = scatter_dir; out->time = in_ray->time;
-        *attenuation = ld3(m->albedo);
-        return 1;
-    }
-    case 5: { /* isotropic phase function of "The Next Week" (extension): a uniformly random direction, always scatters */
-        out->o = ray_at(in_ray, rec->distance); out->d = rng_on_unit3(g); out->time = in_ray->time;
-        *attenuation = ld3(m->albedo);
-        return 1;
-    }
-    default: {
-        float ior = m->param;
-        int hit_backface = dot(in_ray->d, normal) > 0; /* isBackfacing, ray_data.cuh:44-46 */
-        if (hit_backface) normal = neg(normal);
-        float ior_ratio = hit_backface ? ior : 1 / ior;
-        v3 unit_dir = normalize(in_ray->d);
-        float cos_theta = fminf(dot(neg(unit_dir), normal), 1.0f);
-        float sin_theta = sqrtf(1.0f - cos_theta * cos_theta);
-        float reflect_prob = reflectance(cos_theta, ior_ratio);
-        v3 scatter_dir;
-        if (ior_ratio * sin_theta > 1.0f || reflect_prob > rng_next(g))
-            scatter_dir = reflect(unit_dir, normal);
-        else
-            scatter_dir = refract(unit_dir, normal, ior_ratio);
-        out->o = ray_at(in_ray, rec->distance); out->d = scatter_dir; out->time = in_ray->time;
-        *attenuation = ld3(m->albedo);
-        return 1;
-    }
-    }
-}
-
 /* ------------------------------------------------------------------ */
 /* cameras, …/shaders/cu_Cameras.cuh                                   */
 /* ------------------------------------------------------------------ */
@@ -721,28 +649,30 @@ void orc_camera_motion(const float lookfrom[3], const float lookat[3], const flo
     out->t0 = t0; out->t1 = t1;
 }
 
-/* sample_ray :27-30 (pinhole), :54-64 (defocus), :87-89 (motion) */
-static inline ray_t camera_sample_ray(const orc_camera* c, float s, float t, rng_t* g) {
-    ray_t r;
-    v3 o = ld3(c->o), u = ld3(c->u), v = ld3(c->v), w = ld3(c->w);
-    if (c->type == 1) {
-        float dx, dy;
-        rng_in_unit2(g, &dx, &dy);
-        v3 offset = add(muls(u, dx), muls(v, dy));
-        offset = muls(offset, c->lens_radius);
-        v3 forward = muls(w, c->focus_dist);
-        v3 hori = muls(muls(u, c->viewport_width), c->focus_dist);
-        v3 vert = muls(muls(v, c->viewport_height), c->focus_dist);
-        r.o = add(o, offset);
-        r.d = sub(add(add(forward, muls(hori, s)), muls(vert, t)), offset);
-        r.time = 0.0f;
-    } else {
-        r.o = o;
-        r.d = add(add(w, muls(u, s)), muls(v, t));
-        r.time = (c->type == 2) ? mix1(c->t0, c->t1, rng_next(g)) : 0.0f;
-    }
-    return r;
+#define DRAW_GEN rng_t
+#define DRAW_NEXT(g) rng_next(g)
+#define DRAW_FN(name) name
+#include "rt_oracle_draws.inc"
+#undef DRAW_GEN
+#undef DRAW_NEXT
+#undef DRAW_FN
+
+/* A tape of k in [1, 2^24], u = k * 2^-24: the values rng_next can produce, chosen by the caller.  Past the end of the tape it
+ * serves u = (2^23 + 1) * 2^-24, which every rejection loop accepts (so a short tape cannot hang), and keeps counting: draws > the
+ * tape's length reports the overrun. */
+typedef struct { const uint32_t* k; uint32_t n; uint32_t draws; } tape_t;
+static inline float tape_next(tape_t* g) {
+    uint32_t k = g->draws < g->n ? g->k[g->draws] : 0x800001u;
+    g->draws++;
+    return (float)k * 5.9604644775390625e-08f; /* 2^-24 */
 }
+#define DRAW_GEN tape_t
+#define DRAW_NEXT(g) tape_next(g)
+#define DRAW_FN(name) name##_tape
+#include "rt_oracle_draws.inc"
+#undef DRAW_GEN
+#undef DRAW_NEXT
+#undef DRAW_FN
 
 /* ------------------------------------------------------------------ */
 /* sample_world, main/src/Renderer.cu:139-181                          */
@@ -915,6 +845,45 @@ void orc_scatter_batch(uint64_t seed, size_t n, const orc_material* mats, const 
         v3 att = V(0, 0, 0);
         out_scattered[i] = material_scatter(&mats[i], &in, &rec, &g, &out, &att, NULL);
         st_ray7(out_rays + 7 * i, &out); st3(out_atten + 3 * i, att); out_draws[i] = g.draws;
+    }
+}
+/* the same two functions on caller tapes: case i draws tape[offsets[2i] .. offsets[2i] + offsets[2i+1]) */
+void orc_scatter_tape(size_t n, const orc_material* mats, const float* rays, const float* dist, const float* normals,
+                      const uint32_t* tape, const uint32_t* offsets, int32_t* out_scattered, float* out_rays, float* out_atten,
+                      uint32_t* out_draws) {
+    for (size_t i = 0; i < n; i++) {
+        ray_t in = ld_ray7(rays + 7 * i);
+        rec_t rec; rec.distance = dist[i]; rec.normal = ld3(normals + 3 * i); rec.prim = 0; rec.mat = 0;
+        tape_t g; g.k = tape + offsets[2 * i]; g.n = offsets[2 * i + 1]; g.draws = 0;
+        ray_t out; out.o = V(0, 0, 0); out.d = V(0, 0, 0); out.time = 0.0f;
+        v3 att = V(0, 0, 0);
+        out_scattered[i] = material_scatter_tape(&mats[i], &in, &rec, &g, &out, &att, NULL);
+        st_ray7(out_rays + 7 * i, &out); st3(out_atten + 3 * i, att); out_draws[i] = g.draws;
+    }
+}
+void orc_camera_tape(const orc_camera* cam, size_t n, const float* st, const uint32_t* tape, const uint32_t* offsets,
+                     float* out_rays, uint32_t* out_draws) {
+    for (size_t i = 0; i < n; i++) {
+        tape_t g; g.k = tape + offsets[2 * i]; g.n = offsets[2 * i + 1]; g.draws = 0;
+        ray_t r = camera_sample_ray_tape(cam, st[2 * i], st[2 * i + 1], &g);
+        st_ray7(out_rays + 7 * i, &r); out_draws[i] = g.draws;
+    }
+}
+/* SphereHittable / MovingSphereHittable::ClosestIntersection with rec.distance preset (SphereHittable.cu:56-66, :91-102):
+ * prims[i] against ray i, the material index of each prim ignored (a plain sphere) */
+void orc_sphere_hit_batch(size_t n, const orc_prim* prims, const float* rays, const float* preset, int32_t* out_hit,
+                          float* out_dist, float* out_normal) {
+    orc_material mat; memset(&mat, 0, sizeof(mat));
+    orc_counters cnt; memset(&cnt, 0, sizeof(cnt));
+    for (size_t i = 0; i < n; i++) {
+        orc_prim p = prims[i];
+        p.mat &= ORC_PRIM_MOVING;
+        orc_world w; memset(&w, 0, sizeof(w));
+        w.prims = &p; w.n_prims = 1; w.materials = &mat; w.n_materials = 1;
+        ray_t r = ld_ray7(rays + 7 * i);
+        rec_t rec; rec.distance = preset[i]; rec.prim = -1; rec.mat = 0; rec.normal = V(0, 0, 0);
+        out_hit[i] = prim_closest_intersection(&w, 0, &r, &rec, &cnt, NULL);
+        out_dist[i] = rec.distance; st3(out_normal + 3 * i, rec.normal);
     }
 }
 void orc_camera_batch(uint64_t seed, const orc_camera* cam, size_t n, const float* st, const uint32_t* keys,
@@ -1472,6 +1441,25 @@ void orc_ray_batch(size_t n, const float* in, float* out) {
         st3(out + 4 * i, ray_at(&r, in[10 * i + 6]));
         out[4 * i + 3] = dot(r.d, ld3(in + 10 * i + 7)) > 0 ? 1.0f : 0.0f;
     }
+}
+/* the first max_order spheres tested by one trace per ray, in order (-1 past the last): out_order n * max_order */
+int orc_trace_order(const orc_world* w, size_t n, const float* rays, uint32_t max_order, int32_t* out_order) {
+    int err = 0;
+    for (size_t i = 0; i < n; i++) {
+        ray_t r = ld_ray7(rays + 7 * i);
+        rec_t rec;
+        memset(&rec, 0, sizeof(rec));
+        rec.distance = ORC_MISS_DIST; rec.prim = -1;
+        orc_counters c;
+        memset(&c, 0, sizeof(c));
+        rng_t g;
+        rng_init(&g, 0u, (uint32_t)i, 0u, 0x7ACEu);
+        for (uint32_t k = 0; k < max_order; k++) out_order[i * max_order + k] = -1;
+        leaf_log = out_order + i * max_order; leaf_log_cap = max_order;
+        world_closest_intersection(w, &r, &rec, &c, &err, &g);
+        leaf_log = NULL; leaf_log_cap = 0;
+    }
+    return err;
 }
 /* leaf tests / box tests of one trace per ray (the instrumented counters of the render loop, per ray) */
 int orc_trace_counts(const orc_world* w, size_t n, const float* rays, uint32_t* out_leaf_tests, uint32_t* out_box_tests) {

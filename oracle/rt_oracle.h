@@ -17,11 +17,12 @@
  *   - rt_engine/geometry/HittableList.cuh, bvh_node.cuh (probe leaves)  -> ref_agg_*              list_/tree_closest_intersection
  *   - rt_engine/shaders/cu_Textures.cuh                                 -> ref_checker_*          checker_value
  *   - rt_engine/ray_data.cuh, geometry/BVH.cuh (layouts)                -> ref_ray_*, ref_layout.json
- * PARITY UNPINNED against an executing reference — the files do not build here (cuError.h needs <format>, cuda_utils.cuh
- * and Renderer.cu contain <<<>>>, cuRandom.cuh needs curand_kernel.h) and the reference ships no golden vectors (its one
- * gtest depends on cuRAND's host stream): _sphere_closest_intersection and the sphere hittables, BVH::ClosestIntersection
- * and the builders, Scatter, the cameras, sample_world, render_kernel, the scene generators — restated by hand from the
- * source text.  Their outputs of today are frozen in tests/golden/frozen_*.npz (oracle/gen_frozen.py) so that oracle and
+ *   - geometry/SphereHittable.cuh/.cu, BVH.cuh/.cu (traversal, Factory), shaders/cu_materials.cuh, cu_Cameras.cuh, with
+ *     oracle/ref_shim/ (tape-served curand_uniform, cuError.h / cuda_utils.cuh prelude, host cudaMalloc stubs)
+ *                                                                       -> ref_core_*  sphere hits, flat BVH + builders,
+ *                                                                          material_scatter, the cameras (orc_*_tape)
+ * PARITY UNPINNED against an executing reference (Renderer.cu contains <<<>>>; the reference ships no golden vectors):
+ * sample_world, render_kernel, the scene generators — restated by hand from the source text.  Their outputs of today are frozen in tests/golden/frozen_*.npz (oracle/gen_frozen.py) so that oracle and
  * kernels cannot drift together unnoticed.  The RNG is the build's own counter-seeded generator (the reference's cuRAND
  * XORWOW streams are not reproducible offline); Philox is pinned against the Random123 known-answer vectors.
  *
@@ -121,6 +122,14 @@ void orc_scatter_batch(uint64_t seed, size_t n, const orc_material* mats, const 
                        int32_t* out_scattered, float* out_rays, float* out_atten, uint32_t* out_draws);
 void orc_camera_batch(uint64_t seed, const orc_camera* cam, size_t n, const float* st,
                       const uint32_t* keys, float* out_rays, uint32_t* out_draws);
+/* the same on caller tapes of k (u = k * 2^-24): case i draws tape[offsets[2i] ..][: offsets[2i+1]]; draws > that length = overrun */
+void orc_scatter_tape(size_t n, const orc_material* mats, const float* rays, const float* dist, const float* normals,
+                      const uint32_t* tape, const uint32_t* offsets, int32_t* out_scattered, float* out_rays, float* out_atten,
+                      uint32_t* out_draws);
+void orc_camera_tape(const orc_camera* cam, size_t n, const float* st, const uint32_t* tape, const uint32_t* offsets,
+                     float* out_rays, uint32_t* out_draws);
+void orc_sphere_hit_batch(size_t n, const orc_prim* prims, const float* rays, const float* preset, int32_t* out_hit,
+                          float* out_dist, float* out_normal);
 int  orc_radiance_batch(const orc_world* w, const orc_camera* cam, uint32_t width, uint32_t height,
                         uint32_t max_depth, uint64_t seed, size_t n, const uint32_t* keys,
                         float* out_radiance);
@@ -132,6 +141,8 @@ void orc_aabb_misc_batch(size_t n, const float* boxes, float* out);
 void orc_checker_batch(size_t n, const float* in, float* out);
 void orc_ray_batch(size_t n, const float* in, float* out);
 int  orc_trace_counts(const orc_world* w, size_t n, const float* rays, uint32_t* out_leaf_tests, uint32_t* out_box_tests);
+/* the first max_order spheres each trace tests, in order, -1 past the last (not thread-safe: no render may run alongside) */
+int  orc_trace_order(const orc_world* w, size_t n, const float* rays, uint32_t max_order, int32_t* out_order);
 
 /* ---- cameras (constructors) ---- */
 void orc_camera_pinhole(const float lookfrom[3], const float lookat[3], const float up[3],

@@ -415,6 +415,39 @@ def probe_camera(seed, cam, st, keys, device=0):
     return orays, draws
 
 
+def probe_sphere_hit(prims, rays, preset, device=0):
+    """rt_probe_sphere_hit: (n,) PRIM_DT spheres, (n, 7) rays, (n,) preset rec.distance -> hit, rec.distance, normal (n, 3)"""
+    n = len(rays)
+    prims = np.ascontiguousarray(prims, dtype=capi.PRIM_DT)
+    hit = np.zeros(n, np.int32); dist = np.zeros(n, np.float32); nrm = np.zeros((n, 3), np.float32)
+    check(lib().rt_probe_sphere_hit(device, n, prims.ctypes.data, np.ascontiguousarray(rays, np.float32),
+                                    np.ascontiguousarray(preset, np.float32), hit, dist, nrm))
+    return hit, dist, nrm
+
+
+def probe_scatter_tape(mats, rays, dist, normals, tape, offsets, device=0):
+    """rt_probe_scatter_tape: probe_scatter with uniforms u = k * 2^-24 from `tape` (uint32 k); case i draws
+    tape[offsets[i, 0]:][:offsets[i, 1]] (draws > offsets[i, 1] = the case wanted more)"""
+    n = len(rays)
+    mats = np.ascontiguousarray(mats, dtype=capi.MAT_DT)
+    tape = np.ascontiguousarray(tape, np.uint32)
+    sc = np.zeros(n, np.int32); orays = np.zeros((n, 7), np.float32); att = np.zeros((n, 3), np.float32); draws = np.zeros(n, np.uint32)
+    check(lib().rt_probe_scatter_tape(device, n, mats.ctypes.data, np.ascontiguousarray(rays, np.float32),
+                                      np.ascontiguousarray(dist, np.float32), np.ascontiguousarray(normals, np.float32), tape, len(tape),
+                                      np.ascontiguousarray(offsets, np.uint32), sc, orays, att, draws))
+    return sc, orays, att, draws
+
+
+def probe_camera_tape(cam, st, tape, offsets, device=0):
+    """rt_probe_camera_tape: probe_camera with uniforms from `tape`, as probe_scatter_tape"""
+    n = len(st)
+    tape = np.ascontiguousarray(tape, np.uint32)
+    orays = np.zeros((n, 7), np.float32); draws = np.zeros(n, np.uint32)
+    check(lib().rt_probe_camera_tape(device, C.byref(cam), n, np.ascontiguousarray(st, np.float32), tape, len(tape),
+                                     np.ascontiguousarray(offsets, np.uint32), orays, draws))
+    return orays, draws
+
+
 def probe_radiance(cfg, cam, world, keys):
     n = len(keys)
     out = np.zeros((n, 3), np.float32)

@@ -396,7 +396,9 @@ RT_HD f3 image_texel(const uint8_t* image, uint32_t width, uint32_t height, floa
 // Material::Scatter — LambertianAbstract (cu_materials.cuh:52-64), MetalAbstract (:77-95),
 // DielectricAbstract (:115-143), LambertianTexture (:27-40)
 // `w`: the world's Perlin tables / image for the two textured extension materials (may be null otherwise)
-RT_HD bool material_scatter(const rt_material& m, const Ray& in_ray, const HitRec& rec, Rng& rng, Ray& out, f3& attenuation,
+// G: Rng, or the probes' tape of uniforms (rt_probes.hip), for the edges the generator's stream never reaches
+template <class G>
+RT_HD bool material_scatter(const rt_material& m, const Ray& in_ray, const HitRec& rec, G& rng, Ray& out, f3& attenuation,
                             const DeviceWorld* w = nullptr) {
     f3 normal = rec.normal;
     if (m.type == RT_MAT_DIFFUSE_LIGHT) return false;  // diffuse_light of "The Next Week": emits, never scatters
@@ -447,7 +449,8 @@ RT_HD bool material_scatter(const rt_material& m, const Ray& in_ray, const HitRe
 // sample_ray — PinholeCamera (cu_Cameras.cuh:27-30), DefocusBlurCamera (:54-64), MotionBlurCamera (:87-89), in two halves:
 // camera_draw consumes the camera's uniforms (defocus: the lens point InUnit<2>; motion: one uniform -> time), camera_ray
 // is the arithmetic.  The streaming path runs the first half in primary_rays_kernel and the second at regeneration.
-RT_HD void camera_draw(const rt_camera& c, Rng& rng, float& a, float& b) {
+template <class G>
+RT_HD void camera_draw(const rt_camera& c, G& rng, float& a, float& b) {
     a = 0.0f; b = 0.0f;
     if (c.type == RT_CAM_DEFOCUS) rng_in_unit2(rng, a, b);                // a, b = lens point in the unit disc
     else if (c.type == RT_CAM_MOTION) a = mix(c.t0, c.t1, rng.next());  // a = ray time
@@ -472,7 +475,8 @@ RT_HD Ray camera_ray(const rt_camera& c, float s, float t, float a, float b) {
     }
     return r;
 }
-RT_HD Ray camera_sample_ray(const rt_camera& c, float s, float t, Rng& rng) {
+template <class G>
+RT_HD Ray camera_sample_ray(const rt_camera& c, float s, float t, G& rng) {
     float a, b;
     camera_draw(c, rng, a, b);
     return camera_ray(c, s, t, a, b);

@@ -206,8 +206,9 @@ struct Rng {
         return (float)(int32_t)((result >> 8) + 1u - 0x800000u) * 1.1920928955078125e-07f;
     }
 };
-// glm::cuRandomInUnit<2>, utils:84-90
-RT_HD void rng_in_unit2(Rng& g, float& ox, float& oy) {
+// glm::cuRandomInUnit<2>, utils:84-90.  G: Rng, or the probes' tape of uniforms (rt_probes.hip)
+template <class G>
+RT_HD void rng_in_unit2(G& g, float& ox, float& oy) {
     for (;;) {
         float x = g.next_signed();
         float y = g.next_signed();
@@ -215,7 +216,8 @@ RT_HD void rng_in_unit2(Rng& g, float& ox, float& oy) {
     }
 }
 // glm::cuRandomOnUnit<3>, utils:92-98
-RT_HD f3 rng_on_unit3(Rng& g) {
+template <class G>
+RT_HD f3 rng_on_unit3(G& g) {
     // the normalisation (sqrt + division) sits AFTER the rejection loop: inside it a wave would execute it once per
     // iteration in which any lane accepts, i.e. ~6 times per call instead of once
     // `!near_zero(v) && length2(v) < 1` (utils:95): every component is a multiple of 2^-23 (next_signed), so v is near zero (all

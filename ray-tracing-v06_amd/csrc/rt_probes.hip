@@ -35,6 +35,24 @@ __global__ void probe_trace_kernel(DeviceWorld w, size_t n, const float* rays, i
     t[i] = rec.distance; prim[i] = rec.prim;
     st3(normal + 3 * i, rec.normal);
 }
+// SphereHittable / MovingSphereHittable::ClosestIntersection on one sphere per ray, rec.distance preset by the caller: the leaf
+// test every traversal calls (prim_closest_intersection), as a plain sphere (material 0 = a Lambertian, the moving bit kept)
+__global__ void probe_sphere_hit_kernel(size_t n, const rt_prim* prims, const rt_material* mat, const float* rays, const float* preset,
+                                        int32_t* hit, float* dist, float* normal) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Ray r;
+    r.o = ld3(rays + 7 * i); r.d = ld3(rays + 7 * i + 3); r.time = rays[7 * i + 6];
+    HitRec rec;
+    rec.distance = preset[i]; rec.normal = mk3(0.0f); rec.prim = -1; rec.mat = 0;
+    rt_prim p = prims[i];
+    p.mat &= RT_PRIM_MOVING;
+    Rng g;
+    g.init(0u, (uint32_t)i, 0u, 0x7ACEu);   // not drawn from: a Lambertian sphere is no constant medium
+    hit[i] = prim_closest_intersection(p, (int32_t)i, r, rec, mat, &g) ? 1 : 0;
+    dist[i] = rec.distance;
+    st3(normal + 3 * i, rec.normal);
+}
 __global__ void probe_scatter_kernel(uint64_t seed, size_t n, const rt_material* mats, const float* rays, const float* dist,
                                      const float* normals, const uint32_t* keys, int32_t* scattered, float* out_rays,
                                      float* atten, uint32_t* draws) {
@@ -59,6 +77,44 @@ __global__ void probe_camera_kernel(uint64_t seed, rt_camera cam, size_t n, cons
     if (i >= n) return;
     Rng g;
     g.init(seed, keys[2 * i], keys[2 * i + 1], RT_STREAM_RENDER);
+    Ray r = camera_sample_ray(cam, st[2 * i], st[2 * i + 1], g);
+    st3(out_rays + 7 * i, r.o); st3(out_rays + 7 * i + 3, r.d); out_rays[7 * i + 6] = r.time;
+    draws[i] = g.draws;
+}
+// A tape of k in [1, 2^24] in place of Rng: u = k * 2^-24 (next) and (k - 2^23) * 2^-23 (next_signed), the two forms Rng returns
+// for its word (rt_math.hpp).  Reaches the edges of measure zero under the generator's stream (k = 2^23 three times, |v| == 1, ...).
+// Past the end of its tape it serves k = 2^23 + 1, which every rejection loop accepts (no hang), and keeps counting: draws > the
+// tape's length reports the overrun.
+struct TapeRng {
+    const uint32_t* k;
+    uint32_t n, draws;
+    __device__ uint32_t take() { const uint32_t v = draws < n ? k[draws] : 0x800001u; draws++; return v; }
+    __device__ float next() { return (float)take() * 5.9604644775390625e-08f; }
+    __device__ float next_signed() { return (float)(int32_t)(take() - 0x800000u) * 1.1920928955078125e-07f; }
+};
+__global__ void probe_scatter_tape_kernel(size_t n, const rt_material* mats, const float* rays, const float* dist, const float* normals,
+                                          const uint32_t* tape, const uint32_t* offsets, int32_t* scattered, float* out_rays,
+                                          float* atten, uint32_t* draws) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Ray in;
+    in.o = ld3(rays + 7 * i); in.d = ld3(rays + 7 * i + 3); in.time = rays[7 * i + 6];
+    HitRec rec;
+    rec.distance = dist[i]; rec.normal = ld3(normals + 3 * i); rec.prim = 0; rec.mat = 0;
+    TapeRng g{tape + offsets[2 * i], offsets[2 * i + 1], 0u};
+    Ray out;
+    out.o = mk3(0.0f); out.d = mk3(0.0f); out.time = 0.0f;
+    f3 att = mk3(0.0f);
+    scattered[i] = material_scatter(mats[i], in, rec, g, out, att) ? 1 : 0;
+    st3(out_rays + 7 * i, out.o); st3(out_rays + 7 * i + 3, out.d); out_rays[7 * i + 6] = out.time;
+    st3(atten + 3 * i, att);
+    draws[i] = g.draws;
+}
+__global__ void probe_camera_tape_kernel(rt_camera cam, size_t n, const float* st, const uint32_t* tape, const uint32_t* offsets,
+                                         float* out_rays, uint32_t* draws) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    TapeRng g{tape + offsets[2 * i], offsets[2 * i + 1], 0u};
     Ray r = camera_sample_ray(cam, st[2 * i], st[2 * i + 1], g);
     st3(out_rays + 7 * i, r.o); st3(out_rays + 7 * i + 3, r.d); out_rays[7 * i + 6] = r.time;
     draws[i] = g.draws;
@@ -158,6 +214,23 @@ extern "C" int rt_probe_trace(int device, const rt_world_flat* world, size_t n, 
     DOWN(out_hit, h, n * 4); DOWN(out_t, t, n * 4); DOWN(out_prim, p, n * 4); DOWN(out_normal, nn, n * 12);
     return check_traversal_overflow(sc);
 }
+extern "C" int rt_probe_sphere_hit(int device, size_t n, const rt_prim* prims, const float* rays, const float* preset, int32_t* out_hit,
+                                   float* out_dist, float* out_normal) {
+    if (!prims || !rays || !preset || !out_hit || !out_dist || !out_normal) return rt_fail(RT_ERR_INVALID, "rt_probe_sphere_hit: null argument");
+    if (n == 0) return RT_OK;
+    int rc = select_device(device);
+    if (rc != RT_OK) return rc;
+    rt_material lambertian{};
+    lambertian.type = RT_MAT_LAMBERTIAN;
+    DevBuf pr, m, r, ps, h, d, nn;
+    UP(pr, prims, n * sizeof(rt_prim)); UP(m, &lambertian, sizeof(lambertian)); UP(r, rays, n * 28); UP(ps, preset, n * 4);
+    HIP_TRY(h.alloc(n * 4)); HIP_TRY(d.alloc(n * 4)); HIP_TRY(nn.alloc(n * 12));
+    probe_sphere_hit_kernel<<<PROBE_GRID(n)>>>(n, pr.as<rt_prim>(), m.as<rt_material>(), r.as<float>(), ps.as<float>(), h.as<int32_t>(),
+                                               d.as<float>(), nn.as<float>());
+    FINISH();
+    DOWN(out_hit, h, n * 4); DOWN(out_dist, d, n * 4); DOWN(out_normal, nn, n * 12);
+    return RT_OK;
+}
 extern "C" int rt_probe_scatter(int device, uint64_t seed, size_t n, const rt_material* mats, const float* rays, const float* dist,
                                 const float* normals, const uint32_t* keys, int32_t* out_scattered, float* out_rays, float* out_atten,
                                 uint32_t* out_draws) {
@@ -188,6 +261,52 @@ extern "C" int rt_probe_camera(int device, uint64_t seed, const rt_camera* cam, 
     UP(s, st, n * 8); UP(k, keys, n * 8);
     HIP_TRY(r.alloc(n * 28)); HIP_TRY(d.alloc(n * 4));
     probe_camera_kernel<<<PROBE_GRID(n)>>>(seed, *cam, n, s.as<float>(), k.as<uint32_t>(), r.as<float>(), d.as<uint32_t>());
+    FINISH();
+    DOWN(out_rays, r, n * 28); DOWN(out_draws, d, n * 4);
+    return RT_OK;
+}
+// every case's [offset, length) must lie inside the tape: the kernels read tape[offset + j] for j < length only
+static int check_tape(const char* fn, size_t n, size_t tape_len, const uint32_t* offsets) {
+    for (size_t i = 0; i < n; i++)
+        if ((uint64_t)offsets[2 * i] + offsets[2 * i + 1] > tape_len)
+            return rt_fail(RT_ERR_INVALID, "%s: case %zu: tape range [%u, +%u) outside a tape of %zu", fn, i, offsets[2 * i], offsets[2 * i + 1], tape_len);
+    return RT_OK;
+}
+extern "C" int rt_probe_scatter_tape(int device, size_t n, const rt_material* mats, const float* rays, const float* dist, const float* normals,
+                                     const uint32_t* tape, size_t tape_len, const uint32_t* offsets, int32_t* out_scattered, float* out_rays,
+                                     float* out_atten, uint32_t* out_draws) {
+    if (!mats || !rays || !dist || !normals || !tape || !offsets || !out_scattered || !out_rays || !out_atten || !out_draws)
+        return rt_fail(RT_ERR_INVALID, "rt_probe_scatter_tape: null argument");
+    if (n == 0) return RT_OK;
+    for (size_t i = 0; i < n; i++)
+        if (mats[i].type > RT_MAT_ISOTROPIC) return rt_fail(RT_ERR_INVALID, "rt_probe_scatter_tape: case %zu: unknown material type", i);
+    int rc = check_tape("rt_probe_scatter_tape", n, tape_len, offsets);
+    if (rc != RT_OK) return rc;
+    rc = select_device(device);
+    if (rc != RT_OK) return rc;
+    DevBuf m, r, d, nn, tp, of, s, orr, a, dr;
+    UP(m, mats, n * sizeof(rt_material)); UP(r, rays, n * 28); UP(d, dist, n * 4); UP(nn, normals, n * 12); UP(tp, tape, tape_len * 4);
+    UP(of, offsets, n * 8);
+    HIP_TRY(s.alloc(n * 4)); HIP_TRY(orr.alloc(n * 28)); HIP_TRY(a.alloc(n * 12)); HIP_TRY(dr.alloc(n * 4));
+    probe_scatter_tape_kernel<<<PROBE_GRID(n)>>>(n, m.as<rt_material>(), r.as<float>(), d.as<float>(), nn.as<float>(), tp.as<uint32_t>(),
+                                                 of.as<uint32_t>(), s.as<int32_t>(), orr.as<float>(), a.as<float>(), dr.as<uint32_t>());
+    FINISH();
+    DOWN(out_scattered, s, n * 4); DOWN(out_rays, orr, n * 28); DOWN(out_atten, a, n * 12); DOWN(out_draws, dr, n * 4);
+    return RT_OK;
+}
+extern "C" int rt_probe_camera_tape(int device, const rt_camera* cam, size_t n, const float* st, const uint32_t* tape, size_t tape_len,
+                                    const uint32_t* offsets, float* out_rays, uint32_t* out_draws) {
+    if (!cam || !st || !tape || !offsets || !out_rays || !out_draws) return rt_fail(RT_ERR_INVALID, "rt_probe_camera_tape: null argument");
+    if (cam->type > RT_CAM_MOTION) return rt_fail(RT_ERR_INVALID, "rt_probe_camera_tape: unknown camera type");
+    if (n == 0) return RT_OK;
+    int rc = check_tape("rt_probe_camera_tape", n, tape_len, offsets);
+    if (rc != RT_OK) return rc;
+    rc = select_device(device);
+    if (rc != RT_OK) return rc;
+    DevBuf s, tp, of, r, d;
+    UP(s, st, n * 8); UP(tp, tape, tape_len * 4); UP(of, offsets, n * 8);
+    HIP_TRY(r.alloc(n * 28)); HIP_TRY(d.alloc(n * 4));
+    probe_camera_tape_kernel<<<PROBE_GRID(n)>>>(*cam, n, s.as<float>(), tp.as<uint32_t>(), of.as<uint32_t>(), r.as<float>(), d.as<uint32_t>());
     FINISH();
     DOWN(out_rays, r, n * 28); DOWN(out_draws, d, n * 4);
     return RT_OK;
