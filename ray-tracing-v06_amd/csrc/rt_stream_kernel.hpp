@@ -118,16 +118,21 @@ __device__ __forceinline__ bool block_origin(const TileMap& tm, uint32_t blk, ui
 }
 
 // A lane's status lives in `cur` alone (compares and selects are half-rate on gfx950; one register, one compare):
-//   cur <  RT_REF_IRR              at an inner node, ray in the fast-division class            } tracing
-//   cur <  RT_REF_LEAF             at an inner node (marked RT_REF_IRR: ray outside the class) }  (cur < K_SHADE)
-//   cur <  K_SHADE                 at a leaf: RT_REF_LEAF | code (code <= 0x7ffe)              }
-//   cur == K_SHADE                 trace finished, waiting for the shade phase
-//   cur == K_NEED                  path finished, waiting for a new sample
-//   cur == K_OFF                   no samples left
-//   cur == K_START                 got a new ray in this round; its trace begins at the end of the round
-// Values (K_* constants inside the kernel): 16-bit references: SHADE 0xffff (fits a stack entry: the sentinel at the bottom of
-// the stack; leaf codes stop at 0x7ffe), NEED 0x20000, OFF 0x30000, START 0x40000; 32-bit references (BIG): the top four
-// values 0xfffffffc .. 0xffffffff.  "Tracing" is `cur < K_SHADE` either way.
+//   cur <  IRR                     at an inner node, ray in the fast-division class            } tracing
+//   cur <  LEAF                    at an inner node (marked IRR: ray outside the class)        }  (cur < SHADE)
+//   cur <  SHADE                   at a leaf: LEAF | code (code <= 0x7ffe)                     }
+//   cur == SHADE                   trace finished, waiting for the shade phase
+//   cur == NEED                    path finished, waiting for a new sample (render_kernel_xchg's tracers: an empty lane)
+//   cur == OFF                     no samples left
+//   cur == START                   got a new ray in this round; its trace begins at the end of the round
+// 16-bit references: SHADE 0xffff (fits a stack entry: the sentinel at the bottom of the stack; leaf codes stop at 0x7ffe), NEED 0x20000,
+// OFF 0x30000, START 0x40000; 32-bit references (WIDE): the top four values 0xfffffffc .. 0xffffffff.  "Tracing" is `cur < SHADE` either way.
+template <bool WIDE>
+struct LaneStatus {
+    static constexpr uint32_t LEAF = WIDE ? RT_REF_LEAF_BIG : RT_REF_LEAF, IRR = WIDE ? RT_REF_IRR_BIG : RT_REF_IRR;
+    static constexpr uint32_t SHADE = WIDE ? 0xfffffffcu : 0xffffu, NEED = WIDE ? 0xfffffffdu : 0x20000u;
+    static constexpr uint32_t OFF = WIDE ? 0xfffffffeu : 0x30000u, START = WIDE ? 0xffffffffu : 0x40000u;
+};
 
 // The (near, far) plane pairs of both child boxes of wide node `idx` and its two child references.  kx/ky/kz: 0 where the
 // ray direction component is >= 0 (near = box min) or the ray is outside the fast class, 4 where it is negative.
@@ -208,11 +213,9 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
     const uint32_t lane = tid & 63u;
     const uint32_t wave = tid >> 6;
 
-    // reference encoding and lane status codes (see the header of this file)
+    // reference encoding and lane status codes (LaneStatus)
     using ref_t = typename std::conditional<WIDE, uint32_t, uint16_t>::type;
-    constexpr uint32_t K_LEAF = WIDE ? RT_REF_LEAF_BIG : RT_REF_LEAF, K_IRR = WIDE ? RT_REF_IRR_BIG : RT_REF_IRR;
-    constexpr uint32_t K_SHADE = WIDE ? 0xfffffffcu : 0xffffu, K_NEED = WIDE ? 0xfffffffdu : 0x20000u;
-    constexpr uint32_t K_OFF = WIDE ? 0xfffffffeu : 0x30000u, K_START = WIDE ? 0xffffffffu : 0x40000u;
+    using K = LaneStatus<WIDE>;
     static_assert(BIG || !WIDE, "an LDS-resident image always has 16-bit references");
 
     // ---- the scene: staged into the LDS with coalesced 16-B loads, or (BIG) left in global memory / L2 -------------
@@ -250,12 +253,12 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
     float ray_a = 0.0f;     // dot(ray.d, ray.d): the `a` of every sphere test of the trace (SphereHittable.cuh:17), computed once per ray
     float rec_t = RT_MISS_DIST;
     int32_t rec_code = -1;  // leaf code of the closest hit so far, -1 = none
-    uint32_t cur = K_NEED;   // node reference being visited, or the lane's status (see RT_CUR_*)
+    uint32_t cur = K::NEED;   // node reference being visited, or the lane's status (LaneStatus)
     ref_t* sp = stack + 64;   // next free entry of this lane's stack (entries are 64 apart; entry 0 is the sentinel)
-    *stack = (ref_t)K_SHADE;
+    *stack = (ref_t)K::SHADE;
     uint32_t kx = 0, ky = 0, kz = 0;  // byte offset (0 / 4) of the (near, far) pair inside an axis triple, per ray
     // FAST_BVH: the default kernel (variant 3).  Inner references of rays outside the fast-division class are marked
-    // with K_IRR (an LDS-resident tree has < 2^14 inner nodes) so that the hot loop needs no per-lane branch.
+    // with K::IRR (an LDS-resident tree has < 2^14 inner nodes) so that the hot loop needs no per-lane branch.
     constexpr bool FAST_BVH = !EXACT && !FILTER && WORLD == RT_WORLD_BVH;
     bool irr_pending = false;         // wave-uniform: some lane is traversing with a ray outside the class
     uint32_t depth = 0;
@@ -269,49 +272,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
     uint32_t pool_end = min(pool_next + p.chunk, p.total);
     bool pool_dry = false;
 
-// BVH.cu:59-60 / HittableList.cuh:22: root (world) box first, against rec.distance (= _MISS_DIST for a fresh
-// payload); bvh_node.cuh:20 tests a node's own box when it is visited, so a tree starts at its root unconditionally.
-#define RT_BEGIN_TRACE()                                                   \
-    do {                                                                   \
-        rec_t = RT_MISS_DIST;                                              \
-        rec_code = -1;                                                     \
-        if (WORLD == RT_WORLD_BVH_QUEUE) {   /* the whole trace, by this lane alone; leaf code as the shade phase wants it */ \
-            HitRec qrec_;                                                  \
-            qrec_.distance = RT_MISS_DIST; qrec_.normal = mk3(0.0f); qrec_.prim = -1; qrec_.mat = 0; \
-            if (p.world.traversal == RT_TRAVERSAL_WIDE4 ? bvh_closest_intersection_wide4(p.world, ray, qrec_, &rng) \
-                                                         : bvh_closest_intersection_queue(p.world, ray, qrec_, &rng)) { \
-                const uint32_t qp_ = (uint32_t)qrec_.prim;                 \
-                rec_t = qrec_.distance;                                    \
-                rec_code = qp_ < p.scene.n_prims ? (int32_t)(qp_ * 2u + ((p.world.prims[qp_].mat & RT_PRIM_MOVING) ? 1u : 0u)) \
-                                                 : (int32_t)(p.scene.sphere_codes + (qp_ - p.scene.n_prims)); \
-            }                                                              \
-            cur = K_SHADE;                                                 \
-            break;                                                         \
-        }                                                                  \
-        ray_a = dot(ray.d, ray.d);                                         \
-        if (!EXACT) {                                                      \
-            regular = ray_is_regular(ray);                                 \
-            inv_d = mk3(rcp_exact_regular(ray.d.x), rcp_exact_regular(ray.d.y), rcp_exact_regular(ray.d.z)); /* used by regular rays only */ \
-            if (FAST_BVH && !TOL) inv_lo = mk3(rcp_low_word(ray.d.x, inv_d.x), rcp_low_word(ray.d.y, inv_d.y), rcp_low_word(ray.d.z, inv_d.z)); \
-            const uint32_t km_ = (regular && FAST_BVH) ? 4u : 0u;          \
-            kx = (__float_as_uint(ray.d.x) >> 29) & km_;                   \
-            ky = (__float_as_uint(ray.d.y) >> 29) & km_;                   \
-            kz = (__float_as_uint(ray.d.z) >> 29) & km_;                   \
-        }                                                                  \
-        float d_root_;                                                     \
-        bool hit_root_;                                                    \
-        if (WORLD == RT_WORLD_NODE_TREE) hit_root_ = true;                 \
-        else if (EXACT || !regular) hit_root_ = aabb_intersects(root_min, root_max, ray, rec_t, d_root_);         \
-        else hit_root_ = root_box_hit_certified(root_min, root_max, ray, inv_d);   /* rec_t is _MISS_DIST here */  \
-        if (hit_root_) {                                                   \
-            cur = p.scene.root_ref;                                        \
-            if (FAST_BVH && !regular && cur < K_LEAF) cur |= K_IRR; \
-            sp = stack + 64;                                               \
-        } else {                                                           \
-            cur = K_SHADE;                                            \
-        }                                                                  \
-    } while (0)
-/* entry 0 of every lane's stack holds K_SHADE: popping an empty stack IS "trace finished", no test needed */ \
+/* entry 0 of every lane's stack holds K::SHADE: popping an empty stack IS "trace finished", no test needed */ \
 #define RT_POP()                      \
     do {                              \
         sp -= 64;                     \
@@ -321,7 +282,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
 #define RT_EMIT(rx, ry, rz)                                   \
     do {                                                      \
         store_sample(p.samples, out_idx, (rx), (ry), (rz));     \
-        cur = K_NEED;                                    \
+        cur = K::NEED;                                    \
     } while (0)
 
 #ifdef RT_PHASE_TIMERS
@@ -339,9 +300,9 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
         // ================= phase 1: inner-node steps (BVH.cu:76-97) ==================================
         if (FAST_BVH) {
             // Hot loop of the default kernel: lanes whose ray is in the fast-division class (all but a handful).  The
-            // step is straight-line code; lanes outside the class carry K_IRR in their inner references, so they
-            // fail `cur < K_IRR` here and are stepped by the verbatim loop below.
-            bool at_inner = cur < K_IRR;
+            // step is straight-line code; lanes outside the class carry K::IRR in their inner references, so they
+            // fail `cur < K::IRR` here and are stepped by the verbatim loop below.
+            bool at_inner = cur < K::IRR;
             if (__ballot(at_inner) != 0ull) {
                 uint32_t n_inner_lanes;
                 // inner_keep >= 1 (host); once the queue is dry the wave only drains its last paths: no reason to leave early.  The threshold is
@@ -395,7 +356,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                         tr_steps_++;
 #endif
                     }
-                    at_inner = cur < K_IRR;
+                    at_inner = cur < K::IRR;
                     n_inner_lanes = (uint32_t)__popcll(__ballot(at_inner));
 #ifdef RT_PHASE_TIMERS
                     pc_[6]++;
@@ -405,13 +366,13 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
             RT_PT(0);
             if (irr_pending) {   // wave-uniform, rare: rays with a zero / tiny / huge direction or origin component
                 for (;;) {
-                    const bool at_irr = (cur & (K_LEAF | K_IRR)) == K_IRR;
+                    const bool at_irr = (cur & (K::LEAF | K::IRR)) == K::IRR;
                     if (__ballot(at_irr) == 0ull) break;
                     if (at_irr) {
-                        const WideNodeData nd = fetch_wide_node<BIG>(nodes, lds, p.scene.n_top, cur & (K_IRR - 1u), 0u, 0u, 0u);   // near = min, far = max
+                        const WideNodeData nd = fetch_wide_node<BIG>(nodes, lds, p.scene.n_top, cur & (K::IRR - 1u), 0u, 0u, 0u);   // near = min, far = max
                         uint32_t left_idx = nd.left, right_idx = nd.right;
-                        if (left_idx < K_LEAF) left_idx |= K_IRR;     // inner references stay marked all the way down
-                        if (right_idx < K_LEAF) right_idx |= K_IRR;
+                        if (left_idx < K::LEAF) left_idx |= K::IRR;     // inner references stay marked all the way down
+                        if (right_idx < K::LEAF) right_idx |= K::IRR;
                         float left_dist = RT_MISS_DIST, right_dist = RT_MISS_DIST;
                         const bool hl = aabb_intersects(mk3(nd.lnx, nd.lny, nd.lnz), mk3(nd.lfx, nd.lfy, nd.lfz), ray, rec_t, left_dist);
                         const bool hr = aabb_intersects(mk3(nd.rnx, nd.rny, nd.rnz), mk3(nd.rfx, nd.rfy, nd.rfz), ray, rec_t, right_dist);
@@ -424,11 +385,11 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                         if (!(hl || hr)) RT_POP();
                     }
                 }
-                irr_pending = __ballot(!regular && (cur < K_SHADE)) != 0ull;
+                irr_pending = __ballot(!regular && (cur < K::SHADE)) != 0ull;
             }
             RT_PT(1);
         } else if (WORLD != RT_WORLD_BVH_QUEUE) {   // (a queue world's lanes are never "at a node": their trace ran when it began)
-            bool at_inner = cur < K_LEAF;
+            bool at_inner = cur < K::LEAF;
             uint64_t m_inner = __ballot(at_inner);
             while (m_inner != 0ull) {
                 if (at_inner) {
@@ -482,7 +443,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                         if (!(hl || hr)) RT_POP();
                     }
                 }
-                at_inner = cur < K_LEAF;
+                at_inner = cur < K::LEAF;
                 m_inner = __ballot(at_inner);
                 if ((uint32_t)__popcll(m_inner) < p.inner_keep) break;
             }
@@ -490,14 +451,14 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
 
         // ================= phase 2: leaves (BVH.cu:69-73 -> SphereHittable.cu:56-66 / :91-102) ========
         {
-            bool at_leaf = WORLD != RT_WORLD_BVH_QUEUE && (cur - K_LEAF) < (K_SHADE - K_LEAF);
+            bool at_leaf = WORLD != RT_WORLD_BVH_QUEUE && (cur - K::LEAF) < (K::SHADE - K::LEAF);
             uint64_t m_leaf = __ballot(at_leaf);
-            if (m_leaf != 0ull && ((uint32_t)__popcll(m_leaf) >= p.leaf_min || __ballot(cur < K_LEAF) == 0ull)) {
+            if (m_leaf != 0ull && ((uint32_t)__popcll(m_leaf) >= p.leaf_min || __ballot(cur < K::LEAF) == 0ull)) {
                 if (at_leaf) {
 #ifdef RT_TRACE_HIST
                     tr_leafs_++;
 #endif
-                    uint32_t code = cur & (K_LEAF - 1u);   // BVH / tree: prim * 2 + is_moving;  list: unified primitive index
+                    uint32_t code = cur & (K::LEAF - 1u);   // BVH / tree: prim * 2 + is_moving;  list: unified primitive index
                     const uint32_t first_quad = (WORLD == RT_WORLD_LIST) ? p.scene.n_prims : p.scene.sphere_codes;
                     if (EXT && code >= first_quad) {
                         // quad::hit ("The Next Week"), reference conventions: see quad_closest_intersection()
@@ -514,8 +475,8 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                             rec_code = (int32_t)(code - first_quad + p.scene.sphere_codes);   // the shade phase's code space
                         }
                         if (WORLD == RT_WORLD_LIST) {  // HittableList.cuh:26-30: every object, in order (the quads follow the spheres)
-                            if (code + 1u < p.scene.n_prims + p.scene.n_quads) cur = K_LEAF | (code + 1u);
-                            else cur = K_SHADE;
+                            if (code + 1u < p.scene.n_prims + p.scene.n_quads) cur = K::LEAF | (code + 1u);
+                            else cur = K::SHADE;
                         } else {
                             RT_POP();
                         }
@@ -545,8 +506,8 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                         rec_code = (int32_t)code;
                     }
                     if (WORLD == RT_WORLD_LIST) {  // HittableList.cuh:26-30: every object, in order
-                        if (prim + 1u < p.scene.n_prims + (EXT ? p.scene.n_quads : 0u)) cur = K_LEAF | (prim + 1u);
-                        else cur = K_SHADE;
+                        if (prim + 1u < p.scene.n_prims + (EXT ? p.scene.n_quads : 0u)) cur = K::LEAF | (prim + 1u);
+                        else cur = K::SHADE;
                     } else {
                         RT_POP();
                     }
@@ -559,12 +520,12 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
         // ================= phase 3: shade finished traces, regenerate finished paths ==================
         // lanes that are not tracing wait for this phase (switched-off lanes count as waiting: near the end of the
         // pass that only makes the phase run a little earlier)
-        uint64_t m_trav = __ballot((cur < K_SHADE));
+        uint64_t m_trav = __ballot((cur < K::SHADE));
         if (64u - (uint32_t)__popcll(m_trav) < p.shade_min && m_trav != 0ull) continue;
 
         bool start_trace = false;  // lanes that got a new ray this round begin their trace in ONE place below
         RT_PT(8);
-        if (cur == K_SHADE) {  // sample_world's loop body after the trace (Renderer.cu:149-176)
+        if (cur == K::SHADE) {  // sample_world's loop body after the trace (Renderer.cu:149-176)
 #if defined(RT_PHASE_TIMERS) && defined(RT_TRACE_HIST)   // the histogram's atomics slow the kernel 40x: its own build flag
             atomicAdd(p.phase_acc + 32 + min(tr_steps_, 95u) * 16u + min(tr_leafs_, 15u), 1ull);
             tr_steps_ = 0; tr_leafs_ = 0;
@@ -686,7 +647,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
         // ---- (pixel jitter, camera sample, RNG state after those draws: Renderer.cu:199-201) was computed by
         // ---- primary_rays_kernel with every lane busy; here a lane only loads its 48-byte record.
         for (;;) {
-            uint64_t m_need = __ballot(cur == K_NEED);
+            uint64_t m_need = __ballot(cur == K::NEED);
             if (m_need == 0ull) break;
             if (pool_next == pool_end) {
                 if (pool_dry) break;
@@ -699,7 +660,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
             }
             uint32_t take = min(pool_end - pool_next, (uint32_t)__popcll(m_need));
             uint32_t rank = lane_rank(m_need);
-            if (cur == K_NEED && rank < take) {
+            if (cur == K::NEED && rank < take) {
                 const uint32_t n = pool_next + rank;
                 // all three 16-byte parts of the record go out together: ONE global round trip (a padding pixel's two extra loads are wasted, rarely)
                 const uint4 rs = RT_LOAD_ONCE(p.prim_rng + n);
@@ -716,7 +677,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                         RT_EMIT(0.0f, 0.0f, 0.0f);
                     } else {
                         start_trace = true;
-                        cur = K_START;  // no longer K_NEED, so the loop does not hand it another sample
+                        cur = K::START;  // no longer K::NEED, so the loop does not hand it another sample
                     }
                 }
                 // a padding pixel (outside the image / past the last tile) consumes the index and the lane asks again
@@ -724,18 +685,57 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
             pool_next += take;
         }
         RT_PT(4);
-        if (start_trace) RT_BEGIN_TRACE();
+        // BVH.cu:59-60 / HittableList.cuh:22: root (world) box first, against rec.distance (= _MISS_DIST for a fresh
+        // payload); bvh_node.cuh:20 tests a node's own box when it is visited, so a tree starts at its root unconditionally.
+        if (start_trace) {
+            rec_t = RT_MISS_DIST;
+            rec_code = -1;
+            if (WORLD == RT_WORLD_BVH_QUEUE) {   // the whole trace, by this lane alone; leaf code as the shade phase wants it
+                HitRec qrec;
+                qrec.distance = RT_MISS_DIST; qrec.normal = mk3(0.0f); qrec.prim = -1; qrec.mat = 0;
+                if (p.world.traversal == RT_TRAVERSAL_WIDE4 ? bvh_closest_intersection_wide4(p.world, ray, qrec, &rng)
+                                                             : bvh_closest_intersection_queue(p.world, ray, qrec, &rng)) {
+                    const uint32_t qp = (uint32_t)qrec.prim;
+                    rec_t = qrec.distance;
+                    rec_code = qp < p.scene.n_prims ? (int32_t)(qp * 2u + ((p.world.prims[qp].mat & RT_PRIM_MOVING) ? 1u : 0u))
+                                                    : (int32_t)(p.scene.sphere_codes + (qp - p.scene.n_prims));
+                }
+                cur = K::SHADE;
+            } else {
+                ray_a = dot(ray.d, ray.d);
+                if (!EXACT) {
+                    regular = ray_is_regular(ray);
+                    inv_d = mk3(rcp_exact_regular(ray.d.x), rcp_exact_regular(ray.d.y), rcp_exact_regular(ray.d.z));   // used by regular rays only
+                    if (FAST_BVH && !TOL) inv_lo = mk3(rcp_low_word(ray.d.x, inv_d.x), rcp_low_word(ray.d.y, inv_d.y), rcp_low_word(ray.d.z, inv_d.z));
+                    const uint32_t km = (regular && FAST_BVH) ? 4u : 0u;
+                    kx = (__float_as_uint(ray.d.x) >> 29) & km;
+                    ky = (__float_as_uint(ray.d.y) >> 29) & km;
+                    kz = (__float_as_uint(ray.d.z) >> 29) & km;
+                }
+                float d_root;
+                bool hit_root;
+                if (WORLD == RT_WORLD_NODE_TREE) hit_root = true;
+                else if (EXACT || !regular) hit_root = aabb_intersects(root_min, root_max, ray, rec_t, d_root);
+                else hit_root = root_box_hit_certified(root_min, root_max, ray, inv_d);   // rec_t is _MISS_DIST here
+                if (hit_root) {
+                    cur = p.scene.root_ref;
+                    if (FAST_BVH && !regular && cur < K::LEAF) cur |= K::IRR;
+                    sp = stack + 64;
+                } else {
+                    cur = K::SHADE;
+                }
+            }
+        }
         if (FAST_BVH && __ballot(start_trace && !regular) != 0ull) irr_pending = true;
-        if (pool_dry && cur == K_NEED) cur = K_OFF;
+        if (pool_dry && cur == K::NEED) cur = K::OFF;
         RT_PT(5);
-        if (__ballot(cur != K_OFF) == 0ull) break;
+        if (__ballot(cur != K::OFF) == 0ull) break;
     }
 #ifdef RT_PHASE_TIMERS
     if (lane == 0)
         for (int i = 0; i < 16; i++) { atomicAdd(p.phase_acc + i, pt_[i]); atomicAdd(p.phase_acc + 16 + i, (unsigned long long)pc_[i]); }
 #endif
 #undef RT_PT
-#undef RT_BEGIN_TRACE
 #undef RT_POP
 #undef RT_EMIT
 #undef RT_EMIT_DARK

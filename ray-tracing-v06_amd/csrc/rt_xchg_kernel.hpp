@@ -139,7 +139,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_xchg(XchgPar
     const uint32_t tid = threadIdx.x;
     const uint32_t lane = tid & 63u;
     const uint32_t wave = tid >> 6;
-    constexpr uint32_t K_LEAF = RT_REF_LEAF, K_IRR = RT_REF_IRR, K_SHADE = 0xffffu, K_EMPTY = 0x20000u;
+    using K = LaneStatus<false>;   // K::NEED: a tracer lane without a ray
     using ref_t = uint16_t;
 
     // ---- LDS layout: scene image | per-lane stacks of the tracer waves | per shard: control words, sequence words | ring data ----
@@ -190,13 +190,13 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_xchg(XchgPar
         // tracer wave
         // =====================================================================================================================
         ref_t* const stack = reinterpret_cast<ref_t*>(lds + xp.scene_vec4) + wave * 64u * p.scene.stack_cap + lane;
-        *stack = (ref_t)K_SHADE;   // entry 0: popping an empty stack IS "trace finished"
+        *stack = (ref_t)K::SHADE;   // entry 0: popping an empty stack IS "trace finished"
         Ray ray;
         ray.o = mk3(0.0f); ray.d = mk3(0.0f); ray.time = 0.0f;
         f3 inv_d = mk3(0.0f), inv_lo = mk3(0.0f);
         float ray_a = 0.0f, rec_t = RT_MISS_DIST;
         int32_t rec_code = -1;
-        uint32_t cur = K_EMPTY;
+        uint32_t cur = K::NEED;
         ref_t* sp = stack + 64;
         uint32_t kx = 0, ky = 0, kz = 0;
         bool regular = true, irr_pending = false;
@@ -211,7 +211,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_xchg(XchgPar
 
         for (;;) {
             // ---------------- phase 1: inner-node steps (BVH.cu:76-97), as render_kernel_stream's FAST_BVH hot loop ----------------
-            bool at_inner = cur < K_IRR;
+            bool at_inner = cur < K::IRR;
             if (__ballot(at_inner) != 0ull) {
                 uint32_t n_inner_lanes;
                 do {
@@ -239,24 +239,24 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_xchg(XchgPar
                         *xp.error_flag = 6u;
                         uint32_t* o = xp.error_flag + 16u + (blockIdx.x * (blockDim.x / 64u) + wave) * RT_XCHG_DEBUG_WORDS;
                         o[0] = 6u; o[1] = cur; o[2] = (uint32_t)(sp - stack) / 64u; o[3] = __float_as_uint(ray.d.x); o[4] = __float_as_uint(c_att.w); o[5] = depth; o[6] = lane; o[7] = __float_as_uint(ray.o.x);
-                        cur = K_SHADE;
+                        cur = K::SHADE;
                         sp = stack + 64;
                     }
 #endif
-                    at_inner = cur < K_IRR;
+                    at_inner = cur < K::IRR;
                     n_inner_lanes = (uint32_t)__popcll(__ballot(at_inner));
                 } while (n_inner_lanes >= p.inner_keep);
             }
             XC_PT(0);
             if (irr_pending) {   // wave-uniform, rare: rays outside the fast-division class (marked references), verbatim box tests
                 for (;;) {
-                    const bool at_irr = (cur & (K_LEAF | K_IRR)) == K_IRR;
+                    const bool at_irr = (cur & (K::LEAF | K::IRR)) == K::IRR;
                     if (__ballot(at_irr) == 0ull) break;
                     if (at_irr) {
-                        const WideNodeData nd = fetch_wide_node<false>(nodes, lds, 0u, cur & (K_IRR - 1u), 0u, 0u, 0u);
+                        const WideNodeData nd = fetch_wide_node<false>(nodes, lds, 0u, cur & (K::IRR - 1u), 0u, 0u, 0u);
                         uint32_t left_idx = nd.left, right_idx = nd.right;
-                        if (left_idx < K_LEAF) left_idx |= K_IRR;
-                        if (right_idx < K_LEAF) right_idx |= K_IRR;
+                        if (left_idx < K::LEAF) left_idx |= K::IRR;
+                        if (right_idx < K::LEAF) right_idx |= K::IRR;
                         float left_dist = RT_MISS_DIST, right_dist = RT_MISS_DIST;
                         const bool hl = aabb_intersects(mk3(nd.lnx, nd.lny, nd.lnz), mk3(nd.lfx, nd.lfy, nd.lfz), ray, rec_t, left_dist);
                         const bool hr = aabb_intersects(mk3(nd.rnx, nd.rny, nd.rnz), mk3(nd.rfx, nd.rfy, nd.rfz), ray, rec_t, right_dist);
@@ -269,20 +269,20 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_xchg(XchgPar
                         if (!(hl || hr)) { sp -= 64; cur = *sp; }
                     }
                 }
-                irr_pending = __ballot(!regular && (cur < K_SHADE)) != 0ull;
+                irr_pending = __ballot(!regular && (cur < K::SHADE)) != 0ull;
             }
             XC_PT(1);
             // ---------------- phase 2: leaves (BVH.cu:69-73 -> SphereHittable.cu:56-66 / :91-102) ----------------------------------
             {
-                const bool at_leaf = (cur - K_LEAF) < (K_SHADE - K_LEAF);
+                const bool at_leaf = (cur - K::LEAF) < (K::SHADE - K::LEAF);
                 const uint64_t m_leaf = __ballot(at_leaf);
-                if (m_leaf != 0ull && ((uint32_t)__popcll(m_leaf) >= p.leaf_min || __ballot(cur < K_LEAF) == 0ull)) {
+                if (m_leaf != 0ull && ((uint32_t)__popcll(m_leaf) >= p.leaf_min || __ballot(cur < K::LEAF) == 0ull)) {
 #ifdef RT_PHASE_TIMERS
                     pt_[6] += (unsigned long long)__popcll(m_leaf);
                     pc_[6]++;
 #endif
                     if (at_leaf) {
-                        const uint32_t code = cur & (K_LEAF - 1u);   // prim * 2 + is_moving
+                        const uint32_t code = cur & (K::LEAF - 1u);   // prim * 2 + is_moving
                         const uint32_t prim = code >> 1;
                         const float4 sph = spheres[prim];
                         f3 center = mk3(sph.x, sph.y, sph.z);
@@ -302,8 +302,8 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_xchg(XchgPar
             }
             XC_PT(2);
             // ---------------- phase 3: exchange finished traces for fresh rays -------------------------------------------------------
-            const uint64_t m_trav = __ballot(cur < K_SHADE);
-            const uint64_t m_fin = __ballot(cur == K_SHADE);
+            const uint64_t m_trav = __ballot(cur < K::SHADE);
+            const uint64_t m_fin = __ballot(cur == K::SHADE);
             const uint32_t n_fin = (uint32_t)__popcll(m_fin);
             const uint32_t n_idle = 64u - (uint32_t)__popcll(m_trav);
             if (n_idle < xp.swap_min && m_trav != 0ull) continue;
@@ -312,7 +312,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_xchg(XchgPar
             pt_[7] += n_fin; pc_[7]++;   // finished lanes per exchange
 #endif
             // ONE reservation for both directions: g_push finished traces -> SHADE ring, g_pop fresh rays <- TRACE ring
-            const uint64_t m_emp = __ballot(cur == K_EMPTY);
+            const uint64_t m_emp = __ballot(cur == K::NEED);
             const uint32_t n_emp = (uint32_t)__popcll(m_emp);
             const uint32_t rank_fin = lane_rank(m_fin);
             uint32_t n_new = 0;
@@ -326,8 +326,8 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_xchg(XchgPar
                     const uint32_t g_pop = min(n_emp + g_push, (tq_t - tq_h) & 0xffffu);   // the lanes that push are free for a new ray
                     do_push = false; do_pop = false;
                     if ((g_push | g_pop) == 0u) break;
-                    do_push = cur == K_SHADE && rank_fin < g_push;
-                    const bool free_after = cur == K_EMPTY || do_push;
+                    do_push = cur == K::SHADE && rank_fin < g_push;
+                    const bool free_after = cur == K::NEED || do_push;
                     const uint32_t rank_free = lane_rank(__ballot(free_after));
                     do_pop = free_after && rank_free < g_pop;
                     ppos = sq_t + rank_fin; tpos = tq_h + rank_free;
@@ -362,7 +362,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_xchg(XchgPar
             XC_ORDER_RELEASE();   // every write has landed and every read has returned
             if (do_push) {
                 xc_st(sq_seq + (ppos & sq_mask), ppos + 1u);
-                cur = K_EMPTY;
+                cur = K::NEED;
             }
             if (do_pop) {
                 xc_st(tq_seq + (tpos & tq_mask), tpos + xp.tq_cap);
@@ -383,14 +383,14 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_xchg(XchgPar
                 guard_steps = 0;
 #endif
             }
-            if (n_new != 0u && __ballot(!regular && cur < K_SHADE) != 0ull) irr_pending = true;
+            if (n_new != 0u && __ballot(!regular && cur < K::SHADE) != 0ull) irr_pending = true;
             XC_PT(3);
-            if (__ballot(cur < K_SHADE) == 0ull && n_new == 0u) {   // nothing to trace and nothing came: the end, or the shaders are behind
+            if (__ballot(cur < K::SHADE) == 0ull && n_new == 0u) {   // nothing to trace and nothing came: the end, or the shaders are behind
                 if (xc_ld(ctrl + XC_DONE) != 0u) break;
                 if (xc_ld(ctrl + XC_ERR) != 0u || ++idle_rounds > RT_XCHG_IDLE_LIMIT) {
                     xc_st(ctrl + XC_ERR, 3u);
                     *xp.error_flag = 3u;
-                    xc_dump(xp.error_flag, 3u, wave, lane, ctrl, (uint32_t)__popcll(__ballot(cur == K_SHADE)), (uint32_t)__popcll(__ballot(cur == K_EMPTY)), idle_rounds, 0u);
+                    xc_dump(xp.error_flag, 3u, wave, lane, ctrl, (uint32_t)__popcll(__ballot(cur == K::SHADE)), (uint32_t)__popcll(__ballot(cur == K::NEED)), idle_rounds, 0u);
                     break;
                 }
                 __builtin_amdgcn_s_sleep(8);
@@ -619,10 +619,10 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_xchg(XchgPar
                 float d_root;
                 const bool hit_root = regular ? aabb_intersects_regular(root_min, root_max, ray, inv_d, RT_MISS_DIST, d_root)
                                               : aabb_intersects(root_min, root_max, ray, RT_MISS_DIST, d_root);
-                uint32_t cur0 = K_SHADE;
+                uint32_t cur0 = K::SHADE;
                 if (hit_root) {
                     cur0 = p.scene.root_ref;
-                    if (!regular && cur0 < K_LEAF) cur0 |= K_IRR;
+                    if (!regular && cur0 < K::LEAF) cur0 |= K::IRR;
                 }
                 // direction signs select the (near, far) plane pair by address in the tracer (regular rays only)
                 const uint32_t sx = regular ? (__float_as_uint(ray.d.x) >> 31) : 0u, sy = regular ? (__float_as_uint(ray.d.y) >> 31) : 0u,
