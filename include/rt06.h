@@ -291,13 +291,22 @@ typedef struct rt_render_config {
                                      (rt_renderer_kernel_info).                                                                */
 } rt_render_config;
 
-/* Renderer::MakeRenderer (Renderer.cu:31-67).  Copies the flat world and the
- * camera; allocates the device framebuffer.  No RNG-state array is needed
- * (counter-based RNG), so init_random_states (Renderer.cu:22-29) has no twin. */
+/* Renderer::MakeRenderer (Renderer.cu:31-67).  Copies the flat world; allocates the
+ * device framebuffer.  `cam` is the camera of the first launch: the reference keeps
+ * a POINTER to the caller's camera and reads it at every Render() (Renderer.cu:117),
+ * which a C caller restates with rt_renderer_set_camera before a render (the C++
+ * mirror does it inside Render()).  No RNG-state array is needed (counter-based
+ * RNG), so init_random_states (Renderer.cu:22-29) has no twin.                  */
 int rt_renderer_create(const rt_render_config* cfg, const rt_camera* cam,
                        const rt_world_flat* world, rt_renderer** out);
 void rt_renderer_destroy(rt_renderer* r);
 
+/* `params.cam = *m.cam;` of Renderer::Render (Renderer.cu:117): the camera of every launch from now on (render, render_async,
+ * refine*).  Validated as in rt_renderer_create (NULL, type > RT_CAM_MOTION: RT_ERR_INVALID, renderer unchanged).  The camera travels
+ * BY VALUE in the kernel arguments, so a launch that is already enqueued keeps the camera it was given.  A camera whose bytes differ
+ * from the current one discards the refinement state (samples accumulated -> 0); the same bytes keep it.  The world, the per-pass
+ * buffers and the streams are untouched: this is what an animation loop calls instead of destroy + create.                          */
+int rt_renderer_set_camera(rt_renderer* r, const rt_camera* cam);
 /* Renderer::Render (Renderer.cu:111-137): blocking; launches on the
  * renderer's own stream and waits.                                          */
 int rt_renderer_render(rt_renderer* r);
@@ -334,6 +343,35 @@ int rt_renderer_shard_floats(const rt_renderer* r, size_t* out);
 int rt_renderer_assemble(rt_renderer* r, const float* d_gathered, float* d_image, void* hip_stream);
 
 /* ------------------------------------------------------------------ */
+/* Progressive refinement (not in the reference's path tracer; what its  */
+/* viewer, openglApp.cpp, would need of one): a frame that can be shown  */
+/* after a few samples and improved while the camera rests.            */
+/* ------------------------------------------------------------------ */
+/* Adds samples [done, done + n_samples) of every pixel to the renderer's accumulation and writes the frame for done + n_samples
+ * samples.  After ANY sequence of calls the framebuffer has the bits of ONE render at samples_per_pixel = done: the RNG stream is a
+ * function of (seed, pixel, sample index) and the per-pixel sums continue in sample order.  Blocking / on a caller's stream with an
+ * optional shard buffer, like render / render_async (calls on different streams are the caller's to order).  A step larger than one
+ * pass (rt_renderer_refine_info out[1]) is cut into passes as Render() cuts a frame; cfg.samples_per_pixel sizes those passes and is
+ * Render()'s count only — refinement may go past it, up to 2^31 samples.  The accumulation (16 B per local pixel, allocated at the
+ * first call) is separate from Render()'s buffers: a Render() between two steps disturbs neither.  RT_ERR_INVALID: n_samples == 0,
+ * done + n_samples > 2^31, or a renderer on the baseline kernel (variant 1), which has no sample buffer.  The state is discarded by
+ * rt_renderer_refine_reset and by rt_renderer_set_camera with a different camera.                                                    */
+int rt_renderer_refine(rt_renderer* r, uint32_t n_samples);
+int rt_renderer_refine_async(rt_renderer* r, void* hip_stream, float* d_out, uint32_t n_samples);
+int rt_renderer_refine_reset(rt_renderer* r);
+/* out[0] = samples accumulated, out[1] = samples per pixel one internal pass can take, out[2] = bytes held for refinement */
+int rt_renderer_refine_info(rt_renderer* r, uint64_t out[3]);
+/* per-pixel accumulation, row-major like download: (sum R, sum G, sum B, sum Y^2), UNscaled; world_size == 1 only.  The sums are
+ * fp32, in sample order; Y = (0.2126f*R + 0.7152f*G) + 0.0722f*B of each SAMPLE, every operation rounded on its own.              */
+int rt_renderer_refine_download_sums(rt_renderer* r, float* host, size_t n_floats);
+/* relative RMS standard error of the frame's mean luminance after the samples so far (needs >= 2): per pixel, fp32, every operation
+ * rounded on its own, n = (float)done:  m = ((0.2126f*Sr + 0.7152f*Sg) + 0.0722f*Sb) / n,  v = max(0, Q / n - m*m) / (float)(done - 1);
+ * the figure is sqrt(mean(v)) / mean(m), both means in fp64 over the pixels of the image (a shard: its own pixels, padding left out),
+ * reduced in a fixed order, so it repeats bit for bit.  A frame whose mean luminance is 0 gives +inf.  A pixel whose m or v is not
+ * finite (the reference's arithmetic yields a NaN sample about once per 6e8) is left out of both means.                             */
+int rt_renderer_refine_noise(rt_renderer* r, double* out);
+
+/* ------------------------------------------------------------------ */
 /* Multi-GPU renderer — the same three entry points (Renderer.h:38-46)  */
 /* over the N GPUs of one node, driven by ONE host process.            */
 /* ------------------------------------------------------------------ */
@@ -350,6 +388,11 @@ int rt_multi_renderer_create(const rt_render_config* cfg, const rt_camera* cam, 
 void rt_multi_renderer_destroy(rt_multi_renderer* m);
 /* Renderer::Render: blocking; renders all shards side by side, gathers, assembles.                                      */
 int rt_multi_renderer_render(rt_multi_renderer* m);
+/* rt_renderer_set_camera on every rank (validated first: an invalid camera changes no rank).                            */
+int rt_multi_renderer_set_camera(rt_multi_renderer* m, const rt_camera* cam);
+/* rt_renderer_refine on every rank, then the usual gather + assembly: the frame of rt_multi_renderer_download is the
+ * refined one.  No noise figure here (each rank's rt_renderer_refine_noise covers its own pixels only).                 */
+int rt_multi_renderer_refine(rt_multi_renderer* m, uint32_t n_samples);
 /* Renderer::DownloadRenderbuffer: width*height*4 floats from devices[0].                                                */
 int rt_multi_renderer_download(rt_multi_renderer* m, float* host_rgba, size_t n_floats);
 /* ms of the last render: out[0] host wall-clock of Render(), out[1] slowest rank's kernels (HIP events),

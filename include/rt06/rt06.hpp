@@ -455,10 +455,17 @@ class Renderer {
         uint32_t samples_per_pixel{}, max_depth{};
         rt_renderer* r{};          // one GPU
         rt_multi_renderer* mr{};   // n_gpus > 1: tile shards on every GPU, one RCCL gather at frame end
+        const rt_camera* cam{};    // the CALLER's camera (Renderer.h: `const MotionBlurCamera* cam`), read at every Render() / Refine()
     } m;
+    // `params.cam = *m.cam;` (Renderer.cu:117): the library compares the bytes, so an unmoved camera keeps a refinement going
+    void push_camera(const char* what) {
+        if (m.mr) rt06::check(rt_multi_renderer_set_camera(m.mr, m.cam), what);
+        else rt06::check(rt_renderer_set_camera(m.r, m.cam), what);
+    }
     explicit Renderer(M mm) : m(mm) {}
     Renderer(const Renderer&) = delete;
     Renderer& operator=(const Renderer&) = delete;
+    void single(const char* what) const { if (!m.r) throw std::runtime_error(std::string(what) + ": single-GPU renderers only"); }
     void destroy() { rt_renderer_destroy(m.r); rt_multi_renderer_destroy(m.mr); m.r = nullptr; m.mr = nullptr; }
 
     static void flatten(const Hittable* world, rt06::SceneBuilder& tmp, rt_world_flat& w) {
@@ -480,7 +487,7 @@ class Renderer {
         }
         rt06::check(rt_scene_get_flat(tmp.get(), &w), "rt_scene_get_flat");
     }
-    static Renderer make(uint32_t w_, uint32_t h_, uint32_t spp, uint32_t depth, const rt_camera& cam, const Hittable* world, uint64_t seed, int device,
+    static Renderer make(uint32_t w_, uint32_t h_, uint32_t spp, uint32_t depth, const rt_camera* cam, const Hittable* world, uint64_t seed, int device,
                          uint32_t n_gpus, uint32_t variant) {
         if (!world) throw std::runtime_error("Renderer::MakeRenderer: null world");
         rt06::SceneBuilder tmp;
@@ -491,8 +498,9 @@ class Renderer {
         cfg.seed = seed; cfg.device = device; cfg.rank = 0; cfg.world_size = 1; cfg.variant = variant;
         M mm;
         mm.render_width = w_; mm.render_height = h_; mm.samples_per_pixel = spp; mm.max_depth = depth;
-        if (n_gpus > 1) rt06::check(rt_multi_renderer_create(&cfg, &cam, &wf, n_gpus, nullptr, &mm.mr), "Renderer::MakeRenderer");
-        else rt06::check(rt_renderer_create(&cfg, &cam, &wf, &mm.r), "Renderer::MakeRenderer");
+        mm.cam = cam;
+        if (n_gpus > 1) rt06::check(rt_multi_renderer_create(&cfg, cam, &wf, n_gpus, nullptr, &mm.mr), "Renderer::MakeRenderer");
+        else rt06::check(rt_renderer_create(&cfg, cam, &wf, &mm.r), "Renderer::MakeRenderer");
         return Renderer(mm);
     }
 
@@ -503,7 +511,9 @@ public:
         if (this != &o) { destroy(); m = o.m; o.m.r = nullptr; o.m.mr = nullptr; }
         return *this;
     }
-    // The reference takes `const MotionBlurCamera*`; the other two camera types are accepted as well.
+    // The reference takes `const MotionBlurCamera*`; the other two camera types are accepted as well.  As there, the renderer KEEPS the
+    // pointer and reads the camera at every Render() (Renderer.cu:117): the camera object must outlive the renderer, and moving it between
+    // two Render() calls moves the frame.
     // seed: the reference hard-codes 1984 (Renderer.cu:51).  n_gpus > 1: the frame is tile-sharded over GPUs 0 .. n_gpus-1 of the
     // node and gathered on GPU 0 with one RCCL exchange (rt_multi_renderer_*); the image is the same for every n_gpus.
     // variant: rt_render_config::variant — 0 (default: the fastest kernel that renders the reference's bits); kToleranceMode opts a sphere world of the
@@ -512,21 +522,43 @@ public:
     static Renderer MakeRenderer(uint32_t render_width, uint32_t render_height, uint32_t samples_per_pixel, uint32_t max_depth,
                                  const MotionBlurCamera* cam, const Hittable* d_world_ptr, uint64_t seed = 1984, int device = 0, uint32_t n_gpus = 1,
                                  uint32_t variant = 0) {
-        return make(render_width, render_height, samples_per_pixel, max_depth, cam->cam, d_world_ptr, seed, device, n_gpus, variant);
+        return make(render_width, render_height, samples_per_pixel, max_depth, &cam->cam, d_world_ptr, seed, device, n_gpus, variant);
     }
     static Renderer MakeRenderer(uint32_t render_width, uint32_t render_height, uint32_t samples_per_pixel, uint32_t max_depth,
                                  const DefocusBlurCamera* cam, const Hittable* d_world_ptr, uint64_t seed = 1984, int device = 0, uint32_t n_gpus = 1,
                                  uint32_t variant = 0) {
-        return make(render_width, render_height, samples_per_pixel, max_depth, cam->cam, d_world_ptr, seed, device, n_gpus, variant);
+        return make(render_width, render_height, samples_per_pixel, max_depth, &cam->cam, d_world_ptr, seed, device, n_gpus, variant);
     }
     static Renderer MakeRenderer(uint32_t render_width, uint32_t render_height, uint32_t samples_per_pixel, uint32_t max_depth,
                                  const PinholeCamera* cam, const Hittable* d_world_ptr, uint64_t seed = 1984, int device = 0, uint32_t n_gpus = 1,
                                  uint32_t variant = 0) {
-        return make(render_width, render_height, samples_per_pixel, max_depth, cam->cam, d_world_ptr, seed, device, n_gpus, variant);
+        return make(render_width, render_height, samples_per_pixel, max_depth, &cam->cam, d_world_ptr, seed, device, n_gpus, variant);
     }
     void Render() {
+        push_camera("Renderer::Render");
         if (m.mr) rt06::check(rt_multi_renderer_render(m.mr), "Renderer::Render");
         else rt06::check(rt_renderer_render(m.r), "Renderer::Render");
+    }
+    // Progressive refinement (extension; rt_renderer_refine): n more samples per pixel on top of those accumulated; the framebuffer then has
+    // the bits of ONE render at SamplesAccumulated().  The camera is read first, as in Render(): a camera that moved restarts the accumulation.
+    void Refine(uint32_t n) {
+        push_camera("Renderer::Refine");
+        if (m.mr) rt06::check(rt_multi_renderer_refine(m.mr, n), "Renderer::Refine");
+        else rt06::check(rt_renderer_refine(m.r, n), "Renderer::Refine");
+    }
+    // the three below: one GPU only (the multi-GPU renderer has no noise figure)
+    void ResetRefinement() { single("Renderer::ResetRefinement"); rt06::check(rt_renderer_refine_reset(m.r), "Renderer::ResetRefinement"); }
+    uint64_t SamplesAccumulated() {
+        single("Renderer::SamplesAccumulated");
+        uint64_t info[3];
+        rt06::check(rt_renderer_refine_info(m.r, info), "Renderer::SamplesAccumulated");
+        return info[0];
+    }
+    double Noise() {   // relative RMS standard error of the frame's mean luminance (rt_renderer_refine_noise); needs 2 samples
+        single("Renderer::Noise");
+        double v = 0.0;
+        rt06::check(rt_renderer_refine_noise(m.r, &v), "Renderer::Noise");
+        return v;
     }
     float LastKernelMs() {
         float ms = 0;

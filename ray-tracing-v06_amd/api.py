@@ -264,6 +264,39 @@ class Renderer:
     def render_async(self, stream=None, d_out=None):
         check(lib().rt_renderer_render_async(self.h, C.c_void_p(stream or 0), C.c_void_p(d_out or 0)))
 
+    def set_camera(self, cam):
+        """`params.cam = *m.cam` (Renderer.cu:117): the camera of every launch from now on; a different camera discards the refinement state."""
+        check(lib().rt_renderer_set_camera(self.h, C.byref(cam) if cam is not None else None))
+
+    def refine(self, n_samples):
+        """Add n_samples more samples per pixel; the framebuffer then has the bits of ONE render at the accumulated count. Returns that count."""
+        check(lib().rt_renderer_refine(self.h, n_samples))
+        return self.refine_info()["samples"]
+
+    def refine_async(self, n_samples, stream=None, d_out=None):
+        check(lib().rt_renderer_refine_async(self.h, C.c_void_p(stream or 0), C.c_void_p(d_out or 0), n_samples))
+
+    def refine_reset(self):
+        check(lib().rt_renderer_refine_reset(self.h))
+
+    def refine_info(self):
+        """{'samples', 'pass_spp', 'bytes'}: samples accumulated, samples per pixel of one internal pass, bytes held for refinement."""
+        out = (C.c_uint64 * 3)()
+        check(lib().rt_renderer_refine_info(self.h, out))
+        return {"samples": out[0], "pass_spp": out[1], "bytes": out[2]}
+
+    def refine_sums(self):
+        """(H, W, 4) float32: per pixel (sum R, sum G, sum B, sum Y^2) of the samples so far, unscaled (world_size == 1)."""
+        out = np.zeros((self.cfg.height, self.cfg.width, 4), dtype=np.float32)
+        check(lib().rt_renderer_refine_download_sums(self.h, out, out.size))
+        return out
+
+    def noise(self):
+        """Relative RMS standard error of the frame's mean luminance after the samples so far (rt_renderer_refine_noise)."""
+        out = C.c_double()
+        check(lib().rt_renderer_refine_noise(self.h, C.byref(out)))
+        return out.value
+
     def last_kernel_ms(self):
         ms = C.c_float()
         check(lib().rt_renderer_last_kernel_ms(self.h, C.byref(ms)))
@@ -328,6 +361,14 @@ class MultiRenderer:
 
     def Render(self):
         check(lib().rt_multi_renderer_render(self.h))
+
+    def set_camera(self, cam):
+        """rt_renderer_set_camera on every rank."""
+        check(lib().rt_multi_renderer_set_camera(self.h, C.byref(cam) if cam is not None else None))
+
+    def refine(self, n_samples):
+        """rt_renderer_refine on every rank, then the usual gather + assembly."""
+        check(lib().rt_multi_renderer_refine(self.h, n_samples))
 
     def DownloadRenderbuffer(self):
         out = np.zeros((self.cfg.height, self.cfg.width, 4), dtype=np.float32)

@@ -73,6 +73,8 @@ SYMBOLS = [
     "rt_multi_renderer_download", "rt_multi_renderer_times", "rt_multi_renderer_gpus", "rt_shard_layout", "rt_shard_pixel_map", "rt_device_info", "rt_scene_set_traversal", "rt_probe_aabb", "rt_probe_sphere", "rt_probe_trace", "rt_probe_scatter",
     "rt_probe_camera", "rt_probe_scatter_tape", "rt_probe_camera_tape", "rt_probe_sphere_hit", "rt_probe_radiance", "rt_probe_sphere_index", "rt_probe_rng", "rt_probe_math", "rt_probe_glm", "rt_probe_aabb_misc", "rt_probe_aabb_regular", "rt_probe_boxpair_filtered", "rt_probe_boxpair_certified",
     "rt_selftest_fastdiv", "rt_selftest_fastdiv4", "rt_selftest_fastrcp", "rt_device_count", "rt_version", "rt_source_hash", "rt_renderer_pass_info",
+    "rt_renderer_set_camera", "rt_multi_renderer_set_camera", "rt_renderer_refine", "rt_renderer_refine_async", "rt_renderer_refine_reset",
+    "rt_renderer_refine_info", "rt_renderer_refine_download_sums", "rt_renderer_refine_noise", "rt_multi_renderer_refine",
 ]
 
 _lib = None
@@ -176,6 +178,15 @@ def lib():
     L.rt_renderer_last_kernel_ms.argtypes = [C.c_void_p, P(C.c_float)]
     L.rt_renderer_kernel_info.argtypes = [C.c_void_p, P(C.c_uint32 * 4)]
     L.rt_renderer_kernel_times.argtypes = [C.c_void_p, C.c_uint32, C.c_float * 3]
+    L.rt_renderer_set_camera.argtypes = [C.c_void_p, P(Camera)]
+    L.rt_multi_renderer_set_camera.argtypes = [C.c_void_p, P(Camera)]
+    L.rt_renderer_refine.argtypes = [C.c_void_p, C.c_uint32]
+    L.rt_renderer_refine_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+    L.rt_renderer_refine_reset.argtypes = [C.c_void_p]
+    L.rt_renderer_refine_info.argtypes = [C.c_void_p, C.c_uint64 * 3]
+    L.rt_renderer_refine_download_sums.argtypes = [C.c_void_p, f32p, C.c_size_t]
+    L.rt_renderer_refine_noise.argtypes = [C.c_void_p, P(C.c_double)]
+    L.rt_multi_renderer_refine.argtypes = [C.c_void_p, C.c_uint32]
     L.rt_multi_renderer_create.argtypes = [P(RenderConfig), P(Camera), P(WorldFlat), C.c_uint32, C.c_void_p, P(C.c_void_p)]
     L.rt_multi_renderer_destroy.argtypes = [C.c_void_p]
     L.rt_multi_renderer_destroy.restype = None

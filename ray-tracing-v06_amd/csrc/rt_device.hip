@@ -82,8 +82,13 @@ struct rt_renderer {
     // Created at first use (a 10 000-spp render of a 4K frame has > 100 passes).
     static constexpr uint32_t RT_TIMES_RING = 32;
     std::vector<hipEvent_t> kev[RT_TIMES_RING];
+    uint32_t kev_passes[RT_TIMES_RING] = {};   // passes of the call each ring slot holds: a Render() has n_passes, a refine step a count of its own
     uint64_t n_renders = 0;
     uint32_t n_passes = 1;
+    // progressive refinement (rt_renderer_refine*): samples [0, refine_done) of every pixel are in `accum` = (sum R, sum G, sum B, sum Y^2) per local
+    // pixel, a buffer of its own (allocated at the first refine call) so that a Render() between two steps disturbs neither
+    DevBuf accum, noise_partials, noise_out;
+    uint32_t refine_done = 0;
     static constexpr uint32_t SAMPLE_BYTES = RT_SAMPLE_BYTES, PRIMARY_BYTES = 48;   // HBM per sample index of a pass: radiance (float4) + primary ray record
 
     // Pick the kernel variant and size the per-pass sample buffer.
@@ -281,7 +286,9 @@ struct rt_renderer {
         return reinterpret_cast<const void*>(&render_kernel_stream<false, false, 768>);
     }
 
-    int launch(hipStream_t st, float* out) {
+    // One call's launches: samples [first_s, first_s + n_s) of every pixel, cut into passes of at most pass_spp.  Render() is (0, samples_per_pixel)
+    // resolved through `running`; a refine step is (refine_done, n) resolved into `accum` (refine = true), which carries the sums from call to call.
+    int launch(hipStream_t st, float* out, uint32_t first_s, uint32_t n_s, bool refine) {
         if (variant == 1) {
             RenderParams p;
             p.width = cfg.width; p.height = cfg.height;
@@ -296,7 +303,8 @@ struct rt_renderer {
         }
         StreamParams p;
         p.width = cfg.width; p.height = cfg.height;
-        p.spp = cfg.samples_per_pixel; p.max_depth = cfg.max_depth;
+        const uint32_t end_s = first_s + n_s, call_passes = (n_s + pass_spp - 1u) / pass_spp;
+        p.spp = refine ? end_s : cfg.samples_per_pixel; p.max_depth = cfg.max_depth;
         p.seed = cfg.seed;
         p.cam = cam;
         p.tm = tm;
@@ -309,15 +317,16 @@ struct rt_renderer {
         uint32_t n_local_pixels = tm.n_local_tiles * RT_TILE * RT_TILE;
         uint32_t grid = n_cus * stream_blocks_per_cu;
         std::vector<hipEvent_t>& ring = kev[n_renders % RT_TIMES_RING];
-        while (ring.size() < (size_t)n_passes * 4u) {
+        kev_passes[n_renders % RT_TIMES_RING] = call_passes;
+        while (ring.size() < (size_t)call_passes * 4u) {
             hipEvent_t e = nullptr;
             HIP_TRY(hipEventCreate(&e));
             ring.push_back(e);
         }
         uint32_t pass = 0;
-        for (uint32_t first = 0; first < cfg.samples_per_pixel; first += pass_spp, pass++) {
+        for (uint32_t first = first_s; first < end_s; first += pass_spp, pass++) {
             p.pass_first_s = first;
-            p.pass_spp = std::min(pass_spp, cfg.samples_per_pixel - first);
+            p.pass_spp = std::min(pass_spp, end_s - first);
             p.total = n_local_pixels * p.pass_spp;
             // work-queue granularity: ~32 fetches per wave keep the tail short when a shard is small (multi-GPU)
             uint32_t n_waves = grid * (stream_block / 64u);
@@ -395,8 +404,9 @@ struct rt_renderer {
                     fprintf(stderr, "[phase] %-16s %6.2f %% of wave time, %12llu visits, %8.1f cycles per visit\n", names[i], 100.0 * h[i] / (double)tot, h[16 + i], h[16 + i] ? (double)h[i] / h[16 + i] : 0.0);
             }
 #endif
-            uint32_t last = first + p.pass_spp >= cfg.samples_per_pixel ? 1u : 0u;
-            resolve_kernel<<<(n_local_pixels + 255) / 256, 256, 0, st>>>(p, running.as<float4>(), out, last);
+            uint32_t last = first + p.pass_spp >= end_s ? 1u : 0u;
+            if (refine) refine_resolve_kernel<<<(n_local_pixels + 255) / 256, 256, 0, st>>>(p, accum.as<float4>(), out, last, end_s);
+            else resolve_kernel<<<(n_local_pixels + 255) / 256, 256, 0, st>>>(p, running.as<float4>(), out, last);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipEventRecord(ke[3], st));
         }
@@ -422,7 +432,7 @@ extern "C" int rt_renderer_create(const rt_render_config* cfg, const rt_camera* 
     if (rc != RT_OK) return rc;
     rt_renderer* r = new rt_renderer();
     r->cfg = *cfg;
-    r->cam = *cam;
+    r->cam = *cam;   // the camera of the first launch; rt_renderer_set_camera replaces it (Renderer.cu:117 reads the caller's camera at every Render())
     rc = r->scene.upload(world);
     if (rc != RT_OK) { delete r; return rc; }
     r->tm = make_tile_map(cfg->width, cfg->height, cfg->rank, cfg->world_size);
@@ -450,15 +460,127 @@ extern "C" void rt_renderer_destroy(rt_renderer* r) {
     delete r;
 }
 
-extern "C" int rt_renderer_render_async(rt_renderer* r, void* hip_stream, float* d_out) {
-    if (!r) return rt_fail(RT_ERR_INVALID, "rt_renderer_render_async: null renderer");
+// one call's launches between the renderer's two timing events, on the caller's stream
+static int enqueue_call(rt_renderer* r, void* hip_stream, float* d_out, uint32_t first_s, uint32_t n_s, bool refine) {
     HIP_TRY(hipSetDevice(r->cfg.device));
     hipStream_t st = (hipStream_t)hip_stream;  // NULL is the HIP null stream, as for any HIP launch
     HIP_TRY(hipEventRecord(r->ev0, st));
-    int rc = r->launch(st, d_out ? d_out : r->fb.as<float>());
+    int rc = r->launch(st, d_out ? d_out : r->fb.as<float>(), first_s, n_s, refine);
     if (rc != RT_OK) return rc;
     HIP_TRY(hipEventRecord(r->ev1, st));
     r->timed = true;
+    return RT_OK;
+}
+
+extern "C" int rt_renderer_render_async(rt_renderer* r, void* hip_stream, float* d_out) {
+    if (!r) return rt_fail(RT_ERR_INVALID, "rt_renderer_render_async: null renderer");
+    return enqueue_call(r, hip_stream, d_out, 0u, r->cfg.samples_per_pixel, false);
+}
+
+static int wait_and_check(rt_renderer* r) {
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    int rc = check_xchg_error(r->xchg_error);
+    if (rc != RT_OK) return rc;
+    return check_traversal_overflow(r->scene);
+}
+
+extern "C" int rt_renderer_set_camera(rt_renderer* r, const rt_camera* cam) {
+    if (!r || !cam) return rt_fail(RT_ERR_INVALID, "rt_renderer_set_camera: null argument");
+    if (cam->type > RT_CAM_MOTION) return rt_fail(RT_ERR_INVALID, "rt_renderer_set_camera: unknown camera type %u", cam->type);
+    if (std::memcmp(&r->cam, cam, sizeof(rt_camera)) == 0) return RT_OK;   // the same bytes: nothing moves, the refinement goes on
+    r->cam = *cam;          // travels by value in the kernel arguments of the NEXT launch; launches already enqueued keep theirs
+    r->refine_done = 0;     // samples accumulated under another camera belong to another frame
+    return RT_OK;
+}
+
+extern "C" int rt_renderer_refine_async(rt_renderer* r, void* hip_stream, float* d_out, uint32_t n_samples) {
+    if (!r) return rt_fail(RT_ERR_INVALID, "rt_renderer_refine_async: null renderer");
+    if (r->variant < 2)
+        return rt_fail(RT_ERR_INVALID, "rt_renderer_refine: the baseline kernel (variant 1) keeps no per-sample buffer to accumulate from; refinement needs a streaming variant (0, or 2 to 6)");
+    if (n_samples == 0) return rt_fail(RT_ERR_INVALID, "rt_renderer_refine: n_samples must be > 0");
+    if ((uint64_t)r->refine_done + n_samples > 0x80000000ull)
+        return rt_fail(RT_ERR_INVALID, "rt_renderer_refine: %u + %u samples per pixel pass 2^31", r->refine_done, n_samples);
+    HIP_TRY(hipSetDevice(r->cfg.device));
+    if (!r->accum.p) {
+        const size_t bytes = (size_t)r->tm.n_local_tiles * RT_TILE * RT_TILE * sizeof(float4);
+        HIP_TRY(r->accum.alloc(bytes));
+        HIP_TRY(hipMemset(r->accum.p, 0, bytes));   // padding pixels of a shard are never written: they read as zeros
+    }
+    int rc = enqueue_call(r, hip_stream, d_out, r->refine_done, n_samples, true);
+    if (rc != RT_OK) return rc;
+    r->refine_done += n_samples;
+    return RT_OK;
+}
+
+extern "C" int rt_renderer_refine(rt_renderer* r, uint32_t n_samples) {
+    if (!r) return rt_fail(RT_ERR_INVALID, "rt_renderer_refine: null renderer");
+    int rc = rt_renderer_refine_async(r, r->stream, nullptr, n_samples);
+    if (rc != RT_OK) return rc;
+    return wait_and_check(r);
+}
+
+extern "C" int rt_renderer_refine_reset(rt_renderer* r) {
+    if (!r) return rt_fail(RT_ERR_INVALID, "rt_renderer_refine_reset: null renderer");
+    r->refine_done = 0;   // the next step's first pass starts from zero instead of loading the accumulation
+    return RT_OK;
+}
+
+extern "C" int rt_renderer_refine_info(rt_renderer* r, uint64_t out[3]) {
+    if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_refine_info: null argument");
+    out[0] = r->refine_done;
+    out[1] = r->variant >= 2 ? r->pass_spp : 0u;
+    out[2] = r->accum.bytes + r->noise_partials.bytes + r->noise_out.bytes;
+    return RT_OK;
+}
+
+// the work of the last call may be on a caller's stream (the _async entry points): its end event orders what reads the results
+static int wait_last_call(rt_renderer* r) {
+    HIP_TRY(hipSetDevice(r->cfg.device));
+    if (r->timed) HIP_TRY(hipEventSynchronize(r->ev1));
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    return RT_OK;
+}
+
+extern "C" int rt_renderer_refine_download_sums(rt_renderer* r, float* host, size_t n_floats) {
+    if (!r || !host) return rt_fail(RT_ERR_INVALID, "rt_renderer_refine_download_sums: null argument");
+    if (r->cfg.world_size != 1) return rt_fail(RT_ERR_INVALID, "rt_renderer_refine_download_sums: renderer holds one shard of %u", r->cfg.world_size);
+    const size_t need = (size_t)r->cfg.width * r->cfg.height * 4;
+    if (n_floats != need) return rt_fail(RT_ERR_INVALID, "rt_renderer_refine_download_sums: buffer holds %zu floats, image needs %zu", n_floats, need);
+    if (r->refine_done == 0 || !r->accum.p) return rt_fail(RT_ERR_INVALID, "rt_renderer_refine_download_sums: nothing accumulated (refine first)");
+    int rc = wait_last_call(r);
+    if (rc != RT_OK) return rc;
+    const uint32_t n_local = r->tm.n_local_tiles * RT_TILE * RT_TILE;
+    std::vector<float> local((size_t)n_local * 4u);
+    HIP_TRY(hipMemcpy(local.data(), r->accum.p, local.size() * sizeof(float), hipMemcpyDeviceToHost));
+    std::vector<uint32_t> gid(n_local);   // the accumulation is tile-major like a shard: put it in the frame's row-major order
+    rc = rt_shard_pixel_map(r->cfg.width, r->cfg.height, 1u, 0u, gid.data(), gid.size());
+    if (rc != RT_OK) return rc;
+    for (uint32_t L = 0; L < n_local; L++)
+        if (gid[L] != 0xffffffffu) std::memcpy(host + (size_t)gid[L] * 4u, local.data() + (size_t)L * 4u, 4u * sizeof(float));
+    return RT_OK;
+}
+
+extern "C" int rt_renderer_refine_noise(rt_renderer* r, double* out) {
+    if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_refine_noise: null argument");
+    if (r->refine_done < 2 || !r->accum.p) return rt_fail(RT_ERR_INVALID, "rt_renderer_refine_noise: a variance needs 2 samples per pixel; %u accumulated", r->refine_done);
+    int rc = wait_last_call(r);
+    if (rc != RT_OK) return rc;
+    const uint32_t n_local = r->tm.n_local_tiles * RT_TILE * RT_TILE;
+    const uint32_t n_blocks = (n_local + RT_NOISE_BLOCK - 1u) / RT_NOISE_BLOCK;
+    if (!r->noise_partials.p) {
+        HIP_TRY(r->noise_partials.alloc((size_t)n_blocks * sizeof(NoiseSums)));
+        HIP_TRY(r->noise_out.alloc(sizeof(NoiseSums)));
+    }
+    refine_noise_kernel<<<n_blocks, RT_NOISE_BLOCK, 0, r->stream>>>(r->tm, r->accum.as<float4>(), r->refine_done, r->noise_partials.as<NoiseSums>());
+    HIP_TRY(hipGetLastError());
+    refine_noise_finish_kernel<<<1, RT_NOISE_BLOCK, 0, r->stream>>>(r->noise_partials.as<NoiseSums>(), n_blocks, r->noise_out.as<NoiseSums>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    NoiseSums sums = {0.0, 0.0, 0.0};   // over the pixels of this renderer's share of the frame: padding and non-finite pixels left out
+    HIP_TRY(hipMemcpy(&sums, r->noise_out.p, sizeof(sums), hipMemcpyDeviceToHost));
+    if (sums.pixels == 0.0) { *out = (double)INFINITY; return RT_OK; }
+    const double mean_v = sums.v / sums.pixels, mean_m = sums.m / sums.pixels;
+    *out = mean_m == 0.0 ? (double)INFINITY : std::sqrt(mean_v) / mean_m;   // a black frame has no relative error: +inf, not an error
     return RT_OK;
 }
 
@@ -466,10 +588,7 @@ extern "C" int rt_renderer_render(rt_renderer* r) {
     if (!r) return rt_fail(RT_ERR_INVALID, "rt_renderer_render: null renderer");
     int rc = rt_renderer_render_async(r, r->stream, nullptr);
     if (rc != RT_OK) return rc;
-    HIP_TRY(hipStreamSynchronize(r->stream));
-    rc = check_xchg_error(r->xchg_error);
-    if (rc != RT_OK) return rc;
-    return check_traversal_overflow(r->scene);
+    return wait_and_check(r);
 }
 
 extern "C" int rt_renderer_last_kernel_ms(rt_renderer* r, float* out_ms) {
@@ -488,10 +607,12 @@ extern "C" int rt_renderer_kernel_times(rt_renderer* r, uint32_t renders_back, f
         return rt_fail(RT_ERR_INVALID, "rt_renderer_kernel_times: render %u calls back is not recorded (%llu rendered, ring of %u)", renders_back,
                        (unsigned long long)r->n_renders, rt_renderer::RT_TIMES_RING);
     HIP_TRY(hipSetDevice(r->cfg.device));
-    const std::vector<hipEvent_t>& ring = r->kev[(r->n_renders - 1 - renders_back) % rt_renderer::RT_TIMES_RING];
-    HIP_TRY(hipEventSynchronize(ring[(size_t)r->n_passes * 4u - 1u]));
+    const uint64_t slot = (r->n_renders - 1 - renders_back) % rt_renderer::RT_TIMES_RING;
+    const std::vector<hipEvent_t>& ring = r->kev[slot];
+    const uint32_t call_passes = r->kev_passes[slot];   // of THAT call: a refine step has a pass count of its own
+    HIP_TRY(hipEventSynchronize(ring[(size_t)call_passes * 4u - 1u]));
     for (int k = 0; k < 3; k++) out_ms[k] = 0.0f;
-    for (uint32_t pass = 0; pass < r->n_passes; pass++)   // a render is n_passes launches of each kernel: the SUM is the render's time in it
+    for (uint32_t pass = 0; pass < call_passes; pass++)   // a call is that many launches of each kernel: the SUM is the call's time in it
         for (int k = 0; k < 3; k++) {
             float ms = 0.0f;
             HIP_TRY(hipEventElapsedTime(&ms, ring[pass * 4u + k], ring[pass * 4u + k + 1]));

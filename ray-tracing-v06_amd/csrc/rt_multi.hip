@@ -162,12 +162,14 @@ static int multi_fail_drain(rt_multi_renderer* m, int rc) {
 
 // launches, exchange, assembly, final synchronisation; ANY early return leaves work enqueued on some rank's stream and goes through
 // multi_fail_drain in the caller below
-static int multi_render_body(rt_multi_renderer* m) {
+// n_refine == 0: Render(); otherwise every rank adds n_refine samples to its accumulation (rt_renderer_refine_async) and the refined shards travel
+static int multi_render_body(rt_multi_renderer* m, uint32_t n_refine) {
     const uint32_t n = (uint32_t)m->parts.size();
     const auto t0 = std::chrono::steady_clock::now();
     hipStream_t s0 = rt_renderer_own_stream(m->parts[0]);
     for (uint32_t i = 0; i < n; i++) {   // every GPU renders its tiles; the launches are asynchronous, so the N kernels run side by side
-        int rc = rt_renderer_render_async(m->parts[i], rt_renderer_own_stream(m->parts[i]), nullptr);
+        int rc = n_refine ? rt_renderer_refine_async(m->parts[i], rt_renderer_own_stream(m->parts[i]), nullptr, n_refine)
+                          : rt_renderer_render_async(m->parts[i], rt_renderer_own_stream(m->parts[i]), nullptr);
         if (rc != RT_OK) return rc;
         HIP_TRY(hipEventRecord(m->ev_part[i], rt_renderer_own_stream(m->parts[i])));
     }
@@ -235,8 +237,25 @@ static int multi_render_body(rt_multi_renderer* m) {
 
 extern "C" int rt_multi_renderer_render(rt_multi_renderer* m) {
     if (!m) return rt_fail(RT_ERR_INVALID, "rt_multi_renderer_render: null renderer");
-    const int rc = multi_render_body(m);
+    const int rc = multi_render_body(m, 0u);
     return rc == RT_OK ? RT_OK : multi_fail_drain(m, rc);   // nothing stays in flight behind an error, whichever call failed
+}
+
+extern "C" int rt_multi_renderer_refine(rt_multi_renderer* m, uint32_t n_samples) {
+    if (!m) return rt_fail(RT_ERR_INVALID, "rt_multi_renderer_refine: null renderer");
+    if (n_samples == 0) return rt_fail(RT_ERR_INVALID, "rt_multi_renderer_refine: n_samples must be > 0");
+    const int rc = multi_render_body(m, n_samples);
+    return rc == RT_OK ? RT_OK : multi_fail_drain(m, rc);
+}
+
+extern "C" int rt_multi_renderer_set_camera(rt_multi_renderer* m, const rt_camera* cam) {
+    if (!m || !cam) return rt_fail(RT_ERR_INVALID, "rt_multi_renderer_set_camera: null argument");
+    if (cam->type > RT_CAM_MOTION) return rt_fail(RT_ERR_INVALID, "rt_multi_renderer_set_camera: unknown camera type %u", cam->type);   // refused before any part changes
+    for (rt_renderer* r : m->parts) {
+        const int rc = rt_renderer_set_camera(r, cam);
+        if (rc != RT_OK) return rc;
+    }
+    return RT_OK;
 }
 
 extern "C" int rt_multi_renderer_download(rt_multi_renderer* m, float* host_rgba, size_t n_floats) {

@@ -788,6 +788,31 @@ __global__ __launch_bounds__(256) void primary_rays_kernel(StreamParams p, uint3
     rt_store_stream(p.prim_rng + n, make_uint4(rng.s0, rng.s1, rng.s2, rng.s3));
 }
 
+// The two steps every resolve shares, so that a frame refined in steps and a frame rendered in one call cannot drift apart:
+//   add_pass_samples: the samples of one pass added to a pixel's sum IN SAMPLE ORDER (Renderer.cu:198-204: `radiance += ...`);
+//   resolve_pixel:    mean / clamp / sqrt-gamma / alpha over n_samples (Renderer.cu:206-216).
+// WITH_Q (refinement): in the same loop, q += Y * Y with the sample's luminance Y = (0.2126 r + 0.7152 g) + 0.0722 b, every operation
+// rounded on its own (the library is built without contraction; the _rn intrinsics say it again), so numpy float32 restates it bit for bit.
+template <bool WITH_Q>
+__device__ __forceinline__ f3 add_pass_samples(const StreamParams& p, uint32_t L, f3 radiance, float& q) {
+    size_t src = (size_t)(L >> 6) * p.pass_spp * 64u + (L & 63u);   // 64 consecutive pixels per sample row: coalesced
+    for (uint32_t s = 0; s < p.pass_spp; s++) {
+        const f3 c = load_sample(p.samples, src);
+        radiance = radiance + c;
+        if (WITH_Q) {
+            const float y = __fadd_rn(__fadd_rn(__fmul_rn(0.2126f, c.x), __fmul_rn(0.7152f, c.y)), __fmul_rn(0.0722f, c.z));
+            q = __fadd_rn(q, __fmul_rn(y, y));
+        }
+        src += 64u;
+    }
+    return radiance;
+}
+__device__ __forceinline__ float4 resolve_pixel(f3 radiance, uint32_t n_samples) {
+    radiance = radiance * (1.0f / (float)n_samples);
+    const f3 col = clamp01_sqrt(radiance);
+    return make_float4(col.x, col.y, col.z, 1.0f);
+}
+
 // Adds the samples of one pass to each pixel IN SAMPLE ORDER (Renderer.cu:198-204: `radiance += ...`),
 // and on the last pass applies mean / clamp / sqrt-gamma / alpha (Renderer.cu:206-216).
 __global__ __launch_bounds__(256) void resolve_kernel(StreamParams p, float4* __restrict__ running, float* __restrict__ out, uint32_t last_pass) {
@@ -797,16 +822,69 @@ __global__ __launch_bounds__(256) void resolve_kernel(StreamParams p, float4* __
     if (!local_pixel_to_gid(p.tm, L, gid)) return;
     f3 radiance = mk3(0.0f);
     if (p.pass_first_s != 0u) { const float4 r = running[L]; radiance = mk3(r.x, r.y, r.z); }
-    size_t src = (size_t)(L >> 6) * p.pass_spp * 64u + (L & 63u);
-    for (uint32_t s = 0; s < p.pass_spp; s++) {
-        radiance = radiance + load_sample(p.samples, src);
-        src += 64u;
-    }
+    float unused = 0.0f;
+    radiance = add_pass_samples<false>(p, L, radiance, unused);
     if (last_pass) {
-        radiance = radiance * (1.0f / (float)p.spp);
-        f3 col = clamp01_sqrt(radiance);
-        reinterpret_cast<float4*>(out)[p.tm.direct ? gid : L] = make_float4(col.x, col.y, col.z, 1.0f);
+        reinterpret_cast<float4*>(out)[p.tm.direct ? gid : L] = resolve_pixel(radiance, p.spp);
     } else {
         running[L] = make_float4(radiance.x, radiance.y, radiance.z, 0.0f);
     }
+}
+
+// Progressive refinement (rt_renderer_refine): the pass holds samples [pass_first_s, pass_first_s + pass_spp) of every pixel; they are added to
+// the renderer's accumulation `acc` = (sum R, sum G, sum B, sum Y^2) per local pixel, which continues the sum of every earlier refine call
+// in sample order — the float additions are those of ONE render at samples_per_pixel = pass_first_s + pass_spp, whatever the steps were.
+// On the last pass of a step the frame for `done_after` samples is written.  A pure HBM stream: 12 B per sample, 16 B + 16 B per pixel.
+__global__ __launch_bounds__(256) void refine_resolve_kernel(StreamParams p, float4* __restrict__ acc, float* __restrict__ out, uint32_t last_pass, uint32_t done_after) {
+    uint32_t L = blockIdx.x * blockDim.x + threadIdx.x;
+    if (L >= p.tm.n_local_tiles * RT_TILE * RT_TILE) return;
+    uint32_t gid;
+    if (!local_pixel_to_gid(p.tm, L, gid)) return;
+    f3 radiance = mk3(0.0f);
+    float q = 0.0f;
+    if (p.pass_first_s != 0u) { const float4 r = acc[L]; radiance = mk3(r.x, r.y, r.z); q = r.w; }
+    radiance = add_pass_samples<true>(p, L, radiance, q);
+    acc[L] = make_float4(radiance.x, radiance.y, radiance.z, q);
+    if (last_pass) reinterpret_cast<float4*>(out)[p.tm.direct ? gid : L] = resolve_pixel(radiance, done_after);
+}
+
+// Noise figure of a refined frame (rt_renderer_refine_noise), stage 1: per pixel, in fp32 with individually rounded operations and IEEE
+// division, n = samples so far:  m = ((0.2126 Sr + 0.7152 Sg) + 0.0722 Sb) / n  (mean luminance),  v = max(0, Q / n - m * m) / (n - 1)
+// (variance of that mean).  The workgroup's sums of v and of m and its count of pixels are taken in fp64 in a FIXED order — lanes by
+// __shfl_down, the four waves by thread 0 — and written as one partial (sum v, sum m, pixels) per workgroup.  No atomics: the figure
+// repeats bit for bit.  Padding pixels of a shard contribute nothing, and neither does a pixel whose m or v is not finite: the reference's
+// arithmetic makes a NaN sample about once per 6e8 ("NaN pixels"), and one such pixel must not turn a frame's figure into NaN.
+#define RT_NOISE_BLOCK 256u
+struct NoiseSums { double v, m, pixels; };
+__device__ __forceinline__ void noise_block_sum(NoiseSums& a, double (*lds)[3]) {
+    for (int off = 32; off > 0; off >>= 1) { a.v += __shfl_down(a.v, off); a.m += __shfl_down(a.m, off); a.pixels += __shfl_down(a.pixels, off); }
+    const uint32_t wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63u) == 0u) { lds[wave][0] = a.v; lds[wave][1] = a.m; lds[wave][2] = a.pixels; }
+    __syncthreads();
+    if (threadIdx.x == 0u)
+        for (uint32_t w = 1; w < RT_NOISE_BLOCK / 64u; w++) { a.v += lds[w][0]; a.m += lds[w][1]; a.pixels += lds[w][2]; }
+}
+__global__ __launch_bounds__(RT_NOISE_BLOCK) void refine_noise_kernel(TileMap tm, const float4* __restrict__ acc, uint32_t n_done, NoiseSums* __restrict__ partials) {
+    __shared__ double lds[RT_NOISE_BLOCK / 64u][3];
+    const uint32_t L = blockIdx.x * RT_NOISE_BLOCK + threadIdx.x;
+    NoiseSums s = {0.0, 0.0, 0.0};
+    uint32_t gid;
+    if (L < tm.n_local_tiles * RT_TILE * RT_TILE && local_pixel_to_gid(tm, L, gid)) {
+        const float4 a = acc[L];
+        const float n = (float)n_done, n1 = (float)(n_done - 1u);
+        const float m = __fdiv_rn(__fadd_rn(__fadd_rn(__fmul_rn(0.2126f, a.x), __fmul_rn(0.7152f, a.y)), __fmul_rn(0.0722f, a.z)), n);
+        const float d = __fsub_rn(__fdiv_rn(a.w, n), __fmul_rn(m, m));
+        const float v = __fdiv_rn(d < 0.0f ? 0.0f : d, n1);   // max(0, d) that KEEPS a NaN (inf - inf of an overflowed pixel): fmaxf would turn it into 0
+        if (isfinite(m) && isfinite(v)) { s.v = (double)v; s.m = (double)m; s.pixels = 1.0; }
+    }
+    noise_block_sum(s, lds);
+    if (threadIdx.x == 0u) partials[blockIdx.x] = s;
+}
+// stage 2: ONE workgroup; thread t adds partials t, t + 256, ... in that order, then the same fixed-order workgroup sum
+__global__ __launch_bounds__(RT_NOISE_BLOCK) void refine_noise_finish_kernel(const NoiseSums* __restrict__ partials, uint32_t n_partials, NoiseSums* __restrict__ out) {
+    __shared__ double lds[RT_NOISE_BLOCK / 64u][3];
+    NoiseSums s = {0.0, 0.0, 0.0};
+    for (uint32_t i = threadIdx.x; i < n_partials; i += RT_NOISE_BLOCK) { const NoiseSums q = partials[i]; s.v += q.v; s.m += q.m; s.pixels += q.pixels; }
+    noise_block_sum(s, lds);
+    if (threadIdx.x == 0u) out[0] = s;
 }

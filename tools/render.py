@@ -5,6 +5,12 @@
 
 Scenes: book1_final (DefocusBlurCamera vfov 20, aperture 0.1), book2_moving (MotionBlurCamera t in [0,1]),
 three_spheres (PinholeCamera vfov 90).  Prints one JSON line with the render time and Msamples/s.
+
+    python tools/render.py --scene book1_final --spp 500 --refine 50 --until 0.01 --out out.png
+
+renders progressively (rt_renderer_refine): steps of 50 samples up to --spp, one line per step with the samples so far and the noise
+figure (relative RMS standard error of the frame's mean luminance), stopping early once it is below --until.  The image written is the
+last refined frame: bit for bit the frame a one-shot render at that sample count gives.
 """
 import argparse, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -19,8 +25,12 @@ ap.add_argument("--depth", type=int, default=50)
 ap.add_argument("--seed", type=int, default=1984)
 ap.add_argument("--device", type=int, default=0)
 ap.add_argument("--gpus", type=int, default=1, help="> 1: tile-shard the frame over GPUs 0..N-1 of this node from this one process (rt_multi_renderer_*, one RCCL exchange)")
+ap.add_argument("--refine", type=int, default=0, metavar="STEP", help="render in steps of STEP samples up to --spp, printing samples and noise per step")
+ap.add_argument("--until", type=float, default=None, metavar="NOISE", help="with --refine: stop once the noise figure is below NOISE (one GPU)")
 ap.add_argument("--out", default="render.png")
 a = ap.parse_args()
+if a.refine < 0 or (a.until is not None and (a.refine == 0 or a.gpus > 1)):
+    ap.error("--until needs --refine STEP > 0 and one GPU (the multi-GPU renderer has no noise figure)")
 p = G.load_package()
 from ray_tracing_v06_amd import image_io
 W, H = a.width, a.height
@@ -34,7 +44,24 @@ elif a.scene == "book1_final":
     scene, cam = p.Scene.book1_final(a.seed), p.DefocusBlurCamera((13, 2, 3), (0, 0, 0), (0, 1, 0), 20.0, W / H, 0.1, 10.0)
 else:
     scene, cam = p.Scene.book2_moving(a.seed), p.MotionBlurCamera((13, 2, 3), (0, 0, 0), (0, 1, 0), 20.0, W / H, 0.0, 1.0)
-if a.gpus > 1:
+samples = a.spp
+if a.refine:
+    import time
+    step_spp = min(a.refine, a.spp)   # what one pass is sized for; the steps go on to --spp
+    r = (p.MultiRenderer.MakeRenderer(W, H, step_spp, a.depth, cam, scene.getWorldPtr(), a.gpus, seed=a.seed) if a.gpus > 1
+         else p.Renderer.MakeRenderer(W, H, step_spp, a.depth, cam, scene.getWorldPtr(), seed=a.seed, device=a.device))
+    samples, ms = 0, 0.0
+    while samples < a.spp:
+        n = min(a.refine, a.spp - samples)
+        t0 = time.perf_counter()
+        r.refine(n)
+        ms += (time.perf_counter() - t0) * 1e3
+        samples += n
+        noise = r.noise() if a.gpus == 1 and samples >= 2 else None
+        print(json.dumps({"samples": samples, "noise": noise, "elapsed_ms": round(ms, 3)}), flush=True)
+        if a.until is not None and noise is not None and noise < a.until:
+            break
+elif a.gpus > 1:
     r = p.MultiRenderer.MakeRenderer(W, H, a.spp, a.depth, cam, scene.getWorldPtr(), a.gpus, seed=a.seed)
     r.Render()
     ms = r.times()[0]     # host wall-clock of Render(): all shards, the exchange, the assembly
@@ -45,5 +72,5 @@ else:
 fb = r.DownloadRenderbuffer()
 # .jpg = the reference app's own format (stbi_write_jpg quality 95, FirstApp.cpp:120); .ppm / .png are lossless
 (image_io.write_ppm if a.out.endswith(".ppm") else image_io.write_jpg if a.out.endswith((".jpg", ".jpeg")) else image_io.write_png)(a.out, fb)
-print(json.dumps({"scene": a.scene, "width": W, "height": H, "spp": a.spp, "max_depth": a.depth, "render_ms": round(ms, 3),
-                  "msamples_per_s": round(W * H * a.spp / ms / 1e3, 1), "gpus": a.gpus, "out": a.out}))
+print(json.dumps({"scene": a.scene, "width": W, "height": H, "spp": samples, "max_depth": a.depth, "render_ms": round(ms, 3),
+                  "msamples_per_s": round(W * H * samples / ms / 1e3, 1), "gpus": a.gpus, "out": a.out}))
