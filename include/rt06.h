@@ -372,6 +372,59 @@ int rt_renderer_refine_download_sums(rt_renderer* r, float* host, size_t n_float
 int rt_renderer_refine_noise(rt_renderer* r, double* out);
 
 /* ------------------------------------------------------------------ */
+/* Feature buffers and denoiser (not in the reference): what a refined   */
+/* frame looks AT — first-hit normal, depth, albedo — and an edge-aware */
+/* filter guided by them, so that a frame of 8 to 32 samples can be shown. */
+/* ------------------------------------------------------------------ */
+/* Turns the feature buffers on: from now on every refine pass is followed by a feature pass over the pass's OWN primary rays (jitter,
+ * lens point and shutter time included), one bounce through the world's own traversal.  Per local pixel two float4 (32 B, allocated
+ * here): (sum Nx, sum Ny, sum Nz, sum t) and (sum Ar, sum Ag, sum Ab, hits).  A hit adds the trace's normal, its distance (in units of
+ * the ray direction's length, as the reference's records hold it), the first-hit albedo and 1; a miss adds albedo (1,1,1) only.
+ * Albedo: Lambertian and metal: the material's; checker: the texture value at the hit point; dielectric and diffuse light: (1,1,1).
+ * The sums are fp32, IN SAMPLE ORDER per pixel: after any sequence of refine steps they have the bits of one step of the same total.
+ * max_samples == 0: every refined sample is covered; otherwise samples with index >= max_samples skip the feature pass.  The colour
+ * path is untouched: frame and colour sums have the same bits with the buffers on or off.  Discards the refinement state, like
+ * rt_renderer_refine_reset; afterwards the buffers share its lifecycle (reset, set_camera with other bytes: discarded; set_camera with
+ * the same bytes, a Render() between steps: kept).  A sharded renderer accumulates its shard.  RT_ERR_INVALID: a renderer on the
+ * baseline kernel (variant 1); a world with a constant medium (its first "hit" draws from the RNG), a noise or an image texture.       */
+int rt_renderer_aov_enable(rt_renderer* r, uint32_t max_samples);
+/* out[0] = 1 when enabled, out[1] = samples per pixel the buffers cover, out[2] = bytes held */
+int rt_renderer_aov_info(rt_renderer* r, uint64_t out[3]);
+/* width*height*8 floats, row-major like download, the two float4 of a pixel back to back, UNscaled; world_size == 1 only */
+int rt_renderer_aov_download(rt_renderer* r, float* host, size_t n_floats);
+
+/* A variance-guided a-trous wavelet filter of the refined frame.  With n colour samples and na feature samples per pixel:
+ *   c = mean colour (as the frame takes it), A = max(sum A / na, 1e-3), N = sum N / na, Z = sum t / na,
+ *   I = c / A per channel (demodulate = 1) or c,  v = the variance of the mean luminance of rt_renderer_refine_noise, divided by
+ *   max(Y(A), 1e-3)^2 when demodulating;  Y(r,g,b) = (0.2126f*r + 0.7152f*g) + 0.0722f*b.
+ * Iteration i = 0 .. iterations-1, step = 1 << i, 5x5 taps h = (1/16, 1/4, 3/8, 1/4, 1/16) at distance step, row-major tap order
+ * (dy, then dx, from -2 to 2), sequential fp32 sums, taps outside the image left out; the centre weighs h(0)^2; another tap
+ *   w = ((h(dx)*h(dy) * wn) * wz) * wl,   wn = max(0, dot(Np, Nq)) squared five times,
+ *   wz = 1 / (1 + dz*dz),  dz = |Zp - Zq| / ((sigma_depth * (float)step) * min(Zp, Zq) + 1e-6f),
+ *   wl = 1 / (1 + dl*dl),  dl = |Y(Ip) - Y(Iq)| / (sigma_lum * sqrt(max(vp, 0)) + 1e-6f);
+ *   I' = sum(w*Iq) / sum(w),  v' = sum(w*w*vq) / (sum(w))^2.  A tap whose I or v is not finite is left out; a centre that is not
+ * finite is copied through.  Output: clamp, sqrt-gamma, alpha 1 of I * A (demodulate = 1) or of I — the framebuffer's layout and
+ * conventions, in a buffer of its own: the refined frame is never overwritten.  Only fp32 + - * / sqrt and comparisons, each rounded
+ * on its own: numpy float32 restates it bit for bit.  RT_ERR_INVALID: no feature buffers or fewer than 2 accumulated samples, a
+ * renderer that holds a shard, iterations outside 1..8, a sigma that is not finite and > 0.                                          */
+typedef struct rt_denoise_params {
+    uint32_t iterations;   /* default 5 (1..8): the last step is 1 << (iterations - 1) pixels */
+    float sigma_depth;     /* default 0.05: the relative depth difference per pixel of step at which wz = 1/2 */
+    float sigma_lum;       /* default 4: luminance difference in standard deviations of the centre's mean, see wl */
+    uint32_t demodulate;   /* default 1: filter the illumination c / A instead of the colour */
+} rt_denoise_params;
+int rt_denoise_params_default(rt_denoise_params* out);   /* host only */
+int rt_renderer_denoise(rt_renderer* r, const rt_denoise_params* params);   /* blocking, on the renderer's own stream */
+/* The same on a caller's hipStream_t, no host synchronisation.  Ordering the library takes care of, whichever streams are used: the filter
+ * starts behind the last refine step and behind the previous filter (they share buffers), and the next refine step starts behind the filter
+ * (it overwrites the sums the filter reads).  The caller's part: rt_renderer_refine_reset, rt_renderer_set_camera and rt_renderer_aov_enable
+ * are host-side state changes and touch no buffer, so they need no ordering; the HOST calls themselves must not race (one thread at a time
+ * per renderer, as everywhere in this interface); rt_renderer_denoise_download waits for the last filter.                                */
+int rt_renderer_denoise_async(rt_renderer* r, void* hip_stream, const rt_denoise_params* params);
+/* the denoised frame: width*height*4 floats like rt_renderer_download; waits for the last denoise call */
+int rt_renderer_denoise_download(rt_renderer* r, float* host_rgba, size_t n_floats);
+
+/* ------------------------------------------------------------------ */
 /* Multi-GPU renderer — the same three entry points (Renderer.h:38-46)  */
 /* over the N GPUs of one node, driven by ONE host process.            */
 /* ------------------------------------------------------------------ */

@@ -560,6 +560,24 @@ public:
         rt06::check(rt_renderer_refine_noise(m.r, &v), "Renderer::Noise");
         return v;
     }
+    // Feature buffers and denoiser (rt06.h; one GPU only).  EnableAOV restarts the refinement; every Refine() after it also accumulates the
+    // first-hit normal / depth / albedo of its own primary rays.  Denoise() filters the refined frame into a buffer of its own.
+    void EnableAOV(uint32_t max_samples = 0) { single("Renderer::EnableAOV"); rt06::check(rt_renderer_aov_enable(m.r, max_samples), "Renderer::EnableAOV"); }
+    // width*height pairs of vec4: (sum Nx, sum Ny, sum Nz, sum t), (sum Ar, sum Ag, sum Ab, hits), unscaled
+    void DownloadAOV(glm::vec4* host_dst) {
+        single("Renderer::DownloadAOV");
+        rt06::check(rt_renderer_aov_download(m.r, reinterpret_cast<float*>(host_dst), (size_t)m.render_width * m.render_height * 8), "Renderer::DownloadAOV");
+    }
+    void Denoise(const rt_denoise_params* params = nullptr) {
+        single("Renderer::Denoise");
+        rt_denoise_params d;
+        rt06::check(rt_denoise_params_default(&d), "Renderer::Denoise");
+        rt06::check(rt_renderer_denoise(m.r, params ? params : &d), "Renderer::Denoise");
+    }
+    void DownloadDenoised(glm::vec4* host_dst) {
+        single("Renderer::DownloadDenoised");
+        rt06::check(rt_renderer_denoise_download(m.r, reinterpret_cast<float*>(host_dst), (size_t)m.render_width * m.render_height * 4), "Renderer::DownloadDenoised");
+    }
     float LastKernelMs() {
         float ms = 0;
         if (m.mr) { float t[3]; rt06::check(rt_multi_renderer_times(m.mr, t), "Renderer::LastKernelMs"); return t[0]; }

@@ -297,6 +297,48 @@ class Renderer:
         check(lib().rt_renderer_refine_noise(self.h, C.byref(out)))
         return out.value
 
+    def enable_aov(self, max_samples=0):
+        """Accumulate first-hit feature buffers alongside every refine step from now on (restarts the refinement); max_samples = 0: every sample."""
+        check(lib().rt_renderer_aov_enable(self.h, max_samples))
+
+    def aov_info(self):
+        """{'enabled', 'samples', 'bytes'}: whether the feature buffers are on, the samples per pixel they cover, bytes held."""
+        out = (C.c_uint64 * 3)()
+        check(lib().rt_renderer_aov_info(self.h, out))
+        return {"enabled": bool(out[0]), "samples": out[1], "bytes": out[2]}
+
+    def aov_sums(self):
+        """(H, W, 8) float32, unscaled: (sum Nx, sum Ny, sum Nz, sum t, sum Ar, sum Ag, sum Ab, hits) per pixel (world_size == 1)."""
+        out = np.zeros((self.cfg.height, self.cfg.width, 8), dtype=np.float32)
+        check(lib().rt_renderer_aov_download(self.h, out, out.size))
+        return out
+
+    def aov(self):
+        """{'normal' (H,W,3), 'depth' (H,W), 'albedo' (H,W,3), 'coverage' (H,W)}: the feature sums divided by the samples they cover."""
+        sums, inv = self.aov_sums(), np.float32(1.0) / np.float32(self.aov_info()["samples"])
+        return {"normal": sums[..., 0:3] * inv, "depth": sums[..., 3] * inv, "albedo": sums[..., 4:7] * inv, "coverage": sums[..., 7] * inv}
+
+    @staticmethod
+    def denoise_params(**params):
+        """rt_denoise_params with the library's defaults, then iterations / sigma_depth / sigma_lum / demodulate as given."""
+        dp = capi.DenoiseParams()
+        check(lib().rt_denoise_params_default(C.byref(dp)))
+        for k, v in params.items():
+            if k not in ("iterations", "sigma_depth", "sigma_lum", "demodulate"):
+                raise TypeError(f"denoise: unknown parameter {k}")
+            setattr(dp, k, v)
+        return dp
+
+    def denoise(self, **params):
+        """Filter the refined frame (rt_renderer_denoise) and return the denoised image, (H, W, 4) float32; the refined frame stays as it is."""
+        check(lib().rt_renderer_denoise(self.h, C.byref(self.denoise_params(**params))))
+        out = np.zeros((self.cfg.height, self.cfg.width, 4), dtype=np.float32)
+        check(lib().rt_renderer_denoise_download(self.h, out, out.size))
+        return out
+
+    def denoise_async(self, stream=None, **params):
+        check(lib().rt_renderer_denoise_async(self.h, C.c_void_p(stream or 0), C.byref(self.denoise_params(**params))))
+
     def last_kernel_ms(self):
         ms = C.c_float()
         check(lib().rt_renderer_last_kernel_ms(self.h, C.byref(ms)))

@@ -54,6 +54,10 @@ class RenderConfig(C.Structure):
                 ("rank", C.c_uint32), ("world_size", C.c_uint32), ("variant", C.c_uint32)]
 
 
+class DenoiseParams(C.Structure):
+    _fields_ = [("iterations", C.c_uint32), ("sigma_depth", C.c_float), ("sigma_lum", C.c_float), ("demodulate", C.c_uint32)]
+
+
 class RtError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"rt06 error {code}: {msg}")
@@ -75,6 +79,8 @@ SYMBOLS = [
     "rt_selftest_fastdiv", "rt_selftest_fastdiv4", "rt_selftest_fastrcp", "rt_device_count", "rt_version", "rt_source_hash", "rt_renderer_pass_info",
     "rt_renderer_set_camera", "rt_multi_renderer_set_camera", "rt_renderer_refine", "rt_renderer_refine_async", "rt_renderer_refine_reset",
     "rt_renderer_refine_info", "rt_renderer_refine_download_sums", "rt_renderer_refine_noise", "rt_multi_renderer_refine",
+    "rt_renderer_aov_enable", "rt_renderer_aov_info", "rt_renderer_aov_download", "rt_denoise_params_default", "rt_renderer_denoise",
+    "rt_renderer_denoise_async", "rt_renderer_denoise_download",
 ]
 
 _lib = None
@@ -187,6 +193,13 @@ def lib():
     L.rt_renderer_refine_download_sums.argtypes = [C.c_void_p, f32p, C.c_size_t]
     L.rt_renderer_refine_noise.argtypes = [C.c_void_p, P(C.c_double)]
     L.rt_multi_renderer_refine.argtypes = [C.c_void_p, C.c_uint32]
+    L.rt_renderer_aov_enable.argtypes = [C.c_void_p, C.c_uint32]
+    L.rt_renderer_aov_info.argtypes = [C.c_void_p, C.c_uint64 * 3]
+    L.rt_renderer_aov_download.argtypes = [C.c_void_p, f32p, C.c_size_t]
+    L.rt_denoise_params_default.argtypes = [P(DenoiseParams)]
+    L.rt_renderer_denoise.argtypes = [C.c_void_p, P(DenoiseParams)]
+    L.rt_renderer_denoise_async.argtypes = [C.c_void_p, C.c_void_p, P(DenoiseParams)]
+    L.rt_renderer_denoise_download.argtypes = [C.c_void_p, f32p, C.c_size_t]
     L.rt_multi_renderer_create.argtypes = [P(RenderConfig), P(Camera), P(WorldFlat), C.c_uint32, C.c_void_p, P(C.c_void_p)]
     L.rt_multi_renderer_destroy.argtypes = [C.c_void_p]
     L.rt_multi_renderer_destroy.restype = None

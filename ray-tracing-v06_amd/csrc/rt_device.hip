@@ -4,6 +4,7 @@
 #include "rt_render_kernels.hpp"
 #include "rt_stream_kernel.hpp"
 #include "rt_xchg_kernel.hpp"
+#include "rt_aov_kernel.hpp"
 
 extern "C" int rt_device_info(int device, uint32_t out[4]) {
     if (!out) return rt_fail(RT_ERR_INVALID, "rt_device_info: null out");
@@ -89,6 +90,19 @@ struct rt_renderer {
     // pixel, a buffer of its own (allocated at the first refine call) so that a Render() between two steps disturbs neither
     DevBuf accum, noise_partials, noise_out;
     uint32_t refine_done = 0;
+    // first-hit feature buffers (rt_renderer_aov_enable): two float4 per local pixel, continued by aov_kernel after each refine pass; they share the
+    // refinement state's lifecycle.  aov_done = samples [0, aov_done) of every pixel are in them (<= aov_max when that is not 0).
+    DevBuf aov;
+    bool aov_on = false;
+    uint32_t aov_max = 0, aov_done = 0;
+    const char* aov_refused = nullptr;   // the first material of the world the feature pass does not cover (a medium, a noise or an image texture)
+    // denoiser (rt_renderer_denoise): guide records, the two colour buffers the iterations ping-pong, the output frame; allocated at first use
+    DevBuf dn_g0, dn_g1, dn_a, dn_b, dn_out;
+    // ordering between refine steps and the filter, whichever streams the caller gives them: refine_ev = end of the last refine step (the filter
+    // reads accum / aov behind it), dn_ev = end of the last filter (the next step, which overwrites accum / aov, and the next filter, which
+    // shares the colour buffers, start behind it)
+    hipEvent_t dn_ev = nullptr, refine_ev = nullptr;
+    bool dn_valid = false;
     static constexpr uint32_t SAMPLE_BYTES = RT_SAMPLE_BYTES, PRIMARY_BYTES = 48;   // HBM per sample index of a pass: radiance (float4) + primary ray record
 
     // Pick the kernel variant and size the per-pass sample buffer.
@@ -409,11 +423,39 @@ struct rt_renderer {
             else resolve_kernel<<<(n_local_pixels + 255) / 256, 256, 0, st>>>(p, running.as<float4>(), out, last);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipEventRecord(ke[3], st));
+            // feature pass: after the pass's fourth timing event (rt_renderer_kernel_times keeps its meaning), before the next pass's generator
+            // overwrites the primary-ray records
+            if (refine && aov_on) {
+                const uint32_t upto = aov_max ? std::min(aov_max, first + p.pass_spp) : first + p.pass_spp;
+                if (upto > first) {
+                    const int rc = launch_aov(p, upto - first, st);
+                    if (rc != RT_OK) return rc;
+                }
+            }
         }
         n_renders++;
         return RT_OK;
     }
+    // one aov_kernel launch: the traversal is the world's own, picked here so that a kernel carries one traversal stack
+    int launch_aov(const StreamParams& sp, uint32_t n_take, hipStream_t st) {
+        const uint32_t n_local_pixels = tm.n_local_tiles * RT_TILE * RT_TILE;
+        const dim3 grid((n_local_pixels + RT_AOV_BLOCK - 1u) / RT_AOV_BLOCK), block(RT_AOV_BLOCK);
+        AovParams p;
+        p.tm = sp.tm; p.world = sp.world;
+        p.pass_first_s = sp.pass_first_s; p.pass_spp = sp.pass_spp; p.n_take = n_take;
+        p.prim_o = sp.prim_o; p.prim_d = sp.prim_d;
+        float4* out = aov.as<float4>();
+        if (scene.dw.kind == RT_WORLD_LIST) aov_kernel<RT_AOV_WALK_LIST><<<grid, block, 0, st>>>(p, out);
+        else if (scene.dw.kind == RT_WORLD_NODE_TREE) aov_kernel<RT_AOV_WALK_TREE><<<grid, block, 0, st>>>(p, out);
+        else if (scene.dw.traversal == RT_TRAVERSAL_QUEUE) aov_kernel<RT_AOV_WALK_QUEUE><<<grid, block, 0, st>>>(p, out);
+        else if (scene.dw.traversal == RT_TRAVERSAL_WIDE4) aov_kernel<RT_AOV_WALK_WIDE4><<<grid, block, 0, st>>>(p, out);
+        else aov_kernel<RT_AOV_WALK_STACK><<<grid, block, 0, st>>>(p, out);
+        HIP_TRY(hipGetLastError());
+        return RT_OK;
+    }
     ~rt_renderer() {
+        if (dn_ev) (void)hipEventDestroy(dn_ev);
+        if (refine_ev) (void)hipEventDestroy(refine_ev);
         for (auto& q : kev) for (hipEvent_t e : q) if (e) (void)hipEventDestroy(e);
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
@@ -432,6 +474,12 @@ extern "C" int rt_renderer_create(const rt_render_config* cfg, const rt_camera* 
     if (rc != RT_OK) return rc;
     rt_renderer* r = new rt_renderer();
     r->cfg = *cfg;
+    for (uint32_t i = 0; i < world->n_materials && world->materials && !r->aov_refused; i++) {
+        const uint32_t t = world->materials[i].type;
+        if (t == RT_MAT_ISOTROPIC) r->aov_refused = "a constant medium (RT_MAT_ISOTROPIC)";
+        else if (t == RT_MAT_LAMBERTIAN_NOISE) r->aov_refused = "a noise texture (RT_MAT_LAMBERTIAN_NOISE)";
+        else if (t == RT_MAT_LAMBERTIAN_IMAGE) r->aov_refused = "an image texture (RT_MAT_LAMBERTIAN_IMAGE)";
+    }
     r->cam = *cam;   // the camera of the first launch; rt_renderer_set_camera replaces it (Renderer.cu:117 reads the caller's camera at every Render())
     rc = r->scene.upload(world);
     if (rc != RT_OK) { delete r; return rc; }
@@ -490,6 +538,7 @@ extern "C" int rt_renderer_set_camera(rt_renderer* r, const rt_camera* cam) {
     if (std::memcmp(&r->cam, cam, sizeof(rt_camera)) == 0) return RT_OK;   // the same bytes: nothing moves, the refinement goes on
     r->cam = *cam;          // travels by value in the kernel arguments of the NEXT launch; launches already enqueued keep theirs
     r->refine_done = 0;     // samples accumulated under another camera belong to another frame
+    r->aov_done = 0;        // ... and so do their first hits
     return RT_OK;
 }
 
@@ -506,9 +555,13 @@ extern "C" int rt_renderer_refine_async(rt_renderer* r, void* hip_stream, float*
         HIP_TRY(r->accum.alloc(bytes));
         HIP_TRY(hipMemset(r->accum.p, 0, bytes));   // padding pixels of a shard are never written: they read as zeros
     }
+    if (!r->refine_ev) HIP_TRY(hipEventCreate(&r->refine_ev));
+    if (r->dn_valid) HIP_TRY(hipStreamWaitEvent((hipStream_t)hip_stream, r->dn_ev, 0));   // a filter may still read what this step overwrites
     int rc = enqueue_call(r, hip_stream, d_out, r->refine_done, n_samples, true);
     if (rc != RT_OK) return rc;
+    HIP_TRY(hipEventRecord(r->refine_ev, (hipStream_t)hip_stream));
     r->refine_done += n_samples;
+    if (r->aov_on) r->aov_done = r->aov_max ? std::min(r->aov_max, r->refine_done) : r->refine_done;
     return RT_OK;
 }
 
@@ -522,6 +575,7 @@ extern "C" int rt_renderer_refine(rt_renderer* r, uint32_t n_samples) {
 extern "C" int rt_renderer_refine_reset(rt_renderer* r) {
     if (!r) return rt_fail(RT_ERR_INVALID, "rt_renderer_refine_reset: null renderer");
     r->refine_done = 0;   // the next step's first pass starts from zero instead of loading the accumulation
+    r->aov_done = 0;
     return RT_OK;
 }
 
@@ -581,6 +635,114 @@ extern "C" int rt_renderer_refine_noise(rt_renderer* r, double* out) {
     if (sums.pixels == 0.0) { *out = (double)INFINITY; return RT_OK; }
     const double mean_v = sums.v / sums.pixels, mean_m = sums.m / sums.pixels;
     *out = mean_m == 0.0 ? (double)INFINITY : std::sqrt(mean_v) / mean_m;   // a black frame has no relative error: +inf, not an error
+    return RT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Feature buffers and denoiser (rt06.h; kernels: rt_aov_kernel.hpp)
+// ---------------------------------------------------------------------------------------------
+extern "C" int rt_renderer_aov_enable(rt_renderer* r, uint32_t max_samples) {
+    if (!r) return rt_fail(RT_ERR_INVALID, "rt_renderer_aov_enable: null renderer");
+    if (r->variant < 2)
+        return rt_fail(RT_ERR_INVALID, "rt_renderer_aov_enable: the baseline kernel (variant 1) cannot refine and keeps no primary-ray records; feature buffers need a streaming variant (0, or 2 to 6)");
+    if (r->aov_refused)
+        return rt_fail(RT_ERR_INVALID, "rt_renderer_aov_enable: the world has %s: the feature pass covers spheres and quads with Lambertian, metal, dielectric, checker and light materials", r->aov_refused);
+    HIP_TRY(hipSetDevice(r->cfg.device));
+    if (!r->aov.p) {
+        const size_t bytes = (size_t)r->tm.n_local_tiles * RT_TILE * RT_TILE * 2u * sizeof(float4);
+        HIP_TRY(r->aov.alloc(bytes));
+        HIP_TRY(hipMemset(r->aov.p, 0, bytes));   // padding pixels are never written: they read as zeros
+    }
+    r->aov_on = true;
+    r->aov_max = max_samples;
+    r->refine_done = 0;   // like rt_renderer_refine_reset: colour and features restart together
+    r->aov_done = 0;
+    return RT_OK;
+}
+
+extern "C" int rt_renderer_aov_info(rt_renderer* r, uint64_t out[3]) {
+    if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_aov_info: null argument");
+    out[0] = r->aov_on ? 1u : 0u;
+    out[1] = r->aov_done;
+    out[2] = r->aov.bytes;
+    return RT_OK;
+}
+
+extern "C" int rt_renderer_aov_download(rt_renderer* r, float* host, size_t n_floats) {
+    if (!r || !host) return rt_fail(RT_ERR_INVALID, "rt_renderer_aov_download: null argument");
+    if (r->cfg.world_size != 1) return rt_fail(RT_ERR_INVALID, "rt_renderer_aov_download: renderer holds one shard of %u", r->cfg.world_size);
+    const size_t need = (size_t)r->cfg.width * r->cfg.height * 8;
+    if (n_floats != need) return rt_fail(RT_ERR_INVALID, "rt_renderer_aov_download: buffer holds %zu floats, the feature buffers need %zu", n_floats, need);
+    if (!r->aov_on || r->aov_done == 0) return rt_fail(RT_ERR_INVALID, "rt_renderer_aov_download: no feature samples (rt_renderer_aov_enable, then refine)");
+    int rc = wait_last_call(r);
+    if (rc != RT_OK) return rc;
+    const uint32_t n_local = r->tm.n_local_tiles * RT_TILE * RT_TILE;
+    std::vector<float> local((size_t)n_local * 8u);
+    HIP_TRY(hipMemcpy(local.data(), r->aov.p, local.size() * sizeof(float), hipMemcpyDeviceToHost));
+    std::vector<uint32_t> gid(n_local);   // tile-major like the accumulation: put it in the frame's row-major order
+    rc = rt_shard_pixel_map(r->cfg.width, r->cfg.height, 1u, 0u, gid.data(), gid.size());
+    if (rc != RT_OK) return rc;
+    for (uint32_t L = 0; L < n_local; L++)
+        if (gid[L] != 0xffffffffu) std::memcpy(host + (size_t)gid[L] * 8u, local.data() + (size_t)L * 8u, 8u * sizeof(float));
+    return RT_OK;
+}
+
+extern "C" int rt_renderer_denoise_async(rt_renderer* r, void* hip_stream, const rt_denoise_params* params) {
+    if (!r || !params) return rt_fail(RT_ERR_INVALID, "rt_renderer_denoise: null argument");
+    if (r->cfg.world_size != 1) return rt_fail(RT_ERR_INVALID, "rt_renderer_denoise: renderer holds one shard of %u; the filter needs the whole frame", r->cfg.world_size);
+    if (params->iterations < 1 || params->iterations > 8) return rt_fail(RT_ERR_INVALID, "rt_renderer_denoise: iterations must be 1..8, not %u", params->iterations);
+    if (!(params->sigma_depth > 0.0f) || !(params->sigma_lum > 0.0f) || !std::isfinite(params->sigma_depth) || !std::isfinite(params->sigma_lum))
+        return rt_fail(RT_ERR_INVALID, "rt_renderer_denoise: sigma_depth and sigma_lum must be finite and > 0");
+    if (params->demodulate > 1) return rt_fail(RT_ERR_INVALID, "rt_renderer_denoise: demodulate must be 0 or 1");
+    if (!r->aov_on || r->aov_done == 0) return rt_fail(RT_ERR_INVALID, "rt_renderer_denoise: no feature buffers (rt_renderer_aov_enable, then refine)");
+    if (r->refine_done < 2 || !r->accum.p) return rt_fail(RT_ERR_INVALID, "rt_renderer_denoise: a variance needs 2 samples per pixel; %u accumulated", r->refine_done);
+    HIP_TRY(hipSetDevice(r->cfg.device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    const uint32_t n_px = r->cfg.width * r->cfg.height;
+    if (!r->dn_ev) HIP_TRY(hipEventCreate(&r->dn_ev));
+    for (DevBuf* b : {&r->dn_g0, &r->dn_g1, &r->dn_a, &r->dn_b, &r->dn_out})   // each at its first use: a call that failed half-way is simply continued
+        if (!b->p) HIP_TRY(b->alloc((size_t)n_px * sizeof(float4)));
+    HIP_TRY(hipStreamWaitEvent(st, r->refine_ev, 0));                   // the last refine step may have run on another stream
+    if (r->dn_valid) HIP_TRY(hipStreamWaitEvent(st, r->dn_ev, 0));     // ... and so may the last filter, whose buffers this one reuses
+    DenoiseParams dp;
+    dp.width = r->cfg.width; dp.height = r->cfg.height;
+    dp.sigma_depth = params->sigma_depth; dp.sigma_lum = params->sigma_lum; dp.demodulate = params->demodulate;
+    const uint32_t n_local = r->tm.n_local_tiles * RT_TILE * RT_TILE;
+    float4 *src = r->dn_a.as<float4>(), *dst = r->dn_b.as<float4>();
+    denoise_prepare_kernel<<<(n_local + 255u) / 256u, 256, 0, st>>>(r->tm, dp, r->accum.as<float4>(), r->aov.as<float4>(), r->refine_done, r->aov_done,
+                                                                    r->dn_g0.as<float4>(), r->dn_g1.as<float4>(), src);
+    HIP_TRY(hipGetLastError());
+    const dim3 grid((dp.width + RT_DN_TILE - 1u) / RT_DN_TILE, (dp.height + RT_DN_TILE - 1u) / RT_DN_TILE), block(RT_DN_TILE * RT_DN_TILE);
+    for (uint32_t i = 0; i < params->iterations; i++) {
+        if (i == 0) denoise_filter_tile_kernel<1><<<grid, block, 0, st>>>(dp, r->dn_g0.as<float4>(), src, dst);
+        else if (i == 1) denoise_filter_tile_kernel<2><<<grid, block, 0, st>>>(dp, r->dn_g0.as<float4>(), src, dst);
+        else denoise_filter_direct_kernel<<<grid, block, 0, st>>>(dp, 1 << i, r->dn_g0.as<float4>(), src, dst);
+        HIP_TRY(hipGetLastError());
+        std::swap(src, dst);
+    }
+    denoise_final_kernel<<<(n_px + 255u) / 256u, 256, 0, st>>>(dp, r->dn_g1.as<float4>(), src, r->dn_out.as<float4>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(r->dn_ev, st));
+    r->dn_valid = true;
+    return RT_OK;
+}
+
+extern "C" int rt_renderer_denoise(rt_renderer* r, const rt_denoise_params* params) {
+    if (!r || !params) return rt_fail(RT_ERR_INVALID, "rt_renderer_denoise: null argument");
+    int rc = rt_renderer_denoise_async(r, r->stream, params);
+    if (rc != RT_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    return RT_OK;
+}
+
+extern "C" int rt_renderer_denoise_download(rt_renderer* r, float* host_rgba, size_t n_floats) {
+    if (!r || !host_rgba) return rt_fail(RT_ERR_INVALID, "rt_renderer_denoise_download: null argument");
+    const size_t need = (size_t)r->cfg.width * r->cfg.height * 4;
+    if (n_floats != need) return rt_fail(RT_ERR_INVALID, "rt_renderer_denoise_download: buffer holds %zu floats, image needs %zu", n_floats, need);
+    if (!r->dn_valid) return rt_fail(RT_ERR_INVALID, "rt_renderer_denoise_download: nothing denoised yet (rt_renderer_denoise first)");
+    HIP_TRY(hipSetDevice(r->cfg.device));
+    HIP_TRY(hipEventSynchronize(r->dn_ev));
+    HIP_TRY(hipMemcpy(host_rgba, r->dn_out.p, need * sizeof(float), hipMemcpyDeviceToHost));
     return RT_OK;
 }
 

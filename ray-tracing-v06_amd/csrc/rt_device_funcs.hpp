@@ -153,11 +153,30 @@ RT_HD bool node_box(const rt_bvh_node& n, const Ray& ray, float maxd, float& dis
     return aabb_intersects(mk3(n.min[0], n.min[1], n.min[2]), mk3(n.max[0], n.max[1], n.max[2]), ray, maxd, dist);
 }
 
+// Where a traversal keeps its RT_MAX_STACK entries.  OwnStack, the default: the local array `T stack[RT_MAX_STACK]` the traversals always
+// declared — `Local` IS that array type, so every caller but the feature pass compiles to the code it had.  LaneStack: entry i of a lane at
+// base[i * STRIDE], `base` being the lane's own column of a workgroup's LDS array (rt_aov_kernel.hpp): consecutive lanes, consecutive banks.
+// Both are indexed alike, which is all the traversals below ask of `stack`.
+template <class T>
+struct OwnStack {
+    typedef T Local[RT_MAX_STACK];
+    __device__ static __forceinline__ void bind(Local&, OwnStack) {}
+};
+template <class T, int STRIDE>
+struct LaneStack {
+    typedef LaneStack Local;
+    T* base;
+    __device__ static __forceinline__ void bind(Local& l, LaneStack given) { l = given; }
+    __device__ __forceinline__ T& operator[](int i) { return base[i * STRIDE]; }
+};
+
 // BVH::ClosestIntersection, rt_engine/geometry/BVH.cu:54-106 (the live, non-priority-queue branch):
 // root box first; pop; leaf -> primitive; inner -> test BOTH child boxes, order near-first, push far
 // then near iff dist < rec.distance; no re-check at pop.
-__device__ inline bool bvh_closest_intersection(const DeviceWorld& w, const Ray& ray, HitRec& rec, Rng* rng) {
-    int32_t stack[RT_MAX_STACK];
+template <class S = OwnStack<int32_t>>
+__device__ inline bool bvh_closest_intersection(const DeviceWorld& w, const Ray& ray, HitRec& rec, Rng* rng, S given = S()) {
+    typename S::Local stack;
+    S::bind(stack, given);
     int head = 0;
     float root_dist;
     if (!node_box(w.nodes[w.root], ray, rec.distance, root_dist)) return false;
@@ -190,9 +209,12 @@ __device__ inline bool bvh_closest_intersection(const DeviceWorld& w, const Ray&
 // `head++` (:37-39: index and distance end up in different slots); fixed here and in the oracle — same slot, then the
 // insertion sort as written.  Capacity _PRIO_QUEUE_ELEM_COUNT = 32, checked (the reference does not): overflow raises
 // *w.error_flag and ends the walk.  Probes, baseline kernel and the streaming kernel's RT_WORLD_BVH_QUEUE mode (see RT_TRAVERSAL_QUEUE in rt06.h).
-__device__ inline bool bvh_closest_intersection_queue(const DeviceWorld& w, const Ray& ray, HitRec& rec, Rng* rng) {
-    int32_t indices[RT_MAX_STACK];
-    float distances[RT_MAX_STACK];
+template <class SI = OwnStack<int32_t>, class SD = OwnStack<float>>
+__device__ inline bool bvh_closest_intersection_queue(const DeviceWorld& w, const Ray& ray, HitRec& rec, Rng* rng, SI given_i = SI(), SD given_d = SD()) {
+    typename SI::Local indices;
+    typename SD::Local distances;
+    SI::bind(indices, given_i);
+    SD::bind(distances, given_d);
     int head = 0;
     float root_dist;
     if (!node_box(w.nodes[w.root], ray, rec.distance, root_dist)) return false;
@@ -228,8 +250,10 @@ __device__ inline bool bvh_closest_intersection_queue(const DeviceWorld& w, cons
 // rec.distance (BVH.cu:87-88), orders them nearest first (stable, a missed box keeps _MISS_DIST) and pushes them far-to-near iff
 // dist < rec.distance (BVH.cu:95-96).  The oracle's bvh_closest_intersection_wide4, statement by statement.  Overflow of the 32 entries
 // raises *w.error_flag and ends the walk (at most 3 * ceil(depth / 2) + 1 entries are ever needed).
-__device__ inline bool bvh_closest_intersection_wide4(const DeviceWorld& w, const Ray& ray, HitRec& rec, Rng* rng) {
-    int32_t stack[RT_MAX_STACK];
+template <class S = OwnStack<int32_t>>
+__device__ inline bool bvh_closest_intersection_wide4(const DeviceWorld& w, const Ray& ray, HitRec& rec, Rng* rng, S given = S()) {
+    typename S::Local stack;
+    S::bind(stack, given);
     int head = 0;
     float root_dist;
     if (!node_box(w.nodes[w.root], ray, rec.distance, root_dist)) return false;
@@ -280,8 +304,10 @@ __device__ inline bool list_closest_intersection(const DeviceWorld& w, const Ray
 // bvh_node::ClosestIntersection, rt_engine/geometry/bvh_node.cuh:19-24, made iterative: the recursion
 // "own box, then left subtree, then right subtree" is a pre-order walk, i.e. pop / test / push right /
 // push left with the box test at visit time against the current rec.distance.
-__device__ inline bool tree_closest_intersection(const DeviceWorld& w, const Ray& ray, HitRec& rec, Rng* rng) {
-    int32_t stack[RT_MAX_STACK];
+template <class S = OwnStack<int32_t>>
+__device__ inline bool tree_closest_intersection(const DeviceWorld& w, const Ray& ray, HitRec& rec, Rng* rng, S given = S()) {
+    typename S::Local stack;
+    S::bind(stack, given);
     int head = 0;
     stack[head++] = w.root;
     bool hit_any = false;

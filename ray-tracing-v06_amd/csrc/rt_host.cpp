@@ -34,6 +34,16 @@ extern "C" const char* rt_last_error(void) { return g_last_error.c_str(); }
 #ifndef RT06_SRC_SHA256
 #define RT06_SRC_SHA256 "unstamped"
 #endif
+// the documented defaults of the denoiser (rt06.h); host only
+extern "C" int rt_denoise_params_default(rt_denoise_params* out) {
+    if (!out) return rt_fail(RT_ERR_INVALID, "rt_denoise_params_default: null out");
+    out->iterations = 5;
+    out->sigma_depth = 0.05f;
+    out->sigma_lum = 4.0f;
+    out->demodulate = 1;
+    return RT_OK;
+}
+
 extern "C" const char* rt_version(void) { return "rt06-amd 0.3 (gfx950) src " RT06_SRC_SHA256; }
 extern "C" const char* rt_source_hash(void) { return RT06_SRC_SHA256; }
 

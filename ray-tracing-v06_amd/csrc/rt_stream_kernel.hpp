@@ -864,17 +864,21 @@ __device__ __forceinline__ void noise_block_sum(NoiseSums& a, double (*lds)[3]) 
     if (threadIdx.x == 0u)
         for (uint32_t w = 1; w < RT_NOISE_BLOCK / 64u; w++) { a.v += lds[w][0]; a.m += lds[w][1]; a.pixels += lds[w][2]; }
 }
+// m and v of one pixel's accumulation a = (sum R, sum G, sum B, sum Y^2) after n_done samples; the denoiser's prepare step (rt_aov_kernel.hpp) shares it
+__device__ __forceinline__ void mean_luminance_variance(float4 a, uint32_t n_done, float& m, float& v) {
+    const float n = (float)n_done, n1 = (float)(n_done - 1u);
+    m = __fdiv_rn(__fadd_rn(__fadd_rn(__fmul_rn(0.2126f, a.x), __fmul_rn(0.7152f, a.y)), __fmul_rn(0.0722f, a.z)), n);
+    const float d = __fsub_rn(__fdiv_rn(a.w, n), __fmul_rn(m, m));
+    v = __fdiv_rn(d < 0.0f ? 0.0f : d, n1);   // max(0, d) that KEEPS a NaN (inf - inf of an overflowed pixel): fmaxf would turn it into 0
+}
 __global__ __launch_bounds__(RT_NOISE_BLOCK) void refine_noise_kernel(TileMap tm, const float4* __restrict__ acc, uint32_t n_done, NoiseSums* __restrict__ partials) {
     __shared__ double lds[RT_NOISE_BLOCK / 64u][3];
     const uint32_t L = blockIdx.x * RT_NOISE_BLOCK + threadIdx.x;
     NoiseSums s = {0.0, 0.0, 0.0};
     uint32_t gid;
     if (L < tm.n_local_tiles * RT_TILE * RT_TILE && local_pixel_to_gid(tm, L, gid)) {
-        const float4 a = acc[L];
-        const float n = (float)n_done, n1 = (float)(n_done - 1u);
-        const float m = __fdiv_rn(__fadd_rn(__fadd_rn(__fmul_rn(0.2126f, a.x), __fmul_rn(0.7152f, a.y)), __fmul_rn(0.0722f, a.z)), n);
-        const float d = __fsub_rn(__fdiv_rn(a.w, n), __fmul_rn(m, m));
-        const float v = __fdiv_rn(d < 0.0f ? 0.0f : d, n1);   // max(0, d) that KEEPS a NaN (inf - inf of an overflowed pixel): fmaxf would turn it into 0
+        float m, v;
+        mean_luminance_variance(acc[L], n_done, m, v);
         if (isfinite(m) && isfinite(v)) { s.v = (double)v; s.m = (double)m; s.pixels = 1.0; }
     }
     noise_block_sum(s, lds);

@@ -11,6 +11,12 @@ three_spheres (PinholeCamera vfov 90).  Prints one JSON line with the render tim
 renders progressively (rt_renderer_refine): steps of 50 samples up to --spp, one line per step with the samples so far and the noise
 figure (relative RMS standard error of the frame's mean luminance), stopping early once it is below --until.  The image written is the
 last refined frame: bit for bit the frame a one-shot render at that sample count gives.
+
+    python tools/render.py --scene cornell_box --spp 64 --refine 8 --until 0.05 --denoise --aov feat --out out.png
+
+also accumulates first-hit feature buffers (rt_renderer_aov_enable) while refining.  --denoise writes the edge-aware filtered frame
+(rt_renderer_denoise) next to the refined one, as out_denoised.png; --aov PREFIX writes PREFIX_normal.png (n * 0.5 + 0.5),
+PREFIX_depth.png (nearest white, misses black) and PREFIX_albedo.png.  One GPU; worlds with media, noise or image textures are refused.
 """
 import argparse, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -27,10 +33,14 @@ ap.add_argument("--device", type=int, default=0)
 ap.add_argument("--gpus", type=int, default=1, help="> 1: tile-shard the frame over GPUs 0..N-1 of this node from this one process (rt_multi_renderer_*, one RCCL exchange)")
 ap.add_argument("--refine", type=int, default=0, metavar="STEP", help="render in steps of STEP samples up to --spp, printing samples and noise per step")
 ap.add_argument("--until", type=float, default=None, metavar="NOISE", help="with --refine: stop once the noise figure is below NOISE (one GPU)")
+ap.add_argument("--denoise", action="store_true", help="with --refine: also write the denoised frame (<out>_denoised.<ext>)")
+ap.add_argument("--aov", default=None, metavar="PREFIX", help="with --refine: write PREFIX_normal.png, PREFIX_depth.png, PREFIX_albedo.png")
 ap.add_argument("--out", default="render.png")
 a = ap.parse_args()
 if a.refine < 0 or (a.until is not None and (a.refine == 0 or a.gpus > 1)):
     ap.error("--until needs --refine STEP > 0 and one GPU (the multi-GPU renderer has no noise figure)")
+if (a.denoise or a.aov) and (a.refine == 0 or a.gpus > 1):
+    ap.error("--denoise and --aov need --refine STEP > 0 and one GPU (feature buffers accumulate alongside refinement)")
 p = G.load_package()
 from ray_tracing_v06_amd import image_io
 W, H = a.width, a.height
@@ -50,6 +60,8 @@ if a.refine:
     step_spp = min(a.refine, a.spp)   # what one pass is sized for; the steps go on to --spp
     r = (p.MultiRenderer.MakeRenderer(W, H, step_spp, a.depth, cam, scene.getWorldPtr(), a.gpus, seed=a.seed) if a.gpus > 1
          else p.Renderer.MakeRenderer(W, H, step_spp, a.depth, cam, scene.getWorldPtr(), seed=a.seed, device=a.device))
+    if a.denoise or a.aov:
+        r.enable_aov()
     samples, ms = 0, 0.0
     while samples < a.spp:
         n = min(a.refine, a.spp - samples)
@@ -71,6 +83,26 @@ else:
     ms = r.last_kernel_ms()
 fb = r.DownloadRenderbuffer()
 # .jpg = the reference app's own format (stbi_write_jpg quality 95, FirstApp.cpp:120); .ppm / .png are lossless
-(image_io.write_ppm if a.out.endswith(".ppm") else image_io.write_jpg if a.out.endswith((".jpg", ".jpeg")) else image_io.write_png)(a.out, fb)
-print(json.dumps({"scene": a.scene, "width": W, "height": H, "spp": samples, "max_depth": a.depth, "render_ms": round(ms, 3),
+writer = image_io.write_ppm if a.out.endswith(".ppm") else image_io.write_jpg if a.out.endswith((".jpg", ".jpeg")) else image_io.write_png
+writer(a.out, fb)
+extra = {}
+if a.denoise:   # (with --refine only: `time` is imported there)
+    t0 = time.perf_counter()
+    den = r.denoise()
+    stem, ext = os.path.splitext(a.out)
+    extra["denoised"] = stem + "_denoised" + ext
+    extra["denoise_ms"] = round((time.perf_counter() - t0) * 1e3, 3)   # filter + download, host wall-clock
+    writer(extra["denoised"], den)
+if a.aov:
+    import numpy as np
+    f = r.aov()
+    one = np.ones((H, W, 1), dtype=np.float32)
+    near = f["depth"][f["coverage"] > 0]
+    scale = np.float32(near.min()) if near.size else np.float32(1.0)
+    depth = np.where(f["coverage"] > 0, scale / np.maximum(f["depth"], scale), np.float32(0.0)).astype(np.float32)
+    image_io.write_png(a.aov + "_normal.png", np.concatenate([f["normal"] * np.float32(0.5) + np.float32(0.5), one], axis=2))
+    image_io.write_png(a.aov + "_depth.png", np.concatenate([np.repeat(depth[..., None], 3, axis=2), one], axis=2))
+    image_io.write_png(a.aov + "_albedo.png", np.concatenate([f["albedo"], one], axis=2))
+    extra["aov"] = [a.aov + s for s in ("_normal.png", "_depth.png", "_albedo.png")]
+print(json.dumps({**extra, "scene": a.scene, "width": W, "height": H, "spp": samples, "max_depth": a.depth, "render_ms": round(ms, 3),
                   "msamples_per_s": round(W * H * samples / ms / 1e3, 1), "gpus": a.gpus, "out": a.out}))
