@@ -1,4 +1,5 @@
 // rt_device.hip — the device half of the C ABI: Renderer (kernel selection, passes, launches, per-kernel timers), shard layout, assembly.
+// Which streaming kernel a world gets: stream_kernel_key() and stream_kernel_for().  How much LDS it gets: stream_kernel_lds_bytes() (rt_runtime.hpp).
 // Probes and self-tests: rt_probes.hip.  Multi-GPU driver: rt_multi.hip.
 #include "rt_runtime.hpp"
 #include "rt_render_kernels.hpp"
@@ -22,14 +23,14 @@ extern "C" int rt_device_info(int device, uint32_t out[4]) {
 extern "C" int rt_shard_layout(uint32_t width, uint32_t height, uint32_t world_size, uint32_t out[4]) {
     if (!out || width == 0 || height == 0 || world_size == 0) return rt_fail(RT_ERR_INVALID, "rt_shard_layout: bad argument");
     const TileMap tm = make_tile_map(width, height, 0, world_size);
-    out[0] = tm.tiles_x; out[1] = tm.n_tiles; out[2] = tm.n_local_tiles; out[3] = tm.n_local_tiles * RT_TILE * RT_TILE * 4u;
+    out[0] = tm.tiles_x; out[1] = tm.n_tiles; out[2] = tm.n_local_tiles; out[3] = (uint32_t)n_local_pixels(tm) * 4u;
     return RT_OK;
 }
 
 extern "C" int rt_shard_pixel_map(uint32_t width, uint32_t height, uint32_t world_size, uint32_t rank, uint32_t* out_gid, size_t n) {
     if (!out_gid || width == 0 || height == 0 || world_size == 0 || rank >= world_size) return rt_fail(RT_ERR_INVALID, "rt_shard_pixel_map: bad argument");
     const TileMap tm = make_tile_map(width, height, rank, world_size);
-    if (n != (size_t)tm.n_local_tiles * RT_TILE * RT_TILE) return rt_fail(RT_ERR_INVALID, "rt_shard_pixel_map: a shard has %u pixels", tm.n_local_tiles * RT_TILE * RT_TILE);
+    if (n != n_local_pixels(tm)) return rt_fail(RT_ERR_INVALID, "rt_shard_pixel_map: a shard has %u pixels", (uint32_t)n_local_pixels(tm));
     for (uint32_t L = 0; L < (uint32_t)n; L++) {   // the host statement of local_pixel_to_gid (csrc/rt_render_kernels.hpp)
         const uint32_t tl = L / (RT_TILE * RT_TILE), p = L % (RT_TILE * RT_TILE);
         const uint32_t gt = tl * world_size + rank;
@@ -47,6 +48,60 @@ extern "C" int rt_device_count(int* out) {
     return RT_OK;
 }
 
+// Kernel selection.  One instantiation, as a key: the template arguments of render_kernel_stream<exact, filter, RT_STREAM_BLOCK, world, ext, big, wide, tol>, or render_kernel_xchg<RT_XCHG_BLOCK>
+constexpr uint32_t stream_key(bool exact, bool filter, int world, int ext = 0, bool big = false, bool wide = false, bool tol = false) {
+    return (uint32_t)exact | (uint32_t)filter << 1 | (uint32_t)world << 2 | (uint32_t)ext << 4 | (uint32_t)big << 6 | (uint32_t)wide << 7 | (uint32_t)tol << 8;
+}
+constexpr uint32_t RT_KEY_XCHG = 1u << 9;
+
+// The kernel of a renderer: variant = the resolved one (2 verbatim box tests, 3 fast exact division, 4 filtered predicates, 5 ray exchange), tol = requested
+// as variant 6.  rt_renderer::resolve_variant() has refused what has no kernel (3 and 4 on lists and trees, 4 to 6 beyond the LDS or the reference's feature set).
+static uint32_t stream_kernel_key(uint32_t variant, bool tol, const DeviceScene& s) {
+    if (variant == 5) return RT_KEY_XCHG;
+    const bool exact = variant != 3;   // of the BVH kernels; lists and node trees have no box-pair test to speed up
+    const int ext = s.textured ? 2 : 1;
+    // the distance-sorted queue / the 4-wide walk: one instantiation per feature level, records in global memory, 32-bit references
+    if (s.queue) return stream_key(true, false, RT_WORLD_BVH_QUEUE, s.textured || s.extended ? ext : 0, true, true);
+    if (s.big) {   // records in global memory; lists and BVHs in the EXT forms only
+        if (s.dw.kind == RT_WORLD_LIST) return stream_key(true, false, RT_WORLD_LIST, ext, true, true);
+        if (s.dw.kind == RT_WORLD_NODE_TREE) return stream_key(true, false, RT_WORLD_NODE_TREE, 0, true, true);
+        return stream_key(exact, false, RT_WORLD_BVH, ext, true, s.wide);
+    }
+    if (s.extended) return s.dw.kind == RT_WORLD_LIST ? stream_key(true, false, RT_WORLD_LIST, ext) : stream_key(exact, false, RT_WORLD_BVH, ext);
+    if (s.dw.kind != RT_WORLD_BVH) return stream_key(true, false, (int)s.dw.kind);
+    if (tol) return stream_key(false, false, RT_WORLD_BVH, 0, false, false, true);
+    return stream_key(variant == 2, variant == 4, RT_WORLD_BVH);
+}
+
+// Every shipped instantiation, once, a family per line, in the order the code object has them (a key listed twice does not compile).
+// stream_kernel_key() yields no other key, so the default is never taken.
+static const void* stream_kernel_for(uint32_t key) {
+#define RT_KERNEL(exact, filter, world, ext, big, wide, tol) \
+    case stream_key(exact, filter, world, ext, big, wide, tol): return reinterpret_cast<const void*>(&render_kernel_stream<exact, filter, RT_STREAM_BLOCK, world, ext, big, wide, tol>)
+    switch (key) {   // arguments: exact, filter, world, ext, big, wide, tol
+        case RT_KEY_XCHG: return reinterpret_cast<const void*>(&render_kernel_xchg<RT_XCHG_BLOCK>);
+        RT_KERNEL(true, false, RT_WORLD_BVH_QUEUE, 2, true, true, false); RT_KERNEL(true, false, RT_WORLD_BVH_QUEUE, 1, true, true, false); RT_KERNEL(true, false, RT_WORLD_BVH_QUEUE, 0, true, true, false);
+        RT_KERNEL(true, false, RT_WORLD_LIST, 2, true, true, false); RT_KERNEL(true, false, RT_WORLD_LIST, 1, true, true, false); RT_KERNEL(true, false, RT_WORLD_NODE_TREE, 0, true, true, false);
+        RT_KERNEL(false, false, RT_WORLD_BVH, 2, true, true, false); RT_KERNEL(true, false, RT_WORLD_BVH, 2, true, true, false); RT_KERNEL(false, false, RT_WORLD_BVH, 1, true, true, false); RT_KERNEL(true, false, RT_WORLD_BVH, 1, true, true, false);
+        RT_KERNEL(false, false, RT_WORLD_BVH, 2, true, false, false); RT_KERNEL(true, false, RT_WORLD_BVH, 2, true, false, false); RT_KERNEL(false, false, RT_WORLD_BVH, 1, true, false, false); RT_KERNEL(true, false, RT_WORLD_BVH, 1, true, false, false);
+        RT_KERNEL(true, false, RT_WORLD_LIST, 2, false, false, false); RT_KERNEL(true, false, RT_WORLD_LIST, 1, false, false, false);
+        RT_KERNEL(false, false, RT_WORLD_BVH, 2, false, false, false); RT_KERNEL(true, false, RT_WORLD_BVH, 2, false, false, false); RT_KERNEL(false, false, RT_WORLD_BVH, 1, false, false, false); RT_KERNEL(true, false, RT_WORLD_BVH, 1, false, false, false);
+        RT_KERNEL(true, false, RT_WORLD_LIST, 0, false, false, false); RT_KERNEL(true, false, RT_WORLD_NODE_TREE, 0, false, false, false);
+        RT_KERNEL(false, false, RT_WORLD_BVH, 0, false, false, true); RT_KERNEL(true, false, RT_WORLD_BVH, 0, false, false, false); RT_KERNEL(false, true, RT_WORLD_BVH, 0, false, false, false); RT_KERNEL(false, false, RT_WORLD_BVH, 0, false, false, false);
+        default: return nullptr;
+    }
+#undef RT_KERNEL
+}
+
+// the feature pass's kernel: the world's own traversal, so that a kernel carries one traversal stack
+static decltype(&aov_kernel<RT_AOV_WALK_STACK>) aov_kernel_for(const DeviceWorld& w) {
+    if (w.kind == RT_WORLD_LIST) return &aov_kernel<RT_AOV_WALK_LIST>;
+    if (w.kind == RT_WORLD_NODE_TREE) return &aov_kernel<RT_AOV_WALK_TREE>;
+    if (w.traversal == RT_TRAVERSAL_QUEUE) return &aov_kernel<RT_AOV_WALK_QUEUE>;
+    if (w.traversal == RT_TRAVERSAL_WIDE4) return &aov_kernel<RT_AOV_WALK_WIDE4>;
+    return &aov_kernel<RT_AOV_WALK_STACK>;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Renderer
 // ---------------------------------------------------------------------------------------------
@@ -61,7 +116,7 @@ struct rt_renderer {
     // primary rays of one pass: 3 arrays of 16 B per sample index (origin|time, direction, RNG state).  Generated on the render's
     // own stream, before the streaming kernel: generating pass k + 1 on a second stream WHILE pass k is traced was measured and is
     // harmful (the persistent kernel ran 40 % slower with the generator's waves co-resident: 100 ms instead of 70).
-    DevBuf primary[1];
+    DevBuf primary;
     uint32_t pass_spp = 0;       // samples per pixel per pass
     uint32_t n_cus = 0;
     uint32_t stream_lds_bytes = 0;
@@ -69,12 +124,12 @@ struct rt_renderer {
     uint32_t stream_block = RT_STREAM_BLOCK;
     uint32_t stream_blocks_per_cu = 0;
     uint32_t variant = 0;        // resolved kernel variant (see rt_render_config::variant)
+    const void* stream_kernel = nullptr;   // variants 2 to 6: what stream_kernel_for() gave for this world
     bool tol = false;            // variant 3 with the tolerance-mode box test (requested as variant 6)
     uint32_t tune[3] = {RT_INNER_KEEP, RT_SHADE_MIN, RT_LEAF_MIN};  // scheduling thresholds of the streaming kernel
     // render_kernel_xchg (variant 5): roles, ring capacities, population and thresholds (RT06_XCHG=tracers,extra,swap,shade,patience,prio)
     struct { uint32_t n_tracers = 9, tq_cap = 0, sq_cap = 0, pop_extra = 192, swap_min = 16, shade_min = 48, patience = 6, prio = 1, scene_vec4 = 0, extra_in_lds = 0, keep = 44, shards = 1; } xc;
     DevBuf xchg_error;           // set by the kernel when a bounded ring wait ran out (a protocol bug, never expected)
-    size_t shard_floats = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
@@ -105,39 +160,56 @@ struct rt_renderer {
     bool dn_valid = false;
     static constexpr uint32_t SAMPLE_BYTES = RT_SAMPLE_BYTES, PRIMARY_BYTES = 48;   // HBM per sample index of a pass: radiance (float4) + primary ray record
 
-    // Pick the kernel variant and size the per-pass sample buffer.
+    // Pick the kernel variant; size the LDS, the exchange rings and the per-pass sample buffer.
     //   0 = default (the fastest validated variant), 1 = baseline wave-per-pixel kernel,
     //   2 = streaming kernel with verbatim box tests, 3 = streaming kernel with the fast exact division,
-    //   4 = 3 + filtered box-pair predicates (experimental).
+    //   4 = 3 + filtered box-pair predicates (experimental), 5 = ray exchange, 6 = 3 with the tolerance-mode box test.
     int plan() {
         hipDeviceProp_t prop;
         HIP_TRY(hipGetDeviceProperties(&prop, cfg.device));
         n_cus = (uint32_t)prop.multiProcessorCount;
-        const uint32_t lds_per_cu = 160u * 1024u;  // MI355X_MICROARCH.md: 160 KiB LDS per CU
+        if (const int rc = resolve_variant(size_stream_lds())) return rc;
+        if (variant == 5)
+            if (const int rc = size_xchg_rings()) return rc;
+        if (const char* env = std::getenv("RT06_TUNE")) {  // "keep,shade,leaf" — scheduling experiments only; results never change
+            unsigned a = 0, b = 0, c = 0;
+            if (std::sscanf(env, "%u,%u,%u", &a, &b, &c) == 3 && a >= 1 && a <= 64 && b >= 1 && b <= 64 && c >= 1 && c <= 64) {
+                tune[0] = a; tune[1] = b; tune[2] = c;
+            }
+        }
+        if (variant < 2) return RT_OK;
+        if (const int rc = size_passes()) return rc;
+        stream_kernel = stream_kernel_for(stream_kernel_key(variant, tol, scene));
+        HIP_TRY(hipFuncSetAttribute(stream_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)stream_lds_bytes));
+        if (std::getenv("RT06_DEBUG")) {
+            int occ = -1;
+            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, stream_kernel, (int)stream_block, stream_lds_bytes);
+            fprintf(stderr, "[rt06] stream kernel: block %u, LDS %u B, planned %u blocks/CU, runtime occupancy query %d blocks/CU\n",
+                    stream_block, stream_lds_bytes, stream_blocks_per_cu, occ);
+        }
+        return RT_OK;
+    }
+    // LDS of a render_kernel_stream workgroup (RT_STREAM_BLOCK lanes in every instantiation, so the variant can be chosen knowing it); false = the world cannot stream
+    bool size_stream_lds() {
+        if (!scene.has_packed) return false;
+        if (scene.big) {  // beside the per-lane stacks, in what two workgroups per CU leave free: the top of the tree
+            const uint32_t node_bytes = RT_NODE_DWORDS_BIG * 4u, stacks = (uint32_t)stream_kernel_lds_bytes(stream_block, scene.packed, true, scene.wide, 0u);
+            const uint32_t budget = stacks + 4096u <= RT_LDS_PER_CU / 2u ? RT_LDS_PER_CU / 2u : RT_LDS_PER_CU;
+            uint32_t top_bytes = std::min((budget > stacks ? budget - stacks : 0u) & ~63u, scene.packed.n_inner * node_bytes);
+            if (const char* env = std::getenv("RT06_TOP_NODES")) top_bytes = std::min(top_bytes, (uint32_t)std::atoi(env) * node_bytes);
+            if (scene.queue) top_bytes = 0;   // the queue walk reads the flat world's own nodes
+            n_top = top_bytes / node_bytes;
+        }
+        stream_lds_bytes = (uint32_t)stream_kernel_lds_bytes(stream_block, scene.packed, scene.big, scene.wide, n_top);
+        if (stream_lds_bytes <= RT_LDS_PER_CU) stream_blocks_per_cu = std::min(2u, RT_LDS_PER_CU / stream_lds_bytes);
+        return stream_lds_bytes <= RT_LDS_PER_CU;
+    }
+    // cfg.variant -> variant and tol, or the refusal of a world the requested kernel cannot take
+    int resolve_variant(bool can_stream) {
         uint32_t want = cfg.variant;
         if (want > 6) return rt_fail(RT_ERR_INVALID, "unknown kernel variant %u", want);
         const bool want_tol = want == 6;   // variant 6: variant 3 with the tolerance-mode box test (opt-in; inside |delta| < 1e-3, not bit-exact by construction)
         if (want_tol) want = 3;
-        bool can_stream = scene.has_packed;
-        if (can_stream) {
-            stream_block = RT_STREAM_BLOCK;
-            if (scene.big) {  // the per-lane stacks (32-bit entries) and, in what two workgroups per CU leave free, the top of the tree
-                stream_block = RT_STREAM_BLOCK;
-                const uint32_t stacks = (stream_block * scene.packed.stack_cap * (scene.wide ? 4u : 2u) + 63u) & ~63u;
-                const uint32_t budget = stacks + 4096u <= lds_per_cu / 2u ? lds_per_cu / 2u : lds_per_cu;
-                uint32_t top_bytes = budget > stacks ? budget - stacks : 0u;
-                top_bytes = std::min(top_bytes & ~63u, scene.packed.n_inner * (RT_NODE_DWORDS_BIG * 4u));
-                if (const char* env = std::getenv("RT06_TOP_NODES")) top_bytes = std::min(top_bytes, (uint32_t)std::atoi(env) * (RT_NODE_DWORDS_BIG * 4u));
-                if (scene.queue) top_bytes = 0;   // the queue walk reads the flat world's own nodes
-                n_top = top_bytes / (RT_NODE_DWORDS_BIG * 4u);
-                stream_lds_bytes = top_bytes + stacks;
-            } else {
-                stream_lds_bytes = scene.packed.blob_vec4 * 16u + stream_block * scene.packed.stack_cap * 2u;
-                stream_lds_bytes = (stream_lds_bytes + 15u) & ~15u;
-            }
-            if (stream_lds_bytes > lds_per_cu) can_stream = false;
-            else stream_blocks_per_cu = std::min(2u, lds_per_cu / stream_lds_bytes);
-        }
         const bool can_xchg = can_stream && !scene.big && !scene.extended && scene.dw.kind == RT_WORLD_BVH && scene.regular_boxes && !scene.queue;
         if (scene.queue && want >= 3)
             return rt_fail(RT_ERR_INVALID, "kernel variants 3 to 5 walk the tree with the stack of BVH.cu:54-106: a world with another traversal rule (RT_TRAVERSAL_QUEUE, RT_TRAVERSAL_WIDE4) renders on variant 2 (or 0) and on the baseline kernel (1)");
@@ -167,137 +239,80 @@ struct rt_renderer {
                 return rt_fail(RT_ERR_INVALID, "kernel variant 6 (tolerance-mode box test) is instantiated for LDS-resident RT_WORLD_BVH worlds of the reference's feature set only (spheres, the three scattering materials, the sky): use variant 0");
             tol = true;
         }
-        if (variant == 5) {
-            // LDS of a workgroup (two per CU): nodes | spheres | (second centres when a sphere moves) | tracer stacks | rings
-            stream_block = RT_XCHG_BLOCK;
-            if (const char* env = std::getenv("RT06_XCHG")) {
-                unsigned v[8] = {xc.n_tracers, xc.pop_extra, xc.swap_min, xc.shade_min, xc.patience, xc.prio, xc.keep, xc.shards};
-                const int n = std::sscanf(env, "%u,%u,%u,%u,%u,%u,%u,%u", &v[0], &v[1], &v[2], &v[3], &v[4], &v[5], &v[6], &v[7]);
-                if (n >= 1 && v[0] >= 1 && v[0] <= RT_XCHG_BLOCK / 64 - 1) xc.n_tracers = v[0];
-                if (n >= 2 && v[1] <= 1024) xc.pop_extra = v[1];
-                if (n >= 3 && v[2] >= 1 && v[2] <= 64) xc.swap_min = v[2];
-                if (n >= 4 && v[3] >= 1 && v[3] <= 64) xc.shade_min = v[3];
-                if (n >= 5 && v[4] <= 1000) xc.patience = v[4];
-                if (n >= 6) xc.prio = v[5] ? 1u : 0u;
-                if (n >= 7 && v[6] >= 1 && v[6] <= 64) xc.keep = v[6];
-                if (n >= 8 && (v[7] == 1 || v[7] == 2)) xc.shards = v[7];
-            }
-            if (xc.shards > xc.n_tracers || xc.shards > RT_XCHG_BLOCK / 64 - xc.n_tracers) xc.shards = 1;   // every shard needs a tracer and a shader
-            xc.extra_in_lds = scene.any_moving ? 1u : 0u;
-            xc.scene_vec4 = scene.any_moving ? scene.packed.off_mats : scene.packed.off_extra;
-            const uint32_t fixed = xc.scene_vec4 * 16u + ((xc.n_tracers * 64u * scene.packed.stack_cap * 2u + 15u) & ~15u) + xc.shards * XC_WORDS * 4u;
-            static const uint32_t caps[][2] = {{128, 128}, {64, 128}, {64, 64}, {32, 64}, {32, 32}, {16, 32}, {16, 16}};   // per workgroup: divided by the shards
-            xc.tq_cap = 0;
-            for (const auto& c : caps) {
-                const uint32_t total = fixed + c[0] * (4u + XC_TQ_ENTRY_BYTES) + c[1] * (4u + XC_SQ_ENTRY_BYTES);
-                if (total <= lds_per_cu / 2u && c[0] / xc.shards >= 16u) { xc.tq_cap = c[0] / xc.shards; xc.sq_cap = c[1] / xc.shards; stream_lds_bytes = (total + 15u) & ~15u; break; }
-            }
-            if (xc.tq_cap == 0) {
-                if (cfg.variant == 5) return rt_fail(RT_ERR_INVALID, "kernel variant 5: the scene image leaves no room for the ray rings in the LDS");
-                variant = 3;   // chosen by default only: fall back to the streaming kernel
-            } else {
-                stream_blocks_per_cu = 2;
-                // the population must stay below what the places that can hold a ray add up to (no full-ring deadlock)
-                xc.pop_extra = std::min(xc.pop_extra, xc.shards * (xc.tq_cap + xc.sq_cap - 16u));
-                const size_t err_bytes = 64u + (size_t)n_cus * 2u * (RT_XCHG_BLOCK / 64u) * RT_XCHG_DEBUG_WORDS * 4u;
-                HIP_TRY(xchg_error.alloc(err_bytes));
-                HIP_TRY(hipMemset(xchg_error.p, 0, err_bytes));
-            }
-        }
-        if ((variant == 2 || variant == 4) && !scene.big) {
-            stream_block = 768;
-            stream_lds_bytes = (scene.packed.blob_vec4 * 16u + stream_block * scene.packed.stack_cap * 2u + 15u) & ~15u;
-            stream_blocks_per_cu = std::min(2u, lds_per_cu / stream_lds_bytes);
-        }
-        if (const char* env = std::getenv("RT06_TUNE")) {  // "keep,shade,leaf" — scheduling experiments only; results never change
-            unsigned a = 0, b = 0, c = 0;
-            if (std::sscanf(env, "%u,%u,%u", &a, &b, &c) == 3 && a >= 1 && a <= 64 && b >= 1 && b <= 64 && c >= 1 && c <= 64) {
-                tune[0] = a; tune[1] = b; tune[2] = c;
-            }
-        }
-        if (variant >= 2) {
-            // HBM of one pass: every sample index owns SAMPLE_BYTES of radiance + PRIMARY_BYTES of primary-ray record.  The default
-            // budget — 120 GiB of the 288, but never more than 45 % of what is free on the device right now, so that two renderers of a
-            // big frame can live side by side — gives the 1200x800x500 headline one pass (28.8 GB) and a 3840x2160 frame 258 spp per
-            // pass (40 GiB, round 2's default, gave 86: 117 passes instead of 39 for 10 000 spp cost 1.1 % in per-pass tails).
-            uint64_t budget = 120ull << 30;
-            {
-                size_t free_b = 0, total_b = 0;
-                if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > 0) budget = std::min<uint64_t>(budget, (uint64_t)free_b / 100u * 45u);
-            }
-            const uint64_t per_sample = SAMPLE_BYTES + PRIMARY_BYTES;
-            if (const char* env = std::getenv("RT06_PASS_BUDGET_BYTES")) {  // bytes of ALL per-sample buffers of a pass
-                unsigned long long v = std::strtoull(env, nullptr, 10);
-                if (v >= per_sample) budget = v;
-            }
-            uint64_t n_local_pixels = (uint64_t)tm.n_local_tiles * RT_TILE * RT_TILE;
-            uint64_t max_spp = std::max<uint64_t>(1, budget / (n_local_pixels * per_sample));
-            if (const char* env = std::getenv("RT06_PASS_SPP")) {  // tests force multi-pass rendering with this
-                unsigned long long v = std::strtoull(env, nullptr, 10);
-                if (v >= 1) max_spp = v;
-            }
-            max_spp = std::min<uint64_t>(max_spp, (0xF0000000ull - 1) / n_local_pixels);   // sample indices of a pass are 32 bits wide
-            if (max_spp == 0) return rt_fail(RT_ERR_INVALID, "image too large for one pass");
-            pass_spp = (uint32_t)std::min<uint64_t>(cfg.samples_per_pixel, max_spp);
-            for (;;) {   // a device that cannot give the pass its buffers gets smaller passes, not an error: halve until they fit
-                hipError_t e = samples.alloc((size_t)(n_local_pixels * pass_spp * SAMPLE_BYTES));
-                if (e == hipSuccess) e = primary[0].alloc((size_t)(n_local_pixels * pass_spp * PRIMARY_BYTES));
-                if (e == hipSuccess) break;
-                (void)hipGetLastError();   // (clears the sticky out-of-memory status)
-                samples.release(); primary[0].release();
-                if (e != hipErrorOutOfMemory || pass_spp == 1u)
-                    return rt_fail(RT_ERR_HIP, "per-pass buffers (%llu bytes per sample index x %llu sample indices): %s", (unsigned long long)per_sample,
-                                   (unsigned long long)(n_local_pixels * pass_spp), hipGetErrorString(e));
-                pass_spp = (pass_spp + 1u) / 2u;
-            }
-            n_passes = (cfg.samples_per_pixel + pass_spp - 1) / pass_spp;
-            if (n_passes > 1) HIP_TRY(running.alloc((size_t)(n_local_pixels * 16ull)));
-            HIP_TRY(hipFuncSetAttribute(stream_kernel_ptr(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)stream_lds_bytes));
-            if (std::getenv("RT06_DEBUG")) {
-                int occ = -1;
-                (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, stream_kernel_ptr(), (int)stream_block, stream_lds_bytes);
-                fprintf(stderr, "[rt06] stream kernel: block %u, LDS %u B, planned %u blocks/CU, runtime occupancy query %d blocks/CU\n",
-                        stream_block, stream_lds_bytes, stream_blocks_per_cu, occ);
-            }
-        }
         return RT_OK;
     }
-
-    const void* stream_kernel_ptr() const {
-        if (variant == 5) return reinterpret_cast<const void*>(&render_kernel_xchg<RT_XCHG_BLOCK>);
-        const bool fast = variant == 3;
-        if (scene.queue) {   // the distance-sorted queue / the 4-wide walk: one instantiation per feature level, records in global memory, 32-bit references
-            if (scene.textured) return reinterpret_cast<const void*>(&render_kernel_stream<true, false, 768, RT_WORLD_BVH_QUEUE, 2, true, true>);
-            if (scene.extended) return reinterpret_cast<const void*>(&render_kernel_stream<true, false, 768, RT_WORLD_BVH_QUEUE, 1, true, true>);
-            return reinterpret_cast<const void*>(&render_kernel_stream<true, false, 768, RT_WORLD_BVH_QUEUE, 0, true, true>);
+    // render_kernel_xchg: the largest ring pair that fits beside the scene in half a CU's LDS (two workgroups per CU); when none does, the default
+    // falls back to variant 3.  LDS of a workgroup: nodes | spheres | (second centres when a sphere moves) | tracer stacks | rings
+    int size_xchg_rings() {
+        if (const char* env = std::getenv("RT06_XCHG")) {
+            unsigned v[8] = {xc.n_tracers, xc.pop_extra, xc.swap_min, xc.shade_min, xc.patience, xc.prio, xc.keep, xc.shards};
+            const int n = std::sscanf(env, "%u,%u,%u,%u,%u,%u,%u,%u", &v[0], &v[1], &v[2], &v[3], &v[4], &v[5], &v[6], &v[7]);
+            if (n >= 1 && v[0] >= 1 && v[0] <= RT_XCHG_BLOCK / 64 - 1) xc.n_tracers = v[0];
+            if (n >= 2 && v[1] <= 1024) xc.pop_extra = v[1];
+            if (n >= 3 && v[2] >= 1 && v[2] <= 64) xc.swap_min = v[2];
+            if (n >= 4 && v[3] >= 1 && v[3] <= 64) xc.shade_min = v[3];
+            if (n >= 5 && v[4] <= 1000) xc.patience = v[4];
+            if (n >= 6) xc.prio = v[5] ? 1u : 0u;
+            if (n >= 7 && v[6] >= 1 && v[6] <= 64) xc.keep = v[6];
+            if (n >= 8 && (v[7] == 1 || v[7] == 2)) xc.shards = v[7];
         }
-        if (scene.big) {   // records in global memory: <EXACT, FILTER, BLOCK, WORLD, EXT, BIG = true, WIDE>
-#define RT_BIG_KERNEL(exact, world, ext, wide_) reinterpret_cast<const void*>(&render_kernel_stream<exact, false, 768, world, ext, true, wide_>)
-            if (scene.dw.kind == RT_WORLD_LIST) return scene.textured ? RT_BIG_KERNEL(true, RT_WORLD_LIST, 2, true) : RT_BIG_KERNEL(true, RT_WORLD_LIST, 1, true);
-            if (scene.dw.kind == RT_WORLD_NODE_TREE) return RT_BIG_KERNEL(true, RT_WORLD_NODE_TREE, 0, true);
-            if (scene.wide) {
-                if (scene.textured) return fast ? RT_BIG_KERNEL(false, RT_WORLD_BVH, 2, true) : RT_BIG_KERNEL(true, RT_WORLD_BVH, 2, true);
-                return fast ? RT_BIG_KERNEL(false, RT_WORLD_BVH, 1, true) : RT_BIG_KERNEL(true, RT_WORLD_BVH, 1, true);
-            }
-            if (scene.textured) return fast ? RT_BIG_KERNEL(false, RT_WORLD_BVH, 2, false) : RT_BIG_KERNEL(true, RT_WORLD_BVH, 2, false);
-            return fast ? RT_BIG_KERNEL(false, RT_WORLD_BVH, 1, false) : RT_BIG_KERNEL(true, RT_WORLD_BVH, 1, false);
-#undef RT_BIG_KERNEL
+        if (xc.shards > xc.n_tracers || xc.shards > RT_XCHG_BLOCK / 64 - xc.n_tracers) xc.shards = 1;   // every shard needs a tracer and a shader
+        xc.extra_in_lds = scene.any_moving ? 1u : 0u;
+        xc.scene_vec4 = scene.any_moving ? scene.packed.off_mats : scene.packed.off_extra;
+        const uint32_t fixed = xc.scene_vec4 * 16u + ((xc.n_tracers * 64u * scene.packed.stack_cap * 2u + 15u) & ~15u) + xc.shards * XC_WORDS * 4u;
+        static const uint32_t caps[][2] = {{128, 128}, {64, 128}, {64, 64}, {32, 64}, {32, 32}, {16, 32}, {16, 16}};   // per workgroup: divided by the shards
+        for (const auto& c : caps) {
+            const uint32_t total = fixed + c[0] * (4u + XC_TQ_ENTRY_BYTES) + c[1] * (4u + XC_SQ_ENTRY_BYTES);
+            if (total > RT_LDS_PER_CU / 2u || c[0] / xc.shards < 16u) continue;
+            xc.tq_cap = c[0] / xc.shards; xc.sq_cap = c[1] / xc.shards;
+            // the population must stay below what the places that can hold a ray add up to (no full-ring deadlock)
+            xc.pop_extra = std::min(xc.pop_extra, xc.shards * (xc.tq_cap + xc.sq_cap - 16u));
+            stream_block = RT_XCHG_BLOCK;
+            stream_lds_bytes = (total + 15u) & ~15u;
+            stream_blocks_per_cu = 2;
+            HIP_TRY(xchg_error.alloc_zeroed(64u + (size_t)n_cus * 2u * (RT_XCHG_BLOCK / 64u) * RT_XCHG_DEBUG_WORDS * 4u));
+            return RT_OK;
         }
-        if (scene.dw.kind == RT_WORLD_LIST && scene.extended)
-            return scene.textured ? reinterpret_cast<const void*>(&render_kernel_stream<true, false, 768, RT_WORLD_LIST, 2>)
-                                  : reinterpret_cast<const void*>(&render_kernel_stream<true, false, 768, RT_WORLD_LIST, 1>);
-        if (scene.extended) {
-            if (scene.textured) return fast ? reinterpret_cast<const void*>(&render_kernel_stream<false, false, 768, RT_WORLD_BVH, 2>)
-                                            : reinterpret_cast<const void*>(&render_kernel_stream<true, false, 768, RT_WORLD_BVH, 2>);
-            return fast ? reinterpret_cast<const void*>(&render_kernel_stream<false, false, 768, RT_WORLD_BVH, 1>)
-                        : reinterpret_cast<const void*>(&render_kernel_stream<true, false, 768, RT_WORLD_BVH, 1>);
+        if (cfg.variant == 5) return rt_fail(RT_ERR_INVALID, "kernel variant 5: the scene image leaves no room for the ray rings in the LDS");
+        variant = 3;   // chosen by default only: fall back to the streaming kernel
+        return RT_OK;
+    }
+    // HBM of one pass: every sample index owns SAMPLE_BYTES of radiance + PRIMARY_BYTES of primary-ray record.  The default
+    // budget — 120 GiB of the 288, but never more than 45 % of what is free on the device right now, so that two renderers of a
+    // big frame can live side by side — gives the 1200x800x500 headline one pass (28.8 GB) and a 3840x2160 frame 258 spp per
+    // pass (40 GiB, round 2's default, gave 86: 117 passes instead of 39 for 10 000 spp cost 1.1 % in per-pass tails).
+    int size_passes() {
+        uint64_t budget = 120ull << 30;
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > 0) budget = std::min<uint64_t>(budget, (uint64_t)free_b / 100u * 45u);
+        const uint64_t per_sample = SAMPLE_BYTES + PRIMARY_BYTES;
+        if (const char* env = std::getenv("RT06_PASS_BUDGET_BYTES")) {  // bytes of ALL per-sample buffers of a pass
+            unsigned long long v = std::strtoull(env, nullptr, 10);
+            if (v >= per_sample) budget = v;
         }
-        if (scene.dw.kind == RT_WORLD_LIST) return reinterpret_cast<const void*>(&render_kernel_stream<true, false, 768, RT_WORLD_LIST>);
-        if (scene.dw.kind == RT_WORLD_NODE_TREE) return reinterpret_cast<const void*>(&render_kernel_stream<true, false, 768, RT_WORLD_NODE_TREE>);
-        if (tol) return reinterpret_cast<const void*>(&render_kernel_stream<false, false, 768, RT_WORLD_BVH, 0, false, false, true>);
-        if (variant == 2) return reinterpret_cast<const void*>(&render_kernel_stream<true, false, 768>);
-        if (variant == 4) return reinterpret_cast<const void*>(&render_kernel_stream<false, true, 768>);
-        return reinterpret_cast<const void*>(&render_kernel_stream<false, false, 768>);
+        const uint64_t n_pixels = n_local_pixels(tm);
+        uint64_t max_spp = std::max<uint64_t>(1, budget / (n_pixels * per_sample));
+        if (const char* env = std::getenv("RT06_PASS_SPP")) {  // tests force multi-pass rendering with this
+            unsigned long long v = std::strtoull(env, nullptr, 10);
+            if (v >= 1) max_spp = v;
+        }
+        max_spp = std::min<uint64_t>(max_spp, (0xF0000000ull - 1) / n_pixels);   // sample indices of a pass are 32 bits wide
+        if (max_spp == 0) return rt_fail(RT_ERR_INVALID, "image too large for one pass");
+        pass_spp = (uint32_t)std::min<uint64_t>(cfg.samples_per_pixel, max_spp);
+        for (;;) {   // a device that cannot give the pass its buffers gets smaller passes, not an error: halve until they fit
+            hipError_t e = samples.alloc((size_t)(n_pixels * pass_spp * SAMPLE_BYTES));
+            if (e == hipSuccess) e = primary.alloc((size_t)(n_pixels * pass_spp * PRIMARY_BYTES));
+            if (e == hipSuccess) break;
+            (void)hipGetLastError();   // (clears the sticky out-of-memory status)
+            samples.release(); primary.release();
+            if (e != hipErrorOutOfMemory || pass_spp == 1u)
+                return rt_fail(RT_ERR_HIP, "per-pass buffers (%llu bytes per sample index x %llu sample indices): %s", (unsigned long long)per_sample,
+                               (unsigned long long)(n_pixels * pass_spp), hipGetErrorString(e));
+            pass_spp = (pass_spp + 1u) / 2u;
+        }
+        n_passes = (cfg.samples_per_pixel + pass_spp - 1) / pass_spp;
+        if (n_passes > 1) HIP_TRY(running.alloc((size_t)(n_pixels * 16ull)));
+        return RT_OK;
     }
 
     // One call's launches: samples [first_s, first_s + n_s) of every pixel, cut into passes of at most pass_spp.  Render() is (0, samples_per_pixel)
@@ -305,68 +320,30 @@ struct rt_renderer {
     int launch(hipStream_t st, float* out, uint32_t first_s, uint32_t n_s, bool refine) {
         if (variant == 1) {
             RenderParams p;
-            p.width = cfg.width; p.height = cfg.height;
-            p.spp = cfg.samples_per_pixel; p.max_depth = cfg.max_depth;
-            p.seed = cfg.seed;
-            p.cam = cam;
-            p.world = scene.dw;
-            p.tm = tm;
+            frame_params(p, cfg.samples_per_pixel);
             p.out = out;
-            p.work_counter = work_counter.as<uint32_t>();
             return launch_render(p, variant, st);
         }
-        StreamParams p;
-        p.width = cfg.width; p.height = cfg.height;
-        const uint32_t end_s = first_s + n_s, call_passes = (n_s + pass_spp - 1u) / pass_spp;
-        p.spp = refine ? end_s : cfg.samples_per_pixel; p.max_depth = cfg.max_depth;
-        p.seed = cfg.seed;
-        p.cam = cam;
-        p.tm = tm;
-        p.scene = scene.packed;
-        p.world = scene.dw;
-        p.scene.n_top = scene.big ? n_top : 0u;
-        p.samples = samples.as<float4>();
-        p.work_counter = work_counter.as<uint32_t>();
-        p.inner_keep = tune[0] ? tune[0] : 1u; p.shade_min = tune[1]; p.leaf_min = tune[2];
-        uint32_t n_local_pixels = tm.n_local_tiles * RT_TILE * RT_TILE;
-        uint32_t grid = n_cus * stream_blocks_per_cu;
-        std::vector<hipEvent_t>& ring = kev[n_renders % RT_TIMES_RING];
-        kev_passes[n_renders % RT_TIMES_RING] = call_passes;
+        const uint32_t end_s = first_s + n_s, n_pixels = (uint32_t)n_local_pixels(tm), grid = n_cus * stream_blocks_per_cu;
+        StreamParams p = call_params(refine ? end_s : cfg.samples_per_pixel);
+        std::vector<hipEvent_t>& ring = kev[n_renders % RT_TIMES_RING];   // the event ring: this call's slot, four events per pass, created at first use
+        const uint32_t call_passes = kev_passes[n_renders % RT_TIMES_RING] = (n_s + pass_spp - 1u) / pass_spp;
         while (ring.size() < (size_t)call_passes * 4u) {
             hipEvent_t e = nullptr;
             HIP_TRY(hipEventCreate(&e));
             ring.push_back(e);
         }
-        uint32_t pass = 0;
-        for (uint32_t first = first_s; first < end_s; first += pass_spp, pass++) {
-            p.pass_first_s = first;
-            p.pass_spp = std::min(pass_spp, end_s - first);
-            p.total = n_local_pixels * p.pass_spp;
-            // work-queue granularity: ~32 fetches per wave keep the tail short when a shard is small (multi-GPU)
-            uint32_t n_waves = grid * (stream_block / 64u);
-            uint32_t chunk = p.total / (n_waves * 32u);
-            chunk = std::max(64u, std::min(RT_CHUNK_MAX, chunk & ~63u));
-            if (const char* env = std::getenv("RT06_CHUNK")) { int v = std::atoi(env); if (v >= 64 && v <= 1024) chunk = (uint32_t)v & ~63u; }
-            p.chunk = chunk;
-            // the streaming kernel's waves own their first chunk (chunk w for wave w): the counter starts behind those; the exchange
-            // kernel's shader waves draw every chunk from the counter
-            const uint64_t first_shared = variant == 5 ? 0ull : (uint64_t)n_waves * chunk;
-            HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)work_counter.p, (int)(uint32_t)std::min<uint64_t>(first_shared, 0xF0000000ull), 1, st));
+        hipEvent_t* ke = ring.data();
+        for (uint32_t first = first_s; first < end_s; first += pass_spp, ke += 4) {
+            const uint32_t counter_start = pass_params(p, first, end_s, grid);
+            HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)work_counter.p, (int)counter_start, 1, st));
 #ifdef RT_PHASE_TIMERS
             DevBuf phase_acc;
-            HIP_TRY(phase_acc.alloc((32 + 96 * 16) * sizeof(unsigned long long)));
-            HIP_TRY(hipMemsetAsync(phase_acc.p, 0, (32 + 96 * 16) * sizeof(unsigned long long), st));
+            HIP_TRY(phase_acc.alloc(PHASE_WORDS * sizeof(unsigned long long)));
+            HIP_TRY(hipMemsetAsync(phase_acc.p, 0, PHASE_WORDS * sizeof(unsigned long long), st));
             p.phase_acc = phase_acc.as<unsigned long long>();
 #endif
-            const int pb = 0;
-            hipEvent_t* ke = ring.data() + (size_t)pass * 4u;
             HIP_TRY(hipEventRecord(ke[0], st));
-            {
-                const size_t n_pass = (size_t)tm.n_local_tiles * RT_TILE * RT_TILE * pass_spp;   // 16-B records per array
-                p.prim_o = primary[pb].as<float4>();
-                p.prim_d = primary[pb].as<float4>() + n_pass;
-                p.prim_rng = reinterpret_cast<uint4*>(primary[pb].as<float4>() + 2 * n_pass);
-            }
             // The generator declares LDS it does not use: more than two resident persistent workgroups leave free on a CU (160 KiB - 2 x
             // ~77 KiB).  Alone on the GPU that changes nothing.  With a SECOND frame in flight on another stream (bench.py --pipeline 2)
             // it keeps the next frame's generator from moving in beside the persistent kernel's main phase (measured harmful, EXPERIMENTS.md E2) and
@@ -377,79 +354,114 @@ struct rt_renderer {
                 primary_rays_kernel<<<dim3((64u * p.pass_spp + 255u) / 256u, nb), 256, primary_lds, st>>>(p, b0);
                 HIP_TRY(hipGetLastError());
             }
-
             void* args[] = {&p};
             XchgParams xp;
-            if (variant == 5) {
-                if (std::getenv("RT06_XCHG")) p.inner_keep = xc.keep;
-                xp.s = p;
-                xp.n_tracers = xc.n_tracers; xp.n_shards = xc.shards; xp.tq_cap = xc.tq_cap; xp.sq_cap = xc.sq_cap;
-                xp.pop_extra = xc.pop_extra;
-                xp.swap_min = xc.swap_min; xp.shade_min = xc.shade_min; xp.shade_patience = xc.patience;
-                xp.scene_vec4 = xc.scene_vec4; xp.extra_in_lds = xc.extra_in_lds; xp.shader_prio = xc.prio;
-                xp.error_flag = xchg_error.as<uint32_t>();
-#ifdef RT_PHASE_TIMERS
-                xp.xphase_acc = phase_acc.as<unsigned long long>();
-#endif
-                args[0] = &xp;
-            }
+            if (variant == 5) { xp = xchg_params(p); args[0] = &xp; }
             HIP_TRY(hipEventRecord(ke[1], st));
-            HIP_TRY(hipLaunchKernel(stream_kernel_ptr(), dim3(grid), dim3(stream_block), args, stream_lds_bytes, st));
+            HIP_TRY(hipLaunchKernel(stream_kernel, dim3(grid), dim3(stream_block), args, stream_lds_bytes, st));
             HIP_TRY(hipEventRecord(ke[2], st));
 #ifdef RT_PHASE_TIMERS
-            {
-                static unsigned long long h[32 + 96 * 16];
-                HIP_TRY(hipStreamSynchronize(st));
-                HIP_TRY(hipMemcpy(h, phase_acc.p, sizeof(h), hipMemcpyDeviceToHost));
-                if (const char* hp = std::getenv("RT06_TRACE_HIST")) {   // joint histogram (inner steps x leaf tests) per trace, for tools/sched_model.py
-                    if (FILE* f = std::fopen(hp, "w")) {
-                        for (int a = 0; a < 96; a++) { for (int b = 0; b < 16; b++) std::fprintf(f, "%llu ", h[32 + a * 16 + b]); std::fprintf(f, "\n"); }
-                        std::fclose(f);
-                    }
-                }
-                static const char* names_stream[16] = {"hot inner loop", "irregular loop", "leaf phase", "shade (tail)", "regenerate", "begin trace", "(inner steps)", "loop top",
-                                                "schedule check", "shade: miss/sky + hit common", "shade: dielectric prep", "shade: dielectric dir", "shade: on-unit-sphere loop", "shade: metal/lambert/checker", "-", "-"};
-                static const char* names_xchg[16] = {"T hot inner loop", "T irregular loop", "T leaf phase", "T exchange", "T idle", "(lanes per hot step)", "(lanes per leaf phase)", "(finished per exchange)",
-                                                     "S wait", "S pop", "S shade", "S new samples", "S begin trace", "S push", "(traces per shade round)", "-"};
-                const char* const* names = variant == 5 ? names_xchg : names_stream;
-                unsigned long long tot = 0;
-                for (int i = 0; i < 16; i++) if (!(variant == 5 && (i == 5 || i == 6 || i == 7 || i == 14))) tot += h[i];
-                for (int i = 0; i < 16; i++)
-                    fprintf(stderr, "[phase] %-16s %6.2f %% of wave time, %12llu visits, %8.1f cycles per visit\n", names[i], 100.0 * h[i] / (double)tot, h[16 + i], h[16 + i] ? (double)h[i] / h[16 + i] : 0.0);
-            }
+            if (const int rc = report_phase_timers(phase_acc, st)) return rc;
 #endif
-            uint32_t last = first + p.pass_spp >= end_s ? 1u : 0u;
-            if (refine) refine_resolve_kernel<<<(n_local_pixels + 255) / 256, 256, 0, st>>>(p, accum.as<float4>(), out, last, end_s);
-            else resolve_kernel<<<(n_local_pixels + 255) / 256, 256, 0, st>>>(p, running.as<float4>(), out, last);
+            const uint32_t last = first + p.pass_spp >= end_s ? 1u : 0u;
+            if (refine) refine_resolve_kernel<<<(n_pixels + 255) / 256, 256, 0, st>>>(p, accum.as<float4>(), out, last, end_s);
+            else resolve_kernel<<<(n_pixels + 255) / 256, 256, 0, st>>>(p, running.as<float4>(), out, last);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipEventRecord(ke[3], st));
             // feature pass: after the pass's fourth timing event (rt_renderer_kernel_times keeps its meaning), before the next pass's generator
             // overwrites the primary-ray records
-            if (refine && aov_on) {
-                const uint32_t upto = aov_max ? std::min(aov_max, first + p.pass_spp) : first + p.pass_spp;
-                if (upto > first) {
-                    const int rc = launch_aov(p, upto - first, st);
-                    if (rc != RT_OK) return rc;
-                }
-            }
+            if (refine && aov_on)
+                if (const int rc = launch_aov(p, st)) return rc;
         }
         n_renders++;
         return RT_OK;
     }
-    // one aov_kernel launch: the traversal is the world's own, picked here so that a kernel carries one traversal stack
-    int launch_aov(const StreamParams& sp, uint32_t n_take, hipStream_t st) {
-        const uint32_t n_local_pixels = tm.n_local_tiles * RT_TILE * RT_TILE;
-        const dim3 grid((n_local_pixels + RT_AOV_BLOCK - 1u) / RT_AOV_BLOCK), block(RT_AOV_BLOCK);
+    // what the baseline and the streaming kernels' parameters share; spp = the sample count the pixels are resolved against
+    template <typename Params> void frame_params(Params& p, uint32_t spp) const {
+        p.width = cfg.width; p.height = cfg.height;
+        p.spp = spp; p.max_depth = cfg.max_depth;
+        p.seed = cfg.seed;
+        p.cam = cam;
+        p.world = scene.dw;
+        p.tm = tm;
+        p.work_counter = work_counter.as<uint32_t>();
+    }
+    // what every pass of a call shares
+    StreamParams call_params(uint32_t spp) const {
+        StreamParams p;
+        frame_params(p, spp);
+        p.scene = scene.packed;
+        p.scene.n_top = scene.big ? n_top : 0u;
+        p.samples = samples.as<float4>();
+        p.inner_keep = tune[0] ? tune[0] : 1u; p.shade_min = tune[1]; p.leaf_min = tune[2];
+        const size_t n_pass = n_local_pixels(tm) * pass_spp;   // 16-B records per array
+        p.prim_o = primary.as<float4>();
+        p.prim_d = primary.as<float4>() + n_pass;
+        p.prim_rng = reinterpret_cast<uint4*>(primary.as<float4>() + 2 * n_pass);
+        return p;
+    }
+    // the pass that starts at sample `first`: its share of the samples and the work-queue granularity; returns where the work counter starts
+    uint32_t pass_params(StreamParams& p, uint32_t first, uint32_t end_s, uint32_t grid) const {
+        p.pass_first_s = first;
+        p.pass_spp = std::min(pass_spp, end_s - first);
+        p.total = (uint32_t)n_local_pixels(tm) * p.pass_spp;
+        // work-queue granularity: ~32 fetches per wave keep the tail short when a shard is small (multi-GPU)
+        const uint32_t n_waves = grid * (stream_block / 64u);
+        p.chunk = std::max(64u, std::min(RT_CHUNK_MAX, (p.total / (n_waves * 32u)) & ~63u));
+        if (const char* env = std::getenv("RT06_CHUNK")) { int v = std::atoi(env); if (v >= 64 && v <= 1024) p.chunk = (uint32_t)v & ~63u; }
+        // the streaming kernel's waves own their first chunk (chunk w for wave w): the counter starts behind those; the exchange
+        // kernel's shader waves draw every chunk from the counter
+        const uint64_t first_shared = variant == 5 ? 0ull : (uint64_t)n_waves * p.chunk;
+        return (uint32_t)std::min<uint64_t>(first_shared, 0xF0000000ull);
+    }
+    XchgParams xchg_params(const StreamParams& p) const {
+        XchgParams xp;
+        xp.s = p;
+        if (std::getenv("RT06_XCHG")) xp.s.inner_keep = xc.keep;
+        xp.n_tracers = xc.n_tracers; xp.n_shards = xc.shards; xp.tq_cap = xc.tq_cap; xp.sq_cap = xc.sq_cap;
+        xp.pop_extra = xc.pop_extra;
+        xp.swap_min = xc.swap_min; xp.shade_min = xc.shade_min; xp.shade_patience = xc.patience;
+        xp.scene_vec4 = xc.scene_vec4; xp.extra_in_lds = xc.extra_in_lds; xp.shader_prio = xc.prio;
+        xp.error_flag = xchg_error.as<uint32_t>();
+#ifdef RT_PHASE_TIMERS
+        xp.xphase_acc = p.phase_acc;
+#endif
+        return xp;
+    }
+#ifdef RT_PHASE_TIMERS
+    static constexpr size_t PHASE_WORDS = 32 + 96 * 16;   // cycles and visits of 16 phases, then the 96 x 16 trace histogram
+    int report_phase_timers(const DevBuf& phase_acc, hipStream_t st) const {
+        static unsigned long long h[PHASE_WORDS];
+        HIP_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipMemcpy(h, phase_acc.p, sizeof(h), hipMemcpyDeviceToHost));
+        if (const char* hp = std::getenv("RT06_TRACE_HIST")) {   // joint histogram (inner steps x leaf tests) per trace, for tools/sched_model.py
+            if (FILE* f = std::fopen(hp, "w")) {
+                for (int a = 0; a < 96; a++) { for (int b = 0; b < 16; b++) std::fprintf(f, "%llu ", h[32 + a * 16 + b]); std::fprintf(f, "\n"); }
+                std::fclose(f);
+            }
+        }
+        static const char* names_stream[16] = {"hot inner loop", "irregular loop", "leaf phase", "shade (tail)", "regenerate", "begin trace", "(inner steps)", "loop top",
+                                        "schedule check", "shade: miss/sky + hit common", "shade: dielectric prep", "shade: dielectric dir", "shade: on-unit-sphere loop", "shade: metal/lambert/checker", "-", "-"};
+        static const char* names_xchg[16] = {"T hot inner loop", "T irregular loop", "T leaf phase", "T exchange", "T idle", "(lanes per hot step)", "(lanes per leaf phase)", "(finished per exchange)",
+                                             "S wait", "S pop", "S shade", "S new samples", "S begin trace", "S push", "(traces per shade round)", "-"};
+        const char* const* names = variant == 5 ? names_xchg : names_stream;
+        unsigned long long tot = 0;
+        for (int i = 0; i < 16; i++) if (!(variant == 5 && (i == 5 || i == 6 || i == 7 || i == 14))) tot += h[i];
+        for (int i = 0; i < 16; i++)
+            fprintf(stderr, "[phase] %-16s %6.2f %% of wave time, %12llu visits, %8.1f cycles per visit\n", names[i], 100.0 * h[i] / (double)tot, h[16 + i], h[16 + i] ? (double)h[i] / h[16 + i] : 0.0);
+        return RT_OK;
+    }
+#endif
+    // the feature pass of the pass in `sp`: one aov_kernel launch over its samples below aov_max (0 = all of them)
+    int launch_aov(const StreamParams& sp, hipStream_t st) {
+        const uint32_t pass_end = sp.pass_first_s + sp.pass_spp, upto = aov_max ? std::min(aov_max, pass_end) : pass_end;
+        if (upto <= sp.pass_first_s) return RT_OK;
+        const dim3 grid(((uint32_t)n_local_pixels(tm) + RT_AOV_BLOCK - 1u) / RT_AOV_BLOCK), block(RT_AOV_BLOCK);
         AovParams p;
         p.tm = sp.tm; p.world = sp.world;
-        p.pass_first_s = sp.pass_first_s; p.pass_spp = sp.pass_spp; p.n_take = n_take;
+        p.pass_first_s = sp.pass_first_s; p.pass_spp = sp.pass_spp; p.n_take = upto - sp.pass_first_s;
         p.prim_o = sp.prim_o; p.prim_d = sp.prim_d;
-        float4* out = aov.as<float4>();
-        if (scene.dw.kind == RT_WORLD_LIST) aov_kernel<RT_AOV_WALK_LIST><<<grid, block, 0, st>>>(p, out);
-        else if (scene.dw.kind == RT_WORLD_NODE_TREE) aov_kernel<RT_AOV_WALK_TREE><<<grid, block, 0, st>>>(p, out);
-        else if (scene.dw.traversal == RT_TRAVERSAL_QUEUE) aov_kernel<RT_AOV_WALK_QUEUE><<<grid, block, 0, st>>>(p, out);
-        else if (scene.dw.traversal == RT_TRAVERSAL_WIDE4) aov_kernel<RT_AOV_WALK_WIDE4><<<grid, block, 0, st>>>(p, out);
-        else aov_kernel<RT_AOV_WALK_STACK><<<grid, block, 0, st>>>(p, out);
+        aov_kernel_for(scene.dw)<<<grid, block, 0, st>>>(p, aov.as<float4>());
         HIP_TRY(hipGetLastError());
         return RT_OK;
     }
@@ -484,11 +496,8 @@ extern "C" int rt_renderer_create(const rt_render_config* cfg, const rt_camera* 
     rc = r->scene.upload(world);
     if (rc != RT_OK) { delete r; return rc; }
     r->tm = make_tile_map(cfg->width, cfg->height, cfg->rank, cfg->world_size);
-    TileMap& tm = r->tm;
-    r->shard_floats = (size_t)tm.n_local_tiles * RT_TILE * RT_TILE * 4;
-    size_t fb_floats = tm.direct ? (size_t)cfg->width * cfg->height * 4 : r->shard_floats;
-    hipError_t e = r->fb.alloc(fb_floats * sizeof(float));
-    if (e == hipSuccess) e = hipMemset(r->fb.p, 0, fb_floats * sizeof(float));
+    size_t fb_floats = r->tm.direct ? (size_t)cfg->width * cfg->height * 4 : n_local_pixels(r->tm) * 4;
+    hipError_t e = r->fb.alloc_zeroed(fb_floats * sizeof(float));
     if (e == hipSuccess) e = r->work_counter.alloc(256);
     if (e == hipSuccess) {
         rc = r->plan();
@@ -525,11 +534,31 @@ extern "C" int rt_renderer_render_async(rt_renderer* r, void* hip_stream, float*
     return enqueue_call(r, hip_stream, d_out, 0u, r->cfg.samples_per_pixel, false);
 }
 
-static int wait_and_check(rt_renderer* r) {
+// the work of the last call may be on a caller's stream (the _async entry points): its end event orders what reads the results
+static int wait_last_call(rt_renderer* r) {
+    HIP_TRY(hipSetDevice(r->cfg.device));
+    if (r->timed) HIP_TRY(hipEventSynchronize(r->ev1));
     HIP_TRY(hipStreamSynchronize(r->stream));
-    int rc = check_xchg_error(r->xchg_error);
-    if (rc != RT_OK) return rc;
-    return check_traversal_overflow(r->scene);
+    return RT_OK;
+}
+
+// after a synchronisation: ray-exchange protocol error / traversal-queue overflow (both flags are read and cleared by their checks)
+int rt_renderer_check_device_flags(rt_renderer* r) {
+    const int rc = check_xchg_error(r->xchg_error);
+    return rc != RT_OK ? rc : check_traversal_overflow(r->scene);
+}
+
+// A tile-major buffer of one shard that is the whole frame (world_size 1), `fpp` floats per local pixel, into the frame's row-major order on the host.
+static int download_tile_major(rt_renderer* r, const DevBuf& src, uint32_t fpp, float* host) {
+    if (const int rc = wait_last_call(r)) return rc;
+    const uint32_t n_local = (uint32_t)n_local_pixels(r->tm);
+    std::vector<float> local((size_t)n_local * fpp);
+    HIP_TRY(hipMemcpy(local.data(), src.p, local.size() * sizeof(float), hipMemcpyDeviceToHost));
+    std::vector<uint32_t> gid(n_local);
+    if (const int rc = rt_shard_pixel_map(r->cfg.width, r->cfg.height, 1u, 0u, gid.data(), gid.size())) return rc;
+    for (uint32_t L = 0; L < n_local; L++)
+        if (gid[L] != 0xffffffffu) std::memcpy(host + (size_t)gid[L] * fpp, local.data() + (size_t)L * fpp, fpp * sizeof(float));
+    return RT_OK;
 }
 
 extern "C" int rt_renderer_set_camera(rt_renderer* r, const rt_camera* cam) {
@@ -550,11 +579,7 @@ extern "C" int rt_renderer_refine_async(rt_renderer* r, void* hip_stream, float*
     if ((uint64_t)r->refine_done + n_samples > 0x80000000ull)
         return rt_fail(RT_ERR_INVALID, "rt_renderer_refine: %u + %u samples per pixel pass 2^31", r->refine_done, n_samples);
     HIP_TRY(hipSetDevice(r->cfg.device));
-    if (!r->accum.p) {
-        const size_t bytes = (size_t)r->tm.n_local_tiles * RT_TILE * RT_TILE * sizeof(float4);
-        HIP_TRY(r->accum.alloc(bytes));
-        HIP_TRY(hipMemset(r->accum.p, 0, bytes));   // padding pixels of a shard are never written: they read as zeros
-    }
+    if (!r->accum.p) HIP_TRY(r->accum.alloc_zeroed(n_local_pixels(r->tm) * sizeof(float4)));   // padding pixels of a shard are never written: they read as zeros
     if (!r->refine_ev) HIP_TRY(hipEventCreate(&r->refine_ev));
     if (r->dn_valid) HIP_TRY(hipStreamWaitEvent((hipStream_t)hip_stream, r->dn_ev, 0));   // a filter may still read what this step overwrites
     int rc = enqueue_call(r, hip_stream, d_out, r->refine_done, n_samples, true);
@@ -568,8 +593,8 @@ extern "C" int rt_renderer_refine_async(rt_renderer* r, void* hip_stream, float*
 extern "C" int rt_renderer_refine(rt_renderer* r, uint32_t n_samples) {
     if (!r) return rt_fail(RT_ERR_INVALID, "rt_renderer_refine: null renderer");
     int rc = rt_renderer_refine_async(r, r->stream, nullptr, n_samples);
-    if (rc != RT_OK) return rc;
-    return wait_and_check(r);
+    if (rc == RT_OK) rc = wait_last_call(r);
+    return rc != RT_OK ? rc : rt_renderer_check_device_flags(r);
 }
 
 extern "C" int rt_renderer_refine_reset(rt_renderer* r) {
@@ -587,39 +612,20 @@ extern "C" int rt_renderer_refine_info(rt_renderer* r, uint64_t out[3]) {
     return RT_OK;
 }
 
-// the work of the last call may be on a caller's stream (the _async entry points): its end event orders what reads the results
-static int wait_last_call(rt_renderer* r) {
-    HIP_TRY(hipSetDevice(r->cfg.device));
-    if (r->timed) HIP_TRY(hipEventSynchronize(r->ev1));
-    HIP_TRY(hipStreamSynchronize(r->stream));
-    return RT_OK;
-}
-
 extern "C" int rt_renderer_refine_download_sums(rt_renderer* r, float* host, size_t n_floats) {
     if (!r || !host) return rt_fail(RT_ERR_INVALID, "rt_renderer_refine_download_sums: null argument");
     if (r->cfg.world_size != 1) return rt_fail(RT_ERR_INVALID, "rt_renderer_refine_download_sums: renderer holds one shard of %u", r->cfg.world_size);
     const size_t need = (size_t)r->cfg.width * r->cfg.height * 4;
     if (n_floats != need) return rt_fail(RT_ERR_INVALID, "rt_renderer_refine_download_sums: buffer holds %zu floats, image needs %zu", n_floats, need);
     if (r->refine_done == 0 || !r->accum.p) return rt_fail(RT_ERR_INVALID, "rt_renderer_refine_download_sums: nothing accumulated (refine first)");
-    int rc = wait_last_call(r);
-    if (rc != RT_OK) return rc;
-    const uint32_t n_local = r->tm.n_local_tiles * RT_TILE * RT_TILE;
-    std::vector<float> local((size_t)n_local * 4u);
-    HIP_TRY(hipMemcpy(local.data(), r->accum.p, local.size() * sizeof(float), hipMemcpyDeviceToHost));
-    std::vector<uint32_t> gid(n_local);   // the accumulation is tile-major like a shard: put it in the frame's row-major order
-    rc = rt_shard_pixel_map(r->cfg.width, r->cfg.height, 1u, 0u, gid.data(), gid.size());
-    if (rc != RT_OK) return rc;
-    for (uint32_t L = 0; L < n_local; L++)
-        if (gid[L] != 0xffffffffu) std::memcpy(host + (size_t)gid[L] * 4u, local.data() + (size_t)L * 4u, 4u * sizeof(float));
-    return RT_OK;
+    return download_tile_major(r, r->accum, 4u, host);   // the accumulation is tile-major like a shard
 }
 
 extern "C" int rt_renderer_refine_noise(rt_renderer* r, double* out) {
     if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_refine_noise: null argument");
     if (r->refine_done < 2 || !r->accum.p) return rt_fail(RT_ERR_INVALID, "rt_renderer_refine_noise: a variance needs 2 samples per pixel; %u accumulated", r->refine_done);
-    int rc = wait_last_call(r);
-    if (rc != RT_OK) return rc;
-    const uint32_t n_local = r->tm.n_local_tiles * RT_TILE * RT_TILE;
+    if (const int rc = wait_last_call(r)) return rc;
+    const uint32_t n_local = (uint32_t)n_local_pixels(r->tm);
     const uint32_t n_blocks = (n_local + RT_NOISE_BLOCK - 1u) / RT_NOISE_BLOCK;
     if (!r->noise_partials.p) {
         HIP_TRY(r->noise_partials.alloc((size_t)n_blocks * sizeof(NoiseSums)));
@@ -648,11 +654,7 @@ extern "C" int rt_renderer_aov_enable(rt_renderer* r, uint32_t max_samples) {
     if (r->aov_refused)
         return rt_fail(RT_ERR_INVALID, "rt_renderer_aov_enable: the world has %s: the feature pass covers spheres and quads with Lambertian, metal, dielectric, checker and light materials", r->aov_refused);
     HIP_TRY(hipSetDevice(r->cfg.device));
-    if (!r->aov.p) {
-        const size_t bytes = (size_t)r->tm.n_local_tiles * RT_TILE * RT_TILE * 2u * sizeof(float4);
-        HIP_TRY(r->aov.alloc(bytes));
-        HIP_TRY(hipMemset(r->aov.p, 0, bytes));   // padding pixels are never written: they read as zeros
-    }
+    if (!r->aov.p) HIP_TRY(r->aov.alloc_zeroed(n_local_pixels(r->tm) * 2u * sizeof(float4)));   // padding pixels are never written: they read as zeros
     r->aov_on = true;
     r->aov_max = max_samples;
     r->refine_done = 0;   // like rt_renderer_refine_reset: colour and features restart together
@@ -674,17 +676,7 @@ extern "C" int rt_renderer_aov_download(rt_renderer* r, float* host, size_t n_fl
     const size_t need = (size_t)r->cfg.width * r->cfg.height * 8;
     if (n_floats != need) return rt_fail(RT_ERR_INVALID, "rt_renderer_aov_download: buffer holds %zu floats, the feature buffers need %zu", n_floats, need);
     if (!r->aov_on || r->aov_done == 0) return rt_fail(RT_ERR_INVALID, "rt_renderer_aov_download: no feature samples (rt_renderer_aov_enable, then refine)");
-    int rc = wait_last_call(r);
-    if (rc != RT_OK) return rc;
-    const uint32_t n_local = r->tm.n_local_tiles * RT_TILE * RT_TILE;
-    std::vector<float> local((size_t)n_local * 8u);
-    HIP_TRY(hipMemcpy(local.data(), r->aov.p, local.size() * sizeof(float), hipMemcpyDeviceToHost));
-    std::vector<uint32_t> gid(n_local);   // tile-major like the accumulation: put it in the frame's row-major order
-    rc = rt_shard_pixel_map(r->cfg.width, r->cfg.height, 1u, 0u, gid.data(), gid.size());
-    if (rc != RT_OK) return rc;
-    for (uint32_t L = 0; L < n_local; L++)
-        if (gid[L] != 0xffffffffu) std::memcpy(host + (size_t)gid[L] * 8u, local.data() + (size_t)L * 8u, 8u * sizeof(float));
-    return RT_OK;
+    return download_tile_major(r, r->aov, 8u, host);
 }
 
 extern "C" int rt_renderer_denoise_async(rt_renderer* r, void* hip_stream, const rt_denoise_params* params) {
@@ -707,7 +699,7 @@ extern "C" int rt_renderer_denoise_async(rt_renderer* r, void* hip_stream, const
     DenoiseParams dp;
     dp.width = r->cfg.width; dp.height = r->cfg.height;
     dp.sigma_depth = params->sigma_depth; dp.sigma_lum = params->sigma_lum; dp.demodulate = params->demodulate;
-    const uint32_t n_local = r->tm.n_local_tiles * RT_TILE * RT_TILE;
+    const uint32_t n_local = (uint32_t)n_local_pixels(r->tm);
     float4 *src = r->dn_a.as<float4>(), *dst = r->dn_b.as<float4>();
     denoise_prepare_kernel<<<(n_local + 255u) / 256u, 256, 0, st>>>(r->tm, dp, r->accum.as<float4>(), r->aov.as<float4>(), r->refine_done, r->aov_done,
                                                                     r->dn_g0.as<float4>(), r->dn_g1.as<float4>(), src);
@@ -749,8 +741,8 @@ extern "C" int rt_renderer_denoise_download(rt_renderer* r, float* host_rgba, si
 extern "C" int rt_renderer_render(rt_renderer* r) {
     if (!r) return rt_fail(RT_ERR_INVALID, "rt_renderer_render: null renderer");
     int rc = rt_renderer_render_async(r, r->stream, nullptr);
-    if (rc != RT_OK) return rc;
-    return wait_and_check(r);
+    if (rc == RT_OK) rc = wait_last_call(r);
+    return rc != RT_OK ? rc : rt_renderer_check_device_flags(r);
 }
 
 extern "C" int rt_renderer_last_kernel_ms(rt_renderer* r, float* out_ms) {
@@ -788,7 +780,7 @@ extern "C" int rt_renderer_pass_info(rt_renderer* r, uint64_t out[4]) {
     out[0] = r->variant >= 2 ? r->n_passes : 1u;
     out[1] = r->variant >= 2 ? r->pass_spp : r->cfg.samples_per_pixel;
     out[2] = r->variant >= 2 ? rt_renderer::SAMPLE_BYTES + rt_renderer::PRIMARY_BYTES : 0u;
-    out[3] = r->samples.bytes + r->primary[0].bytes + r->running.bytes;
+    out[3] = r->samples.bytes + r->primary.bytes + r->running.bytes;
     return RT_OK;
 }
 
@@ -806,19 +798,14 @@ extern "C" int rt_renderer_download(rt_renderer* r, float* host_rgba, size_t n_f
     if (r->cfg.world_size != 1) return rt_fail(RT_ERR_INVALID, "rt_renderer_download: renderer holds one shard of %u; gather and rt_renderer_assemble first", r->cfg.world_size);
     size_t need = (size_t)r->cfg.width * r->cfg.height * 4;
     if (n_floats != need) return rt_fail(RT_ERR_INVALID, "rt_renderer_download: buffer holds %zu floats, image needs %zu", n_floats, need);
-    HIP_TRY(hipSetDevice(r->cfg.device));
-    // the last render may have been launched on a caller's stream (rt_renderer_render_async): its end event orders the copy
-    if (r->timed) HIP_TRY(hipEventSynchronize(r->ev1));
-    HIP_TRY(hipStreamSynchronize(r->stream));
+    if (const int rc = wait_last_call(r)) return rc;
     HIP_TRY(hipMemcpy(host_rgba, r->fb.p, need * sizeof(float), hipMemcpyDeviceToHost));
-    int rc = check_xchg_error(r->xchg_error);
-    if (rc != RT_OK) return rc;
-    return check_traversal_overflow(r->scene);
+    return rt_renderer_check_device_flags(r);
 }
 
 extern "C" int rt_renderer_shard_floats(const rt_renderer* r, size_t* out) {
     if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_shard_floats: null argument");
-    *out = r->shard_floats;
+    *out = n_local_pixels(r->tm) * 4;
     return RT_OK;
 }
 
@@ -838,16 +825,10 @@ extern "C" int rt_renderer_assemble(rt_renderer* r, const float* d_gathered, flo
     HIP_TRY(hipSetDevice(r->cfg.device));
     hipStream_t st = (hipStream_t)hip_stream;
     uint32_t n = r->cfg.width * r->cfg.height;
-    assemble_kernel<<<(n + 255) / 256, 256, 0, st>>>((const float4*)d_gathered, (float4*)d_image, r->tm,
-                                                      (uint32_t)(r->shard_floats / 4));
+    assemble_kernel<<<(n + 255) / 256, 256, 0, st>>>((const float4*)d_gathered, (float4*)d_image, r->tm, (uint32_t)n_local_pixels(r->tm));
     HIP_TRY(hipGetLastError());
     return RT_OK;
 }
 
-
 hipStream_t rt_renderer_own_stream(rt_renderer* r) { return r->stream; }
 float* rt_renderer_own_framebuffer(rt_renderer* r) { return r->fb.as<float>(); }
-int rt_renderer_check_device_flags(rt_renderer* r) {
-    const int rc = check_xchg_error(r->xchg_error);
-    return rc != RT_OK ? rc : check_traversal_overflow(r->scene);
-}

@@ -57,6 +57,7 @@ struct DevBuf {
         if (p) { (void)hipFree(p); p = nullptr; }
         bytes = 0;
     }
+    hipError_t alloc_zeroed(size_t n) { const hipError_t e = alloc(n); return e == hipSuccess ? hipMemset(p, 0, n) : e; }
     hipError_t upload(const void* src, size_t n) {
         hipError_t e = alloc(n);
         if (e != hipSuccess) return e;
@@ -82,6 +83,15 @@ static void write_wide_node(uint4* blob, bool big, uint32_t index, const float l
         d[9 + 3 * k + 0] = bits(rmin[k]); d[9 + 3 * k + 1] = bits(rmax[k]); d[9 + 3 * k + 2] = bits(rmin[k]);
     }
     d[RT_NODE_REFS] = (lref & 0xffffu) | (rref << 16);
+}
+
+constexpr uint32_t RT_LDS_PER_CU = 160u * 1024u;   // MI355X_MICROARCH.md: 160 KiB LDS per CU, all of which one workgroup may take
+
+// Dynamic LDS of one render_kernel_stream workgroup of `block` lanes (layout: rt_stream_kernel.hpp): the whole image, then a stack of 16-bit entries per lane;
+// BIG: the first n_top wide nodes (64 B each), then the stacks (16-bit entries, 32-bit when WIDE) rounded up to whole 64-byte lines.
+inline size_t stream_kernel_lds_bytes(uint32_t block, const PackedSceneRef& ps, bool big, bool wide, uint32_t n_top) {
+    if (big) return (size_t)n_top * (RT_NODE_DWORDS_BIG * 4u) + (((size_t)block * ps.stack_cap * (wide ? 4u : 2u) + 63u) & ~(size_t)63u);
+    return ((size_t)ps.blob_vec4 * 16u + (size_t)block * ps.stack_cap * 2u + 15u) & ~(size_t)15u;
 }
 
 struct DeviceScene {
@@ -314,16 +324,15 @@ struct DeviceScene {
         dw.image = w->image ? image.as<uint8_t>() : nullptr;
         dw.image_w = w->image_width; dw.image_h = w->image_height;
         dw.traversal = w->traversal;
-        HIP_TRY(error_flag.alloc(4));
-        HIP_TRY(hipMemset(error_flag.p, 0, 4));
+        HIP_TRY(error_flag.alloc_zeroed(4));
         dw.error_flag = error_flag.as<uint32_t>();
-        // 16-bit references and an LDS-resident image when that fits (2 x 768-thread workgroups per CU want <= 80 KiB each,
-        // one workgroup may take all 160 KiB); otherwise 32-bit references and the records stay in global memory / L2
+        // 16-bit references and an LDS-resident image when that fits (2 x 768-thread workgroups per CU want half the LDS each,
+        // one workgroup may take all of it); otherwise 32-bit references and the records stay in global memory / L2
         queue = w->traversal != RT_TRAVERSAL_STACK;   // the queue or the 4-wide walk: every lane walks its trace on its own
         if (queue) return pack(w, true);   // the queue walk reads the flat world itself; the shade phase reads the packed records from global memory
         int rc = pack(w, false);
         if (rc != RT_OK) return rc;
-        const bool fits_lds = has_packed && (size_t)packed.blob_vec4 * 16u + (size_t)RT_STREAM_BLOCK * packed.stack_cap * 2u <= 160u * 1024u;
+        const bool fits_lds = has_packed && stream_kernel_lds_bytes(RT_STREAM_BLOCK, packed, false, false, 0u) <= RT_LDS_PER_CU;
         const char* force = std::getenv("RT06_FORCE_BIG");  // measurements / tests: take the global-memory path for any BVH world
         if (!fits_lds || (force && force[0] == '1')) rc = pack(w, true);
         return rc;
@@ -390,6 +399,7 @@ static TileMap make_tile_map(uint32_t width, uint32_t height, uint32_t rank, uin
     tm.direct = world_size == 1 ? 1u : 0u;
     return tm;
 }
+static inline size_t n_local_pixels(const TileMap& tm) { return (size_t)tm.n_local_tiles * RT_TILE * RT_TILE; }   // of a rank's shard, padding included
 
 // what the multi-GPU driver (rt_multi.hip) needs of a renderer beyond the C ABI; defined in rt_device.hip
 hipStream_t rt_renderer_own_stream(rt_renderer* r);      // the renderer's non-blocking stream
