@@ -425,6 +425,32 @@ int rt_renderer_denoise_async(rt_renderer* r, void* hip_stream, const rt_denoise
 int rt_renderer_denoise_download(rt_renderer* r, float* host_rgba, size_t n_floats);
 
 /* ------------------------------------------------------------------ */
+/* Light sampling (not in the reference; "Ray Tracing: The Rest of Your */
+/* Life"): opt-in next-event estimation for worlds lit by quad lights.  */
+/* ------------------------------------------------------------------ */
+/* A light is a quad whose material is RT_MAT_DIFFUSE_LIGHT; they are taken in quad-index order, 1 <= n_l <= RT_MAX_LIGHTS, each with
+ * area = sqrt(dot(n, n)), n = cross(u, v), in fp32.  With sampling on, a hit on RT_MAT_LAMBERTIAN or RT_MAT_LAMBERTIAN_CHECKER that does
+ * not end the path draws, in this order: c; if c < 0.5f a light — i = min((uint32_t)(next * (float)n_l), n_l - 1) when n_l > 1 (no draw
+ * otherwise), then a, then b, and d = ((Q_i + u_i * a) + v_i * b) - hit_p, not normalised; otherwise d = normal + on_unit as without
+ * sampling (near_zero(d) fails the scatter).  Then, from hit_p before the 0.001 offset:  len2 = dot(d, d), len = sqrt(len2),
+ * cosn = dot(normal, d) / len, sp = cosn > 0 ? cosn * 0.318309886f : 0;  per light j the library's own quad test on the ray (hit_p, d)
+ * over a fresh trace's interval gives t or a miss:  pl_j = ((t * t) * len2) / ((fabs(dot(d, normal_j)) / len) * area_j) or 0;
+ * pl = (sum of pl_j in index order) / (float)n_l;  pdf = 0.5f * sp + 0.5f * pl.  sp == 0 or a pdf that is not > 0 ends the path like a
+ * failed scatter (what was accumulated is kept); otherwise atten = atten * (albedo * (sp / pdf)) and the ray goes on along d.  Every
+ * operation is rounded on its own.  Emission is untouched (two-sided, added when a path hits a light); sphere lights emit but are not
+ * sampled; every other material scatters and draws as without sampling.  Off (the default), every launch is exactly what it was.
+ * Enabling or disabling takes effect from the next launch and, when it changes anything, discards the refinement and feature-buffer
+ * state as rt_renderer_set_camera with other bytes does.  RT_ERR_INVALID, with the cause in rt_last_error: no quad light; more than
+ * RT_MAX_LIGHTS; a renderer on variant 1, 5 or 6; a world with a queue or wide4 traversal; a world with a constant medium.            */
+#define RT_MAX_LIGHTS 16
+int rt_renderer_light_sampling_enable(rt_renderer* r, uint32_t on);
+/* out[0] = 1 when on, out[1] = n_l, the quad lights of the world (0 when it cannot be light-sampled) */
+int rt_renderer_light_sampling_info(rt_renderer* r, uint32_t out[2]);
+/* HOST (no GPU): the light table of a world as rt_renderer_light_sampling_enable would take it — quad index and area of light i < *out_n —
+ * or RT_ERR_INVALID with the world's own reason for refusal (no quad light, more than RT_MAX_LIGHTS, traversal, constant medium).     */
+int rt_world_quad_lights(const rt_world_flat* w, uint32_t out_quad[RT_MAX_LIGHTS], float out_area[RT_MAX_LIGHTS], uint32_t* out_n);
+
+/* ------------------------------------------------------------------ */
 /* Multi-GPU renderer — the same three entry points (Renderer.h:38-46)  */
 /* over the N GPUs of one node, driven by ONE host process.            */
 /* ------------------------------------------------------------------ */
@@ -446,6 +472,8 @@ int rt_multi_renderer_set_camera(rt_multi_renderer* m, const rt_camera* cam);
 /* rt_renderer_refine on every rank, then the usual gather + assembly: the frame of rt_multi_renderer_download is the
  * refined one.  No noise figure here (each rank's rt_renderer_refine_noise covers its own pixels only).                 */
 int rt_multi_renderer_refine(rt_multi_renderer* m, uint32_t n_samples);
+/* rt_renderer_light_sampling_enable on every rank (the first rank refuses what any would, before any changes).          */
+int rt_multi_renderer_light_sampling_enable(rt_multi_renderer* m, uint32_t on);
 /* Renderer::DownloadRenderbuffer: width*height*4 floats from devices[0].                                                */
 int rt_multi_renderer_download(rt_multi_renderer* m, float* host_rgba, size_t n_floats);
 /* ms of the last render: out[0] host wall-clock of Render(), out[1] slowest rank's kernels (HIP events),

@@ -578,6 +578,12 @@ public:
         single("Renderer::DownloadDenoised");
         rt06::check(rt_renderer_denoise_download(m.r, reinterpret_cast<float*>(host_dst), (size_t)m.render_width * m.render_height * 4), "Renderer::DownloadDenoised");
     }
+    // Light sampling (rt06.h; opt-in): Lambertian and checker hits draw from the mixture of their cosine distribution and the world's quad
+    // lights, from the next Render() / Refine() on; a change restarts the refinement.  Refused for worlds and variants that have no such kernel.
+    void SetLightSampling(bool on) {
+        if (m.mr) rt06::check(rt_multi_renderer_light_sampling_enable(m.mr, on ? 1u : 0u), "Renderer::SetLightSampling");
+        else rt06::check(rt_renderer_light_sampling_enable(m.r, on ? 1u : 0u), "Renderer::SetLightSampling");
+    }
     float LastKernelMs() {
         float ms = 0;
         if (m.mr) { float t[3]; rt06::check(rt_multi_renderer_times(m.mr, t), "Renderer::LastKernelMs"); return t[0]; }

@@ -339,6 +339,16 @@ class Renderer:
     def denoise_async(self, stream=None, **params):
         check(lib().rt_renderer_denoise_async(self.h, C.c_void_p(stream or 0), C.byref(self.denoise_params(**params))))
 
+    def light_sampling(self, on=True):
+        """Next-event estimation over the world's quad lights from the next launch on (rt_renderer_light_sampling_enable); a change restarts the refinement."""
+        check(lib().rt_renderer_light_sampling_enable(self.h, 1 if on else 0))
+
+    def light_sampling_info(self):
+        """{'enabled', 'lights'}: whether light sampling is on, and the number of quad lights it samples (0: the world cannot be light-sampled)."""
+        out = (C.c_uint32 * 2)()
+        check(lib().rt_renderer_light_sampling_info(self.h, out))
+        return {"enabled": bool(out[0]), "lights": out[1]}
+
     def last_kernel_ms(self):
         ms = C.c_float()
         check(lib().rt_renderer_last_kernel_ms(self.h, C.byref(ms)))
@@ -411,6 +421,10 @@ class MultiRenderer:
     def refine(self, n_samples):
         """rt_renderer_refine on every rank, then the usual gather + assembly."""
         check(lib().rt_multi_renderer_refine(self.h, n_samples))
+
+    def light_sampling(self, on=True):
+        """rt_renderer_light_sampling_enable on every rank."""
+        check(lib().rt_multi_renderer_light_sampling_enable(self.h, 1 if on else 0))
 
     def DownloadRenderbuffer(self):
         out = np.zeros((self.cfg.height, self.cfg.width, 4), dtype=np.float32)

@@ -81,6 +81,7 @@ SYMBOLS = [
     "rt_renderer_refine_info", "rt_renderer_refine_download_sums", "rt_renderer_refine_noise", "rt_multi_renderer_refine",
     "rt_renderer_aov_enable", "rt_renderer_aov_info", "rt_renderer_aov_download", "rt_denoise_params_default", "rt_renderer_denoise",
     "rt_renderer_denoise_async", "rt_renderer_denoise_download",
+    "rt_renderer_light_sampling_enable", "rt_renderer_light_sampling_info", "rt_multi_renderer_light_sampling_enable", "rt_world_quad_lights",
 ]
 
 _lib = None
@@ -200,6 +201,10 @@ def lib():
     L.rt_renderer_denoise.argtypes = [C.c_void_p, P(DenoiseParams)]
     L.rt_renderer_denoise_async.argtypes = [C.c_void_p, C.c_void_p, P(DenoiseParams)]
     L.rt_renderer_denoise_download.argtypes = [C.c_void_p, f32p, C.c_size_t]
+    L.rt_renderer_light_sampling_enable.argtypes = [C.c_void_p, C.c_uint32]
+    L.rt_renderer_light_sampling_info.argtypes = [C.c_void_p, C.c_uint32 * 2]
+    L.rt_multi_renderer_light_sampling_enable.argtypes = [C.c_void_p, C.c_uint32]
+    L.rt_world_quad_lights.argtypes = [P(WorldFlat), C.c_uint32 * 16, C.c_float * 16, P(C.c_uint32)]
     L.rt_multi_renderer_create.argtypes = [P(RenderConfig), P(Camera), P(WorldFlat), C.c_uint32, C.c_void_p, P(C.c_void_p)]
     L.rt_multi_renderer_destroy.argtypes = [C.c_void_p]
     L.rt_multi_renderer_destroy.restype = None

@@ -53,6 +53,7 @@ constexpr uint32_t stream_key(bool exact, bool filter, int world, int ext = 0, b
     return (uint32_t)exact | (uint32_t)filter << 1 | (uint32_t)world << 2 | (uint32_t)ext << 4 | (uint32_t)big << 6 | (uint32_t)wide << 7 | (uint32_t)tol << 8;
 }
 constexpr uint32_t RT_KEY_XCHG = 1u << 9;
+constexpr uint32_t RT_KEY_NEE = 1u << 10;   // light sampling (rt_renderer_light_sampling_enable): the NEE form of an EXT >= 1 stack-walk or list key
 
 // The kernel of a renderer: variant = the resolved one (2 verbatim box tests, 3 fast exact division, 4 filtered predicates, 5 ray exchange), tol = requested
 // as variant 6.  rt_renderer::resolve_variant() has refused what has no kernel (3 and 4 on lists and trees, 4 to 6 beyond the LDS or the reference's feature set).
@@ -78,6 +79,8 @@ static uint32_t stream_kernel_key(uint32_t variant, bool tol, const DeviceScene&
 static const void* stream_kernel_for(uint32_t key) {
 #define RT_KERNEL(exact, filter, world, ext, big, wide, tol) \
     case stream_key(exact, filter, world, ext, big, wide, tol): return reinterpret_cast<const void*>(&render_kernel_stream<exact, filter, RT_STREAM_BLOCK, world, ext, big, wide, tol>)
+#define RT_KERNEL_NEE(exact, world, ext, big, wide) \
+    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_NEE: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, true>)
     switch (key) {   // arguments: exact, filter, world, ext, big, wide, tol
         case RT_KEY_XCHG: return reinterpret_cast<const void*>(&render_kernel_xchg<RT_XCHG_BLOCK>);
         RT_KERNEL(true, false, RT_WORLD_BVH_QUEUE, 2, true, true, false); RT_KERNEL(true, false, RT_WORLD_BVH_QUEUE, 1, true, true, false); RT_KERNEL(true, false, RT_WORLD_BVH_QUEUE, 0, true, true, false);
@@ -88,9 +91,16 @@ static const void* stream_kernel_for(uint32_t key) {
         RT_KERNEL(false, false, RT_WORLD_BVH, 2, false, false, false); RT_KERNEL(true, false, RT_WORLD_BVH, 2, false, false, false); RT_KERNEL(false, false, RT_WORLD_BVH, 1, false, false, false); RT_KERNEL(true, false, RT_WORLD_BVH, 1, false, false, false);
         RT_KERNEL(true, false, RT_WORLD_LIST, 0, false, false, false); RT_KERNEL(true, false, RT_WORLD_NODE_TREE, 0, false, false, false);
         RT_KERNEL(false, false, RT_WORLD_BVH, 0, false, false, true); RT_KERNEL(true, false, RT_WORLD_BVH, 0, false, false, false); RT_KERNEL(false, true, RT_WORLD_BVH, 0, false, false, false); RT_KERNEL(false, false, RT_WORLD_BVH, 0, false, false, false);
+        // light sampling: every EXT >= 1 list and stack-walk family once more (arguments: exact, world, ext, big, wide)
+        RT_KERNEL_NEE(true, RT_WORLD_LIST, 2, true, true); RT_KERNEL_NEE(true, RT_WORLD_LIST, 1, true, true);
+        RT_KERNEL_NEE(false, RT_WORLD_BVH, 2, true, true); RT_KERNEL_NEE(true, RT_WORLD_BVH, 2, true, true); RT_KERNEL_NEE(false, RT_WORLD_BVH, 1, true, true); RT_KERNEL_NEE(true, RT_WORLD_BVH, 1, true, true);
+        RT_KERNEL_NEE(false, RT_WORLD_BVH, 2, true, false); RT_KERNEL_NEE(true, RT_WORLD_BVH, 2, true, false); RT_KERNEL_NEE(false, RT_WORLD_BVH, 1, true, false); RT_KERNEL_NEE(true, RT_WORLD_BVH, 1, true, false);
+        RT_KERNEL_NEE(true, RT_WORLD_LIST, 2, false, false); RT_KERNEL_NEE(true, RT_WORLD_LIST, 1, false, false);
+        RT_KERNEL_NEE(false, RT_WORLD_BVH, 2, false, false); RT_KERNEL_NEE(true, RT_WORLD_BVH, 2, false, false); RT_KERNEL_NEE(false, RT_WORLD_BVH, 1, false, false); RT_KERNEL_NEE(true, RT_WORLD_BVH, 1, false, false);
         default: return nullptr;
     }
 #undef RT_KERNEL
+#undef RT_KERNEL_NEE
 }
 
 // the feature pass's kernel: the world's own traversal, so that a kernel carries one traversal stack
@@ -151,6 +161,10 @@ struct rt_renderer {
     bool aov_on = false;
     uint32_t aov_max = 0, aov_done = 0;
     const char* aov_refused = nullptr;   // the first material of the world the feature pass does not cover (a medium, a noise or an image texture)
+    // light sampling (rt_renderer_light_sampling_enable): the world's quad lights as rt_world_quad_lights gave them at creation (or why it gave none), and —
+    // from the first enable — the scene image with the light table behind it, the NEE form of this renderer's kernel and the LDS that one takes
+    struct { bool on = false; uint32_t n = 0, quad[RT_MAX_LIGHTS] = {}; float area[RT_MAX_LIGHTS] = {}; std::string refused;
+             DevBuf blob; const void* kernel = nullptr; uint32_t lds_bytes = 0, blocks_per_cu = 0; } nee;
     // denoiser (rt_renderer_denoise): guide records, the two colour buffers the iterations ping-pong, the output frame; allocated at first use
     DevBuf dn_g0, dn_g1, dn_a, dn_b, dn_out;
     // ordering between refine steps and the filter, whichever streams the caller gives them: refine_ev = end of the last refine step (the filter
@@ -324,7 +338,7 @@ struct rt_renderer {
             p.out = out;
             return launch_render(p, variant, st);
         }
-        const uint32_t end_s = first_s + n_s, n_pixels = (uint32_t)n_local_pixels(tm), grid = n_cus * stream_blocks_per_cu;
+        const uint32_t end_s = first_s + n_s, n_pixels = (uint32_t)n_local_pixels(tm), grid = n_cus * (nee.on ? nee.blocks_per_cu : stream_blocks_per_cu);
         StreamParams p = call_params(refine ? end_s : cfg.samples_per_pixel);
         std::vector<hipEvent_t>& ring = kev[n_renders % RT_TIMES_RING];   // the event ring: this call's slot, four events per pass, created at first use
         const uint32_t call_passes = kev_passes[n_renders % RT_TIMES_RING] = (n_s + pass_spp - 1u) / pass_spp;
@@ -358,7 +372,7 @@ struct rt_renderer {
             XchgParams xp;
             if (variant == 5) { xp = xchg_params(p); args[0] = &xp; }
             HIP_TRY(hipEventRecord(ke[1], st));
-            HIP_TRY(hipLaunchKernel(stream_kernel, dim3(grid), dim3(stream_block), args, stream_lds_bytes, st));
+            HIP_TRY(hipLaunchKernel(nee.on ? nee.kernel : stream_kernel, dim3(grid), dim3(stream_block), args, nee.on ? nee.lds_bytes : stream_lds_bytes, st));
             HIP_TRY(hipEventRecord(ke[2], st));
 #ifdef RT_PHASE_TIMERS
             if (const int rc = report_phase_timers(phase_acc, st)) return rc;
@@ -392,6 +406,7 @@ struct rt_renderer {
         frame_params(p, spp);
         p.scene = scene.packed;
         p.scene.n_top = scene.big ? n_top : 0u;
+        if (nee.on) { p.scene.blob = nee.blob.as<uint4>(); p.scene.blob_vec4 += 1u + nee.n; }   // the same image with the light table behind it
         p.samples = samples.as<float4>();
         p.inner_keep = tune[0] ? tune[0] : 1u; p.shade_min = tune[1]; p.leaf_min = tune[2];
         const size_t n_pass = n_local_pixels(tm) * pass_spp;   // 16-B records per array
@@ -492,6 +507,7 @@ extern "C" int rt_renderer_create(const rt_render_config* cfg, const rt_camera* 
         else if (t == RT_MAT_LAMBERTIAN_NOISE) r->aov_refused = "a noise texture (RT_MAT_LAMBERTIAN_NOISE)";
         else if (t == RT_MAT_LAMBERTIAN_IMAGE) r->aov_refused = "an image texture (RT_MAT_LAMBERTIAN_IMAGE)";
     }
+    if (rt_world_quad_lights(world, r->nee.quad, r->nee.area, &r->nee.n) != RT_OK) { r->nee.refused = rt_last_error(); r->nee.n = 0; }
     r->cam = *cam;   // the camera of the first launch; rt_renderer_set_camera replaces it (Renderer.cu:117 reads the caller's camera at every Render())
     rc = r->scene.upload(world);
     if (rc != RT_OK) { delete r; return rc; }
@@ -568,6 +584,50 @@ extern "C" int rt_renderer_set_camera(rt_renderer* r, const rt_camera* cam) {
     r->cam = *cam;          // travels by value in the kernel arguments of the NEXT launch; launches already enqueued keep theirs
     r->refine_done = 0;     // samples accumulated under another camera belong to another frame
     r->aov_done = 0;        // ... and so do their first hits
+    return RT_OK;
+}
+
+// Light sampling.  Off: every launch is what it was.  On: the NEE form of the renderer's own kernel, on a copy of the scene image that ends with the light table.
+extern "C" int rt_renderer_light_sampling_enable(rt_renderer* r, uint32_t on) {
+    if (!r) return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: null renderer");
+    if (on > 1) return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: on must be 0 or 1");
+    if ((on != 0) == r->nee.on) return RT_OK;   // nothing changes, the refinement goes on
+    if (on) {
+        if (r->variant < 2 || r->variant == 5 || r->tol)
+            return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: kernel variant %u has no light-sampling form (the baseline kernel 1, the ray exchange 5 and the tolerance mode 6 do not; use variant 0, 2 or 3)", r->tol ? 6u : r->variant);
+        if (!r->nee.refused.empty()) return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: %s", r->nee.refused.c_str());
+        HIP_TRY(hipSetDevice(r->cfg.device));
+        if (!r->nee.kernel) {
+            const uint32_t table_vec4 = 1u + r->nee.n;
+            PackedSceneRef with_table = r->scene.packed;
+            with_table.blob_vec4 += table_vec4;
+            const uint32_t lds = (uint32_t)stream_kernel_lds_bytes(r->stream_block, with_table, r->scene.big, r->scene.wide, r->n_top);
+            if (lds > RT_LDS_PER_CU)
+                return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: the light table (%u bytes) does not fit beside the scene image in the LDS", table_vec4 * 16u);
+            const void* k = stream_kernel_for(stream_kernel_key(r->variant, false, r->scene) | RT_KEY_NEE);
+            if (!k) return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: this world's kernel has no light-sampling form");
+            std::vector<uint4> table(table_vec4, make_uint4(0u, 0u, 0u, 0u));
+            table[0].x = r->nee.n;
+            for (uint32_t i = 0; i < r->nee.n; i++) { table[1u + i].x = r->nee.quad[i]; std::memcpy(&table[1u + i].y, &r->nee.area[i], 4); }
+            HIP_TRY(r->nee.blob.alloc(((size_t)r->scene.packed.blob_vec4 + table_vec4) * sizeof(uint4)));
+            HIP_TRY(hipMemcpy(r->nee.blob.p, r->scene.blob.p, (size_t)r->scene.packed.blob_vec4 * sizeof(uint4), hipMemcpyDeviceToDevice));
+            HIP_TRY(hipMemcpy(r->nee.blob.as<uint4>() + r->scene.packed.blob_vec4, table.data(), table.size() * sizeof(uint4), hipMemcpyHostToDevice));
+            HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            r->nee.lds_bytes = lds;
+            r->nee.blocks_per_cu = std::min(2u, RT_LDS_PER_CU / lds);
+            r->nee.kernel = k;
+        }
+    }
+    r->nee.on = on != 0;    // of the NEXT launch; launches already enqueued keep their kernel and their image (the image with the table stays allocated)
+    r->refine_done = 0;     // samples drawn by the other estimator belong to another sequence
+    r->aov_done = 0;
+    return RT_OK;
+}
+
+extern "C" int rt_renderer_light_sampling_info(rt_renderer* r, uint32_t out[2]) {
+    if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_info: null argument");
+    out[0] = r->nee.on ? 1u : 0u;
+    out[1] = r->nee.refused.empty() ? r->nee.n : 0u;
     return RT_OK;
 }
 

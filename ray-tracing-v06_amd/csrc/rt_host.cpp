@@ -498,6 +498,33 @@ extern "C" int rt_scene_get_flat(const rt_scene* s, rt_world_flat* out) {
 
 // perlin::perlin() ("The Next Week"): randvec[i] = unit_vector(vec3::random(-1, 1)); perm = identity shuffled by
 // `for i = n-1 .. 1: swap(p[i], p[random_int(0, i)])`, three times.  Uniforms: the build's sequential host stream, id 0x9E81.
+// The lights of light sampling: the quads whose material is a diffuse light, in quad-index order, each with the area of its
+// parallelogram — sqrt(dot(n, n)) of n = cross(u, v), fp32, in that order — or the reason this world has no light-sampling form.
+extern "C" int rt_world_quad_lights(const rt_world_flat* w, uint32_t out_quad[RT_MAX_LIGHTS], float out_area[RT_MAX_LIGHTS], uint32_t* out_n) {
+    if (!w || !out_quad || !out_area || !out_n) return rt_fail(RT_ERR_INVALID, "rt_world_quad_lights: null argument");
+    *out_n = 0;
+    if ((w->n_quads && !w->quads) || (w->n_materials && !w->materials)) return rt_fail(RT_ERR_INVALID, "rt_world_quad_lights: world array is null");
+    if (w->traversal != RT_TRAVERSAL_STACK)
+        return rt_fail(RT_ERR_INVALID, "light sampling: the world has a queue or wide4 traversal (RT_TRAVERSAL_QUEUE, RT_TRAVERSAL_WIDE4); the light-sampling kernels walk the tree with the stack");
+    for (uint32_t i = 0; i < w->n_materials; i++)
+        if (w->materials[i].type == RT_MAT_ISOTROPIC)
+            return rt_fail(RT_ERR_INVALID, "light sampling: the world has a constant medium (RT_MAT_ISOTROPIC), whose hit test draws from the path's RNG stream");
+    uint32_t n = 0;
+    for (uint32_t i = 0; i < w->n_quads; i++) {
+        const rt_quad& q = w->quads[i];
+        if (q.mat >= w->n_materials) return rt_fail(RT_ERR_INVALID, "quad %u: material index out of range", i);
+        if (w->materials[q.mat].type != RT_MAT_DIFFUSE_LIGHT) continue;
+        if (n == RT_MAX_LIGHTS) return rt_fail(RT_ERR_INVALID, "light sampling: the world has more than %d quad lights", RT_MAX_LIGHTS);
+        const f3 nrm = cross(mk3(q.u[0], q.u[1], q.u[2]), mk3(q.v[0], q.v[1], q.v[2]));
+        out_quad[n] = i;
+        out_area[n] = sqrtf(dot(nrm, nrm));
+        n++;
+    }
+    if (n == 0) return rt_fail(RT_ERR_INVALID, "light sampling: the world has no quad light (a quad whose material is RT_MAT_DIFFUSE_LIGHT); sphere lights emit but are not sampled");
+    *out_n = n;
+    return RT_OK;
+}
+
 extern "C" int rt_scene_set_perlin(rt_scene* s, uint64_t seed) {
     if (!s) return rt_fail(RT_ERR_INVALID, "rt_scene_set_perlin: null scene");
     Rng g;

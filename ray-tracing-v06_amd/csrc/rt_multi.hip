@@ -258,6 +258,15 @@ extern "C" int rt_multi_renderer_set_camera(rt_multi_renderer* m, const rt_camer
     return RT_OK;
 }
 
+extern "C" int rt_multi_renderer_light_sampling_enable(rt_multi_renderer* m, uint32_t on) {
+    if (!m) return rt_fail(RT_ERR_INVALID, "rt_multi_renderer_light_sampling_enable: null renderer");
+    for (rt_renderer* r : m->parts) {   // every rank holds the same world on the same variant: the first refuses what any would, before any part changes
+        const int rc = rt_renderer_light_sampling_enable(r, on);
+        if (rc != RT_OK) return rc;
+    }
+    return RT_OK;
+}
+
 extern "C" int rt_multi_renderer_download(rt_multi_renderer* m, float* host_rgba, size_t n_floats) {
     if (!m || !host_rgba) return rt_fail(RT_ERR_INVALID, "rt_multi_renderer_download: null argument");
     const size_t need = (size_t)m->width * m->height * 4;

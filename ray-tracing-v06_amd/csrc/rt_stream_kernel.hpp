@@ -206,8 +206,13 @@ __device__ __forceinline__ WideNodeData fetch_wide_node(const char* nodes, const
 //      the per-lane stacks and leaves that much more of the LDS for the top of the tree.
 // TOL (variant 6, opt-in): the hot loop's plane parameters are (b - o) * RN(1/d) instead of the exact quotients — inside north_star's |delta| < 1e-3,
 //      not bit-exact by construction (rt_fastdiv.hpp: slab_near_far_tolerant).  LDS-resident RT_WORLD_BVH worlds of the reference's feature set (EXT == 0) only.
-template <bool EXACT, bool FILTER, int BLOCK, int WORLD = RT_WORLD_BVH, int EXT = 0, bool BIG = false, bool WIDE = BIG, bool TOL = false>
+// NEE (rt_renderer_light_sampling_enable, opt-in; EXT >= 1 only): a Lambertian / checker hit draws its next direction from the mixture of its own cosine
+//      distribution and a distribution over the world's quad lights, and weighs the path by the ratio of the densities.  The light table —
+//      a header (n_l, -, -, -), then (quad index, area, -, -) per light — lies behind the quads' shade records in the image the NEE launches are given, so it
+//      costs no kernel argument: the other instantiations neither see it nor pay for it.
+template <bool EXACT, bool FILTER, int BLOCK, int WORLD = RT_WORLD_BVH, int EXT = 0, bool BIG = false, bool WIDE = BIG, bool TOL = false, bool NEE = false>
 __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(StreamParams p) {
+    static_assert(!NEE || (EXT >= 1 && WORLD != RT_WORLD_BVH_QUEUE), "light sampling: worlds with quads, walked by the stack or as a list");
     extern __shared__ uint4 lds[];
     const uint32_t tid = threadIdx.x;
     const uint32_t lane = tid & 63u;
@@ -594,6 +599,8 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                 RT_PT(10);
                 f3 scatter_dir = mk3(0.0f);
                 bool scattered_ok = !path_over;
+                float nee_weight = 1.0f;   // NEE: cosine density / mixture density of the direction taken, at a Lambertian / checker hit
+                bool nee_weighted = false;
                 if (path_over) {
                     // nothing to sample: the path ends here with what it has collected
                 } else if (is_diel) {
@@ -601,7 +608,11 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                     else scatter_dir = refract(unit_dir, normal, ior_ratio);
                 } else {
                     RT_PT(11);
-                    f3 on_unit = rng_on_unit3(rng);
+                    // NEE: the first draw of a Lambertian / checker hit picks the half of the mixture; the light half draws no on-unit vector
+                    const bool nee_mat = NEE && (mtype == RT_MAT_LAMBERTIAN || mtype == RT_MAT_LAMBERTIAN_CHECKER);
+                    const bool to_light = nee_mat && rng.next() < 0.5f;
+                    f3 on_unit = mk3(0.0f);
+                    if (!NEE || !to_light) on_unit = rng_on_unit3(rng);
                     RT_PT(12);
                     if (EXT && mtype == RT_MAT_ISOTROPIC) {
                         scatter_dir = on_unit;   // isotropic phase function: any direction, never absorbed
@@ -609,8 +620,48 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                         scatter_dir = reflect(ray.d, normal) + on_unit * mparam;
                         scattered_ok = !(dot(scatter_dir, normal) < 0 || near_zero(scatter_dir));
                     } else {
+                        if (NEE && to_light) {   // a point of light i, uniform over its parallelogram; the direction stays unnormalised
+                            const float4* lights = quads + p.scene.n_quads * 5u;
+                            const uint32_t n_l = __float_as_uint(lights[0].x);
+                            uint32_t li = 0u;
+                            if (n_l > 1u) li = min((uint32_t)(rng.next() * (float)n_l), n_l - 1u);
+                            const float la = rng.next();
+                            const float lb = rng.next();
+                            const float4* qd = quads + __float_as_uint(lights[1u + li].x) * 4u;
+                            const float4 a0 = qd[0], a1 = qd[1], a2 = qd[2];
+                            scatter_dir = ((mk3(a0.x, a0.y, a0.z) + mk3(a1.x, a1.y, a1.z) * la) + mk3(a1.w, a2.x, a2.y) * lb) - hit_p;
+                        } else {
                         scatter_dir = normal + on_unit;
                         scattered_ok = !near_zero(scatter_dir);
+                        }
+                        if (NEE && nee_mat && scattered_ok) {
+                            // densities of the direction under both halves, from hit_p before the offset: cosine, and per light the solid-angle density
+                            // of its area where the ray (hit_p, d) meets it — quad::hit as the leaf phase runs it, on a fresh trace's interval
+                            const f3 d = scatter_dir;
+                            const float len2 = dot(d, d), len = sqrtf(len2), cosn = dot(normal, d) / len;
+                            const float pdf_cos = cosn > 0 ? cosn * 0.318309886f : 0.0f;
+                            const float4* lights = quads + p.scene.n_quads * 5u;
+                            const uint32_t n_l = __float_as_uint(lights[0].x);
+                            Ray lray;
+                            lray.o = hit_p; lray.d = d; lray.time = ray.time;
+                            float pdf_light = 0.0f;
+                            for (uint32_t j = 0; j < n_l; j++) {
+                                const float4 lt = lights[1u + j];
+                                const float4* qd = quads + __float_as_uint(lt.x) * 4u;
+                                const float4 a0 = qd[0], a1 = qd[1], a2 = qd[2], a3 = qd[3];
+                                const f3 ln = mk3(a2.z, a2.w, a3.x);
+                                HitRec tmp;
+                                tmp.distance = RT_MISS_DIST; tmp.normal = mk3(0.0f); tmp.prim = -1; tmp.mat = 0;
+                                float pl_j = 0.0f;
+                                if (quad_closest_intersection(mk3(a0.x, a0.y, a0.z), a0.w, mk3(a1.x, a1.y, a1.z), mk3(a1.w, a2.x, a2.y), ln, mk3(a3.y, a3.z, a3.w), 0u, 0, lray, tmp))
+                                    pl_j = ((tmp.distance * tmp.distance) * len2) / ((fabsf(dot(d, ln)) / len) * lt.y);
+                                pdf_light = pdf_light + pl_j;
+                            }
+                            pdf_light = pdf_light / (float)n_l;
+                            const float pdf = 0.5f * pdf_cos + 0.5f * pdf_light;
+                            if (pdf_cos == 0.0f || !(pdf > 0)) scattered_ok = false;   // below the surface, or a density that is not a number: a failed scatter
+                            else { nee_weight = pdf_cos / pdf; nee_weighted = true; }
+                        }
                         if (mtype == RT_MAT_LAMBERTIAN_CHECKER) {
                             const rt_material& mg = p.scene.mats[mat_bits & RT_MAT_INDEX_MASK];
                             albedo = checker_value(albedo, mk3(mg.albedo2[0], mg.albedo2[1], mg.albedo2[2]), mparam, hit_p);
@@ -632,6 +683,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                 if (!scattered_ok) {
                     RT_EMIT_DARK();
                 } else {
+                    if (NEE && nee_weighted) albedo = albedo * nee_weight;
                     atten = atten * albedo;
                     ray.o = hit_p;
                     ray.d = scatter_dir;  // time is inherited

@@ -17,6 +17,11 @@ last refined frame: bit for bit the frame a one-shot render at that sample count
 also accumulates first-hit feature buffers (rt_renderer_aov_enable) while refining.  --denoise writes the edge-aware filtered frame
 (rt_renderer_denoise) next to the refined one, as out_denoised.png; --aov PREFIX writes PREFIX_normal.png (n * 0.5 + 0.5),
 PREFIX_depth.png (nearest white, misses black) and PREFIX_albedo.png.  One GPU; worlds with media, noise or image textures are refused.
+
+    python tools/render.py --scene cornell_box --spp 64 --light-sampling --out out.png
+
+samples the world's quad lights at every Lambertian hit (rt_renderer_light_sampling_enable): the same expected image from far fewer
+samples where a small emitter lights the world.  Works with every mode above; refused for worlds without a quad light or with a medium.
 """
 import argparse, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -35,6 +40,7 @@ ap.add_argument("--refine", type=int, default=0, metavar="STEP", help="render in
 ap.add_argument("--until", type=float, default=None, metavar="NOISE", help="with --refine: stop once the noise figure is below NOISE (one GPU)")
 ap.add_argument("--denoise", action="store_true", help="with --refine: also write the denoised frame (<out>_denoised.<ext>)")
 ap.add_argument("--aov", default=None, metavar="PREFIX", help="with --refine: write PREFIX_normal.png, PREFIX_depth.png, PREFIX_albedo.png")
+ap.add_argument("--light-sampling", action="store_true", help="next-event estimation over the world's quad lights (rt_renderer_light_sampling_enable)")
 ap.add_argument("--out", default="render.png")
 a = ap.parse_args()
 if a.refine < 0 or (a.until is not None and (a.refine == 0 or a.gpus > 1)):
@@ -60,6 +66,8 @@ if a.refine:
     step_spp = min(a.refine, a.spp)   # what one pass is sized for; the steps go on to --spp
     r = (p.MultiRenderer.MakeRenderer(W, H, step_spp, a.depth, cam, scene.getWorldPtr(), a.gpus, seed=a.seed) if a.gpus > 1
          else p.Renderer.MakeRenderer(W, H, step_spp, a.depth, cam, scene.getWorldPtr(), seed=a.seed, device=a.device))
+    if a.light_sampling:
+        r.light_sampling(True)
     if a.denoise or a.aov:
         r.enable_aov()
     samples, ms = 0, 0.0
@@ -75,10 +83,14 @@ if a.refine:
             break
 elif a.gpus > 1:
     r = p.MultiRenderer.MakeRenderer(W, H, a.spp, a.depth, cam, scene.getWorldPtr(), a.gpus, seed=a.seed)
+    if a.light_sampling:
+        r.light_sampling(True)
     r.Render()
     ms = r.times()[0]     # host wall-clock of Render(): all shards, the exchange, the assembly
 else:
     r = p.Renderer.MakeRenderer(W, H, a.spp, a.depth, cam, scene.getWorldPtr(), seed=a.seed, device=a.device)
+    if a.light_sampling:
+        r.light_sampling(True)
     r.Render()
     ms = r.last_kernel_ms()
 fb = r.DownloadRenderbuffer()
@@ -105,4 +117,4 @@ if a.aov:
     image_io.write_png(a.aov + "_albedo.png", np.concatenate([f["albedo"], one], axis=2))
     extra["aov"] = [a.aov + s for s in ("_normal.png", "_depth.png", "_albedo.png")]
 print(json.dumps({**extra, "scene": a.scene, "width": W, "height": H, "spp": samples, "max_depth": a.depth, "render_ms": round(ms, 3),
-                  "msamples_per_s": round(W * H * samples / ms / 1e3, 1), "gpus": a.gpus, "out": a.out}))
+                  "msamples_per_s": round(W * H * samples / ms / 1e3, 1), "gpus": a.gpus, "light_sampling": a.light_sampling, "out": a.out}))
