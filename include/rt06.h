@@ -332,6 +332,14 @@ int rt_renderer_pass_info(rt_renderer* r, uint64_t out[4]);
  * LDS-resident (0: baseline kernel, or a world too large for the LDS, served from global memory / L2 with 32-bit
  * references), out[2] = workgroup size, out[3] = workgroups per CU.                                              */
 int rt_renderer_kernel_info(rt_renderer* r, uint32_t out[4]);
+/* Which instantiation the NEXT launch runs (a diagnostic: it changes no launch).  out[0] = the kernel: RT_KERNEL_BASELINE (variant 1),
+ * RT_KERNEL_STREAM (render_kernel_stream) or RT_KERNEL_XCHG (render_kernel_xchg, variant 5); for RT_KERNEL_STREAM out[1..8] are the template
+ * arguments read back from the key the kernel table is indexed with: exact, filter, world (RT_WORLD_*; 3 = the BVH walked by the queue / wide4
+ * traversal), ext, big, wide, tol, and nee = 1 while light sampling is on.  The other two kernels have no such arguments: zeros.               */
+#define RT_KERNEL_BASELINE 0
+#define RT_KERNEL_STREAM 1
+#define RT_KERNEL_XCHG 2
+int rt_renderer_kernel_form(rt_renderer* r, uint32_t out[9]);
 /* Renderer::DownloadRenderbuffer (Renderer.cu:94-96): width*height*4 floats,
  * row-major, row 0 = bottom.  Only valid for world_size == 1.               */
 int rt_renderer_download(rt_renderer* r, float* host_rgba, size_t n_floats);

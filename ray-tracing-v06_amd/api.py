@@ -372,6 +372,15 @@ class Renderer:
         check(lib().rt_renderer_kernel_info(self.h, C.byref(out)))
         return {"variant": out[0], "lds_resident": bool(out[1]), "workgroup": out[2], "workgroups_per_cu": out[3]}
 
+    def kernel_form(self):
+        """{'kernel': 'baseline' | 'stream' | 'xchg', 'exact', 'filter', 'world', 'ext', 'big', 'wide', 'tol', 'nee'}: the instantiation the next
+        launch runs (rt_renderer_kernel_form); the template arguments are zeros for the baseline and the exchange kernel."""
+        out = (C.c_uint32 * 9)()
+        check(lib().rt_renderer_kernel_form(self.h, out))
+        form = {"kernel": ("baseline", "stream", "xchg")[out[0]]}
+        form.update(zip(("exact", "filter", "world", "ext", "big", "wide", "tol", "nee"), out[1:]))
+        return form
+
     def DownloadRenderbuffer(self):
         out = np.zeros((self.cfg.height, self.cfg.width, 4), dtype=np.float32)
         check(lib().rt_renderer_download(self.h, out, out.size))

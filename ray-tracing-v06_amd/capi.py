@@ -82,6 +82,7 @@ SYMBOLS = [
     "rt_renderer_aov_enable", "rt_renderer_aov_info", "rt_renderer_aov_download", "rt_denoise_params_default", "rt_renderer_denoise",
     "rt_renderer_denoise_async", "rt_renderer_denoise_download",
     "rt_renderer_light_sampling_enable", "rt_renderer_light_sampling_info", "rt_multi_renderer_light_sampling_enable", "rt_world_quad_lights",
+    "rt_renderer_kernel_form",
 ]
 
 _lib = None
@@ -184,6 +185,7 @@ def lib():
     L.rt_renderer_render_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.rt_renderer_last_kernel_ms.argtypes = [C.c_void_p, P(C.c_float)]
     L.rt_renderer_kernel_info.argtypes = [C.c_void_p, P(C.c_uint32 * 4)]
+    L.rt_renderer_kernel_form.argtypes = [C.c_void_p, C.c_uint32 * 9]
     L.rt_renderer_kernel_times.argtypes = [C.c_void_p, C.c_uint32, C.c_float * 3]
     L.rt_renderer_set_camera.argtypes = [C.c_void_p, P(Camera)]
     L.rt_multi_renderer_set_camera.argtypes = [C.c_void_p, P(Camera)]

@@ -54,6 +54,11 @@ constexpr uint32_t stream_key(bool exact, bool filter, int world, int ext = 0, b
 }
 constexpr uint32_t RT_KEY_XCHG = 1u << 9;
 constexpr uint32_t RT_KEY_NEE = 1u << 10;   // light sampling (rt_renderer_light_sampling_enable): the NEE form of an EXT >= 1 stack-walk or list key
+// a stream key read back into render_kernel_stream's template arguments, in stream_key()'s order, then NEE: what rt_renderer_kernel_form reports
+static void stream_key_fields(uint32_t key, uint32_t out[8]) {
+    out[0] = key & 1u; out[1] = key >> 1 & 1u; out[2] = key >> 2 & 3u; out[3] = key >> 4 & 3u;
+    out[4] = key >> 6 & 1u; out[5] = key >> 7 & 1u; out[6] = key >> 8 & 1u; out[7] = key >> 10 & 1u;
+}
 
 // The kernel of a renderer: variant = the resolved one (2 verbatim box tests, 3 fast exact division, 4 filtered predicates, 5 ray exchange), tol = requested
 // as variant 6.  rt_renderer::resolve_variant() has refused what has no kernel (3 and 4 on lists and trees, 4 to 6 beyond the LDS or the reference's feature set).
@@ -850,6 +855,19 @@ extern "C" int rt_renderer_kernel_info(rt_renderer* r, uint32_t out[4]) {
     out[1] = (r->variant >= 2 && !r->scene.big) ? 1u : 0u;
     out[2] = r->variant >= 2 ? r->stream_block : 64u;
     out[3] = r->variant >= 2 ? r->stream_blocks_per_cu : 0u;
+    return RT_OK;
+}
+
+extern "C" int rt_renderer_kernel_form(rt_renderer* r, uint32_t out[9]) {
+    if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_kernel_form: null argument");
+    for (int i = 0; i < 9; i++) out[i] = 0u;
+    if (r->variant < 2) { out[0] = RT_KERNEL_BASELINE; return RT_OK; }
+    // the key launch() resolves: plan()'s for the plain kernel, rt_renderer_light_sampling_enable's while sampling is on
+    const uint32_t key = r->nee.on ? stream_kernel_key(r->variant, false, r->scene) | RT_KEY_NEE : stream_kernel_key(r->variant, r->tol, r->scene);
+    if (stream_kernel_for(key) != (r->nee.on ? r->nee.kernel : r->stream_kernel)) return rt_fail(RT_ERR_INVALID, "rt_renderer_kernel_form: the key does not name the kernel the renderer holds");
+    if (key == RT_KEY_XCHG) { out[0] = RT_KERNEL_XCHG; return RT_OK; }
+    out[0] = RT_KERNEL_STREAM;
+    stream_key_fields(key, out + 1);
     return RT_OK;
 }
 

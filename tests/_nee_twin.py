@@ -8,6 +8,9 @@ orc_trace_batch tests a world's bounds before its primitives, which the bare tes
 
 Scope: pinhole cameras; worlds of spheres and quads with Lambertian, checker, metal and diffuse-light materials.  A sample that meets
 anything else (a dielectric, a medium, a textured material) is not followed: its radiance is NaN and `followed` is False.
+
+What a run exercised: radiance() and frame_samples() fill an optional `stats` dict (new_stats() names its counters), so that a test world can
+be shown to reach the estimator's edges before a kernel is compared with it.  Counting reads the values the arithmetic produced; it changes none.
 """
 import ctypes as C
 
@@ -99,6 +102,16 @@ class _Tape:
         return out * inv[:, None]
 
 
+def new_stats():
+    """light_samples[i]: light-half draws sent to light i; below_surface: light-half directions failed for pdf_cos == 0; cos_one_light /
+    cos_many_lights: cosine-half directions that met one light / two or more; checker_light_half: checker hits that took the light half;
+    light_half_unmet: light-half directions that no light's quad test accepts (the sampled point lies in a plane through the hit point: |denom| < 1e-8);
+    index_clamped: light-index draws whose uniform is 1 (one in 2^24), so that only the min(..., n_l - 1) keeps the index inside the table;
+    not_followed: samples that met something outside the twin's scope"""
+    return {"light_samples": np.zeros(MAX_LIGHTS, np.int64), "below_surface": 0, "cos_one_light": 0, "cos_many_lights": 0, "checker_light_half": 0, "light_half_unmet": 0,
+            "index_clamped": 0, "not_followed": 0}
+
+
 def _quad_hit(q, o, d):
     """quad::hit (quad_closest_intersection) of one quad on rays (o, d) over a fresh trace's interval [0, MISS): (hit, t)"""
     n = np.broadcast_to(q["normal"].astype(F), d.shape)
@@ -113,8 +126,9 @@ def _quad_hit(q, o, d):
     return hit, t
 
 
-def radiance(world, cam, width, height, max_depth, seed, gids, samples, light_sampling=False):
-    """Radiance of sample samples[i] of pixel gids[i]: ((n, 3) float32, followed (n,) bool).  world: _oracle.World, cam: _oracle.Camera (pinhole)."""
+def radiance(world, cam, width, height, max_depth, seed, gids, samples, light_sampling=False, stats=None):
+    """Radiance of sample samples[i] of pixel gids[i]: ((n, 3) float32, followed (n,) bool).  world: _oracle.World, cam: _oracle.Camera (pinhole).
+    stats: a dict of new_stats()'s shape (or an empty one, which is given it) that the run adds its counts to."""
     assert cam.type == 0, "the twin restates the pinhole camera"
     gids = np.ascontiguousarray(gids, np.uint32)
     samples = np.ascontiguousarray(samples, np.uint32)
@@ -129,6 +143,9 @@ def radiance(world, cam, width, height, max_depth, seed, gids, samples, light_sa
     mat_of_prim = np.concatenate([(prims["mat"] & ~np.uint32(PRIM_MOVING)), quads["mat"]]).astype(np.int64)
     m_type, m_albedo, m_albedo2, m_param = mats["type"].astype(np.int64), mats["albedo"].astype(F), mats["albedo2"].astype(F), mats["param"].astype(F)
 
+    if stats is not None:
+        for key, zero in new_stats().items():
+            stats.setdefault(key, zero)
     tape = _Tape(seed, gids, samples)
     rows = np.arange(n)
     with np.errstate(all="ignore"):
@@ -200,9 +217,15 @@ def radiance(world, cam, width, height, max_depth, seed, gids, samples, light_sa
                 s = np.nonzero(to_light)[0]
                 li = np.zeros(len(s), np.int64)
                 if n_l > 1:
-                    li = np.minimum((tape.next(r[s]) * F(n_l)).astype(np.uint32), np.uint32(n_l - 1)).astype(np.int64)
+                    scaled = (tape.next(r[s]) * F(n_l)).astype(np.uint32)
+                    li = np.minimum(scaled, np.uint32(n_l - 1)).astype(np.int64)
+                    if stats is not None:
+                        stats["index_clamped"] += int((scaled >= n_l).sum())
                 la = tape.next(r[s])
                 lb = tape.next(r[s])
+                if stats is not None:
+                    stats["light_samples"] += np.bincount(li, minlength=MAX_LIGHTS)
+                    stats["checker_light_half"] += int((mt[s] == 3).sum())
                 q = quads[light_idx[li]]
                 new_d[s] = ((q["Q"].astype(F) + q["u"].astype(F) * la[:, None]) + q["v"].astype(F) * lb[:, None]) - hit_p[s]
             s = np.nonzero(~to_light)[0]
@@ -230,15 +253,22 @@ def radiance(world, cam, width, height, max_depth, seed, gids, samples, light_sa
                     cosn = dot(nn, dd) / ln
                     pdf_cos = np.where(cosn > F(0), cosn * INV_PI, F(0)).astype(F)
                     pdf_light = np.zeros(len(s), F)
+                    met = np.zeros(len(s), np.int64)   # lights the direction meets (stats only)
                     for j in range(n_l):
                         q = quads[light_idx[j]]
                         qhit, qt = _quad_hit(q, hp, dd)
                         nj = np.broadcast_to(q["normal"].astype(F), dd.shape)
                         pl = ((qt * qt) * len2) / ((np.abs(dot(dd, nj)) / ln) * light_area[j])
                         pdf_light = pdf_light + np.where(qhit, pl, F(0)).astype(F)
+                        met += qhit
                     pdf_light = pdf_light / F(n_l)
                     pdf = F(0.5) * pdf_cos + F(0.5) * pdf_light
                     good = ~(pdf_cos == F(0)) & (pdf > F(0))
+                    if stats is not None:
+                        stats["below_surface"] += int((to_light[s] & (pdf_cos == F(0))).sum())
+                        stats["light_half_unmet"] += int((to_light[s] & (met == 0)).sum())
+                        stats["cos_one_light"] += int((~to_light[s] & (met == 1)).sum())
+                        stats["cos_many_lights"] += int((~to_light[s] & (met >= 2)).sum())
                     ok[s[~good]] = False
                     weight[s[good]] = pdf_cos[good] / pdf[good]
                     weighted[s[good]] = True
@@ -249,14 +279,16 @@ def radiance(world, cam, width, height, max_depth, seed, gids, samples, light_sa
             ray_d[r] = new_d
             ray_o[r] = hit_p + new_d * F(0.001)
             live = r
+    if stats is not None:
+        stats["not_followed"] += int((~followed).sum())
     return out, followed
 
 
-def frame_samples(world, cam, width, height, spp, max_depth, seed, light_sampling=False, first_sample=0):
+def frame_samples(world, cam, width, height, spp, max_depth, seed, light_sampling=False, first_sample=0, stats=None):
     """(height, width, spp, 3) float32: every sample of every pixel; followed (height, width, spp)"""
     gids = np.repeat(np.arange(width * height, dtype=np.uint32), spp)
     smp = np.tile(np.arange(first_sample, first_sample + spp, dtype=np.uint32), width * height)
-    rad, ok = radiance(world, cam, width, height, max_depth, seed, gids, smp, light_sampling)
+    rad, ok = radiance(world, cam, width, height, max_depth, seed, gids, smp, light_sampling, stats)
     return rad.reshape(height, width, spp, 3), ok.reshape(height, width, spp)
 
 

@@ -1,5 +1,7 @@
 """Light sampling without a GPU: the numpy twin of a whole sample is pinned to the oracle, the estimator it states is
 shown unbiased against the oracle's plain path tracer, and the host surface — symbols, the light table, the worlds it refuses — is checked.
+The matrix of kernel forms the GPU tests run (tests/_nee_worlds.py) is held against the instantiations csrc/rt_device.hip lists, and every test
+world against what it is there to exercise, by the twin's own counts: a world that stops reaching an edge fails here, before any GPU is needed.
 
 The twin (tests/_nee_twin.py) is what the GPU tests of tests/test_gpu_light_sampling.py compare the kernels with, so the first test here
 pins it to orc_radiance_batch with sampling off before anything is compared against it."""
@@ -12,11 +14,13 @@ import numpy as np
 import pytest
 
 import _nee_twin as T
+import _nee_worlds as NW
 import _oracle as O
 from _common import ROOT, as_oracle_world, bits_equal, mismatch_report, pkg
 
 SEED = 1984
-SYMBOLS = ["rt_renderer_light_sampling_enable", "rt_renderer_light_sampling_info", "rt_multi_renderer_light_sampling_enable", "rt_world_quad_lights"]
+SYMBOLS = ["rt_renderer_light_sampling_enable", "rt_renderer_light_sampling_info", "rt_multi_renderer_light_sampling_enable", "rt_world_quad_lights",
+           "rt_renderer_kernel_form"]
 
 
 def cornell_camera(W, H):
@@ -112,8 +116,69 @@ def test_symbols_are_declared_exported_bound_and_mirrored():
         assert getattr(L, name).argtypes, f"capi.py gives {name} no signature"
     assert "RT_MAX_LIGHTS 16" in header
     assert "void SetLightSampling(bool on)" in open(os.path.join(ROOT, "include", "rt06", "rt06.hpp")).read()
+    assert callable(p.Renderer.kernel_form) and all(f"#define RT_KERNEL_{k}" in header for k in ("BASELINE 0", "STREAM 1", "XCHG 2"))
     assert callable(p.Renderer.light_sampling) and callable(p.Renderer.light_sampling_info) and callable(p.MultiRenderer.light_sampling)
     assert "--light-sampling" in open(os.path.join(ROOT, "tools", "render.py")).read()
+
+
+def test_form_matrix_is_the_set_of_light_sampling_instantiations():
+    """every RT_KERNEL_NEE(exact, world, ext, big, wide) of stream_kernel_for() has a recipe in the matrix the GPU tests run, and nothing else has"""
+    src = open(os.path.join(ROOT, "ray-tracing-v06_amd", "csrc", "rt_device.hip")).read()
+    table = src[src.index("switch (key)"):]
+    entries = re.findall(r"RT_KERNEL_NEE\(\s*(true|false)\s*,\s*(RT_WORLD_\w+)\s*,\s*(\d)\s*,\s*(true|false)\s*,\s*(true|false)\s*\)", table)
+    assert len(entries) == table.count("RT_KERNEL_NEE(") == 16   # every use is one the pattern reads; the #define above the switch is not a use
+    shipped = {(world, int(exact == "true"), int(ext), int(big == "true"), int(wide == "true")) for exact, world, ext, big, wide in entries}
+    assert len(shipped) == len(entries)
+    assert shipped == set(NW.FORMS), shipped ^ set(NW.FORMS)
+    assert len({NW.form_id(f) for f in NW.FORMS}) == len(NW.FORMS)
+    assert all(name in NW.MATRIX_WORLDS for name, _, _ in NW.FORMS.values())
+
+
+def test_counting_changes_no_bit_of_the_twin():
+    scene = O.Scene.cornell_box()
+    cam = cornell_camera(12, 12)
+    plain, f0 = T.frame_samples(scene.world, cam, 12, 12, 4, 6, SEED, light_sampling=True)
+    stats = {}
+    counted, f1 = T.frame_samples(scene.world, cam, 12, 12, 4, 6, SEED, light_sampling=True, stats=stats)
+    assert bits_equal(plain, counted) and np.array_equal(f0, f1)
+    assert set(stats) == set(T.new_stats()) and stats["light_samples"][0] > 0 and stats["light_samples"][1:].sum() == 0 and stats["not_followed"] == 0
+
+
+@pytest.mark.parametrize("name", NW.MATRIX_WORLDS + ("irregular_room",))
+def test_matrix_worlds_are_mostly_followed_and_leave_pixels_to_the_cross_form_check(name):
+    run = NW.run(name)
+    print(name, f"fully followed pixels {run.followed.mean():.3f}", run.stats)
+    assert run.scene.getWorldPtr().kind == (pkg().capi.WORLD_LIST if name.endswith("_list") else pkg().capi.WORLD_BVH)
+    assert 0.5 <= run.followed.mean() < 1.0   # the dielectric (and the noise and image materials) are in view; elsewhere the twin goes all the way
+    assert run.stats["not_followed"] > 0 and np.isfinite(run.sums[run.followed]).all()
+    assert run.stats["light_samples"][:run.lights].min() > 0 and run.stats["light_samples"][run.lights:].sum() == 0
+    assert run.stats["checker_light_half"] > 0 and run.stats["below_surface"] > 0
+    quad, area, n = (C.c_uint32 * 16)(), (C.c_float * 16)(), C.c_uint32()
+    assert pkg().lib().rt_world_quad_lights(C.byref(run.scene.getWorldPtr()), quad, area, C.byref(n)) == 0 and n.value == run.lights
+    if "textured" in name:   # what makes it an EXT = 2 world, and the twin leaves more samples unfollowed for it
+        _, _, mats = run.scene.arrays()
+        assert {pkg().capi.MAT_LAMBERTIAN_NOISE, pkg().capi.MAT_LAMBERTIAN_IMAGE} <= set(mats["type"].tolist())
+        assert run.stats["not_followed"] > NW.run(name.replace("textured_", "")).stats["not_followed"]
+
+
+@pytest.mark.parametrize("name", NW.EDGE_WORLDS)
+def test_edge_worlds_exercise_what_they_are_there_for(name):
+    run = NW.run(name)
+    st = run.stats
+    print(name, st)
+    assert run.followed.all() and st["not_followed"] == 0 and np.isfinite(run.sums).all()
+    assert st["light_samples"][:run.lights].min() > 0 and st["light_samples"][run.lights:].sum() == 0   # every light index receives a sample
+    assert (st["index_clamped"] > 0) == (name == "clamped_index")   # one draw in 2^24: only the world whose seed was searched for it has one
+    if name in ("sixteen_lights", "clamped_index"):
+        assert run.lights == T.MAX_LIGHTS and st["checker_light_half"] > 0
+        quads = run.scene.quads()
+        _, _, mats = run.scene.arrays()
+        _, areas = T.quad_lights(quads, mats)
+        assert len(set(areas.tolist())) == 16   # different sizes: a wrong light's area changes the weight
+    if name == "stacked_lights":
+        assert st["cos_many_lights"] > 0 and st["cos_one_light"] > 0 and st["checker_light_half"] > 0
+    if name == "lights_behind":
+        assert st["below_surface"] > 0 and st["light_half_unmet"] > 0
 
 
 def _lights(p, world):

@@ -9,6 +9,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import __graft_entry__ as G
+import _nee_twin as T
 import _oracle as O
 from _common import as_oracle_camera, as_oracle_world, bits_equal
 
@@ -80,6 +81,35 @@ def make_world(rng):
     return s, kinds, builder, big
 
 
+def light_sampling_check(s, w, cam, ck, W, H, depth, variant):
+    """A world rt_world_quad_lights accepts, with sampling on, at 4 spp on at most 48 x 32 pixels: the renderer's own form and the global-memory form must agree in
+    every bit, and both must be the twin (tests/_nee_twin.py) on every pixel it follows (pinhole cameras).  None: not applicable; else (ok, forms)."""
+    W, H, spp = min(W, 48), min(H, 32), 4
+    sums, forms = [], []
+    for env in ({}, {"RT06_FORCE_BIG": "1"}):
+        os.environ.pop("RT06_FORCE_BIG", None)
+        os.environ.update(env)
+        try:
+            r = p.Renderer.MakeRenderer(W, H, spp, depth, cam, w, variant=variant)
+            if not r.light_sampling_info()["lights"] or r.kernel_info()["variant"] not in (2, 3):
+                return None
+            r.light_sampling(True)
+        except p.capi.RtError:
+            return None   # no kernel for the world, or no light-sampling form for it
+        finally:
+            os.environ.pop("RT06_FORCE_BIG", None)
+        forms.append(r.kernel_form())
+        r.refine(spp)
+        sums.append(r.refine_sums())
+        r.close()
+    ok = bits_equal(sums[0], sums[1])
+    if ck == 0:
+        samples, followed = T.frame_samples(as_oracle_world(w), as_oracle_camera(cam), W, H, spp, depth, 1984, light_sampling=True)
+        px = followed.all(axis=2)
+        ok = ok and bits_equal(sums[0][px], T.in_order_sums(np.where(followed[..., None], samples, 0))[px])
+    return ok, forms
+
+
 fails = 0
 t0 = time.time()
 stats = {"lds": 0, "global": 0, "baseline": 0, "xchg": 0}
@@ -147,6 +177,13 @@ for seed in range(args.first, args.first + args.seeds):
         fails += 1
         bad = int((img.view(np.uint32) != ref.view(np.uint32)).sum())
         print(f"FAIL seed {seed}: kinds {kinds} builder {builder} big {big} cam {ck} {W}x{H}x{spp} depth {depth} info {info}: {bad} words differ", flush=True)
+    if ok and kinds >= 1 and info["variant"] in (2, 3):   # light sampling as one more feature of the case
+        ls = light_sampling_check(s, w, cam, ck, W, H, depth, variant)
+        if ls is not None:
+            stats["light_sampling"] = stats.get("light_sampling", 0) + 1
+            if not ls[0]:
+                fails += 1
+                print(f"FAIL seed {seed} with light sampling: kinds {kinds} builder {builder} big {big} cam {ck} depth {depth} forms {ls[1]}", flush=True)
     if (seed - args.first) % 25 == 24:
         print(f"... {seed - args.first + 1} worlds, {fails} failures, {time.time() - t0:.0f}s, paths {stats}", flush=True)
 print(f"DONE: {args.seeds} worlds, {fails} failures, paths {stats}, {time.time() - t0:.0f}s")
