@@ -2,6 +2,7 @@
 // the exact-division building blocks).  Test entry points of the C ABI; nothing here is on the render path.
 #include "rt_runtime.hpp"
 #include "rt_fastdiv.hpp"
+#include <deque>
 
 // ---------------------------------------------------------------------------------------------
 // probes
@@ -53,34 +54,6 @@ __global__ void probe_sphere_hit_kernel(size_t n, const rt_prim* prims, const rt
     dist[i] = rec.distance;
     st3(normal + 3 * i, rec.normal);
 }
-__global__ void probe_scatter_kernel(uint64_t seed, size_t n, const rt_material* mats, const float* rays, const float* dist,
-                                     const float* normals, const uint32_t* keys, int32_t* scattered, float* out_rays,
-                                     float* atten, uint32_t* draws) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    Ray in;
-    in.o = ld3(rays + 7 * i); in.d = ld3(rays + 7 * i + 3); in.time = rays[7 * i + 6];
-    HitRec rec;
-    rec.distance = dist[i]; rec.normal = ld3(normals + 3 * i); rec.prim = 0; rec.mat = 0;
-    Rng g;
-    g.init(seed, keys[2 * i], keys[2 * i + 1], RT_STREAM_RENDER);
-    Ray out;
-    out.o = mk3(0.0f); out.d = mk3(0.0f); out.time = 0.0f;
-    f3 att = mk3(0.0f);
-    scattered[i] = material_scatter(mats[i], in, rec, g, out, att) ? 1 : 0;
-    st3(out_rays + 7 * i, out.o); st3(out_rays + 7 * i + 3, out.d); out_rays[7 * i + 6] = out.time;
-    st3(atten + 3 * i, att);
-    draws[i] = g.draws;
-}
-__global__ void probe_camera_kernel(uint64_t seed, rt_camera cam, size_t n, const float* st, const uint32_t* keys, float* out_rays, uint32_t* draws) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    Rng g;
-    g.init(seed, keys[2 * i], keys[2 * i + 1], RT_STREAM_RENDER);
-    Ray r = camera_sample_ray(cam, st[2 * i], st[2 * i + 1], g);
-    st3(out_rays + 7 * i, r.o); st3(out_rays + 7 * i + 3, r.d); out_rays[7 * i + 6] = r.time;
-    draws[i] = g.draws;
-}
 // A tape of k in [1, 2^24] in place of Rng: u = k * 2^-24 (next) and (k - 2^23) * 2^-23 (next_signed), the two forms Rng returns
 // for its word (rt_math.hpp).  Reaches the edges of measure zero under the generator's stream (k = 2^23 three times, |v| == 1, ...).
 // Past the end of its tape it serves k = 2^23 + 1, which every rejection loop accepts (no hang), and keeps counting: draws > the
@@ -92,16 +65,26 @@ struct TapeRng {
     __device__ float next() { return (float)take() * 5.9604644775390625e-08f; }
     __device__ float next_signed() { return (float)(int32_t)(take() - 0x800000u) * 1.1920928955078125e-07f; }
 };
-__global__ void probe_scatter_tape_kernel(size_t n, const rt_material* mats, const float* rays, const float* dist, const float* normals,
-                                          const uint32_t* tape, const uint32_t* offsets, int32_t* scattered, float* out_rays,
-                                          float* atten, uint32_t* draws) {
+// How the generator of case i is made: a seeded Rng from (pixel, sample) keys, or a TapeRng from a tape and (offset, length) pairs
+struct KeyedRng {
+    uint64_t seed;
+    const uint32_t* keys;
+    __device__ Rng operator()(size_t i) const { Rng g; g.init(seed, keys[2 * i], keys[2 * i + 1], RT_STREAM_RENDER); return g; }
+};
+struct TapedRng {
+    const uint32_t *tape, *offsets;
+    __device__ TapeRng operator()(size_t i) const { return TapeRng{tape + offsets[2 * i], offsets[2 * i + 1], 0u}; }
+};
+template <typename MakeRng>
+__global__ void probe_scatter_kernel(MakeRng make_rng, size_t n, const rt_material* mats, const float* rays, const float* dist,
+                                     const float* normals, int32_t* scattered, float* out_rays, float* atten, uint32_t* draws) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     Ray in;
     in.o = ld3(rays + 7 * i); in.d = ld3(rays + 7 * i + 3); in.time = rays[7 * i + 6];
     HitRec rec;
     rec.distance = dist[i]; rec.normal = ld3(normals + 3 * i); rec.prim = 0; rec.mat = 0;
-    TapeRng g{tape + offsets[2 * i], offsets[2 * i + 1], 0u};
+    auto g = make_rng(i);
     Ray out;
     out.o = mk3(0.0f); out.d = mk3(0.0f); out.time = 0.0f;
     f3 att = mk3(0.0f);
@@ -110,11 +93,11 @@ __global__ void probe_scatter_tape_kernel(size_t n, const rt_material* mats, con
     st3(atten + 3 * i, att);
     draws[i] = g.draws;
 }
-__global__ void probe_camera_tape_kernel(rt_camera cam, size_t n, const float* st, const uint32_t* tape, const uint32_t* offsets,
-                                         float* out_rays, uint32_t* draws) {
+template <typename MakeRng>
+__global__ void probe_camera_kernel(MakeRng make_rng, rt_camera cam, size_t n, const float* st, float* out_rays, uint32_t* draws) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    TapeRng g{tape + offsets[2 * i], offsets[2 * i + 1], 0u};
+    auto g = make_rng(i);
     Ray r = camera_sample_ray(cam, st[2 * i], st[2 * i + 1], g);
     st3(out_rays + 7 * i, r.o); st3(out_rays + 7 * i + 3, r.d); out_rays[7 * i + 6] = r.time;
     draws[i] = g.draws;
@@ -163,106 +146,95 @@ __global__ void probe_rng_kernel(uint64_t seed, size_t n, const uint32_t* keys, 
     g.init(seed, keys[2 * i], keys[2 * i + 1], RT_STREAM_RENDER);
     for (uint32_t k = 0; k < n_draws; k++) out[i * n_draws + k] = g.next();
 }
+// ---------------------------------------------------------------------------------------------
+// The host side of one probe call: selects the device and owns the call's device buffers.  in() uploads a typed host array, out()
+// allocates a device array (cleared on request) and registers its download; finish() takes the launch's error, synchronises, then
+// downloads in the order of registration.  Counts are ELEMENTS of the pointer's type, so every array states its stride once
+// (7 * n floats: n rays with a time).  The first failure sticks: the steps after it, launch() included, do nothing and finish()
+// returns its code.  Everything runs on the null stream.
+// ---------------------------------------------------------------------------------------------
+struct ProbeRun {
+    struct Download { void* host; const DevBuf* dev; };
+    std::deque<DevBuf> bufs;   // (a deque: a buffer stays where it was made)
+    std::vector<Download> downloads;
+    int rc;
 
-#define PROBE_GRID(n) dim3((unsigned)(((n) + 127) / 128)), dim3(128)
-#define UP(buf, src, bytes) HIP_TRY((buf).upload((src), (bytes)))
-#define DOWN(dst, buf, bytes) HIP_TRY(hipMemcpy((dst), (buf).p, (bytes), hipMemcpyDeviceToHost))
-#define FINISH()                     \
-    HIP_TRY(hipGetLastError());      \
-    HIP_TRY(hipDeviceSynchronize())
+    explicit ProbeRun(int device) : rc(select_device(device)) {}
+    bool ok() const { return rc == RT_OK; }
+    void step(hipError_t e, const char* what) {
+        if (e != hipSuccess) rc = rt_fail(RT_ERR_HIP, "probe: %s failed: %s", what, hipGetErrorString(e));
+    }
+    template <typename T> const T* in(const T* host, size_t count) {
+        if (!ok()) return nullptr;
+        step(bufs.emplace_back().upload(host, count * sizeof(T)), "upload");
+        return bufs.back().as<T>();
+    }
+    template <typename T> T* out(T* host, size_t count, bool cleared = false) {
+        if (!ok()) return nullptr;
+        DevBuf& b = bufs.emplace_back();
+        step(cleared ? b.alloc_zeroed(count * sizeof(T)) : b.alloc(count * sizeof(T)), "allocation");
+        downloads.push_back({host, &b});
+        return b.as<T>();
+    }
+    static dim3 per_case(size_t n) { return dim3((unsigned)((n + 127) / 128)); }   // blocks of 128 threads, one thread per case
+    template <typename... P, typename... A> void launch(void (*kernel)(P...), dim3 grid, unsigned block, A... args) {
+        if (ok()) kernel<<<grid, dim3(block)>>>(args...);
+    }
+    int finish() {
+        if (ok()) step(hipGetLastError(), "launch");
+        if (ok()) step(hipDeviceSynchronize(), "kernel");
+        for (const Download& d : downloads)
+            if (ok()) step(hipMemcpy(d.host, d.dev->p, d.dev->bytes, hipMemcpyDeviceToHost), "download");
+        return rc;
+    }
+};
 
 extern "C" int rt_probe_aabb(int device, size_t n, const float* boxes, const float* rays, const float* max_dist, int32_t* out_hit, float* out_dist) {
     if (!boxes || !rays || !max_dist || !out_hit || !out_dist) return rt_fail(RT_ERR_INVALID, "rt_probe_aabb: null argument");
     if (n == 0) return RT_OK;
-    int rc = select_device(device);
-    if (rc != RT_OK) return rc;
-    DevBuf b, r, m, h, d;
-    UP(b, boxes, n * 24); UP(r, rays, n * 24); UP(m, max_dist, n * 4);
-    HIP_TRY(h.alloc(n * 4)); HIP_TRY(d.alloc(n * 4));
-    probe_aabb_kernel<<<PROBE_GRID(n)>>>(n, b.as<float>(), r.as<float>(), m.as<float>(), h.as<int32_t>(), d.as<float>());
-    FINISH();
-    DOWN(out_hit, h, n * 4); DOWN(out_dist, d, n * 4);
-    return RT_OK;
+    ProbeRun p(device);
+    auto b = p.in(boxes, 6 * n); auto r = p.in(rays, 6 * n); auto m = p.in(max_dist, n);
+    auto h = p.out(out_hit, n); auto d = p.out(out_dist, n);
+    p.launch(probe_aabb_kernel, p.per_case(n), 128, n, b, r, m, h, d);
+    return p.finish();
 }
 extern "C" int rt_probe_sphere(int device, size_t n, const float* rays, const float* spheres, float* out_t) {
     if (!rays || !spheres || !out_t) return rt_fail(RT_ERR_INVALID, "rt_probe_sphere: null argument");
     if (n == 0) return RT_OK;
-    int rc = select_device(device);
-    if (rc != RT_OK) return rc;
-    DevBuf r, s, t;
-    UP(r, rays, n * 24); UP(s, spheres, n * 16);
-    HIP_TRY(t.alloc(n * 4));
-    probe_sphere_kernel<<<PROBE_GRID(n)>>>(n, r.as<float>(), s.as<float>(), t.as<float>());
-    FINISH();
-    DOWN(out_t, t, n * 4);
-    return RT_OK;
+    ProbeRun p(device);
+    auto r = p.in(rays, 6 * n); auto s = p.in(spheres, 4 * n);
+    auto t = p.out(out_t, n);
+    p.launch(probe_sphere_kernel, p.per_case(n), 128, n, r, s, t);
+    return p.finish();
 }
 extern "C" int rt_probe_trace(int device, const rt_world_flat* world, size_t n, const float* rays, int32_t* out_hit, float* out_t,
                               int32_t* out_prim, float* out_normal) {
     if (!rays || !out_hit || !out_t || !out_prim || !out_normal) return rt_fail(RT_ERR_INVALID, "rt_probe_trace: null argument");
-    int rc = select_device(device);
-    if (rc != RT_OK) return rc;
+    ProbeRun p(device);
     DeviceScene sc;
-    rc = sc.upload(world);
-    if (rc != RT_OK) return rc;
-    if (n == 0) return RT_OK;
-    DevBuf r, h, t, p, nn;
-    UP(r, rays, n * 28);
-    HIP_TRY(h.alloc(n * 4)); HIP_TRY(t.alloc(n * 4)); HIP_TRY(p.alloc(n * 4)); HIP_TRY(nn.alloc(n * 12));
-    probe_trace_kernel<<<PROBE_GRID(n)>>>(sc.dw, n, r.as<float>(), h.as<int32_t>(), t.as<float>(), p.as<int32_t>(), nn.as<float>());
-    FINISH();
-    DOWN(out_hit, h, n * 4); DOWN(out_t, t, n * 4); DOWN(out_prim, p, n * 4); DOWN(out_normal, nn, n * 12);
-    return check_traversal_overflow(sc);
+    if (p.ok()) p.rc = sc.upload(world);
+    if (!p.ok() || n == 0) return p.rc;
+    auto r = p.in(rays, 7 * n);
+    auto h = p.out(out_hit, n); auto t = p.out(out_t, n); auto pr = p.out(out_prim, n); auto nn = p.out(out_normal, 3 * n);
+    p.launch(probe_trace_kernel, p.per_case(n), 128, sc.dw, n, r, h, t, pr, nn);
+    return p.finish() != RT_OK ? p.rc : check_traversal_overflow(sc);
 }
 extern "C" int rt_probe_sphere_hit(int device, size_t n, const rt_prim* prims, const float* rays, const float* preset, int32_t* out_hit,
                                    float* out_dist, float* out_normal) {
     if (!prims || !rays || !preset || !out_hit || !out_dist || !out_normal) return rt_fail(RT_ERR_INVALID, "rt_probe_sphere_hit: null argument");
     if (n == 0) return RT_OK;
-    int rc = select_device(device);
-    if (rc != RT_OK) return rc;
     rt_material lambertian{};
     lambertian.type = RT_MAT_LAMBERTIAN;
-    DevBuf pr, m, r, ps, h, d, nn;
-    UP(pr, prims, n * sizeof(rt_prim)); UP(m, &lambertian, sizeof(lambertian)); UP(r, rays, n * 28); UP(ps, preset, n * 4);
-    HIP_TRY(h.alloc(n * 4)); HIP_TRY(d.alloc(n * 4)); HIP_TRY(nn.alloc(n * 12));
-    probe_sphere_hit_kernel<<<PROBE_GRID(n)>>>(n, pr.as<rt_prim>(), m.as<rt_material>(), r.as<float>(), ps.as<float>(), h.as<int32_t>(),
-                                               d.as<float>(), nn.as<float>());
-    FINISH();
-    DOWN(out_hit, h, n * 4); DOWN(out_dist, d, n * 4); DOWN(out_normal, nn, n * 12);
-    return RT_OK;
+    ProbeRun p(device);
+    auto pr = p.in(prims, n); auto m = p.in(&lambertian, 1); auto r = p.in(rays, 7 * n); auto ps = p.in(preset, n);
+    auto h = p.out(out_hit, n); auto d = p.out(out_dist, n); auto nn = p.out(out_normal, 3 * n);
+    p.launch(probe_sphere_hit_kernel, p.per_case(n), 128, n, pr, m, r, ps, h, d, nn);
+    return p.finish();
 }
-extern "C" int rt_probe_scatter(int device, uint64_t seed, size_t n, const rt_material* mats, const float* rays, const float* dist,
-                                const float* normals, const uint32_t* keys, int32_t* out_scattered, float* out_rays, float* out_atten,
-                                uint32_t* out_draws) {
-    if (!mats || !rays || !dist || !normals || !keys || !out_scattered || !out_rays || !out_atten || !out_draws)
-        return rt_fail(RT_ERR_INVALID, "rt_probe_scatter: null argument");
-    if (n == 0) return RT_OK;
+
+static int check_materials(const char* fn, size_t n, const rt_material* mats) {
     for (size_t i = 0; i < n; i++)
-        if (mats[i].type > RT_MAT_ISOTROPIC) return rt_fail(RT_ERR_INVALID, "rt_probe_scatter: case %zu: unknown material type", i);
-    int rc = select_device(device);
-    if (rc != RT_OK) return rc;
-    DevBuf m, r, d, nn, k, s, orr, a, dr;
-    UP(m, mats, n * sizeof(rt_material)); UP(r, rays, n * 28); UP(d, dist, n * 4); UP(nn, normals, n * 12); UP(k, keys, n * 8);
-    HIP_TRY(s.alloc(n * 4)); HIP_TRY(orr.alloc(n * 28)); HIP_TRY(a.alloc(n * 12)); HIP_TRY(dr.alloc(n * 4));
-    probe_scatter_kernel<<<PROBE_GRID(n)>>>(seed, n, m.as<rt_material>(), r.as<float>(), d.as<float>(), nn.as<float>(), k.as<uint32_t>(),
-                                            s.as<int32_t>(), orr.as<float>(), a.as<float>(), dr.as<uint32_t>());
-    FINISH();
-    DOWN(out_scattered, s, n * 4); DOWN(out_rays, orr, n * 28); DOWN(out_atten, a, n * 12); DOWN(out_draws, dr, n * 4);
-    return RT_OK;
-}
-extern "C" int rt_probe_camera(int device, uint64_t seed, const rt_camera* cam, size_t n, const float* st, const uint32_t* keys,
-                               float* out_rays, uint32_t* out_draws) {
-    if (!cam || !st || !keys || !out_rays || !out_draws) return rt_fail(RT_ERR_INVALID, "rt_probe_camera: null argument");
-    if (cam->type > RT_CAM_MOTION) return rt_fail(RT_ERR_INVALID, "rt_probe_camera: unknown camera type");
-    if (n == 0) return RT_OK;
-    int rc = select_device(device);
-    if (rc != RT_OK) return rc;
-    DevBuf s, k, r, d;
-    UP(s, st, n * 8); UP(k, keys, n * 8);
-    HIP_TRY(r.alloc(n * 28)); HIP_TRY(d.alloc(n * 4));
-    probe_camera_kernel<<<PROBE_GRID(n)>>>(seed, *cam, n, s.as<float>(), k.as<uint32_t>(), r.as<float>(), d.as<uint32_t>());
-    FINISH();
-    DOWN(out_rays, r, n * 28); DOWN(out_draws, d, n * 4);
+        if (mats[i].type > RT_MAT_ISOTROPIC) return rt_fail(RT_ERR_INVALID, "%s: case %zu: unknown material type", fn, i);
     return RT_OK;
 }
 // every case's [offset, length) must lie inside the tape: the kernels read tape[offset + j] for j < length only
@@ -272,44 +244,63 @@ static int check_tape(const char* fn, size_t n, size_t tape_len, const uint32_t*
             return rt_fail(RT_ERR_INVALID, "%s: case %zu: tape range [%u, +%u) outside a tape of %zu", fn, i, offsets[2 * i], offsets[2 * i + 1], tape_len);
     return RT_OK;
 }
+// the two scatter probes and the two camera probes behind their checks; the caller has put its generator's arrays into p
+template <typename MakeRng>
+static int scatter_cases(ProbeRun& p, MakeRng make_rng, size_t n, const rt_material* mats, const float* rays, const float* dist, const float* normals,
+                         int32_t* out_scattered, float* out_rays, float* out_atten, uint32_t* out_draws) {
+    auto m = p.in(mats, n); auto r = p.in(rays, 7 * n); auto d = p.in(dist, n); auto nn = p.in(normals, 3 * n);
+    auto s = p.out(out_scattered, n); auto orr = p.out(out_rays, 7 * n); auto a = p.out(out_atten, 3 * n); auto dr = p.out(out_draws, n);
+    p.launch(probe_scatter_kernel<MakeRng>, p.per_case(n), 128, make_rng, n, m, r, d, nn, s, orr, a, dr);
+    return p.finish();
+}
+template <typename MakeRng>
+static int camera_cases(ProbeRun& p, MakeRng make_rng, const rt_camera& cam, size_t n, const float* st, float* out_rays, uint32_t* out_draws) {
+    auto s = p.in(st, 2 * n);
+    auto r = p.out(out_rays, 7 * n); auto d = p.out(out_draws, n);
+    p.launch(probe_camera_kernel<MakeRng>, p.per_case(n), 128, make_rng, cam, n, s, r, d);
+    return p.finish();
+}
+extern "C" int rt_probe_scatter(int device, uint64_t seed, size_t n, const rt_material* mats, const float* rays, const float* dist,
+                                const float* normals, const uint32_t* keys, int32_t* out_scattered, float* out_rays, float* out_atten,
+                                uint32_t* out_draws) {
+    if (!mats || !rays || !dist || !normals || !keys || !out_scattered || !out_rays || !out_atten || !out_draws)
+        return rt_fail(RT_ERR_INVALID, "rt_probe_scatter: null argument");
+    if (n == 0) return RT_OK;
+    if (int rc = check_materials("rt_probe_scatter", n, mats)) return rc;
+    ProbeRun p(device);
+    const KeyedRng make_rng{seed, p.in(keys, 2 * n)};
+    return scatter_cases(p, make_rng, n, mats, rays, dist, normals, out_scattered, out_rays, out_atten, out_draws);
+}
+extern "C" int rt_probe_camera(int device, uint64_t seed, const rt_camera* cam, size_t n, const float* st, const uint32_t* keys,
+                               float* out_rays, uint32_t* out_draws) {
+    if (!cam || !st || !keys || !out_rays || !out_draws) return rt_fail(RT_ERR_INVALID, "rt_probe_camera: null argument");
+    if (cam->type > RT_CAM_MOTION) return rt_fail(RT_ERR_INVALID, "rt_probe_camera: unknown camera type");
+    if (n == 0) return RT_OK;
+    ProbeRun p(device);
+    const KeyedRng make_rng{seed, p.in(keys, 2 * n)};
+    return camera_cases(p, make_rng, *cam, n, st, out_rays, out_draws);
+}
 extern "C" int rt_probe_scatter_tape(int device, size_t n, const rt_material* mats, const float* rays, const float* dist, const float* normals,
                                      const uint32_t* tape, size_t tape_len, const uint32_t* offsets, int32_t* out_scattered, float* out_rays,
                                      float* out_atten, uint32_t* out_draws) {
     if (!mats || !rays || !dist || !normals || !tape || !offsets || !out_scattered || !out_rays || !out_atten || !out_draws)
         return rt_fail(RT_ERR_INVALID, "rt_probe_scatter_tape: null argument");
     if (n == 0) return RT_OK;
-    for (size_t i = 0; i < n; i++)
-        if (mats[i].type > RT_MAT_ISOTROPIC) return rt_fail(RT_ERR_INVALID, "rt_probe_scatter_tape: case %zu: unknown material type", i);
-    int rc = check_tape("rt_probe_scatter_tape", n, tape_len, offsets);
-    if (rc != RT_OK) return rc;
-    rc = select_device(device);
-    if (rc != RT_OK) return rc;
-    DevBuf m, r, d, nn, tp, of, s, orr, a, dr;
-    UP(m, mats, n * sizeof(rt_material)); UP(r, rays, n * 28); UP(d, dist, n * 4); UP(nn, normals, n * 12); UP(tp, tape, tape_len * 4);
-    UP(of, offsets, n * 8);
-    HIP_TRY(s.alloc(n * 4)); HIP_TRY(orr.alloc(n * 28)); HIP_TRY(a.alloc(n * 12)); HIP_TRY(dr.alloc(n * 4));
-    probe_scatter_tape_kernel<<<PROBE_GRID(n)>>>(n, m.as<rt_material>(), r.as<float>(), d.as<float>(), nn.as<float>(), tp.as<uint32_t>(),
-                                                 of.as<uint32_t>(), s.as<int32_t>(), orr.as<float>(), a.as<float>(), dr.as<uint32_t>());
-    FINISH();
-    DOWN(out_scattered, s, n * 4); DOWN(out_rays, orr, n * 28); DOWN(out_atten, a, n * 12); DOWN(out_draws, dr, n * 4);
-    return RT_OK;
+    if (int rc = check_materials("rt_probe_scatter_tape", n, mats)) return rc;
+    if (int rc = check_tape("rt_probe_scatter_tape", n, tape_len, offsets)) return rc;
+    ProbeRun p(device);
+    const TapedRng make_rng{p.in(tape, tape_len), p.in(offsets, 2 * n)};
+    return scatter_cases(p, make_rng, n, mats, rays, dist, normals, out_scattered, out_rays, out_atten, out_draws);
 }
 extern "C" int rt_probe_camera_tape(int device, const rt_camera* cam, size_t n, const float* st, const uint32_t* tape, size_t tape_len,
                                     const uint32_t* offsets, float* out_rays, uint32_t* out_draws) {
     if (!cam || !st || !tape || !offsets || !out_rays || !out_draws) return rt_fail(RT_ERR_INVALID, "rt_probe_camera_tape: null argument");
     if (cam->type > RT_CAM_MOTION) return rt_fail(RT_ERR_INVALID, "rt_probe_camera_tape: unknown camera type");
     if (n == 0) return RT_OK;
-    int rc = check_tape("rt_probe_camera_tape", n, tape_len, offsets);
-    if (rc != RT_OK) return rc;
-    rc = select_device(device);
-    if (rc != RT_OK) return rc;
-    DevBuf s, tp, of, r, d;
-    UP(s, st, n * 8); UP(tp, tape, tape_len * 4); UP(of, offsets, n * 8);
-    HIP_TRY(r.alloc(n * 28)); HIP_TRY(d.alloc(n * 4));
-    probe_camera_tape_kernel<<<PROBE_GRID(n)>>>(*cam, n, s.as<float>(), tp.as<uint32_t>(), of.as<uint32_t>(), r.as<float>(), d.as<uint32_t>());
-    FINISH();
-    DOWN(out_rays, r, n * 28); DOWN(out_draws, d, n * 4);
-    return RT_OK;
+    if (int rc = check_tape("rt_probe_camera_tape", n, tape_len, offsets)) return rc;
+    ProbeRun p(device);
+    const TapedRng make_rng{p.in(tape, tape_len), p.in(offsets, 2 * n)};
+    return camera_cases(p, make_rng, *cam, n, st, out_rays, out_draws);
 }
 extern "C" int rt_probe_radiance(const rt_render_config* cfg, const rt_camera* cam, const rt_world_flat* world, size_t n,
                                  const uint32_t* keys, float* out_radiance) {
@@ -318,50 +309,36 @@ extern "C" int rt_probe_radiance(const rt_render_config* cfg, const rt_camera* c
     if (cam->type > RT_CAM_MOTION) return rt_fail(RT_ERR_INVALID, "rt_probe_radiance: unknown camera type");
     for (size_t i = 0; i < n; i++)
         if (keys[2 * i] >= cfg->width * cfg->height) return rt_fail(RT_ERR_INVALID, "rt_probe_radiance: key %zu: pixel out of range", i);
-    int rc = select_device(cfg->device);
-    if (rc != RT_OK) return rc;
+    ProbeRun p(cfg->device);
     DeviceScene sc;
-    rc = sc.upload(world);
-    if (rc != RT_OK) return rc;
-    if (n == 0) return RT_OK;
-    DevBuf k, o;
-    UP(k, keys, n * 8);
-    HIP_TRY(o.alloc(n * 12));
-    probe_radiance_kernel<<<PROBE_GRID(n)>>>(sc.dw, *cam, cfg->width, cfg->height, cfg->max_depth, cfg->seed, n, k.as<uint32_t>(), o.as<float>());
-    FINISH();
-    DOWN(out_radiance, o, n * 12);
-    return check_traversal_overflow(sc);
+    if (p.ok()) p.rc = sc.upload(world);
+    if (!p.ok() || n == 0) return p.rc;
+    auto k = p.in(keys, 2 * n);
+    auto o = p.out(out_radiance, 3 * n);
+    p.launch(probe_radiance_kernel, p.per_case(n), 128, sc.dw, *cam, cfg->width, cfg->height, cfg->max_depth, cfg->seed, n, k, o);
+    return p.finish() != RT_OK ? p.rc : check_traversal_overflow(sc);
 }
 extern "C" int rt_probe_sphere_index(int device, const rt_camera* cam, uint32_t width, uint32_t height, size_t n_spheres,
                                      const float* spheres, int32_t* out_index) {
     if (!cam || !spheres || !out_index) return rt_fail(RT_ERR_INVALID, "rt_probe_sphere_index: null argument");
     if (width == 0 || height == 0) return RT_OK;
-    int rc = select_device(device);
-    if (rc != RT_OK) return rc;
-    DevBuf s, o;
-    UP(s, spheres, n_spheres * 16);
-    HIP_TRY(o.alloc((size_t)width * height * 4));
+    ProbeRun p(device);
+    auto s = p.in(reinterpret_cast<const float4*>(spheres), n_spheres);
+    auto o = p.out(out_index, (size_t)width * height);
+    if (!p.ok()) return p.rc;   // (sizes that cannot even be allocated are reported as that)
     if (n_spheres > 0x7fffffffull || (uint64_t)width * height > 0xffffff00ull) return rt_fail(RT_ERR_INVALID, "rt_probe_sphere_index: too large");
-    probe_sphere_index_kernel<<<(width * height + 255u) / 256u, 256>>>(s.as<float4>(), (uint32_t)n_spheres, *cam, width, height, o.as<int32_t>());
-    FINISH();
-    DOWN(out_index, o, (size_t)width * height * 4);
-    return RT_OK;
+    p.launch(probe_sphere_index_kernel, dim3((width * height + 255u) / 256u), 256, s, (uint32_t)n_spheres, *cam, width, height, o);
+    return p.finish();
 }
 extern "C" int rt_probe_rng(int device, uint64_t seed, size_t n, const uint32_t* keys, uint32_t n_draws, float* out) {
     if (!keys || !out) return rt_fail(RT_ERR_INVALID, "rt_probe_rng: null argument");
     if (n == 0 || n_draws == 0) return RT_OK;
-    int rc = select_device(device);
-    if (rc != RT_OK) return rc;
-    DevBuf k, o;
-    UP(k, keys, n * 8);
-    HIP_TRY(o.alloc(n * n_draws * 4));
-    probe_rng_kernel<<<PROBE_GRID(n)>>>(seed, n, k.as<uint32_t>(), n_draws, o.as<float>());
-    FINISH();
-    DOWN(out, o, n * n_draws * 4);
-    return RT_OK;
+    ProbeRun p(device);
+    auto k = p.in(keys, 2 * n);
+    auto o = p.out(out, n * n_draws);
+    p.launch(probe_rng_kernel, p.per_case(n), 128, seed, n, k, n_draws, o);
+    return p.finish();
 }
-
-
 __global__ void probe_math_kernel(int fn, size_t n, const float* a, const float* b, float* out) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -371,15 +348,11 @@ extern "C" int rt_probe_math(int device, int fn, size_t n, const float* a, const
     if (!a || !b || !out) return rt_fail(RT_ERR_INVALID, "rt_probe_math: null argument");
     if (fn < 0 || fn > 3) return rt_fail(RT_ERR_INVALID, "rt_probe_math: unknown function %d", fn);
     if (n == 0) return RT_OK;
-    int rc = select_device(device);
-    if (rc != RT_OK) return rc;
-    DevBuf da, db, o;
-    UP(da, a, n * 4); UP(db, b, n * 4);
-    HIP_TRY(o.alloc(n * 4));
-    probe_math_kernel<<<PROBE_GRID(n)>>>(fn, n, da.as<float>(), db.as<float>(), o.as<float>());
-    FINISH();
-    DOWN(out, o, n * 4);
-    return RT_OK;
+    ProbeRun p(device);
+    auto da = p.in(a, n); auto db = p.in(b, n);
+    auto o = p.out(out, n);
+    p.launch(probe_math_kernel, p.per_case(n), 128, fn, n, da, db, o);
+    return p.finish();
 }
 
 // The device half of the math vocabulary (csrc/rt_math.hpp) over arrays: the functions the fixtures tests/golden/glm_*.f32 —
@@ -420,16 +393,12 @@ extern "C" int rt_probe_glm(int device, int fn, size_t n, const float* in, float
     if (!in || !out) return rt_fail(RT_ERR_INVALID, "rt_probe_glm: null argument");
     if (fn < 0 || fn > 16) return rt_fail(RT_ERR_INVALID, "rt_probe_glm: unknown function %d", fn);
     if (n == 0) return RT_OK;
-    int rc = select_device(device);
-    if (rc != RT_OK) return rc;
     const uint32_t nin = shape[fn][0], nout = shape[fn][1];
-    DevBuf di, dout;
-    UP(di, in, n * nin * 4);
-    HIP_TRY(dout.alloc(n * nout * 4));
-    probe_glm_kernel<<<PROBE_GRID(n)>>>(fn, n, nin, nout, di.as<float>(), dout.as<float>());
-    FINISH();
-    DOWN(out, dout, n * nout * 4);
-    return RT_OK;
+    ProbeRun p(device);
+    auto di = p.in(in, n * nin);
+    auto dout = p.out(out, n * nout);
+    p.launch(probe_glm_kernel, p.per_case(n), 128, fn, n, nin, nout, di, dout);
+    return p.finish();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -459,15 +428,11 @@ extern "C" int rt_probe_aabb_regular(int device, size_t n, const float* boxes, c
                                      int32_t* out_regular, int32_t* out_hit, float* out_dist) {
     if (!boxes || !rays || !max_dist || !out_regular || !out_hit || !out_dist) return rt_fail(RT_ERR_INVALID, "rt_probe_aabb_regular: null argument");
     if (n == 0) return RT_OK;
-    int rc = select_device(device);
-    if (rc != RT_OK) return rc;
-    DevBuf b, r, m, g, h, d;
-    UP(b, boxes, n * 24); UP(r, rays, n * 24); UP(m, max_dist, n * 4);
-    HIP_TRY(g.alloc(n * 4)); HIP_TRY(h.alloc(n * 4)); HIP_TRY(d.alloc(n * 4));
-    probe_aabb_regular_kernel<<<PROBE_GRID(n)>>>(n, b.as<float>(), r.as<float>(), m.as<float>(), g.as<int32_t>(), h.as<int32_t>(), d.as<float>());
-    FINISH();
-    DOWN(out_regular, g, n * 4); DOWN(out_hit, h, n * 4); DOWN(out_dist, d, n * 4);
-    return RT_OK;
+    ProbeRun p(device);
+    auto b = p.in(boxes, 6 * n); auto r = p.in(rays, 6 * n); auto m = p.in(max_dist, n);
+    auto g = p.out(out_regular, n); auto h = p.out(out_hit, n); auto d = p.out(out_dist, n);
+    p.launch(probe_aabb_regular_kernel, p.per_case(n), 128, n, b, r, m, g, h, d);
+    return p.finish();
 }
 
 // one block per divisor significand; its 256 threads sweep all 2^23 numerator significands
@@ -489,19 +454,11 @@ __global__ __launch_bounds__(256) void selftest_fastrcp_kernel(unsigned long lon
 
 extern "C" int rt_selftest_fastrcp(int device, uint64_t* checked, uint64_t* mismatches, uint32_t* example) {
     if (!checked || !mismatches || !example) return rt_fail(RT_ERR_INVALID, "rt_selftest_fastrcp: null argument");
-    int rc = select_device(device);
-    if (rc != RT_OK) return rc;
-    DevBuf counts, ex;
-    HIP_TRY(counts.alloc(16));
-    HIP_TRY(ex.alloc(4));
-    HIP_TRY(hipMemset(counts.p, 0, 16));
-    HIP_TRY(hipMemset(ex.p, 0, 4));
-    selftest_fastrcp_kernel<<<8192, 256>>>(counts.as<unsigned long long>(), ex.as<uint32_t>());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    unsigned long long h[2];
-    HIP_TRY(hipMemcpy(h, counts.p, 16, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(example, ex.p, 4, hipMemcpyDeviceToHost));
+    unsigned long long h[2] = {0, 0};
+    ProbeRun p(device);
+    auto counts = p.out(h, 2, true); auto ex = p.out(example, 1, true);   // the kernel adds to them
+    p.launch(selftest_fastrcp_kernel, dim3(8192), 256, counts, ex);
+    if (p.finish() != RT_OK) return p.rc;
     *checked = h[0];
     *mismatches = h[1];
     return RT_OK;
@@ -528,79 +485,80 @@ __global__ __launch_bounds__(256) void selftest_fastdiv_kernel(uint32_t first_de
     }
 }
 
+// mode: bit 0 of the kernel's numerator exponent word — 0 fast_div_exact, 1 fast_div_exact4
+static int selftest_fastdiv(const char* fn, uint32_t mode, int device, uint32_t first_den, uint32_t n_den, int32_t num_exp, int32_t den_exp,
+                            uint64_t* mismatches, uint32_t example[2]) {
+    if (!mismatches || !example) return rt_fail(RT_ERR_INVALID, "%s: null argument", fn);
+    if (first_den >= (1u << 23) || n_den == 0 || n_den > (1u << 23) - first_den) return rt_fail(RT_ERR_INVALID, "%s: significand range out of bounds", fn);
+    if (num_exp < -126 || num_exp > 127 || den_exp < -126 || den_exp > 127) return rt_fail(RT_ERR_INVALID, "%s: exponent out of range", fn);
+    unsigned long long bad = 0;
+    ProbeRun p(device);
+    auto cnt = p.out(&bad, 1, true); auto ex = p.out(example, 2, true);   // the kernel adds to the count
+    p.launch(selftest_fastdiv_kernel, dim3(n_den), 256, first_den, ((uint32_t)(num_exp + 127) << 23) | mode, (uint32_t)(den_exp + 127) << 23, cnt, ex);
+    if (p.finish() == RT_OK) *mismatches = bad;
+    return p.rc;
+}
 extern "C" int rt_selftest_fastdiv(int device, uint32_t first_den, uint32_t n_den, int32_t num_exp, int32_t den_exp,
                                    uint64_t* mismatches, uint32_t example[2]) {
-    if (!mismatches || !example) return rt_fail(RT_ERR_INVALID, "rt_selftest_fastdiv: null argument");
-    if (first_den >= (1u << 23) || n_den == 0 || n_den > (1u << 23) - first_den) return rt_fail(RT_ERR_INVALID, "rt_selftest_fastdiv: significand range out of bounds");
-    if (num_exp < -126 || num_exp > 127 || den_exp < -126 || den_exp > 127) return rt_fail(RT_ERR_INVALID, "rt_selftest_fastdiv: exponent out of range");
-    int rc = select_device(device);
-    if (rc != RT_OK) return rc;
-    DevBuf cnt, ex;
-    HIP_TRY(cnt.alloc(8)); HIP_TRY(ex.alloc(8));
-    HIP_TRY(hipMemset(cnt.p, 0, 8)); HIP_TRY(hipMemset(ex.p, 0, 8));
-    selftest_fastdiv_kernel<<<n_den, 256>>>(first_den, (uint32_t)(num_exp + 127) << 23, (uint32_t)(den_exp + 127) << 23,
-                                            cnt.as<unsigned long long>(), ex.as<uint32_t>());
-    FINISH();
-    DOWN(mismatches, cnt, 8); DOWN(example, ex, 8);
-    return RT_OK;
+    return selftest_fastdiv("rt_selftest_fastdiv", 0u, device, first_den, n_den, num_exp, den_exp, mismatches, example);
 }
-
 extern "C" int rt_selftest_fastdiv4(int device, uint32_t first_den, uint32_t n_den, int32_t num_exp, int32_t den_exp,
-                                   uint64_t* mismatches, uint32_t example[2]) {
-    if (!mismatches || !example) return rt_fail(RT_ERR_INVALID, "rt_selftest_fastdiv4: null argument");
-    if (first_den >= (1u << 23) || n_den == 0 || n_den > (1u << 23) - first_den) return rt_fail(RT_ERR_INVALID, "rt_selftest_fastdiv4: significand range out of bounds");
-    if (num_exp < -126 || num_exp > 127 || den_exp < -126 || den_exp > 127) return rt_fail(RT_ERR_INVALID, "rt_selftest_fastdiv4: exponent out of range");
-    int rc = select_device(device);
-    if (rc != RT_OK) return rc;
-    DevBuf cnt, ex;
-    HIP_TRY(cnt.alloc(8)); HIP_TRY(ex.alloc(8));
-    HIP_TRY(hipMemset(cnt.p, 0, 8)); HIP_TRY(hipMemset(ex.p, 0, 8));
-    selftest_fastdiv_kernel<<<n_den, 256>>>(first_den, ((uint32_t)(num_exp + 127) << 23) | 1u, (uint32_t)(den_exp + 127) << 23,
-                                            cnt.as<unsigned long long>(), ex.as<uint32_t>());
-    FINISH();
-    DOWN(mismatches, cnt, 8); DOWN(example, ex, 8);
-    return RT_OK;
+                                    uint64_t* mismatches, uint32_t example[2]) {
+    return selftest_fastdiv("rt_selftest_fastdiv4", 1u, device, first_den, n_den, num_exp, den_exp, mismatches, example);
 }
-
+// One case of the two box-pair probes: the ray, the two boxes (12 coordinates) and the 8-int record
+// [regular, uncertain, hit_left, hit_right, swap | verbatim: hit_left, hit_right, left_dist > right_dist].
+struct BoxPairCase {
+    Ray r;
+    const float* b;
+    int32_t* o;
+    bool regular;   // ray and coordinates inside the fast-division class, boxes not inverted: only then is the rest of the record filled in
+};
+__device__ BoxPairCase boxpair_case(size_t i, const float* boxes, const float* rays, int32_t* out) {
+    BoxPairCase c;
+    c.r.o = ld3(rays + 6 * i); c.r.d = ld3(rays + 6 * i + 3); c.r.time = 0.0f;
+    c.b = boxes + 12 * i;
+    c.regular = ray_is_regular(c.r);
+    for (int k = 0; k < 12; k++) c.regular = c.regular && coord_is_regular(c.b[k]);
+    for (int k = 0; k < 3; k++) c.regular = c.regular && c.b[k] <= c.b[3 + k] && c.b[6 + k] <= c.b[9 + k];
+    c.o = out + 8 * i;
+    for (int k = 0; k < 8; k++) c.o[k] = 0;
+    c.o[0] = c.regular ? 1 : 0;
+    return c;
+}
+// o[5..7]: the decisions of the verbatim box tests
+__device__ void boxpair_verbatim(const BoxPairCase& c, float max_dist) {
+    float dl = RT_MISS_DIST, dr = RT_MISS_DIST;
+    const bool hl = aabb_intersects(ld3(c.b), ld3(c.b + 3), c.r, max_dist, dl);
+    const bool hr = aabb_intersects(ld3(c.b + 6), ld3(c.b + 9), c.r, max_dist, dr);
+    c.o[5] = hl; c.o[6] = hr; c.o[7] = dl > dr;
+}
 
 // box_pair_filtered vs the exact decisions, on regular inputs only
-__global__ void probe_boxpair_kernel(size_t n, const float* boxes, const float* rays, const float* maxd, int32_t* out) {
+__global__ void probe_boxpair_filtered_kernel(size_t n, const float* boxes, const float* rays, const float* maxd, int32_t* out) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    Ray r;
-    r.o = ld3(rays + 6 * i); r.d = ld3(rays + 6 * i + 3); r.time = 0.0f;
-    const float* b = boxes + 12 * i;
-    bool reg = ray_is_regular(r);
-    for (int k = 0; k < 12; k++) reg = reg && coord_is_regular(b[k]);
-    for (int k = 0; k < 3; k++) reg = reg && b[k] <= b[3 + k] && b[6 + k] <= b[9 + k];
-    int32_t* o = out + 8 * i;
-    for (int k = 0; k < 8; k++) o[k] = 0;
-    o[0] = reg ? 1 : 0;
-    if (!reg) return;
+    const BoxPairCase c = boxpair_case(i, boxes, rays, out);
+    if (!c.regular) return;
+    const Ray& r = c.r;
+    const float* b = c.b;
     f3 inv_d = mk3(1.0f / r.d.x, 1.0f / r.d.y, 1.0f / r.d.z);
     BoxPairDecision d = box_pair_filtered(ld3(b), ld3(b + 3), ld3(b + 6), ld3(b + 9), r, inv_d, maxd[i]);
-    float dl = RT_MISS_DIST, dr = RT_MISS_DIST;
-    bool hl = aabb_intersects(ld3(b), ld3(b + 3), r, maxd[i], dl);
-    bool hr = aabb_intersects(ld3(b + 6), ld3(b + 9), r, maxd[i], dr);
-    o[1] = d.uncertain; o[2] = d.hit_left; o[3] = d.hit_right; o[4] = d.swap;
-    o[5] = hl; o[6] = hr; o[7] = dl > dr;
+    c.o[1] = d.uncertain; c.o[2] = d.hit_left; c.o[3] = d.hit_right; c.o[4] = d.swap;
+    boxpair_verbatim(c, maxd[i]);
 }
 
 // The hot loop's box pair (rt_fastdiv.hpp: CERTIFIED FAR PLANES) next to the verbatim box tests: near parameters as exact quotients, far parameters as
 // products whose `tmin <= tmax` decisions are certified — a lane that cannot certify redoes its far planes exactly (the kernel does that for the whole wave).
+// The two hit decisions and the order are written as render_kernel_stream writes them, but they are a copy: as scalar helpers shared with the hot loops
+// they changed the machine code of the stream (hit decision) and exchange (order) kernels.
 __global__ void probe_boxpair_certified_kernel(size_t n, const float* boxes, const float* rays, const float* maxd, int32_t* out) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    Ray r;
-    r.o = ld3(rays + 6 * i); r.d = ld3(rays + 6 * i + 3); r.time = 0.0f;
-    const float* b = boxes + 12 * i;
-    bool reg = ray_is_regular(r);
-    for (int k = 0; k < 12; k++) reg = reg && coord_is_regular(b[k]);
-    for (int k = 0; k < 3; k++) reg = reg && b[k] <= b[3 + k] && b[6 + k] <= b[9 + k];
-    int32_t* o = out + 8 * i;
-    for (int k = 0; k < 8; k++) o[k] = 0;
-    o[0] = reg ? 1 : 0;
-    if (!reg) return;
+    const BoxPairCase c = boxpair_case(i, boxes, rays, out);
+    if (!c.regular) return;
+    const Ray& r = c.r;
+    const float* b = c.b;
     const f3 inv_d = mk3(rcp_exact_regular(r.d.x), rcp_exact_regular(r.d.y), rcp_exact_regular(r.d.z));
     const f3 inv_lo = mk3(rcp_low_word(r.d.x, inv_d.x), rcp_low_word(r.d.y, inv_d.y), rcp_low_word(r.d.z, inv_d.z));
     // near = the plane the ray enters through (box min where d >= 0), as the kernel's (min, max, min) triples deliver it
@@ -611,38 +569,25 @@ __global__ void probe_boxpair_certified_kernel(size_t n, const float* boxes, con
     float far_l = slab_far_product(lfx, lfy, lfz, r, inv_d), far_r = slab_far_product(rfx, rfy, rfz, r, inv_d);
     const bool unc = far_pair_uncertain(tl, far_l, tr, far_r);
     if (unc) { far_l = slab_far_exact(lfx, lfy, lfz, r, inv_d, inv_lo); far_r = slab_far_exact(rfx, rfy, rfz, r, inv_d, inv_lo); }
-    const bool hl_c = tl <= far_l && tl < maxd[i] && far_l > 0, hr_c = tr <= far_r && tr < maxd[i] && far_r > 0;
-    float dl = RT_MISS_DIST, dr = RT_MISS_DIST;
-    const bool hl = aabb_intersects(ld3(b), ld3(b + 3), r, maxd[i], dl);
-    const bool hr = aabb_intersects(ld3(b + 6), ld3(b + 9), r, maxd[i], dr);
-    o[1] = unc; o[2] = hl_c; o[3] = hr_c; o[4] = (hl_c ? tl : RT_MISS_DIST) > (hr_c ? tr : RT_MISS_DIST);
-    o[5] = hl; o[6] = hr; o[7] = dl > dr;
+    const float rec_t = maxd[i];
+    const bool hl = tl <= far_l && tl < rec_t && far_l > 0, hr = tr <= far_r && tr < rec_t && far_r > 0;
+    c.o[1] = unc; c.o[2] = hl; c.o[3] = hr; c.o[4] = hr && (!hl || tl > tr);
+    boxpair_verbatim(c, maxd[i]);
 }
 
+static int boxpair_probe(const char* fn, void (*kernel)(size_t, const float*, const float*, const float*, int32_t*), int device, size_t n,
+                         const float* boxes, const float* rays, const float* max_dist, int32_t* out) {
+    if (!boxes || !rays || !max_dist || !out) return rt_fail(RT_ERR_INVALID, "%s: null argument", fn);
+    if (n == 0) return RT_OK;
+    ProbeRun p(device);
+    auto b = p.in(boxes, 12 * n); auto r = p.in(rays, 6 * n); auto m = p.in(max_dist, n);
+    auto o = p.out(out, 8 * n);
+    p.launch(kernel, p.per_case(n), 128, n, b, r, m, o);
+    return p.finish();
+}
 extern "C" int rt_probe_boxpair_certified(int device, size_t n, const float* boxes, const float* rays, const float* max_dist, int32_t* out) {
-    if (!boxes || !rays || !max_dist || !out) return rt_fail(RT_ERR_INVALID, "rt_probe_boxpair_certified: null argument");
-    if (n == 0) return RT_OK;
-    int rc = select_device(device);
-    if (rc != RT_OK) return rc;
-    DevBuf b, r, m, o;
-    UP(b, boxes, n * 48); UP(r, rays, n * 24); UP(m, max_dist, n * 4);
-    HIP_TRY(o.alloc(n * 32));
-    probe_boxpair_certified_kernel<<<PROBE_GRID(n)>>>(n, b.as<float>(), r.as<float>(), m.as<float>(), o.as<int32_t>());
-    FINISH();
-    DOWN(out, o, n * 32);
-    return RT_OK;
+    return boxpair_probe("rt_probe_boxpair_certified", probe_boxpair_certified_kernel, device, n, boxes, rays, max_dist, out);
 }
-
 extern "C" int rt_probe_boxpair_filtered(int device, size_t n, const float* boxes, const float* rays, const float* max_dist, int32_t* out) {
-    if (!boxes || !rays || !max_dist || !out) return rt_fail(RT_ERR_INVALID, "rt_probe_boxpair_filtered: null argument");
-    if (n == 0) return RT_OK;
-    int rc = select_device(device);
-    if (rc != RT_OK) return rc;
-    DevBuf b, r, m, o;
-    UP(b, boxes, n * 48); UP(r, rays, n * 24); UP(m, max_dist, n * 4);
-    HIP_TRY(o.alloc(n * 32));
-    probe_boxpair_kernel<<<PROBE_GRID(n)>>>(n, b.as<float>(), r.as<float>(), m.as<float>(), o.as<int32_t>());
-    FINISH();
-    DOWN(out, o, n * 32);
-    return RT_OK;
+    return boxpair_probe("rt_probe_boxpair_filtered", probe_boxpair_filtered_kernel, device, n, boxes, rays, max_dist, out);
 }
