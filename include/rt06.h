@@ -253,6 +253,9 @@ int rt_scene_three_spheres(rt_scene** out);
 /* BASELINE.json configs[3]: the Cornell box of "The Next Week" (5 walls, light, two rotated boxes = 18 quads),
  * black background, median-split BVH.  Not in the reference (no quads / emission there).                  */
 int rt_scene_cornell_box(rt_scene** out);
+/* The Cornell box lit by a lamp: the same walls and boxes without the ceiling quad light, and a sphere light of radius 40 at
+ * (278, 470, 278) emitting (40, 40, 40) — the small-emitter world of RT_LIGHT_SAMPLING_ALL.  Host only.                  */
+int rt_scene_cornell_lamp(rt_scene** out);
 /* box(a, b, mat) of "The Next Week" as 6 quads, rotated about y and translated on the host (the book wraps instances) */
 int rt_scene_add_box(rt_scene* s, const float a[3], const float b[3], int32_t mat, float rotate_y_degrees,
                      const float translate[3], int32_t* out_first_quad);
@@ -451,12 +454,39 @@ int rt_renderer_denoise_download(rt_renderer* r, float* host_rgba, size_t n_floa
  * state as rt_renderer_set_camera with other bytes does.  RT_ERR_INVALID, with the cause in rt_last_error: no quad light; more than
  * RT_MAX_LIGHTS; a renderer on variant 1, 5 or 6; a world with a queue or wide4 traversal; a world with a constant medium.            */
 #define RT_MAX_LIGHTS 16
+/* on: RT_LIGHT_SAMPLING_OFF (0), RT_LIGHT_SAMPLING_QUADS (1, the estimator above) or RT_LIGHT_SAMPLING_ALL (2, below); more is refused */
 int rt_renderer_light_sampling_enable(rt_renderer* r, uint32_t on);
-/* out[0] = 1 when on, out[1] = n_l, the quad lights of the world (0 when it cannot be light-sampled) */
+/* out[0] = the mode (RT_LIGHT_SAMPLING_OFF / _QUADS / _ALL), out[1] = n_l of that mode's table — off: of the quad lights, as ever — (0 when the
+ * world cannot be light-sampled)                                                                     */
 int rt_renderer_light_sampling_info(rt_renderer* r, uint32_t out[2]);
 /* HOST (no GPU): the light table of a world as rt_renderer_light_sampling_enable would take it — quad index and area of light i < *out_n —
  * or RT_ERR_INVALID with the world's own reason for refusal (no quad light, more than RT_MAX_LIGHTS, traversal, constant medium).     */
 int rt_world_quad_lights(const rt_world_flat* w, uint32_t out_quad[RT_MAX_LIGHTS], float out_area[RT_MAX_LIGHTS], uint32_t* out_n);
+
+/* Sphere lights too: mode RT_LIGHT_SAMPLING_ALL of rt_renderer_light_sampling_enable (opt-in beside mode 1, which stays what it is).
+ * Lights of mode 2: first the quad lights exactly as mode 1 lists them, then the sphere lights in the order of the flat world's primitives —
+ * a STATIC sphere with radius > 0 whose material is RT_MAT_DIFFUSE_LIGHT, area = (12.566371f * r) * r in fp32; a moving sphere with a light
+ * material is not in the table and keeps emitting when hit.  1 <= n_l <= RT_MAX_LIGHTS over both kinds together.  The draw order is mode 1's:
+ * c; if c < 0.5f the index i as above; for a quad a, b as above; for a sphere (centre C, radius r) u = the library's on-unit-sphere draw (its
+ * rejection loop, as many uniforms as it takes) and d = ((C + u * r)) - hit_p, not normalised; otherwise the cosine half.  Densities: len2,
+ * len, cosn, sp as above; a quad light j as above; a sphere light j, with oc = C - hit_p:  h = dot(d, oc), cr = cross(oc, d),
+ * disc = (r * r) * len2 - dot(cr, cr);  !(disc > 0) gives pl_j = 0, and ends the path like a failed scatter if j is the light this hit drew its point
+ * from (a point lost on the silhouette to rounding; its exact weight is nearly 0);  otherwise sq = sqrt(disc), cosl = (sq / r) / len, t1 = (h - sq) / len2,
+ * t2 = (h + sq) / len2, pl_j = 0, and for each of t1, t2 (in this order) that is > 0:  pl_j = pl_j + ((t * t) * len2) / (cosl * area_j) —
+ * the solid-angle density of an area-uniform point, summed over both crossings of the line through the sphere.  pl, pdf, the sp == 0 /
+ * !(pdf > 0) rule, the weight and the new ray are mode 1's.  Refused as mode 1 is, with two messages of its own: no light to sample; more
+ * than RT_MAX_LIGHTS lights.  A switch between any two different modes discards the refinement and feature-buffer state; a switch to the
+ * mode a renderer is in keeps it.                                                                                                       */
+#define RT_LIGHT_SAMPLING_OFF 0
+#define RT_LIGHT_SAMPLING_QUADS 1
+#define RT_LIGHT_SAMPLING_ALL 2
+#define RT_LIGHT_QUAD 0
+#define RT_LIGHT_SPHERE 1
+/* HOST (no GPU): the light table of `mode` (RT_LIGHT_SAMPLING_QUADS: what rt_world_quad_lights gives; RT_LIGHT_SAMPLING_ALL: the combined list) —
+ * kind (RT_LIGHT_QUAD: index is a quad index; RT_LIGHT_SPHERE: a primitive index), index and area of light i < *out_n — or RT_ERR_INVALID with
+ * the world's own reason for refusal.                                                                                                    */
+int rt_world_lights(const rt_world_flat* w, uint32_t mode, uint32_t out_kind[RT_MAX_LIGHTS], uint32_t out_index[RT_MAX_LIGHTS],
+                    float out_area[RT_MAX_LIGHTS], uint32_t* out_n);
 
 /* ------------------------------------------------------------------ */
 /* Multi-GPU renderer — the same three entry points (Renderer.h:38-46)  */

@@ -71,6 +71,13 @@ class Scene:
         return cls(h)
 
     @classmethod
+    def cornell_lamp(cls):
+        """The Cornell box lit by a lamp (not in the reference): no ceiling quad light, a sphere light of radius 40 at (278, 470, 278)."""
+        h = C.c_void_p()
+        check(lib().rt_scene_cornell_lamp(C.byref(h)))
+        return cls(h)
+
+    @classmethod
     def book2_final(cls, seed=1984):
         """BASELINE.json configs[4] (not in the reference): final_scene() of "The Next Week"."""
         h = C.c_void_p()
@@ -243,6 +250,15 @@ class Scene:
             pass
 
 
+def light_sampling_mode(on):
+    """False / 0 / "off" -> 0, True / 1 / "quads" -> 1, 2 / "all" -> 2 (RT_LIGHT_SAMPLING_*)"""
+    if isinstance(on, str):
+        if on not in ("off", "quads", "all"):
+            raise ValueError(f"light sampling mode {on!r}: one of 'off', 'quads', 'all'")
+        return ("off", "quads", "all").index(on)
+    return int(on)
+
+
 class Renderer:
     """Renderer (main/src/Renderer.h:12-47) over the C ABI."""
 
@@ -340,11 +356,19 @@ class Renderer:
         check(lib().rt_renderer_denoise_async(self.h, C.c_void_p(stream or 0), C.byref(self.denoise_params(**params))))
 
     def light_sampling(self, on=True):
-        """Next-event estimation over the world's quad lights from the next launch on (rt_renderer_light_sampling_enable); a change restarts the refinement."""
-        check(lib().rt_renderer_light_sampling_enable(self.h, 1 if on else 0))
+        """Next-event estimation from the next launch on (rt_renderer_light_sampling_enable); a change restarts the refinement.
+        False / 0 / "off": off; True / 1 / "quads": over the world's quad lights; 2 / "all": over its quad and sphere lights."""
+        check(lib().rt_renderer_light_sampling_enable(self.h, light_sampling_mode(on)))
+
+    def light_sampling_mode(self):
+        """0 (off), 1 (quad lights) or 2 (quad and sphere lights): the mode the next launch runs in."""
+        out = (C.c_uint32 * 2)()
+        check(lib().rt_renderer_light_sampling_info(self.h, out))
+        return out[0]
 
     def light_sampling_info(self):
-        """{'enabled', 'lights'}: whether light sampling is on, and the number of quad lights it samples (0: the world cannot be light-sampled)."""
+        """{'enabled', 'lights'}: whether light sampling is on (in either mode: light_sampling_mode() tells which), and the number of lights in the
+        mode's table — off: of quad lights — (0: the world cannot be light-sampled)."""
         out = (C.c_uint32 * 2)()
         check(lib().rt_renderer_light_sampling_info(self.h, out))
         return {"enabled": bool(out[0]), "lights": out[1]}
@@ -432,8 +456,8 @@ class MultiRenderer:
         check(lib().rt_multi_renderer_refine(self.h, n_samples))
 
     def light_sampling(self, on=True):
-        """rt_renderer_light_sampling_enable on every rank."""
-        check(lib().rt_multi_renderer_light_sampling_enable(self.h, 1 if on else 0))
+        """rt_renderer_light_sampling_enable on every rank; `on` as Renderer.light_sampling takes it."""
+        check(lib().rt_multi_renderer_light_sampling_enable(self.h, light_sampling_mode(on)))
 
     def DownloadRenderbuffer(self):
         out = np.zeros((self.cfg.height, self.cfg.width, 4), dtype=np.float32)

@@ -82,7 +82,7 @@ SYMBOLS = [
     "rt_renderer_aov_enable", "rt_renderer_aov_info", "rt_renderer_aov_download", "rt_denoise_params_default", "rt_renderer_denoise",
     "rt_renderer_denoise_async", "rt_renderer_denoise_download",
     "rt_renderer_light_sampling_enable", "rt_renderer_light_sampling_info", "rt_multi_renderer_light_sampling_enable", "rt_world_quad_lights",
-    "rt_renderer_kernel_form",
+    "rt_renderer_kernel_form", "rt_world_lights", "rt_scene_cornell_lamp",
 ]
 
 _lib = None
@@ -166,6 +166,7 @@ def lib():
     L.rt_scene_set_perlin.argtypes = [C.c_void_p, C.c_uint64]
     L.rt_scene_set_image.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
     L.rt_scene_cornell_box.argtypes = [P(C.c_void_p)]
+    L.rt_scene_cornell_lamp.argtypes = [P(C.c_void_p)]
     L.rt_scene_add_box.argtypes = [C.c_void_p, vec3, vec3, C.c_int32, C.c_float, vec3, P(C.c_int32)]
     L.rt_scene_book2_final.argtypes = [C.c_uint64, P(C.c_void_p)]
     L.rt_scene_prim_bounds.argtypes = [C.c_void_p, C.c_int32, vec3, vec3]
@@ -207,6 +208,7 @@ def lib():
     L.rt_renderer_light_sampling_info.argtypes = [C.c_void_p, C.c_uint32 * 2]
     L.rt_multi_renderer_light_sampling_enable.argtypes = [C.c_void_p, C.c_uint32]
     L.rt_world_quad_lights.argtypes = [P(WorldFlat), C.c_uint32 * 16, C.c_float * 16, P(C.c_uint32)]
+    L.rt_world_lights.argtypes = [P(WorldFlat), C.c_uint32, C.c_uint32 * 16, C.c_uint32 * 16, C.c_float * 16, P(C.c_uint32)]
     L.rt_multi_renderer_create.argtypes = [P(RenderConfig), P(Camera), P(WorldFlat), C.c_uint32, C.c_void_p, P(C.c_void_p)]
     L.rt_multi_renderer_destroy.argtypes = [C.c_void_p]
     L.rt_multi_renderer_destroy.restype = None

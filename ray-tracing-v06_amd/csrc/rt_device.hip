@@ -166,10 +166,14 @@ struct rt_renderer {
     bool aov_on = false;
     uint32_t aov_max = 0, aov_done = 0;
     const char* aov_refused = nullptr;   // the first material of the world the feature pass does not cover (a medium, a noise or an image texture)
-    // light sampling (rt_renderer_light_sampling_enable): the world's quad lights as rt_world_quad_lights gave them at creation (or why it gave none), and —
-    // from the first enable — the scene image with the light table behind it, the NEE form of this renderer's kernel and the LDS that one takes
-    struct { bool on = false; uint32_t n = 0, quad[RT_MAX_LIGHTS] = {}; float area[RT_MAX_LIGHTS] = {}; std::string refused;
-             DevBuf blob; const void* kernel = nullptr; uint32_t lds_bytes = 0, blocks_per_cu = 0; } nee;
+    // light sampling (rt_renderer_light_sampling_enable): per mode (tab[mode - 1]) the world's lights as rt_world_lights gave them at creation (or why it gave
+    // none) and — from the first enable of that mode — the scene image with its light table behind it and the LDS that takes; one NEE form of this renderer's
+    // kernel serves both modes (they differ only in what the table holds)
+    struct LightTable { uint32_t n = 0, kind[RT_MAX_LIGHTS] = {}, index[RT_MAX_LIGHTS] = {}; float area[RT_MAX_LIGHTS] = {}, sphere[RT_MAX_LIGHTS][4] = {}; std::string refused;
+                        DevBuf blob; uint32_t table_vec4 = 0, lds_bytes = 0, blocks_per_cu = 0; bool built = false; };
+    struct { uint32_t mode = RT_LIGHT_SAMPLING_OFF; LightTable tab[2]; const void* kernel = nullptr;
+             bool on() const { return mode != RT_LIGHT_SAMPLING_OFF; }
+             const LightTable& cur() const { return tab[mode - 1u]; } } nee;
     // denoiser (rt_renderer_denoise): guide records, the two colour buffers the iterations ping-pong, the output frame; allocated at first use
     DevBuf dn_g0, dn_g1, dn_a, dn_b, dn_out;
     // ordering between refine steps and the filter, whichever streams the caller gives them: refine_ev = end of the last refine step (the filter
@@ -343,7 +347,7 @@ struct rt_renderer {
             p.out = out;
             return launch_render(p, variant, st);
         }
-        const uint32_t end_s = first_s + n_s, n_pixels = (uint32_t)n_local_pixels(tm), grid = n_cus * (nee.on ? nee.blocks_per_cu : stream_blocks_per_cu);
+        const uint32_t end_s = first_s + n_s, n_pixels = (uint32_t)n_local_pixels(tm), grid = n_cus * (nee.on() ? nee.cur().blocks_per_cu : stream_blocks_per_cu);
         StreamParams p = call_params(refine ? end_s : cfg.samples_per_pixel);
         std::vector<hipEvent_t>& ring = kev[n_renders % RT_TIMES_RING];   // the event ring: this call's slot, four events per pass, created at first use
         const uint32_t call_passes = kev_passes[n_renders % RT_TIMES_RING] = (n_s + pass_spp - 1u) / pass_spp;
@@ -377,7 +381,7 @@ struct rt_renderer {
             XchgParams xp;
             if (variant == 5) { xp = xchg_params(p); args[0] = &xp; }
             HIP_TRY(hipEventRecord(ke[1], st));
-            HIP_TRY(hipLaunchKernel(nee.on ? nee.kernel : stream_kernel, dim3(grid), dim3(stream_block), args, nee.on ? nee.lds_bytes : stream_lds_bytes, st));
+            HIP_TRY(hipLaunchKernel(nee.on() ? nee.kernel : stream_kernel, dim3(grid), dim3(stream_block), args, nee.on() ? nee.cur().lds_bytes : stream_lds_bytes, st));
             HIP_TRY(hipEventRecord(ke[2], st));
 #ifdef RT_PHASE_TIMERS
             if (const int rc = report_phase_timers(phase_acc, st)) return rc;
@@ -411,7 +415,7 @@ struct rt_renderer {
         frame_params(p, spp);
         p.scene = scene.packed;
         p.scene.n_top = scene.big ? n_top : 0u;
-        if (nee.on) { p.scene.blob = nee.blob.as<uint4>(); p.scene.blob_vec4 += 1u + nee.n; }   // the same image with the light table behind it
+        if (nee.on()) { p.scene.blob = nee.cur().blob.as<uint4>(); p.scene.blob_vec4 += nee.cur().table_vec4; }   // the same image with the light table behind it
         p.samples = samples.as<float4>();
         p.inner_keep = tune[0] ? tune[0] : 1u; p.shade_min = tune[1]; p.leaf_min = tune[2];
         const size_t n_pass = n_local_pixels(tm) * pass_spp;   // 16-B records per array
@@ -512,7 +516,15 @@ extern "C" int rt_renderer_create(const rt_render_config* cfg, const rt_camera* 
         else if (t == RT_MAT_LAMBERTIAN_NOISE) r->aov_refused = "a noise texture (RT_MAT_LAMBERTIAN_NOISE)";
         else if (t == RT_MAT_LAMBERTIAN_IMAGE) r->aov_refused = "an image texture (RT_MAT_LAMBERTIAN_IMAGE)";
     }
-    if (rt_world_quad_lights(world, r->nee.quad, r->nee.area, &r->nee.n) != RT_OK) { r->nee.refused = rt_last_error(); r->nee.n = 0; }
+    for (uint32_t mode = RT_LIGHT_SAMPLING_QUADS; mode <= RT_LIGHT_SAMPLING_ALL; mode++) {
+        rt_renderer::LightTable& t = r->nee.tab[mode - 1u];
+        if (rt_world_lights(world, mode, t.kind, t.index, t.area, &t.n) != RT_OK) { t.refused = rt_last_error(); t.n = 0; }
+        for (uint32_t i = 0; i < t.n; i++)
+            if (t.kind[i] == RT_LIGHT_SPHERE) {   // the world's arrays are borrowed during creation only: what the table says of a sphere is taken now
+                const rt_prim& pr = world->prims[t.index[i]];
+                t.sphere[i][0] = pr.c0[0]; t.sphere[i][1] = pr.c0[1]; t.sphere[i][2] = pr.c0[2]; t.sphere[i][3] = pr.radius;
+            }
+    }
     r->cam = *cam;   // the camera of the first launch; rt_renderer_set_camera replaces it (Renderer.cu:117 reads the caller's camera at every Render())
     rc = r->scene.upload(world);
     if (rc != RT_OK) { delete r; return rc; }
@@ -592,18 +604,20 @@ extern "C" int rt_renderer_set_camera(rt_renderer* r, const rt_camera* cam) {
     return RT_OK;
 }
 
-// Light sampling.  Off: every launch is what it was.  On: the NEE form of the renderer's own kernel, on a copy of the scene image that ends with the light table.
+// Light sampling.  Off: every launch is what it was.  On: the NEE form of the renderer's own kernel, on a copy of the scene image that ends with the light table
+// of the mode: a header (n_l, -, -, -), n_l entries (index, area, kind, -), and — mode RT_LIGHT_SAMPLING_ALL — n_l more (Cx, Cy, Cz, r), zeros for a quad.
 extern "C" int rt_renderer_light_sampling_enable(rt_renderer* r, uint32_t on) {
     if (!r) return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: null renderer");
-    if (on > 1) return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: on must be 0 or 1");
-    if ((on != 0) == r->nee.on) return RT_OK;   // nothing changes, the refinement goes on
+    if (on > RT_LIGHT_SAMPLING_ALL) return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: on must be 0 (off), 1 (quad lights) or 2 (quad and sphere lights)");
+    if (on == r->nee.mode) return RT_OK;   // nothing changes, the refinement goes on
     if (on) {
+        rt_renderer::LightTable& t = r->nee.tab[on - 1u];
         if (r->variant < 2 || r->variant == 5 || r->tol)
             return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: kernel variant %u has no light-sampling form (the baseline kernel 1, the ray exchange 5 and the tolerance mode 6 do not; use variant 0, 2 or 3)", r->tol ? 6u : r->variant);
-        if (!r->nee.refused.empty()) return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: %s", r->nee.refused.c_str());
+        if (!t.refused.empty()) return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: %s", t.refused.c_str());
         HIP_TRY(hipSetDevice(r->cfg.device));
-        if (!r->nee.kernel) {
-            const uint32_t table_vec4 = 1u + r->nee.n;
+        if (!t.built) {   // set last: a failure on the way is tried again
+            const uint32_t table_vec4 = 1u + t.n * (on == RT_LIGHT_SAMPLING_ALL ? 2u : 1u);
             PackedSceneRef with_table = r->scene.packed;
             with_table.blob_vec4 += table_vec4;
             const uint32_t lds = (uint32_t)stream_kernel_lds_bytes(r->stream_block, with_table, r->scene.big, r->scene.wide, r->n_top);
@@ -612,27 +626,34 @@ extern "C" int rt_renderer_light_sampling_enable(rt_renderer* r, uint32_t on) {
             const void* k = stream_kernel_for(stream_kernel_key(r->variant, false, r->scene) | RT_KEY_NEE);
             if (!k) return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: this world's kernel has no light-sampling form");
             std::vector<uint4> table(table_vec4, make_uint4(0u, 0u, 0u, 0u));
-            table[0].x = r->nee.n;
-            for (uint32_t i = 0; i < r->nee.n; i++) { table[1u + i].x = r->nee.quad[i]; std::memcpy(&table[1u + i].y, &r->nee.area[i], 4); }
-            HIP_TRY(r->nee.blob.alloc(((size_t)r->scene.packed.blob_vec4 + table_vec4) * sizeof(uint4)));
-            HIP_TRY(hipMemcpy(r->nee.blob.p, r->scene.blob.p, (size_t)r->scene.packed.blob_vec4 * sizeof(uint4), hipMemcpyDeviceToDevice));
-            HIP_TRY(hipMemcpy(r->nee.blob.as<uint4>() + r->scene.packed.blob_vec4, table.data(), table.size() * sizeof(uint4), hipMemcpyHostToDevice));
-            HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            r->nee.lds_bytes = lds;
-            r->nee.blocks_per_cu = std::min(2u, RT_LDS_PER_CU / lds);
+            table[0].x = t.n;
+            for (uint32_t i = 0; i < t.n; i++) {
+                table[1u + i].x = t.index[i]; std::memcpy(&table[1u + i].y, &t.area[i], 4); table[1u + i].z = t.kind[i];
+                if (t.kind[i] == RT_LIGHT_SPHERE) std::memcpy(&table[1u + t.n + i], t.sphere[i], 16);
+            }
+            HIP_TRY(t.blob.alloc(((size_t)r->scene.packed.blob_vec4 + table_vec4) * sizeof(uint4)));
+            HIP_TRY(hipMemcpy(t.blob.p, r->scene.blob.p, (size_t)r->scene.packed.blob_vec4 * sizeof(uint4), hipMemcpyDeviceToDevice));
+            HIP_TRY(hipMemcpy(t.blob.as<uint4>() + r->scene.packed.blob_vec4, table.data(), table.size() * sizeof(uint4), hipMemcpyHostToDevice));
+            const uint32_t lds_set = std::max(lds, std::max(r->nee.tab[0].lds_bytes, r->nee.tab[1].lds_bytes));   // one kernel, two tables: the attribute covers the larger
+            HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_set));
+            t.table_vec4 = table_vec4;
+            t.lds_bytes = lds;
+            t.blocks_per_cu = std::min(2u, RT_LDS_PER_CU / lds);
             r->nee.kernel = k;
+            t.built = true;
         }
     }
-    r->nee.on = on != 0;    // of the NEXT launch; launches already enqueued keep their kernel and their image (the image with the table stays allocated)
-    r->refine_done = 0;     // samples drawn by the other estimator belong to another sequence
+    r->nee.mode = on;       // of the NEXT launch; launches already enqueued keep their kernel and their image (the images with the tables stay allocated)
+    r->refine_done = 0;     // samples drawn by another estimator belong to another sequence
     r->aov_done = 0;
     return RT_OK;
 }
 
 extern "C" int rt_renderer_light_sampling_info(rt_renderer* r, uint32_t out[2]) {
     if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_info: null argument");
-    out[0] = r->nee.on ? 1u : 0u;
-    out[1] = r->nee.refused.empty() ? r->nee.n : 0u;
+    const rt_renderer::LightTable& t = r->nee.tab[r->nee.on() ? r->nee.mode - 1u : 0u];
+    out[0] = r->nee.mode;
+    out[1] = t.refused.empty() ? t.n : 0u;
     return RT_OK;
 }
 
@@ -863,8 +884,8 @@ extern "C" int rt_renderer_kernel_form(rt_renderer* r, uint32_t out[9]) {
     for (int i = 0; i < 9; i++) out[i] = 0u;
     if (r->variant < 2) { out[0] = RT_KERNEL_BASELINE; return RT_OK; }
     // the key launch() resolves: plan()'s for the plain kernel, rt_renderer_light_sampling_enable's while sampling is on
-    const uint32_t key = r->nee.on ? stream_kernel_key(r->variant, false, r->scene) | RT_KEY_NEE : stream_kernel_key(r->variant, r->tol, r->scene);
-    if (stream_kernel_for(key) != (r->nee.on ? r->nee.kernel : r->stream_kernel)) return rt_fail(RT_ERR_INVALID, "rt_renderer_kernel_form: the key does not name the kernel the renderer holds");
+    const uint32_t key = r->nee.on() ? stream_kernel_key(r->variant, false, r->scene) | RT_KEY_NEE : stream_kernel_key(r->variant, r->tol, r->scene);
+    if (stream_kernel_for(key) != (r->nee.on() ? r->nee.kernel : r->stream_kernel)) return rt_fail(RT_ERR_INVALID, "rt_renderer_kernel_form: the key does not name the kernel the renderer holds");
     if (key == RT_KEY_XCHG) { out[0] = RT_KERNEL_XCHG; return RT_OK; }
     out[0] = RT_KERNEL_STREAM;
     stream_key_fields(key, out + 1);

@@ -498,12 +498,13 @@ extern "C" int rt_scene_get_flat(const rt_scene* s, rt_world_flat* out) {
 
 // perlin::perlin() ("The Next Week"): randvec[i] = unit_vector(vec3::random(-1, 1)); perm = identity shuffled by
 // `for i = n-1 .. 1: swap(p[i], p[random_int(0, i)])`, three times.  Uniforms: the build's sequential host stream, id 0x9E81.
-// The lights of light sampling: the quads whose material is a diffuse light, in quad-index order, each with the area of its
-// parallelogram — sqrt(dot(n, n)) of n = cross(u, v), fp32, in that order — or the reason this world has no light-sampling form.
-extern "C" int rt_world_quad_lights(const rt_world_flat* w, uint32_t out_quad[RT_MAX_LIGHTS], float out_area[RT_MAX_LIGHTS], uint32_t* out_n) {
-    if (!w || !out_quad || !out_area || !out_n) return rt_fail(RT_ERR_INVALID, "rt_world_quad_lights: null argument");
-    *out_n = 0;
-    if ((w->n_quads && !w->quads) || (w->n_materials && !w->materials)) return rt_fail(RT_ERR_INVALID, "rt_world_quad_lights: world array is null");
+// The lights of light sampling, for both entry points below: what every mode refuses (traversal, constant medium), then the quads whose
+// material is a diffuse light, in quad-index order, each with the area of its parallelogram — sqrt(dot(n, n)) of n = cross(u, v), fp32, in that order — and,
+// with_spheres, the static spheres with radius > 0 whose material is a diffuse light, in primitive order, area = (12.566371f * r) * r.  `none` and `many`
+// are the caller's words for an empty list and for one past RT_MAX_LIGHTS.  out_kind may be null.
+static_assert(RT_MAX_LIGHTS == 16, "the refusal messages below say 16");
+static int world_lights(const rt_world_flat* w, bool with_spheres, const char* none, const char* many, uint32_t* out_kind, uint32_t* out_index, float* out_area,
+                        uint32_t* out_n) {
     if (w->traversal != RT_TRAVERSAL_STACK)
         return rt_fail(RT_ERR_INVALID, "light sampling: the world has a queue or wide4 traversal (RT_TRAVERSAL_QUEUE, RT_TRAVERSAL_WIDE4); the light-sampling kernels walk the tree with the stack");
     for (uint32_t i = 0; i < w->n_materials; i++)
@@ -514,15 +515,52 @@ extern "C" int rt_world_quad_lights(const rt_world_flat* w, uint32_t out_quad[RT
         const rt_quad& q = w->quads[i];
         if (q.mat >= w->n_materials) return rt_fail(RT_ERR_INVALID, "quad %u: material index out of range", i);
         if (w->materials[q.mat].type != RT_MAT_DIFFUSE_LIGHT) continue;
-        if (n == RT_MAX_LIGHTS) return rt_fail(RT_ERR_INVALID, "light sampling: the world has more than %d quad lights", RT_MAX_LIGHTS);
+        if (n == RT_MAX_LIGHTS) return rt_fail(RT_ERR_INVALID, "%s", many);
         const f3 nrm = cross(mk3(q.u[0], q.u[1], q.u[2]), mk3(q.v[0], q.v[1], q.v[2]));
-        out_quad[n] = i;
+        if (out_kind) out_kind[n] = RT_LIGHT_QUAD;
+        out_index[n] = i;
         out_area[n] = sqrtf(dot(nrm, nrm));
         n++;
     }
-    if (n == 0) return rt_fail(RT_ERR_INVALID, "light sampling: the world has no quad light (a quad whose material is RT_MAT_DIFFUSE_LIGHT); sphere lights emit but are not sampled");
+    for (uint32_t i = 0; with_spheres && i < w->n_prims; i++) {
+        const rt_prim& pr = w->prims[i];
+        const uint32_t mat = pr.mat & ~RT_PRIM_MOVING;
+        if (mat >= w->n_materials) return rt_fail(RT_ERR_INVALID, "primitive %u: material index out of range", i);
+        if (w->materials[mat].type != RT_MAT_DIFFUSE_LIGHT || (pr.mat & RT_PRIM_MOVING) || !(pr.radius > 0.0f)) continue;
+        if (n == RT_MAX_LIGHTS) return rt_fail(RT_ERR_INVALID, "%s", many);
+        if (out_kind) out_kind[n] = RT_LIGHT_SPHERE;
+        out_index[n] = i;
+        out_area[n] = (12.566371f * pr.radius) * pr.radius;
+        n++;
+    }
+    if (n == 0) return rt_fail(RT_ERR_INVALID, "%s", none);
     *out_n = n;
     return RT_OK;
+}
+
+extern "C" int rt_world_quad_lights(const rt_world_flat* w, uint32_t out_quad[RT_MAX_LIGHTS], float out_area[RT_MAX_LIGHTS], uint32_t* out_n) {
+    if (!w || !out_quad || !out_area || !out_n) return rt_fail(RT_ERR_INVALID, "rt_world_quad_lights: null argument");
+    *out_n = 0;
+    if ((w->n_quads && !w->quads) || (w->n_materials && !w->materials)) return rt_fail(RT_ERR_INVALID, "rt_world_quad_lights: world array is null");
+    return world_lights(w, false, "light sampling: the world has no quad light (a quad whose material is RT_MAT_DIFFUSE_LIGHT); sphere lights emit but are not sampled",
+                        "light sampling: the world has more than 16 quad lights", nullptr, out_quad, out_area, out_n);
+}
+
+// The lights of either mode.  RT_LIGHT_SAMPLING_QUADS: rt_world_quad_lights' list and refusals.  RT_LIGHT_SAMPLING_ALL: the same quads in the same order,
+// then the sphere lights; a moving sphere is not in the table and keeps emitting when hit.
+extern "C" int rt_world_lights(const rt_world_flat* w, uint32_t mode, uint32_t out_kind[RT_MAX_LIGHTS], uint32_t out_index[RT_MAX_LIGHTS], float out_area[RT_MAX_LIGHTS],
+                               uint32_t* out_n) {
+    if (!w || !out_kind || !out_index || !out_area || !out_n) return rt_fail(RT_ERR_INVALID, "rt_world_lights: null argument");
+    *out_n = 0;
+    if (mode != RT_LIGHT_SAMPLING_QUADS && mode != RT_LIGHT_SAMPLING_ALL)
+        return rt_fail(RT_ERR_INVALID, "rt_world_lights: mode must be RT_LIGHT_SAMPLING_QUADS (1) or RT_LIGHT_SAMPLING_ALL (2)");
+    if (mode == RT_LIGHT_SAMPLING_QUADS) {
+        for (uint32_t i = 0; i < RT_MAX_LIGHTS; i++) out_kind[i] = RT_LIGHT_QUAD;
+        return rt_world_quad_lights(w, out_index, out_area, out_n);
+    }
+    if ((w->n_quads && !w->quads) || (w->n_materials && !w->materials) || (w->n_prims && !w->prims)) return rt_fail(RT_ERR_INVALID, "rt_world_lights: world array is null");
+    return world_lights(w, true, "light sampling: the world has no light to sample (a quad or a static sphere of radius > 0 whose material is RT_MAT_DIFFUSE_LIGHT)",
+                        "light sampling: the world has more than 16 lights (quads and static spheres whose material is RT_MAT_DIFFUSE_LIGHT)", out_kind, out_index, out_area, out_n);
 }
 
 extern "C" int rt_scene_set_perlin(rt_scene* s, uint64_t seed) {
@@ -759,6 +797,33 @@ extern "C" int rt_scene_cornell_box(rt_scene** out) {
     cornell_quad(s, mk3(0, 0, 555), mk3(555, 0, 0), mk3(0, 555, 0), m_white);
     cornell_box(s, mk3(0, 0, 0), mk3(165, 330, 165), 15.0f, mk3(265, 0, 295), m_white);
     cornell_box(s, mk3(0, 0, 0), mk3(165, 165, 165), -18.0f, mk3(130, 0, 65), m_white);
+    const float black[3] = {0.0f, 0.0f, 0.0f};
+    rt_scene_set_background(s, 1, black);
+    int rc = rt_scene_build_bvh_topdown(s);
+    if (rc != RT_OK) { delete s; return rc; }
+    *out = s;
+    return RT_OK;
+}
+
+// The Cornell box lit by a lamp: no ceiling quad light, a sphere light of radius 40 at (278, 470, 278) emitting (40, 40, 40), the two boxes as they are.
+extern "C" int rt_scene_cornell_lamp(rt_scene** out) {
+    if (!out) return rt_fail(RT_ERR_INVALID, "rt_scene_cornell_lamp: null out");
+    rt_scene* s = new rt_scene();
+    const float red[3] = {0.65f, 0.05f, 0.05f}, white[3] = {0.73f, 0.73f, 0.73f}, green[3] = {0.12f, 0.45f, 0.15f}, light[3] = {40.0f, 40.0f, 40.0f};
+    int32_t m_red, m_white, m_green, m_light;
+    rt_scene_add_material(s, RT_MAT_LAMBERTIAN, red, 0.0f, nullptr, &m_red);
+    rt_scene_add_material(s, RT_MAT_LAMBERTIAN, white, 0.0f, nullptr, &m_white);
+    rt_scene_add_material(s, RT_MAT_LAMBERTIAN, green, 0.0f, nullptr, &m_green);
+    rt_scene_add_material(s, RT_MAT_DIFFUSE_LIGHT, light, 0.0f, nullptr, &m_light);
+    cornell_quad(s, mk3(555, 0, 0), mk3(0, 555, 0), mk3(0, 0, 555), m_green);
+    cornell_quad(s, mk3(0, 0, 0), mk3(0, 555, 0), mk3(0, 0, 555), m_red);
+    cornell_quad(s, mk3(0, 0, 0), mk3(555, 0, 0), mk3(0, 0, 555), m_white);
+    cornell_quad(s, mk3(555, 555, 555), mk3(-555, 0, 0), mk3(0, 0, -555), m_white);
+    cornell_quad(s, mk3(0, 0, 555), mk3(555, 0, 0), mk3(0, 555, 0), m_white);
+    cornell_box(s, mk3(0, 0, 0), mk3(165, 330, 165), 15.0f, mk3(265, 0, 295), m_white);
+    cornell_box(s, mk3(0, 0, 0), mk3(165, 165, 165), -18.0f, mk3(130, 0, 65), m_white);
+    const float lamp_at[3] = {278.0f, 470.0f, 278.0f};
+    rt_scene_add_sphere(s, lamp_at, 40.0f, m_light, nullptr);
     const float black[3] = {0.0f, 0.0f, 0.0f};
     rt_scene_set_background(s, 1, black);
     int rc = rt_scene_build_bvh_topdown(s);

@@ -260,7 +260,7 @@ extern "C" int rt_multi_renderer_set_camera(rt_multi_renderer* m, const rt_camer
 
 extern "C" int rt_multi_renderer_light_sampling_enable(rt_multi_renderer* m, uint32_t on) {
     if (!m) return rt_fail(RT_ERR_INVALID, "rt_multi_renderer_light_sampling_enable: null renderer");
-    for (rt_renderer* r : m->parts) {   // every rank holds the same world on the same variant: the first refuses what any would, before any part changes
+    for (rt_renderer* r : m->parts) {   // every rank holds the same world on the same variant: the first refuses what any would (mode included), before any part changes
         const int rc = rt_renderer_light_sampling_enable(r, on);
         if (rc != RT_OK) return rc;
     }

@@ -207,9 +207,9 @@ __device__ __forceinline__ WideNodeData fetch_wide_node(const char* nodes, const
 // TOL (variant 6, opt-in): the hot loop's plane parameters are (b - o) * RN(1/d) instead of the exact quotients — inside north_star's |delta| < 1e-3,
 //      not bit-exact by construction (rt_fastdiv.hpp: slab_near_far_tolerant).  LDS-resident RT_WORLD_BVH worlds of the reference's feature set (EXT == 0) only.
 // NEE (rt_renderer_light_sampling_enable, opt-in; EXT >= 1 only): a Lambertian / checker hit draws its next direction from the mixture of its own cosine
-//      distribution and a distribution over the world's quad lights, and weighs the path by the ratio of the densities.  The light table —
-//      a header (n_l, -, -, -), then (quad index, area, -, -) per light — lies behind the quads' shade records in the image the NEE launches are given, so it
-//      costs no kernel argument: the other instantiations neither see it nor pay for it.
+//      distribution and a distribution over the world's lights, and weighs the path by the ratio of the densities.  The light table —
+//      a header (n_l, -, -, -), then (index, area, kind, -) per light, then — only where a kind says sphere — (Cx, Cy, Cz, r) per light — lies behind the
+//      quads' shade records in the image the NEE launches are given, so it costs no kernel argument: the other instantiations neither see it nor pay for it.
 template <bool EXACT, bool FILTER, int BLOCK, int WORLD = RT_WORLD_BVH, int EXT = 0, bool BIG = false, bool WIDE = BIG, bool TOL = false, bool NEE = false>
 __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(StreamParams p) {
     static_assert(!NEE || (EXT >= 1 && WORLD != RT_WORLD_BVH_QUEUE), "light sampling: worlds with quads, walked by the stack or as a list");
@@ -612,7 +612,18 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                     const bool nee_mat = NEE && (mtype == RT_MAT_LAMBERTIAN || mtype == RT_MAT_LAMBERTIAN_CHECKER);
                     const bool to_light = nee_mat && rng.next() < 0.5f;
                     f3 on_unit = mk3(0.0f);
-                    if (!NEE || !to_light) on_unit = rng_on_unit3(rng);
+                    uint32_t nee_li = 0u, nee_quad = 0u;   // NEE, light half: the light drawn, and its quad index
+                    bool to_sphere = false;                // ... or that it is a sphere light (§17), whose point is C + on_unit * r: the draw below serves it too
+                    if (NEE && to_light) {
+                        const float4* lights = quads + p.scene.n_quads * 5u;
+                        const uint32_t n_l = __float_as_uint(lights[0].x);
+                        if (n_l > 1u) nee_li = min((uint32_t)(rng.next() * (float)n_l), n_l - 1u);
+                        const float4 le = lights[1u + nee_li];
+                        nee_quad = __float_as_uint(le.x);
+                        to_sphere = __float_as_uint(le.z) != 0u;
+                        if (to_sphere) nee_li += n_l;      // where its (Cx, Cy, Cz, r) lies behind the entries
+                    }
+                    if (!NEE || !to_light || to_sphere) on_unit = rng_on_unit3(rng);
                     RT_PT(12);
                     if (EXT && mtype == RT_MAT_ISOTROPIC) {
                         scatter_dir = on_unit;   // isotropic phase function: any direction, never absorbed
@@ -620,16 +631,17 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                         scatter_dir = reflect(ray.d, normal) + on_unit * mparam;
                         scattered_ok = !(dot(scatter_dir, normal) < 0 || near_zero(scatter_dir));
                     } else {
-                        if (NEE && to_light) {   // a point of light i, uniform over its parallelogram; the direction stays unnormalised
-                            const float4* lights = quads + p.scene.n_quads * 5u;
-                            const uint32_t n_l = __float_as_uint(lights[0].x);
-                            uint32_t li = 0u;
-                            if (n_l > 1u) li = min((uint32_t)(rng.next() * (float)n_l), n_l - 1u);
+                        if (NEE && to_light) {   // a point of light i, uniform over its area; the direction stays unnormalised
+                            if (to_sphere) {
+                                const float4 sc = (quads + p.scene.n_quads * 5u)[1u + nee_li];
+                                scatter_dir = (mk3(sc.x, sc.y, sc.z) + on_unit * sc.w) - hit_p;
+                            } else {
                             const float la = rng.next();
                             const float lb = rng.next();
-                            const float4* qd = quads + __float_as_uint(lights[1u + li].x) * 4u;
+                            const float4* qd = quads + nee_quad * 4u;
                             const float4 a0 = qd[0], a1 = qd[1], a2 = qd[2];
                             scatter_dir = ((mk3(a0.x, a0.y, a0.z) + mk3(a1.x, a1.y, a1.z) * la) + mk3(a1.w, a2.x, a2.y) * lb) - hit_p;
+                            }
                         } else {
                         scatter_dir = normal + on_unit;
                         scattered_ok = !near_zero(scatter_dir);
@@ -647,14 +659,33 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                             float pdf_light = 0.0f;
                             for (uint32_t j = 0; j < n_l; j++) {
                                 const float4 lt = lights[1u + j];
+                                float pl_j = 0.0f;
+                                if (__float_as_uint(lt.z) != 0u) {
+                                    // a sphere light (§17): the area-uniform point's solid-angle density, summed over both crossings of the line through the
+                                    // sphere; |n.d| = sqrt(disc) / r at both
+                                    const float4 sc = lights[1u + n_l + j];
+                                    const f3 oc = mk3(sc.x, sc.y, sc.z) - hit_p;
+                                    const float h = dot(d, oc);
+                                    const f3 cr = cross(oc, d);
+                                    const float disc = (sc.w * sc.w) * len2 - dot(cr, cr);   // = h^2 - len2 (|oc|^2 - r^2), without the cancellation of numbers of size len2 |oc|^2
+                                    if (!(disc > 0)) {
+                                        if (to_sphere && nee_li == n_l + j) scattered_ok = false;   // the drawn point itself, lost on the silhouette: a failed scatter
+                                    } else {
+                                        const float sq = sqrtf(disc);
+                                        const float den = ((sq / sc.w) / len) * lt.y;
+                                        const float t1 = (h - sq) / len2, t2 = (h + sq) / len2;
+                                        if (t1 > 0) pl_j = pl_j + ((t1 * t1) * len2) / den;
+                                        if (t2 > 0) pl_j = pl_j + ((t2 * t2) * len2) / den;
+                                    }
+                                } else {
                                 const float4* qd = quads + __float_as_uint(lt.x) * 4u;
                                 const float4 a0 = qd[0], a1 = qd[1], a2 = qd[2], a3 = qd[3];
                                 const f3 ln = mk3(a2.z, a2.w, a3.x);
                                 HitRec tmp;
                                 tmp.distance = RT_MISS_DIST; tmp.normal = mk3(0.0f); tmp.prim = -1; tmp.mat = 0;
-                                float pl_j = 0.0f;
                                 if (quad_closest_intersection(mk3(a0.x, a0.y, a0.z), a0.w, mk3(a1.x, a1.y, a1.z), mk3(a1.w, a2.x, a2.y), ln, mk3(a3.y, a3.z, a3.w), 0u, 0, lray, tmp))
                                     pl_j = ((tmp.distance * tmp.distance) * len2) / ((fabsf(dot(d, ln)) / len) * lt.y);
+                                }
                                 pdf_light = pdf_light + pl_j;
                             }
                             pdf_light = pdf_light / (float)n_l;

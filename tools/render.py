@@ -22,13 +22,17 @@ PREFIX_depth.png (nearest white, misses black) and PREFIX_albedo.png.  One GPU; 
 
 samples the world's quad lights at every Lambertian hit (rt_renderer_light_sampling_enable): the same expected image from far fewer
 samples where a small emitter lights the world.  Works with every mode above; refused for worlds without a quad light or with a medium.
+
+    python tools/render.py --scene cornell_lamp --spp 64 --light-sampling-mode all --out out.png
+
+samples sphere lights too (RT_LIGHT_SAMPLING_ALL): the Cornell box lit by a lamp, which has no quad light for --light-sampling to take.
 """
 import argparse, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import __graft_entry__ as G
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--scene", default="book1_final", choices=["book1_final", "book2_moving", "three_spheres", "cornell_box", "book2_final"])
+ap.add_argument("--scene", default="book1_final", choices=["book1_final", "book2_moving", "three_spheres", "cornell_box", "cornell_lamp", "book2_final"])
 ap.add_argument("--width", type=int, default=1200)
 ap.add_argument("--height", type=int, default=800)
 ap.add_argument("--spp", type=int, default=500)
@@ -41,8 +45,11 @@ ap.add_argument("--until", type=float, default=None, metavar="NOISE", help="with
 ap.add_argument("--denoise", action="store_true", help="with --refine: also write the denoised frame (<out>_denoised.<ext>)")
 ap.add_argument("--aov", default=None, metavar="PREFIX", help="with --refine: write PREFIX_normal.png, PREFIX_depth.png, PREFIX_albedo.png")
 ap.add_argument("--light-sampling", action="store_true", help="next-event estimation over the world's quad lights (rt_renderer_light_sampling_enable)")
+ap.add_argument("--light-sampling-mode", choices=["quads", "all"], default=None,
+                help="switch light sampling on in this mode: quads (what --light-sampling selects) or all (quad and sphere lights, e.g. --scene cornell_lamp)")
 ap.add_argument("--out", default="render.png")
 a = ap.parse_args()
+light_mode = {"quads": 1, "all": 2}.get(a.light_sampling_mode, 1 if a.light_sampling else 0)   # RT_LIGHT_SAMPLING_*
 if a.refine < 0 or (a.until is not None and (a.refine == 0 or a.gpus > 1)):
     ap.error("--until needs --refine STEP > 0 and one GPU (the multi-GPU renderer has no noise figure)")
 if (a.denoise or a.aov) and (a.refine == 0 or a.gpus > 1):
@@ -52,8 +59,8 @@ from ray_tracing_v06_amd import image_io
 W, H = a.width, a.height
 if a.scene == "three_spheres":
     scene, cam = p.Scene.three_spheres(), p.PinholeCamera((0, 0, 0), (0, 0, -1), (0, 1, 0), 90.0, W / H)
-elif a.scene == "cornell_box":
-    scene, cam = p.Scene.cornell_box(), p.PinholeCamera((278, 278, -800), (278, 278, 0), (0, 1, 0), 40.0, W / H)
+elif a.scene in ("cornell_box", "cornell_lamp"):
+    scene, cam = getattr(p.Scene, a.scene)(), p.PinholeCamera((278, 278, -800), (278, 278, 0), (0, 1, 0), 40.0, W / H)
 elif a.scene == "book2_final":
     scene, cam = p.Scene.book2_final(a.seed), p.MotionBlurCamera((478, 278, -600), (278, 278, 0), (0, 1, 0), 40.0, W / H, 0.0, 1.0)
 elif a.scene == "book1_final":
@@ -66,8 +73,8 @@ if a.refine:
     step_spp = min(a.refine, a.spp)   # what one pass is sized for; the steps go on to --spp
     r = (p.MultiRenderer.MakeRenderer(W, H, step_spp, a.depth, cam, scene.getWorldPtr(), a.gpus, seed=a.seed) if a.gpus > 1
          else p.Renderer.MakeRenderer(W, H, step_spp, a.depth, cam, scene.getWorldPtr(), seed=a.seed, device=a.device))
-    if a.light_sampling:
-        r.light_sampling(True)
+    if light_mode:
+        r.light_sampling(light_mode)
     if a.denoise or a.aov:
         r.enable_aov()
     samples, ms = 0, 0.0
@@ -83,14 +90,14 @@ if a.refine:
             break
 elif a.gpus > 1:
     r = p.MultiRenderer.MakeRenderer(W, H, a.spp, a.depth, cam, scene.getWorldPtr(), a.gpus, seed=a.seed)
-    if a.light_sampling:
-        r.light_sampling(True)
+    if light_mode:
+        r.light_sampling(light_mode)
     r.Render()
     ms = r.times()[0]     # host wall-clock of Render(): all shards, the exchange, the assembly
 else:
     r = p.Renderer.MakeRenderer(W, H, a.spp, a.depth, cam, scene.getWorldPtr(), seed=a.seed, device=a.device)
-    if a.light_sampling:
-        r.light_sampling(True)
+    if light_mode:
+        r.light_sampling(light_mode)
     r.Render()
     ms = r.last_kernel_ms()
 fb = r.DownloadRenderbuffer()
@@ -117,4 +124,4 @@ if a.aov:
     image_io.write_png(a.aov + "_albedo.png", np.concatenate([f["albedo"], one], axis=2))
     extra["aov"] = [a.aov + s for s in ("_normal.png", "_depth.png", "_albedo.png")]
 print(json.dumps({**extra, "scene": a.scene, "width": W, "height": H, "spp": samples, "max_depth": a.depth, "render_ms": round(ms, 3),
-                  "msamples_per_s": round(W * H * samples / ms / 1e3, 1), "gpus": a.gpus, "light_sampling": a.light_sampling, "out": a.out}))
+                  "msamples_per_s": round(W * H * samples / ms / 1e3, 1), "gpus": a.gpus, "light_sampling": light_mode > 0, "light_sampling_mode": light_mode, "out": a.out}))
