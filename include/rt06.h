@@ -71,11 +71,16 @@ typedef struct rt_prim {
  * "Ray Tracing: The Next Week" (quad(Q,u,v), diffuse_light, camera background) in the reference's conventions.
  * PARITY UNPINNED: checked GPU against the build's own CPU oracle only. ---- */
 /* quad(Q,u,v,mat): plane point Q, edge vectors u and v; normal/D/w are the cached plane quantities
- * (n = cross(u,v), normal = unit(n), D = dot(normal,Q), w = n/dot(n,n)), filled by rt_scene_add_quad.  80 B.     */
+ * (n = cross(u,v), normal = unit(n), D = dot(normal,Q), w = n/dot(n,n)), filled by rt_scene_add_quad.  80 B.
+ * kind: RT_QUAD_PARALLELOGRAM (0, what every quad was: the interior is 0 <= alpha, beta <= 1) or RT_QUAD_TRIANGLE (1, the book's `tri`: the
+ * same plane and coordinates, the interior is alpha >= 0, beta >= 0, alpha + beta <= 1 — the triangle Q, Q + u, Q + v).  In a flat world the
+ * triangles FOLLOW the parallelograms: a kind above 1, or a kind-1 record in front of a kind-0 one, is refused before any kernel reads it.   */
+#define RT_QUAD_PARALLELOGRAM 0u
+#define RT_QUAD_TRIANGLE 1u
 typedef struct rt_quad {
     float    Q[3];      float D;
     float    u[3];      uint32_t mat;
-    float    v[3];      float pad0;
+    float    v[3];      uint32_t kind;
     float    normal[3]; float pad1;
     float    w[3];      float pad2;
 } rt_quad;
@@ -125,7 +130,7 @@ typedef struct rt_world_flat {
     const rt_bvh_node* nodes;
     const rt_prim*     prims;
     const rt_material* materials;
-    /* extension (see rt_quad): a primitive index i >= n_prims means quad i - n_prims                      */
+    /* extension (see rt_quad): a primitive index i >= n_prims means quad i - n_prims; the triangles are the last of the quads */
     const rt_quad*     quads;
     uint32_t n_quads;
     uint32_t background;         /* 0: the reference's sky gradient (Renderer.cu:150-151); 1: background_color */
@@ -204,6 +209,19 @@ int rt_scene_prim_bounds(const rt_scene* s, int32_t prim, float out_min[3], floa
 /* quad(Q,u,v,mat) of "The Next Week"; returns the quad index (worlds: BVH builders and HittableList, where the
  * quads follow the spheres; bvh_node trees take spheres only).                                            */
 int rt_scene_add_quad(rt_scene* s, const float Q[3], const float u[3], const float v[3], int32_t mat, int32_t* out_quad);
+/* tri(Q,u,v,mat) of "The Next Week" (a quad whose interior test is alpha >= 0 && beta >= 0 && alpha + beta <= 1; nothing of it is in the
+ * reference) from its vertices: Q = a, u = b - a, v = c - a, kind RT_QUAD_TRIANGLE; normal, D and w as rt_scene_add_quad fills them.  Bounds:
+ * the box of the three vertices, every axis padded to 1e-4 as a quad's.  RT_ERR_INVALID when dot(n, n) of n = cross(u, v) is not finite and
+ * > 0 (a degenerate face).  The scene keeps its triangles behind its parallelograms, whatever the order of the calls: *out_quad is the
+ * record's index among the scene's quads at the time of the call (a parallelogram added later moves it up by one).                     */
+int rt_scene_add_triangle(rt_scene* s, const float a[3], const float b[3], const float c[3], int32_t mat, int32_t* out_quad);
+/* An indexed triangle mesh (the book has none; not in the reference): n_vertices points xyz[3 * i ..], n_triangles faces indices[3 * f ..].
+ * Every vertex is scaled, rotated about y and translated on the host — p' = rot_y(p * scale, degrees) + translate, rt_scene_add_box's order
+ * and arithmetic (translate NULL = none) — and each face goes through rt_scene_add_triangle.  An index >= n_vertices, a scale that is not
+ * finite, or a bad material fails the whole call and leaves the scene unchanged.  Degenerate faces are skipped and counted out:
+ * *out_added = faces added, *out_first = index of the first of them among the scene's quads (either may be NULL).                       */
+int rt_scene_add_mesh(rt_scene* s, uint32_t n_vertices, const float* xyz, uint32_t n_triangles, const uint32_t* indices, int32_t mat,
+                      float scale, float rotate_y_degrees, const float translate[3], int32_t* out_first, uint32_t* out_added);
 /* camera::background of "The Next Week": mode 0 = the reference's sky gradient, 1 = constant colour       */
 int rt_scene_set_background(rt_scene* s, uint32_t mode, const float color[3]);
 /* selects RT_TRAVERSAL_STACK / RT_TRAVERSAL_QUEUE / RT_TRAVERSAL_WIDE4 for the BVH world of this scene (see the enum) */
@@ -234,6 +252,10 @@ int rt_scene_set_world_node_tree(rt_scene* s, int32_t root_ref);
 /* SceneBook2BVH::getWorldPtr (Scenes.h:72) resolved to flat arrays.  Pointers
  * stay valid until the scene is modified or destroyed.                        */
 int rt_scene_get_flat(const rt_scene* s, rt_world_flat* out);
+
+/* HOST (no GPU): how many of a flat world's quads are triangles (they are its last *out_n quads) — after the validation every consumer of a
+ * flat world runs: RT_ERR_INVALID for a kind above RT_QUAD_TRIANGLE or a triangle in front of a parallelogram.  Not in the reference.       */
+int rt_world_triangles(const rt_world_flat* world, uint32_t* out_n);
 
 /* cuHostRND::next (utilities/cuda_utilities/cuHostRND.h:9-32, cuHostRND.cpp:57-65): the host uniform
  * stream scene factories draw from.  Uniforms first .. first+n-1 of the library's counter-based host
@@ -343,6 +365,10 @@ int rt_renderer_kernel_info(rt_renderer* r, uint32_t out[4]);
 #define RT_KERNEL_STREAM 1
 #define RT_KERNEL_XCHG 2
 int rt_renderer_kernel_form(rt_renderer* r, uint32_t out[9]);
+/* *out = 1 when the NEXT launch runs an instantiation of the streaming kernel's triangle family: the same nine arguments as above, plus the book's `tri`
+ * interior test for the quads of kind RT_QUAD_TRIANGLE.  A world without triangles never does (it keeps the kernels it had); a world with triangles does
+ * on every streaming variant but under the queue / wide4 traversal, whose lane walks — like the baseline kernel — read the kind from the flat record.   */
+int rt_renderer_kernel_triangles(rt_renderer* r, uint32_t* out);
 /* Renderer::DownloadRenderbuffer (Renderer.cu:94-96): width*height*4 floats,
  * row-major, row 0 = bottom.  Only valid for world_size == 1.               */
 int rt_renderer_download(rt_renderer* r, float* host_rgba, size_t n_floats);
@@ -439,7 +465,8 @@ int rt_renderer_denoise_download(rt_renderer* r, float* host_rgba, size_t n_floa
 /* Light sampling (not in the reference; "Ray Tracing: The Rest of Your */
 /* Life"): opt-in next-event estimation for worlds lit by quad lights.  */
 /* ------------------------------------------------------------------ */
-/* A light is a quad whose material is RT_MAT_DIFFUSE_LIGHT; they are taken in quad-index order, 1 <= n_l <= RT_MAX_LIGHTS, each with
+/* A light is a quad of kind RT_QUAD_PARALLELOGRAM whose material is RT_MAT_DIFFUSE_LIGHT (a triangle with a light material emits when hit and is
+ * not sampled, like a moving sphere light); they are taken in quad-index order, 1 <= n_l <= RT_MAX_LIGHTS, each with
  * area = sqrt(dot(n, n)), n = cross(u, v), in fp32.  With sampling on, a hit on RT_MAT_LAMBERTIAN or RT_MAT_LAMBERTIAN_CHECKER that does
  * not end the path draws, in this order: c; if c < 0.5f a light — i = min((uint32_t)(next * (float)n_l), n_l - 1) when n_l > 1 (no draw
  * otherwise), then a, then b, and d = ((Q_i + u_i * a) + v_i * b) - hit_p, not normalised; otherwise d = normal + on_unit as without

@@ -268,6 +268,25 @@ public:
         }
         return prim;
     }
+    // tri(Q,u,v) of "The Next Week" from its vertices, and an indexed mesh of them (extensions, nothing of either in the reference; rt06.h:
+    // rt_scene_add_triangle, rt_scene_add_mesh).  AddTriangle returns the quad index, AddMesh the number of faces added (degenerate ones are skipped).
+    int32_t AddTriangle(glm::vec3 a, glm::vec3 b, glm::vec3 c, const Material* mat) {
+        const float pa[3] = {a[0], a[1], a[2]}, pb[3] = {b[0], b[1], b[2]}, pc[3] = {c[0], c[1], c[2]};
+        int32_t quad = 0;
+        check(rt_scene_add_triangle(s_, pa, pb, pc, material(mat), &quad), "rt_scene_add_triangle");
+        return quad;
+    }
+    uint32_t AddMesh(const std::vector<glm::vec3>& vertices, const std::vector<uint32_t>& indices, const Material* mat, float scale = 1.0f, float rotate_y_degrees = 0.0f,
+                     glm::vec3 translate = glm::vec3(0.0f), int32_t* out_first = nullptr) {
+        std::vector<float> xyz;
+        xyz.reserve(vertices.size() * 3);
+        for (const glm::vec3& p : vertices) { xyz.push_back(p[0]); xyz.push_back(p[1]); xyz.push_back(p[2]); }
+        const float t[3] = {translate[0], translate[1], translate[2]};
+        uint32_t added = 0;
+        check(rt_scene_add_mesh(s_, (uint32_t)vertices.size(), xyz.data(), (uint32_t)(indices.size() / 3), indices.data(), material(mat), scale, rotate_y_degrees, t, out_first, &added),
+              "rt_scene_add_mesh");
+        return added;
+    }
     void perlin(uint64_t seed) { check(rt_scene_set_perlin(s_, seed), "rt_scene_set_perlin"); }
     void image(uint32_t w, uint32_t h, const uint8_t* rgb) { check(rt_scene_set_image(s_, w, h, rgb), "rt_scene_set_image"); }
     void background(const Background& b) {

@@ -147,6 +147,30 @@ class Scene:
         check(lib().rt_scene_add_quad(self.h, v3(Q), v3(u), v3(v), mat, C.byref(out)))
         return out.value
 
+    def MakeTriangle(self, a, b, c, mat):
+        """tri of "The Next Week" from its three vertices (extension, not in the reference): a quad of kind 1; returns its quad index."""
+        out = C.c_int32()
+        check(lib().rt_scene_add_triangle(self.h, v3(a), v3(b), v3(c), mat, C.byref(out)))
+        return out.value
+
+    def MakeMesh(self, vertices, faces, mat, scale=1.0, rotate_y=0.0, translate=(0, 0, 0)):
+        """An indexed triangle mesh (extension): vertices (n, 3), faces (m, 3); every vertex is scaled, rotated about y (degrees) and translated
+        as MakeBox does it.  Degenerate faces are skipped.  Returns (index of the first triangle added, number added)."""
+        xyz = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+        idx = np.ascontiguousarray(faces, dtype=np.int64).reshape(-1, 3)
+        if idx.size and (idx.min() < 0 or idx.max() > 0xffffffff):
+            raise ValueError("MakeMesh: a face index is negative or does not fit 32 bits")
+        idx = np.ascontiguousarray(idx, dtype=np.uint32)
+        first, added = C.c_int32(), C.c_uint32()
+        check(lib().rt_scene_add_mesh(self.h, xyz.shape[0], xyz, idx.shape[0], idx, mat, scale, rotate_y, v3(translate), C.byref(first), C.byref(added)))
+        return first.value, added.value
+
+    def n_triangles(self):
+        """How many of the flat world's quads are triangles (its last ones): rt_world_triangles."""
+        w, n = self.getWorldPtr(), C.c_uint32()
+        check(lib().rt_world_triangles(C.byref(w), C.byref(n)))
+        return n.value
+
     def set_background(self, color=None):
         """None: the reference's sky gradient; a colour: camera::background of "The Next Week"."""
         if color is None:
@@ -404,6 +428,12 @@ class Renderer:
         form = {"kernel": ("baseline", "stream", "xchg")[out[0]]}
         form.update(zip(("exact", "filter", "world", "ext", "big", "wide", "tol", "nee"), out[1:]))
         return form
+
+    def kernel_triangles(self):
+        """True when the next launch runs the streaming kernel's triangle family (rt_renderer_kernel_triangles)."""
+        out = C.c_uint32()
+        check(lib().rt_renderer_kernel_triangles(self.h, C.byref(out)))
+        return bool(out.value)
 
     def DownloadRenderbuffer(self):
         out = np.zeros((self.cfg.height, self.cfg.width, 4), dtype=np.float32)

@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("RT06_LIB") or os.path.join(CSRC_DIR, "librt06.so")
 RT_OK = 0
 RT_PRIM_MOVING = 0x80000000
 MAT_LAMBERTIAN, MAT_METAL, MAT_DIELECTRIC, MAT_LAMBERTIAN_CHECKER, MAT_DIFFUSE_LIGHT, MAT_ISOTROPIC, MAT_LAMBERTIAN_NOISE, MAT_LAMBERTIAN_IMAGE = 0, 1, 2, 3, 4, 5, 6, 7
+QUAD_PARALLELOGRAM, QUAD_TRIANGLE = 0, 1
 WORLD_BVH, WORLD_LIST, WORLD_NODE_TREE = 0, 1, 2
 CAM_PINHOLE, CAM_DEFOCUS, CAM_MOTION = 0, 1, 2
 
@@ -28,7 +29,7 @@ vec3 = C.c_float * 3
 NODE_DT = np.dtype([("min", "<f4", 3), ("max", "<f4", 3), ("left", "<i4"), ("right", "<i4")])
 PRIM_DT = np.dtype([("c0", "<f4", 3), ("radius", "<f4"), ("c1", "<f4", 3), ("mat", "<u4")])
 MAT_DT = np.dtype([("albedo", "<f4", 3), ("param", "<f4"), ("albedo2", "<f4", 3), ("type", "<u4")])
-QUAD_DT = np.dtype([("Q", "<f4", 3), ("D", "<f4"), ("u", "<f4", 3), ("mat", "<u4"), ("v", "<f4", 3), ("pad0", "<f4"),
+QUAD_DT = np.dtype([("Q", "<f4", 3), ("D", "<f4"), ("u", "<f4", 3), ("mat", "<u4"), ("v", "<f4", 3), ("kind", "<u4"),
                     ("normal", "<f4", 3), ("pad1", "<f4"), ("w", "<f4", 3), ("pad2", "<f4")])
 
 
@@ -83,6 +84,7 @@ SYMBOLS = [
     "rt_renderer_denoise_async", "rt_renderer_denoise_download",
     "rt_renderer_light_sampling_enable", "rt_renderer_light_sampling_info", "rt_multi_renderer_light_sampling_enable", "rt_world_quad_lights",
     "rt_renderer_kernel_form", "rt_world_lights", "rt_scene_cornell_lamp",
+    "rt_scene_add_triangle", "rt_scene_add_mesh", "rt_world_triangles", "rt_renderer_kernel_triangles",
 ]
 
 _lib = None
@@ -162,6 +164,9 @@ def lib():
     L.rt_scene_add_sphere.argtypes = [C.c_void_p, vec3, C.c_float, C.c_int32, P(C.c_int32)]
     L.rt_scene_add_moving_sphere.argtypes = [C.c_void_p, vec3, vec3, C.c_float, C.c_int32, P(C.c_int32)]
     L.rt_scene_add_quad.argtypes = [C.c_void_p, vec3, vec3, vec3, C.c_int32, P(C.c_int32)]
+    L.rt_scene_add_triangle.argtypes = [C.c_void_p, vec3, vec3, vec3, C.c_int32, P(C.c_int32)]
+    L.rt_scene_add_mesh.argtypes = [C.c_void_p, C.c_uint32, f32p, C.c_uint32, u32p, C.c_int32, C.c_float, C.c_float, vec3, P(C.c_int32), P(C.c_uint32)]
+    L.rt_world_triangles.argtypes = [P(WorldFlat), P(C.c_uint32)]
     L.rt_scene_set_background.argtypes = [C.c_void_p, C.c_uint32, vec3]
     L.rt_scene_set_perlin.argtypes = [C.c_void_p, C.c_uint64]
     L.rt_scene_set_image.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
@@ -187,6 +192,7 @@ def lib():
     L.rt_renderer_last_kernel_ms.argtypes = [C.c_void_p, P(C.c_float)]
     L.rt_renderer_kernel_info.argtypes = [C.c_void_p, P(C.c_uint32 * 4)]
     L.rt_renderer_kernel_form.argtypes = [C.c_void_p, C.c_uint32 * 9]
+    L.rt_renderer_kernel_triangles.argtypes = [C.c_void_p, P(C.c_uint32)]
     L.rt_renderer_kernel_times.argtypes = [C.c_void_p, C.c_uint32, C.c_float * 3]
     L.rt_renderer_set_camera.argtypes = [C.c_void_p, P(Camera)]
     L.rt_multi_renderer_set_camera.argtypes = [C.c_void_p, P(Camera)]

@@ -54,6 +54,7 @@ constexpr uint32_t stream_key(bool exact, bool filter, int world, int ext = 0, b
 }
 constexpr uint32_t RT_KEY_XCHG = 1u << 9;
 constexpr uint32_t RT_KEY_NEE = 1u << 10;   // light sampling (rt_renderer_light_sampling_enable): the NEE form of an EXT >= 1 stack-walk or list key
+constexpr uint32_t RT_KEY_TRI = 1u << 11;   // the world has triangles: the TRI form of an EXT >= 1 stack-walk or list key, plain or NEE; not one of rt_renderer_kernel_form's fields
 // a stream key read back into render_kernel_stream's template arguments, in stream_key()'s order, then NEE: what rt_renderer_kernel_form reports
 static void stream_key_fields(uint32_t key, uint32_t out[8]) {
     out[0] = key & 1u; out[1] = key >> 1 & 1u; out[2] = key >> 2 & 3u; out[3] = key >> 4 & 3u;
@@ -67,13 +68,15 @@ static uint32_t stream_kernel_key(uint32_t variant, bool tol, const DeviceScene&
     const bool exact = variant != 3;   // of the BVH kernels; lists and node trees have no box-pair test to speed up
     const int ext = s.textured ? 2 : 1;
     // the distance-sorted queue / the 4-wide walk: one instantiation per feature level, records in global memory, 32-bit references
-    if (s.queue) return stream_key(true, false, RT_WORLD_BVH_QUEUE, s.textured || s.extended ? ext : 0, true, true);
+    if (s.queue) return stream_key(true, false, RT_WORLD_BVH_QUEUE, s.textured || s.extended ? ext : 0, true, true);   // (a lane walk reads a quad's kind from the flat record: no TRI form)
+    // triangles (§18): the TRI form of the list and stack-walk EXT families; a world with triangles has quads, so it is a list or a BVH and `extended`
+    const uint32_t tri = s.n_triangles ? RT_KEY_TRI : 0u;
     if (s.big) {   // records in global memory; lists and BVHs in the EXT forms only
-        if (s.dw.kind == RT_WORLD_LIST) return stream_key(true, false, RT_WORLD_LIST, ext, true, true);
+        if (s.dw.kind == RT_WORLD_LIST) return stream_key(true, false, RT_WORLD_LIST, ext, true, true) | tri;
         if (s.dw.kind == RT_WORLD_NODE_TREE) return stream_key(true, false, RT_WORLD_NODE_TREE, 0, true, true);
-        return stream_key(exact, false, RT_WORLD_BVH, ext, true, s.wide);
+        return stream_key(exact, false, RT_WORLD_BVH, ext, true, s.wide) | tri;
     }
-    if (s.extended) return s.dw.kind == RT_WORLD_LIST ? stream_key(true, false, RT_WORLD_LIST, ext) : stream_key(exact, false, RT_WORLD_BVH, ext);
+    if (s.extended) return (s.dw.kind == RT_WORLD_LIST ? stream_key(true, false, RT_WORLD_LIST, ext) : stream_key(exact, false, RT_WORLD_BVH, ext)) | tri;
     if (s.dw.kind != RT_WORLD_BVH) return stream_key(true, false, (int)s.dw.kind);
     if (tol) return stream_key(false, false, RT_WORLD_BVH, 0, false, false, true);
     return stream_key(variant == 2, variant == 4, RT_WORLD_BVH);
@@ -86,6 +89,10 @@ static const void* stream_kernel_for(uint32_t key) {
     case stream_key(exact, filter, world, ext, big, wide, tol): return reinterpret_cast<const void*>(&render_kernel_stream<exact, filter, RT_STREAM_BLOCK, world, ext, big, wide, tol>)
 #define RT_KERNEL_NEE(exact, world, ext, big, wide) \
     case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_NEE: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, true>)
+#define RT_KERNEL_TRI(exact, world, ext, big, wide) \
+    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, false, true>)
+#define RT_KERNEL_TRI_NEE(exact, world, ext, big, wide) \
+    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NEE: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, true, true>)
     switch (key) {   // arguments: exact, filter, world, ext, big, wide, tol
         case RT_KEY_XCHG: return reinterpret_cast<const void*>(&render_kernel_xchg<RT_XCHG_BLOCK>);
         RT_KERNEL(true, false, RT_WORLD_BVH_QUEUE, 2, true, true, false); RT_KERNEL(true, false, RT_WORLD_BVH_QUEUE, 1, true, true, false); RT_KERNEL(true, false, RT_WORLD_BVH_QUEUE, 0, true, true, false);
@@ -102,10 +109,23 @@ static const void* stream_kernel_for(uint32_t key) {
         RT_KERNEL_NEE(false, RT_WORLD_BVH, 2, true, false); RT_KERNEL_NEE(true, RT_WORLD_BVH, 2, true, false); RT_KERNEL_NEE(false, RT_WORLD_BVH, 1, true, false); RT_KERNEL_NEE(true, RT_WORLD_BVH, 1, true, false);
         RT_KERNEL_NEE(true, RT_WORLD_LIST, 2, false, false); RT_KERNEL_NEE(true, RT_WORLD_LIST, 1, false, false);
         RT_KERNEL_NEE(false, RT_WORLD_BVH, 2, false, false); RT_KERNEL_NEE(true, RT_WORLD_BVH, 2, false, false); RT_KERNEL_NEE(false, RT_WORLD_BVH, 1, false, false); RT_KERNEL_NEE(true, RT_WORLD_BVH, 1, false, false);
+        // triangles (§18): the same sixteen families once more, plain and with light sampling (arguments: exact, world, ext, big, wide)
+        RT_KERNEL_TRI(true, RT_WORLD_LIST, 2, true, true); RT_KERNEL_TRI(true, RT_WORLD_LIST, 1, true, true);
+        RT_KERNEL_TRI(false, RT_WORLD_BVH, 2, true, true); RT_KERNEL_TRI(true, RT_WORLD_BVH, 2, true, true); RT_KERNEL_TRI(false, RT_WORLD_BVH, 1, true, true); RT_KERNEL_TRI(true, RT_WORLD_BVH, 1, true, true);
+        RT_KERNEL_TRI(false, RT_WORLD_BVH, 2, true, false); RT_KERNEL_TRI(true, RT_WORLD_BVH, 2, true, false); RT_KERNEL_TRI(false, RT_WORLD_BVH, 1, true, false); RT_KERNEL_TRI(true, RT_WORLD_BVH, 1, true, false);
+        RT_KERNEL_TRI(true, RT_WORLD_LIST, 2, false, false); RT_KERNEL_TRI(true, RT_WORLD_LIST, 1, false, false);
+        RT_KERNEL_TRI(false, RT_WORLD_BVH, 2, false, false); RT_KERNEL_TRI(true, RT_WORLD_BVH, 2, false, false); RT_KERNEL_TRI(false, RT_WORLD_BVH, 1, false, false); RT_KERNEL_TRI(true, RT_WORLD_BVH, 1, false, false);
+        RT_KERNEL_TRI_NEE(true, RT_WORLD_LIST, 2, true, true); RT_KERNEL_TRI_NEE(true, RT_WORLD_LIST, 1, true, true);
+        RT_KERNEL_TRI_NEE(false, RT_WORLD_BVH, 2, true, true); RT_KERNEL_TRI_NEE(true, RT_WORLD_BVH, 2, true, true); RT_KERNEL_TRI_NEE(false, RT_WORLD_BVH, 1, true, true); RT_KERNEL_TRI_NEE(true, RT_WORLD_BVH, 1, true, true);
+        RT_KERNEL_TRI_NEE(false, RT_WORLD_BVH, 2, true, false); RT_KERNEL_TRI_NEE(true, RT_WORLD_BVH, 2, true, false); RT_KERNEL_TRI_NEE(false, RT_WORLD_BVH, 1, true, false); RT_KERNEL_TRI_NEE(true, RT_WORLD_BVH, 1, true, false);
+        RT_KERNEL_TRI_NEE(true, RT_WORLD_LIST, 2, false, false); RT_KERNEL_TRI_NEE(true, RT_WORLD_LIST, 1, false, false);
+        RT_KERNEL_TRI_NEE(false, RT_WORLD_BVH, 2, false, false); RT_KERNEL_TRI_NEE(true, RT_WORLD_BVH, 2, false, false); RT_KERNEL_TRI_NEE(false, RT_WORLD_BVH, 1, false, false); RT_KERNEL_TRI_NEE(true, RT_WORLD_BVH, 1, false, false);
         default: return nullptr;
     }
 #undef RT_KERNEL
 #undef RT_KERNEL_NEE
+#undef RT_KERNEL_TRI
+#undef RT_KERNEL_TRI_NEE
 }
 
 // the feature pass's kernel: the world's own traversal, so that a kernel carries one traversal stack
@@ -889,6 +909,13 @@ extern "C" int rt_renderer_kernel_form(rt_renderer* r, uint32_t out[9]) {
     if (key == RT_KEY_XCHG) { out[0] = RT_KERNEL_XCHG; return RT_OK; }
     out[0] = RT_KERNEL_STREAM;
     stream_key_fields(key, out + 1);
+    return RT_OK;
+}
+
+// Whether the NEXT launch runs an instantiation of the triangle family: a query of its own, so that rt_renderer_kernel_form's nine outputs stay what they are.
+extern "C" int rt_renderer_kernel_triangles(rt_renderer* r, uint32_t* out) {
+    if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_kernel_triangles: null argument");
+    *out = r->variant >= 2 && (stream_kernel_key(r->variant, r->tol, r->scene) & RT_KEY_TRI) ? 1u : 0u;
     return RT_OK;
 }
 

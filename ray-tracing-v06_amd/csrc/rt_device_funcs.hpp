@@ -123,7 +123,9 @@ RT_HD bool prim_closest_intersection(const rt_prim& p, int32_t idx, const Ray& r
 
 // quad::hit of "Ray Tracing: The Next Week" in the reference's conventions: t >= 0 accepted (no t_min: the origin is
 // offset instead, Renderer.cu:175), `t >= rec.distance` rejects; the stored normal faces AGAINST the ray (two-sided).
-RT_HD bool quad_closest_intersection(f3 Q, float D, f3 u, f3 v, f3 n, f3 w, uint32_t mat, int32_t unified, const Ray& ray, HitRec& rec) {
+// kind (rt_quad::kind): RT_QUAD_TRIANGLE is the book's `tri` — the same plane and coordinates, and alpha + beta > 1 rejects too (one fp32 add, rounded
+// on its own; a sum of exactly 1 is inside).
+RT_HD bool quad_closest_intersection(f3 Q, float D, f3 u, f3 v, f3 n, f3 w, uint32_t mat, int32_t unified, uint32_t kind, const Ray& ray, HitRec& rec) {
     float denom = dot(n, ray.d);
     if (fabsf(denom) < 1e-8f) return false;
     float t = (D - dot(n, ray.o)) / denom;
@@ -133,6 +135,7 @@ RT_HD bool quad_closest_intersection(f3 Q, float D, f3 u, f3 v, f3 n, f3 w, uint
     float alpha = dot(w, cross(planar, v));
     float beta = dot(w, cross(u, planar));
     if (!(alpha >= 0.0f && alpha <= 1.0f && beta >= 0.0f && beta <= 1.0f)) return false;
+    if (kind == RT_QUAD_TRIANGLE && !(alpha + beta <= 1.0f)) return false;
     rec.mat = mat;
     rec.distance = t;
     rec.prim = unified;
@@ -144,7 +147,7 @@ __device__ inline bool any_prim_closest_intersection(const DeviceWorld& w, int32
     if ((uint32_t)idx >= w.n_prims) {
         const rt_quad& q = w.quads[(uint32_t)idx - w.n_prims];
         return quad_closest_intersection(mk3(q.Q[0], q.Q[1], q.Q[2]), q.D, mk3(q.u[0], q.u[1], q.u[2]), mk3(q.v[0], q.v[1], q.v[2]),
-                                         mk3(q.normal[0], q.normal[1], q.normal[2]), mk3(q.w[0], q.w[1], q.w[2]), q.mat, idx, ray, rec);
+                                         mk3(q.normal[0], q.normal[1], q.normal[2]), mk3(q.w[0], q.w[1], q.w[2]), q.mat, idx, q.kind, ray, rec);
     }
     return prim_closest_intersection(w.prims[idx], idx, ray, rec, w.mats, rng);
 }

@@ -149,7 +149,8 @@ static Box prim_bounds(const rt_prim& p) {
 // ---------------------------------------------------------------------------------------------
 struct rt_scene {
     std::vector<rt_prim> prims;
-    std::vector<rt_quad> quads;
+    std::vector<rt_quad> quads;           // the parallelograms, then the n_tris triangles (rt_quad::kind), whatever the order of the calls
+    uint32_t n_tris = 0;
     uint32_t background = 0;
     float background_color[3] = {0.0f, 0.0f, 0.0f};
     uint32_t traversal = RT_TRAVERSAL_STACK;
@@ -222,7 +223,7 @@ static void quad_finalize(rt_quad& q) {
     st3(q.normal, normal);
     q.D = dot(normal, ld3(q.Q));
     st3(q.w, n / dot(n, n));
-    q.pad0 = q.pad1 = q.pad2 = 0.0f;
+    q.pad1 = q.pad2 = 0.0f;
 }
 static Box box_of_points(f3 a, f3 b) { return Box{glm_min(a, b), glm_max(a, b)}; }
 // bbox = box(Q, Q+u+v) U box(Q+u, Q+v), every axis padded to at least 0.0001 (the book's aabb::pad_to_minimums)
@@ -235,6 +236,17 @@ static Box quad_bounds(const rt_quad& q) {
     if (b.mx.z - b.mn.z < delta) { b.mn.z -= delta / 2; b.mx.z += delta / 2; }
     return b;
 }
+// a triangle (rt_quad::kind == RT_QUAD_TRIANGLE): the box of its vertices Q, Q + u, Q + v, padded like a quad's
+static Box tri_bounds(const rt_quad& q) {
+    f3 Q = ld3(q.Q), u = ld3(q.u), v = ld3(q.v);
+    Box b = box_union(box_of_points(Q, Q + u), box_of_points(Q + v, Q + v));
+    const float delta = 0.0001f;
+    if (b.mx.x - b.mn.x < delta) { b.mn.x -= delta / 2; b.mx.x += delta / 2; }
+    if (b.mx.y - b.mn.y < delta) { b.mn.y -= delta / 2; b.mx.y += delta / 2; }
+    if (b.mx.z - b.mn.z < delta) { b.mn.z -= delta / 2; b.mx.z += delta / 2; }
+    return b;
+}
+static Box quad_record_bounds(const rt_quad& q) { return q.kind == RT_QUAD_TRIANGLE ? tri_bounds(q) : quad_bounds(q); }
 extern "C" int rt_scene_add_quad(rt_scene* s, const float Q[3], const float u[3], const float v[3], int32_t mat, int32_t* out_quad) {
     if (!s || !Q || !u || !v) return rt_fail(RT_ERR_INVALID, "rt_scene_add_quad: null argument");
     if (mat < 0 || (size_t)mat >= s->mats.size()) return rt_fail(RT_ERR_INVALID, "rt_scene_add_quad: material index %d out of range", mat);
@@ -243,7 +255,34 @@ extern "C" int rt_scene_add_quad(rt_scene* s, const float Q[3], const float u[3]
     st3(q.Q, ld3(Q)); st3(q.u, ld3(u)); st3(q.v, ld3(v));
     q.mat = (uint32_t)mat;
     quad_finalize(q);
+    const size_t at = s->quads.size() - s->n_tris;   // in front of the triangles
+    s->quads.insert(s->quads.begin() + at, q);
+    s->world_set = false;
+    if (out_quad) *out_quad = (int32_t)at;
+    return RT_OK;
+}
+
+// ---- triangles and meshes (not in the reference; the `tri` of "Ray Tracing: The Next Week": a quad with another interior test) ----
+// the record of triangle (a, b, c), or false for a degenerate face: dot(n, n) of n = cross(b - a, c - a) not finite and > 0
+static bool tri_record(f3 a, f3 b, f3 c, uint32_t mat, rt_quad& q) {
+    std::memset(&q, 0, sizeof(q));
+    st3(q.Q, a); st3(q.u, b - a); st3(q.v, c - a);
+    q.mat = mat;
+    q.kind = RT_QUAD_TRIANGLE;
+    const f3 n = cross(ld3(q.u), ld3(q.v));
+    const float nn = dot(n, n);
+    if (!(std::isfinite(nn) && nn > 0.0f)) return false;
+    quad_finalize(q);
+    return true;
+}
+extern "C" int rt_scene_add_triangle(rt_scene* s, const float a[3], const float b[3], const float c[3], int32_t mat, int32_t* out_quad) {
+    if (!s || !a || !b || !c) return rt_fail(RT_ERR_INVALID, "rt_scene_add_triangle: null argument");
+    if (mat < 0 || (size_t)mat >= s->mats.size()) return rt_fail(RT_ERR_INVALID, "rt_scene_add_triangle: material index %d out of range", mat);
+    rt_quad q;
+    if (!tri_record(ld3(a), ld3(b), ld3(c), (uint32_t)mat, q))
+        return rt_fail(RT_ERR_INVALID, "rt_scene_add_triangle: degenerate triangle (the squared length of cross(b - a, c - a) is not finite and > 0)");
     s->quads.push_back(q);
+    s->n_tris++;
     s->world_set = false;
     if (out_quad) *out_quad = (int32_t)s->quads.size() - 1;
     return RT_OK;
@@ -384,18 +423,21 @@ static int build_bvh(rt_scene* s, int builder) {
     Builder B(s->nodes);
     B.arr.reserve(s->prims.size() + s->quads.size());
     for (const rt_prim& p : s->prims) B.arr.push_back(Item{prim_bounds(p), false, p, rt_quad{}});
-    for (const rt_quad& q : s->quads) B.arr.push_back(Item{quad_bounds(q), true, rt_prim{}, q});
+    for (const rt_quad& q : s->quads) B.arr.push_back(Item{quad_record_bounds(q), true, rt_prim{}, q});
     int32_t root;
     if (builder == 0) root = B.rec1(0, (int)B.arr.size());
     else if (builder == 1) root = B.rec2(0, (int)B.arr.size());
     else root = B.bottom_up();
-    // hittables[] = arr order (BVH.cu:174-177), kept per kind: spheres first, then quads; leaf indices are remapped
+    // hittables[] = arr order (BVH.cu:174-177), kept per kind: spheres first, then quads, then triangles; leaf indices are remapped
     {
         std::vector<int32_t> unified(B.arr.size());
         const size_t ns = s->prims.size();
-        size_t si = 0, qi = 0;
+        size_t si = 0, qi = 0, ti = s->quads.size() - s->n_tris;
         for (size_t i = 0; i < B.arr.size(); i++) {
-            if (B.arr[i].is_quad) { s->quads[qi] = B.arr[i].q; unified[i] = (int32_t)(ns + qi); qi++; }
+            if (B.arr[i].is_quad) {
+                size_t& at = B.arr[i].q.kind == RT_QUAD_TRIANGLE ? ti : qi;
+                s->quads[at] = B.arr[i].q; unified[i] = (int32_t)(ns + at); at++;
+            }
             else { s->prims[si] = B.arr[i].p; unified[i] = (int32_t)si; si++; }
         }
         for (rt_bvh_node& n : s->nodes)
@@ -424,7 +466,7 @@ extern "C" int rt_scene_set_world_list(rt_scene* s) {
     s->max_stack = 0;
     Box b = box_empty();
     for (const rt_prim& p : s->prims) b = box_union(b, prim_bounds(p));  // world_bounds += handle.getBounds(), Scenes.cu:61
-    for (const rt_quad& q : s->quads) b = box_union(b, quad_bounds(q));
+    for (const rt_quad& q : s->quads) b = box_union(b, quad_record_bounds(q));
     s->bounds = b;
     s->world_set = true;
     return RT_OK;
@@ -503,6 +545,22 @@ extern "C" int rt_scene_get_flat(const rt_scene* s, rt_world_flat* out) {
 // with_spheres, the static spheres with radius > 0 whose material is a diffuse light, in primitive order, area = (12.566371f * r) * r.  `none` and `many`
 // are the caller's words for an empty list and for one past RT_MAX_LIGHTS.  out_kind may be null.
 static_assert(RT_MAX_LIGHTS == 16, "the refusal messages below say 16");
+// The kinds of a flat world's quads: parallelograms, then triangles.  Every consumer of a caller's rt_world_flat runs this on the host
+// before a kernel turns "quad index >= count of parallelograms" into "triangle".
+extern "C" int rt_world_triangles(const rt_world_flat* w, uint32_t* out_n) {
+    if (!w || !out_n) return rt_fail(RT_ERR_INVALID, "rt_world_triangles: null argument");
+    *out_n = 0;
+    if (w->n_quads && !w->quads) return rt_fail(RT_ERR_INVALID, "rt_world_triangles: world array is null");
+    uint32_t n = 0;
+    for (uint32_t i = 0; i < w->n_quads; i++) {
+        const uint32_t kind = w->quads[i].kind;
+        if (kind > RT_QUAD_TRIANGLE) return rt_fail(RT_ERR_INVALID, "quad %u: unknown kind %u (RT_QUAD_PARALLELOGRAM 0, RT_QUAD_TRIANGLE 1)", i, kind);
+        if (kind == RT_QUAD_TRIANGLE) n++;
+        else if (n) return rt_fail(RT_ERR_INVALID, "quad %u: a parallelogram behind a triangle (the triangles follow the parallelograms in a flat world)", i);
+    }
+    *out_n = n;
+    return RT_OK;
+}
 static int world_lights(const rt_world_flat* w, bool with_spheres, const char* none, const char* many, uint32_t* out_kind, uint32_t* out_index, float* out_area,
                         uint32_t* out_n) {
     if (w->traversal != RT_TRAVERSAL_STACK)
@@ -510,11 +568,12 @@ static int world_lights(const rt_world_flat* w, bool with_spheres, const char* n
     for (uint32_t i = 0; i < w->n_materials; i++)
         if (w->materials[i].type == RT_MAT_ISOTROPIC)
             return rt_fail(RT_ERR_INVALID, "light sampling: the world has a constant medium (RT_MAT_ISOTROPIC), whose hit test draws from the path's RNG stream");
-    uint32_t n = 0;
+    uint32_t n = 0, n_tris = 0;
+    if (int rc = rt_world_triangles(w, &n_tris)) return rc;
     for (uint32_t i = 0; i < w->n_quads; i++) {
         const rt_quad& q = w->quads[i];
         if (q.mat >= w->n_materials) return rt_fail(RT_ERR_INVALID, "quad %u: material index out of range", i);
-        if (w->materials[q.mat].type != RT_MAT_DIFFUSE_LIGHT) continue;
+        if (w->materials[q.mat].type != RT_MAT_DIFFUSE_LIGHT || q.kind == RT_QUAD_TRIANGLE) continue;   // a triangle light emits when hit and is not sampled (§18)
         if (n == RT_MAX_LIGHTS) return rt_fail(RT_ERR_INVALID, "%s", many);
         const f3 nrm = cross(mk3(q.u[0], q.u[1], q.u[2]), mk3(q.v[0], q.v[1], q.v[2]));
         if (out_kind) out_kind[n] = RT_LIGHT_QUAD;
@@ -701,8 +760,35 @@ extern "C" int rt_scene_add_box(rt_scene* s, const float a[3], const float b[3],
                                 const float translate[3], int32_t* out_first_quad) {
     if (!s || !a || !b) return rt_fail(RT_ERR_INVALID, "rt_scene_add_box: null argument");
     if (mat < 0 || (size_t)mat >= s->mats.size()) return rt_fail(RT_ERR_INVALID, "rt_scene_add_box: material %d out of range", mat);
-    if (out_first_quad) *out_first_quad = (int32_t)s->quads.size();
+    if (out_first_quad) *out_first_quad = (int32_t)(s->quads.size() - s->n_tris);
     cornell_box(s, ld3(a), ld3(b), rotate_y_degrees, translate ? ld3(translate) : mk3(0.0f), mat);
+    return RT_OK;
+}
+
+// An indexed mesh as triangles: every vertex p -> rot_y(p * scale) + translate (cornell_box's order and arithmetic), then tri_record per face.
+extern "C" int rt_scene_add_mesh(rt_scene* s, uint32_t n_vertices, const float* xyz, uint32_t n_triangles, const uint32_t* indices, int32_t mat, float scale,
+                                 float rotate_y_degrees, const float translate[3], int32_t* out_first, uint32_t* out_added) {
+    if (!s || (n_vertices && !xyz) || (n_triangles && !indices)) return rt_fail(RT_ERR_INVALID, "rt_scene_add_mesh: null argument");
+    if (mat < 0 || (size_t)mat >= s->mats.size()) return rt_fail(RT_ERR_INVALID, "rt_scene_add_mesh: material %d out of range", mat);
+    if (!std::isfinite(scale) || !std::isfinite(rotate_y_degrees)) return rt_fail(RT_ERR_INVALID, "rt_scene_add_mesh: scale and rotation must be finite");
+    for (size_t i = 0; i < (size_t)n_triangles * 3u; i++)
+        if (indices[i] >= n_vertices)
+            return rt_fail(RT_ERR_INVALID, "rt_scene_add_mesh: face %zu: vertex index %u out of range (%u vertices)", i / 3u, indices[i], n_vertices);
+    const float rad = radians(rotate_y_degrees), c = cosf(rad), sn = sinf(rad);
+    const f3 offset = translate ? ld3(translate) : mk3(0.0f);
+    std::vector<f3> pts(n_vertices);
+    for (uint32_t i = 0; i < n_vertices; i++) pts[i] = rot_y(ld3(xyz + 3 * (size_t)i) * scale, c, sn) + offset;
+    std::vector<rt_quad> tris;
+    tris.reserve(n_triangles);
+    for (uint32_t f = 0; f < n_triangles; f++) {
+        rt_quad q;
+        if (tri_record(pts[indices[3 * (size_t)f]], pts[indices[3 * (size_t)f + 1]], pts[indices[3 * (size_t)f + 2]], (uint32_t)mat, q)) tris.push_back(q);
+    }
+    if (out_first) *out_first = (int32_t)s->quads.size();
+    if (out_added) *out_added = (uint32_t)tris.size();
+    s->quads.insert(s->quads.end(), tris.begin(), tris.end());
+    s->n_tris += (uint32_t)tris.size();
+    if (!tris.empty()) s->world_set = false;
     return RT_OK;
 }
 

@@ -61,7 +61,10 @@ struct PackedSceneRef {
     uint32_t root_ref;
     float root_min[3], root_max[3];
     uint32_t stack_cap;      // entries per lane
-    uint32_t n_inner, n_codes, n_prims, n_quads;
+    uint32_t n_inner;
+    uint32_t n_plain_quads;  // quads below this index are parallelograms, the others triangles (rt_quad::kind; the trace record has no free dword).  It took the
+                             // place of a leaf-code count that nothing read, so the kernel arguments of the EXT == 0 instantiations are what they were
+    uint32_t n_prims, n_quads;
     uint32_t n_top;          // BIG: the first n_top wide nodes (breadth-first order = the top of the tree) are staged in the LDS
     const rt_material* mats; // full 32-B records in global memory (second colour of a checker material)
     const rt_perlin* perlin; // EXT: noise tables / image of the two textured materials (global memory), or null

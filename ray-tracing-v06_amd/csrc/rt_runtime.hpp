@@ -106,6 +106,7 @@ struct DeviceScene {
     bool big = false;            // packed for the global-memory kernel (the image does not fit the LDS): 64-byte nodes, breadth-first
     bool wide = false;           // ... with 32-bit references (2^14 inner nodes / 2^15 leaf codes or more); otherwise 16-bit like the LDS image
     bool any_moving = false;     // a MovingSphere is in the world: the leaf phase reads the second centres
+    uint32_t n_triangles = 0;    // how many of the world's quads are triangles: its last ones (rt_world_triangles)
     bool queue = false;          // RT_TRAVERSAL_QUEUE (BVH.cu:17-49's distance-sorted walk) or RT_TRAVERSAL_WIDE4: every lane walks its whole trace on its own
                                  // (the streaming kernel's RT_WORLD_BVH_QUEUE mode, records in global memory)
 
@@ -226,7 +227,7 @@ struct DeviceScene {
         packed.background = w->background;
         for (int k = 0; k < 3; k++) packed.background_color[k] = w->background_color[k];
         packed.n_inner = n_inner;
-        packed.n_codes = sphere_codes + w->n_quads;
+        packed.n_plain_quads = w->n_quads - n_triangles;
         packed.n_prims = w->n_prims;
         packed.n_quads = w->n_quads;
         packed.stack_cap = (true_stack ? true_stack : 1u) + 1u;  // + the sentinel entry at the bottom (RT_POP)
@@ -245,6 +246,7 @@ struct DeviceScene {
             return rt_fail(RT_ERR_INVALID, "traversal mode %u: the distance-sorted queue and the 4-wide walk belong to RT_WORLD_BVH worlds", w->traversal);
         if (w->n_quads && w->kind == RT_WORLD_NODE_TREE) return rt_fail(RT_ERR_INVALID, "bvh_node trees take spheres only");
         const uint32_t n_all = w->n_prims + w->n_quads;
+        if (int rc = rt_world_triangles(w, &n_triangles)) return rc;   // kinds, and that the triangles follow the parallelograms: the kernels tell them apart by index
         if (w->n_materials == 0 || !w->materials) return rt_fail(RT_ERR_INVALID, "world has no materials");
         if (w->kind != RT_WORLD_LIST && (w->n_nodes == 0 || !w->nodes)) return rt_fail(RT_ERR_INVALID, "BVH world has no nodes");
         if (w->max_stack > RT_MAX_STACK) return rt_fail(RT_ERR_STACK, "world needs a %u-entry traversal stack; limit %d", w->max_stack, RT_MAX_STACK);

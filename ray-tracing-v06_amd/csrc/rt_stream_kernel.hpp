@@ -206,13 +206,17 @@ __device__ __forceinline__ WideNodeData fetch_wide_node(const char* nodes, const
 //      the per-lane stacks and leaves that much more of the LDS for the top of the tree.
 // TOL (variant 6, opt-in): the hot loop's plane parameters are (b - o) * RN(1/d) instead of the exact quotients — inside north_star's |delta| < 1e-3,
 //      not bit-exact by construction (rt_fastdiv.hpp: slab_near_far_tolerant).  LDS-resident RT_WORLD_BVH worlds of the reference's feature set (EXT == 0) only.
+// TRI: the world has triangles — quads at or past p.scene.n_plain_quads take the book's `tri` interior test in the leaf phase.  A family of its own:
+//      measured in one instantiation with the quads, the extra compare and add cost the Cornell box 1.0 % (EXPERIMENTS.md E9), so worlds without triangles keep
+//      the kernels they had, instruction for instruction.
 // NEE (rt_renderer_light_sampling_enable, opt-in; EXT >= 1 only): a Lambertian / checker hit draws its next direction from the mixture of its own cosine
 //      distribution and a distribution over the world's lights, and weighs the path by the ratio of the densities.  The light table —
 //      a header (n_l, -, -, -), then (index, area, kind, -) per light, then — only where a kind says sphere — (Cx, Cy, Cz, r) per light — lies behind the
 //      quads' shade records in the image the NEE launches are given, so it costs no kernel argument: the other instantiations neither see it nor pay for it.
-template <bool EXACT, bool FILTER, int BLOCK, int WORLD = RT_WORLD_BVH, int EXT = 0, bool BIG = false, bool WIDE = BIG, bool TOL = false, bool NEE = false>
+template <bool EXACT, bool FILTER, int BLOCK, int WORLD = RT_WORLD_BVH, int EXT = 0, bool BIG = false, bool WIDE = BIG, bool TOL = false, bool NEE = false, bool TRI = false>
 __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(StreamParams p) {
     static_assert(!NEE || (EXT >= 1 && WORLD != RT_WORLD_BVH_QUEUE), "light sampling: worlds with quads, walked by the stack or as a list");
+    static_assert(!TRI || (EXT >= 1 && WORLD != RT_WORLD_BVH_QUEUE), "triangles: worlds with quads; a lane walk reads the kind from the flat record");
     extern __shared__ uint4 lds[];
     const uint32_t tid = threadIdx.x;
     const uint32_t lane = tid & 63u;
@@ -474,8 +478,10 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                         asm volatile("" : : "v"(a0.x), "v"(a0.w));
                         HitRec tmp;
                         tmp.distance = rec_t; tmp.normal = mk3(0.0f); tmp.prim = -1; tmp.mat = 0;
+                        // the triangles follow the parallelograms (§18): the quad's index says which interior test it takes
+                        const uint32_t quad_kind = TRI && (code - first_quad) >= p.scene.n_plain_quads ? RT_QUAD_TRIANGLE : RT_QUAD_PARALLELOGRAM;
                         if (quad_closest_intersection(mk3(a0.x, a0.y, a0.z), a0.w, mk3(a1.x, a1.y, a1.z), mk3(a1.w, a2.x, a2.y),
-                                                      mk3(a2.z, a2.w, a3.x), mk3(a3.y, a3.z, a3.w), 0u, 0, ray, tmp)) {
+                                                      mk3(a2.z, a2.w, a3.x), mk3(a3.y, a3.z, a3.w), 0u, 0, quad_kind, ray, tmp)) {
                             rec_t = tmp.distance;
                             rec_code = (int32_t)(code - first_quad + p.scene.sphere_codes);   // the shade phase's code space
                         }
@@ -683,7 +689,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                                 const f3 ln = mk3(a2.z, a2.w, a3.x);
                                 HitRec tmp;
                                 tmp.distance = RT_MISS_DIST; tmp.normal = mk3(0.0f); tmp.prim = -1; tmp.mat = 0;
-                                if (quad_closest_intersection(mk3(a0.x, a0.y, a0.z), a0.w, mk3(a1.x, a1.y, a1.z), mk3(a1.w, a2.x, a2.y), ln, mk3(a3.y, a3.z, a3.w), 0u, 0, lray, tmp))
+                                if (quad_closest_intersection(mk3(a0.x, a0.y, a0.z), a0.w, mk3(a1.x, a1.y, a1.z), mk3(a1.w, a2.x, a2.y), ln, mk3(a3.y, a3.z, a3.w), 0u, 0, RT_QUAD_PARALLELOGRAM, lray, tmp))   // a light of the table is never a triangle
                                     pl_j = ((tmp.distance * tmp.distance) * len2) / ((fabsf(dot(d, ln)) / len) * lt.y);
                                 }
                                 pdf_light = pdf_light + pl_j;

@@ -1,0 +1,86 @@
+"""Triangle meshes for Scene.MakeMesh: a Wavefront OBJ reader and two generators, so that demos, tests and measurements need no file.
+
+Every function returns (vertices float32 (n, 3), faces uint32 (m, 3)).  Normals and texture coordinates of a file are ignored: the renderer's
+triangles are flat-shaded and take their texture coordinates from their own plane.
+"""
+import numpy as np
+
+
+def _obj_index(token, n_vertices, where):
+    """the vertex index of an `i`, `i/j`, `i/j/k` or `i//k` token: 1-based, or negative = counted back from the vertices read so far"""
+    try:
+        i = int(token.split("/")[0])
+    except ValueError:
+        raise ValueError(f"{where}: bad face index {token!r}") from None
+    k = i - 1 if i > 0 else n_vertices + i
+    if i == 0 or not 0 <= k < n_vertices:
+        raise ValueError(f"{where}: face index {token!r} out of range ({n_vertices} vertices so far)")
+    return k
+
+
+def load_obj(path):
+    """`v x y z` and `f a b c ...` lines of a Wavefront OBJ file; a polygon of more than three corners is cut into a fan around its first corner;
+    every other line (vn, vt, g, o, s, usemtl, mtllib, comments) is ignored."""
+    vertices, faces = [], []
+    with open(path, "r", encoding="utf-8", errors="replace") as f:
+        for lineno, line in enumerate(f, 1):
+            parts = line.split("#", 1)[0].split()
+            if not parts:
+                continue
+            where = f"{path}:{lineno}"
+            if parts[0] == "v":
+                if len(parts) < 4:
+                    raise ValueError(f"{where}: a vertex needs three coordinates")
+                vertices.append([float(parts[1]), float(parts[2]), float(parts[3])])
+            elif parts[0] == "f":
+                if len(parts) < 4:
+                    raise ValueError(f"{where}: a face needs at least three corners")
+                corners = [_obj_index(t, len(vertices), where) for t in parts[1:]]
+                for k in range(1, len(corners) - 1):
+                    faces.append([corners[0], corners[k], corners[k + 1]])
+    return np.array(vertices, np.float32).reshape(-1, 3), np.array(faces, np.uint32).reshape(-1, 3)
+
+
+def tetrahedron():
+    """a regular tetrahedron inscribed in the unit sphere, faces counter-clockwise seen from outside"""
+    v = np.array([[1, 1, 1], [1, -1, -1], [-1, 1, -1], [-1, -1, 1]], np.float64) / np.sqrt(3.0)
+    f = np.array([[0, 1, 2], [0, 3, 1], [0, 2, 3], [1, 3, 2]], np.uint32)
+    return v.astype(np.float32), f
+
+
+def icosphere(level):
+    """an icosahedron subdivided `level` times (every triangle into four, new vertices pushed out to the unit sphere): 20 * 4**level faces,
+    10 * 4**level + 2 vertices, closed — every edge belongs to exactly two faces"""
+    if not 0 <= int(level) <= 7:
+        raise ValueError("icosphere: level must be 0..7")
+    t = (1.0 + np.sqrt(5.0)) / 2.0
+    v = [[-1, t, 0], [1, t, 0], [-1, -t, 0], [1, -t, 0], [0, -1, t], [0, 1, t], [0, -1, -t], [0, 1, -t], [t, 0, -1], [t, 0, 1], [-t, 0, -1], [-t, 0, 1]]
+    v = [list(np.array(p, np.float64) / np.linalg.norm(p)) for p in v]
+    f = [[0, 11, 5], [0, 5, 1], [0, 1, 7], [0, 7, 10], [0, 10, 11], [1, 5, 9], [5, 11, 4], [11, 10, 2], [10, 7, 6], [7, 1, 8],
+         [3, 9, 4], [3, 4, 2], [3, 2, 6], [3, 6, 8], [3, 8, 9], [4, 9, 5], [2, 4, 11], [6, 2, 10], [8, 6, 7], [9, 8, 1]]
+    for _ in range(int(level)):
+        mid = {}
+
+        def midpoint(a, b):
+            key = (a, b) if a < b else (b, a)
+            if key not in mid:
+                m = (np.array(v[a]) + np.array(v[b])) * 0.5
+                v.append(list(m / np.linalg.norm(m)))
+                mid[key] = len(v) - 1
+            return mid[key]
+
+        nf = []
+        for a, b, c in f:
+            ab, bc, ca = midpoint(a, b), midpoint(b, c), midpoint(c, a)
+            nf += [[a, ab, ca], [b, bc, ab], [c, ca, bc], [ab, bc, ca]]
+        f = nf
+    return np.array(v, np.float32), np.array(f, np.uint32)
+
+
+def from_spec(spec):
+    """`icosphere:LEVEL`, `tetrahedron`, or the path of an OBJ file (tools/render.py --mesh)"""
+    if spec.startswith("icosphere:"):
+        return icosphere(int(spec.split(":", 1)[1]))
+    if spec == "tetrahedron":
+        return tetrahedron()
+    return load_obj(spec)

@@ -1,0 +1,273 @@
+"""Triangles on the GPU: rt_probe_trace on crafted rays and every kernel form a world with triangles can resolve to, against the numpy twin
+(tests/_tri_twin.py, pinned to the oracle on worlds without triangles by tests/test_triangles_cpu.py), bit for bit."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import _tri_twin as TT
+import _tri_worlds as TW
+from _common import ROOT, as_oracle_camera, as_oracle_world, bits_equal, mismatch_report, pkg
+
+pytestmark = pytest.mark.gpu
+F = np.float32
+
+
+@pytest.fixture(scope="module")
+def p():
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    return pkg()
+
+
+def unit_world(p, triangle, as_list, second=False):
+    """the unit triangle (0,0,0), (1,0,0), (0,1,0) or the quad of the same Q, u, v; second: plus the coplanar triangle across the diagonal"""
+    s = p.Scene()
+    m = s.Lambertian((0.5, 0.5, 0.5))
+    if triangle:
+        s.MakeTriangle((0, 0, 0), (1, 0, 0), (0, 1, 0), m)
+        if second:
+            s.MakeTriangle((1, 1, 0), (0, 1, 0), (1, 0, 0), m)
+    else:
+        s.MakeQuad((0, 0, 0), (1, 0, 0), (0, 1, 0), m)
+    s.MakeSphere((0.5, 0.5, -10), 3.0, m)   # behind the plane; widens a list's bounds, so that the rays at the vertices and on the edges get past them to the interior test
+    s.MakeHittableList() if as_list else s.BuildBVH_TopDown()
+    return s
+
+
+def down_z(points):
+    rays = np.zeros((len(points), 7), F)
+    rays[:, 0:2] = np.array(points, F)
+    rays[:, 2], rays[:, 5] = 1, -1
+    return rays
+
+
+EPS = F(2.0 ** -23)
+CRAFTED = [(0.25, 0.25), (0.5, 0.5), (0.5, F(0.5) + EPS), (0.75, 0.75), (0, 0), (1, 0), (0, 1), (0.5, 0), (0, 0.5), (-0.25, 0.5), (0.5, -0.25), (1.25, 0.1)]
+
+
+def crafted_rays():
+    rays = down_z(CRAFTED)
+    in_plane = np.array([[-1, 0.25, 0, 1, 0, 0, 0], [-1, 0.25, 0, 1, 0, 1e-9, 0]], F)   # |denom| < 1e-8: rejected whatever it would meet
+    return np.concatenate([rays, in_plane])
+
+
+@pytest.mark.parametrize("as_list", [False, True], ids=["bvh", "list"])
+def test_crafted_rays_meet_the_triangle_as_the_twin_says_and_the_quad_as_ever(p, as_list):
+    rays = crafted_rays()
+    tri, quad = unit_world(p, True, as_list), unit_world(p, False, as_list)
+    got_t = p.api.probe_trace(tri.getWorldPtr(), rays)
+    got_q = p.api.probe_trace(quad.getWorldPtr(), rays)
+    exp_t = TT.closest_intersection(as_oracle_world(tri.getWorldPtr()), rays)
+    exp_q = TT.closest_intersection(as_oracle_world(quad.getWorldPtr()), rays)
+    for got, exp in ((got_t, exp_t), (got_q, exp_q)):
+        for g, e in zip(got, exp):
+            assert bits_equal(np.asarray(g, F), np.asarray(e, F)), mismatch_report(np.asarray(g, F), np.asarray(e, F))
+    prim_t, prim_q = np.asarray(got_t[2]), np.asarray(got_q[2])   # primitive 0 is the sphere behind the plane, 1 the triangle / the quad
+    # inside; alpha + beta exactly 1: inside; one ulp more: outside; (0.75, 0.75) hits the quad and misses the triangle — the kind, carried all the way
+    assert prim_t[:4].tolist() == [1, 1, 0, 0] and prim_q[:4].tolist() == [1, 1, 1, 1]
+    if as_list:   # past the list's bounds every vertex and edge midpoint reaches the interior test and is inside; a BVH leaf's box ends where the triangle ends,
+        assert prim_t[4:9].tolist() == [1, 1, 1, 1, 1]   # and aabb::intersects' 0 / 0 on a face decides there (the twin says which way, above)
+    assert (prim_t[9:] != 1).all() and (prim_q[9:] != 1).all()   # outside, and in the plane (|denom| < 1e-8)
+
+
+@pytest.mark.parametrize("as_list", [False, True], ids=["bvh", "list"])
+def test_a_hit_at_exactly_the_distance_already_recorded_is_rejected(p, as_list):
+    """`t >= rec.distance` with equality, which rt_probe_trace (no preset argument) reaches through what was visited before: a quad and two triangles in one
+    plane, the second triangle a copy of the first.  Down z every one of them gives t = 1 exactly; whichever is visited first keeps the record — in a list
+    that is the quad, which precedes every triangle; in a tree the twin says which — and each later one meets rec.distance == t and is rejected."""
+    s = p.Scene()
+    m = s.Lambertian((0.5, 0.5, 0.5))
+    s.MakeSphere((0.5, 0.5, -10), 3.0, m)
+    s.MakeTriangle((0, 0, 0), (1, 0, 0), (0, 1, 0), m)
+    s.MakeTriangle((0, 0, 0), (1, 0, 0), (0, 1, 0), m)
+    s.MakeQuad((0, 0, 0), (1, 0, 0), (0, 1, 0), m)
+    s.MakeHittableList() if as_list else s.BuildBVH_TopDown()
+    rays = down_z([(0.25, 0.25), (0.125, 0.5), (0.75, 0.75)])
+    got = p.api.probe_trace(s.getWorldPtr(), rays)
+    exp = TT.closest_intersection(as_oracle_world(s.getWorldPtr()), rays)
+    for g, e in zip(got, exp):
+        assert bits_equal(np.asarray(g, F), np.asarray(e, F))
+    assert np.asarray(got[1]).tolist() == [1.0, 1.0, 1.0] and np.asarray(got[2])[2] == 1   # (0.75, 0.75): the quad (primitive 1) alone
+    if as_list:
+        assert np.asarray(got[2]).tolist() == [1, 1, 1]   # the quad was there first; both triangles found rec.distance == t
+    else:
+        assert set(np.asarray(got[2])[:2].tolist()) <= {1, 2, 3}
+
+
+@pytest.mark.parametrize("n", [0, 1, 127, 128, 129])
+def test_probe_shapes(p, n):
+    rng = np.random.default_rng(n)
+    scene = TW.tri_room(p)
+    rays = np.zeros((n, 7), F)
+    rays[:, 0:3] = (rng.random((n, 3), dtype=F) * 8 + 1)
+    rays[:, 3:6] = rng.standard_normal((n, 3)).astype(F)
+    got = p.api.probe_trace(scene.getWorldPtr(), rays)
+    exp = TT.closest_intersection(as_oracle_world(scene.getWorldPtr()), rays) if n else (np.zeros(0, np.int32), np.zeros(0, F), np.zeros(0, np.int32), np.zeros((0, 3), F))
+    for g, e in zip(got, exp):
+        assert bits_equal(np.asarray(g, F), np.asarray(e, F))
+    if n >= 127:
+        prim = np.asarray(got[2])
+        assert (prim >= scene.getWorldPtr().n_prims + 7).any()   # some rays end on a triangle
+
+
+@pytest.mark.parametrize("as_list", [False, True], ids=["bvh", "list"])
+def test_two_coplanar_triangles_hit_on_their_shared_diagonal_the_first_visited_wins(p, as_list):
+    s = unit_world(p, True, as_list, second=True)
+    rays = down_z([(0.5, 0.5), (0.25, 0.75), (0.75, 0.25), (0.25, 0.25), (0.75, 0.75)])
+    got = p.api.probe_trace(s.getWorldPtr(), rays)
+    exp = TT.closest_intersection(as_oracle_world(s.getWorldPtr()), rays)
+    for g, e in zip(got, exp):
+        assert bits_equal(np.asarray(g, F), np.asarray(e, F))
+    assert np.asarray(got[2]).tolist() == [1, 1, 1, 1, 2]   # every point of the diagonal is inside both (alpha + beta == 1 in each frame): the first keeps it
+
+
+def _form(exact, world, big=0, wide=0, nee=0):
+    return {"kernel": "stream", "exact": exact, "filter": 0, "world": world, "ext": 1, "big": big, "wide": wide, "tol": 0, "nee": nee}
+
+
+BIG, WIDE = TW.NARROW, TW.WIDE
+
+
+@pytest.mark.parametrize("mode", [0, 2], ids=["plain", "nee"])
+@pytest.mark.parametrize("form", list(TW.FORMS), ids=[TW.form_id(f) for f in TW.FORMS])
+def test_every_triangle_instantiation_renders_its_room_as_the_twin_does(p, monkeypatch, form, mode):
+    """All 16 RT_KERNEL_TRI and all 16 RT_KERNEL_TRI_NEE keys of stream_kernel_for() (tests/_tri_worlds.FORMS, held against the source without a GPU), each
+    identified through kernel_form() and kernel_triangles(): frame and refinement sums against the twin, two passes, uneven steps.  With light sampling
+    (mode 2) the room has a quad light and a sphere lamp.  An EXT = 2 room holds an image-textured triangle: the twin follows every other pixel."""
+    world, exact, ext, big, wide = form
+    variant, env = TW.FORMS[form]
+    room = {"as_list": world == TW.LIST, "lamp": True, "textured": ext == 2}
+    run = TW.run(mode=mode, **room)
+    keep = run.pixel_followed
+    assert run.followed if ext == 1 else 0.8 < keep.mean() < 1.0
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    monkeypatch.setenv("RT06_PASS_SPP", "3")   # a cut inside the frame: two passes
+    scene = TW.tri_room(p, **room)
+    r = p.Renderer.MakeRenderer(TW.W, TW.H, TW.SPP, TW.DEPTH, run.cam, scene.getWorldPtr(), seed=TW.SEED, variant=variant)
+    if mode:
+        r.light_sampling(mode)
+        assert r.light_sampling_info() == {"enabled": True, "lights": 2}   # the quad light and the lamp; never a triangle
+    assert r.kernel_form() == TW.kernel_form_of(form, nee=1 if mode else 0) and r.kernel_triangles()
+    r.Render()
+    img = r.DownloadRenderbuffer()
+    assert bits_equal(img[keep], run.frame[keep]), mismatch_report(img[keep], run.frame[keep])
+    r.refine(1)
+    r.refine(3)   # uneven steps
+    sums = r.refine_sums()
+    assert bits_equal(sums[keep], run.sums[keep]), mismatch_report(sums[keep], run.sums[keep])
+    assert bits_equal(r.DownloadRenderbuffer(), img) and np.isfinite(sums[keep]).all()
+    r.close()
+
+
+@pytest.mark.parametrize("traversal", [1, 2], ids=["queue", "wide4"])
+def test_the_lane_walks_render_the_room_as_the_twin_does(p, traversal):
+    """the queue and the 4-wide walk read a quad's kind from the flat record: no triangle family.  The room has no two primitives at one distance on any ray
+    (tests/test_triangles_cpu.py: its list and its tree see the same hits), so the stack walk's twin speaks for them."""
+    run = TW.run()
+    scene = TW.tri_room(p, traversal=traversal)
+    r = p.Renderer.MakeRenderer(TW.W, TW.H, TW.SPP, TW.DEPTH, run.cam, scene.getWorldPtr(), seed=TW.SEED)
+    assert r.kernel_form() == _form(1, 3, 1, 1) and not r.kernel_triangles()
+    r.refine(TW.SPP)
+    assert bits_equal(r.refine_sums(), run.sums), mismatch_report(r.refine_sums(), run.sums)
+    assert bits_equal(r.DownloadRenderbuffer(), run.frame)
+    r.close()
+
+
+def test_the_baseline_kernel_renders_the_room_as_the_twin_does(p):
+    run = TW.run()
+    r = p.Renderer.MakeRenderer(TW.W, TW.H, TW.SPP, TW.DEPTH, run.cam, run.scene.getWorldPtr(), seed=TW.SEED, variant=1)
+    assert r.kernel_form()["kernel"] == "baseline" and not r.kernel_triangles()
+    r.Render()
+    img = r.DownloadRenderbuffer()
+    assert bits_equal(img, run.frame), mismatch_report(img, run.frame)
+    r.close()
+
+
+def test_two_ranks_through_the_memcpy_transport(p, monkeypatch):
+    run = TW.run()
+    monkeypatch.setenv("RT06_MULTI_TRANSPORT", "memcpy")
+    m = p.MultiRenderer.MakeRenderer(TW.W, TW.H, TW.SPP, TW.DEPTH, run.cam, run.scene.getWorldPtr(), 2, seed=TW.SEED)
+    m.Render()
+    img = m.DownloadRenderbuffer()
+    assert bits_equal(img, run.frame), mismatch_report(img, run.frame)
+    m.close()
+
+
+@pytest.mark.parametrize("mode", [1, 2])
+@pytest.mark.parametrize("tri_light", [False, True], ids=["", "triangle-light"])
+def test_light_sampling_leaves_triangles_out_of_the_table_and_equals_the_twin(p, mode, tri_light):
+    run = TW.run(mode=mode, lamp=True, tri_light=tri_light)
+    assert run.followed
+    r = p.Renderer.MakeRenderer(TW.W, TW.H, TW.SPP, TW.DEPTH, run.cam, run.scene.getWorldPtr(), seed=TW.SEED)
+    r.light_sampling(mode)
+    assert r.light_sampling_info() == {"enabled": True, "lights": mode} and r.kernel_form() == _form(0, 0, nee=1) and r.kernel_triangles()   # one quad light, one sphere lamp, never the triangle
+    r.refine(TW.SPP)
+    assert bits_equal(r.refine_sums(), run.sums), mismatch_report(r.refine_sums(), run.sums)
+    r.close()
+    if tri_light:   # ... which emits all the same: the frame is not the frame without it
+        assert not bits_equal(run.sums, TW.run(mode=mode, lamp=True).sums)
+
+
+def test_feature_buffers_are_the_twins_first_hits_and_the_denoiser_runs(p):
+    import test_gpu_denoise as D
+    run = TW.run()
+    r = p.Renderer.MakeRenderer(TW.W, TW.H, TW.SPP, TW.DEPTH, run.cam, run.scene.getWorldPtr(), seed=TW.SEED)
+    r.enable_aov()
+    r.refine(1)
+    r.refine(TW.SPP - 1)
+    got = r.aov_sums()
+    exp = TT.first_hit_sums(run.world, as_oracle_camera(run.cam), TW.W, TW.H, TW.SPP, TW.SEED)
+    assert bits_equal(got[..., 0:4], exp[..., 0:4]), mismatch_report(got[..., 0:4], exp[..., 0:4])
+    assert bits_equal(got[..., 7], exp[..., 4]) and (got[..., 7] == TW.SPP).all()   # a closed room: every primary ray hits
+    den = r.denoise()
+    dp = p.Renderer.denoise_params()
+    twin = D.twin_denoise(r.refine_sums(), got, TW.SPP, TW.SPP, dp.iterations, dp.sigma_depth, dp.sigma_lum, dp.demodulate)
+    assert bits_equal(den, twin), mismatch_report(den, twin)
+    r.close()
+
+
+def test_an_image_textured_triangle_has_the_same_bits_in_the_lds_and_the_global_forms(p, monkeypatch):
+    from _nee_worlds import small_image
+    frames = []
+    for env in ({}, BIG, WIDE):
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        s = TW.tri_room(p)
+        s.set_image(small_image())
+        s.MakeTriangle((0.8, 0.2, 9.9), (4.8, 0.2, 9.9), (0.8, 4.2, 9.9), s.ImageTexture())
+        s.BuildBVH_SAH()
+        r = p.Renderer.MakeRenderer(TW.W, TW.H, TW.SPP, TW.DEPTH, TW.camera(p), s.getWorldPtr(), seed=TW.SEED)
+        f = r.kernel_form()
+        assert f["ext"] == 2 and (f["big"], f["wide"]) == ((0, 0), (1, 0), (1, 1))[len(env)]
+        r.refine(TW.SPP)
+        frames.append(r.refine_sums())
+        r.close()
+    assert bits_equal(frames[0], frames[1]) and bits_equal(frames[0], frames[2])
+    assert not bits_equal(frames[0], TW.run().sums)   # the textured triangle is in view
+
+
+def test_render_tool_places_a_mesh_and_writes_the_api_frame_as_png(p, tmp_path):
+    out = tmp_path / "mesh.png"
+    args = ["--scene", "cornell_box", "--width", "32", "--height", "32", "--spp", "4", "--depth", "8", "--mesh", "icosphere:2", "--mesh-scale", "80",
+            "--mesh-rotate-y", "10", "--mesh-translate", "278,278,200", "--mesh-material", "metal", "--out", str(out)]
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "render.py")] + args, capture_output=True, text=True, timeout=120)
+    assert res.returncode == 0, res.stderr
+    lines = [json.loads(l) for l in res.stdout.splitlines() if l.startswith("{")]
+    assert lines[0] == {"mesh": "icosphere:2", "triangles": 320, "skipped_degenerate": 0}
+    s = p.Scene.cornell_box()
+    s.MakeMesh(*TW.mesh_io().icosphere(2), s.Metal((0.8, 0.85, 0.88), 0.0), 80.0, 10.0, (278, 278, 200))
+    s.BuildBVH_TopDown()
+    r = p.Renderer.MakeRenderer(32, 32, 4, 8, p.PinholeCamera((278, 278, -800), (278, 278, 0), (0, 1, 0), 40.0, 1.0), s.getWorldPtr(), seed=1984)
+    r.Render()
+    frame = r.DownloadRenderbuffer()
+    r.close()
+    from ray_tracing_v06_amd import image_io
+    expected = tmp_path / "api.png"
+    image_io.write_png(str(expected), frame)   # the tool prints no floats: its PNG against the PNG of the API's float frame, byte for byte
+    assert out.read_bytes() == expected.read_bytes() and out.read_bytes()[:8] == b"\x89PNG\r\n\x1a\n"
