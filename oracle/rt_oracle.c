@@ -345,6 +345,10 @@ static inline int quad_closest_intersection(const orc_world* w, int32_t qi, int3
     float alpha = dot(ld3(q->w), cross(planar, ld3(q->v)));
     float beta = dot(ld3(q->w), cross(ld3(q->u), planar));
     if (!(alpha >= 0.0f && alpha <= 1.0f && beta >= 0.0f && beta <= 1.0f)) return 0;
+    if (q->kind == ORC_QUAD_TRIANGLE) {   /* the book's triangle::is_interior: one fp32 add, rounded on its own; a sum of exactly 1 is inside */
+        float sum = alpha + beta;
+        if (!(sum <= 1.0f)) return 0;
+    }
     rec->mat = q->mat;
     rec->distance = t;
     rec->prim = unified;
@@ -989,7 +993,7 @@ static void quad_finalize(orc_quad* q) {
     st3(q->normal, normal);
     q->D = dot(normal, ld3(q->Q));
     st3(q->w, divs(n, dot(n, n)));
-    q->pad0 = q->pad1 = q->pad2 = 0.0f;
+    q->kind = ORC_QUAD_PARALLELOGRAM; q->pad1 = q->pad2 = 0.0f;
 }
 static box_t box_of_points(v3 a, v3 b) { box_t r = {vmin(a, b), vmax(a, b)}; return r; }
 static box_t quad_bounds(const orc_quad* q) {
@@ -1181,6 +1185,8 @@ static void finish_scene(orc_scene* s, int builder) {
 
 orc_scene* orc_scene_from_arrays_ext(size_t n_prims, const orc_prim* prims, size_t n_quads, const orc_quad* quads, size_t n_mats,
                                      const orc_material* mats, int builder, uint32_t background, const float background_color[3]) {
+    /* the builders below sort, bound and finalize parallelograms only: a triangle is refused, not mis-sorted (a world with triangles comes as a flat orc_world) */
+    for (size_t i = 0; i < n_quads; i++) if (quads[i].kind != ORC_QUAD_PARALLELOGRAM) return NULL;
     orc_scene* s = (orc_scene*)calloc(1, sizeof(orc_scene));
     s->prims = (orc_prim*)malloc((n_prims + 1) * sizeof(orc_prim)); if (n_prims) memcpy(s->prims, prims, n_prims * sizeof(orc_prim));
     s->n_prims = n_prims;

@@ -50,7 +50,16 @@ typedef struct { float c0[3]; float radius; float c1[3]; uint32_t mat; } orc_pri
 typedef struct { float albedo[3]; float param; float albedo2[3]; uint32_t type; } orc_material;
 /* quad(Q,u,v) of "Ray Tracing: The Next Week" (absent from the reference: SURVEY.md §8f rank 1); normal, D, w are
  * the cached plane quantities of that book's quad class */
-typedef struct { float Q[3]; float D; float u[3]; uint32_t mat; float v[3]; float pad0; float normal[3]; float pad1; float w[3]; float pad2; } orc_quad;
+/* kind: 0 = the parallelogram Q + a u + b v, 0 <= a, b <= 1; 1 = the triangle Q, Q + u, Q + v, which also asks a + b <= 1 (the book's triangle, a
+ * subclass of its quad); the same dword as rt_quad::kind of include/rt06.h, where earlier layouts had a padding word */
+#define ORC_QUAD_PARALLELOGRAM 0u
+#define ORC_QUAD_TRIANGLE 1u
+typedef struct { float Q[3]; float D; float u[3]; uint32_t mat; float v[3]; uint32_t kind; float normal[3]; float pad1; float w[3]; float pad2; } orc_quad;
+#ifndef __cplusplus
+_Static_assert(sizeof(orc_quad) == 80 && offsetof(orc_quad, kind) == 44 && sizeof(((orc_quad*)0)->kind) == 4, "the kind takes the old padding word: no byte of orc_quad moves");
+#else
+static_assert(sizeof(orc_quad) == 80 && offsetof(orc_quad, kind) == 44, "the kind takes the old padding word: no byte of orc_quad moves");
+#endif
 typedef struct {
     uint32_t kind; int32_t root; uint32_t n_nodes, n_prims, n_materials, max_stack;
     float bounds_min[3], bounds_max[3];

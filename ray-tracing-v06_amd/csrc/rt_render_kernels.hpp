@@ -41,14 +41,16 @@ __device__ __forceinline__ void write_pixel(const RenderParams& p, uint32_t L, u
     reinterpret_cast<float4*>(p.out)[p.tm.direct ? gid : L] = o;
 }
 
-__device__ __forceinline__ f3 wave_sum(f3 a) {
+// total + a[lane 0] + a[lane 1] + ... + a[lane 63], each addition rounded on its own, the same value in every lane: the samples of a pixel are added in
+// sample order, as the reference's loop (Renderer.cu:199-204) and the oracle add them (a pairwise sum over the lanes was one ulp off)
+__device__ __forceinline__ f3 add_lanes_in_order(f3 total, f3 a) {
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        a.x += __shfl_xor(a.x, off);
-        a.y += __shfl_xor(a.y, off);
-        a.z += __shfl_xor(a.z, off);
+    for (int l = 0; l < 64; l++) {
+        total.x += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(a.x), l));
+        total.y += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(a.y), l));
+        total.z += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(a.z), l));
     }
-    return a;
+    return total;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -62,9 +64,12 @@ __global__ __launch_bounds__(256) void render_kernel_wave_per_pixel(RenderParams
     uint32_t gid;
     if (!local_pixel_to_gid(p.tm, wave, gid)) return;
     f3 acc = mk3(0.0f);
-    for (uint32_t s = lane; s < p.spp; s += 64u)
-        acc = acc + one_sample(p.world, p.cam, p.width, p.height, p.max_depth, p.seed, gid, s);
-    acc = wave_sum(acc);
+    for (uint32_t first = 0; first < p.spp; first += 64u) {   // (wave-uniform: every lane is there for the sum; a lane past the last sample adds 0)
+        uint32_t s = first + lane;
+        f3 smp = mk3(0.0f);
+        if (s < p.spp) smp = one_sample(p.world, p.cam, p.width, p.height, p.max_depth, p.seed, gid, s);
+        acc = add_lanes_in_order(acc, smp);
+    }
     if (lane == 0) write_pixel(p, wave, gid, acc);
 }
 

@@ -1,6 +1,7 @@
 """A numpy float32 twin of closest intersection and of one whole sample for worlds with TRIANGLES — test infrastructure only.
 
-The oracle does not know triangles (to it a kind-1 record is a parallelogram), so nothing here asks it for a closest intersection.  closest_intersection()
+Nothing here asks the oracle for a closest intersection: the twin is an independent statement of the triangle rule, and the oracle's own (orc_quad::kind) is pinned
+to it (tests/test_triangles_cpu.py, pins 3 and 4).  closest_intersection()
 walks the flat world itself — RT_WORLD_BVH as BVH::ClosestIntersection does (BVH.cu:54-106: root box, pop, leaf -> primitive, inner -> both child boxes
 against rec.distance, near first, push far then near iff dist < rec.distance, no re-check at pop), RT_WORLD_LIST as HittableList.cuh:21-34 (bounds, then every
 object in order) — with box decisions from orc_aabb_batch, sphere roots from orc_sphere_batch and the quad test of _nee_twin._quad_hit's arithmetic plus the
@@ -30,8 +31,8 @@ _quad_hit = T._quad_hit   # the density step's per-light test: a light of the ta
 
 
 def kinds(quads):
-    """rt_quad::kind of every record (the dword the oracle's layout calls pad0)"""
-    return quads["pad0"].view(np.uint32)
+    """rt_quad::kind of every record"""
+    return quads["kind"]
 
 
 def lights_of(prims, quads, mats, mode):

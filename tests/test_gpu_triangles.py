@@ -24,36 +24,7 @@ def p():
     return pkg()
 
 
-def unit_world(p, triangle, as_list, second=False):
-    """the unit triangle (0,0,0), (1,0,0), (0,1,0) or the quad of the same Q, u, v; second: plus the coplanar triangle across the diagonal"""
-    s = p.Scene()
-    m = s.Lambertian((0.5, 0.5, 0.5))
-    if triangle:
-        s.MakeTriangle((0, 0, 0), (1, 0, 0), (0, 1, 0), m)
-        if second:
-            s.MakeTriangle((1, 1, 0), (0, 1, 0), (1, 0, 0), m)
-    else:
-        s.MakeQuad((0, 0, 0), (1, 0, 0), (0, 1, 0), m)
-    s.MakeSphere((0.5, 0.5, -10), 3.0, m)   # behind the plane; widens a list's bounds, so that the rays at the vertices and on the edges get past them to the interior test
-    s.MakeHittableList() if as_list else s.BuildBVH_TopDown()
-    return s
-
-
-def down_z(points):
-    rays = np.zeros((len(points), 7), F)
-    rays[:, 0:2] = np.array(points, F)
-    rays[:, 2], rays[:, 5] = 1, -1
-    return rays
-
-
-EPS = F(2.0 ** -23)
-CRAFTED = [(0.25, 0.25), (0.5, 0.5), (0.5, F(0.5) + EPS), (0.75, 0.75), (0, 0), (1, 0), (0, 1), (0.5, 0), (0, 0.5), (-0.25, 0.5), (0.5, -0.25), (1.25, 0.1)]
-
-
-def crafted_rays():
-    rays = down_z(CRAFTED)
-    in_plane = np.array([[-1, 0.25, 0, 1, 0, 0, 0], [-1, 0.25, 0, 1, 0, 1e-9, 0]], F)   # |denom| < 1e-8: rejected whatever it would meet
-    return np.concatenate([rays, in_plane])
+unit_world, down_z, crafted_rays, EPS, CRAFTED = TW.unit_world, TW.down_z, TW.crafted_rays, TW.EPS, TW.CRAFTED   # shared with tests/test_triangles_cpu.py
 
 
 @pytest.mark.parametrize("as_list", [False, True], ids=["bvh", "list"])
@@ -80,14 +51,8 @@ def test_a_hit_at_exactly_the_distance_already_recorded_is_rejected(p, as_list):
     """`t >= rec.distance` with equality, which rt_probe_trace (no preset argument) reaches through what was visited before: a quad and two triangles in one
     plane, the second triangle a copy of the first.  Down z every one of them gives t = 1 exactly; whichever is visited first keeps the record — in a list
     that is the quad, which precedes every triangle; in a tree the twin says which — and each later one meets rec.distance == t and is rejected."""
-    s = p.Scene()
-    m = s.Lambertian((0.5, 0.5, 0.5))
-    s.MakeSphere((0.5, 0.5, -10), 3.0, m)
-    s.MakeTriangle((0, 0, 0), (1, 0, 0), (0, 1, 0), m)
-    s.MakeTriangle((0, 0, 0), (1, 0, 0), (0, 1, 0), m)
-    s.MakeQuad((0, 0, 0), (1, 0, 0), (0, 1, 0), m)
-    s.MakeHittableList() if as_list else s.BuildBVH_TopDown()
-    rays = down_z([(0.25, 0.25), (0.125, 0.5), (0.75, 0.75)])
+    s = TW.equal_distance_world(p, as_list)
+    rays = down_z(TW.EQUAL_DISTANCE)
     got = p.api.probe_trace(s.getWorldPtr(), rays)
     exp = TT.closest_intersection(as_oracle_world(s.getWorldPtr()), rays)
     for g, e in zip(got, exp):
@@ -118,7 +83,7 @@ def test_probe_shapes(p, n):
 @pytest.mark.parametrize("as_list", [False, True], ids=["bvh", "list"])
 def test_two_coplanar_triangles_hit_on_their_shared_diagonal_the_first_visited_wins(p, as_list):
     s = unit_world(p, True, as_list, second=True)
-    rays = down_z([(0.5, 0.5), (0.25, 0.75), (0.75, 0.25), (0.25, 0.25), (0.75, 0.75)])
+    rays = down_z(TW.DIAGONAL)
     got = p.api.probe_trace(s.getWorldPtr(), rays)
     exp = TT.closest_intersection(as_oracle_world(s.getWorldPtr()), rays)
     for g, e in zip(got, exp):

@@ -1,5 +1,6 @@
-"""Triangles without a GPU: the twin's two pins, rt_quad's layout, that no earlier world moved a byte, the order of a flat world, bounds,
-refusals, the mesh transform, what light sampling does with a triangle, and the estimator's sanity on the twin."""
+"""Triangles without a GPU: the twin's two pins, the oracle's triangle rule pinned to the twin (crafted rays, room rays, whole samples), what
+the worlds of tests/test_gpu_triangles_oracle.py hold, rt_quad's layout, that no earlier world moved a byte, the order of a flat world, bounds, refusals, the
+mesh transform, what light sampling does with a triangle, and the estimator's sanity on the twin."""
 import ctypes as C
 import os
 import re
@@ -70,6 +71,182 @@ def test_pin_2_a_whole_sample_is_the_oracle_and_with_sampling_on_the_light_sampl
         assert not bits_equal(got, off)
 
 
+# ---- the oracle's kind rule, pinned to the twin: two independent statements of `alpha + beta <= 1`, one in C and one in numpy ------------------------
+def orc_trace(w, rays):
+    n = len(rays)
+    hit, t, prim, normal = np.zeros(n, np.int32), np.zeros(n, F), np.zeros(n, np.int32), np.zeros((n, 3), F)
+    assert O.lib().orc_trace_batch(C.byref(w), n, np.ascontiguousarray(rays, F), hit, t, prim, normal) == 0
+    return hit, t, prim, normal
+
+
+def assert_oracle_is_twin(w, rays):
+    """hit, t, primitive and normal of every ray, bit for bit, nothing masked; returns the oracle's answer"""
+    got, exp = orc_trace(w, rays), TT.closest_intersection(w, rays)
+    assert np.array_equal(got[0], exp[0]) and np.array_equal(got[2], exp[2]), np.nonzero(got[2] != exp[2])[0][:5]
+    assert bits_equal(got[1], exp[1]), mismatch_report(got[1], exp[1])
+    assert bits_equal(got[3], exp[3]), mismatch_report(got[3], exp[3])
+    return got
+
+
+def test_oracle_quad_keeps_its_layout_and_has_the_kind():
+    dt = O.QUAD_DT
+    assert dt.itemsize == 80 and {n: dt.fields[n][1] for n in dt.names} == {"Q": 0, "D": 12, "u": 16, "mat": 28, "v": 32, "kind": 44, "normal": 48, "pad1": 60, "w": 64, "pad2": 76}
+    assert dt.fields["kind"][0] == np.dtype("<u4") and dt == pkg().capi.QUAD_DT
+    header = open(os.path.join(ROOT, "oracle", "rt_oracle.h")).read()
+    assert "pad0" not in header and "sizeof(orc_quad) == 80 && offsetof(orc_quad, kind) == 44" in header   # the compile-time statement
+
+
+@pytest.mark.parametrize("as_list", [False, True], ids=["bvh", "list"])
+def test_pin_3_the_oracle_meets_crafted_rays_as_the_twin_does(as_list):
+    p = pkg()
+    rays = TW.crafted_rays()
+    keep = [TW.unit_world(p, True, as_list), TW.unit_world(p, False, as_list), TW.unit_world(p, True, as_list, second=True), TW.equal_distance_world(p, as_list)]
+    tri_w, quad_w, diagonal_w, equal_w = (as_oracle_world(s.getWorldPtr()) for s in keep)   # (a flat world points into its scene: `keep` outlives the views)
+    tri, quad = assert_oracle_is_twin(tri_w, rays), assert_oracle_is_twin(quad_w, rays)
+    # inside; alpha + beta exactly 1: inside; one ulp more: outside; (0.75, 0.75) hits the quad and misses the triangle (primitive 0 is the sphere behind the plane)
+    assert tri[2][:4].tolist() == [1, 1, 0, 0] and quad[2][:4].tolist() == [1, 1, 1, 1]
+    if as_list:
+        assert tri[2][4:9].tolist() == [1, 1, 1, 1, 1]     # every vertex and edge midpoint is inside
+    assert (tri[2][9:] != 1).all() and (quad[2][9:] != 1).all()
+    diagonal = assert_oracle_is_twin(diagonal_w, TW.down_z(TW.DIAGONAL))
+    assert diagonal[2].tolist() == [1, 1, 1, 1, 2]          # a point of the shared diagonal is inside both triangles: the first visited keeps it
+    equal = assert_oracle_is_twin(equal_w, TW.down_z(TW.EQUAL_DISTANCE))
+    assert equal[1].tolist() == [1.0, 1.0, 1.0] and equal[2][2] == 1   # (0.75, 0.75): the quad alone
+    if as_list:
+        assert equal[2].tolist() == [1, 1, 1]                # the quad was there first; both triangles met rec.distance == t
+
+
+@pytest.mark.parametrize("builder", ["BuildBVH_TopDown", "BuildBVH_SAH", "BuildBVH_BottomUp", "MakeHittableList"])
+def test_pin_3_the_oracle_meets_4096_room_rays_as_the_twin_does(builder):
+    p = pkg()
+    scene = TW.tri_room(p, as_list=builder == "MakeHittableList", builder=builder)
+    got = assert_oracle_is_twin(as_oracle_world(scene.getWorldPtr()), TW.room_rays(4096))
+    assert got[0].all() and 0.1 < (got[2] >= 7).mean() < 0.9   # a closed room; rays end on triangles and on parallelograms
+
+
+def test_pin_4_whole_samples_of_the_oracle_are_the_twins():
+    run = TW.run()
+    assert run.followed
+    w, cam = run.world, as_oracle_camera(run.cam)
+    samples = plain_samples(w, cam, TW.W, TW.H, TW.SPP, TW.DEPTH)   # orc_radiance_batch, one call per sample index
+    assert bits_equal(samples, run.samples), mismatch_report(samples, run.samples)
+    sums = TT.in_order_sums(samples)
+    assert bits_equal(sums, run.sums), mismatch_report(sums, run.sums)
+    frame, _ = O.render(w, cam, TW.W, TW.H, TW.SPP, TW.DEPTH, TW.SEED)
+    assert bits_equal(frame, run.frame), mismatch_report(frame, run.frame)
+    assert not bits_equal(frame, TW.run(lamp=True).frame)
+
+
+def test_the_oracles_scene_builders_refuse_a_triangle():
+    mats = np.zeros(1, O.MAT_DT)
+    quads = np.zeros(2, O.QUAD_DT)
+    quads["u"], quads["v"] = (1, 0, 0), (0, 1, 0)
+    quads["Q"][1] = (0, 0, 1)
+    for builder in (0, 1, 2, 3):
+        assert O.Scene.from_arrays_ext(np.zeros(0, O.PRIM_DT), quads, mats, builder).h   # parallelograms: built as ever
+    quads["kind"][1] = 1
+    for builder in (0, 1, 2, 3):
+        assert O.lib().orc_scene_from_arrays_ext(0, None, 2, quads.ctypes.data, 1, mats.ctypes.data, builder, 0, None) is None   # NULL, not a mis-sorted world
+
+
+# ---- what the worlds of tests/test_gpu_triangles_oracle.py hold ---------------------------------------------------------------------------------------
+def contents(scene):
+    """(n_prims, n_plain_quads, triangles, materials in use on a primitive, moving spheres)"""
+    w, q = scene.getWorldPtr(), scene.quads()
+    _, prims, mats = scene.arrays()
+    used = set(mats["type"][q["mat"]].tolist()) | set(mats["type"][prims["mat"] & np.uint32(0x7fffffff)].tolist())
+    n_plain = int((q["kind"] == 0).sum())
+    assert scene.n_triangles() == w.n_quads - n_plain and (q["kind"][:n_plain] == 0).all() and (q["kind"][n_plain:] == 1).all()
+    return w.n_prims, n_plain, scene.n_triangles(), used, int((prims["mat"] >> 31).sum())
+
+
+def ext_level(scene):
+    """the EXT level of the kernel a world gets (DeviceScene::pack): 2 with a noise or image material, else 1 with anything beyond the reference's features"""
+    w = scene.getWorldPtr()
+    types = scene.arrays()[2]["type"]
+    return 2 if (types >= TW.MAT["noise"]).any() else int(w.n_quads != 0 or w.background != 0 or (types >= TW.MAT["light"]).any())
+
+
+M = TW.MAT
+
+
+@pytest.mark.parametrize("as_list", [False, True], ids=["bvh", "list"])
+def test_the_wide_rooms_hold_what_they_are_for(as_list):
+    p = pkg()
+    base = contents(TW.tri_room(p, as_list=as_list))
+    assert base == (0, 7, 85, {M["lambertian"], M["metal"], M["checker"], M["light"]}, 0)
+    wide = TW.wide_room(p, as_list=as_list)
+    # one wall less; icosphere(1) of glass (80) and a metal tetrahedron (4) more; one moving sphere
+    assert contents(wide) == (1, 6, 85 + 84, {M["lambertian"], M["metal"], M["dielectric"], M["checker"], M["light"]}, 1) and ext_level(wide) == 1
+    w, q, mats = wide.getWorldPtr(), wide.quads(), wide.arrays()[2]
+    assert w.background == 1 and tuple(w.background_color) == tuple(F(TW.SKY)) and w.kind == int(as_list)
+    assert (mats["type"][q["mat"][q["kind"] == 1]] == M["dielectric"]).sum() == 80
+    fuzzy = q[(q["kind"] == 1) & (mats["type"][q["mat"]] == M["metal"]) & (mats["param"][q["mat"]] == F(0.4))]
+    assert len(fuzzy) == 4
+    assert not ((q["kind"] == 0) & (q["Q"] == F([10, 0, 0])).all(axis=1)).any()   # the right wall is gone
+    ext2 = TW.wide_room(p, ext=2, as_list=as_list)
+    assert contents(ext2) == (2, 6, 85 + 84 + 2, set(range(8)), 1) and ext_level(ext2) == 2
+    q2, mats2, prims2 = ext2.quads(), ext2.arrays()[2], ext2.arrays()[1]
+    for kind in ("noise", "image"):   # each on exactly one triangle, and on nothing else
+        assert (mats2["type"][q2["mat"]] == M[kind]).sum() == 1 and q2["kind"][mats2["type"][q2["mat"]] == M[kind]].tolist() == [1]
+    assert (mats2["type"][prims2["mat"] & np.uint32(0x7fffffff)] == M["isotropic"]).sum() == 1
+    assert ext2.getWorldPtr().perlin and ext2.getWorldPtr().image
+    assert contents(TW.wide_room(p, ext=2, medium=False, as_list=as_list))[:3] == (1, 6, 171)
+
+
+@pytest.mark.parametrize("builder", TW.BUILDERS)
+def test_the_boundary_worlds_hold_what_they_are_for(builder):
+    p = pkg()
+    expect = {"triangles_only": (0, 0, 86), "one_quad": (1, 1, 84), "one_triangle": (1, 14, 1), "siblings": (0, 7, 7)}
+    for which, exp in expect.items():
+        s = TW.boundary_world(p, which, builder)
+        assert contents(s)[:3] == exp and ext_level(s) == 1 and s.getWorldPtr().kind == int(builder == "MakeHittableList")
+    assert M["dielectric"] in contents(TW.boundary_world(p, "one_quad", builder))[3] and M["dielectric"] in contents(TW.boundary_world(p, "one_triangle", builder))[3]
+
+
+def test_the_last_parallelogram_and_the_first_triangle_are_the_two_leaves_of_one_node():
+    """a leaf of the flat tree holds one primitive, so two primitives are never closer in it than as the two leaf children of one inner node"""
+    p = pkg()
+    s = TW.boundary_world(p, "siblings", "BuildBVH_SAH")
+    n_prims, n_plain, _, _, _ = contents(s)
+    last, first = n_prims + n_plain - 1, n_prims + n_plain
+    assert (last, first) in TW.sibling_leaves(s) or (first, last) in TW.sibling_leaves(s)
+    q = s.quads()
+    assert q["kind"][n_plain - 1] == 0 and q["kind"][n_plain] == 1 and q["Q"][n_plain - 1].tolist() == [0.5, 0, 0] and bits_equal(q["Q"][n_plain], F([1.6, 0, 0]))
+
+
+def test_the_mesh_rooms_and_the_closed_mesh_hold_what_they_are_for():
+    p = pkg()
+    assert contents(TW.mesh_room(p, 2))[:3] == (0, 7, 85 + 320) and contents(TW.mesh_room(p, 4))[:3] == (0, 7, 85 + 5120)
+    assert M["dielectric"] in contents(TW.mesh_room(p, 2))[3]
+    for as_list in (False, True):
+        s, rays, (nv, ne, nf) = TW.closed_mesh_world(p, as_list)
+        assert contents(s)[:3] == (0, 0, 320) and (nv, ne, nf) == (162, 480, 320) and len(rays) == 2 * (nv + ne + nf)
+        hit = orc_trace(as_oracle_world(s.getWorldPtr()), rays)[0]
+        print(f"closed icosphere(2), {'list' if as_list else 'bvh'}: {int((hit == 0).sum())} of {len(rays)} rays at vertices, edge midpoints and centroids pass through")   # a measurement (§18)
+        assert hit[nv + ne:nv + ne + nf].all() and hit[-nf:].all()   # the centroids are well inside their faces
+
+
+def test_the_random_triangle_worlds_cover_what_they_are_for():
+    p = pkg()
+    seen = {"builder": set(), "camera": set(), "ext": set(), "mats": set(), "shapes": set(), "meshes": set()}
+    specials = moving = no_quads = 0
+    for seed in range(12):
+        s, cam, W, H, spp, depth, r = TW.random_tri_world(p, seed)
+        n_prims, n_plain, n_tri, used, n_moving = contents(s)
+        assert n_tri >= 5 and W <= 48 and H <= 32 and 1 <= spp <= 8 and ext_level(s) == r["ext"]
+        assert 1 <= len(r["triangles"]["meshes"]) <= 3 and 5 <= n_tri - sum(n for _, n in r["triangles"]["meshes"]) <= 30
+        seen["builder"].add(r["builder"]); seen["camera"].add(r["camera"]); seen["ext"].add(r["ext"]); seen["mats"] |= used
+        seen["shapes"] |= {k for k, v in r["triangles"]["free"].items() if v}
+        seen["meshes"] |= {name for name, _ in r["triangles"]["meshes"]}
+        specials += any(float(F(x)) in [float(F(v)) for v in TW.EYE_SPECIALS] for x in r["eye"])
+        moving += n_moving > 0
+        no_quads += n_plain == 0
+    assert seen["builder"] == set(TW.BUILDERS) and seen["camera"] == set(TW.CAMERAS) and seen["ext"] == {1, 2} and seen["mats"] == set(range(8))
+    assert seen["shapes"] == {"plain", "axis", "sliver", "large"} and seen["meshes"] == {"tetrahedron", "icosphere(0)", "icosphere(1)", "icosphere(2)"}
+    assert specials >= 1 and moving >= 6 and no_quads >= 1
+
+
 # ---- data ----------------------------------------------------------------------------------------------------------------------------------------
 def test_rt_quad_keeps_its_layout_and_the_c_check_agrees():
     p = pkg()
@@ -84,6 +261,8 @@ def test_rt_quad_keeps_its_layout_and_the_c_check_agrees():
         assert name in declared and name in p.capi.SYMBOLS and getattr(p.lib(), name).argtypes, name
     hpp = open(os.path.join(ROOT, "include", "rt06", "rt06.hpp")).read()
     assert "int32_t AddTriangle(" in hpp and "uint32_t AddMesh(" in hpp
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "ray-tracing-v06_amd", "csrc")])   # as the other ABI tests do: the check is built where it is missing
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "cpp_triangles")])
     out = subprocess.check_output([os.path.join(ROOT, "tests", "cpp_triangles", "triangle_abi_check")], text=True)
     assert out.strip() == "triangle ABI ok"
 
@@ -327,3 +506,37 @@ def test_every_triangle_instantiation_has_a_recipe_in_the_matrix_the_gpu_tests_r
         assert variant == ({0: 3, 1: 2}[exact] if world == TW.BVH else 0)
         assert env == (TW.LDS, TW.NARROW, TW.WIDE)[big + wide] if world == TW.BVH else env == (TW.NARROW if big else TW.LDS)
     assert len({TW.form_id(f) for f in TW.FORMS}) == 16
+
+
+# ---- the fuzzer's worlds -------------------------------------------------------------------------------------------------------------------------------
+def test_the_fuzzer_builds_its_first_fifty_worlds_on_the_host_and_no_triangles_restores_the_recorded_ones():
+    """tests/golden/fuzz_worlds_first50.txt: per seed, the sha256 of the flat world (TW.flat_bytes) that tools/fuzz_campaign.py made before it knew triangles, and
+    the next draw of the seed's generator after the world — the campaigns recorded under profiles/ ran those worlds, frames and cameras."""
+    import hashlib
+    import importlib.util
+    p = pkg()
+    spec = importlib.util.spec_from_file_location("fuzz_campaign", os.path.join(ROOT, "tools", "fuzz_campaign.py"))
+    fuzz = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(fuzz)   # starts nothing
+    recorded = [line.split() for line in open(os.path.join(ROOT, "tests", "golden", "fuzz_worlds_first50.txt"))]
+    assert [int(r[0]) for r in recorded] == list(range(50))
+    with_triangles = tri_lists = meshes = 0
+    for seed, digest, next_draw in recorded:
+        seed = int(seed)
+        s0, kinds0, builder0, big0, rng0 = fuzz.world_of_seed(p, seed, triangles=False)
+        assert hashlib.sha256(TW.flat_bytes(s0)).hexdigest() == digest and int(rng0.integers(0, 1 << 30)) == int(next_draw), seed
+        s1, kinds1, builder1, big1, rng1 = fuzz.world_of_seed(p, seed)
+        assert (kinds1, builder1, big1) == (kinds0, builder0, big0) and int(rng1.integers(0, 1 << 30)) == int(next_draw), seed   # the frame and the camera stay too
+        n = s1.n_triangles()
+        assert s0.n_triangles() == 0 and (n == 0 or kinds1 >= 1)
+        q0, q1 = s0.quads(), s1.quads()
+        assert sorted(map(bytes, q1[q1["kind"] == 0])) == sorted(map(bytes, q0))   # the rest of the world is what it was
+        assert sorted(map(bytes, s1.arrays()[1])) == sorted(map(bytes, s0.arrays()[1])) and s1.arrays()[2].tobytes() == s0.arrays()[2].tobytes()
+        if n == 0:
+            assert TW.flat_bytes(s1) == TW.flat_bytes(s0)
+        with_triangles += n > 0
+        tri_lists += n > 0 and builder1 == 3
+        meshes += n > 30
+    print(f"{with_triangles} of 50 worlds hold triangles, {meshes} of them a mesh, {tri_lists} are lists")
+    assert with_triangles * 3 >= 50 and meshes >= 1
+    assert fuzz.parse_args(["--no-triangles", "--seeds", "3"]).no_triangles and not fuzz.parse_args([]).no_triangles

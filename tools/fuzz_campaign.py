@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
-"""Differential fuzz campaign: random worlds (spheres, moving spheres, quads, lights, media, textures; every builder; LDS
+"""Differential fuzz campaign: random worlds (spheres, moving spheres, quads, triangles and meshes, lights, media, textures; every builder; LDS
 and global-memory paths; three cameras) rendered on the GPU and by the CPU oracle, compared bit for bit.
-    python tools/fuzz_campaign.py --seeds 200 [--first 0]
-Prints one line per failure and a summary; exit code 1 if anything differed."""
+    python tools/fuzz_campaign.py --seeds 200 [--first 0] [--no-triangles]
+Prints one line per failure and a summary; exit code 1 if anything differed.  The triangles of a world come from a generator of their own, so the rest of a seed's
+world is what it was before the fuzzer made triangles, and --no-triangles renders exactly those earlier worlds.  Importing this file starts nothing:
+world_of_seed() builds a seed's world on the host, without a device."""
 import argparse, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -11,25 +13,32 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import __graft_entry__ as G
 import _nee_twin as T
 import _oracle as O
+import _tri_twin as TT
+import _tri_worlds as TW
 from _common import as_oracle_camera, as_oracle_world, bits_equal
 
-ap = argparse.ArgumentParser()
-ap.add_argument("--seeds", type=int, default=100)
-ap.add_argument("--first", type=int, default=0)
-ap.add_argument("--variants", action="store_true", help="pick a random kernel variant (0..5) per world — variant 5 (ray exchange) with random roles / thresholds / ring pairs —, now and then a forced multi-pass cut; unsupported combinations are skipped")
-ap.add_argument("--force-variant", type=int, default=None, help="render every world with this kernel variant; 6 (tolerance mode) is held to |delta| < 1e-3 and its differing frames are counted, not failed")
-args = ap.parse_args()
-p = G.load_package()
+TRIANGLE_SHARE = 0.6   # of the worlds with quads; the others keep the kernels without the triangle family under the campaign
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--seeds", type=int, default=100)
+    ap.add_argument("--first", type=int, default=0)
+    ap.add_argument("--variants", action="store_true", help="pick a random kernel variant (0..5) per world — variant 5 (ray exchange) with random roles / thresholds / ring pairs —, now and then a forced multi-pass cut; unsupported combinations are skipped")
+    ap.add_argument("--force-variant", type=int, default=None, help="render every world with this kernel variant; 6 (tolerance mode) is held to |delta| < 1e-3 and its differing frames are counted, not failed")
+    ap.add_argument("--no-triangles", action="store_true", help="the worlds as they were before the fuzzer made triangles, byte for byte")
+    return ap.parse_args(argv)
 
 
 def image(h, w, rng):
     return rng.integers(0, 256, (h, w, 3)).astype(np.uint8)
 
 
-def make_world(rng):
+def make_world(p, rng, tri_rng=None, force_variant=None):
+    """the world of one seed: everything but the triangles is drawn from rng, the triangles (kinds >= 1, tri_rng given) from tri_rng alone"""
     s = p.Scene()
     kinds = rng.integers(0, 4)   # 0 spheres only (reference features), 1 + quads/lights/background, 2 + media, 3 + textures
-    if args.force_variant == 6:
+    if force_variant == 6:
         kinds = 0   # the tolerance mode exists for sphere worlds of the reference's feature set only
     mats = [s.Lambertian(rng.random(3)), s.Metal(rng.random(3), float(rng.choice([0.0, 0.1, 0.7, 1.0]))),
             s.Dielectric((1, 1, 1), float(rng.choice([1.5, 1.33, 1 / 1.5, 2.4]))),
@@ -44,7 +53,7 @@ def make_world(rng):
     media = []
     if kinds >= 2:
         media = [s.Isotropic(rng.random(3), float(rng.choice([0.01, 0.3, 2.0])))]
-    big = rng.random() < 0.15 and args.force_variant != 6   # (and for LDS-resident worlds only)
+    big = rng.random() < 0.15 and force_variant != 6   # (and for LDS-resident worlds only)
     n = int(rng.integers(1500, 2600)) if big else int(rng.integers(1, 70))
     spread = 30.0 if big else 6.0
     for i in range(n):
@@ -73,6 +82,8 @@ def make_world(rng):
             s.MakeBox((-1, 0, -1), (1.5, 2, 1), quad_mats[0], float(rng.uniform(-40, 40)), (rng.random(3) * 4).astype(np.float32))
         if rng.random() < 0.6:
             s.set_background(tuple(float(x) for x in rng.random(3) * 0.4))
+    if kinds >= 1 and tri_rng is not None and tri_rng.random() < TRIANGLE_SHARE:   # free triangles and now and then a mesh, as the random worlds of tests/_tri_worlds.py have them
+        TW.random_triangles(s, tri_rng, quad_mats, spread=spread, meshes=int(tri_rng.random() < 0.3))
     # big worlds: the two O(n log n) builders, and (round 2) now and then a HittableList — the global-memory form of the list kernel
     builder = int(rng.integers(0, 4)) if not big else (3 if rng.random() < 0.08 else int(rng.integers(0, 2)))
     [s.BuildBVH_TopDown, s.BuildBVH_SAH, s.BuildBVH_BottomUp, s.MakeHittableList][builder]()
@@ -81,9 +92,17 @@ def make_world(rng):
     return s, kinds, builder, big
 
 
-def light_sampling_check(s, w, cam, ck, W, H, depth, variant):
+def world_of_seed(p, seed, triangles=True, force_variant=None):
+    """(scene, kinds, builder, big, rng): rng is the seed's generator after the world, from which the frame and the camera are drawn next"""
+    rng = np.random.default_rng(900000 + seed)
+    tri_rng = np.random.default_rng(700000 + seed) if triangles else None
+    return make_world(p, rng, tri_rng, force_variant) + (rng,)
+
+
+def light_sampling_check(p, s, w, cam, ck, W, H, depth, variant):
     """A world rt_world_quad_lights accepts, with sampling on, at 4 spp on at most 48 x 32 pixels: the renderer's own form and the global-memory form must agree in
-    every bit, and both must be the twin (tests/_nee_twin.py) on every pixel it follows (pinhole cameras).  None: not applicable; else (ok, forms)."""
+    every bit, and both must be the twin on every pixel it follows (pinhole cameras): tests/_nee_twin.py, or tests/_tri_twin.py for a world with triangles (static
+    spheres and the stack walk only: another world with triangles is held across the two forms alone).  None: not applicable; else (ok, forms)."""
     W, H, spp = min(W, 48), min(H, 32), 4
     sums, forms = [], []
     for env in ({}, {"RT06_FORCE_BIG": "1"}):
@@ -104,87 +123,102 @@ def light_sampling_check(s, w, cam, ck, W, H, depth, variant):
         r.close()
     ok = bits_equal(sums[0], sums[1])
     if ck == 0:
-        samples, followed = T.frame_samples(as_oracle_world(w), as_oracle_camera(cam), W, H, spp, depth, 1984, light_sampling=True)
+        if not s.n_triangles():
+            samples, followed = T.frame_samples(as_oracle_world(w), as_oracle_camera(cam), W, H, spp, depth, 1984, light_sampling=True)
+        elif w.traversal == 0 and not (s.arrays()[1]["mat"] >> 31).any():
+            samples, followed = TT.frame_samples(as_oracle_world(w), as_oracle_camera(cam), W, H, spp, depth, 1984, mode=1)
+        else:
+            return ok, forms
         px = followed.all(axis=2)
         ok = ok and bits_equal(sums[0][px], T.in_order_sums(np.where(followed[..., None], samples, 0))[px])
     return ok, forms
 
 
-fails = 0
-t0 = time.time()
-stats = {"lds": 0, "global": 0, "baseline": 0, "xchg": 0}
-for seed in range(args.first, args.first + args.seeds):
-    rng = np.random.default_rng(900000 + seed)
-    s, kinds, builder, big = make_world(rng)
-    W, H = int(rng.integers(17, 120)), int(rng.integers(9, 80))
-    spp, depth = int(rng.integers(1, 20)), int(rng.choice([1, 2, 5, 50]))
-    eye = ((rng.random(3) * 2 - 1) * np.array([9, 4, 9])).astype(np.float32)
-    if rng.random() < 0.1:
-        eye[int(rng.integers(0, 3))] = float(rng.choice([0.0, 1e-30, -1e-25]))   # rays outside the fast-division class
-    ck = int(rng.integers(0, 3))
-    if ck == 0:
-        cam = p.PinholeCamera(eye, (0, 0, 0), (0, 1, 0), float(rng.uniform(20, 100)), W / H)
-    elif ck == 1:
-        cam = p.DefocusBlurCamera(eye, (0, 0, 0), (0, 1, 0), float(rng.uniform(20, 100)), W / H, float(rng.uniform(0, 0.5)), float(rng.uniform(2, 12)))
-    else:
-        cam = p.MotionBlurCamera(eye, (0, 0, 0), (0, 1, 0), float(rng.uniform(20, 100)), W / H, 0.0, 1.0)
-    w = s.getWorldPtr()
-    variant = int(rng.integers(0, 6)) if args.variants else 0
-    if args.force_variant is not None:
-        variant = args.force_variant
-    for k in ("RT06_XCHG", "RT06_PASS_SPP"):
-        os.environ.pop(k, None)
-    if args.variants and variant == 5:   # tracers, extra rays, exchange / shade thresholds, patience, priority, keep, ring pairs
-        os.environ["RT06_XCHG"] = ",".join(str(int(x)) for x in (rng.integers(1, 12), rng.integers(0, 300), rng.integers(1, 65), rng.integers(1, 65),
-                                                                   rng.integers(0, 12), rng.integers(0, 2), rng.integers(1, 65), rng.integers(1, 3)))
-    if args.variants and rng.random() < 0.15:
-        os.environ["RT06_PASS_SPP"] = str(int(rng.integers(1, 6)))
-    try:
-        r = p.Renderer.MakeRenderer(W, H, spp, depth, cam, w, variant=variant)
-    except p.capi.RtError:
-        stats["refused"] = stats.get("refused", 0) + 1   # e.g. variant 4 on an extended world, variant 3 on a HittableList
-        continue
-    info = r.kernel_info()
-    try:
-        r.Render()
-        img = r.DownloadRenderbuffer()
-    except p.capi.RtError as e:
-        if e.code != 4:
-            raise
-        stats["queue_overflow"] = stats.get("queue_overflow", 0) + 1
+def main(argv=None):
+    args = parse_args(argv)
+    p = G.load_package()
+    fails = 0
+    t0 = time.time()
+    stats = {"lds": 0, "global": 0, "baseline": 0, "xchg": 0, "triangle_worlds": 0, "tri_kernels": 0}
+    for seed in range(args.first, args.first + args.seeds):
+        s, kinds, builder, big, rng = world_of_seed(p, seed, not args.no_triangles, args.force_variant)
+        W, H = int(rng.integers(17, 120)), int(rng.integers(9, 80))
+        spp, depth = int(rng.integers(1, 20)), int(rng.choice([1, 2, 5, 50]))
+        eye = ((rng.random(3) * 2 - 1) * np.array([9, 4, 9])).astype(np.float32)
+        if rng.random() < 0.1:
+            eye[int(rng.integers(0, 3))] = float(rng.choice([0.0, 1e-30, -1e-25]))   # rays outside the fast-division class
+        ck = int(rng.integers(0, 3))
+        if ck == 0:
+            cam = p.PinholeCamera(eye, (0, 0, 0), (0, 1, 0), float(rng.uniform(20, 100)), W / H)
+        elif ck == 1:
+            cam = p.DefocusBlurCamera(eye, (0, 0, 0), (0, 1, 0), float(rng.uniform(20, 100)), W / H, float(rng.uniform(0, 0.5)), float(rng.uniform(2, 12)))
+        else:
+            cam = p.MotionBlurCamera(eye, (0, 0, 0), (0, 1, 0), float(rng.uniform(20, 100)), W / H, 0.0, 1.0)
+        w = s.getWorldPtr()
+        variant = int(rng.integers(0, 6)) if args.variants else 0
+        if args.force_variant is not None:
+            variant = args.force_variant
+        for k in ("RT06_XCHG", "RT06_PASS_SPP"):
+            os.environ.pop(k, None)
+        if args.variants and variant == 5:   # tracers, extra rays, exchange / shade thresholds, patience, priority, keep, ring pairs
+            os.environ["RT06_XCHG"] = ",".join(str(int(x)) for x in (rng.integers(1, 12), rng.integers(0, 300), rng.integers(1, 65), rng.integers(1, 65),
+                                                                       rng.integers(0, 12), rng.integers(0, 2), rng.integers(1, 65), rng.integers(1, 3)))
+        if args.variants and rng.random() < 0.15:
+            os.environ["RT06_PASS_SPP"] = str(int(rng.integers(1, 6)))
+        try:
+            r = p.Renderer.MakeRenderer(W, H, spp, depth, cam, w, variant=variant)
+        except p.capi.RtError:
+            stats["refused"] = stats.get("refused", 0) + 1   # e.g. variant 4 on an extended world, variant 3 on a HittableList
+            continue
+        info = r.kernel_info()
+        tri_kernel = r.kernel_triangles()
+        try:
+            r.Render()
+            img = r.DownloadRenderbuffer()
+        except p.capi.RtError as e:
+            if e.code != 4:
+                raise
+            stats["queue_overflow"] = stats.get("queue_overflow", 0) + 1
+            r.close()
+            continue
         r.close()
-        continue
-    r.close()
-    if big and builder == 3:
-        W, H, spp = min(W, 40), min(H, 24), min(spp, 3)   # (a 2000-sphere list costs the CPU oracle 2000 sphere tests per ray)
-        r = p.Renderer.MakeRenderer(W, H, spp, depth, cam, w, variant=variant)
-        r.Render(); img = r.DownloadRenderbuffer(); r.close()
-    ref, _ = O.render(as_oracle_world(w), as_oracle_camera(cam), W, H, spp, depth)
-    stats["baseline" if info["variant"] == 1 else ("xchg" if info["variant"] == 5 else ("lds" if info["lds_resident"] else "global"))] += 1
-    if w.traversal:
-        stats[("queue", "wide4")[w.traversal - 1]] = stats.get(("queue", "wide4")[w.traversal - 1], 0) + 1
-    if info["variant"] == 6:   # tolerance mode: inside |delta| < 1e-3; frames that are not the oracle's bits are counted
-        same = bits_equal(img, ref)
-        stats["tol_frames_not_bit_identical"] = stats.get("tol_frames_not_bit_identical", 0) + (0 if same else 1)
-        dmax = 0.0 if same else float(np.nanmax(np.abs(img - ref)))
-        stats["tol_max_abs_delta"] = max(stats.get("tol_max_abs_delta", 0.0), dmax)
-        ok = np.array_equal(np.isnan(img), np.isnan(ref)) and dmax < 1e-3
-    elif info["variant"] == 1:
-        ok = np.array_equal(np.isnan(img), np.isnan(ref)) and float(np.nanmax(np.abs(img - ref))) <= 1e-5 * max(1.0, float(np.nanmax(ref)))
-    else:
-        ok = bits_equal(img, ref)
-    if not ok:
-        fails += 1
-        bad = int((img.view(np.uint32) != ref.view(np.uint32)).sum())
-        print(f"FAIL seed {seed}: kinds {kinds} builder {builder} big {big} cam {ck} {W}x{H}x{spp} depth {depth} info {info}: {bad} words differ", flush=True)
-    if ok and kinds >= 1 and info["variant"] in (2, 3):   # light sampling as one more feature of the case
-        ls = light_sampling_check(s, w, cam, ck, W, H, depth, variant)
-        if ls is not None:
-            stats["light_sampling"] = stats.get("light_sampling", 0) + 1
-            if not ls[0]:
-                fails += 1
-                print(f"FAIL seed {seed} with light sampling: kinds {kinds} builder {builder} big {big} cam {ck} depth {depth} forms {ls[1]}", flush=True)
-    if (seed - args.first) % 25 == 24:
-        print(f"... {seed - args.first + 1} worlds, {fails} failures, {time.time() - t0:.0f}s, paths {stats}", flush=True)
-print(f"DONE: {args.seeds} worlds, {fails} failures, paths {stats}, {time.time() - t0:.0f}s")
-sys.exit(1 if fails else 0)
+        if big and builder == 3:
+            W, H, spp = min(W, 40), min(H, 24), min(spp, 3)   # (a 2000-sphere list costs the CPU oracle 2000 sphere tests per ray)
+            r = p.Renderer.MakeRenderer(W, H, spp, depth, cam, w, variant=variant)
+            r.Render(); img = r.DownloadRenderbuffer(); r.close()
+        ref, _ = O.render(as_oracle_world(w), as_oracle_camera(cam), W, H, spp, depth)
+        stats["baseline" if info["variant"] == 1 else ("xchg" if info["variant"] == 5 else ("lds" if info["lds_resident"] else "global"))] += 1
+        if s.n_triangles():
+            stats["triangle_worlds"] += 1
+            stats["tri_kernels"] += int(tri_kernel)
+        if w.traversal:
+            stats[("queue", "wide4")[w.traversal - 1]] = stats.get(("queue", "wide4")[w.traversal - 1], 0) + 1
+        if info["variant"] == 6:   # tolerance mode: inside |delta| < 1e-3; frames that are not the oracle's bits are counted
+            same = bits_equal(img, ref)
+            stats["tol_frames_not_bit_identical"] = stats.get("tol_frames_not_bit_identical", 0) + (0 if same else 1)
+            dmax = 0.0 if same else float(np.nanmax(np.abs(img - ref)))
+            stats["tol_max_abs_delta"] = max(stats.get("tol_max_abs_delta", 0.0), dmax)
+            ok = np.array_equal(np.isnan(img), np.isnan(ref)) and dmax < 1e-3
+        elif info["variant"] == 1:
+            ok = np.array_equal(np.isnan(img), np.isnan(ref)) and float(np.nanmax(np.abs(img - ref))) <= 1e-5 * max(1.0, float(np.nanmax(ref)))
+        else:
+            ok = bits_equal(img, ref)
+        if not ok:
+            fails += 1
+            bad = int((img.view(np.uint32) != ref.view(np.uint32)).sum())
+            print(f"FAIL seed {seed}: kinds {kinds} triangles {s.n_triangles()} builder {builder} big {big} cam {ck} {W}x{H}x{spp} depth {depth} info {info}: {bad} words differ", flush=True)
+        if ok and kinds >= 1 and info["variant"] in (2, 3):   # light sampling as one more feature of the case
+            ls = light_sampling_check(p, s, w, cam, ck, W, H, depth, variant)
+            if ls is not None:
+                stats["light_sampling"] = stats.get("light_sampling", 0) + 1
+                if not ls[0]:
+                    fails += 1
+                    print(f"FAIL seed {seed} with light sampling: kinds {kinds} builder {builder} big {big} cam {ck} depth {depth} forms {ls[1]}", flush=True)
+        if (seed - args.first) % 25 == 24:
+            print(f"... {seed - args.first + 1} worlds, {fails} failures, {time.time() - t0:.0f}s, paths {stats}", flush=True)
+    print(f"DONE: {args.seeds} worlds, {fails} failures, paths {stats}, {time.time() - t0:.0f}s")
+    return 1 if fails else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
