@@ -481,9 +481,10 @@ int rt_renderer_denoise_download(rt_renderer* r, float* host_rgba, size_t n_floa
  * state as rt_renderer_set_camera with other bytes does.  RT_ERR_INVALID, with the cause in rt_last_error: no quad light; more than
  * RT_MAX_LIGHTS; a renderer on variant 1, 5 or 6; a world with a queue or wide4 traversal; a world with a constant medium.            */
 #define RT_MAX_LIGHTS 16
-/* on: RT_LIGHT_SAMPLING_OFF (0), RT_LIGHT_SAMPLING_QUADS (1, the estimator above) or RT_LIGHT_SAMPLING_ALL (2, below); more is refused */
+/* on: RT_LIGHT_SAMPLING_OFF (0), RT_LIGHT_SAMPLING_QUADS (1, the estimator above), RT_LIGHT_SAMPLING_ALL (2, below) or RT_LIGHT_SAMPLING_MESH (4, further
+ * below); every other value — 3 too, which is no mode — is refused */
 int rt_renderer_light_sampling_enable(rt_renderer* r, uint32_t on);
-/* out[0] = the mode (RT_LIGHT_SAMPLING_OFF / _QUADS / _ALL), out[1] = n_l of that mode's table — off: of the quad lights, as ever — (0 when the
+/* out[0] = the mode (RT_LIGHT_SAMPLING_OFF / _QUADS / _ALL / _MESH), out[1] = n_l of that mode's table — off: of the quad lights, as ever — (0 when the
  * world cannot be light-sampled)                                                                     */
 int rt_renderer_light_sampling_info(rt_renderer* r, uint32_t out[2]);
 /* HOST (no GPU): the light table of a world as rt_renderer_light_sampling_enable would take it — quad index and area of light i < *out_n —
@@ -514,6 +515,26 @@ int rt_world_quad_lights(const rt_world_flat* w, uint32_t out_quad[RT_MAX_LIGHTS
  * the world's own reason for refusal.                                                                                                    */
 int rt_world_lights(const rt_world_flat* w, uint32_t mode, uint32_t out_kind[RT_MAX_LIGHTS], uint32_t out_index[RT_MAX_LIGHTS],
                     float out_area[RT_MAX_LIGHTS], uint32_t* out_n);
+
+/* Triangle and mesh lights too: mode RT_LIGHT_SAMPLING_MESH of rt_renderer_light_sampling_enable (opt-in beside modes 1 and 2, which stay what they are;
+ * in those a triangle with a light material emits when hit and is not sampled).  Lights of mode 4: first mode 2's list in mode 2's order (quad lights, then
+ * static sphere lights), then every quad of kind RT_QUAD_TRIANGLE whose material is RT_MAT_DIFFUSE_LIGHT, in quad-index order — kind RT_LIGHT_TRIANGLE,
+ * index = its quad index, area = 0.5f * sqrtf(dot(n, n)), n = cross(u, v), in fp32.  1 <= n_l <= RT_MAX_LIGHTS_MESH over the three kinds together (a cap,
+ * not a tuning result: the density step is linear in n_l); RT_MAX_LIGHTS keeps governing modes 1 and 2.  The draw order is mode 1's: c; if c < 0.5f the
+ * index i; a quad and a sphere as in mode 2; a triangle draws a = next, b = next, then  if (a + b > 1.0f) { a = 1.0f - a; b = 1.0f - b; }  — the test is
+ * one fp32 add, a sum of exactly 1 is not folded — and d = ((Q_i + u_i * a) + v_i * b) - hit_p, not normalised; it draws no on-unit vector.  Densities:
+ * quad and sphere lights as in mode 2; a triangle light j: the library's own quad test with kind RT_QUAD_TRIANGLE on the ray (hit_p, d) over a fresh
+ * trace's interval gives t or a miss:  pl_j = ((t * t) * len2) / ((fabs(dot(d, normal_j)) / len) * area_j) or 0 — 0 also for a drawn point that rounding
+ * put just outside its own triangle: the direction is still taken, as mode 1 does at a quad's edge.  A closed emissive mesh needs nothing of its own: a ray
+ * through it crosses two table entries and both contribute, as both crossings of a sphere do.  pl, pdf, the sp == 0 / !(pdf > 0) rule, the weight and the
+ * new ray are mode 1's.  Refused as mode 2 is, with two messages of its own: no light to sample; more than RT_MAX_LIGHTS_MESH lights.                  */
+#define RT_LIGHT_SAMPLING_MESH 4
+#define RT_LIGHT_TRIANGLE 2
+#define RT_MAX_LIGHTS_MESH 64
+/* HOST (no GPU): the light table of `mode` into arrays of `capacity` entries.  RT_LIGHT_SAMPLING_QUADS and RT_LIGHT_SAMPLING_ALL: exactly what rt_world_lights
+ * gives, refusals included (capacity >= their n_l).  RT_LIGHT_SAMPLING_MESH: the table above (RT_LIGHT_TRIANGLE: index is a quad index).  A table larger
+ * than `capacity` is RT_ERR_INVALID.                                                                                                                     */
+int rt_world_light_table(const rt_world_flat* w, uint32_t mode, uint32_t capacity, uint32_t* out_kind, uint32_t* out_index, float* out_area, uint32_t* out_n);
 
 /* ------------------------------------------------------------------ */
 /* Multi-GPU renderer — the same three entry points (Renderer.h:38-46)  */

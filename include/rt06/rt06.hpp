@@ -466,7 +466,7 @@ struct MotionBlurCamera {
 };
 
 // the modes of Renderer::SetLightSampling (RT_LIGHT_SAMPLING_* of rt06.h)
-enum class LightSampling : uint32_t { Off = RT_LIGHT_SAMPLING_OFF, Quads = RT_LIGHT_SAMPLING_QUADS, All = RT_LIGHT_SAMPLING_ALL };
+enum class LightSampling : uint32_t { Off = RT_LIGHT_SAMPLING_OFF, Quads = RT_LIGHT_SAMPLING_QUADS, All = RT_LIGHT_SAMPLING_ALL, Mesh = RT_LIGHT_SAMPLING_MESH };
 
 // ----------------------------------------------------------------------------------------------------
 // Renderer — main/src/Renderer.h:12-47
@@ -606,7 +606,8 @@ public:
         if (m.mr) rt06::check(rt_multi_renderer_light_sampling_enable(m.mr, on ? 1u : 0u), "Renderer::SetLightSampling");
         else rt06::check(rt_renderer_light_sampling_enable(m.r, on ? 1u : 0u), "Renderer::SetLightSampling");
     }
-    // Off, the quad lights (what SetLightSampling(true) selects), or the quad and the sphere lights (RT_LIGHT_SAMPLING_ALL)
+    // Off, the quad lights (what SetLightSampling(true) selects), the quad and the sphere lights (RT_LIGHT_SAMPLING_ALL), or those and the triangle lights of
+    // an emissive mesh (RT_LIGHT_SAMPLING_MESH)
     void SetLightSampling(LightSampling mode) {
         if (m.mr) rt06::check(rt_multi_renderer_light_sampling_enable(m.mr, (uint32_t)mode), "Renderer::SetLightSampling");
         else rt06::check(rt_renderer_light_sampling_enable(m.r, (uint32_t)mode), "Renderer::SetLightSampling");

@@ -254,6 +254,15 @@ class Scene:
         w = self.getWorldPtr()
         return self._arr(w.quads, w.n_quads, capi.QUAD_DT)
 
+    def light_table(self, mode):
+        """(kind, index, area) arrays of the light table of `mode` ("quads" / 1, "all" / 2, "mesh" / 4) as rt_renderer_light_sampling_enable would take it
+        (rt_world_light_table; no GPU); RtError with the world's own reason where it refuses."""
+        cap = 64   # RT_MAX_LIGHTS_MESH
+        kind, index, area, n = (C.c_uint32 * cap)(), (C.c_uint32 * cap)(), (C.c_float * cap)(), C.c_uint32(0)
+        w = self.getWorldPtr()
+        check(lib().rt_world_light_table(C.byref(w), light_sampling_mode(mode), cap, kind, index, area, C.byref(n)))
+        return (np.array(kind[: n.value], np.uint32), np.array(index[: n.value], np.uint32), np.array(area[: n.value], np.float32))
+
     def perlin_bytes(self):
         w = self.getWorldPtr()
         return bytes((C.c_char * 6144).from_address(w.perlin)) if w.perlin else b""
@@ -274,12 +283,15 @@ class Scene:
             pass
 
 
+LIGHT_SAMPLING_MODES = {"off": 0, "quads": 1, "all": 2, "mesh": 4}   # RT_LIGHT_SAMPLING_*
+
+
 def light_sampling_mode(on):
-    """False / 0 / "off" -> 0, True / 1 / "quads" -> 1, 2 / "all" -> 2 (RT_LIGHT_SAMPLING_*)"""
+    """False / 0 / "off" -> 0, True / 1 / "quads" -> 1, 2 / "all" -> 2, 4 / "mesh" -> 4 (RT_LIGHT_SAMPLING_*)"""
     if isinstance(on, str):
-        if on not in ("off", "quads", "all"):
-            raise ValueError(f"light sampling mode {on!r}: one of 'off', 'quads', 'all'")
-        return ("off", "quads", "all").index(on)
+        if on not in LIGHT_SAMPLING_MODES:
+            raise ValueError(f"light sampling mode {on!r}: one of 'off', 'quads', 'all', 'mesh'")
+        return LIGHT_SAMPLING_MODES[on]
     return int(on)
 
 
@@ -381,17 +393,18 @@ class Renderer:
 
     def light_sampling(self, on=True):
         """Next-event estimation from the next launch on (rt_renderer_light_sampling_enable); a change restarts the refinement.
-        False / 0 / "off": off; True / 1 / "quads": over the world's quad lights; 2 / "all": over its quad and sphere lights."""
+        False / 0 / "off": off; True / 1 / "quads": over the world's quad lights; 2 / "all": over its quad and sphere lights; 4 / "mesh": over its quad,
+        sphere and triangle lights (an emissive mesh)."""
         check(lib().rt_renderer_light_sampling_enable(self.h, light_sampling_mode(on)))
 
     def light_sampling_mode(self):
-        """0 (off), 1 (quad lights) or 2 (quad and sphere lights): the mode the next launch runs in."""
+        """0 (off), 1 (quad lights), 2 (quad and sphere lights) or 4 (quad, sphere and triangle lights): the mode the next launch runs in."""
         out = (C.c_uint32 * 2)()
         check(lib().rt_renderer_light_sampling_info(self.h, out))
         return out[0]
 
     def light_sampling_info(self):
-        """{'enabled', 'lights'}: whether light sampling is on (in either mode: light_sampling_mode() tells which), and the number of lights in the
+        """{'enabled', 'lights'}: whether light sampling is on (in any mode: light_sampling_mode() tells which), and the number of lights in the
         mode's table — off: of quad lights — (0: the world cannot be light-sampled)."""
         out = (C.c_uint32 * 2)()
         check(lib().rt_renderer_light_sampling_info(self.h, out))

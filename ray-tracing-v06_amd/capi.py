@@ -83,7 +83,7 @@ SYMBOLS = [
     "rt_renderer_aov_enable", "rt_renderer_aov_info", "rt_renderer_aov_download", "rt_denoise_params_default", "rt_renderer_denoise",
     "rt_renderer_denoise_async", "rt_renderer_denoise_download",
     "rt_renderer_light_sampling_enable", "rt_renderer_light_sampling_info", "rt_multi_renderer_light_sampling_enable", "rt_world_quad_lights",
-    "rt_renderer_kernel_form", "rt_world_lights", "rt_scene_cornell_lamp",
+    "rt_renderer_kernel_form", "rt_world_lights", "rt_scene_cornell_lamp", "rt_world_light_table",
     "rt_scene_add_triangle", "rt_scene_add_mesh", "rt_world_triangles", "rt_renderer_kernel_triangles",
 ]
 
@@ -215,6 +215,7 @@ def lib():
     L.rt_multi_renderer_light_sampling_enable.argtypes = [C.c_void_p, C.c_uint32]
     L.rt_world_quad_lights.argtypes = [P(WorldFlat), C.c_uint32 * 16, C.c_float * 16, P(C.c_uint32)]
     L.rt_world_lights.argtypes = [P(WorldFlat), C.c_uint32, C.c_uint32 * 16, C.c_uint32 * 16, C.c_float * 16, P(C.c_uint32)]
+    L.rt_world_light_table.argtypes = [P(WorldFlat), C.c_uint32, C.c_uint32, P(C.c_uint32), P(C.c_uint32), P(C.c_float), P(C.c_uint32)]
     L.rt_multi_renderer_create.argtypes = [P(RenderConfig), P(Camera), P(WorldFlat), C.c_uint32, C.c_void_p, P(C.c_void_p)]
     L.rt_multi_renderer_destroy.argtypes = [C.c_void_p]
     L.rt_multi_renderer_destroy.restype = None

@@ -186,14 +186,15 @@ struct rt_renderer {
     bool aov_on = false;
     uint32_t aov_max = 0, aov_done = 0;
     const char* aov_refused = nullptr;   // the first material of the world the feature pass does not cover (a medium, a noise or an image texture)
-    // light sampling (rt_renderer_light_sampling_enable): per mode (tab[mode - 1]) the world's lights as rt_world_lights gave them at creation (or why it gave
-    // none) and — from the first enable of that mode — the scene image with its light table behind it and the LDS that takes; one NEE form of this renderer's
-    // kernel serves both modes (they differ only in what the table holds)
-    struct LightTable { uint32_t n = 0, kind[RT_MAX_LIGHTS] = {}, index[RT_MAX_LIGHTS] = {}; float area[RT_MAX_LIGHTS] = {}, sphere[RT_MAX_LIGHTS][4] = {}; std::string refused;
-                        DevBuf blob; uint32_t table_vec4 = 0, lds_bytes = 0, blocks_per_cu = 0; bool built = false; };
-    struct { uint32_t mode = RT_LIGHT_SAMPLING_OFF; LightTable tab[2]; const void* kernel = nullptr;
+    // light sampling (rt_renderer_light_sampling_enable): per mode (tab[slot(mode)]) the world's lights as rt_world_light_table gave them at creation (or why it
+    // gave none) and — from the first enable of that mode — the scene image with its light table behind it and the LDS that takes; one NEE form of this renderer's
+    // kernel serves all three modes (they differ only in what the table holds)
+    struct LightTable { uint32_t n = 0, kind[RT_MAX_LIGHTS_MESH] = {}, index[RT_MAX_LIGHTS_MESH] = {}; float area[RT_MAX_LIGHTS_MESH] = {}, sphere[RT_MAX_LIGHTS_MESH][4] = {};
+                        std::string refused; DevBuf blob; uint32_t table_vec4 = 0, lds_bytes = 0, blocks_per_cu = 0; bool built = false; };
+    struct { uint32_t mode = RT_LIGHT_SAMPLING_OFF; LightTable tab[3]; const void* kernel = nullptr;
              bool on() const { return mode != RT_LIGHT_SAMPLING_OFF; }
-             const LightTable& cur() const { return tab[mode - 1u]; } } nee;
+             static uint32_t slot(uint32_t m) { return m == RT_LIGHT_SAMPLING_MESH ? 2u : m - 1u; }   // modes 1, 2, 4
+             const LightTable& cur() const { return tab[slot(mode)]; } } nee;
     // denoiser (rt_renderer_denoise): guide records, the two colour buffers the iterations ping-pong, the output frame; allocated at first use
     DevBuf dn_g0, dn_g1, dn_a, dn_b, dn_out;
     // ordering between refine steps and the filter, whichever streams the caller gives them: refine_ev = end of the last refine step (the filter
@@ -536,9 +537,9 @@ extern "C" int rt_renderer_create(const rt_render_config* cfg, const rt_camera* 
         else if (t == RT_MAT_LAMBERTIAN_NOISE) r->aov_refused = "a noise texture (RT_MAT_LAMBERTIAN_NOISE)";
         else if (t == RT_MAT_LAMBERTIAN_IMAGE) r->aov_refused = "an image texture (RT_MAT_LAMBERTIAN_IMAGE)";
     }
-    for (uint32_t mode = RT_LIGHT_SAMPLING_QUADS; mode <= RT_LIGHT_SAMPLING_ALL; mode++) {
-        rt_renderer::LightTable& t = r->nee.tab[mode - 1u];
-        if (rt_world_lights(world, mode, t.kind, t.index, t.area, &t.n) != RT_OK) { t.refused = rt_last_error(); t.n = 0; }
+    for (const uint32_t mode : {RT_LIGHT_SAMPLING_QUADS, RT_LIGHT_SAMPLING_ALL, RT_LIGHT_SAMPLING_MESH}) {
+        rt_renderer::LightTable& t = r->nee.tab[r->nee.slot(mode)];
+        if (rt_world_light_table(world, mode, RT_MAX_LIGHTS_MESH, t.kind, t.index, t.area, &t.n) != RT_OK) { t.refused = rt_last_error(); t.n = 0; }
         for (uint32_t i = 0; i < t.n; i++)
             if (t.kind[i] == RT_LIGHT_SPHERE) {   // the world's arrays are borrowed during creation only: what the table says of a sphere is taken now
                 const rt_prim& pr = world->prims[t.index[i]];
@@ -625,19 +626,21 @@ extern "C" int rt_renderer_set_camera(rt_renderer* r, const rt_camera* cam) {
 }
 
 // Light sampling.  Off: every launch is what it was.  On: the NEE form of the renderer's own kernel, on a copy of the scene image that ends with the light table
-// of the mode: a header (n_l, -, -, -), n_l entries (index, area, kind, -), and — mode RT_LIGHT_SAMPLING_ALL — n_l more (Cx, Cy, Cz, r), zeros for a quad.
+// of the mode: a header (n_l, -, -, -), n_l entries (index, area, kind, -), and — modes RT_LIGHT_SAMPLING_ALL and RT_LIGHT_SAMPLING_MESH — n_l more
+// (Cx, Cy, Cz, r), zeros for a quad and for a triangle.
 extern "C" int rt_renderer_light_sampling_enable(rt_renderer* r, uint32_t on) {
     if (!r) return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: null renderer");
-    if (on > RT_LIGHT_SAMPLING_ALL) return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: on must be 0 (off), 1 (quad lights) or 2 (quad and sphere lights)");
+    if (on > RT_LIGHT_SAMPLING_ALL && on != RT_LIGHT_SAMPLING_MESH)   // 3 is no mode
+        return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: on must be 0 (off), 1 (quad lights), 2 (quad and sphere lights) or 4 (quad, sphere and triangle lights)");
     if (on == r->nee.mode) return RT_OK;   // nothing changes, the refinement goes on
     if (on) {
-        rt_renderer::LightTable& t = r->nee.tab[on - 1u];
+        rt_renderer::LightTable& t = r->nee.tab[r->nee.slot(on)];
         if (r->variant < 2 || r->variant == 5 || r->tol)
             return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: kernel variant %u has no light-sampling form (the baseline kernel 1, the ray exchange 5 and the tolerance mode 6 do not; use variant 0, 2 or 3)", r->tol ? 6u : r->variant);
         if (!t.refused.empty()) return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: %s", t.refused.c_str());
         HIP_TRY(hipSetDevice(r->cfg.device));
         if (!t.built) {   // set last: a failure on the way is tried again
-            const uint32_t table_vec4 = 1u + t.n * (on == RT_LIGHT_SAMPLING_ALL ? 2u : 1u);
+            const uint32_t table_vec4 = 1u + t.n * (on == RT_LIGHT_SAMPLING_QUADS ? 1u : 2u);
             PackedSceneRef with_table = r->scene.packed;
             with_table.blob_vec4 += table_vec4;
             const uint32_t lds = (uint32_t)stream_kernel_lds_bytes(r->stream_block, with_table, r->scene.big, r->scene.wide, r->n_top);
@@ -654,7 +657,7 @@ extern "C" int rt_renderer_light_sampling_enable(rt_renderer* r, uint32_t on) {
             HIP_TRY(t.blob.alloc(((size_t)r->scene.packed.blob_vec4 + table_vec4) * sizeof(uint4)));
             HIP_TRY(hipMemcpy(t.blob.p, r->scene.blob.p, (size_t)r->scene.packed.blob_vec4 * sizeof(uint4), hipMemcpyDeviceToDevice));
             HIP_TRY(hipMemcpy(t.blob.as<uint4>() + r->scene.packed.blob_vec4, table.data(), table.size() * sizeof(uint4), hipMemcpyHostToDevice));
-            const uint32_t lds_set = std::max(lds, std::max(r->nee.tab[0].lds_bytes, r->nee.tab[1].lds_bytes));   // one kernel, two tables: the attribute covers the larger
+            const uint32_t lds_set = std::max({lds, r->nee.tab[0].lds_bytes, r->nee.tab[1].lds_bytes, r->nee.tab[2].lds_bytes});   // one kernel, three tables: the attribute covers the largest
             HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_set));
             t.table_vec4 = table_vec4;
             t.lds_bytes = lds;
@@ -671,7 +674,7 @@ extern "C" int rt_renderer_light_sampling_enable(rt_renderer* r, uint32_t on) {
 
 extern "C" int rt_renderer_light_sampling_info(rt_renderer* r, uint32_t out[2]) {
     if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_info: null argument");
-    const rt_renderer::LightTable& t = r->nee.tab[r->nee.on() ? r->nee.mode - 1u : 0u];
+    const rt_renderer::LightTable& t = r->nee.tab[r->nee.on() ? r->nee.slot(r->nee.mode) : 0u];
     out[0] = r->nee.mode;
     out[1] = t.refused.empty() ? t.n : 0u;
     return RT_OK;

@@ -561,8 +561,10 @@ extern "C" int rt_world_triangles(const rt_world_flat* w, uint32_t* out_n) {
     *out_n = n;
     return RT_OK;
 }
+// with_triangles: behind those, the triangles whose material is a diffuse light, in quad-index order, area = 0.5f * sqrtf(dot(n, n)).  `cap`
+// is where `many` is said: RT_MAX_LIGHTS, or RT_MAX_LIGHTS_MESH for the table with triangles.
 static int world_lights(const rt_world_flat* w, bool with_spheres, const char* none, const char* many, uint32_t* out_kind, uint32_t* out_index, float* out_area,
-                        uint32_t* out_n) {
+                        uint32_t* out_n, bool with_triangles = false, uint32_t cap = RT_MAX_LIGHTS) {
     if (w->traversal != RT_TRAVERSAL_STACK)
         return rt_fail(RT_ERR_INVALID, "light sampling: the world has a queue or wide4 traversal (RT_TRAVERSAL_QUEUE, RT_TRAVERSAL_WIDE4); the light-sampling kernels walk the tree with the stack");
     for (uint32_t i = 0; i < w->n_materials; i++)
@@ -574,7 +576,7 @@ static int world_lights(const rt_world_flat* w, bool with_spheres, const char* n
         const rt_quad& q = w->quads[i];
         if (q.mat >= w->n_materials) return rt_fail(RT_ERR_INVALID, "quad %u: material index out of range", i);
         if (w->materials[q.mat].type != RT_MAT_DIFFUSE_LIGHT || q.kind == RT_QUAD_TRIANGLE) continue;   // a triangle light emits when hit and is not sampled (§18)
-        if (n == RT_MAX_LIGHTS) return rt_fail(RT_ERR_INVALID, "%s", many);
+        if (n == cap) return rt_fail(RT_ERR_INVALID, "%s", many);
         const f3 nrm = cross(mk3(q.u[0], q.u[1], q.u[2]), mk3(q.v[0], q.v[1], q.v[2]));
         if (out_kind) out_kind[n] = RT_LIGHT_QUAD;
         out_index[n] = i;
@@ -586,10 +588,20 @@ static int world_lights(const rt_world_flat* w, bool with_spheres, const char* n
         const uint32_t mat = pr.mat & ~RT_PRIM_MOVING;
         if (mat >= w->n_materials) return rt_fail(RT_ERR_INVALID, "primitive %u: material index out of range", i);
         if (w->materials[mat].type != RT_MAT_DIFFUSE_LIGHT || (pr.mat & RT_PRIM_MOVING) || !(pr.radius > 0.0f)) continue;
-        if (n == RT_MAX_LIGHTS) return rt_fail(RT_ERR_INVALID, "%s", many);
+        if (n == cap) return rt_fail(RT_ERR_INVALID, "%s", many);
         if (out_kind) out_kind[n] = RT_LIGHT_SPHERE;
         out_index[n] = i;
         out_area[n] = (12.566371f * pr.radius) * pr.radius;
+        n++;
+    }
+    for (uint32_t i = w->n_quads - n_tris; with_triangles && i < w->n_quads; i++) {
+        const rt_quad& q = w->quads[i];
+        if (w->materials[q.mat].type != RT_MAT_DIFFUSE_LIGHT) continue;   // q.mat was checked above
+        if (n == cap) return rt_fail(RT_ERR_INVALID, "%s", many);
+        const f3 nrm = cross(mk3(q.u[0], q.u[1], q.u[2]), mk3(q.v[0], q.v[1], q.v[2]));
+        if (out_kind) out_kind[n] = RT_LIGHT_TRIANGLE;
+        out_index[n] = i;
+        out_area[n] = 0.5f * sqrtf(dot(nrm, nrm));
         n++;
     }
     if (n == 0) return rt_fail(RT_ERR_INVALID, "%s", none);
@@ -620,6 +632,31 @@ extern "C" int rt_world_lights(const rt_world_flat* w, uint32_t mode, uint32_t o
     if ((w->n_quads && !w->quads) || (w->n_materials && !w->materials) || (w->n_prims && !w->prims)) return rt_fail(RT_ERR_INVALID, "rt_world_lights: world array is null");
     return world_lights(w, true, "light sampling: the world has no light to sample (a quad or a static sphere of radius > 0 whose material is RT_MAT_DIFFUSE_LIGHT)",
                         "light sampling: the world has more than 16 lights (quads and static spheres whose material is RT_MAT_DIFFUSE_LIGHT)", out_kind, out_index, out_area, out_n);
+}
+
+// The light table of any mode, into the caller's arrays of `capacity` entries.  Modes 1 and 2: rt_world_lights' own answer, through arrays of its size.  Mode
+// RT_LIGHT_SAMPLING_MESH: mode 2's list, then the triangle lights.
+static_assert(RT_MAX_LIGHTS_MESH == 64, "the refusal message below says 64");
+extern "C" int rt_world_light_table(const rt_world_flat* w, uint32_t mode, uint32_t capacity, uint32_t* out_kind, uint32_t* out_index, float* out_area, uint32_t* out_n) {
+    if (!w || !out_kind || !out_index || !out_area || !out_n) return rt_fail(RT_ERR_INVALID, "rt_world_light_table: null argument");
+    *out_n = 0;
+    if (mode != RT_LIGHT_SAMPLING_QUADS && mode != RT_LIGHT_SAMPLING_ALL && mode != RT_LIGHT_SAMPLING_MESH)
+        return rt_fail(RT_ERR_INVALID, "rt_world_light_table: mode must be RT_LIGHT_SAMPLING_QUADS (1), RT_LIGHT_SAMPLING_ALL (2) or RT_LIGHT_SAMPLING_MESH (4)");
+    uint32_t kind[RT_MAX_LIGHTS_MESH], index[RT_MAX_LIGHTS_MESH], n = 0;
+    float area[RT_MAX_LIGHTS_MESH];
+    if (mode != RT_LIGHT_SAMPLING_MESH) {
+        if (int rc = rt_world_lights(w, mode, kind, index, area, &n)) return rc;
+    } else {
+        if ((w->n_quads && !w->quads) || (w->n_materials && !w->materials) || (w->n_prims && !w->prims)) return rt_fail(RT_ERR_INVALID, "rt_world_light_table: world array is null");
+        if (int rc = world_lights(w, true, "light sampling: the world has no light to sample (a quad, a triangle or a static sphere of radius > 0 whose material is RT_MAT_DIFFUSE_LIGHT)",
+                                  "light sampling: the world has more than 64 lights (quads, triangles and static spheres whose material is RT_MAT_DIFFUSE_LIGHT)", kind, index, area, &n,
+                                  true, RT_MAX_LIGHTS_MESH))
+            return rc;
+    }
+    if (n > capacity) return rt_fail(RT_ERR_INVALID, "rt_world_light_table: the table has %u lights, the caller's arrays hold %u", n, capacity);
+    for (uint32_t i = 0; i < n; i++) { out_kind[i] = kind[i]; out_index[i] = index[i]; out_area[i] = area[i]; }
+    *out_n = n;
+    return RT_OK;
 }
 
 extern "C" int rt_scene_set_perlin(rt_scene* s, uint64_t seed) {

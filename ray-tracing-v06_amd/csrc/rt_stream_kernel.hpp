@@ -210,9 +210,10 @@ __device__ __forceinline__ WideNodeData fetch_wide_node(const char* nodes, const
 //      measured in one instantiation with the quads, the extra compare and add cost the Cornell box 1.0 % (EXPERIMENTS.md E9), so worlds without triangles keep
 //      the kernels they had, instruction for instruction.
 // NEE (rt_renderer_light_sampling_enable, opt-in; EXT >= 1 only): a Lambertian / checker hit draws its next direction from the mixture of its own cosine
-//      distribution and a distribution over the world's lights, and weighs the path by the ratio of the densities (DESIGN.md §16, §17).  The light table —
+//      distribution and a distribution over the world's lights, and weighs the path by the ratio of the densities (DESIGN.md §16, §17, §19).  The light table —
 //      a header (n_l, -, -, -), then (index, area, kind, -) per light, then — only where a kind says sphere — (Cx, Cy, Cz, r) per light — lies behind the
 //      quads' shade records in the image the NEE launches are given, so it costs no kernel argument: the other instantiations neither see it nor pay for it.
+//      A kind RT_LIGHT_TRIANGLE (mode RT_LIGHT_SAMPLING_MESH) exists only in a world with triangles, so only the TRI && NEE forms hold code for it.
 template <bool EXACT, bool FILTER, int BLOCK, int WORLD = RT_WORLD_BVH, int EXT = 0, bool BIG = false, bool WIDE = BIG, bool TOL = false, bool NEE = false, bool TRI = false>
 __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(StreamParams p) {
     static_assert(!NEE || (EXT >= 1 && WORLD != RT_WORLD_BVH_QUEUE), "light sampling: worlds with quads, walked by the stack or as a list");
@@ -620,13 +621,19 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                     f3 on_unit = mk3(0.0f);
                     uint32_t nee_li = 0u, nee_quad = 0u;   // NEE, light half: the light drawn, and its quad index
                     bool to_sphere = false;                // ... or that it is a sphere light (§17), whose point is C + on_unit * r: the draw below serves it too
+                    bool to_tri = false;                   // ... or a triangle light (§19, TRI only): a quad's two draws, folded into the triangle
                     if (NEE && to_light) {
                         const float4* lights = quads + p.scene.n_quads * 5u;
                         const uint32_t n_l = __float_as_uint(lights[0].x);
                         if (n_l > 1u) nee_li = min((uint32_t)(rng.next() * (float)n_l), n_l - 1u);
                         const float4 le = lights[1u + nee_li];
                         nee_quad = __float_as_uint(le.x);
-                        to_sphere = __float_as_uint(le.z) != 0u;
+                        if constexpr (TRI) {
+                            to_sphere = __float_as_uint(le.z) == RT_LIGHT_SPHERE;
+                            to_tri = __float_as_uint(le.z) == RT_LIGHT_TRIANGLE;
+                        } else {
+                            to_sphere = __float_as_uint(le.z) != 0u;
+                        }
                         if (to_sphere) nee_li += n_l;      // where its (Cx, Cy, Cz, r) lies behind the entries
                     }
                     if (!NEE || !to_light || to_sphere) on_unit = rng_on_unit3(rng);
@@ -642,8 +649,11 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                                 const float4 sc = (quads + p.scene.n_quads * 5u)[1u + nee_li];
                                 scatter_dir = (mk3(sc.x, sc.y, sc.z) + on_unit * sc.w) - hit_p;
                             } else {
-                            const float la = rng.next();
-                            const float lb = rng.next();
+                            float la = rng.next();
+                            float lb = rng.next();
+                            if constexpr (TRI) {
+                                if (to_tri && la + lb > 1.0f) { la = 1.0f - la; lb = 1.0f - lb; }   // one fp32 add decides; a sum of exactly 1 stays
+                            }
                             const float4* qd = quads + nee_quad * 4u;
                             const float4 a0 = qd[0], a1 = qd[1], a2 = qd[2];
                             scatter_dir = ((mk3(a0.x, a0.y, a0.z) + mk3(a1.x, a1.y, a1.z) * la) + mk3(a1.w, a2.x, a2.y) * lb) - hit_p;
@@ -666,7 +676,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                             for (uint32_t j = 0; j < n_l; j++) {
                                 const float4 lt = lights[1u + j];
                                 float pl_j = 0.0f;
-                                if (__float_as_uint(lt.z) != 0u) {
+                                if (TRI ? __float_as_uint(lt.z) == RT_LIGHT_SPHERE : __float_as_uint(lt.z) != 0u) {
                                     // a sphere light (§17): the area-uniform point's solid-angle density, summed over both crossings of the line through the
                                     // sphere; |n.d| = sqrt(disc) / r at both
                                     const float4 sc = lights[1u + n_l + j];
@@ -689,7 +699,8 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                                 const f3 ln = mk3(a2.z, a2.w, a3.x);
                                 HitRec tmp;
                                 tmp.distance = RT_MISS_DIST; tmp.normal = mk3(0.0f); tmp.prim = -1; tmp.mat = 0;
-                                if (quad_closest_intersection(mk3(a0.x, a0.y, a0.z), a0.w, mk3(a1.x, a1.y, a1.z), mk3(a1.w, a2.x, a2.y), ln, mk3(a3.y, a3.z, a3.w), 0u, 0, RT_QUAD_PARALLELOGRAM, lray, tmp))   // a light of the table is never a triangle
+                                if (quad_closest_intersection(mk3(a0.x, a0.y, a0.z), a0.w, mk3(a1.x, a1.y, a1.z), mk3(a1.w, a2.x, a2.y), ln, mk3(a3.y, a3.z, a3.w), 0u, 0,
+                                                              TRI && __float_as_uint(lt.z) == RT_LIGHT_TRIANGLE ? RT_QUAD_TRIANGLE : RT_QUAD_PARALLELOGRAM, lray, tmp))   // §19: a triangle light's area (lt.y) is half its parallelogram's
                                     pl_j = ((tmp.distance * tmp.distance) * len2) / ((fabsf(dot(d, ln)) / len) * lt.y);
                                 }
                                 pdf_light = pdf_light + pl_j;

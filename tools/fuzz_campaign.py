@@ -1,16 +1,18 @@
 #!/usr/bin/env python3
 """Differential fuzz campaign: random worlds (spheres, moving spheres, quads, triangles and meshes, lights, media, textures; every builder; LDS
 and global-memory paths; three cameras) rendered on the GPU and by the CPU oracle, compared bit for bit.
-    python tools/fuzz_campaign.py --seeds 200 [--first 0] [--no-triangles]
+    python tools/fuzz_campaign.py --seeds 200 [--first 0] [--no-triangles] [--mesh-lights]
 Prints one line per failure and a summary; exit code 1 if anything differed.  The triangles of a world come from a generator of their own, so the rest of a seed's
 world is what it was before the fuzzer made triangles, and --no-triangles renders exactly those earlier worlds.  Importing this file starts nothing:
-world_of_seed() builds a seed's world on the host, without a device."""
+world_of_seed() builds a seed's world on the host, without a device.  --mesh-lights (off by default: the recorded campaigns ran without it) also renders every
+world that RT_LIGHT_SAMPLING_MESH accepts in that mode; it draws nothing, so the worlds, frames and cameras of a seed stay what they are."""
 import argparse, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import __graft_entry__ as G
+import _mesh_light_twin as MT
 import _nee_twin as T
 import _oracle as O
 import _tri_twin as TT
@@ -27,6 +29,7 @@ def parse_args(argv=None):
     ap.add_argument("--variants", action="store_true", help="pick a random kernel variant (0..5) per world — variant 5 (ray exchange) with random roles / thresholds / ring pairs —, now and then a forced multi-pass cut; unsupported combinations are skipped")
     ap.add_argument("--force-variant", type=int, default=None, help="render every world with this kernel variant; 6 (tolerance mode) is held to |delta| < 1e-3 and its differing frames are counted, not failed")
     ap.add_argument("--no-triangles", action="store_true", help="the worlds as they were before the fuzzer made triangles, byte for byte")
+    ap.add_argument("--mesh-lights", action="store_true", help="also render the worlds that light-sampling mode 4 (triangle and mesh lights) accepts in that mode: both memory forms, and the twin where it follows")
     return ap.parse_args(argv)
 
 
@@ -99,8 +102,8 @@ def world_of_seed(p, seed, triangles=True, force_variant=None):
     return make_world(p, rng, tri_rng, force_variant) + (rng,)
 
 
-def light_sampling_check(p, s, w, cam, ck, W, H, depth, variant):
-    """A world rt_world_quad_lights accepts, with sampling on, at 4 spp on at most 48 x 32 pixels: the renderer's own form and the global-memory form must agree in
+def light_sampling_check(p, s, w, cam, ck, W, H, depth, variant, mode=1):
+    """A world rt_world_quad_lights accepts (mode 4, --mesh-lights: rt_world_light_table, and tests/_mesh_light_twin.py is the twin), with sampling on, at 4 spp on at most 48 x 32 pixels: the renderer's own form and the global-memory form must agree in
     every bit, and both must be the twin on every pixel it follows (pinhole cameras): tests/_nee_twin.py, or tests/_tri_twin.py for a world with triangles (static
     spheres and the stack walk only: another world with triangles is held across the two forms alone).  None: not applicable; else (ok, forms)."""
     W, H, spp = min(W, 48), min(H, 32), 4
@@ -110,9 +113,9 @@ def light_sampling_check(p, s, w, cam, ck, W, H, depth, variant):
         os.environ.update(env)
         try:
             r = p.Renderer.MakeRenderer(W, H, spp, depth, cam, w, variant=variant)
-            if not r.light_sampling_info()["lights"] or r.kernel_info()["variant"] not in (2, 3):
+            if (mode == 1 and not r.light_sampling_info()["lights"]) or r.kernel_info()["variant"] not in (2, 3):
                 return None
-            r.light_sampling(True)
+            r.light_sampling(mode)
         except p.capi.RtError:
             return None   # no kernel for the world, or no light-sampling form for it
         finally:
@@ -123,7 +126,11 @@ def light_sampling_check(p, s, w, cam, ck, W, H, depth, variant):
         r.close()
     ok = bits_equal(sums[0], sums[1])
     if ck == 0:
-        if not s.n_triangles():
+        if mode == 4:
+            if w.traversal != 0 or (s.arrays()[1]["mat"] >> 31).any():
+                return ok, forms
+            samples, followed = MT.frame_samples(as_oracle_world(w), as_oracle_camera(cam), W, H, spp, depth, 1984, mode=4)
+        elif not s.n_triangles():
             samples, followed = T.frame_samples(as_oracle_world(w), as_oracle_camera(cam), W, H, spp, depth, 1984, light_sampling=True)
         elif w.traversal == 0 and not (s.arrays()[1]["mat"] >> 31).any():
             samples, followed = TT.frame_samples(as_oracle_world(w), as_oracle_camera(cam), W, H, spp, depth, 1984, mode=1)
@@ -214,6 +221,12 @@ def main(argv=None):
                 if not ls[0]:
                     fails += 1
                     print(f"FAIL seed {seed} with light sampling: kinds {kinds} builder {builder} big {big} cam {ck} depth {depth} forms {ls[1]}", flush=True)
+            ls = light_sampling_check(p, s, w, cam, ck, W, H, depth, variant, mode=4) if args.mesh_lights else None
+            if ls is not None:
+                stats["mesh_light_sampling"] = stats.get("mesh_light_sampling", 0) + 1
+                if not ls[0]:
+                    fails += 1
+                    print(f"FAIL seed {seed} with light sampling mode 4: kinds {kinds} triangles {s.n_triangles()} builder {builder} big {big} cam {ck} depth {depth} forms {ls[1]}", flush=True)
         if (seed - args.first) % 25 == 24:
             print(f"... {seed - args.first + 1} worlds, {fails} failures, {time.time() - t0:.0f}s, paths {stats}", flush=True)
     print(f"DONE: {args.seeds} worlds, {fails} failures, paths {stats}, {time.time() - t0:.0f}s")
