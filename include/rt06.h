@@ -367,8 +367,13 @@ int rt_renderer_kernel_info(rt_renderer* r, uint32_t out[4]);
 int rt_renderer_kernel_form(rt_renderer* r, uint32_t out[9]);
 /* *out = 1 when the NEXT launch runs an instantiation of the streaming kernel's triangle family: the same nine arguments as above, plus the book's `tri`
  * interior test for the quads of kind RT_QUAD_TRIANGLE.  A world without triangles never does (it keeps the kernels it had); a world with triangles does
- * on every streaming variant but under the queue / wide4 traversal, whose lane walks — like the baseline kernel — read the kind from the flat record.   */
+ * on every streaming variant but under the queue / wide4 traversal, whose lane walks — like the baseline kernel — read the kind from the flat record.
+ * That holds for light-sampling modes 0 to 4.  Mode RT_LIGHT_SAMPLING_TREE has kernels in the triangle family only, so while it is on the answer is 1 for
+ * a world without triangles too (all its quads are plain ones: a valid world of that family).                                                           */
 int rt_renderer_kernel_triangles(rt_renderer* r, uint32_t* out);
+/* *out = 1 when the NEXT launch runs an instantiation of the light-tree family (mode RT_LIGHT_SAMPLING_TREE is on): rt_renderer_kernel_form's nine fields,
+ * with nee = 1, plus the tree walk and the choice by area.  A query of its own, so that the nine fields stay what they are.                              */
+int rt_renderer_kernel_light_tree(rt_renderer* r, uint32_t* out);
 /* Renderer::DownloadRenderbuffer (Renderer.cu:94-96): width*height*4 floats,
  * row-major, row 0 = bottom.  Only valid for world_size == 1.               */
 int rt_renderer_download(rt_renderer* r, float* host_rgba, size_t n_floats);
@@ -481,10 +486,10 @@ int rt_renderer_denoise_download(rt_renderer* r, float* host_rgba, size_t n_floa
  * state as rt_renderer_set_camera with other bytes does.  RT_ERR_INVALID, with the cause in rt_last_error: no quad light; more than
  * RT_MAX_LIGHTS; a renderer on variant 1, 5 or 6; a world with a queue or wide4 traversal; a world with a constant medium.            */
 #define RT_MAX_LIGHTS 16
-/* on: RT_LIGHT_SAMPLING_OFF (0), RT_LIGHT_SAMPLING_QUADS (1, the estimator above), RT_LIGHT_SAMPLING_ALL (2, below) or RT_LIGHT_SAMPLING_MESH (4, further
- * below); every other value — 3 too, which is no mode — is refused */
+/* on: RT_LIGHT_SAMPLING_OFF (0), RT_LIGHT_SAMPLING_QUADS (1, the estimator above), RT_LIGHT_SAMPLING_ALL (2, below), RT_LIGHT_SAMPLING_MESH (4, further
+ * below) or RT_LIGHT_SAMPLING_TREE (16, last below); every other value — 3 too, which is no mode — is refused */
 int rt_renderer_light_sampling_enable(rt_renderer* r, uint32_t on);
-/* out[0] = the mode (RT_LIGHT_SAMPLING_OFF / _QUADS / _ALL / _MESH), out[1] = n_l of that mode's table — off: of the quad lights, as ever — (0 when the
+/* out[0] = the mode (RT_LIGHT_SAMPLING_OFF / _QUADS / _ALL / _MESH / _TREE), out[1] = n_l of that mode's table — off: of the quad lights, as ever — (0 when the
  * world cannot be light-sampled)                                                                     */
 int rt_renderer_light_sampling_info(rt_renderer* r, uint32_t out[2]);
 /* HOST (no GPU): the light table of a world as rt_renderer_light_sampling_enable would take it — quad index and area of light i < *out_n —
@@ -535,6 +540,32 @@ int rt_world_lights(const rt_world_flat* w, uint32_t mode, uint32_t out_kind[RT_
  * gives, refusals included (capacity >= their n_l).  RT_LIGHT_SAMPLING_MESH: the table above (RT_LIGHT_TRIANGLE: index is a quad index).  A table larger
  * than `capacity` is RT_ERR_INVALID.                                                                                                                     */
 int rt_world_light_table(const rt_world_flat* w, uint32_t mode, uint32_t capacity, uint32_t* out_kind, uint32_t* out_index, float* out_area, uint32_t* out_n);
+
+/* A light tree and a choice by area: mode RT_LIGHT_SAMPLING_TREE of rt_renderer_light_sampling_enable (opt-in beside modes 1, 2 and 4, which
+ * stay what they are).  The lights are mode 4's, 1 <= n_l <= RT_MAX_LIGHTS_TREE (a cap, not a tuning result), PERMUTED into the leaf order of a bounding-volume
+ * tree built on the host:  box of a light = the box of its vertices (quad: Q, Q + u, Q + v, (Q + u) + v; triangle: the first three; sphere: C - r, C + r),
+ * widened on every side by pad = RT_LIGHT_TREE_PAD * M, M = the largest absolute coordinate of the world's bounds (a sphere by pad + (RT_LIGHT_TREE_PAD_SPHERE
+ * * (M * M)) / r);  centroid = (bmin + bmax) * 0.5f;  a range of one light is a leaf, any other is split on the longest axis of its centroids' bounds (ties: the
+ * lowest axis), stable-sorted by that coordinate (ties keep mode 4's order) and cut at a + (b - a) / 2.  Nodes are numbered in preorder, 2 n_l - 1 of them, each
+ * (min.xyz, skip) (max.xyz, leaf): skip = the first node behind the subtree, leaf = the light's position in the permuted table or 0xffffffff.  c_j = the
+ * sequential fp32 sum of the areas in table order, A = c_{n_l - 1}; a light with c_j == c_{j-1} is refused.
+ * Draws: c; if c < 0.5f a light: with n_l > 1, x = next * A and i = the smallest j with c_j > x (none: n_l - 1), no draw with one light; the point by mode 4's
+ * rule for the kind.  Density: len2, len, cosn, sp as ever; rd = 1.0f / d per component; the walk starts at node 0 and ends at node n_nodes; a node is ENTERED
+ * when tmin <= tmax * RT_LIGHT_TREE_K && tmax > 0, with ta = (min - hit_p) * rd, tb = (max - hit_p) * rd, tmin = the largest of the per-axis smaller, tmax = the
+ * smallest of the per-axis larger, every selection glm's `(y < x) ? y : x` / `(x < y) ? y : x` in x, y, z order (a NaN from 0 * inf is kept or dropped by its
+ * position in those; a NaN tmin or tmax enters nothing); an inner node entered goes to the next node, a leaf entered adds its term and goes to skip, a node
+ * not entered goes to skip.  The term of a leaf is mode 4's pl_j without the division by area_j; pl = (the sum in walk order) / A; pdf, the weight, the
+ * sp == 0 / !(pdf > 0) rule and the new ray are mode 1's.  A drawn sphere light that the walk did not credit with disc > 0 fails the scatter.
+ * Refused as mode 4 is, with messages of its own: no light to sample; more than RT_MAX_LIGHTS_TREE lights; a light whose area is lost in the running sum.  */
+#define RT_LIGHT_SAMPLING_TREE 16
+#define RT_MAX_LIGHTS_TREE 4096
+#define RT_LIGHT_TREE_PAD 0x1p-10f
+#define RT_LIGHT_TREE_PAD_SPHERE 0x1p-18f
+#define RT_LIGHT_TREE_K 0x1.0001p+0f
+/* HOST (no GPU): the tree of mode RT_LIGHT_SAMPLING_TREE over the table rt_world_light_table(w, RT_LIGHT_SAMPLING_TREE, ...) gives (which is the permuted one):
+ * 8 floats per node — min.xyz, skip (bits), max.xyz, leaf (bits) — into out_nodes, 2 n_l - 1 into *out_n_nodes, c_j of every light into out_cdf.  `capacity`
+ * counts lights: out_nodes holds 8 * (2 * capacity - 1) floats, out_cdf capacity.  Refused as the table is.                                                 */
+int rt_world_light_tree(const rt_world_flat* w, uint32_t capacity, float* out_nodes, uint32_t* out_n_nodes, float* out_cdf);
 
 /* ------------------------------------------------------------------ */
 /* Multi-GPU renderer — the same three entry points (Renderer.h:38-46)  */

@@ -466,7 +466,8 @@ struct MotionBlurCamera {
 };
 
 // the modes of Renderer::SetLightSampling (RT_LIGHT_SAMPLING_* of rt06.h)
-enum class LightSampling : uint32_t { Off = RT_LIGHT_SAMPLING_OFF, Quads = RT_LIGHT_SAMPLING_QUADS, All = RT_LIGHT_SAMPLING_ALL, Mesh = RT_LIGHT_SAMPLING_MESH };
+enum class LightSampling : uint32_t { Off = RT_LIGHT_SAMPLING_OFF, Quads = RT_LIGHT_SAMPLING_QUADS, All = RT_LIGHT_SAMPLING_ALL, Mesh = RT_LIGHT_SAMPLING_MESH,
+                                      Tree = RT_LIGHT_SAMPLING_TREE };
 
 // ----------------------------------------------------------------------------------------------------
 // Renderer — main/src/Renderer.h:12-47
@@ -607,7 +608,7 @@ public:
         else rt06::check(rt_renderer_light_sampling_enable(m.r, on ? 1u : 0u), "Renderer::SetLightSampling");
     }
     // Off, the quad lights (what SetLightSampling(true) selects), the quad and the sphere lights (RT_LIGHT_SAMPLING_ALL), or those and the triangle lights of
-    // an emissive mesh (RT_LIGHT_SAMPLING_MESH)
+    // an emissive mesh (RT_LIGHT_SAMPLING_MESH), or the same lights — up to RT_MAX_LIGHTS_TREE — chosen by area and found through a light tree (RT_LIGHT_SAMPLING_TREE)
     void SetLightSampling(LightSampling mode) {
         if (m.mr) rt06::check(rt_multi_renderer_light_sampling_enable(m.mr, (uint32_t)mode), "Renderer::SetLightSampling");
         else rt06::check(rt_renderer_light_sampling_enable(m.r, (uint32_t)mode), "Renderer::SetLightSampling");

@@ -255,13 +255,23 @@ class Scene:
         return self._arr(w.quads, w.n_quads, capi.QUAD_DT)
 
     def light_table(self, mode):
-        """(kind, index, area) arrays of the light table of `mode` ("quads" / 1, "all" / 2, "mesh" / 4) as rt_renderer_light_sampling_enable would take it
-        (rt_world_light_table; no GPU); RtError with the world's own reason where it refuses."""
-        cap = 64   # RT_MAX_LIGHTS_MESH
+        """(kind, index, area) arrays of the light table of `mode` ("quads" / 1, "all" / 2, "mesh" / 4, "tree" / 16: permuted into the tree's leaf order) as
+        rt_renderer_light_sampling_enable would take it (rt_world_light_table; no GPU); RtError with the world's own reason where it refuses."""
+        cap = 4096 if light_sampling_mode(mode) == 16 else 64   # RT_MAX_LIGHTS_TREE, RT_MAX_LIGHTS_MESH
         kind, index, area, n = (C.c_uint32 * cap)(), (C.c_uint32 * cap)(), (C.c_float * cap)(), C.c_uint32(0)
         w = self.getWorldPtr()
         check(lib().rt_world_light_table(C.byref(w), light_sampling_mode(mode), cap, kind, index, area, C.byref(n)))
         return (np.array(kind[: n.value], np.uint32), np.array(index[: n.value], np.uint32), np.array(area[: n.value], np.float32))
+
+    def light_tree(self):
+        """(nodes (2 n_l - 1, 8) float32 — min.xyz, skip bits, max.xyz, leaf bits —, cdf (n_l,) float32) of mode "tree" over light_table("tree")
+        (rt_world_light_tree; no GPU); RtError with the world's own reason where it refuses."""
+        cap = 4096   # RT_MAX_LIGHTS_TREE
+        nodes, cdf, n = (C.c_float * (8 * (2 * cap - 1)))(), (C.c_float * cap)(), C.c_uint32(0)
+        w = self.getWorldPtr()
+        check(lib().rt_world_light_tree(C.byref(w), cap, nodes, C.byref(n), cdf))
+        n_l = (n.value + 1) // 2
+        return np.array(nodes[: 8 * n.value], np.float32).reshape(n.value, 8), np.array(cdf[:n_l], np.float32)
 
     def perlin_bytes(self):
         w = self.getWorldPtr()
@@ -283,14 +293,14 @@ class Scene:
             pass
 
 
-LIGHT_SAMPLING_MODES = {"off": 0, "quads": 1, "all": 2, "mesh": 4}   # RT_LIGHT_SAMPLING_*
+LIGHT_SAMPLING_MODES = {"off": 0, "quads": 1, "all": 2, "mesh": 4, "tree": 16}   # RT_LIGHT_SAMPLING_*
 
 
 def light_sampling_mode(on):
-    """False / 0 / "off" -> 0, True / 1 / "quads" -> 1, 2 / "all" -> 2, 4 / "mesh" -> 4 (RT_LIGHT_SAMPLING_*)"""
+    """False / 0 / "off" -> 0, True / 1 / "quads" -> 1, 2 / "all" -> 2, 4 / "mesh" -> 4, 16 / "tree" -> 16 (RT_LIGHT_SAMPLING_*)"""
     if isinstance(on, str):
         if on not in LIGHT_SAMPLING_MODES:
-            raise ValueError(f"light sampling mode {on!r}: one of 'off', 'quads', 'all', 'mesh'")
+            raise ValueError(f"light sampling mode {on!r}: one of 'off', 'quads', 'all', 'mesh', 'tree'")
         return LIGHT_SAMPLING_MODES[on]
     return int(on)
 
@@ -394,11 +404,12 @@ class Renderer:
     def light_sampling(self, on=True):
         """Next-event estimation from the next launch on (rt_renderer_light_sampling_enable); a change restarts the refinement.
         False / 0 / "off": off; True / 1 / "quads": over the world's quad lights; 2 / "all": over its quad and sphere lights; 4 / "mesh": over its quad,
-        sphere and triangle lights (an emissive mesh)."""
+        sphere and triangle lights (an emissive mesh); 16 / "tree": over the same lights, up to 4096, chosen by area and found through a light tree."""
         check(lib().rt_renderer_light_sampling_enable(self.h, light_sampling_mode(on)))
 
     def light_sampling_mode(self):
-        """0 (off), 1 (quad lights), 2 (quad and sphere lights) or 4 (quad, sphere and triangle lights): the mode the next launch runs in."""
+        """0 (off), 1 (quad lights), 2 (quad and sphere lights), 4 (quad, sphere and triangle lights) or 16 (those, by area, through a light tree): the mode
+        the next launch runs in."""
         out = (C.c_uint32 * 2)()
         check(lib().rt_renderer_light_sampling_info(self.h, out))
         return out[0]
@@ -441,6 +452,12 @@ class Renderer:
         form = {"kernel": ("baseline", "stream", "xchg")[out[0]]}
         form.update(zip(("exact", "filter", "world", "ext", "big", "wide", "tol", "nee"), out[1:]))
         return form
+
+    def kernel_light_tree(self):
+        """True when the next launch runs the streaming kernel's light-tree family (rt_renderer_kernel_light_tree): mode "tree" is on."""
+        out = C.c_uint32(0)
+        check(lib().rt_renderer_kernel_light_tree(self.h, C.byref(out)))
+        return bool(out.value)
 
     def kernel_triangles(self):
         """True when the next launch runs the streaming kernel's triangle family (rt_renderer_kernel_triangles)."""

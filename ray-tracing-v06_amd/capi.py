@@ -85,6 +85,7 @@ SYMBOLS = [
     "rt_renderer_light_sampling_enable", "rt_renderer_light_sampling_info", "rt_multi_renderer_light_sampling_enable", "rt_world_quad_lights",
     "rt_renderer_kernel_form", "rt_world_lights", "rt_scene_cornell_lamp", "rt_world_light_table",
     "rt_scene_add_triangle", "rt_scene_add_mesh", "rt_world_triangles", "rt_renderer_kernel_triangles",
+    "rt_world_light_tree", "rt_renderer_kernel_light_tree",
 ]
 
 _lib = None
@@ -216,6 +217,8 @@ def lib():
     L.rt_world_quad_lights.argtypes = [P(WorldFlat), C.c_uint32 * 16, C.c_float * 16, P(C.c_uint32)]
     L.rt_world_lights.argtypes = [P(WorldFlat), C.c_uint32, C.c_uint32 * 16, C.c_uint32 * 16, C.c_float * 16, P(C.c_uint32)]
     L.rt_world_light_table.argtypes = [P(WorldFlat), C.c_uint32, C.c_uint32, P(C.c_uint32), P(C.c_uint32), P(C.c_float), P(C.c_uint32)]
+    L.rt_world_light_tree.argtypes = [P(WorldFlat), C.c_uint32, P(C.c_float), P(C.c_uint32), P(C.c_float)]
+    L.rt_renderer_kernel_light_tree.argtypes = [C.c_void_p, P(C.c_uint32)]
     L.rt_multi_renderer_create.argtypes = [P(RenderConfig), P(Camera), P(WorldFlat), C.c_uint32, C.c_void_p, P(C.c_void_p)]
     L.rt_multi_renderer_destroy.argtypes = [C.c_void_p]
     L.rt_multi_renderer_destroy.restype = None

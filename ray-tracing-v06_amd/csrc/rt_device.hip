@@ -54,6 +54,7 @@ constexpr uint32_t stream_key(bool exact, bool filter, int world, int ext = 0, b
 }
 constexpr uint32_t RT_KEY_XCHG = 1u << 9;
 constexpr uint32_t RT_KEY_NEE = 1u << 10;   // light sampling (rt_renderer_light_sampling_enable): the NEE form of an EXT >= 1 stack-walk or list key
+constexpr uint32_t RT_KEY_LTREE = 1u << 12; // the light tree (mode RT_LIGHT_SAMPLING_TREE): the LTREE form of a TRI && NEE key; reported by rt_renderer_kernel_light_tree
 constexpr uint32_t RT_KEY_TRI = 1u << 11;   // the world has triangles: the TRI form of an EXT >= 1 stack-walk or list key, plain or NEE; not one of rt_renderer_kernel_form's fields
 // a stream key read back into render_kernel_stream's template arguments, in stream_key()'s order, then NEE: what rt_renderer_kernel_form reports
 static void stream_key_fields(uint32_t key, uint32_t out[8]) {
@@ -93,6 +94,8 @@ static const void* stream_kernel_for(uint32_t key) {
     case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, false, true>)
 #define RT_KERNEL_TRI_NEE(exact, world, ext, big, wide) \
     case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NEE: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, true, true>)
+#define RT_KERNEL_LIGHT_TREE(exact, world, ext, big, wide) \
+    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NEE | RT_KEY_LTREE: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, true, true, true>)
     switch (key) {   // arguments: exact, filter, world, ext, big, wide, tol
         case RT_KEY_XCHG: return reinterpret_cast<const void*>(&render_kernel_xchg<RT_XCHG_BLOCK>);
         RT_KERNEL(true, false, RT_WORLD_BVH_QUEUE, 2, true, true, false); RT_KERNEL(true, false, RT_WORLD_BVH_QUEUE, 1, true, true, false); RT_KERNEL(true, false, RT_WORLD_BVH_QUEUE, 0, true, true, false);
@@ -120,9 +123,16 @@ static const void* stream_kernel_for(uint32_t key) {
         RT_KERNEL_TRI_NEE(false, RT_WORLD_BVH, 2, true, false); RT_KERNEL_TRI_NEE(true, RT_WORLD_BVH, 2, true, false); RT_KERNEL_TRI_NEE(false, RT_WORLD_BVH, 1, true, false); RT_KERNEL_TRI_NEE(true, RT_WORLD_BVH, 1, true, false);
         RT_KERNEL_TRI_NEE(true, RT_WORLD_LIST, 2, false, false); RT_KERNEL_TRI_NEE(true, RT_WORLD_LIST, 1, false, false);
         RT_KERNEL_TRI_NEE(false, RT_WORLD_BVH, 2, false, false); RT_KERNEL_TRI_NEE(true, RT_WORLD_BVH, 2, false, false); RT_KERNEL_TRI_NEE(false, RT_WORLD_BVH, 1, false, false); RT_KERNEL_TRI_NEE(true, RT_WORLD_BVH, 1, false, false);
+        // the light tree (§20): the TRI && NEE families once more (arguments: exact, world, ext, big, wide)
+        RT_KERNEL_LIGHT_TREE(true, RT_WORLD_LIST, 2, true, true); RT_KERNEL_LIGHT_TREE(true, RT_WORLD_LIST, 1, true, true);
+        RT_KERNEL_LIGHT_TREE(false, RT_WORLD_BVH, 2, true, true); RT_KERNEL_LIGHT_TREE(true, RT_WORLD_BVH, 2, true, true); RT_KERNEL_LIGHT_TREE(false, RT_WORLD_BVH, 1, true, true); RT_KERNEL_LIGHT_TREE(true, RT_WORLD_BVH, 1, true, true);
+        RT_KERNEL_LIGHT_TREE(false, RT_WORLD_BVH, 2, true, false); RT_KERNEL_LIGHT_TREE(true, RT_WORLD_BVH, 2, true, false); RT_KERNEL_LIGHT_TREE(false, RT_WORLD_BVH, 1, true, false); RT_KERNEL_LIGHT_TREE(true, RT_WORLD_BVH, 1, true, false);
+        RT_KERNEL_LIGHT_TREE(true, RT_WORLD_LIST, 2, false, false); RT_KERNEL_LIGHT_TREE(true, RT_WORLD_LIST, 1, false, false);
+        RT_KERNEL_LIGHT_TREE(false, RT_WORLD_BVH, 2, false, false); RT_KERNEL_LIGHT_TREE(true, RT_WORLD_BVH, 2, false, false); RT_KERNEL_LIGHT_TREE(false, RT_WORLD_BVH, 1, false, false); RT_KERNEL_LIGHT_TREE(true, RT_WORLD_BVH, 1, false, false);
         default: return nullptr;
     }
 #undef RT_KERNEL
+#undef RT_KERNEL_LIGHT_TREE
 #undef RT_KERNEL_NEE
 #undef RT_KERNEL_TRI
 #undef RT_KERNEL_TRI_NEE
@@ -189,11 +199,12 @@ struct rt_renderer {
     // light sampling (rt_renderer_light_sampling_enable): per mode (tab[slot(mode)]) the world's lights as rt_world_light_table gave them at creation (or why it
     // gave none) and — from the first enable of that mode — the scene image with its light table behind it and the LDS that takes; one NEE form of this renderer's
     // kernel serves all three modes (they differ only in what the table holds)
-    struct LightTable { uint32_t n = 0, kind[RT_MAX_LIGHTS_MESH] = {}, index[RT_MAX_LIGHTS_MESH] = {}; float area[RT_MAX_LIGHTS_MESH] = {}, sphere[RT_MAX_LIGHTS_MESH][4] = {};
-                        std::string refused; DevBuf blob; uint32_t table_vec4 = 0, lds_bytes = 0, blocks_per_cu = 0; bool built = false; };
-    struct { uint32_t mode = RT_LIGHT_SAMPLING_OFF; LightTable tab[3]; const void* kernel = nullptr;
+    // (mode RT_LIGHT_SAMPLING_TREE, §20, has a family of its own — `key` says which form a table runs — and, behind the table, cdf in the entries and the tree's nodes)
+    struct LightTable { uint32_t n = 0; std::vector<uint32_t> kind, index; std::vector<float> area, sphere /* 4 per light */, cdf, nodes /* 8 per node */;
+                        std::string refused; DevBuf blob; uint32_t table_vec4 = 0, lds_bytes = 0, blocks_per_cu = 0, key = 0; const void* kernel = nullptr; bool built = false; };
+    struct { uint32_t mode = RT_LIGHT_SAMPLING_OFF; LightTable tab[4]; const void* kernel = nullptr;   // kernel: the current mode's
              bool on() const { return mode != RT_LIGHT_SAMPLING_OFF; }
-             static uint32_t slot(uint32_t m) { return m == RT_LIGHT_SAMPLING_MESH ? 2u : m - 1u; }   // modes 1, 2, 4
+             static uint32_t slot(uint32_t m) { return m == RT_LIGHT_SAMPLING_TREE ? 3u : m == RT_LIGHT_SAMPLING_MESH ? 2u : m - 1u; }   // modes 1, 2, 4, 16
              const LightTable& cur() const { return tab[slot(mode)]; } } nee;
     // denoiser (rt_renderer_denoise): guide records, the two colour buffers the iterations ping-pong, the output frame; allocated at first use
     DevBuf dn_g0, dn_g1, dn_a, dn_b, dn_out;
@@ -537,13 +548,21 @@ extern "C" int rt_renderer_create(const rt_render_config* cfg, const rt_camera* 
         else if (t == RT_MAT_LAMBERTIAN_NOISE) r->aov_refused = "a noise texture (RT_MAT_LAMBERTIAN_NOISE)";
         else if (t == RT_MAT_LAMBERTIAN_IMAGE) r->aov_refused = "an image texture (RT_MAT_LAMBERTIAN_IMAGE)";
     }
-    for (const uint32_t mode : {RT_LIGHT_SAMPLING_QUADS, RT_LIGHT_SAMPLING_ALL, RT_LIGHT_SAMPLING_MESH}) {
+    for (const uint32_t mode : {RT_LIGHT_SAMPLING_QUADS, RT_LIGHT_SAMPLING_ALL, RT_LIGHT_SAMPLING_MESH, RT_LIGHT_SAMPLING_TREE}) {
         rt_renderer::LightTable& t = r->nee.tab[r->nee.slot(mode)];
-        if (rt_world_light_table(world, mode, RT_MAX_LIGHTS_MESH, t.kind, t.index, t.area, &t.n) != RT_OK) { t.refused = rt_last_error(); t.n = 0; }
+        const uint32_t cap = mode == RT_LIGHT_SAMPLING_TREE ? RT_MAX_LIGHTS_TREE : RT_MAX_LIGHTS_MESH;
+        t.kind.assign(cap, 0u); t.index.assign(cap, 0u); t.area.assign(cap, 0.0f);
+        if (rt_world_light_table(world, mode, cap, t.kind.data(), t.index.data(), t.area.data(), &t.n) != RT_OK) { t.refused = rt_last_error(); t.n = 0; }
+        t.kind.resize(t.n); t.index.resize(t.n); t.area.resize(t.n); t.sphere.assign((size_t)t.n * 4u, 0.0f);
+        if (mode == RT_LIGHT_SAMPLING_TREE && t.n) {
+            uint32_t n_nodes = 0;
+            t.cdf.assign(t.n, 0.0f); t.nodes.assign((size_t)(2u * t.n - 1u) * 8u, 0.0f);
+            if (rt_world_light_tree(world, t.n, t.nodes.data(), &n_nodes, t.cdf.data()) != RT_OK) { t.refused = rt_last_error(); t.n = 0; }
+        }
         for (uint32_t i = 0; i < t.n; i++)
             if (t.kind[i] == RT_LIGHT_SPHERE) {   // the world's arrays are borrowed during creation only: what the table says of a sphere is taken now
                 const rt_prim& pr = world->prims[t.index[i]];
-                t.sphere[i][0] = pr.c0[0]; t.sphere[i][1] = pr.c0[1]; t.sphere[i][2] = pr.c0[2]; t.sphere[i][3] = pr.radius;
+                t.sphere[4u * i] = pr.c0[0]; t.sphere[4u * i + 1u] = pr.c0[1]; t.sphere[4u * i + 2u] = pr.c0[2]; t.sphere[4u * i + 3u] = pr.radius;
             }
     }
     r->cam = *cam;   // the camera of the first launch; rt_renderer_set_camera replaces it (Renderer.cu:117 reads the caller's camera at every Render())
@@ -630,8 +649,8 @@ extern "C" int rt_renderer_set_camera(rt_renderer* r, const rt_camera* cam) {
 // (Cx, Cy, Cz, r), zeros for a quad and for a triangle.
 extern "C" int rt_renderer_light_sampling_enable(rt_renderer* r, uint32_t on) {
     if (!r) return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: null renderer");
-    if (on > RT_LIGHT_SAMPLING_ALL && on != RT_LIGHT_SAMPLING_MESH)   // 3 is no mode
-        return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: on must be 0 (off), 1 (quad lights), 2 (quad and sphere lights) or 4 (quad, sphere and triangle lights)");
+    if (on > RT_LIGHT_SAMPLING_ALL && on != RT_LIGHT_SAMPLING_MESH && on != RT_LIGHT_SAMPLING_TREE)   // 3 is no mode
+        return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: on must be 0 (off), 1 (quad lights), 2 (quad and sphere lights), 4 (quad, sphere and triangle lights) or 16 (those, through a light tree, chosen by area)");
     if (on == r->nee.mode) return RT_OK;   // nothing changes, the refinement goes on
     if (on) {
         rt_renderer::LightTable& t = r->nee.tab[r->nee.slot(on)];
@@ -640,31 +659,41 @@ extern "C" int rt_renderer_light_sampling_enable(rt_renderer* r, uint32_t on) {
         if (!t.refused.empty()) return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: %s", t.refused.c_str());
         HIP_TRY(hipSetDevice(r->cfg.device));
         if (!t.built) {   // set last: a failure on the way is tried again
-            const uint32_t table_vec4 = 1u + t.n * (on == RT_LIGHT_SAMPLING_QUADS ? 1u : 2u);
+            const bool tree = on == RT_LIGHT_SAMPLING_TREE;   // §20: 2 n_l - 1 nodes of two vec4 behind the table: 1 + 2 n_l + 2 (2 n_l - 1) = 6 n_l - 1 vec4
+            const uint32_t table_vec4 = 1u + t.n * (on == RT_LIGHT_SAMPLING_QUADS ? 1u : 2u) + (tree ? 2u * (2u * t.n - 1u) : 0u);
             PackedSceneRef with_table = r->scene.packed;
             with_table.blob_vec4 += table_vec4;
             const uint32_t lds = (uint32_t)stream_kernel_lds_bytes(r->stream_block, with_table, r->scene.big, r->scene.wide, r->n_top);
             if (lds > RT_LDS_PER_CU)
                 return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: the light table (%u bytes) does not fit beside the scene image in the LDS", table_vec4 * 16u);
-            const void* k = stream_kernel_for(stream_kernel_key(r->variant, false, r->scene) | RT_KEY_NEE);
+            const uint32_t key = stream_kernel_key(r->variant, false, r->scene) | RT_KEY_NEE | (tree ? RT_KEY_TRI | RT_KEY_LTREE : 0u);   // a world without triangles is a TRI world too
+            const void* k = stream_kernel_for(key);
             if (!k) return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: this world's kernel has no light-sampling form");
             std::vector<uint4> table(table_vec4, make_uint4(0u, 0u, 0u, 0u));
             table[0].x = t.n;
             for (uint32_t i = 0; i < t.n; i++) {
                 table[1u + i].x = t.index[i]; std::memcpy(&table[1u + i].y, &t.area[i], 4); table[1u + i].z = t.kind[i];
-                if (t.kind[i] == RT_LIGHT_SPHERE) std::memcpy(&table[1u + t.n + i], t.sphere[i], 16);
+                if (t.kind[i] == RT_LIGHT_SPHERE) std::memcpy(&table[1u + t.n + i], &t.sphere[4u * i], 16);
+                if (tree) std::memcpy(&table[1u + i].w, &t.cdf[i], 4);
+            }
+            if (tree) {
+                std::memcpy(&table[0].y, &t.cdf[t.n - 1u], 4);   // A
+                std::memcpy(&table[1u + 2u * t.n], t.nodes.data(), t.nodes.size() * sizeof(float));
             }
             HIP_TRY(t.blob.alloc(((size_t)r->scene.packed.blob_vec4 + table_vec4) * sizeof(uint4)));
             HIP_TRY(hipMemcpy(t.blob.p, r->scene.blob.p, (size_t)r->scene.packed.blob_vec4 * sizeof(uint4), hipMemcpyDeviceToDevice));
             HIP_TRY(hipMemcpy(t.blob.as<uint4>() + r->scene.packed.blob_vec4, table.data(), table.size() * sizeof(uint4), hipMemcpyHostToDevice));
-            const uint32_t lds_set = std::max({lds, r->nee.tab[0].lds_bytes, r->nee.tab[1].lds_bytes, r->nee.tab[2].lds_bytes});   // one kernel, three tables: the attribute covers the largest
+            uint32_t lds_set = lds;   // one kernel may serve several tables: the attribute covers the largest of its own
+            for (const rt_renderer::LightTable& o : r->nee.tab) if (o.built && o.kernel == k) lds_set = std::max(lds_set, o.lds_bytes);
             HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_set));
             t.table_vec4 = table_vec4;
             t.lds_bytes = lds;
             t.blocks_per_cu = std::min(2u, RT_LDS_PER_CU / lds);
-            r->nee.kernel = k;
+            t.key = key;
+            t.kernel = k;
             t.built = true;
         }
+        r->nee.kernel = t.kernel;
     }
     r->nee.mode = on;       // of the NEXT launch; launches already enqueued keep their kernel and their image (the images with the tables stay allocated)
     r->refine_done = 0;     // samples drawn by another estimator belong to another sequence
@@ -907,7 +936,7 @@ extern "C" int rt_renderer_kernel_form(rt_renderer* r, uint32_t out[9]) {
     for (int i = 0; i < 9; i++) out[i] = 0u;
     if (r->variant < 2) { out[0] = RT_KERNEL_BASELINE; return RT_OK; }
     // the key launch() resolves: plan()'s for the plain kernel, rt_renderer_light_sampling_enable's while sampling is on
-    const uint32_t key = r->nee.on() ? stream_kernel_key(r->variant, false, r->scene) | RT_KEY_NEE : stream_kernel_key(r->variant, r->tol, r->scene);
+    const uint32_t key = r->nee.on() ? r->nee.cur().key : stream_kernel_key(r->variant, r->tol, r->scene);
     if (stream_kernel_for(key) != (r->nee.on() ? r->nee.kernel : r->stream_kernel)) return rt_fail(RT_ERR_INVALID, "rt_renderer_kernel_form: the key does not name the kernel the renderer holds");
     if (key == RT_KEY_XCHG) { out[0] = RT_KERNEL_XCHG; return RT_OK; }
     out[0] = RT_KERNEL_STREAM;
@@ -918,7 +947,14 @@ extern "C" int rt_renderer_kernel_form(rt_renderer* r, uint32_t out[9]) {
 // Whether the NEXT launch runs an instantiation of the triangle family: a query of its own, so that rt_renderer_kernel_form's nine outputs stay what they are.
 extern "C" int rt_renderer_kernel_triangles(rt_renderer* r, uint32_t* out) {
     if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_kernel_triangles: null argument");
-    *out = r->variant >= 2 && (stream_kernel_key(r->variant, r->tol, r->scene) & RT_KEY_TRI) ? 1u : 0u;
+    *out = r->variant >= 2 && ((r->nee.on() ? r->nee.cur().key : stream_kernel_key(r->variant, r->tol, r->scene)) & RT_KEY_TRI) ? 1u : 0u;
+    return RT_OK;
+}
+
+// Whether the NEXT launch runs an instantiation of the light-tree family: a query of its own, for the same reason.
+extern "C" int rt_renderer_kernel_light_tree(rt_renderer* r, uint32_t* out) {
+    if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_kernel_light_tree: null argument");
+    *out = r->nee.on() && (r->nee.cur().key & RT_KEY_LTREE) ? 1u : 0u;
     return RT_OK;
 }
 

@@ -634,14 +634,128 @@ extern "C" int rt_world_lights(const rt_world_flat* w, uint32_t mode, uint32_t o
                         "light sampling: the world has more than 16 lights (quads and static spheres whose material is RT_MAT_DIFFUSE_LIGHT)", out_kind, out_index, out_area, out_n);
 }
 
+// The light tree of mode RT_LIGHT_SAMPLING_TREE: mode 4's lights (cap RT_MAX_LIGHTS_TREE) permuted into the leaf order of a median-split
+// bounding-volume tree over their padded boxes, the running sum of their areas, and the nodes in preorder, 8 floats each: min.xyz, skip, max.xyz, leaf.
+static_assert(RT_MAX_LIGHTS_TREE == 4096, "the refusal message below says 4096");
+namespace {
+struct LightTree { std::vector<uint32_t> kind, index; std::vector<float> area, cdf, nodes; };
+struct LightTreeBuilder {
+    std::vector<f3> bmin, bmax, cen;   // per light, in mode 4's order
+    std::vector<uint32_t> order;       // the permutation under construction: a node's range [a, b) of it
+    std::vector<float> nodes;
+    static float bits(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
+    void build(uint32_t a, uint32_t b, f3& out_min, f3& out_max) {
+        const size_t at = nodes.size();
+        nodes.resize(at + 8);
+        uint32_t leaf = 0xffffffffu;
+        if (b - a == 1u) {
+            out_min = bmin[order[a]]; out_max = bmax[order[a]];
+            leaf = a;   // leaves are met in range order: the light's position in the permuted table
+        } else {
+            f3 cmin = cen[order[a]], cmax = cmin;
+            for (uint32_t i = a + 1u; i < b; i++) { cmin = glm_min(cmin, cen[order[i]]); cmax = glm_max(cmax, cen[order[i]]); }
+            const f3 e = cmax - cmin;
+            const float ext[3] = {e.x, e.y, e.z};
+            int axis = 0;
+            if (ext[1] > ext[axis]) axis = 1;
+            if (ext[2] > ext[axis]) axis = 2;
+            std::stable_sort(order.begin() + a, order.begin() + b, [&](uint32_t p, uint32_t q) {
+                const float cp = axis == 0 ? cen[p].x : axis == 1 ? cen[p].y : cen[p].z, cq = axis == 0 ? cen[q].x : axis == 1 ? cen[q].y : cen[q].z;
+                return cp < cq;
+            });
+            const uint32_t mid = a + (b - a) / 2u;
+            f3 lmin, lmax, rmin, rmax;
+            build(a, mid, lmin, lmax);
+            build(mid, b, rmin, rmax);
+            out_min = glm_min(lmin, rmin); out_max = glm_max(lmax, rmax);
+        }
+        float* nd = nodes.data() + at;
+        nd[0] = out_min.x; nd[1] = out_min.y; nd[2] = out_min.z; nd[3] = bits((uint32_t)(nodes.size() / 8));
+        nd[4] = out_max.x; nd[5] = out_max.y; nd[6] = out_max.z; nd[7] = bits(leaf);
+    }
+};
+}  // namespace
+static int world_light_tree(const rt_world_flat* w, const char* who, LightTree& out) {
+    if ((w->n_quads && !w->quads) || (w->n_materials && !w->materials) || (w->n_prims && !w->prims)) return rt_fail(RT_ERR_INVALID, "%s: world array is null", who);
+    std::vector<uint32_t> kind(RT_MAX_LIGHTS_TREE), index(RT_MAX_LIGHTS_TREE);
+    std::vector<float> area(RT_MAX_LIGHTS_TREE);
+    uint32_t n = 0;
+    if (int rc = world_lights(w, true, "light sampling: the world has no light to sample (a quad, a triangle or a static sphere of radius > 0 whose material is RT_MAT_DIFFUSE_LIGHT)",
+                              "light sampling: the world has more than 4096 lights (quads, triangles and static spheres whose material is RT_MAT_DIFFUSE_LIGHT)", kind.data(), index.data(),
+                              area.data(), &n, true, RT_MAX_LIGHTS_TREE))
+        return rc;
+    float M = 0.0f;
+    for (int k = 0; k < 3; k++) M = glm_max(M, glm_max(fabsf(w->bounds_min[k]), fabsf(w->bounds_max[k])));
+    const float pad = RT_LIGHT_TREE_PAD * M;
+    LightTreeBuilder tb;
+    tb.bmin.resize(n); tb.bmax.resize(n); tb.cen.resize(n); tb.order.resize(n);
+    for (uint32_t i = 0; i < n; i++) {
+        f3 lo, hi;
+        float p = pad;
+        if (kind[i] == RT_LIGHT_SPHERE) {
+            const rt_prim& pr = w->prims[index[i]];
+            const f3 c = mk3(pr.c0[0], pr.c0[1], pr.c0[2]);
+            lo = c - mk3(pr.radius); hi = c + mk3(pr.radius);
+            p = pad + (RT_LIGHT_TREE_PAD_SPHERE * (M * M)) / pr.radius;
+        } else {
+            const rt_quad& q = w->quads[index[i]];
+            const f3 Q = mk3(q.Q[0], q.Q[1], q.Q[2]), u = mk3(q.u[0], q.u[1], q.u[2]), v = mk3(q.v[0], q.v[1], q.v[2]);
+            const f3 qu = Q + u, qv = Q + v;
+            lo = glm_min(glm_min(Q, qu), qv); hi = glm_max(glm_max(Q, qu), qv);
+            if (kind[i] == RT_LIGHT_QUAD) { const f3 quv = qu + v; lo = glm_min(lo, quv); hi = glm_max(hi, quv); }
+        }
+        tb.bmin[i] = lo - mk3(p); tb.bmax[i] = hi + mk3(p);
+        tb.cen[i] = (tb.bmin[i] + tb.bmax[i]) * 0.5f;
+        tb.order[i] = i;
+    }
+    tb.nodes.reserve((size_t)(2u * n - 1u) * 8u);
+    f3 rmin, rmax;
+    tb.build(0u, n, rmin, rmax);
+    out.kind.resize(n); out.index.resize(n); out.area.resize(n); out.cdf.resize(n);
+    float c = 0.0f;
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t o = tb.order[i];
+        out.kind[i] = kind[o]; out.index[i] = index[o]; out.area[i] = area[o];
+        const float c1 = c + area[o];
+        if (c1 == c)
+            return rt_fail(RT_ERR_INVALID, "light sampling: the area of a light (kind %u, index %u: %g) is lost in the fp32 running sum of the areas (%g); it could never be drawn", kind[o], index[o],
+                           (double)area[o], (double)c);
+        out.cdf[i] = c = c1;
+    }
+    out.nodes.swap(tb.nodes);
+    return RT_OK;
+}
+
+extern "C" int rt_world_light_tree(const rt_world_flat* w, uint32_t capacity, float* out_nodes, uint32_t* out_n_nodes, float* out_cdf) {
+    if (!w || !out_nodes || !out_n_nodes || !out_cdf) return rt_fail(RT_ERR_INVALID, "rt_world_light_tree: null argument");
+    *out_n_nodes = 0;
+    LightTree t;
+    if (int rc = world_light_tree(w, "rt_world_light_tree", t)) return rc;
+    const uint32_t n = (uint32_t)t.kind.size();
+    if (n > capacity) return rt_fail(RT_ERR_INVALID, "rt_world_light_tree: the table has %u lights, the caller's arrays hold %u", n, capacity);
+    std::memcpy(out_nodes, t.nodes.data(), t.nodes.size() * sizeof(float));
+    std::memcpy(out_cdf, t.cdf.data(), n * sizeof(float));
+    *out_n_nodes = 2u * n - 1u;
+    return RT_OK;
+}
+
 // The light table of any mode, into the caller's arrays of `capacity` entries.  Modes 1 and 2: rt_world_lights' own answer, through arrays of its size.  Mode
 // RT_LIGHT_SAMPLING_MESH: mode 2's list, then the triangle lights.
 static_assert(RT_MAX_LIGHTS_MESH == 64, "the refusal message below says 64");
 extern "C" int rt_world_light_table(const rt_world_flat* w, uint32_t mode, uint32_t capacity, uint32_t* out_kind, uint32_t* out_index, float* out_area, uint32_t* out_n) {
     if (!w || !out_kind || !out_index || !out_area || !out_n) return rt_fail(RT_ERR_INVALID, "rt_world_light_table: null argument");
     *out_n = 0;
-    if (mode != RT_LIGHT_SAMPLING_QUADS && mode != RT_LIGHT_SAMPLING_ALL && mode != RT_LIGHT_SAMPLING_MESH)
-        return rt_fail(RT_ERR_INVALID, "rt_world_light_table: mode must be RT_LIGHT_SAMPLING_QUADS (1), RT_LIGHT_SAMPLING_ALL (2) or RT_LIGHT_SAMPLING_MESH (4)");
+    if (mode != RT_LIGHT_SAMPLING_QUADS && mode != RT_LIGHT_SAMPLING_ALL && mode != RT_LIGHT_SAMPLING_MESH && mode != RT_LIGHT_SAMPLING_TREE)
+        return rt_fail(RT_ERR_INVALID, "rt_world_light_table: mode must be RT_LIGHT_SAMPLING_QUADS (1), RT_LIGHT_SAMPLING_ALL (2), RT_LIGHT_SAMPLING_MESH (4) or RT_LIGHT_SAMPLING_TREE (16)");
+    if (mode == RT_LIGHT_SAMPLING_TREE) {   // §20: mode 4's lights in the tree's leaf order
+        LightTree t;
+        if (int rc = world_light_tree(w, "rt_world_light_table", t)) return rc;
+        const uint32_t n_t = (uint32_t)t.kind.size();
+        if (n_t > capacity) return rt_fail(RT_ERR_INVALID, "rt_world_light_table: the table has %u lights, the caller's arrays hold %u", n_t, capacity);
+        for (uint32_t i = 0; i < n_t; i++) { out_kind[i] = t.kind[i]; out_index[i] = t.index[i]; out_area[i] = t.area[i]; }
+        *out_n = n_t;
+        return RT_OK;
+    }
     uint32_t kind[RT_MAX_LIGHTS_MESH], index[RT_MAX_LIGHTS_MESH], n = 0;
     float area[RT_MAX_LIGHTS_MESH];
     if (mode != RT_LIGHT_SAMPLING_MESH) {

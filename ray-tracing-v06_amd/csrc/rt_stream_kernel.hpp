@@ -214,10 +214,15 @@ __device__ __forceinline__ WideNodeData fetch_wide_node(const char* nodes, const
 //      a header (n_l, -, -, -), then (index, area, kind, -) per light, then — only where a kind says sphere — (Cx, Cy, Cz, r) per light — lies behind the
 //      quads' shade records in the image the NEE launches are given, so it costs no kernel argument: the other instantiations neither see it nor pay for it.
 //      A kind RT_LIGHT_TRIANGLE (mode RT_LIGHT_SAMPLING_MESH) exists only in a world with triangles, so only the TRI && NEE forms hold code for it.
-template <bool EXACT, bool FILTER, int BLOCK, int WORLD = RT_WORLD_BVH, int EXT = 0, bool BIG = false, bool WIDE = BIG, bool TOL = false, bool NEE = false, bool TRI = false>
+// LTREE (mode RT_LIGHT_SAMPLING_TREE; NEE && TRI only, whether or not the world has a triangle): the light is drawn in proportion to its area — a
+//      binary search over the cumulative areas in the entries' fourth lane, A in the header's second — and the density step walks a threaded bounding-volume tree
+//      of the lights, two vec4 per node behind the table ((min.xyz, skip), (max.xyz, leaf)), instead of testing every light: no stack, no indexed private array.
+template <bool EXACT, bool FILTER, int BLOCK, int WORLD = RT_WORLD_BVH, int EXT = 0, bool BIG = false, bool WIDE = BIG, bool TOL = false, bool NEE = false, bool TRI = false,
+          bool LTREE = false>
 __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(StreamParams p) {
     static_assert(!NEE || (EXT >= 1 && WORLD != RT_WORLD_BVH_QUEUE), "light sampling: worlds with quads, walked by the stack or as a list");
     static_assert(!TRI || (EXT >= 1 && WORLD != RT_WORLD_BVH_QUEUE), "triangles: worlds with quads; a lane walk reads the kind from the flat record");
+    static_assert(!LTREE || (NEE && TRI), "the light tree: one family, which knows all three kinds of light");
     extern __shared__ uint4 lds[];
     const uint32_t tid = threadIdx.x;
     const uint32_t lane = tid & 63u;
@@ -625,6 +630,17 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                     if (NEE && to_light) {
                         const float4* lights = quads + p.scene.n_quads * 5u;
                         const uint32_t n_l = __float_as_uint(lights[0].x);
+                        if constexpr (LTREE) {   // §20: the smallest j with c_j > x, x = next * A; none (x rounded up to A): the last light
+                            if (n_l > 1u) {
+                                const float x = rng.next() * lights[0].y;
+                                uint32_t hi = n_l - 1u;
+                                while (nee_li < hi) {
+                                    const uint32_t mid = (nee_li + hi) >> 1;
+                                    if (lights[1u + mid].w > x) hi = mid;
+                                    else nee_li = mid + 1u;
+                                }
+                            }
+                        } else
                         if (n_l > 1u) nee_li = min((uint32_t)(rng.next() * (float)n_l), n_l - 1u);
                         const float4 le = lights[1u + nee_li];
                         nee_quad = __float_as_uint(le.x);
@@ -673,6 +689,53 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                             Ray lray;
                             lray.o = hit_p; lray.d = d; lray.time = ray.time;
                             float pdf_light = 0.0f;
+                            if constexpr (LTREE) {
+                                // §20: the threaded tree of the lights' padded boxes, in preorder; a leaf met adds mode 4's term without its division by area_j,
+                                // in ascending table position — the linear loop's order with its zeros left out — and the sum is divided by A once
+                                const float4* tnodes = lights + 1u + 2u * n_l;
+                                const uint32_t n_nodes = 2u * n_l - 1u;
+                                const f3 rd = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+                                bool own_met = !to_sphere;   // a drawn sphere whose leaf the walk credits with disc > 0
+                                uint32_t i = 0u;
+                                while (i < n_nodes) {
+                                    const float4 b0 = tnodes[2u * i], b1 = tnodes[2u * i + 1u];
+                                    const f3 ta = (mk3(b0.x, b0.y, b0.z) - hit_p) * rd, tb = (mk3(b1.x, b1.y, b1.z) - hit_p) * rd;
+                                    const float tmin = comp_max(glm_min(ta, tb)), tmax = comp_min(glm_max(ta, tb));
+                                    const uint32_t leaf = __float_as_uint(b1.w);
+                                    if (!(tmin <= tmax * RT_LIGHT_TREE_K && tmax > 0)) { i = __float_as_uint(b0.w); continue; }
+                                    if (leaf == 0xffffffffu) { i++; continue; }
+                                    i = __float_as_uint(b0.w);
+                                    const float4 lt = lights[1u + leaf];
+                                    if (__float_as_uint(lt.z) == RT_LIGHT_SPHERE) {
+                                        const float4 sc = lights[1u + n_l + leaf];
+                                        const f3 oc = mk3(sc.x, sc.y, sc.z) - hit_p;
+                                        const float h = dot(d, oc);
+                                        const f3 cr = cross(oc, d);
+                                        const float disc = (sc.w * sc.w) * len2 - dot(cr, cr);
+                                        if (disc > 0) {
+                                            if (nee_li == n_l + leaf) own_met = true;
+                                            const float sq = sqrtf(disc);
+                                            const float den = (sq / sc.w) / len;
+                                            const float t1 = (h - sq) / len2, t2 = (h + sq) / len2;
+                                            float pl_j = 0.0f;
+                                            if (t1 > 0) pl_j = pl_j + ((t1 * t1) * len2) / den;
+                                            if (t2 > 0) pl_j = pl_j + ((t2 * t2) * len2) / den;
+                                            pdf_light = pdf_light + pl_j;
+                                        }
+                                    } else {
+                                        const float4* qd = quads + __float_as_uint(lt.x) * 4u;
+                                        const float4 a0 = qd[0], a1 = qd[1], a2 = qd[2], a3 = qd[3];
+                                        const f3 ln = mk3(a2.z, a2.w, a3.x);
+                                        HitRec tmp;
+                                        tmp.distance = RT_MISS_DIST; tmp.normal = mk3(0.0f); tmp.prim = -1; tmp.mat = 0;
+                                        if (quad_closest_intersection(mk3(a0.x, a0.y, a0.z), a0.w, mk3(a1.x, a1.y, a1.z), mk3(a1.w, a2.x, a2.y), ln, mk3(a3.y, a3.z, a3.w), 0u, 0,
+                                                                      __float_as_uint(lt.z) == RT_LIGHT_TRIANGLE ? RT_QUAD_TRIANGLE : RT_QUAD_PARALLELOGRAM, lray, tmp))
+                                            pdf_light = pdf_light + ((tmp.distance * tmp.distance) * len2) / (fabsf(dot(d, ln)) / len);
+                                    }
+                                }
+                                if (!own_met) scattered_ok = false;   // §17's silhouette rule, for a walk that may not reach the leaf
+                                pdf_light = pdf_light / lights[0].y;
+                            } else {
                             for (uint32_t j = 0; j < n_l; j++) {
                                 const float4 lt = lights[1u + j];
                                 float pl_j = 0.0f;
@@ -706,6 +769,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                                 pdf_light = pdf_light + pl_j;
                             }
                             pdf_light = pdf_light / (float)n_l;
+                            }
                             const float pdf = 0.5f * pdf_cos + 0.5f * pdf_light;
                             if (pdf_cos == 0.0f || !(pdf > 0)) scattered_ok = false;   // below the surface, or a density that is not a number: a failed scatter
                             else { nee_weight = pdf_cos / pdf; nee_weighted = true; }

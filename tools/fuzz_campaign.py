@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Differential fuzz campaign: random worlds (spheres, moving spheres, quads, triangles and meshes, lights, media, textures; every builder; LDS
 and global-memory paths; three cameras) rendered on the GPU and by the CPU oracle, compared bit for bit.
-    python tools/fuzz_campaign.py --seeds 200 [--first 0] [--no-triangles] [--mesh-lights]
+    python tools/fuzz_campaign.py --seeds 200 [--first 0] [--no-triangles] [--mesh-lights] [--light-tree]
 Prints one line per failure and a summary; exit code 1 if anything differed.  The triangles of a world come from a generator of their own, so the rest of a seed's
 world is what it was before the fuzzer made triangles, and --no-triangles renders exactly those earlier worlds.  Importing this file starts nothing:
 world_of_seed() builds a seed's world on the host, without a device.  --mesh-lights (off by default: the recorded campaigns ran without it) also renders every
@@ -12,6 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import __graft_entry__ as G
+import _light_tree_twin as LT
 import _mesh_light_twin as MT
 import _nee_twin as T
 import _oracle as O
@@ -29,6 +30,7 @@ def parse_args(argv=None):
     ap.add_argument("--variants", action="store_true", help="pick a random kernel variant (0..5) per world — variant 5 (ray exchange) with random roles / thresholds / ring pairs —, now and then a forced multi-pass cut; unsupported combinations are skipped")
     ap.add_argument("--force-variant", type=int, default=None, help="render every world with this kernel variant; 6 (tolerance mode) is held to |delta| < 1e-3 and its differing frames are counted, not failed")
     ap.add_argument("--no-triangles", action="store_true", help="the worlds as they were before the fuzzer made triangles, byte for byte")
+    ap.add_argument("--light-tree", action="store_true", help="also render the worlds that light-sampling mode 16 (the light tree, chosen by area) accepts in that mode: both memory forms, and the twin (tests/_light_tree_twin.py) where it follows")
     ap.add_argument("--mesh-lights", action="store_true", help="also render the worlds that light-sampling mode 4 (triangle and mesh lights) accepts in that mode: both memory forms, and the twin where it follows")
     return ap.parse_args(argv)
 
@@ -126,10 +128,10 @@ def light_sampling_check(p, s, w, cam, ck, W, H, depth, variant, mode=1):
         r.close()
     ok = bits_equal(sums[0], sums[1])
     if ck == 0:
-        if mode == 4:
+        if mode in (4, 16):   # 16, --light-tree: tests/_light_tree_twin.py
             if w.traversal != 0 or (s.arrays()[1]["mat"] >> 31).any():
                 return ok, forms
-            samples, followed = MT.frame_samples(as_oracle_world(w), as_oracle_camera(cam), W, H, spp, depth, 1984, mode=4)
+            samples, followed = (LT if mode == 16 else MT).frame_samples(as_oracle_world(w), as_oracle_camera(cam), W, H, spp, depth, 1984, mode=mode)
         elif not s.n_triangles():
             samples, followed = T.frame_samples(as_oracle_world(w), as_oracle_camera(cam), W, H, spp, depth, 1984, light_sampling=True)
         elif w.traversal == 0 and not (s.arrays()[1]["mat"] >> 31).any():
@@ -227,6 +229,12 @@ def main(argv=None):
                 if not ls[0]:
                     fails += 1
                     print(f"FAIL seed {seed} with light sampling mode 4: kinds {kinds} triangles {s.n_triangles()} builder {builder} big {big} cam {ck} depth {depth} forms {ls[1]}", flush=True)
+            ls = light_sampling_check(p, s, w, cam, ck, W, H, depth, variant, mode=16) if args.light_tree else None
+            if ls is not None:
+                stats["light_tree_sampling"] = stats.get("light_tree_sampling", 0) + 1
+                if not ls[0]:
+                    fails += 1
+                    print(f"FAIL seed {seed} with light sampling mode 16: kinds {kinds} triangles {s.n_triangles()} builder {builder} big {big} cam {ck} depth {depth} forms {ls[1]}", flush=True)
         if (seed - args.first) % 25 == 24:
             print(f"... {seed - args.first + 1} worlds, {fails} failures, {time.time() - t0:.0f}s, paths {stats}", flush=True)
     print(f"DONE: {args.seeds} worlds, {fails} failures, paths {stats}, {time.time() - t0:.0f}s")

@@ -30,7 +30,8 @@ samples sphere lights too (RT_LIGHT_SAMPLING_ALL): the Cornell box lit by a lamp
     python tools/render.py --scene cornell_lamp --mesh icosphere:0 --mesh-scale 30 --mesh-translate 150,400,300 --mesh-material light \
         --spp 64 --light-sampling-mode mesh --out out.png
 
-samples the triangles of an emissive mesh too (RT_LIGHT_SAMPLING_MESH), up to 64 lights of all kinds together.
+samples the triangles of an emissive mesh too (RT_LIGHT_SAMPLING_MESH), up to 64 lights of all kinds together.  --light-sampling-mode tree
+(RT_LIGHT_SAMPLING_TREE) takes up to 4096 — e.g. --mesh icosphere:2 — picks a light by its area and finds the lights a direction crosses through a tree.
 
     python tools/render.py --scene cornell_box --mesh icosphere:2 --mesh-scale 80 --mesh-translate 278,278,200 --mesh-material metal --out out.png
 
@@ -55,9 +56,9 @@ ap.add_argument("--until", type=float, default=None, metavar="NOISE", help="with
 ap.add_argument("--denoise", action="store_true", help="with --refine: also write the denoised frame (<out>_denoised.<ext>)")
 ap.add_argument("--aov", default=None, metavar="PREFIX", help="with --refine: write PREFIX_normal.png, PREFIX_depth.png, PREFIX_albedo.png")
 ap.add_argument("--light-sampling", action="store_true", help="next-event estimation over the world's quad lights (rt_renderer_light_sampling_enable)")
-ap.add_argument("--light-sampling-mode", choices=["quads", "all", "mesh"], default=None,
+ap.add_argument("--light-sampling-mode", choices=["quads", "all", "mesh", "tree"], default=None,
                 help="switch light sampling on in this mode: quads (what --light-sampling selects), all (quad and sphere lights, e.g. --scene cornell_lamp) or "
-                     "mesh (those and triangle lights, e.g. --mesh ... --mesh-material light)")
+                     "mesh (those and triangle lights, e.g. --mesh ... --mesh-material light), tree (mesh's lights, up to 4096, by area through a light tree)")
 ap.add_argument("--mesh", default=None, metavar="FILE.obj|icosphere:LEVEL|tetrahedron", help="a triangle mesh to place into the scene (rt_scene_add_mesh)")
 ap.add_argument("--mesh-scale", type=float, default=1.0)
 ap.add_argument("--mesh-rotate-y", type=float, default=0.0, metavar="DEGREES")
@@ -65,7 +66,7 @@ ap.add_argument("--mesh-translate", default="0,0,0", metavar="X,Y,Z")
 ap.add_argument("--mesh-material", default="white", choices=["white", "red", "metal", "glass", "checker", "light"])
 ap.add_argument("--out", default="render.png")
 a = ap.parse_args()
-light_mode = {"quads": 1, "all": 2, "mesh": 4}.get(a.light_sampling_mode, 1 if a.light_sampling else 0)   # RT_LIGHT_SAMPLING_*
+light_mode = {"quads": 1, "all": 2, "mesh": 4, "tree": 16}.get(a.light_sampling_mode, 1 if a.light_sampling else 0)   # RT_LIGHT_SAMPLING_*
 if a.refine < 0 or (a.until is not None and (a.refine == 0 or a.gpus > 1)):
     ap.error("--until needs --refine STEP > 0 and one GPU (the multi-GPU renderer has no noise figure)")
 if (a.denoise or a.aov) and (a.refine == 0 or a.gpus > 1):
