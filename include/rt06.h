@@ -222,6 +222,32 @@ int rt_scene_add_triangle(rt_scene* s, const float a[3], const float b[3], const
  * *out_added = faces added, *out_first = index of the first of them among the scene's quads (either may be NULL).                       */
 int rt_scene_add_mesh(rt_scene* s, uint32_t n_vertices, const float* xyz, uint32_t n_triangles, const uint32_t* indices, int32_t mat,
                       float scale, float rotate_y_degrees, const float translate[3], int32_t* out_first, uint32_t* out_added);
+/* ---- smooth shading (not in the reference): per-vertex normals for triangles.  A triangle record Q, u, v has the vertices a = Q, b = Q + u,
+ * c = Q + v; it MAY carry three normals n0, n1, n2, one per vertex in that order.  sizeof(rt_quad) and sizeof(rt_world_flat) are what they were: the normals
+ * travel BESIDE the flat world, one 36-byte record per triangle of the flat world in the flat world's triangle order; nine zeros = a flat triangle.
+ * The rule, at a hit on such a triangle, after the flat normal f (the record's normal, negated if dot(ray.d, normal) > 0) is formed as ever:
+ *   planar = hit_p - Q;  alpha = dot(w, cross(planar, v));  beta = dot(w, cross(u, planar));         (image_value_quad's three lines)
+ *   g = (n0 * ((1 - alpha) - beta) + n1 * alpha) + n2 * beta;   l2 = dot(g, g);   !(l2 > 0): keep f   (an all-zero record, cancellation, NaN)
+ *   s = g / sqrt(l2);   dot(s, f) < 0: s = -s   (the side of the face the ray sees);   !(dot(ray.d, s) < 0): keep f   (the normal faces AGAINST the ray, always)
+ *   normal = s.   Only fp32 + - * / sqrt and comparisons, each rounded on its own.  Everything after it reads `normal` as it did.  Nothing is done about
+ * scattered rays that dip under the geometric surface (the shading-normal terminator); a dielectric triangle keeps behaving as on a quad.               */
+typedef struct rt_tri_normals { float n0[3], n1[3], n2[3]; } rt_tri_normals;   /* 36 B */
+/* rt_scene_add_triangle with a normal per vertex: each must be finite and of non-zero length (RT_ERR_INVALID otherwise, scene unchanged) and is normalised here */
+int rt_scene_add_triangle_smooth(rt_scene* s, const float a[3], const float b[3], const float c[3], const float na[3], const float nb[3], const float nc[3],
+                                 int32_t mat, int32_t* out_quad);
+/* rt_scene_add_mesh with n_normals normals (3 floats each) and, per face, three indices into them (normal_indices; NULL = the vertex indices).  The normals are
+ * rotated about y with rt_scene_add_mesh's arithmetic, neither scaled nor translated, and normalised on the host.  A normal that is not finite or has zero length,
+ * or a normal index out of range, fails the whole call and leaves the scene unchanged.  Degenerate faces are skipped and counted out as ever.                 */
+int rt_scene_add_mesh_smooth(rt_scene* s, uint32_t n_vertices, const float* xyz, uint32_t n_normals, const float* normals, uint32_t n_triangles,
+                             const uint32_t* indices, const uint32_t* normal_indices, int32_t mat, float scale, float rotate_y_degrees, const float translate[3],
+                             int32_t* out_first, uint32_t* out_added);
+/* One record per triangle of the flat world, in its triangle order (record i belongs to quad n_quads - n_triangles + i), carried through everything that permutes
+ * triangles: the three BVH builders, the list, a parallelogram added later.  *out_n = 0 (and *out = NULL) when no triangle of the scene has normals.  The
+ * pointer stays valid until the scene is modified or destroyed.                                                                                               */
+int rt_scene_vertex_normals(const rt_scene* s, const rt_tri_normals** out, uint32_t* out_n);
+/* HOST (no GPU): the rule above on n hits — triangle tris[i] (Q, u, v, normal, w read), record vn[i], ray rays[6 i ..] = (o, d), hit distance t[i] ->
+ * out_normal[3 i ..], out_interpolated[i] = 1 where the normal is the interpolated one, 0 where it is the flat one.  The function the kernels call.          */
+int rt_shading_normal_batch(size_t n, const rt_quad* tris, const rt_tri_normals* vn, const float* rays, const float* t, float* out_normal, uint32_t* out_interpolated);
 /* camera::background of "The Next Week": mode 0 = the reference's sky gradient, 1 = constant colour       */
 int rt_scene_set_background(rt_scene* s, uint32_t mode, const float color[3]);
 /* selects RT_TRAVERSAL_STACK / RT_TRAVERSAL_QUEUE / RT_TRAVERSAL_WIDE4 for the BVH world of this scene (see the enum) */
@@ -567,6 +593,16 @@ int rt_world_light_table(const rt_world_flat* w, uint32_t mode, uint32_t capacit
  * counts lights: out_nodes holds 8 * (2 * capacity - 1) floats, out_cdf capacity.  Refused as the table is.                                                 */
 int rt_world_light_tree(const rt_world_flat* w, uint32_t capacity, float* out_nodes, uint32_t* out_n_nodes, float* out_cdf);
 
+/* Smooth shading (see rt_tri_normals): the renderer's table of vertex normals, one record per triangle of its world — n must equal rt_world_triangles of it —
+ * or NULL, 0 to turn it off.  Copied.  Takes effect at the next launch and, like a light-sampling change, discards the refinement and feature-buffer state.  The
+ * table lies in global memory behind the scene image (in every light-sampling mode) and is read once per shaded hit on a triangle; with it on, the feature
+ * pass's first-hit normal is the shading normal by the same function (depth and albedo unchanged).  Validated on the host: every value finite; each record all
+ * zero, or three normals of non-zero length.  RT_ERR_INVALID with a message of its own: the baseline kernel (variant 1), a queue or wide4 traversal, variants
+ * 5 and 6, a wrong n, a bad record.                                                                                                                      */
+int rt_renderer_shading_normals(rt_renderer* r, const rt_tri_normals* table, uint32_t n);
+/* out[0] = 1 while a table is on, out[1] = how many of its records are not flat */
+int rt_renderer_shading_normals_info(rt_renderer* r, uint32_t out[2]);
+
 /* ------------------------------------------------------------------ */
 /* Multi-GPU renderer — the same three entry points (Renderer.h:38-46)  */
 /* over the N GPUs of one node, driven by ONE host process.            */
@@ -591,6 +627,8 @@ int rt_multi_renderer_set_camera(rt_multi_renderer* m, const rt_camera* cam);
 int rt_multi_renderer_refine(rt_multi_renderer* m, uint32_t n_samples);
 /* rt_renderer_light_sampling_enable on every rank (the first rank refuses what any would, before any changes).          */
 int rt_multi_renderer_light_sampling_enable(rt_multi_renderer* m, uint32_t on);
+/* rt_renderer_shading_normals on every rank (the first rank refuses what any would, before any changes).                 */
+int rt_multi_renderer_shading_normals(rt_multi_renderer* m, const rt_tri_normals* table, uint32_t n);
 /* Renderer::DownloadRenderbuffer: width*height*4 floats from devices[0].                                                */
 int rt_multi_renderer_download(rt_multi_renderer* m, float* host_rgba, size_t n_floats);
 /* ms of the last render: out[0] host wall-clock of Render(), out[1] slowest rank's kernels (HIP events),
@@ -619,6 +657,10 @@ int rt_probe_sphere(int device, size_t n, const float* rays, const float* sphere
  * hit n, t n, prim n, normal n*3                                             */
 int rt_probe_trace(int device, const rt_world_flat* world, size_t n, const float* rays,
                    int32_t* out_hit, float* out_t, int32_t* out_prim, float* out_normal);
+/* Hittable::ClosestIntersection on a whole world, then the smooth-shading rule on a triangle hit: rays n*7 (o,d,time), table = n_table records (n_table ==
+ * rt_world_triangles of the world, or NULL, 0) -> hit n, normal n*3 (the flat normal where the rule keeps it; 0 on a miss), interpolated n (0/1)            */
+int rt_probe_shading_normal(int device, const rt_world_flat* world, const rt_tri_normals* table, uint32_t n_table, size_t n, const float* rays,
+                            int32_t* out_hit, float* out_normal, uint32_t* out_interpolated);
 /* SphereHittable / MovingSphereHittable::ClosestIntersection (SphereHittable.cu:56-66, :91-102): sphere
  * prims[i] (material ignored, RT_PRIM_MOVING kept) against ray i (o,d,time) with rec.distance preset[i]
  * -> hit n, rec.distance n, normal n*3 (0 when not hit)                      */

@@ -287,6 +287,27 @@ public:
               "rt_scene_add_mesh");
         return added;
     }
+    // the same two with a normal per vertex, for smooth shading (rt_scene_add_triangle_smooth, rt_scene_add_mesh_smooth): normal_indices empty = the vertex indices
+    int32_t AddTriangle(glm::vec3 a, glm::vec3 b, glm::vec3 c, glm::vec3 na, glm::vec3 nb, glm::vec3 nc, const Material* mat) {
+        const float pa[3] = {a[0], a[1], a[2]}, pb[3] = {b[0], b[1], b[2]}, pc[3] = {c[0], c[1], c[2]};
+        const float qa[3] = {na[0], na[1], na[2]}, qb[3] = {nb[0], nb[1], nb[2]}, qc[3] = {nc[0], nc[1], nc[2]};
+        int32_t quad = 0;
+        check(rt_scene_add_triangle_smooth(s_, pa, pb, pc, qa, qb, qc, material(mat), &quad), "rt_scene_add_triangle_smooth");
+        return quad;
+    }
+    uint32_t AddMesh(const std::vector<glm::vec3>& vertices, const std::vector<glm::vec3>& normals, const std::vector<uint32_t>& indices, const std::vector<uint32_t>& normal_indices,
+                     const Material* mat, float scale = 1.0f, float rotate_y_degrees = 0.0f, glm::vec3 translate = glm::vec3(0.0f), int32_t* out_first = nullptr) {
+        std::vector<float> xyz, nrm;
+        for (const glm::vec3& p : vertices) { xyz.push_back(p[0]); xyz.push_back(p[1]); xyz.push_back(p[2]); }
+        for (const glm::vec3& n : normals) { nrm.push_back(n[0]); nrm.push_back(n[1]); nrm.push_back(n[2]); }
+        if (!normal_indices.empty() && normal_indices.size() != indices.size()) throw std::runtime_error("AddMesh: one normal index per vertex index");
+        const float t[3] = {translate[0], translate[1], translate[2]};
+        uint32_t added = 0;
+        check(rt_scene_add_mesh_smooth(s_, (uint32_t)vertices.size(), xyz.data(), (uint32_t)normals.size(), nrm.data(), (uint32_t)(indices.size() / 3), indices.data(),
+                                       normal_indices.empty() ? nullptr : normal_indices.data(), material(mat), scale, rotate_y_degrees, t, out_first, &added),
+              "rt_scene_add_mesh_smooth");
+        return added;
+    }
     void perlin(uint64_t seed) { check(rt_scene_set_perlin(s_, seed), "rt_scene_set_perlin"); }
     void image(uint32_t w, uint32_t h, const uint8_t* rgb) { check(rt_scene_set_image(s_, w, h, rgb), "rt_scene_set_image"); }
     void background(const Background& b) {
@@ -524,7 +545,14 @@ class Renderer {
         mm.cam = cam;
         if (n_gpus > 1) rt06::check(rt_multi_renderer_create(&cfg, cam, &wf, n_gpus, nullptr, &mm.mr), "Renderer::MakeRenderer");
         else rt06::check(rt_renderer_create(&cfg, cam, &wf, &mm.r), "Renderer::MakeRenderer");
-        return Renderer(mm);
+        Renderer made(mm);
+        if (world->kind() == Hittable::BVH_WORLD) {   // a scene with vertex normals brings its table along (smooth shading)
+            const rt_tri_normals* table = nullptr;
+            uint32_t n = 0;
+            rt06::check(rt_scene_vertex_normals(static_cast<const BVH*>(world)->scene, &table, &n), "rt_scene_vertex_normals");
+            if (n) made.SetShadingNormals(table, n);
+        }
+        return made;
     }
 
 public:
@@ -603,6 +631,11 @@ public:
     }
     // Light sampling (rt06.h; opt-in): Lambertian and checker hits draw from the mixture of their cosine distribution and the world's quad
     // lights, from the next Render() / Refine() on; a change restarts the refinement.  Refused for worlds and variants that have no such kernel.
+    // Smooth shading (extension; rt_renderer_shading_normals): one record of three vertex normals per triangle of the world, or (nullptr, 0) for off; restarts a refinement
+    void SetShadingNormals(const rt_tri_normals* table, uint32_t n) {
+        if (m.mr) rt06::check(rt_multi_renderer_shading_normals(m.mr, table, n), "Renderer::SetShadingNormals");
+        else rt06::check(rt_renderer_shading_normals(m.r, table, n), "Renderer::SetShadingNormals");
+    }
     void SetLightSampling(bool on) {
         if (m.mr) rt06::check(rt_multi_renderer_light_sampling_enable(m.mr, on ? 1u : 0u), "Renderer::SetLightSampling");
         else rt06::check(rt_renderer_light_sampling_enable(m.r, on ? 1u : 0u), "Renderer::SetLightSampling");

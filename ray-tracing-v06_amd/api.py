@@ -147,23 +147,52 @@ class Scene:
         check(lib().rt_scene_add_quad(self.h, v3(Q), v3(u), v3(v), mat, C.byref(out)))
         return out.value
 
-    def MakeTriangle(self, a, b, c, mat):
-        """tri of "The Next Week" from its three vertices (extension, not in the reference): a quad of kind 1; returns its quad index."""
+    def MakeTriangle(self, a, b, c, mat, normals=None):
+        """tri of "The Next Week" from its three vertices (extension, not in the reference): a quad of kind 1; returns its quad index.
+        normals: one normal per vertex, (3, 3), for smooth shading (rt_scene_add_triangle_smooth)."""
         out = C.c_int32()
-        check(lib().rt_scene_add_triangle(self.h, v3(a), v3(b), v3(c), mat, C.byref(out)))
+        if normals is None:
+            check(lib().rt_scene_add_triangle(self.h, v3(a), v3(b), v3(c), mat, C.byref(out)))
+        else:
+            na, nb, nc = np.asarray(normals, dtype=np.float32).reshape(3, 3)
+            check(lib().rt_scene_add_triangle_smooth(self.h, v3(a), v3(b), v3(c), v3(na), v3(nb), v3(nc), mat, C.byref(out)))
+            self._smooth = True
         return out.value
 
-    def MakeMesh(self, vertices, faces, mat, scale=1.0, rotate_y=0.0, translate=(0, 0, 0)):
+    def MakeMesh(self, vertices, faces, mat, scale=1.0, rotate_y=0.0, translate=(0, 0, 0), normals=None, normal_faces=None):
         """An indexed triangle mesh (extension): vertices (n, 3), faces (m, 3); every vertex is scaled, rotated about y (degrees) and translated
-        as MakeBox does it.  Degenerate faces are skipped.  Returns (index of the first triangle added, number added)."""
+        as MakeBox does it.  Degenerate faces are skipped.  Returns (index of the first triangle added, number added).
+        normals (k, 3): vertex normals for smooth shading, rotated with the mesh and normalised; normal_faces (m, 3): per face the
+        indices into them (default: the faces' vertex indices)."""
         xyz = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
         idx = np.ascontiguousarray(faces, dtype=np.int64).reshape(-1, 3)
         if idx.size and (idx.min() < 0 or idx.max() > 0xffffffff):
             raise ValueError("MakeMesh: a face index is negative or does not fit 32 bits")
         idx = np.ascontiguousarray(idx, dtype=np.uint32)
         first, added = C.c_int32(), C.c_uint32()
-        check(lib().rt_scene_add_mesh(self.h, xyz.shape[0], xyz, idx.shape[0], idx, mat, scale, rotate_y, v3(translate), C.byref(first), C.byref(added)))
+        if normals is None:
+            if normal_faces is not None:
+                raise ValueError("MakeMesh: normal_faces without normals")
+            check(lib().rt_scene_add_mesh(self.h, xyz.shape[0], xyz, idx.shape[0], idx, mat, scale, rotate_y, v3(translate), C.byref(first), C.byref(added)))
+            return first.value, added.value
+        nrm = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+        nidx = None
+        if normal_faces is not None:
+            nidx = np.ascontiguousarray(normal_faces, dtype=np.int64).reshape(-1, 3)
+            if nidx.shape != idx.shape or (nidx.size and (nidx.min() < 0 or nidx.max() > 0xffffffff)):
+                raise ValueError("MakeMesh: normal_faces must hold one non-negative 32-bit index triple per face")
+            nidx = np.ascontiguousarray(nidx, dtype=np.uint32)
+        check(lib().rt_scene_add_mesh_smooth(self.h, xyz.shape[0], xyz, nrm.shape[0], nrm, idx.shape[0], idx, nidx.ctypes.data if nidx is not None else None,
+                                             mat, scale, rotate_y, v3(translate), C.byref(first), C.byref(added)))
+        self._smooth = True
         return first.value, added.value
+
+    def vertex_normals(self):
+        """The scene's vertex normals, one record per triangle of the flat world in its triangle order (rt_scene_vertex_normals): a structured array of
+        capi.TRI_NORMALS_DT (n0, n1, n2; nine zeros = a flat triangle); empty when no triangle of the scene has normals."""
+        ptr, n = C.c_void_p(), C.c_uint32()
+        check(lib().rt_scene_vertex_normals(self.h, C.byref(ptr), C.byref(n)))
+        return self._arr(ptr.value, n.value, capi.TRI_NORMALS_DT)
 
     def n_triangles(self):
         """How many of the flat world's quads are triangles (its last ones): rt_world_triangles."""
@@ -237,6 +266,8 @@ class Scene:
     def getWorldPtr(self):
         w = WorldFlat()
         check(lib().rt_scene_get_flat(self.h, C.byref(w)))
+        if getattr(self, "_smooth", False):   # the table travels beside the flat world: Renderer / MultiRenderer push it at creation (a scene without normals: no call)
+            w.vertex_normals = self.vertex_normals()
         return w
 
     def _arr(self, ptr, n, dt):
@@ -305,6 +336,21 @@ def light_sampling_mode(on):
     return int(on)
 
 
+def normals_table(table):
+    """a table of vertex normals as float32 (n, 9): from Scene.vertex_normals()'s records or an array of shape (n, 9) / (n, 3, 3)"""
+    a = np.asarray(table)
+    if a.dtype == capi.TRI_NORMALS_DT:
+        return np.ascontiguousarray(a).view(np.float32).reshape(-1, 9)
+    return np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 9)
+
+
+def _push_normals(fn, handle, table):
+    if table is None:
+        return fn(handle, None, 0)
+    t = normals_table(table)
+    return fn(handle, t.ctypes.data if len(t) else None, len(t))
+
+
 class Renderer:
     """Renderer (main/src/Renderer.h:12-47) over the C ABI."""
 
@@ -318,7 +364,10 @@ class Renderer:
         cfg = RenderConfig(render_width, render_height, samples_per_pixel, max_depth, seed, device, rank, world_size, variant)
         h = C.c_void_p()
         check(lib().rt_renderer_create(C.byref(cfg), C.byref(cam), C.byref(world), C.byref(h)))
-        return cls(h, cfg)
+        r = cls(h, cfg)
+        if len(getattr(world, "vertex_normals", ())):
+            r.shading_normals(world.vertex_normals)
+        return r
 
     def Render(self):
         check(lib().rt_renderer_render(self.h))
@@ -421,6 +470,17 @@ class Renderer:
         check(lib().rt_renderer_light_sampling_info(self.h, out))
         return {"enabled": bool(out[0]), "lights": out[1]}
 
+    def shading_normals(self, table):
+        """Smooth shading from the next launch on (rt_renderer_shading_normals): table = one record of three vertex normals per triangle of
+        the world (Scene.vertex_normals(), or anything of shape (n, 9) / (n, 3, 3)), None = off.  A change restarts the refinement."""
+        check(_push_normals(lib().rt_renderer_shading_normals, self.h, table))
+
+    def shading_normals_info(self):
+        """{'enabled', 'smooth'}: whether a table of vertex normals is on, and how many of its records are not flat."""
+        out = (C.c_uint32 * 2)()
+        check(lib().rt_renderer_shading_normals_info(self.h, out))
+        return {"enabled": bool(out[0]), "smooth": out[1]}
+
     def last_kernel_ms(self):
         ms = C.c_float()
         check(lib().rt_renderer_last_kernel_ms(self.h, C.byref(ms)))
@@ -502,7 +562,10 @@ class MultiRenderer:
         devs = (C.c_int32 * n_gpus)(*devices) if devices is not None else None
         h = C.c_void_p()
         check(lib().rt_multi_renderer_create(C.byref(cfg), C.byref(cam), C.byref(world), n_gpus, devs, C.byref(h)))
-        return cls(h, cfg)
+        m = cls(h, cfg)
+        if len(getattr(world, "vertex_normals", ())):
+            m.shading_normals(world.vertex_normals)
+        return m
 
     def Render(self):
         check(lib().rt_multi_renderer_render(self.h))
@@ -518,6 +581,10 @@ class MultiRenderer:
     def light_sampling(self, on=True):
         """rt_renderer_light_sampling_enable on every rank; `on` as Renderer.light_sampling takes it."""
         check(lib().rt_multi_renderer_light_sampling_enable(self.h, light_sampling_mode(on)))
+
+    def shading_normals(self, table):
+        """rt_renderer_shading_normals on every rank; `table` as Renderer.shading_normals takes it."""
+        check(_push_normals(lib().rt_multi_renderer_shading_normals, self.h, table))
 
     def DownloadRenderbuffer(self):
         out = np.zeros((self.cfg.height, self.cfg.width, 4), dtype=np.float32)
@@ -737,3 +804,25 @@ def probe_boxpair_filtered(boxes, rays, max_dist, device=0):
     check(lib().rt_probe_boxpair_filtered(device, n, np.ascontiguousarray(boxes, np.float32), np.ascontiguousarray(rays, np.float32),
                                           np.ascontiguousarray(max_dist, np.float32), out))
     return out
+
+
+def shading_normal_batch(tris, vn, rays, t):
+    """rt_shading_normal_batch (host only): the smooth-shading rule on hit i of triangle record tris[i] (capi.QUAD_DT) with vertex normals vn[i], ray rays[i]
+    (o, d) and hit distance t[i] -> (normal (n, 3) float32, interpolated (n,) uint32)"""
+    tris = np.ascontiguousarray(tris, dtype=capi.QUAD_DT)
+    vn, rays, t = normals_table(vn), np.ascontiguousarray(rays, np.float32).reshape(-1, 6), np.ascontiguousarray(t, np.float32)
+    n = len(tris)
+    assert len(vn) == n and len(rays) == n and len(t) == n
+    normal, took = np.zeros((n, 3), np.float32), np.zeros(n, np.uint32)
+    check(lib().rt_shading_normal_batch(n, tris.ctypes.data, vn.ctypes.data, rays, t, normal, took))
+    return normal, took
+
+
+def probe_shading_normal(world, table, rays, device=0):
+    """rt_probe_shading_normal: the world's walk, then the smooth-shading rule on a triangle hit -> (hit int32, normal (n, 3), interpolated uint32)"""
+    rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 7)
+    n = len(rays)
+    tab = normals_table(table) if table is not None else np.zeros((0, 9), np.float32)
+    hit, normal, took = np.zeros(n, np.int32), np.zeros((n, 3), np.float32), np.zeros(n, np.uint32)
+    check(lib().rt_probe_shading_normal(device, C.byref(world), tab.ctypes.data if len(tab) else None, len(tab), n, rays, hit, normal, took))
+    return hit, normal, took

@@ -29,6 +29,7 @@ vec3 = C.c_float * 3
 NODE_DT = np.dtype([("min", "<f4", 3), ("max", "<f4", 3), ("left", "<i4"), ("right", "<i4")])
 PRIM_DT = np.dtype([("c0", "<f4", 3), ("radius", "<f4"), ("c1", "<f4", 3), ("mat", "<u4")])
 MAT_DT = np.dtype([("albedo", "<f4", 3), ("param", "<f4"), ("albedo2", "<f4", 3), ("type", "<u4")])
+TRI_NORMALS_DT = np.dtype([("n0", "<f4", 3), ("n1", "<f4", 3), ("n2", "<f4", 3)])   # rt_tri_normals, 36 B
 QUAD_DT = np.dtype([("Q", "<f4", 3), ("D", "<f4"), ("u", "<f4", 3), ("mat", "<u4"), ("v", "<f4", 3), ("kind", "<u4"),
                     ("normal", "<f4", 3), ("pad1", "<f4"), ("w", "<f4", 3), ("pad2", "<f4")])
 
@@ -86,6 +87,8 @@ SYMBOLS = [
     "rt_renderer_kernel_form", "rt_world_lights", "rt_scene_cornell_lamp", "rt_world_light_table",
     "rt_scene_add_triangle", "rt_scene_add_mesh", "rt_world_triangles", "rt_renderer_kernel_triangles",
     "rt_world_light_tree", "rt_renderer_kernel_light_tree",
+    "rt_scene_add_triangle_smooth", "rt_scene_add_mesh_smooth", "rt_scene_vertex_normals", "rt_shading_normal_batch", "rt_renderer_shading_normals",
+    "rt_renderer_shading_normals_info", "rt_multi_renderer_shading_normals", "rt_probe_shading_normal",
 ]
 
 _lib = None
@@ -168,6 +171,15 @@ def lib():
     L.rt_scene_add_triangle.argtypes = [C.c_void_p, vec3, vec3, vec3, C.c_int32, P(C.c_int32)]
     L.rt_scene_add_mesh.argtypes = [C.c_void_p, C.c_uint32, f32p, C.c_uint32, u32p, C.c_int32, C.c_float, C.c_float, vec3, P(C.c_int32), P(C.c_uint32)]
     L.rt_world_triangles.argtypes = [P(WorldFlat), P(C.c_uint32)]
+    L.rt_scene_add_triangle_smooth.argtypes = [C.c_void_p, vec3, vec3, vec3, vec3, vec3, vec3, C.c_int32, P(C.c_int32)]
+    L.rt_scene_add_mesh_smooth.argtypes = [C.c_void_p, C.c_uint32, f32p, C.c_uint32, f32p, C.c_uint32, u32p, C.c_void_p, C.c_int32, C.c_float, C.c_float, vec3,
+                                           P(C.c_int32), P(C.c_uint32)]
+    L.rt_scene_vertex_normals.argtypes = [C.c_void_p, P(C.c_void_p), P(C.c_uint32)]
+    L.rt_shading_normal_batch.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p, f32p, f32p, f32p, u32p]
+    L.rt_renderer_shading_normals.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+    L.rt_renderer_shading_normals_info.argtypes = [C.c_void_p, C.c_uint32 * 2]
+    L.rt_multi_renderer_shading_normals.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+    L.rt_probe_shading_normal.argtypes = [C.c_int, P(WorldFlat), C.c_void_p, C.c_uint32, C.c_size_t, f32p, i32p, f32p, u32p]
     L.rt_scene_set_background.argtypes = [C.c_void_p, C.c_uint32, vec3]
     L.rt_scene_set_perlin.argtypes = [C.c_void_p, C.c_uint64]
     L.rt_scene_set_image.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]

@@ -60,10 +60,9 @@ struct AovParams {
     const float4* prim_d;
 };
 
-template <int WALK>
-__global__ __launch_bounds__(RT_AOV_BLOCK) void aov_kernel(AovParams p, float4* __restrict__ aov) {
-    __shared__ int32_t lds_i[WALK == RT_AOV_WALK_LIST ? 1u : RT_MAX_STACK * RT_AOV_BLOCK];
-    __shared__ float lds_f[WALK == RT_AOV_WALK_QUEUE ? RT_MAX_STACK * RT_AOV_BLOCK : 1u];
+// SMOOTH (aov_kernel_smooth): a hit on a triangle — unified index >= first_tri — takes its normal through shading_normal() from the table's record
+template <int WALK, bool SMOOTH>
+__device__ __forceinline__ void aov_body(const AovParams& p, float4* __restrict__ aov, int32_t* lds_i, float* lds_f, const rt_tri_normals* vn, uint32_t first_tri) {
     const uint32_t L = blockIdx.x * RT_AOV_BLOCK + threadIdx.x;
     if (L >= p.tm.n_local_tiles * RT_TILE * RT_TILE) return;
     uint32_t gid;
@@ -80,6 +79,7 @@ __global__ __launch_bounds__(RT_AOV_BLOCK) void aov_kernel(AovParams p, float4* 
         f3 alb = mk3(1.0f);
         if (aov_first_hit<WALK>(p.world, ray, rec, lds_i, lds_f)) {
             alb = aov_albedo(p.world.mats[rec.mat], ray, rec);
+            if (SMOOTH && (uint32_t)rec.prim >= first_tri) shading_normal_flat(p.world.quads[(uint32_t)rec.prim - p.world.n_prims], vn[(uint32_t)rec.prim - first_tri], ray, rec.distance, rec.normal);
             g.x += rec.normal.x; g.y += rec.normal.y; g.z += rec.normal.z; g.w += rec.distance;
             a.w += 1.0f;
         }
@@ -88,6 +88,20 @@ __global__ __launch_bounds__(RT_AOV_BLOCK) void aov_kernel(AovParams p, float4* 
     }
     aov[2u * L] = g;
     aov[2u * L + 1u] = a;
+}
+template <int WALK>
+__global__ __launch_bounds__(RT_AOV_BLOCK) void aov_kernel(AovParams p, float4* __restrict__ aov) {
+    __shared__ int32_t lds_i[WALK == RT_AOV_WALK_LIST ? 1u : RT_MAX_STACK * RT_AOV_BLOCK];
+    __shared__ float lds_f[WALK == RT_AOV_WALK_QUEUE ? RT_MAX_STACK * RT_AOV_BLOCK : 1u];
+    aov_body<WALK, false>(p, aov, lds_i, lds_f, nullptr, 0u);
+}
+// the same pass with a table of vertex normals on (lists and stack-walked BVHs: what rt_renderer_shading_normals accepts)
+template <int WALK>
+__global__ __launch_bounds__(RT_AOV_BLOCK) void aov_kernel_smooth(AovParams p, float4* __restrict__ aov, const rt_tri_normals* __restrict__ vn, uint32_t first_tri) {
+    static_assert(WALK == RT_AOV_WALK_LIST || WALK == RT_AOV_WALK_STACK, "vertex normals: lists and stack-walked BVHs");
+    __shared__ int32_t lds_i[WALK == RT_AOV_WALK_LIST ? 1u : RT_MAX_STACK * RT_AOV_BLOCK];
+    __shared__ float lds_f[1u];
+    aov_body<WALK, true>(p, aov, lds_i, lds_f, vn, first_tri);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -206,6 +206,21 @@ struct rt_renderer {
              bool on() const { return mode != RT_LIGHT_SAMPLING_OFF; }
              static uint32_t slot(uint32_t m) { return m == RT_LIGHT_SAMPLING_TREE ? 3u : m == RT_LIGHT_SAMPLING_MESH ? 2u : m - 1u; }   // modes 1, 2, 4, 16
              const LightTable& cur() const { return tab[slot(mode)]; } } nee;
+    // smooth shading (rt_renderer_shading_normals): the table as given (9 floats per triangle of the world), a flat copy for the feature pass, and
+    // the images the triangle kernels launch on while it is on — the plain image and, per light-sampling mode already built, the image with that mode's light
+    // table — each followed by the header (1, -, -, -) and the table.  Off, every launch gets the image it always got, whose header is zero.
+    struct { bool on = false; uint32_t n_smooth = 0; std::vector<float> host; DevBuf table, blob, nee_blob[4]; } vn;
+    // `src` holds staged_vec4 units of image (and a zero header); dst = the same units, then the header that says a table follows, then the table
+    int image_with_normals(const DevBuf& src, uint32_t staged_vec4, DevBuf& dst) const {
+        const size_t tab_vec4 = (vn.host.size() * sizeof(float) + 15u) / 16u;
+        std::vector<uint4> tail(1u + tab_vec4, make_uint4(0u, 0u, 0u, 0u));
+        tail[0].x = 1u;
+        std::memcpy(&tail[1], vn.host.data(), vn.host.size() * sizeof(float));
+        HIP_TRY(dst.alloc(((size_t)staged_vec4 + tail.size()) * sizeof(uint4)));
+        HIP_TRY(hipMemcpy(dst.p, src.p, (size_t)staged_vec4 * sizeof(uint4), hipMemcpyDeviceToDevice));
+        HIP_TRY(hipMemcpy(dst.as<uint4>() + staged_vec4, tail.data(), tail.size() * sizeof(uint4), hipMemcpyHostToDevice));
+        return RT_OK;
+    }
     // denoiser (rt_renderer_denoise): guide records, the two colour buffers the iterations ping-pong, the output frame; allocated at first use
     DevBuf dn_g0, dn_g1, dn_a, dn_b, dn_out;
     // ordering between refine steps and the filter, whichever streams the caller gives them: refine_ev = end of the last refine step (the filter
@@ -447,7 +462,8 @@ struct rt_renderer {
         frame_params(p, spp);
         p.scene = scene.packed;
         p.scene.n_top = scene.big ? n_top : 0u;
-        if (nee.on()) { p.scene.blob = nee.cur().blob.as<uint4>(); p.scene.blob_vec4 += nee.cur().table_vec4; }   // the same image with the light table behind it
+        if (nee.on()) { p.scene.blob = (vn.on ? vn.nee_blob[nee.slot(nee.mode)] : nee.cur().blob).as<uint4>(); p.scene.blob_vec4 += nee.cur().table_vec4; }   // the same image with the light table behind it
+        else if (vn.on) p.scene.blob = vn.blob.as<uint4>();   // ... with the vertex normals behind it (§21)
         p.samples = samples.as<float4>();
         p.inner_keep = tune[0] ? tune[0] : 1u; p.shade_min = tune[1]; p.leaf_min = tune[2];
         const size_t n_pass = n_local_pixels(tm) * pass_spp;   // 16-B records per array
@@ -517,6 +533,11 @@ struct rt_renderer {
         p.tm = sp.tm; p.world = sp.world;
         p.pass_first_s = sp.pass_first_s; p.pass_spp = sp.pass_spp; p.n_take = upto - sp.pass_first_s;
         p.prim_o = sp.prim_o; p.prim_d = sp.prim_d;
+        if (vn.on) {   // §21: the first-hit normal is the shading normal; a table is on only where the world is a list or a BVH walked by the stack
+            const uint32_t first_tri = scene.dw.n_prims + scene.dw.n_quads - scene.n_triangles;
+            if (scene.dw.kind == RT_WORLD_LIST) aov_kernel_smooth<RT_AOV_WALK_LIST><<<grid, block, 0, st>>>(p, aov.as<float4>(), vn.table.as<rt_tri_normals>(), first_tri);
+            else aov_kernel_smooth<RT_AOV_WALK_STACK><<<grid, block, 0, st>>>(p, aov.as<float4>(), vn.table.as<rt_tri_normals>(), first_tri);
+        } else
         aov_kernel_for(scene.dw)<<<grid, block, 0, st>>>(p, aov.as<float4>());
         HIP_TRY(hipGetLastError());
         return RT_OK;
@@ -680,7 +701,8 @@ extern "C" int rt_renderer_light_sampling_enable(rt_renderer* r, uint32_t on) {
                 std::memcpy(&table[0].y, &t.cdf[t.n - 1u], 4);   // A
                 std::memcpy(&table[1u + 2u * t.n], t.nodes.data(), t.nodes.size() * sizeof(float));
             }
-            HIP_TRY(t.blob.alloc(((size_t)r->scene.packed.blob_vec4 + table_vec4) * sizeof(uint4)));
+            table.push_back(make_uint4(0u, 0u, 0u, 0u));   // the vertex-normal header behind this image (§21): zero = no table follows
+            HIP_TRY(t.blob.alloc(((size_t)r->scene.packed.blob_vec4 + table.size()) * sizeof(uint4)));
             HIP_TRY(hipMemcpy(t.blob.p, r->scene.blob.p, (size_t)r->scene.packed.blob_vec4 * sizeof(uint4), hipMemcpyDeviceToDevice));
             HIP_TRY(hipMemcpy(t.blob.as<uint4>() + r->scene.packed.blob_vec4, table.data(), table.size() * sizeof(uint4), hipMemcpyHostToDevice));
             uint32_t lds_set = lds;   // one kernel may serve several tables: the attribute covers the largest of its own
@@ -693,6 +715,8 @@ extern "C" int rt_renderer_light_sampling_enable(rt_renderer* r, uint32_t on) {
             t.kernel = k;
             t.built = true;
         }
+        if (r->vn.on && !r->vn.nee_blob[r->nee.slot(on)].p)   // this mode's image once more, with the vertex normals behind its light table
+            if (const int rc = r->image_with_normals(t.blob, r->scene.packed.blob_vec4 + t.table_vec4, r->vn.nee_blob[r->nee.slot(on)])) return rc;
         r->nee.kernel = t.kernel;
     }
     r->nee.mode = on;       // of the NEXT launch; launches already enqueued keep their kernel and their image (the images with the tables stay allocated)
@@ -706,6 +730,56 @@ extern "C" int rt_renderer_light_sampling_info(rt_renderer* r, uint32_t out[2]) 
     const rt_renderer::LightTable& t = r->nee.tab[r->nee.on() ? r->nee.slot(r->nee.mode) : 0u];
     out[0] = r->nee.mode;
     out[1] = t.refused.empty() ? t.n : 0u;
+    return RT_OK;
+}
+
+// Smooth shading.  Off: every launch is what it was.  On: the same kernels on copies of their images that end with (1, -, -, -) and the table.
+extern "C" int rt_renderer_shading_normals(rt_renderer* r, const rt_tri_normals* table, uint32_t n) {
+    if (!r) return rt_fail(RT_ERR_INVALID, "rt_renderer_shading_normals: null renderer");
+    if ((table == nullptr) != (n == 0u)) return rt_fail(RT_ERR_INVALID, "rt_renderer_shading_normals: a table and its count go together (NULL, 0 turns it off)");
+    uint32_t n_smooth = 0;
+    if (n) {
+        if (r->variant < 2) return rt_fail(RT_ERR_INVALID, "rt_renderer_shading_normals: the baseline kernel (variant 1) reads no table of vertex normals; use variant 0, 2 or 3");
+        if (r->scene.queue) return rt_fail(RT_ERR_INVALID, "rt_renderer_shading_normals: a world with a queue or wide4 traversal renders on lane walks that read no table of vertex normals (RT_TRAVERSAL_STACK and lists do)");
+        if (r->variant == 5 || r->tol) return rt_fail(RT_ERR_INVALID, "rt_renderer_shading_normals: kernel variant %u renders no triangles", r->tol ? 6u : 5u);
+        if (n != r->scene.n_triangles) return rt_fail(RT_ERR_INVALID, "rt_renderer_shading_normals: %u records for a world of %u triangles", n, r->scene.n_triangles);
+        for (uint32_t i = 0; i < n; i++) {
+            const float* v = table[i].n0;   // nine floats: n0, n1, n2
+            uint32_t n_zero = 0;
+            for (int k = 0; k < 9; k++)
+                if (!std::isfinite(v[k])) return rt_fail(RT_ERR_INVALID, "rt_renderer_shading_normals: record %u: a value that is not finite", i);
+            for (int k = 0; k < 3; k++)
+                if (v[3 * k] == 0.0f && v[3 * k + 1] == 0.0f && v[3 * k + 2] == 0.0f) n_zero++;
+            if (n_zero != 0u && n_zero != 3u) return rt_fail(RT_ERR_INVALID, "rt_renderer_shading_normals: record %u: %u of its three normals are zero (all zero = a flat triangle, or none)", i, n_zero);
+            if (n_zero == 0u) n_smooth++;
+        }
+    }
+    const size_t bytes = (size_t)n * sizeof(rt_tri_normals);
+    if (n ? (r->vn.on && r->vn.host.size() * sizeof(float) == bytes && std::memcmp(r->vn.host.data(), table, bytes) == 0) : !r->vn.on) return RT_OK;   // nothing changes, the refinement goes on
+    if (const int rc = wait_last_call(r)) return rc;   // launches already enqueued read the images that are replaced below
+    r->vn.on = false;
+    r->vn.table.release(); r->vn.blob.release();
+    for (DevBuf& b : r->vn.nee_blob) b.release();
+    r->refine_done = 0;   // samples shaded with other normals belong to another frame
+    r->aov_done = 0;
+    if (!n) { r->vn.host.clear(); r->vn.n_smooth = 0; return RT_OK; }
+    r->vn.host.assign(table[0].n0, table[0].n0 + (size_t)n * 9u);
+    r->vn.n_smooth = n_smooth;
+    HIP_TRY(r->vn.table.upload(r->vn.host.data(), bytes));
+    if (const int rc = r->image_with_normals(r->scene.blob, r->scene.packed.blob_vec4, r->vn.blob)) return rc;
+    for (const uint32_t mode : {RT_LIGHT_SAMPLING_QUADS, RT_LIGHT_SAMPLING_ALL, RT_LIGHT_SAMPLING_MESH, RT_LIGHT_SAMPLING_TREE}) {
+        const rt_renderer::LightTable& t = r->nee.tab[r->nee.slot(mode)];
+        if (t.built)
+            if (const int rc = r->image_with_normals(t.blob, r->scene.packed.blob_vec4 + t.table_vec4, r->vn.nee_blob[r->nee.slot(mode)])) return rc;
+    }
+    r->vn.on = true;
+    return RT_OK;
+}
+
+extern "C" int rt_renderer_shading_normals_info(rt_renderer* r, uint32_t out[2]) {
+    if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_shading_normals_info: null argument");
+    out[0] = r->vn.on ? 1u : 0u;
+    out[1] = r->vn.on ? r->vn.n_smooth : 0u;
     return RT_OK;
 }
 

@@ -143,6 +143,29 @@ RT_HD bool quad_closest_intersection(f3 Q, float D, f3 u, f3 v, f3 n, f3 w, uint
     return true;
 }
 
+// Smooth shading (rt06.h: rt_tri_normals): the shading normal at hit_p on the triangle (Q, u, v, w) with the vertex normals n0, n1, n2, given
+// the flat normal `normal` that already faces against the ray.  image_value_quad's planar coordinates, the interpolated normal g, and two ways back to the flat
+// one: g has no direction (an all-zero record, cancellation, a NaN), or the interpolated normal does not face the ray — every hit keeps the invariant "the
+// normal faces against the ray".  Returns whether `normal` was replaced.  Only + - * / sqrt and comparisons, each rounded on its own: the streaming kernels,
+// the feature pass, the probe and rt_shading_normal_batch call this one function, and numpy float32 restates it bit for bit.
+RT_HD bool shading_normal(f3 Q, f3 u, f3 v, f3 w, f3 n0, f3 n1, f3 n2, f3 ray_d, f3 hit_p, f3& normal) {
+    f3 planar = hit_p - Q;
+    float alpha = dot(w, cross(planar, v));
+    float beta = dot(w, cross(u, planar));
+    const f3 g = (n0 * ((1.0f - alpha) - beta) + n1 * alpha) + n2 * beta;
+    const float l2 = dot(g, g);
+    if (!(l2 > 0.0f)) return false;
+    f3 s = g / sqrtf(l2);
+    if (dot(s, normal) < 0.0f) s = -s;
+    if (!(dot(ray_d, s) < 0.0f)) return false;
+    normal = s;
+    return true;
+}
+// the same on a hit of a world walk: rec.prim is the unified index of a triangle whose record in the table is vn (the caller has found it)
+RT_HD bool shading_normal_flat(const rt_quad& q, const rt_tri_normals& vn, const Ray& ray, float t, f3& normal) {
+    return shading_normal(ld3(q.Q), ld3(q.u), ld3(q.v), ld3(q.w), ld3(vn.n0), ld3(vn.n1), ld3(vn.n2), ray.d, ray_at(ray, t), normal);
+}
+
 __device__ inline bool any_prim_closest_intersection(const DeviceWorld& w, int32_t idx, const Ray& ray, HitRec& rec, Rng* rng) {
     if ((uint32_t)idx >= w.n_prims) {
         const rt_quad& q = w.quads[(uint32_t)idx - w.n_prims];

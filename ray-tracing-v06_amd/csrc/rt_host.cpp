@@ -151,6 +151,8 @@ struct rt_scene {
     std::vector<rt_prim> prims;
     std::vector<rt_quad> quads;           // the parallelograms, then the n_tris triangles (rt_quad::kind), whatever the order of the calls
     uint32_t n_tris = 0;
+    std::vector<rt_tri_normals> tri_vn;   // vertex normals: one record per triangle, in the triangles' order (nine zeros = flat); moves with them
+    uint32_t n_smooth = 0;                // how many of those records are not flat: 0 = the scene has no table
     uint32_t background = 0;
     float background_color[3] = {0.0f, 0.0f, 0.0f};
     uint32_t traversal = RT_TRAVERSAL_STACK;
@@ -282,9 +284,34 @@ extern "C" int rt_scene_add_triangle(rt_scene* s, const float a[3], const float 
     if (!tri_record(ld3(a), ld3(b), ld3(c), (uint32_t)mat, q))
         return rt_fail(RT_ERR_INVALID, "rt_scene_add_triangle: degenerate triangle (the squared length of cross(b - a, c - a) is not finite and > 0)");
     s->quads.push_back(q);
+    s->tri_vn.push_back(rt_tri_normals{});
     s->n_tris++;
     s->world_set = false;
     if (out_quad) *out_quad = (int32_t)s->quads.size() - 1;
+    return RT_OK;
+}
+// a vertex normal as the scene keeps it: finite, of non-zero length, normalised (x / sqrt(dot(x, x)) per component); false otherwise
+static bool unit_normal(f3 x, float out[3]) {
+    const float l2 = dot(x, x);
+    if (!(std::isfinite(l2) && l2 > 0.0f)) return false;
+    st3(out, x / sqrtf(l2));
+    return std::isfinite(out[0]) && std::isfinite(out[1]) && std::isfinite(out[2]) && !(out[0] == 0.0f && out[1] == 0.0f && out[2] == 0.0f);
+}
+extern "C" int rt_scene_add_triangle_smooth(rt_scene* s, const float a[3], const float b[3], const float c[3], const float na[3], const float nb[3], const float nc[3],
+                                            int32_t mat, int32_t* out_quad) {
+    if (!s || !a || !b || !c || !na || !nb || !nc) return rt_fail(RT_ERR_INVALID, "rt_scene_add_triangle_smooth: null argument");
+    rt_tri_normals vn;
+    if (!unit_normal(ld3(na), vn.n0) || !unit_normal(ld3(nb), vn.n1) || !unit_normal(ld3(nc), vn.n2))
+        return rt_fail(RT_ERR_INVALID, "rt_scene_add_triangle_smooth: a vertex normal is not finite or has zero length");
+    if (const int rc = rt_scene_add_triangle(s, a, b, c, mat, out_quad)) return rc;
+    s->tri_vn.back() = vn;
+    s->n_smooth++;
+    return RT_OK;
+}
+extern "C" int rt_scene_vertex_normals(const rt_scene* s, const rt_tri_normals** out, uint32_t* out_n) {
+    if (!s || !out || !out_n) return rt_fail(RT_ERR_INVALID, "rt_scene_vertex_normals: null argument");
+    *out = s->n_smooth ? s->tri_vn.data() : nullptr;
+    *out_n = s->n_smooth ? (uint32_t)s->tri_vn.size() : 0u;
     return RT_OK;
 }
 extern "C" int rt_scene_set_background(rt_scene* s, uint32_t mode, const float color[3]) {
@@ -309,6 +336,7 @@ struct Item {
     bool is_quad;
     rt_prim p;
     rt_quad q;
+    rt_tri_normals vn;   // of a triangle: its vertex normals travel with it
 };
 struct Builder {
     std::vector<Item> arr;
@@ -422,8 +450,9 @@ static int build_bvh(rt_scene* s, int builder) {
     s->nodes.clear();
     Builder B(s->nodes);
     B.arr.reserve(s->prims.size() + s->quads.size());
-    for (const rt_prim& p : s->prims) B.arr.push_back(Item{prim_bounds(p), false, p, rt_quad{}});
-    for (const rt_quad& q : s->quads) B.arr.push_back(Item{quad_record_bounds(q), true, rt_prim{}, q});
+    const size_t n_plain = s->quads.size() - s->n_tris;
+    for (const rt_prim& p : s->prims) B.arr.push_back(Item{prim_bounds(p), false, p, rt_quad{}, rt_tri_normals{}});
+    for (size_t i = 0; i < s->quads.size(); i++) B.arr.push_back(Item{quad_record_bounds(s->quads[i]), true, rt_prim{}, s->quads[i], i >= n_plain ? s->tri_vn[i - n_plain] : rt_tri_normals{}});
     int32_t root;
     if (builder == 0) root = B.rec1(0, (int)B.arr.size());
     else if (builder == 1) root = B.rec2(0, (int)B.arr.size());
@@ -436,6 +465,7 @@ static int build_bvh(rt_scene* s, int builder) {
         for (size_t i = 0; i < B.arr.size(); i++) {
             if (B.arr[i].is_quad) {
                 size_t& at = B.arr[i].q.kind == RT_QUAD_TRIANGLE ? ti : qi;
+                if (B.arr[i].q.kind == RT_QUAD_TRIANGLE) s->tri_vn[at - n_plain] = B.arr[i].vn;
                 s->quads[at] = B.arr[i].q; unified[i] = (int32_t)(ns + at); at++;
             }
             else { s->prims[si] = B.arr[i].p; unified[i] = (int32_t)si; si++; }
@@ -917,30 +947,60 @@ extern "C" int rt_scene_add_box(rt_scene* s, const float a[3], const float b[3],
 }
 
 // An indexed mesh as triangles: every vertex p -> rot_y(p * scale) + translate (cornell_box's order and arithmetic), then tri_record per face.
-extern "C" int rt_scene_add_mesh(rt_scene* s, uint32_t n_vertices, const float* xyz, uint32_t n_triangles, const uint32_t* indices, int32_t mat, float scale,
-                                 float rotate_y_degrees, const float translate[3], int32_t* out_first, uint32_t* out_added) {
-    if (!s || (n_vertices && !xyz) || (n_triangles && !indices)) return rt_fail(RT_ERR_INVALID, "rt_scene_add_mesh: null argument");
-    if (mat < 0 || (size_t)mat >= s->mats.size()) return rt_fail(RT_ERR_INVALID, "rt_scene_add_mesh: material %d out of range", mat);
-    if (!std::isfinite(scale) || !std::isfinite(rotate_y_degrees)) return rt_fail(RT_ERR_INVALID, "rt_scene_add_mesh: scale and rotation must be finite");
+// normals (rt_scene_add_mesh_smooth; null for the flat mesh): rot_y of each, then unit_normal; a face takes normal_indices' three, or its vertex indices.
+static int add_mesh(const char* who, rt_scene* s, uint32_t n_vertices, const float* xyz, uint32_t n_normals, const float* normals, uint32_t n_triangles, const uint32_t* indices,
+                    const uint32_t* normal_indices, int32_t mat, float scale, float rotate_y_degrees, const float translate[3], int32_t* out_first, uint32_t* out_added) {
+    if (!s || (n_vertices && !xyz) || (n_triangles && !indices)) return rt_fail(RT_ERR_INVALID, "%s: null argument", who);
+    if (mat < 0 || (size_t)mat >= s->mats.size()) return rt_fail(RT_ERR_INVALID, "%s: material %d out of range", who, mat);
+    if (!std::isfinite(scale) || !std::isfinite(rotate_y_degrees)) return rt_fail(RT_ERR_INVALID, "%s: scale and rotation must be finite", who);
     for (size_t i = 0; i < (size_t)n_triangles * 3u; i++)
         if (indices[i] >= n_vertices)
-            return rt_fail(RT_ERR_INVALID, "rt_scene_add_mesh: face %zu: vertex index %u out of range (%u vertices)", i / 3u, indices[i], n_vertices);
+            return rt_fail(RT_ERR_INVALID, "%s: face %zu: vertex index %u out of range (%u vertices)", who, i / 3u, indices[i], n_vertices);
+    const uint32_t* nidx = normal_indices ? normal_indices : indices;
+    if (normals)
+        for (size_t i = 0; i < (size_t)n_triangles * 3u; i++)
+            if (nidx[i] >= n_normals)
+                return rt_fail(RT_ERR_INVALID, "%s: face %zu: normal index %u out of range (%u normals)", who, i / 3u, nidx[i], n_normals);
     const float rad = radians(rotate_y_degrees), c = cosf(rad), sn = sinf(rad);
     const f3 offset = translate ? ld3(translate) : mk3(0.0f);
     std::vector<f3> pts(n_vertices);
     for (uint32_t i = 0; i < n_vertices; i++) pts[i] = rot_y(ld3(xyz + 3 * (size_t)i) * scale, c, sn) + offset;
+    std::vector<float> unit((size_t)(normals ? n_normals : 0u) * 3u);
+    for (uint32_t i = 0; normals && i < n_normals; i++)
+        if (!unit_normal(rot_y(ld3(normals + 3 * (size_t)i), c, sn), &unit[3 * (size_t)i]))
+            return rt_fail(RT_ERR_INVALID, "%s: normal %u is not finite or has zero length", who, i);
     std::vector<rt_quad> tris;
+    std::vector<rt_tri_normals> vns;
     tris.reserve(n_triangles);
     for (uint32_t f = 0; f < n_triangles; f++) {
         rt_quad q;
-        if (tri_record(pts[indices[3 * (size_t)f]], pts[indices[3 * (size_t)f + 1]], pts[indices[3 * (size_t)f + 2]], (uint32_t)mat, q)) tris.push_back(q);
+        if (!tri_record(pts[indices[3 * (size_t)f]], pts[indices[3 * (size_t)f + 1]], pts[indices[3 * (size_t)f + 2]], (uint32_t)mat, q)) continue;
+        tris.push_back(q);
+        rt_tri_normals vn{};
+        if (normals) {
+            std::memcpy(vn.n0, &unit[3 * (size_t)nidx[3 * (size_t)f]], 12); std::memcpy(vn.n1, &unit[3 * (size_t)nidx[3 * (size_t)f + 1]], 12);
+            std::memcpy(vn.n2, &unit[3 * (size_t)nidx[3 * (size_t)f + 2]], 12);
+        }
+        vns.push_back(vn);
     }
     if (out_first) *out_first = (int32_t)s->quads.size();
     if (out_added) *out_added = (uint32_t)tris.size();
     s->quads.insert(s->quads.end(), tris.begin(), tris.end());
+    s->tri_vn.insert(s->tri_vn.end(), vns.begin(), vns.end());
     s->n_tris += (uint32_t)tris.size();
+    if (normals) s->n_smooth += (uint32_t)tris.size();
     if (!tris.empty()) s->world_set = false;
     return RT_OK;
+}
+extern "C" int rt_scene_add_mesh(rt_scene* s, uint32_t n_vertices, const float* xyz, uint32_t n_triangles, const uint32_t* indices, int32_t mat, float scale,
+                                 float rotate_y_degrees, const float translate[3], int32_t* out_first, uint32_t* out_added) {
+    return add_mesh("rt_scene_add_mesh", s, n_vertices, xyz, 0u, nullptr, n_triangles, indices, nullptr, mat, scale, rotate_y_degrees, translate, out_first, out_added);
+}
+extern "C" int rt_scene_add_mesh_smooth(rt_scene* s, uint32_t n_vertices, const float* xyz, uint32_t n_normals, const float* normals, uint32_t n_triangles,
+                                        const uint32_t* indices, const uint32_t* normal_indices, int32_t mat, float scale, float rotate_y_degrees, const float translate[3],
+                                        int32_t* out_first, uint32_t* out_added) {
+    if (!normals) return rt_fail(RT_ERR_INVALID, "rt_scene_add_mesh_smooth: null normals (rt_scene_add_mesh adds a flat mesh)");
+    return add_mesh("rt_scene_add_mesh_smooth", s, n_vertices, xyz, n_normals, normals, n_triangles, indices, normal_indices, mat, scale, rotate_y_degrees, translate, out_first, out_added);
 }
 
 // The image the book loads from earthmap.jpg is not redistributable here: a synthetic 256 x 128 "planet" (integer

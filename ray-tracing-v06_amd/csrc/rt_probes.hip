@@ -36,6 +36,23 @@ __global__ void probe_trace_kernel(DeviceWorld w, size_t n, const float* rays, i
     t[i] = rec.distance; prim[i] = rec.prim;
     st3(normal + 3 * i, rec.normal);
 }
+// the world's own walk, then the smooth-shading rule (shading_normal) on a triangle hit: vn = one record per triangle, or null
+__global__ void probe_shading_normal_kernel(DeviceWorld w, const rt_tri_normals* vn, uint32_t first_tri, size_t n, const float* rays, int32_t* hit, float* normal, uint32_t* interpolated) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Ray r;
+    r.o = ld3(rays + 7 * i); r.d = ld3(rays + 7 * i + 3); r.time = rays[7 * i + 6];
+    HitRec rec;
+    rec.distance = RT_MISS_DIST; rec.normal = mk3(0.0f); rec.prim = -1; rec.mat = 0;
+    Rng g;
+    g.init(0u, (uint32_t)i, 0u, 0x7ACEu);
+    const bool h = world_closest_intersection(w, r, rec, &g);
+    bool took = false;
+    if (h && vn && (uint32_t)rec.prim >= first_tri) took = shading_normal_flat(w.quads[(uint32_t)rec.prim - w.n_prims], vn[(uint32_t)rec.prim - first_tri], r, rec.distance, rec.normal);
+    hit[i] = h ? 1 : 0;
+    interpolated[i] = took ? 1u : 0u;
+    st3(normal + 3 * i, rec.normal);
+}
 // SphereHittable / MovingSphereHittable::ClosestIntersection on one sphere per ray, rec.distance preset by the caller: the leaf
 // test every traversal calls (prim_closest_intersection), as a plain sphere (material 0 = a Lambertian, the moving bit kept)
 __global__ void probe_sphere_hit_kernel(size_t n, const rt_prim* prims, const rt_material* mat, const float* rays, const float* preset,
@@ -218,6 +235,34 @@ extern "C" int rt_probe_trace(int device, const rt_world_flat* world, size_t n, 
     auto h = p.out(out_hit, n); auto t = p.out(out_t, n); auto pr = p.out(out_prim, n); auto nn = p.out(out_normal, 3 * n);
     p.launch(probe_trace_kernel, p.per_case(n), 128, sc.dw, n, r, h, t, pr, nn);
     return p.finish() != RT_OK ? p.rc : check_traversal_overflow(sc);
+}
+extern "C" int rt_probe_shading_normal(int device, const rt_world_flat* world, const rt_tri_normals* table, uint32_t n_table, size_t n, const float* rays,
+                                       int32_t* out_hit, float* out_normal, uint32_t* out_interpolated) {
+    if (!rays || !out_hit || !out_normal || !out_interpolated) return rt_fail(RT_ERR_INVALID, "rt_probe_shading_normal: null argument");
+    if ((table == nullptr) != (n_table == 0u)) return rt_fail(RT_ERR_INVALID, "rt_probe_shading_normal: a table and its count go together");
+    ProbeRun p(device);
+    DeviceScene sc;
+    if (p.ok()) p.rc = sc.upload(world);
+    if (p.ok() && n_table && n_table != sc.n_triangles) p.rc = rt_fail(RT_ERR_INVALID, "rt_probe_shading_normal: %u records for a world of %u triangles", n_table, sc.n_triangles);
+    if (!p.ok() || n == 0) return p.rc;
+    auto r = p.in(rays, 7 * n);
+    const rt_tri_normals* vn = n_table ? p.in(table, (size_t)n_table) : nullptr;
+    auto h = p.out(out_hit, n); auto nn = p.out(out_normal, 3 * n); auto it = p.out(out_interpolated, n);
+    p.launch(probe_shading_normal_kernel, p.per_case(n), 128, sc.dw, vn, world->n_prims + world->n_quads - sc.n_triangles, n, r, h, nn, it);
+    return p.finish() != RT_OK ? p.rc : check_traversal_overflow(sc);
+}
+// HOST (no GPU): the kernels' shading_normal() over arrays — here, not in rt_host.cpp, because this translation unit sees rt_device_funcs.hpp
+extern "C" int rt_shading_normal_batch(size_t n, const rt_quad* tris, const rt_tri_normals* vn, const float* rays, const float* t, float* out_normal, uint32_t* out_interpolated) {
+    if (n && (!tris || !vn || !rays || !t || !out_normal || !out_interpolated)) return rt_fail(RT_ERR_INVALID, "rt_shading_normal_batch: null argument");
+    for (size_t i = 0; i < n; i++) {
+        Ray r;
+        r.o = ld3(rays + 6 * i); r.d = ld3(rays + 6 * i + 3); r.time = 0.0f;
+        f3 normal = ld3(tris[i].normal);
+        if (dot(r.d, normal) > 0) normal = -normal;
+        out_interpolated[i] = shading_normal_flat(tris[i], vn[i], r, t[i], normal) ? 1u : 0u;
+        st3(out_normal + 3 * i, normal);
+    }
+    return RT_OK;
 }
 extern "C" int rt_probe_sphere_hit(int device, size_t n, const rt_prim* prims, const float* rays, const float* preset, int32_t* out_hit,
                                    float* out_dist, float* out_normal) {

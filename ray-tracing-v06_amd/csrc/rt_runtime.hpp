@@ -155,7 +155,7 @@ struct DeviceScene {
         const uint32_t nodes_vec4 = RT_NODES_VEC4(n_inner, big);
         const uint32_t quads_at = (nodes_vec4 + w->n_prims * 2 + w->n_materials + 3u) & ~3u;   // 64-byte records on 64-byte boundaries: one cache line each
         size_t n_vec4 = (size_t)quads_at + (size_t)w->n_quads * 5;
-        std::vector<uint4> host(n_vec4, make_uint4(0, 0, 0, 0));
+        std::vector<uint4> host(n_vec4 + 1u, make_uint4(0, 0, 0, 0));   // + the vertex-normal header behind the image: zero = no table follows
         if (w->kind == RT_WORLD_BVH) {
             auto ref_of = [&](int32_t node) -> uint32_t {
                 const rt_bvh_node& n = w->nodes[node];
@@ -216,7 +216,7 @@ struct DeviceScene {
             qd[4 * i + 3] = make_float4(q.normal[2], q.w[0], q.w[1], q.w[2]);
             qd[4 * (size_t)w->n_quads + i] = make_float4(q.normal[0], q.normal[1], q.normal[2], __uint_as_float_host(mat_bits(q.mat, 0u)));
         }
-        HIP_TRY(blob.upload(host.data(), n_vec4 * sizeof(uint4)));
+        HIP_TRY(blob.upload(host.data(), (n_vec4 + 1u) * sizeof(uint4)));
         packed.blob = blob.as<uint4>();
         packed.blob_vec4 = (uint32_t)n_vec4;
         packed.off_spheres = nodes_vec4;

@@ -252,6 +252,10 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
     // per-lane traversal stack of references (16 bits, BIG: 32).  Entry k of this lane is stack[k * 64].
     ref_t* stack = reinterpret_cast<ref_t*>(lds + (BIG ? p.scene.n_top * (RT_NODE_DWORDS_BIG / 4u) : p.scene.blob_vec4)) + wave * 64u * p.scene.stack_cap + lane;
 
+    // §21, TRI only: one vec4 behind the image the launch was given (behind its light table too) says whether vertex normals follow it — (on, -, -, -), then 36 B per
+    // triangle, in global memory whatever the form of the image.  Wave-uniform; a world without a table pays this one scalar load and one scalar branch per shaded quad hit.
+    uint32_t vn_on = 0u;
+    if constexpr (TRI) vn_on = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.scene.blob[p.scene.blob_vec4].x);
     const f3 root_min = mk3(p.scene.root_min[0], p.scene.root_min[1], p.scene.root_min[2]);
     const f3 root_max = mk3(p.scene.root_max[0], p.scene.root_max[1], p.scene.root_max[2]);
 
@@ -570,6 +574,16 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                     normal = mk3(qs.x, qs.y, qs.z);
                     if (dot(ray.d, normal) > 0) normal = -normal;  // the book's set_face_normal: a quad is two-sided
                     mat_bits = __float_as_uint(qs.w);
+                    if constexpr (TRI) {
+                        const uint32_t qi = (uint32_t)rec_code - p.scene.sphere_codes;
+                        if (vn_on != 0u && qi >= p.scene.n_plain_quads) {   // §21: the shading normal of a triangle with vertex normals, or the flat one again
+                            const float* vr = reinterpret_cast<const float*>(p.scene.blob + p.scene.blob_vec4 + 1u) + (size_t)(qi - p.scene.n_plain_quads) * 9u;
+                            const f3 n0 = mk3(vr[0], vr[1], vr[2]), n1 = mk3(vr[3], vr[4], vr[5]), n2 = mk3(vr[6], vr[7], vr[8]);
+                            const float4* qd = quads + qi * 4u;
+                            const float4 a0 = qd[0], a1 = qd[1], a2 = qd[2], a3 = qd[3];
+                            shading_normal(mk3(a0.x, a0.y, a0.z), mk3(a1.x, a1.y, a1.z), mk3(a1.w, a2.x, a2.y), mk3(a3.y, a3.z, a3.w), n0, n1, n2, ray.d, hit_p, normal);
+                        }
+                    }
                 } else {
                     uint32_t prim = (uint32_t)rec_code >> 1;
                     float4 sph = spheres[prim];

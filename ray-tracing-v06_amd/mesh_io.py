@@ -1,7 +1,8 @@
 """Triangle meshes for Scene.MakeMesh: a Wavefront OBJ reader and two generators, so that demos, tests and measurements need no file.
 
-Every function returns (vertices float32 (n, 3), faces uint32 (m, 3)).  Normals and texture coordinates of a file are ignored: the renderer's
-triangles are flat-shaded and take their texture coordinates from their own plane.
+Every function returns (vertices float32 (n, 3), faces uint32 (m, 3)) but the ones that say otherwise.  load_obj ignores a file's normals; load_obj_normals
+reads them, vertex_normals makes area-weighted ones for a mesh without, icosphere_normals gives the sphere's own (smooth shading).  Texture
+coordinates of a file are ignored: a triangle takes them from its own plane.
 """
 import numpy as np
 
@@ -39,6 +40,77 @@ def load_obj(path):
                 for k in range(1, len(corners) - 1):
                     faces.append([corners[0], corners[k], corners[k + 1]])
     return np.array(vertices, np.float32).reshape(-1, 3), np.array(faces, np.uint32).reshape(-1, 3)
+
+
+def _obj_third(token, n_normals, where):
+    """the normal index of an `i/j/k` or `i//k` token (1-based, negative = counted back from the normals read so far), or None for a token without one"""
+    parts = token.split("/")
+    if len(parts) < 3 or parts[2] == "":
+        return None
+    try:
+        i = int(parts[2])
+    except ValueError:
+        raise ValueError(f"{where}: bad normal index {token!r}") from None
+    k = i - 1 if i > 0 else n_normals + i
+    if i == 0 or not 0 <= k < n_normals:
+        raise ValueError(f"{where}: normal index {token!r} out of range ({n_normals} normals so far)")
+    return k
+
+
+def load_obj_normals(path):
+    """load_obj that keeps the normals: (vertices, faces, normals float32 (k, 3) | None, normal_faces uint32 (m, 3) | None) from the `v`, `vn` and `f` lines;
+    the third index of an `i/j/k` or `i//k` corner names its normal (negative indices and fans as for vertices).  A file without `vn` lines, or one face
+    corner without a normal index, gives None, None: the mesh has no complete set of normals (vertex_normals makes one)."""
+    vertices, faces, normals, normal_faces = [], [], [], []
+    complete = True
+    with open(path, "r", encoding="utf-8", errors="replace") as f:
+        for lineno, line in enumerate(f, 1):
+            parts = line.split("#", 1)[0].split()
+            if not parts:
+                continue
+            where = f"{path}:{lineno}"
+            if parts[0] == "v":
+                if len(parts) < 4:
+                    raise ValueError(f"{where}: a vertex needs three coordinates")
+                vertices.append([float(parts[1]), float(parts[2]), float(parts[3])])
+            elif parts[0] == "vn":
+                if len(parts) < 4:
+                    raise ValueError(f"{where}: a normal needs three coordinates")
+                normals.append([float(parts[1]), float(parts[2]), float(parts[3])])
+            elif parts[0] == "f":
+                if len(parts) < 4:
+                    raise ValueError(f"{where}: a face needs at least three corners")
+                corners = [_obj_index(t, len(vertices), where) for t in parts[1:]]
+                thirds = [_obj_third(t, len(normals), where) for t in parts[1:]]
+                if any(k is None for k in thirds):
+                    complete = False
+                for k in range(1, len(corners) - 1):
+                    faces.append([corners[0], corners[k], corners[k + 1]])
+                    if complete:
+                        normal_faces.append([thirds[0], thirds[k], thirds[k + 1]])
+    v, fa = np.array(vertices, np.float32).reshape(-1, 3), np.array(faces, np.uint32).reshape(-1, 3)
+    if not normals or not complete:
+        return v, fa, None, None
+    return v, fa, np.array(normals, np.float32).reshape(-1, 3), np.array(normal_faces, np.uint32).reshape(-1, 3)
+
+
+def vertex_normals(vertices, faces):
+    """area-weighted vertex normals of an indexed mesh, float32 (n, 3): per vertex the sum of cross(b - a, c - a) over its faces (twice the face's area
+    along its normal), normalised in float64; a vertex no face uses, or whose sum vanishes, gets (0, 0, 1)"""
+    v = np.asarray(vertices, np.float64).reshape(-1, 3)
+    f = np.asarray(faces, np.int64).reshape(-1, 3)
+    fn = np.cross(v[f[:, 1]] - v[f[:, 0]], v[f[:, 2]] - v[f[:, 0]])
+    acc = np.zeros_like(v)
+    for k in range(3):
+        np.add.at(acc, f[:, k], fn)
+    ln = np.linalg.norm(acc, axis=1)
+    out = np.where((ln > 0)[:, None], acc / np.where(ln > 0, ln, 1.0)[:, None], np.array([0.0, 0.0, 1.0]))
+    return out.astype(np.float32)
+
+
+def icosphere_normals(level):
+    """the vertex normals of icosphere(level): its unit positions, float32 (n, 3)"""
+    return icosphere(level)[0].copy()
 
 
 def tetrahedron():

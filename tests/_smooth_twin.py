@@ -1,0 +1,133 @@
+"""A numpy float32 twin of the smooth-shading rule — test infrastructure only.
+
+shading_normal() restates the rule of include/rt06.h (rt_tri_normals) in float32 numpy, every operation rounded on its own: image_value_quad's planar
+coordinates, g = (n0 * ((1 - alpha) - beta) + n1 * alpha) + n2 * beta, the two ways back to the flat normal.  closest_intersection_smooth() is
+_tri_twin.closest_intersection followed by that on triangle hits.  radiance() for modes 0, 1, 2 (_tri_twin), 4 (_mesh_light_twin) and 16 (_light_tree_twin) is
+those modules' own radiance with the walk replaced: their files are not edited, their module-level `closest_intersection` is substituted for the duration of
+the call.  The oracle does not know the rule, so nothing here asks it about one; the twin is pinned before use (tests/test_smooth_normals_cpu.py): with a
+table of zeros it IS _tri_twin, bit for bit, and rt_shading_normal_batch — the kernels' own function on the host — equals shading_normal() bit for bit.
+
+Scope, as the twins have it: pinhole camera, static spheres, Lambertian, checker, metal and light materials, stack traversal.
+"""
+import contextlib
+
+import numpy as np
+
+import _light_tree_twin as LT
+import _mesh_light_twin as MT
+import _tri_twin as TT
+from _nee2_twin import world_arrays
+from _nee_twin import F, cross, dot
+
+in_order_sums, resolve = TT.in_order_sums, TT.resolve
+_flat_walk = TT.closest_intersection   # the walk itself, taken before any substitution below
+
+
+def table(vn):
+    """a table of vertex normals as float32 (n, 3, 3): n0, n1, n2 of every triangle"""
+    a = np.asarray(vn)
+    if a.dtype.names:
+        a = np.stack([a["n0"], a["n1"], a["n2"]], axis=1)
+    return np.ascontiguousarray(a, F).reshape(-1, 3, 3)
+
+
+def shading_normal(tris, vn, o, d, t):
+    """The rule on hit i: triangle record tris[i] (Q, u, v, normal, w), vertex normals vn[i] (3, 3), ray (o[i], d[i]), distance t[i].
+    Returns (normal (n, 3) float32, interpolated (n,) bool, fallback (n,) int: 0 interpolated, 1 `!(l2 > 0)`, 2 `!(dot(ray.d, s) < 0)`)."""
+    vn = table(vn)
+    o, d, t = np.ascontiguousarray(o, F).reshape(-1, 3), np.ascontiguousarray(d, F).reshape(-1, 3), np.ascontiguousarray(t, F).reshape(-1)
+    with np.errstate(all="ignore"):
+        nrm = tris["normal"].astype(F)
+        f = np.where((dot(d, nrm) > F(0))[:, None], -nrm, nrm)
+        hit_p = o + d * t[:, None]
+        u, v, w = tris["u"].astype(F), tris["v"].astype(F), tris["w"].astype(F)
+        planar = hit_p - tris["Q"].astype(F)
+        alpha = dot(w, cross(planar, v))
+        beta = dot(w, cross(u, planar))
+        g = (vn[:, 0] * ((F(1) - alpha) - beta)[:, None] + vn[:, 1] * alpha[:, None]) + vn[:, 2] * beta[:, None]
+        l2 = dot(g, g)
+        has_dir = l2 > F(0)
+        s = g / np.sqrt(l2)[:, None]
+        s = np.where((dot(s, f) < F(0))[:, None], -s, s)
+        faces = dot(d, s) < F(0)
+        took = has_dir & faces
+        fallback = np.where(~has_dir, 1, np.where(~faces, 2, 0))
+        return np.where(took[:, None], s, f).astype(F), took, fallback
+
+
+def closest_intersection_smooth(world, vn, rays, preset=None, info=None):
+    """_tri_twin.closest_intersection, then the rule on the hits whose primitive is a triangle; vn: one record per triangle of the flat world.
+    info (a dict): gets added up 'smooth' (hits on triangles with a non-zero record), 'interpolated' and 'fallback2' (of those), and 'fallback1' — every
+    triangle hit that `!(l2 > 0)` sends back to the flat normal: all-zero records are the rule's own first case of it, and between three unit normals of one
+    record g vanishes only on a set of measure zero, which no rendered frame meets."""
+    hit, t, prim, normal = _flat_walk(world, rays, preset)
+    vn = table(vn)
+    prims, quads, _ = world_arrays(world)
+    first_tri = len(prims) + int((quads["kind"] == 0).sum())
+    assert len(vn) == len(prims) + len(quads) - first_tri, "one record per triangle of the flat world"
+    rows = np.nonzero((hit != 0) & (prim >= first_tri))[0]
+    if len(rows):
+        q = quads[prim[rows] - len(prims)]
+        rec = vn[prim[rows] - first_tri]
+        n, took, fb = shading_normal(q, rec, rays[rows, 0:3], rays[rows, 3:6], t[rows])
+        normal = normal.copy()
+        normal[rows] = n
+        if info is not None:
+            nonflat = (rec != 0).any(axis=(1, 2))
+            for key, add in (("smooth", nonflat.sum()), ("interpolated", (took & nonflat).sum()), ("fallback1", (fb == 1).sum()), ("fallback2", ((fb == 2) & nonflat).sum())):
+                info[key] = info.get(key, 0) + int(add)
+    return hit, t, prim, normal
+
+
+TWIN_OF_MODE = {0: TT, 1: TT, 2: TT, 4: MT, 16: LT}
+
+
+@contextlib.contextmanager
+def _walk(module, vn, info):
+    """module.closest_intersection = the smooth walk, for the duration of the block (the twins call their module-level name)"""
+    saved = module.closest_intersection
+    module.closest_intersection = lambda world, rays, preset=None: closest_intersection_smooth(world, vn, rays, preset, info)
+    try:
+        yield
+    finally:
+        module.closest_intersection = saved
+
+
+def radiance(world, vn, cam, width, height, max_depth, seed, gids, samples, mode=0, info=None):
+    """the mode's own twin's radiance with the walk replaced: ((n, 3) float32, followed (n,) bool)"""
+    module = TWIN_OF_MODE[mode]
+    with _walk(module, vn, info):
+        return module.radiance(world, cam, width, height, max_depth, seed, gids, samples, mode)
+
+
+def frame_samples(world, vn, cam, width, height, spp, max_depth, seed, mode=0, first_sample=0, info=None):
+    """(height, width, spp, 3) float32: every sample of every pixel; followed (height, width, spp)"""
+    gids = np.repeat(np.arange(width * height, dtype=np.uint32), spp)
+    smp = np.tile(np.arange(first_sample, first_sample + spp, dtype=np.uint32), width * height)
+    rad, ok = radiance(world, vn, cam, width, height, max_depth, seed, gids, smp, mode, info)
+    return rad.reshape(height, width, spp, 3), ok.reshape(height, width, spp)
+
+
+def first_hit_sums(world, vn, cam, width, height, spp, seed, first_sample=0):
+    """_tri_twin.first_hit_sums with the rule applied to the first hits: (H, W, 5) float32 = (sum Nx, sum Ny, sum Nz, sum t, hits)"""
+    with _walk(TT, vn, None):
+        return TT.first_hit_sums(world, cam, width, height, spp, seed, first_sample)
+
+
+def shading_normal64(Q, u, v, n0, n1, n2, d, hit_p):
+    """the rule in float64 (w from u, v), for the mathematics no kernel shares: (normal, interpolated)"""
+    Q, u, v, n0, n1, n2, d, hit_p = (np.asarray(a, np.float64) for a in (Q, u, v, n0, n1, n2, d, hit_p))
+    n = np.cross(u, v)
+    w = n / (n * n).sum(axis=-1, keepdims=True)
+    unit = n / np.linalg.norm(n, axis=-1, keepdims=True)
+    f = np.where(((d * unit).sum(axis=-1) > 0)[..., None], -unit, unit)
+    planar = hit_p - Q
+    alpha = (w * np.cross(planar, v)).sum(axis=-1)
+    beta = (w * np.cross(u, planar)).sum(axis=-1)
+    g = n0 * (1 - alpha - beta)[..., None] + n1 * alpha[..., None] + n2 * beta[..., None]
+    l2 = (g * g).sum(axis=-1)
+    with np.errstate(all="ignore"):
+        s = g / np.sqrt(l2)[..., None]
+    s = np.where(((s * f).sum(axis=-1) < 0)[..., None], -s, s)
+    took = (l2 > 0) & ((d * s).sum(axis=-1) < 0)
+    return np.where(took[..., None], s, f), took, g

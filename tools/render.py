@@ -64,6 +64,8 @@ ap.add_argument("--mesh-scale", type=float, default=1.0)
 ap.add_argument("--mesh-rotate-y", type=float, default=0.0, metavar="DEGREES")
 ap.add_argument("--mesh-translate", default="0,0,0", metavar="X,Y,Z")
 ap.add_argument("--mesh-material", default="white", choices=["white", "red", "metal", "glass", "checker", "light"])
+ap.add_argument("--smooth", action="store_true", help="with --mesh: smooth shading from per-vertex normals (DESIGN.md §21) — an OBJ file's own `vn` normals if it has a complete "
+                    "set, an icosphere's unit positions, else area-weighted ones (mesh_io.vertex_normals)")
 ap.add_argument("--out", default="render.png")
 a = ap.parse_args()
 light_mode = {"quads": 1, "all": 2, "mesh": 4, "tree": 16}.get(a.light_sampling_mode, 1 if a.light_sampling else 0)   # RT_LIGHT_SAMPLING_*
@@ -87,10 +89,18 @@ else:
 if a.mesh:
     from ray_tracing_v06_amd import mesh_io
     vertices, faces = mesh_io.from_spec(a.mesh)
+    normals = normal_faces = None
+    if a.smooth:
+        if a.mesh.startswith("icosphere:"):
+            normals = mesh_io.icosphere_normals(int(a.mesh.split(":", 1)[1]))
+        elif a.mesh != "tetrahedron":
+            _, _, normals, normal_faces = mesh_io.load_obj_normals(a.mesh)
+        if normals is None:
+            normals = mesh_io.vertex_normals(vertices, faces)
     mat = {"white": lambda: scene.Lambertian((0.73, 0.73, 0.73)), "red": lambda: scene.Lambertian((0.65, 0.05, 0.05)), "metal": lambda: scene.Metal((0.8, 0.85, 0.88), 0.0),
            "glass": lambda: scene.Dielectric((1, 1, 1), 1.5), "checker": lambda: scene.LambertianTexture((0.2, 0.3, 0.1), (0.9, 0.9, 0.9), abs(a.mesh_scale) / 4 if a.mesh_scale else 1.0),   # four squares across a unit mesh
            "light": lambda: scene.DiffuseLight((4, 4, 4))}[a.mesh_material]()
-    first, added = scene.MakeMesh(vertices, faces, mat, a.mesh_scale, a.mesh_rotate_y, [float(x) for x in a.mesh_translate.split(",")])
+    first, added = scene.MakeMesh(vertices, faces, mat, a.mesh_scale, a.mesh_rotate_y, [float(x) for x in a.mesh_translate.split(",")], normals=normals, normal_faces=normal_faces)
     if a.scene == "three_spheres":
         scene.MakeHittableList()   # the prefab's own world kind
     else:
