@@ -363,15 +363,28 @@ int rt_renderer_set_camera(rt_renderer* r, const rt_camera* cam);
 int rt_renderer_render(rt_renderer* r);
 /* Same launch on a caller-provided hipStream_t, no host synchronisation.
  * d_out = device buffer for this rank's shard (rt_renderer_shard_floats
- * floats) or NULL to use the renderer's own framebuffer.                    */
+ * floats) or NULL to use the renderer's own framebuffer.
+ * What it promises: `d_out` (or the framebuffer) is written by work in the stream's order, behind everything enqueued on `hip_stream` before the
+ * call, and is complete for everything enqueued behind it.  Nothing else the caller owns is read or written.  A renderer with two frame slots
+ * (rt_renderer_run_ahead_info) generates and traces the frame on a stream of its own, which does not wait for `hip_stream`, and only resolves into
+ * `d_out` in the stream's order: calls enqueued back to back overlap each frame's tail with the next frame's start.  The frame's bits are the same.  */
 int rt_renderer_render_async(rt_renderer* r, void* hip_stream, float* d_out);
+/* Frame slots (run-ahead).  out[0] = slots: 2 when a render is ONE pass of a streaming kernel (variant >= 2) over an RT_WORLD_BVH world, a second set of per-pass buffers fits the
+ * budget of rt_renderer_pass_info beside the first, the device gave it, and RT06_RUN_AHEAD is not 0; else 1, and every call runs on the caller's stream
+ * alone.  out[1] = render_async calls that ran ahead, out[2] = those of them that found the call before them still unfinished when they were enqueued
+ * (so that frames really were in flight together), out[3] = bytes of the second set (the same as the first: 60 B per sample index of a pass).
+ * rt_renderer_render, refine steps, the feature pass and the denoiser never run ahead: they order behind every queued render.  Nor does a
+ * render_async enqueued while the last call of ANOTHER renderer on the same device is unfinished: two frames in flight on a device is what pays.  */
+int rt_renderer_run_ahead_info(rt_renderer* r, uint64_t out[4]);
 /* HIP-event time of the last render launch(es) in ms (cudaTimer twin,
  * Renderer.cu:127-136).  Synchronises on the events.                        */
 int rt_renderer_last_kernel_ms(rt_renderer* r, float* out_ms);
 /* Per-kernel HIP-event times (ms) of one of the last 32 render calls (renders_back = 0: the most recent), measured on the
  * stream the kernels ran on: out[0] = primary_rays_kernel, out[1] = the dominant kernel (render_kernel_stream /
  * render_kernel_xchg), out[2] = resolve_kernel — each SUMMED over the passes of that call (rt_renderer_pass_info).
- * Synchronises on that call's end.  Streaming variants (>= 2) only.                                                       */
+ * Synchronises on that call's end.  Streaming variants (>= 2) only.  A call that ran ahead (rt_renderer_run_ahead_info) shares the GPU
+ * with its neighbours: its three numbers are durations of kernels that ran beside another frame's, and its resolve is timed from behind
+ * the wait for its tracer.                                                                                                  */
 int rt_renderer_kernel_times(rt_renderer* r, uint32_t renders_back, float out_ms[3]);
 /* How a render is cut into passes: out[0] = passes per render, out[1] = samples per pixel per pass, out[2] = HBM bytes per
  * sample index of a pass (12 B radiance + 48 B primary-ray record), out[3] = bytes of the per-pass buffers this renderer

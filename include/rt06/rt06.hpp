@@ -564,7 +564,9 @@ public:
     }
     // The reference takes `const MotionBlurCamera*`; the other two camera types are accepted as well.  As there, the renderer KEEPS the
     // pointer and reads the camera at every Render() (Renderer.cu:117): the camera object must outlive the renderer, and moving it between
-    // two Render() calls moves the frame.
+    // two Render() calls moves the frame.  The camera is copied into the launch at the call (by value): Render() here is the blocking
+    // rt_renderer_render, and a C caller that queues rt_renderer_render_async calls — whose frames a two-slot renderer traces ahead of the caller's
+    // stream (rt_renderer_run_ahead_info) — may move the camera between them: every queued frame keeps the camera of its own call.
     // seed: the reference hard-codes 1984 (Renderer.cu:51).  n_gpus > 1: the frame is tile-sharded over GPUs 0 .. n_gpus-1 of the
     // node and gathered on GPU 0 with one RCCL exchange (rt_multi_renderer_*); the image is the same for every n_gpus.
     // variant: rt_render_config::variant — 0 (default: the fastest kernel that renders the reference's bits); kToleranceMode opts a sphere world of the

@@ -373,6 +373,8 @@ class Renderer:
         check(lib().rt_renderer_render(self.h))
 
     def render_async(self, stream=None, d_out=None):
+        """Render() on the caller's stream without a host wait.  d_out is written in the stream's order; on a two-slot renderer (run_ahead_info) the
+        frame is generated and traced ahead of the stream, on a stream of the renderer's own, and only resolved into d_out in order."""
         check(lib().rt_renderer_render_async(self.h, C.c_void_p(stream or 0), C.c_void_p(d_out or 0)))
 
     def set_camera(self, cam):
@@ -497,6 +499,13 @@ class Renderer:
         out = (C.c_uint64 * 4)()
         check(lib().rt_renderer_pass_info(self.h, out))
         return {"n_passes": out[0], "pass_spp": out[1], "bytes_per_sample": out[2], "buffer_bytes": out[3]}
+
+    def run_ahead_info(self):
+        """{'slots', 'calls', 'overlapped', 'second_set_bytes'}: frame slots, render_async calls that ran ahead, those that found the call before them
+        still in flight when they were enqueued, bytes of the second set of per-pass buffers (rt_renderer_run_ahead_info)."""
+        out = (C.c_uint64 * 4)()
+        check(lib().rt_renderer_run_ahead_info(self.h, out))
+        return {"slots": out[0], "calls": out[1], "overlapped": out[2], "second_set_bytes": out[3]}
 
     def kernel_info(self):
         """{'variant', 'lds_resident', 'workgroup', 'workgroups_per_cu'} the renderer resolved to."""

@@ -89,6 +89,7 @@ SYMBOLS = [
     "rt_world_light_tree", "rt_renderer_kernel_light_tree",
     "rt_scene_add_triangle_smooth", "rt_scene_add_mesh_smooth", "rt_scene_vertex_normals", "rt_shading_normal_batch", "rt_renderer_shading_normals",
     "rt_renderer_shading_normals_info", "rt_multi_renderer_shading_normals", "rt_probe_shading_normal",
+    "rt_renderer_run_ahead_info",
 ]
 
 _lib = None
@@ -158,6 +159,7 @@ def lib():
     L.rt_version.restype = C.c_char_p
     L.rt_source_hash.restype = C.c_char_p
     L.rt_renderer_pass_info.argtypes = [C.c_void_p, C.c_uint64 * 4]
+    L.rt_renderer_run_ahead_info.argtypes = [C.c_void_p, C.c_uint64 * 4]
     L.rt_camera_pinhole.argtypes = [vec3, vec3, vec3, C.c_float, C.c_float, P(Camera)]
     L.rt_camera_defocus.argtypes = [vec3, vec3, vec3, C.c_float, C.c_float, C.c_float, C.c_float, P(Camera)]
     L.rt_camera_motion.argtypes = [vec3, vec3, vec3, C.c_float, C.c_float, C.c_float, C.c_float, P(Camera)]

@@ -150,18 +150,29 @@ static decltype(&aov_kernel<RT_AOV_WALK_STACK>) aov_kernel_for(const DeviceWorld
 // ---------------------------------------------------------------------------------------------
 // Renderer
 // ---------------------------------------------------------------------------------------------
+static bool another_renderer_busy(const rt_renderer* self);   // is the last call of another renderer on self's device still unfinished?
+
 struct rt_renderer {
     rt_render_config cfg{};
     rt_camera cam{};
     DeviceScene scene;
     TileMap tm{};
     DevBuf fb;
-    DevBuf work_counter;
-    DevBuf samples, running;     // sample buffer of one pass (12 B per sample); running sums (16 B per pixel) when spp needs several passes
-    // primary rays of one pass: 3 arrays of 16 B per sample index (origin|time, direction, RNG state).  Generated on the render's
-    // own stream, before the streaming kernel: generating pass k + 1 on a second stream WHILE pass k is traced was measured and is
-    // harmful (the persistent kernel ran 40 % slower with the generator's waves co-resident: 100 ms instead of 70).
-    DevBuf primary;
+    // A frame slot: what one call's generator and tracer write and its resolve reads.
+    //   samples = sample buffer of one pass (12 B per sample).
+    //   primary = primary rays of one pass: 3 arrays of 16 B per sample index (origin|time, direction, RNG state), generated before the streaming kernel
+    //   on the same stream: generating pass k + 1 on a second stream WHILE pass k is traced was measured and is harmful (the persistent kernel ran 40 %
+    //   slower with the generator's waves co-resident: 100 ms instead of 70).
+    // Every renderer has slot[0].  A renderer whose Render() is one pass of a streaming kernel gets a second set and two streams of its own, and a plain
+    // render_async then runs ahead ("Run-ahead"): call k generates and traces into slot k mod 2 on that slot's stream, which waits for
+    // nothing of the caller's, and only its resolve — the one kernel that touches `out` — runs on the caller's stream.
+    //   traced = the slot's last tracer has finished (the resolve waits for it); consumed = whatever last read or wrote the slot's buffers on a caller's
+    //   stream has finished (the slot's next generator waits for it).
+    struct Slot { DevBuf samples, primary, work_counter; hipStream_t stream = nullptr; hipEvent_t traced = nullptr, consumed = nullptr; };
+    Slot slot[2];
+    uint32_t n_slots = 1;
+    uint64_t n_ahead = 0, n_overlapped = 0;   // calls that ran ahead; those that found the call before them still in flight when they were enqueued
+    DevBuf running;              // running sums (16 B per pixel) when spp needs several passes
     uint32_t pass_spp = 0;       // samples per pixel per pass
     uint32_t n_cus = 0;
     uint32_t stream_lds_bytes = 0;
@@ -181,8 +192,12 @@ struct rt_renderer {
     // per-kernel HIP events of the last RT_TIMES_RING render calls, on the stream the kernels run on, four per PASS:
     // [4k] before primary_rays_kernel of pass k, [4k+1] before the streaming kernel, [4k+2] after it, [4k+3] after resolve_kernel.
     // Created at first use (a 10 000-spp render of a 4K frame has > 100 passes).
+    // A call that ran ahead has [0] to [2] on its slot's stream and [3] on the caller's, where the resolve starts behind a wait for the tracer: its
+    // resolve is timed from an event of its own (kev_resolve0) behind that wait.
     static constexpr uint32_t RT_TIMES_RING = 32;
     std::vector<hipEvent_t> kev[RT_TIMES_RING];
+    hipEvent_t kev_resolve0[RT_TIMES_RING] = {};
+    bool kev_ahead[RT_TIMES_RING] = {};
     uint32_t kev_passes[RT_TIMES_RING] = {};   // passes of the call each ring slot holds: a Render() has n_passes, a refine step a count of its own
     uint64_t n_renders = 0;
     uint32_t n_passes = 1;
@@ -370,11 +385,11 @@ struct rt_renderer {
         if (max_spp == 0) return rt_fail(RT_ERR_INVALID, "image too large for one pass");
         pass_spp = (uint32_t)std::min<uint64_t>(cfg.samples_per_pixel, max_spp);
         for (;;) {   // a device that cannot give the pass its buffers gets smaller passes, not an error: halve until they fit
-            hipError_t e = samples.alloc((size_t)(n_pixels * pass_spp * SAMPLE_BYTES));
-            if (e == hipSuccess) e = primary.alloc((size_t)(n_pixels * pass_spp * PRIMARY_BYTES));
+            hipError_t e = slot[0].samples.alloc((size_t)(n_pixels * pass_spp * SAMPLE_BYTES));
+            if (e == hipSuccess) e = slot[0].primary.alloc((size_t)(n_pixels * pass_spp * PRIMARY_BYTES));
             if (e == hipSuccess) break;
             (void)hipGetLastError();   // (clears the sticky out-of-memory status)
-            samples.release(); primary.release();
+            slot[0].samples.release(); slot[0].primary.release();
             if (e != hipErrorOutOfMemory || pass_spp == 1u)
                 return rt_fail(RT_ERR_HIP, "per-pass buffers (%llu bytes per sample index x %llu sample indices): %s", (unsigned long long)per_sample,
                                (unsigned long long)(n_pixels * pass_spp), hipGetErrorString(e));
@@ -382,20 +397,74 @@ struct rt_renderer {
         }
         n_passes = (cfg.samples_per_pixel + pass_spp - 1) / pass_spp;
         if (n_passes > 1) HIP_TRY(running.alloc((size_t)(n_pixels * 16ull)));
+#ifndef RT_PHASE_TIMERS   // (the phase-timer build synchronises inside every launch: nothing to run ahead of)
+        const char* ahead = std::getenv("RT06_RUN_AHEAD");
+        // (BVH worlds: a HittableList or a bvh_node tree tests far more per ray, its frames are long and their tails a small share, like a multi-pass call's)
+        if (n_passes == 1 && scene.dw.kind == RT_WORLD_BVH && 2u * n_pixels * pass_spp * per_sample <= budget && !(ahead && ahead[0] == '0')) add_second_slot();
+#endif
+        return RT_OK;
+    }
+    // The second frame slot, its streams and events.  A multi-pass call stays on one slot: its passes are long (the tail is ~0.1 % of them) and its buffers
+    // are what the budget allowed.  A device that cannot give the second set leaves the renderer what it was: one slot, every call on the caller's stream.
+    void add_second_slot() {
+        hipError_t e = slot[1].samples.alloc(slot[0].samples.bytes);
+        if (e == hipSuccess) e = slot[1].primary.alloc(slot[0].primary.bytes);
+        if (e == hipSuccess) e = slot[1].work_counter.alloc(256);
+        for (Slot& s : slot) {
+            if (e == hipSuccess) e = hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking);
+            if (e == hipSuccess) e = hipEventCreateWithFlags(&s.traced, hipEventDisableTiming);
+            if (e == hipSuccess) e = hipEventCreateWithFlags(&s.consumed, hipEventDisableTiming);
+        }
+        if (e == hipSuccess) { n_slots = 2; return; }
+        (void)hipGetLastError();
+        drop_second_slot();
+    }
+    void drop_second_slot() {
+        slot[1].samples.release(); slot[1].primary.release(); slot[1].work_counter.release();
+        for (Slot& s : slot) {
+            if (s.stream) (void)hipStreamDestroy(s.stream);
+            if (s.traced) (void)hipEventDestroy(s.traced);
+            if (s.consumed) (void)hipEventDestroy(s.consumed);
+            s.stream = nullptr; s.traced = s.consumed = nullptr;
+        }
+        n_slots = 1;
+    }
+    // the host waits for everything queued on the slots: the generators and tracers on their streams, and the resolves that read them
+    int drain_slots() {
+        for (Slot& s : slot)
+            if (s.stream) { HIP_TRY(hipStreamSynchronize(s.stream)); HIP_TRY(hipEventSynchronize(s.consumed)); }
         return RT_OK;
     }
 
     // One call's launches: samples [first_s, first_s + n_s) of every pixel, cut into passes of at most pass_spp.  Render() is (0, samples_per_pixel)
     // resolved through `running`; a refine step is (refine_done, n) resolved into `accum` (refine = true), which carries the sums from call to call.
-    int launch(hipStream_t st, float* out, uint32_t first_s, uint32_t n_s, bool refine) {
+    // run_ahead: a plain render_async.  On a two-slot renderer its generator and tracer go to the stream of slot k mod 2 (k = the calls that ran ahead so
+    // far), which waits for the slot's `consumed` and for nothing of `st`: what they read is by value in the kernel arguments (the camera too) or
+    // immutable after creation (the scene images), and what they write is the slot's own.  Every other call is serial on `st`, behind all that is queued.
+    int launch(hipStream_t st, float* out, uint32_t first_s, uint32_t n_s, bool refine, bool run_ahead) {
         if (variant == 1) {
             RenderParams p;
-            frame_params(p, cfg.samples_per_pixel);
+            frame_params(p, cfg.samples_per_pixel, slot[0]);
             p.out = out;
             return launch_render(p, variant, st);
         }
+        // two slots: one pass, a streaming kernel.  Two frames in flight on a device is what pays: a caller that already keeps a frame of ANOTHER renderer
+        // in flight (bench.py --pipeline 2) would have four with run-ahead, and two generators beside the tracers (measured: 79.7 instead of 66.4 ms per frame)
+        const bool ahead = run_ahead && n_slots == 2 && !another_renderer_busy(this);
+        Slot& sl = slot[ahead ? n_ahead % 2u : 0u];
+        const hipStream_t gs = ahead ? sl.stream : st;   // the generator's and the tracer's stream
+        if (ahead) {
+            if (n_ahead && hipEventQuery(slot[(n_ahead - 1u) % 2u].consumed) == hipErrorNotReady) { n_overlapped++; (void)hipGetLastError(); }
+            HIP_TRY(hipStreamWaitEvent(gs, sl.consumed, 0));   // the resolve two calls ago has read these buffers
+            n_ahead++;
+        } else if (n_slots == 2) {
+            for (Slot& s : slot) { HIP_TRY(hipStreamWaitEvent(st, s.traced, 0)); HIP_TRY(hipStreamWaitEvent(st, s.consumed, 0)); }
+        }
         const uint32_t end_s = first_s + n_s, n_pixels = (uint32_t)n_local_pixels(tm), grid = n_cus * (nee.on() ? nee.cur().blocks_per_cu : stream_blocks_per_cu);
-        StreamParams p = call_params(refine ? end_s : cfg.samples_per_pixel);
+        StreamParams p = call_params(refine ? end_s : cfg.samples_per_pixel, sl);
+        const uint32_t ring_at = (uint32_t)(n_renders % RT_TIMES_RING);
+        kev_ahead[ring_at] = ahead;
+        if (ahead && !kev_resolve0[ring_at]) HIP_TRY(hipEventCreate(&kev_resolve0[ring_at]));
         std::vector<hipEvent_t>& ring = kev[n_renders % RT_TIMES_RING];   // the event ring: this call's slot, four events per pass, created at first use
         const uint32_t call_passes = kev_passes[n_renders % RT_TIMES_RING] = (n_s + pass_spp - 1u) / pass_spp;
         while (ring.size() < (size_t)call_passes * 4u) {
@@ -406,33 +475,38 @@ struct rt_renderer {
         hipEvent_t* ke = ring.data();
         for (uint32_t first = first_s; first < end_s; first += pass_spp, ke += 4) {
             const uint32_t counter_start = pass_params(p, first, end_s, grid);
-            HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)work_counter.p, (int)counter_start, 1, st));
+            HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)sl.work_counter.p, (int)counter_start, 1, gs));
 #ifdef RT_PHASE_TIMERS
             DevBuf phase_acc;
             HIP_TRY(phase_acc.alloc(PHASE_WORDS * sizeof(unsigned long long)));
-            HIP_TRY(hipMemsetAsync(phase_acc.p, 0, PHASE_WORDS * sizeof(unsigned long long), st));
+            HIP_TRY(hipMemsetAsync(phase_acc.p, 0, PHASE_WORDS * sizeof(unsigned long long), gs));
             p.phase_acc = phase_acc.as<unsigned long long>();
 #endif
-            HIP_TRY(hipEventRecord(ke[0], st));
-            // The generator declares LDS it does not use: more than two resident persistent workgroups leave free on a CU (160 KiB - 2 x
-            // ~77 KiB).  Alone on the GPU that changes nothing.  With a SECOND frame in flight on another stream (bench.py --pipeline 2)
-            // it keeps the next frame's generator from moving in beside the persistent kernel's main phase (measured harmful, EXPERIMENTS.md E2) and
-            // lets it start exactly when workgroups of the draining frame exit — it fills the tail instead.
+            HIP_TRY(hipEventRecord(ke[0], gs));
+            // RT06_PRIMARY_LDS: the generator declares LDS it does not use, more than two resident persistent workgroups leave free on a CU (160 KiB -
+            // 2 x ~77 KiB).  Alone on the GPU that changes nothing.  With a SECOND frame in flight (run-ahead, or bench.py --pipeline 2) it keeps the next
+            // frame's generator from moving in beside the persistent kernel's main phase and lets it start when workgroups of the draining frame exit.
+            // Off by default, on both paths: measured under run-ahead it is the slower setting (EXPERIMENTS.md E13), as it was with two renderers.
             static const uint32_t primary_lds = [] { const char* e = std::getenv("RT06_PRIMARY_LDS"); return e ? (uint32_t)std::atoi(e) : 0u; }();
             for (uint32_t b0 = 0; b0 < tm.n_local_tiles; b0 += 65535u) {   // grid.y = 64-pixel block, at most 65535 per launch
                 const uint32_t nb = std::min(65535u, tm.n_local_tiles - b0);
-                primary_rays_kernel<<<dim3((64u * p.pass_spp + 255u) / 256u, nb), 256, primary_lds, st>>>(p, b0);
+                primary_rays_kernel<<<dim3((64u * p.pass_spp + 255u) / 256u, nb), 256, primary_lds, gs>>>(p, b0);
                 HIP_TRY(hipGetLastError());
             }
             void* args[] = {&p};
             XchgParams xp;
             if (variant == 5) { xp = xchg_params(p); args[0] = &xp; }
-            HIP_TRY(hipEventRecord(ke[1], st));
-            HIP_TRY(hipLaunchKernel(nee.on() ? nee.kernel : stream_kernel, dim3(grid), dim3(stream_block), args, nee.on() ? nee.cur().lds_bytes : stream_lds_bytes, st));
-            HIP_TRY(hipEventRecord(ke[2], st));
+            HIP_TRY(hipEventRecord(ke[1], gs));
+            HIP_TRY(hipLaunchKernel(nee.on() ? nee.kernel : stream_kernel, dim3(grid), dim3(stream_block), args, nee.on() ? nee.cur().lds_bytes : stream_lds_bytes, gs));
+            HIP_TRY(hipEventRecord(ke[2], gs));
 #ifdef RT_PHASE_TIMERS
-            if (const int rc = report_phase_timers(phase_acc, st)) return rc;
+            if (const int rc = report_phase_timers(phase_acc, gs)) return rc;
 #endif
+            if (ahead) {   // back to the caller's stream: the resolve writes `out`, in the caller's order
+                HIP_TRY(hipEventRecord(sl.traced, gs));
+                HIP_TRY(hipStreamWaitEvent(st, sl.traced, 0));
+                HIP_TRY(hipEventRecord(kev_resolve0[ring_at], st));
+            }
             const uint32_t last = first + p.pass_spp >= end_s ? 1u : 0u;
             if (refine) refine_resolve_kernel<<<(n_pixels + 255) / 256, 256, 0, st>>>(p, accum.as<float4>(), out, last, end_s);
             else resolve_kernel<<<(n_pixels + 255) / 256, 256, 0, st>>>(p, running.as<float4>(), out, last);
@@ -443,33 +517,34 @@ struct rt_renderer {
             if (refine && aov_on)
                 if (const int rc = launch_aov(p, st)) return rc;
         }
+        if (n_slots == 2) HIP_TRY(hipEventRecord(sl.consumed, st));   // (a serial call has used slot 0)
         n_renders++;
         return RT_OK;
     }
     // what the baseline and the streaming kernels' parameters share; spp = the sample count the pixels are resolved against
-    template <typename Params> void frame_params(Params& p, uint32_t spp) const {
+    template <typename Params> void frame_params(Params& p, uint32_t spp, const Slot& sl) const {
         p.width = cfg.width; p.height = cfg.height;
         p.spp = spp; p.max_depth = cfg.max_depth;
         p.seed = cfg.seed;
         p.cam = cam;
         p.world = scene.dw;
         p.tm = tm;
-        p.work_counter = work_counter.as<uint32_t>();
+        p.work_counter = sl.work_counter.as<uint32_t>();
     }
     // what every pass of a call shares
-    StreamParams call_params(uint32_t spp) const {
+    StreamParams call_params(uint32_t spp, const Slot& sl) const {
         StreamParams p;
-        frame_params(p, spp);
+        frame_params(p, spp, sl);
         p.scene = scene.packed;
         p.scene.n_top = scene.big ? n_top : 0u;
         if (nee.on()) { p.scene.blob = (vn.on ? vn.nee_blob[nee.slot(nee.mode)] : nee.cur().blob).as<uint4>(); p.scene.blob_vec4 += nee.cur().table_vec4; }   // the same image with the light table behind it
         else if (vn.on) p.scene.blob = vn.blob.as<uint4>();   // ... with the vertex normals behind it (§21)
-        p.samples = samples.as<float4>();
+        p.samples = sl.samples.as<float4>();
         p.inner_keep = tune[0] ? tune[0] : 1u; p.shade_min = tune[1]; p.leaf_min = tune[2];
         const size_t n_pass = n_local_pixels(tm) * pass_spp;   // 16-B records per array
-        p.prim_o = primary.as<float4>();
-        p.prim_d = primary.as<float4>() + n_pass;
-        p.prim_rng = reinterpret_cast<uint4*>(primary.as<float4>() + 2 * n_pass);
+        p.prim_o = sl.primary.as<float4>();
+        p.prim_d = sl.primary.as<float4>() + n_pass;
+        p.prim_rng = reinterpret_cast<uint4*>(sl.primary.as<float4>() + 2 * n_pass);
         return p;
     }
     // the pass that starts at sample `first`: its share of the samples and the work-queue granularity; returns where the work counter starts
@@ -546,11 +621,23 @@ struct rt_renderer {
         if (dn_ev) (void)hipEventDestroy(dn_ev);
         if (refine_ev) (void)hipEventDestroy(refine_ev);
         for (auto& q : kev) for (hipEvent_t e : q) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : kev_resolve0) if (e) (void)hipEventDestroy(e);
+        drop_second_slot();
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
         if (stream) (void)hipStreamDestroy(stream);
     }
 };
+
+// the renderers alive in this process: what a renderer that could run ahead asks about the others (launch())
+static std::mutex g_live_mutex;
+static std::vector<rt_renderer*> g_live;
+static bool another_renderer_busy(const rt_renderer* self) {
+    std::lock_guard<std::mutex> lock(g_live_mutex);
+    for (const rt_renderer* o : g_live)
+        if (o != self && o->cfg.device == self->cfg.device && o->timed && hipEventQuery(o->ev1) == hipErrorNotReady) { (void)hipGetLastError(); return true; }
+    return false;
+}
 
 extern "C" int rt_renderer_create(const rt_render_config* cfg, const rt_camera* cam, const rt_world_flat* world, rt_renderer** out) {
     if (!cfg || !cam || !world || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_create: null argument");
@@ -592,7 +679,7 @@ extern "C" int rt_renderer_create(const rt_render_config* cfg, const rt_camera* 
     r->tm = make_tile_map(cfg->width, cfg->height, cfg->rank, cfg->world_size);
     size_t fb_floats = r->tm.direct ? (size_t)cfg->width * cfg->height * 4 : n_local_pixels(r->tm) * 4;
     hipError_t e = r->fb.alloc_zeroed(fb_floats * sizeof(float));
-    if (e == hipSuccess) e = r->work_counter.alloc(256);
+    if (e == hipSuccess) e = r->slot[0].work_counter.alloc(256);
     if (e == hipSuccess) {
         rc = r->plan();
         if (rc != RT_OK) { delete r; return rc; }
@@ -601,6 +688,7 @@ extern "C" int rt_renderer_create(const rt_render_config* cfg, const rt_camera* 
     if (e == hipSuccess) e = hipEventCreate(&r->ev0);
     if (e == hipSuccess) e = hipEventCreate(&r->ev1);
     if (e != hipSuccess) { delete r; return rt_fail(RT_ERR_HIP, "rt_renderer_create: %s", hipGetErrorString(e)); }
+    { std::lock_guard<std::mutex> lock(g_live_mutex); g_live.push_back(r); }
     *out = r;
     return RT_OK;
 }
@@ -608,15 +696,18 @@ extern "C" int rt_renderer_create(const rt_render_config* cfg, const rt_camera* 
 extern "C" void rt_renderer_destroy(rt_renderer* r) {
     if (!r) return;
     (void)hipSetDevice(r->cfg.device);
+    { std::lock_guard<std::mutex> lock(g_live_mutex); g_live.erase(std::remove(g_live.begin(), g_live.end(), r), g_live.end()); }
+    (void)r->drain_slots();   // queued launches read and write what is freed below
     delete r;
 }
 
-// one call's launches between the renderer's two timing events, on the caller's stream
-static int enqueue_call(rt_renderer* r, void* hip_stream, float* d_out, uint32_t first_s, uint32_t n_s, bool refine) {
+// one call's launches between the renderer's two timing events on the caller's stream (a call that runs ahead has its resolve between them, and
+// the wait for its tracer)
+static int enqueue_call(rt_renderer* r, void* hip_stream, float* d_out, uint32_t first_s, uint32_t n_s, bool refine, bool run_ahead = false) {
     HIP_TRY(hipSetDevice(r->cfg.device));
     hipStream_t st = (hipStream_t)hip_stream;  // NULL is the HIP null stream, as for any HIP launch
     HIP_TRY(hipEventRecord(r->ev0, st));
-    int rc = r->launch(st, d_out ? d_out : r->fb.as<float>(), first_s, n_s, refine);
+    int rc = r->launch(st, d_out ? d_out : r->fb.as<float>(), first_s, n_s, refine, run_ahead);
     if (rc != RT_OK) return rc;
     HIP_TRY(hipEventRecord(r->ev1, st));
     r->timed = true;
@@ -625,7 +716,7 @@ static int enqueue_call(rt_renderer* r, void* hip_stream, float* d_out, uint32_t
 
 extern "C" int rt_renderer_render_async(rt_renderer* r, void* hip_stream, float* d_out) {
     if (!r) return rt_fail(RT_ERR_INVALID, "rt_renderer_render_async: null renderer");
-    return enqueue_call(r, hip_stream, d_out, 0u, r->cfg.samples_per_pixel, false);
+    return enqueue_call(r, hip_stream, d_out, 0u, r->cfg.samples_per_pixel, false, true);
 }
 
 // the work of the last call may be on a caller's stream (the _async entry points): its end event orders what reads the results
@@ -633,7 +724,7 @@ static int wait_last_call(rt_renderer* r) {
     HIP_TRY(hipSetDevice(r->cfg.device));
     if (r->timed) HIP_TRY(hipEventSynchronize(r->ev1));
     HIP_TRY(hipStreamSynchronize(r->stream));
-    return RT_OK;
+    return r->drain_slots();   // ... and calls before the last may have been given other streams
 }
 
 // after a synchronisation: ray-exchange protocol error / traversal-queue overflow (both flags are read and cleared by their checks)
@@ -659,7 +750,7 @@ extern "C" int rt_renderer_set_camera(rt_renderer* r, const rt_camera* cam) {
     if (!r || !cam) return rt_fail(RT_ERR_INVALID, "rt_renderer_set_camera: null argument");
     if (cam->type > RT_CAM_MOTION) return rt_fail(RT_ERR_INVALID, "rt_renderer_set_camera: unknown camera type %u", cam->type);
     if (std::memcmp(&r->cam, cam, sizeof(rt_camera)) == 0) return RT_OK;   // the same bytes: nothing moves, the refinement goes on
-    r->cam = *cam;          // travels by value in the kernel arguments of the NEXT launch; launches already enqueued keep theirs
+    r->cam = *cam;          // travels by value in the kernel arguments of the NEXT launch; launches already enqueued keep theirs (those that run ahead too: no drain)
     r->refine_done = 0;     // samples accumulated under another camera belong to another frame
     r->aov_done = 0;        // ... and so do their first hits
     return RT_OK;
@@ -679,6 +770,7 @@ extern "C" int rt_renderer_light_sampling_enable(rt_renderer* r, uint32_t on) {
             return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: kernel variant %u has no light-sampling form (the baseline kernel 1, the ray exchange 5 and the tolerance mode 6 do not; use variant 0, 2 or 3)", r->tol ? 6u : r->variant);
         if (!t.refused.empty()) return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: %s", t.refused.c_str());
         HIP_TRY(hipSetDevice(r->cfg.device));
+        if (const int rc = r->drain_slots()) return rc;   // renders that ran ahead may still be queued: the tables and the kernel's LDS limit change behind them
         if (!t.built) {   // set last: a failure on the way is tried again
             const bool tree = on == RT_LIGHT_SAMPLING_TREE;   // §20: 2 n_l - 1 nodes of two vec4 behind the table: 1 + 2 n_l + 2 (2 n_l - 1) = 6 n_l - 1 vec4
             const uint32_t table_vec4 = 1u + t.n * (on == RT_LIGHT_SAMPLING_QUADS ? 1u : 2u) + (tree ? 2u * (2u * t.n - 1u) : 0u);
@@ -952,7 +1044,7 @@ extern "C" int rt_renderer_denoise_download(rt_renderer* r, float* host_rgba, si
 
 extern "C" int rt_renderer_render(rt_renderer* r) {
     if (!r) return rt_fail(RT_ERR_INVALID, "rt_renderer_render: null renderer");
-    int rc = rt_renderer_render_async(r, r->stream, nullptr);
+    int rc = enqueue_call(r, r->stream, nullptr, 0u, r->cfg.samples_per_pixel, false);   // serial: the host waits below, there is nothing to run ahead of
     if (rc == RT_OK) rc = wait_last_call(r);
     return rc != RT_OK ? rc : rt_renderer_check_device_flags(r);
 }
@@ -981,9 +1073,19 @@ extern "C" int rt_renderer_kernel_times(rt_renderer* r, uint32_t renders_back, f
     for (uint32_t pass = 0; pass < call_passes; pass++)   // a call is that many launches of each kernel: the SUM is the call's time in it
         for (int k = 0; k < 3; k++) {
             float ms = 0.0f;
-            HIP_TRY(hipEventElapsedTime(&ms, ring[pass * 4u + k], ring[pass * 4u + k + 1]));
+            // (a call that ran ahead is one pass; its resolve starts behind the wait for its tracer, at an event of its own)
+            HIP_TRY(hipEventElapsedTime(&ms, k == 2 && r->kev_ahead[slot] ? r->kev_resolve0[slot] : ring[pass * 4u + k], ring[pass * 4u + k + 1]));
             out_ms[k] += ms;
         }
+    return RT_OK;
+}
+
+extern "C" int rt_renderer_run_ahead_info(rt_renderer* r, uint64_t out[4]) {
+    if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_run_ahead_info: null argument");
+    out[0] = r->n_slots;
+    out[1] = r->n_ahead;
+    out[2] = r->n_overlapped;
+    out[3] = r->slot[1].samples.bytes + r->slot[1].primary.bytes;
     return RT_OK;
 }
 
@@ -992,7 +1094,7 @@ extern "C" int rt_renderer_pass_info(rt_renderer* r, uint64_t out[4]) {
     out[0] = r->variant >= 2 ? r->n_passes : 1u;
     out[1] = r->variant >= 2 ? r->pass_spp : r->cfg.samples_per_pixel;
     out[2] = r->variant >= 2 ? rt_renderer::SAMPLE_BYTES + rt_renderer::PRIMARY_BYTES : 0u;
-    out[3] = r->samples.bytes + r->primary.bytes + r->running.bytes;
+    out[3] = r->slot[0].samples.bytes + r->slot[0].primary.bytes + r->running.bytes;   // of one slot: what a call's passes use (the second set: rt_renderer_run_ahead_info)
     return RT_OK;
 }
 
@@ -1071,3 +1173,4 @@ extern "C" int rt_renderer_assemble(rt_renderer* r, const float* d_gathered, flo
 
 hipStream_t rt_renderer_own_stream(rt_renderer* r) { return r->stream; }
 float* rt_renderer_own_framebuffer(rt_renderer* r) { return r->fb.as<float>(); }
+void rt_renderer_one_slot(rt_renderer* r) { r->drop_second_slot(); }

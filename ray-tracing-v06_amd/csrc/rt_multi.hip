@@ -127,6 +127,7 @@ extern "C" int rt_multi_renderer_create(const rt_render_config* cfg, const rt_ca
         rt_renderer* r = nullptr;
         rc = rt_renderer_create(&c, cam, world, &r);
         if (rc != RT_OK) return rc;
+        rt_renderer_one_slot(r);   // this driver waits for every frame's exchange on the host: a second frame slot would be memory that nothing runs ahead into
         m->parts.push_back(r);
     }
     if (transport == RT_TRANSPORT_RCCL) {

@@ -407,3 +407,4 @@ static inline size_t n_local_pixels(const TileMap& tm) { return (size_t)tm.n_loc
 hipStream_t rt_renderer_own_stream(rt_renderer* r);      // the renderer's non-blocking stream
 float* rt_renderer_own_framebuffer(rt_renderer* r);      // its device framebuffer (world_size > 1: the tile-major shard)
 int rt_renderer_check_device_flags(rt_renderer* r);      // after a synchronisation: ray-exchange protocol error / traversal-queue overflow
+void rt_renderer_one_slot(rt_renderer* r);               // directly after creation: give the second frame slot back (every call then runs on the caller's stream)
