@@ -248,6 +248,32 @@ int rt_scene_vertex_normals(const rt_scene* s, const rt_tri_normals** out, uint3
 /* HOST (no GPU): the rule above on n hits — triangle tris[i] (Q, u, v, normal, w read), record vn[i], ray rays[6 i ..] = (o, d), hit distance t[i] ->
  * out_normal[3 i ..], out_interpolated[i] = 1 where the normal is the interpolated one, 0 where it is the flat one.  The function the kernels call.          */
 int rt_shading_normal_batch(size_t n, const rt_quad* tris, const rt_tri_normals* vn, const float* rays, const float* t, float* out_normal, uint32_t* out_interpolated);
+/* ---- texture coordinates (not in the reference): a (u, v) per vertex of a triangle, in the order a = Q, b = Q + u, c = Q + v.  Like the normals they
+ * travel BESIDE the flat world, one 24-byte record per triangle in the flat world's triangle order; sizeof(rt_quad) and sizeof(rt_world_flat) are what they were.
+ * The rule changes one thing: the albedo of an RT_MAT_LAMBERTIAN_IMAGE hit on a triangle (parallelograms and spheres look the image up as ever):
+ *   planar = hit_p - Q;  alpha = dot(w, cross(planar, v));  beta = dot(w, cross(u, planar));         (image_value_quad's three lines)
+ *   tu = (t0.u * ((1 - alpha) - beta) + t1.u * alpha) + t2.u * beta;   tv = (t0.v * ((1 - alpha) - beta) + t1.v * alpha) + t2.v * beta
+ *   albedo = the image's texel at (tu, tv): clamp to [0, 1], flip v, nearest texel, 1/255 — the lookup every image hit makes.
+ * Only fp32 + - *, each rounded on its own.  There is NO sentinel: a triangle without coordinates carries the identity record (0,0), (1,0), (0,1), under which
+ * tu = alpha and tv = beta up to the sign of a zero, so the texel is the one the planar lookup picks and "identity table" == "no table" bit for bit.
+ * No wrap modes, no filtering, one image per world, none on parallelograms.                                                                                  */
+typedef struct rt_tri_uvs { float t0[2], t1[2], t2[2]; } rt_tri_uvs;   /* 24 B */
+/* rt_scene_add_triangle with a texture coordinate per vertex (ta, tb, tc: two floats each, finite; RT_ERR_INVALID otherwise, scene unchanged) and, optionally,
+ * a normal per vertex as rt_scene_add_triangle_smooth takes them (na = nb = nc = NULL: a flat triangle)                                                     */
+int rt_scene_add_triangle_uv(rt_scene* s, const float a[3], const float b[3], const float c[3], const float na[3], const float nb[3], const float nc[3],
+                             const float ta[2], const float tb[2], const float tc[2], int32_t mat, int32_t* out_quad);
+/* rt_scene_add_mesh_smooth (normals = NULL with n_normals = 0: a flat mesh) with n_uvs texture coordinates (2 floats each) and, per face, three indices into them
+ * (uv_indices; NULL = the vertex indices).  The coordinates are neither rotated, scaled nor translated.  One that is not finite, or an index out of range, fails
+ * the whole call and leaves the scene unchanged.                                                                                                                */
+int rt_scene_add_mesh_uv(rt_scene* s, uint32_t n_vertices, const float* xyz, uint32_t n_normals, const float* normals, uint32_t n_uvs, const float* uvs,
+                         uint32_t n_triangles, const uint32_t* indices, const uint32_t* normal_indices, const uint32_t* uv_indices, int32_t mat, float scale,
+                         float rotate_y_degrees, const float translate[3], int32_t* out_first, uint32_t* out_added);
+/* One record per triangle of the flat world, in its triangle order, carried through everything that permutes triangles as the normals are.  *out_n = 0 (and
+ * *out = NULL) when every record is the identity.  The pointer stays valid until the scene is modified or destroyed.                                         */
+int rt_scene_texture_coords(const rt_scene* s, const rt_tri_uvs** out, uint32_t* out_n);
+/* HOST (no GPU): the rule above on n hits — triangle tris[i] (Q, u, v, w read), record uv[i], ray rays[6 i ..] = (o, d), hit distance t[i] -> out_uv[2 i ..] =
+ * (tu, tv) BEFORE the clamp.  The function the kernels call.                                                                                                 */
+int rt_tri_uv_batch(size_t n, const rt_quad* tris, const rt_tri_uvs* uv, const float* rays, const float* t, float* out_uv);
 /* camera::background of "The Next Week": mode 0 = the reference's sky gradient, 1 = constant colour       */
 int rt_scene_set_background(rt_scene* s, uint32_t mode, const float color[3]);
 /* selects RT_TRAVERSAL_STACK / RT_TRAVERSAL_QUEUE / RT_TRAVERSAL_WIDE4 for the BVH world of this scene (see the enum) */
@@ -615,6 +641,14 @@ int rt_world_light_tree(const rt_world_flat* w, uint32_t capacity, float* out_no
 int rt_renderer_shading_normals(rt_renderer* r, const rt_tri_normals* table, uint32_t n);
 /* out[0] = 1 while a table is on, out[1] = how many of its records are not flat */
 int rt_renderer_shading_normals_info(rt_renderer* r, uint32_t out[2]);
+/* Texture coordinates (see rt_tri_uvs): the renderer's table, one record per triangle of its world — n must equal rt_world_triangles of it — or NULL, 0 to turn
+ * it off.  Copied; every value finite.  Takes effect at the next launch; an unchanged table is a no-op that keeps the refinement, a change discards the refinement
+ * and feature-buffer state.  The table lies in global memory behind the scene image and the vertex normals (either may be on without the other) and is read once
+ * per image-textured hit on a triangle.  RT_ERR_INVALID with a message of its own: the baseline kernel (variant 1), a queue or wide4 traversal, variants 5 and 6,
+ * a wrong n, a value that is not finite.                                                                                                                      */
+int rt_renderer_texture_coords(rt_renderer* r, const rt_tri_uvs* table, uint32_t n);
+/* out[0] = 1 while a table is on, out[1] = how many of its records are not the identity */
+int rt_renderer_texture_coords_info(rt_renderer* r, uint32_t out[2]);
 
 /* ------------------------------------------------------------------ */
 /* Multi-GPU renderer — the same three entry points (Renderer.h:38-46)  */
@@ -642,6 +676,8 @@ int rt_multi_renderer_refine(rt_multi_renderer* m, uint32_t n_samples);
 int rt_multi_renderer_light_sampling_enable(rt_multi_renderer* m, uint32_t on);
 /* rt_renderer_shading_normals on every rank (the first rank refuses what any would, before any changes).                 */
 int rt_multi_renderer_shading_normals(rt_multi_renderer* m, const rt_tri_normals* table, uint32_t n);
+/* rt_renderer_texture_coords on every rank (refused before any rank changes).                                             */
+int rt_multi_renderer_texture_coords(rt_multi_renderer* m, const rt_tri_uvs* table, uint32_t n);
 /* Renderer::DownloadRenderbuffer: width*height*4 floats from devices[0].                                                */
 int rt_multi_renderer_download(rt_multi_renderer* m, float* host_rgba, size_t n_floats);
 /* ms of the last render: out[0] host wall-clock of Render(), out[1] slowest rank's kernels (HIP events),
@@ -674,6 +710,10 @@ int rt_probe_trace(int device, const rt_world_flat* world, size_t n, const float
  * rt_world_triangles of the world, or NULL, 0) -> hit n, normal n*3 (the flat normal where the rule keeps it; 0 on a miss), interpolated n (0/1)            */
 int rt_probe_shading_normal(int device, const rt_world_flat* world, const rt_tri_normals* table, uint32_t n_table, size_t n, const float* rays,
                             int32_t* out_hit, float* out_normal, uint32_t* out_interpolated);
+/* Hittable::ClosestIntersection on a whole world, then the texture-coordinate rule on a triangle hit: rays n*7 (o,d,time), table = n_table records (n_table ==
+ * rt_world_triangles of the world, or NULL, 0 = no table: the planar coordinates on a triangle too) -> hit n, uv n*2: (tu, tv) before the clamp on a triangle,
+ * the planar (alpha, beta) on a parallelogram, 0 on a sphere or a miss                                                                                        */
+int rt_probe_tri_uv(int device, const rt_world_flat* world, const rt_tri_uvs* table, uint32_t n_table, size_t n, const float* rays, int32_t* out_hit, float* out_uv);
 /* SphereHittable / MovingSphereHittable::ClosestIntersection (SphereHittable.cu:56-66, :91-102): sphere
  * prims[i] (material ignored, RT_PRIM_MOVING kept) against ray i (o,d,time) with rec.distance preset[i]
  * -> hit n, rec.distance n, normal n*3 (0 when not hit)                      */

@@ -44,6 +44,13 @@ struct vec3 {
 };
 inline vec3 operator+(const vec3& a, const vec3& b) { return vec3(a.x + b.x, a.y + b.y, a.z + b.z); }
 inline vec3 operator-(const vec3& a, const vec3& b) { return vec3(a.x - b.x, a.y - b.y, a.z - b.z); }
+struct vec2 {
+    float x, y;
+    vec2() : x(0), y(0) {}
+    vec2(float x_, float y_) : x(x_), y(y_) {}
+    float& operator[](int i) { return (&x)[i]; }
+    const float& operator[](int i) const { return (&x)[i]; }
+};
 struct vec4 {
     float x, y, z, w;
     vec4() : x(0), y(0), z(0), w(0) {}
@@ -308,6 +315,35 @@ public:
               "rt_scene_add_mesh_smooth");
         return added;
     }
+    // ... and with a texture coordinate per vertex, for an image-textured material (rt_scene_add_triangle_uv, rt_scene_add_mesh_uv): `normals` may be null / empty
+    // (a flat triangle, a flat mesh); normal_indices, uv_indices empty = the vertex indices
+    int32_t AddTriangle(glm::vec3 a, glm::vec3 b, glm::vec3 c, const glm::vec3* normals, glm::vec2 ta, glm::vec2 tb, glm::vec2 tc, const Material* mat) {
+        const float pa[3] = {a[0], a[1], a[2]}, pb[3] = {b[0], b[1], b[2]}, pc[3] = {c[0], c[1], c[2]};
+        const float ua[2] = {ta[0], ta[1]}, ub[2] = {tb[0], tb[1]}, uc[2] = {tc[0], tc[1]};
+        float q[3][3] = {};
+        for (int i = 0; normals && i < 3; i++) { q[i][0] = normals[i][0]; q[i][1] = normals[i][1]; q[i][2] = normals[i][2]; }
+        int32_t quad = 0;
+        check(rt_scene_add_triangle_uv(s_, pa, pb, pc, normals ? q[0] : nullptr, normals ? q[1] : nullptr, normals ? q[2] : nullptr, ua, ub, uc, material(mat), &quad),
+              "rt_scene_add_triangle_uv");
+        return quad;
+    }
+    uint32_t AddMesh(const std::vector<glm::vec3>& vertices, const std::vector<glm::vec3>& normals, const std::vector<glm::vec2>& uvs, const std::vector<uint32_t>& indices,
+                     const std::vector<uint32_t>& normal_indices, const std::vector<uint32_t>& uv_indices, const Material* mat, float scale = 1.0f, float rotate_y_degrees = 0.0f,
+                     glm::vec3 translate = glm::vec3(0.0f), int32_t* out_first = nullptr) {
+        std::vector<float> xyz, nrm, tuv;
+        for (const glm::vec3& p : vertices) { xyz.push_back(p[0]); xyz.push_back(p[1]); xyz.push_back(p[2]); }
+        for (const glm::vec3& n : normals) { nrm.push_back(n[0]); nrm.push_back(n[1]); nrm.push_back(n[2]); }
+        for (const glm::vec2& t : uvs) { tuv.push_back(t[0]); tuv.push_back(t[1]); }
+        if (!normal_indices.empty() && normal_indices.size() != indices.size()) throw std::runtime_error("AddMesh: one normal index per vertex index");
+        if (!uv_indices.empty() && uv_indices.size() != indices.size()) throw std::runtime_error("AddMesh: one texture coordinate index per vertex index");
+        const float t[3] = {translate[0], translate[1], translate[2]};
+        uint32_t added = 0;
+        check(rt_scene_add_mesh_uv(s_, (uint32_t)vertices.size(), xyz.data(), (uint32_t)normals.size(), normals.empty() ? nullptr : nrm.data(), (uint32_t)uvs.size(), tuv.data(),
+                                   (uint32_t)(indices.size() / 3), indices.data(), normal_indices.empty() ? nullptr : normal_indices.data(),
+                                   uv_indices.empty() ? nullptr : uv_indices.data(), material(mat), scale, rotate_y_degrees, t, out_first, &added),
+              "rt_scene_add_mesh_uv");
+        return added;
+    }
     void perlin(uint64_t seed) { check(rt_scene_set_perlin(s_, seed), "rt_scene_set_perlin"); }
     void image(uint32_t w, uint32_t h, const uint8_t* rgb) { check(rt_scene_set_image(s_, w, h, rgb), "rt_scene_set_image"); }
     void background(const Background& b) {
@@ -551,6 +587,10 @@ class Renderer {
             uint32_t n = 0;
             rt06::check(rt_scene_vertex_normals(static_cast<const BVH*>(world)->scene, &table, &n), "rt_scene_vertex_normals");
             if (n) made.SetShadingNormals(table, n);
+            const rt_tri_uvs* uv = nullptr;                // ... and one with texture coordinates theirs
+            uint32_t n_uv = 0;
+            rt06::check(rt_scene_texture_coords(static_cast<const BVH*>(world)->scene, &uv, &n_uv), "rt_scene_texture_coords");
+            if (n_uv) made.SetTextureCoords(uv, n_uv);
         }
         return made;
     }
@@ -637,6 +677,11 @@ public:
     void SetShadingNormals(const rt_tri_normals* table, uint32_t n) {
         if (m.mr) rt06::check(rt_multi_renderer_shading_normals(m.mr, table, n), "Renderer::SetShadingNormals");
         else rt06::check(rt_renderer_shading_normals(m.r, table, n), "Renderer::SetShadingNormals");
+    }
+    // Texture coordinates (extension; rt_renderer_texture_coords): one record of three (u, v) per triangle of the world, or (nullptr, 0) for off; restarts a refinement
+    void SetTextureCoords(const rt_tri_uvs* table, uint32_t n) {
+        if (m.mr) rt06::check(rt_multi_renderer_texture_coords(m.mr, table, n), "Renderer::SetTextureCoords");
+        else rt06::check(rt_renderer_texture_coords(m.r, table, n), "Renderer::SetTextureCoords");
     }
     void SetLightSampling(bool on) {
         if (m.mr) rt06::check(rt_multi_renderer_light_sampling_enable(m.mr, on ? 1u : 0u), "Renderer::SetLightSampling");

@@ -147,11 +147,21 @@ class Scene:
         check(lib().rt_scene_add_quad(self.h, v3(Q), v3(u), v3(v), mat, C.byref(out)))
         return out.value
 
-    def MakeTriangle(self, a, b, c, mat, normals=None):
+    def MakeTriangle(self, a, b, c, mat, normals=None, uvs=None):
         """tri of "The Next Week" from its three vertices (extension, not in the reference): a quad of kind 1; returns its quad index.
-        normals: one normal per vertex, (3, 3), for smooth shading (rt_scene_add_triangle_smooth)."""
+        normals: one normal per vertex, (3, 3), for smooth shading (rt_scene_add_triangle_smooth).
+        uvs: one texture coordinate per vertex, (3, 2), for an image-textured material (rt_scene_add_triangle_uv)."""
         out = C.c_int32()
-        if normals is None:
+        if uvs is not None:
+            ta, tb, tc = (capi.vec2(*t) for t in np.asarray(uvs, dtype=np.float32).reshape(3, 2))
+            if normals is None:
+                na = nb = nc = None
+            else:
+                na, nb, nc = (v3(n) for n in np.asarray(normals, dtype=np.float32).reshape(3, 3))
+            check(lib().rt_scene_add_triangle_uv(self.h, v3(a), v3(b), v3(c), na, nb, nc, ta, tb, tc, mat, C.byref(out)))
+            self._uv = True
+            self._smooth = getattr(self, "_smooth", False) or normals is not None
+        elif normals is None:
             check(lib().rt_scene_add_triangle(self.h, v3(a), v3(b), v3(c), mat, C.byref(out)))
         else:
             na, nb, nc = np.asarray(normals, dtype=np.float32).reshape(3, 3)
@@ -159,17 +169,42 @@ class Scene:
             self._smooth = True
         return out.value
 
-    def MakeMesh(self, vertices, faces, mat, scale=1.0, rotate_y=0.0, translate=(0, 0, 0), normals=None, normal_faces=None):
+    def MakeMesh(self, vertices, faces, mat, scale=1.0, rotate_y=0.0, translate=(0, 0, 0), normals=None, normal_faces=None, uvs=None, uv_faces=None):
         """An indexed triangle mesh (extension): vertices (n, 3), faces (m, 3); every vertex is scaled, rotated about y (degrees) and translated
         as MakeBox does it.  Degenerate faces are skipped.  Returns (index of the first triangle added, number added).
         normals (k, 3): vertex normals for smooth shading, rotated with the mesh and normalised; normal_faces (m, 3): per face the
-        indices into them (default: the faces' vertex indices)."""
+        indices into them (default: the faces' vertex indices).
+        uvs (k, 2): texture coordinates for an image-textured material, taken as they are; uv_faces (m, 3): per face the indices into
+        them (default: the faces' vertex indices)."""
         xyz = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
         idx = np.ascontiguousarray(faces, dtype=np.int64).reshape(-1, 3)
         if idx.size and (idx.min() < 0 or idx.max() > 0xffffffff):
             raise ValueError("MakeMesh: a face index is negative or does not fit 32 bits")
         idx = np.ascontiguousarray(idx, dtype=np.uint32)
         first, added = C.c_int32(), C.c_uint32()
+
+        def index_triples(name, given):
+            if given is None:
+                return None
+            a = np.ascontiguousarray(given, dtype=np.int64).reshape(-1, 3)
+            if a.shape != idx.shape or (a.size and (a.min() < 0 or a.max() > 0xffffffff)):
+                raise ValueError(f"MakeMesh: {name} must hold one non-negative 32-bit index triple per face")
+            return np.ascontiguousarray(a, dtype=np.uint32)
+
+        if uvs is None and uv_faces is not None:
+            raise ValueError("MakeMesh: uv_faces without uvs")
+        if uvs is not None:
+            if normals is None and normal_faces is not None:
+                raise ValueError("MakeMesh: normal_faces without normals")
+            tuv = np.ascontiguousarray(uvs, dtype=np.float32).reshape(-1, 2)
+            nrm = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3) if normals is not None else None
+            nidx, tidx = index_triples("normal_faces", normal_faces), index_triples("uv_faces", uv_faces)
+            check(lib().rt_scene_add_mesh_uv(self.h, xyz.shape[0], xyz, nrm.shape[0] if nrm is not None else 0, nrm.ctypes.data if nrm is not None else None,
+                                             tuv.shape[0], tuv, idx.shape[0], idx, nidx.ctypes.data if nidx is not None else None,
+                                             tidx.ctypes.data if tidx is not None else None, mat, scale, rotate_y, v3(translate), C.byref(first), C.byref(added)))
+            self._uv = True
+            self._smooth = getattr(self, "_smooth", False) or normals is not None
+            return first.value, added.value
         if normals is None:
             if normal_faces is not None:
                 raise ValueError("MakeMesh: normal_faces without normals")
@@ -193,6 +228,13 @@ class Scene:
         ptr, n = C.c_void_p(), C.c_uint32()
         check(lib().rt_scene_vertex_normals(self.h, C.byref(ptr), C.byref(n)))
         return self._arr(ptr.value, n.value, capi.TRI_NORMALS_DT)
+
+    def texture_coords(self):
+        """The scene's texture coordinates, one record per triangle of the flat world in its triangle order (rt_scene_texture_coords): a structured array of
+        capi.TRI_UVS_DT (t0, t1, t2; (0,0), (1,0), (0,1) = a triangle without any); empty when every record is that identity."""
+        ptr, n = C.c_void_p(), C.c_uint32()
+        check(lib().rt_scene_texture_coords(self.h, C.byref(ptr), C.byref(n)))
+        return self._arr(ptr.value, n.value, capi.TRI_UVS_DT)
 
     def n_triangles(self):
         """How many of the flat world's quads are triangles (its last ones): rt_world_triangles."""
@@ -268,6 +310,8 @@ class Scene:
         check(lib().rt_scene_get_flat(self.h, C.byref(w)))
         if getattr(self, "_smooth", False):   # the table travels beside the flat world: Renderer / MultiRenderer push it at creation (a scene without normals: no call)
             w.vertex_normals = self.vertex_normals()
+        if getattr(self, "_uv", False):       # likewise the texture coordinates (a scene that was given none: no call)
+            w.texture_coords = self.texture_coords()
         return w
 
     def _arr(self, ptr, n, dt):
@@ -351,6 +395,21 @@ def _push_normals(fn, handle, table):
     return fn(handle, t.ctypes.data if len(t) else None, len(t))
 
 
+def uvs_table(table):
+    """a table of texture coordinates as float32 (n, 6): from Scene.texture_coords()'s records or an array of shape (n, 6) / (n, 3, 2)"""
+    a = np.asarray(table)
+    if a.dtype == capi.TRI_UVS_DT:
+        return np.ascontiguousarray(a).view(np.float32).reshape(-1, 6)
+    return np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 6)
+
+
+def _push_uvs(fn, handle, table):
+    if table is None:
+        return fn(handle, None, 0)
+    t = uvs_table(table)
+    return fn(handle, t.ctypes.data if len(t) else None, len(t))
+
+
 class Renderer:
     """Renderer (main/src/Renderer.h:12-47) over the C ABI."""
 
@@ -367,6 +426,8 @@ class Renderer:
         r = cls(h, cfg)
         if len(getattr(world, "vertex_normals", ())):
             r.shading_normals(world.vertex_normals)
+        if len(getattr(world, "texture_coords", ())):
+            r.texture_coords(world.texture_coords)
         return r
 
     def Render(self):
@@ -483,6 +544,17 @@ class Renderer:
         check(lib().rt_renderer_shading_normals_info(self.h, out))
         return {"enabled": bool(out[0]), "smooth": out[1]}
 
+    def texture_coords(self, table):
+        """Texture coordinates from the next launch on (rt_renderer_texture_coords): table = one record of three (u, v) per triangle of the
+        world (Scene.texture_coords(), or anything of shape (n, 6) / (n, 3, 2)), None = off.  A change restarts the refinement."""
+        check(_push_uvs(lib().rt_renderer_texture_coords, self.h, table))
+
+    def texture_coords_info(self):
+        """{'enabled', 'mapped'}: whether a table of texture coordinates is on, and how many of its records are not the identity."""
+        out = (C.c_uint32 * 2)()
+        check(lib().rt_renderer_texture_coords_info(self.h, out))
+        return {"enabled": bool(out[0]), "mapped": out[1]}
+
     def last_kernel_ms(self):
         ms = C.c_float()
         check(lib().rt_renderer_last_kernel_ms(self.h, C.byref(ms)))
@@ -574,6 +646,8 @@ class MultiRenderer:
         m = cls(h, cfg)
         if len(getattr(world, "vertex_normals", ())):
             m.shading_normals(world.vertex_normals)
+        if len(getattr(world, "texture_coords", ())):
+            m.texture_coords(world.texture_coords)
         return m
 
     def Render(self):
@@ -594,6 +668,10 @@ class MultiRenderer:
     def shading_normals(self, table):
         """rt_renderer_shading_normals on every rank; `table` as Renderer.shading_normals takes it."""
         check(_push_normals(lib().rt_multi_renderer_shading_normals, self.h, table))
+
+    def texture_coords(self, table):
+        """rt_renderer_texture_coords on every rank; `table` as Renderer.texture_coords takes it."""
+        check(_push_uvs(lib().rt_multi_renderer_texture_coords, self.h, table))
 
     def DownloadRenderbuffer(self):
         out = np.zeros((self.cfg.height, self.cfg.width, 4), dtype=np.float32)
@@ -835,3 +913,25 @@ def probe_shading_normal(world, table, rays, device=0):
     hit, normal, took = np.zeros(n, np.int32), np.zeros((n, 3), np.float32), np.zeros(n, np.uint32)
     check(lib().rt_probe_shading_normal(device, C.byref(world), tab.ctypes.data if len(tab) else None, len(tab), n, rays, hit, normal, took))
     return hit, normal, took
+
+
+def tri_uv_batch(tris, uv, rays, t):
+    """rt_tri_uv_batch (host only): the texture-coordinate rule on hit i of triangle record tris[i] (capi.QUAD_DT) with the record uv[i], ray rays[i] (o, d)
+    and hit distance t[i] -> (n, 2) float32: (tu, tv) before the clamp"""
+    tris = np.ascontiguousarray(tris, dtype=capi.QUAD_DT)
+    uv, rays, t = uvs_table(uv), np.ascontiguousarray(rays, np.float32).reshape(-1, 6), np.ascontiguousarray(t, np.float32)
+    n = len(tris)
+    assert len(uv) == n and len(rays) == n and len(t) == n
+    out = np.zeros((n, 2), np.float32)
+    check(lib().rt_tri_uv_batch(n, tris.ctypes.data, uv.ctypes.data, rays, t, out))
+    return out
+
+
+def probe_tri_uv(world, table, rays, device=0):
+    """rt_probe_tri_uv: the world's walk, then the texture-coordinate rule on a triangle hit -> (hit int32, uv (n, 2): before the clamp; planar on a parallelogram)"""
+    rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 7)
+    n = len(rays)
+    tab = uvs_table(table) if table is not None else np.zeros((0, 6), np.float32)
+    hit, uv = np.zeros(n, np.int32), np.zeros((n, 2), np.float32)
+    check(lib().rt_probe_tri_uv(device, C.byref(world), tab.ctypes.data if len(tab) else None, len(tab), n, rays, hit, uv))
+    return hit, uv

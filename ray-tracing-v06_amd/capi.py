@@ -25,11 +25,13 @@ f32p = np.ctypeslib.ndpointer(dtype=np.float32, flags="C_CONTIGUOUS")
 i32p = np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")
 u32p = np.ctypeslib.ndpointer(dtype=np.uint32, flags="C_CONTIGUOUS")
 vec3 = C.c_float * 3
+vec2 = C.c_float * 2
 
 NODE_DT = np.dtype([("min", "<f4", 3), ("max", "<f4", 3), ("left", "<i4"), ("right", "<i4")])
 PRIM_DT = np.dtype([("c0", "<f4", 3), ("radius", "<f4"), ("c1", "<f4", 3), ("mat", "<u4")])
 MAT_DT = np.dtype([("albedo", "<f4", 3), ("param", "<f4"), ("albedo2", "<f4", 3), ("type", "<u4")])
 TRI_NORMALS_DT = np.dtype([("n0", "<f4", 3), ("n1", "<f4", 3), ("n2", "<f4", 3)])   # rt_tri_normals, 36 B
+TRI_UVS_DT = np.dtype([("t0", "<f4", 2), ("t1", "<f4", 2), ("t2", "<f4", 2)])   # rt_tri_uvs, 24 B
 QUAD_DT = np.dtype([("Q", "<f4", 3), ("D", "<f4"), ("u", "<f4", 3), ("mat", "<u4"), ("v", "<f4", 3), ("kind", "<u4"),
                     ("normal", "<f4", 3), ("pad1", "<f4"), ("w", "<f4", 3), ("pad2", "<f4")])
 
@@ -90,6 +92,8 @@ SYMBOLS = [
     "rt_scene_add_triangle_smooth", "rt_scene_add_mesh_smooth", "rt_scene_vertex_normals", "rt_shading_normal_batch", "rt_renderer_shading_normals",
     "rt_renderer_shading_normals_info", "rt_multi_renderer_shading_normals", "rt_probe_shading_normal",
     "rt_renderer_run_ahead_info",
+    "rt_scene_add_triangle_uv", "rt_scene_add_mesh_uv", "rt_scene_texture_coords", "rt_tri_uv_batch", "rt_renderer_texture_coords",
+    "rt_renderer_texture_coords_info", "rt_multi_renderer_texture_coords", "rt_probe_tri_uv",
 ]
 
 _lib = None
@@ -182,6 +186,15 @@ def lib():
     L.rt_renderer_shading_normals_info.argtypes = [C.c_void_p, C.c_uint32 * 2]
     L.rt_multi_renderer_shading_normals.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     L.rt_probe_shading_normal.argtypes = [C.c_int, P(WorldFlat), C.c_void_p, C.c_uint32, C.c_size_t, f32p, i32p, f32p, u32p]
+    L.rt_scene_add_triangle_uv.argtypes = [C.c_void_p, vec3, vec3, vec3, C.c_void_p, C.c_void_p, C.c_void_p, vec2, vec2, vec2, C.c_int32, P(C.c_int32)]
+    L.rt_scene_add_mesh_uv.argtypes = [C.c_void_p, C.c_uint32, f32p, C.c_uint32, C.c_void_p, C.c_uint32, f32p, C.c_uint32, u32p, C.c_void_p, C.c_void_p, C.c_int32,
+                                       C.c_float, C.c_float, vec3, P(C.c_int32), P(C.c_uint32)]
+    L.rt_scene_texture_coords.argtypes = [C.c_void_p, P(C.c_void_p), P(C.c_uint32)]
+    L.rt_tri_uv_batch.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p, f32p, f32p, f32p]
+    L.rt_renderer_texture_coords.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+    L.rt_renderer_texture_coords_info.argtypes = [C.c_void_p, C.c_uint32 * 2]
+    L.rt_multi_renderer_texture_coords.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+    L.rt_probe_tri_uv.argtypes = [C.c_int, P(WorldFlat), C.c_void_p, C.c_uint32, C.c_size_t, f32p, i32p, f32p]
     L.rt_scene_set_background.argtypes = [C.c_void_p, C.c_uint32, vec3]
     L.rt_scene_set_perlin.argtypes = [C.c_void_p, C.c_uint64]
     L.rt_scene_set_image.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]

@@ -224,16 +224,38 @@ struct rt_renderer {
     // smooth shading (rt_renderer_shading_normals): the table as given (9 floats per triangle of the world), a flat copy for the feature pass, and
     // the images the triangle kernels launch on while it is on — the plain image and, per light-sampling mode already built, the image with that mode's light
     // table — each followed by the header (1, -, -, -) and the table.  Off, every launch gets the image it always got, whose header is zero.
-    struct { bool on = false; uint32_t n_smooth = 0; std::vector<float> host; DevBuf table, blob, nee_blob[4]; } vn;
-    // `src` holds staged_vec4 units of image (and a zero header); dst = the same units, then the header that says a table follows, then the table
-    int image_with_normals(const DevBuf& src, uint32_t staged_vec4, DevBuf& dst) const {
-        const size_t tab_vec4 = (vn.host.size() * sizeof(float) + 15u) / 16u;
-        std::vector<uint4> tail(1u + tab_vec4, make_uint4(0u, 0u, 0u, 0u));
-        tail[0].x = 1u;
-        std::memcpy(&tail[1], vn.host.data(), vn.host.size() * sizeof(float));
-        HIP_TRY(dst.alloc(((size_t)staged_vec4 + tail.size()) * sizeof(uint4)));
+    struct { bool on = false; uint32_t n_smooth = 0; std::vector<float> host; DevBuf table; } vn;
+    // texture coordinates (rt_renderer_texture_coords): the table as given (6 floats per triangle of the world); it rides in the same tail
+    struct { bool on = false; uint32_t n_mapped = 0; std::vector<float> host; } uv;
+    // the images with a tail, held while either table is on: the plain image's and each built light-sampling mode's
+    struct { DevBuf blob, nee_blob[4]; } tail;
+    bool tail_on() const { return vn.on || uv.on; }
+    // `src` holds staged_vec4 units of image (and a zero header); dst = the same units, then the header (normals follow at +1 ? 1 : 0, vec4 from the header to
+    // the texture coordinates or 0, -, -), then the normals if on, then the texture coordinates if on — each table from a 16-byte boundary
+    int image_with_tail(const DevBuf& src, uint32_t staged_vec4, DevBuf& dst) const {
+        const size_t vn_vec4 = vn.on ? (vn.host.size() * sizeof(float) + 15u) / 16u : 0u;
+        const size_t uv_vec4 = uv.on ? (uv.host.size() * sizeof(float) + 15u) / 16u : 0u;
+        std::vector<uint4> t(1u + vn_vec4 + uv_vec4, make_uint4(0u, 0u, 0u, 0u));
+        t[0].x = vn.on ? 1u : 0u;
+        t[0].y = uv.on ? (uint32_t)(1u + vn_vec4) : 0u;
+        if (vn.on) std::memcpy(&t[1], vn.host.data(), vn.host.size() * sizeof(float));
+        if (uv.on) std::memcpy(&t[1u + vn_vec4], uv.host.data(), uv.host.size() * sizeof(float));
+        HIP_TRY(dst.alloc(((size_t)staged_vec4 + t.size()) * sizeof(uint4)));
         HIP_TRY(hipMemcpy(dst.p, src.p, (size_t)staged_vec4 * sizeof(uint4), hipMemcpyDeviceToDevice));
-        HIP_TRY(hipMemcpy(dst.as<uint4>() + staged_vec4, tail.data(), tail.size() * sizeof(uint4), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(dst.as<uint4>() + staged_vec4, t.data(), t.size() * sizeof(uint4), hipMemcpyHostToDevice));
+        return RT_OK;
+    }
+    // the tails anew from vn and uv as they stand: none while both are off, else the plain image's and one per light-sampling mode already built
+    int rebuild_tails() {
+        tail.blob.release();
+        for (DevBuf& b : tail.nee_blob) b.release();
+        if (!tail_on()) return RT_OK;
+        if (const int rc = image_with_tail(scene.blob, scene.packed.blob_vec4, tail.blob)) return rc;
+        for (const uint32_t mode : {RT_LIGHT_SAMPLING_QUADS, RT_LIGHT_SAMPLING_ALL, RT_LIGHT_SAMPLING_MESH, RT_LIGHT_SAMPLING_TREE}) {
+            const LightTable& t = nee.tab[nee.slot(mode)];
+            if (t.built)
+                if (const int rc = image_with_tail(t.blob, scene.packed.blob_vec4 + t.table_vec4, tail.nee_blob[nee.slot(mode)])) return rc;
+        }
         return RT_OK;
     }
     // denoiser (rt_renderer_denoise): guide records, the two colour buffers the iterations ping-pong, the output frame; allocated at first use
@@ -537,8 +559,8 @@ struct rt_renderer {
         frame_params(p, spp, sl);
         p.scene = scene.packed;
         p.scene.n_top = scene.big ? n_top : 0u;
-        if (nee.on()) { p.scene.blob = (vn.on ? vn.nee_blob[nee.slot(nee.mode)] : nee.cur().blob).as<uint4>(); p.scene.blob_vec4 += nee.cur().table_vec4; }   // the same image with the light table behind it
-        else if (vn.on) p.scene.blob = vn.blob.as<uint4>();   // ... with the vertex normals behind it (§21)
+        if (nee.on()) { p.scene.blob = (tail_on() ? tail.nee_blob[nee.slot(nee.mode)] : nee.cur().blob).as<uint4>(); p.scene.blob_vec4 += nee.cur().table_vec4; }   // the same image with the light table behind it
+        else if (tail_on()) p.scene.blob = tail.blob.as<uint4>();   // ... with the vertex normals (§21) and the texture coordinates (§22) behind it
         p.samples = sl.samples.as<float4>();
         p.inner_keep = tune[0] ? tune[0] : 1u; p.shade_min = tune[1]; p.leaf_min = tune[2];
         const size_t n_pass = n_local_pixels(tm) * pass_spp;   // 16-B records per array
@@ -807,8 +829,8 @@ extern "C" int rt_renderer_light_sampling_enable(rt_renderer* r, uint32_t on) {
             t.kernel = k;
             t.built = true;
         }
-        if (r->vn.on && !r->vn.nee_blob[r->nee.slot(on)].p)   // this mode's image once more, with the vertex normals behind its light table
-            if (const int rc = r->image_with_normals(t.blob, r->scene.packed.blob_vec4 + t.table_vec4, r->vn.nee_blob[r->nee.slot(on)])) return rc;
+        if (r->tail_on() && !r->tail.nee_blob[r->nee.slot(on)].p)   // this mode's image once more, with the vertex normals and texture coordinates behind its light table
+            if (const int rc = r->image_with_tail(t.blob, r->scene.packed.blob_vec4 + t.table_vec4, r->tail.nee_blob[r->nee.slot(on)])) return rc;
         r->nee.kernel = t.kernel;
     }
     r->nee.mode = on;       // of the NEXT launch; launches already enqueued keep their kernel and their image (the images with the tables stay allocated)
@@ -850,21 +872,55 @@ extern "C" int rt_renderer_shading_normals(rt_renderer* r, const rt_tri_normals*
     if (n ? (r->vn.on && r->vn.host.size() * sizeof(float) == bytes && std::memcmp(r->vn.host.data(), table, bytes) == 0) : !r->vn.on) return RT_OK;   // nothing changes, the refinement goes on
     if (const int rc = wait_last_call(r)) return rc;   // launches already enqueued read the images that are replaced below
     r->vn.on = false;
-    r->vn.table.release(); r->vn.blob.release();
-    for (DevBuf& b : r->vn.nee_blob) b.release();
+    r->vn.table.release();
     r->refine_done = 0;   // samples shaded with other normals belong to another frame
     r->aov_done = 0;
-    if (!n) { r->vn.host.clear(); r->vn.n_smooth = 0; return RT_OK; }
+    if (!n) { r->vn.host.clear(); r->vn.n_smooth = 0; return r->rebuild_tails(); }   // the texture coordinates, if on, stay on
     r->vn.host.assign(table[0].n0, table[0].n0 + (size_t)n * 9u);
     r->vn.n_smooth = n_smooth;
-    HIP_TRY(r->vn.table.upload(r->vn.host.data(), bytes));
-    if (const int rc = r->image_with_normals(r->scene.blob, r->scene.packed.blob_vec4, r->vn.blob)) return rc;
-    for (const uint32_t mode : {RT_LIGHT_SAMPLING_QUADS, RT_LIGHT_SAMPLING_ALL, RT_LIGHT_SAMPLING_MESH, RT_LIGHT_SAMPLING_TREE}) {
-        const rt_renderer::LightTable& t = r->nee.tab[r->nee.slot(mode)];
-        if (t.built)
-            if (const int rc = r->image_with_normals(t.blob, r->scene.packed.blob_vec4 + t.table_vec4, r->vn.nee_blob[r->nee.slot(mode)])) return rc;
-    }
+    if (const hipError_t e = r->vn.table.upload(r->vn.host.data(), bytes); e != hipSuccess) { r->rebuild_tails(); HIP_TRY(e); }
     r->vn.on = true;
+    if (const int rc = r->rebuild_tails()) { r->vn.on = false; r->rebuild_tails(); return rc; }
+    return RT_OK;
+}
+
+// Texture coordinates, as the normals above: off, every launch is what it was; on, the same kernels on images whose tail holds the table.
+extern "C" int rt_renderer_texture_coords(rt_renderer* r, const rt_tri_uvs* table, uint32_t n) {
+    if (!r) return rt_fail(RT_ERR_INVALID, "rt_renderer_texture_coords: null renderer");
+    if ((table == nullptr) != (n == 0u)) return rt_fail(RT_ERR_INVALID, "rt_renderer_texture_coords: a table and its count go together (NULL, 0 turns it off)");
+    uint32_t n_mapped = 0;
+    if (n) {
+        if (r->variant < 2) return rt_fail(RT_ERR_INVALID, "rt_renderer_texture_coords: the baseline kernel (variant 1) reads no table of texture coordinates; use variant 0, 2 or 3");
+        if (r->scene.queue) return rt_fail(RT_ERR_INVALID, "rt_renderer_texture_coords: a world with a queue or wide4 traversal renders on lane walks that read no table of texture coordinates (RT_TRAVERSAL_STACK and lists do)");
+        if (r->variant == 5 || r->tol) return rt_fail(RT_ERR_INVALID, "rt_renderer_texture_coords: kernel variant %u renders no triangles", r->tol ? 6u : 5u);
+        if (n != r->scene.n_triangles) return rt_fail(RT_ERR_INVALID, "rt_renderer_texture_coords: %u records for a world of %u triangles", n, r->scene.n_triangles);
+        static const float identity[6] = {0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 1.0f};
+        for (uint32_t i = 0; i < n; i++) {
+            const float* v = table[i].t0;   // six floats: t0, t1, t2
+            for (int k = 0; k < 6; k++)
+                if (!std::isfinite(v[k])) return rt_fail(RT_ERR_INVALID, "rt_renderer_texture_coords: record %u: a value that is not finite", i);
+            for (int k = 0; k < 6; k++)
+                if (v[k] != identity[k]) { n_mapped++; break; }
+        }
+    }
+    const size_t bytes = (size_t)n * sizeof(rt_tri_uvs);
+    if (n ? (r->uv.on && r->uv.host.size() * sizeof(float) == bytes && std::memcmp(r->uv.host.data(), table, bytes) == 0) : !r->uv.on) return RT_OK;   // nothing changes, the refinement goes on
+    if (const int rc = wait_last_call(r)) return rc;   // launches already enqueued read the images that are replaced below
+    r->uv.on = false;
+    r->refine_done = 0;   // samples textured through other coordinates belong to another frame
+    r->aov_done = 0;
+    if (!n) { r->uv.host.clear(); r->uv.n_mapped = 0; return r->rebuild_tails(); }   // the vertex normals, if on, stay on
+    r->uv.host.assign(table[0].t0, table[0].t0 + (size_t)n * 6u);
+    r->uv.n_mapped = n_mapped;
+    r->uv.on = true;
+    if (const int rc = r->rebuild_tails()) { r->uv.on = false; r->rebuild_tails(); return rc; }
+    return RT_OK;
+}
+
+extern "C" int rt_renderer_texture_coords_info(rt_renderer* r, uint32_t out[2]) {
+    if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_texture_coords_info: null argument");
+    out[0] = r->uv.on ? 1u : 0u;
+    out[1] = r->uv.on ? r->uv.n_mapped : 0u;
     return RT_OK;
 }
 

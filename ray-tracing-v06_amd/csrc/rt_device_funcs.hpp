@@ -433,6 +433,23 @@ RT_HD f3 image_value_quad(const uint8_t* image, uint32_t width, uint32_t height,
     float beta = dot(w, cross(u, planar));
     return image_texel(image, width, height, alpha, beta);
 }
+// Texture coordinates (rt06.h: rt_tri_uvs): on a triangle the planar coordinates weigh the three vertices' (u, v), t0 at Q, t1 at Q + u, t2 at
+// Q + v.  Only + - *, each rounded on its own, in this association.  Under the identity record (0,0), (1,0), (0,1) the products with 0 are zeros and those with
+// 1 are exact, so tu = alpha and tv = beta up to the sign of a zero: the texel is image_value_quad's.  The streaming kernels, the probe and rt_tri_uv_batch call
+// this one function, and numpy float32 restates it bit for bit.
+RT_HD void tri_uv(f3 Q, f3 u, f3 v, f3 w, const float t0[2], const float t1[2], const float t2[2], f3 hit_p, float& tu, float& tv) {
+    f3 planar = hit_p - Q;
+    float alpha = dot(w, cross(planar, v));
+    float beta = dot(w, cross(u, planar));
+    const float gamma = (1.0f - alpha) - beta;
+    tu = (t0[0] * gamma + t1[0] * alpha) + t2[0] * beta;
+    tv = (t0[1] * gamma + t1[1] * alpha) + t2[1] * beta;
+}
+RT_HD f3 image_value_tri(const uint8_t* image, uint32_t width, uint32_t height, f3 Q, f3 u, f3 v, f3 w, const float t0[2], const float t1[2], const float t2[2], f3 hit_p) {
+    float tu, tv;
+    tri_uv(Q, u, v, w, t0, t1, t2, hit_p, tu, tv);
+    return image_texel(image, width, height, tu, tv);
+}
 // image_texture::value(u, v) of "The Next Week": clamp, flip v to image coordinates, nearest texel, 1/255
 RT_HD f3 image_texel(const uint8_t* image, uint32_t width, uint32_t height, float u, float v) {
     u = u < 0.0f ? 0.0f : (u > 1.0f ? 1.0f : u);

@@ -153,6 +153,7 @@ struct rt_scene {
     uint32_t n_tris = 0;
     std::vector<rt_tri_normals> tri_vn;   // vertex normals: one record per triangle, in the triangles' order (nine zeros = flat); moves with them
     uint32_t n_smooth = 0;                // how many of those records are not flat: 0 = the scene has no table
+    std::vector<rt_tri_uvs> tri_uv;       // texture coordinates: parallel to tri_vn; a triangle without any holds the identity (0,0), (1,0), (0,1)
     uint32_t background = 0;
     float background_color[3] = {0.0f, 0.0f, 0.0f};
     uint32_t traversal = RT_TRAVERSAL_STACK;
@@ -266,6 +267,7 @@ extern "C" int rt_scene_add_quad(rt_scene* s, const float Q[3], const float u[3]
 
 // ---- triangles and meshes (not in the reference; the `tri` of "Ray Tracing: The Next Week": a quad with another interior test) ----
 // the record of triangle (a, b, c), or false for a degenerate face: dot(n, n) of n = cross(b - a, c - a) not finite and > 0
+static const rt_tri_uvs RT_TRI_UVS_IDENTITY = {{0.0f, 0.0f}, {1.0f, 0.0f}, {0.0f, 1.0f}};   // §22: under it a triangle's texture coordinates are its planar ones
 static bool tri_record(f3 a, f3 b, f3 c, uint32_t mat, rt_quad& q) {
     std::memset(&q, 0, sizeof(q));
     st3(q.Q, a); st3(q.u, b - a); st3(q.v, c - a);
@@ -285,6 +287,7 @@ extern "C" int rt_scene_add_triangle(rt_scene* s, const float a[3], const float 
         return rt_fail(RT_ERR_INVALID, "rt_scene_add_triangle: degenerate triangle (the squared length of cross(b - a, c - a) is not finite and > 0)");
     s->quads.push_back(q);
     s->tri_vn.push_back(rt_tri_normals{});
+    s->tri_uv.push_back(RT_TRI_UVS_IDENTITY);
     s->n_tris++;
     s->world_set = false;
     if (out_quad) *out_quad = (int32_t)s->quads.size() - 1;
@@ -306,6 +309,26 @@ extern "C" int rt_scene_add_triangle_smooth(rt_scene* s, const float a[3], const
     if (const int rc = rt_scene_add_triangle(s, a, b, c, mat, out_quad)) return rc;
     s->tri_vn.back() = vn;
     s->n_smooth++;
+    return RT_OK;
+}
+extern "C" int rt_scene_add_triangle_uv(rt_scene* s, const float a[3], const float b[3], const float c[3], const float na[3], const float nb[3], const float nc[3],
+                                        const float ta[2], const float tb[2], const float tc[2], int32_t mat, int32_t* out_quad) {
+    if (!s || !a || !b || !c || !ta || !tb || !tc) return rt_fail(RT_ERR_INVALID, "rt_scene_add_triangle_uv: null argument");
+    if ((na == nullptr) != (nb == nullptr) || (na == nullptr) != (nc == nullptr)) return rt_fail(RT_ERR_INVALID, "rt_scene_add_triangle_uv: three vertex normals or none");
+    const rt_tri_uvs uv = {{ta[0], ta[1]}, {tb[0], tb[1]}, {tc[0], tc[1]}};
+    for (int k = 0; k < 6; k++)
+        if (!std::isfinite(uv.t0[k])) return rt_fail(RT_ERR_INVALID, "rt_scene_add_triangle_uv: a texture coordinate is not finite");
+    if (const int rc = na ? rt_scene_add_triangle_smooth(s, a, b, c, na, nb, nc, mat, out_quad) : rt_scene_add_triangle(s, a, b, c, mat, out_quad)) return rc;
+    s->tri_uv.back() = uv;
+    return RT_OK;
+}
+extern "C" int rt_scene_texture_coords(const rt_scene* s, const rt_tri_uvs** out, uint32_t* out_n) {
+    if (!s || !out || !out_n) return rt_fail(RT_ERR_INVALID, "rt_scene_texture_coords: null argument");
+    bool any = false;
+    for (const rt_tri_uvs& r : s->tri_uv)
+        if (!(r.t0[0] == 0.0f && r.t0[1] == 0.0f && r.t1[0] == 1.0f && r.t1[1] == 0.0f && r.t2[0] == 0.0f && r.t2[1] == 1.0f)) { any = true; break; }
+    *out = any ? s->tri_uv.data() : nullptr;
+    *out_n = any ? (uint32_t)s->tri_uv.size() : 0u;
     return RT_OK;
 }
 extern "C" int rt_scene_vertex_normals(const rt_scene* s, const rt_tri_normals** out, uint32_t* out_n) {
@@ -337,6 +360,7 @@ struct Item {
     rt_prim p;
     rt_quad q;
     rt_tri_normals vn;   // of a triangle: its vertex normals travel with it
+    rt_tri_uvs uv;       // ... and its texture coordinates (§22)
 };
 struct Builder {
     std::vector<Item> arr;
@@ -451,8 +475,8 @@ static int build_bvh(rt_scene* s, int builder) {
     Builder B(s->nodes);
     B.arr.reserve(s->prims.size() + s->quads.size());
     const size_t n_plain = s->quads.size() - s->n_tris;
-    for (const rt_prim& p : s->prims) B.arr.push_back(Item{prim_bounds(p), false, p, rt_quad{}, rt_tri_normals{}});
-    for (size_t i = 0; i < s->quads.size(); i++) B.arr.push_back(Item{quad_record_bounds(s->quads[i]), true, rt_prim{}, s->quads[i], i >= n_plain ? s->tri_vn[i - n_plain] : rt_tri_normals{}});
+    for (const rt_prim& p : s->prims) B.arr.push_back(Item{prim_bounds(p), false, p, rt_quad{}, rt_tri_normals{}, rt_tri_uvs{}});
+    for (size_t i = 0; i < s->quads.size(); i++) B.arr.push_back(Item{quad_record_bounds(s->quads[i]), true, rt_prim{}, s->quads[i], i >= n_plain ? s->tri_vn[i - n_plain] : rt_tri_normals{}, i >= n_plain ? s->tri_uv[i - n_plain] : rt_tri_uvs{}});
     int32_t root;
     if (builder == 0) root = B.rec1(0, (int)B.arr.size());
     else if (builder == 1) root = B.rec2(0, (int)B.arr.size());
@@ -465,7 +489,7 @@ static int build_bvh(rt_scene* s, int builder) {
         for (size_t i = 0; i < B.arr.size(); i++) {
             if (B.arr[i].is_quad) {
                 size_t& at = B.arr[i].q.kind == RT_QUAD_TRIANGLE ? ti : qi;
-                if (B.arr[i].q.kind == RT_QUAD_TRIANGLE) s->tri_vn[at - n_plain] = B.arr[i].vn;
+                if (B.arr[i].q.kind == RT_QUAD_TRIANGLE) { s->tri_vn[at - n_plain] = B.arr[i].vn; s->tri_uv[at - n_plain] = B.arr[i].uv; }
                 s->quads[at] = B.arr[i].q; unified[i] = (int32_t)(ns + at); at++;
             }
             else { s->prims[si] = B.arr[i].p; unified[i] = (int32_t)si; si++; }
@@ -948,8 +972,9 @@ extern "C" int rt_scene_add_box(rt_scene* s, const float a[3], const float b[3],
 
 // An indexed mesh as triangles: every vertex p -> rot_y(p * scale) + translate (cornell_box's order and arithmetic), then tri_record per face.
 // normals (rt_scene_add_mesh_smooth; null for the flat mesh): rot_y of each, then unit_normal; a face takes normal_indices' three, or its vertex indices.
-static int add_mesh(const char* who, rt_scene* s, uint32_t n_vertices, const float* xyz, uint32_t n_normals, const float* normals, uint32_t n_triangles, const uint32_t* indices,
-                    const uint32_t* normal_indices, int32_t mat, float scale, float rotate_y_degrees, const float translate[3], int32_t* out_first, uint32_t* out_added) {
+// uvs (rt_scene_add_mesh_uv; null otherwise): as given, finite; a face takes uv_indices' three, or its vertex indices; without them every face gets the identity.
+static int add_mesh(const char* who, rt_scene* s, uint32_t n_vertices, const float* xyz, uint32_t n_normals, const float* normals, uint32_t n_uvs, const float* uvs,
+                    uint32_t n_triangles, const uint32_t* indices, const uint32_t* normal_indices, const uint32_t* uv_indices, int32_t mat, float scale, float rotate_y_degrees, const float translate[3], int32_t* out_first, uint32_t* out_added) {
     if (!s || (n_vertices && !xyz) || (n_triangles && !indices)) return rt_fail(RT_ERR_INVALID, "%s: null argument", who);
     if (mat < 0 || (size_t)mat >= s->mats.size()) return rt_fail(RT_ERR_INVALID, "%s: material %d out of range", who, mat);
     if (!std::isfinite(scale) || !std::isfinite(rotate_y_degrees)) return rt_fail(RT_ERR_INVALID, "%s: scale and rotation must be finite", who);
@@ -961,6 +986,14 @@ static int add_mesh(const char* who, rt_scene* s, uint32_t n_vertices, const flo
         for (size_t i = 0; i < (size_t)n_triangles * 3u; i++)
             if (nidx[i] >= n_normals)
                 return rt_fail(RT_ERR_INVALID, "%s: face %zu: normal index %u out of range (%u normals)", who, i / 3u, nidx[i], n_normals);
+    const uint32_t* tidx = uv_indices ? uv_indices : indices;
+    if (uvs) {
+        for (size_t i = 0; i < (size_t)n_triangles * 3u; i++)
+            if (tidx[i] >= n_uvs)
+                return rt_fail(RT_ERR_INVALID, "%s: face %zu: texture coordinate index %u out of range (%u texture coordinates)", who, i / 3u, tidx[i], n_uvs);
+        for (size_t i = 0; i < (size_t)n_uvs * 2u; i++)
+            if (!std::isfinite(uvs[i])) return rt_fail(RT_ERR_INVALID, "%s: texture coordinate %zu is not finite", who, i / 2u);
+    }
     const float rad = radians(rotate_y_degrees), c = cosf(rad), sn = sinf(rad);
     const f3 offset = translate ? ld3(translate) : mk3(0.0f);
     std::vector<f3> pts(n_vertices);
@@ -971,6 +1004,7 @@ static int add_mesh(const char* who, rt_scene* s, uint32_t n_vertices, const flo
             return rt_fail(RT_ERR_INVALID, "%s: normal %u is not finite or has zero length", who, i);
     std::vector<rt_quad> tris;
     std::vector<rt_tri_normals> vns;
+    std::vector<rt_tri_uvs> tuv;
     tris.reserve(n_triangles);
     for (uint32_t f = 0; f < n_triangles; f++) {
         rt_quad q;
@@ -982,11 +1016,18 @@ static int add_mesh(const char* who, rt_scene* s, uint32_t n_vertices, const flo
             std::memcpy(vn.n2, &unit[3 * (size_t)nidx[3 * (size_t)f + 2]], 12);
         }
         vns.push_back(vn);
+        rt_tri_uvs uv = RT_TRI_UVS_IDENTITY;
+        if (uvs) {
+            std::memcpy(uv.t0, &uvs[2 * (size_t)tidx[3 * (size_t)f]], 8); std::memcpy(uv.t1, &uvs[2 * (size_t)tidx[3 * (size_t)f + 1]], 8);
+            std::memcpy(uv.t2, &uvs[2 * (size_t)tidx[3 * (size_t)f + 2]], 8);
+        }
+        tuv.push_back(uv);
     }
     if (out_first) *out_first = (int32_t)s->quads.size();
     if (out_added) *out_added = (uint32_t)tris.size();
     s->quads.insert(s->quads.end(), tris.begin(), tris.end());
     s->tri_vn.insert(s->tri_vn.end(), vns.begin(), vns.end());
+    s->tri_uv.insert(s->tri_uv.end(), tuv.begin(), tuv.end());
     s->n_tris += (uint32_t)tris.size();
     if (normals) s->n_smooth += (uint32_t)tris.size();
     if (!tris.empty()) s->world_set = false;
@@ -994,13 +1035,20 @@ static int add_mesh(const char* who, rt_scene* s, uint32_t n_vertices, const flo
 }
 extern "C" int rt_scene_add_mesh(rt_scene* s, uint32_t n_vertices, const float* xyz, uint32_t n_triangles, const uint32_t* indices, int32_t mat, float scale,
                                  float rotate_y_degrees, const float translate[3], int32_t* out_first, uint32_t* out_added) {
-    return add_mesh("rt_scene_add_mesh", s, n_vertices, xyz, 0u, nullptr, n_triangles, indices, nullptr, mat, scale, rotate_y_degrees, translate, out_first, out_added);
+    return add_mesh("rt_scene_add_mesh", s, n_vertices, xyz, 0u, nullptr, 0u, nullptr, n_triangles, indices, nullptr, nullptr, mat, scale, rotate_y_degrees, translate, out_first, out_added);
 }
 extern "C" int rt_scene_add_mesh_smooth(rt_scene* s, uint32_t n_vertices, const float* xyz, uint32_t n_normals, const float* normals, uint32_t n_triangles,
                                         const uint32_t* indices, const uint32_t* normal_indices, int32_t mat, float scale, float rotate_y_degrees, const float translate[3],
                                         int32_t* out_first, uint32_t* out_added) {
     if (!normals) return rt_fail(RT_ERR_INVALID, "rt_scene_add_mesh_smooth: null normals (rt_scene_add_mesh adds a flat mesh)");
-    return add_mesh("rt_scene_add_mesh_smooth", s, n_vertices, xyz, n_normals, normals, n_triangles, indices, normal_indices, mat, scale, rotate_y_degrees, translate, out_first, out_added);
+    return add_mesh("rt_scene_add_mesh_smooth", s, n_vertices, xyz, n_normals, normals, 0u, nullptr, n_triangles, indices, normal_indices, nullptr, mat, scale, rotate_y_degrees, translate, out_first, out_added);
+}
+extern "C" int rt_scene_add_mesh_uv(rt_scene* s, uint32_t n_vertices, const float* xyz, uint32_t n_normals, const float* normals, uint32_t n_uvs, const float* uvs,
+                                    uint32_t n_triangles, const uint32_t* indices, const uint32_t* normal_indices, const uint32_t* uv_indices, int32_t mat, float scale,
+                                    float rotate_y_degrees, const float translate[3], int32_t* out_first, uint32_t* out_added) {
+    if (!uvs) return rt_fail(RT_ERR_INVALID, "rt_scene_add_mesh_uv: null texture coordinates (rt_scene_add_mesh and rt_scene_add_mesh_smooth add a mesh without)");
+    return add_mesh("rt_scene_add_mesh_uv", s, n_vertices, xyz, normals ? n_normals : 0u, normals, n_uvs, uvs, n_triangles, indices, normal_indices, uv_indices, mat, scale, rotate_y_degrees, translate,
+                    out_first, out_added);
 }
 
 // The image the book loads from earthmap.jpg is not redistributable here: a synthetic 256 x 128 "planet" (integer

@@ -277,6 +277,15 @@ extern "C" int rt_multi_renderer_shading_normals(rt_multi_renderer* m, const rt_
     return RT_OK;
 }
 
+extern "C" int rt_multi_renderer_texture_coords(rt_multi_renderer* m, const rt_tri_uvs* table, uint32_t n) {
+    if (!m) return rt_fail(RT_ERR_INVALID, "rt_multi_renderer_texture_coords: null renderer");
+    for (rt_renderer* r : m->parts) {   // every rank holds the same world on the same variant: the first refuses what any would, before any part changes
+        const int rc = rt_renderer_texture_coords(r, table, n);
+        if (rc != RT_OK) return rc;
+    }
+    return RT_OK;
+}
+
 extern "C" int rt_multi_renderer_download(rt_multi_renderer* m, float* host_rgba, size_t n_floats) {
     if (!m || !host_rgba) return rt_fail(RT_ERR_INVALID, "rt_multi_renderer_download: null argument");
     const size_t need = (size_t)m->width * m->height * 4;

@@ -53,6 +53,34 @@ __global__ void probe_shading_normal_kernel(DeviceWorld w, const rt_tri_normals*
     interpolated[i] = took ? 1u : 0u;
     st3(normal + 3 * i, rec.normal);
 }
+// the world's own walk, then the texture-coordinate rule (tri_uv) on a triangle hit: uv = one record per triangle, or null = the identity on each;
+// a parallelogram keeps its planar coordinates, whatever the table says
+__global__ void probe_tri_uv_kernel(DeviceWorld w, const rt_tri_uvs* uv, uint32_t first_tri, size_t n, const float* rays, int32_t* hit, float* out_uv) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Ray r;
+    r.o = ld3(rays + 7 * i); r.d = ld3(rays + 7 * i + 3); r.time = rays[7 * i + 6];
+    HitRec rec;
+    rec.distance = RT_MISS_DIST; rec.normal = mk3(0.0f); rec.prim = -1; rec.mat = 0;
+    Rng g;
+    g.init(0u, (uint32_t)i, 0u, 0x7ACEu);
+    const bool h = world_closest_intersection(w, r, rec, &g);
+    float tu = 0.0f, tv = 0.0f;
+    if (h && (uint32_t)rec.prim >= w.n_prims) {
+        const rt_quad& q = w.quads[(uint32_t)rec.prim - w.n_prims];
+        const f3 hit_p = ray_at(r, rec.distance);
+        if (uv && (uint32_t)rec.prim >= first_tri) {
+            const rt_tri_uvs& t = uv[(uint32_t)rec.prim - first_tri];
+            tri_uv(ld3(q.Q), ld3(q.u), ld3(q.v), ld3(q.w), t.t0, t.t1, t.t2, hit_p, tu, tv);
+        } else {   // image_value_quad's coordinates
+            const f3 planar = hit_p - ld3(q.Q);
+            tu = dot(ld3(q.w), cross(planar, ld3(q.v)));
+            tv = dot(ld3(q.w), cross(ld3(q.u), planar));
+        }
+    }
+    hit[i] = h ? 1 : 0;
+    out_uv[2 * i] = tu; out_uv[2 * i + 1] = tv;
+}
 // SphereHittable / MovingSphereHittable::ClosestIntersection on one sphere per ray, rec.distance preset by the caller: the leaf
 // test every traversal calls (prim_closest_intersection), as a plain sphere (material 0 = a Lambertian, the moving bit kept)
 __global__ void probe_sphere_hit_kernel(size_t n, const rt_prim* prims, const rt_material* mat, const float* rays, const float* preset,
@@ -250,6 +278,30 @@ extern "C" int rt_probe_shading_normal(int device, const rt_world_flat* world, c
     auto h = p.out(out_hit, n); auto nn = p.out(out_normal, 3 * n); auto it = p.out(out_interpolated, n);
     p.launch(probe_shading_normal_kernel, p.per_case(n), 128, sc.dw, vn, world->n_prims + world->n_quads - sc.n_triangles, n, r, h, nn, it);
     return p.finish() != RT_OK ? p.rc : check_traversal_overflow(sc);
+}
+extern "C" int rt_probe_tri_uv(int device, const rt_world_flat* world, const rt_tri_uvs* table, uint32_t n_table, size_t n, const float* rays, int32_t* out_hit, float* out_uv) {
+    if (!rays || !out_hit || !out_uv) return rt_fail(RT_ERR_INVALID, "rt_probe_tri_uv: null argument");
+    if ((table == nullptr) != (n_table == 0u)) return rt_fail(RT_ERR_INVALID, "rt_probe_tri_uv: a table and its count go together");
+    ProbeRun p(device);
+    DeviceScene sc;
+    if (p.ok()) p.rc = sc.upload(world);
+    if (p.ok() && n_table && n_table != sc.n_triangles) p.rc = rt_fail(RT_ERR_INVALID, "rt_probe_tri_uv: %u records for a world of %u triangles", n_table, sc.n_triangles);
+    if (!p.ok() || n == 0) return p.rc;
+    auto r = p.in(rays, 7 * n);
+    const rt_tri_uvs* uv = n_table ? p.in(table, (size_t)n_table) : nullptr;
+    auto h = p.out(out_hit, n); auto o = p.out(out_uv, 2 * n);
+    p.launch(probe_tri_uv_kernel, p.per_case(n), 128, sc.dw, uv, world->n_prims + world->n_quads - sc.n_triangles, n, r, h, o);
+    return p.finish() != RT_OK ? p.rc : check_traversal_overflow(sc);
+}
+// HOST (no GPU): the kernels' tri_uv() over arrays
+extern "C" int rt_tri_uv_batch(size_t n, const rt_quad* tris, const rt_tri_uvs* uv, const float* rays, const float* t, float* out_uv) {
+    if (n && (!tris || !uv || !rays || !t || !out_uv)) return rt_fail(RT_ERR_INVALID, "rt_tri_uv_batch: null argument");
+    for (size_t i = 0; i < n; i++) {
+        Ray r;
+        r.o = ld3(rays + 6 * i); r.d = ld3(rays + 6 * i + 3); r.time = 0.0f;
+        tri_uv(ld3(tris[i].Q), ld3(tris[i].u), ld3(tris[i].v), ld3(tris[i].w), uv[i].t0, uv[i].t1, uv[i].t2, ray_at(r, t[i]), out_uv[2 * i], out_uv[2 * i + 1]);
+    }
+    return RT_OK;
 }
 // HOST (no GPU): the kernels' shading_normal() over arrays — here, not in rt_host.cpp, because this translation unit sees rt_device_funcs.hpp
 extern "C" int rt_shading_normal_batch(size_t n, const rt_quad* tris, const rt_tri_normals* vn, const float* rays, const float* t, float* out_normal, uint32_t* out_interpolated) {

@@ -256,6 +256,9 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
     // triangle, in global memory whatever the form of the image.  Wave-uniform; a world without a table pays this one scalar load and one scalar branch per shaded quad hit.
     uint32_t vn_on = 0u;
     if constexpr (TRI) vn_on = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.scene.blob[p.scene.blob_vec4].x);
+    // §22, TRI with image textures (EXT >= 2) only: the same header's .y = how many vec4 behind the header the texture coordinates start (24 B per triangle), 0 = none
+    uint32_t uv_at = 0u;
+    if constexpr (TRI && EXT >= 2) uv_at = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.scene.blob[p.scene.blob_vec4].y);
     const f3 root_min = mk3(p.scene.root_min[0], p.scene.root_min[1], p.scene.root_min[2]);
     const f3 root_max = mk3(p.scene.root_max[0], p.scene.root_max[1], p.scene.root_max[2]);
 
@@ -795,8 +798,15 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                         if (EXT >= 2 && mtype == RT_MAT_LAMBERTIAN_NOISE) albedo = noise_value(p.scene.perlin, albedo, mparam, hit_p);
                         if (EXT >= 2 && mtype == RT_MAT_LAMBERTIAN_IMAGE) {
                             if ((uint32_t)rec_code >= p.scene.sphere_codes) {   // on a quad: (u, v) = the planar coordinates of the hit
-                                const float4* qd = quads + ((uint32_t)rec_code - p.scene.sphere_codes) * 4u;
+                                const uint32_t qi = (uint32_t)rec_code - p.scene.sphere_codes;
+                                const float4* qd = quads + qi * 4u;
                                 const float4 a0 = qd[0], a1 = qd[1], a2 = qd[2], a3 = qd[3];
+                                if (TRI && uv_at != 0u && qi >= p.scene.n_plain_quads) {   // §22: a triangle under a table of texture coordinates weighs its vertices' (u, v)
+                                    const float* tr = reinterpret_cast<const float*>(p.scene.blob + p.scene.blob_vec4 + uv_at) + (size_t)(qi - p.scene.n_plain_quads) * 6u;
+                                    const float t0[2] = {tr[0], tr[1]}, t1[2] = {tr[2], tr[3]}, t2[2] = {tr[4], tr[5]};
+                                    albedo = image_value_tri(p.scene.image, p.scene.image_w, p.scene.image_h, mk3(a0.x, a0.y, a0.z), mk3(a1.x, a1.y, a1.z),
+                                                             mk3(a1.w, a2.x, a2.y), mk3(a3.y, a3.z, a3.w), t0, t1, t2, hit_p);
+                                } else
                                 albedo = image_value_quad(p.scene.image, p.scene.image_w, p.scene.image_h, mk3(a0.x, a0.y, a0.z), mk3(a1.x, a1.y, a1.z),
                                                           mk3(a1.w, a2.x, a2.y), mk3(a3.y, a3.z, a3.w), hit_p);
                             } else {

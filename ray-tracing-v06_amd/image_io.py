@@ -4,6 +4,7 @@
 writes JPEG q95 through stb_image_write; here PNG (lossless, zlib from the standard library) and binary PPM.
 A NaN channel (NaN pixels) is written as 0: the reference's static_cast of NaN is undefined
 behaviour and yields 0 on x86.
+read_ppm and read_png go the other way, for texture images (Scene.set_image).
 """
 import struct
 import zlib
@@ -40,6 +41,102 @@ def write_png(path, framebuffer):
     with open(path, "wb") as f:
         f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0))
                 + chunk(b"IDAT", zlib.compress(raw, 6)) + chunk(b"IEND", b""))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Readers, for Scene.set_image (texture images): uint8 RGB [H][W][3], row 0 = top, as the file has it.
+# ---------------------------------------------------------------------------------------------------------------------
+def read_ppm(path):
+    """A binary PPM (P6, maxval 255; `#` comments in the header) -> uint8 [H][W][3]."""
+    with open(path, "rb") as f:
+        data = f.read()
+    pos, fields = 0, []
+    while len(fields) < 4:   # magic, width, height, maxval: tokens between whitespace, comments run to the end of their line
+        while pos < len(data) and (data[pos:pos + 1].isspace() or data[pos:pos + 1] == b"#"):
+            if data[pos:pos + 1] == b"#":
+                while pos < len(data) and data[pos:pos + 1] != b"\n":
+                    pos += 1
+            else:
+                pos += 1
+        start = pos
+        while pos < len(data) and not data[pos:pos + 1].isspace() and data[pos:pos + 1] != b"#":
+            pos += 1
+        if start == pos:
+            raise ValueError(f"{path}: truncated PPM header")
+        fields.append(data[start:pos])
+    if fields[0] != b"P6":
+        raise ValueError(f"{path}: not a binary PPM (P6)")
+    try:
+        w, h, maxval = int(fields[1]), int(fields[2]), int(fields[3])
+    except ValueError:
+        raise ValueError(f"{path}: bad PPM header") from None
+    if w <= 0 or h <= 0 or maxval != 255:
+        raise ValueError(f"{path}: a PPM of positive size with maxval 255 is read (got {w} x {h}, maxval {maxval})")
+    pos += 1   # the single whitespace byte behind maxval
+    if len(data) - pos < w * h * 3:
+        raise ValueError(f"{path}: {len(data) - pos} bytes of pixels, {w * h * 3} expected")
+    return np.frombuffer(data, np.uint8, w * h * 3, pos).reshape(h, w, 3).copy()
+
+
+def read_png(path):
+    """An 8-bit RGB or RGBA PNG without interlacing (alpha dropped) -> uint8 [H][W][3]; all five filter types."""
+    with open(path, "rb") as f:
+        data = f.read()
+    if data[:8] != b"\x89PNG\r\n\x1a\n":
+        raise ValueError(f"{path}: not a PNG file")
+    pos, head, idat = 8, None, []
+    while pos + 8 <= len(data):
+        (length,), tag = struct.unpack(">I", data[pos:pos + 4]), data[pos + 4:pos + 8]
+        body = data[pos + 8:pos + 8 + length]
+        if len(body) != length or pos + 12 + length > len(data):
+            raise ValueError(f"{path}: truncated chunk {tag!r}")
+        if struct.unpack(">I", data[pos + 8 + length:pos + 12 + length])[0] != (zlib.crc32(tag + body) & 0xFFFFFFFF):
+            raise ValueError(f"{path}: chunk {tag!r} fails its CRC")
+        if tag == b"IHDR":
+            head = struct.unpack(">IIBBBBB", body)
+        elif tag == b"IDAT":
+            idat.append(body)
+        elif tag == b"IEND":
+            break
+        pos += 12 + length
+    if head is None:
+        raise ValueError(f"{path}: no IHDR chunk")
+    w, h, depth, colour, compression, filtering, interlace = head
+    if depth != 8 or colour not in (2, 6) or compression != 0 or filtering != 0 or interlace != 0 or w == 0 or h == 0:
+        raise ValueError(f"{path}: 8-bit RGB / RGBA PNGs without interlacing are read (bit depth {depth}, colour type {colour}, interlace {interlace})")
+    bpp = 3 if colour == 2 else 4
+    stride = w * bpp
+    raw = zlib.decompress(b"".join(idat))
+    if len(raw) != h * (stride + 1):
+        raise ValueError(f"{path}: {len(raw)} bytes of scanlines, {h * (stride + 1)} expected")
+    out = np.zeros((h, stride), np.uint8)
+    prev = np.zeros(stride, np.int64)
+    for y in range(h):
+        kind = raw[y * (stride + 1)]
+        line = np.frombuffer(raw, np.uint8, stride, y * (stride + 1) + 1).astype(np.int64)
+        if kind == 0:
+            cur = line
+        elif kind == 2:   # Up
+            cur = (line + prev) & 255
+        elif kind in (1, 3, 4):   # Sub, Average, Paeth: each byte needs the reconstructed byte bpp to its left
+            cur = np.zeros(stride, np.int64)
+            for x in range(stride):
+                a = cur[x - bpp] if x >= bpp else 0
+                b = prev[x]
+                if kind == 1:
+                    pred = a
+                elif kind == 3:
+                    pred = (a + b) >> 1
+                else:
+                    c = prev[x - bpp] if x >= bpp else 0
+                    pa, pb, pc = abs(b - c), abs(a - c), abs(a + b - 2 * c)
+                    pred = a if pa <= pb and pa <= pc else (b if pb <= pc else c)
+                cur[x] = (line[x] + pred) & 255
+        else:
+            raise ValueError(f"{path}: row {y}: unknown filter type {kind}")
+        out[y] = cur
+        prev = cur
+    return np.ascontiguousarray(out.reshape(h, w, bpp)[:, :, :3])
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -1,8 +1,9 @@
 """Triangle meshes for Scene.MakeMesh: a Wavefront OBJ reader and two generators, so that demos, tests and measurements need no file.
 
 Every function returns (vertices float32 (n, 3), faces uint32 (m, 3)) but the ones that say otherwise.  load_obj ignores a file's normals; load_obj_normals
-reads them, vertex_normals makes area-weighted ones for a mesh without, icosphere_normals gives the sphere's own (smooth shading).  Texture
-coordinates of a file are ignored: a triangle takes them from its own plane.
+reads them, vertex_normals makes area-weighted ones for a mesh without, icosphere_normals gives the sphere's own (smooth shading).  load_obj_uvs
+reads a file's texture coordinates, uv_sphere makes a sphere with the ones an image-textured sphere has; without any a triangle takes them from
+its own plane.
 """
 import numpy as np
 
@@ -92,6 +93,85 @@ def load_obj_normals(path):
     if not normals or not complete:
         return v, fa, None, None
     return v, fa, np.array(normals, np.float32).reshape(-1, 3), np.array(normal_faces, np.uint32).reshape(-1, 3)
+
+
+def _obj_second(token, n_uvs, where):
+    """the texture-coordinate index of an `i/j` or `i/j/k` token (1-based, negative = counted back from the `vt` lines read so far), or None for a token without one"""
+    parts = token.split("/")
+    if len(parts) < 2 or parts[1] == "":
+        return None
+    try:
+        i = int(parts[1])
+    except ValueError:
+        raise ValueError(f"{where}: bad texture coordinate index {token!r}") from None
+    k = i - 1 if i > 0 else n_uvs + i
+    if i == 0 or not 0 <= k < n_uvs:
+        raise ValueError(f"{where}: texture coordinate index {token!r} out of range ({n_uvs} texture coordinates so far)")
+    return k
+
+
+def load_obj_uvs(path):
+    """load_obj that keeps the texture coordinates: (vertices, faces, uvs float32 (k, 2) | None, uv_faces uint32 (m, 3) | None) from the `v`, `vt` and `f` lines;
+    the second index of an `i/j` or `i/j/k` corner names its `vt` (negative indices and fans as for vertices; a third coordinate of a `vt` line is dropped).
+    A file without `vt` lines, or one face corner without a second index, gives None, None: the mesh has no complete set of texture coordinates."""
+    vertices, faces, uvs, uv_faces = [], [], [], []
+    complete = True
+    with open(path, "r", encoding="utf-8", errors="replace") as f:
+        for lineno, line in enumerate(f, 1):
+            parts = line.split("#", 1)[0].split()
+            if not parts:
+                continue
+            where = f"{path}:{lineno}"
+            if parts[0] == "v":
+                if len(parts) < 4:
+                    raise ValueError(f"{where}: a vertex needs three coordinates")
+                vertices.append([float(parts[1]), float(parts[2]), float(parts[3])])
+            elif parts[0] == "vt":
+                if len(parts) < 3:
+                    raise ValueError(f"{where}: a texture coordinate needs two values")
+                uvs.append([float(parts[1]), float(parts[2])])
+            elif parts[0] == "f":
+                if len(parts) < 4:
+                    raise ValueError(f"{where}: a face needs at least three corners")
+                corners = [_obj_index(t, len(vertices), where) for t in parts[1:]]
+                seconds = [_obj_second(t, len(uvs), where) for t in parts[1:]]
+                if any(k is None for k in seconds):
+                    complete = False
+                for k in range(1, len(corners) - 1):
+                    faces.append([corners[0], corners[k], corners[k + 1]])
+                    if complete:
+                        uv_faces.append([seconds[0], seconds[k], seconds[k + 1]])
+    v, fa = np.array(vertices, np.float32).reshape(-1, 3), np.array(faces, np.uint32).reshape(-1, 3)
+    if not uvs or not complete:
+        return v, fa, None, None
+    return v, fa, np.array(uvs, np.float32).reshape(-1, 2), np.array(uv_faces, np.uint32).reshape(-1, 3)
+
+
+def uv_sphere(n_lon, n_lat):
+    """a latitude-longitude unit sphere: (vertices (n, 3), faces (m, 3), normals (n, 3), uvs (n, 2)), n = (n_lat + 1) (n_lon + 1), m = 2 n_lon (n_lat - 1).
+    Vertex (j, i) has u = i / n_lon, v = j / n_lat and stands where an image-textured sphere has that (u, v) (sphere::get_sphere_uv: theta = pi v from -y,
+    phi = 2 pi u): (-cos(phi) sin(theta), -cos(theta), sin(phi) sin(theta)).  The seam column i = n_lon repeats i = 0 with u = 1, and each pole is one vertex per
+    column, so every coordinate lies in [0, 1] and no face spans the seam.  The normals are the positions; faces are counter-clockwise seen from outside."""
+    if n_lon < 3 or n_lat < 2:
+        raise ValueError("uv_sphere: at least 3 columns and 2 rows")
+    u = np.arange(n_lon + 1, dtype=np.float64) / n_lon
+    v = np.arange(n_lat + 1, dtype=np.float64) / n_lat
+    theta, phi = np.pi * v[:, None], 2.0 * np.pi * u[None, :]
+    pos = np.stack([-np.cos(phi) * np.sin(theta), -np.cos(theta) * np.ones_like(phi), np.sin(phi) * np.sin(theta)], axis=-1).reshape(-1, 3)
+    uv = np.stack(np.broadcast_arrays(u[None, :], v[:, None]), axis=-1).reshape(-1, 2)
+    at = lambda j, i: j * (n_lon + 1) + i
+    faces = []
+    for j in range(n_lat):
+        for i in range(n_lon):
+            if j > 0:               # not at the south pole, where (j, i) and (j, i + 1) coincide
+                faces.append([at(j, i), at(j + 1, i + 1), at(j, i + 1)])
+            if j < n_lat - 1:       # not at the north pole
+                faces.append([at(j, i), at(j + 1, i), at(j + 1, i + 1)])
+    f = np.array(faces, np.int64)
+    outward = (np.cross(pos[f[:, 1]] - pos[f[:, 0]], pos[f[:, 2]] - pos[f[:, 0]]) * pos[f].mean(axis=1)).sum(axis=1)
+    f[outward < 0] = f[outward < 0][:, [0, 2, 1]]
+    nrm = pos / np.linalg.norm(pos, axis=1)[:, None]
+    return pos.astype(np.float32), f.astype(np.uint32), nrm.astype(np.float32), uv.astype(np.float32)
 
 
 def vertex_normals(vertices, faces):

@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
 """Differential fuzz campaign: random worlds (spheres, moving spheres, quads, triangles and meshes, lights, media, textures; every builder; LDS
 and global-memory paths; three cameras) rendered on the GPU and by the CPU oracle, compared bit for bit.
-    python tools/fuzz_campaign.py --seeds 200 [--first 0] [--no-triangles] [--mesh-lights] [--light-tree]
+    python tools/fuzz_campaign.py --seeds 200 [--first 0] [--no-triangles] [--mesh-lights] [--light-tree] [--texture-coords]
 Prints one line per failure and a summary; exit code 1 if anything differed.  The triangles of a world come from a generator of their own, so the rest of a seed's
 world is what it was before the fuzzer made triangles, and --no-triangles renders exactly those earlier worlds.  Importing this file starts nothing:
 world_of_seed() builds a seed's world on the host, without a device.  --mesh-lights (off by default: the recorded campaigns ran without it) also renders every
-world that RT_LIGHT_SAMPLING_MESH accepts in that mode; it draws nothing, so the worlds, frames and cameras of a seed stay what they are."""
+world that RT_LIGHT_SAMPLING_MESH accepts in that mode; it draws nothing, so the worlds, frames and cameras of a seed stay what they are.  --texture-coords
+ gives random triangles of every world with an image and triangles random texture coordinates from [-0.5, 1.5) — wider than the unit square —,
+drawn from the seed's generator AFTER every other draw of the case, so committed seeds give the worlds, frames and cameras they gave."""
 import argparse, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -32,6 +34,7 @@ def parse_args(argv=None):
     ap.add_argument("--no-triangles", action="store_true", help="the worlds as they were before the fuzzer made triangles, byte for byte")
     ap.add_argument("--light-tree", action="store_true", help="also render the worlds that light-sampling mode 16 (the light tree, chosen by area) accepts in that mode: both memory forms, and the twin (tests/_light_tree_twin.py) where it follows")
     ap.add_argument("--mesh-lights", action="store_true", help="also render the worlds that light-sampling mode 4 (triangle and mesh lights) accepts in that mode: both memory forms, and the twin where it follows")
+    ap.add_argument("--texture-coords", action="store_true", help="also render the worlds with an image and triangles under a table of random texture coordinates on random triangles: both memory forms must agree, and the identity table must be the oracle's frame")
     return ap.parse_args(argv)
 
 
@@ -143,6 +146,43 @@ def light_sampling_check(p, s, w, cam, ck, W, H, depth, variant, mode=1):
     return ok, forms
 
 
+def texture_coords_check(p, s, w, cam, W, H, spp, depth, variant, rng, ref):
+    """A world with an image and triangles on a stack-walk or list kernel: (1) under the identity table the frame is `ref`, the oracle's; (2) under a table of
+    random coordinates on a random half of the triangles the renderer's own form and the global-memory form agree in every bit, and the table shows wherever an
+    image-textured triangle was given coordinates and is seen.  The oracle does not know the rule (tests/test_gpu_texture_coords.py holds it absolutely).
+    None: not applicable; else (ok, forms, mapped image-textured triangles)."""
+    n = s.n_triangles()
+    if not n or not w.image_width:
+        return None
+    table = np.tile(np.float32([0, 0, 1, 0, 0, 1]), (n, 1))
+    chosen = rng.random(n) < 0.5                                                   # drawn after every other draw of the case
+    table[chosen] = (rng.random((int(chosen.sum()), 6)) * 2.0 - 0.5).astype(np.float32)
+    frames, forms = [], []
+    for env in ({}, {"RT06_FORCE_BIG": "1"}):
+        os.environ.pop("RT06_FORCE_BIG", None)
+        os.environ.update(env)
+        try:
+            r = p.Renderer.MakeRenderer(W, H, spp, depth, cam, w, variant=variant)
+            r.texture_coords(np.tile(np.float32([0, 0, 1, 0, 0, 1]), (n, 1)))
+        except p.capi.RtError:
+            return None   # no kernel for the world, or one that reads no table (queue / wide4 walks)
+        finally:
+            os.environ.pop("RT06_FORCE_BIG", None)
+        forms.append(r.kernel_form())
+        r.Render()
+        identity = r.DownloadRenderbuffer()
+        r.texture_coords(table)
+        r.Render()
+        frames.append(r.DownloadRenderbuffer())
+        r.close()
+        if not bits_equal(identity, ref):
+            return False, forms, 0
+    quads, mats = s.quads(), s.arrays()[2]
+    tris = quads[quads["kind"] == 1]
+    mapped = int((chosen & (mats["type"][tris["mat"]] == 7)).sum())   # RT_MAT_LAMBERTIAN_IMAGE
+    return bits_equal(frames[0], frames[1]), forms, mapped
+
+
 def main(argv=None):
     args = parse_args(argv)
     p = G.load_package()
@@ -235,6 +275,14 @@ def main(argv=None):
                 if not ls[0]:
                     fails += 1
                     print(f"FAIL seed {seed} with light sampling mode 16: kinds {kinds} triangles {s.n_triangles()} builder {builder} big {big} cam {ck} depth {depth} forms {ls[1]}", flush=True)
+        if args.texture_coords and ok and info["variant"] in (2, 3) and not (big and builder == 3):
+            tc = texture_coords_check(p, s, w, cam, W, H, spp, depth, variant, rng, ref)
+            if tc is not None:
+                stats["texture_coords"] = stats.get("texture_coords", 0) + 1
+                stats["texture_coords_mapped_image_triangles"] = stats.get("texture_coords_mapped_image_triangles", 0) + tc[2]
+                if not tc[0]:
+                    fails += 1
+                    print(f"FAIL seed {seed} with texture coordinates: kinds {kinds} triangles {s.n_triangles()} builder {builder} big {big} cam {ck} depth {depth} forms {tc[1]}", flush=True)
         if (seed - args.first) % 25 == 24:
             print(f"... {seed - args.first + 1} worlds, {fails} failures, {time.time() - t0:.0f}s, paths {stats}", flush=True)
     print(f"DONE: {args.seeds} worlds, {fails} failures, paths {stats}, {time.time() - t0:.0f}s")

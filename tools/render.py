@@ -66,6 +66,8 @@ ap.add_argument("--mesh-translate", default="0,0,0", metavar="X,Y,Z")
 ap.add_argument("--mesh-material", default="white", choices=["white", "red", "metal", "glass", "checker", "light"])
 ap.add_argument("--smooth", action="store_true", help="with --mesh: smooth shading from per-vertex normals (DESIGN.md §21) — an OBJ file's own `vn` normals if it has a complete "
                     "set, an icosphere's unit positions, else area-weighted ones (mesh_io.vertex_normals)")
+ap.add_argument("--texture", default=None, metavar="FILE.ppm|FILE.png", help="with --mesh FILE.obj: the mesh's material is this image over the file's `vt` texture "
+                    "coordinates (DESIGN.md §22; binary PPM or 8-bit RGB / RGBA PNG); refused when the OBJ has no complete set of them")
 ap.add_argument("--out", default="render.png")
 a = ap.parse_args()
 light_mode = {"quads": 1, "all": 2, "mesh": 4, "tree": 16}.get(a.light_sampling_mode, 1 if a.light_sampling else 0)   # RT_LIGHT_SAMPLING_*
@@ -86,6 +88,8 @@ elif a.scene == "book1_final":
     scene, cam = p.Scene.book1_final(a.seed), p.DefocusBlurCamera((13, 2, 3), (0, 0, 0), (0, 1, 0), 20.0, W / H, 0.1, 10.0)
 else:
     scene, cam = p.Scene.book2_moving(a.seed), p.MotionBlurCamera((13, 2, 3), (0, 0, 0), (0, 1, 0), 20.0, W / H, 0.0, 1.0)
+if a.texture and not a.mesh:
+    sys.exit("--texture needs --mesh FILE.obj")
 if a.mesh:
     from ray_tracing_v06_amd import mesh_io
     vertices, faces = mesh_io.from_spec(a.mesh)
@@ -97,10 +101,22 @@ if a.mesh:
             _, _, normals, normal_faces = mesh_io.load_obj_normals(a.mesh)
         if normals is None:
             normals = mesh_io.vertex_normals(vertices, faces)
+    uvs = uv_faces = None
+    if a.texture:
+        from ray_tracing_v06_amd import image_io
+        if a.mesh.startswith("icosphere:") or a.mesh == "tetrahedron":
+            sys.exit(f"--texture: {a.mesh} has no texture coordinates; give an OBJ file with `vt` lines")
+        _, _, uvs, uv_faces = mesh_io.load_obj_uvs(a.mesh)
+        if uvs is None:
+            sys.exit(f"--texture: {a.mesh} has no complete set of texture coordinates (`vt` lines and a second index at every face corner)")
+        if a.scene == "book2_final":
+            sys.exit("--texture: book2_final has an image of its own, and a world holds one")
+        scene.set_image((image_io.read_png if a.texture.lower().endswith(".png") else image_io.read_ppm)(a.texture))
     mat = {"white": lambda: scene.Lambertian((0.73, 0.73, 0.73)), "red": lambda: scene.Lambertian((0.65, 0.05, 0.05)), "metal": lambda: scene.Metal((0.8, 0.85, 0.88), 0.0),
            "glass": lambda: scene.Dielectric((1, 1, 1), 1.5), "checker": lambda: scene.LambertianTexture((0.2, 0.3, 0.1), (0.9, 0.9, 0.9), abs(a.mesh_scale) / 4 if a.mesh_scale else 1.0),   # four squares across a unit mesh
-           "light": lambda: scene.DiffuseLight((4, 4, 4))}[a.mesh_material]()
-    first, added = scene.MakeMesh(vertices, faces, mat, a.mesh_scale, a.mesh_rotate_y, [float(x) for x in a.mesh_translate.split(",")], normals=normals, normal_faces=normal_faces)
+           "light": lambda: scene.DiffuseLight((4, 4, 4))}[a.mesh_material]() if not a.texture else scene.ImageTexture()
+    first, added = scene.MakeMesh(vertices, faces, mat, a.mesh_scale, a.mesh_rotate_y, [float(x) for x in a.mesh_translate.split(",")], normals=normals, normal_faces=normal_faces,
+                                  uvs=uvs, uv_faces=uv_faces)
     if a.scene == "three_spheres":
         scene.MakeHittableList()   # the prefab's own world kind
     else:
