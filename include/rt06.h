@@ -133,7 +133,7 @@ typedef struct rt_world_flat {
     /* extension (see rt_quad): a primitive index i >= n_prims means quad i - n_prims; the triangles are the last of the quads */
     const rt_quad*     quads;
     uint32_t n_quads;
-    uint32_t background;         /* 0: the reference's sky gradient (Renderer.cu:150-151); 1: background_color */
+    uint32_t background;         /* 0: the reference's sky gradient (Renderer.cu:150-151); 1: background_color; 2: the renderer's environment map (rt_renderer_environment) */
     float    background_color[3];
     uint32_t image_width;        /* RT_MAT_LAMBERTIAN_IMAGE: one RGB8 image per world, row 0 = top (as stb_image loads it) */
     const rt_perlin* perlin;     /* RT_MAT_LAMBERTIAN_NOISE: the world's noise tables, or NULL                            */
@@ -276,6 +276,25 @@ int rt_scene_texture_coords(const rt_scene* s, const rt_tri_uvs** out, uint32_t*
 int rt_tri_uv_batch(size_t n, const rt_quad* tris, const rt_tri_uvs* uv, const float* rays, const float* t, float* out_uv);
 /* camera::background of "The Next Week": mode 0 = the reference's sky gradient, 1 = constant colour       */
 int rt_scene_set_background(rt_scene* s, uint32_t mode, const float color[3]);
+/* ---- environment maps (not in the reference): a width x height image of fp32 RGB radiance, row 0 at the top, values finite and >= 0 (they may be
+ * far above 1), plus a rotation about y, u0 in [0, 1).  At a miss (no hit), with d = the ray's direction:
+ *   n     = normalize(d)                                   (the normalize of the sky gradient)
+ *   cy    = clamp(-n.y, -1, 1);  theta = acos cy;  phi = atan2 (-n.z, n.x) + pi_f        (the library's own rt_acosf and rt_atan2f, shared with the CPU oracle)
+ *   u     = phi / two_pi_f + u0;  if (u >= 1) u = u - 1;   v = theta / pi_f                  (the constants of the image texture's sphere map)
+ *   texel : clamp u, v to [0, 1] as !(x > 0) ? 0 : (x > 1 ? 1 : x) (a NaN lands on 0); v = 1 - v; i = (int)(u * W), j = (int)(v * H), capped at W - 1, H - 1
+ *   sky   = that texel's (r, g, b) as stored;   rad = atten * sky + accum_rad                (as for the constant background)
+ * Only fp32 + - * / sqrt, comparisons and those two functions, each rounded on its own, no FMA.  With u0 = 0 a direction sees the texel that an image-textured
+ * sphere around the viewer shows at normal n.  A miss at the last allowed bounce collects the map as it collects the constant background.  The map is NOT sampled
+ * as a light: the light-sampling modes never put it in their tables.  Nearest texel, one map, rotation about y only.
+ * rt_scene_set_environment copies the image (3 floats per texel), sets background mode 2 and stores u0 = frac(rotate_y_degrees / 360).  RT_ERR_INVALID, scene
+ * unchanged: a texel that is not finite or is negative, a zero dimension, width * height > 2^25, a rotation that is not finite.                                  */
+#define RT_ENV_MAX_TEXELS (1u << 25)
+int rt_scene_set_environment(rt_scene* s, uint32_t width, uint32_t height, const float* rgb, float rotate_y_degrees);
+/* What rt_scene_set_environment stored (*out_w = *out_h = 0, *out_rgb = NULL when the scene has none; rt_scene_set_background drops it).  The pointer stays valid
+ * until the scene's environment or background is set again or the scene is destroyed.                                                                            */
+int rt_scene_environment(const rt_scene* s, uint32_t* out_w, uint32_t* out_h, const float** out_rgb, float* out_u0);
+/* HOST (no GPU): the rule above on n directions dirs[3 i ..] -> out_rgb[3 i ..], out_texel[i] = j * width + i.  The function the kernels call.                   */
+int rt_environment_batch(size_t n, uint32_t width, uint32_t height, const float* rgb, float u0, const float* dirs, float* out_rgb, uint32_t* out_texel);
 /* selects RT_TRAVERSAL_STACK / RT_TRAVERSAL_QUEUE / RT_TRAVERSAL_WIDE4 for the BVH world of this scene (see the enum) */
 int rt_scene_set_traversal(rt_scene* s, uint32_t mode);
 /* perlin::perlin() of "The Next Week": 256 random unit vectors + three Fisher-Yates permutations, drawn from the
@@ -649,6 +668,14 @@ int rt_renderer_shading_normals_info(rt_renderer* r, uint32_t out[2]);
 int rt_renderer_texture_coords(rt_renderer* r, const rt_tri_uvs* table, uint32_t n);
 /* out[0] = 1 while a table is on, out[1] = how many of its records are not the identity */
 int rt_renderer_texture_coords_info(rt_renderer* r, uint32_t out[2]);
+/* The environment map (see rt_scene_set_environment) of a renderer whose world has background mode 2: width x height texels of 3 floats, u0 in [0, 1); or
+ * NULL, 0, 0 to turn it off.  Validated as rt_scene_set_environment validates; copied into a device buffer of the renderer's own, one 16-byte record per texel (the
+ * images the kernels launch on carry two vec4 that point to it).  Takes effect at the next launch; an unchanged map is a no-op that keeps the refinement, a change
+ * discards the refinement and feature-buffer state.  RT_ERR_INVALID with a message of its own: a world whose background is not 2, a bad image, a bad u0.
+ * While a background-2 renderer has no map, rt_renderer_render, the refine calls and their async forms return RT_ERR_INVALID and launch nothing.                */
+int rt_renderer_environment(rt_renderer* r, uint32_t width, uint32_t height, const float* rgb, float u0);
+/* out[0] = 1 while a map is on, out[1] = width, out[2] = height, out[3] = the bits of u0 */
+int rt_renderer_environment_info(rt_renderer* r, uint32_t out[4]);
 
 /* ------------------------------------------------------------------ */
 /* Multi-GPU renderer — the same three entry points (Renderer.h:38-46)  */
@@ -678,6 +705,8 @@ int rt_multi_renderer_light_sampling_enable(rt_multi_renderer* m, uint32_t on);
 int rt_multi_renderer_shading_normals(rt_multi_renderer* m, const rt_tri_normals* table, uint32_t n);
 /* rt_renderer_texture_coords on every rank (refused before any rank changes).                                             */
 int rt_multi_renderer_texture_coords(rt_multi_renderer* m, const rt_tri_uvs* table, uint32_t n);
+/* rt_renderer_environment on every rank (refused before any rank changes).                                                */
+int rt_multi_renderer_environment(rt_multi_renderer* m, uint32_t width, uint32_t height, const float* rgb, float u0);
 /* Renderer::DownloadRenderbuffer: width*height*4 floats from devices[0].                                                */
 int rt_multi_renderer_download(rt_multi_renderer* m, float* host_rgba, size_t n_floats);
 /* ms of the last render: out[0] host wall-clock of Render(), out[1] slowest rank's kernels (HIP events),
@@ -714,6 +743,8 @@ int rt_probe_shading_normal(int device, const rt_world_flat* world, const rt_tri
  * rt_world_triangles of the world, or NULL, 0 = no table: the planar coordinates on a triangle too) -> hit n, uv n*2: (tu, tv) before the clamp on a triangle,
  * the planar (alpha, beta) on a parallelogram, 0 on a sphere or a miss                                                                                        */
 int rt_probe_tri_uv(int device, const rt_world_flat* world, const rt_tri_uvs* table, uint32_t n_table, size_t n, const float* rays, int32_t* out_hit, float* out_uv);
+/* rt_environment_batch on the device, one lane per direction: the map as the renderer holds it (one 16-byte record per texel)                                  */
+int rt_probe_environment(int device, size_t n, uint32_t width, uint32_t height, const float* rgb, float u0, const float* dirs, float* out_rgb, uint32_t* out_texel);
 /* SphereHittable / MovingSphereHittable::ClosestIntersection (SphereHittable.cu:56-66, :91-102): sphere
  * prims[i] (material ignored, RT_PRIM_MOVING kept) against ray i (o,d,time) with rec.distance preset[i]
  * -> hit n, rec.distance n, normal n*3 (0 when not hit)                      */

@@ -350,6 +350,11 @@ public:
         float c[3] = {b.color[0], b.color[1], b.color[2]};
         check(rt_scene_set_background(s_, b.constant ? 1u : 0u, c), "rt_scene_set_background");
     }
+    // an environment map in the place of the background (extension; rt_scene_set_environment): width x height texels of 3 floats, row 0 at the top,
+    // turned about y by rotate_y_degrees; Renderer::MakeRenderer pushes it to the renderer it makes of a BVH world of this scene
+    void SetEnvironment(uint32_t width, uint32_t height, const float* rgb, float rotate_y_degrees = 0.0f) {
+        check(rt_scene_set_environment(s_, width, height, rgb, rotate_y_degrees), "rt_scene_set_environment");
+    }
     // child reference of a bvh_node tree: >= 0 node, < 0 primitive
     int32_t tree_ref(const Hittable* h) {
         if (h->kind() == Hittable::NODE) {
@@ -591,6 +596,11 @@ class Renderer {
             uint32_t n_uv = 0;
             rt06::check(rt_scene_texture_coords(static_cast<const BVH*>(world)->scene, &uv, &n_uv), "rt_scene_texture_coords");
             if (n_uv) made.SetTextureCoords(uv, n_uv);
+            uint32_t env_w = 0, env_h = 0;                 // ... and one lit by an environment map its map
+            const float* env = nullptr;
+            float u0 = 0.0f;
+            rt06::check(rt_scene_environment(static_cast<const BVH*>(world)->scene, &env_w, &env_h, &env, &u0), "rt_scene_environment");
+            if (env) made.SetEnvironment(env_w, env_h, env, u0);
         }
         return made;
     }
@@ -682,6 +692,12 @@ public:
     void SetTextureCoords(const rt_tri_uvs* table, uint32_t n) {
         if (m.mr) rt06::check(rt_multi_renderer_texture_coords(m.mr, table, n), "Renderer::SetTextureCoords");
         else rt06::check(rt_renderer_texture_coords(m.r, table, n), "Renderer::SetTextureCoords");
+    }
+    // The environment map of a background-2 world (extension; rt_renderer_environment): width x height texels of 3 floats and the rotation u0 in [0, 1), or
+    // (0, 0, nullptr) for off — Render() then refuses; restarts a refinement
+    void SetEnvironment(uint32_t width, uint32_t height, const float* rgb, float u0 = 0.0f) {
+        if (m.mr) rt06::check(rt_multi_renderer_environment(m.mr, width, height, rgb, u0), "Renderer::SetEnvironment");
+        else rt06::check(rt_renderer_environment(m.r, width, height, rgb, u0), "Renderer::SetEnvironment");
     }
     void SetLightSampling(bool on) {
         if (m.mr) rt06::check(rt_multi_renderer_light_sampling_enable(m.mr, on ? 1u : 0u), "Renderer::SetLightSampling");

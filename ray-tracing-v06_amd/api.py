@@ -242,6 +242,23 @@ class Scene:
         check(lib().rt_world_triangles(C.byref(w), C.byref(n)))
         return n.value
 
+    def set_environment(self, image, rotate_y=0.0):
+        """An environment map (extension): image (H, W, 3) float, fp32 RGB radiance, row 0 at the top, finite and >= 0; rotate_y in degrees about y.
+        Sets background mode 2; Renderer / MultiRenderer push the map at creation."""
+        img = np.ascontiguousarray(image, dtype=np.float32)
+        if img.ndim != 3 or img.shape[2] != 3:
+            raise ValueError("set_environment: the image must have shape (H, W, 3)")
+        check(lib().rt_scene_set_environment(self.h, img.shape[1], img.shape[0], img.ctypes.data, float(rotate_y)))
+
+    def environment(self):
+        """What set_environment stored: ((H, W, 3) float32 copy, u0), or None when the scene has no environment map (rt_scene_environment)."""
+        w, h, ptr, u0 = C.c_uint32(), C.c_uint32(), C.c_void_p(), C.c_float()
+        check(lib().rt_scene_environment(self.h, C.byref(w), C.byref(h), C.byref(ptr), C.byref(u0)))
+        if not ptr.value:
+            return None
+        buf = (C.c_float * (w.value * h.value * 3)).from_address(ptr.value)
+        return np.frombuffer(buf, np.float32).reshape(h.value, w.value, 3).copy(), np.float32(u0.value)
+
     def set_background(self, color=None):
         """None: the reference's sky gradient; a colour: camera::background of "The Next Week"."""
         if color is None:
@@ -312,6 +329,8 @@ class Scene:
             w.vertex_normals = self.vertex_normals()
         if getattr(self, "_uv", False):       # likewise the texture coordinates (a scene that was given none: no call)
             w.texture_coords = self.texture_coords()
+        if w.background == 2:                 # likewise the environment map
+            w.environment = self.environment()
         return w
 
     def _arr(self, ptr, n, dt):
@@ -410,6 +429,20 @@ def _push_uvs(fn, handle, table):
     return fn(handle, t.ctypes.data if len(t) else None, len(t))
 
 
+def _env_image(image):
+    img = np.ascontiguousarray(image, dtype=np.float32)
+    if img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError("environment: the image must have shape (H, W, 3)")
+    return img
+
+
+def _push_environment(fn, handle, image, u0):
+    if image is None:
+        return fn(handle, 0, 0, None, 0.0)
+    img = _env_image(image)
+    return fn(handle, img.shape[1], img.shape[0], img.ctypes.data, float(u0))
+
+
 class Renderer:
     """Renderer (main/src/Renderer.h:12-47) over the C ABI."""
 
@@ -428,6 +461,8 @@ class Renderer:
             r.shading_normals(world.vertex_normals)
         if len(getattr(world, "texture_coords", ())):
             r.texture_coords(world.texture_coords)
+        if getattr(world, "environment", None) is not None:
+            r.environment(world.environment[0], u0=world.environment[1])
         return r
 
     def Render(self):
@@ -555,6 +590,17 @@ class Renderer:
         check(lib().rt_renderer_texture_coords_info(self.h, out))
         return {"enabled": bool(out[0]), "mapped": out[1]}
 
+    def environment(self, image, u0=0.0):
+        """The environment map of a background-2 world from the next launch on (rt_renderer_environment): image (H, W, 3) float, u0 in [0, 1) the
+        rotation about y as a shift of u; None = off (Render() then refuses).  A change restarts the refinement."""
+        check(_push_environment(lib().rt_renderer_environment, self.h, image, u0))
+
+    def environment_info(self):
+        """{'enabled', 'width', 'height', 'u0'} of the renderer's environment map."""
+        out = (C.c_uint32 * 4)()
+        check(lib().rt_renderer_environment_info(self.h, out))
+        return {"enabled": bool(out[0]), "width": out[1], "height": out[2], "u0": np.array([out[3]], np.uint32).view(np.float32)[0]}
+
     def last_kernel_ms(self):
         ms = C.c_float()
         check(lib().rt_renderer_last_kernel_ms(self.h, C.byref(ms)))
@@ -648,6 +694,8 @@ class MultiRenderer:
             m.shading_normals(world.vertex_normals)
         if len(getattr(world, "texture_coords", ())):
             m.texture_coords(world.texture_coords)
+        if getattr(world, "environment", None) is not None:
+            m.environment(world.environment[0], u0=world.environment[1])
         return m
 
     def Render(self):
@@ -672,6 +720,10 @@ class MultiRenderer:
     def texture_coords(self, table):
         """rt_renderer_texture_coords on every rank; `table` as Renderer.texture_coords takes it."""
         check(_push_uvs(lib().rt_multi_renderer_texture_coords, self.h, table))
+
+    def environment(self, image, u0=0.0):
+        """rt_renderer_environment on every rank; arguments as Renderer.environment takes them."""
+        check(_push_environment(lib().rt_multi_renderer_environment, self.h, image, u0))
 
     def DownloadRenderbuffer(self):
         out = np.zeros((self.cfg.height, self.cfg.width, 4), dtype=np.float32)
@@ -935,3 +987,23 @@ def probe_tri_uv(world, table, rays, device=0):
     hit, uv = np.zeros(n, np.int32), np.zeros((n, 2), np.float32)
     check(lib().rt_probe_tri_uv(device, C.byref(world), tab.ctypes.data if len(tab) else None, len(tab), n, rays, hit, uv))
     return hit, uv
+
+
+def environment_batch(image, u0, dirs):
+    """rt_environment_batch (host only): the environment rule on directions (n, 3) -> (rgb (n, 3) float32, texel (n,) uint32 = j * W + i)"""
+    img = _env_image(image)
+    dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+    n = len(dirs)
+    rgb, texel = np.zeros((n, 3), np.float32), np.zeros(n, np.uint32)
+    check(lib().rt_environment_batch(n, img.shape[1], img.shape[0], img.ctypes.data, float(u0), dirs, rgb, texel))
+    return rgb, texel
+
+
+def probe_environment(image, u0, dirs, device=0):
+    """rt_probe_environment: environment_batch on the device, one lane per direction"""
+    img = _env_image(image)
+    dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+    n = len(dirs)
+    rgb, texel = np.zeros((n, 3), np.float32), np.zeros(n, np.uint32)
+    check(lib().rt_probe_environment(device, n, img.shape[1], img.shape[0], img.ctypes.data, float(u0), dirs, rgb, texel))
+    return rgb, texel

@@ -94,6 +94,8 @@ SYMBOLS = [
     "rt_renderer_run_ahead_info",
     "rt_scene_add_triangle_uv", "rt_scene_add_mesh_uv", "rt_scene_texture_coords", "rt_tri_uv_batch", "rt_renderer_texture_coords",
     "rt_renderer_texture_coords_info", "rt_multi_renderer_texture_coords", "rt_probe_tri_uv",
+    "rt_scene_set_environment", "rt_scene_environment", "rt_environment_batch", "rt_renderer_environment", "rt_renderer_environment_info",
+    "rt_multi_renderer_environment", "rt_probe_environment",
 ]
 
 _lib = None
@@ -195,6 +197,13 @@ def lib():
     L.rt_renderer_texture_coords_info.argtypes = [C.c_void_p, C.c_uint32 * 2]
     L.rt_multi_renderer_texture_coords.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     L.rt_probe_tri_uv.argtypes = [C.c_int, P(WorldFlat), C.c_void_p, C.c_uint32, C.c_size_t, f32p, i32p, f32p]
+    L.rt_scene_set_environment.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_float]
+    L.rt_scene_environment.argtypes = [C.c_void_p, P(C.c_uint32), P(C.c_uint32), P(C.c_void_p), P(C.c_float)]
+    L.rt_environment_batch.argtypes = [C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_float, f32p, f32p, u32p]
+    L.rt_renderer_environment.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_float]
+    L.rt_renderer_environment_info.argtypes = [C.c_void_p, C.c_uint32 * 4]
+    L.rt_multi_renderer_environment.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_float]
+    L.rt_probe_environment.argtypes = [C.c_int, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_float, f32p, f32p, u32p]
     L.rt_scene_set_background.argtypes = [C.c_void_p, C.c_uint32, vec3]
     L.rt_scene_set_perlin.argtypes = [C.c_void_p, C.c_uint64]
     L.rt_scene_set_image.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]

@@ -227,17 +227,28 @@ struct rt_renderer {
     struct { bool on = false; uint32_t n_smooth = 0; std::vector<float> host; DevBuf table; } vn;
     // texture coordinates (rt_renderer_texture_coords): the table as given (6 floats per triangle of the world); it rides in the same tail
     struct { bool on = false; uint32_t n_mapped = 0; std::vector<float> host; } uv;
-    // the images with a tail, held while either table is on: the plain image's and each built light-sampling mode's
+    // the environment map (rt_renderer_environment) of a background-2 world: the image as given (3 floats per texel) and a device buffer of the
+    // renderer's own with one float4 per texel; the tail carries only a two-vec4 record that points to it (a 2048 x 1024 map is 32 MiB, and there are up to five tails)
+    struct { bool on = false; uint32_t w = 0, h = 0; float u0 = 0.0f; std::vector<float> host; DevBuf texels; } env;
+    // the images with a tail, held while any of the three is on: the plain image's and each built light-sampling mode's
     struct { DevBuf blob, nee_blob[4]; } tail;
-    bool tail_on() const { return vn.on || uv.on; }
+    bool tail_on() const { return vn.on || uv.on || env.on; }
     // `src` holds staged_vec4 units of image (and a zero header); dst = the same units, then the header (normals follow at +1 ? 1 : 0, vec4 from the header to
-    // the texture coordinates or 0, -, -), then the normals if on, then the texture coordinates if on — each table from a 16-byte boundary
+    // the texture coordinates or 0, vec4 from the header to the environment record or 0, -), then the normals if on, then the texture coordinates if on — each
+    // table from a 16-byte boundary — then the environment record if on: (W, H, u0 bits, -), (pointer low, pointer high, -, -)
     int image_with_tail(const DevBuf& src, uint32_t staged_vec4, DevBuf& dst) const {
         const size_t vn_vec4 = vn.on ? (vn.host.size() * sizeof(float) + 15u) / 16u : 0u;
         const size_t uv_vec4 = uv.on ? (uv.host.size() * sizeof(float) + 15u) / 16u : 0u;
-        std::vector<uint4> t(1u + vn_vec4 + uv_vec4, make_uint4(0u, 0u, 0u, 0u));
+        std::vector<uint4> t(1u + vn_vec4 + uv_vec4 + (env.on ? 2u : 0u), make_uint4(0u, 0u, 0u, 0u));
         t[0].x = vn.on ? 1u : 0u;
         t[0].y = uv.on ? (uint32_t)(1u + vn_vec4) : 0u;
+        if (env.on) {
+            const size_t at = 1u + vn_vec4 + uv_vec4;
+            const uint64_t ptr = (uint64_t)reinterpret_cast<uintptr_t>(env.texels.p);
+            t[0].z = (uint32_t)at;
+            t[at].x = env.w; t[at].y = env.h; std::memcpy(&t[at].z, &env.u0, 4);
+            t[at + 1u].x = (uint32_t)ptr; t[at + 1u].y = (uint32_t)(ptr >> 32);
+        }
         if (vn.on) std::memcpy(&t[1], vn.host.data(), vn.host.size() * sizeof(float));
         if (uv.on) std::memcpy(&t[1u + vn_vec4], uv.host.data(), uv.host.size() * sizeof(float));
         HIP_TRY(dst.alloc(((size_t)staged_vec4 + t.size()) * sizeof(uint4)));
@@ -245,7 +256,7 @@ struct rt_renderer {
         HIP_TRY(hipMemcpy(dst.as<uint4>() + staged_vec4, t.data(), t.size() * sizeof(uint4), hipMemcpyHostToDevice));
         return RT_OK;
     }
-    // the tails anew from vn and uv as they stand: none while both are off, else the plain image's and one per light-sampling mode already built
+    // the tails anew from vn, uv and env as they stand: none while all are off, else the plain image's and one per light-sampling mode already built
     int rebuild_tails() {
         tail.blob.release();
         for (DevBuf& b : tail.nee_blob) b.release();
@@ -324,6 +335,11 @@ struct rt_renderer {
         if (want == 3 && cfg.variant == 0 && can_xchg) {
             const char* env = std::getenv("RT06_DEFAULT_XCHG");
             if (env && env[0] == '1') want = 5;
+        }
+        if (scene.dw.background == 2u) {   // §23: the environment map is looked up in render_kernel_stream's EXT 2 forms only
+            if (want == 1) return rt_fail(RT_ERR_INVALID, "the baseline kernel (variant 1) looks no environment map up: a world with background mode 2 renders on variant 0, 2 or 3");
+            if (want == 5) return rt_fail(RT_ERR_INVALID, "kernel variant 5 (ray exchange) looks no environment map up: a world with background mode 2 renders on variant 0, 2 or 3");
+            if (want_tol) return rt_fail(RT_ERR_INVALID, "kernel variant 6 (tolerance-mode box test) looks no environment map up: a world with background mode 2 renders on variant 0, 2 or 3");
         }
         if (want == 5 && !can_xchg)
             return rt_fail(RT_ERR_INVALID, "kernel variant 5 (ray exchange) needs an LDS-resident RT_WORLD_BVH world of the reference's feature set with box coordinates in the fast-division class");
@@ -726,6 +742,8 @@ extern "C" void rt_renderer_destroy(rt_renderer* r) {
 // one call's launches between the renderer's two timing events on the caller's stream (a call that runs ahead has its resolve between them, and
 // the wait for its tracer)
 static int enqueue_call(rt_renderer* r, void* hip_stream, float* d_out, uint32_t first_s, uint32_t n_s, bool refine, bool run_ahead = false) {
+    if (r->scene.dw.background == 2u && !r->env.on)   // never launch with a dangling record
+        return rt_fail(RT_ERR_INVALID, "the world's background is an environment map (mode 2) and the renderer has none: give it one with rt_renderer_environment before rendering");
     HIP_TRY(hipSetDevice(r->cfg.device));
     hipStream_t st = (hipStream_t)hip_stream;  // NULL is the HIP null stream, as for any HIP launch
     HIP_TRY(hipEventRecord(r->ev0, st));
@@ -921,6 +939,44 @@ extern "C" int rt_renderer_texture_coords_info(rt_renderer* r, uint32_t out[2]) 
     if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_texture_coords_info: null argument");
     out[0] = r->uv.on ? 1u : 0u;
     out[1] = r->uv.on ? r->uv.n_mapped : 0u;
+    return RT_OK;
+}
+
+// The environment map of a background-2 world.  The texels live in a buffer of the renderer's own; every image it launches on gets the tail record
+// that points there.  Off, a background-2 renderer refuses to launch (enqueue_call).
+extern "C" int rt_renderer_environment(rt_renderer* r, uint32_t width, uint32_t height, const float* rgb, float u0) {
+    if (!r) return rt_fail(RT_ERR_INVALID, "rt_renderer_environment: null renderer");
+    const bool off = rgb == nullptr && width == 0u && height == 0u;
+    if (!off) {
+        if (r->scene.dw.background != 2u)
+            return rt_fail(RT_ERR_INVALID, "rt_renderer_environment: the world's background mode is %u; an environment map belongs to a world created with mode 2 (rt_scene_set_environment)", r->scene.dw.background);
+        if (const char* why = rt_environment_image_refusal(width, height, rgb)) return rt_fail(RT_ERR_INVALID, "rt_renderer_environment: %s", why);
+        if (!(u0 >= 0.0f && u0 < 1.0f)) return rt_fail(RT_ERR_INVALID, "rt_renderer_environment: u0 must lie in [0, 1)");
+    }
+    const size_t n_texels = (size_t)width * height;
+    if (off ? !r->env.on : (r->env.on && r->env.w == width && r->env.h == height && std::memcmp(&r->env.u0, &u0, 4) == 0 &&
+                            std::memcmp(r->env.host.data(), rgb, n_texels * 3u * sizeof(float)) == 0)) return RT_OK;   // nothing changes, the refinement goes on
+    if (const int rc = wait_last_call(r)) return rc;   // launches already enqueued read the images and the texels that are replaced below
+    r->env.on = false;
+    r->refine_done = 0;   // samples lit by another sky belong to another frame
+    r->aov_done = 0;
+    r->env.texels.release();
+    r->env.host.clear(); r->env.w = r->env.h = 0u; r->env.u0 = 0.0f;
+    if (off) return r->rebuild_tails();   // the vertex normals and the texture coordinates, if on, stay on
+    std::vector<float4> texels(n_texels);
+    for (size_t i = 0; i < n_texels; i++) texels[i] = make_float4(rgb[3u * i], rgb[3u * i + 1u], rgb[3u * i + 2u], 0.0f);
+    if (const hipError_t e = r->env.texels.upload(texels.data(), n_texels * sizeof(float4)); e != hipSuccess) { r->rebuild_tails(); HIP_TRY(e); }
+    r->env.host.assign(rgb, rgb + n_texels * 3u);
+    r->env.w = width; r->env.h = height; r->env.u0 = u0;
+    r->env.on = true;
+    if (const int rc = r->rebuild_tails()) { r->env.on = false; r->env.texels.release(); r->rebuild_tails(); return rc; }
+    return RT_OK;
+}
+
+extern "C" int rt_renderer_environment_info(rt_renderer* r, uint32_t out[4]) {
+    if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_environment_info: null argument");
+    out[0] = r->env.on ? 1u : 0u; out[1] = r->env.w; out[2] = r->env.h;
+    std::memcpy(&out[3], &r->env.u0, 4);
     return RT_OK;
 }
 

@@ -462,6 +462,32 @@ RT_HD f3 image_texel(const uint8_t* image, uint32_t width, uint32_t height, floa
     return mk3((float)px[0] * 0x1.010102p-8f, (float)px[1] * 0x1.010102p-8f, (float)px[2] * 0x1.010102p-8f);
 }
 
+// Environment maps (rt06.h: rt_scene_set_environment): what a ray that leaves the world sees.  d = the ray's direction (any length), texels =
+// width x height records (r, g, b, -), row 0 at the top, u0 in [0, 1) = the rotation about y.  image_value's map and constants, the rotation added to u, then
+// image_texel's rule; the clamps are written so that a NaN coordinate lands on texel 0 on host and device alike.  Only + - * / sqrt, comparisons and the two rt_
+// functions, each rounded on its own.  The streaming kernels, the probe and rt_environment_batch call this one function; numpy float32 restates it bit for bit.
+RT_HD uint32_t environment_texel_index(uint32_t width, uint32_t height, float u0, f3 d) {
+    const f3 n = normalize(d);
+    float cy = -n.y;
+    cy = cy < -1.0f ? -1.0f : (cy > 1.0f ? 1.0f : cy);
+    const float theta = rt_acosf(cy);
+    const float phi = rt_atan2f(-n.z, n.x) + 0x1.921fb6p+1f;
+    float u = phi / 0x1.921fb6p+2f + u0;
+    if (u >= 1.0f) u = u - 1.0f;
+    float v = theta / 0x1.921fb6p+1f;
+    u = !(u > 0.0f) ? 0.0f : (u > 1.0f ? 1.0f : u);
+    v = !(v > 0.0f) ? 0.0f : (v > 1.0f ? 1.0f : v);
+    v = 1.0f - v;   // flip to image coordinates
+    int i = (int)(u * (float)width), j = (int)(v * (float)height);
+    if (i > (int)width - 1) i = (int)width - 1;
+    if (j > (int)height - 1) j = (int)height - 1;
+    return (uint32_t)j * width + (uint32_t)i;
+}
+RT_HD f3 environment_value(const float4* texels, uint32_t width, uint32_t height, float u0, f3 d) {
+    const float4 t = texels[environment_texel_index(width, height, u0, d)];   // one 16-byte load
+    return mk3(t.x, t.y, t.z);
+}
+
 // Material::Scatter — LambertianAbstract (cu_materials.cuh:52-64), MetalAbstract (:77-95),
 // DielectricAbstract (:115-143), LambertianTexture (:27-40)
 // `w`: the world's Perlin tables / image for the two textured extension materials (may be null otherwise)

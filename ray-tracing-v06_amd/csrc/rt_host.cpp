@@ -156,6 +156,9 @@ struct rt_scene {
     std::vector<rt_tri_uvs> tri_uv;       // texture coordinates: parallel to tri_vn; a triangle without any holds the identity (0,0), (1,0), (0,1)
     uint32_t background = 0;
     float background_color[3] = {0.0f, 0.0f, 0.0f};
+    std::vector<float> env;               // environment map (background == 2): env_w x env_h texels of 3 floats, row 0 at the top
+    uint32_t env_w = 0, env_h = 0;
+    float env_u0 = 0.0f;                  // its rotation about y as a shift of u, in [0, 1)
     uint32_t traversal = RT_TRAVERSAL_STACK;
     std::vector<rt_material> mats;
     std::vector<rt_perlin> perlin;        // 0 or 1 table set (RT_MAT_LAMBERTIAN_NOISE)
@@ -342,6 +345,36 @@ extern "C" int rt_scene_set_background(rt_scene* s, uint32_t mode, const float c
     if (mode > 1) return rt_fail(RT_ERR_INVALID, "rt_scene_set_background: unknown mode %u", mode);
     s->background = mode;
     if (color) st3(s->background_color, ld3(color));
+    s->env.clear(); s->env_w = s->env_h = 0u; s->env_u0 = 0.0f;   // the gradient and the constant colour drop an environment map
+    return RT_OK;
+}
+// what rt_scene_set_environment and rt_renderer_environment refuse of an image; null = nothing
+const char* rt_environment_image_refusal(uint32_t width, uint32_t height, const float* rgb) {
+    if (width == 0u || height == 0u) return "a dimension is zero";
+    if ((uint64_t)width * height > (uint64_t)RT_ENV_MAX_TEXELS) return "more than 2^25 texels";
+    if (!rgb) return "null image";
+    for (size_t i = 0; i < (size_t)width * height * 3u; i++) {
+        if (!std::isfinite(rgb[i])) return "a texel that is not finite";
+        if (rgb[i] < 0.0f) return "a negative texel";
+    }
+    return nullptr;
+}
+extern "C" int rt_scene_set_environment(rt_scene* s, uint32_t width, uint32_t height, const float* rgb, float rotate_y_degrees) {
+    if (!s) return rt_fail(RT_ERR_INVALID, "rt_scene_set_environment: null scene");
+    if (const char* why = rt_environment_image_refusal(width, height, rgb)) return rt_fail(RT_ERR_INVALID, "rt_scene_set_environment: %s", why);
+    if (!std::isfinite(rotate_y_degrees)) return rt_fail(RT_ERR_INVALID, "rt_scene_set_environment: the rotation is not finite");
+    const double turns = (double)rotate_y_degrees / 360.0;
+    float u0 = (float)(turns - std::floor(turns));   // frac: in [0, 1] after the rounding to fp32
+    if (!(u0 < 1.0f)) u0 = 0.0f;
+    s->env.assign(rgb, rgb + (size_t)width * height * 3u);
+    s->env_w = width; s->env_h = height; s->env_u0 = u0;
+    s->background = 2u;
+    return RT_OK;
+}
+extern "C" int rt_scene_environment(const rt_scene* s, uint32_t* out_w, uint32_t* out_h, const float** out_rgb, float* out_u0) {
+    if (!s || !out_w || !out_h || !out_rgb || !out_u0) return rt_fail(RT_ERR_INVALID, "rt_scene_environment: null argument");
+    *out_w = s->env_w; *out_h = s->env_h; *out_u0 = s->env_u0;
+    *out_rgb = s->env.empty() ? nullptr : s->env.data();
     return RT_OK;
 }
 

@@ -6,3 +6,4 @@
 #define RT_TILE 8        // 8x8-pixel tiles: the reference's thread-block shape, Renderer.cu:130
 
 int rt_fail(int code, const char* fmt, ...);
+const char* rt_environment_image_refusal(uint32_t width, uint32_t height, const float* rgb);   // rt_host.cpp: why an environment map is refused, or null

@@ -56,7 +56,7 @@ struct PackedSceneRef {
     uint32_t off_mats;
     uint32_t off_quads;
     uint32_t sphere_codes;   // leaf codes below this are spheres (prim * 2 + is_moving); code - sphere_codes is a quad index
-    uint32_t background;     // 0 = reference sky gradient, 1 = background_color
+    uint32_t background;     // 0 = reference sky gradient, 1 = background_color, 2 = the environment map behind the image
     float background_color[3];
     uint32_t root_ref;
     float root_min[3], root_max[3];

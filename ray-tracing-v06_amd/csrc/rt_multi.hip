@@ -286,6 +286,15 @@ extern "C" int rt_multi_renderer_texture_coords(rt_multi_renderer* m, const rt_t
     return RT_OK;
 }
 
+extern "C" int rt_multi_renderer_environment(rt_multi_renderer* m, uint32_t width, uint32_t height, const float* rgb, float u0) {
+    if (!m) return rt_fail(RT_ERR_INVALID, "rt_multi_renderer_environment: null renderer");
+    for (rt_renderer* r : m->parts) {   // every rank holds the same world: the first refuses what any would, before any part changes
+        const int rc = rt_renderer_environment(r, width, height, rgb, u0);
+        if (rc != RT_OK) return rc;
+    }
+    return RT_OK;
+}
+
 extern "C" int rt_multi_renderer_download(rt_multi_renderer* m, float* host_rgba, size_t n_floats) {
     if (!m || !host_rgba) return rt_fail(RT_ERR_INVALID, "rt_multi_renderer_download: null argument");
     const size_t need = (size_t)m->width * m->height * 4;

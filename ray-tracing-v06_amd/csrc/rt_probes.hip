@@ -81,6 +81,14 @@ __global__ void probe_tri_uv_kernel(DeviceWorld w, const rt_tri_uvs* uv, uint32_
     hit[i] = h ? 1 : 0;
     out_uv[2 * i] = tu; out_uv[2 * i + 1] = tv;
 }
+// the environment rule (environment_value), one lane per direction, on the map as the renderer holds it: one float4 per texel
+__global__ void probe_environment_kernel(size_t n, const float4* texels, uint32_t width, uint32_t height, float u0, const float* dirs, float* out_rgb, uint32_t* out_texel) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const f3 d = ld3(dirs + 3 * i);
+    out_texel[i] = environment_texel_index(width, height, u0, d);
+    st3(out_rgb + 3 * i, environment_value(texels, width, height, u0, d));
+}
 // SphereHittable / MovingSphereHittable::ClosestIntersection on one sphere per ray, rec.distance preset by the caller: the leaf
 // test every traversal calls (prim_closest_intersection), as a plain sphere (material 0 = a Lambertian, the moving bit kept)
 __global__ void probe_sphere_hit_kernel(size_t n, const rt_prim* prims, const rt_material* mat, const float* rays, const float* preset,
@@ -293,6 +301,40 @@ extern "C" int rt_probe_tri_uv(int device, const rt_world_flat* world, const rt_
     p.launch(probe_tri_uv_kernel, p.per_case(n), 128, sc.dw, uv, world->n_prims + world->n_quads - sc.n_triangles, n, r, h, o);
     return p.finish() != RT_OK ? p.rc : check_traversal_overflow(sc);
 }
+static int environment_args(const char* who, size_t n, uint32_t width, uint32_t height, const float* rgb, float u0, const float* dirs, float* out_rgb, uint32_t* out_texel) {
+    if (const char* why = rt_environment_image_refusal(width, height, rgb)) return rt_fail(RT_ERR_INVALID, "%s: %s", who, why);
+    if (!(u0 >= 0.0f && u0 < 1.0f)) return rt_fail(RT_ERR_INVALID, "%s: u0 must lie in [0, 1)", who);
+    if (n && (!dirs || !out_rgb || !out_texel)) return rt_fail(RT_ERR_INVALID, "%s: null argument", who);
+    return RT_OK;
+}
+static std::vector<float4> environment_texels(uint32_t width, uint32_t height, const float* rgb) {   // the renderer's form: one 16-byte record per texel
+    std::vector<float4> t((size_t)width * height);
+    for (size_t i = 0; i < t.size(); i++) t[i] = make_float4(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2], 0.0f);
+    return t;
+}
+extern "C" int rt_probe_environment(int device, size_t n, uint32_t width, uint32_t height, const float* rgb, float u0, const float* dirs, float* out_rgb, uint32_t* out_texel) {
+    if (const int rc = environment_args("rt_probe_environment", n, width, height, rgb, u0, dirs, out_rgb, out_texel)) return rc;
+    if (n == 0) return RT_OK;
+    const std::vector<float4> texels = environment_texels(width, height, rgb);
+    ProbeRun p(device);
+    auto t = p.in(texels.data(), texels.size());
+    auto d = p.in(dirs, 3 * n);
+    auto o = p.out(out_rgb, 3 * n); auto x = p.out(out_texel, n);
+    p.launch(probe_environment_kernel, p.per_case(n), 128, n, t, width, height, u0, d, o, x);
+    return p.finish();
+}
+// HOST (no GPU): the kernels' environment_value() over arrays
+extern "C" int rt_environment_batch(size_t n, uint32_t width, uint32_t height, const float* rgb, float u0, const float* dirs, float* out_rgb, uint32_t* out_texel) {
+    if (const int rc = environment_args("rt_environment_batch", n, width, height, rgb, u0, dirs, out_rgb, out_texel)) return rc;
+    if (n == 0) return RT_OK;
+    const std::vector<float4> texels = environment_texels(width, height, rgb);
+    for (size_t i = 0; i < n; i++) {
+        const f3 d = ld3(dirs + 3 * i);
+        out_texel[i] = environment_texel_index(width, height, u0, d);
+        st3(out_rgb + 3 * i, environment_value(texels.data(), width, height, u0, d));
+    }
+    return RT_OK;
+}
 // HOST (no GPU): the kernels' tri_uv() over arrays
 extern "C" int rt_tri_uv_batch(size_t n, const rt_quad* tris, const rt_tri_uvs* uv, const float* rays, const float* t, float* out_uv) {
     if (n && (!tris || !uv || !rays || !t || !out_uv)) return rt_fail(RT_ERR_INVALID, "rt_tri_uv_batch: null argument");
@@ -406,6 +448,8 @@ extern "C" int rt_probe_radiance(const rt_render_config* cfg, const rt_camera* c
     if (cam->type > RT_CAM_MOTION) return rt_fail(RT_ERR_INVALID, "rt_probe_radiance: unknown camera type");
     for (size_t i = 0; i < n; i++)
         if (keys[2 * i] >= cfg->width * cfg->height) return rt_fail(RT_ERR_INVALID, "rt_probe_radiance: key %zu: pixel out of range", i);
+    if (world && world->background == 2u)
+        return rt_fail(RT_ERR_INVALID, "rt_probe_radiance: the probe runs sample_world, which looks no environment map up (background mode 2); rt_probe_environment probes the map");
     ProbeRun p(cfg->device);
     DeviceScene sc;
     if (p.ok()) p.rc = sc.upload(world);

@@ -259,6 +259,10 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
     // §22, TRI with image textures (EXT >= 2) only: the same header's .y = how many vec4 behind the header the texture coordinates start (24 B per triangle), 0 = none
     uint32_t uv_at = 0u;
     if constexpr (TRI && EXT >= 2) uv_at = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.scene.blob[p.scene.blob_vec4].y);
+    // §23, EXT >= 2 only: the same header's .z = how many vec4 behind the header the environment record lies — (W, H, u0 bits, -), (pointer low, pointer high, -, -) —
+    // 0 = none.  The renderer launches a background-2 world only with a record.
+    uint32_t env_at = 0u;
+    if constexpr (EXT >= 2) env_at = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.scene.blob[p.scene.blob_vec4].z);
     const f3 root_min = mk3(p.scene.root_min[0], p.scene.root_min[1], p.scene.root_min[2]);
     const f3 root_max = mk3(p.scene.root_max[0], p.scene.root_max[1], p.scene.root_max[2]);
 
@@ -559,8 +563,22 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                 if (EXT && p.scene.background == 1u) {
                     sky = mk3(p.scene.background_color[0], p.scene.background_color[1], p.scene.background_color[2]);
                 } else {
+                    bool from_map = false;
+                    if constexpr (EXT >= 2) {
+                        if (p.scene.background == 2u && env_at != 0u) {   // §23: the environment map; the record through scalars, the lookup per lane
+                            const uint4* er = p.scene.blob + p.scene.blob_vec4 + env_at;
+                            const uint4 e0 = er[0], e1 = er[1];
+                            const uint32_t env_w = (uint32_t)__builtin_amdgcn_readfirstlane((int)e0.x), env_h = (uint32_t)__builtin_amdgcn_readfirstlane((int)e0.y);
+                            const float env_u0 = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)e0.z));
+                            const uint64_t env_p = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)e1.x) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)e1.y) << 32;
+                            sky = environment_value(reinterpret_cast<const float4*>(env_p), env_w, env_h, env_u0, ray.d);
+                            from_map = true;
+                        }
+                    }
+                    if (!from_map) {
                     float t = normalize(ray.d).y * 0.5f + 0.5f;
                     sky = linear_interpolate(mk3(0.1f, 0.2f, 0.4f), mk3(0.9f, 0.9f, 0.99f), t);
+                    }
                 }
                 f3 rad = atten * sky;
                 if (EXT) rad = rad + accum_rad;

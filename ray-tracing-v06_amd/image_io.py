@@ -276,3 +276,126 @@ def write_jpg(path, framebuffer, quality=95):
     head += segment(0xDA, bytes([3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0]))
     with open(path, "wb") as f:
         f.write(head + bytes(out) + b"\xff\xd9")
+
+
+# ---- Radiance RGBE (.hdr) pictures and a procedural sky: environment maps ----
+# A pixel is three 8-bit mantissas and one shared exponent: channel = (mantissa + 0.5) * 2^(e - 136), all zero bytes = black (Radiance's color.c).  The largest
+# channel's mantissa is >= 128, so a channel is off by at most 2^-8 of the LARGEST channel of its pixel after a round trip.
+def _rgbe_encode(rgb):
+    rgb = np.asarray(rgb, dtype=np.float64)
+    v = rgb.max(axis=-1)
+    m, e = np.frexp(v)
+    ok = v >= 1e-32
+    scale = np.where(ok, m * 256.0 / np.where(ok, v, 1.0), 0.0)
+    out = np.zeros(rgb.shape[:-1] + (4,), np.uint8)
+    out[..., :3] = np.clip(np.floor(rgb * scale[..., None]), 0, 255).astype(np.uint8)
+    out[..., 3] = np.where(ok, e + 128, 0).astype(np.uint8)
+    out[~ok] = 0
+    return out
+
+
+def _rgbe_decode(rgbe):
+    e = rgbe[..., 3].astype(np.int32)
+    f = np.ldexp(1.0, e - 136)
+    out = (rgbe[..., :3].astype(np.float64) + 0.5) * f[..., None]
+    out[e == 0] = 0.0
+    return out.astype(np.float32)
+
+
+def write_hdr(path, image):
+    """A Radiance RGBE picture of image (H, W, 3) float, finite and >= 0, row 0 at the top: `-Y H +X W`, flat scanlines."""
+    img = np.asarray(image, dtype=np.float32)
+    if img.ndim != 3 or img.shape[2] != 3 or img.shape[0] == 0 or img.shape[1] == 0:
+        raise ValueError("write_hdr: the image must have shape (H, W, 3)")
+    if not np.isfinite(img).all() or (img < 0).any():
+        raise ValueError("write_hdr: values must be finite and >= 0")
+    h, w, _ = img.shape
+    with open(path, "wb") as f:
+        f.write(b"#?RADIANCE\nFORMAT=32-bit_rle_rgbe\n\n" + f"-Y {h} +X {w}\n".encode("ascii") + _rgbe_encode(img).tobytes())
+
+
+def read_hdr(path):
+    """A Radiance RGBE picture as (H, W, 3) float32, row 0 at the top.  Flat and new-style run-length encoded scanlines, orientation `-Y H +X W` only;
+    anything else raises ValueError."""
+    with open(path, "rb") as f:
+        data = f.read()
+    if not data.startswith(b"#?"):
+        raise ValueError("read_hdr: not a Radiance picture (no #? signature)")
+    pos, fmt = 0, None
+    while True:
+        end = data.find(b"\n", pos)
+        if end < 0:
+            raise ValueError("read_hdr: the header does not end")
+        line = data[pos:end]
+        pos = end + 1
+        if not line:
+            break
+        if line.startswith(b"FORMAT="):
+            fmt = line[7:].strip()
+    if fmt != b"32-bit_rle_rgbe":
+        raise ValueError(f"read_hdr: FORMAT must be 32-bit_rle_rgbe, not {fmt!r}")
+    end = data.find(b"\n", pos)
+    parts = data[pos:end].split() if end >= 0 else []
+    if len(parts) != 4 or parts[0] != b"-Y" or parts[2] != b"+X" or not parts[1].isdigit() or not parts[3].isdigit():
+        raise ValueError("read_hdr: the resolution line must read -Y H +X W")
+    h, w = int(parts[1]), int(parts[3])
+    if h == 0 or w == 0:
+        raise ValueError("read_hdr: empty picture")
+    pos = end + 1
+    out = np.zeros((h, w, 4), np.uint8)
+    for y in range(h):
+        if 8 <= w <= 0x7fff and data[pos:pos + 2] == b"\x02\x02" and pos + 4 <= len(data) and data[pos + 2] < 128:   # a new-style run-length encoded scanline
+            if (data[pos + 2] << 8 | data[pos + 3]) != w:
+                raise ValueError(f"read_hdr: scanline {y}: its length does not match the width")
+            pos += 4
+            for c in range(4):   # the four bytes of every pixel are coded apart
+                x = 0
+                while x < w:
+                    if pos >= len(data):
+                        raise ValueError(f"read_hdr: scanline {y}: the data ends early")
+                    count = data[pos]
+                    pos += 1
+                    if count > 128:   # a run: count - 128 copies of one byte
+                        count -= 128
+                        if x + count > w or pos >= len(data):
+                            raise ValueError(f"read_hdr: scanline {y}: a run passes the end of the line")
+                        out[y, x:x + count, c] = data[pos]
+                        pos += 1
+                    else:             # count bytes as they are
+                        if count == 0 or x + count > w or pos + count > len(data):
+                            raise ValueError(f"read_hdr: scanline {y}: a bad literal count")
+                        out[y, x:x + count, c] = np.frombuffer(data, np.uint8, count, pos)
+                        pos += count
+                    x += count
+        else:   # flat: four bytes per pixel
+            if pos + 4 * w > len(data):
+                raise ValueError(f"read_hdr: scanline {y}: the data ends early")
+            row = np.frombuffer(data, np.uint8, 4 * w, pos).reshape(w, 4)
+            if ((row[:, 0] == 1) & (row[:, 1] == 1) & (row[:, 2] == 1)).any():
+                raise ValueError(f"read_hdr: scanline {y}: old-style run-length encoding is not read")
+            out[y] = row
+            pos += 4 * w
+    return _rgbe_decode(out)
+
+
+def sky_environment(width, height, sun_dir=(0.4, 0.6, -0.7), sun_radiance=(60.0, 54.0, 45.0), sun_radius_deg=4.0, zenith=(0.15, 0.3, 0.8), horizon=(0.8, 0.85, 0.9),
+                    ground=(0.25, 0.22, 0.2)):
+    """A procedural HDR sky as an environment map (H, W, 3) float32, row 0 at the top, in the layout the lookup reads with u0 = 0: a gradient from
+    the horizon to the zenith, a flat ground below the horizon, a sun disc of sun_radiance within sun_radius_deg of sun_dir and a glow around it."""
+    u = (np.arange(width, dtype=np.float64) + 0.5) / width
+    theta = np.pi * (1.0 - (np.arange(height, dtype=np.float64) + 0.5) / height)   # of the lookup: acos(-n.y); row 0 looks up
+    a = 2.0 * np.pi * u - np.pi                                                   # atan2(-n.z, n.x)
+    ny = -np.cos(theta)[:, None] * np.ones((1, width))
+    nx = np.sin(theta)[:, None] * np.cos(a)[None, :]
+    nz = -np.sin(theta)[:, None] * np.sin(a)[None, :]
+    s = np.asarray(sun_dir, dtype=np.float64)
+    s = s / np.sqrt((s * s).sum())
+    up = np.clip(ny, 0.0, 1.0)[..., None]
+    sky = np.asarray(horizon, np.float64) * (1.0 - up) + np.asarray(zenith, np.float64) * up
+    img = np.where((ny >= 0.0)[..., None], sky, np.asarray(ground, np.float64))
+    cos_sun = nx * s[0] + ny * s[1] + nz * s[2]
+    sun = np.asarray(sun_radiance, np.float64)
+    glow = np.clip(cos_sun, 0.0, 1.0) ** 64
+    img = img + (ny >= 0.0)[..., None] * glow[..., None] * sun * 0.02
+    img = np.where((cos_sun >= np.cos(np.radians(sun_radius_deg)))[..., None], sun, img)
+    return np.ascontiguousarray(img, dtype=np.float32)

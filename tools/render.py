@@ -37,6 +37,12 @@ samples the triangles of an emissive mesh too (RT_LIGHT_SAMPLING_MESH), up to 64
 
 places a triangle mesh — an OBJ file, icosphere:LEVEL or tetrahedron (ray-tracing-v06_amd/mesh_io.py) — into the prefab scene before its BVH is
 built again (rt_scene_add_mesh): scaled, rotated about y (degrees), translated, in that order.  Materials: white, red, metal, glass, checker, light.
+
+    python tools/render.py --scene book1_final --env sky --env-rotate 90 --env-scale 0.5 --out out.png
+
+lights the world with an environment map (rt_scene_set_environment) in the place of its background: a Radiance .hdr picture, a float .npy array
+(H, W, 3), an 8-bit .png / .ppm (mapped to [0, 1]) or `sky`, the procedural sky of image_io.sky_environment.  --env-rotate turns it about y (degrees),
+--env-scale multiplies it on the host before upload.
 """
 import argparse, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -68,6 +74,10 @@ ap.add_argument("--smooth", action="store_true", help="with --mesh: smooth shadi
                     "set, an icosphere's unit positions, else area-weighted ones (mesh_io.vertex_normals)")
 ap.add_argument("--texture", default=None, metavar="FILE.ppm|FILE.png", help="with --mesh FILE.obj: the mesh's material is this image over the file's `vt` texture "
                     "coordinates (DESIGN.md §22; binary PPM or 8-bit RGB / RGBA PNG); refused when the OBJ has no complete set of them")
+ap.add_argument("--env", default=None, metavar="FILE.hdr|FILE.npy|FILE.png|FILE.ppm|sky", help="an equirectangular environment map in the place of the scene's background "
+                    "(DESIGN.md §23): Radiance RGBE, a float (H, W, 3) numpy array, an 8-bit picture (mapped to [0, 1]) or the procedural sky")
+ap.add_argument("--env-rotate", type=float, default=0.0, metavar="DEG", help="with --env: turn the map about y")
+ap.add_argument("--env-scale", type=float, default=1.0, metavar="X", help="with --env: multiply the map's radiance, on the host before upload")
 ap.add_argument("--out", default="render.png")
 a = ap.parse_args()
 light_mode = {"quads": 1, "all": 2, "mesh": 4, "tree": 16}.get(a.light_sampling_mode, 1 if a.light_sampling else 0)   # RT_LIGHT_SAMPLING_*
@@ -122,6 +132,20 @@ if a.mesh:
     else:
         scene.BuildBVH_TopDown()
     print(json.dumps({"mesh": a.mesh, "triangles": added, "skipped_degenerate": len(faces) - added}), flush=True)
+if a.env:
+    import numpy as np
+    low = a.env.lower()
+    if a.env == "sky":
+        env = image_io.sky_environment(1024, 512)
+    elif low.endswith(".hdr"):
+        env = image_io.read_hdr(a.env)
+    elif low.endswith(".npy"):
+        env = np.load(a.env)
+    elif low.endswith((".png", ".ppm")):
+        env = (image_io.read_png if low.endswith(".png") else image_io.read_ppm)(a.env).astype(np.float32) / np.float32(255.0)
+    else:
+        sys.exit("--env: a .hdr, .npy, .png or .ppm file, or `sky`")
+    scene.set_environment(np.asarray(env, dtype=np.float32) * np.float32(a.env_scale), rotate_y=a.env_rotate)
 samples = a.spp
 if a.refine:
     import time
