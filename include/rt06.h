@@ -295,6 +295,29 @@ int rt_scene_set_environment(rt_scene* s, uint32_t width, uint32_t height, const
 int rt_scene_environment(const rt_scene* s, uint32_t* out_w, uint32_t* out_h, const float** out_rgb, float* out_u0);
 /* HOST (no GPU): the rule above on n directions dirs[3 i ..] -> out_rgb[3 i ..], out_texel[i] = j * width + i.  The function the kernels call.                   */
 int rt_environment_batch(size_t n, uint32_t width, uint32_t height, const float* rgb, float u0, const float* dirs, float* out_rgb, uint32_t* out_texel);
+/* ---- environment light sampling: the distribution mode RT_LIGHT_SAMPLING_ENV draws directions from, in proportion to radiance times solid angle.
+ * HOST (no GPU).  Built in double, stored as fp32; image row j (0 = the top) is the band n.y in [rowy[j + 1], rowy[j]]:
+ *   rowy[j]    = fp32(cos(pi j / H)), rowy[0] = 1 and rowy[H] = -1 exactly;   h_j = rowy[j] - rowy[j + 1] (of the fp32 values);   omega_j = (2 pi / W) h_j
+ *   w_ji       = ((0.2126 r + 0.7152 g) + 0.0722 b) h_j
+ *   colc[j][i] = fp32(sum over k <= i of w_jk);   rowc[j] = fp32(sum over l <= j of row l's whole sum): running sums in double, rounded when stored
+ *   A = rowc[H - 1], R_j = colc[j][W - 1]
+ *   density[j][i] = fp32(P_j P_i|j / omega_j), P_j = (rowc[j] - rowc[j - 1]) / A, P_i|j = (colc[j][i] - colc[j][i - 1]) / R_j: differences of the STORED values,
+ *                   taken in double, the predecessor of index 0 being 0; P_i|j = 0 in a row with R_j = 0; density 0 where either factor is 0
+ * so the density is that of what the binary searches below really draw: a texel whose weight is lost in a running sum has density 0 and is never drawn (the cosine
+ * half of the estimator still reaches it).  RT_ERR_INVALID: what rt_scene_set_environment refuses of an image; a null array; A = 0 (an all-black map: nothing to
+ * sample); A not finite.  Sizes: rowc[H], rowy[H + 1], colc[H W], density[H W].                                                                                  */
+int rt_environment_distribution(uint32_t width, uint32_t height, const float* rgb, float* rowc, float* rowy, float* colc, float* density);
+/* The rule, with x1, x2, a, b uniforms in (0, 1]:
+ *   x = x1 * A;   if (!(x < A)) x = the float just below A (bit pattern - 1);      j = the smallest row with rowc[j] > x        (binary search)
+ *   x = x2 * R_j; if (!(x < R_j)) x = the float just below R_j;                    i = the smallest column with colc[j][i] > x
+ *   u = ((float)i + a) / (float)W;   y = rowy[j + 1] + (rowy[j] - rowy[j + 1]) * b;   s2 = 1 - y * y;   s = sqrt(s2 > 0 ? s2 : 0)
+ *   t = u - u0; if (t < 0) t = t + 1;   psi = t * two_pi_f - pi_f;   d = (s * sin(psi + half_pi_f), y, -(s * sin psi))          (the library's own rt_sinf)
+ * d is unit only up to rounding and is not renormalised.  The density of ANY direction is density[the texel the lookup above puts it in], so a drawn direction
+ * that rounding put across a border has its neighbour's.  Only fp32 + - * / sqrt, comparisons, that sine and the lookup, each rounded on its own, no FMA.
+ * HOST (no GPU): the rule on n quadruples uniforms[4 i ..] -> out_dir[3 i ..], out_texel[i] = j * width + i as drawn, out_density[i] = the density of out_dir.
+ * The functions the kernels call.  Refused as rt_environment_distribution refuses, and for a uniform outside (0, 1] or u0 outside [0, 1).                        */
+int rt_environment_sample_batch(size_t n, uint32_t width, uint32_t height, const float* rgb, float u0, const float* uniforms, float* out_dir, uint32_t* out_texel,
+                                float* out_density);
 /* selects RT_TRAVERSAL_STACK / RT_TRAVERSAL_QUEUE / RT_TRAVERSAL_WIDE4 for the BVH world of this scene (see the enum) */
 int rt_scene_set_traversal(rt_scene* s, uint32_t mode);
 /* perlin::perlin() of "The Next Week": 256 random unit vectors + three Fisher-Yates permutations, drawn from the
@@ -458,6 +481,9 @@ int rt_renderer_kernel_triangles(rt_renderer* r, uint32_t* out);
 /* *out = 1 when the NEXT launch runs an instantiation of the light-tree family (mode RT_LIGHT_SAMPLING_TREE is on): rt_renderer_kernel_form's nine fields,
  * with nee = 1, plus the tree walk and the choice by area.  A query of its own, so that the nine fields stay what they are.                              */
 int rt_renderer_kernel_light_tree(rt_renderer* r, uint32_t* out);
+/* *out = 1 when the NEXT launch runs an instantiation of the environment-sampling family (mode RT_LIGHT_SAMPLING_ENV is on): the nine fields with nee = 1 and
+ * ext = 2, plus the draw from the map; rt_renderer_kernel_triangles answers 1 too, as under the light tree.  A query of its own, for the same reason.        */
+int rt_renderer_kernel_env_light(rt_renderer* r, uint32_t* out);
 /* Renderer::DownloadRenderbuffer (Renderer.cu:94-96): width*height*4 floats,
  * row-major, row 0 = bottom.  Only valid for world_size == 1.               */
 int rt_renderer_download(rt_renderer* r, float* host_rgba, size_t n_floats);
@@ -571,10 +597,10 @@ int rt_renderer_denoise_download(rt_renderer* r, float* host_rgba, size_t n_floa
  * RT_MAX_LIGHTS; a renderer on variant 1, 5 or 6; a world with a queue or wide4 traversal; a world with a constant medium.            */
 #define RT_MAX_LIGHTS 16
 /* on: RT_LIGHT_SAMPLING_OFF (0), RT_LIGHT_SAMPLING_QUADS (1, the estimator above), RT_LIGHT_SAMPLING_ALL (2, below), RT_LIGHT_SAMPLING_MESH (4, further
- * below) or RT_LIGHT_SAMPLING_TREE (16, last below); every other value — 3 too, which is no mode — is refused */
+ * below), RT_LIGHT_SAMPLING_TREE (16, below that) or RT_LIGHT_SAMPLING_ENV (32, last below); every other value — 3 too, which is no mode — is refused */
 int rt_renderer_light_sampling_enable(rt_renderer* r, uint32_t on);
-/* out[0] = the mode (RT_LIGHT_SAMPLING_OFF / _QUADS / _ALL / _MESH / _TREE), out[1] = n_l of that mode's table — off: of the quad lights, as ever — (0 when the
- * world cannot be light-sampled)                                                                     */
+/* out[0] = the mode (RT_LIGHT_SAMPLING_OFF / _QUADS / _ALL / _MESH / _TREE / _ENV), out[1] = n_l of that mode's table — off: of the quad lights, as ever — (0 when
+ * the world cannot be light-sampled); mode RT_LIGHT_SAMPLING_ENV: the texels of the map, W H                                */
 int rt_renderer_light_sampling_info(rt_renderer* r, uint32_t out[2]);
 /* HOST (no GPU): the light table of a world as rt_renderer_light_sampling_enable would take it — quad index and area of light i < *out_n —
  * or RT_ERR_INVALID with the world's own reason for refusal (no quad light, more than RT_MAX_LIGHTS, traversal, constant medium).     */
@@ -650,6 +676,20 @@ int rt_world_light_table(const rt_world_flat* w, uint32_t mode, uint32_t capacit
  * 8 floats per node — min.xyz, skip (bits), max.xyz, leaf (bits) — into out_nodes, 2 n_l - 1 into *out_n_nodes, c_j of every light into out_cdf.  `capacity`
  * counts lights: out_nodes holds 8 * (2 * capacity - 1) floats, out_cdf capacity.  Refused as the table is.                                                 */
 int rt_world_light_tree(const rt_world_flat* w, uint32_t capacity, float* out_nodes, uint32_t* out_n_nodes, float* out_cdf);
+
+/* The environment map as the light: mode RT_LIGHT_SAMPLING_ENV of rt_renderer_light_sampling_enable (opt-in beside modes 1, 2, 4 and 16, which
+ * stay what they are).  It samples the MAP ONLY: the world's quad, sphere and triangle lights emit when hit and are not sampled, as a sphere light in mode 1.
+ * At a Lambertian or checker hit that does not end the path:  c = next;  if c < 0.5f, x1, x2, a, b = next four times, in that order, and d = the rule of
+ * rt_environment_sample_batch (no on-unit vector is drawn);  otherwise d = normal + on-unit vector, with its near-zero failure.  len2, len, cosn, sp as in the
+ * estimator above;  pl = the density of d (no division by a light count);  pdf = 0.5f * sp + 0.5f * pl;  sp == 0 or !(pdf > 0) ends the path as a failed
+ * scatter;  otherwise atten *= albedo * (sp / pdf) and the new ray is hit_p + d * 0.001f, d.  No shadow ray: the direction is followed, and a miss collects the
+ * map as ever.  Every other material draws and scatters as with sampling off.
+ * The distribution is built when the mode is first enabled and again when rt_renderer_environment replaces the map while the mode is on; the densities ride in
+ * the fourth lane of the renderer's texel records, the tables in one more buffer of its own.  rt_renderer_light_sampling_info gives (32, W H).
+ * RT_ERR_INVALID, each with a message of its own: a world whose background is not 2; a renderer without a map; an all-black map; a renderer on variant 1, 5 or 6;
+ * a world with a queue or wide4 traversal; a world with a constant medium.  While the mode is on, rt_renderer_environment refuses NULL (switch sampling off
+ * first) and an all-black map (the old map stays).                                                                                                       */
+#define RT_LIGHT_SAMPLING_ENV 32
 
 /* Smooth shading (see rt_tri_normals): the renderer's table of vertex normals, one record per triangle of its world — n must equal rt_world_triangles of it —
  * or NULL, 0 to turn it off.  Copied.  Takes effect at the next launch and, like a light-sampling change, discards the refinement and feature-buffer state.  The
@@ -745,6 +785,9 @@ int rt_probe_shading_normal(int device, const rt_world_flat* world, const rt_tri
 int rt_probe_tri_uv(int device, const rt_world_flat* world, const rt_tri_uvs* table, uint32_t n_table, size_t n, const float* rays, int32_t* out_hit, float* out_uv);
 /* rt_environment_batch on the device, one lane per direction: the map as the renderer holds it (one 16-byte record per texel)                                  */
 int rt_probe_environment(int device, size_t n, uint32_t width, uint32_t height, const float* rgb, float u0, const float* dirs, float* out_rgb, uint32_t* out_texel);
+/* rt_environment_sample_batch on the device, one lane per quadruple: the records and the tables as the renderer holds them in mode RT_LIGHT_SAMPLING_ENV        */
+int rt_probe_environment_sample(int device, size_t n, uint32_t width, uint32_t height, const float* rgb, float u0, const float* uniforms, float* out_dir,
+                                uint32_t* out_texel, float* out_density);
 /* SphereHittable / MovingSphereHittable::ClosestIntersection (SphereHittable.cu:56-66, :91-102): sphere
  * prims[i] (material ignored, RT_PRIM_MOVING kept) against ray i (o,d,time) with rec.distance preset[i]
  * -> hit n, rec.distance n, normal n*3 (0 when not hit)                      */

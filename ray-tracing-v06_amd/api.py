@@ -387,14 +387,14 @@ class Scene:
             pass
 
 
-LIGHT_SAMPLING_MODES = {"off": 0, "quads": 1, "all": 2, "mesh": 4, "tree": 16}   # RT_LIGHT_SAMPLING_*
+LIGHT_SAMPLING_MODES = {"off": 0, "quads": 1, "all": 2, "mesh": 4, "tree": 16, "env": 32}   # RT_LIGHT_SAMPLING_*
 
 
 def light_sampling_mode(on):
-    """False / 0 / "off" -> 0, True / 1 / "quads" -> 1, 2 / "all" -> 2, 4 / "mesh" -> 4, 16 / "tree" -> 16 (RT_LIGHT_SAMPLING_*)"""
+    """False / 0 / "off" -> 0, True / 1 / "quads" -> 1, 2 / "all" -> 2, 4 / "mesh" -> 4, 16 / "tree" -> 16, 32 / "env" -> 32 (RT_LIGHT_SAMPLING_*)"""
     if isinstance(on, str):
         if on not in LIGHT_SAMPLING_MODES:
-            raise ValueError(f"light sampling mode {on!r}: one of 'off', 'quads', 'all', 'mesh', 'tree'")
+            raise ValueError(f"light sampling mode {on!r}: one of 'off', 'quads', 'all', 'mesh', 'tree', 'env'")
         return LIGHT_SAMPLING_MODES[on]
     return int(on)
 
@@ -551,19 +551,20 @@ class Renderer:
     def light_sampling(self, on=True):
         """Next-event estimation from the next launch on (rt_renderer_light_sampling_enable); a change restarts the refinement.
         False / 0 / "off": off; True / 1 / "quads": over the world's quad lights; 2 / "all": over its quad and sphere lights; 4 / "mesh": over its quad,
-        sphere and triangle lights (an emissive mesh); 16 / "tree": over the same lights, up to 4096, chosen by area and found through a light tree."""
+        sphere and triangle lights (an emissive mesh); 16 / "tree": over the same lights, up to 4096, chosen by area and found through a light tree;
+        32 / "env": over the environment map of a background-2 world alone, directions drawn in proportion to radiance times solid angle."""
         check(lib().rt_renderer_light_sampling_enable(self.h, light_sampling_mode(on)))
 
     def light_sampling_mode(self):
-        """0 (off), 1 (quad lights), 2 (quad and sphere lights), 4 (quad, sphere and triangle lights) or 16 (those, by area, through a light tree): the mode
-        the next launch runs in."""
+        """0 (off), 1 (quad lights), 2 (quad and sphere lights), 4 (quad, sphere and triangle lights), 16 (those, by area, through a light tree) or 32 (the
+        environment map): the mode the next launch runs in."""
         out = (C.c_uint32 * 2)()
         check(lib().rt_renderer_light_sampling_info(self.h, out))
         return out[0]
 
     def light_sampling_info(self):
         """{'enabled', 'lights'}: whether light sampling is on (in any mode: light_sampling_mode() tells which), and the number of lights in the
-        mode's table — off: of quad lights — (0: the world cannot be light-sampled)."""
+        mode's table — off: of quad lights; "env": the texels of the map — (0: the world cannot be light-sampled)."""
         out = (C.c_uint32 * 2)()
         check(lib().rt_renderer_light_sampling_info(self.h, out))
         return {"enabled": bool(out[0]), "lights": out[1]}
@@ -646,6 +647,12 @@ class Renderer:
         check(lib().rt_renderer_kernel_light_tree(self.h, C.byref(out)))
         return bool(out.value)
 
+    def kernel_env_light(self):
+        """True when the next launch runs the streaming kernel's environment-sampling family (rt_renderer_kernel_env_light): mode "env" is on."""
+        out = C.c_uint32(0)
+        check(lib().rt_renderer_kernel_env_light(self.h, C.byref(out)))
+        return bool(out.value)
+
     def kernel_triangles(self):
         """True when the next launch runs the streaming kernel's triangle family (rt_renderer_kernel_triangles)."""
         out = C.c_uint32()
@@ -710,7 +717,7 @@ class MultiRenderer:
         check(lib().rt_multi_renderer_refine(self.h, n_samples))
 
     def light_sampling(self, on=True):
-        """rt_renderer_light_sampling_enable on every rank; `on` as Renderer.light_sampling takes it."""
+        """rt_renderer_light_sampling_enable on every rank; `on` as Renderer.light_sampling takes it ("env" included)."""
         check(lib().rt_multi_renderer_light_sampling_enable(self.h, light_sampling_mode(on)))
 
     def shading_normals(self, table):
@@ -1007,3 +1014,36 @@ def probe_environment(image, u0, dirs, device=0):
     rgb, texel = np.zeros((n, 3), np.float32), np.zeros(n, np.uint32)
     check(lib().rt_probe_environment(device, n, img.shape[1], img.shape[0], img.ctypes.data, float(u0), dirs, rgb, texel))
     return rgb, texel
+
+
+def environment_distribution(image):
+    """rt_environment_distribution (host only): the sampling distribution of an environment map, image (H, W, 3) ->
+    {'rowc' (H,), 'rowy' (H + 1,), 'colc' (H, W), 'density' (H, W)} float32; RtError for an all-black map"""
+    img = _env_image(image)
+    h, w = img.shape[:2]
+    rowc, rowy, colc, density = np.zeros(h, np.float32), np.zeros(h + 1, np.float32), np.zeros((h, w), np.float32), np.zeros((h, w), np.float32)
+    check(lib().rt_environment_distribution(w, h, img.ctypes.data, rowc, rowy, colc.reshape(-1), density.reshape(-1)))
+    return {"rowc": rowc, "rowy": rowy, "colc": colc, "density": density}
+
+
+def _env_uniforms(uniforms):
+    return np.ascontiguousarray(uniforms, np.float32).reshape(-1, 4)
+
+
+def environment_sample_batch(image, u0, uniforms):
+    """rt_environment_sample_batch (host only): the sampling rule on uniforms (n, 4) = (x1, x2, a, b) in (0, 1] ->
+    (directions (n, 3) float32, drawn texel (n,) uint32 = j * W + i, density of the direction (n,) float32)"""
+    img, u = _env_image(image), _env_uniforms(uniforms)
+    n = len(u)
+    d, texel, density = np.zeros((n, 3), np.float32), np.zeros(n, np.uint32), np.zeros(n, np.float32)
+    check(lib().rt_environment_sample_batch(n, img.shape[1], img.shape[0], img.ctypes.data, float(u0), u.reshape(-1), d.reshape(-1), texel, density))
+    return d, texel, density
+
+
+def probe_environment_sample(image, u0, uniforms, device=0):
+    """rt_probe_environment_sample: environment_sample_batch on the device, one lane per quadruple"""
+    img, u = _env_image(image), _env_uniforms(uniforms)
+    n = len(u)
+    d, texel, density = np.zeros((n, 3), np.float32), np.zeros(n, np.uint32), np.zeros(n, np.float32)
+    check(lib().rt_probe_environment_sample(device, n, img.shape[1], img.shape[0], img.ctypes.data, float(u0), u.reshape(-1), d.reshape(-1), texel, density))
+    return d, texel, density

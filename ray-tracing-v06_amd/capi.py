@@ -96,6 +96,7 @@ SYMBOLS = [
     "rt_renderer_texture_coords_info", "rt_multi_renderer_texture_coords", "rt_probe_tri_uv",
     "rt_scene_set_environment", "rt_scene_environment", "rt_environment_batch", "rt_renderer_environment", "rt_renderer_environment_info",
     "rt_multi_renderer_environment", "rt_probe_environment",
+    "rt_environment_distribution", "rt_environment_sample_batch", "rt_probe_environment_sample", "rt_renderer_kernel_env_light",
 ]
 
 _lib = None
@@ -204,6 +205,10 @@ def lib():
     L.rt_renderer_environment_info.argtypes = [C.c_void_p, C.c_uint32 * 4]
     L.rt_multi_renderer_environment.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_float]
     L.rt_probe_environment.argtypes = [C.c_int, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_float, f32p, f32p, u32p]
+    L.rt_environment_distribution.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, f32p, f32p, f32p, f32p]
+    L.rt_environment_sample_batch.argtypes = [C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_float, f32p, f32p, u32p, f32p]
+    L.rt_probe_environment_sample.argtypes = [C.c_int, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_float, f32p, f32p, u32p, f32p]
+    L.rt_renderer_kernel_env_light.argtypes = [C.c_void_p, P(C.c_uint32)]
     L.rt_scene_set_background.argtypes = [C.c_void_p, C.c_uint32, vec3]
     L.rt_scene_set_perlin.argtypes = [C.c_void_p, C.c_uint64]
     L.rt_scene_set_image.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]

@@ -55,6 +55,7 @@ constexpr uint32_t stream_key(bool exact, bool filter, int world, int ext = 0, b
 constexpr uint32_t RT_KEY_XCHG = 1u << 9;
 constexpr uint32_t RT_KEY_NEE = 1u << 10;   // light sampling (rt_renderer_light_sampling_enable): the NEE form of an EXT >= 1 stack-walk or list key
 constexpr uint32_t RT_KEY_LTREE = 1u << 12; // the light tree (mode RT_LIGHT_SAMPLING_TREE): the LTREE form of a TRI && NEE key; reported by rt_renderer_kernel_light_tree
+constexpr uint32_t RT_KEY_ENVL = 1u << 13;  // environment light sampling (mode RT_LIGHT_SAMPLING_ENV): the ENVL form of an EXT 2 TRI && NEE key; reported by rt_renderer_kernel_env_light
 constexpr uint32_t RT_KEY_TRI = 1u << 11;   // the world has triangles: the TRI form of an EXT >= 1 stack-walk or list key, plain or NEE; not one of rt_renderer_kernel_form's fields
 // a stream key read back into render_kernel_stream's template arguments, in stream_key()'s order, then NEE: what rt_renderer_kernel_form reports
 static void stream_key_fields(uint32_t key, uint32_t out[8]) {
@@ -96,6 +97,8 @@ static const void* stream_kernel_for(uint32_t key) {
     case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NEE: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, true, true>)
 #define RT_KERNEL_LIGHT_TREE(exact, world, ext, big, wide) \
     case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NEE | RT_KEY_LTREE: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, true, true, true>)
+#define RT_KERNEL_ENV_LIGHT(exact, world, ext, big, wide) \
+    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NEE | RT_KEY_ENVL: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, true, true, false, true>)
     switch (key) {   // arguments: exact, filter, world, ext, big, wide, tol
         case RT_KEY_XCHG: return reinterpret_cast<const void*>(&render_kernel_xchg<RT_XCHG_BLOCK>);
         RT_KERNEL(true, false, RT_WORLD_BVH_QUEUE, 2, true, true, false); RT_KERNEL(true, false, RT_WORLD_BVH_QUEUE, 1, true, true, false); RT_KERNEL(true, false, RT_WORLD_BVH_QUEUE, 0, true, true, false);
@@ -129,9 +132,16 @@ static const void* stream_kernel_for(uint32_t key) {
         RT_KERNEL_LIGHT_TREE(false, RT_WORLD_BVH, 2, true, false); RT_KERNEL_LIGHT_TREE(true, RT_WORLD_BVH, 2, true, false); RT_KERNEL_LIGHT_TREE(false, RT_WORLD_BVH, 1, true, false); RT_KERNEL_LIGHT_TREE(true, RT_WORLD_BVH, 1, true, false);
         RT_KERNEL_LIGHT_TREE(true, RT_WORLD_LIST, 2, false, false); RT_KERNEL_LIGHT_TREE(true, RT_WORLD_LIST, 1, false, false);
         RT_KERNEL_LIGHT_TREE(false, RT_WORLD_BVH, 2, false, false); RT_KERNEL_LIGHT_TREE(true, RT_WORLD_BVH, 2, false, false); RT_KERNEL_LIGHT_TREE(false, RT_WORLD_BVH, 1, false, false); RT_KERNEL_LIGHT_TREE(true, RT_WORLD_BVH, 1, false, false);
+        // environment light sampling (§24): the EXT 2 families of TRI && NEE once more (arguments: exact, world, ext, big, wide)
+        RT_KERNEL_ENV_LIGHT(true, RT_WORLD_LIST, 2, true, true);
+        RT_KERNEL_ENV_LIGHT(false, RT_WORLD_BVH, 2, true, true); RT_KERNEL_ENV_LIGHT(true, RT_WORLD_BVH, 2, true, true);
+        RT_KERNEL_ENV_LIGHT(false, RT_WORLD_BVH, 2, true, false); RT_KERNEL_ENV_LIGHT(true, RT_WORLD_BVH, 2, true, false);
+        RT_KERNEL_ENV_LIGHT(true, RT_WORLD_LIST, 2, false, false);
+        RT_KERNEL_ENV_LIGHT(false, RT_WORLD_BVH, 2, false, false); RT_KERNEL_ENV_LIGHT(true, RT_WORLD_BVH, 2, false, false);
         default: return nullptr;
     }
 #undef RT_KERNEL
+#undef RT_KERNEL_ENV_LIGHT
 #undef RT_KERNEL_LIGHT_TREE
 #undef RT_KERNEL_NEE
 #undef RT_KERNEL_TRI
@@ -217,9 +227,10 @@ struct rt_renderer {
     // (mode RT_LIGHT_SAMPLING_TREE, §20, has a family of its own — `key` says which form a table runs — and, behind the table, cdf in the entries and the tree's nodes)
     struct LightTable { uint32_t n = 0; std::vector<uint32_t> kind, index; std::vector<float> area, sphere /* 4 per light */, cdf, nodes /* 8 per node */;
                         std::string refused; DevBuf blob; uint32_t table_vec4 = 0, lds_bytes = 0, blocks_per_cu = 0, key = 0; const void* kernel = nullptr; bool built = false; };
-    struct { uint32_t mode = RT_LIGHT_SAMPLING_OFF; LightTable tab[4]; const void* kernel = nullptr;   // kernel: the current mode's
+    // (mode RT_LIGHT_SAMPLING_ENV, §24, has no table: its slot holds the key, the kernel and the LDS of the plain image, and its launches run on tail.blob)
+    struct { uint32_t mode = RT_LIGHT_SAMPLING_OFF; LightTable tab[5]; const void* kernel = nullptr;   // kernel: the current mode's
              bool on() const { return mode != RT_LIGHT_SAMPLING_OFF; }
-             static uint32_t slot(uint32_t m) { return m == RT_LIGHT_SAMPLING_TREE ? 3u : m == RT_LIGHT_SAMPLING_MESH ? 2u : m - 1u; }   // modes 1, 2, 4, 16
+             static uint32_t slot(uint32_t m) { return m == RT_LIGHT_SAMPLING_ENV ? 4u : m == RT_LIGHT_SAMPLING_TREE ? 3u : m == RT_LIGHT_SAMPLING_MESH ? 2u : m - 1u; }   // modes 1, 2, 4, 16, 32
              const LightTable& cur() const { return tab[slot(mode)]; } } nee;
     // smooth shading (rt_renderer_shading_normals): the table as given (9 floats per triangle of the world), a flat copy for the feature pass, and
     // the images the triangle kernels launch on while it is on — the plain image and, per light-sampling mode already built, the image with that mode's light
@@ -229,13 +240,16 @@ struct rt_renderer {
     struct { bool on = false; uint32_t n_mapped = 0; std::vector<float> host; } uv;
     // the environment map (rt_renderer_environment) of a background-2 world: the image as given (3 floats per texel) and a device buffer of the
     // renderer's own with one float4 per texel; the tail carries only a two-vec4 record that points to it (a 2048 x 1024 map is 32 MiB, and there are up to five tails)
-    struct { bool on = false; uint32_t w = 0, h = 0; float u0 = 0.0f; std::vector<float> host; DevBuf texels; } env;
+    // (§24: while dist_on, the records' fourth lane holds the sampling density and `dist` rowc[H], rowy[H + 1], colc[H W] of rt_environment_distribution)
+    struct { bool on = false, dist_on = false; uint32_t w = 0, h = 0; float u0 = 0.0f; std::vector<float> host; DevBuf texels, dist; } env;
+    bool has_medium = false;   // the world has a constant medium (RT_MAT_ISOTROPIC): mode RT_LIGHT_SAMPLING_ENV refuses it
     // the images with a tail, held while any of the three is on: the plain image's and each built light-sampling mode's
     struct { DevBuf blob, nee_blob[4]; } tail;
     bool tail_on() const { return vn.on || uv.on || env.on; }
     // `src` holds staged_vec4 units of image (and a zero header); dst = the same units, then the header (normals follow at +1 ? 1 : 0, vec4 from the header to
     // the texture coordinates or 0, vec4 from the header to the environment record or 0, -), then the normals if on, then the texture coordinates if on — each
-    // table from a 16-byte boundary — then the environment record if on: (W, H, u0 bits, -), (pointer low, pointer high, -, -)
+    // table from a 16-byte boundary — then the environment record if on: (W, H, u0 bits, -), (texels low, texels high, distribution low, distribution high); the
+    // distribution's words are zero until mode RT_LIGHT_SAMPLING_ENV has built it (§24)
     int image_with_tail(const DevBuf& src, uint32_t staged_vec4, DevBuf& dst) const {
         const size_t vn_vec4 = vn.on ? (vn.host.size() * sizeof(float) + 15u) / 16u : 0u;
         const size_t uv_vec4 = uv.on ? (uv.host.size() * sizeof(float) + 15u) / 16u : 0u;
@@ -248,12 +262,36 @@ struct rt_renderer {
             t[0].z = (uint32_t)at;
             t[at].x = env.w; t[at].y = env.h; std::memcpy(&t[at].z, &env.u0, 4);
             t[at + 1u].x = (uint32_t)ptr; t[at + 1u].y = (uint32_t)(ptr >> 32);
+            const uint64_t dptr = env.dist_on ? (uint64_t)reinterpret_cast<uintptr_t>(env.dist.p) : 0ull;
+            t[at + 1u].z = (uint32_t)dptr; t[at + 1u].w = (uint32_t)(dptr >> 32);
         }
         if (vn.on) std::memcpy(&t[1], vn.host.data(), vn.host.size() * sizeof(float));
         if (uv.on) std::memcpy(&t[1u + vn_vec4], uv.host.data(), uv.host.size() * sizeof(float));
         HIP_TRY(dst.alloc(((size_t)staged_vec4 + t.size()) * sizeof(uint4)));
         HIP_TRY(hipMemcpy(dst.p, src.p, (size_t)staged_vec4 * sizeof(uint4), hipMemcpyDeviceToDevice));
         HIP_TRY(hipMemcpy(dst.as<uint4>() + staged_vec4, t.data(), t.size() * sizeof(uint4), hipMemcpyHostToDevice));
+        return RT_OK;
+    }
+    // The map in env.host (w x h, 3 floats per texel) onto the device: one record per texel, and — with_dist, §24 — the sampling density in the records' fourth lane
+    // and the tables in `dist`.  Into fresh buffers that replace the old ones only when everything has succeeded; the caller has waited for the launches that
+    // read the old ones, and rebuilds the tails.  An all-black map is refused (RT_ERR_INVALID, `who` names the caller) before anything changes.
+    int upload_environment(const char* who, uint32_t w, uint32_t h, const float* rgb, bool with_dist) {
+        const size_t n_texels = (size_t)w * h;
+        std::vector<float> tables, density;
+        if (with_dist) {
+            tables.resize(2u * (size_t)h + 1u + n_texels); density.resize(n_texels);
+            if (const char* why = rt_environment_distribution_refusal(w, h, rgb, tables.data(), tables.data() + h, tables.data() + 2u * (size_t)h + 1u, density.data()))
+                return rt_fail(RT_ERR_INVALID, "%s: %s", who, why);
+        }
+        std::vector<float4> records(n_texels);
+        for (size_t i = 0; i < n_texels; i++) records[i] = make_float4(rgb[3u * i], rgb[3u * i + 1u], rgb[3u * i + 2u], with_dist ? density[i] : 0.0f);
+        DevBuf new_texels, new_dist;
+        HIP_TRY(new_texels.upload(records.data(), n_texels * sizeof(float4)));
+        if (with_dist) HIP_TRY(new_dist.upload(tables.data(), tables.size() * sizeof(float)));
+        env.texels.release(); env.dist.release();
+        std::swap(env.texels.p, new_texels.p); std::swap(env.texels.bytes, new_texels.bytes);
+        std::swap(env.dist.p, new_dist.p); std::swap(env.dist.bytes, new_dist.bytes);
+        env.dist_on = with_dist;
         return RT_OK;
     }
     // the tails anew from vn, uv and env as they stand: none while all are off, else the plain image's and one per light-sampling mode already built
@@ -575,7 +613,8 @@ struct rt_renderer {
         frame_params(p, spp, sl);
         p.scene = scene.packed;
         p.scene.n_top = scene.big ? n_top : 0u;
-        if (nee.on()) { p.scene.blob = (tail_on() ? tail.nee_blob[nee.slot(nee.mode)] : nee.cur().blob).as<uint4>(); p.scene.blob_vec4 += nee.cur().table_vec4; }   // the same image with the light table behind it
+        if (nee.mode == RT_LIGHT_SAMPLING_ENV) p.scene.blob = tail.blob.as<uint4>();   // §24: no table; the plain image with its tail, whose environment record is on while the mode is
+        else if (nee.on()) { p.scene.blob = (tail_on() ? tail.nee_blob[nee.slot(nee.mode)] : nee.cur().blob).as<uint4>(); p.scene.blob_vec4 += nee.cur().table_vec4; }   // the same image with the light table behind it
         else if (tail_on()) p.scene.blob = tail.blob.as<uint4>();   // ... with the vertex normals (§21) and the texture coordinates (§22) behind it
         p.samples = sl.samples.as<float4>();
         p.inner_keep = tune[0] ? tune[0] : 1u; p.shade_min = tune[1]; p.leaf_min = tune[2];
@@ -694,6 +733,8 @@ extern "C" int rt_renderer_create(const rt_render_config* cfg, const rt_camera* 
         else if (t == RT_MAT_LAMBERTIAN_NOISE) r->aov_refused = "a noise texture (RT_MAT_LAMBERTIAN_NOISE)";
         else if (t == RT_MAT_LAMBERTIAN_IMAGE) r->aov_refused = "an image texture (RT_MAT_LAMBERTIAN_IMAGE)";
     }
+    for (uint32_t i = 0; i < world->n_materials && world->materials; i++)
+        if (world->materials[i].type == RT_MAT_ISOTROPIC) r->has_medium = true;
     for (const uint32_t mode : {RT_LIGHT_SAMPLING_QUADS, RT_LIGHT_SAMPLING_ALL, RT_LIGHT_SAMPLING_MESH, RT_LIGHT_SAMPLING_TREE}) {
         rt_renderer::LightTable& t = r->nee.tab[r->nee.slot(mode)];
         const uint32_t cap = mode == RT_LIGHT_SAMPLING_TREE ? RT_MAX_LIGHTS_TREE : RT_MAX_LIGHTS_MESH;
@@ -801,9 +842,41 @@ extern "C" int rt_renderer_set_camera(rt_renderer* r, const rt_camera* cam) {
 // (Cx, Cy, Cz, r), zeros for a quad and for a triangle.
 extern "C" int rt_renderer_light_sampling_enable(rt_renderer* r, uint32_t on) {
     if (!r) return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: null renderer");
-    if (on > RT_LIGHT_SAMPLING_ALL && on != RT_LIGHT_SAMPLING_MESH && on != RT_LIGHT_SAMPLING_TREE)   // 3 is no mode
-        return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: on must be 0 (off), 1 (quad lights), 2 (quad and sphere lights), 4 (quad, sphere and triangle lights) or 16 (those, through a light tree, chosen by area)");
+    if (on > RT_LIGHT_SAMPLING_ALL && on != RT_LIGHT_SAMPLING_MESH && on != RT_LIGHT_SAMPLING_TREE && on != RT_LIGHT_SAMPLING_ENV)   // 3 is no mode
+        return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: on must be 0 (off), 1 (quad lights), 2 (quad and sphere lights), 4 (quad, sphere and triangle lights), 16 (those, through a light tree, chosen by area) or 32 (the environment map)");
     if (on == r->nee.mode) return RT_OK;   // nothing changes, the refinement goes on
+    if (on == RT_LIGHT_SAMPLING_ENV) {   // §24: the map is the one light; no table, a kernel family of its own on the image every launch of this renderer gets
+        rt_renderer::LightTable& t = r->nee.tab[r->nee.slot(on)];
+        if (r->variant < 2 || r->variant == 5 || r->tol)
+            return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: kernel variant %u has no light-sampling form (the baseline kernel 1, the ray exchange 5 and the tolerance mode 6 do not; use variant 0, 2 or 3)", r->tol ? 6u : r->variant);
+        if (r->scene.dw.background != 2u)   // a world of this kind takes the modes of the light tables only, so the message lists them
+            return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: mode 32 samples the environment map of a world with background mode 2 (rt_scene_set_environment); this world's is %u, for which on must be 0 (off), 1 (quad lights), 2 (quad and sphere lights), 4 (quad, sphere and triangle lights) or 16 (those, through a light tree, chosen by area)", r->scene.dw.background);
+        if (r->scene.queue)
+            return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: mode 32: a world with a queue or wide4 traversal renders on lane walks that have no light-sampling form (RT_TRAVERSAL_STACK and lists do)");
+        if (r->has_medium)
+            return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: mode 32: the world has a constant medium (RT_MAT_ISOTROPIC), which the environment estimator does not cover");
+        if (!r->env.on)
+            return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: mode 32: the renderer has no environment map to sample: give it one with rt_renderer_environment first");
+        HIP_TRY(hipSetDevice(r->cfg.device));
+        if (const int rc = wait_last_call(r)) return rc;   // launches already enqueued read the texel records that are replaced below
+        if (!t.built) {
+            const uint32_t key = stream_kernel_key(r->variant, false, r->scene) | RT_KEY_NEE | RT_KEY_TRI | RT_KEY_ENVL;   // a world without triangles is a TRI world too
+            const void* k = stream_kernel_for(key);
+            if (!k) return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: mode 32: this world's kernel has no environment-sampling form");
+            HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r->stream_lds_bytes));
+            t.table_vec4 = 0u;
+            t.lds_bytes = r->stream_lds_bytes;
+            t.blocks_per_cu = r->stream_blocks_per_cu;
+            t.key = key;
+            t.kernel = k;
+            t.built = true;
+        }
+        if (!r->env.dist_on) {   // the distribution of the map as it stands (a map given while the mode is on brings its own: rt_renderer_environment)
+            if (const int rc = r->upload_environment("rt_renderer_light_sampling_enable: mode 32", r->env.w, r->env.h, r->env.host.data(), true)) return rc;
+            if (const int rc = r->rebuild_tails()) return rc;
+        }
+        r->nee.kernel = t.kernel;
+    } else
     if (on) {
         rt_renderer::LightTable& t = r->nee.tab[r->nee.slot(on)];
         if (r->variant < 2 || r->variant == 5 || r->tol)
@@ -862,6 +935,7 @@ extern "C" int rt_renderer_light_sampling_info(rt_renderer* r, uint32_t out[2]) 
     const rt_renderer::LightTable& t = r->nee.tab[r->nee.on() ? r->nee.slot(r->nee.mode) : 0u];
     out[0] = r->nee.mode;
     out[1] = t.refused.empty() ? t.n : 0u;
+    if (r->nee.mode == RT_LIGHT_SAMPLING_ENV) out[1] = r->env.w * r->env.h;   // §24: the texels of the map
     return RT_OK;
 }
 
@@ -956,16 +1030,21 @@ extern "C" int rt_renderer_environment(rt_renderer* r, uint32_t width, uint32_t 
     const size_t n_texels = (size_t)width * height;
     if (off ? !r->env.on : (r->env.on && r->env.w == width && r->env.h == height && std::memcmp(&r->env.u0, &u0, 4) == 0 &&
                             std::memcmp(r->env.host.data(), rgb, n_texels * 3u * sizeof(float)) == 0)) return RT_OK;   // nothing changes, the refinement goes on
+    const bool sampled = r->nee.mode == RT_LIGHT_SAMPLING_ENV;   // §24: the map is being sampled: it cannot leave, and its successor brings a distribution
+    if (sampled && off)
+        return rt_fail(RT_ERR_INVALID, "rt_renderer_environment: the map is being sampled (light-sampling mode 32): switch light sampling off before taking the map away");
     if (const int rc = wait_last_call(r)) return rc;   // launches already enqueued read the images and the texels that are replaced below
+    if (sampled) {   // an all-black successor is refused here, and the old map stays as it is
+        if (const int rc = r->upload_environment("rt_renderer_environment: light-sampling mode 32 is on", width, height, rgb, true)) return rc;
+    }
     r->env.on = false;
     r->refine_done = 0;   // samples lit by another sky belong to another frame
     r->aov_done = 0;
-    r->env.texels.release();
+    if (!sampled) { r->env.texels.release(); r->env.dist.release(); r->env.dist_on = false; }
     r->env.host.clear(); r->env.w = r->env.h = 0u; r->env.u0 = 0.0f;
     if (off) return r->rebuild_tails();   // the vertex normals and the texture coordinates, if on, stay on
-    std::vector<float4> texels(n_texels);
-    for (size_t i = 0; i < n_texels; i++) texels[i] = make_float4(rgb[3u * i], rgb[3u * i + 1u], rgb[3u * i + 2u], 0.0f);
-    if (const hipError_t e = r->env.texels.upload(texels.data(), n_texels * sizeof(float4)); e != hipSuccess) { r->rebuild_tails(); HIP_TRY(e); }
+    if (!sampled)
+        if (const int rc = r->upload_environment("rt_renderer_environment", width, height, rgb, false)) { r->rebuild_tails(); return rc; }
     r->env.host.assign(rgb, rgb + n_texels * 3u);
     r->env.w = width; r->env.h = height; r->env.u0 = u0;
     r->env.on = true;
@@ -1236,6 +1315,13 @@ extern "C" int rt_renderer_kernel_form(rt_renderer* r, uint32_t out[9]) {
 extern "C" int rt_renderer_kernel_triangles(rt_renderer* r, uint32_t* out) {
     if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_kernel_triangles: null argument");
     *out = r->variant >= 2 && ((r->nee.on() ? r->nee.cur().key : stream_kernel_key(r->variant, r->tol, r->scene)) & RT_KEY_TRI) ? 1u : 0u;
+    return RT_OK;
+}
+
+// Whether the NEXT launch runs an instantiation of the environment-sampling family: a query of its own, for the same reason.
+extern "C" int rt_renderer_kernel_env_light(rt_renderer* r, uint32_t* out) {
+    if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_kernel_env_light: null argument");
+    *out = r->nee.on() && (r->nee.cur().key & RT_KEY_ENVL) ? 1u : 0u;
     return RT_OK;
 }
 

@@ -488,6 +488,50 @@ RT_HD f3 environment_value(const float4* texels, uint32_t width, uint32_t height
     return mk3(t.x, t.y, t.z);
 }
 
+// Environment light sampling (rt06.h: RT_LIGHT_SAMPLING_ENV): a direction drawn from the map in proportion to radiance times solid angle, and the
+// density of any direction.  dist = rt_environment_distribution's tables in one array: rowc[H], rowy[H + 1], colc[H * W]; x1, x2, a, b = uniforms in (0, 1].
+// Two binary searches — the smallest row whose running sum passes x1 * A, the smallest column of it whose running sum passes x2 * R_j; a product that rounds up to
+// the total takes the float just below it, so a search always ends on an entry whose sum rose — then a point uniform in the texel's (u, n.y) rectangle, which is
+// uniform in solid angle.  Only + - * / sqrt, comparisons and rt_sinf, each rounded on its own; d is unit up to rounding and is not renormalised.  *out_texel =
+// j * W + i as drawn.  The streaming kernels' ENVL forms, the probe and rt_environment_sample_batch call these two functions; numpy float32 restates them bit for bit.
+RT_HD uint32_t environment_search(const float* c, uint32_t n, float x) {   // the smallest k with c[k] > x, or n - 1
+    uint32_t lo = 0u, hi = n - 1u;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (c[mid] > x) hi = mid;
+        else lo = mid + 1u;
+    }
+    return lo;
+}
+RT_HD f3 environment_sample(const float* dist, uint32_t width, uint32_t height, float u0, float x1, float x2, float a, float b, uint32_t* out_texel) {
+    const float* rowc = dist;
+    const float* rowy = dist + height;
+    const float* colc = dist + 2u * height + 1u;
+    const float A = rowc[height - 1u];
+    float x = x1 * A;
+    if (!(x < A)) x = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, A) - 1u);
+    const uint32_t j = environment_search(rowc, height, x);
+    const float* row = colc + (size_t)j * width;
+    const float R = row[width - 1u];
+    x = x2 * R;
+    if (!(x < R)) x = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, R) - 1u);
+    const uint32_t i = environment_search(row, width, x);
+    const float u = ((float)i + a) / (float)width;
+    const float y1 = rowy[j + 1u];
+    const float y = y1 + (rowy[j] - y1) * b;
+    const float s2 = 1.0f - y * y;
+    const float s = sqrtf(s2 > 0.0f ? s2 : 0.0f);
+    float t = u - u0;
+    if (t < 0.0f) t = t + 1.0f;
+    const float psi = t * 0x1.921fb6p+2f - 0x1.921fb6p+1f;
+    if (out_texel) *out_texel = j * width + i;
+    return mk3(s * rt_sinf(psi + 0x1.921fb6p+0f), y, -(s * rt_sinf(psi)));
+}
+// texels = the renderer's records (r, g, b, density): the density of d is that of the texel §23's lookup puts it in, even where rounding put a drawn d across a border
+RT_HD float environment_density(const float4* texels, uint32_t width, uint32_t height, float u0, f3 d) {
+    return texels[environment_texel_index(width, height, u0, d)].w;
+}
+
 // Material::Scatter — LambertianAbstract (cu_materials.cuh:52-64), MetalAbstract (:77-95),
 // DielectricAbstract (:115-143), LambertianTexture (:27-40)
 // `w`: the world's Perlin tables / image for the two textured extension materials (may be null otherwise)

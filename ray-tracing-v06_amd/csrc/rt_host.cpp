@@ -359,6 +359,44 @@ const char* rt_environment_image_refusal(uint32_t width, uint32_t height, const 
     }
     return nullptr;
 }
+// The sampling distribution of an environment map, built in double and stored as fp32: see rt_environment_distribution in rt06.h.
+const char* rt_environment_distribution_refusal(uint32_t width, uint32_t height, const float* rgb, float* rowc, float* rowy, float* colc, float* density) {
+    const size_t W = width, H = height;
+    const double pi = 3.14159265358979323846;
+    for (size_t j = 0; j <= H; j++) rowy[j] = j == 0 ? 1.0f : j == H ? -1.0f : (float)std::cos(pi * (double)j / (double)H);
+    double total = 0.0;
+    for (size_t j = 0; j < H; j++) {
+        const double h = (double)rowy[j] - (double)rowy[j + 1];
+        double row = 0.0;
+        for (size_t i = 0; i < W; i++) {
+            const float* t = rgb + (j * W + i) * 3u;
+            row += ((0.2126 * (double)t[0] + 0.7152 * (double)t[1]) + 0.0722 * (double)t[2]) * h;
+            colc[j * W + i] = (float)row;
+        }
+        total += row;
+        rowc[j] = (float)total;
+    }
+    const double A = (double)rowc[H - 1];
+    if (!(A > 0.0)) return "the map is all black: nothing to sample";
+    if (!std::isfinite(rowc[H - 1])) return "the map's radiance times solid angle does not sum to a finite fp32 number";
+    for (size_t j = 0; j < H; j++) {   // from the stored values: what the binary searches really draw
+        const double omega = (2.0 * pi / (double)W) * ((double)rowy[j] - (double)rowy[j + 1]);
+        const double Pj = ((double)rowc[j] - (j ? (double)rowc[j - 1] : 0.0)) / A;
+        const double R = (double)colc[j * W + W - 1];
+        for (size_t i = 0; i < W; i++) {
+            const double Pi = R > 0.0 ? ((double)colc[j * W + i] - (i ? (double)colc[j * W + i - 1] : 0.0)) / R : 0.0;
+            density[j * W + i] = (Pj > 0.0 && Pi > 0.0) ? (float)((Pj * Pi) / omega) : 0.0f;
+        }
+    }
+    return nullptr;
+}
+extern "C" int rt_environment_distribution(uint32_t width, uint32_t height, const float* rgb, float* rowc, float* rowy, float* colc, float* density) {
+    if (const char* why = rt_environment_image_refusal(width, height, rgb)) return rt_fail(RT_ERR_INVALID, "rt_environment_distribution: %s", why);
+    if (!rowc || !rowy || !colc || !density) return rt_fail(RT_ERR_INVALID, "rt_environment_distribution: null argument");
+    if (const char* why = rt_environment_distribution_refusal(width, height, rgb, rowc, rowy, colc, density)) return rt_fail(RT_ERR_INVALID, "rt_environment_distribution: %s", why);
+    return RT_OK;
+}
+
 extern "C" int rt_scene_set_environment(rt_scene* s, uint32_t width, uint32_t height, const float* rgb, float rotate_y_degrees) {
     if (!s) return rt_fail(RT_ERR_INVALID, "rt_scene_set_environment: null scene");
     if (const char* why = rt_environment_image_refusal(width, height, rgb)) return rt_fail(RT_ERR_INVALID, "rt_scene_set_environment: %s", why);

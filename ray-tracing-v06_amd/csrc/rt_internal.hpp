@@ -7,3 +7,5 @@
 
 int rt_fail(int code, const char* fmt, ...);
 const char* rt_environment_image_refusal(uint32_t width, uint32_t height, const float* rgb);   // rt_host.cpp: why an environment map is refused, or null
+// rt_host.cpp: rt_environment_distribution's tables of a valid image, or why it has none (an all-black map)
+const char* rt_environment_distribution_refusal(uint32_t width, uint32_t height, const float* rgb, float* rowc, float* rowy, float* colc, float* density);

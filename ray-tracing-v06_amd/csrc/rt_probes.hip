@@ -335,6 +335,63 @@ extern "C" int rt_environment_batch(size_t n, uint32_t width, uint32_t height, c
     }
     return RT_OK;
 }
+// Environment light sampling: what the renderer uploads in mode RT_LIGHT_SAMPLING_ENV — the records with the density in their fourth lane, and
+// rowc | rowy | colc in one array — or the refusal of a bad image, a bad u0, a null argument or an all-black map
+static int environment_sample_args(const char* who, size_t n, uint32_t width, uint32_t height, const float* rgb, float u0, const float* uniforms, float* out_dir, uint32_t* out_texel,
+                                   float* out_density, std::vector<float4>& records, std::vector<float>& tables) {
+    if (const char* why = rt_environment_image_refusal(width, height, rgb)) return rt_fail(RT_ERR_INVALID, "%s: %s", who, why);
+    if (!(u0 >= 0.0f && u0 < 1.0f)) return rt_fail(RT_ERR_INVALID, "%s: u0 must lie in [0, 1)", who);
+    if (n && (!uniforms || !out_dir || !out_texel || !out_density)) return rt_fail(RT_ERR_INVALID, "%s: null argument", who);
+    for (size_t i = 0; i < 4u * n; i++)
+        if (!(uniforms[i] > 0.0f && uniforms[i] <= 1.0f)) return rt_fail(RT_ERR_INVALID, "%s: uniform %zu is outside (0, 1]", who, i);
+    const size_t n_texels = (size_t)width * height;
+    std::vector<float> density(n_texels);
+    tables.resize(2u * (size_t)height + 1u + n_texels);
+    if (const char* why = rt_environment_distribution_refusal(width, height, rgb, tables.data(), tables.data() + height, tables.data() + 2u * (size_t)height + 1u, density.data()))
+        return rt_fail(RT_ERR_INVALID, "%s: %s", who, why);
+    records.resize(n_texels);
+    for (size_t i = 0; i < n_texels; i++) records[i] = make_float4(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2], density[i]);
+    return RT_OK;
+}
+// the sampling rule (environment_sample, environment_density), one lane per quadruple of uniforms
+__global__ void probe_environment_sample_kernel(size_t n, const float4* texels, const float* dist, uint32_t width, uint32_t height, float u0, const float* uniforms,
+                                                float* out_dir, uint32_t* out_texel, float* out_density) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint32_t texel = 0u;
+    const f3 d = environment_sample(dist, width, height, u0, uniforms[4 * i], uniforms[4 * i + 1], uniforms[4 * i + 2], uniforms[4 * i + 3], &texel);
+    st3(out_dir + 3 * i, d);
+    out_texel[i] = texel;
+    out_density[i] = environment_density(texels, width, height, u0, d);
+}
+extern "C" int rt_probe_environment_sample(int device, size_t n, uint32_t width, uint32_t height, const float* rgb, float u0, const float* uniforms, float* out_dir,
+                                           uint32_t* out_texel, float* out_density) {
+    std::vector<float4> records;
+    std::vector<float> tables;
+    if (const int rc = environment_sample_args("rt_probe_environment_sample", n, width, height, rgb, u0, uniforms, out_dir, out_texel, out_density, records, tables)) return rc;
+    if (n == 0) return RT_OK;
+    ProbeRun p(device);
+    auto t = p.in(records.data(), records.size()); auto c = p.in(tables.data(), tables.size());
+    auto u = p.in(uniforms, 4 * n);
+    auto d = p.out(out_dir, 3 * n); auto x = p.out(out_texel, n); auto y = p.out(out_density, n);
+    p.launch(probe_environment_sample_kernel, p.per_case(n), 128, n, t, c, width, height, u0, u, d, x, y);
+    return p.finish();
+}
+// HOST (no GPU): the kernels' environment_sample() and environment_density() over arrays
+extern "C" int rt_environment_sample_batch(size_t n, uint32_t width, uint32_t height, const float* rgb, float u0, const float* uniforms, float* out_dir, uint32_t* out_texel,
+                                           float* out_density) {
+    std::vector<float4> records;
+    std::vector<float> tables;
+    if (const int rc = environment_sample_args("rt_environment_sample_batch", n, width, height, rgb, u0, uniforms, out_dir, out_texel, out_density, records, tables)) return rc;
+    for (size_t i = 0; i < n; i++) {
+        uint32_t texel = 0u;
+        const f3 d = environment_sample(tables.data(), width, height, u0, uniforms[4 * i], uniforms[4 * i + 1], uniforms[4 * i + 2], uniforms[4 * i + 3], &texel);
+        st3(out_dir + 3 * i, d);
+        out_texel[i] = texel;
+        out_density[i] = environment_density(records.data(), width, height, u0, d);
+    }
+    return RT_OK;
+}
 // HOST (no GPU): the kernels' tri_uv() over arrays
 extern "C" int rt_tri_uv_batch(size_t n, const rt_quad* tris, const rt_tri_uvs* uv, const float* rays, const float* t, float* out_uv) {
     if (n && (!tris || !uv || !rays || !t || !out_uv)) return rt_fail(RT_ERR_INVALID, "rt_tri_uv_batch: null argument");

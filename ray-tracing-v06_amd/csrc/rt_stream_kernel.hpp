@@ -181,6 +181,19 @@ __device__ __forceinline__ WideNodeData fetch_wide_node(const char* nodes, const
     return n;
 }
 
+// The tail's environment record: (W, H, u0 bits, -), (texels low, texels high, distribution low, distribution high), read wave-uniformly —
+// every lane sees the same record, so it travels through scalars.  The miss branch keeps its own statement of the first six words; the ENVL forms read all eight here.
+struct EnvRecord { uint32_t w, h; float u0; const float4* texels; const float* dist; };
+__device__ __forceinline__ EnvRecord load_env_record(const uint4* er) {
+    const uint4 e0 = er[0], e1 = er[1];
+    EnvRecord r;
+    r.w = (uint32_t)__builtin_amdgcn_readfirstlane((int)e0.x); r.h = (uint32_t)__builtin_amdgcn_readfirstlane((int)e0.y);
+    r.u0 = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)e0.z));
+    r.texels = reinterpret_cast<const float4*>((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)e1.x) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)e1.y) << 32);
+    r.dist = reinterpret_cast<const float*>((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)e1.z) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)e1.w) << 32);
+    return r;
+}
+
 // EXACT = true : box tests use aabb_intersects() verbatim (IEEE division, GLM min/max).
 // EXACT = false: rays classified "regular" use the 4-instruction correctly-rounded division (two-word reciprocal) and
 //                near/far plane selection by address (rt_fastdiv.hpp) — identical decisions, proven + exhaustively
@@ -217,12 +230,16 @@ __device__ __forceinline__ WideNodeData fetch_wide_node(const char* nodes, const
 // LTREE (mode RT_LIGHT_SAMPLING_TREE; NEE && TRI only, whether or not the world has a triangle): the light is drawn in proportion to its area — a
 //      binary search over the cumulative areas in the entries' fourth lane, A in the header's second — and the density step walks a threaded bounding-volume tree
 //      of the lights, two vec4 per node behind the table ((min.xyz, skip), (max.xyz, leaf)), instead of testing every light: no stack, no indexed private array.
+// ENVL (mode RT_LIGHT_SAMPLING_ENV; EXT == 2 && NEE && TRI only, whether or not the world has a triangle): the light half draws its direction from
+//      the environment map — environment_sample on the distribution the tail's environment record points to — and the light density is the map's own
+//      (environment_density); the light table's pick, point, density loop and tree walk are compiled out.  No shadow ray: the direction is followed.
 template <bool EXACT, bool FILTER, int BLOCK, int WORLD = RT_WORLD_BVH, int EXT = 0, bool BIG = false, bool WIDE = BIG, bool TOL = false, bool NEE = false, bool TRI = false,
-          bool LTREE = false>
+          bool LTREE = false, bool ENVL = false>
 __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(StreamParams p) {
     static_assert(!NEE || (EXT >= 1 && WORLD != RT_WORLD_BVH_QUEUE), "light sampling: worlds with quads, walked by the stack or as a list");
     static_assert(!TRI || (EXT >= 1 && WORLD != RT_WORLD_BVH_QUEUE), "triangles: worlds with quads; a lane walk reads the kind from the flat record");
     static_assert(!LTREE || (NEE && TRI), "the light tree: one family, which knows all three kinds of light");
+    static_assert(!ENVL || (EXT == 2 && NEE && TRI && !LTREE), "environment light sampling: one family of the kernels that look the map up");
     extern __shared__ uint4 lds[];
     const uint32_t tid = threadIdx.x;
     const uint32_t lane = tid & 63u;
@@ -662,6 +679,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                     uint32_t nee_li = 0u, nee_quad = 0u;   // NEE, light half: the light drawn, and its quad index
                     bool to_sphere = false;                // ... or that it is a sphere light (§17), whose point is C + on_unit * r: the draw below serves it too
                     bool to_tri = false;                   // ... or a triangle light (§19, TRI only): a quad's two draws, folded into the triangle
+                    if constexpr (!ENVL)   // (§24: the map is the one light; its draws are made where the direction is)
                     if (NEE && to_light) {
                         const float4* lights = quads + p.scene.n_quads * 5u;
                         const uint32_t n_l = __float_as_uint(lights[0].x);
@@ -695,6 +713,19 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                         scatter_dir = reflect(ray.d, normal) + on_unit * mparam;
                         scattered_ok = !(dot(scatter_dir, normal) < 0 || near_zero(scatter_dir));
                     } else {
+                        if constexpr (ENVL) {
+                            if (to_light) {   // §24: four draws, then the rule; the record through scalars as the miss branch reads it
+                                const EnvRecord er = load_env_record(p.scene.blob + p.scene.blob_vec4 + env_at);
+                                const float x1 = rng.next();
+                                const float x2 = rng.next();
+                                const float ea = rng.next();
+                                const float eb = rng.next();
+                                scatter_dir = environment_sample(er.dist, er.w, er.h, er.u0, x1, x2, ea, eb, nullptr);
+                            } else {
+                                scatter_dir = normal + on_unit;
+                                scattered_ok = !near_zero(scatter_dir);
+                            }
+                        } else
                         if (NEE && to_light) {   // a point of light i, uniform over its area; the direction stays unnormalised
                             if (to_sphere) {
                                 const float4 sc = (quads + p.scene.n_quads * 5u)[1u + nee_li];
@@ -719,11 +750,15 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                             const f3 d = scatter_dir;
                             const float len2 = dot(d, d), len = sqrtf(len2), cosn = dot(normal, d) / len;
                             const float pdf_cos = cosn > 0 ? cosn * 0.318309886f : 0.0f;
+                            float pdf_light = 0.0f;
+                            if constexpr (ENVL) {   // §24: the density of the texel §23's lookup puts d in; no division by a light count
+                                const EnvRecord er = load_env_record(p.scene.blob + p.scene.blob_vec4 + env_at);
+                                pdf_light = environment_density(er.texels, er.w, er.h, er.u0, d);
+                            } else {
                             const float4* lights = quads + p.scene.n_quads * 5u;
                             const uint32_t n_l = __float_as_uint(lights[0].x);
                             Ray lray;
                             lray.o = hit_p; lray.d = d; lray.time = ray.time;
-                            float pdf_light = 0.0f;
                             if constexpr (LTREE) {
                                 // §20: the threaded tree of the lights' padded boxes, in preorder; a leaf met adds mode 4's term without its division by area_j,
                                 // in ascending table position — the linear loop's order with its zeros left out — and the sum is divided by A once
@@ -804,6 +839,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                                 pdf_light = pdf_light + pl_j;
                             }
                             pdf_light = pdf_light / (float)n_l;
+                            }
                             }
                             const float pdf = 0.5f * pdf_cos + 0.5f * pdf_light;
                             if (pdf_cos == 0.0f || !(pdf > 0)) scattered_ok = false;   // below the surface, or a density that is not a number: a failed scatter

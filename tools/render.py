@@ -43,6 +43,11 @@ built again (rt_scene_add_mesh): scaled, rotated about y (degrees), translated, 
 lights the world with an environment map (rt_scene_set_environment) in the place of its background: a Radiance .hdr picture, a float .npy array
 (H, W, 3), an 8-bit .png / .ppm (mapped to [0, 1]) or `sky`, the procedural sky of image_io.sky_environment.  --env-rotate turns it about y (degrees),
 --env-scale multiplies it on the host before upload.
+
+    python tools/render.py --scene three_spheres --env sky --light-sampling-mode env --spp 64 --out out.png
+
+draws half of every Lambertian hit's directions from the map itself, in proportion to radiance times solid angle (RT_LIGHT_SAMPLING_ENV): a small
+bright sun is found at once instead of by the few rays that happen to leave towards it.  Needs --env.
 """
 import argparse, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -62,9 +67,9 @@ ap.add_argument("--until", type=float, default=None, metavar="NOISE", help="with
 ap.add_argument("--denoise", action="store_true", help="with --refine: also write the denoised frame (<out>_denoised.<ext>)")
 ap.add_argument("--aov", default=None, metavar="PREFIX", help="with --refine: write PREFIX_normal.png, PREFIX_depth.png, PREFIX_albedo.png")
 ap.add_argument("--light-sampling", action="store_true", help="next-event estimation over the world's quad lights (rt_renderer_light_sampling_enable)")
-ap.add_argument("--light-sampling-mode", choices=["quads", "all", "mesh", "tree"], default=None,
+ap.add_argument("--light-sampling-mode", choices=["quads", "all", "mesh", "tree", "env"], default=None,
                 help="switch light sampling on in this mode: quads (what --light-sampling selects), all (quad and sphere lights, e.g. --scene cornell_lamp) or "
-                     "mesh (those and triangle lights, e.g. --mesh ... --mesh-material light), tree (mesh's lights, up to 4096, by area through a light tree)")
+                     "mesh (those and triangle lights, e.g. --mesh ... --mesh-material light), tree (mesh's lights, up to 4096, by area through a light tree), env (the environment map of --env alone, by radiance times solid angle)")
 ap.add_argument("--mesh", default=None, metavar="FILE.obj|icosphere:LEVEL|tetrahedron", help="a triangle mesh to place into the scene (rt_scene_add_mesh)")
 ap.add_argument("--mesh-scale", type=float, default=1.0)
 ap.add_argument("--mesh-rotate-y", type=float, default=0.0, metavar="DEGREES")
@@ -80,7 +85,7 @@ ap.add_argument("--env-rotate", type=float, default=0.0, metavar="DEG", help="wi
 ap.add_argument("--env-scale", type=float, default=1.0, metavar="X", help="with --env: multiply the map's radiance, on the host before upload")
 ap.add_argument("--out", default="render.png")
 a = ap.parse_args()
-light_mode = {"quads": 1, "all": 2, "mesh": 4, "tree": 16}.get(a.light_sampling_mode, 1 if a.light_sampling else 0)   # RT_LIGHT_SAMPLING_*
+light_mode = {"quads": 1, "all": 2, "mesh": 4, "tree": 16, "env": 32}.get(a.light_sampling_mode, 1 if a.light_sampling else 0)   # RT_LIGHT_SAMPLING_*
 if a.refine < 0 or (a.until is not None and (a.refine == 0 or a.gpus > 1)):
     ap.error("--until needs --refine STEP > 0 and one GPU (the multi-GPU renderer has no noise figure)")
 if (a.denoise or a.aov) and (a.refine == 0 or a.gpus > 1):
