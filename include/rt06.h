@@ -96,7 +96,8 @@ enum {
     RT_MAT_LAMBERTIAN_NOISE = 6,   /* lambertian(noise_texture(scale)) of "The Next Week" (not in the reference): colour =
                                     * albedo * (1 + sin(param * p.z + 10 * turb(p, 7))) over the world's Perlin tables        */
     RT_MAT_LAMBERTIAN_IMAGE = 7    /* lambertian(image_texture) of "The Next Week": colour = the world's RGB8 image at (u, v) — on a sphere
-                                    * sphere::get_sphere_uv of the normal, on a quad the planar coordinates (alpha, beta) of quad::hit   */
+                                    * sphere::get_sphere_uv of the normal, on a quad the planar coordinates (alpha, beta) of quad::hit;
+                                    * albedo2[0] = which image of the texture table (rt_scene_add_image), 0 = the world's own; param unused */
 };
 typedef struct rt_material {
     float    albedo[3];
@@ -256,7 +257,8 @@ int rt_shading_normal_batch(size_t n, const rt_quad* tris, const rt_tri_normals*
  *   albedo = the image's texel at (tu, tv): clamp to [0, 1], flip v, nearest texel, 1/255 — the lookup every image hit makes.
  * Only fp32 + - *, each rounded on its own.  There is NO sentinel: a triangle without coordinates carries the identity record (0,0), (1,0), (0,1), under which
  * tu = alpha and tv = beta up to the sign of a zero, so the texel is the one the planar lookup picks and "identity table" == "no table" bit for bit.
- * No wrap modes, no filtering, one image per world, none on parallelograms.                                                                                  */
+ * The image, its wrap mode and its filter are the texture table's (below at rt_scene_add_image): the clamp and the nearest texel named above are
+ * the defaults.  No coordinates on parallelograms.                                                                                                           */
 typedef struct rt_tri_uvs { float t0[2], t1[2], t2[2]; } rt_tri_uvs;   /* 24 B */
 /* rt_scene_add_triangle with a texture coordinate per vertex (ta, tb, tc: two floats each, finite; RT_ERR_INVALID otherwise, scene unchanged) and, optionally,
  * a normal per vertex as rt_scene_add_triangle_smooth takes them (na = nb = nc = NULL: a flat triangle)                                                     */
@@ -325,6 +327,42 @@ int rt_scene_set_traversal(rt_scene* s, uint32_t mode);
 int rt_scene_set_perlin(rt_scene* s, uint64_t seed);
 /* the image of image_texture (the book loads earthmap.jpg; any RGB8 array here), copied                     */
 int rt_scene_set_image(rt_scene* s, uint32_t width, uint32_t height, const uint8_t* rgb);
+/* ---- the texture table (not in the reference): several RGB8 images per world, each with a wrap mode and a filter.  Entry 0 is the world's image
+ * of rt_scene_set_image; rt_scene_add_image appends entries 1, 2, ...  An RT_MAT_LAMBERTIAN_IMAGE material names its entry in rt_material.albedo2[0], as an
+ * integer-valued float (0 from every adder before this, so every world means what it meant; not in param, where callers have been free to write anything for
+ * this type).  rt_scene_add_material refuses an index that is negative, not an integer or >= RT_MAX_IMAGES.  This is a change at the edge for callers that
+ * passed an albedo2 for an image material: any value was accepted and ignored before; now it must be an image index (renderer creation checks it too), and
+ * "every world means what it meant" holds for the callers that left albedo2 at zero or NULL, as every adder of this library does.  The device's 16-byte
+ * material record carries albedo2[0] in its fourth lane for this type, where it carried param, which nothing read.  The table travels BESIDE the flat world, as the texture coordinates
+ * do: sizeof(rt_world_flat) is what it was and rt_world_flat.image stays entry 0's texels.
+ * The rule, for entry (W, H, wrap, filter, texels) at the (u, v) a hit has before any clamp (sphere map, planar coordinates or the rule of rt_tri_uvs):
+ *   wrap    : REPEAT: x = x - floor(x) (the result may be exactly 1; an infinite x gives NaN).  Then, under both modes, x = !(x > 0) ? 0 : (x > 1 ? 1 : x), so a
+ *             coordinate that is not a number becomes 0: column 0 and, after the flip, the bottom row.  Then v = 1 - v.
+ *   nearest : i = (int)(u * W), j = (int)(v * H), capped at W - 1, H - 1;  c = the texel's bytes * 0x1.010102p-8f             (image_texel's choice and constant)
+ *   bilinear: x = u * W - 0.5;  x0 = floor(x);  fx = x - x0;  columns x0 and x0 + 1, under CLAMP each clamped into [0, W - 1], under REPEAT -1 -> W - 1 and W -> 0;
+ *             the same in y;  the four texels converted as in nearest;  per channel c = lerp(lerp(c00, c10, fx), lerp(c01, c11, fx), fy),
+ *             lerp(a, b, t) = a + (b - a) * t — this form: a constant image is exactly constant, and fx = 0 returns the texel itself
+ * Only fp32 + - * /, comparisons, float/int conversion and floor, each rounded on its own, no FMA.  CLAMP with NEAREST gives the bits image_texel gives for every
+ * coordinate that is a number.  No mirror wrap, no mip maps, no filtering of the environment map, images on Lambertian image materials only.                    */
+enum { RT_WRAP_CLAMP = 0, RT_WRAP_REPEAT = 1 };
+enum { RT_FILTER_NEAREST = 0, RT_FILTER_BILINEAR = 1 };
+#define RT_MAX_IMAGES 256u
+#define RT_MAX_TABLE_TEXELS (1u << 28)   /* of all the images of one table together */
+/* One entry of the table on the host: `first` = the index of its first texel in the table's texel array (3 bytes per texel, rows from the top, images back to back
+ * in the entries' order).  width = height = 0: an empty entry (entry 0 of a scene without rt_scene_set_image); a material may not use it.                         */
+typedef struct rt_texture { uint32_t width, height, wrap, filter, first; } rt_texture;   /* 20 B */
+/* Appends an image (copied) and returns its index (1, 2, ...) in *out_index.  RT_ERR_INVALID, scene unchanged: what rt_scene_set_image refuses, an unknown wrap
+ * or filter, a 257th image (RT_MAX_IMAGES counts entry 0), more than RT_MAX_TABLE_TEXELS texels in all.                                                          */
+int rt_scene_add_image(rt_scene* s, uint32_t width, uint32_t height, const uint8_t* rgb, uint32_t wrap, uint32_t filter, uint32_t* out_index);
+/* The modes of any entry, 0 included (entry 0 may get its modes before or after, or without, its image).                                                       */
+int rt_scene_image_sampling(rt_scene* s, uint32_t index, uint32_t wrap, uint32_t filter);
+/* The table on the host: *out_n entries (1 + the images added; 0 and NULL pointers for a scene without any image and with default modes) and all texels.  The
+ * pointers stay valid until an image or a mode of the scene is set or the scene is destroyed.                                                                  */
+int rt_scene_textures(const rt_scene* s, const rt_texture** out_records, uint32_t* out_n, const uint8_t** out_texels);
+/* HOST (no GPU): the rule above — out_rgb[3 i ..] = entry index[i] of the table at (u[i], v[i]).  The function the kernels call.  RT_ERR_INVALID: a table
+ * rt_renderer_textures would refuse, an index without an entry.                                                                                                 */
+int rt_texture_lookup_batch(const rt_texture* records, uint32_t n, const uint8_t* texels, const uint32_t* index, const float* u, const float* v, size_t count,
+                            float* out_rgb);
 
 /* BVH_Handle::Factory::BuildBVH_TopDown -> _build_bvh_rec1 (BVH.cu:166-210):
  * median split on the longest axis, leaf size 1, post-order numbering, root =
@@ -716,6 +754,17 @@ int rt_renderer_texture_coords_info(rt_renderer* r, uint32_t out[2]);
 int rt_renderer_environment(rt_renderer* r, uint32_t width, uint32_t height, const float* rgb, float u0);
 /* out[0] = 1 while a map is on, out[1] = width, out[2] = height, out[3] = the bits of u0 */
 int rt_renderer_environment_info(rt_renderer* r, uint32_t out[4]);
+/* The texture table (see rt_scene_add_image) of a renderer: n entries as rt_scene_textures gives them and their texels; or NULL, 0, NULL to turn it off.  Entries
+ * must sit back to back (first = the sum of the sizes before), an entry is empty (0 x 0) or has both dimensions > 0, known modes, n <= RT_MAX_IMAGES.  Copied into
+ * a device buffer of the renderer's own, one 4-byte record (r, g, b, 0) per texel; the images the kernels launch on carry the entries.  With a table on, entry 0
+ * stands for the world's image: every image hit is looked up through the table.  Takes effect at the next launch; an unchanged table is a no-op that keeps the
+ * refinement, a change discards the refinement and feature-buffer state.  RT_ERR_INVALID with a message of its own: a bad table; the baseline kernel (variant 1),
+ * the ray exchange (5) and the tolerance mode (6), which read no table.
+ * rt_renderer_render, the refine calls and their async forms return RT_ERR_INVALID and launch nothing while an image material of the world names an entry the
+ * renderer does not have: any index above 0 without a table, an index past the table's end, an empty entry.                                                      */
+int rt_renderer_textures(rt_renderer* r, const rt_texture* records, uint32_t n, const uint8_t* texels);
+/* out[0] = 1 while a table is on, out[1] = how many entries it has */
+int rt_renderer_textures_info(rt_renderer* r, uint32_t out[2]);
 
 /* ------------------------------------------------------------------ */
 /* Multi-GPU renderer — the same three entry points (Renderer.h:38-46)  */
@@ -747,6 +796,10 @@ int rt_multi_renderer_shading_normals(rt_multi_renderer* m, const rt_tri_normals
 int rt_multi_renderer_texture_coords(rt_multi_renderer* m, const rt_tri_uvs* table, uint32_t n);
 /* rt_renderer_environment on every rank (refused before any rank changes).                                                */
 int rt_multi_renderer_environment(rt_multi_renderer* m, uint32_t width, uint32_t height, const float* rgb, float u0);
+/* rt_renderer_textures on every rank (refused before any rank changes).                                                   */
+int rt_multi_renderer_textures(rt_multi_renderer* m, const rt_texture* records, uint32_t n, const uint8_t* texels);
+/* rt_renderer_textures_info of the ranks (they hold the same table).                                                      */
+int rt_multi_renderer_textures_info(rt_multi_renderer* m, uint32_t out[2]);
 /* Renderer::DownloadRenderbuffer: width*height*4 floats from devices[0].                                                */
 int rt_multi_renderer_download(rt_multi_renderer* m, float* host_rgba, size_t n_floats);
 /* ms of the last render: out[0] host wall-clock of Render(), out[1] slowest rank's kernels (HIP events),
@@ -785,6 +838,9 @@ int rt_probe_shading_normal(int device, const rt_world_flat* world, const rt_tri
 int rt_probe_tri_uv(int device, const rt_world_flat* world, const rt_tri_uvs* table, uint32_t n_table, size_t n, const float* rays, int32_t* out_hit, float* out_uv);
 /* rt_environment_batch on the device, one lane per direction: the map as the renderer holds it (one 16-byte record per texel)                                  */
 int rt_probe_environment(int device, size_t n, uint32_t width, uint32_t height, const float* rgb, float u0, const float* dirs, float* out_rgb, uint32_t* out_texel);
+/* rt_texture_lookup_batch on the device, one lane per lookup: the table as the renderer holds it (one 4-byte record per texel, the entries as vec4)              */
+int rt_probe_texture(int device, const rt_texture* records, uint32_t n, const uint8_t* texels, const uint32_t* index, const float* u, const float* v, size_t count,
+                     float* out_rgb);
 /* rt_environment_sample_batch on the device, one lane per quadruple: the records and the tables as the renderer holds them in mode RT_LIGHT_SAMPLING_ENV        */
 int rt_probe_environment_sample(int device, size_t n, uint32_t width, uint32_t height, const float* rgb, float u0, const float* uniforms, float* out_dir,
                                 uint32_t* out_texel, float* out_density);

@@ -171,6 +171,9 @@ public:
 template <typename G> class ImageTextureAbstract : public GeometryDependantMaterial<G> {   // needs Factory::SetImage; spheres only
 public:
     ImageTextureAbstract() : GeometryDependantMaterial<G>(RT_MAT_LAMBERTIAN_IMAGE, glm::vec3(1.0f), 0.0f) {}
+    // image: which image of the scene (extension) — 0 = the one of SetImage, 1, 2, ... = what SceneBuilder::AddImage returned
+    // (the index rides in rt_material.albedo2[0])
+    explicit ImageTextureAbstract(uint32_t image) : GeometryDependantMaterial<G>(RT_MAT_LAMBERTIAN_IMAGE, glm::vec3(1.0f), 0.0f, glm::vec3((float)image, 0.0f, 0.0f)) {}
 };
 
 // newOnDevice<T>(args...) (cuda_utils.cuh:16-23): the reference cudaMallocs one object and runs a <<<1,1>>>
@@ -355,6 +358,15 @@ public:
     void SetEnvironment(uint32_t width, uint32_t height, const float* rgb, float rotate_y_degrees = 0.0f) {
         check(rt_scene_set_environment(s_, width, height, rgb, rotate_y_degrees), "rt_scene_set_environment");
     }
+    // one more image of the scene (extension; rt_scene_add_image) under a wrap mode (RT_WRAP_*) and a filter (RT_FILTER_*): returns its index for
+    // ImageTextureAbstract(index); Renderer::MakeRenderer pushes the table to the renderer it makes of a BVH world of this scene
+    uint32_t AddImage(uint32_t width, uint32_t height, const uint8_t* rgb, uint32_t wrap = RT_WRAP_CLAMP, uint32_t filter = RT_FILTER_NEAREST) {
+        uint32_t index = 0;
+        check(rt_scene_add_image(s_, width, height, rgb, wrap, filter, &index), "rt_scene_add_image");
+        return index;
+    }
+    // the modes of image `index`, 0 (the image of SetImage) included
+    void SetImageSampling(uint32_t index, uint32_t wrap, uint32_t filter) { check(rt_scene_image_sampling(s_, index, wrap, filter), "rt_scene_image_sampling"); }
     // child reference of a bvh_node tree: >= 0 node, < 0 primitive
     int32_t tree_ref(const Hittable* h) {
         if (h->kind() == Hittable::NODE) {
@@ -601,6 +613,11 @@ class Renderer {
             float u0 = 0.0f;
             rt06::check(rt_scene_environment(static_cast<const BVH*>(world)->scene, &env_w, &env_h, &env, &u0), "rt_scene_environment");
             if (env) made.SetEnvironment(env_w, env_h, env, u0);
+            const rt_texture* tex = nullptr;               // ... and one with more than one image, or a mode that is not the default, its texture table
+            uint32_t n_tex = 0;
+            const uint8_t* texels = nullptr;
+            rt06::check(rt_scene_textures(static_cast<const BVH*>(world)->scene, &tex, &n_tex, &texels), "rt_scene_textures");
+            if (n_tex > 1u || (n_tex == 1u && (tex[0].wrap != RT_WRAP_CLAMP || tex[0].filter != RT_FILTER_NEAREST))) made.SetTextures(tex, n_tex, texels);
         }
         return made;
     }
@@ -698,6 +715,12 @@ public:
     void SetEnvironment(uint32_t width, uint32_t height, const float* rgb, float u0 = 0.0f) {
         if (m.mr) rt06::check(rt_multi_renderer_environment(m.mr, width, height, rgb, u0), "Renderer::SetEnvironment");
         else rt06::check(rt_renderer_environment(m.r, width, height, rgb, u0), "Renderer::SetEnvironment");
+    }
+    // The texture table (extension; rt_renderer_textures): n entries and their texels as rt_scene_textures gives them, or (nullptr, 0, nullptr)
+    // for off; restarts a refinement
+    void SetTextures(const rt_texture* records, uint32_t n, const uint8_t* texels) {
+        if (m.mr) rt06::check(rt_multi_renderer_textures(m.mr, records, n, texels), "Renderer::SetTextures");
+        else rt06::check(rt_renderer_textures(m.r, records, n, texels), "Renderer::SetTextures");
     }
     void SetLightSampling(bool on) {
         if (m.mr) rt06::check(rt_multi_renderer_light_sampling_enable(m.mr, on ? 1u : 0u), "Renderer::SetLightSampling");

@@ -131,9 +131,36 @@ class Scene:
         check(lib().rt_scene_set_image(self.h, rgb.shape[1], rgb.shape[0], rgb.ctypes.data))
         return self
 
-    def ImageTexture(self):
-        """lambertian(image_texture) of "The Next Week" (extension) on spheres (u, v from the normal) and quads (u, v = the planar coordinates of the hit); needs set_image()."""
-        return self.add_material(capi.MAT_LAMBERTIAN_IMAGE, (1, 1, 1))
+    def ImageTexture(self, image=0):
+        """lambertian(image_texture) of "The Next Week" (extension) on spheres (u, v from the normal), quads (u, v = the planar coordinates of the hit) and triangles
+        (DESIGN.md §22).  image: which image of the scene — 0 = the one of set_image(), 1, 2, ... = what add_image() returned."""
+        return self.add_material(capi.MAT_LAMBERTIAN_IMAGE, (1, 1, 1), 0.0, (float(image), 0.0, 0.0))   # the index rides in rt_material.albedo2[0]
+
+    def add_image(self, rgb, wrap="clamp", filter="nearest"):
+        """One more image (extension): uint8 array [H][W][3], row 0 = top, under a wrap mode ("clamp" / "repeat") and a filter ("nearest" /
+        "bilinear").  Returns its index (1, 2, ...) for ImageTexture(image=...); Renderer / MultiRenderer push the table at creation."""
+        rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
+        if rgb.ndim != 3 or rgb.shape[2] != 3:
+            raise ValueError("add_image: the image must have shape (H, W, 3)")
+        out = C.c_uint32()
+        check(lib().rt_scene_add_image(self.h, rgb.shape[1], rgb.shape[0], rgb.ctypes.data, wrap_mode(wrap), filter_mode(filter), C.byref(out)))
+        return out.value
+
+    def image_sampling(self, index, wrap="clamp", filter="nearest"):
+        """The wrap mode and the filter of image `index` of the scene, 0 (the image of set_image()) included (rt_scene_image_sampling)."""
+        check(lib().rt_scene_image_sampling(self.h, index, wrap_mode(wrap), filter_mode(filter)))
+        return self
+
+    def textures(self):
+        """The scene's texture table (rt_scene_textures) as (records, texels): a structured array of capi.TEXTURE_DT, entry 0 = the image of set_image() (0 x 0 when
+        there is none), and all texels (n, 3) uint8, the images back to back; None for a scene without any image and with default modes."""
+        rec, n, tex = C.c_void_p(), C.c_uint32(), C.c_void_p()
+        check(lib().rt_scene_textures(self.h, C.byref(rec), C.byref(n), C.byref(tex)))
+        if n.value == 0:
+            return None
+        records = self._arr(rec.value, n.value, capi.TEXTURE_DT)
+        total = int((records["width"].astype(np.int64) * records["height"]).sum())
+        return records, self._arr(tex.value, total * 3, np.dtype(np.uint8)).reshape(-1, 3)
 
     def MakeBox(self, a, b, mat, rotate_y=0.0, translate=(0, 0, 0)):
         """box(a, b, mat) of "The Next Week" as 6 quads, optionally rotate_y(degrees) then translate; returns the first quad index."""
@@ -331,6 +358,9 @@ class Scene:
             w.texture_coords = self.texture_coords()
         if w.background == 2:                 # likewise the environment map
             w.environment = self.environment()
+        table = self.textures()               # likewise the texture table, when it says more than the flat world does: an image beyond 0 or a mode that is not the default
+        if table is not None and (len(table[0]) > 1 or table[0]["wrap"][0] != capi.WRAP_CLAMP or table[0]["filter"][0] != capi.FILTER_NEAREST):
+            w.textures = table
         return w
 
     def _arr(self, ptr, n, dt):
@@ -429,6 +459,39 @@ def _push_uvs(fn, handle, table):
     return fn(handle, t.ctypes.data if len(t) else None, len(t))
 
 
+def wrap_mode(wrap):
+    """"clamp" / 0, "repeat" / 1 -> RT_WRAP_*"""
+    return {"clamp": capi.WRAP_CLAMP, "repeat": capi.WRAP_REPEAT}.get(wrap, wrap)
+
+
+def filter_mode(filter):
+    """"nearest" / 0, "bilinear" / 1 -> RT_FILTER_*"""
+    return {"nearest": capi.FILTER_NEAREST, "bilinear": capi.FILTER_BILINEAR}.get(filter, filter)
+
+
+def texture_table(entries):
+    """A texture table as (records, texels) from entries (rgb, wrap, filter): rgb a uint8 array [H][W][3] or None for an empty entry; entry 0
+    stands for the world's image.  A (records, texels) pair passes through."""
+    if isinstance(entries, tuple) and len(entries) == 2 and getattr(entries[0], "dtype", None) == capi.TEXTURE_DT:
+        return np.ascontiguousarray(entries[0]), np.ascontiguousarray(entries[1], np.uint8).reshape(-1, 3)
+    records, texels, at = np.zeros(len(entries), capi.TEXTURE_DT), [], 0
+    for k, (rgb, wrap, filt) in enumerate(entries):
+        img = np.zeros((0, 0, 3), np.uint8) if rgb is None else np.ascontiguousarray(rgb, np.uint8)
+        if img.ndim != 3 or img.shape[2] != 3:
+            raise ValueError("texture_table: an image must have shape (H, W, 3)")
+        records[k] = (img.shape[1], img.shape[0], wrap_mode(wrap), filter_mode(filt), at)
+        texels.append(img.reshape(-1, 3))
+        at += img.shape[0] * img.shape[1]
+    return records, (np.concatenate(texels) if texels else np.zeros((0, 3), np.uint8))
+
+
+def _push_textures(fn, handle, table):
+    if table is None:
+        return fn(handle, None, 0, None)
+    records, texels = texture_table(table)
+    return fn(handle, records.ctypes.data if len(records) else None, len(records), texels.ctypes.data if len(texels) else None)
+
+
 def _env_image(image):
     img = np.ascontiguousarray(image, dtype=np.float32)
     if img.ndim != 3 or img.shape[2] != 3:
@@ -463,6 +526,8 @@ class Renderer:
             r.texture_coords(world.texture_coords)
         if getattr(world, "environment", None) is not None:
             r.environment(world.environment[0], u0=world.environment[1])
+        if getattr(world, "textures", None) is not None:
+            r.textures(world.textures)
         return r
 
     def Render(self):
@@ -596,6 +661,17 @@ class Renderer:
         rotation about y as a shift of u; None = off (Render() then refuses).  A change restarts the refinement."""
         check(_push_environment(lib().rt_renderer_environment, self.h, image, u0))
 
+    def textures(self, table):
+        """The texture table from the next launch on (rt_renderer_textures): (records, texels) as Scene.textures() gives it, or a list of
+        (rgb, wrap, filter) entries (api.texture_table); None = off.  A change restarts the refinement; an unchanged table keeps it."""
+        check(_push_textures(lib().rt_renderer_textures, self.h, table))
+
+    def textures_info(self):
+        """{'enabled', 'entries'} of the renderer's texture table."""
+        out = (C.c_uint32 * 2)()
+        check(lib().rt_renderer_textures_info(self.h, out))
+        return {"enabled": bool(out[0]), "entries": out[1]}
+
     def environment_info(self):
         """{'enabled', 'width', 'height', 'u0'} of the renderer's environment map."""
         out = (C.c_uint32 * 4)()
@@ -703,6 +779,8 @@ class MultiRenderer:
             m.texture_coords(world.texture_coords)
         if getattr(world, "environment", None) is not None:
             m.environment(world.environment[0], u0=world.environment[1])
+        if getattr(world, "textures", None) is not None:
+            m.textures(world.textures)
         return m
 
     def Render(self):
@@ -731,6 +809,16 @@ class MultiRenderer:
     def environment(self, image, u0=0.0):
         """rt_renderer_environment on every rank; arguments as Renderer.environment takes them."""
         check(_push_environment(lib().rt_multi_renderer_environment, self.h, image, u0))
+
+    def textures(self, table):
+        """rt_renderer_textures on every rank; `table` as Renderer.textures takes it."""
+        check(_push_textures(lib().rt_multi_renderer_textures, self.h, table))
+
+    def textures_info(self):
+        """{'enabled', 'entries'} of the ranks' texture table (they hold the same one)."""
+        out = (C.c_uint32 * 2)()
+        check(lib().rt_multi_renderer_textures_info(self.h, out))
+        return {"enabled": bool(out[0]), "entries": out[1]}
 
     def DownloadRenderbuffer(self):
         out = np.zeros((self.cfg.height, self.cfg.width, 4), dtype=np.float32)
@@ -994,6 +1082,26 @@ def probe_tri_uv(world, table, rays, device=0):
     hit, uv = np.zeros(n, np.int32), np.zeros((n, 2), np.float32)
     check(lib().rt_probe_tri_uv(device, C.byref(world), tab.ctypes.data if len(tab) else None, len(tab), n, rays, hit, uv))
     return hit, uv
+
+
+def _texture_lookup(fn, table, index, u, v):
+    records, texels = texture_table(table)
+    index, u, v = np.ascontiguousarray(index, np.uint32).reshape(-1), np.ascontiguousarray(u, np.float32).reshape(-1), np.ascontiguousarray(v, np.float32).reshape(-1)
+    if not (len(index) == len(u) == len(v)):
+        raise ValueError("texture lookup: index, u and v must have one length")
+    rgb = np.zeros((len(index), 3), np.float32)
+    check(fn(records.ctypes.data if len(records) else None, len(records), texels.ctypes.data if len(texels) else None, index, u, v, len(index), rgb))
+    return rgb
+
+
+def texture_lookup_batch(table, index, u, v):
+    """rt_texture_lookup_batch (host only): the texture rule — entry index[i] of `table` (as Renderer.textures takes it) at (u[i], v[i]) -> (n, 3) float32"""
+    return _texture_lookup(lib().rt_texture_lookup_batch, table, index, u, v)
+
+
+def probe_texture(table, index, u, v, device=0):
+    """rt_probe_texture: texture_lookup_batch on the device, one lane per lookup"""
+    return _texture_lookup(lambda *a: lib().rt_probe_texture(device, *a), table, index, u, v)
 
 
 def environment_batch(image, u0, dirs):

@@ -32,6 +32,10 @@ PRIM_DT = np.dtype([("c0", "<f4", 3), ("radius", "<f4"), ("c1", "<f4", 3), ("mat
 MAT_DT = np.dtype([("albedo", "<f4", 3), ("param", "<f4"), ("albedo2", "<f4", 3), ("type", "<u4")])
 TRI_NORMALS_DT = np.dtype([("n0", "<f4", 3), ("n1", "<f4", 3), ("n2", "<f4", 3)])   # rt_tri_normals, 36 B
 TRI_UVS_DT = np.dtype([("t0", "<f4", 2), ("t1", "<f4", 2), ("t2", "<f4", 2)])   # rt_tri_uvs, 24 B
+TEXTURE_DT = np.dtype([("width", "<u4"), ("height", "<u4"), ("wrap", "<u4"), ("filter", "<u4"), ("first", "<u4")])   # rt_texture, 20 B
+WRAP_CLAMP, WRAP_REPEAT = 0, 1
+FILTER_NEAREST, FILTER_BILINEAR = 0, 1
+MAX_IMAGES = 256
 QUAD_DT = np.dtype([("Q", "<f4", 3), ("D", "<f4"), ("u", "<f4", 3), ("mat", "<u4"), ("v", "<f4", 3), ("kind", "<u4"),
                     ("normal", "<f4", 3), ("pad1", "<f4"), ("w", "<f4", 3), ("pad2", "<f4")])
 
@@ -97,6 +101,8 @@ SYMBOLS = [
     "rt_scene_set_environment", "rt_scene_environment", "rt_environment_batch", "rt_renderer_environment", "rt_renderer_environment_info",
     "rt_multi_renderer_environment", "rt_probe_environment",
     "rt_environment_distribution", "rt_environment_sample_batch", "rt_probe_environment_sample", "rt_renderer_kernel_env_light",
+    "rt_scene_add_image", "rt_scene_image_sampling", "rt_scene_textures", "rt_texture_lookup_batch", "rt_renderer_textures", "rt_renderer_textures_info",
+    "rt_multi_renderer_textures", "rt_multi_renderer_textures_info", "rt_probe_texture",
 ]
 
 _lib = None
@@ -209,6 +215,15 @@ def lib():
     L.rt_environment_sample_batch.argtypes = [C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_float, f32p, f32p, u32p, f32p]
     L.rt_probe_environment_sample.argtypes = [C.c_int, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_float, f32p, f32p, u32p, f32p]
     L.rt_renderer_kernel_env_light.argtypes = [C.c_void_p, P(C.c_uint32)]
+    L.rt_scene_add_image.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, P(C.c_uint32)]
+    L.rt_scene_image_sampling.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
+    L.rt_scene_textures.argtypes = [C.c_void_p, P(C.c_void_p), P(C.c_uint32), P(C.c_void_p)]
+    L.rt_texture_lookup_batch.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, u32p, f32p, f32p, C.c_size_t, f32p]
+    L.rt_renderer_textures.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+    L.rt_renderer_textures_info.argtypes = [C.c_void_p, C.c_uint32 * 2]
+    L.rt_multi_renderer_textures.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+    L.rt_multi_renderer_textures_info.argtypes = [C.c_void_p, C.c_uint32 * 2]
+    L.rt_probe_texture.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, u32p, f32p, f32p, C.c_size_t, f32p]
     L.rt_scene_set_background.argtypes = [C.c_void_p, C.c_uint32, vec3]
     L.rt_scene_set_perlin.argtypes = [C.c_void_p, C.c_uint64]
     L.rt_scene_set_image.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]

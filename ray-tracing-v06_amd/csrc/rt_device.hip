@@ -243,19 +243,38 @@ struct rt_renderer {
     // (§24: while dist_on, the records' fourth lane holds the sampling density and `dist` rowc[H], rowy[H + 1], colc[H W] of rt_environment_distribution)
     struct { bool on = false, dist_on = false; uint32_t w = 0, h = 0; float u0 = 0.0f; std::vector<float> host; DevBuf texels, dist; } env;
     bool has_medium = false;   // the world has a constant medium (RT_MAT_ISOTROPIC): mode RT_LIGHT_SAMPLING_ENV refuses it
-    // the images with a tail, held while any of the three is on: the plain image's and each built light-sampling mode's
+    // the texture table (rt_renderer_textures): the entries and the texels as given (3 bytes per texel), and a device buffer of the renderer's own
+    // with one dword r | g << 8 | b << 16 per texel, all images back to back; the tail carries (pointer low, pointer high, n, -) and one vec4 per entry
+    struct { bool on = false; std::vector<rt_texture> records; std::vector<uint8_t> host; DevBuf texels; } tex;
+    // the images with a tail, held while any of the four is on: the plain image's and each built light-sampling mode's
     struct { DevBuf blob, nee_blob[4]; } tail;
-    bool tail_on() const { return vn.on || uv.on || env.on; }
+    bool tail_on() const { return vn.on || uv.on || env.on || tex.on; }
+    // whether a launch is refused for its image materials (§25): one of them names an entry (*which) the renderer does not have
+    bool texture_entry_missing(uint32_t* which) const {
+        for (const uint32_t k : scene.image_indices)
+            if (tex.on ? (k >= tex.records.size() || tex.records[k].width == 0u) : k != 0u) { *which = k; return true; }
+        return false;
+    }
     // `src` holds staged_vec4 units of image (and a zero header); dst = the same units, then the header (normals follow at +1 ? 1 : 0, vec4 from the header to
-    // the texture coordinates or 0, vec4 from the header to the environment record or 0, -), then the normals if on, then the texture coordinates if on — each
+    // the texture coordinates or 0, vec4 from the header to the environment record or 0, vec4 from the header to the texture table or 0 — §25, written last), then
+    // the normals if on, then the texture coordinates if on — each
     // table from a 16-byte boundary — then the environment record if on: (W, H, u0 bits, -), (texels low, texels high, distribution low, distribution high); the
     // distribution's words are zero until mode RT_LIGHT_SAMPLING_ENV has built it (§24)
     int image_with_tail(const DevBuf& src, uint32_t staged_vec4, DevBuf& dst) const {
         const size_t vn_vec4 = vn.on ? (vn.host.size() * sizeof(float) + 15u) / 16u : 0u;
         const size_t uv_vec4 = uv.on ? (uv.host.size() * sizeof(float) + 15u) / 16u : 0u;
-        std::vector<uint4> t(1u + vn_vec4 + uv_vec4 + (env.on ? 2u : 0u), make_uint4(0u, 0u, 0u, 0u));
+        const size_t tex_vec4 = tex.on ? 1u + tex.records.size() : 0u;
+        std::vector<uint4> t(1u + vn_vec4 + uv_vec4 + (env.on ? 2u : 0u) + tex_vec4, make_uint4(0u, 0u, 0u, 0u));
         t[0].x = vn.on ? 1u : 0u;
         t[0].y = uv.on ? (uint32_t)(1u + vn_vec4) : 0u;
+        if (tex.on) {   // §25, behind everything else: (texels low, texels high, n, -), then (W, H, wrap | filter << 8, first texel) per entry
+            const size_t at = 1u + vn_vec4 + uv_vec4 + (env.on ? 2u : 0u);
+            const uint64_t ptr = (uint64_t)reinterpret_cast<uintptr_t>(tex.texels.p);
+            t[0].w = (uint32_t)at;
+            t[at] = make_uint4((uint32_t)ptr, (uint32_t)(ptr >> 32), (uint32_t)tex.records.size(), 0u);
+            for (size_t k = 0; k < tex.records.size(); k++)
+                t[at + 1u + k] = make_uint4(tex.records[k].width, tex.records[k].height, tex.records[k].wrap | tex.records[k].filter << 8, tex.records[k].first);
+        }
         if (env.on) {
             const size_t at = 1u + vn_vec4 + uv_vec4;
             const uint64_t ptr = (uint64_t)reinterpret_cast<uintptr_t>(env.texels.p);
@@ -753,7 +772,7 @@ extern "C" int rt_renderer_create(const rt_render_config* cfg, const rt_camera* 
             }
     }
     r->cam = *cam;   // the camera of the first launch; rt_renderer_set_camera replaces it (Renderer.cu:117 reads the caller's camera at every Render())
-    rc = r->scene.upload(world);
+    rc = r->scene.upload(world, true);
     if (rc != RT_OK) { delete r; return rc; }
     r->tm = make_tile_map(cfg->width, cfg->height, cfg->rank, cfg->world_size);
     size_t fb_floats = r->tm.direct ? (size_t)cfg->width * cfg->height * 4 : n_local_pixels(r->tm) * 4;
@@ -785,6 +804,8 @@ extern "C" void rt_renderer_destroy(rt_renderer* r) {
 static int enqueue_call(rt_renderer* r, void* hip_stream, float* d_out, uint32_t first_s, uint32_t n_s, bool refine, bool run_ahead = false) {
     if (r->scene.dw.background == 2u && !r->env.on)   // never launch with a dangling record
         return rt_fail(RT_ERR_INVALID, "the world's background is an environment map (mode 2) and the renderer has none: give it one with rt_renderer_environment before rendering");
+    if (uint32_t k = 0u; r->texture_entry_missing(&k))   // never launch on an index the table does not hold
+        return rt_fail(RT_ERR_INVALID, "an image material of the world names image %u and the renderer's texture table has no such entry: give it one with rt_renderer_textures before rendering", k);
     HIP_TRY(hipSetDevice(r->cfg.device));
     hipStream_t st = (hipStream_t)hip_stream;  // NULL is the HIP null stream, as for any HIP launch
     HIP_TRY(hipEventRecord(r->ev0, st));
@@ -1056,6 +1077,52 @@ extern "C" int rt_renderer_environment_info(rt_renderer* r, uint32_t out[4]) {
     if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_environment_info: null argument");
     out[0] = r->env.on ? 1u : 0u; out[1] = r->env.w; out[2] = r->env.h;
     std::memcpy(&out[3], &r->env.u0, 4);
+    return RT_OK;
+}
+
+// The texture table.  The texels live in a buffer of the renderer's own, one dword per texel; every image it launches on gets the entries in its
+// tail.  Off, image hits read the world's image as ever, and a launch whose materials name an image above 0 is refused (enqueue_call).
+extern "C" int rt_renderer_textures(rt_renderer* r, const rt_texture* records, uint32_t n, const uint8_t* texels) {
+    if (!r) return rt_fail(RT_ERR_INVALID, "rt_renderer_textures: null renderer");
+    const bool off = records == nullptr && n == 0u;
+    uint64_t n_texels = 0;
+    if (!off) {
+        if (r->variant < 2) return rt_fail(RT_ERR_INVALID, "rt_renderer_textures: the baseline kernel (variant 1) reads no texture table; use variant 0, 2 or 3");
+        if (r->variant == 5 || r->tol) return rt_fail(RT_ERR_INVALID, "rt_renderer_textures: kernel variant %u renders no image textures and reads no texture table", r->tol ? 6u : 5u);
+        if (const char* why = rt_texture_table_refusal(records, n, texels, &n_texels)) return rt_fail(RT_ERR_INVALID, "rt_renderer_textures: %s", why);
+    }
+    if (off ? !r->tex.on : (r->tex.on && r->tex.records.size() == n && std::memcmp(r->tex.records.data(), records, n * sizeof(rt_texture)) == 0 &&
+                            (n_texels == 0u || std::memcmp(r->tex.host.data(), texels, n_texels * 3u) == 0))) return RT_OK;   // nothing changes, the refinement goes on
+    DevBuf fresh;   // everything that can fail comes before anything changes
+    if (!off) {
+        std::vector<uint32_t> dwords(n_texels ? n_texels : 1u, 0u);
+        for (uint64_t i = 0; i < n_texels; i++) dwords[i] = (uint32_t)texels[3u * i] | (uint32_t)texels[3u * i + 1u] << 8 | (uint32_t)texels[3u * i + 2u] << 16;
+        HIP_TRY(hipSetDevice(r->cfg.device));
+        HIP_TRY(fresh.upload(dwords.data(), dwords.size() * sizeof(uint32_t)));
+    }
+    if (const int rc = wait_last_call(r)) return rc;   // launches already enqueued read the images and the texels that are replaced below
+    r->refine_done = 0;   // samples textured by other images belong to another frame
+    r->aov_done = 0;
+    std::vector<rt_texture> old_records = std::move(r->tex.records);
+    std::vector<uint8_t> old_host = std::move(r->tex.host);
+    const bool was_on = r->tex.on;
+    std::swap(r->tex.texels.p, fresh.p); std::swap(r->tex.texels.bytes, fresh.bytes);   // `fresh` now holds the old buffer
+    r->tex.on = !off;
+    r->tex.records.clear(); r->tex.host.clear();
+    if (!off) { r->tex.records.assign(records, records + n); r->tex.host.assign(texels, texels + n_texels * 3u); }
+    if (const int rc = r->rebuild_tails()) {   // back to the old table
+        std::swap(r->tex.texels.p, fresh.p); std::swap(r->tex.texels.bytes, fresh.bytes);
+        r->tex.on = was_on; r->tex.records = std::move(old_records); r->tex.host = std::move(old_host);
+        r->rebuild_tails();
+        return rc;
+    }
+    return RT_OK;
+}
+
+extern "C" int rt_renderer_textures_info(rt_renderer* r, uint32_t out[2]) {
+    if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_textures_info: null argument");
+    out[0] = r->tex.on ? 1u : 0u;
+    out[1] = r->tex.on ? (uint32_t)r->tex.records.size() : 0u;
     return RT_OK;
 }
 

@@ -462,6 +462,70 @@ RT_HD f3 image_texel(const uint8_t* image, uint32_t width, uint32_t height, floa
     return mk3((float)px[0] * 0x1.010102p-8f, (float)px[1] * 0x1.010102p-8f, (float)px[2] * 0x1.010102p-8f);
 }
 
+// The texture table (rt06.h: rt_scene_add_image): what image `rec` = (W, H, wrap | filter << 8, first texel) of the table shows at (u, v), the
+// coordinates as image_value, image_value_quad and tri_uv compute them, before any clamp.  texels = one dword r | g << 8 | b << 16 per texel, all images back to
+// back, rows from the top.  Only + - * /, comparisons, float/int conversion and floor, each rounded on its own; a coordinate that is not a number wraps to 0
+// (column 0, the bottom row) on host and device alike.  Under clamp and nearest the texel and its bits are image_texel's for every coordinate that is a number.
+// The streaming kernels, the probe and rt_texture_lookup_batch call this one function; numpy float32 restates it bit for bit.
+RT_HD void sphere_uv(f3 n, float& u, float& v) {   // image_value's coordinates
+    float cy = -n.y;
+    cy = cy < -1.0f ? -1.0f : (cy > 1.0f ? 1.0f : cy);
+    const float theta = rt_acosf(cy);
+    const float phi = rt_atan2f(-n.z, n.x) + 0x1.921fb6p+1f;
+    u = phi / 0x1.921fb6p+2f; v = theta / 0x1.921fb6p+1f;
+}
+RT_HD void quad_uv(f3 Q, f3 u, f3 v, f3 w, f3 hit_p, float& alpha, float& beta) {   // image_value_quad's coordinates
+    const f3 planar = hit_p - Q;
+    alpha = dot(w, cross(planar, v));
+    beta = dot(w, cross(u, planar));
+}
+RT_HD float texture_wrap(float x, bool repeat) {
+    const float frac = x - floorf(x);   // may be exactly 1 (a tiny negative x); infinity gives NaN
+    x = repeat ? frac : x;              // selects, not branches: the shade phase has no scalars to spare for another level of divergence
+    return !(x > 0.0f) ? 0.0f : (x > 1.0f ? 1.0f : x);
+}
+RT_HD f3 texture_texel(const uint32_t* texels, uint32_t at) {
+    const uint32_t t = texels[at];   // one dword load
+    return mk3((float)(t & 255u) * 0x1.010102p-8f, (float)((t >> 8) & 255u) * 0x1.010102p-8f, (float)((t >> 16) & 255u) * 0x1.010102p-8f);
+}
+RT_HD f3 texture_lerp(f3 a, f3 b, float t) { return a + (b - a) * t; }
+// the rule's three parts: wrap and flip; the nearest texel of wrapped coordinates; the bilinear blend of them
+RT_HD void texture_wrap_uv(uint4 rec, float& u, float& v) {
+    const bool repeat = (rec.z & 255u) == RT_WRAP_REPEAT;
+    u = texture_wrap(u, repeat);
+    v = texture_wrap(v, repeat);
+    v = 1.0f - v;   // flip to image coordinates
+}
+RT_HD f3 texture_nearest(const uint32_t* texels, uint4 rec, float u, float v) {
+    const int W = (int)rec.x, H = (int)rec.y;
+    int i = (int)(u * (float)W), j = (int)(v * (float)H);
+    if (i > W - 1) i = W - 1;
+    if (j > H - 1) j = H - 1;
+    return texture_texel(texels, rec.w + (uint32_t)j * rec.x + (uint32_t)i);
+}
+RT_HD f3 texture_bilinear(const uint32_t* texels, uint4 rec, float u, float v) {
+    const int W = (int)rec.x, H = (int)rec.y;
+    const bool repeat = (rec.z & 255u) == RT_WRAP_REPEAT;
+    const float x = u * (float)W - 0.5f, y = v * (float)H - 0.5f;   // in [-1/2, W - 1/2]: texel centres sit on the integers
+    const float x0 = floorf(x), y0 = floorf(y);
+    const float fx = x - x0, fy = y - y0;
+    int i0 = (int)x0, j0 = (int)y0;
+    int i1 = i0 + 1, j1 = j0 + 1;
+    i0 = i0 < 0 ? (repeat ? W - 1 : 0) : i0;
+    i1 = i1 > W - 1 ? (repeat ? 0 : W - 1) : i1;
+    j0 = j0 < 0 ? (repeat ? H - 1 : 0) : j0;
+    j1 = j1 > H - 1 ? (repeat ? 0 : H - 1) : j1;
+    const uint32_t r0 = rec.w + (uint32_t)j0 * rec.x, r1 = rec.w + (uint32_t)j1 * rec.x;
+    const f3 top = texture_lerp(texture_texel(texels, r0 + (uint32_t)i0), texture_texel(texels, r0 + (uint32_t)i1), fx);
+    const f3 bottom = texture_lerp(texture_texel(texels, r1 + (uint32_t)i0), texture_texel(texels, r1 + (uint32_t)i1), fx);
+    return texture_lerp(top, bottom, fy);
+}
+RT_HD f3 texture_value(const uint32_t* texels, uint4 rec, float u, float v) {
+    texture_wrap_uv(rec, u, v);
+    if (((rec.z >> 8) & 255u) != RT_FILTER_BILINEAR) return texture_nearest(texels, rec, u, v);
+    return texture_bilinear(texels, rec, u, v);
+}
+
 // Environment maps (rt06.h: rt_scene_set_environment): what a ray that leaves the world sees.  d = the ray's direction (any length), texels =
 // width x height records (r, g, b, -), row 0 at the top, u0 in [0, 1) = the rotation about y.  image_value's map and constants, the rotation added to u, then
 // image_texel's rule; the clamps are written so that a NaN coordinate lands on texel 0 on host and device alike.  Only + - * / sqrt, comparisons and the two rt_

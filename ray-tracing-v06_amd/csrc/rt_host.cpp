@@ -164,7 +164,14 @@ struct rt_scene {
     std::vector<rt_perlin> perlin;        // 0 or 1 table set (RT_MAT_LAMBERTIAN_NOISE)
     std::vector<uint8_t> image;           // RGB8 (RT_MAT_LAMBERTIAN_IMAGE)
     uint32_t image_w = 0, image_h = 0;
-    std::vector<rt_bvh_node> nodes;       // world nodes (BVH or bvh_node tree)
+    // the texture table: entry 0 = `image` above under image_modes[0]; entries 1.. = more_images; `table` and `table_texels` are what
+    // rt_scene_textures last handed out
+    struct Image { uint32_t w = 0, h = 0; std::vector<uint8_t> rgb; };
+    std::vector<Image> more_images;
+    std::vector<uint32_t> image_wrap = {RT_WRAP_CLAMP}, image_filter = {RT_FILTER_NEAREST};   // one per entry, entry 0 included
+    mutable std::vector<rt_texture> table;
+    mutable std::vector<uint8_t> table_texels;
+    std::vector<rt_bvh_node> nodes;      // world nodes (BVH or bvh_node tree)
     std::vector<rt_bvh_node> tree_nodes;  // bvh_node objects created by rt_scene_add_bvh_node
     uint32_t kind = RT_WORLD_LIST;
     int32_t root = 0;
@@ -185,6 +192,8 @@ extern "C" int rt_scene_add_material(rt_scene* s, uint32_t type, const float alb
     if (!s || !albedo) return rt_fail(RT_ERR_INVALID, "rt_scene_add_material: null argument");
     if (type > RT_MAT_LAMBERTIAN_IMAGE) return rt_fail(RT_ERR_INVALID, "rt_scene_add_material: unknown material type %u", type);
     if (type == RT_MAT_ISOTROPIC && !(param > 0.0f)) return rt_fail(RT_ERR_INVALID, "rt_scene_add_material: a constant medium needs a density > 0");
+    if (type == RT_MAT_LAMBERTIAN_IMAGE && albedo2 && !rt_image_index_ok(albedo2[0]))   // §25: albedo2[0] names the image (param means nothing for this type)
+        return rt_fail(RT_ERR_INVALID, "rt_scene_add_material: an image texture's albedo2[0] is its image index: an integer in [0, %u), not %g", RT_MAX_IMAGES, (double)albedo2[0]);
     rt_material m;
     std::memset(&m, 0, sizeof(m));
     st3(m.albedo, ld3(albedo));
@@ -926,9 +935,78 @@ extern "C" int rt_scene_set_perlin(rt_scene* s, uint64_t seed) {
 extern "C" int rt_scene_set_image(rt_scene* s, uint32_t width, uint32_t height, const uint8_t* rgb) {
     if (!s || !rgb) return rt_fail(RT_ERR_INVALID, "rt_scene_set_image: null argument");
     if (width == 0 || height == 0 || (uint64_t)width * height > (1ull << 26)) return rt_fail(RT_ERR_INVALID, "rt_scene_set_image: bad size %u x %u", width, height);
+    uint64_t total = (uint64_t)width * height;   // §25: the scene's table, this image as its entry 0, stays one a renderer takes
+    for (const rt_scene::Image& im : s->more_images) total += (uint64_t)im.w * im.h;
+    if (total > (uint64_t)RT_MAX_TABLE_TEXELS) return rt_fail(RT_ERR_INVALID, "rt_scene_set_image: with the images added, more than RT_MAX_TABLE_TEXELS (2^28) texels in all");
     s->image.assign(rgb, rgb + (size_t)width * height * 3);
     s->image_w = width;
     s->image_h = height;
+    return RT_OK;
+}
+
+// ---- the texture table ----
+bool rt_image_index_ok(float param) { return param >= 0.0f && param < (float)RT_MAX_IMAGES && param == (float)(uint32_t)param; }
+static const char* sampling_refusal(uint32_t wrap, uint32_t filter) {
+    if (wrap > RT_WRAP_REPEAT) return "unknown wrap mode (RT_WRAP_CLAMP or RT_WRAP_REPEAT)";
+    if (filter > RT_FILTER_BILINEAR) return "unknown filter (RT_FILTER_NEAREST or RT_FILTER_BILINEAR)";
+    return nullptr;
+}
+const char* rt_texture_table_refusal(const rt_texture* records, uint32_t n, const uint8_t* texels, uint64_t* out_texels) {
+    if (!records || n == 0u) return "a table and its count go together";
+    if (n > RT_MAX_IMAGES) return "more than RT_MAX_IMAGES (256) entries";
+    uint64_t at = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const rt_texture& t = records[i];
+        if ((t.width == 0u) != (t.height == 0u)) return "an entry with one dimension zero (an empty entry is 0 x 0)";
+        if ((uint64_t)t.width * t.height > (1ull << 26)) return "an entry of more than 2^26 texels";
+        if (const char* why = sampling_refusal(t.wrap, t.filter)) return why;
+        if ((uint64_t)t.first != at) return "the entries' texels do not sit back to back (first = the sum of the sizes before)";
+        at += (uint64_t)t.width * t.height;
+        if (at > (uint64_t)RT_MAX_TABLE_TEXELS) return "more than RT_MAX_TABLE_TEXELS (2^28) texels in all";
+    }
+    if (at != 0u && !texels) return "null texels";
+    if (out_texels) *out_texels = at;
+    return nullptr;
+}
+extern "C" int rt_scene_add_image(rt_scene* s, uint32_t width, uint32_t height, const uint8_t* rgb, uint32_t wrap, uint32_t filter, uint32_t* out_index) {
+    if (!s || !rgb) return rt_fail(RT_ERR_INVALID, "rt_scene_add_image: null argument");
+    if (width == 0 || height == 0 || (uint64_t)width * height > (1ull << 26)) return rt_fail(RT_ERR_INVALID, "rt_scene_add_image: bad size %u x %u", width, height);
+    if (const char* why = sampling_refusal(wrap, filter)) return rt_fail(RT_ERR_INVALID, "rt_scene_add_image: %s", why);
+    if (1u + s->more_images.size() >= RT_MAX_IMAGES) return rt_fail(RT_ERR_INVALID, "rt_scene_add_image: a scene holds at most RT_MAX_IMAGES (%u) images, entry 0 included", RT_MAX_IMAGES);
+    uint64_t total = (uint64_t)s->image_w * s->image_h + (uint64_t)width * height;
+    for (const rt_scene::Image& im : s->more_images) total += (uint64_t)im.w * im.h;
+    if (total > (uint64_t)RT_MAX_TABLE_TEXELS) return rt_fail(RT_ERR_INVALID, "rt_scene_add_image: more than RT_MAX_TABLE_TEXELS (2^28) texels in all");
+    rt_scene::Image im;
+    im.w = width; im.h = height;
+    im.rgb.assign(rgb, rgb + (size_t)width * height * 3);
+    s->more_images.push_back(std::move(im));
+    s->image_wrap.push_back(wrap); s->image_filter.push_back(filter);
+    if (out_index) *out_index = (uint32_t)s->more_images.size();
+    return RT_OK;
+}
+extern "C" int rt_scene_image_sampling(rt_scene* s, uint32_t index, uint32_t wrap, uint32_t filter) {
+    if (!s) return rt_fail(RT_ERR_INVALID, "rt_scene_image_sampling: null scene");
+    if (index > s->more_images.size()) return rt_fail(RT_ERR_INVALID, "rt_scene_image_sampling: the scene has no image %u", index);
+    if (const char* why = sampling_refusal(wrap, filter)) return rt_fail(RT_ERR_INVALID, "rt_scene_image_sampling: %s", why);
+    s->image_wrap[index] = wrap; s->image_filter[index] = filter;
+    return RT_OK;
+}
+extern "C" int rt_scene_textures(const rt_scene* s, const rt_texture** out_records, uint32_t* out_n, const uint8_t** out_texels) {
+    if (!s || !out_records || !out_n || !out_texels) return rt_fail(RT_ERR_INVALID, "rt_scene_textures: null argument");
+    s->table.clear(); s->table_texels.clear();
+    *out_records = nullptr; *out_n = 0u; *out_texels = nullptr;
+    if (s->image.empty() && s->more_images.empty() && s->image_wrap[0] == RT_WRAP_CLAMP && s->image_filter[0] == RT_FILTER_NEAREST) return RT_OK;
+    uint32_t at = 0u;
+    auto entry = [&](uint32_t w, uint32_t h, const std::vector<uint8_t>& rgb) {
+        const size_t k = s->table.size();
+        s->table.push_back(rt_texture{w, h, s->image_wrap[k], s->image_filter[k], at});
+        s->table_texels.insert(s->table_texels.end(), rgb.begin(), rgb.end());
+        at += w * h;
+    };
+    entry(s->image_w, s->image_h, s->image);
+    for (const rt_scene::Image& im : s->more_images) entry(im.w, im.h, im.rgb);
+    *out_records = s->table.data(); *out_n = (uint32_t)s->table.size();
+    *out_texels = s->table_texels.empty() ? nullptr : s->table_texels.data();
     return RT_OK;
 }
 

@@ -295,6 +295,20 @@ extern "C" int rt_multi_renderer_environment(rt_multi_renderer* m, uint32_t widt
     return RT_OK;
 }
 
+extern "C" int rt_multi_renderer_textures(rt_multi_renderer* m, const rt_texture* records, uint32_t n, const uint8_t* texels) {
+    if (!m) return rt_fail(RT_ERR_INVALID, "rt_multi_renderer_textures: null renderer");
+    for (rt_renderer* r : m->parts) {   // every rank holds the same world: the first refuses what any would, before any part changes
+        const int rc = rt_renderer_textures(r, records, n, texels);
+        if (rc != RT_OK) return rc;
+    }
+    return RT_OK;
+}
+
+extern "C" int rt_multi_renderer_textures_info(rt_multi_renderer* m, uint32_t out[2]) {   // every rank holds the same table: rank 0 answers
+    if (!m || !out || m->parts.empty()) return rt_fail(RT_ERR_INVALID, "rt_multi_renderer_textures_info: null argument");
+    return rt_renderer_textures_info(m->parts[0], out);
+}
+
 extern "C" int rt_multi_renderer_download(rt_multi_renderer* m, float* host_rgba, size_t n_floats) {
     if (!m || !host_rgba) return rt_fail(RT_ERR_INVALID, "rt_multi_renderer_download: null argument");
     const size_t need = (size_t)m->width * m->height * 4;

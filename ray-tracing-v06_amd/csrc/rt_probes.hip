@@ -89,6 +89,12 @@ __global__ void probe_environment_kernel(size_t n, const float4* texels, uint32_
     out_texel[i] = environment_texel_index(width, height, u0, d);
     st3(out_rgb + 3 * i, environment_value(texels, width, height, u0, d));
 }
+// the texture rule (texture_value), one lane per lookup, on the table as the renderer holds it; the host has checked every index
+__global__ void probe_texture_kernel(size_t n, const uint32_t* texels, const uint4* entries, const uint32_t* index, const float* u, const float* v, float* out_rgb) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    st3(out_rgb + 3 * i, texture_value(texels, entries[index[i]], u[i], v[i]));
+}
 // SphereHittable / MovingSphereHittable::ClosestIntersection on one sphere per ray, rec.distance preset by the caller: the leaf
 // test every traversal calls (prim_closest_intersection), as a plain sphere (material 0 = a Lambertian, the moving bit kept)
 __global__ void probe_sphere_hit_kernel(size_t n, const rt_prim* prims, const rt_material* mat, const float* rays, const float* preset,
@@ -392,6 +398,42 @@ extern "C" int rt_environment_sample_batch(size_t n, uint32_t width, uint32_t he
     }
     return RT_OK;
 }
+// The texture table in the renderer's form: one dword per texel, one vec4 per entry
+struct TextureTable { std::vector<uint32_t> dwords; std::vector<uint4> entries; };
+static int texture_table_args(const char* who, const rt_texture* records, uint32_t n, const uint8_t* texels, const uint32_t* index, const float* u, const float* v,
+                              size_t count, float* out_rgb, TextureTable& t) {
+    uint64_t n_texels = 0;
+    if (const char* why = rt_texture_table_refusal(records, n, texels, &n_texels)) return rt_fail(RT_ERR_INVALID, "%s: %s", who, why);
+    if (count && (!index || !u || !v || !out_rgb)) return rt_fail(RT_ERR_INVALID, "%s: null argument", who);
+    for (size_t i = 0; i < count; i++)
+        if (index[i] >= n || records[index[i]].width == 0u) return rt_fail(RT_ERR_INVALID, "%s: lookup %zu: the table has no entry %u", who, i, index[i]);
+    t.dwords.assign(n_texels ? n_texels : 1u, 0u);
+    for (uint64_t i = 0; i < n_texels; i++) t.dwords[i] = (uint32_t)texels[3u * i] | (uint32_t)texels[3u * i + 1u] << 8 | (uint32_t)texels[3u * i + 2u] << 16;
+    t.entries.resize(n);
+    for (uint32_t k = 0; k < n; k++) t.entries[k] = make_uint4(records[k].width, records[k].height, records[k].wrap | records[k].filter << 8, records[k].first);
+    return RT_OK;
+}
+extern "C" int rt_probe_texture(int device, const rt_texture* records, uint32_t n, const uint8_t* texels, const uint32_t* index, const float* u, const float* v,
+                                size_t count, float* out_rgb) {
+    TextureTable t;
+    if (const int rc = texture_table_args("rt_probe_texture", records, n, texels, index, u, v, count, out_rgb, t)) return rc;
+    if (count == 0) return RT_OK;
+    ProbeRun p(device);
+    auto dw = p.in(t.dwords.data(), t.dwords.size());
+    auto en = p.in(t.entries.data(), t.entries.size());
+    auto ix = p.in(index, count); auto du = p.in(u, count); auto dv = p.in(v, count);
+    auto o = p.out(out_rgb, 3 * count);
+    p.launch(probe_texture_kernel, p.per_case(count), 128, count, dw, en, ix, du, dv, o);
+    return p.finish();
+}
+// HOST (no GPU): the kernels' texture_value() over arrays
+extern "C" int rt_texture_lookup_batch(const rt_texture* records, uint32_t n, const uint8_t* texels, const uint32_t* index, const float* u, const float* v, size_t count,
+                                       float* out_rgb) {
+    TextureTable t;
+    if (const int rc = texture_table_args("rt_texture_lookup_batch", records, n, texels, index, u, v, count, out_rgb, t)) return rc;
+    for (size_t i = 0; i < count; i++) st3(out_rgb + 3 * i, texture_value(t.dwords.data(), t.entries[index[i]], u[i], v[i]));
+    return RT_OK;
+}
 // HOST (no GPU): the kernels' tri_uv() over arrays
 extern "C" int rt_tri_uv_batch(size_t n, const rt_quad* tris, const rt_tri_uvs* uv, const float* rays, const float* t, float* out_uv) {
     if (n && (!tris || !uv || !rays || !t || !out_uv)) return rt_fail(RT_ERR_INVALID, "rt_tri_uv_batch: null argument");
@@ -507,6 +549,9 @@ extern "C" int rt_probe_radiance(const rt_render_config* cfg, const rt_camera* c
         if (keys[2 * i] >= cfg->width * cfg->height) return rt_fail(RT_ERR_INVALID, "rt_probe_radiance: key %zu: pixel out of range", i);
     if (world && world->background == 2u)
         return rt_fail(RT_ERR_INVALID, "rt_probe_radiance: the probe runs sample_world, which looks no environment map up (background mode 2); rt_probe_environment probes the map");
+    for (uint32_t i = 0; world && world->materials && i < world->n_materials; i++)
+        if (world->materials[i].type == RT_MAT_LAMBERTIAN_IMAGE && world->materials[i].albedo2[0] != 0.0f)
+            return rt_fail(RT_ERR_INVALID, "rt_probe_radiance: the probe runs sample_world, which reads no texture table (material %u names an image other than 0); rt_probe_texture probes the table", i);
     ProbeRun p(cfg->device);
     DeviceScene sc;
     if (p.ok()) p.rc = sc.upload(world);

@@ -98,6 +98,7 @@ struct DeviceScene {
     DevBuf nodes, prims, mats, blob, quads, perlin, image, error_flag;
     bool extended = false;  // quads, an emissive material or a constant background: beyond the reference's feature set
     bool textured = false;  // a Perlin or image material: the EXT = 2 kernels
+    std::vector<uint32_t> image_indices;   // §25: the image each RT_MAT_LAMBERTIAN_IMAGE material names, in the materials' order
     DeviceWorld dw{};
     PackedSceneRef packed{};  // valid when has_packed
     bool has_packed = false;
@@ -203,7 +204,8 @@ struct DeviceScene {
         float4* m16 = ext + w->n_prims;
         for (uint32_t i = 0; i < w->n_materials; i++) {
             const rt_material& m = w->materials[i];
-            m16[i] = make_float4(m.albedo[0], m.albedo[1], m.albedo[2], m.param);
+            // an image material's fourth lane is its image index (albedo2[0]): its param means nothing and callers have written anything there
+            m16[i] = make_float4(m.albedo[0], m.albedo[1], m.albedo[2], m.type == RT_MAT_LAMBERTIAN_IMAGE ? m.albedo2[0] : m.param);
         }
         float4* qd = reinterpret_cast<float4*>(host.data()) + quads_at;
         for (uint32_t i = 0; i < w->n_quads; i++) {
@@ -236,7 +238,8 @@ struct DeviceScene {
         has_packed = true;
         return RT_OK;
     }
-    int upload(const rt_world_flat* w) {
+    // table_images: the caller reads image materials through a texture table (a renderer); the probes read the world's own image and nothing else
+    int upload(const rt_world_flat* w, bool table_images = false) {
         if (!w) return rt_fail(RT_ERR_INVALID, "null world");
         if (w->kind > RT_WORLD_NODE_TREE) return rt_fail(RT_ERR_INVALID, "unknown world kind %u", w->kind);
         if ((w->n_prims == 0 || !w->prims) && (w->n_quads == 0 || !w->quads)) return rt_fail(RT_ERR_INVALID, "world has no primitives");
@@ -259,11 +262,21 @@ struct DeviceScene {
         }
         extended = w->n_quads != 0 || w->background != 0;
         textured = w->background == 2u;   // an environment map is looked up by the EXT = 2 kernels: the world is theirs from creation
+        image_indices.clear();
         for (uint32_t i = 0; i < w->n_materials; i++) {
             if (w->materials[i].type > RT_MAT_LAMBERTIAN_IMAGE) return rt_fail(RT_ERR_INVALID, "material %u: unknown type", i);
             if (w->materials[i].type == RT_MAT_LAMBERTIAN_NOISE && !w->perlin) return rt_fail(RT_ERR_INVALID, "material %u is a noise texture but the world has no Perlin tables (rt_scene_set_perlin)", i);
-            if (w->materials[i].type == RT_MAT_LAMBERTIAN_IMAGE && (!w->image || w->image_width == 0 || w->image_height == 0))
-                return rt_fail(RT_ERR_INVALID, "material %u is an image texture but the world has no image (rt_scene_set_image)", i);
+            if (w->materials[i].type == RT_MAT_LAMBERTIAN_IMAGE) {   // §25: albedo2[0] names the image; param means nothing here
+                const float index = w->materials[i].albedo2[0];
+                if (!rt_image_index_ok(index))
+                    return rt_fail(RT_ERR_INVALID, "material %u is an image texture whose albedo2[0] is no image index (an integer in [0, %u))", i, RT_MAX_IMAGES);
+                // an image above 0 comes with the renderer's texture table (a launch without its entry is refused); image 0 is the world's own
+                if (index != 0.0f && !table_images)
+                    return rt_fail(RT_ERR_INVALID, "material %u names image %u of a texture table, and the probes read the world's own image only (rt_probe_texture probes the table)", i, (uint32_t)index);
+                if (index == 0.0f && (!w->image || w->image_width == 0 || w->image_height == 0))
+                    return rt_fail(RT_ERR_INVALID, "material %u is an image texture but the world has no image (rt_scene_set_image)", i);
+                image_indices.push_back((uint32_t)index);
+            }
             if (w->materials[i].type == RT_MAT_ISOTROPIC && !(w->materials[i].param > 0.0f)) return rt_fail(RT_ERR_INVALID, "material %u: a constant medium needs a density > 0", i);
             if (w->materials[i].type >= RT_MAT_DIFFUSE_LIGHT) extended = true;
             if (w->materials[i].type >= RT_MAT_LAMBERTIAN_NOISE) textured = true;

@@ -194,6 +194,15 @@ __device__ __forceinline__ EnvRecord load_env_record(const uint4* er) {
     return r;
 }
 
+// The tail's texture table at tt: (texels low, texels high, n, -), then one vec4 per image; entry `image` at (u, v) by texture_value.  Inlined:
+// behind a __noinline__ call — the whole of it, or its bilinear part alone — most EXT 2 kernels take 4 to 20 bytes of scratch more (EXPERIMENTS.md E17).  The header is the same for every
+// lane and goes through scalars; the entry is loaded per lane, since lanes may sit on different images.
+__device__ __forceinline__ f3 texture_table_value(const uint4* tt, uint32_t image, float u, float v) {
+    const uint4 th = tt[0];
+    const uint64_t texels = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)th.x) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)th.y) << 32;
+    return texture_value(reinterpret_cast<const uint32_t*>(texels), tt[1u + image], u, v);
+}
+
 // EXACT = true : box tests use aabb_intersects() verbatim (IEEE division, GLM min/max).
 // EXACT = false: rays classified "regular" use the 4-instruction correctly-rounded division (two-word reciprocal) and
 //                near/far plane selection by address (rt_fastdiv.hpp) — identical decisions, proven + exhaustively
@@ -280,6 +289,9 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
     // 0 = none.  The renderer launches a background-2 world only with a record.
     uint32_t env_at = 0u;
     if constexpr (EXT >= 2) env_at = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.scene.blob[p.scene.blob_vec4].z);
+    // §25, EXT >= 2 only: the same header's .w = how many vec4 behind the header the texture table lies — (texels low, texels high, n, -), then one vec4
+    // (W, H, wrap | filter << 8, first texel) per image — 0 = none.  The renderer launches only when every image material's index has an entry.  That word is
+    // NOT read here: a scalar kept live across the path loop cost every EXT 2 kernel spills (EXPERIMENTS.md E17); the image hit reads it where it needs it.
     const f3 root_min = mk3(p.scene.root_min[0], p.scene.root_min[1], p.scene.root_min[2]);
     const f3 root_max = mk3(p.scene.root_max[0], p.scene.root_max[1], p.scene.root_max[2]);
 
@@ -850,22 +862,24 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                             albedo = checker_value(albedo, mk3(mg.albedo2[0], mg.albedo2[1], mg.albedo2[2]), mparam, hit_p);
                         }
                         if (EXT >= 2 && mtype == RT_MAT_LAMBERTIAN_NOISE) albedo = noise_value(p.scene.perlin, albedo, mparam, hit_p);
-                        if (EXT >= 2 && mtype == RT_MAT_LAMBERTIAN_IMAGE) {
-                            if ((uint32_t)rec_code >= p.scene.sphere_codes) {   // on a quad: (u, v) = the planar coordinates of the hit
+                        if (EXT >= 2 && mtype == RT_MAT_LAMBERTIAN_IMAGE) {   // (u, v) three ways, then the world's image or — §25 — the material's entry of the texture table
+                            float tu, tv;
+                            if ((uint32_t)rec_code >= p.scene.sphere_codes) {   // on a quad: the planar coordinates of the hit
                                 const uint32_t qi = (uint32_t)rec_code - p.scene.sphere_codes;
                                 const float4* qd = quads + qi * 4u;
                                 const float4 a0 = qd[0], a1 = qd[1], a2 = qd[2], a3 = qd[3];
                                 if (TRI && uv_at != 0u && qi >= p.scene.n_plain_quads) {   // §22: a triangle under a table of texture coordinates weighs its vertices' (u, v)
                                     const float* tr = reinterpret_cast<const float*>(p.scene.blob + p.scene.blob_vec4 + uv_at) + (size_t)(qi - p.scene.n_plain_quads) * 6u;
                                     const float t0[2] = {tr[0], tr[1]}, t1[2] = {tr[2], tr[3]}, t2[2] = {tr[4], tr[5]};
-                                    albedo = image_value_tri(p.scene.image, p.scene.image_w, p.scene.image_h, mk3(a0.x, a0.y, a0.z), mk3(a1.x, a1.y, a1.z),
-                                                             mk3(a1.w, a2.x, a2.y), mk3(a3.y, a3.z, a3.w), t0, t1, t2, hit_p);
+                                    tri_uv(mk3(a0.x, a0.y, a0.z), mk3(a1.x, a1.y, a1.z), mk3(a1.w, a2.x, a2.y), mk3(a3.y, a3.z, a3.w), t0, t1, t2, hit_p, tu, tv);
                                 } else
-                                albedo = image_value_quad(p.scene.image, p.scene.image_w, p.scene.image_h, mk3(a0.x, a0.y, a0.z), mk3(a1.x, a1.y, a1.z),
-                                                          mk3(a1.w, a2.x, a2.y), mk3(a3.y, a3.z, a3.w), hit_p);
+                                quad_uv(mk3(a0.x, a0.y, a0.z), mk3(a1.x, a1.y, a1.z), mk3(a1.w, a2.x, a2.y), mk3(a3.y, a3.z, a3.w), hit_p, tu, tv);
                             } else {
-                                albedo = image_value(p.scene.image, p.scene.image_w, p.scene.image_h, normal);
+                                sphere_uv(normal, tu, tv);
                             }
+                            const uint32_t tex_here = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.scene.blob[p.scene.blob_vec4].w);   // the tail header's fourth word: wave-uniform
+                            if (tex_here != 0u) albedo = texture_table_value(p.scene.blob + p.scene.blob_vec4 + tex_here, (uint32_t)mparam, tu, tv);
+                            else albedo = image_texel(p.scene.image, p.scene.image_w, p.scene.image_h, tu, tv);
                         }
                     }
                 }

@@ -3,7 +3,8 @@
 Every function returns (vertices float32 (n, 3), faces uint32 (m, 3)) but the ones that say otherwise.  load_obj ignores a file's normals; load_obj_normals
 reads them, vertex_normals makes area-weighted ones for a mesh without, icosphere_normals gives the sphere's own (smooth shading).  load_obj_uvs
 reads a file's texture coordinates, uv_sphere makes a sphere with the ones an image-textured sphere has; without any a triangle takes them from
-its own plane.
+its own plane.  load_obj_materials reads a file's `usemtl` groups and `mtllib` names, load_mtl the `Kd` and `map_Kd` of an MTL file (the scene's
+texture table).
 """
 import numpy as np
 
@@ -145,6 +146,55 @@ def load_obj_uvs(path):
     if not uvs or not complete:
         return v, fa, None, None
     return v, fa, np.array(uvs, np.float32).reshape(-1, 2), np.array(uv_faces, np.uint32).reshape(-1, 3)
+
+
+def load_obj_materials(path):
+    """The material groups of a Wavefront OBJ file: (names, libraries) — per triangle of load_obj's faces (a polygon's fan shares one) the name its `usemtl`
+    line gave it, None before the first; and the file names of the `mtllib` lines in order.  Nothing else is read."""
+    names, libraries, current = [], [], None
+    with open(path, "r", encoding="utf-8", errors="replace") as f:
+        for lineno, line in enumerate(f, 1):
+            parts = line.split("#", 1)[0].split()
+            if not parts:
+                continue
+            if parts[0] == "usemtl":
+                current = parts[1] if len(parts) > 1 else None
+            elif parts[0] == "mtllib":
+                libraries.extend(parts[1:])
+            elif parts[0] == "f":
+                if len(parts) < 4:
+                    raise ValueError(f"{path}:{lineno}: a face needs at least three corners")
+                names.extend([current] * (len(parts) - 3))
+    return names, libraries
+
+
+def load_mtl(path):
+    """`newmtl`, `Kd` and `map_Kd` of a Wavefront MTL file: {name: {"Kd": (r, g, b) | None, "map_Kd": path | None}} in the file's order; the image's name is
+    resolved beside the file, options in front of it (-s, -o, ...) are skipped.  Nothing else of MTL is read."""
+    import os
+    out, current = {}, None
+    with open(path, "r", encoding="utf-8", errors="replace") as f:
+        for lineno, line in enumerate(f, 1):
+            parts = line.split("#", 1)[0].split()
+            if not parts:
+                continue
+            where = f"{path}:{lineno}"
+            if parts[0] == "newmtl":
+                if len(parts) < 2:
+                    raise ValueError(f"{where}: newmtl needs a name")
+                current = out.setdefault(parts[1], {"Kd": None, "map_Kd": None})
+            elif parts[0] in ("Kd", "map_Kd"):
+                if current is None:
+                    raise ValueError(f"{where}: {parts[0]} before any newmtl")
+                if parts[0] == "Kd":
+                    if len(parts) < 4:
+                        raise ValueError(f"{where}: Kd needs three values")
+                    current["Kd"] = (float(parts[1]), float(parts[2]), float(parts[3]))
+                else:
+                    if len(parts) < 2:
+                        raise ValueError(f"{where}: map_Kd needs a file name")
+                    current["map_Kd"] = os.path.join(os.path.dirname(os.path.abspath(path)), *parts[-1].replace("\\", "/").split("/"))
+    return out
 
 
 def uv_sphere(n_lon, n_lat):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Differential fuzz campaign: random worlds (spheres, moving spheres, quads, triangles and meshes, lights, media, textures; every builder; LDS
 and global-memory paths; three cameras) rendered on the GPU and by the CPU oracle, compared bit for bit.
-    python tools/fuzz_campaign.py --seeds 200 [--first 0] [--no-triangles] [--mesh-lights] [--light-tree] [--texture-coords]
+    python tools/fuzz_campaign.py --seeds 200 [--first 0] [--no-triangles] [--mesh-lights] [--light-tree] [--texture-coords] [--textures]
 Prints one line per failure and a summary; exit code 1 if anything differed.  The triangles of a world come from a generator of their own, so the rest of a seed's
 world is what it was before the fuzzer made triangles, and --no-triangles renders exactly those earlier worlds.  Importing this file starts nothing:
 world_of_seed() builds a seed's world on the host, without a device.  --mesh-lights (off by default: the recorded campaigns ran without it) also renders every
@@ -34,6 +34,7 @@ def parse_args(argv=None):
     ap.add_argument("--no-triangles", action="store_true", help="the worlds as they were before the fuzzer made triangles, byte for byte")
     ap.add_argument("--light-tree", action="store_true", help="also render the worlds that light-sampling mode 16 (the light tree, chosen by area) accepts in that mode: both memory forms, and the twin (tests/_light_tree_twin.py) where it follows")
     ap.add_argument("--mesh-lights", action="store_true", help="also render the worlds that light-sampling mode 4 (triangle and mesh lights) accepts in that mode: both memory forms, and the twin where it follows")
+    ap.add_argument("--textures", action="store_true", help="also render the worlds with an image under a texture table of several random images and random modes: the world's image under clamp / nearest must be the oracle's frame, and under another mode pair both memory forms must agree")
     ap.add_argument("--texture-coords", action="store_true", help="also render the worlds with an image and triangles under a table of random texture coordinates on random triangles: both memory forms must agree, and the identity table must be the oracle's frame")
     return ap.parse_args(argv)
 
@@ -183,6 +184,41 @@ def texture_coords_check(p, s, w, cam, W, H, spp, depth, variant, rng, ref):
     return bits_equal(frames[0], frames[1]), forms, mapped
 
 
+def textures_check(p, s, w, cam, W, H, spp, depth, variant, rng, ref):
+    """A world with an image on a streaming kernel, under a texture table of several random images and random modes: (1) entry 0 = the world's
+    image under clamp / nearest, one to three random further entries behind it: the frame is `ref`, the oracle's, in the renderer's own form and in the
+    global-memory form; (2) entry 0 under a random other mode pair: the two forms agree in every bit.  The worlds' materials all name image 0 (the oracle knows no
+    other; tests/test_gpu_textures.py holds the further entries absolutely), so the further entries test the table's layout, not its routing.
+    None: not applicable; else (ok, forms, the mode pair of (2))."""
+    if not w.image_width:
+        return None
+    image0 = s.textures()[1][: w.image_width * w.image_height].reshape(w.image_height, w.image_width, 3)   # entry 0's texels come first
+    more = [(rng.integers(0, 256, (int(rng.integers(1, 20)), int(rng.integers(1, 20)), 3)).astype(np.uint8), int(rng.integers(0, 2)), int(rng.integers(0, 2)))
+            for _ in range(int(rng.integers(1, 4)))]                                # drawn after every other draw of the case
+    modes = [(0, 1), (1, 0), (1, 1)][int(rng.integers(0, 3))]
+    frames, forms = [], []
+    for env in ({}, {"RT06_FORCE_BIG": "1"}):
+        os.environ.pop("RT06_FORCE_BIG", None)
+        os.environ.update(env)
+        try:
+            r = p.Renderer.MakeRenderer(W, H, spp, depth, cam, w, variant=variant)
+            r.textures([(image0, 0, 0)] + more)
+        except p.capi.RtError:
+            return None   # no kernel for the world
+        finally:
+            os.environ.pop("RT06_FORCE_BIG", None)
+        forms.append(r.kernel_form())
+        r.Render()
+        plain = r.DownloadRenderbuffer()
+        r.textures([(image0, *modes)] + more)
+        r.Render()
+        frames.append(r.DownloadRenderbuffer())
+        r.close()
+        if not bits_equal(plain, ref):
+            return False, forms, modes
+    return bits_equal(frames[0], frames[1]), forms, modes
+
+
 def main(argv=None):
     args = parse_args(argv)
     p = G.load_package()
@@ -283,6 +319,13 @@ def main(argv=None):
                 if not tc[0]:
                     fails += 1
                     print(f"FAIL seed {seed} with texture coordinates: kinds {kinds} triangles {s.n_triangles()} builder {builder} big {big} cam {ck} depth {depth} forms {tc[1]}", flush=True)
+        if args.textures and ok and info["variant"] in (2, 3) and not (big and builder == 3):
+            tx = textures_check(p, s, w, cam, W, H, spp, depth, variant, rng, ref)
+            if tx is not None:
+                stats["textures"] = stats.get("textures", 0) + 1
+                if not tx[0]:
+                    fails += 1
+                    print(f"FAIL seed {seed} with a texture table: kinds {kinds} builder {builder} big {big} cam {ck} depth {depth} modes {tx[2]} forms {tx[1]}", flush=True)
         if (seed - args.first) % 25 == 24:
             print(f"... {seed - args.first + 1} worlds, {fails} failures, {time.time() - t0:.0f}s, paths {stats}", flush=True)
     print(f"DONE: {args.seeds} worlds, {fails} failures, paths {stats}, {time.time() - t0:.0f}s")

@@ -48,6 +48,12 @@ lights the world with an environment map (rt_scene_set_environment, DESIGN.md §
 
 draws half of every Lambertian hit's directions from the map itself, in proportion to radiance times solid angle (RT_LIGHT_SAMPLING_ENV): a small
 bright sun is found at once instead of by the few rays that happen to leave towards it.  Needs --env.
+
+    python tools/render.py --scene book2_final --mesh tests/golden/tex_demo.obj --mtl --texture-wrap repeat --texture-filter bilinear \
+        --mesh-scale 120 --mesh-translate 150,160,120 --spp 64 --out out.png
+
+renders each `usemtl` group of the OBJ as a mesh of its own with the image its material's map_Kd names (the scene's texture table): here the
+book's earth sphere (image 0), a floor whose `vt` run to 4 — tiled under --texture-wrap repeat — and a UV-mapped pyramid, both filtered bilinearly.
 """
 import argparse, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -77,8 +83,13 @@ ap.add_argument("--mesh-translate", default="0,0,0", metavar="X,Y,Z")
 ap.add_argument("--mesh-material", default="white", choices=["white", "red", "metal", "glass", "checker", "light"])
 ap.add_argument("--smooth", action="store_true", help="with --mesh: smooth shading from per-vertex normals (DESIGN.md §21) — an OBJ file's own `vn` normals if it has a complete "
                     "set, an icosphere's unit positions, else area-weighted ones (mesh_io.vertex_normals)")
-ap.add_argument("--texture", default=None, metavar="FILE.ppm|FILE.png", help="with --mesh FILE.obj: the mesh's material is this image over the file's `vt` texture "
-                    "coordinates (DESIGN.md §22; binary PPM or 8-bit RGB / RGBA PNG); refused when the OBJ has no complete set of them")
+ap.add_argument("--texture", default=None, action="append", metavar="FILE.ppm|FILE.png", help="with --mesh FILE.obj: the mesh's material is this image over the file's `vt` texture "
+                    "coordinates (DESIGN.md §22; binary PPM or 8-bit RGB / RGBA PNG); refused when the OBJ has no complete set of them.  With --mtl it may be repeated: "
+                    "the k-th one replaces the map_Kd of the k-th material group, in the order the OBJ first uses them")
+ap.add_argument("--mtl", action="store_true", help="with --mesh FILE.obj: one mesh per `usemtl` group, each with the image its material's map_Kd names (mtllib files beside the "
+                    "OBJ; DESIGN.md §25) or a Lambertian of its Kd; a group without either takes --mesh-material")
+ap.add_argument("--texture-wrap", choices=["clamp", "repeat"], default="clamp", help="the wrap mode of the images --texture / --mtl bring (DESIGN.md §25)")
+ap.add_argument("--texture-filter", choices=["nearest", "bilinear"], default="nearest", help="their filter")
 ap.add_argument("--env", default=None, metavar="FILE.hdr|FILE.npy|FILE.png|FILE.ppm|sky", help="an equirectangular environment map in the place of the scene's background "
                     "(DESIGN.md §23): Radiance RGBE, a float (H, W, 3) numpy array, an 8-bit picture (mapped to [0, 1]) or the procedural sky")
 ap.add_argument("--env-rotate", type=float, default=0.0, metavar="DEG", help="with --env: turn the map about y")
@@ -103,8 +114,8 @@ elif a.scene == "book1_final":
     scene, cam = p.Scene.book1_final(a.seed), p.DefocusBlurCamera((13, 2, 3), (0, 0, 0), (0, 1, 0), 20.0, W / H, 0.1, 10.0)
 else:
     scene, cam = p.Scene.book2_moving(a.seed), p.MotionBlurCamera((13, 2, 3), (0, 0, 0), (0, 1, 0), 20.0, W / H, 0.0, 1.0)
-if a.texture and not a.mesh:
-    sys.exit("--texture needs --mesh FILE.obj")
+if (a.texture or a.mtl) and not a.mesh:
+    sys.exit("--texture needs --mesh FILE.obj" if a.texture else "--mtl needs --mesh FILE.obj")
 if a.mesh:
     from ray_tracing_v06_amd import mesh_io
     vertices, faces = mesh_io.from_spec(a.mesh)
@@ -117,21 +128,50 @@ if a.mesh:
         if normals is None:
             normals = mesh_io.vertex_normals(vertices, faces)
     uvs = uv_faces = None
-    if a.texture:
-        from ray_tracing_v06_amd import image_io
+    read_image = lambda path: (image_io.read_png if path.lower().endswith(".png") else image_io.read_ppm)(path)   # noqa: E731
+    # the images of this call go into the scene's texture table once there is more to say than "one image, clamp, nearest" — or when the scene
+    # has an image of its own (book2_final's earth stays image 0); otherwise the one image is the world's, as ever
+    in_table = a.mtl or a.scene == "book2_final" or (a.texture_wrap, a.texture_filter) != ("clamp", "nearest")
+
+    def image_material(path):
+        if in_table:
+            return scene.ImageTexture(scene.add_image(read_image(path), a.texture_wrap, a.texture_filter))
+        scene.set_image(read_image(path))
+        return scene.ImageTexture()
+    if a.texture or a.mtl:
         if a.mesh.startswith("icosphere:") or a.mesh == "tetrahedron":
             sys.exit(f"--texture: {a.mesh} has no texture coordinates; give an OBJ file with `vt` lines")
+        if a.texture and len(a.texture) > 1 and not a.mtl:
+            sys.exit("--texture: more than one image needs --mtl (one per material group of the OBJ)")
         _, _, uvs, uv_faces = mesh_io.load_obj_uvs(a.mesh)
-        if uvs is None:
+        if uvs is None and a.texture:
             sys.exit(f"--texture: {a.mesh} has no complete set of texture coordinates (`vt` lines and a second index at every face corner)")
-        if a.scene == "book2_final":
-            sys.exit("--texture: book2_final has an image of its own, and a world holds one")
-        scene.set_image((image_io.read_png if a.texture.lower().endswith(".png") else image_io.read_ppm)(a.texture))
-    mat = {"white": lambda: scene.Lambertian((0.73, 0.73, 0.73)), "red": lambda: scene.Lambertian((0.65, 0.05, 0.05)), "metal": lambda: scene.Metal((0.8, 0.85, 0.88), 0.0),
-           "glass": lambda: scene.Dielectric((1, 1, 1), 1.5), "checker": lambda: scene.LambertianTexture((0.2, 0.3, 0.1), (0.9, 0.9, 0.9), abs(a.mesh_scale) / 4 if a.mesh_scale else 1.0),   # four squares across a unit mesh
-           "light": lambda: scene.DiffuseLight((4, 4, 4))}[a.mesh_material]() if not a.texture else scene.ImageTexture()
-    first, added = scene.MakeMesh(vertices, faces, mat, a.mesh_scale, a.mesh_rotate_y, [float(x) for x in a.mesh_translate.split(",")], normals=normals, normal_faces=normal_faces,
-                                  uvs=uvs, uv_faces=uv_faces)
+    plain = {"white": lambda: scene.Lambertian((0.73, 0.73, 0.73)), "red": lambda: scene.Lambertian((0.65, 0.05, 0.05)), "metal": lambda: scene.Metal((0.8, 0.85, 0.88), 0.0),
+             "glass": lambda: scene.Dielectric((1, 1, 1), 1.5), "checker": lambda: scene.LambertianTexture((0.2, 0.3, 0.1), (0.9, 0.9, 0.9), abs(a.mesh_scale) / 4 if a.mesh_scale else 1.0),   # four squares across a unit mesh
+             "light": lambda: scene.DiffuseLight((4, 4, 4))}[a.mesh_material]
+    place = dict(scale=a.mesh_scale, rotate_y=a.mesh_rotate_y, translate=[float(x) for x in a.mesh_translate.split(",")])
+    if a.mtl:   # one mesh per material group, in the order the OBJ first uses them
+        import numpy as np
+        names, libraries = mesh_io.load_obj_materials(a.mesh)
+        library = {}
+        for lib in libraries:
+            library.update(mesh_io.load_mtl(os.path.join(os.path.dirname(os.path.abspath(a.mesh)), lib)))
+        groups = list(dict.fromkeys(names))
+        added = 0
+        for k, name in enumerate(groups):
+            rows = np.array([i for i, n in enumerate(names) if n == name])
+            entry = library.get(name, {"Kd": None, "map_Kd": None})
+            picture = a.texture[k] if a.texture and k < len(a.texture) else entry["map_Kd"]
+            if picture and uvs is None:
+                sys.exit(f"--mtl: material {name!r} has an image and {a.mesh} has no complete set of texture coordinates")
+            mat = image_material(picture) if picture else scene.Lambertian(entry["Kd"]) if entry["Kd"] else plain()
+            group_normals = dict(normals=normals, normal_faces=normal_faces[rows] if normal_faces is not None else faces[rows]) if normals is not None else {}
+            group_uvs = dict(uvs=uvs, uv_faces=uv_faces[rows]) if picture else {}
+            added += scene.MakeMesh(vertices, faces[rows], mat, **place, **group_normals, **group_uvs)[1]
+            print(json.dumps({"material": name, "triangles": len(rows), "image": picture, "Kd": entry["Kd"]}), flush=True)
+    else:
+        mat = image_material(a.texture[0]) if a.texture else plain()
+        first, added = scene.MakeMesh(vertices, faces, mat, **place, normals=normals, normal_faces=normal_faces, uvs=uvs, uv_faces=uv_faces)
     if a.scene == "three_spheres":
         scene.MakeHittableList()   # the prefab's own world kind
     else:
