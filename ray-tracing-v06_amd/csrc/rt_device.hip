@@ -192,7 +192,8 @@ struct rt_renderer {
     uint32_t variant = 0;        // resolved kernel variant (see rt_render_config::variant)
     const void* stream_kernel = nullptr;   // variants 2 to 6: what stream_kernel_for() gave for this world
     bool tol = false;            // variant 3 with the tolerance-mode box test (requested as variant 6)
-    uint32_t tune[3] = {RT_INNER_KEEP, RT_SHADE_MIN, RT_LEAF_MIN};  // scheduling thresholds of the streaming kernel
+    uint32_t tune[5] = {RT_INNER_KEEP, RT_SHADE_MIN, RT_LEAF_MIN, RT_INNER_DROP, RT_INNER_FLOOR};  // scheduling thresholds of the streaming kernel
+    bool tune_exit_forced = false;   // RT06_TUNE named inner_drop and inner_floor: they hold for every kernel of this renderer
     // render_kernel_xchg (variant 5): roles, ring capacities, population and thresholds (RT06_XCHG=tracers,extra,swap,shade,patience,prio)
     struct { uint32_t n_tracers = 9, tq_cap = 0, sq_cap = 0, pop_extra = 192, swap_min = 16, shade_min = 48, patience = 6, prio = 1, scene_vec4 = 0, extra_in_lds = 0, keep = 44, shards = 1; } xc;
     DevBuf xchg_error;           // set by the kernel when a bounded ring wait ran out (a protocol bug, never expected)
@@ -339,6 +340,22 @@ struct rt_renderer {
     //   0 = default (the fastest validated variant), 1 = baseline wave-per-pixel kernel,
     //   2 = streaming kernel with verbatim box tests, 3 = streaming kernel with the fast exact division,
     //   4 = 3 + filtered box-pair predicates (experimental), 5 = ray exchange, 6 = 3 with the tolerance-mode box test.
+    // The streaming kernel's scheduling thresholds: every family runs the fixed exit rule of the node loop (inner_drop 0, inner_floor 64: "fewer than
+    // inner_keep") unless it was measured to gain from the entry-relative one (EXPERIMENTS.md E18).  RT06_TUNE="keep,shade,leaf" or
+    // "keep,shade,leaf,drop,floor" overrides them for scheduling experiments (results never change); 0 for keep, shade, leaf or floor leaves the planned value.
+    void plan_thresholds() {
+        // measured: the hot loop of variant 3, on all four workloads, every kind of image (E18).  The generic node loop, tolerance mode and the
+        // light-sampling forms (call_params) were not, and keep the fixed rule.
+        if (variant == 3 && !tol) { tune[3] = RT_INNER_DROP_HOT; tune[4] = RT_INNER_FLOOR_HOT; }
+        const char* env = std::getenv("RT06_TUNE");
+        if (!env) return;
+        unsigned v[5] = {0, 0, 0, 0, 0};
+        const int n = std::sscanf(env, "%u,%u,%u,%u,%u", &v[0], &v[1], &v[2], &v[3], &v[4]);
+        if ((n != 3 && n != 5) || v[0] > 64 || v[1] > 64 || v[2] > 64 || v[3] > 64 || v[4] > 64) return;
+        for (int k = 0; k < 3; k++)
+            if (v[k]) tune[k] = v[k];
+        if (n == 5) { tune[3] = v[3]; if (v[4]) tune[4] = v[4]; tune_exit_forced = true; }
+    }
     int plan() {
         hipDeviceProp_t prop;
         HIP_TRY(hipGetDeviceProperties(&prop, cfg.device));
@@ -346,12 +363,7 @@ struct rt_renderer {
         if (const int rc = resolve_variant(size_stream_lds())) return rc;
         if (variant == 5)
             if (const int rc = size_xchg_rings()) return rc;
-        if (const char* env = std::getenv("RT06_TUNE")) {  // "keep,shade,leaf" — scheduling experiments only; results never change
-            unsigned a = 0, b = 0, c = 0;
-            if (std::sscanf(env, "%u,%u,%u", &a, &b, &c) == 3 && a >= 1 && a <= 64 && b >= 1 && b <= 64 && c >= 1 && c <= 64) {
-                tune[0] = a; tune[1] = b; tune[2] = c;
-            }
-        }
+        plan_thresholds();
         if (variant < 2) return RT_OK;
         if (const int rc = size_passes()) return rc;
         stream_kernel = stream_kernel_for(stream_kernel_key(variant, tol, scene));
@@ -637,6 +649,8 @@ struct rt_renderer {
         else if (tail_on()) p.scene.blob = tail.blob.as<uint4>();   // ... with the vertex normals (§21) and the texture coordinates (§22) behind it
         p.samples = sl.samples.as<float4>();
         p.inner_keep = tune[0] ? tune[0] : 1u; p.shade_min = tune[1]; p.leaf_min = tune[2];
+        p.inner_drop = tune[3]; p.inner_floor = tune[4];
+        if (nee.on() && !tune_exit_forced) { p.inner_drop = RT_INNER_DROP; p.inner_floor = RT_INNER_FLOOR; }   // not retuned (plan_thresholds)
         const size_t n_pass = n_local_pixels(tm) * pass_spp;   // 16-B records per array
         p.prim_o = sl.primary.as<float4>();
         p.prim_d = sl.primary.as<float4>() + n_pass;

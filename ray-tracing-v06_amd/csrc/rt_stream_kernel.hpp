@@ -43,10 +43,18 @@
 
 #define RT_WORLD_BVH_QUEUE 3     // internal WORLD mode of render_kernel_stream: an RT_WORLD_BVH world walked by each lane on its own — the distance-sorted queue (RT_TRAVERSAL_QUEUE) or the 4-wide walk (RT_TRAVERSAL_WIDE4)
 #define RT_CHUNK_MAX 768u        // sample indices a wave pulls per atomic (the host shrinks it for small frames / shards); 768 measured 0.35 ms ahead of 1024 and of 512 on config 2
-// scheduling thresholds (lanes of 64); overridable per renderer for tuning (RT06_TUNE=keep,shade,leaf)
+// scheduling thresholds (lanes of 64); overridable per renderer for tuning (RT06_TUNE=keep,shade,leaf[,drop,floor])
 #define RT_INNER_KEEP 36         // keep iterating inner-node steps while at least this many lanes want one (round 4, with the cheaper hot step: 36 / 52 / 4 is 0.3-1.2 % ahead of 40 / 56 / 4 on all four workloads)
 #define RT_SHADE_MIN 52          // run the shade/regenerate phase once this many lanes wait for it
 #define RT_LEAF_MIN 4            // run the leaf phase once this many lanes sit at a leaf (or nobody is at an inner node)
+// ... and the node loop's exit relative to the lane count it was entered with (node_loop_keep).  0 / 64 is the fixed rule "fewer than inner_keep": the floor never
+// lies below inner_keep, so the minimum is inner_keep whatever the entry count.
+#define RT_INNER_DROP 0          // leave the node loop once this many of the lanes it was entered with have left their inner nodes ...
+#define RT_INNER_FLOOR 64        // ... but never ask for fewer than this many lanes (nor for more than inner_keep)
+// what variant 3's hot loop runs with (EXPERIMENTS.md E18: 36 / 52 / 4 / 16 / 8 is 2.2-4.3 % ahead of the fixed rule on all four workloads; the sweep is flat from
+// drop 12 to 24 and floor 8 to 12, and loses half of the gain at floor 24)
+#define RT_INNER_DROP_HOT 16
+#define RT_INNER_FLOOR_HOT 8
 
 // A primary-ray record is read exactly once: a non-temporal load, so that this 23 GB stream does not push the partially written lines of
 // the sample buffer out of the L2 before their neighbours arrive.  Measured (config 2, round 3): HBM write traffic of the kernel
@@ -90,6 +98,7 @@ struct StreamParams {
     uint32_t pass_spp;       // samples per pixel in this pass
     uint32_t total;          // n_local_pixels * pass_spp
     uint32_t inner_keep, shade_min, leaf_min;
+    uint32_t inner_drop, inner_floor;   // the node loop's exit, relative to its entry lane count: node_loop_keep()
     uint32_t chunk;          // sample indices per work-queue fetch
     float4* samples;         // [n_local_pixels/64][pass_spp][64] radiance, RT_SAMPLE_BYTES = 12 bytes per sample index n (one global_store_dwordx3;
                              // 16-byte slots were measured slower and MORE HBM write traffic: EXPERIMENTS.md)
@@ -106,6 +115,16 @@ struct StreamParams {
 
 __device__ __forceinline__ uint32_t lane_rank(uint64_t mask) {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+
+// The node loop runs on while at least this many lanes want an inner-node step, for a loop entered with `n_entry` such lanes: the loop is left once
+// inner_drop of them have gone elsewhere, but the threshold stays within [inner_floor, inner_keep].  A wave that enters with few inner lanes late in a
+// shade period then stays for more than the one step a fixed threshold gives it, and one that enters full leaves for a leaf round before it has thinned
+// to the fixed threshold.  Scheduling only: which lane takes which step of which trace does not depend on it.  All operands are wave-uniform.
+__device__ __forceinline__ uint32_t node_loop_keep(const StreamParams& p, uint32_t n_entry) {
+    // (signed: all three are at most 64, and inner_floor >= 1 takes care of a negative difference.  An unsigned saturating difference, however it is spelt,
+    // has no scalar instruction, and the compiler moves the whole chain to the vector unit for it)
+    return (uint32_t)min((int)p.inner_keep, max((int)p.inner_floor, (int)n_entry - (int)p.inner_drop));
 }
 
 // pixel origin of the 8x8 tile that local 64-pixel block `blk` covers; false for a padding block
@@ -358,11 +377,13 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
             // step is straight-line code; lanes outside the class carry K::IRR in their inner references, so they
             // fail `cur < K::IRR` here and are stepped by the verbatim loop below.
             bool at_inner = cur < K::IRR;
-            if (__ballot(at_inner) != 0ull) {
+            const uint64_t m_entry = __ballot(at_inner);
+            if (m_entry != 0ull) {
                 uint32_t n_inner_lanes;
-                // inner_keep >= 1 (host); once the queue is dry the wave only drains its last paths: no reason to leave early.  The threshold is
-                // wave-uniform; readfirstlane tells the compiler so (a scalar compare and branch instead of a vector compare and an exec-mask loop exit)
-                const uint32_t keep_now = (uint32_t)__builtin_amdgcn_readfirstlane((int)(pool_dry ? 1u : p.inner_keep));
+                // The loop is left relative to the lane count it was entered with (node_loop_keep); inner_keep >= 1 (host).  Once the queue is dry the
+                // wave only drains its last paths: no reason to leave early.  The threshold is wave-uniform, worked out once per entry in scalar registers;
+                // readfirstlane tells the compiler so (a scalar compare and branch instead of a vector compare and an exec-mask loop exit)
+                const uint32_t keep_now = (uint32_t)__builtin_amdgcn_readfirstlane((int)(pool_dry ? 1u : node_loop_keep(p, (uint32_t)__popcll(m_entry))));
                 // Certified far planes (rt_fastdiv.hpp) pay where boxes have thickness.  The box of an axis-aligned quad is 1e-4 thick: the near and far
                 // parameters of a ray that hits it agree to ~2e-7, inside the certificate's margin, so nearly every hit box would take the exact redo
                 // (measured: Cornell box -6 %, Book-2 final scene -5 %).  Worlds with quads therefore keep the twelve exact quotients; the reference's
@@ -446,6 +467,8 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
         } else if (WORLD != RT_WORLD_BVH_QUEUE) {   // (a queue world's lanes are never "at a node": their trace ran when it began)
             bool at_inner = cur < K::LEAF;
             uint64_t m_inner = __ballot(at_inner);
+            // the hot loop's exit rule (node_loop_keep); these kernels never stayed on a dry queue, and do not now
+            const uint32_t keep_now = (uint32_t)__builtin_amdgcn_readfirstlane((int)node_loop_keep(p, (uint32_t)__popcll(m_inner)));
             while (m_inner != 0ull) {
                 if (at_inner) {
                     // kx/ky/kz are 0 in these kernels: near == box min, far == box max
@@ -500,7 +523,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                 }
                 at_inner = cur < K::LEAF;
                 m_inner = __ballot(at_inner);
-                if ((uint32_t)__popcll(m_inner) < p.inner_keep) break;
+                if ((uint32_t)__popcll(m_inner) < keep_now) break;
             }
         }
 

@@ -7,6 +7,7 @@ per-phase issue costs taken from the phase timers (unit = one hot-loop step) and
 the cost per trace.  Used to decide which scheduling changes are worth building.
 
     python tools/sched_model.py gpurun_out/trace_hist_book1.txt [--policy one|two] [--keep 40 --shade 56 --leaf 4 --swap 16]
+    --drop 16 --floor 8: the node loop's exit relative to its entry lane count (EXPERIMENTS.md E18)
 """
 import argparse, random, sys
 import numpy as np
@@ -18,6 +19,8 @@ ap.add_argument("--keep", type=int, default=40)
 ap.add_argument("--shade", type=int, default=56)
 ap.add_argument("--leaf", type=int, default=4)
 ap.add_argument("--swap", type=int, default=16)
+ap.add_argument("--drop", type=int, default=0)     # the node loop's exit relative to its entry lane count: a loop entered with n inner lanes
+ap.add_argument("--floor", type=int, default=64)   # runs while >= min(keep, max(floor, n - drop)) want a step; 0 / 64 = the fixed rule "while >= keep"
 ap.add_argument("--stall", type=int, default=8)
 ap.add_argument("--traces", type=int, default=200000)
 ap.add_argument("--c-leaf", type=float, default=1.2)     # one leaf phase, in hot steps
@@ -64,6 +67,7 @@ while done < a.traces:
     n_inner = st.count('I')
     # phase 1
     if n_inner:
+        keep_now = min(a.keep, max(a.floor, n_inner - a.drop))
         while True:
             k = 0
             for l in lanes:
@@ -71,7 +75,7 @@ while done < a.traces:
                     l.pos += 1; k += 1
             acc["hot"] += 1.0; acc["hot_lanes"] += k
             n_inner = sum(1 for l in lanes if l.state() == 'I')
-            if n_inner < a.keep: break
+            if n_inner < keep_now: break
     # phase 2
     n_leaf = sum(1 for l in lanes if l.state() == 'L')
     n_inner = sum(1 for l in lanes if l.state() == 'I')

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
-"""Sweep the wave-scheduling thresholds of render_kernel_stream (RT06_TUNE=keep,shade,leaf) in one process (dev tool).
-    python tools/tune_sweep.py 40,56,4 32,48,4 ...      env: W H SPP DEPTH SCENE REPS"""
+"""Sweep the wave-scheduling thresholds of render_kernel_stream in one process (dev tool): RT06_TUNE=keep,shade,leaf or
+keep,shade,leaf,drop,floor (the node loop's exit relative to its entry lane count; 0 = the planned default, except for drop).
+    python tools/tune_sweep.py 40,56,4 36,52,4,16,12 ...      env: W H SPP DEPTH SCENE REPS
+Each point prints the best and the median kernel time of REPS renders; `0,0,0` is the shipped plan."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import __graft_entry__ as G
@@ -21,9 +23,10 @@ else:
 for t in sys.argv[1:] or ["40,56,4"]:
     os.environ["RT06_TUNE"] = t
     r = p.Renderer.MakeRenderer(W, H, spp, depth, cam, scene.getWorldPtr())
-    best = 1e30
+    ms = []
     for it in range(reps):
         r.Render()
-        best = min(best, r.last_kernel_ms())
-    print(f"tune {t}: {best:.2f} ms  {W*H*spp/best/1e3:.1f} Msamples/s", flush=True)
+        ms.append(r.last_kernel_ms())
+    ms.sort()
+    print(f"tune {t}: {ms[0]:.2f} ms (median {ms[len(ms) // 2]:.2f})  {W*H*spp/ms[0]/1e3:.1f} Msamples/s", flush=True)
     r.close()
