@@ -635,10 +635,12 @@ int rt_renderer_denoise_download(rt_renderer* r, float* host_rgba, size_t n_floa
  * RT_MAX_LIGHTS; a renderer on variant 1, 5 or 6; a world with a queue or wide4 traversal; a world with a constant medium.            */
 #define RT_MAX_LIGHTS 16
 /* on: RT_LIGHT_SAMPLING_OFF (0), RT_LIGHT_SAMPLING_QUADS (1, the estimator above), RT_LIGHT_SAMPLING_ALL (2, below), RT_LIGHT_SAMPLING_MESH (4, further
- * below), RT_LIGHT_SAMPLING_TREE (16, below that) or RT_LIGHT_SAMPLING_ENV (32, last below); every other value — 3 too, which is no mode — is refused */
+ * below), RT_LIGHT_SAMPLING_TREE (16, below that), RT_LIGHT_SAMPLING_ENV (32) or RT_LIGHT_SAMPLING_ENV_TREE (48, last below); every other value — 3 too, which is
+ * no mode — is refused */
 int rt_renderer_light_sampling_enable(rt_renderer* r, uint32_t on);
-/* out[0] = the mode (RT_LIGHT_SAMPLING_OFF / _QUADS / _ALL / _MESH / _TREE / _ENV), out[1] = n_l of that mode's table — off: of the quad lights, as ever — (0 when
- * the world cannot be light-sampled); mode RT_LIGHT_SAMPLING_ENV: the texels of the map, W H                                */
+/* out[0] = the mode (RT_LIGHT_SAMPLING_OFF / _QUADS / _ALL / _MESH / _TREE / _ENV / _ENV_TREE), out[1] = n_l of that mode's table — off: of the quad lights, as
+ * ever — (0 when the world cannot be light-sampled); mode RT_LIGHT_SAMPLING_ENV: the texels of the map, W H; mode RT_LIGHT_SAMPLING_ENV_TREE: n_l of mode 16's
+ * table, which may be 0                                                                                                       */
 int rt_renderer_light_sampling_info(rt_renderer* r, uint32_t out[2]);
 /* HOST (no GPU): the light table of a world as rt_renderer_light_sampling_enable would take it — quad index and area of light i < *out_n —
  * or RT_ERR_INVALID with the world's own reason for refusal (no quad light, more than RT_MAX_LIGHTS, traversal, constant medium).     */
@@ -728,6 +730,20 @@ int rt_world_light_tree(const rt_world_flat* w, uint32_t capacity, float* out_no
  * a world with a queue or wide4 traversal; a world with a constant medium.  While the mode is on, rt_renderer_environment refuses NULL (switch sampling off
  * first) and an all-black map (the old map stays).                                                                                                       */
 #define RT_LIGHT_SAMPLING_ENV 32
+
+/* The map and the light tree together: mode RT_LIGHT_SAMPLING_ENV_TREE = 16 | 32 of rt_renderer_light_sampling_enable (opt-in beside modes 1 to
+ * 32, which stay what they are).  A hit is sampled when its material is RT_MAT_LAMBERTIAN, RT_MAT_LAMBERTIAN_CHECKER or RT_MAT_LAMBERTIAN_IMAGE (whose albedo is
+ * looked up behind the direction, as ever); RT_MAT_LAMBERTIAN_NOISE and every other material draw and scatter as with sampling off.  The table is mode 16's, and
+ * n_l == 0 is accepted: the mode then behaves as the map alone.  Draws at a sampled hit:  c = next;  if c < 0.5f and n_l > 0, c2 = next: c2 < 0.5f is the map,
+ * otherwise the table (n_l == 0: the map, no draw);  the map: x1, x2, a, b and the rule of mode 32;  the table: mode 16's choice and point;  c >= 0.5f:
+ * d = normal + on-unit vector.  Density, whichever branch drew d:  pe = the map's density of d;  pl = mode 16's walk sum / A;  pm = 0.5f * pe + 0.5f * pl
+ * (n_l == 0: pm = pe, pl is not computed);  pdf = 0.5f * sp + 0.5f * pm;  sp == 0 or !(pdf > 0) ends the path as a failed scatter, as does a drawn sphere light
+ * the walk did not credit;  otherwise atten *= albedo * (sp / pdf) and the new ray is hit_p + d * 0.001f, d.  No shadow ray.
+ * rt_renderer_light_sampling_info gives (48, n_l); rt_renderer_kernel_light_tree and rt_renderer_kernel_env_light both say 1.
+ * RT_ERR_INVALID, each with a message of its own: a world whose background is not 2; a renderer without a map; an all-black map; a renderer on variant 1, 5 or 6;
+ * a world with a queue or wide4 traversal; a world with a constant medium; more than RT_MAX_LIGHTS_TREE lights; a light whose area is lost in the running sum;
+ * a table that does not fit beside an LDS-resident image.  While the mode is on, rt_renderer_environment behaves as in mode 32.                            */
+#define RT_LIGHT_SAMPLING_ENV_TREE 48
 
 /* Smooth shading (see rt_tri_normals): the renderer's table of vertex normals, one record per triangle of its world — n must equal rt_world_triangles of it —
  * or NULL, 0 to turn it off.  Copied.  Takes effect at the next launch and, like a light-sampling change, discards the refinement and feature-buffer state.  The

@@ -541,7 +541,8 @@ struct MotionBlurCamera {
 
 // the modes of Renderer::SetLightSampling (RT_LIGHT_SAMPLING_* of rt06.h)
 enum class LightSampling : uint32_t { Off = RT_LIGHT_SAMPLING_OFF, Quads = RT_LIGHT_SAMPLING_QUADS, All = RT_LIGHT_SAMPLING_ALL, Mesh = RT_LIGHT_SAMPLING_MESH,
-                                      Tree = RT_LIGHT_SAMPLING_TREE, Env = RT_LIGHT_SAMPLING_ENV /* the environment map of a background-2 world */ };
+                                      Tree = RT_LIGHT_SAMPLING_TREE, Env = RT_LIGHT_SAMPLING_ENV /* the environment map of a background-2 world */,
+                                      EnvTree = RT_LIGHT_SAMPLING_ENV_TREE /* that map and the light tree together, image-textured hits included */ };
 
 // ----------------------------------------------------------------------------------------------------
 // Renderer — main/src/Renderer.h:12-47
@@ -728,7 +729,8 @@ public:
     }
     // Off, the quad lights (what SetLightSampling(true) selects), the quad and the sphere lights (RT_LIGHT_SAMPLING_ALL), or those and the triangle lights of
     // an emissive mesh (RT_LIGHT_SAMPLING_MESH), or the same lights — up to RT_MAX_LIGHTS_TREE — chosen by area and found through a light tree (RT_LIGHT_SAMPLING_TREE);
-    // or LightSampling::Env: the environment map of a background-2 world alone, directions drawn in proportion to radiance times solid angle (RT_LIGHT_SAMPLING_ENV)
+    // or LightSampling::Env: the environment map of a background-2 world alone, directions drawn in proportion to radiance times solid angle (RT_LIGHT_SAMPLING_ENV);
+    // or LightSampling::EnvTree: that map and the light tree together, half of the light draws each, at image-textured Lambertian hits too (RT_LIGHT_SAMPLING_ENV_TREE)
     void SetLightSampling(LightSampling mode) {
         if (m.mr) rt06::check(rt_multi_renderer_light_sampling_enable(m.mr, (uint32_t)mode), "Renderer::SetLightSampling");
         else rt06::check(rt_renderer_light_sampling_enable(m.r, (uint32_t)mode), "Renderer::SetLightSampling");

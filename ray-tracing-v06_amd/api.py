@@ -417,14 +417,18 @@ class Scene:
             pass
 
 
-LIGHT_SAMPLING_MODES = {"off": 0, "quads": 1, "all": 2, "mesh": 4, "tree": 16, "env": 32}   # RT_LIGHT_SAMPLING_*
+LIGHT_SAMPLING_MODES = {"off": 0, "quads": 1, "all": 2, "mesh": 4, "tree": 16, "env": 32}   # RT_LIGHT_SAMPLING_* of one light source each
+LIGHT_SAMPLING_COMBINED = {"env+tree": 48}   # RT_LIGHT_SAMPLING_ENV_TREE: the map and the light tree together; a table of its own, the one above is held by name
 
 
 def light_sampling_mode(on):
-    """False / 0 / "off" -> 0, True / 1 / "quads" -> 1, 2 / "all" -> 2, 4 / "mesh" -> 4, 16 / "tree" -> 16, 32 / "env" -> 32 (RT_LIGHT_SAMPLING_*)"""
+    """False / 0 / "off" -> 0, True / 1 / "quads" -> 1, 2 / "all" -> 2, 4 / "mesh" -> 4, 16 / "tree" -> 16, 32 / "env" -> 32, 48 / "env+tree" -> 48
+    (RT_LIGHT_SAMPLING_*)"""
     if isinstance(on, str):
+        if on in LIGHT_SAMPLING_COMBINED:
+            return LIGHT_SAMPLING_COMBINED[on]
         if on not in LIGHT_SAMPLING_MODES:
-            raise ValueError(f"light sampling mode {on!r}: one of 'off', 'quads', 'all', 'mesh', 'tree', 'env'")
+            raise ValueError(f"light sampling mode {on!r}: one of 'off', 'quads', 'all', 'mesh', 'tree', 'env', 'env+tree'")
         return LIGHT_SAMPLING_MODES[on]
     return int(on)
 
@@ -617,19 +621,21 @@ class Renderer:
         """Next-event estimation from the next launch on (rt_renderer_light_sampling_enable); a change restarts the refinement.
         False / 0 / "off": off; True / 1 / "quads": over the world's quad lights; 2 / "all": over its quad and sphere lights; 4 / "mesh": over its quad,
         sphere and triangle lights (an emissive mesh); 16 / "tree": over the same lights, up to 4096, chosen by area and found through a light tree;
-        32 / "env": over the environment map of a background-2 world alone, directions drawn in proportion to radiance times solid angle."""
+        32 / "env": over the environment map of a background-2 world alone, directions drawn in proportion to radiance times solid angle (DESIGN.md §24);
+        48 / "env+tree": over that map and the light tree together, half of the light draws each, at image-textured Lambertian hits too; a world without
+        lights is accepted and sampled as the map alone."""
         check(lib().rt_renderer_light_sampling_enable(self.h, light_sampling_mode(on)))
 
     def light_sampling_mode(self):
-        """0 (off), 1 (quad lights), 2 (quad and sphere lights), 4 (quad, sphere and triangle lights), 16 (those, by area, through a light tree) or 32 (the
-        environment map): the mode the next launch runs in."""
+        """0 (off), 1 (quad lights), 2 (quad and sphere lights), 4 (quad, sphere and triangle lights), 16 (those, by area, through a light tree), 32 (the
+        environment map) or 48 (the map and the light tree together): the mode the next launch runs in."""
         out = (C.c_uint32 * 2)()
         check(lib().rt_renderer_light_sampling_info(self.h, out))
         return out[0]
 
     def light_sampling_info(self):
         """{'enabled', 'lights'}: whether light sampling is on (in any mode: light_sampling_mode() tells which), and the number of lights in the
-        mode's table — off: of quad lights; "env": the texels of the map — (0: the world cannot be light-sampled)."""
+        mode's table — off: of quad lights; "env": the texels of the map; "env+tree": of the light tree's table, which may be empty — (0: the world cannot be light-sampled)."""
         out = (C.c_uint32 * 2)()
         check(lib().rt_renderer_light_sampling_info(self.h, out))
         return {"enabled": bool(out[0]), "lights": out[1]}
@@ -718,13 +724,13 @@ class Renderer:
         return form
 
     def kernel_light_tree(self):
-        """True when the next launch runs the streaming kernel's light-tree family (rt_renderer_kernel_light_tree): mode "tree" is on."""
+        """True when the next launch runs the streaming kernel's light-tree family (rt_renderer_kernel_light_tree): mode "tree" or "env+tree" is on."""
         out = C.c_uint32(0)
         check(lib().rt_renderer_kernel_light_tree(self.h, C.byref(out)))
         return bool(out.value)
 
     def kernel_env_light(self):
-        """True when the next launch runs the streaming kernel's environment-sampling family (rt_renderer_kernel_env_light): mode "env" is on."""
+        """True when the next launch runs the streaming kernel's environment-sampling family (rt_renderer_kernel_env_light): mode "env" or "env+tree" is on."""
         out = C.c_uint32(0)
         check(lib().rt_renderer_kernel_env_light(self.h, C.byref(out)))
         return bool(out.value)

@@ -99,6 +99,8 @@ static const void* stream_kernel_for(uint32_t key) {
     case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NEE | RT_KEY_LTREE: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, true, true, true>)
 #define RT_KERNEL_ENV_LIGHT(exact, world, ext, big, wide) \
     case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NEE | RT_KEY_ENVL: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, true, true, false, true>)
+#define RT_KERNEL_ENV_TREE(exact, world, ext, big, wide) \
+    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NEE | RT_KEY_LTREE | RT_KEY_ENVL: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, true, true, true, true>)
     switch (key) {   // arguments: exact, filter, world, ext, big, wide, tol
         case RT_KEY_XCHG: return reinterpret_cast<const void*>(&render_kernel_xchg<RT_XCHG_BLOCK>);
         RT_KERNEL(true, false, RT_WORLD_BVH_QUEUE, 2, true, true, false); RT_KERNEL(true, false, RT_WORLD_BVH_QUEUE, 1, true, true, false); RT_KERNEL(true, false, RT_WORLD_BVH_QUEUE, 0, true, true, false);
@@ -138,9 +140,16 @@ static const void* stream_kernel_for(uint32_t key) {
         RT_KERNEL_ENV_LIGHT(false, RT_WORLD_BVH, 2, true, false); RT_KERNEL_ENV_LIGHT(true, RT_WORLD_BVH, 2, true, false);
         RT_KERNEL_ENV_LIGHT(true, RT_WORLD_LIST, 2, false, false);
         RT_KERNEL_ENV_LIGHT(false, RT_WORLD_BVH, 2, false, false); RT_KERNEL_ENV_LIGHT(true, RT_WORLD_BVH, 2, false, false);
+        // the map and the light tree together (§26): the same eight once more, LTREE && ENVL (arguments: exact, world, ext, big, wide)
+        RT_KERNEL_ENV_TREE(true, RT_WORLD_LIST, 2, true, true);
+        RT_KERNEL_ENV_TREE(false, RT_WORLD_BVH, 2, true, true); RT_KERNEL_ENV_TREE(true, RT_WORLD_BVH, 2, true, true);
+        RT_KERNEL_ENV_TREE(false, RT_WORLD_BVH, 2, true, false); RT_KERNEL_ENV_TREE(true, RT_WORLD_BVH, 2, true, false);
+        RT_KERNEL_ENV_TREE(true, RT_WORLD_LIST, 2, false, false);
+        RT_KERNEL_ENV_TREE(false, RT_WORLD_BVH, 2, false, false); RT_KERNEL_ENV_TREE(true, RT_WORLD_BVH, 2, false, false);
         default: return nullptr;
     }
 #undef RT_KERNEL
+#undef RT_KERNEL_ENV_TREE
 #undef RT_KERNEL_ENV_LIGHT
 #undef RT_KERNEL_LIGHT_TREE
 #undef RT_KERNEL_NEE
@@ -227,11 +236,13 @@ struct rt_renderer {
     // kernel serves all three modes (they differ only in what the table holds)
     // (mode RT_LIGHT_SAMPLING_TREE, §20, has a family of its own — `key` says which form a table runs — and, behind the table, cdf in the entries and the tree's nodes)
     struct LightTable { uint32_t n = 0; std::vector<uint32_t> kind, index; std::vector<float> area, sphere /* 4 per light */, cdf, nodes /* 8 per node */;
-                        std::string refused; DevBuf blob; uint32_t table_vec4 = 0, lds_bytes = 0, blocks_per_cu = 0, key = 0; const void* kernel = nullptr; bool built = false; };
+                        std::string refused; bool none = false /* refused for having no light: what mode 48 accepts (§26) */; DevBuf blob; uint32_t table_vec4 = 0, lds_bytes = 0, blocks_per_cu = 0, key = 0; const void* kernel = nullptr; bool built = false; };
     // (mode RT_LIGHT_SAMPLING_ENV, §24, has no table: its slot holds the key, the kernel and the LDS of the plain image, and its launches run on tail.blob)
-    struct { uint32_t mode = RT_LIGHT_SAMPLING_OFF; LightTable tab[5]; const void* kernel = nullptr;   // kernel: the current mode's
+    // (mode RT_LIGHT_SAMPLING_ENV_TREE, §26, runs on mode 16's image — image_slot — and its own slot holds the key, the kernel, n_l and a copy of that image's sizes)
+    struct { uint32_t mode = RT_LIGHT_SAMPLING_OFF; LightTable tab[6]; const void* kernel = nullptr;   // kernel: the current mode's
              bool on() const { return mode != RT_LIGHT_SAMPLING_OFF; }
-             static uint32_t slot(uint32_t m) { return m == RT_LIGHT_SAMPLING_ENV ? 4u : m == RT_LIGHT_SAMPLING_TREE ? 3u : m == RT_LIGHT_SAMPLING_MESH ? 2u : m - 1u; }   // modes 1, 2, 4, 16, 32
+             static uint32_t slot(uint32_t m) { return m == RT_LIGHT_SAMPLING_ENV_TREE ? 5u : m == RT_LIGHT_SAMPLING_ENV ? 4u : m == RT_LIGHT_SAMPLING_TREE ? 3u : m == RT_LIGHT_SAMPLING_MESH ? 2u : m - 1u; }   // modes 1, 2, 4, 16, 32, 48
+             static uint32_t image_slot(uint32_t m) { return slot(m == RT_LIGHT_SAMPLING_ENV_TREE ? RT_LIGHT_SAMPLING_TREE : m); }   // whose image (and tail) the mode launches on
              const LightTable& cur() const { return tab[slot(mode)]; } } nee;
     // smooth shading (rt_renderer_shading_normals): the table as given (9 floats per triangle of the world), a flat copy for the feature pass, and
     // the images the triangle kernels launch on while it is on — the plain image and, per light-sampling mode already built, the image with that mode's light
@@ -314,6 +325,40 @@ struct rt_renderer {
         env.dist_on = with_dist;
         return RT_OK;
     }
+    // The scene image with the light table of `mode` (1, 2, 4 or 16) behind it, once per table: t.blob, and with it t.table_vec4, t.lds_bytes and t.blocks_per_cu.
+    // A header (n_l, A, -, -), n_l entries (index, area, kind, c_j), — all modes but 1 — n_l more (Cx, Cy, Cz, r), and — mode 16, §20 — 2 n_l - 1 nodes of two vec4:
+    // 1 + 2 n_l + 2 (2 n_l - 1) = 6 n_l - 1 vec4.  An empty table (mode 48 on a world without lights, §26) is the header alone.
+    int light_image(uint32_t mode, LightTable& t) {
+        if (t.blob.p) return RT_OK;
+        const bool tree = mode == RT_LIGHT_SAMPLING_TREE;
+        const uint32_t table_vec4 = 1u + t.n * (mode == RT_LIGHT_SAMPLING_QUADS ? 1u : 2u) + (tree && t.n ? 2u * (2u * t.n - 1u) : 0u);
+        PackedSceneRef with_table = scene.packed;
+        with_table.blob_vec4 += table_vec4;
+        const uint32_t lds = (uint32_t)stream_kernel_lds_bytes(stream_block, with_table, scene.big, scene.wide, n_top);
+        if (lds > RT_LDS_PER_CU)
+            return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: the light table (%u bytes) does not fit beside the scene image in the LDS", table_vec4 * 16u);
+        std::vector<uint4> table(table_vec4, make_uint4(0u, 0u, 0u, 0u));
+        table[0].x = t.n;
+        for (uint32_t i = 0; i < t.n; i++) {
+            table[1u + i].x = t.index[i]; std::memcpy(&table[1u + i].y, &t.area[i], 4); table[1u + i].z = t.kind[i];
+            if (t.kind[i] == RT_LIGHT_SPHERE) std::memcpy(&table[1u + t.n + i], &t.sphere[4u * i], 16);
+            if (tree) std::memcpy(&table[1u + i].w, &t.cdf[i], 4);
+        }
+        if (tree && t.n) {
+            std::memcpy(&table[0].y, &t.cdf[t.n - 1u], 4);   // A
+            std::memcpy(&table[1u + 2u * t.n], t.nodes.data(), t.nodes.size() * sizeof(float));
+        }
+        table.push_back(make_uint4(0u, 0u, 0u, 0u));   // the vertex-normal header behind this image (§21): zero = no table follows
+        DevBuf fresh;
+        HIP_TRY(fresh.alloc(((size_t)scene.packed.blob_vec4 + table.size()) * sizeof(uint4)));
+        HIP_TRY(hipMemcpy(fresh.p, scene.blob.p, (size_t)scene.packed.blob_vec4 * sizeof(uint4), hipMemcpyDeviceToDevice));
+        HIP_TRY(hipMemcpy(fresh.as<uint4>() + scene.packed.blob_vec4, table.data(), table.size() * sizeof(uint4), hipMemcpyHostToDevice));
+        std::swap(t.blob.p, fresh.p); std::swap(t.blob.bytes, fresh.bytes);
+        t.table_vec4 = table_vec4;
+        t.lds_bytes = lds;
+        t.blocks_per_cu = std::min(2u, RT_LDS_PER_CU / lds);
+        return RT_OK;
+    }
     // the tails anew from vn, uv and env as they stand: none while all are off, else the plain image's and one per light-sampling mode already built
     int rebuild_tails() {
         tail.blob.release();
@@ -322,7 +367,7 @@ struct rt_renderer {
         if (const int rc = image_with_tail(scene.blob, scene.packed.blob_vec4, tail.blob)) return rc;
         for (const uint32_t mode : {RT_LIGHT_SAMPLING_QUADS, RT_LIGHT_SAMPLING_ALL, RT_LIGHT_SAMPLING_MESH, RT_LIGHT_SAMPLING_TREE}) {
             const LightTable& t = nee.tab[nee.slot(mode)];
-            if (t.built)
+            if (t.blob.p)
                 if (const int rc = image_with_tail(t.blob, scene.packed.blob_vec4 + t.table_vec4, tail.nee_blob[nee.slot(mode)])) return rc;
         }
         return RT_OK;
@@ -645,7 +690,7 @@ struct rt_renderer {
         p.scene = scene.packed;
         p.scene.n_top = scene.big ? n_top : 0u;
         if (nee.mode == RT_LIGHT_SAMPLING_ENV) p.scene.blob = tail.blob.as<uint4>();   // §24: no table; the plain image with its tail, whose environment record is on while the mode is
-        else if (nee.on()) { p.scene.blob = (tail_on() ? tail.nee_blob[nee.slot(nee.mode)] : nee.cur().blob).as<uint4>(); p.scene.blob_vec4 += nee.cur().table_vec4; }   // the same image with the light table behind it
+        else if (nee.on()) { p.scene.blob = (tail_on() ? tail.nee_blob[nee.image_slot(nee.mode)] : nee.tab[nee.image_slot(nee.mode)].blob).as<uint4>(); p.scene.blob_vec4 += nee.cur().table_vec4; }   // the same image with the light table behind it
         else if (tail_on()) p.scene.blob = tail.blob.as<uint4>();   // ... with the vertex normals (§21) and the texture coordinates (§22) behind it
         p.samples = sl.samples.as<float4>();
         p.inner_keep = tune[0] ? tune[0] : 1u; p.shade_min = tune[1]; p.leaf_min = tune[2];
@@ -773,6 +818,7 @@ extern "C" int rt_renderer_create(const rt_render_config* cfg, const rt_camera* 
         const uint32_t cap = mode == RT_LIGHT_SAMPLING_TREE ? RT_MAX_LIGHTS_TREE : RT_MAX_LIGHTS_MESH;
         t.kind.assign(cap, 0u); t.index.assign(cap, 0u); t.area.assign(cap, 0.0f);
         if (rt_world_light_table(world, mode, cap, t.kind.data(), t.index.data(), t.area.data(), &t.n) != RT_OK) { t.refused = rt_last_error(); t.n = 0; }
+        t.none = t.refused.find("has no light to sample") != std::string::npos;
         t.kind.resize(t.n); t.index.resize(t.n); t.area.resize(t.n); t.sphere.assign((size_t)t.n * 4u, 0.0f);
         if (mode == RT_LIGHT_SAMPLING_TREE && t.n) {
             uint32_t n_nodes = 0;
@@ -877,9 +923,49 @@ extern "C" int rt_renderer_set_camera(rt_renderer* r, const rt_camera* cam) {
 // (Cx, Cy, Cz, r), zeros for a quad and for a triangle.
 extern "C" int rt_renderer_light_sampling_enable(rt_renderer* r, uint32_t on) {
     if (!r) return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: null renderer");
-    if (on > RT_LIGHT_SAMPLING_ALL && on != RT_LIGHT_SAMPLING_MESH && on != RT_LIGHT_SAMPLING_TREE && on != RT_LIGHT_SAMPLING_ENV)   // 3 is no mode
-        return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: on must be 0 (off), 1 (quad lights), 2 (quad and sphere lights), 4 (quad, sphere and triangle lights), 16 (those, through a light tree, chosen by area) or 32 (the environment map)");
+    if (on > RT_LIGHT_SAMPLING_ALL && on != RT_LIGHT_SAMPLING_MESH && on != RT_LIGHT_SAMPLING_TREE && on != RT_LIGHT_SAMPLING_ENV && on != RT_LIGHT_SAMPLING_ENV_TREE)   // 3 is no mode
+        return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: on must be 0 (off), 1 (quad lights), 2 (quad and sphere lights), 4 (quad, sphere and triangle lights), 16 (those, through a light tree, chosen by area) or 32 (the environment map), or 48 (the map and the light tree together)");
     if (on == r->nee.mode) return RT_OK;   // nothing changes, the refinement goes on
+    if (on == RT_LIGHT_SAMPLING_ENV_TREE) {   // §26: mode 32's map and mode 16's table at once — mode 16's image (an empty table is a header alone) under the tail's environment record
+        rt_renderer::LightTable& t = r->nee.tab[r->nee.slot(on)];
+        rt_renderer::LightTable& tree = r->nee.tab[r->nee.slot(RT_LIGHT_SAMPLING_TREE)];
+        if (r->variant < 2 || r->variant == 5 || r->tol)
+            return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: kernel variant %u has no light-sampling form (the baseline kernel 1, the ray exchange 5 and the tolerance mode 6 do not; use variant 0, 2 or 3)", r->tol ? 6u : r->variant);
+        if (r->scene.dw.background != 2u)
+            return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: mode 48 samples the environment map of a world with background mode 2 (rt_scene_set_environment) beside its lights; this world's is %u, for which on must be 0 (off), 1 (quad lights), 2 (quad and sphere lights), 4 (quad, sphere and triangle lights) or 16 (those, through a light tree, chosen by area)", r->scene.dw.background);
+        if (r->scene.queue)
+            return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: mode 48: a world with a queue or wide4 traversal renders on lane walks that have no light-sampling form (RT_TRAVERSAL_STACK and lists do)");
+        if (r->has_medium)
+            return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: mode 48: the world has a constant medium (RT_MAT_ISOTROPIC), which neither the environment estimator nor the light tree covers");
+        if (!r->env.on)
+            return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: mode 48: the renderer has no environment map to sample: give it one with rt_renderer_environment first");
+        if (!tree.refused.empty() && !tree.none)   // more than RT_MAX_LIGHTS_TREE lights, or an area lost in the running sum; a world with no light at all is the map alone
+            return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: mode 48: %s", tree.refused.c_str());
+        HIP_TRY(hipSetDevice(r->cfg.device));
+        if (const int rc = wait_last_call(r)) return rc;   // launches already enqueued read the texel records that are replaced below
+        if (const int rc = r->drain_slots()) return rc;
+        if (!t.built) {
+            if (const int rc = r->light_image(RT_LIGHT_SAMPLING_TREE, tree)) return rc;
+            const uint32_t key = stream_kernel_key(r->variant, false, r->scene) | RT_KEY_NEE | RT_KEY_TRI | RT_KEY_LTREE | RT_KEY_ENVL;   // a world without triangles is a TRI world too
+            const void* k = stream_kernel_for(key);
+            if (!k) return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: mode 48: this world's kernel has no form that samples the map and the light tree");
+            HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tree.lds_bytes));
+            t.n = tree.n;
+            t.table_vec4 = tree.table_vec4;
+            t.lds_bytes = tree.lds_bytes;
+            t.blocks_per_cu = tree.blocks_per_cu;
+            t.key = key;
+            t.kernel = k;
+            t.built = true;
+        }
+        if (!r->env.dist_on) {   // as mode 32 does: the distribution of the map as it stands; an all-black map is refused here
+            if (const int rc = r->upload_environment("rt_renderer_light_sampling_enable: mode 48", r->env.w, r->env.h, r->env.host.data(), true)) return rc;
+            if (const int rc = r->rebuild_tails()) return rc;
+        }
+        if (!r->tail.nee_blob[r->nee.image_slot(on)].p)   // mode 16's image with the tail (the environment record is always on here) behind its table
+            if (const int rc = r->image_with_tail(tree.blob, r->scene.packed.blob_vec4 + tree.table_vec4, r->tail.nee_blob[r->nee.image_slot(on)])) return rc;
+        r->nee.kernel = t.kernel;
+    } else
     if (on == RT_LIGHT_SAMPLING_ENV) {   // §24: the map is the one light; no table, a kernel family of its own on the image every launch of this renderer gets
         rt_renderer::LightTable& t = r->nee.tab[r->nee.slot(on)];
         if (r->variant < 2 || r->variant == 5 || r->tol)
@@ -920,37 +1006,14 @@ extern "C" int rt_renderer_light_sampling_enable(rt_renderer* r, uint32_t on) {
         HIP_TRY(hipSetDevice(r->cfg.device));
         if (const int rc = r->drain_slots()) return rc;   // renders that ran ahead may still be queued: the tables and the kernel's LDS limit change behind them
         if (!t.built) {   // set last: a failure on the way is tried again
-            const bool tree = on == RT_LIGHT_SAMPLING_TREE;   // §20: 2 n_l - 1 nodes of two vec4 behind the table: 1 + 2 n_l + 2 (2 n_l - 1) = 6 n_l - 1 vec4
-            const uint32_t table_vec4 = 1u + t.n * (on == RT_LIGHT_SAMPLING_QUADS ? 1u : 2u) + (tree ? 2u * (2u * t.n - 1u) : 0u);
-            PackedSceneRef with_table = r->scene.packed;
-            with_table.blob_vec4 += table_vec4;
-            const uint32_t lds = (uint32_t)stream_kernel_lds_bytes(r->stream_block, with_table, r->scene.big, r->scene.wide, r->n_top);
-            if (lds > RT_LDS_PER_CU)
-                return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: the light table (%u bytes) does not fit beside the scene image in the LDS", table_vec4 * 16u);
+            const bool tree = on == RT_LIGHT_SAMPLING_TREE;
+            if (const int rc = r->light_image(on, t)) return rc;   // (mode 48 may have built mode 16's already: §26)
             const uint32_t key = stream_kernel_key(r->variant, false, r->scene) | RT_KEY_NEE | (tree ? RT_KEY_TRI | RT_KEY_LTREE : 0u);   // a world without triangles is a TRI world too
             const void* k = stream_kernel_for(key);
             if (!k) return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: this world's kernel has no light-sampling form");
-            std::vector<uint4> table(table_vec4, make_uint4(0u, 0u, 0u, 0u));
-            table[0].x = t.n;
-            for (uint32_t i = 0; i < t.n; i++) {
-                table[1u + i].x = t.index[i]; std::memcpy(&table[1u + i].y, &t.area[i], 4); table[1u + i].z = t.kind[i];
-                if (t.kind[i] == RT_LIGHT_SPHERE) std::memcpy(&table[1u + t.n + i], &t.sphere[4u * i], 16);
-                if (tree) std::memcpy(&table[1u + i].w, &t.cdf[i], 4);
-            }
-            if (tree) {
-                std::memcpy(&table[0].y, &t.cdf[t.n - 1u], 4);   // A
-                std::memcpy(&table[1u + 2u * t.n], t.nodes.data(), t.nodes.size() * sizeof(float));
-            }
-            table.push_back(make_uint4(0u, 0u, 0u, 0u));   // the vertex-normal header behind this image (§21): zero = no table follows
-            HIP_TRY(t.blob.alloc(((size_t)r->scene.packed.blob_vec4 + table.size()) * sizeof(uint4)));
-            HIP_TRY(hipMemcpy(t.blob.p, r->scene.blob.p, (size_t)r->scene.packed.blob_vec4 * sizeof(uint4), hipMemcpyDeviceToDevice));
-            HIP_TRY(hipMemcpy(t.blob.as<uint4>() + r->scene.packed.blob_vec4, table.data(), table.size() * sizeof(uint4), hipMemcpyHostToDevice));
-            uint32_t lds_set = lds;   // one kernel may serve several tables: the attribute covers the largest of its own
+            uint32_t lds_set = t.lds_bytes;   // one kernel may serve several tables: the attribute covers the largest of its own
             for (const rt_renderer::LightTable& o : r->nee.tab) if (o.built && o.kernel == k) lds_set = std::max(lds_set, o.lds_bytes);
             HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_set));
-            t.table_vec4 = table_vec4;
-            t.lds_bytes = lds;
-            t.blocks_per_cu = std::min(2u, RT_LDS_PER_CU / lds);
             t.key = key;
             t.kernel = k;
             t.built = true;
@@ -1065,12 +1128,12 @@ extern "C" int rt_renderer_environment(rt_renderer* r, uint32_t width, uint32_t 
     const size_t n_texels = (size_t)width * height;
     if (off ? !r->env.on : (r->env.on && r->env.w == width && r->env.h == height && std::memcmp(&r->env.u0, &u0, 4) == 0 &&
                             std::memcmp(r->env.host.data(), rgb, n_texels * 3u * sizeof(float)) == 0)) return RT_OK;   // nothing changes, the refinement goes on
-    const bool sampled = r->nee.mode == RT_LIGHT_SAMPLING_ENV;   // §24: the map is being sampled: it cannot leave, and its successor brings a distribution
+    const bool sampled = r->nee.mode == RT_LIGHT_SAMPLING_ENV || r->nee.mode == RT_LIGHT_SAMPLING_ENV_TREE;   // §24, §26: the map is being sampled: it cannot leave, and its successor brings a distribution
     if (sampled && off)
-        return rt_fail(RT_ERR_INVALID, "rt_renderer_environment: the map is being sampled (light-sampling mode 32): switch light sampling off before taking the map away");
+        return rt_fail(RT_ERR_INVALID, "rt_renderer_environment: the map is being sampled (light-sampling mode %u): switch light sampling off before taking the map away", r->nee.mode);
     if (const int rc = wait_last_call(r)) return rc;   // launches already enqueued read the images and the texels that are replaced below
     if (sampled) {   // an all-black successor is refused here, and the old map stays as it is
-        if (const int rc = r->upload_environment("rt_renderer_environment: light-sampling mode 32 is on", width, height, rgb, true)) return rc;
+        if (const int rc = r->upload_environment(r->nee.mode == RT_LIGHT_SAMPLING_ENV ? "rt_renderer_environment: light-sampling mode 32 is on" : "rt_renderer_environment: light-sampling mode 48 is on", width, height, rgb, true)) return rc;
     }
     r->env.on = false;
     r->refine_done = 0;   // samples lit by another sky belong to another frame

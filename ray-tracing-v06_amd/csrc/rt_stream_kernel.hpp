@@ -261,13 +261,17 @@ __device__ __forceinline__ f3 texture_table_value(const uint4* tt, uint32_t imag
 // ENVL (mode RT_LIGHT_SAMPLING_ENV; EXT == 2 && NEE && TRI only, whether or not the world has a triangle): the light half draws its direction from
 //      the environment map — environment_sample on the distribution the tail's environment record points to — and the light density is the map's own
 //      (environment_density); the light table's pick, point, density loop and tree walk are compiled out.  No shadow ray: the direction is followed.
+// LTREE && ENVL (mode RT_LIGHT_SAMPLING_ENV_TREE): both at once.  The light half tosses once more between the map and mode 16's table (no toss
+//      when the table is empty: n_l == 0 is the map alone), the light density is the mean of the map's and the walk's, and an image-textured Lambertian hit is
+//      sampled as the diffuse hit it is — its albedo is looked up behind the direction, as ever.
 template <bool EXACT, bool FILTER, int BLOCK, int WORLD = RT_WORLD_BVH, int EXT = 0, bool BIG = false, bool WIDE = BIG, bool TOL = false, bool NEE = false, bool TRI = false,
           bool LTREE = false, bool ENVL = false>
 __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(StreamParams p) {
     static_assert(!NEE || (EXT >= 1 && WORLD != RT_WORLD_BVH_QUEUE), "light sampling: worlds with quads, walked by the stack or as a list");
     static_assert(!TRI || (EXT >= 1 && WORLD != RT_WORLD_BVH_QUEUE), "triangles: worlds with quads; a lane walk reads the kind from the flat record");
     static_assert(!LTREE || (NEE && TRI), "the light tree: one family, which knows all three kinds of light");
-    static_assert(!ENVL || (EXT == 2 && NEE && TRI && !LTREE), "environment light sampling: one family of the kernels that look the map up");
+    static_assert(!ENVL || (EXT == 2 && NEE && TRI), "environment light sampling: one family of the kernels that look the map up, and one more with the light tree");
+    constexpr bool ENVT = LTREE && ENVL;   // §26
     extern __shared__ uint4 lds[];
     const uint32_t tid = threadIdx.x;
     const uint32_t lane = tid & 63u;
@@ -708,14 +712,18 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                 } else {
                     RT_PT(11);
                     // NEE: the first draw of a Lambertian / checker hit picks the half of the mixture; the light half draws no on-unit vector
-                    const bool nee_mat = NEE && (mtype == RT_MAT_LAMBERTIAN || mtype == RT_MAT_LAMBERTIAN_CHECKER);
+                    const bool nee_mat = NEE && (mtype == RT_MAT_LAMBERTIAN || mtype == RT_MAT_LAMBERTIAN_CHECKER || (ENVT && mtype == RT_MAT_LAMBERTIAN_IMAGE));
                     const bool to_light = nee_mat && rng.next() < 0.5f;
+                    bool to_env = ENVL;   // §26: which light the light half goes to — the map unless a second draw says the table; with an empty table no draw is made
+                    if constexpr (ENVT) {
+                        if (to_light && __float_as_uint((quads + p.scene.n_quads * 5u)[0].x) != 0u) to_env = rng.next() < 0.5f;
+                    }
                     f3 on_unit = mk3(0.0f);
                     uint32_t nee_li = 0u, nee_quad = 0u;   // NEE, light half: the light drawn, and its quad index
                     bool to_sphere = false;                // ... or that it is a sphere light (§17), whose point is C + on_unit * r: the draw below serves it too
                     bool to_tri = false;                   // ... or a triangle light (§19, TRI only): a quad's two draws, folded into the triangle
-                    if constexpr (!ENVL)   // (§24: the map is the one light; its draws are made where the direction is)
-                    if (NEE && to_light) {
+                    if constexpr (!ENVL || LTREE)   // (§24: the map is the one light; its draws are made where the direction is)
+                    if (NEE && to_light && !(ENVT && to_env)) {
                         const float4* lights = quads + p.scene.n_quads * 5u;
                         const uint32_t n_l = __float_as_uint(lights[0].x);
                         if constexpr (LTREE) {   // §20: the smallest j with c_j > x, x = next * A; none (x rounded up to A): the last light
@@ -749,17 +757,20 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                         scattered_ok = !(dot(scatter_dir, normal) < 0 || near_zero(scatter_dir));
                     } else {
                         if constexpr (ENVL) {
-                            if (to_light) {   // §24: four draws, then the rule; the record through scalars as the miss branch reads it
+                            if (to_light && to_env) {   // §24: four draws, then the rule; the record through scalars as the miss branch reads it
                                 const EnvRecord er = load_env_record(p.scene.blob + p.scene.blob_vec4 + env_at);
                                 const float x1 = rng.next();
                                 const float x2 = rng.next();
                                 const float ea = rng.next();
                                 const float eb = rng.next();
                                 scatter_dir = environment_sample(er.dist, er.w, er.h, er.u0, x1, x2, ea, eb, nullptr);
-                            } else {
+                            } else if (!LTREE || !to_light) {
                                 scatter_dir = normal + on_unit;
                                 scattered_ok = !near_zero(scatter_dir);
                             }
+                        }
+                        if (ENVL && !(ENVT && to_light && !to_env)) {
+                            // (drawn above; §26: all but a light half that goes to the table, whose point is mode 16's below)
                         } else
                         if (NEE && to_light) {   // a point of light i, uniform over its area; the direction stays unnormalised
                             if (to_sphere) {
@@ -786,15 +797,20 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                             const float len2 = dot(d, d), len = sqrtf(len2), cosn = dot(normal, d) / len;
                             const float pdf_cos = cosn > 0 ? cosn * 0.318309886f : 0.0f;
                             float pdf_light = 0.0f;
+                            float pdf_env = 0.0f;
                             if constexpr (ENVL) {   // §24: the density of the texel §23's lookup puts d in; no division by a light count
                                 const EnvRecord er = load_env_record(p.scene.blob + p.scene.blob_vec4 + env_at);
-                                pdf_light = environment_density(er.texels, er.w, er.h, er.u0, d);
-                            } else {
+                                pdf_env = environment_density(er.texels, er.w, er.h, er.u0, d);
+                                if constexpr (!LTREE) pdf_light = pdf_env;
+                            }
+                            if constexpr (!ENVL || LTREE) {
                             const float4* lights = quads + p.scene.n_quads * 5u;
                             const uint32_t n_l = __float_as_uint(lights[0].x);
                             Ray lray;
                             lray.o = hit_p; lray.d = d; lray.time = ray.time;
                             if constexpr (LTREE) {
+                                if (ENVT && n_l == 0u) pdf_light = pdf_env;   // §26: an empty table: the map alone, and no walk
+                                else {
                                 // §20: the threaded tree of the lights' padded boxes, in preorder; a leaf met adds mode 4's term without its division by area_j,
                                 // in ascending table position — the linear loop's order with its zeros left out — and the sum is divided by A once
                                 const float4* tnodes = lights + 1u + 2u * n_l;
@@ -840,6 +856,8 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                                 }
                                 if (!own_met) scattered_ok = false;   // §17's silhouette rule, for a walk that may not reach the leaf
                                 pdf_light = pdf_light / lights[0].y;
+                                if constexpr (ENVT) pdf_light = 0.5f * pdf_env + 0.5f * pdf_light;   // §26: pm, the light half's own mixture
+                                }
                             } else {
                             for (uint32_t j = 0; j < n_l; j++) {
                                 const float4 lt = lights[1u + j];

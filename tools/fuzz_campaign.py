@@ -1,19 +1,23 @@
 #!/usr/bin/env python3
 """Differential fuzz campaign: random worlds (spheres, moving spheres, quads, triangles and meshes, lights, media, textures; every builder; LDS
 and global-memory paths; three cameras) rendered on the GPU and by the CPU oracle, compared bit for bit.
-    python tools/fuzz_campaign.py --seeds 200 [--first 0] [--no-triangles] [--mesh-lights] [--light-tree] [--texture-coords] [--textures]
+    python tools/fuzz_campaign.py --seeds 200 [--first 0] [--no-triangles] [--mesh-lights] [--light-tree] [--texture-coords] [--textures] [--env-tree]
 Prints one line per failure and a summary; exit code 1 if anything differed.  The triangles of a world come from a generator of their own, so the rest of a seed's
 world is what it was before the fuzzer made triangles, and --no-triangles renders exactly those earlier worlds.  Importing this file starts nothing:
 world_of_seed() builds a seed's world on the host, without a device.  --mesh-lights (off by default: the recorded campaigns ran without it) also renders every
 world that RT_LIGHT_SAMPLING_MESH accepts in that mode; it draws nothing, so the worlds, frames and cameras of a seed stay what they are.  --texture-coords
  gives random triangles of every world with an image and triangles random texture coordinates from [-0.5, 1.5) — wider than the unit square —,
-drawn from the seed's generator AFTER every other draw of the case, so committed seeds give the worlds, frames and cameras they gave."""
+drawn from the seed's generator AFTER every other draw of the case, so committed seeds give the worlds, frames and cameras they gave.  --env-tree
+puts every world with quads under the procedural sky as its LAST check — it draws nothing and the scene is not used again — and renders it in light-sampling
+mode 48: both memory forms, and the twin (tests/_env_tree_twin.py) where it follows."""
 import argparse, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import __graft_entry__ as G
+import _env_tree_twin as VT
+import _env_twin as ET
 import _light_tree_twin as LT
 import _mesh_light_twin as MT
 import _nee_twin as T
@@ -33,6 +37,7 @@ def parse_args(argv=None):
     ap.add_argument("--force-variant", type=int, default=None, help="render every world with this kernel variant; 6 (tolerance mode) is held to |delta| < 1e-3 and its differing frames are counted, not failed")
     ap.add_argument("--no-triangles", action="store_true", help="the worlds as they were before the fuzzer made triangles, byte for byte")
     ap.add_argument("--light-tree", action="store_true", help="also render the worlds that light-sampling mode 16 (the light tree, chosen by area) accepts in that mode: both memory forms, and the twin (tests/_light_tree_twin.py) where it follows")
+    ap.add_argument("--env-tree", action="store_true", help="also render the worlds with quads, put under the procedural sky, in light-sampling mode 48 (the map and the light tree together, image hits sampled): both memory forms, and the twin (tests/_env_tree_twin.py) where it follows")
     ap.add_argument("--mesh-lights", action="store_true", help="also render the worlds that light-sampling mode 4 (triangle and mesh lights) accepts in that mode: both memory forms, and the twin where it follows")
     ap.add_argument("--textures", action="store_true", help="also render the worlds with an image under a texture table of several random images and random modes: the world's image under clamp / nearest must be the oracle's frame, and under another mode pair both memory forms must agree")
     ap.add_argument("--texture-coords", action="store_true", help="also render the worlds with an image and triangles under a table of random texture coordinates on random triangles: both memory forms must agree, and the identity table must be the oracle's frame")
@@ -145,6 +150,49 @@ def light_sampling_check(p, s, w, cam, ck, W, H, depth, variant, mode=1):
         px = followed.all(axis=2)
         ok = ok and bits_equal(sums[0][px], T.in_order_sums(np.where(followed[..., None], samples, 0))[px])
     return ok, forms
+
+
+def env_tree_check(p, s, cam, ck, W, H, depth, variant):
+    """The world of a seed under image_io.sky_environment(32, 16) turned by 108 degrees (background mode 2), in mode 48 at 4 spp on at most 48 x 32
+    pixels: the renderer's own form and the global-memory form must agree in every bit, and both must be the twin on every pixel it follows (a pinhole camera,
+    the stack walk, no moving sphere; dielectrics and noise textures end the twin's following of a sample, image textures do not).  Changes the scene's
+    background: the caller runs it last.  None: not applicable (a medium, a lane walk, a kernel without the form); else (ok, forms, lights)."""
+    from ray_tracing_v06_amd import image_io
+    s.set_environment(image_io.sky_environment(32, 16), rotate_y=108.0)
+    w = s.getWorldPtr()
+    W, H, spp = min(W, 48), min(H, 32), 4
+    sums, forms, lights = [], [], 0
+    for env in ({}, {"RT06_FORCE_BIG": "1"}):
+        os.environ.pop("RT06_FORCE_BIG", None)
+        os.environ.update(env)
+        try:
+            r = p.Renderer.MakeRenderer(W, H, spp, depth, cam, w, variant=variant)
+            if r.kernel_info()["variant"] not in (2, 3):
+                return None
+            r.light_sampling("env+tree")
+        except p.capi.RtError:
+            return None   # no kernel for the world under a map, or a refusal of the mode (a medium, a lane walk, a light lost in the running sum)
+        finally:
+            os.environ.pop("RT06_FORCE_BIG", None)
+        forms.append(r.kernel_form())
+        lights = r.light_sampling_info()["lights"]
+        r.refine(spp)
+        sums.append(r.refine_sums())
+        r.close()
+    ok = bits_equal(sums[0], sums[1])
+    if ck == 0 and w.traversal == 0 and not (s.arrays()[1]["mat"] >> 31).any():
+        env_map, u0 = s.environment()
+        world = as_oracle_world(w)
+        tex = None
+        if w.image_width:   # the world's image, entry 0 under clamp / nearest, and the scene's texture coordinates if it has any
+            image0 = s.textures()[1][: w.image_width * w.image_height].reshape(w.image_height, w.image_width, 3)
+            uv = s.texture_coords()
+            tex = (uv if len(uv) else None, [(image0, 0, 0)])
+        samples, followed = VT.frame_samples(world, as_oracle_camera(cam), W, H, spp, depth, 1984, ET.sky_environment(env_map, u0),
+                                             light=(p.api.environment_distribution(env_map), u0), tree=VT.table_of(world), tex=tex)
+        px = followed.all(axis=2)
+        ok = ok and bits_equal(sums[0][px], T.in_order_sums(np.where(followed[..., None], samples, 0))[px])
+    return ok, forms, lights
 
 
 def texture_coords_check(p, s, w, cam, W, H, spp, depth, variant, rng, ref):
@@ -326,6 +374,14 @@ def main(argv=None):
                 if not tx[0]:
                     fails += 1
                     print(f"FAIL seed {seed} with a texture table: kinds {kinds} builder {builder} big {big} cam {ck} depth {depth} modes {tx[2]} forms {tx[1]}", flush=True)
+        if args.env_tree and ok and kinds >= 1 and info["variant"] in (2, 3) and not (big and builder == 3):   # last: it changes the scene's background
+            et = env_tree_check(p, s, cam, ck, W, H, depth, variant)
+            if et is not None:
+                stats["env_tree_sampling"] = stats.get("env_tree_sampling", 0) + 1
+                stats["env_tree_without_lights"] = stats.get("env_tree_without_lights", 0) + int(et[2] == 0)
+                if not et[0]:
+                    fails += 1
+                    print(f"FAIL seed {seed} with light sampling mode 48: kinds {kinds} triangles {s.n_triangles()} builder {builder} big {big} cam {ck} depth {depth} lights {et[2]} forms {et[1]}", flush=True)
         if (seed - args.first) % 25 == 24:
             print(f"... {seed - args.first + 1} worlds, {fails} failures, {time.time() - t0:.0f}s, paths {stats}", flush=True)
     print(f"DONE: {args.seeds} worlds, {fails} failures, paths {stats}, {time.time() - t0:.0f}s")

@@ -47,7 +47,8 @@ lights the world with an environment map (rt_scene_set_environment, DESIGN.md §
     python tools/render.py --scene three_spheres --env sky --light-sampling-mode env --spp 64 --out out.png
 
 draws half of every Lambertian hit's directions from the map itself, in proportion to radiance times solid angle (RT_LIGHT_SAMPLING_ENV): a small
-bright sun is found at once instead of by the few rays that happen to leave towards it.  Needs --env.
+bright sun is found at once instead of by the few rays that happen to leave towards it.  Needs --env.  `--light-sampling-mode env+tree` samples the map and the
+world's lights together (RT_LIGHT_SAMPLING_ENV_TREE), and samples at image-textured hits, which no other mode does.
 
     python tools/render.py --scene book2_final --mesh tests/golden/tex_demo.obj --mtl --texture-wrap repeat --texture-filter bilinear \
         --mesh-scale 120 --mesh-translate 150,160,120 --spp 64 --out out.png
@@ -73,9 +74,10 @@ ap.add_argument("--until", type=float, default=None, metavar="NOISE", help="with
 ap.add_argument("--denoise", action="store_true", help="with --refine: also write the denoised frame (<out>_denoised.<ext>)")
 ap.add_argument("--aov", default=None, metavar="PREFIX", help="with --refine: write PREFIX_normal.png, PREFIX_depth.png, PREFIX_albedo.png")
 ap.add_argument("--light-sampling", action="store_true", help="next-event estimation over the world's quad lights (rt_renderer_light_sampling_enable)")
-ap.add_argument("--light-sampling-mode", choices=["quads", "all", "mesh", "tree", "env"], default=None,
+ap.add_argument("--light-sampling-mode", choices=["quads", "all", "mesh", "tree", "env", "env+tree"], default=None,
                 help="switch light sampling on in this mode: quads (what --light-sampling selects), all (quad and sphere lights, e.g. --scene cornell_lamp) or "
-                     "mesh (those and triangle lights, e.g. --mesh ... --mesh-material light), tree (mesh's lights, up to 4096, by area through a light tree), env (the environment map of --env alone, by radiance times solid angle)")
+                     "mesh (those and triangle lights, e.g. --mesh ... --mesh-material light), tree (mesh's lights, up to 4096, by area through a light tree), env (the environment map of --env alone, by radiance times solid angle), "
+                     "env+tree (that map and tree's lights together, at image-textured hits too; a world without lights is taken as the map alone)")
 ap.add_argument("--mesh", default=None, metavar="FILE.obj|icosphere:LEVEL|tetrahedron", help="a triangle mesh to place into the scene (rt_scene_add_mesh)")
 ap.add_argument("--mesh-scale", type=float, default=1.0)
 ap.add_argument("--mesh-rotate-y", type=float, default=0.0, metavar="DEGREES")
@@ -96,7 +98,7 @@ ap.add_argument("--env-rotate", type=float, default=0.0, metavar="DEG", help="wi
 ap.add_argument("--env-scale", type=float, default=1.0, metavar="X", help="with --env: multiply the map's radiance, on the host before upload")
 ap.add_argument("--out", default="render.png")
 a = ap.parse_args()
-light_mode = {"quads": 1, "all": 2, "mesh": 4, "tree": 16, "env": 32}.get(a.light_sampling_mode, 1 if a.light_sampling else 0)   # RT_LIGHT_SAMPLING_*
+light_mode = {"quads": 1, "all": 2, "mesh": 4, "tree": 16, "env": 32, "env+tree": 48}.get(a.light_sampling_mode, 1 if a.light_sampling else 0)   # RT_LIGHT_SAMPLING_*
 if a.refine < 0 or (a.until is not None and (a.refine == 0 or a.gpus > 1)):
     ap.error("--until needs --refine STEP > 0 and one GPU (the multi-GPU renderer has no noise figure)")
 if (a.denoise or a.aov) and (a.refine == 0 or a.gpus > 1):
