@@ -363,6 +363,10 @@ int rt_scene_textures(const rt_scene* s, const rt_texture** out_records, uint32_
  * rt_renderer_textures would refuse, an index without an entry.                                                                                                 */
 int rt_texture_lookup_batch(const rt_texture* records, uint32_t n, const uint8_t* texels, const uint32_t* index, const float* u, const float* v, size_t count,
                             float* out_rgb);
+/* HOST (no GPU): noise_texture::value of "The Next Week" as the kernels compute it (RT_MAT_LAMBERTIAN_NOISE: albedo * (1 + sin(scale * z + 10 * turb(p, 7))), fp32,
+ * one fixed evaluation order, the library's own sine) — out_rgb[3 i ..] = the marble of `perlin` (rt_scene_set_perlin's tables) with the material's albedo and
+ * param (`scale`) at points[3 i ..].  The function the kernels call.  RT_ERR_INVALID: a null argument, whatever n.                                         */
+int rt_noise_value_batch(const rt_perlin* perlin, const float albedo[3], float scale, const float* points, size_t n, float* out_rgb);
 
 /* BVH_Handle::Factory::BuildBVH_TopDown -> _build_bvh_rec1 (BVH.cu:166-210):
  * median split on the longest axis, leaf size 1, post-order numbering, root =
@@ -576,8 +580,23 @@ int rt_renderer_refine_noise(rt_renderer* r, double* out);
  * path is untouched: frame and colour sums have the same bits with the buffers on or off.  Discards the refinement state, like
  * rt_renderer_refine_reset; afterwards the buffers share its lifecycle (reset, set_camera with other bytes: discarded; set_camera with
  * the same bytes, a Render() between steps: kept).  A sharded renderer accumulates its shard.  RT_ERR_INVALID: a renderer on the
- * baseline kernel (variant 1); a world with a constant medium (its first "hit" draws from the RNG), a noise or an image texture.       */
+ * baseline kernel (variant 1); a world with a constant medium (its first "hit" draws from the RNG), a noise or an image texture
+ * (rt_renderer_aov_enable_mode with RT_AOV_TEXTURED takes the last two).                                                               */
 int rt_renderer_aov_enable(rt_renderer* r, uint32_t max_samples);
+/* The same with a mode.  RT_AOV_PLAIN is rt_renderer_aov_enable, refusals and messages included.  RT_AOV_TEXTURED also covers the two textured Lambertians; every
+ * other material, the normal, the distance and the hit count are as above:
+ *   RT_MAT_LAMBERTIAN_NOISE: the marble at the hit point — rt_noise_value_batch's rule with the material's albedo and param;
+ *   RT_MAT_LAMBERTIAN_IMAGE: the texel the colour path shades that hit with: (u, v) of the hit — the sphere map of the outward normal, the planar coordinates on a
+ *   parallelogram, rt_tri_uvs' rule on a triangle while the renderer has texture coordinates (the planar coordinates otherwise) — looked up in the material's entry
+ *   (albedo2[0]) of the renderer's texture table, or, without a table, in the world's image.
+ * Tables given or taken away later (rt_renderer_textures, _texture_coords, _shading_normals) are followed: they restart the refinement anyway.  A launch whose
+ * materials name an entry the renderer does not have is refused before any kernel runs, as without features.  Enabling in either mode restarts the refinement;
+ * switching the mode is an enable.  RT_ERR_INVALID: variant 1; a constant medium (the message names RT_MAT_ISOTROPIC); an unknown mode.                        */
+#define RT_AOV_PLAIN    0u
+#define RT_AOV_TEXTURED 1u
+int rt_renderer_aov_enable_mode(rt_renderer* r, uint32_t max_samples, uint32_t mode);
+/* *out_mode = the mode of the last successful enable; RT_AOV_PLAIN before any */
+int rt_renderer_aov_mode(rt_renderer* r, uint32_t* out_mode);
 /* out[0] = 1 when enabled, out[1] = samples per pixel the buffers cover, out[2] = bytes held */
 int rt_renderer_aov_info(rt_renderer* r, uint64_t out[3]);
 /* width*height*8 floats, row-major like download, the two float4 of a pixel back to back, UNscaled; world_size == 1 only */
@@ -857,6 +876,8 @@ int rt_probe_environment(int device, size_t n, uint32_t width, uint32_t height, 
 /* rt_texture_lookup_batch on the device, one lane per lookup: the table as the renderer holds it (one 4-byte record per texel, the entries as vec4)              */
 int rt_probe_texture(int device, const rt_texture* records, uint32_t n, const uint8_t* texels, const uint32_t* index, const float* u, const float* v, size_t count,
                      float* out_rgb);
+/* rt_noise_value_batch on the device, one lane per point: the tables in global memory, as the renderer holds them                                              */
+int rt_probe_noise_value(int device, const rt_perlin* perlin, const float albedo[3], float scale, const float* points, size_t n, float* out_rgb);
 /* rt_environment_sample_batch on the device, one lane per quadruple: the records and the tables as the renderer holds them in mode RT_LIGHT_SAMPLING_ENV        */
 int rt_probe_environment_sample(int device, size_t n, uint32_t width, uint32_t height, const float* rgb, float u0, const float* uniforms, float* out_dir,
                                 uint32_t* out_texel, float* out_density);

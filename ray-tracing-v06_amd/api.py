@@ -575,9 +575,19 @@ class Renderer:
         check(lib().rt_renderer_refine_noise(self.h, C.byref(out)))
         return out.value
 
-    def enable_aov(self, max_samples=0):
-        """Accumulate first-hit feature buffers alongside every refine step from now on (restarts the refinement); max_samples = 0: every sample."""
-        check(lib().rt_renderer_aov_enable(self.h, max_samples))
+    def enable_aov(self, max_samples=0, textured=False):
+        """Accumulate first-hit feature buffers alongside every refine step from now on (restarts the refinement); max_samples = 0: every sample.
+        textured: mode RT_AOV_TEXTURED, which also covers noise and image materials (the plain mode refuses a world that has one)."""
+        if textured:
+            check(lib().rt_renderer_aov_enable_mode(self.h, max_samples, capi.AOV_TEXTURED))
+        else:
+            check(lib().rt_renderer_aov_enable(self.h, max_samples))
+
+    def aov_mode(self):
+        """'plain' or 'textured': the mode of the last successful enable_aov ('plain' before any)."""
+        out = C.c_uint32()
+        check(lib().rt_renderer_aov_mode(self.h, C.byref(out)))
+        return {capi.AOV_PLAIN: "plain", capi.AOV_TEXTURED: "textured"}[out.value]
 
     def aov_info(self):
         """{'enabled', 'samples', 'bytes'}: whether the feature buffers are on, the samples per pixel they cover, bytes held."""
@@ -1108,6 +1118,28 @@ def texture_lookup_batch(table, index, u, v):
 def probe_texture(table, index, u, v, device=0):
     """rt_probe_texture: texture_lookup_batch on the device, one lane per lookup"""
     return _texture_lookup(lambda *a: lib().rt_probe_texture(device, *a), table, index, u, v)
+
+
+def _noise_value(fn, world, albedo, scale, points):
+    perlin = world.perlin if hasattr(world, "perlin") else world   # a world (rt_world_flat) or the address of its rt_perlin
+    if not perlin:
+        raise ValueError("noise value: the world has no Perlin tables (Scene.set_perlin)")
+    albedo, points = np.ascontiguousarray(albedo, np.float32).reshape(3), np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    rgb = np.zeros((len(points), 3), np.float32)
+    if len(points):
+        check(fn(perlin, albedo.ctypes.data, float(scale), points.ctypes.data, len(points), rgb.ctypes.data))
+    return rgb
+
+
+def noise_value_batch(world, albedo, scale, points):
+    """rt_noise_value_batch (host only): the marble of RT_MAT_LAMBERTIAN_NOISE — the world's Perlin tables, the material's albedo and param
+    (`scale`) at points (n, 3) -> (n, 3) float32"""
+    return _noise_value(lib().rt_noise_value_batch, world, albedo, scale, points)
+
+
+def probe_noise_value(world, albedo, scale, points, device=0):
+    """rt_probe_noise_value: noise_value_batch on the device, one lane per point"""
+    return _noise_value(lambda *a: lib().rt_probe_noise_value(device, *a), world, albedo, scale, points)
 
 
 def environment_batch(image, u0, dirs):

@@ -36,6 +36,7 @@ TEXTURE_DT = np.dtype([("width", "<u4"), ("height", "<u4"), ("wrap", "<u4"), ("f
 WRAP_CLAMP, WRAP_REPEAT = 0, 1
 FILTER_NEAREST, FILTER_BILINEAR = 0, 1
 MAX_IMAGES = 256
+AOV_PLAIN, AOV_TEXTURED = 0, 1
 QUAD_DT = np.dtype([("Q", "<f4", 3), ("D", "<f4"), ("u", "<f4", 3), ("mat", "<u4"), ("v", "<f4", 3), ("kind", "<u4"),
                     ("normal", "<f4", 3), ("pad1", "<f4"), ("w", "<f4", 3), ("pad2", "<f4")])
 
@@ -103,6 +104,7 @@ SYMBOLS = [
     "rt_environment_distribution", "rt_environment_sample_batch", "rt_probe_environment_sample", "rt_renderer_kernel_env_light",
     "rt_scene_add_image", "rt_scene_image_sampling", "rt_scene_textures", "rt_texture_lookup_batch", "rt_renderer_textures", "rt_renderer_textures_info",
     "rt_multi_renderer_textures", "rt_multi_renderer_textures_info", "rt_probe_texture",
+    "rt_renderer_aov_enable_mode", "rt_renderer_aov_mode", "rt_noise_value_batch", "rt_probe_noise_value",
 ]
 
 _lib = None
@@ -261,6 +263,10 @@ def lib():
     L.rt_renderer_refine_noise.argtypes = [C.c_void_p, P(C.c_double)]
     L.rt_multi_renderer_refine.argtypes = [C.c_void_p, C.c_uint32]
     L.rt_renderer_aov_enable.argtypes = [C.c_void_p, C.c_uint32]
+    L.rt_renderer_aov_enable_mode.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
+    L.rt_renderer_aov_mode.argtypes = [C.c_void_p, C.c_void_p]
+    L.rt_noise_value_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.rt_probe_noise_value.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]
     L.rt_renderer_aov_info.argtypes = [C.c_void_p, C.c_uint64 * 3]
     L.rt_renderer_aov_download.argtypes = [C.c_void_p, f32p, C.c_size_t]
     L.rt_denoise_params_default.argtypes = [P(DenoiseParams)]

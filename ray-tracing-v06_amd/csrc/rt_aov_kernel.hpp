@@ -49,6 +49,32 @@ __device__ __forceinline__ f3 aov_albedo(const rt_material& m, const Ray& ray, c
         return checker_value(mk3(m.albedo[0], m.albedo[1], m.albedo[2]), mk3(m.albedo2[0], m.albedo2[1], m.albedo2[2]), m.param, ray_at(ray, rec.distance));
     return mk3(1.0f);
 }
+// Mode RT_AOV_TEXTURED: the two textured Lambertians too, restated from the leaf functions the shade phase calls (rt_stream_kernel.hpp, "(u, v) three
+// ways"), on the flat world's records — the same floats the packed image holds.  Noise: noise_value at the hit point.  Image: (u, v) of the hit — sphere_uv of the
+// OUTWARD normal (the trace returns a sphere's normal unflipped, as the shade phase computes it: a camera inside the sphere sees the same texel), quad_uv on a
+// parallelogram, tri_uv with the tail's record on a triangle when a table of texture coordinates is on (uv_at != 0), quad_uv otherwise — then the material's entry
+// of the tail's texture table (tex_at != 0; the entry is albedo2[0], the shade phase's fourth material lane) or the world's own image.  tail = the header behind the
+// image the colour pass launches on: (-, uv_at, -, tex_at), wave-uniform.  A launch whose materials name an entry the renderer lacks is refused before any kernel.
+__device__ __forceinline__ f3 aov_albedo_tex(const DeviceWorld& w, const uint4* tail, uint32_t uv_at, uint32_t tex_at, uint32_t first_tri, const rt_material& m,
+                                             const Ray& ray, const HitRec& rec) {
+    if (m.type == RT_MAT_LAMBERTIAN_NOISE) return noise_value(w.perlin, mk3(m.albedo[0], m.albedo[1], m.albedo[2]), m.param, ray_at(ray, rec.distance));
+    if (m.type != RT_MAT_LAMBERTIAN_IMAGE) return aov_albedo(m, ray, rec);
+    float tu, tv;
+    if ((uint32_t)rec.prim >= w.n_prims) {
+        const rt_quad& q = w.quads[(uint32_t)rec.prim - w.n_prims];
+        const f3 hit_p = ray_at(ray, rec.distance);
+        if (uv_at != 0u && (uint32_t)rec.prim >= first_tri) {
+            const float* tr = reinterpret_cast<const float*>(tail + uv_at) + (size_t)((uint32_t)rec.prim - first_tri) * 6u;
+            const float t0[2] = {tr[0], tr[1]}, t1[2] = {tr[2], tr[3]}, t2[2] = {tr[4], tr[5]};
+            tri_uv(ld3(q.Q), ld3(q.u), ld3(q.v), ld3(q.w), t0, t1, t2, hit_p, tu, tv);
+        } else
+        quad_uv(ld3(q.Q), ld3(q.u), ld3(q.v), ld3(q.w), hit_p, tu, tv);
+    } else {
+        sphere_uv(rec.normal, tu, tv);
+    }
+    if (tex_at != 0u) return texture_table_value(tail + tex_at, (uint32_t)m.albedo2[0], tu, tv);
+    return image_texel(w.image, w.image_w, w.image_h, tu, tv);
+}
 
 // what the feature pass reads of a refine pass (a StreamParams would occupy scalar registers the traversal needs)
 struct AovParams {
@@ -61,8 +87,10 @@ struct AovParams {
 };
 
 // SMOOTH (aov_kernel_smooth): a hit on a triangle — unified index >= first_tri — takes its normal through shading_normal() from the table's record
-template <int WALK, bool SMOOTH>
-__device__ __forceinline__ void aov_body(const AovParams& p, float4* __restrict__ aov, int32_t* lds_i, float* lds_f, const rt_tri_normals* vn, uint32_t first_tri) {
+// TEX (aov_kernel_tex / aov_kernel_smooth_tex): the albedo is aov_albedo_tex's; tail = the header of the image's tail, first_tri as above
+template <int WALK, bool SMOOTH, bool TEX = false>
+__device__ __forceinline__ void aov_body(const AovParams& p, float4* __restrict__ aov, int32_t* lds_i, float* lds_f, const rt_tri_normals* vn, uint32_t first_tri,
+                                         const uint4* tail = nullptr) {
     const uint32_t L = blockIdx.x * RT_AOV_BLOCK + threadIdx.x;
     if (L >= p.tm.n_local_tiles * RT_TILE * RT_TILE) return;
     uint32_t gid;
@@ -70,6 +98,11 @@ __device__ __forceinline__ void aov_body(const AovParams& p, float4* __restrict_
     float4 g = make_float4(0.0f, 0.0f, 0.0f, 0.0f), a = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (p.pass_first_s != 0u) { g = aov[2u * L]; a = aov[2u * L + 1u]; }
     size_t src = (size_t)(L >> 6) * p.pass_spp * 64u + (L & 63u);
+    uint32_t uv_at = 0u, tex_at = 0u;
+    if constexpr (TEX) {   // the tail header's second and fourth words: the same for every lane
+        const uint4 th = tail[0];
+        uv_at = (uint32_t)__builtin_amdgcn_readfirstlane((int)th.y); tex_at = (uint32_t)__builtin_amdgcn_readfirstlane((int)th.w);
+    }
     for (uint32_t s = 0; s < p.n_take; s++) {
         const float4 o = p.prim_o[src], d = p.prim_d[src];
         Ray ray;
@@ -78,7 +111,8 @@ __device__ __forceinline__ void aov_body(const AovParams& p, float4* __restrict_
         rec.distance = RT_MISS_DIST; rec.normal = mk3(0.0f); rec.prim = -1; rec.mat = 0;   // as sample_world starts a trace
         f3 alb = mk3(1.0f);
         if (aov_first_hit<WALK>(p.world, ray, rec, lds_i, lds_f)) {
-            alb = aov_albedo(p.world.mats[rec.mat], ray, rec);
+            if constexpr (TEX) alb = aov_albedo_tex(p.world, tail, uv_at, tex_at, first_tri, p.world.mats[rec.mat], ray, rec);
+            else alb = aov_albedo(p.world.mats[rec.mat], ray, rec);
             if (SMOOTH && (uint32_t)rec.prim >= first_tri) shading_normal_flat(p.world.quads[(uint32_t)rec.prim - p.world.n_prims], vn[(uint32_t)rec.prim - first_tri], ray, rec.distance, rec.normal);
             g.x += rec.normal.x; g.y += rec.normal.y; g.z += rec.normal.z; g.w += rec.distance;
             a.w += 1.0f;
@@ -102,6 +136,22 @@ __global__ __launch_bounds__(RT_AOV_BLOCK) void aov_kernel_smooth(AovParams p, f
     __shared__ int32_t lds_i[WALK == RT_AOV_WALK_LIST ? 1u : RT_MAX_STACK * RT_AOV_BLOCK];
     __shared__ float lds_f[1u];
     aov_body<WALK, true>(p, aov, lds_i, lds_f, vn, first_tri);
+}
+// mode RT_AOV_TEXTURED: the same passes with aov_albedo_tex.  What they need beyond AovParams — the tail's header and the first triangle's unified index — are
+// arguments of these kernels only (the Perlin tables and the world's own image are in AovParams' DeviceWorld already), so the plain forms' parameter block is as it was.
+template <int WALK>
+__global__ __launch_bounds__(RT_AOV_BLOCK) void aov_kernel_tex(AovParams p, float4* __restrict__ aov, const uint4* __restrict__ blob, uint32_t blob_vec4, uint32_t first_tri) {
+    __shared__ int32_t lds_i[WALK == RT_AOV_WALK_LIST ? 1u : RT_MAX_STACK * RT_AOV_BLOCK];
+    __shared__ float lds_f[WALK == RT_AOV_WALK_QUEUE ? RT_MAX_STACK * RT_AOV_BLOCK : 1u];
+    aov_body<WALK, false, true>(p, aov, lds_i, lds_f, nullptr, first_tri, blob + blob_vec4);
+}
+template <int WALK>
+__global__ __launch_bounds__(RT_AOV_BLOCK) void aov_kernel_smooth_tex(AovParams p, float4* __restrict__ aov, const rt_tri_normals* __restrict__ vn, const uint4* __restrict__ blob,
+                                                                      uint32_t blob_vec4, uint32_t first_tri) {
+    static_assert(WALK == RT_AOV_WALK_LIST || WALK == RT_AOV_WALK_STACK, "vertex normals: lists and stack-walked BVHs");
+    __shared__ int32_t lds_i[WALK == RT_AOV_WALK_LIST ? 1u : RT_MAX_STACK * RT_AOV_BLOCK];
+    __shared__ float lds_f[1u];
+    aov_body<WALK, true, true>(p, aov, lds_i, lds_f, vn, first_tri, blob + blob_vec4);
 }
 
 // ---------------------------------------------------------------------------------------------

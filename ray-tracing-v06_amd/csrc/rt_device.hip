@@ -165,6 +165,14 @@ static decltype(&aov_kernel<RT_AOV_WALK_STACK>) aov_kernel_for(const DeviceWorld
     if (w.traversal == RT_TRAVERSAL_WIDE4) return &aov_kernel<RT_AOV_WALK_WIDE4>;
     return &aov_kernel<RT_AOV_WALK_STACK>;
 }
+// ... and its RT_AOV_TEXTURED form
+static decltype(&aov_kernel_tex<RT_AOV_WALK_STACK>) aov_kernel_tex_for(const DeviceWorld& w) {
+    if (w.kind == RT_WORLD_LIST) return &aov_kernel_tex<RT_AOV_WALK_LIST>;
+    if (w.kind == RT_WORLD_NODE_TREE) return &aov_kernel_tex<RT_AOV_WALK_TREE>;
+    if (w.traversal == RT_TRAVERSAL_QUEUE) return &aov_kernel_tex<RT_AOV_WALK_QUEUE>;
+    if (w.traversal == RT_TRAVERSAL_WIDE4) return &aov_kernel_tex<RT_AOV_WALK_WIDE4>;
+    return &aov_kernel_tex<RT_AOV_WALK_STACK>;
+}
 
 // ---------------------------------------------------------------------------------------------
 // Renderer
@@ -230,7 +238,8 @@ struct rt_renderer {
     DevBuf aov;
     bool aov_on = false;
     uint32_t aov_max = 0, aov_done = 0;
-    const char* aov_refused = nullptr;   // the first material of the world the feature pass does not cover (a medium, a noise or an image texture)
+    uint32_t aov_mode = RT_AOV_PLAIN;    // the mode of the last successful enable: RT_AOV_TEXTURED launches the TEX forms
+    const char* aov_refused = nullptr;   // the first material of the world the plain feature pass does not cover (a medium, a noise or an image texture)
     // light sampling (rt_renderer_light_sampling_enable): per mode (tab[slot(mode)]) the world's lights as rt_world_light_table gave them at creation (or why it
     // gave none) and — from the first enable of that mode — the scene image with its light table behind it and the LDS that takes; one NEE form of this renderer's
     // kernel serves all three modes (they differ only in what the table holds)
@@ -763,8 +772,15 @@ struct rt_renderer {
         p.tm = sp.tm; p.world = sp.world;
         p.pass_first_s = sp.pass_first_s; p.pass_spp = sp.pass_spp; p.n_take = upto - sp.pass_first_s;
         p.prim_o = sp.prim_o; p.prim_d = sp.prim_d;
+        const uint32_t first_tri = scene.dw.n_prims + scene.dw.n_quads - scene.n_triangles;
+        if (aov_mode == RT_AOV_TEXTURED) {   // §27: the plain image's tail, or — no table on — the image itself, whose header is zero; every tail holds the same tables
+            const uint4* blob = (tail_on() ? tail.blob : scene.blob).as<uint4>();
+            const uint32_t blob_vec4 = scene.packed.blob_vec4;
+            if (!vn.on) aov_kernel_tex_for(scene.dw)<<<grid, block, 0, st>>>(p, aov.as<float4>(), blob, blob_vec4, first_tri);
+            else if (scene.dw.kind == RT_WORLD_LIST) aov_kernel_smooth_tex<RT_AOV_WALK_LIST><<<grid, block, 0, st>>>(p, aov.as<float4>(), vn.table.as<rt_tri_normals>(), blob, blob_vec4, first_tri);
+            else aov_kernel_smooth_tex<RT_AOV_WALK_STACK><<<grid, block, 0, st>>>(p, aov.as<float4>(), vn.table.as<rt_tri_normals>(), blob, blob_vec4, first_tri);
+        } else
         if (vn.on) {   // §21: the first-hit normal is the shading normal; a table is on only where the world is a list or a BVH walked by the stack
-            const uint32_t first_tri = scene.dw.n_prims + scene.dw.n_quads - scene.n_triangles;
             if (scene.dw.kind == RT_WORLD_LIST) aov_kernel_smooth<RT_AOV_WALK_LIST><<<grid, block, 0, st>>>(p, aov.as<float4>(), vn.table.as<rt_tri_normals>(), first_tri);
             else aov_kernel_smooth<RT_AOV_WALK_STACK><<<grid, block, 0, st>>>(p, aov.as<float4>(), vn.table.as<rt_tri_normals>(), first_tri);
         } else
@@ -1286,18 +1302,31 @@ extern "C" int rt_renderer_refine_noise(rt_renderer* r, double* out) {
 // ---------------------------------------------------------------------------------------------
 // Feature buffers and denoiser (rt06.h; kernels: rt_aov_kernel.hpp)
 // ---------------------------------------------------------------------------------------------
-extern "C" int rt_renderer_aov_enable(rt_renderer* r, uint32_t max_samples) {
-    if (!r) return rt_fail(RT_ERR_INVALID, "rt_renderer_aov_enable: null renderer");
+// `who` = the entry point the caller used: rt_renderer_aov_enable keeps its messages
+static int aov_enable(const char* who, rt_renderer* r, uint32_t max_samples, uint32_t mode) {
+    if (!r) return rt_fail(RT_ERR_INVALID, "%s: null renderer", who);
+    if (mode > RT_AOV_TEXTURED) return rt_fail(RT_ERR_INVALID, "%s: unknown mode %u (RT_AOV_PLAIN = 0, RT_AOV_TEXTURED = 1)", who, mode);
     if (r->variant < 2)
-        return rt_fail(RT_ERR_INVALID, "rt_renderer_aov_enable: the baseline kernel (variant 1) cannot refine and keeps no primary-ray records; feature buffers need a streaming variant (0, or 2 to 6)");
-    if (r->aov_refused)
-        return rt_fail(RT_ERR_INVALID, "rt_renderer_aov_enable: the world has %s: the feature pass covers spheres and quads with Lambertian, metal, dielectric, checker and light materials", r->aov_refused);
+        return rt_fail(RT_ERR_INVALID, "%s: the baseline kernel (variant 1) cannot refine and keeps no primary-ray records; feature buffers need a streaming variant (0, or 2 to 6)", who);
+    if (mode == RT_AOV_PLAIN && r->aov_refused)
+        return rt_fail(RT_ERR_INVALID, "%s: the world has %s: the feature pass covers spheres and quads with Lambertian, metal, dielectric, checker and light materials", who, r->aov_refused);
+    if (mode == RT_AOV_TEXTURED && r->has_medium)   // §27: a medium's first event is an RNG draw, which no trace of the feature pass makes
+        return rt_fail(RT_ERR_INVALID, "%s: the world has a constant medium (RT_MAT_ISOTROPIC): the textured feature pass covers spheres and quads with Lambertian, metal, dielectric, checker, light, noise and image materials", who);
     HIP_TRY(hipSetDevice(r->cfg.device));
     if (!r->aov.p) HIP_TRY(r->aov.alloc_zeroed(n_local_pixels(r->tm) * 2u * sizeof(float4)));   // padding pixels are never written: they read as zeros
     r->aov_on = true;
+    r->aov_mode = mode;
     r->aov_max = max_samples;
     r->refine_done = 0;   // like rt_renderer_refine_reset: colour and features restart together
     r->aov_done = 0;
+    return RT_OK;
+}
+extern "C" int rt_renderer_aov_enable(rt_renderer* r, uint32_t max_samples) { return aov_enable("rt_renderer_aov_enable", r, max_samples, RT_AOV_PLAIN); }
+extern "C" int rt_renderer_aov_enable_mode(rt_renderer* r, uint32_t max_samples, uint32_t mode) { return aov_enable("rt_renderer_aov_enable_mode", r, max_samples, mode); }
+
+extern "C" int rt_renderer_aov_mode(rt_renderer* r, uint32_t* out_mode) {
+    if (!r || !out_mode) return rt_fail(RT_ERR_INVALID, "rt_renderer_aov_mode: null argument");
+    *out_mode = r->aov_mode;
     return RT_OK;
 }
 

@@ -95,6 +95,11 @@ __global__ void probe_texture_kernel(size_t n, const uint32_t* texels, const uin
     if (i >= n) return;
     st3(out_rgb + 3 * i, texture_value(texels, entries[index[i]], u[i], v[i]));
 }
+__global__ void probe_noise_value_kernel(size_t n, const rt_perlin* perlin, f3 albedo, float scale, const float* points, float* out_rgb) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    st3(out_rgb + 3 * i, noise_value(perlin, albedo, scale, ld3(points + 3 * i)));
+}
 // SphereHittable / MovingSphereHittable::ClosestIntersection on one sphere per ray, rec.distance preset by the caller: the leaf
 // test every traversal calls (prim_closest_intersection), as a plain sphere (material 0 = a Lambertian, the moving bit kept)
 __global__ void probe_sphere_hit_kernel(size_t n, const rt_prim* prims, const rt_material* mat, const float* rays, const float* preset,
@@ -432,6 +437,21 @@ extern "C" int rt_texture_lookup_batch(const rt_texture* records, uint32_t n, co
     TextureTable t;
     if (const int rc = texture_table_args("rt_texture_lookup_batch", records, n, texels, index, u, v, count, out_rgb, t)) return rc;
     for (size_t i = 0; i < count; i++) st3(out_rgb + 3 * i, texture_value(t.dwords.data(), t.entries[index[i]], u[i], v[i]));
+    return RT_OK;
+}
+// The marble: the kernels' noise_value() over arrays, on the device and — HOST (no GPU) — here
+extern "C" int rt_probe_noise_value(int device, const rt_perlin* perlin, const float albedo[3], float scale, const float* points, size_t n, float* out_rgb) {
+    if (!perlin || !albedo || !points || !out_rgb) return rt_fail(RT_ERR_INVALID, "rt_probe_noise_value: null argument");
+    if (n == 0) return RT_OK;
+    ProbeRun p(device);
+    auto t = p.in(perlin, 1); auto pt = p.in(points, 3 * n);
+    auto o = p.out(out_rgb, 3 * n);
+    p.launch(probe_noise_value_kernel, p.per_case(n), 128, n, t, ld3(albedo), scale, pt, o);
+    return p.finish();
+}
+extern "C" int rt_noise_value_batch(const rt_perlin* perlin, const float albedo[3], float scale, const float* points, size_t n, float* out_rgb) {
+    if (!perlin || !albedo || !points || !out_rgb) return rt_fail(RT_ERR_INVALID, "rt_noise_value_batch: null argument");
+    for (size_t i = 0; i < n; i++) st3(out_rgb + 3 * i, noise_value(perlin, ld3(albedo), scale, ld3(points + 3 * i)));
     return RT_OK;
 }
 // HOST (no GPU): the kernels' tri_uv() over arrays

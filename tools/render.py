@@ -16,7 +16,8 @@ last refined frame: bit for bit the frame a one-shot render at that sample count
 
 also accumulates first-hit feature buffers (rt_renderer_aov_enable) while refining.  --denoise writes the edge-aware filtered frame
 (rt_renderer_denoise) next to the refined one, as out_denoised.png; --aov PREFIX writes PREFIX_normal.png (n * 0.5 + 0.5),
-PREFIX_depth.png (nearest white, misses black) and PREFIX_albedo.png.  One GPU; worlds with media, noise or image textures are refused.
+PREFIX_depth.png (nearest white, misses black) and PREFIX_albedo.png.  One GPU; a world with a noise or an image texture takes the textured
+feature mode (rt_renderer_aov_enable_mode, DESIGN.md §27: the albedo is the first hit's marble or texel); worlds with media are refused.
 
     python tools/render.py --scene cornell_box --spp 64 --light-sampling --out out.png
 
@@ -201,8 +202,13 @@ if a.refine:
          else p.Renderer.MakeRenderer(W, H, step_spp, a.depth, cam, scene.getWorldPtr(), seed=a.seed, device=a.device))
     if light_mode:
         r.light_sampling(light_mode)
-    if a.denoise or a.aov:
-        r.enable_aov()
+    if a.denoise or a.aov:   # a world with a noise or an image material takes the textured feature mode; every other one the plain mode, as ever
+        import ctypes
+        import numpy as np
+        flat = scene.getWorldPtr()
+        kinds = np.frombuffer((ctypes.c_char * (flat.n_materials * p.capi.MAT_DT.itemsize)).from_address(flat.materials), dtype=p.capi.MAT_DT)["type"]
+        textured = bool(np.isin(kinds, (p.capi.MAT_LAMBERTIAN_NOISE, p.capi.MAT_LAMBERTIAN_IMAGE)).any())
+        r.enable_aov(textured=textured)
     samples, ms = 0, 0.0
     while samples < a.spp:
         n = min(a.refine, a.spp - samples)
@@ -230,7 +236,7 @@ fb = r.DownloadRenderbuffer()
 # .jpg = the reference app's own format (stbi_write_jpg quality 95, FirstApp.cpp:120); .ppm / .png are lossless
 writer = image_io.write_ppm if a.out.endswith(".ppm") else image_io.write_jpg if a.out.endswith((".jpg", ".jpeg")) else image_io.write_png
 writer(a.out, fb)
-extra = {}
+extra = {"aov_mode": r.aov_mode()} if a.denoise or a.aov else {}
 if a.denoise:   # (with --refine only: `time` is imported there)
     t0 = time.perf_counter()
     den = r.denoise()
