@@ -6,6 +6,8 @@
 #include "rt_stream_kernel.hpp"
 #include "rt_xchg_kernel.hpp"
 #include "rt_aov_kernel.hpp"
+#include "rt_launch_image.hpp"
+static_assert(sizeof(rt_image::Vec4) == sizeof(uint4), "the unit of a launch image is uint4");
 
 extern "C" int rt_device_info(int device, uint32_t out[4]) {
     if (!out) return rt_fail(RT_ERR_INVALID, "rt_device_info: null out");
@@ -179,6 +181,31 @@ static decltype(&aov_kernel_tex<RT_AOV_WALK_STACK>) aov_kernel_tex_for(const Dev
 // ---------------------------------------------------------------------------------------------
 static bool another_renderer_busy(const rt_renderer* self);   // is the last call of another renderer on self's device still unfinished?
 
+// a device buffer that can change hands: what is replaced as a whole (a launch image, a rider's table) is built aside and swapped in
+struct OwnedBuf : DevBuf {
+    OwnedBuf() = default;
+    OwnedBuf(OwnedBuf&& o) noexcept { *this = std::move(o); }
+    OwnedBuf& operator=(OwnedBuf&& o) noexcept { std::swap(p, o.p); std::swap(bytes, o.bytes); return *this; }
+};
+
+// The light-sampling modes, a row each: the image the mode launches on (0: the plain one; 1 to 4: the one with the light table of mode 1, 2, 4, 16 — rows 0 to 3
+// in that order), the key bits it adds to stream_kernel_key() (a world without triangles is a TRI world too), whether it samples the environment map (§24, §26:
+// it then needs the map and its distribution, and refuses what the map's estimator does not cover), and the pieces of its refusals.
+struct LightMode { uint32_t mode, image, key_bits; bool env; const char *tag, *beside, *medium, *no_form; };
+static const LightMode LIGHT_MODES[6] = {
+    {RT_LIGHT_SAMPLING_QUADS, 1u, RT_KEY_NEE, false, "", "", "", "this world's kernel has no light-sampling form"},
+    {RT_LIGHT_SAMPLING_ALL, 2u, RT_KEY_NEE, false, "", "", "", "this world's kernel has no light-sampling form"},
+    {RT_LIGHT_SAMPLING_MESH, 3u, RT_KEY_NEE, false, "", "", "", "this world's kernel has no light-sampling form"},
+    {RT_LIGHT_SAMPLING_TREE, 4u, RT_KEY_NEE | RT_KEY_TRI | RT_KEY_LTREE, false, "", "", "", "this world's kernel has no light-sampling form"},
+    {RT_LIGHT_SAMPLING_ENV, 0u, RT_KEY_NEE | RT_KEY_TRI | RT_KEY_ENVL, true, "mode 32: ", "", "which the environment estimator does not cover", "this world's kernel has no environment-sampling form"},
+    {RT_LIGHT_SAMPLING_ENV_TREE, 4u, RT_KEY_NEE | RT_KEY_TRI | RT_KEY_LTREE | RT_KEY_ENVL, true, "mode 48: ", " beside its lights",
+     "which neither the environment estimator nor the light tree covers", "this world's kernel has no form that samples the map and the light tree"},
+};
+static const LightMode* light_mode(uint32_t mode) {   // NULL: off, or no mode
+    for (const LightMode& m : LIGHT_MODES) if (m.mode == mode) return &m;
+    return nullptr;
+}
+
 struct rt_renderer {
     rt_render_config cfg{};
     rt_camera cam{};
@@ -240,35 +267,29 @@ struct rt_renderer {
     uint32_t aov_max = 0, aov_done = 0;
     uint32_t aov_mode = RT_AOV_PLAIN;    // the mode of the last successful enable: RT_AOV_TEXTURED launches the TEX forms
     const char* aov_refused = nullptr;   // the first material of the world the plain feature pass does not cover (a medium, a noise or an image texture)
-    // light sampling (rt_renderer_light_sampling_enable): per mode (tab[slot(mode)]) the world's lights as rt_world_light_table gave them at creation (or why it
-    // gave none) and — from the first enable of that mode — the scene image with its light table behind it and the LDS that takes; one NEE form of this renderer's
-    // kernel serves all three modes (they differ only in what the table holds)
-    // (mode RT_LIGHT_SAMPLING_TREE, §20, has a family of its own — `key` says which form a table runs — and, behind the table, cdf in the entries and the tree's nodes)
+    // light sampling (rt_renderer_light_sampling_enable).  tab[i]: the world's lights as rt_world_light_table gave them at creation for the table modes 1, 2, 4
+    // and 16 (or why it gave none; mode 16, §20, with cdf and the tree's nodes).  image[0]: the plain image; image[1 + i]: the image with tab[i]'s table, from
+    // the first enable of a mode that launches on it.  resolved[k]: the key and the kernel of LIGHT_MODES[k], from its first enable.  launch_on() reads them.
     struct LightTable { uint32_t n = 0; std::vector<uint32_t> kind, index; std::vector<float> area, sphere /* 4 per light */, cdf, nodes /* 8 per node */;
-                        std::string refused; bool none = false /* refused for having no light: what mode 48 accepts (§26) */; DevBuf blob; uint32_t table_vec4 = 0, lds_bytes = 0, blocks_per_cu = 0, key = 0; const void* kernel = nullptr; bool built = false; };
-    // (mode RT_LIGHT_SAMPLING_ENV, §24, has no table: its slot holds the key, the kernel and the LDS of the plain image, and its launches run on tail.blob)
-    // (mode RT_LIGHT_SAMPLING_ENV_TREE, §26, runs on mode 16's image — image_slot — and its own slot holds the key, the kernel, n_l and a copy of that image's sizes)
-    struct { uint32_t mode = RT_LIGHT_SAMPLING_OFF; LightTable tab[6]; const void* kernel = nullptr;   // kernel: the current mode's
-             bool on() const { return mode != RT_LIGHT_SAMPLING_OFF; }
-             static uint32_t slot(uint32_t m) { return m == RT_LIGHT_SAMPLING_ENV_TREE ? 5u : m == RT_LIGHT_SAMPLING_ENV ? 4u : m == RT_LIGHT_SAMPLING_TREE ? 3u : m == RT_LIGHT_SAMPLING_MESH ? 2u : m - 1u; }   // modes 1, 2, 4, 16, 32, 48
-             static uint32_t image_slot(uint32_t m) { return slot(m == RT_LIGHT_SAMPLING_ENV_TREE ? RT_LIGHT_SAMPLING_TREE : m); }   // whose image (and tail) the mode launches on
-             const LightTable& cur() const { return tab[slot(mode)]; } } nee;
-    // smooth shading (rt_renderer_shading_normals): the table as given (9 floats per triangle of the world), a flat copy for the feature pass, and
-    // the images the triangle kernels launch on while it is on — the plain image and, per light-sampling mode already built, the image with that mode's light
-    // table — each followed by the header (1, -, -, -) and the table.  Off, every launch gets the image it always got, whose header is zero.
-    struct { bool on = false; uint32_t n_smooth = 0; std::vector<float> host; DevBuf table; } vn;
-    // texture coordinates (rt_renderer_texture_coords): the table as given (6 floats per triangle of the world); it rides in the same tail
+                        std::string refused; bool none = false /* refused for having no light: what mode 48 accepts (§26) */; };
+    // One launch image ("The launch images"): scene | light table (if any) | tail header | tail (if any), in ONE device buffer, composed anew
+    // whenever a rider changes.  The plain image while no rider is on is scene.blob itself: its buffer here stays empty.
+    struct Image { OwnedBuf blob; uint32_t table_vec4 = 0, lds_bytes = 0, blocks_per_cu = 0; };
+    struct { uint32_t mode = RT_LIGHT_SAMPLING_OFF; LightTable tab[4]; Image image[5]; struct { uint32_t key = 0; const void* kernel = nullptr; } resolved[6];
+             bool on() const { return mode != RT_LIGHT_SAMPLING_OFF; } } nee;
+    // The riders: what every launch image carries in its tail while it is on.  Each setter builds the next state of its rider and hands it to replace_rider().
+    // smooth shading (rt_renderer_shading_normals): the table as given (9 floats per triangle of the world) and a flat copy for the feature pass
+    struct { bool on = false; uint32_t n_smooth = 0; std::vector<float> host; OwnedBuf table; } vn;
+    // texture coordinates (rt_renderer_texture_coords): the table as given (6 floats per triangle of the world)
     struct { bool on = false; uint32_t n_mapped = 0; std::vector<float> host; } uv;
     // the environment map (rt_renderer_environment) of a background-2 world: the image as given (3 floats per texel) and a device buffer of the
-    // renderer's own with one float4 per texel; the tail carries only a two-vec4 record that points to it (a 2048 x 1024 map is 32 MiB, and there are up to five tails)
+    // renderer's own with one float4 per texel; the tail carries only a two-vec4 record that points to it (a 2048 x 1024 map is 32 MiB, and there are up to five images)
     // (§24: while dist_on, the records' fourth lane holds the sampling density and `dist` rowc[H], rowy[H + 1], colc[H W] of rt_environment_distribution)
-    struct { bool on = false, dist_on = false; uint32_t w = 0, h = 0; float u0 = 0.0f; std::vector<float> host; DevBuf texels, dist; } env;
-    bool has_medium = false;   // the world has a constant medium (RT_MAT_ISOTROPIC): mode RT_LIGHT_SAMPLING_ENV refuses it
+    struct Environment { bool on = false, dist_on = false; uint32_t w = 0, h = 0; float u0 = 0.0f; std::vector<float> host; OwnedBuf texels, dist; } env;
+    bool has_medium = false;   // the world has a constant medium (RT_MAT_ISOTROPIC): the modes that sample the map refuse it
     // the texture table (rt_renderer_textures): the entries and the texels as given (3 bytes per texel), and a device buffer of the renderer's own
     // with one dword r | g << 8 | b << 16 per texel, all images back to back; the tail carries (pointer low, pointer high, n, -) and one vec4 per entry
-    struct { bool on = false; std::vector<rt_texture> records; std::vector<uint8_t> host; DevBuf texels; } tex;
-    // the images with a tail, held while any of the four is on: the plain image's and each built light-sampling mode's
-    struct { DevBuf blob, nee_blob[4]; } tail;
+    struct { bool on = false; std::vector<rt_texture> records; std::vector<uint8_t> host; OwnedBuf texels; } tex;
     bool tail_on() const { return vn.on || uv.on || env.on || tex.on; }
     // whether a launch is refused for its image materials (§25): one of them names an entry (*which) the renderer does not have
     bool texture_entry_missing(uint32_t* which) const {
@@ -276,110 +297,87 @@ struct rt_renderer {
             if (tex.on ? (k >= tex.records.size() || tex.records[k].width == 0u) : k != 0u) { *which = k; return true; }
         return false;
     }
-    // `src` holds staged_vec4 units of image (and a zero header); dst = the same units, then the header (normals follow at +1 ? 1 : 0, vec4 from the header to
-    // the texture coordinates or 0, vec4 from the header to the environment record or 0, vec4 from the header to the texture table or 0 — §25, written last), then
-    // the normals if on, then the texture coordinates if on — each
-    // table from a 16-byte boundary — then the environment record if on: (W, H, u0 bits, -), (texels low, texels high, distribution low, distribution high); the
-    // distribution's words are zero until mode RT_LIGHT_SAMPLING_ENV has built it (§24)
-    int image_with_tail(const DevBuf& src, uint32_t staged_vec4, DevBuf& dst) const {
-        const size_t vn_vec4 = vn.on ? (vn.host.size() * sizeof(float) + 15u) / 16u : 0u;
-        const size_t uv_vec4 = uv.on ? (uv.host.size() * sizeof(float) + 15u) / 16u : 0u;
-        const size_t tex_vec4 = tex.on ? 1u + tex.records.size() : 0u;
-        std::vector<uint4> t(1u + vn_vec4 + uv_vec4 + (env.on ? 2u : 0u) + tex_vec4, make_uint4(0u, 0u, 0u, 0u));
-        t[0].x = vn.on ? 1u : 0u;
-        t[0].y = uv.on ? (uint32_t)(1u + vn_vec4) : 0u;
-        if (tex.on) {   // §25, behind everything else: (texels low, texels high, n, -), then (W, H, wrap | filter << 8, first texel) per entry
-            const size_t at = 1u + vn_vec4 + uv_vec4 + (env.on ? 2u : 0u);
-            const uint64_t ptr = (uint64_t)reinterpret_cast<uintptr_t>(tex.texels.p);
-            t[0].w = (uint32_t)at;
-            t[at] = make_uint4((uint32_t)ptr, (uint32_t)(ptr >> 32), (uint32_t)tex.records.size(), 0u);
-            for (size_t k = 0; k < tex.records.size(); k++)
-                t[at + 1u + k] = make_uint4(tex.records[k].width, tex.records[k].height, tex.records[k].wrap | tex.records[k].filter << 8, tex.records[k].first);
-        }
-        if (env.on) {
-            const size_t at = 1u + vn_vec4 + uv_vec4;
-            const uint64_t ptr = (uint64_t)reinterpret_cast<uintptr_t>(env.texels.p);
-            t[0].z = (uint32_t)at;
-            t[at].x = env.w; t[at].y = env.h; std::memcpy(&t[at].z, &env.u0, 4);
-            t[at + 1u].x = (uint32_t)ptr; t[at + 1u].y = (uint32_t)(ptr >> 32);
-            const uint64_t dptr = env.dist_on ? (uint64_t)reinterpret_cast<uintptr_t>(env.dist.p) : 0ull;
-            t[at + 1u].z = (uint32_t)dptr; t[at + 1u].w = (uint32_t)(dptr >> 32);
-        }
-        if (vn.on) std::memcpy(&t[1], vn.host.data(), vn.host.size() * sizeof(float));
-        if (uv.on) std::memcpy(&t[1u + vn_vec4], uv.host.data(), uv.host.size() * sizeof(float));
-        HIP_TRY(dst.alloc(((size_t)staged_vec4 + t.size()) * sizeof(uint4)));
-        HIP_TRY(hipMemcpy(dst.p, src.p, (size_t)staged_vec4 * sizeof(uint4), hipMemcpyDeviceToDevice));
-        HIP_TRY(hipMemcpy(dst.as<uint4>() + staged_vec4, t.data(), t.size() * sizeof(uint4), hipMemcpyHostToDevice));
-        return RT_OK;
-    }
-    // The map in env.host (w x h, 3 floats per texel) onto the device: one record per texel, and — with_dist, §24 — the sampling density in the records' fourth lane
-    // and the tables in `dist`.  Into fresh buffers that replace the old ones only when everything has succeeded; the caller has waited for the launches that
-    // read the old ones, and rebuilds the tails.  An all-black map is refused (RT_ERR_INVALID, `who` names the caller) before anything changes.
-    int upload_environment(const char* who, uint32_t w, uint32_t h, const float* rgb, bool with_dist) {
-        const size_t n_texels = (size_t)w * h;
+    // The map in e.host (e.w x e.h, 3 floats per texel) onto the device, into e's own buffers: one record per texel, and — with_dist, §24 — the sampling density in
+    // the records' fourth lane and the tables in e.dist.  An all-black map is refused (RT_ERR_INVALID, `who` names the caller).
+    static int upload_environment(const char* who, Environment& e, bool with_dist) {
+        const size_t n_texels = (size_t)e.w * e.h;
+        const float* rgb = e.host.data();
         std::vector<float> tables, density;
         if (with_dist) {
-            tables.resize(2u * (size_t)h + 1u + n_texels); density.resize(n_texels);
-            if (const char* why = rt_environment_distribution_refusal(w, h, rgb, tables.data(), tables.data() + h, tables.data() + 2u * (size_t)h + 1u, density.data()))
+            tables.resize(2u * (size_t)e.h + 1u + n_texels); density.resize(n_texels);
+            if (const char* why = rt_environment_distribution_refusal(e.w, e.h, rgb, tables.data(), tables.data() + e.h, tables.data() + 2u * (size_t)e.h + 1u, density.data()))
                 return rt_fail(RT_ERR_INVALID, "%s: %s", who, why);
         }
         std::vector<float4> records(n_texels);
         for (size_t i = 0; i < n_texels; i++) records[i] = make_float4(rgb[3u * i], rgb[3u * i + 1u], rgb[3u * i + 2u], with_dist ? density[i] : 0.0f);
-        DevBuf new_texels, new_dist;
-        HIP_TRY(new_texels.upload(records.data(), n_texels * sizeof(float4)));
-        if (with_dist) HIP_TRY(new_dist.upload(tables.data(), tables.size() * sizeof(float)));
-        env.texels.release(); env.dist.release();
-        std::swap(env.texels.p, new_texels.p); std::swap(env.texels.bytes, new_texels.bytes);
-        std::swap(env.dist.p, new_dist.p); std::swap(env.dist.bytes, new_dist.bytes);
-        env.dist_on = with_dist;
+        HIP_TRY(e.texels.upload(records.data(), n_texels * sizeof(float4)));
+        if (with_dist) HIP_TRY(e.dist.upload(tables.data(), tables.size() * sizeof(float)));
+        e.dist_on = with_dist;
         return RT_OK;
     }
-    // The scene image with the light table of `mode` (1, 2, 4 or 16) behind it, once per table: t.blob, and with it t.table_vec4, t.lds_bytes and t.blocks_per_cu.
-    // A header (n_l, A, -, -), n_l entries (index, area, kind, c_j), — all modes but 1 — n_l more (Cx, Cy, Cz, r), and — mode 16, §20 — 2 n_l - 1 nodes of two vec4:
-    // 1 + 2 n_l + 2 (2 n_l - 1) = 6 n_l - 1 vec4.  An empty table (mode 48 on a world without lights, §26) is the header alone.
-    int light_image(uint32_t mode, LightTable& t) {
-        if (t.blob.p) return RT_OK;
-        const bool tree = mode == RT_LIGHT_SAMPLING_TREE;
-        const uint32_t table_vec4 = 1u + t.n * (mode == RT_LIGHT_SAMPLING_QUADS ? 1u : 2u) + (tree && t.n ? 2u * (2u * t.n - 1u) : 0u);
-        PackedSceneRef with_table = scene.packed;
-        with_table.blob_vec4 += table_vec4;
-        const uint32_t lds = (uint32_t)stream_kernel_lds_bytes(stream_block, with_table, scene.big, scene.wide, n_top);
-        if (lds > RT_LDS_PER_CU)
-            return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: the light table (%u bytes) does not fit beside the scene image in the LDS", table_vec4 * 16u);
-        std::vector<uint4> table(table_vec4, make_uint4(0u, 0u, 0u, 0u));
-        table[0].x = t.n;
-        for (uint32_t i = 0; i < t.n; i++) {
-            table[1u + i].x = t.index[i]; std::memcpy(&table[1u + i].y, &t.area[i], 4); table[1u + i].z = t.kind[i];
-            if (t.kind[i] == RT_LIGHT_SPHERE) std::memcpy(&table[1u + t.n + i], &t.sphere[4u * i], 16);
-            if (tree) std::memcpy(&table[1u + i].w, &t.cdf[i], 4);
-        }
-        if (tree && t.n) {
-            std::memcpy(&table[0].y, &t.cdf[t.n - 1u], 4);   // A
-            std::memcpy(&table[1u + 2u * t.n], t.nodes.data(), t.nodes.size() * sizeof(float));
-        }
-        table.push_back(make_uint4(0u, 0u, 0u, 0u));   // the vertex-normal header behind this image (§21): zero = no table follows
-        DevBuf fresh;
-        HIP_TRY(fresh.alloc(((size_t)scene.packed.blob_vec4 + table.size()) * sizeof(uint4)));
-        HIP_TRY(hipMemcpy(fresh.p, scene.blob.p, (size_t)scene.packed.blob_vec4 * sizeof(uint4), hipMemcpyDeviceToDevice));
-        HIP_TRY(hipMemcpy(fresh.as<uint4>() + scene.packed.blob_vec4, table.data(), table.size() * sizeof(uint4), hipMemcpyHostToDevice));
-        std::swap(t.blob.p, fresh.p); std::swap(t.blob.bytes, fresh.bytes);
-        t.table_vec4 = table_vec4;
-        t.lds_bytes = lds;
-        t.blocks_per_cu = std::min(2u, RT_LDS_PER_CU / lds);
+    // What a launch in light-sampling `mode` (RT_LIGHT_SAMPLING_OFF: the plain kernel) runs and on what: the one place that knows which image, kernel, LDS and
+    // workgroup count belong together.  `lights` is what rt_renderer_light_sampling_info reports: the table's lights, or the texels of a map sampled alone.
+    struct LaunchOn { const void* kernel; uint32_t key; const uint4* blob; uint32_t blob_vec4, lds_bytes, blocks_per_cu, lights; };
+    LaunchOn launch_on(uint32_t mode) const {
+        const LightMode* m = light_mode(mode);
+        const uint32_t i = m ? m->image : 0u;
+        const Image& im = nee.image[i];
+        const LightTable& t = nee.tab[i ? i - 1u : 0u];   // (off: the quad lights)
+        LaunchOn l;
+        l.kernel = m ? nee.resolved[m - LIGHT_MODES].kernel : stream_kernel;
+        l.key = m ? nee.resolved[m - LIGHT_MODES].key : stream_kernel_key(variant, tol, scene);
+        l.blob = (im.blob.p ? im.blob : scene.blob).as<uint4>();
+        l.blob_vec4 = scene.packed.blob_vec4 + im.table_vec4;
+        l.lds_bytes = i ? im.lds_bytes : stream_lds_bytes;
+        l.blocks_per_cu = i ? im.blocks_per_cu : stream_blocks_per_cu;
+        l.lights = m && !i ? env.w * env.h : t.refused.empty() ? t.n : 0u;
+        return l;
+    }
+    // Image i (0: the plain one; 1 to 4: with the light table of mode 1, 2, 4, 16) from the riders as they stand, into `fresh`: scene | light table | tail
+    // (rt_launch_image.hpp has both layouts).  The scene part is copied device to device, the rest uploaded once.  The plain image without a tail gets no buffer.
+    int compose(uint32_t i, Image& fresh) const {
+        std::vector<rt_image::Vec4> rest;
+        if (i) {
+            const LightTable& t = nee.tab[i - 1u];
+            rt_image::append_light_table(rest, LIGHT_MODES[i - 1u].mode, t.n, t.kind.data(), t.index.data(), t.area.data(), t.sphere.data(), t.cdf.data(), t.nodes.data());
+            fresh.table_vec4 = (uint32_t)rest.size();
+            PackedSceneRef with_table = scene.packed;
+            with_table.blob_vec4 += fresh.table_vec4;
+            fresh.lds_bytes = (uint32_t)stream_kernel_lds_bytes(stream_block, with_table, scene.big, scene.wide, n_top);
+            if (fresh.lds_bytes > RT_LDS_PER_CU)
+                return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: the light table (%u bytes) does not fit beside the scene image in the LDS", fresh.table_vec4 * 16u);
+            fresh.blocks_per_cu = std::min(2u, RT_LDS_PER_CU / fresh.lds_bytes);
+        } else if (!tail_on()) return RT_OK;
+        rt_image::Riders<rt_texture> rd;
+        if (vn.on) { rd.normals = vn.host.data(); rd.n_normal_floats = vn.host.size(); }
+        if (uv.on) { rd.coords = uv.host.data(); rd.n_coord_floats = uv.host.size(); }
+        rd.env = env.on; rd.env_w = env.w; rd.env_h = env.h; rd.env_u0 = env.u0;
+        rd.env_texels = (uint64_t)reinterpret_cast<uintptr_t>(env.texels.p); rd.env_dist = env.dist_on ? (uint64_t)reinterpret_cast<uintptr_t>(env.dist.p) : 0ull;
+        rd.textures = tex.on; rd.texture = tex.records.data(); rd.n_textures = tex.records.size(); rd.texture_texels = (uint64_t)reinterpret_cast<uintptr_t>(tex.texels.p);
+        rt_image::append_tail(rest, rd);
+        const size_t scene_bytes = (size_t)scene.packed.blob_vec4 * sizeof(uint4);
+        HIP_TRY(fresh.blob.alloc(scene_bytes + rest.size() * sizeof(uint4)));
+        HIP_TRY(hipMemcpy(fresh.blob.p, scene.blob.p, scene_bytes, hipMemcpyDeviceToDevice));
+        HIP_TRY(hipMemcpy(fresh.blob.as<uint4>() + scene.packed.blob_vec4, rest.data(), rest.size() * sizeof(uint4), hipMemcpyHostToDevice));
         return RT_OK;
     }
-    // the tails anew from vn, uv and env as they stand: none while all are off, else the plain image's and one per light-sampling mode already built
-    int rebuild_tails() {
-        tail.blob.release();
-        for (DevBuf& b : tail.nee_blob) b.release();
-        if (!tail_on()) return RT_OK;
-        if (const int rc = image_with_tail(scene.blob, scene.packed.blob_vec4, tail.blob)) return rc;
-        for (const uint32_t mode : {RT_LIGHT_SAMPLING_QUADS, RT_LIGHT_SAMPLING_ALL, RT_LIGHT_SAMPLING_MESH, RT_LIGHT_SAMPLING_TREE}) {
-            const LightTable& t = nee.tab[nee.slot(mode)];
-            if (t.blob.p)
-                if (const int rc = image_with_tail(t.blob, scene.packed.blob_vec4 + t.table_vec4, tail.nee_blob[nee.slot(mode)])) return rc;
-        }
+    // Every image there is — the plain one and those whose table has been built — anew, all or none: into fresh buffers that are swapped in only when every one
+    // has succeeded.  The caller has waited for the launches that read the old buffers (wait_last_call).
+    int recompose() {
+        Image fresh[5];
+        for (uint32_t i = 0; i < 5u; i++)
+            if (!i || nee.image[i].blob.p)
+                if (const int rc = compose(i, fresh[i])) return rc;
+        for (uint32_t i = 0; i < 5u; i++)
+            if (!i || nee.image[i].blob.p) std::swap(nee.image[i], fresh[i]);
         return RT_OK;
+    }
+    // A rider's state replaced by `next` and the images composed anew; on failure the rider gets its old state back, and no image has changed.
+    template <typename Rider> int replace_rider(Rider& rider, Rider& next) {
+        std::swap(rider, next);
+        const int rc = recompose();
+        if (rc != RT_OK) std::swap(rider, next);
+        return rc;
     }
     // denoiser (rt_renderer_denoise): guide records, the two colour buffers the iterations ping-pong, the output frame; allocated at first use
     DevBuf dn_g0, dn_g1, dn_a, dn_b, dn_out;
@@ -621,8 +619,9 @@ struct rt_renderer {
         } else if (n_slots == 2) {
             for (Slot& s : slot) { HIP_TRY(hipStreamWaitEvent(st, s.traced, 0)); HIP_TRY(hipStreamWaitEvent(st, s.consumed, 0)); }
         }
-        const uint32_t end_s = first_s + n_s, n_pixels = (uint32_t)n_local_pixels(tm), grid = n_cus * (nee.on() ? nee.cur().blocks_per_cu : stream_blocks_per_cu);
-        StreamParams p = call_params(refine ? end_s : cfg.samples_per_pixel, sl);
+        const LaunchOn on = launch_on(nee.mode);
+        const uint32_t end_s = first_s + n_s, n_pixels = (uint32_t)n_local_pixels(tm), grid = n_cus * on.blocks_per_cu;
+        StreamParams p = call_params(refine ? end_s : cfg.samples_per_pixel, sl, on);
         const uint32_t ring_at = (uint32_t)(n_renders % RT_TIMES_RING);
         kev_ahead[ring_at] = ahead;
         if (ahead && !kev_resolve0[ring_at]) HIP_TRY(hipEventCreate(&kev_resolve0[ring_at]));
@@ -658,7 +657,7 @@ struct rt_renderer {
             XchgParams xp;
             if (variant == 5) { xp = xchg_params(p); args[0] = &xp; }
             HIP_TRY(hipEventRecord(ke[1], gs));
-            HIP_TRY(hipLaunchKernel(nee.on() ? nee.kernel : stream_kernel, dim3(grid), dim3(stream_block), args, nee.on() ? nee.cur().lds_bytes : stream_lds_bytes, gs));
+            HIP_TRY(hipLaunchKernel(on.kernel, dim3(grid), dim3(stream_block), args, on.lds_bytes, gs));
             HIP_TRY(hipEventRecord(ke[2], gs));
 #ifdef RT_PHASE_TIMERS
             if (const int rc = report_phase_timers(phase_acc, gs)) return rc;
@@ -693,14 +692,12 @@ struct rt_renderer {
         p.work_counter = sl.work_counter.as<uint32_t>();
     }
     // what every pass of a call shares
-    StreamParams call_params(uint32_t spp, const Slot& sl) const {
+    StreamParams call_params(uint32_t spp, const Slot& sl, const LaunchOn& on) const {
         StreamParams p;
         frame_params(p, spp, sl);
         p.scene = scene.packed;
         p.scene.n_top = scene.big ? n_top : 0u;
-        if (nee.mode == RT_LIGHT_SAMPLING_ENV) p.scene.blob = tail.blob.as<uint4>();   // §24: no table; the plain image with its tail, whose environment record is on while the mode is
-        else if (nee.on()) { p.scene.blob = (tail_on() ? tail.nee_blob[nee.image_slot(nee.mode)] : nee.tab[nee.image_slot(nee.mode)].blob).as<uint4>(); p.scene.blob_vec4 += nee.cur().table_vec4; }   // the same image with the light table behind it
-        else if (tail_on()) p.scene.blob = tail.blob.as<uint4>();   // ... with the vertex normals (§21) and the texture coordinates (§22) behind it
+        p.scene.blob = on.blob; p.scene.blob_vec4 = on.blob_vec4;   // the mode's image: the light table, if any, is staged with the scene; the tail behind it is not
         p.samples = sl.samples.as<float4>();
         p.inner_keep = tune[0] ? tune[0] : 1u; p.shade_min = tune[1]; p.leaf_min = tune[2];
         p.inner_drop = tune[3]; p.inner_floor = tune[4];
@@ -773,9 +770,10 @@ struct rt_renderer {
         p.pass_first_s = sp.pass_first_s; p.pass_spp = sp.pass_spp; p.n_take = upto - sp.pass_first_s;
         p.prim_o = sp.prim_o; p.prim_d = sp.prim_d;
         const uint32_t first_tri = scene.dw.n_prims + scene.dw.n_quads - scene.n_triangles;
-        if (aov_mode == RT_AOV_TEXTURED) {   // §27: the plain image's tail, or — no table on — the image itself, whose header is zero; every tail holds the same tables
-            const uint4* blob = (tail_on() ? tail.blob : scene.blob).as<uint4>();
-            const uint32_t blob_vec4 = scene.packed.blob_vec4;
+        if (aov_mode == RT_AOV_TEXTURED) {   // §27: the plain image, whose header is zero while no rider is on; every image's tail holds the same tables
+            const LaunchOn plain = launch_on(RT_LIGHT_SAMPLING_OFF);
+            const uint4* blob = plain.blob;
+            const uint32_t blob_vec4 = plain.blob_vec4;
             if (!vn.on) aov_kernel_tex_for(scene.dw)<<<grid, block, 0, st>>>(p, aov.as<float4>(), blob, blob_vec4, first_tri);
             else if (scene.dw.kind == RT_WORLD_LIST) aov_kernel_smooth_tex<RT_AOV_WALK_LIST><<<grid, block, 0, st>>>(p, aov.as<float4>(), vn.table.as<rt_tri_normals>(), blob, blob_vec4, first_tri);
             else aov_kernel_smooth_tex<RT_AOV_WALK_STACK><<<grid, block, 0, st>>>(p, aov.as<float4>(), vn.table.as<rt_tri_normals>(), blob, blob_vec4, first_tri);
@@ -821,16 +819,16 @@ extern "C" int rt_renderer_create(const rt_render_config* cfg, const rt_camera* 
     if (rc != RT_OK) return rc;
     rt_renderer* r = new rt_renderer();
     r->cfg = *cfg;
-    for (uint32_t i = 0; i < world->n_materials && world->materials && !r->aov_refused; i++) {
+    for (uint32_t i = 0; i < world->n_materials && world->materials; i++) {
         const uint32_t t = world->materials[i].type;
-        if (t == RT_MAT_ISOTROPIC) r->aov_refused = "a constant medium (RT_MAT_ISOTROPIC)";
-        else if (t == RT_MAT_LAMBERTIAN_NOISE) r->aov_refused = "a noise texture (RT_MAT_LAMBERTIAN_NOISE)";
-        else if (t == RT_MAT_LAMBERTIAN_IMAGE) r->aov_refused = "an image texture (RT_MAT_LAMBERTIAN_IMAGE)";
+        const char* refused = t == RT_MAT_ISOTROPIC ? "a constant medium (RT_MAT_ISOTROPIC)" : t == RT_MAT_LAMBERTIAN_NOISE ? "a noise texture (RT_MAT_LAMBERTIAN_NOISE)"
+                            : t == RT_MAT_LAMBERTIAN_IMAGE ? "an image texture (RT_MAT_LAMBERTIAN_IMAGE)" : nullptr;
+        if (!r->aov_refused) r->aov_refused = refused;   // the first such material
+        if (t == RT_MAT_ISOTROPIC) r->has_medium = true;
     }
-    for (uint32_t i = 0; i < world->n_materials && world->materials; i++)
-        if (world->materials[i].type == RT_MAT_ISOTROPIC) r->has_medium = true;
-    for (const uint32_t mode : {RT_LIGHT_SAMPLING_QUADS, RT_LIGHT_SAMPLING_ALL, RT_LIGHT_SAMPLING_MESH, RT_LIGHT_SAMPLING_TREE}) {
-        rt_renderer::LightTable& t = r->nee.tab[r->nee.slot(mode)];
+    for (uint32_t k = 0; k < 4u; k++) {   // the table modes: LIGHT_MODES' first four rows
+        const uint32_t mode = LIGHT_MODES[k].mode;
+        rt_renderer::LightTable& t = r->nee.tab[k];
         const uint32_t cap = mode == RT_LIGHT_SAMPLING_TREE ? RT_MAX_LIGHTS_TREE : RT_MAX_LIGHTS_MESH;
         t.kind.assign(cap, 0u); t.index.assign(cap, 0u); t.area.assign(cap, 0.0f);
         if (rt_world_light_table(world, mode, cap, t.kind.data(), t.index.data(), t.area.data(), &t.n) != RT_OK) { t.refused = rt_last_error(); t.n = 0; }
@@ -934,111 +932,58 @@ extern "C" int rt_renderer_set_camera(rt_renderer* r, const rt_camera* cam) {
     return RT_OK;
 }
 
-// Light sampling.  Off: every launch is what it was.  On: the NEE form of the renderer's own kernel, on a copy of the scene image that ends with the light table
-// of the mode: a header (n_l, -, -, -), n_l entries (index, area, kind, -), and — modes RT_LIGHT_SAMPLING_ALL and RT_LIGHT_SAMPLING_MESH — n_l more
-// (Cx, Cy, Cz, r), zeros for a quad and for a triangle.
+// Light sampling.  Off: every launch is what it was.  On: the mode's form of the renderer's own kernel on the mode's image (LIGHT_MODES, rt_renderer::launch_on).
+// One sequence for every mode: refusals — variant; for the modes of the map: background, queue, medium, no map; the table's own —, then, behind a wait for every
+// launch already enqueued (they keep their kernel and their image: nothing below frees or overwrites a buffer a queued launch may read), the image, the kernel,
+// its LDS limit and the map's distribution, each built once.  A failure leaves the mode as it was, and what was not finished is tried again by the next call.
 extern "C" int rt_renderer_light_sampling_enable(rt_renderer* r, uint32_t on) {
     if (!r) return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: null renderer");
-    if (on > RT_LIGHT_SAMPLING_ALL && on != RT_LIGHT_SAMPLING_MESH && on != RT_LIGHT_SAMPLING_TREE && on != RT_LIGHT_SAMPLING_ENV && on != RT_LIGHT_SAMPLING_ENV_TREE)   // 3 is no mode
+    const LightMode* m = light_mode(on);
+    if (on != RT_LIGHT_SAMPLING_OFF && !m)   // 3 is no mode
         return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: on must be 0 (off), 1 (quad lights), 2 (quad and sphere lights), 4 (quad, sphere and triangle lights), 16 (those, through a light tree, chosen by area) or 32 (the environment map), or 48 (the map and the light tree together)");
     if (on == r->nee.mode) return RT_OK;   // nothing changes, the refinement goes on
-    if (on == RT_LIGHT_SAMPLING_ENV_TREE) {   // §26: mode 32's map and mode 16's table at once — mode 16's image (an empty table is a header alone) under the tail's environment record
-        rt_renderer::LightTable& t = r->nee.tab[r->nee.slot(on)];
-        rt_renderer::LightTable& tree = r->nee.tab[r->nee.slot(RT_LIGHT_SAMPLING_TREE)];
+    if (m) {
+        const rt_renderer::LightTable* t = m->image ? &r->nee.tab[m->image - 1u] : nullptr;
         if (r->variant < 2 || r->variant == 5 || r->tol)
             return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: kernel variant %u has no light-sampling form (the baseline kernel 1, the ray exchange 5 and the tolerance mode 6 do not; use variant 0, 2 or 3)", r->tol ? 6u : r->variant);
-        if (r->scene.dw.background != 2u)
-            return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: mode 48 samples the environment map of a world with background mode 2 (rt_scene_set_environment) beside its lights; this world's is %u, for which on must be 0 (off), 1 (quad lights), 2 (quad and sphere lights), 4 (quad, sphere and triangle lights) or 16 (those, through a light tree, chosen by area)", r->scene.dw.background);
-        if (r->scene.queue)
-            return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: mode 48: a world with a queue or wide4 traversal renders on lane walks that have no light-sampling form (RT_TRAVERSAL_STACK and lists do)");
-        if (r->has_medium)
-            return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: mode 48: the world has a constant medium (RT_MAT_ISOTROPIC), which neither the environment estimator nor the light tree covers");
-        if (!r->env.on)
-            return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: mode 48: the renderer has no environment map to sample: give it one with rt_renderer_environment first");
-        if (!tree.refused.empty() && !tree.none)   // more than RT_MAX_LIGHTS_TREE lights, or an area lost in the running sum; a world with no light at all is the map alone
-            return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: mode 48: %s", tree.refused.c_str());
-        HIP_TRY(hipSetDevice(r->cfg.device));
-        if (const int rc = wait_last_call(r)) return rc;   // launches already enqueued read the texel records that are replaced below
-        if (const int rc = r->drain_slots()) return rc;
-        if (!t.built) {
-            if (const int rc = r->light_image(RT_LIGHT_SAMPLING_TREE, tree)) return rc;
-            const uint32_t key = stream_kernel_key(r->variant, false, r->scene) | RT_KEY_NEE | RT_KEY_TRI | RT_KEY_LTREE | RT_KEY_ENVL;   // a world without triangles is a TRI world too
+        if (m->env && r->scene.dw.background != 2u)   // a world of this kind takes the modes of the light tables only, so the message lists them
+            return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: mode %u samples the environment map of a world with background mode 2 (rt_scene_set_environment)%s; this world's is %u, for which on must be 0 (off), 1 (quad lights), 2 (quad and sphere lights), 4 (quad, sphere and triangle lights) or 16 (those, through a light tree, chosen by area)", on, m->beside, r->scene.dw.background);
+        if (m->env && r->scene.queue)
+            return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: %sa world with a queue or wide4 traversal renders on lane walks that have no light-sampling form (RT_TRAVERSAL_STACK and lists do)", m->tag);
+        if (m->env && r->has_medium)
+            return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: %sthe world has a constant medium (RT_MAT_ISOTROPIC), %s", m->tag, m->medium);
+        if (m->env && !r->env.on)
+            return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: %sthe renderer has no environment map to sample: give it one with rt_renderer_environment first", m->tag);
+        if (t && !t->refused.empty() && !(m->env && t->none))   // beside the map, a world with no light at all is the map alone (§26): its table is the header
+            return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: %s%s", m->tag, t->refused.c_str());
+        if (const int rc = wait_last_call(r)) return rc;   // (sets the device)
+        if (m->image && !r->nee.image[m->image].blob.p) {   // the image with the mode's table, once (mode 16's serves mode 48 too)
+            rt_renderer::Image fresh;
+            if (const int rc = r->compose(m->image, fresh)) return rc;
+            std::swap(r->nee.image[m->image], fresh);
+        }
+        auto& resolved = r->nee.resolved[m - LIGHT_MODES];
+        if (!resolved.kernel) {   // set last: a failure on the way is tried again
+            const uint32_t key = stream_kernel_key(r->variant, false, r->scene) | m->key_bits;
             const void* k = stream_kernel_for(key);
-            if (!k) return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: mode 48: this world's kernel has no form that samples the map and the light tree");
-            HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tree.lds_bytes));
-            t.n = tree.n;
-            t.table_vec4 = tree.table_vec4;
-            t.lds_bytes = tree.lds_bytes;
-            t.blocks_per_cu = tree.blocks_per_cu;
-            t.key = key;
-            t.kernel = k;
-            t.built = true;
-        }
-        if (!r->env.dist_on) {   // as mode 32 does: the distribution of the map as it stands; an all-black map is refused here
-            if (const int rc = r->upload_environment("rt_renderer_light_sampling_enable: mode 48", r->env.w, r->env.h, r->env.host.data(), true)) return rc;
-            if (const int rc = r->rebuild_tails()) return rc;
-        }
-        if (!r->tail.nee_blob[r->nee.image_slot(on)].p)   // mode 16's image with the tail (the environment record is always on here) behind its table
-            if (const int rc = r->image_with_tail(tree.blob, r->scene.packed.blob_vec4 + tree.table_vec4, r->tail.nee_blob[r->nee.image_slot(on)])) return rc;
-        r->nee.kernel = t.kernel;
-    } else
-    if (on == RT_LIGHT_SAMPLING_ENV) {   // §24: the map is the one light; no table, a kernel family of its own on the image every launch of this renderer gets
-        rt_renderer::LightTable& t = r->nee.tab[r->nee.slot(on)];
-        if (r->variant < 2 || r->variant == 5 || r->tol)
-            return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: kernel variant %u has no light-sampling form (the baseline kernel 1, the ray exchange 5 and the tolerance mode 6 do not; use variant 0, 2 or 3)", r->tol ? 6u : r->variant);
-        if (r->scene.dw.background != 2u)   // a world of this kind takes the modes of the light tables only, so the message lists them
-            return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: mode 32 samples the environment map of a world with background mode 2 (rt_scene_set_environment); this world's is %u, for which on must be 0 (off), 1 (quad lights), 2 (quad and sphere lights), 4 (quad, sphere and triangle lights) or 16 (those, through a light tree, chosen by area)", r->scene.dw.background);
-        if (r->scene.queue)
-            return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: mode 32: a world with a queue or wide4 traversal renders on lane walks that have no light-sampling form (RT_TRAVERSAL_STACK and lists do)");
-        if (r->has_medium)
-            return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: mode 32: the world has a constant medium (RT_MAT_ISOTROPIC), which the environment estimator does not cover");
-        if (!r->env.on)
-            return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: mode 32: the renderer has no environment map to sample: give it one with rt_renderer_environment first");
-        HIP_TRY(hipSetDevice(r->cfg.device));
-        if (const int rc = wait_last_call(r)) return rc;   // launches already enqueued read the texel records that are replaced below
-        if (!t.built) {
-            const uint32_t key = stream_kernel_key(r->variant, false, r->scene) | RT_KEY_NEE | RT_KEY_TRI | RT_KEY_ENVL;   // a world without triangles is a TRI world too
-            const void* k = stream_kernel_for(key);
-            if (!k) return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: mode 32: this world's kernel has no environment-sampling form");
-            HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r->stream_lds_bytes));
-            t.table_vec4 = 0u;
-            t.lds_bytes = r->stream_lds_bytes;
-            t.blocks_per_cu = r->stream_blocks_per_cu;
-            t.key = key;
-            t.kernel = k;
-            t.built = true;
-        }
-        if (!r->env.dist_on) {   // the distribution of the map as it stands (a map given while the mode is on brings its own: rt_renderer_environment)
-            if (const int rc = r->upload_environment("rt_renderer_light_sampling_enable: mode 32", r->env.w, r->env.h, r->env.host.data(), true)) return rc;
-            if (const int rc = r->rebuild_tails()) return rc;
-        }
-        r->nee.kernel = t.kernel;
-    } else
-    if (on) {
-        rt_renderer::LightTable& t = r->nee.tab[r->nee.slot(on)];
-        if (r->variant < 2 || r->variant == 5 || r->tol)
-            return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: kernel variant %u has no light-sampling form (the baseline kernel 1, the ray exchange 5 and the tolerance mode 6 do not; use variant 0, 2 or 3)", r->tol ? 6u : r->variant);
-        if (!t.refused.empty()) return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: %s", t.refused.c_str());
-        HIP_TRY(hipSetDevice(r->cfg.device));
-        if (const int rc = r->drain_slots()) return rc;   // renders that ran ahead may still be queued: the tables and the kernel's LDS limit change behind them
-        if (!t.built) {   // set last: a failure on the way is tried again
-            const bool tree = on == RT_LIGHT_SAMPLING_TREE;
-            if (const int rc = r->light_image(on, t)) return rc;   // (mode 48 may have built mode 16's already: §26)
-            const uint32_t key = stream_kernel_key(r->variant, false, r->scene) | RT_KEY_NEE | (tree ? RT_KEY_TRI | RT_KEY_LTREE : 0u);   // a world without triangles is a TRI world too
-            const void* k = stream_kernel_for(key);
-            if (!k) return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: this world's kernel has no light-sampling form");
-            uint32_t lds_set = t.lds_bytes;   // one kernel may serve several tables: the attribute covers the largest of its own
-            for (const rt_renderer::LightTable& o : r->nee.tab) if (o.built && o.kernel == k) lds_set = std::max(lds_set, o.lds_bytes);
+            if (!k) return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: %s%s", m->tag, m->no_form);
+            uint32_t lds_set = r->launch_on(on).lds_bytes;   // one kernel may serve several tables: the attribute covers the largest of its own
+            for (const LightMode& o : LIGHT_MODES)
+                if (r->nee.resolved[&o - LIGHT_MODES].kernel == k) lds_set = std::max(lds_set, r->launch_on(o.mode).lds_bytes);
             HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_set));
-            t.key = key;
-            t.kernel = k;
-            t.built = true;
+            resolved.key = key;
+            resolved.kernel = k;
         }
-        if (r->tail_on() && !r->tail.nee_blob[r->nee.slot(on)].p)   // this mode's image once more, with the vertex normals and texture coordinates behind its light table
-            if (const int rc = r->image_with_tail(t.blob, r->scene.packed.blob_vec4 + t.table_vec4, r->tail.nee_blob[r->nee.slot(on)])) return rc;
-        r->nee.kernel = t.kernel;
+        if (m->env && !r->env.dist_on) {   // the distribution of the map as it stands (a map given while the mode is on brings its own: rt_renderer_environment); an all-black map is refused here
+            char who[64];
+            std::snprintf(who, sizeof(who), "rt_renderer_light_sampling_enable: mode %u", on);
+            rt_renderer::Environment next;
+            next.on = true; next.w = r->env.w; next.h = r->env.h; next.u0 = r->env.u0; next.host = r->env.host;
+            if (const int rc = rt_renderer::upload_environment(who, next, true)) return rc;
+            if (const int rc = r->replace_rider(r->env, next)) return rc;
+        }
     }
-    r->nee.mode = on;       // of the NEXT launch; launches already enqueued keep their kernel and their image (the images with the tables stay allocated)
+    r->nee.mode = on;       // of the NEXT launch
     r->refine_done = 0;     // samples drawn by another estimator belong to another sequence
     r->aov_done = 0;
     return RT_OK;
@@ -1046,14 +991,12 @@ extern "C" int rt_renderer_light_sampling_enable(rt_renderer* r, uint32_t on) {
 
 extern "C" int rt_renderer_light_sampling_info(rt_renderer* r, uint32_t out[2]) {
     if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_info: null argument");
-    const rt_renderer::LightTable& t = r->nee.tab[r->nee.on() ? r->nee.slot(r->nee.mode) : 0u];
     out[0] = r->nee.mode;
-    out[1] = t.refused.empty() ? t.n : 0u;
-    if (r->nee.mode == RT_LIGHT_SAMPLING_ENV) out[1] = r->env.w * r->env.h;   // §24: the texels of the map
+    out[1] = r->launch_on(r->nee.mode).lights;   // §24: of a map sampled alone, its texels
     return RT_OK;
 }
 
-// Smooth shading.  Off: every launch is what it was.  On: the same kernels on copies of their images that end with (1, -, -, -) and the table.
+// Smooth shading.  Off: every launch is what it was.  On: the same kernels on images whose tail holds the table.
 extern "C" int rt_renderer_shading_normals(rt_renderer* r, const rt_tri_normals* table, uint32_t n) {
     if (!r) return rt_fail(RT_ERR_INVALID, "rt_renderer_shading_normals: null renderer");
     if ((table == nullptr) != (n == 0u)) return rt_fail(RT_ERR_INVALID, "rt_renderer_shading_normals: a table and its count go together (NULL, 0 turns it off)");
@@ -1077,17 +1020,15 @@ extern "C" int rt_renderer_shading_normals(rt_renderer* r, const rt_tri_normals*
     const size_t bytes = (size_t)n * sizeof(rt_tri_normals);
     if (n ? (r->vn.on && r->vn.host.size() * sizeof(float) == bytes && std::memcmp(r->vn.host.data(), table, bytes) == 0) : !r->vn.on) return RT_OK;   // nothing changes, the refinement goes on
     if (const int rc = wait_last_call(r)) return rc;   // launches already enqueued read the images that are replaced below
-    r->vn.on = false;
-    r->vn.table.release();
     r->refine_done = 0;   // samples shaded with other normals belong to another frame
     r->aov_done = 0;
-    if (!n) { r->vn.host.clear(); r->vn.n_smooth = 0; return r->rebuild_tails(); }   // the texture coordinates, if on, stay on
-    r->vn.host.assign(table[0].n0, table[0].n0 + (size_t)n * 9u);
-    r->vn.n_smooth = n_smooth;
-    if (const hipError_t e = r->vn.table.upload(r->vn.host.data(), bytes); e != hipSuccess) { r->rebuild_tails(); HIP_TRY(e); }
-    r->vn.on = true;
-    if (const int rc = r->rebuild_tails()) { r->vn.on = false; r->rebuild_tails(); return rc; }
-    return RT_OK;
+    decltype(r->vn) next;   // off, unless a table is given; the other riders stay as they are
+    if (n) {
+        next.on = true; next.n_smooth = n_smooth;
+        next.host.assign(table[0].n0, table[0].n0 + (size_t)n * 9u);
+        HIP_TRY(next.table.upload(next.host.data(), bytes));
+    }
+    return r->replace_rider(r->vn, next);
 }
 
 // Texture coordinates, as the normals above: off, every launch is what it was; on, the same kernels on images whose tail holds the table.
@@ -1112,15 +1053,11 @@ extern "C" int rt_renderer_texture_coords(rt_renderer* r, const rt_tri_uvs* tabl
     const size_t bytes = (size_t)n * sizeof(rt_tri_uvs);
     if (n ? (r->uv.on && r->uv.host.size() * sizeof(float) == bytes && std::memcmp(r->uv.host.data(), table, bytes) == 0) : !r->uv.on) return RT_OK;   // nothing changes, the refinement goes on
     if (const int rc = wait_last_call(r)) return rc;   // launches already enqueued read the images that are replaced below
-    r->uv.on = false;
     r->refine_done = 0;   // samples textured through other coordinates belong to another frame
     r->aov_done = 0;
-    if (!n) { r->uv.host.clear(); r->uv.n_mapped = 0; return r->rebuild_tails(); }   // the vertex normals, if on, stay on
-    r->uv.host.assign(table[0].t0, table[0].t0 + (size_t)n * 6u);
-    r->uv.n_mapped = n_mapped;
-    r->uv.on = true;
-    if (const int rc = r->rebuild_tails()) { r->uv.on = false; r->rebuild_tails(); return rc; }
-    return RT_OK;
+    decltype(r->uv) next;
+    if (n) { next.on = true; next.n_mapped = n_mapped; next.host.assign(table[0].t0, table[0].t0 + (size_t)n * 6u); }
+    return r->replace_rider(r->uv, next);
 }
 
 extern "C" int rt_renderer_texture_coords_info(rt_renderer* r, uint32_t out[2]) {
@@ -1148,22 +1085,17 @@ extern "C" int rt_renderer_environment(rt_renderer* r, uint32_t width, uint32_t 
     if (sampled && off)
         return rt_fail(RT_ERR_INVALID, "rt_renderer_environment: the map is being sampled (light-sampling mode %u): switch light sampling off before taking the map away", r->nee.mode);
     if (const int rc = wait_last_call(r)) return rc;   // launches already enqueued read the images and the texels that are replaced below
-    if (sampled) {   // an all-black successor is refused here, and the old map stays as it is
-        if (const int rc = r->upload_environment(r->nee.mode == RT_LIGHT_SAMPLING_ENV ? "rt_renderer_environment: light-sampling mode 32 is on" : "rt_renderer_environment: light-sampling mode 48 is on", width, height, rgb, true)) return rc;
+    rt_renderer::Environment next;
+    if (!off) {   // a map that is being sampled brings its distribution; an all-black successor is refused here, and the old map stays as it is
+        char who[64] = "rt_renderer_environment";
+        if (sampled) std::snprintf(who, sizeof(who), "rt_renderer_environment: light-sampling mode %u is on", r->nee.mode);
+        next.on = true; next.w = width; next.h = height; next.u0 = u0;
+        next.host.assign(rgb, rgb + n_texels * 3u);
+        if (const int rc = rt_renderer::upload_environment(who, next, sampled)) return rc;
     }
-    r->env.on = false;
     r->refine_done = 0;   // samples lit by another sky belong to another frame
     r->aov_done = 0;
-    if (!sampled) { r->env.texels.release(); r->env.dist.release(); r->env.dist_on = false; }
-    r->env.host.clear(); r->env.w = r->env.h = 0u; r->env.u0 = 0.0f;
-    if (off) return r->rebuild_tails();   // the vertex normals and the texture coordinates, if on, stay on
-    if (!sampled)
-        if (const int rc = r->upload_environment("rt_renderer_environment", width, height, rgb, false)) { r->rebuild_tails(); return rc; }
-    r->env.host.assign(rgb, rgb + n_texels * 3u);
-    r->env.w = width; r->env.h = height; r->env.u0 = u0;
-    r->env.on = true;
-    if (const int rc = r->rebuild_tails()) { r->env.on = false; r->env.texels.release(); r->rebuild_tails(); return rc; }
-    return RT_OK;
+    return r->replace_rider(r->env, next);
 }
 
 extern "C" int rt_renderer_environment_info(rt_renderer* r, uint32_t out[4]) {
@@ -1186,30 +1118,18 @@ extern "C" int rt_renderer_textures(rt_renderer* r, const rt_texture* records, u
     }
     if (off ? !r->tex.on : (r->tex.on && r->tex.records.size() == n && std::memcmp(r->tex.records.data(), records, n * sizeof(rt_texture)) == 0 &&
                             (n_texels == 0u || std::memcmp(r->tex.host.data(), texels, n_texels * 3u) == 0))) return RT_OK;   // nothing changes, the refinement goes on
-    DevBuf fresh;   // everything that can fail comes before anything changes
+    decltype(r->tex) next;   // everything that can fail comes before anything changes
     if (!off) {
         std::vector<uint32_t> dwords(n_texels ? n_texels : 1u, 0u);
         for (uint64_t i = 0; i < n_texels; i++) dwords[i] = (uint32_t)texels[3u * i] | (uint32_t)texels[3u * i + 1u] << 8 | (uint32_t)texels[3u * i + 2u] << 16;
         HIP_TRY(hipSetDevice(r->cfg.device));
-        HIP_TRY(fresh.upload(dwords.data(), dwords.size() * sizeof(uint32_t)));
+        HIP_TRY(next.texels.upload(dwords.data(), dwords.size() * sizeof(uint32_t)));
+        next.on = true; next.records.assign(records, records + n); next.host.assign(texels, texels + n_texels * 3u);
     }
     if (const int rc = wait_last_call(r)) return rc;   // launches already enqueued read the images and the texels that are replaced below
     r->refine_done = 0;   // samples textured by other images belong to another frame
     r->aov_done = 0;
-    std::vector<rt_texture> old_records = std::move(r->tex.records);
-    std::vector<uint8_t> old_host = std::move(r->tex.host);
-    const bool was_on = r->tex.on;
-    std::swap(r->tex.texels.p, fresh.p); std::swap(r->tex.texels.bytes, fresh.bytes);   // `fresh` now holds the old buffer
-    r->tex.on = !off;
-    r->tex.records.clear(); r->tex.host.clear();
-    if (!off) { r->tex.records.assign(records, records + n); r->tex.host.assign(texels, texels + n_texels * 3u); }
-    if (const int rc = r->rebuild_tails()) {   // back to the old table
-        std::swap(r->tex.texels.p, fresh.p); std::swap(r->tex.texels.bytes, fresh.bytes);
-        r->tex.on = was_on; r->tex.records = std::move(old_records); r->tex.host = std::move(old_host);
-        r->rebuild_tails();
-        return rc;
-    }
-    return RT_OK;
+    return r->replace_rider(r->tex, next);
 }
 
 extern "C" int rt_renderer_textures_info(rt_renderer* r, uint32_t out[2]) {
@@ -1476,8 +1396,9 @@ extern "C" int rt_renderer_kernel_form(rt_renderer* r, uint32_t out[9]) {
     for (int i = 0; i < 9; i++) out[i] = 0u;
     if (r->variant < 2) { out[0] = RT_KERNEL_BASELINE; return RT_OK; }
     // the key launch() resolves: plan()'s for the plain kernel, rt_renderer_light_sampling_enable's while sampling is on
-    const uint32_t key = r->nee.on() ? r->nee.cur().key : stream_kernel_key(r->variant, r->tol, r->scene);
-    if (stream_kernel_for(key) != (r->nee.on() ? r->nee.kernel : r->stream_kernel)) return rt_fail(RT_ERR_INVALID, "rt_renderer_kernel_form: the key does not name the kernel the renderer holds");
+    const rt_renderer::LaunchOn on = r->launch_on(r->nee.mode);
+    const uint32_t key = on.key;
+    if (stream_kernel_for(key) != on.kernel) return rt_fail(RT_ERR_INVALID, "rt_renderer_kernel_form: the key does not name the kernel the renderer holds");
     if (key == RT_KEY_XCHG) { out[0] = RT_KERNEL_XCHG; return RT_OK; }
     out[0] = RT_KERNEL_STREAM;
     stream_key_fields(key, out + 1);
@@ -1487,21 +1408,21 @@ extern "C" int rt_renderer_kernel_form(rt_renderer* r, uint32_t out[9]) {
 // Whether the NEXT launch runs an instantiation of the triangle family: a query of its own, so that rt_renderer_kernel_form's nine outputs stay what they are.
 extern "C" int rt_renderer_kernel_triangles(rt_renderer* r, uint32_t* out) {
     if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_kernel_triangles: null argument");
-    *out = r->variant >= 2 && ((r->nee.on() ? r->nee.cur().key : stream_kernel_key(r->variant, r->tol, r->scene)) & RT_KEY_TRI) ? 1u : 0u;
+    *out = r->variant >= 2 && (r->launch_on(r->nee.mode).key & RT_KEY_TRI) ? 1u : 0u;
     return RT_OK;
 }
 
 // Whether the NEXT launch runs an instantiation of the environment-sampling family: a query of its own, for the same reason.
 extern "C" int rt_renderer_kernel_env_light(rt_renderer* r, uint32_t* out) {
     if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_kernel_env_light: null argument");
-    *out = r->nee.on() && (r->nee.cur().key & RT_KEY_ENVL) ? 1u : 0u;
+    *out = r->launch_on(r->nee.mode).key & RT_KEY_ENVL ? 1u : 0u;   // (no plain key has the bit)
     return RT_OK;
 }
 
 // Whether the NEXT launch runs an instantiation of the light-tree family: a query of its own, for the same reason.
 extern "C" int rt_renderer_kernel_light_tree(rt_renderer* r, uint32_t* out) {
     if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_kernel_light_tree: null argument");
-    *out = r->nee.on() && (r->nee.cur().key & RT_KEY_LTREE) ? 1u : 0u;
+    *out = r->launch_on(r->nee.mode).key & RT_KEY_LTREE ? 1u : 0u;   // (no plain key has the bit)
     return RT_OK;
 }
 
