@@ -367,6 +367,41 @@ int rt_texture_lookup_batch(const rt_texture* records, uint32_t n, const uint8_t
  * one fixed evaluation order, the library's own sine) — out_rgb[3 i ..] = the marble of `perlin` (rt_scene_set_perlin's tables) with the material's albedo and
  * param (`scale`) at points[3 i ..].  The function the kernels call.  RT_ERR_INVALID: a null argument, whatever n.                                         */
 int rt_noise_value_batch(const rt_perlin* perlin, const float albedo[3], float scale, const float* points, size_t n, float* out_rgb);
+/* ---- normal maps (not in the reference): an entry of the texture table read as a tangent-space normal map (OpenGL convention: red = +u, green = +v,
+ * blue = along the normal; byte 128 is zero) that bends the normal a hit is shaded with.  A map is attached PER MATERIAL, in a table beside the flat world: one
+ * 16-byte record per material; rt_material and rt_world_flat are what they were.  Lambertian, checker, noise, image and metal materials take one.
+ * Tangents, unnormalised, the directions in which the lookup's u and v grow before the image flip:
+ *   sphere, n = its normal: dPdu = (n.z, 0, -n.x), dPdv = (0, 1, 0)          parallelogram, triangle without coordinates: the record's u and v
+ *   triangle with coordinates t0, t1, t2: (du1, dv1) = t1 - t0, (du2, dv2) = t2 - t0, det = du1 dv2 - du2 dv1; !(det > 0 || det < 0): no frame, the normal stays;
+ *     dPdu = u dv2 - v dv1, dPdv = v du1 - u du2, both negated when det < 0
+ * The rule, with c = the entry's texture value at the hit's (u, v) (its own wrap and filter), N = the flat or smooth normal as the shade phase has it:
+ *   m = (c - C0) * K per component, C0 = 128.0f * 0x1.010102p-8f, K = fp32(255 / 127);   m.x *= strength; m.y *= strength;   m.x == 0 && m.y == 0: N stays
+ *   T = dPdu - N dot(N, dPdu);  tt = dot(T, T);  !(tt > 0): N stays (a sphere's poles);  T = T / sqrt(tt);  B = cross(N, T), negated when dot(B, dPdv) < 0
+ *   g = (T m.x + B m.y) + N m.z;  l2 = dot(g, g);  !(l2 > 0): N stays;  s = g / sqrt(l2)
+ *   s replaces N only when dot(ray.d, s) is not zero and has the sign of dot(ray.d, N): every hit keeps the facing the rest of the shade phase assumes.
+ * Only fp32 + - * / sqrt and comparisons, each rounded on its own, no FMA.  A flat map (bytes 128, 128, z) and strength 0 leave every normal's bits alone, under
+ * both filters.  No maps on glass, lights or media; no parallax, displacement, mip maps, terminator correction, object-space maps or tangents from a file.   */
+typedef struct rt_normal_map { uint32_t on, image; float strength; uint32_t pad; } rt_normal_map;   /* 16 B, one per material */
+/* Attaches entry `image` of the scene's texture table to `material` as its normal map.  RT_ERR_INVALID, scene unchanged: no such material; a dielectric, a light or
+ * an isotropic material; image >= RT_MAX_IMAGES; a strength that is not finite or is negative.  The entry itself is checked where a table is given to a renderer. */
+int rt_scene_set_normal_map(rt_scene* s, uint32_t material, uint32_t image, float strength);
+int rt_scene_clear_normal_map(rt_scene* s, uint32_t material);
+/* One record per material of the scene (*out = NULL, *out_n = 0 while no material has a map).  Materials are never permuted: the table is the same under every
+ * builder.  The pointer stays valid until the scene is modified or destroyed.                                                                                */
+int rt_scene_normal_maps(const rt_scene* s, const rt_normal_map** out, uint32_t* out_n);
+/* Where case i takes its tangents from (rt_normal_map_batch): a sphere's normal in a[3 i ..]; a record's u and v in a[], b[]; the same with the triangle's
+ * coordinates t0, t1, t2 in tri_uv[6 i ..]; or dPdu and dPdv as given in a[], b[]                                                                           */
+enum { RT_NMAP_SURFACE_SPHERE = 0, RT_NMAP_SURFACE_PLANAR = 1, RT_NMAP_SURFACE_TRI_UV = 2, RT_NMAP_SURFACE_GIVEN = 3 };
+/* Which way a case left the rule: the normal was replaced, or it stays because the decoded x and y are zero, the coordinates span no area (det), the tangent has
+ * no part across the normal (tt), the bent normal has no length (l2), or it would see the ray from the other side                                           */
+enum { RT_NMAP_REPLACED = 1, RT_NMAP_FLAT = 2, RT_NMAP_NO_TANGENT = 3, RT_NMAP_NO_LENGTH = 4, RT_NMAP_FACING = 5, RT_NMAP_NO_FRAME = 6 };
+/* HOST (no GPU): the two functions the kernels call, on `count` cases — the table as rt_texture_lookup_batch takes it; per case its surface (above), a, b, tri_uv
+ * (NULL when no case is RT_NMAP_SURFACE_TRI_UV), the normal N, the ray's direction, the lookup's (u, v), the entry and the strength (finite, >= 0) ->
+ * out_normal[3 i ..] (N where it stays), out_path[i] = RT_NMAP_*: the normal was replaced exactly where out_path[i] == RT_NMAP_REPLACED.  RT_ERR_INVALID: a table
+ * rt_renderer_textures would refuse, an index without an entry, an unknown surface, a bad strength, a null argument.                                         */
+int rt_normal_map_batch(const rt_texture* records, uint32_t n, const uint8_t* texels, size_t count, const uint32_t* surface, const float* a, const float* b,
+                        const float* tri_uv, const float* normal, const float* ray_d, const float* u, const float* v, const uint32_t* index, const float* strength,
+                        float* out_normal, uint32_t* out_path);
 
 /* BVH_Handle::Factory::BuildBVH_TopDown -> _build_bvh_rec1 (BVH.cu:166-210):
  * median split on the longest axis, leaf size 1, post-order numbering, root =
@@ -526,6 +561,8 @@ int rt_renderer_kernel_light_tree(rt_renderer* r, uint32_t* out);
 /* *out = 1 when the NEXT launch runs an instantiation of the environment-sampling family (mode RT_LIGHT_SAMPLING_ENV is on): the nine fields with nee = 1 and
  * ext = 2, plus the draw from the map; rt_renderer_kernel_triangles answers 1 too, as under the light tree.  A query of its own, for the same reason.        */
 int rt_renderer_kernel_env_light(rt_renderer* r, uint32_t* out);
+/* *out = 1 when the next launch runs an instantiation of the normal-map family, as rt_renderer_kernel_env_light answers for its own */
+int rt_renderer_kernel_normal_map(rt_renderer* r, uint32_t* out);
 /* Renderer::DownloadRenderbuffer (Renderer.cu:94-96): width*height*4 floats,
  * row-major, row 0 = bottom.  Only valid for world_size == 1.               */
 int rt_renderer_download(rt_renderer* r, float* host_rgba, size_t n_floats);
@@ -800,6 +837,19 @@ int rt_renderer_environment_info(rt_renderer* r, uint32_t out[4]);
 int rt_renderer_textures(rt_renderer* r, const rt_texture* records, uint32_t n, const uint8_t* texels);
 /* out[0] = 1 while a table is on, out[1] = how many entries it has */
 int rt_renderer_textures_info(rt_renderer* r, uint32_t out[2]);
+/* Normal maps (rt_scene_normal_maps): table = one record per material of the world, or NULL, 0 for off (the default).  While a table is on, plain
+ * launches and those of light-sampling mode 48 run the NMAP form of the renderer's kernel (rt_renderer_kernel_normal_map), which bends the normal of every hit on
+ * a material whose record says `on`, right after the flat or smooth normal is known; the feature pass in RT_AOV_TEXTURED mode accumulates the mapped normal.
+ * Takes effect at the next launch; an unchanged table is a no-op that keeps the refinement, a change discards the refinement and feature-buffer state.
+ * RT_ERR_INVALID with a message of its own: a count that is not the world's number of materials; a record on a dielectric, a light or a medium, with an image
+ * index past RT_MAX_IMAGES or a strength that is not finite and >= 0; the baseline kernel (variant 1), the ray exchange (5) and the tolerance mode (6); a world
+ * with a queue or wide4 traversal, or a bvh_node tree; light-sampling modes 1, 2, 4, 16 and 32 (rt_renderer_light_sampling_enable refuses them in turn while a
+ * table is on); the plain feature pass (rt_renderer_aov_enable refuses in turn, and names the textured mode).
+ * rt_renderer_render, the refine calls and their async forms return RT_ERR_INVALID and launch nothing while a record names an entry the renderer's texture
+ * table (rt_renderer_textures) does not have — entry 0 included: normal maps are read through the table only.                                               */
+int rt_renderer_normal_maps(rt_renderer* r, const rt_normal_map* table, uint32_t n);
+/* out[0] = 1 while a table is on, out[1] = how many of its records are on */
+int rt_renderer_normal_maps_info(rt_renderer* r, uint32_t out[2]);
 
 /* ------------------------------------------------------------------ */
 /* Multi-GPU renderer — the same three entry points (Renderer.h:38-46)  */
@@ -835,6 +885,9 @@ int rt_multi_renderer_environment(rt_multi_renderer* m, uint32_t width, uint32_t
 int rt_multi_renderer_textures(rt_multi_renderer* m, const rt_texture* records, uint32_t n, const uint8_t* texels);
 /* rt_renderer_textures_info of the ranks (they hold the same table).                                                      */
 int rt_multi_renderer_textures_info(rt_multi_renderer* m, uint32_t out[2]);
+/* rt_renderer_normal_maps on every rank (refused before any rank changes), and rt_renderer_normal_maps_info of the ranks.    */
+int rt_multi_renderer_normal_maps(rt_multi_renderer* m, const rt_normal_map* table, uint32_t n);
+int rt_multi_renderer_normal_maps_info(rt_multi_renderer* m, uint32_t out[2]);
 /* Renderer::DownloadRenderbuffer: width*height*4 floats from devices[0].                                                */
 int rt_multi_renderer_download(rt_multi_renderer* m, float* host_rgba, size_t n_floats);
 /* ms of the last render: out[0] host wall-clock of Render(), out[1] slowest rank's kernels (HIP events),
@@ -876,6 +929,10 @@ int rt_probe_environment(int device, size_t n, uint32_t width, uint32_t height, 
 /* rt_texture_lookup_batch on the device, one lane per lookup: the table as the renderer holds it (one 4-byte record per texel, the entries as vec4)              */
 int rt_probe_texture(int device, const rt_texture* records, uint32_t n, const uint8_t* texels, const uint32_t* index, const float* u, const float* v, size_t count,
                      float* out_rgb);
+/* rt_normal_map_batch on the device, one lane per case: the table as the renderer holds it (one 4-byte record per texel, the entries as vec4)                  */
+int rt_probe_normal_map(int device, const rt_texture* records, uint32_t n, const uint8_t* texels, size_t count, const uint32_t* surface, const float* a,
+                        const float* b, const float* tri_uv, const float* normal, const float* ray_d, const float* u, const float* v, const uint32_t* index,
+                        const float* strength, float* out_normal, uint32_t* out_path);
 /* rt_noise_value_batch on the device, one lane per point: the tables in global memory, as the renderer holds them                                              */
 int rt_probe_noise_value(int device, const rt_perlin* perlin, const float albedo[3], float scale, const float* points, size_t n, float* out_rgb);
 /* rt_environment_sample_batch on the device, one lane per quadruple: the records and the tables as the renderer holds them in mode RT_LIGHT_SAMPLING_ENV        */

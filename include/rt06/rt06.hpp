@@ -367,6 +367,15 @@ public:
     }
     // the modes of image `index`, 0 (the image of SetImage) included
     void SetImageSampling(uint32_t index, uint32_t wrap, uint32_t filter) { check(rt_scene_image_sampling(s_, index, wrap, filter), "rt_scene_image_sampling"); }
+    // a tangent-space normal map (extension; rt_scene_set_normal_map): image `image` of the scene bends the normals of material index `material`
+    // (Lambertian, checker, noise, image and metal materials); the table as rt_scene_normal_maps hands it out
+    void SetNormalMap(uint32_t material, uint32_t image, float strength = 1.0f) { check(rt_scene_set_normal_map(s_, material, image, strength), "rt_scene_set_normal_map"); }
+    void ClearNormalMap(uint32_t material) { check(rt_scene_clear_normal_map(s_, material), "rt_scene_clear_normal_map"); }
+    uint32_t NormalMaps(const rt_normal_map** out) const {
+        uint32_t n = 0;
+        check(rt_scene_normal_maps(s_, out, &n), "rt_scene_normal_maps");
+        return n;
+    }
     // child reference of a bvh_node tree: >= 0 node, < 0 primitive
     int32_t tree_ref(const Hittable* h) {
         if (h->kind() == Hittable::NODE) {
@@ -620,7 +629,12 @@ class Renderer {
             uint32_t n_tex = 0;
             const uint8_t* texels = nullptr;
             rt06::check(rt_scene_textures(static_cast<const BVH*>(world)->scene, &tex, &n_tex, &texels), "rt_scene_textures");
-            if (n_tex > 1u || (n_tex == 1u && (tex[0].wrap != RT_WRAP_CLAMP || tex[0].filter != RT_FILTER_NEAREST))) made.SetTextures(tex, n_tex, texels);
+            const bool table_says_more = n_tex > 1u || (n_tex == 1u && (tex[0].wrap != RT_WRAP_CLAMP || tex[0].filter != RT_FILTER_NEAREST));
+            const rt_normal_map* nmaps = nullptr;          // ... and one with normal maps theirs, and with them the table they name their images in
+            uint32_t n_nmaps = 0;
+            rt06::check(rt_scene_normal_maps(static_cast<const BVH*>(world)->scene, &nmaps, &n_nmaps), "rt_scene_normal_maps");
+            if (table_says_more || (n_nmaps && n_tex)) made.SetTextures(tex, n_tex, texels);
+            if (n_nmaps) made.SetNormalMaps(nmaps, n_nmaps);
         }
         return made;
     }
@@ -731,6 +745,12 @@ public:
     }
     // The texture table (extension; rt_renderer_textures): n entries and their texels as rt_scene_textures gives them, or (nullptr, 0, nullptr)
     // for off; restarts a refinement
+    // Normal maps (extension; rt_renderer_normal_maps): one record per material of the world as SceneBuilder::NormalMaps hands them out, or
+    // (nullptr, 0) for off; the images they name are the texture table's (SetTextures); restarts a refinement
+    void SetNormalMaps(const rt_normal_map* table, uint32_t n) {
+        if (m.mr) rt06::check(rt_multi_renderer_normal_maps(m.mr, table, n), "Renderer::SetNormalMaps");
+        else rt06::check(rt_renderer_normal_maps(m.r, table, n), "Renderer::SetNormalMaps");
+    }
     void SetTextures(const rt_texture* records, uint32_t n, const uint8_t* texels) {
         if (m.mr) rt06::check(rt_multi_renderer_textures(m.mr, records, n, texels), "Renderer::SetTextures");
         else rt06::check(rt_renderer_textures(m.r, records, n, texels), "Renderer::SetTextures");

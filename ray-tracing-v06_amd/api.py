@@ -162,6 +162,22 @@ class Scene:
         total = int((records["width"].astype(np.int64) * records["height"]).sum())
         return records, self._arr(tex.value, total * 3, np.dtype(np.uint8)).reshape(-1, 3)
 
+    def set_normal_map(self, material, image, strength=1.0):
+        """Attaches image `image` of the scene (set_image() = 0, add_image() = 1, 2, ...) to `material` as its tangent-space normal map (extension; DESIGN.md §28;
+        rt_scene_set_normal_map): OpenGL convention, green = +v.  Lambertian (plain, checker, noise, image) and metal materials take one."""
+        check(lib().rt_scene_set_normal_map(self.h, material, image, float(strength)))
+        return self
+
+    def clear_normal_map(self, material):
+        check(lib().rt_scene_clear_normal_map(self.h, material))
+        return self
+
+    def normal_maps(self):
+        """The scene's normal-map table (rt_scene_normal_maps): one record of capi.NORMAL_MAP_DT per material, or None while no material has a map."""
+        rec, n = C.c_void_p(), C.c_uint32()
+        check(lib().rt_scene_normal_maps(self.h, C.byref(rec), C.byref(n)))
+        return None if n.value == 0 else self._arr(rec.value, n.value, capi.NORMAL_MAP_DT)
+
     def MakeBox(self, a, b, mat, rotate_y=0.0, translate=(0, 0, 0)):
         """box(a, b, mat) of "The Next Week" as 6 quads, optionally rotate_y(degrees) then translate; returns the first quad index."""
         out = C.c_int32()
@@ -361,6 +377,11 @@ class Scene:
         table = self.textures()               # likewise the texture table, when it says more than the flat world does: an image beyond 0 or a mode that is not the default
         if table is not None and (len(table[0]) > 1 or table[0]["wrap"][0] != capi.WRAP_CLAMP or table[0]["filter"][0] != capi.FILTER_NEAREST):
             w.textures = table
+        nmaps = self.normal_maps()            # likewise the normal maps, and with them the table they name their images in
+        if nmaps is not None:
+            w.normal_maps = nmaps
+            if table is not None:
+                w.textures = table
         return w
 
     def _arr(self, ptr, n, dt):
@@ -496,6 +517,13 @@ def _push_textures(fn, handle, table):
     return fn(handle, records.ctypes.data if len(records) else None, len(records), texels.ctypes.data if len(texels) else None)
 
 
+def _push_normal_maps(fn, handle, table):
+    if table is None:
+        return fn(handle, None, 0)
+    table = np.ascontiguousarray(table, capi.NORMAL_MAP_DT).reshape(-1)
+    return fn(handle, table.ctypes.data if len(table) else None, len(table))
+
+
 def _env_image(image):
     img = np.ascontiguousarray(image, dtype=np.float32)
     if img.ndim != 3 or img.shape[2] != 3:
@@ -532,6 +560,8 @@ class Renderer:
             r.environment(world.environment[0], u0=world.environment[1])
         if getattr(world, "textures", None) is not None:
             r.textures(world.textures)
+        if getattr(world, "normal_maps", None) is not None:
+            r.normal_maps(world.normal_maps)
         return r
 
     def Render(self):
@@ -682,6 +712,23 @@ class Renderer:
         (rgb, wrap, filter) entries (api.texture_table); None = off.  A change restarts the refinement; an unchanged table keeps it."""
         check(_push_textures(lib().rt_renderer_textures, self.h, table))
 
+    def normal_maps(self, table):
+        """The normal-map table from the next launch on (rt_renderer_normal_maps): one record of capi.NORMAL_MAP_DT per material as Scene.normal_maps()
+        gives it; None = off.  The images it names are the texture table's (Renderer.textures).  A change restarts the refinement; an unchanged table keeps it."""
+        check(_push_normal_maps(lib().rt_renderer_normal_maps, self.h, table))
+
+    def normal_maps_info(self):
+        """{'enabled', 'mapped'} of the renderer's normal-map table: mapped = how many materials have a map."""
+        out = (C.c_uint32 * 2)()
+        check(lib().rt_renderer_normal_maps_info(self.h, out))
+        return {"enabled": bool(out[0]), "mapped": out[1]}
+
+    def kernel_normal_map(self):
+        """True when the next launch runs the streaming kernel's normal-map family (rt_renderer_kernel_normal_map): a normal-map table is on."""
+        out = C.c_uint32(0)
+        check(lib().rt_renderer_kernel_normal_map(self.h, C.byref(out)))
+        return bool(out.value)
+
     def textures_info(self):
         """{'enabled', 'entries'} of the renderer's texture table."""
         out = (C.c_uint32 * 2)()
@@ -797,6 +844,8 @@ class MultiRenderer:
             m.environment(world.environment[0], u0=world.environment[1])
         if getattr(world, "textures", None) is not None:
             m.textures(world.textures)
+        if getattr(world, "normal_maps", None) is not None:
+            m.normal_maps(world.normal_maps)
         return m
 
     def Render(self):
@@ -829,6 +878,16 @@ class MultiRenderer:
     def textures(self, table):
         """rt_renderer_textures on every rank; `table` as Renderer.textures takes it."""
         check(_push_textures(lib().rt_multi_renderer_textures, self.h, table))
+
+    def normal_maps(self, table):
+        """rt_renderer_normal_maps on every rank; `table` as Renderer.normal_maps takes it."""
+        check(_push_normal_maps(lib().rt_multi_renderer_normal_maps, self.h, table))
+
+    def normal_maps_info(self):
+        """{'enabled', 'mapped'} of the ranks' normal-map table (they hold the same one)."""
+        out = (C.c_uint32 * 2)()
+        check(lib().rt_multi_renderer_normal_maps_info(self.h, out))
+        return {"enabled": bool(out[0]), "mapped": out[1]}
 
     def textures_info(self):
         """{'enabled', 'entries'} of the ranks' texture table (they hold the same one)."""
@@ -1118,6 +1177,33 @@ def texture_lookup_batch(table, index, u, v):
 def probe_texture(table, index, u, v, device=0):
     """rt_probe_texture: texture_lookup_batch on the device, one lane per lookup"""
     return _texture_lookup(lambda *a: lib().rt_probe_texture(device, *a), table, index, u, v)
+
+
+def _normal_map(fn, table, surface, a, b, tri_uv, normal, ray_d, u, v, index, strength):
+    records, texels = texture_table(table)
+    surface, index = np.ascontiguousarray(surface, np.uint32).reshape(-1), np.ascontiguousarray(index, np.uint32).reshape(-1)
+    n = len(surface)
+    a, b, normal, ray_d = (np.ascontiguousarray(x, np.float32).reshape(-1, 3) for x in (a, b, normal, ray_d))
+    u, v, strength = (np.ascontiguousarray(x, np.float32).reshape(-1) for x in (u, v, strength))
+    tri_uv = None if tri_uv is None else np.ascontiguousarray(tri_uv, np.float32).reshape(-1, 6)
+    if not all(len(x) == n for x in (a, b, normal, ray_d, u, v, index, strength)) or (tri_uv is not None and len(tri_uv) != n):
+        raise ValueError("normal map: every array must have one entry per case")
+    out, path = np.zeros((n, 3), np.float32), np.zeros(n, np.uint32)
+    check(fn(records.ctypes.data if len(records) else None, len(records), texels.ctypes.data if len(texels) else None, n, surface, a, b,
+             None if tri_uv is None else tri_uv.ctypes.data, normal, ray_d, u, v, index, strength, out, path))
+    return out, path
+
+
+def normal_map_batch(table, surface, a, b, tri_uv, normal, ray_d, u, v, index, strength):
+    """rt_normal_map_batch (host only): the normal-map rule on n cases — per case its surface (capi.NMAP_SURFACE_*), a and b (a sphere's normal; a
+    record's u and v; given tangents), tri_uv (n, 6) or None, the normal, the ray's direction, the lookup's (u, v), the entry of `table` (as Renderer.textures
+    takes it) and the strength -> (normals (n, 3), path (n,) of capi.NMAP_*: replaced where path == capi.NMAP_REPLACED)"""
+    return _normal_map(lib().rt_normal_map_batch, table, surface, a, b, tri_uv, normal, ray_d, u, v, index, strength)
+
+
+def probe_normal_map(table, surface, a, b, tri_uv, normal, ray_d, u, v, index, strength, device=0):
+    """rt_probe_normal_map: normal_map_batch on the device, one lane per case"""
+    return _normal_map(lambda *args: lib().rt_probe_normal_map(device, *args), table, surface, a, b, tri_uv, normal, ray_d, u, v, index, strength)
 
 
 def _noise_value(fn, world, albedo, scale, points):

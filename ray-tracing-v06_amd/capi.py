@@ -33,6 +33,9 @@ MAT_DT = np.dtype([("albedo", "<f4", 3), ("param", "<f4"), ("albedo2", "<f4", 3)
 TRI_NORMALS_DT = np.dtype([("n0", "<f4", 3), ("n1", "<f4", 3), ("n2", "<f4", 3)])   # rt_tri_normals, 36 B
 TRI_UVS_DT = np.dtype([("t0", "<f4", 2), ("t1", "<f4", 2), ("t2", "<f4", 2)])   # rt_tri_uvs, 24 B
 TEXTURE_DT = np.dtype([("width", "<u4"), ("height", "<u4"), ("wrap", "<u4"), ("filter", "<u4"), ("first", "<u4")])   # rt_texture, 20 B
+NORMAL_MAP_DT = np.dtype([("on", "<u4"), ("image", "<u4"), ("strength", "<f4"), ("pad", "<u4")])   # rt_normal_map, 16 B
+NMAP_SURFACE_SPHERE, NMAP_SURFACE_PLANAR, NMAP_SURFACE_TRI_UV, NMAP_SURFACE_GIVEN = 0, 1, 2, 3
+NMAP_REPLACED, NMAP_FLAT, NMAP_NO_TANGENT, NMAP_NO_LENGTH, NMAP_FACING, NMAP_NO_FRAME = 1, 2, 3, 4, 5, 6
 WRAP_CLAMP, WRAP_REPEAT = 0, 1
 FILTER_NEAREST, FILTER_BILINEAR = 0, 1
 MAX_IMAGES = 256
@@ -105,6 +108,8 @@ SYMBOLS = [
     "rt_scene_add_image", "rt_scene_image_sampling", "rt_scene_textures", "rt_texture_lookup_batch", "rt_renderer_textures", "rt_renderer_textures_info",
     "rt_multi_renderer_textures", "rt_multi_renderer_textures_info", "rt_probe_texture",
     "rt_renderer_aov_enable_mode", "rt_renderer_aov_mode", "rt_noise_value_batch", "rt_probe_noise_value",
+    "rt_scene_set_normal_map", "rt_scene_clear_normal_map", "rt_scene_normal_maps", "rt_normal_map_batch", "rt_probe_normal_map",
+    "rt_renderer_normal_maps", "rt_renderer_normal_maps_info", "rt_renderer_kernel_normal_map", "rt_multi_renderer_normal_maps", "rt_multi_renderer_normal_maps_info",
 ]
 
 _lib = None
@@ -226,6 +231,16 @@ def lib():
     L.rt_multi_renderer_textures.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     L.rt_multi_renderer_textures_info.argtypes = [C.c_void_p, C.c_uint32 * 2]
     L.rt_probe_texture.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, u32p, f32p, f32p, C.c_size_t, f32p]
+    L.rt_scene_set_normal_map.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float]
+    L.rt_scene_clear_normal_map.argtypes = [C.c_void_p, C.c_uint32]
+    L.rt_scene_normal_maps.argtypes = [C.c_void_p, P(C.c_void_p), P(C.c_uint32)]
+    L.rt_normal_map_batch.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, u32p, f32p, f32p, C.c_void_p, f32p, f32p, f32p, f32p, u32p, f32p, f32p, u32p]
+    L.rt_probe_normal_map.argtypes = [C.c_int] + L.rt_normal_map_batch.argtypes
+    L.rt_renderer_normal_maps.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+    L.rt_renderer_normal_maps_info.argtypes = [C.c_void_p, C.c_uint32 * 2]
+    L.rt_renderer_kernel_normal_map.argtypes = [C.c_void_p, P(C.c_uint32)]
+    L.rt_multi_renderer_normal_maps.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+    L.rt_multi_renderer_normal_maps_info.argtypes = [C.c_void_p, C.c_uint32 * 2]
     L.rt_scene_set_background.argtypes = [C.c_void_p, C.c_uint32, vec3]
     L.rt_scene_set_perlin.argtypes = [C.c_void_p, C.c_uint64]
     L.rt_scene_set_image.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]

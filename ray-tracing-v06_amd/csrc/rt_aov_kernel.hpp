@@ -76,6 +76,39 @@ __device__ __forceinline__ f3 aov_albedo_tex(const DeviceWorld& w, const uint4* 
     return image_texel(w.image, w.image_w, w.image_h, tu, tv);
 }
 
+// Normal maps (aov_kernel_nmap): the first hit's normal is the mapped one, as the shade phase of an NMAP kernel forms it — the material's record of
+// the table behind the texture table (tail + tex_at, whose header's fourth lane says where), (u, v) and the tangents by the kind of surface, then normal_map_apply
+// on rec.normal, which is the flat or the smooth normal by now.
+__device__ __forceinline__ void aov_normal_map(const DeviceWorld& w, const uint4* tail, uint32_t uv_at, uint32_t tex_at, uint32_t first_tri, const Ray& ray, HitRec& rec) {
+    if (tex_at == 0u) return;
+    const uint4* tt = tail + tex_at;
+    const uint4 th = tt[0];
+    const uint32_t nm_at = (uint32_t)__builtin_amdgcn_readfirstlane((int)th.w);
+    if (nm_at == 0u) return;
+    const uint4 nr = tt[nm_at + rec.mat];
+    if (nr.x == 0u) return;
+    float tu, tv;
+    f3 dPdu, dPdv;
+    if ((uint32_t)rec.prim >= w.n_prims) {
+        const rt_quad& q = w.quads[(uint32_t)rec.prim - w.n_prims];
+        const f3 hit_p = ray_at(ray, rec.distance);
+        if (uv_at != 0u && (uint32_t)rec.prim >= first_tri) {
+            const float* tr = reinterpret_cast<const float*>(tail + uv_at) + (size_t)((uint32_t)rec.prim - first_tri) * 6u;
+            const float t0[2] = {tr[0], tr[1]}, t1[2] = {tr[2], tr[3]}, t2[2] = {tr[4], tr[5]};
+            tri_uv(ld3(q.Q), ld3(q.u), ld3(q.v), ld3(q.w), t0, t1, t2, hit_p, tu, tv);
+            if (!normal_map_tri_tangents(ld3(q.u), ld3(q.v), t0, t1, t2, dPdu, dPdv)) return;
+        } else {
+            quad_uv(ld3(q.Q), ld3(q.u), ld3(q.v), ld3(q.w), hit_p, tu, tv);
+            dPdu = ld3(q.u); dPdv = ld3(q.v);
+        }
+    } else {
+        sphere_uv(rec.normal, tu, tv);
+        normal_map_sphere_tangents(rec.normal, dPdu, dPdv);
+    }
+    const uint64_t texels = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)th.x) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)th.y) << 32;
+    normal_map_apply(texture_value(reinterpret_cast<const uint32_t*>(texels), tt[1u + nr.y], tu, tv), __uint_as_float(nr.z), dPdu, dPdv, ray.d, rec.normal);
+}
+
 // what the feature pass reads of a refine pass (a StreamParams would occupy scalar registers the traversal needs)
 struct AovParams {
     TileMap tm;
@@ -88,7 +121,8 @@ struct AovParams {
 
 // SMOOTH (aov_kernel_smooth): a hit on a triangle — unified index >= first_tri — takes its normal through shading_normal() from the table's record
 // TEX (aov_kernel_tex / aov_kernel_smooth_tex): the albedo is aov_albedo_tex's; tail = the header of the image's tail, first_tri as above
-template <int WALK, bool SMOOTH, bool TEX = false>
+// NMAP (aov_kernel_nmap): TEX, and the normal goes through aov_normal_map behind the smooth rule; vn may be null (no table of vertex normals)
+template <int WALK, bool SMOOTH, bool TEX = false, bool NMAP = false>
 __device__ __forceinline__ void aov_body(const AovParams& p, float4* __restrict__ aov, int32_t* lds_i, float* lds_f, const rt_tri_normals* vn, uint32_t first_tri,
                                          const uint4* tail = nullptr) {
     const uint32_t L = blockIdx.x * RT_AOV_BLOCK + threadIdx.x;
@@ -113,7 +147,8 @@ __device__ __forceinline__ void aov_body(const AovParams& p, float4* __restrict_
         if (aov_first_hit<WALK>(p.world, ray, rec, lds_i, lds_f)) {
             if constexpr (TEX) alb = aov_albedo_tex(p.world, tail, uv_at, tex_at, first_tri, p.world.mats[rec.mat], ray, rec);
             else alb = aov_albedo(p.world.mats[rec.mat], ray, rec);
-            if (SMOOTH && (uint32_t)rec.prim >= first_tri) shading_normal_flat(p.world.quads[(uint32_t)rec.prim - p.world.n_prims], vn[(uint32_t)rec.prim - first_tri], ray, rec.distance, rec.normal);
+            if (SMOOTH && (!NMAP || vn) && (uint32_t)rec.prim >= first_tri) shading_normal_flat(p.world.quads[(uint32_t)rec.prim - p.world.n_prims], vn[(uint32_t)rec.prim - first_tri], ray, rec.distance, rec.normal);
+            if constexpr (NMAP) aov_normal_map(p.world, tail, uv_at, tex_at, first_tri, ray, rec);
             g.x += rec.normal.x; g.y += rec.normal.y; g.z += rec.normal.z; g.w += rec.distance;
             a.w += 1.0f;
         }
@@ -152,6 +187,16 @@ __global__ __launch_bounds__(RT_AOV_BLOCK) void aov_kernel_smooth_tex(AovParams 
     __shared__ int32_t lds_i[WALK == RT_AOV_WALK_LIST ? 1u : RT_MAX_STACK * RT_AOV_BLOCK];
     __shared__ float lds_f[1u];
     aov_body<WALK, true, true>(p, aov, lds_i, lds_f, vn, first_tri, blob + blob_vec4);
+}
+
+// mode RT_AOV_TEXTURED of a renderer with a normal-map table: aov_kernel_smooth_tex with the mapped normal; vn = the table of vertex normals or null
+template <int WALK>
+__global__ __launch_bounds__(RT_AOV_BLOCK) void aov_kernel_nmap(AovParams p, float4* __restrict__ aov, const rt_tri_normals* __restrict__ vn, const uint4* __restrict__ blob,
+                                                                uint32_t blob_vec4, uint32_t first_tri) {
+    static_assert(WALK == RT_AOV_WALK_LIST || WALK == RT_AOV_WALK_STACK, "normal maps: lists and stack-walked BVHs");
+    __shared__ int32_t lds_i[WALK == RT_AOV_WALK_LIST ? 1u : RT_MAX_STACK * RT_AOV_BLOCK];
+    __shared__ float lds_f[1u];
+    aov_body<WALK, true, true, true>(p, aov, lds_i, lds_f, vn, first_tri, blob + blob_vec4);
 }
 
 // ---------------------------------------------------------------------------------------------

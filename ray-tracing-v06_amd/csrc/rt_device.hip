@@ -58,6 +58,7 @@ constexpr uint32_t RT_KEY_XCHG = 1u << 9;
 constexpr uint32_t RT_KEY_NEE = 1u << 10;   // light sampling (rt_renderer_light_sampling_enable): the NEE form of an EXT >= 1 stack-walk or list key
 constexpr uint32_t RT_KEY_LTREE = 1u << 12; // the light tree (mode RT_LIGHT_SAMPLING_TREE): the LTREE form of a TRI && NEE key; reported by rt_renderer_kernel_light_tree
 constexpr uint32_t RT_KEY_ENVL = 1u << 13;  // environment light sampling (mode RT_LIGHT_SAMPLING_ENV): the ENVL form of an EXT 2 TRI && NEE key; reported by rt_renderer_kernel_env_light
+constexpr uint32_t RT_KEY_NMAP = 1u << 14;  // normal maps (rt_renderer_normal_maps): the NMAP form of an EXT 2 TRI key, plain or with mode 48; reported by rt_renderer_kernel_normal_map
 constexpr uint32_t RT_KEY_TRI = 1u << 11;   // the world has triangles: the TRI form of an EXT >= 1 stack-walk or list key, plain or NEE; not one of rt_renderer_kernel_form's fields
 // a stream key read back into render_kernel_stream's template arguments, in stream_key()'s order, then NEE: what rt_renderer_kernel_form reports
 static void stream_key_fields(uint32_t key, uint32_t out[8]) {
@@ -103,6 +104,10 @@ static const void* stream_kernel_for(uint32_t key) {
     case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NEE | RT_KEY_ENVL: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, true, true, false, true>)
 #define RT_KERNEL_ENV_TREE(exact, world, ext, big, wide) \
     case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NEE | RT_KEY_LTREE | RT_KEY_ENVL: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, true, true, true, true>)
+#define RT_KERNEL_NORMAL_MAP(exact, world, ext, big, wide) \
+    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NMAP: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, false, true, false, false, true>)
+#define RT_KERNEL_NORMAL_MAP_ENV_TREE(exact, world, ext, big, wide) \
+    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NEE | RT_KEY_LTREE | RT_KEY_ENVL | RT_KEY_NMAP: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, true, true, true, true, true>)
     switch (key) {   // arguments: exact, filter, world, ext, big, wide, tol
         case RT_KEY_XCHG: return reinterpret_cast<const void*>(&render_kernel_xchg<RT_XCHG_BLOCK>);
         RT_KERNEL(true, false, RT_WORLD_BVH_QUEUE, 2, true, true, false); RT_KERNEL(true, false, RT_WORLD_BVH_QUEUE, 1, true, true, false); RT_KERNEL(true, false, RT_WORLD_BVH_QUEUE, 0, true, true, false);
@@ -148,9 +153,23 @@ static const void* stream_kernel_for(uint32_t key) {
         RT_KERNEL_ENV_TREE(false, RT_WORLD_BVH, 2, true, false); RT_KERNEL_ENV_TREE(true, RT_WORLD_BVH, 2, true, false);
         RT_KERNEL_ENV_TREE(true, RT_WORLD_LIST, 2, false, false);
         RT_KERNEL_ENV_TREE(false, RT_WORLD_BVH, 2, false, false); RT_KERNEL_ENV_TREE(true, RT_WORLD_BVH, 2, false, false);
+        // normal maps: the shapes of the environment-light family, plain ...
+        RT_KERNEL_NORMAL_MAP(true, RT_WORLD_LIST, 2, true, true);
+        RT_KERNEL_NORMAL_MAP(false, RT_WORLD_BVH, 2, true, true); RT_KERNEL_NORMAL_MAP(true, RT_WORLD_BVH, 2, true, true);
+        RT_KERNEL_NORMAL_MAP(false, RT_WORLD_BVH, 2, true, false); RT_KERNEL_NORMAL_MAP(true, RT_WORLD_BVH, 2, true, false);
+        RT_KERNEL_NORMAL_MAP(true, RT_WORLD_LIST, 2, false, false);
+        RT_KERNEL_NORMAL_MAP(false, RT_WORLD_BVH, 2, false, false); RT_KERNEL_NORMAL_MAP(true, RT_WORLD_BVH, 2, false, false);
+        // ... and under mode 48
+        RT_KERNEL_NORMAL_MAP_ENV_TREE(true, RT_WORLD_LIST, 2, true, true);
+        RT_KERNEL_NORMAL_MAP_ENV_TREE(false, RT_WORLD_BVH, 2, true, true); RT_KERNEL_NORMAL_MAP_ENV_TREE(true, RT_WORLD_BVH, 2, true, true);
+        RT_KERNEL_NORMAL_MAP_ENV_TREE(false, RT_WORLD_BVH, 2, true, false); RT_KERNEL_NORMAL_MAP_ENV_TREE(true, RT_WORLD_BVH, 2, true, false);
+        RT_KERNEL_NORMAL_MAP_ENV_TREE(true, RT_WORLD_LIST, 2, false, false);
+        RT_KERNEL_NORMAL_MAP_ENV_TREE(false, RT_WORLD_BVH, 2, false, false); RT_KERNEL_NORMAL_MAP_ENV_TREE(true, RT_WORLD_BVH, 2, false, false);
         default: return nullptr;
     }
 #undef RT_KERNEL
+#undef RT_KERNEL_NORMAL_MAP
+#undef RT_KERNEL_NORMAL_MAP_ENV_TREE
 #undef RT_KERNEL_ENV_TREE
 #undef RT_KERNEL_ENV_LIGHT
 #undef RT_KERNEL_LIGHT_TREE
@@ -290,7 +309,24 @@ struct rt_renderer {
     // the texture table (rt_renderer_textures): the entries and the texels as given (3 bytes per texel), and a device buffer of the renderer's own
     // with one dword r | g << 8 | b << 16 per texel, all images back to back; the tail carries (pointer low, pointer high, n, -) and one vec4 per entry
     struct { bool on = false; std::vector<rt_texture> records; std::vector<uint8_t> host; OwnedBuf texels; } tex;
+    // normal maps (rt_renderer_normal_maps): one record per material as given; the tail carries them behind the texture table, whose header points
+    // there.  While on, a plain launch and a mode-48 launch run the NMAP form of their kernel (plain / envt, resolved when the table or the mode comes on).
+    struct NormalMaps { bool on = false; uint32_t n_mapped = 0; std::vector<rt_normal_map> host; } nm;
+    struct { uint32_t key = 0; const void* kernel = nullptr; } nm_plain, nm_envt;
     bool tail_on() const { return vn.on || uv.on || env.on || tex.on; }
+    // the NMAP form of the renderer's kernel: the world's own shape at EXT 2 with TRI, plain or with mode 48's bits (0: a world no NMAP form walks)
+    uint32_t normal_map_key(bool envt) const {
+        if (variant < 2 || variant == 5 || tol || scene.queue || scene.dw.kind == RT_WORLD_NODE_TREE) return 0u;
+        const uint32_t base = stream_kernel_key(variant, false, scene);
+        return stream_key(base & 1u, false, (int)(base >> 2 & 3u), 2, base >> 6 & 1u, base >> 7 & 1u) | RT_KEY_TRI | RT_KEY_NMAP | (envt ? RT_KEY_NEE | RT_KEY_LTREE | RT_KEY_ENVL : 0u);
+    }
+    // whether a launch is refused for its normal maps (§28): one of them names an entry (*which) the renderer's texture table does not have
+    bool normal_map_entry_missing(uint32_t* which) const {
+        if (!nm.on) return false;
+        for (const rt_normal_map& m : nm.host)
+            if (m.on && (!tex.on || m.image >= tex.records.size() || tex.records[m.image].width == 0u)) { *which = m.image; return true; }
+        return false;
+    }
     // whether a launch is refused for its image materials (§25): one of them names an entry (*which) the renderer does not have
     bool texture_entry_missing(uint32_t* which) const {
         for (const uint32_t k : scene.image_indices)
@@ -326,12 +362,25 @@ struct rt_renderer {
         LaunchOn l;
         l.kernel = m ? nee.resolved[m - LIGHT_MODES].kernel : stream_kernel;
         l.key = m ? nee.resolved[m - LIGHT_MODES].key : stream_kernel_key(variant, tol, scene);
+        if (nm.on && !m) { l.kernel = nm_plain.kernel; l.key = nm_plain.key; }   // §28: the other modes are refused while a table is on
+        if (nm.on && mode == RT_LIGHT_SAMPLING_ENV_TREE) { l.kernel = nm_envt.kernel; l.key = nm_envt.key; }
         l.blob = (im.blob.p ? im.blob : scene.blob).as<uint4>();
         l.blob_vec4 = scene.packed.blob_vec4 + im.table_vec4;
         l.lds_bytes = i ? im.lds_bytes : stream_lds_bytes;
         l.blocks_per_cu = i ? im.blocks_per_cu : stream_blocks_per_cu;
         l.lights = m && !i ? env.w * env.h : t.refused.empty() ? t.n : 0u;
         return l;
+    }
+    // §28: the NMAP form of the plain kernel, or of mode 48's, once: the kernel and its LDS limit
+    int resolve_normal_map_kernel(bool envt, uint32_t lds_bytes) {
+        auto& slot_of = envt ? nm_envt : nm_plain;
+        if (slot_of.kernel) return RT_OK;
+        const uint32_t key = normal_map_key(envt);
+        const void* k = key ? stream_kernel_for(key) : nullptr;
+        if (!k) return rt_fail(RT_ERR_INVALID, "rt_renderer_normal_maps: this world's kernel has no form that reads a normal-map table");
+        HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+        slot_of.key = key; slot_of.kernel = k;
+        return RT_OK;
     }
     // Image i (0: the plain one; 1 to 4: with the light table of mode 1, 2, 4, 16) from the riders as they stand, into `fresh`: scene | light table | tail
     // (rt_launch_image.hpp has both layouts).  The scene part is copied device to device, the rest uploaded once.  The plain image without a tail gets no buffer.
@@ -354,6 +403,7 @@ struct rt_renderer {
         rd.env = env.on; rd.env_w = env.w; rd.env_h = env.h; rd.env_u0 = env.u0;
         rd.env_texels = (uint64_t)reinterpret_cast<uintptr_t>(env.texels.p); rd.env_dist = env.dist_on ? (uint64_t)reinterpret_cast<uintptr_t>(env.dist.p) : 0ull;
         rd.textures = tex.on; rd.texture = tex.records.data(); rd.n_textures = tex.records.size(); rd.texture_texels = (uint64_t)reinterpret_cast<uintptr_t>(tex.texels.p);
+        if (nm.on) { rd.normal_maps = nm.host.data(); rd.n_normal_maps = nm.host.size(); }
         rt_image::append_tail(rest, rd);
         const size_t scene_bytes = (size_t)scene.packed.blob_vec4 * sizeof(uint4);
         HIP_TRY(fresh.blob.alloc(scene_bytes + rest.size() * sizeof(uint4)));
@@ -774,6 +824,11 @@ struct rt_renderer {
             const LaunchOn plain = launch_on(RT_LIGHT_SAMPLING_OFF);
             const uint4* blob = plain.blob;
             const uint32_t blob_vec4 = plain.blob_vec4;
+            if (nm.on) {   // §28: the mapped normal; a table is on only where the world is a list or a BVH walked by the stack
+                const rt_tri_normals* vt = vn.on ? vn.table.as<rt_tri_normals>() : nullptr;
+                if (scene.dw.kind == RT_WORLD_LIST) aov_kernel_nmap<RT_AOV_WALK_LIST><<<grid, block, 0, st>>>(p, aov.as<float4>(), vt, blob, blob_vec4, first_tri);
+                else aov_kernel_nmap<RT_AOV_WALK_STACK><<<grid, block, 0, st>>>(p, aov.as<float4>(), vt, blob, blob_vec4, first_tri);
+            } else
             if (!vn.on) aov_kernel_tex_for(scene.dw)<<<grid, block, 0, st>>>(p, aov.as<float4>(), blob, blob_vec4, first_tri);
             else if (scene.dw.kind == RT_WORLD_LIST) aov_kernel_smooth_tex<RT_AOV_WALK_LIST><<<grid, block, 0, st>>>(p, aov.as<float4>(), vn.table.as<rt_tri_normals>(), blob, blob_vec4, first_tri);
             else aov_kernel_smooth_tex<RT_AOV_WALK_STACK><<<grid, block, 0, st>>>(p, aov.as<float4>(), vn.table.as<rt_tri_normals>(), blob, blob_vec4, first_tri);
@@ -880,6 +935,8 @@ static int enqueue_call(rt_renderer* r, void* hip_stream, float* d_out, uint32_t
         return rt_fail(RT_ERR_INVALID, "the world's background is an environment map (mode 2) and the renderer has none: give it one with rt_renderer_environment before rendering");
     if (uint32_t k = 0u; r->texture_entry_missing(&k))   // never launch on an index the table does not hold
         return rt_fail(RT_ERR_INVALID, "an image material of the world names image %u and the renderer's texture table has no such entry: give it one with rt_renderer_textures before rendering", k);
+    if (uint32_t k = 0u; r->normal_map_entry_missing(&k))   // ... nor on a normal map the table does not hold
+        return rt_fail(RT_ERR_INVALID, "a normal map of the world names image %u and the renderer's texture table has no such entry: give it one with rt_renderer_textures before rendering", k);
     HIP_TRY(hipSetDevice(r->cfg.device));
     hipStream_t st = (hipStream_t)hip_stream;  // NULL is the HIP null stream, as for any HIP launch
     HIP_TRY(hipEventRecord(r->ev0, st));
@@ -946,6 +1003,8 @@ extern "C" int rt_renderer_light_sampling_enable(rt_renderer* r, uint32_t on) {
         const rt_renderer::LightTable* t = m->image ? &r->nee.tab[m->image - 1u] : nullptr;
         if (r->variant < 2 || r->variant == 5 || r->tol)
             return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: kernel variant %u has no light-sampling form (the baseline kernel 1, the ray exchange 5 and the tolerance mode 6 do not; use variant 0, 2 or 3)", r->tol ? 6u : r->variant);
+        if (r->nm.on && on != RT_LIGHT_SAMPLING_ENV_TREE)
+            return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: the renderer has a normal-map table, and light-sampling mode %u has no kernel that reads one: normal maps render with light sampling off or in mode 48 (take the table away with rt_renderer_normal_maps(NULL, 0) first)", on);
         if (m->env && r->scene.dw.background != 2u)   // a world of this kind takes the modes of the light tables only, so the message lists them
             return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: mode %u samples the environment map of a world with background mode 2 (rt_scene_set_environment)%s; this world's is %u, for which on must be 0 (off), 1 (quad lights), 2 (quad and sphere lights), 4 (quad, sphere and triangle lights) or 16 (those, through a light tree, chosen by area)", on, m->beside, r->scene.dw.background);
         if (m->env && r->scene.queue)
@@ -974,6 +1033,8 @@ extern "C" int rt_renderer_light_sampling_enable(rt_renderer* r, uint32_t on) {
             resolved.key = key;
             resolved.kernel = k;
         }
+        if (r->nm.on)   // §28: mode 48's NMAP form, on the image of mode 16's table
+            if (const int rc = r->resolve_normal_map_kernel(true, r->launch_on(on).lds_bytes)) return rc;
         if (m->env && !r->env.dist_on) {   // the distribution of the map as it stands (a map given while the mode is on brings its own: rt_renderer_environment); an all-black map is refused here
             char who[64];
             std::snprintf(who, sizeof(who), "rt_renderer_light_sampling_enable: mode %u", on);
@@ -1132,6 +1193,57 @@ extern "C" int rt_renderer_textures(rt_renderer* r, const rt_texture* records, u
     return r->replace_rider(r->tex, next);
 }
 
+// Normal maps.  Off: every launch is what it was.  On: the NMAP form of the renderer's kernel on images whose tail holds the records behind the
+// texture table.  The entries the records name are checked at every launch (enqueue_call), as an image material's is: the tables come and go independently.
+extern "C" int rt_renderer_normal_maps(rt_renderer* r, const rt_normal_map* table, uint32_t n) {
+    if (!r) return rt_fail(RT_ERR_INVALID, "rt_renderer_normal_maps: null renderer");
+    if ((table == nullptr) != (n == 0u)) return rt_fail(RT_ERR_INVALID, "rt_renderer_normal_maps: a table and its count go together (NULL, 0 turns it off)");
+    uint32_t n_mapped = 0;
+    if (n) {
+        if (r->variant < 2) return rt_fail(RT_ERR_INVALID, "rt_renderer_normal_maps: the baseline kernel (variant 1) reads no normal-map table; use variant 0, 2 or 3");
+        if (r->variant == 5 || r->tol) return rt_fail(RT_ERR_INVALID, "rt_renderer_normal_maps: kernel variant %u reads no texture table and no normal-map table", r->tol ? 6u : 5u);
+        if (r->scene.queue) return rt_fail(RT_ERR_INVALID, "rt_renderer_normal_maps: a world with a queue or wide4 traversal renders on lane walks that read no normal-map table (RT_TRAVERSAL_STACK and lists do)");
+        if (r->scene.dw.kind == RT_WORLD_NODE_TREE) return rt_fail(RT_ERR_INVALID, "rt_renderer_normal_maps: a bvh_node tree renders on a walk that reads no normal-map table (BVHs walked by the stack and lists do)");
+        if (r->nee.on() && r->nee.mode != RT_LIGHT_SAMPLING_ENV_TREE)
+            return rt_fail(RT_ERR_INVALID, "rt_renderer_normal_maps: light-sampling mode %u is on, which has no kernel that reads a normal-map table: normal maps render with light sampling off or in mode 48", r->nee.mode);
+        if (r->aov_on && r->aov_mode == RT_AOV_PLAIN)
+            return rt_fail(RT_ERR_INVALID, "rt_renderer_normal_maps: the plain feature pass is on, whose normals know no normal map: enable it in RT_AOV_TEXTURED mode (rt_renderer_aov_enable_mode)");
+        if (n != r->scene.dw.n_mats) return rt_fail(RT_ERR_INVALID, "rt_renderer_normal_maps: %u records for a world of %u materials", n, r->scene.dw.n_mats);
+        for (uint32_t i = 0; i < n; i++) {
+            if (!table[i].on) continue;
+            const uint32_t type = r->scene.mat_types[i];
+            if (type == RT_MAT_DIELECTRIC || type == RT_MAT_DIFFUSE_LIGHT || type == RT_MAT_ISOTROPIC)
+                return rt_fail(RT_ERR_INVALID, "rt_renderer_normal_maps: record %u: a dielectric, a light or a medium takes no normal map", i);
+            if (table[i].image >= RT_MAX_IMAGES) return rt_fail(RT_ERR_INVALID, "rt_renderer_normal_maps: record %u: an image index lies in [0, %u)", i, RT_MAX_IMAGES);
+            if (!(std::isfinite(table[i].strength) && table[i].strength >= 0.0f)) return rt_fail(RT_ERR_INVALID, "rt_renderer_normal_maps: record %u: a strength must be finite and >= 0", i);
+            n_mapped++;
+        }
+    }
+    const size_t bytes = (size_t)n * sizeof(rt_normal_map);
+    if (n ? (r->nm.on && r->nm.host.size() == n && std::memcmp(r->nm.host.data(), table, bytes) == 0) : !r->nm.on) return RT_OK;   // nothing changes, the refinement goes on
+    if (const int rc = wait_last_call(r)) return rc;   // launches already enqueued read the images that are replaced below (sets the device)
+    if (n) {
+        if (const int rc = r->resolve_normal_map_kernel(false, r->stream_lds_bytes)) return rc;
+        if (r->nee.mode == RT_LIGHT_SAMPLING_ENV_TREE)
+            if (const int rc = r->resolve_normal_map_kernel(true, r->launch_on(RT_LIGHT_SAMPLING_ENV_TREE).lds_bytes)) return rc;
+    }
+    r->refine_done = 0;   // samples shaded with other normals belong to another frame
+    r->aov_done = 0;
+    rt_renderer::NormalMaps next;
+    if (n) {
+        next.on = true; next.n_mapped = n_mapped; next.host.assign(table, table + n);
+        for (rt_normal_map& m : next.host) { m.pad = 0u; if (!m.on) m = rt_normal_map{0u, 0u, 0.0f, 0u}; }
+    }
+    return r->replace_rider(r->nm, next);
+}
+
+extern "C" int rt_renderer_normal_maps_info(rt_renderer* r, uint32_t out[2]) {
+    if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_normal_maps_info: null argument");
+    out[0] = r->nm.on ? 1u : 0u;
+    out[1] = r->nm.on ? r->nm.n_mapped : 0u;
+    return RT_OK;
+}
+
 extern "C" int rt_renderer_textures_info(rt_renderer* r, uint32_t out[2]) {
     if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_textures_info: null argument");
     out[0] = r->tex.on ? 1u : 0u;
@@ -1228,6 +1340,8 @@ static int aov_enable(const char* who, rt_renderer* r, uint32_t max_samples, uin
     if (mode > RT_AOV_TEXTURED) return rt_fail(RT_ERR_INVALID, "%s: unknown mode %u (RT_AOV_PLAIN = 0, RT_AOV_TEXTURED = 1)", who, mode);
     if (r->variant < 2)
         return rt_fail(RT_ERR_INVALID, "%s: the baseline kernel (variant 1) cannot refine and keeps no primary-ray records; feature buffers need a streaming variant (0, or 2 to 6)", who);
+    if (mode == RT_AOV_PLAIN && r->nm.on)
+        return rt_fail(RT_ERR_INVALID, "%s: the renderer has a normal-map table, and the plain feature pass's normals know no normal map: enable the pass in RT_AOV_TEXTURED mode (rt_renderer_aov_enable_mode)", who);
     if (mode == RT_AOV_PLAIN && r->aov_refused)
         return rt_fail(RT_ERR_INVALID, "%s: the world has %s: the feature pass covers spheres and quads with Lambertian, metal, dielectric, checker and light materials", who, r->aov_refused);
     if (mode == RT_AOV_TEXTURED && r->has_medium)   // §27: a medium's first event is an RNG draw, which no trace of the feature pass makes
@@ -1416,6 +1530,11 @@ extern "C" int rt_renderer_kernel_triangles(rt_renderer* r, uint32_t* out) {
 extern "C" int rt_renderer_kernel_env_light(rt_renderer* r, uint32_t* out) {
     if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_kernel_env_light: null argument");
     *out = r->launch_on(r->nee.mode).key & RT_KEY_ENVL ? 1u : 0u;   // (no plain key has the bit)
+    return RT_OK;
+}
+extern "C" int rt_renderer_kernel_normal_map(rt_renderer* r, uint32_t* out) {
+    if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_kernel_normal_map: null argument");
+    *out = r->variant >= 2 && (r->launch_on(r->nee.mode).key & RT_KEY_NMAP) ? 1u : 0u;
     return RT_OK;
 }
 

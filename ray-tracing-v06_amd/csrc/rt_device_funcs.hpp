@@ -526,6 +526,53 @@ RT_HD f3 texture_value(const uint32_t* texels, uint4 rec, float u, float v) {
     return texture_bilinear(texels, rec, u, v);
 }
 
+// Normal maps (rt06.h: rt_scene_set_normal_map): a tangent-space map bends the normal the shade phase has.  Two functions: the directions in
+// which a triangle's texture coordinates grow, and the rule.  The tangents are unnormalised and belong to the lookup's (u, v) before the image flip: on a sphere
+// (n.z, 0, -n.x) and (0, 1, 0) (sphere_uv's phi = atan2(-z, x)), on a parallelogram and on a triangle without coordinates the record's u and v, on a triangle
+// with coordinates t0, t1, t2 the two below.  Only + - * / sqrt and comparisons, each rounded on its own: the probe and rt_normal_map_batch call these
+// functions, and numpy float32 restates them bit for bit.
+RT_HD void normal_map_sphere_tangents(f3 n, f3& dPdu, f3& dPdv) {
+    dPdu = mk3(n.z, 0.0f, -n.x);
+    dPdv = mk3(0.0f, 1.0f, 0.0f);
+}
+// false: the coordinates span no area (det == 0, or a NaN), there is no frame and the normal stays
+RT_HD bool normal_map_tri_tangents(f3 u, f3 v, const float t0[2], const float t1[2], const float t2[2], f3& dPdu, f3& dPdv) {
+    const float du1 = t1[0] - t0[0], dv1 = t1[1] - t0[1];
+    const float du2 = t2[0] - t0[0], dv2 = t2[1] - t0[1];
+    const float det = du1 * dv2 - du2 * dv1;
+    if (!(det > 0.0f || det < 0.0f)) return false;
+    dPdu = u * dv2 - v * dv1;
+    dPdv = v * du1 - u * du2;
+    if (det < 0.0f) { dPdu = -dPdu; dPdv = -dPdv; }   // mirrored coordinates
+    return true;
+}
+// c = texture_value of the map's entry at the hit's (u, v); `normal` = the flat or smooth normal, facing as the shade phase leaves it.  Decode (byte 128 is zero,
+// 127 steps are one), scale x and y, Gram-Schmidt dPdu against the normal, a bitangent on dPdv's side, and the mapped normal only if it sees the ray from the
+// side the normal sees it from.  Returns the path taken (rt06.h): RT_NMAP_REPLACED, or why the normal stays.
+RT_HD uint32_t normal_map_apply(f3 c, float strength, f3 dPdu, f3 dPdv, f3 ray_d, f3& normal) {
+    const float C0 = 128.0f * 0x1.010102p-8f;   // texture_texel's byte 128
+    const float K = 255.0f / 127.0f;
+    f3 m = (c - mk3(C0)) * K;
+    m.x = m.x * strength;
+    m.y = m.y * strength;
+    if (m.x == 0.0f && m.y == 0.0f) return RT_NMAP_FLAT;
+    const f3 N = normal;
+    f3 T = dPdu - N * dot(N, dPdu);
+    const float tt = dot(T, T);
+    if (!(tt > 0.0f)) return RT_NMAP_NO_TANGENT;   // a sphere's poles, a degenerate u
+    T = T / sqrtf(tt);
+    f3 B = cross(N, T);
+    if (dot(B, dPdv) < 0.0f) B = -B;
+    const f3 g = (T * m.x + B * m.y) + N * m.z;
+    const float l2 = dot(g, g);
+    if (!(l2 > 0.0f)) return RT_NMAP_NO_LENGTH;
+    const f3 s = g / sqrtf(l2);
+    const float ds = dot(ray_d, s), dn = dot(ray_d, N);
+    if (!((ds > 0.0f && dn > 0.0f) || (ds < 0.0f && dn < 0.0f))) return RT_NMAP_FACING;
+    normal = s;
+    return RT_NMAP_REPLACED;
+}
+
 // Environment maps (rt06.h: rt_scene_set_environment): what a ray that leaves the world sees.  d = the ray's direction (any length), texels =
 // width x height records (r, g, b, -), row 0 at the top, u0 in [0, 1) = the rotation about y.  image_value's map and constants, the rotation added to u, then
 // image_texel's rule; the clamps are written so that a NaN coordinate lands on texel 0 on host and device alike.  Only + - * / sqrt, comparisons and the two rt_

@@ -171,7 +171,9 @@ struct rt_scene {
     std::vector<uint32_t> image_wrap = {RT_WRAP_CLAMP}, image_filter = {RT_FILTER_NEAREST};   // one per entry, entry 0 included
     mutable std::vector<rt_texture> table;
     mutable std::vector<uint8_t> table_texels;
-    std::vector<rt_bvh_node> nodes;      // world nodes (BVH or bvh_node tree)
+    std::vector<rt_normal_map> nmaps;    // normal maps: a record per material, grown on demand (a material behind its end has none)
+    mutable std::vector<rt_normal_map> nmap_table;   // what rt_scene_normal_maps last handed out
+    std::vector<rt_bvh_node> nodes;     // world nodes (BVH or bvh_node tree)
     std::vector<rt_bvh_node> tree_nodes;  // bvh_node objects created by rt_scene_add_bvh_node
     uint32_t kind = RT_WORLD_LIST;
     int32_t root = 0;
@@ -1007,6 +1009,38 @@ extern "C" int rt_scene_textures(const rt_scene* s, const rt_texture** out_recor
     for (const rt_scene::Image& im : s->more_images) entry(im.w, im.h, im.rgb);
     *out_records = s->table.data(); *out_n = (uint32_t)s->table.size();
     *out_texels = s->table_texels.empty() ? nullptr : s->table_texels.data();
+    return RT_OK;
+}
+
+// ---- normal maps ----
+extern "C" int rt_scene_set_normal_map(rt_scene* s, uint32_t material, uint32_t image, float strength) {
+    if (!s) return rt_fail(RT_ERR_INVALID, "rt_scene_set_normal_map: null scene");
+    if (material >= s->mats.size()) return rt_fail(RT_ERR_INVALID, "rt_scene_set_normal_map: the scene has no material %u", material);
+    const uint32_t type = s->mats[material].type;
+    if (type == RT_MAT_DIELECTRIC || type == RT_MAT_DIFFUSE_LIGHT || type == RT_MAT_ISOTROPIC)
+        return rt_fail(RT_ERR_INVALID, "rt_scene_set_normal_map: material %u is a dielectric, a light or a medium; Lambertian (plain, checker, noise, image) and metal materials take a normal map", material);
+    if (image >= RT_MAX_IMAGES) return rt_fail(RT_ERR_INVALID, "rt_scene_set_normal_map: an image index lies in [0, %u), not %u", RT_MAX_IMAGES, image);
+    if (!(std::isfinite(strength) && strength >= 0.0f)) return rt_fail(RT_ERR_INVALID, "rt_scene_set_normal_map: a strength must be finite and >= 0");
+    if (s->nmaps.size() <= material) s->nmaps.resize((size_t)material + 1u, rt_normal_map{0u, 0u, 0.0f, 0u});
+    s->nmaps[material] = rt_normal_map{1u, image, strength, 0u};
+    return RT_OK;
+}
+extern "C" int rt_scene_clear_normal_map(rt_scene* s, uint32_t material) {
+    if (!s) return rt_fail(RT_ERR_INVALID, "rt_scene_clear_normal_map: null scene");
+    if (material >= s->mats.size()) return rt_fail(RT_ERR_INVALID, "rt_scene_clear_normal_map: the scene has no material %u", material);
+    if (material < s->nmaps.size()) s->nmaps[material] = rt_normal_map{0u, 0u, 0.0f, 0u};
+    return RT_OK;
+}
+extern "C" int rt_scene_normal_maps(const rt_scene* s, const rt_normal_map** out, uint32_t* out_n) {
+    if (!s || !out || !out_n) return rt_fail(RT_ERR_INVALID, "rt_scene_normal_maps: null argument");
+    *out = nullptr; *out_n = 0u;
+    s->nmap_table.clear();
+    bool any = false;
+    for (const rt_normal_map& m : s->nmaps) any = any || m.on != 0u;
+    if (!any) return RT_OK;
+    s->nmap_table = s->nmaps;
+    s->nmap_table.resize(s->mats.size(), rt_normal_map{0u, 0u, 0.0f, 0u});
+    *out = s->nmap_table.data(); *out_n = (uint32_t)s->nmap_table.size();
     return RT_OK;
 }
 

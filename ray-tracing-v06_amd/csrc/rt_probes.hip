@@ -95,6 +95,23 @@ __global__ void probe_texture_kernel(size_t n, const uint32_t* texels, const uin
     if (i >= n) return;
     st3(out_rgb + 3 * i, texture_value(texels, entries[index[i]], u[i], v[i]));
 }
+// the normal-map rule (normal_map_apply and the tangents) on one case: what rt_normal_map_batch runs on the host and the probe one lane each
+RT_HD uint32_t normal_map_case(const uint32_t* texels, uint4 entry, uint32_t surface, f3 a, f3 b, const float* t, f3 ray_d, float u, float v, float strength, f3& normal) {
+    f3 dPdu = a, dPdv = b;
+    if (surface == RT_NMAP_SURFACE_SPHERE) normal_map_sphere_tangents(a, dPdu, dPdv);
+    else if (surface == RT_NMAP_SURFACE_TRI_UV && !normal_map_tri_tangents(a, b, t, t + 2, t + 4, dPdu, dPdv)) return RT_NMAP_NO_FRAME;
+    return normal_map_apply(texture_value(texels, entry, u, v), strength, dPdu, dPdv, ray_d, normal);
+}
+__global__ void probe_normal_map_kernel(size_t n, const uint32_t* texels, const uint4* entries, const uint32_t* surface, const float* a, const float* b, const float* tri_uv,
+                                        const float* normal, const float* ray_d, const float* u, const float* v, const uint32_t* index, const float* strength,
+                                        float* out_normal, uint32_t* out_path) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    f3 nn = ld3(normal + 3 * i);
+    out_path[i] = normal_map_case(texels, entries[index[i]], surface[i], ld3(a + 3 * i), ld3(b + 3 * i), tri_uv ? tri_uv + 6 * i : nullptr, ld3(ray_d + 3 * i), u[i], v[i],
+                                  strength[i], nn);
+    st3(out_normal + 3 * i, nn);
+}
 __global__ void probe_noise_value_kernel(size_t n, const rt_perlin* perlin, f3 albedo, float scale, const float* points, float* out_rgb) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -437,6 +454,49 @@ extern "C" int rt_texture_lookup_batch(const rt_texture* records, uint32_t n, co
     TextureTable t;
     if (const int rc = texture_table_args("rt_texture_lookup_batch", records, n, texels, index, u, v, count, out_rgb, t)) return rc;
     for (size_t i = 0; i < count; i++) st3(out_rgb + 3 * i, texture_value(t.dwords.data(), t.entries[index[i]], u[i], v[i]));
+    return RT_OK;
+}
+// Normal maps: the rule over arrays of cases, on the device and — HOST (no GPU) — here
+static int normal_map_args(const char* who, const rt_texture* records, uint32_t n, const uint8_t* texels, size_t count, const uint32_t* surface, const float* a, const float* b,
+                           const float* tri_uv, const float* normal, const float* ray_d, const float* u, const float* v, const uint32_t* index, const float* strength,
+                           float* out_normal, uint32_t* out_path, TextureTable& t) {
+    if (count && (!surface || !a || !b || !normal || !ray_d || !strength || !out_path)) return rt_fail(RT_ERR_INVALID, "%s: null argument", who);
+    if (const int rc = texture_table_args(who, records, n, texels, index, u, v, count, out_normal, t)) return rc;
+    for (size_t i = 0; i < count; i++) {
+        if (surface[i] > RT_NMAP_SURFACE_GIVEN) return rt_fail(RT_ERR_INVALID, "%s: case %zu: unknown surface %u", who, i, surface[i]);
+        if (surface[i] == RT_NMAP_SURFACE_TRI_UV && !tri_uv) return rt_fail(RT_ERR_INVALID, "%s: case %zu is a triangle with coordinates, and tri_uv is null", who, i);
+        if (!(std::isfinite(strength[i]) && strength[i] >= 0.0f)) return rt_fail(RT_ERR_INVALID, "%s: case %zu: a strength must be finite and >= 0", who, i);
+    }
+    return RT_OK;
+}
+extern "C" int rt_probe_normal_map(int device, const rt_texture* records, uint32_t n, const uint8_t* texels, size_t count, const uint32_t* surface, const float* a,
+                                   const float* b, const float* tri_uv, const float* normal, const float* ray_d, const float* u, const float* v, const uint32_t* index,
+                                   const float* strength, float* out_normal, uint32_t* out_path) {
+    TextureTable t;
+    if (const int rc = normal_map_args("rt_probe_normal_map", records, n, texels, count, surface, a, b, tri_uv, normal, ray_d, u, v, index, strength, out_normal, out_path, t)) return rc;
+    if (count == 0) return RT_OK;
+    ProbeRun p(device);
+    auto dw = p.in(t.dwords.data(), t.dwords.size());
+    auto en = p.in(t.entries.data(), t.entries.size());
+    auto sf = p.in(surface, count); auto da = p.in(a, 3 * count); auto db = p.in(b, 3 * count);
+    const float* dt = tri_uv ? p.in(tri_uv, 6 * count) : nullptr;
+    auto dn = p.in(normal, 3 * count); auto dd = p.in(ray_d, 3 * count); auto du = p.in(u, count); auto dv = p.in(v, count);
+    auto ix = p.in(index, count); auto st = p.in(strength, count);
+    auto on = p.out(out_normal, 3 * count); auto op = p.out(out_path, count);
+    p.launch(probe_normal_map_kernel, p.per_case(count), 128, count, dw, en, sf, da, db, dt, dn, dd, du, dv, ix, st, on, op);
+    return p.finish();
+}
+extern "C" int rt_normal_map_batch(const rt_texture* records, uint32_t n, const uint8_t* texels, size_t count, const uint32_t* surface, const float* a, const float* b,
+                                   const float* tri_uv, const float* normal, const float* ray_d, const float* u, const float* v, const uint32_t* index, const float* strength,
+                                   float* out_normal, uint32_t* out_path) {
+    TextureTable t;
+    if (const int rc = normal_map_args("rt_normal_map_batch", records, n, texels, count, surface, a, b, tri_uv, normal, ray_d, u, v, index, strength, out_normal, out_path, t)) return rc;
+    for (size_t i = 0; i < count; i++) {
+        f3 nn = ld3(normal + 3 * i);
+        out_path[i] = normal_map_case(t.dwords.data(), t.entries[index[i]], surface[i], ld3(a + 3 * i), ld3(b + 3 * i), tri_uv ? tri_uv + 6 * i : nullptr, ld3(ray_d + 3 * i),
+                                      u[i], v[i], strength[i], nn);
+        st3(out_normal + 3 * i, nn);
+    }
     return RT_OK;
 }
 // The marble: the kernels' noise_value() over arrays, on the device and — HOST (no GPU) — here

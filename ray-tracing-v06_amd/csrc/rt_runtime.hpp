@@ -99,6 +99,7 @@ struct DeviceScene {
     bool extended = false;  // quads, an emissive material or a constant background: beyond the reference's feature set
     bool textured = false;  // a Perlin or image material: the EXT = 2 kernels
     std::vector<uint32_t> image_indices;   // §25: the image each RT_MAT_LAMBERTIAN_IMAGE material names, in the materials' order
+    std::vector<uint32_t> mat_types;       // §28: every material's type, for the renderer's check of a normal-map table
     DeviceWorld dw{};
     PackedSceneRef packed{};  // valid when has_packed
     bool has_packed = false;
@@ -263,7 +264,9 @@ struct DeviceScene {
         extended = w->n_quads != 0 || w->background != 0;
         textured = w->background == 2u;   // an environment map is looked up by the EXT = 2 kernels: the world is theirs from creation
         image_indices.clear();
+        mat_types.clear();
         for (uint32_t i = 0; i < w->n_materials; i++) {
+            mat_types.push_back(w->materials[i].type);
             if (w->materials[i].type > RT_MAT_LAMBERTIAN_IMAGE) return rt_fail(RT_ERR_INVALID, "material %u: unknown type", i);
             if (w->materials[i].type == RT_MAT_LAMBERTIAN_NOISE && !w->perlin) return rt_fail(RT_ERR_INVALID, "material %u is a noise texture but the world has no Perlin tables (rt_scene_set_perlin)", i);
             if (w->materials[i].type == RT_MAT_LAMBERTIAN_IMAGE) {   // §25: albedo2[0] names the image; param means nothing here

@@ -261,12 +261,16 @@ __device__ __forceinline__ f3 texture_table_value(const uint4* tt, uint32_t imag
 // ENVL (mode RT_LIGHT_SAMPLING_ENV; EXT == 2 && NEE && TRI only, whether or not the world has a triangle): the light half draws its direction from
 //      the environment map — environment_sample on the distribution the tail's environment record points to — and the light density is the map's own
 //      (environment_density); the light table's pick, point, density loop and tree walk are compiled out.  No shadow ray: the direction is followed.
+// NMAP (rt_renderer_normal_maps; EXT == 2 && TRI only, whether or not the world has a triangle): a hit on a material whose record of the tail's
+//      normal-map table says `on` bends its normal by normal_map_apply, once, right after the flat or smooth normal is known; an image-textured hit shares its
+//      (u, v) with the map.  The table lies behind the texture table, whose header's fourth lane says where; both words are read at the hit, through scalars.
 // LTREE && ENVL (mode RT_LIGHT_SAMPLING_ENV_TREE): both at once.  The light half tosses once more between the map and mode 16's table (no toss
 //      when the table is empty: n_l == 0 is the map alone), the light density is the mean of the map's and the walk's, and an image-textured Lambertian hit is
 //      sampled as the diffuse hit it is — its albedo is looked up behind the direction, as ever.
 template <bool EXACT, bool FILTER, int BLOCK, int WORLD = RT_WORLD_BVH, int EXT = 0, bool BIG = false, bool WIDE = BIG, bool TOL = false, bool NEE = false, bool TRI = false,
-          bool LTREE = false, bool ENVL = false>
+          bool LTREE = false, bool ENVL = false, bool NMAP = false>
 __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(StreamParams p) {
+    static_assert(!NMAP || (EXT == 2 && TRI), "normal maps: one family of the kernels that read the texture table, plain and with mode 48");
     static_assert(!NEE || (EXT >= 1 && WORLD != RT_WORLD_BVH_QUEUE), "light sampling: worlds with quads, walked by the stack or as a list");
     static_assert(!TRI || (EXT >= 1 && WORLD != RT_WORLD_BVH_QUEUE), "triangles: worlds with quads; a lane walk reads the kind from the flat record");
     static_assert(!LTREE || (NEE && TRI), "the light tree: one family, which knows all three kinds of light");
@@ -670,6 +674,48 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                     normal = (hit_p - center) / sph.w;  // SphereHittable.cu:64 / :100
                     mat_bits = __float_as_uint(ex.w);
                 }
+                // §28: the normal map of the hit's material, if it has one: (u, v) and the tangents by the kind of surface, then the rule; the image lookup below
+                // takes the same (u, v) — on a sphere the normal it would compute them from may just have been replaced
+                float nm_tu = 0.0f, nm_tv = 0.0f;
+                bool nm_uv = false;
+                if constexpr (NMAP) {
+                    const uint32_t tex_here = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.scene.blob[p.scene.blob_vec4].w);
+                    if (tex_here != 0u) {
+                        const uint4* tt = p.scene.blob + p.scene.blob_vec4 + tex_here;
+                        const uint4 th = tt[0];
+                        const uint32_t nm_at = (uint32_t)__builtin_amdgcn_readfirstlane((int)th.w);
+                        if (nm_at != 0u) {
+                            const uint4 nr = tt[nm_at + (mat_bits & RT_MAT_INDEX_MASK)];   // (on, image, strength bits, -): per lane, lanes sit on different materials
+                            if (nr.x != 0u) {
+                                f3 dPdu, dPdv;
+                                bool frame = true;
+                                if ((uint32_t)rec_code >= p.scene.sphere_codes) {
+                                    const uint32_t qi = (uint32_t)rec_code - p.scene.sphere_codes;
+                                    const float4* qd = quads + qi * 4u;
+                                    const float4 a0 = qd[0], a1 = qd[1], a2 = qd[2], a3 = qd[3];
+                                    const f3 qu = mk3(a1.x, a1.y, a1.z), qv = mk3(a1.w, a2.x, a2.y);
+                                    if (uv_at != 0u && qi >= p.scene.n_plain_quads) {
+                                        const float* tr = reinterpret_cast<const float*>(p.scene.blob + p.scene.blob_vec4 + uv_at) + (size_t)(qi - p.scene.n_plain_quads) * 6u;
+                                        const float t0[2] = {tr[0], tr[1]}, t1[2] = {tr[2], tr[3]}, t2[2] = {tr[4], tr[5]};
+                                        tri_uv(mk3(a0.x, a0.y, a0.z), qu, qv, mk3(a3.y, a3.z, a3.w), t0, t1, t2, hit_p, nm_tu, nm_tv);
+                                        frame = normal_map_tri_tangents(qu, qv, t0, t1, t2, dPdu, dPdv);
+                                    } else {
+                                        quad_uv(mk3(a0.x, a0.y, a0.z), qu, qv, mk3(a3.y, a3.z, a3.w), hit_p, nm_tu, nm_tv);
+                                        dPdu = qu; dPdv = qv;
+                                    }
+                                } else {
+                                    sphere_uv(normal, nm_tu, nm_tv);
+                                    normal_map_sphere_tangents(normal, dPdu, dPdv);
+                                }
+                                nm_uv = true;
+                                if (frame) {
+                                    const uint64_t texels = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)th.x) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)th.y) << 32;
+                                    normal_map_apply(texture_value(reinterpret_cast<const uint32_t*>(texels), tt[1u + nr.y], nm_tu, nm_tv), __uint_as_float(nr.z), dPdu, dPdv, ray.d, normal);
+                                }
+                            }
+                        }
+                    }
+                }
                 const uint32_t mtype = mat_bits >> 29;
                 const float4 mrec = mats16[mat_bits & RT_MAT_INDEX_MASK];
                 f3 albedo = mk3(mrec.x, mrec.y, mrec.z);
@@ -905,6 +951,8 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                         if (EXT >= 2 && mtype == RT_MAT_LAMBERTIAN_NOISE) albedo = noise_value(p.scene.perlin, albedo, mparam, hit_p);
                         if (EXT >= 2 && mtype == RT_MAT_LAMBERTIAN_IMAGE) {   // (u, v) three ways, then the world's image or — §25 — the material's entry of the texture table
                             float tu, tv;
+                            if (NMAP && nm_uv) { tu = nm_tu; tv = nm_tv; }   // §28: the map's own (u, v)
+                            else
                             if ((uint32_t)rec_code >= p.scene.sphere_codes) {   // on a quad: the planar coordinates of the hit
                                 const uint32_t qi = (uint32_t)rec_code - p.scene.sphere_codes;
                                 const float4* qd = quads + qi * 4u;

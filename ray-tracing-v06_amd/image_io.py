@@ -399,3 +399,24 @@ def sky_environment(width, height, sun_dir=(0.4, 0.6, -0.7), sun_radiance=(60.0,
     img = img + (ny >= 0.0)[..., None] * glow[..., None] * sun * 0.02
     img = np.where((cos_sun >= np.cos(np.radians(sun_radius_deg)))[..., None], sun, img)
     return np.ascontiguousarray(img, dtype=np.float32)
+
+
+def height_to_normal_map(height, scale=1.0, wrap="repeat"):
+    """A grey height field (H, W), row 0 at the top, as a tangent-space normal map (H, W, 3) uint8 for Scene.set_normal_map (OpenGL convention:
+    red = +u, the columns' direction; green = +v, towards row 0; blue = along the surface normal).  Central differences per texel, the neighbours wrapped
+    ("repeat") or clamped ("clamp") as the image's wrap mode will have them: n = normalize(-scale dh/du, -scale dh/dv, 1), byte = 128 + round(127 n), which
+    the rule decodes as (byte - 128) / 127.  A constant field gives the flat map (128, 128, 255)."""
+    h = np.asarray(height, dtype=np.float64)
+    if h.ndim != 2 or h.size == 0:
+        raise ValueError("height_to_normal_map: the height field must have shape (H, W)")
+    if wrap not in ("repeat", "clamp"):
+        raise ValueError("height_to_normal_map: wrap is \"repeat\" or \"clamp\"")
+    if wrap == "repeat":
+        right, left, up, down = np.roll(h, -1, axis=1), np.roll(h, 1, axis=1), np.roll(h, 1, axis=0), np.roll(h, -1, axis=0)
+    else:
+        p = np.pad(h, 1, mode="edge")
+        right, left, up, down = p[1:-1, 2:], p[1:-1, :-2], p[:-2, 1:-1], p[2:, 1:-1]
+    dhdu, dhdv = (right - left) * 0.5, (up - down) * 0.5   # v grows towards row 0
+    n = np.stack([-float(scale) * dhdu, -float(scale) * dhdv, np.ones_like(h)], axis=-1)
+    n = n / np.sqrt((n * n).sum(axis=-1, keepdims=True))
+    return np.ascontiguousarray(np.clip(128.0 + np.rint(127.0 * n), 0.0, 255.0).astype(np.uint8))

@@ -170,9 +170,12 @@ def load_obj_materials(path):
 
 def load_mtl(path):
     """`newmtl`, `Kd` and `map_Kd` of a Wavefront MTL file: {name: {"Kd": (r, g, b) | None, "map_Kd": path | None}} in the file's order; the image's name is
-    resolved beside the file, options in front of it (-s, -o, ...) are skipped.  Nothing else of MTL is read."""
+    resolved beside the file, options in front of it (-s, -o, ...) are skipped.  `norm`, `map_Bump`, `map_bump` and `bump` name the material's normal map
+    (the file is taken as a tangent-space normal map, OpenGL convention, green = +v): "normal_map": path | None and "normal_strength": the `-bm X`
+    in front of the name, 1.0 without one; the last such line of a material counts.  Nothing else of MTL is read."""
     import os
     out, current = {}, None
+    beside = lambda name: os.path.join(os.path.dirname(os.path.abspath(path)), *name.replace("\\", "/").split("/"))
     with open(path, "r", encoding="utf-8", errors="replace") as f:
         for lineno, line in enumerate(f, 1):
             parts = line.split("#", 1)[0].split()
@@ -182,7 +185,21 @@ def load_mtl(path):
             if parts[0] == "newmtl":
                 if len(parts) < 2:
                     raise ValueError(f"{where}: newmtl needs a name")
-                current = out.setdefault(parts[1], {"Kd": None, "map_Kd": None})
+                current = out.setdefault(parts[1], {"Kd": None, "map_Kd": None, "normal_map": None, "normal_strength": 1.0})
+            elif parts[0] in ("norm", "map_Bump", "map_bump", "bump"):
+                if current is None:
+                    raise ValueError(f"{where}: {parts[0]} before any newmtl")
+                if len(parts) < 2:
+                    raise ValueError(f"{where}: {parts[0]} needs a file name")
+                strength = 1.0
+                if "-bm" in parts[1:-1]:
+                    at = parts.index("-bm", 1)
+                    if at + 1 >= len(parts) - 1:
+                        raise ValueError(f"{where}: -bm needs a value in front of the file name")
+                    strength = float(parts[at + 1])
+                    if not (np.isfinite(strength) and strength >= 0.0):
+                        raise ValueError(f"{where}: -bm must be finite and >= 0")
+                current["normal_map"], current["normal_strength"] = beside(parts[-1]), strength
             elif parts[0] in ("Kd", "map_Kd"):
                 if current is None:
                     raise ValueError(f"{where}: {parts[0]} before any newmtl")

@@ -1,0 +1,200 @@
+"""The maps, cases and worlds of the normal-map tests — test infrastructure only.
+
+table(): six small maps under the four mode pairs.  random_cases() / aimed_cases(): inputs of rt_normal_map_batch, shared by the CPU test (host batch against
+the numpy twin) and the GPU test (device probe against the host batch).  Every world is built through the product's host vocabulary, which needs no device.
+"""
+import numpy as np
+
+import _nmap_twin as NT
+import _tex_worlds as XW
+
+F = np.float32
+FLAT_A, FLAT_B, ZERO_Z = 2, 3, 5   # entries of table() that are flat maps (x = y = 0 after the decode)
+
+
+def table():
+    """[(image, wrap, filter)] as _tex_twin.lookup and api.texture_table take it: two random maps, two flat ones (bytes 128, 128, z), one whose blue lies below
+    128, one 2 x 1 map of (128, 128, 128) and (129, 129, 128): no z at all"""
+    low_blue = XW.image(4, 4, seed=11)
+    low_blue[:, :, 2] //= 2
+    return [(XW.image(5, 3, seed=5), 0, 0), (XW.image(8, 4, seed=5), 1, 1), (XW.constant(2, 2, (128, 128, 255)), 0, 1), (XW.constant(3, 2, (128, 128, 40)), 1, 0),
+            (low_blue, 1, 1), (np.array([[[128, 128, 128], [129, 129, 128]]], np.uint8), 0, 0)]
+
+
+def api_table(tab):
+    return [(img, XW.MODE_NAMES[(w, f)][0], XW.MODE_NAMES[(w, f)][1]) for img, w, f in tab]
+
+
+def _unit(x):
+    x = np.asarray(x, np.float64)
+    return (x / np.linalg.norm(x, axis=-1, keepdims=True)).astype(F)
+
+
+def random_cases(n=4096, seed=28):
+    """n cases over every surface kind, entry and a handful of strengths: a dict of the batch's arguments"""
+    rng = np.random.default_rng(seed)
+    surface = rng.integers(0, 4, n).astype(np.uint32)
+    normal = _unit(rng.standard_normal((n, 3)))
+    a = (rng.standard_normal((n, 3)) * 2).astype(F)
+    b = (rng.standard_normal((n, 3)) * 2).astype(F)
+    a[surface == NT.SPHERE] = normal[surface == NT.SPHERE]
+    planar = (surface == NT.PLANAR) | (surface == NT.TRI_UV)   # a record's u, v and the normal of their plane, towards either side
+    flat = _unit(np.cross(a[planar].astype(np.float64), b[planar].astype(np.float64)))
+    normal[planar] = flat * np.where(rng.random(int(planar.sum())) < 0.5, -1, 1).astype(F)[:, None]
+    tri_uv = (rng.random((n, 6)) * 3 - 1).astype(F)
+    ray_d = (rng.standard_normal((n, 3)) * 3).astype(F)
+    u, v = (rng.random(n) * 3 - 1).astype(F), (rng.random(n) * 3 - 1).astype(F)
+    index = rng.integers(0, 6, n).astype(np.uint32)
+    strength = rng.choice(np.array([0.0, 0.25, 1.0, 2.0, 50.0], F), n).astype(F)
+    return dict(surface=surface, a=a, b=b, tri_uv=tri_uv, normal=normal, ray_d=ray_d, u=u, v=v, index=index, strength=strength)
+
+
+AIMED = ["north pole", "south pole", "det == 0", "NaN coordinates", "mirrored UVs", "upright UVs", "strength 0", "grazing strength", "blue below 128",
+         "inside a sphere", "flat record underneath", "no length", "flat map", "flat map, repeat"]
+
+
+def aimed_cases():
+    """one case per name of AIMED, in that order, and the path each must leave the rule by"""
+    z = (0.0, 0.0, 1.0)
+    tilt = 0.4   # u = 0.4 on entry 0 (5 x 3): a random texel
+    inside_n = _unit([0.3, 0.5, 0.8])
+    tri_u, tri_v = (2.0, 0.0, 0.0), (0.5, 1.5, 0.0)   # a triangle in z = 0, flat normal +z
+    rows = [
+        # surface, a, b, tri_uv, normal, ray_d, u, v, index, strength, path
+        (NT.SPHERE, (0, 1, 0), (0, 0, 0), None, (0, 1, 0), (0.1, -1, 0.2), 0.5, 1.0, 0, 1.0, NT.NO_TANGENT),
+        (NT.SPHERE, (0, -1, 0), (0, 0, 0), None, (0, -1, 0), (0.1, 1, 0.2), 0.5, 0.0, 0, 1.0, NT.NO_TANGENT),
+        (NT.TRI_UV, tri_u, tri_v, (0, 0, 1, 1, 2, 2), z, (0.1, 0.2, -1), tilt, 0.3, 0, 1.0, NT.NO_FRAME),
+        (NT.TRI_UV, tri_u, tri_v, (0, 0, np.nan, 0, 0, 1), z, (0.1, 0.2, -1), tilt, 0.3, 0, 1.0, NT.NO_FRAME),
+        (NT.TRI_UV, tri_u, tri_v, (1, 0, 0, 0, 1, 1), z, (0.1, 0.2, -1), 0.1, 0.1, 2, 1.0, None),     # filled in below: a gentle tilt on a map of its own
+        (NT.TRI_UV, tri_u, tri_v, (0, 0, 1, 0, 0, 1), z, (0.1, 0.2, -1), 0.1, 0.1, 2, 1.0, None),
+        (NT.PLANAR, tri_u, tri_v, None, z, (0.1, 0.2, -1), tilt, 0.3, 0, 0.0, NT.FLAT),
+        (NT.PLANAR, (1, 0, 0), (0, 1, 0), None, z, (0.3, 0, -1), 0.9, 0.5, 5, 1e4, NT.FACING),
+        (NT.PLANAR, (1, 0, 0), (0, 1, 0), None, z, (0.0, 0.0, -1), 0.3, 0.3, 4, 1.0, NT.FACING),
+        (NT.SPHERE, tuple(inside_n), (0, 0, 0), None, tuple(inside_n), tuple(inside_n * F(2)), 0.3, 0.6, 6, 1.0, NT.REPLACED),
+        (NT.PLANAR, tri_u, tri_v, None, z, (0.1, 0.2, -1), 0.3, 0.6, 6, 1.0, NT.REPLACED),
+        (NT.PLANAR, (1, 0, 0), (0, 1, 0), None, z, (0.1, 0.2, -1), 0.9, 0.5, 5, 1e-30, NT.NO_LENGTH),
+        (NT.PLANAR, tri_u, tri_v, None, z, (0.1, 0.2, -1), 0.37, 0.81, FLAT_A, 7.0, NT.FLAT),
+        (NT.SPHERE, tuple(inside_n), (0, 0, 0), None, tuple(inside_n), (0.1, -1, 0.2), -3.3, 4.7, FLAT_B, 0.5, NT.FLAT),
+    ]
+    gentle = (NT.encode(_unit([0.2, 0.1, 1.0])).reshape(1, 1, 3), 0, 0)   # entry 6: one texel, tilted a little towards +u and +v
+    tab = table() + [gentle]
+    rows[4] = rows[4][:8] + (6, 1.0, NT.REPLACED)
+    rows[5] = rows[5][:8] + (6, 1.0, NT.REPLACED)
+    cols = list(zip(*rows))
+    tri_uv = np.array([(0,) * 6 if t is None else t for t in cols[3]], F)
+    cases = dict(surface=np.array(cols[0], np.uint32), a=np.array(cols[1], F), b=np.array(cols[2], F), tri_uv=tri_uv, normal=np.array(cols[4], F),
+                 ray_d=np.array(cols[5], F), u=np.array(cols[6], F), v=np.array(cols[7], F), index=np.array(cols[8], np.uint32), strength=np.array(cols[9], F))
+    assert len(rows) == len(AIMED)
+    return tab, cases, np.array(cols[10], np.uint32)
+
+
+def run_cases(fn, tab, cases):
+    """fn = api.normal_map_batch, api.probe_normal_map or the twin's case()"""
+    c = cases
+    return fn(tab, c["surface"], c["a"], c["b"], c["tri_uv"], c["normal"], c["ray_d"], c["u"], c["v"], c["index"], c["strength"])
+
+
+# ---- the test room and the kernel forms ------------------------------------------------------------------------------------------------------------------------
+import functools  # noqa: E402
+
+import _env_tree_twin as VT  # noqa: E402
+import _env_twin as ET  # noqa: E402
+import _env_worlds as EW  # noqa: E402
+import _tri_worlds as TW  # noqa: E402
+from _common import as_oracle_camera, as_oracle_world, pkg  # noqa: E402
+
+SEED = EW.SEED
+W, H, SPP, DEPTH = EW.W, EW.H, EW.SPP, EW.DEPTH   # 24 x 16 at 8 spp and depth 6
+ENV_TREE = 48
+BACKGROUND = (0.55, 0.65, 0.85)
+
+# The suite's statement of which NMAP instantiations of render_kernel_stream exist: one (world, exact, ext, big, wide) key per RT_KERNEL_NORMAL_MAP(...) line of
+# csrc/rt_device.hip and, the same eight once more, per RT_KERNEL_NORMAL_MAP_ENV_TREE(...) line, each with _tri_worlds' recipe (kernel variant, environment) that
+# makes a renderer with a normal-map table resolve to it.  tests/test_normal_maps_cpu.py holds the list against the source; tests/test_gpu_normal_maps.py renders
+# every key, plain and in mode 48, and compares it with the twin.
+FORMS = {f: TW.FORMS[f] for f in [(TW.BVH, 0, 2, 0, 0), (TW.BVH, 1, 2, 0, 0), (TW.BVH, 0, 2, 1, 0), (TW.BVH, 1, 2, 1, 0), (TW.BVH, 0, 2, 1, 1), (TW.BVH, 1, 2, 1, 1),
+                                  (TW.LIST, 1, 2, 0, 0), (TW.LIST, 1, 2, 1, 1)]}
+
+
+def bumps():
+    """a height field of a few bumps as a normal map, 8 x 8, for repeat / bilinear"""
+    pkg()
+    from ray_tracing_v06_amd import image_io
+    y, x = np.mgrid[0:8, 0:8]
+    return image_io.height_to_normal_map(np.sin(x * np.pi / 2) * np.cos(y * np.pi / 4) + 0.3 * np.sin(x * y * 0.7), 1.2, wrap="repeat")
+
+
+def tilts():
+    """5 x 3 random unit vectors of the upper hemisphere, leaning up to about 50 degrees, for clamp / nearest"""
+    rng = np.random.default_rng(28)
+    v = np.concatenate([rng.random((3, 5, 2)) * 2.4 - 1.2, np.ones((3, 5, 1))], axis=2)
+    return NT.encode(v / np.linalg.norm(v, axis=2, keepdims=True))
+
+
+def room_table(flat=False):
+    """the room's texture table as the twin takes it: entry 0 the mesh's colours, entries 1 and 2 the maps (flat: two flat maps of those sizes and modes)"""
+    one, two = (XW.constant(8, 8, (128, 128, 255)), XW.constant(5, 3, (128, 128, 90))) if flat else (bumps(), tilts())
+    return [(XW.image(8, 4, seed=28), 0, 0), (one, 1, 1), (two, 0, 0)]
+
+
+def room(p, env=False, as_list=False, flat=False, strength=None, maps=True, smooth=True):
+    """A checker floor, a Lambertian sphere and a fuzzy-metal sphere, a parallelogram wall, an image-textured uv_sphere(8, 4) mesh with its vertex normals and
+    coordinates, and a quad light — under a constant background or, env, the sky map —; maps: the two spheres, the wall and the mesh carry a normal map each
+    (strength: one value for all four instead of four different ones).  No glass, medium or noise material: the whole-sample twin follows every sample."""
+    tab = room_table(flat)
+    s = p.Scene()
+    s.MakeQuad((-15, 0, -15), (40, 0, 0), (0, 0, 40), s.LambertianTexture((0.2, 0.3, 0.1), (0.9, 0.9, 0.9), 0.5))
+    lam, metal, wall = s.Lambertian((0.7, 0.3, 0.3)), s.Metal((0.9, 0.7, 0.4), 0.3), s.Lambertian((0.4, 0.5, 0.7))
+    s.MakeSphere((2.2, 1.0, 5.5), 1.0, lam)
+    s.MakeSphere((8, 1.2, 6), 1.2, metal)
+    s.MakeQuad((1.0, 0.0, 9.5), (8.0, 0, 0.5), (0, 4.0, 0), wall)
+    s.set_image(tab[0][0])
+    assert s.add_image(tab[1][0], "repeat", "bilinear") == 1 and s.add_image(tab[2][0], "clamp", "nearest") == 2
+    mesh = s.ImageTexture(0)
+    v, f, n, uv = TW.mesh_io().uv_sphere(8, 4)
+    s.MakeMesh(v, f, mesh, 1.5, 20.0, (5, 1.6, 6.5), normals=n if smooth else None, uvs=uv * F(2.0) - F(0.25))
+    s.MakeQuad((3.5, 6, 3.5), (3, 0, 0), (0, 0, 3), s.DiffuseLight((8, 8, 8)))
+    if maps:
+        for k, (m, image) in enumerate(((lam, 1), (metal, 2), (wall, 2), (mesh, 1))):
+            s.set_normal_map(m, image, (1.0, 0.7, 2.0, 1.5)[k] if strength is None else strength)
+    if env:
+        s.set_environment(EW.sky_map(), rotate_y=EW.SKY_U0_DEGREES)
+    else:
+        s.set_background(BACKGROUND)
+    s.MakeHittableList() if as_list else s.BuildBVH_SAH()
+    return s
+
+
+def camera(p, w=W, h=H):
+    return EW.camera(p, w, h)
+
+
+class Run:
+    """the room and the whole-sample twin's samples of it, plain (a constant background) or in mode 48 (the sky map and the light tree)"""
+
+    def __init__(self, env, as_list=False, smooth=True, spp=SPP, first_sample=0, w=W, h=H):
+        p = pkg()
+        self.scene = room(p, env=env, as_list=as_list, smooth=smooth)
+        self.table = room_table()
+        self.world = as_oracle_world(self.scene.getWorldPtr())
+        vn, uv, nmaps = self.scene.vertex_normals(), self.scene.texture_coords(), self.scene.normal_maps()
+        cam = as_oracle_camera(camera(p, w, h))
+        if env:
+            image, u0 = self.scene.environment()
+            sky, light, tree = ET.sky_environment(image, u0), (p.api.environment_distribution(image), u0), VT.table_of(self.world)
+        else:
+            colour = np.array(BACKGROUND, F)
+            sky, light, tree = (lambda d: np.broadcast_to(colour, (len(d), 3))), None, None
+        self.info = {}
+        args = (self.world, cam, w, h, spp, DEPTH, SEED, sky, vn if smooth else None, uv)
+        self.samples, self.followed = NT.frame_samples(*args, nmaps, self.table, light=light, tree=tree, first_sample=first_sample, info=self.info)
+        self.unmapped, _ = NT.frame_samples(*args, None, self.table, light=light, tree=tree, first_sample=first_sample)
+        self.sums = VT.in_order_sums(self.samples)
+        self.frame = VT.resolve(self.sums, spp)
+        for a in (self.samples, self.followed, self.unmapped, self.sums, self.frame):
+            a.setflags(write=False)
+
+
+@functools.lru_cache(maxsize=None)
+def run(env, as_list=False, smooth=True):
+    return Run(env, as_list, smooth)
