@@ -998,6 +998,9 @@ int rt_probe_boxpair_filtered(int device, size_t n, const float* boxes, const fl
  * boxes: same layout as above -> out n*8 int32: [regular, could not certify, hit_left, hit_right, left_dist > right_dist,
  * exact hit_left, exact hit_right, exact left_dist > right_dist].                                                                       */
 int rt_probe_boxpair_certified(int device, size_t n, const float* boxes, const float* rays, const float* max_dist, int32_t* out);
+/* The same pair as the hot loop takes it since E23: a far parameter is fma(plane, RN(1/d), RN(-o * RN(1/d))), and both `tmin <= tmax` and the sign
+ * of tmax are certified under a margin with a per-ray additive term (rt_fastdiv.hpp, CERTIFIED FAR PLANES, ONE FMA EACH).  Same layout, same out. */
+int rt_probe_boxpair_certified_fma(int device, size_t n, const float* boxes, const float* rays, const float* max_dist, int32_t* out);
 /* Exhaustive self-test: for each of n_den divisor significands starting at first_den (0 .. 2^23-1) and
  * ALL 2^23 numerator significands, compare the 5-instruction quotient with IEEE n/d bit for bit.
  * num_exp / den_exp are the unbiased exponents given to numerator and divisor.  Returns the number of

@@ -1107,6 +1107,15 @@ def probe_boxpair_certified(boxes, rays, max_dist, device=0):
     return out
 
 
+def probe_boxpair_certified_fma(boxes, rays, max_dist, device=0):
+    """rt_probe_boxpair_certified_fma: the same pair with the far parameters as one fma each, as the hot loop takes it, (n, 8) int32."""
+    n = len(boxes)
+    out = np.zeros((n, 8), np.int32)
+    check(lib().rt_probe_boxpair_certified_fma(device, n, np.ascontiguousarray(boxes, np.float32), np.ascontiguousarray(rays, np.float32),
+                                               np.ascontiguousarray(max_dist, np.float32), out))
+    return out
+
+
 def probe_boxpair_filtered(boxes, rays, max_dist, device=0):
     n = len(boxes)
     out = np.zeros((n, 8), np.int32)

@@ -147,6 +147,53 @@ __device__ __forceinline__ bool far_pair_uncertain(float tmin_l, float far_l, fl
     return gap <= scale * RT_FAR_EPS;
 }
 
+// CERTIFIED FAR PLANES, ONE FMA EACH (the default hot loop since E23): the subtraction of the product form goes too.  Per ray and axis, once per trace,
+// r = RN(1/d) and c = RN(-o * r); per far plane f one instruction, t' = RN(f * r + c) (an explicit fma: one rounding).  The reference's q = RN(RN(f - o) / d)
+// rounds the offset first, which t' does not reproduce — the far parameters feed decisions only, so it need not.  With u = 2^-24, T = (f - o) / d, and every
+// rounding written as a factor (1 + e), |e| <= u (no under- or overflow, see below):
+//     q  = T (1 + e4)(1 + e5)                                              |q - T|  <= (2u + u^2) |T|
+//     t' = (T (1 + e1) - o r e2)(1 + e3),  |o r| <= |c| / (1 - u)          |t' - T| <= (2u + u^2) |T| + u (1 + u) / (1 - u) |c|
+//  => |t' - q| <= (4u + 2u^2) |T| + 1.0000002 u |c|, and with |T| <= (|t'| + 1.0000002 u |c|) / (1 - 2u - u^2):
+//     |t' - q| <= 4.01 u |t'| + 1.01 u |c|.
+// The first term is relative to the parameter itself and survives min3 as it does in the product form (x -> x -+ 4.01 u |x| is monotone).  The second is the
+// price of the cancellation in f r + c: it is relative to |o / d|, not to t', and does not survive a minimum — it enters once per ray as S = max3 |c|:
+//     |min3(t') - min3(q)| <= 4.01 u |min3(t')| + 1.01 u S  =: E.
+// Under- and overflow: |c| is 0 (o == 0, where t' is the plain product) or within [2^-100, 2^80]; |f r| likewise; denormals are kept, and f r + c may cancel
+// to as little as the rounding error of o * r, which is a float.  A t' that rounds in the subnormal range errs by <= 2^-150 <= 2^-50 u |c| more: inside 1.01.
+// The sign.  The product form's sign was the quotient's; this form's is too, with ONE exception.  The fma sees X = (f - o) r + delta exactly, delta the rounding
+// error of o * r: |delta| <= 2^(E-24) for 2^E <= |o r| < 2^(E+1).  Two different floats f, o are further apart than u |o| — at least an ulp of o when f is of
+// o's binade or above, at least |o| when it is zero or of the other sign, and the float just below a power of two o is u |o| away exactly, but then o * r is
+// exact and delta = 0 — so |(f - o) r| > 2^-24 2^E >= |delta|: X is not zero and has the sign of (f - o) / d; X is a multiple of 2^-126, so t' = RN(X) keeps it.
+// With f == o the quotient is 0 and t' = delta, of either sign, |delta| <= 1.01 u |c|.  (o == 0: c = 0 and t' = RN(f r), sign-exact, zero with f.)  Hence
+//     min3(t') <= 0  =>  min3(q) <= 0;          min3(t') > 0 and min3(q) <= 0  =>  some f == o and 0 < min3(t') <= 1.01 u S.
+// Decisions.  `tmin <= tmax`: if |min3(t') - tmin| > E the two sides order as the exact ones do.  `tmax > 0`: certain unless 0 <= min3(t') <= 1.01 u S — one
+// side of zero only, which matters: a ray that leaves the ground of the book scenes has its origin within a rounding of the plane y = 0, and with |t'| <= margin
+// on both sides nearly every such trace redid the ground's box (1.1 % of the steps of the headline frame instead of 0.08 %, EXPERIMENTS.md E23).  The margin
+// keeps the safety factor the product form has (8 u over 3.1 u, 2.58): RT_FAR_EPS_FMA = 10.5 u over 4.01 u, RT_FAR_ABS_EPS = 2.625 u over 1.01 u (2.6 each):
+//     uncertain  <=>  |t' - tmin| - 10.5 u |t'| <= s_eps  or  0 <= t' <= s_eps,       s_eps = RN(S * 2.625 u), per ray, at begin-trace      (t' = min3(t'), per box)
+// — the relative term per box, on the gap's side.  The roundings of the certificate's own arithmetic (the gap's subtraction, its fma, s_eps: a relative u each)
+// vanish in the factor.  All of it is ONE unsigned comparison: the gap is clamped to [0, 1] (free, an output modifier; s_eps >= 1 would only redo always), and
+// among non-negative floats the bit patterns order like the values, while a far parameter with its sign bit set — a certain miss, whatever its gap — is larger
+// than any of them.  So min_u32 of the two gaps and the two far parameters against the bits of s_eps: seven instructions for the pair, one more than the
+// product form's.  s_eps is per ray; a near-axis-parallel ray that starts far from the world (|o / d| >> t) has a wide margin and redoes more often, but
+// certifies nothing false.  A lane that cannot certify makes the wave redo the far planes of the visit with the exact quotients, as before; that path
+// reproduces RN(f - o).
+// Restated in numpy float32 by tests/test_far_plane_fma_bound.py; on the GPU, next to aabb::intersects, by rt_probe_boxpair_certified_fma.
+#define RT_FAR_EPS_FMA 6.2584877014160156e-07f   /* 10.5 u = 21 * 2^-25 */
+#define RT_FAR_ABS_EPS 1.5646219253540039e-07f   /* 2.625 u = 21 * 2^-27 */
+// per ray, at begin-trace: c, and the additive term of the margin
+__device__ __forceinline__ f3 slab_fma_offset(const Ray& ray, f3 inv_d) { return mk3(-ray.o.x * inv_d.x, -ray.o.y * inv_d.y, -ray.o.z * inv_d.z); }
+__device__ __forceinline__ float slab_fma_margin(f3 c) { return fmaxf(fmaxf(fabsf(c.x), fabsf(c.y)), fabsf(c.z)) * RT_FAR_ABS_EPS; }
+__device__ __forceinline__ float slab_far_fma(float fx, float fy, float fz, f3 inv_d, f3 c) {
+    return fminf(fminf(__builtin_fmaf(fx, inv_d.x, c.x), __builtin_fmaf(fy, inv_d.y, c.y)), __builtin_fmaf(fz, inv_d.z, c.z));
+}
+// true when the `tmin <= tmax` and `tmax > 0` decisions taken with the FMA forms (far_l, far_r) are NOT all certain (fmed3(x, 0, 1) becomes the fma's clamp)
+__device__ __forceinline__ bool far_pair_uncertain_fma(float tmin_l, float far_l, float tmin_r, float far_r, float s_eps) {
+    const float gap_l = __builtin_amdgcn_fmed3f(__builtin_fmaf(-RT_FAR_EPS_FMA, fabsf(far_l), fabsf(far_l - tmin_l)), 0.0f, 1.0f);
+    const float gap_r = __builtin_amdgcn_fmed3f(__builtin_fmaf(-RT_FAR_EPS_FMA, fabsf(far_r), fabsf(far_r - tmin_r)), 0.0f, 1.0f);
+    return min(min(min(__float_as_uint(gap_l), __float_as_uint(gap_r)), __float_as_uint(far_l)), __float_as_uint(far_r)) <= __float_as_uint(s_eps);
+}
+
 // The root box of a trace (BVH.cu:59-60) decides one thing — is the world entered at all, against a fresh rec.distance = _MISS_DIST — so ALL six of its
 // plane parameters can be products: `tmin <= tmax` is certified as above (both sides are approximate now: twice the margin), `tmin < _MISS_DIST` holds
 // for every parameter of the class, `tmax > 0` is sign-exact; a lane that cannot certify (a ray that grazes the world's bounds) takes the exact test.

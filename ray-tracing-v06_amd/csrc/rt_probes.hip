@@ -898,6 +898,32 @@ __global__ void probe_boxpair_certified_kernel(size_t n, const float* boxes, con
     boxpair_verbatim(c, maxd[i]);
 }
 
+// The same pair with the far parameters as one fma each (rt_fastdiv.hpp: CERTIFIED FAR PLANES, ONE FMA EACH): the per-ray offset and margin, the far
+// parameters and the certificate come from the helpers the hot loop calls; the redo and the decisions are written as above.
+__global__ void probe_boxpair_certified_fma_kernel(size_t n, const float* boxes, const float* rays, const float* maxd, int32_t* out) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const BoxPairCase c = boxpair_case(i, boxes, rays, out);
+    if (!c.regular) return;
+    const Ray& r = c.r;
+    const float* b = c.b;
+    const f3 inv_d = mk3(rcp_exact_regular(r.d.x), rcp_exact_regular(r.d.y), rcp_exact_regular(r.d.z));
+    const f3 inv_lo = mk3(rcp_low_word(r.d.x, inv_d.x), rcp_low_word(r.d.y, inv_d.y), rcp_low_word(r.d.z, inv_d.z));
+    const f3 far_c = slab_fma_offset(r, inv_d);
+    const float s_eps = slab_fma_margin(far_c);
+    const bool sx = r.d.x < 0, sy = r.d.y < 0, sz = r.d.z < 0;
+    const float lnx = sx ? b[3] : b[0], lny = sy ? b[4] : b[1], lnz = sz ? b[5] : b[2], lfx = sx ? b[0] : b[3], lfy = sy ? b[1] : b[4], lfz = sz ? b[2] : b[5];
+    const float rnx = sx ? b[9] : b[6], rny = sy ? b[10] : b[7], rnz = sz ? b[11] : b[8], rfx = sx ? b[6] : b[9], rfy = sy ? b[7] : b[10], rfz = sz ? b[8] : b[11];
+    const float tl = slab_near_exact(lnx, lny, lnz, r, inv_d, inv_lo), tr = slab_near_exact(rnx, rny, rnz, r, inv_d, inv_lo);
+    float far_l = slab_far_fma(lfx, lfy, lfz, inv_d, far_c), far_r = slab_far_fma(rfx, rfy, rfz, inv_d, far_c);
+    const bool unc = far_pair_uncertain_fma(tl, far_l, tr, far_r, s_eps);
+    if (unc) { far_l = slab_far_exact(lfx, lfy, lfz, r, inv_d, inv_lo); far_r = slab_far_exact(rfx, rfy, rfz, r, inv_d, inv_lo); }
+    const float rec_t = maxd[i];
+    const bool hl = tl <= far_l && tl < rec_t && far_l > 0, hr = tr <= far_r && tr < rec_t && far_r > 0;
+    c.o[1] = unc; c.o[2] = hl; c.o[3] = hr; c.o[4] = hr && (!hl || tl > tr);
+    boxpair_verbatim(c, maxd[i]);
+}
+
 static int boxpair_probe(const char* fn, void (*kernel)(size_t, const float*, const float*, const float*, int32_t*), int device, size_t n,
                          const float* boxes, const float* rays, const float* max_dist, int32_t* out) {
     if (!boxes || !rays || !max_dist || !out) return rt_fail(RT_ERR_INVALID, "%s: null argument", fn);
@@ -910,6 +936,9 @@ static int boxpair_probe(const char* fn, void (*kernel)(size_t, const float*, co
 }
 extern "C" int rt_probe_boxpair_certified(int device, size_t n, const float* boxes, const float* rays, const float* max_dist, int32_t* out) {
     return boxpair_probe("rt_probe_boxpair_certified", probe_boxpair_certified_kernel, device, n, boxes, rays, max_dist, out);
+}
+extern "C" int rt_probe_boxpair_certified_fma(int device, size_t n, const float* boxes, const float* rays, const float* max_dist, int32_t* out) {
+    return boxpair_probe("rt_probe_boxpair_certified_fma", probe_boxpair_certified_fma_kernel, device, n, boxes, rays, max_dist, out);
 }
 extern "C" int rt_probe_boxpair_filtered(int device, size_t n, const float* boxes, const float* rays, const float* max_dist, int32_t* out) {
     return boxpair_probe("rt_probe_boxpair_filtered", probe_boxpair_filtered_kernel, device, n, boxes, rays, max_dist, out);

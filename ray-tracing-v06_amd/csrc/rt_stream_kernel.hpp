@@ -269,6 +269,9 @@ __device__ __forceinline__ f3 texture_table_value(const uint4* tt, uint32_t imag
 //      sampled as the diffuse hit it is — its albedo is looked up behind the direction, as ever.
 template <bool EXACT, bool FILTER, int BLOCK, int WORLD = RT_WORLD_BVH, int EXT = 0, bool BIG = false, bool WIDE = BIG, bool TOL = false, bool NEE = false, bool TRI = false,
           bool LTREE = false, bool ENVL = false, bool NMAP = false>
+// (the second launch bound is hipcc's minimum of waves per SIMD — 6 for 768 threads, what two workgroups per CU are, and all the LDS admits: the register budget is
+//  80, not the 64 of a full SIMD.  The default instantiation took 64 while it needed no more and takes 68 since E23, with no scratch; the occupancy the compiler
+//  reports for it, 8 and now 7, is what its register count would admit, not what the launch gets.)
 __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(StreamParams p) {
     static_assert(!NMAP || (EXT == 2 && TRI), "normal maps: one family of the kernels that read the texture table, plain and with mode 48");
     static_assert(!NEE || (EXT >= 1 && WORLD != RT_WORLD_BVH_QUEUE), "light sampling: worlds with quads, walked by the stack or as a list");
@@ -327,6 +330,8 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
     ray.o = mk3(0.0f); ray.d = mk3(0.0f); ray.time = 0.0f;
     f3 inv_d = mk3(0.0f);   // RN(1/d) of a regular ray (EXACT == false)
     f3 inv_lo = mk3(0.0f);  // its low word: inv_d + inv_lo ~= 1/d to 47 bits (fast_div_exact4, FAST_BVH only)
+    f3 far_c = mk3(0.0f);   // RN(-o * inv_d): a far plane parameter is fma(plane, inv_d, far_c) (slab_far_fma, FAST_BVH only)
+    float far_s_eps = 0.0f; // the per-ray term of that form's certificate margin (slab_fma_margin)
     bool regular = false;
     f3 atten = mk3(0.0f);
     f3 accum_rad = mk3(0.0f);  // EXT only: radiance emitted along the path so far
@@ -342,6 +347,9 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
     // FAST_BVH: the default kernel (variant 3).  Inner references of rays outside the fast-division class are marked
     // with K::IRR (an LDS-resident tree has < 2^14 inner nodes) so that the hot loop needs no per-lane branch.
     constexpr bool FAST_BVH = !EXACT && !FILTER && WORLD == RT_WORLD_BVH;
+    // The certified far planes as one fma each (E23): the kernels of the reference's feature set.  The form keeps four more registers alive per ray, and every
+    // EXT kernel that was at its 80 registers answered them with scratch (EXPERIMENTS.md E23), so a quad-free world on an EXT kernel keeps the product form.
+    constexpr bool FAR_FMA = FAST_BVH && !TOL && EXT == 0;
     bool irr_pending = false;         // wave-uniform: some lane is traversing with a ray outside the class
     uint32_t depth = 0;
     uint32_t out_idx = 0;   // == the sample index n: the sample buffer is laid out in index order
@@ -410,14 +418,27 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                             hl = slab_near_far_regular(nd.lnx, nd.lny, nd.lnz, nd.lfx, nd.lfy, nd.lfz, ray, inv_d, inv_lo, rec_t, tl);
                             hr = slab_near_far_regular(nd.rnx, nd.rny, nd.rnz, nd.rfx, nd.rfy, nd.rfz, ray, inv_d, inv_lo, rec_t, tr);
                         } else {
-                            // near parameters: exact quotients (tl, tr are compared with each other and with rec.distance); far parameters: products,
-                            // with the `tmin <= tmax` decisions certified (rt_fastdiv.hpp: CERTIFIED FAR PLANES) — or, rarely and for the whole wave,
-                            // redone exactly from a second read of the node
+                            // near parameters: exact quotients (tl, tr are compared with each other and with rec.distance); far parameters: one fma each
+                            // (FAR_FMA) or products, with the `tmin <= tmax` decisions — and, of the fma form, the sign of tmax — certified (rt_fastdiv.hpp:
+                            // CERTIFIED FAR PLANES) — or, rarely and for the whole wave, redone exactly from a second read of the node
                             tl = slab_near_exact(nd.lnx, nd.lny, nd.lnz, ray, inv_d, inv_lo);
                             tr = slab_near_exact(nd.rnx, nd.rny, nd.rnz, ray, inv_d, inv_lo);
-                            float far_l = slab_far_product(nd.lfx, nd.lfy, nd.lfz, ray, inv_d);
-                            float far_r = slab_far_product(nd.rfx, nd.rfy, nd.rfz, ray, inv_d);
-                            if (__ballot(far_pair_uncertain(tl, far_l, tr, far_r)) != 0ull) {
+                            float far_l, far_r;
+                            bool unsure;
+                            if (FAR_FMA) {
+                                far_l = slab_far_fma(nd.lfx, nd.lfy, nd.lfz, inv_d, far_c);
+                                far_r = slab_far_fma(nd.rfx, nd.rfy, nd.rfz, inv_d, far_c);
+                                unsure = far_pair_uncertain_fma(tl, far_l, tr, far_r, far_s_eps);
+                            } else {
+                                far_l = slab_far_product(nd.lfx, nd.lfy, nd.lfz, ray, inv_d);
+                                far_r = slab_far_product(nd.rfx, nd.rfy, nd.rfz, ray, inv_d);
+                                unsure = far_pair_uncertain(tl, far_l, tr, far_r);
+                            }
+                            if (__ballot(unsure) != 0ull) {
+#ifdef RT_PHASE_TIMERS
+                                pc_[14]++;   // hot-loop steps that take the exact redo (wave level), and those of them that some lane asks for over the sign of tmax
+                                if (FAR_FMA && __ballot(min(__float_as_uint(far_l), __float_as_uint(far_r)) <= __float_as_uint(far_s_eps)) != 0ull) pc_[15]++;
+#endif
                                 asm volatile("" ::: "memory");   // (a second read of the node: the common path need not keep six plane offsets alive)
                                 const WideNodeData n2 = fetch_wide_node<BIG>(nodes, lds, p.scene.n_top, cur, kx, ky, kz);
                                 far_l = slab_far_exact(n2.lfx, n2.lfy, n2.lfz, ray, inv_d, inv_lo);
@@ -1052,6 +1073,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                     regular = ray_is_regular(ray);
                     inv_d = mk3(rcp_exact_regular(ray.d.x), rcp_exact_regular(ray.d.y), rcp_exact_regular(ray.d.z));   // used by regular rays only
                     if (FAST_BVH && !TOL) inv_lo = mk3(rcp_low_word(ray.d.x, inv_d.x), rcp_low_word(ray.d.y, inv_d.y), rcp_low_word(ray.d.z, inv_d.z));
+                    if (FAR_FMA) { far_c = slab_fma_offset(ray, inv_d); far_s_eps = slab_fma_margin(far_c); }
                     const uint32_t km = (regular && FAST_BVH) ? 4u : 0u;
                     kx = (__float_as_uint(ray.d.x) >> 29) & km;
                     ky = (__float_as_uint(ray.d.y) >> 29) & km;
