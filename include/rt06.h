@@ -402,6 +402,47 @@ enum { RT_NMAP_REPLACED = 1, RT_NMAP_FLAT = 2, RT_NMAP_NO_TANGENT = 3, RT_NMAP_N
 int rt_normal_map_batch(const rt_texture* records, uint32_t n, const uint8_t* texels, size_t count, const uint32_t* surface, const float* a, const float* b,
                         const float* tri_uv, const float* normal, const float* ray_d, const float* u, const float* v, const uint32_t* index, const float* strength,
                         float* out_normal, uint32_t* out_path);
+/* ---- microfacet surfaces (not in the reference): a GGX lobe with visible-normal sampling, attached PER MATERIAL in a table beside the flat world,
+ * one 16-byte record per material, as a normal map is.  On RT_MAT_METAL the record makes a rough conductor: albedo is F0, the record's roughness replaces the fuzz
+ * (which is not read), specular is ignored.  On Lambertian, checker, noise and image materials it lays a glossy dielectric coat of scalar F0 = specular over the
+ * base, which stays what it was.  on == RT_MICROFACET_MAPPED multiplies the roughness by the green channel of entry `image` of the texture table at the hit's (u, v).
+ * The rule, with N = the shading normal the shade phase holds (after a normal map), d = the ray's direction, r = the roughness, G = the hit's generator:
+ *   1  v = -d / sqrt(dot(d, d));  co = dot(N, v);  !(co > 0): RT_MFAC_BACKSIDE, the hit is shaded as if its material had no record (a sphere seen from inside)
+ *   2  a = max(r r, 0x1p-10f)
+ *   3  s = N.z >= 0 ? 1 : -1;  k = -1 / (s + N.z);  b = (N.x N.y) k;  T = (1 + ((s N.x) N.x) k, s b, -(s N.x));  B = (b, s + (N.y N.y) k, -N.y)
+ *   4  h = normalize((a dot(T, v), a dot(B, v), co))
+ *   5  l2 = h.x h.x + h.y h.y;  T1 = l2 > 0 ? (-h.y, h.x, 0) / sqrt(l2) : (1, 0, 0);  T2 = cross(h, T1)
+ *   6  (t1, t2) = a point of the unit disc, drawn as the lens's is (a rejection loop: the number of uniforms varies);  q = 0.5 (1 + h.z);
+ *      t2 = (1 - q) sqrt(max(0, 1 - t1 t1)) + q t2;  nh = (T1 t1 + T2 t2) + h sqrt(max(0, (1 - t1 t1) - t2 t2))
+ *   7  m = normalize((a nh.x, a nh.y, max(0, nh.z)));  M = (T m.x + B m.y) + N m.z;  ch = dot(v, M);  x = 1 - min(max(ch, 0), 1);  k5 = ((x x) (x x)) x
+ *   8  conductor: F = F0 + (1 - F0) k5 per channel, and the hit is specular.  coat: F = f0 + (1 - f0) k5, one uniform u, specular exactly when u < F; otherwise
+ *      RT_MFAC_BASE: the base material's scatter runs verbatim, with the draws, albedo, light-sampling half and weights it would have had without a record
+ *   9  w = M (2 ch) - v;  ci = dot(N, w);  !(ci > 0): RT_MFAC_ABSORBED, as a metal's ray below the surface;
+ *      G = 2 / (1 + sqrt(1 + ((a a) max(0, 1 - ci ci)) / (ci ci)));  RT_MFAC_SPECULAR: the direction is w, the throughput is multiplied by F G (conductor) or by
+ *      G alone (coat: the toss already paid F); no light-sampling weight applies.
+ * normalize(x) = x (1 / sqrt(dot(x, x))); max(x, c) = x > c ? x : c and min(x, c) = x < c ? x : c, so a NaN takes c.  Only fp32 + - * / sqrt and comparisons, each
+ * rounded on its own, no FMA.  A material without a record changes no bit of any frame; roughness 0 is no special case.  Not done: anisotropy, the height-
+ * correlated masking term, multiple-scattering compensation, rough refraction and records on glass, sampling the lobe towards lights, metallic maps.        */
+typedef struct rt_microfacet { uint32_t on, image; float roughness, specular; } rt_microfacet;   /* 16 B, one per material */
+enum { RT_MICROFACET_OFF = 0, RT_MICROFACET_CONSTANT = 1, RT_MICROFACET_MAPPED = 2 };
+/* Gives `material` a constant-roughness record.  RT_ERR_INVALID, scene unchanged: no such material; a dielectric, a light or an isotropic material; a roughness
+ * or a specular that is not finite or lies outside [0, 1].  A record that is already mapped keeps its map.                                                   */
+int rt_scene_set_microfacet(rt_scene* s, uint32_t material, float roughness, float specular);
+/* Makes the record of `material` a mapped one: its roughness is multiplied by the green channel of entry `image` of the scene's texture table.  RT_ERR_INVALID:
+ * no such material, a material without a record (rt_scene_set_microfacet first), image >= RT_MAX_IMAGES.  The entry is checked where a renderer launches.      */
+int rt_scene_set_roughness_map(rt_scene* s, uint32_t material, uint32_t image);
+int rt_scene_clear_microfacet(rt_scene* s, uint32_t material);
+/* One record per material of the scene (*out = NULL, *out_n = 0 while no material has one), as rt_scene_normal_maps hands its table out                      */
+int rt_scene_microfacets(const rt_scene* s, const rt_microfacet** out, uint32_t* out_n);
+/* Which way a case left the rule (above) */
+enum { RT_MFAC_SPECULAR = 1, RT_MFAC_BASE = 2, RT_MFAC_ABSORBED = 3, RT_MFAC_BACKSIDE = 4 };
+/* HOST (no GPU): the function the kernels call, on `count` cases — per case N, d, the roughness (finite, in [0, 1]; no map: the product is the caller's), F0 in
+ * f0[3 i ..] (a coat reads f0[3 i] alone), coat[i] != 0 for a coat, and its uniforms: the words tape[offsets[2 i] ..] of which there are offsets[2 i + 1], each k
+ * in [1, 2^24] standing for the uniform k 2^-24 (past its end a tape serves 2^23 + 1, which every rejection loop accepts) -> out_dir[3 i ..] (w; zero unless the
+ * case is specular), out_weight[3 i ..] (F G or G three times; zero unless specular), out_path[i] = RT_MFAC_*, out_draws[i] = uniforms consumed.
+ * RT_ERR_INVALID: a null argument, a tape range outside the tape, a roughness out of range.                                                                    */
+int rt_microfacet_batch(size_t count, const float* normal, const float* ray_d, const float* roughness, const float* f0, const uint32_t* coat, const uint32_t* tape,
+                        size_t tape_len, const uint32_t* offsets, float* out_dir, float* out_weight, uint32_t* out_path, uint32_t* out_draws);
 
 /* BVH_Handle::Factory::BuildBVH_TopDown -> _build_bvh_rec1 (BVH.cu:166-210):
  * median split on the longest axis, leaf size 1, post-order numbering, root =
@@ -563,6 +604,9 @@ int rt_renderer_kernel_light_tree(rt_renderer* r, uint32_t* out);
 int rt_renderer_kernel_env_light(rt_renderer* r, uint32_t* out);
 /* *out = 1 when the next launch runs an instantiation of the normal-map family, as rt_renderer_kernel_env_light answers for its own */
 int rt_renderer_kernel_normal_map(rt_renderer* r, uint32_t* out);
+/* *out = 1 when the next launch runs an instantiation of the microfacet family: a microfacet table is on.  rt_renderer_kernel_normal_map answers
+ * 0 then, whether or not a normal-map table is on too: the microfacet forms read both tables.                                                                 */
+int rt_renderer_kernel_microfacet(rt_renderer* r, uint32_t* out);
 /* Renderer::DownloadRenderbuffer (Renderer.cu:94-96): width*height*4 floats,
  * row-major, row 0 = bottom.  Only valid for world_size == 1.               */
 int rt_renderer_download(rt_renderer* r, float* host_rgba, size_t n_floats);
@@ -850,6 +894,18 @@ int rt_renderer_textures_info(rt_renderer* r, uint32_t out[2]);
 int rt_renderer_normal_maps(rt_renderer* r, const rt_normal_map* table, uint32_t n);
 /* out[0] = 1 while a table is on, out[1] = how many of its records are on */
 int rt_renderer_normal_maps_info(rt_renderer* r, uint32_t out[2]);
+/* Microfacet surfaces (rt_scene_microfacets): table = one record per material of the world, or NULL, 0 for off (the default).  While a table is on,
+ * plain launches and those of light-sampling mode 48 run the MFAC form of the renderer's kernel (rt_renderer_kernel_microfacet), whether or not a normal-map table
+ * is on; that form reads both.  A table without a mapped record needs no texture table.  The feature pass does not read the table and is what it was.
+ * Takes effect at the next launch; an unchanged table is a no-op that keeps the refinement, a change discards the refinement and feature-buffer state.
+ * RT_ERR_INVALID with a message of its own: a count that is not the world's number of materials; a record on a dielectric, a light or a medium, with an unknown
+ * `on`, an image index past RT_MAX_IMAGES, or a roughness or specular that is not finite and in [0, 1]; kernel variants 1, 5 and 6; a world with a queue or wide4
+ * traversal, or a bvh_node tree; light-sampling modes 1, 2, 4, 16 and 32 (rt_renderer_light_sampling_enable refuses them in turn while a table is on).
+ * rt_renderer_render, the refine calls and their async forms return RT_ERR_INVALID and launch nothing while a mapped record names an entry the renderer's texture
+ * table (rt_renderer_textures) does not have.                                                                                                                  */
+int rt_renderer_microfacets(rt_renderer* r, const rt_microfacet* table, uint32_t n);
+/* out[0] = 1 while a table is on, out[1] = how many of its records are on */
+int rt_renderer_microfacets_info(rt_renderer* r, uint32_t out[2]);
 
 /* ------------------------------------------------------------------ */
 /* Multi-GPU renderer — the same three entry points (Renderer.h:38-46)  */
@@ -888,6 +944,9 @@ int rt_multi_renderer_textures_info(rt_multi_renderer* m, uint32_t out[2]);
 /* rt_renderer_normal_maps on every rank (refused before any rank changes), and rt_renderer_normal_maps_info of the ranks.    */
 int rt_multi_renderer_normal_maps(rt_multi_renderer* m, const rt_normal_map* table, uint32_t n);
 int rt_multi_renderer_normal_maps_info(rt_multi_renderer* m, uint32_t out[2]);
+/* rt_renderer_microfacets on every rank (refused before any rank changes), and rt_renderer_microfacets_info of the ranks.    */
+int rt_multi_renderer_microfacets(rt_multi_renderer* m, const rt_microfacet* table, uint32_t n);
+int rt_multi_renderer_microfacets_info(rt_multi_renderer* m, uint32_t out[2]);
 /* Renderer::DownloadRenderbuffer: width*height*4 floats from devices[0].                                                */
 int rt_multi_renderer_download(rt_multi_renderer* m, float* host_rgba, size_t n_floats);
 /* ms of the last render: out[0] host wall-clock of Render(), out[1] slowest rank's kernels (HIP events),
@@ -933,6 +992,9 @@ int rt_probe_texture(int device, const rt_texture* records, uint32_t n, const ui
 int rt_probe_normal_map(int device, const rt_texture* records, uint32_t n, const uint8_t* texels, size_t count, const uint32_t* surface, const float* a,
                         const float* b, const float* tri_uv, const float* normal, const float* ray_d, const float* u, const float* v, const uint32_t* index,
                         const float* strength, float* out_normal, uint32_t* out_path);
+/* rt_microfacet_batch on the device, one lane per case                                                                                                        */
+int rt_probe_microfacet(int device, size_t count, const float* normal, const float* ray_d, const float* roughness, const float* f0, const uint32_t* coat,
+                        const uint32_t* tape, size_t tape_len, const uint32_t* offsets, float* out_dir, float* out_weight, uint32_t* out_path, uint32_t* out_draws);
 /* rt_noise_value_batch on the device, one lane per point: the tables in global memory, as the renderer holds them                                              */
 int rt_probe_noise_value(int device, const rt_perlin* perlin, const float albedo[3], float scale, const float* points, size_t n, float* out_rgb);
 /* rt_environment_sample_batch on the device, one lane per quadruple: the records and the tables as the renderer holds them in mode RT_LIGHT_SAMPLING_ENV        */

@@ -376,6 +376,16 @@ public:
         check(rt_scene_normal_maps(s_, out, &n), "rt_scene_normal_maps");
         return n;
     }
+    // microfacet surfaces (extension; rt_scene_set_microfacet): a metal material becomes a rough GGX conductor, a Lambertian kind gets a glossy
+    // coat of F0 = specular; a roughness map scales the record's roughness by the green channel of image `image`; the table as rt_scene_microfacets hands it out
+    void SetMicrofacet(uint32_t material, float roughness, float specular = 0.04f) { check(rt_scene_set_microfacet(s_, material, roughness, specular), "rt_scene_set_microfacet"); }
+    void SetRoughnessMap(uint32_t material, uint32_t image) { check(rt_scene_set_roughness_map(s_, material, image), "rt_scene_set_roughness_map"); }
+    void ClearMicrofacet(uint32_t material) { check(rt_scene_clear_microfacet(s_, material), "rt_scene_clear_microfacet"); }
+    uint32_t Microfacets(const rt_microfacet** out) const {
+        uint32_t n = 0;
+        check(rt_scene_microfacets(s_, out, &n), "rt_scene_microfacets");
+        return n;
+    }
     // child reference of a bvh_node tree: >= 0 node, < 0 primitive
     int32_t tree_ref(const Hittable* h) {
         if (h->kind() == Hittable::NODE) {
@@ -633,8 +643,14 @@ class Renderer {
             const rt_normal_map* nmaps = nullptr;          // ... and one with normal maps theirs, and with them the table they name their images in
             uint32_t n_nmaps = 0;
             rt06::check(rt_scene_normal_maps(static_cast<const BVH*>(world)->scene, &nmaps, &n_nmaps), "rt_scene_normal_maps");
-            if (table_says_more || (n_nmaps && n_tex)) made.SetTextures(tex, n_tex, texels);
+            const rt_microfacet* mfacs = nullptr;         // ... and one with microfacet records theirs; the texture table with them when one is mapped
+            uint32_t n_mfacs = 0;
+            rt06::check(rt_scene_microfacets(static_cast<const BVH*>(world)->scene, &mfacs, &n_mfacs), "rt_scene_microfacets");
+            bool roughness_mapped = false;
+            for (uint32_t i = 0; i < n_mfacs; i++) roughness_mapped = roughness_mapped || mfacs[i].on == RT_MICROFACET_MAPPED;
+            if (table_says_more || ((n_nmaps || roughness_mapped) && n_tex)) made.SetTextures(tex, n_tex, texels);
             if (n_nmaps) made.SetNormalMaps(nmaps, n_nmaps);
+            if (n_mfacs) made.SetMicrofacets(mfacs, n_mfacs);
         }
         return made;
     }
@@ -750,6 +766,12 @@ public:
     void SetNormalMaps(const rt_normal_map* table, uint32_t n) {
         if (m.mr) rt06::check(rt_multi_renderer_normal_maps(m.mr, table, n), "Renderer::SetNormalMaps");
         else rt06::check(rt_renderer_normal_maps(m.r, table, n), "Renderer::SetNormalMaps");
+    }
+    // Microfacet surfaces (extension; rt_renderer_microfacets): one record per material of the world as SceneBuilder::Microfacets hands them out,
+    // or (nullptr, 0) for off; restarts a refinement
+    void SetMicrofacets(const rt_microfacet* table, uint32_t n) {
+        if (m.mr) rt06::check(rt_multi_renderer_microfacets(m.mr, table, n), "Renderer::SetMicrofacets");
+        else rt06::check(rt_renderer_microfacets(m.r, table, n), "Renderer::SetMicrofacets");
     }
     void SetTextures(const rt_texture* records, uint32_t n, const uint8_t* texels) {
         if (m.mr) rt06::check(rt_multi_renderer_textures(m.mr, records, n, texels), "Renderer::SetTextures");

@@ -178,6 +178,27 @@ class Scene:
         check(lib().rt_scene_normal_maps(self.h, C.byref(rec), C.byref(n)))
         return None if n.value == 0 else self._arr(rec.value, n.value, capi.NORMAL_MAP_DT)
 
+    def set_microfacet(self, material, roughness, specular=0.04):
+        """Gives `material` a microfacet record (extension; rt_scene_set_microfacet): a metal becomes a rough GGX conductor with F0 = its albedo
+        (its fuzz is no longer read, `specular` is ignored); a Lambertian (plain, checker, noise, image) material gets a glossy coat of F0 = specular over it."""
+        check(lib().rt_scene_set_microfacet(self.h, material, float(roughness), float(specular)))
+        return self
+
+    def set_roughness_map(self, material, image):
+        """The green channel of image `image` of the scene scales the roughness of `material`'s record (rt_scene_set_roughness_map; set_microfacet first)."""
+        check(lib().rt_scene_set_roughness_map(self.h, material, image))
+        return self
+
+    def clear_microfacet(self, material):
+        check(lib().rt_scene_clear_microfacet(self.h, material))
+        return self
+
+    def microfacets(self):
+        """The scene's microfacet table (rt_scene_microfacets): one record of capi.MICROFACET_DT per material, or None while no material has a record."""
+        rec, n = C.c_void_p(), C.c_uint32()
+        check(lib().rt_scene_microfacets(self.h, C.byref(rec), C.byref(n)))
+        return None if n.value == 0 else self._arr(rec.value, n.value, capi.MICROFACET_DT)
+
     def MakeBox(self, a, b, mat, rotate_y=0.0, translate=(0, 0, 0)):
         """box(a, b, mat) of "The Next Week" as 6 quads, optionally rotate_y(degrees) then translate; returns the first quad index."""
         out = C.c_int32()
@@ -382,6 +403,11 @@ class Scene:
             w.normal_maps = nmaps
             if table is not None:
                 w.textures = table
+        mfacs = self.microfacets()            # likewise the microfacet records; the texture table only with a roughness map
+        if mfacs is not None:
+            w.microfacets = mfacs
+            if table is not None and (mfacs["on"] == capi.MICROFACET_MAPPED).any():
+                w.textures = table
         return w
 
     def _arr(self, ptr, n, dt):
@@ -524,6 +550,13 @@ def _push_normal_maps(fn, handle, table):
     return fn(handle, table.ctypes.data if len(table) else None, len(table))
 
 
+def _push_microfacets(fn, handle, table):
+    if table is None:
+        return fn(handle, None, 0)
+    table = np.ascontiguousarray(table, capi.MICROFACET_DT).reshape(-1)
+    return fn(handle, table.ctypes.data if len(table) else None, len(table))
+
+
 def _env_image(image):
     img = np.ascontiguousarray(image, dtype=np.float32)
     if img.ndim != 3 or img.shape[2] != 3:
@@ -562,6 +595,8 @@ class Renderer:
             r.textures(world.textures)
         if getattr(world, "normal_maps", None) is not None:
             r.normal_maps(world.normal_maps)
+        if getattr(world, "microfacets", None) is not None:
+            r.microfacets(world.microfacets)
         return r
 
     def Render(self):
@@ -729,6 +764,23 @@ class Renderer:
         check(lib().rt_renderer_kernel_normal_map(self.h, C.byref(out)))
         return bool(out.value)
 
+    def microfacets(self, table):
+        """The microfacet table from the next launch on (rt_renderer_microfacets): one record of capi.MICROFACET_DT per material as
+        Scene.microfacets() gives it; None = off.  A mapped record names its image in the texture table (Renderer.textures).  A change restarts the refinement."""
+        check(_push_microfacets(lib().rt_renderer_microfacets, self.h, table))
+
+    def microfacets_info(self):
+        """{'enabled', 'records'} of the renderer's microfacet table: records = how many materials have one."""
+        out = (C.c_uint32 * 2)()
+        check(lib().rt_renderer_microfacets_info(self.h, out))
+        return {"enabled": bool(out[0]), "records": out[1]}
+
+    def kernel_microfacet(self):
+        """True when the next launch runs the streaming kernel's microfacet family (rt_renderer_kernel_microfacet): a microfacet table is on."""
+        out = C.c_uint32(0)
+        check(lib().rt_renderer_kernel_microfacet(self.h, C.byref(out)))
+        return bool(out.value)
+
     def textures_info(self):
         """{'enabled', 'entries'} of the renderer's texture table."""
         out = (C.c_uint32 * 2)()
@@ -846,6 +898,8 @@ class MultiRenderer:
             m.textures(world.textures)
         if getattr(world, "normal_maps", None) is not None:
             m.normal_maps(world.normal_maps)
+        if getattr(world, "microfacets", None) is not None:
+            m.microfacets(world.microfacets)
         return m
 
     def Render(self):
@@ -888,6 +942,16 @@ class MultiRenderer:
         out = (C.c_uint32 * 2)()
         check(lib().rt_multi_renderer_normal_maps_info(self.h, out))
         return {"enabled": bool(out[0]), "mapped": out[1]}
+
+    def microfacets(self, table):
+        """rt_renderer_microfacets on every rank; `table` as Renderer.microfacets takes it."""
+        check(_push_microfacets(lib().rt_multi_renderer_microfacets, self.h, table))
+
+    def microfacets_info(self):
+        """{'enabled', 'records'} of the ranks' microfacet table (they hold the same one)."""
+        out = (C.c_uint32 * 2)()
+        check(lib().rt_multi_renderer_microfacets_info(self.h, out))
+        return {"enabled": bool(out[0]), "records": out[1]}
 
     def textures_info(self):
         """{'enabled', 'entries'} of the ranks' texture table (they hold the same one)."""
@@ -1213,6 +1277,35 @@ def normal_map_batch(table, surface, a, b, tri_uv, normal, ray_d, u, v, index, s
 def probe_normal_map(table, surface, a, b, tri_uv, normal, ray_d, u, v, index, strength, device=0):
     """rt_probe_normal_map: normal_map_batch on the device, one lane per case"""
     return _normal_map(lambda *args: lib().rt_probe_normal_map(device, *args), table, surface, a, b, tri_uv, normal, ray_d, u, v, index, strength)
+
+
+def _microfacet(fn, normal, ray_d, roughness, f0, coat, tapes):
+    normal, ray_d, f0 = (np.ascontiguousarray(x, np.float32).reshape(-1, 3) for x in (normal, ray_d, f0))
+    roughness = np.ascontiguousarray(roughness, np.float32).reshape(-1)
+    coat = np.ascontiguousarray(coat, np.uint32).reshape(-1)
+    n = len(roughness)
+    if not all(len(x) == n for x in (normal, ray_d, f0, coat, tapes)):
+        raise ValueError("microfacet: every array must have one entry per case")
+    lengths = np.array([len(t) for t in tapes], np.uint32)
+    offsets = np.zeros((n, 2), np.uint32)
+    offsets[:, 1] = lengths
+    offsets[1:, 0] = np.cumsum(lengths, dtype=np.uint64)[:-1]
+    tape = np.ascontiguousarray(np.concatenate([np.asarray(t, np.uint32) for t in tapes] + [np.array([0x800001], np.uint32)]), np.uint32)
+    out_dir, weight, path, draws = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+    check(fn(n, normal, ray_d, roughness, f0, coat, tape, len(tape), offsets, out_dir, weight, path, draws))
+    return out_dir, weight, path, draws
+
+
+def microfacet_batch(normal, ray_d, roughness, f0, coat, tapes):
+    """rt_microfacet_batch (host only): the microfacet rule on n cases — per case the normal, the ray's direction, the roughness, F0 (n, 3; a coat
+    reads its first component), coat != 0 for a coat, and tapes[i] = its uniforms as words k in [1, 2^24] (u = k 2^-24) -> (directions (n, 3), weights (n, 3),
+    path (n,) of capi.MFAC_*, uniforms consumed (n,))"""
+    return _microfacet(lib().rt_microfacet_batch, normal, ray_d, roughness, f0, coat, tapes)
+
+
+def probe_microfacet(normal, ray_d, roughness, f0, coat, tapes, device=0):
+    """rt_probe_microfacet: microfacet_batch on the device, one lane per case"""
+    return _microfacet(lambda *args: lib().rt_probe_microfacet(device, *args), normal, ray_d, roughness, f0, coat, tapes)
 
 
 def _noise_value(fn, world, albedo, scale, points):

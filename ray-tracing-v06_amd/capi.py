@@ -36,6 +36,9 @@ TEXTURE_DT = np.dtype([("width", "<u4"), ("height", "<u4"), ("wrap", "<u4"), ("f
 NORMAL_MAP_DT = np.dtype([("on", "<u4"), ("image", "<u4"), ("strength", "<f4"), ("pad", "<u4")])   # rt_normal_map, 16 B
 NMAP_SURFACE_SPHERE, NMAP_SURFACE_PLANAR, NMAP_SURFACE_TRI_UV, NMAP_SURFACE_GIVEN = 0, 1, 2, 3
 NMAP_REPLACED, NMAP_FLAT, NMAP_NO_TANGENT, NMAP_NO_LENGTH, NMAP_FACING, NMAP_NO_FRAME = 1, 2, 3, 4, 5, 6
+MICROFACET_DT = np.dtype([("on", "<u4"), ("image", "<u4"), ("roughness", "<f4"), ("specular", "<f4")])   # rt_microfacet, 16 B
+MICROFACET_OFF, MICROFACET_CONSTANT, MICROFACET_MAPPED = 0, 1, 2
+MFAC_SPECULAR, MFAC_BASE, MFAC_ABSORBED, MFAC_BACKSIDE = 1, 2, 3, 4
 WRAP_CLAMP, WRAP_REPEAT = 0, 1
 FILTER_NEAREST, FILTER_BILINEAR = 0, 1
 MAX_IMAGES = 256
@@ -110,6 +113,8 @@ SYMBOLS = [
     "rt_renderer_aov_enable_mode", "rt_renderer_aov_mode", "rt_noise_value_batch", "rt_probe_noise_value",
     "rt_scene_set_normal_map", "rt_scene_clear_normal_map", "rt_scene_normal_maps", "rt_normal_map_batch", "rt_probe_normal_map",
     "rt_renderer_normal_maps", "rt_renderer_normal_maps_info", "rt_renderer_kernel_normal_map", "rt_multi_renderer_normal_maps", "rt_multi_renderer_normal_maps_info",
+    "rt_scene_set_microfacet", "rt_scene_set_roughness_map", "rt_scene_clear_microfacet", "rt_scene_microfacets", "rt_microfacet_batch", "rt_probe_microfacet",
+    "rt_renderer_microfacets", "rt_renderer_microfacets_info", "rt_renderer_kernel_microfacet", "rt_multi_renderer_microfacets", "rt_multi_renderer_microfacets_info",
 ]
 
 _lib = None
@@ -241,6 +246,17 @@ def lib():
     L.rt_renderer_kernel_normal_map.argtypes = [C.c_void_p, P(C.c_uint32)]
     L.rt_multi_renderer_normal_maps.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     L.rt_multi_renderer_normal_maps_info.argtypes = [C.c_void_p, C.c_uint32 * 2]
+    L.rt_scene_set_microfacet.argtypes = [C.c_void_p, C.c_uint32, C.c_float, C.c_float]
+    L.rt_scene_set_roughness_map.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
+    L.rt_scene_clear_microfacet.argtypes = [C.c_void_p, C.c_uint32]
+    L.rt_scene_microfacets.argtypes = [C.c_void_p, P(C.c_void_p), P(C.c_uint32)]
+    L.rt_microfacet_batch.argtypes = [C.c_size_t, f32p, f32p, f32p, f32p, u32p, u32p, C.c_size_t, u32p, f32p, f32p, u32p, u32p]
+    L.rt_probe_microfacet.argtypes = [C.c_int] + L.rt_microfacet_batch.argtypes
+    L.rt_renderer_microfacets.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+    L.rt_renderer_microfacets_info.argtypes = [C.c_void_p, C.c_uint32 * 2]
+    L.rt_renderer_kernel_microfacet.argtypes = [C.c_void_p, P(C.c_uint32)]
+    L.rt_multi_renderer_microfacets.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+    L.rt_multi_renderer_microfacets_info.argtypes = [C.c_void_p, C.c_uint32 * 2]
     L.rt_scene_set_background.argtypes = [C.c_void_p, C.c_uint32, vec3]
     L.rt_scene_set_perlin.argtypes = [C.c_void_p, C.c_uint64]
     L.rt_scene_set_image.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]

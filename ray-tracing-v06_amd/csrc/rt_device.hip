@@ -59,6 +59,7 @@ constexpr uint32_t RT_KEY_NEE = 1u << 10;   // light sampling (rt_renderer_light
 constexpr uint32_t RT_KEY_LTREE = 1u << 12; // the light tree (mode RT_LIGHT_SAMPLING_TREE): the LTREE form of a TRI && NEE key; reported by rt_renderer_kernel_light_tree
 constexpr uint32_t RT_KEY_ENVL = 1u << 13;  // environment light sampling (mode RT_LIGHT_SAMPLING_ENV): the ENVL form of an EXT 2 TRI && NEE key; reported by rt_renderer_kernel_env_light
 constexpr uint32_t RT_KEY_NMAP = 1u << 14;  // normal maps (rt_renderer_normal_maps): the NMAP form of an EXT 2 TRI key, plain or with mode 48; reported by rt_renderer_kernel_normal_map
+constexpr uint32_t RT_KEY_MFAC = 1u << 15;  // microfacet surfaces (rt_renderer_microfacets): the MFAC form of an EXT 2 TRI key, plain or with mode 48, which reads the normal-map table too; reported by rt_renderer_kernel_microfacet
 constexpr uint32_t RT_KEY_TRI = 1u << 11;   // the world has triangles: the TRI form of an EXT >= 1 stack-walk or list key, plain or NEE; not one of rt_renderer_kernel_form's fields
 // a stream key read back into render_kernel_stream's template arguments, in stream_key()'s order, then NEE: what rt_renderer_kernel_form reports
 static void stream_key_fields(uint32_t key, uint32_t out[8]) {
@@ -105,9 +106,13 @@ static const void* stream_kernel_for(uint32_t key) {
 #define RT_KERNEL_ENV_TREE(exact, world, ext, big, wide) \
     case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NEE | RT_KEY_LTREE | RT_KEY_ENVL: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, true, true, true, true>)
 #define RT_KERNEL_NORMAL_MAP(exact, world, ext, big, wide) \
-    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NMAP: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, false, true, false, false, true>)
+    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NMAP: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, false, true, false, false, false, true>)
 #define RT_KERNEL_NORMAL_MAP_ENV_TREE(exact, world, ext, big, wide) \
-    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NEE | RT_KEY_LTREE | RT_KEY_ENVL | RT_KEY_NMAP: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, true, true, true, true, true>)
+    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NEE | RT_KEY_LTREE | RT_KEY_ENVL | RT_KEY_NMAP: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, true, true, true, true, false, true>)
+#define RT_KERNEL_MICROFACET(exact, world, ext, big, wide) \
+    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_MFAC: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, false, true, false, false, true, true>)
+#define RT_KERNEL_MICROFACET_ENV_TREE(exact, world, ext, big, wide) \
+    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NEE | RT_KEY_LTREE | RT_KEY_ENVL | RT_KEY_MFAC: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, true, true, true, true, true, true>)
     switch (key) {   // arguments: exact, filter, world, ext, big, wide, tol
         case RT_KEY_XCHG: return reinterpret_cast<const void*>(&render_kernel_xchg<RT_XCHG_BLOCK>);
         RT_KERNEL(true, false, RT_WORLD_BVH_QUEUE, 2, true, true, false); RT_KERNEL(true, false, RT_WORLD_BVH_QUEUE, 1, true, true, false); RT_KERNEL(true, false, RT_WORLD_BVH_QUEUE, 0, true, true, false);
@@ -165,9 +170,23 @@ static const void* stream_kernel_for(uint32_t key) {
         RT_KERNEL_NORMAL_MAP_ENV_TREE(false, RT_WORLD_BVH, 2, true, false); RT_KERNEL_NORMAL_MAP_ENV_TREE(true, RT_WORLD_BVH, 2, true, false);
         RT_KERNEL_NORMAL_MAP_ENV_TREE(true, RT_WORLD_LIST, 2, false, false);
         RT_KERNEL_NORMAL_MAP_ENV_TREE(false, RT_WORLD_BVH, 2, false, false); RT_KERNEL_NORMAL_MAP_ENV_TREE(true, RT_WORLD_BVH, 2, false, false);
+        // microfacet surfaces: the same eight shapes, reading both tables, plain ...
+        RT_KERNEL_MICROFACET(true, RT_WORLD_LIST, 2, true, true);
+        RT_KERNEL_MICROFACET(false, RT_WORLD_BVH, 2, true, true); RT_KERNEL_MICROFACET(true, RT_WORLD_BVH, 2, true, true);
+        RT_KERNEL_MICROFACET(false, RT_WORLD_BVH, 2, true, false); RT_KERNEL_MICROFACET(true, RT_WORLD_BVH, 2, true, false);
+        RT_KERNEL_MICROFACET(true, RT_WORLD_LIST, 2, false, false);
+        RT_KERNEL_MICROFACET(false, RT_WORLD_BVH, 2, false, false); RT_KERNEL_MICROFACET(true, RT_WORLD_BVH, 2, false, false);
+        // ... and under mode 48
+        RT_KERNEL_MICROFACET_ENV_TREE(true, RT_WORLD_LIST, 2, true, true);
+        RT_KERNEL_MICROFACET_ENV_TREE(false, RT_WORLD_BVH, 2, true, true); RT_KERNEL_MICROFACET_ENV_TREE(true, RT_WORLD_BVH, 2, true, true);
+        RT_KERNEL_MICROFACET_ENV_TREE(false, RT_WORLD_BVH, 2, true, false); RT_KERNEL_MICROFACET_ENV_TREE(true, RT_WORLD_BVH, 2, true, false);
+        RT_KERNEL_MICROFACET_ENV_TREE(true, RT_WORLD_LIST, 2, false, false);
+        RT_KERNEL_MICROFACET_ENV_TREE(false, RT_WORLD_BVH, 2, false, false); RT_KERNEL_MICROFACET_ENV_TREE(true, RT_WORLD_BVH, 2, false, false);
         default: return nullptr;
     }
 #undef RT_KERNEL
+#undef RT_KERNEL_MICROFACET
+#undef RT_KERNEL_MICROFACET_ENV_TREE
 #undef RT_KERNEL_NORMAL_MAP
 #undef RT_KERNEL_NORMAL_MAP_ENV_TREE
 #undef RT_KERNEL_ENV_TREE
@@ -312,8 +331,11 @@ struct rt_renderer {
     // normal maps (rt_renderer_normal_maps): one record per material as given; the tail carries them behind the texture table, whose header points
     // there.  While on, a plain launch and a mode-48 launch run the NMAP form of their kernel (plain / envt, resolved when the table or the mode comes on).
     struct NormalMaps { bool on = false; uint32_t n_mapped = 0; std::vector<rt_normal_map> host; } nm;
-    struct { uint32_t key = 0; const void* kernel = nullptr; } nm_plain, nm_envt;
-    bool tail_on() const { return vn.on || uv.on || env.on || tex.on; }
+    // microfacet surfaces (rt_renderer_microfacets): one record per material as given; the tail carries them last, and the bits above bit 0 of its
+    // header's first lane say where.  While on, a plain launch and a mode-48 launch run the MFAC form of their kernel, which reads the normal-map table too.
+    struct Microfacets { bool on = false; uint32_t n_on = 0; std::vector<rt_microfacet> host; } mf;
+    struct { uint32_t key = 0; const void* kernel = nullptr; } nm_plain, nm_envt, mf_plain, mf_envt;
+    bool tail_on() const { return vn.on || uv.on || env.on || tex.on || mf.on; }
     // the NMAP form of the renderer's kernel: the world's own shape at EXT 2 with TRI, plain or with mode 48's bits (0: a world no NMAP form walks)
     uint32_t normal_map_key(bool envt) const {
         if (variant < 2 || variant == 5 || tol || scene.queue || scene.dw.kind == RT_WORLD_NODE_TREE) return 0u;
@@ -325,6 +347,13 @@ struct rt_renderer {
         if (!nm.on) return false;
         for (const rt_normal_map& m : nm.host)
             if (m.on && (!tex.on || m.image >= tex.records.size() || tex.records[m.image].width == 0u)) { *which = m.image; return true; }
+        return false;
+    }
+    // ... or for its roughness maps (§29); a table of constant records needs no texture table
+    bool roughness_map_entry_missing(uint32_t* which) const {
+        if (!mf.on) return false;
+        for (const rt_microfacet& m : mf.host)
+            if (m.on == RT_MICROFACET_MAPPED && (!tex.on || m.image >= tex.records.size() || tex.records[m.image].width == 0u)) { *which = m.image; return true; }
         return false;
     }
     // whether a launch is refused for its image materials (§25): one of them names an entry (*which) the renderer does not have
@@ -364,6 +393,8 @@ struct rt_renderer {
         l.key = m ? nee.resolved[m - LIGHT_MODES].key : stream_kernel_key(variant, tol, scene);
         if (nm.on && !m) { l.kernel = nm_plain.kernel; l.key = nm_plain.key; }   // §28: the other modes are refused while a table is on
         if (nm.on && mode == RT_LIGHT_SAMPLING_ENV_TREE) { l.kernel = nm_envt.kernel; l.key = nm_envt.key; }
+        if (mf.on && !m) { l.kernel = mf_plain.kernel; l.key = mf_plain.key; }   // §29: likewise, and before a normal-map table's form: the MFAC forms read both
+        if (mf.on && mode == RT_LIGHT_SAMPLING_ENV_TREE) { l.kernel = mf_envt.kernel; l.key = mf_envt.key; }
         l.blob = (im.blob.p ? im.blob : scene.blob).as<uint4>();
         l.blob_vec4 = scene.packed.blob_vec4 + im.table_vec4;
         l.lds_bytes = i ? im.lds_bytes : stream_lds_bytes;
@@ -378,6 +409,18 @@ struct rt_renderer {
         const uint32_t key = normal_map_key(envt);
         const void* k = key ? stream_kernel_for(key) : nullptr;
         if (!k) return rt_fail(RT_ERR_INVALID, "rt_renderer_normal_maps: this world's kernel has no form that reads a normal-map table");
+        HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+        slot_of.key = key; slot_of.kernel = k;
+        return RT_OK;
+    }
+    // §29: the MFAC form of the plain kernel, or of mode 48's, once: the NMAP form's shape with the microfacet bit in the normal-map bit's place
+    int resolve_microfacet_kernel(bool envt, uint32_t lds_bytes) {
+        auto& slot_of = envt ? mf_envt : mf_plain;
+        if (slot_of.kernel) return RT_OK;
+        const uint32_t nmap_key = normal_map_key(envt);
+        const uint32_t key = nmap_key ? (nmap_key & ~RT_KEY_NMAP) | RT_KEY_MFAC : 0u;
+        const void* k = key ? stream_kernel_for(key) : nullptr;
+        if (!k) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: this world's kernel has no form that reads a microfacet table");
         HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
         slot_of.key = key; slot_of.kernel = k;
         return RT_OK;
@@ -404,6 +447,7 @@ struct rt_renderer {
         rd.env_texels = (uint64_t)reinterpret_cast<uintptr_t>(env.texels.p); rd.env_dist = env.dist_on ? (uint64_t)reinterpret_cast<uintptr_t>(env.dist.p) : 0ull;
         rd.textures = tex.on; rd.texture = tex.records.data(); rd.n_textures = tex.records.size(); rd.texture_texels = (uint64_t)reinterpret_cast<uintptr_t>(tex.texels.p);
         if (nm.on) { rd.normal_maps = nm.host.data(); rd.n_normal_maps = nm.host.size(); }
+        if (mf.on) { rd.microfacets = mf.host.data(); rd.n_microfacets = mf.host.size(); }
         rt_image::append_tail(rest, rd);
         const size_t scene_bytes = (size_t)scene.packed.blob_vec4 * sizeof(uint4);
         HIP_TRY(fresh.blob.alloc(scene_bytes + rest.size() * sizeof(uint4)));
@@ -937,6 +981,8 @@ static int enqueue_call(rt_renderer* r, void* hip_stream, float* d_out, uint32_t
         return rt_fail(RT_ERR_INVALID, "an image material of the world names image %u and the renderer's texture table has no such entry: give it one with rt_renderer_textures before rendering", k);
     if (uint32_t k = 0u; r->normal_map_entry_missing(&k))   // ... nor on a normal map the table does not hold
         return rt_fail(RT_ERR_INVALID, "a normal map of the world names image %u and the renderer's texture table has no such entry: give it one with rt_renderer_textures before rendering", k);
+    if (uint32_t k = 0u; r->roughness_map_entry_missing(&k))   // ... nor on a roughness map it does not hold
+        return rt_fail(RT_ERR_INVALID, "a roughness map of the world names image %u and the renderer's texture table has no such entry: give it one with rt_renderer_textures before rendering", k);
     HIP_TRY(hipSetDevice(r->cfg.device));
     hipStream_t st = (hipStream_t)hip_stream;  // NULL is the HIP null stream, as for any HIP launch
     HIP_TRY(hipEventRecord(r->ev0, st));
@@ -1005,6 +1051,8 @@ extern "C" int rt_renderer_light_sampling_enable(rt_renderer* r, uint32_t on) {
             return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: kernel variant %u has no light-sampling form (the baseline kernel 1, the ray exchange 5 and the tolerance mode 6 do not; use variant 0, 2 or 3)", r->tol ? 6u : r->variant);
         if (r->nm.on && on != RT_LIGHT_SAMPLING_ENV_TREE)
             return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: the renderer has a normal-map table, and light-sampling mode %u has no kernel that reads one: normal maps render with light sampling off or in mode 48 (take the table away with rt_renderer_normal_maps(NULL, 0) first)", on);
+        if (r->mf.on && on != RT_LIGHT_SAMPLING_ENV_TREE)
+            return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: the renderer has a microfacet table, and light-sampling mode %u has no kernel that reads one: microfacet surfaces render with light sampling off or in mode 48 (take the table away with rt_renderer_microfacets(NULL, 0) first)", on);
         if (m->env && r->scene.dw.background != 2u)   // a world of this kind takes the modes of the light tables only, so the message lists them
             return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: mode %u samples the environment map of a world with background mode 2 (rt_scene_set_environment)%s; this world's is %u, for which on must be 0 (off), 1 (quad lights), 2 (quad and sphere lights), 4 (quad, sphere and triangle lights) or 16 (those, through a light tree, chosen by area)", on, m->beside, r->scene.dw.background);
         if (m->env && r->scene.queue)
@@ -1035,6 +1083,8 @@ extern "C" int rt_renderer_light_sampling_enable(rt_renderer* r, uint32_t on) {
         }
         if (r->nm.on)   // §28: mode 48's NMAP form, on the image of mode 16's table
             if (const int rc = r->resolve_normal_map_kernel(true, r->launch_on(on).lds_bytes)) return rc;
+        if (r->mf.on)   // §29: likewise
+            if (const int rc = r->resolve_microfacet_kernel(true, r->launch_on(on).lds_bytes)) return rc;
         if (m->env && !r->env.dist_on) {   // the distribution of the map as it stands (a map given while the mode is on brings its own: rt_renderer_environment); an all-black map is refused here
             char who[64];
             std::snprintf(who, sizeof(who), "rt_renderer_light_sampling_enable: mode %u", on);
@@ -1241,6 +1291,59 @@ extern "C" int rt_renderer_normal_maps_info(rt_renderer* r, uint32_t out[2]) {
     if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_normal_maps_info: null argument");
     out[0] = r->nm.on ? 1u : 0u;
     out[1] = r->nm.on ? r->nm.n_mapped : 0u;
+    return RT_OK;
+}
+
+// Microfacet surfaces.  Off: every launch is what it was.  On: the MFAC form of the renderer's kernel on images whose tail ends with the records.
+// The entries mapped records name are checked at every launch (enqueue_call), as a normal map's are: the tables come and go independently.
+extern "C" int rt_renderer_microfacets(rt_renderer* r, const rt_microfacet* table, uint32_t n) {
+    if (!r) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: null renderer");
+    if ((table == nullptr) != (n == 0u)) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: a table and its count go together (NULL, 0 turns it off)");
+    uint32_t n_on = 0;
+    if (n) {
+        if (r->variant < 2) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: the baseline kernel (variant 1) reads no microfacet table; use variant 0, 2 or 3");
+        if (r->variant == 5 || r->tol) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: kernel variant %u reads no microfacet table", r->tol ? 6u : 5u);
+        if (r->scene.queue) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: a world with a queue or wide4 traversal renders on lane walks that read no microfacet table (RT_TRAVERSAL_STACK and lists do)");
+        if (r->scene.dw.kind == RT_WORLD_NODE_TREE) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: a bvh_node tree renders on a walk that reads no microfacet table (BVHs walked by the stack and lists do)");
+        if (r->nee.on() && r->nee.mode != RT_LIGHT_SAMPLING_ENV_TREE)
+            return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: light-sampling mode %u is on, which has no kernel that reads a microfacet table: microfacet surfaces render with light sampling off or in mode 48", r->nee.mode);
+        if (n != r->scene.dw.n_mats) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: %u records for a world of %u materials", n, r->scene.dw.n_mats);
+        for (uint32_t i = 0; i < n; i++) {
+            if (table[i].on == RT_MICROFACET_OFF) continue;
+            if (table[i].on > RT_MICROFACET_MAPPED) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: record %u: on is 0 (off), 1 (constant roughness) or 2 (roughness under a map), not %u", i, table[i].on);
+            const uint32_t type = r->scene.mat_types[i];
+            if (type == RT_MAT_DIELECTRIC || type == RT_MAT_DIFFUSE_LIGHT || type == RT_MAT_ISOTROPIC)
+                return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: record %u: a dielectric, a light or a medium takes no microfacet record", i);
+            if (table[i].on == RT_MICROFACET_MAPPED && table[i].image >= RT_MAX_IMAGES) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: record %u: an image index lies in [0, %u)", i, RT_MAX_IMAGES);
+            if (!(std::isfinite(table[i].roughness) && table[i].roughness >= 0.0f && table[i].roughness <= 1.0f)) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: record %u: a roughness must be finite and in [0, 1]", i);
+            if (!(std::isfinite(table[i].specular) && table[i].specular >= 0.0f && table[i].specular <= 1.0f)) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: record %u: a specular must be finite and in [0, 1]", i);
+            n_on++;
+        }
+    }
+    rt_renderer::Microfacets next;
+    if (n) {
+        next.on = true; next.n_on = n_on; next.host.assign(table, table + n);
+        for (rt_microfacet& m : next.host) {   // what no kernel reads is zero, so that equal tables are equal bytes
+            if (m.on == RT_MICROFACET_OFF) m = rt_microfacet{RT_MICROFACET_OFF, 0u, 0.0f, 0.0f};
+            if (m.on == RT_MICROFACET_CONSTANT) m.image = 0u;
+        }
+    }
+    if (n ? (r->mf.on && r->mf.host.size() == n && std::memcmp(r->mf.host.data(), next.host.data(), (size_t)n * sizeof(rt_microfacet)) == 0) : !r->mf.on) return RT_OK;   // nothing changes, the refinement goes on
+    if (const int rc = wait_last_call(r)) return rc;   // launches already enqueued read the images that are replaced below (sets the device)
+    if (n) {
+        if (const int rc = r->resolve_microfacet_kernel(false, r->stream_lds_bytes)) return rc;
+        if (r->nee.mode == RT_LIGHT_SAMPLING_ENV_TREE)
+            if (const int rc = r->resolve_microfacet_kernel(true, r->launch_on(RT_LIGHT_SAMPLING_ENV_TREE).lds_bytes)) return rc;
+    }
+    r->refine_done = 0;   // samples scattered by another rule belong to another frame
+    r->aov_done = 0;
+    return r->replace_rider(r->mf, next);
+}
+
+extern "C" int rt_renderer_microfacets_info(rt_renderer* r, uint32_t out[2]) {
+    if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets_info: null argument");
+    out[0] = r->mf.on ? 1u : 0u;
+    out[1] = r->mf.on ? r->mf.n_on : 0u;
     return RT_OK;
 }
 
@@ -1535,6 +1638,11 @@ extern "C" int rt_renderer_kernel_env_light(rt_renderer* r, uint32_t* out) {
 extern "C" int rt_renderer_kernel_normal_map(rt_renderer* r, uint32_t* out) {
     if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_kernel_normal_map: null argument");
     *out = r->variant >= 2 && (r->launch_on(r->nee.mode).key & RT_KEY_NMAP) ? 1u : 0u;
+    return RT_OK;
+}
+extern "C" int rt_renderer_kernel_microfacet(rt_renderer* r, uint32_t* out) {
+    if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_kernel_microfacet: null argument");
+    *out = r->variant >= 2 && (r->launch_on(r->nee.mode).key & RT_KEY_MFAC) ? 1u : 0u;
     return RT_OK;
 }
 

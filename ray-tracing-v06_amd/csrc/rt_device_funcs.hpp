@@ -573,6 +573,54 @@ RT_HD uint32_t normal_map_apply(f3 c, float strength, f3 dPdu, f3 dPdv, f3 ray_d
     return RT_NMAP_REPLACED;
 }
 
+// Microfacet surfaces (rt06.h: rt_scene_set_microfacet): a GGX lobe, its normals drawn from the distribution of those the viewer sees.  Two
+// functions: the record's roughness under its map, and the rule, numbered as rt06.h numbers it.  Only + - * / sqrt and comparisons, each rounded on its own:
+// the probe and rt_microfacet_batch call these functions, and numpy float32 restates them bit for bit.
+RT_HD float mfac_max(float x, float c) { return x > c ? x : c; }   // a NaN takes c
+RT_HD float mfac_min(float x, float c) { return x < c ? x : c; }
+// c = texture_value of the record's entry at the hit's (u, v): the green channel scales the roughness
+RT_HD float microfacet_roughness(float roughness, f3 c) { return roughness * c.y; }
+// N = the shading normal, d = the ray's direction, r = the roughness, F0 = the conductor's albedo or — coat — the scalar specular three times; G: Rng, or the
+// probes' tape.  Returns the way out (rt06.h): RT_MFAC_SPECULAR with the direction and the factor of the throughput, or why there is neither.
+template <class G>
+RT_HD uint32_t microfacet_scatter(f3 N, f3 d, float r, f3 F0, bool coat, G& g, f3& out_dir, f3& out_weight) {
+    const f3 v = (-d) / sqrtf(dot(d, d));                                   // 1
+    const float co = dot(N, v);
+    if (!(co > 0.0f)) return RT_MFAC_BACKSIDE;
+    const float a = mfac_max(r * r, 0x1p-10f);                              // 2
+    const float s = N.z >= 0.0f ? 1.0f : -1.0f;                             // 3
+    const float k = -1.0f / (s + N.z);
+    const float b = (N.x * N.y) * k;
+    const float sx = s * N.x;
+    const f3 T = mk3(1.0f + (sx * N.x) * k, s * b, -sx);
+    const f3 B = mk3(b, s + (N.y * N.y) * k, -N.y);
+    const f3 h = normalize(mk3(a * dot(T, v), a * dot(B, v), co));          // 4
+    const float l2 = h.x * h.x + h.y * h.y;                                 // 5
+    const f3 T1 = l2 > 0.0f ? mk3(-h.y, h.x, 0.0f) / sqrtf(l2) : mk3(1.0f, 0.0f, 0.0f);
+    const f3 T2 = cross(h, T1);
+    float t1, t2;                                                           // 6
+    rng_in_unit2(g, t1, t2);
+    const float q = 0.5f * (1.0f + h.z);
+    const float t11 = t1 * t1;
+    t2 = (1.0f - q) * sqrtf(mfac_max(1.0f - t11, 0.0f)) + q * t2;
+    const f3 nh = (T1 * t1 + T2 * t2) + h * sqrtf(mfac_max((1.0f - t11) - t2 * t2, 0.0f));
+    const f3 m = normalize(mk3(a * nh.x, a * nh.y, mfac_max(nh.z, 0.0f)));  // 7
+    const f3 M = (T * m.x + B * m.y) + N * m.z;
+    const float ch = dot(v, M);
+    const float x = 1.0f - mfac_min(mfac_max(ch, 0.0f), 1.0f);
+    const float k5 = ((x * x) * (x * x)) * x;
+    const f3 F = F0 + (mk3(1.0f) - F0) * k5;                                // 8
+    if (coat && !(g.next() < F.x)) return RT_MFAC_BASE;
+    const f3 w = M * (2.0f * ch) - v;                                       // 9
+    const float ci = dot(N, w);
+    if (!(ci > 0.0f)) return RT_MFAC_ABSORBED;
+    const float ci2 = ci * ci;
+    const float Gm = 2.0f / (1.0f + sqrtf(1.0f + ((a * a) * mfac_max(1.0f - ci2, 0.0f)) / ci2));
+    out_dir = w;
+    out_weight = coat ? mk3(Gm) : F * Gm;
+    return RT_MFAC_SPECULAR;
+}
+
 // Environment maps (rt06.h: rt_scene_set_environment): what a ray that leaves the world sees.  d = the ray's direction (any length), texels =
 // width x height records (r, g, b, -), row 0 at the top, u0 in [0, 1) = the rotation about y.  image_value's map and constants, the rotation added to u, then
 // image_texel's rule; the clamps are written so that a NaN coordinate lands on texel 0 on host and device alike.  Only + - * / sqrt, comparisons and the two rt_

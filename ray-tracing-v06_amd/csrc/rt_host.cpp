@@ -173,6 +173,8 @@ struct rt_scene {
     mutable std::vector<uint8_t> table_texels;
     std::vector<rt_normal_map> nmaps;    // normal maps: a record per material, grown on demand (a material behind its end has none)
     mutable std::vector<rt_normal_map> nmap_table;   // what rt_scene_normal_maps last handed out
+    std::vector<rt_microfacet> mfacs;    // microfacet surfaces: likewise
+    mutable std::vector<rt_microfacet> mfac_table;
     std::vector<rt_bvh_node> nodes;     // world nodes (BVH or bvh_node tree)
     std::vector<rt_bvh_node> tree_nodes;  // bvh_node objects created by rt_scene_add_bvh_node
     uint32_t kind = RT_WORLD_LIST;
@@ -1041,6 +1043,50 @@ extern "C" int rt_scene_normal_maps(const rt_scene* s, const rt_normal_map** out
     s->nmap_table = s->nmaps;
     s->nmap_table.resize(s->mats.size(), rt_normal_map{0u, 0u, 0.0f, 0u});
     *out = s->nmap_table.data(); *out_n = (uint32_t)s->nmap_table.size();
+    return RT_OK;
+}
+
+// ---- microfacet surfaces ----
+extern "C" int rt_scene_set_microfacet(rt_scene* s, uint32_t material, float roughness, float specular) {
+    if (!s) return rt_fail(RT_ERR_INVALID, "rt_scene_set_microfacet: null scene");
+    if (material >= s->mats.size()) return rt_fail(RT_ERR_INVALID, "rt_scene_set_microfacet: the scene has no material %u", material);
+    const uint32_t type = s->mats[material].type;
+    if (type == RT_MAT_DIELECTRIC || type == RT_MAT_DIFFUSE_LIGHT || type == RT_MAT_ISOTROPIC)
+        return rt_fail(RT_ERR_INVALID, "rt_scene_set_microfacet: material %u is a dielectric, a light or a medium; a metal becomes a rough conductor, and Lambertian (plain, checker, noise, image) materials take a coat", material);
+    if (!(std::isfinite(roughness) && roughness >= 0.0f && roughness <= 1.0f)) return rt_fail(RT_ERR_INVALID, "rt_scene_set_microfacet: a roughness must be finite and in [0, 1]");
+    if (!(std::isfinite(specular) && specular >= 0.0f && specular <= 1.0f)) return rt_fail(RT_ERR_INVALID, "rt_scene_set_microfacet: a specular must be finite and in [0, 1]");
+    if (s->mfacs.size() <= material) s->mfacs.resize((size_t)material + 1u, rt_microfacet{RT_MICROFACET_OFF, 0u, 0.0f, 0.0f});
+    rt_microfacet& m = s->mfacs[material];
+    if (m.on != RT_MICROFACET_MAPPED) m = rt_microfacet{RT_MICROFACET_CONSTANT, 0u, 0.0f, 0.0f};
+    m.roughness = roughness; m.specular = specular;
+    return RT_OK;
+}
+extern "C" int rt_scene_set_roughness_map(rt_scene* s, uint32_t material, uint32_t image) {
+    if (!s) return rt_fail(RT_ERR_INVALID, "rt_scene_set_roughness_map: null scene");
+    if (material >= s->mats.size()) return rt_fail(RT_ERR_INVALID, "rt_scene_set_roughness_map: the scene has no material %u", material);
+    if (material >= s->mfacs.size() || s->mfacs[material].on == RT_MICROFACET_OFF)
+        return rt_fail(RT_ERR_INVALID, "rt_scene_set_roughness_map: material %u has no microfacet record; give it one with rt_scene_set_microfacet first", material);
+    if (image >= RT_MAX_IMAGES) return rt_fail(RT_ERR_INVALID, "rt_scene_set_roughness_map: an image index lies in [0, %u), not %u", RT_MAX_IMAGES, image);
+    s->mfacs[material].on = RT_MICROFACET_MAPPED;
+    s->mfacs[material].image = image;
+    return RT_OK;
+}
+extern "C" int rt_scene_clear_microfacet(rt_scene* s, uint32_t material) {
+    if (!s) return rt_fail(RT_ERR_INVALID, "rt_scene_clear_microfacet: null scene");
+    if (material >= s->mats.size()) return rt_fail(RT_ERR_INVALID, "rt_scene_clear_microfacet: the scene has no material %u", material);
+    if (material < s->mfacs.size()) s->mfacs[material] = rt_microfacet{RT_MICROFACET_OFF, 0u, 0.0f, 0.0f};
+    return RT_OK;
+}
+extern "C" int rt_scene_microfacets(const rt_scene* s, const rt_microfacet** out, uint32_t* out_n) {
+    if (!s || !out || !out_n) return rt_fail(RT_ERR_INVALID, "rt_scene_microfacets: null argument");
+    *out = nullptr; *out_n = 0u;
+    s->mfac_table.clear();
+    bool any = false;
+    for (const rt_microfacet& m : s->mfacs) any = any || m.on != RT_MICROFACET_OFF;
+    if (!any) return RT_OK;
+    s->mfac_table = s->mfacs;
+    s->mfac_table.resize(s->mats.size(), rt_microfacet{RT_MICROFACET_OFF, 0u, 0.0f, 0.0f});
+    *out = s->mfac_table.data(); *out_n = (uint32_t)s->mfac_table.size();
     return RT_OK;
 }
 

@@ -323,6 +323,20 @@ extern "C" int rt_multi_renderer_normal_maps_info(rt_multi_renderer* m, uint32_t
     return rt_renderer_normal_maps_info(m->parts[0], out);
 }
 
+extern "C" int rt_multi_renderer_microfacets(rt_multi_renderer* m, const rt_microfacet* table, uint32_t n) {
+    if (!m) return rt_fail(RT_ERR_INVALID, "rt_multi_renderer_microfacets: null renderer");
+    for (rt_renderer* r : m->parts) {   // every rank holds the same world: the first refuses what any would, before any part changes
+        const int rc = rt_renderer_microfacets(r, table, n);
+        if (rc != RT_OK) return rc;
+    }
+    return RT_OK;
+}
+
+extern "C" int rt_multi_renderer_microfacets_info(rt_multi_renderer* m, uint32_t out[2]) {   // every rank holds the same table: rank 0 answers
+    if (!m || !out || m->parts.empty()) return rt_fail(RT_ERR_INVALID, "rt_multi_renderer_microfacets_info: null argument");
+    return rt_renderer_microfacets_info(m->parts[0], out);
+}
+
 extern "C" int rt_multi_renderer_download(rt_multi_renderer* m, float* host_rgba, size_t n_floats) {
     if (!m || !host_rgba) return rt_fail(RT_ERR_INVALID, "rt_multi_renderer_download: null argument");
     const size_t need = (size_t)m->width * m->height * 4;

@@ -142,9 +142,9 @@ __global__ void probe_sphere_hit_kernel(size_t n, const rt_prim* prims, const rt
 struct TapeRng {
     const uint32_t* k;
     uint32_t n, draws;
-    __device__ uint32_t take() { const uint32_t v = draws < n ? k[draws] : 0x800001u; draws++; return v; }
-    __device__ float next() { return (float)take() * 5.9604644775390625e-08f; }
-    __device__ float next_signed() { return (float)(int32_t)(take() - 0x800000u) * 1.1920928955078125e-07f; }
+    RT_HD uint32_t take() { const uint32_t v = draws < n ? k[draws] : 0x800001u; draws++; return v; }
+    RT_HD float next() { return (float)take() * 5.9604644775390625e-08f; }
+    RT_HD float next_signed() { return (float)(int32_t)(take() - 0x800000u) * 1.1920928955078125e-07f; }
 };
 // How the generator of case i is made: a seeded Rng from (pixel, sample) keys, or a TapeRng from a tape and (offset, length) pairs
 struct KeyedRng {
@@ -182,6 +182,22 @@ __global__ void probe_camera_kernel(MakeRng make_rng, rt_camera cam, size_t n, c
     Ray r = camera_sample_ray(cam, st[2 * i], st[2 * i + 1], g);
     st3(out_rays + 7 * i, r.o); st3(out_rays + 7 * i + 3, r.d); out_rays[7 * i + 6] = r.time;
     draws[i] = g.draws;
+}
+// the microfacet rule (microfacet_scatter) on one case with its tape: what rt_microfacet_batch runs on the host and the probe one lane each
+RT_HD void microfacet_case(size_t i, const float* normal, const float* ray_d, const float* roughness, const float* f0, const uint32_t* coat, const uint32_t* tape,
+                           const uint32_t* offsets, float* out_dir, float* out_weight, uint32_t* out_path, uint32_t* out_draws) {
+    TapeRng g{tape + offsets[2 * i], offsets[2 * i + 1], 0u};
+    f3 dir = mk3(0.0f), weight = mk3(0.0f);
+    const bool is_coat = coat[i] != 0u;
+    out_path[i] = microfacet_scatter(ld3(normal + 3 * i), ld3(ray_d + 3 * i), roughness[i], is_coat ? mk3(f0[3 * i]) : ld3(f0 + 3 * i), is_coat, g, dir, weight);
+    st3(out_dir + 3 * i, dir); st3(out_weight + 3 * i, weight);
+    out_draws[i] = g.draws;
+}
+__global__ void probe_microfacet_kernel(size_t n, const float* normal, const float* ray_d, const float* roughness, const float* f0, const uint32_t* coat,
+                                        const uint32_t* tape, const uint32_t* offsets, float* out_dir, float* out_weight, uint32_t* out_path, uint32_t* out_draws) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    microfacet_case(i, normal, ray_d, roughness, f0, coat, tape, offsets, out_dir, out_weight, out_path, out_draws);
 }
 __global__ void probe_radiance_kernel(DeviceWorld w, rt_camera cam, uint32_t width, uint32_t height, uint32_t max_depth,
                                       uint64_t seed, size_t n, const uint32_t* keys, float* out) {
@@ -619,6 +635,36 @@ extern "C" int rt_probe_camera_tape(int device, const rt_camera* cam, size_t n, 
     ProbeRun p(device);
     const TapedRng make_rng{p.in(tape, tape_len), p.in(offsets, 2 * n)};
     return camera_cases(p, make_rng, *cam, n, st, out_rays, out_draws);
+}
+// Microfacet surfaces: the rule over arrays of cases, on the device and — HOST (no GPU) — here
+static int microfacet_args(const char* who, size_t count, const float* normal, const float* ray_d, const float* roughness, const float* f0, const uint32_t* coat,
+                           const uint32_t* tape, size_t tape_len, const uint32_t* offsets, float* out_dir, float* out_weight, uint32_t* out_path, uint32_t* out_draws) {
+    if (!normal || !ray_d || !roughness || !f0 || !coat || !tape || !offsets || !out_dir || !out_weight || !out_path || !out_draws)
+        return rt_fail(RT_ERR_INVALID, "%s: null argument", who);
+    if (int rc = check_tape(who, count, tape_len, offsets)) return rc;
+    for (size_t i = 0; i < count; i++)
+        if (!(std::isfinite(roughness[i]) && roughness[i] >= 0.0f && roughness[i] <= 1.0f))
+            return rt_fail(RT_ERR_INVALID, "%s: case %zu: a roughness must be finite and in [0, 1]", who, i);
+    return RT_OK;
+}
+extern "C" int rt_probe_microfacet(int device, size_t count, const float* normal, const float* ray_d, const float* roughness, const float* f0, const uint32_t* coat,
+                                   const uint32_t* tape, size_t tape_len, const uint32_t* offsets, float* out_dir, float* out_weight, uint32_t* out_path,
+                                   uint32_t* out_draws) {
+    if (const int rc = microfacet_args("rt_probe_microfacet", count, normal, ray_d, roughness, f0, coat, tape, tape_len, offsets, out_dir, out_weight, out_path, out_draws)) return rc;
+    if (count == 0) return RT_OK;
+    ProbeRun p(device);
+    auto dn = p.in(normal, 3 * count); auto dd = p.in(ray_d, 3 * count); auto dr = p.in(roughness, count); auto df = p.in(f0, 3 * count); auto dc = p.in(coat, count);
+    const uint32_t no_tape = 0x800001u;   // an empty tape: every case's range is empty, and one word keeps the upload from being one of no bytes
+    auto dt = tape_len ? p.in(tape, tape_len) : p.in(&no_tape, 1); auto dof = p.in(offsets, 2 * count);
+    auto od = p.out(out_dir, 3 * count); auto ow = p.out(out_weight, 3 * count); auto op = p.out(out_path, count); auto on = p.out(out_draws, count);
+    p.launch(probe_microfacet_kernel, p.per_case(count), 128, count, dn, dd, dr, df, dc, dt, dof, od, ow, op, on);
+    return p.finish();
+}
+extern "C" int rt_microfacet_batch(size_t count, const float* normal, const float* ray_d, const float* roughness, const float* f0, const uint32_t* coat, const uint32_t* tape,
+                                   size_t tape_len, const uint32_t* offsets, float* out_dir, float* out_weight, uint32_t* out_path, uint32_t* out_draws) {
+    if (const int rc = microfacet_args("rt_microfacet_batch", count, normal, ray_d, roughness, f0, coat, tape, tape_len, offsets, out_dir, out_weight, out_path, out_draws)) return rc;
+    for (size_t i = 0; i < count; i++) microfacet_case(i, normal, ray_d, roughness, f0, coat, tape, offsets, out_dir, out_weight, out_path, out_draws);
+    return RT_OK;
 }
 extern "C" int rt_probe_radiance(const rt_render_config* cfg, const rt_camera* cam, const rt_world_flat* world, size_t n,
                                  const uint32_t* keys, float* out_radiance) {

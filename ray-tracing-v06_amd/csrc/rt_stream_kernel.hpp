@@ -264,16 +264,21 @@ __device__ __forceinline__ f3 texture_table_value(const uint4* tt, uint32_t imag
 // NMAP (rt_renderer_normal_maps; EXT == 2 && TRI only, whether or not the world has a triangle): a hit on a material whose record of the tail's
 //      normal-map table says `on` bends its normal by normal_map_apply, once, right after the flat or smooth normal is known; an image-textured hit shares its
 //      (u, v) with the map.  The table lies behind the texture table, whose header's fourth lane says where; both words are read at the hit, through scalars.
+// MFAC (rt_renderer_microfacets; NMAP only): a hit on a material whose record of the tail's microfacet table says `on` runs microfacet_scatter
+//      before the scatter branches: a metal is a rough conductor, a Lambertian kind wears a coat whose toss comes before every draw of the base.  A specular or
+//      absorbed hit takes none of the base's draws; a base or backside hit runs the code below as it stands.  The records lie last in the tail, where the bits
+//      above bit 0 of the header's first lane say; that word is read at the hit, through a scalar, and vn_on keeps bit 0 alone.
 // LTREE && ENVL (mode RT_LIGHT_SAMPLING_ENV_TREE): both at once.  The light half tosses once more between the map and mode 16's table (no toss
 //      when the table is empty: n_l == 0 is the map alone), the light density is the mean of the map's and the walk's, and an image-textured Lambertian hit is
 //      sampled as the diffuse hit it is — its albedo is looked up behind the direction, as ever.
 template <bool EXACT, bool FILTER, int BLOCK, int WORLD = RT_WORLD_BVH, int EXT = 0, bool BIG = false, bool WIDE = BIG, bool TOL = false, bool NEE = false, bool TRI = false,
-          bool LTREE = false, bool ENVL = false, bool NMAP = false>
+          bool LTREE = false, bool ENVL = false, bool MFAC = false, bool NMAP = false>
 // (the second launch bound is hipcc's minimum of waves per SIMD — 6 for 768 threads, what two workgroups per CU are, and all the LDS admits: the register budget is
 //  80, not the 64 of a full SIMD.  The default instantiation took 64 while it needed no more and takes 68 since E23, with no scratch; the occupancy the compiler
 //  reports for it, 8 and now 7, is what its register count would admit, not what the launch gets.)
 __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(StreamParams p) {
     static_assert(!NMAP || (EXT == 2 && TRI), "normal maps: one family of the kernels that read the texture table, plain and with mode 48");
+    static_assert(!MFAC || NMAP, "microfacet surfaces: a glossy asset wants its normal map in the same launch, and the roughness map shares the map's (u, v)");
     static_assert(!NEE || (EXT >= 1 && WORLD != RT_WORLD_BVH_QUEUE), "light sampling: worlds with quads, walked by the stack or as a list");
     static_assert(!TRI || (EXT >= 1 && WORLD != RT_WORLD_BVH_QUEUE), "triangles: worlds with quads; a lane walk reads the kind from the flat record");
     static_assert(!LTREE || (NEE && TRI), "the light tree: one family, which knows all three kinds of light");
@@ -312,6 +317,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
     // triangle, in global memory whatever the form of the image.  Wave-uniform; a world without a table pays this one scalar load and one scalar branch per shaded quad hit.
     uint32_t vn_on = 0u;
     if constexpr (TRI) vn_on = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.scene.blob[p.scene.blob_vec4].x);
+    if constexpr (MFAC) vn_on &= 1u;   // §29: the bits above say where the microfacet records lie; the hit reads them
     // §22, TRI with image textures (EXT >= 2) only: the same header's .y = how many vec4 behind the header the texture coordinates start (24 B per triangle), 0 = none
     uint32_t uv_at = 0u;
     if constexpr (TRI && EXT >= 2) uv_at = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.scene.blob[p.scene.blob_vec4].y);
@@ -699,15 +705,26 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                 // takes the same (u, v) — on a sphere the normal it would compute them from may just have been replaced
                 float nm_tu = 0.0f, nm_tv = 0.0f;
                 bool nm_uv = false;
+                // §29: the microfacet record of the hit's material, (on, image, roughness bits, specular bits), zero where there is none; a mapped record's
+                // roughness takes its map's green channel in the block below, which computes the (u, v) when either record needs them
+                uint4 mf_rec = make_uint4(0u, 0u, 0u, 0u);
+                float mf_rough = 0.0f;
+                if constexpr (MFAC) {
+                    const uint32_t mf_at = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.scene.blob[p.scene.blob_vec4].x) >> 1;
+                    if (mf_at != 0u) mf_rec = p.scene.blob[p.scene.blob_vec4 + mf_at + (mat_bits & RT_MAT_INDEX_MASK)];
+                    mf_rough = __uint_as_float(mf_rec.z);
+                }
                 if constexpr (NMAP) {
                     const uint32_t tex_here = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.scene.blob[p.scene.blob_vec4].w);
                     if (tex_here != 0u) {
                         const uint4* tt = p.scene.blob + p.scene.blob_vec4 + tex_here;
                         const uint4 th = tt[0];
                         const uint32_t nm_at = (uint32_t)__builtin_amdgcn_readfirstlane((int)th.w);
-                        if (nm_at != 0u) {
-                            const uint4 nr = tt[nm_at + (mat_bits & RT_MAT_INDEX_MASK)];   // (on, image, strength bits, -): per lane, lanes sit on different materials
-                            if (nr.x != 0u) {
+                        const bool mf_mapped = MFAC && mf_rec.x == RT_MICROFACET_MAPPED;
+                        if (nm_at != 0u || mf_mapped) {
+                            uint4 nr = make_uint4(0u, 0u, 0u, 0u);
+                            if (!MFAC || nm_at != 0u) nr = tt[nm_at + (mat_bits & RT_MAT_INDEX_MASK)];   // (on, image, strength bits, -): per lane, lanes sit on different materials
+                            if (nr.x != 0u || mf_mapped) {
                                 f3 dPdu, dPdv;
                                 bool frame = true;
                                 if ((uint32_t)rec_code >= p.scene.sphere_codes) {
@@ -729,9 +746,15 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                                     normal_map_sphere_tangents(normal, dPdu, dPdv);
                                 }
                                 nm_uv = true;
-                                if (frame) {
+                                if (frame && (!MFAC || nr.x != 0u)) {
                                     const uint64_t texels = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)th.x) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)th.y) << 32;
                                     normal_map_apply(texture_value(reinterpret_cast<const uint32_t*>(texels), tt[1u + nr.y], nm_tu, nm_tv), __uint_as_float(nr.z), dPdu, dPdv, ray.d, normal);
+                                }
+                                if constexpr (MFAC) {
+                                    if (mf_mapped) {   // §29: the roughness map, at the same (u, v)
+                                        const uint64_t texels = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)th.x) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)th.y) << 32;
+                                        mf_rough = microfacet_roughness(mf_rough, texture_value(reinterpret_cast<const uint32_t*>(texels), tt[1u + mf_rec.y], nm_tu, nm_tv));
+                                    }
                                 }
                             }
                         }
@@ -778,6 +801,20 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                     else scatter_dir = refract(unit_dir, normal, ior_ratio);
                 } else {
                     RT_PT(11);
+                    // §29: a material with a microfacet record — a metal as a rough conductor with F0 = its albedo, the Lambertian kinds under a coat — before any
+                    // draw of the base.  Specular: the direction and the factor of the throughput are the rule's; absorbed: a failed scatter.  Otherwise (the coat's
+                    // toss fell to the base, or the surface is seen from behind) everything below runs as if there were no record.
+                    bool mf_done = false;
+                    if constexpr (MFAC) {
+                        if (mf_rec.x != 0u) {
+                            const bool coat = mtype != RT_MAT_METAL;
+                            f3 mf_weight = mk3(0.0f);
+                            const uint32_t way = microfacet_scatter(normal, ray.d, mf_rough, coat ? mk3(__uint_as_float(mf_rec.w)) : albedo, coat, rng, scatter_dir, mf_weight);
+                            if (way == RT_MFAC_SPECULAR) { albedo = mf_weight; mf_done = true; }
+                            else if (way == RT_MFAC_ABSORBED) { scattered_ok = false; mf_done = true; }
+                        }
+                    }
+                    if (!(MFAC && mf_done)) {
                     // NEE: the first draw of a Lambertian / checker hit picks the half of the mixture; the light half draws no on-unit vector
                     const bool nee_mat = NEE && (mtype == RT_MAT_LAMBERTIAN || mtype == RT_MAT_LAMBERTIAN_CHECKER || (ENVT && mtype == RT_MAT_LAMBERTIAN_IMAGE));
                     const bool to_light = nee_mat && rng.next() < 0.5f;
@@ -992,6 +1029,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                             else albedo = image_texel(p.scene.image, p.scene.image_w, p.scene.image_h, tu, tv);
                         }
                     }
+                    }   // (§29: not a specular or absorbed microfacet hit)
                 }
                 RT_PT(13);
                 if (!scattered_ok) {

@@ -172,7 +172,8 @@ def load_mtl(path):
     """`newmtl`, `Kd` and `map_Kd` of a Wavefront MTL file: {name: {"Kd": (r, g, b) | None, "map_Kd": path | None}} in the file's order; the image's name is
     resolved beside the file, options in front of it (-s, -o, ...) are skipped.  `norm`, `map_Bump`, `map_bump` and `bump` name the material's normal map
     (the file is taken as a tangent-space normal map, OpenGL convention, green = +v): "normal_map": path | None and "normal_strength": the `-bm X`
-    in front of the name, 1.0 without one; the last such line of a material counts.  Nothing else of MTL is read."""
+    in front of the name, 1.0 without one; the last such line of a material counts.  The PBR extension's `Pr`, `map_Pr` and `Pm` become
+    "roughness": float | None, "roughness_map": path | None and "metallic": float | None.  Nothing else of MTL is read."""
     import os
     out, current = {}, None
     beside = lambda name: os.path.join(os.path.dirname(os.path.abspath(path)), *name.replace("\\", "/").split("/"))
@@ -185,7 +186,8 @@ def load_mtl(path):
             if parts[0] == "newmtl":
                 if len(parts) < 2:
                     raise ValueError(f"{where}: newmtl needs a name")
-                current = out.setdefault(parts[1], {"Kd": None, "map_Kd": None, "normal_map": None, "normal_strength": 1.0})
+                current = out.setdefault(parts[1], {"Kd": None, "map_Kd": None, "normal_map": None, "normal_strength": 1.0, "roughness": None, "roughness_map": None,
+                                                    "metallic": None})
             elif parts[0] in ("norm", "map_Bump", "map_bump", "bump"):
                 if current is None:
                     raise ValueError(f"{where}: {parts[0]} before any newmtl")
@@ -200,6 +202,18 @@ def load_mtl(path):
                     if not (np.isfinite(strength) and strength >= 0.0):
                         raise ValueError(f"{where}: -bm must be finite and >= 0")
                 current["normal_map"], current["normal_strength"] = beside(parts[-1]), strength
+            elif parts[0] in ("Pr", "Pm", "map_Pr"):
+                if current is None:
+                    raise ValueError(f"{where}: {parts[0]} before any newmtl")
+                if len(parts) < 2:
+                    raise ValueError(f"{where}: {parts[0]} needs a {'file name' if parts[0] == 'map_Pr' else 'value'}")
+                if parts[0] == "map_Pr":
+                    current["roughness_map"] = beside(parts[-1])
+                else:
+                    value = float(parts[1])
+                    if not (np.isfinite(value) and 0.0 <= value <= 1.0):
+                        raise ValueError(f"{where}: {parts[0]} must be finite and in [0, 1]")
+                    current["roughness" if parts[0] == "Pr" else "metallic"] = value
             elif parts[0] in ("Kd", "map_Kd"):
                 if current is None:
                     raise ValueError(f"{where}: {parts[0]} before any newmtl")

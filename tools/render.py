@@ -55,7 +55,9 @@ world's lights together (RT_LIGHT_SAMPLING_ENV_TREE), and sample
         --mesh-scale 120 --mesh-translate 150,160,120 --spp 64 --out out.png
 
 renders each `usemtl` group of the OBJ as a mesh of its own with the image its material's map_Kd names (the scene's texture table): here the
-book's earth sphere (image 0), a floor whose `vt` run to 4 — tiled under --texture-wrap repeat — and a UV-mapped pyramid, both filtered bilinearly.
+book's earth sphere (image 0), a floor whose `vt` run to 4 — tiled under --texture-wrap repeat — and a UV-mapped pyramid, both filtered bilinearly.  A material's
+`Pm`, `Pr` and `map_Pr` are applied too: `Pm >= 0.5` makes the group a metal with `Kd` as F0; `Pr` or `map_Pr` gives it a microfacet record — a rough
+conductor on the metal, a coat of specular 0.04 on anything else —, `map_Pr` scaling the roughness by the image's green channel.
 """
 import argparse, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -168,10 +170,22 @@ if a.mesh:
             if picture and uvs is None:
                 sys.exit(f"--mtl: material {name!r} has an image and {a.mesh} has no complete set of texture coordinates")
             mat = image_material(picture) if picture else scene.Lambertian(entry["Kd"]) if entry["Kd"] else plain()
+            # microfacet surfaces: Pm >= 0.5 makes the group a metal with Kd as F0; Pr or map_Pr gives it a record — a rough conductor on the
+            # metal, a coat of specular 0.04 on anything else — and map_Pr scales the roughness by the image's green channel (Pr = 1 when the file has none)
+            roughness, roughness_map, metallic = entry.get("roughness"), entry.get("roughness_map"), entry.get("metallic")
+            if metallic is not None and metallic >= 0.5:
+                mat, picture = scene.Metal(entry["Kd"] or (0.8, 0.85, 0.88), 0.0), None
+            if roughness is not None or roughness_map:
+                scene.set_microfacet(mat, 1.0 if roughness is None else roughness, 0.04)
+                if roughness_map:
+                    if uvs is None:
+                        sys.exit(f"--mtl: material {name!r} has a roughness map and {a.mesh} has no complete set of texture coordinates")
+                    scene.set_roughness_map(mat, scene.add_image(read_image(roughness_map), a.texture_wrap, a.texture_filter))
             group_normals = dict(normals=normals, normal_faces=normal_faces[rows] if normal_faces is not None else faces[rows]) if normals is not None else {}
-            group_uvs = dict(uvs=uvs, uv_faces=uv_faces[rows]) if picture else {}
+            group_uvs = dict(uvs=uvs, uv_faces=uv_faces[rows]) if picture or roughness_map else {}
             added += scene.MakeMesh(vertices, faces[rows], mat, **place, **group_normals, **group_uvs)[1]
-            print(json.dumps({"material": name, "triangles": len(rows), "image": picture, "Kd": entry["Kd"]}), flush=True)
+            print(json.dumps({"material": name, "triangles": len(rows), "image": picture, "Kd": entry["Kd"], "roughness": roughness, "roughness_map": roughness_map,
+                              "metallic": metallic}), flush=True)
     else:
         mat = image_material(a.texture[0]) if a.texture else plain()
         first, added = scene.MakeMesh(vertices, faces, mat, **place, normals=normals, normal_faces=normal_faces, uvs=uvs, uv_faces=uv_faces)
