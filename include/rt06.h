@@ -422,7 +422,7 @@ int rt_normal_map_batch(const rt_texture* records, uint32_t n, const uint8_t* te
  *      G alone (coat: the toss already paid F); no light-sampling weight applies.
  * normalize(x) = x (1 / sqrt(dot(x, x))); max(x, c) = x > c ? x : c and min(x, c) = x < c ? x : c, so a NaN takes c.  Only fp32 + - * / sqrt and comparisons, each
  * rounded on its own, no FMA.  A material without a record changes no bit of any frame; roughness 0 is no special case.  Not done: anisotropy, the height-
- * correlated masking term, multiple-scattering compensation, rough refraction and records on glass, sampling the lobe towards lights, metallic maps.        */
+ * correlated masking term, multiple-scattering compensation, sampling the lobe towards lights, metallic maps.  Rough refraction has kinds of its own, below. */
 typedef struct rt_microfacet { uint32_t on, image; float roughness, specular; } rt_microfacet;   /* 16 B, one per material */
 enum { RT_MICROFACET_OFF = 0, RT_MICROFACET_CONSTANT = 1, RT_MICROFACET_MAPPED = 2 };
 /* Gives `material` a constant-roughness record.  RT_ERR_INVALID, scene unchanged: no such material; a dielectric, a light or an isotropic material; a roughness
@@ -443,6 +443,31 @@ enum { RT_MFAC_SPECULAR = 1, RT_MFAC_BASE = 2, RT_MFAC_ABSORBED = 3, RT_MFAC_BAC
  * RT_ERR_INVALID: a null argument, a tape range outside the tape, a roughness out of range.                                                                    */
 int rt_microfacet_batch(size_t count, const float* normal, const float* ray_d, const float* roughness, const float* f0, const uint32_t* coat, const uint32_t* tape,
                         size_t tape_len, const uint32_t* offsets, float* out_dir, float* out_weight, uint32_t* out_path, uint32_t* out_draws);
+/* ---- rough glass (not in the reference): the same lobe on RT_MAT_DIELECTRIC, reflecting or refracting about a micro-normal.  Record kinds of its
+ * own in the same table: on == RT_MICROFACET_GLASS, a constant roughness, and RT_MICROFACET_GLASS_MAPPED, the roughness scaled by the green channel of entry
+ * `image` as RT_MICROFACET_MAPPED scales it; specular is stored as 0 and not read.  The rule, with N = the normal the shade phase holds, d = the ray's direction,
+ * r = the roughness, ior = the material's index of refraction, G = the hit's generator:
+ *   1  back = dot(d, N) > 0;  n = back ? -N : N;  eta = back ? ior : 1 / ior                       (the smooth dielectric's own expressions)
+ *   2  v = -d / sqrt(dot(d, d));  co = dot(n, v);  !(co > 0): RT_MFAC_BASE, the smooth dielectric runs verbatim, with its draws
+ *   3  M = steps 2 to 7 of the rule above with n for N (the same draws), up to and including M;  ch = dot(v, M)
+ *   4  x = 1 - min(max(ch, 0), 1);  r0 = (1 - eta) / (1 + eta);  r0 = r0 r0;  F = r0 + (1 - r0) (((x x) (x x)) x)     (the library's Schlick term, with the ratio)
+ *   5  k = 1 - (eta eta) (1 - ch ch);  !(k >= 0): the reflection is total and no uniform is drawn;  otherwise one uniform u, and the hit reflects exactly when F > u
+ *   6  reflect:  w = M (2 ch) - v;  ci = dot(n, w);  !(ci > 0): RT_MFAC_ABSORBED;  otherwise RT_MFAC_SPECULAR
+ *   7  transmit: w = (-v) eta - M (eta (-ch) + sqrt(k))   (refract(-v, M, eta));  ci = -dot(n, w);  !(ci > 0): RT_MFAC_ABSORBED;  otherwise RT_MFAC_TRANSMITTED
+ *      either way the direction is w and the throughput is multiplied by the material's albedo times G = 2 / (1 + sqrt(1 + ((a a) max(0, 1 - ci ci)) / (ci ci))):
+ *      the toss paid F or 1 - F, the visible-normal draw paid the masking of v and the Jacobians.  No eta^2 radiance scaling, as the book's glass applies none.
+ * The same arithmetic rules as above.  On parallelograms and triangles the shading normal always faces the ray, so such glass is always entered, as smooth glass on
+ * them is.  Not done: tinted transmission, normal maps on glass, the eta^2 scaling.                                                                              */
+enum { RT_MICROFACET_GLASS = 4, RT_MICROFACET_GLASS_MAPPED = 6 };
+enum { RT_MFAC_TRANSMITTED = 5 };
+/* Gives `material`, an RT_MAT_DIELECTRIC, a rough-glass record of constant roughness.  RT_ERR_INVALID, scene unchanged: no such material; any other type of
+ * material; a roughness that is not finite or lies outside [0, 1].  A record that is already mapped keeps its map.  rt_scene_set_roughness_map on a material
+ * with a glass record makes it RT_MICROFACET_GLASS_MAPPED; rt_scene_clear_microfacet clears it.                                                               */
+int rt_scene_set_rough_glass(rt_scene* s, uint32_t material, float roughness);
+/* HOST (no GPU): the rule on `count` cases, as rt_microfacet_batch runs its own — per case N, d, the roughness (finite, in [0, 1]), the index of refraction and
+ * a tape -> out_dir[3 i ..] (w; zero unless specular or transmitted), out_weight[i] (G; zero likewise), out_path[i] = RT_MFAC_*, out_draws[i].               */
+int rt_rough_glass_batch(size_t count, const float* normal, const float* ray_d, const float* roughness, const float* ior, const uint32_t* tape, size_t tape_len,
+                         const uint32_t* offsets, float* out_dir, float* out_weight, uint32_t* out_path, uint32_t* out_draws);
 
 /* BVH_Handle::Factory::BuildBVH_TopDown -> _build_bvh_rec1 (BVH.cu:166-210):
  * median split on the longest axis, leaf size 1, post-order numbering, root =
@@ -902,7 +927,8 @@ int rt_renderer_normal_maps_info(rt_renderer* r, uint32_t out[2]);
  * `on`, an image index past RT_MAX_IMAGES, or a roughness or specular that is not finite and in [0, 1]; kernel variants 1, 5 and 6; a world with a queue or wide4
  * traversal, or a bvh_node tree; light-sampling modes 1, 2, 4, 16 and 32 (rt_renderer_light_sampling_enable refuses them in turn while a table is on).
  * rt_renderer_render, the refine calls and their async forms return RT_ERR_INVALID and launch nothing while a mapped record names an entry the renderer's texture
- * table (rt_renderer_textures) does not have.                                                                                                                  */
+ * table (rt_renderer_textures) does not have.  Rough glass (§30): on == RT_MICROFACET_GLASS and RT_MICROFACET_GLASS_MAPPED are accepted on dielectrics alone, with a
+ * specular of 0, and refused in words of their own elsewhere; the mapped kind's entry is checked at launch like the other's.                                 */
 int rt_renderer_microfacets(rt_renderer* r, const rt_microfacet* table, uint32_t n);
 /* out[0] = 1 while a table is on, out[1] = how many of its records are on */
 int rt_renderer_microfacets_info(rt_renderer* r, uint32_t out[2]);
@@ -995,6 +1021,9 @@ int rt_probe_normal_map(int device, const rt_texture* records, uint32_t n, const
 /* rt_microfacet_batch on the device, one lane per case                                                                                                        */
 int rt_probe_microfacet(int device, size_t count, const float* normal, const float* ray_d, const float* roughness, const float* f0, const uint32_t* coat,
                         const uint32_t* tape, size_t tape_len, const uint32_t* offsets, float* out_dir, float* out_weight, uint32_t* out_path, uint32_t* out_draws);
+/* rt_rough_glass_batch on the device, one lane per case                                                                                                       */
+int rt_probe_rough_glass(int device, size_t count, const float* normal, const float* ray_d, const float* roughness, const float* ior, const uint32_t* tape,
+                         size_t tape_len, const uint32_t* offsets, float* out_dir, float* out_weight, uint32_t* out_path, uint32_t* out_draws);
 /* rt_noise_value_batch on the device, one lane per point: the tables in global memory, as the renderer holds them                                              */
 int rt_probe_noise_value(int device, const rt_perlin* perlin, const float albedo[3], float scale, const float* points, size_t n, float* out_rgb);
 /* rt_environment_sample_batch on the device, one lane per quadruple: the records and the tables as the renderer holds them in mode RT_LIGHT_SAMPLING_ENV        */

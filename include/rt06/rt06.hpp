@@ -379,6 +379,9 @@ public:
     // microfacet surfaces (extension; rt_scene_set_microfacet): a metal material becomes a rough GGX conductor, a Lambertian kind gets a glossy
     // coat of F0 = specular; a roughness map scales the record's roughness by the green channel of image `image`; the table as rt_scene_microfacets hands it out
     void SetMicrofacet(uint32_t material, float roughness, float specular = 0.04f) { check(rt_scene_set_microfacet(s_, material, roughness, specular), "rt_scene_set_microfacet"); }
+    // rough glass (extension; rt_scene_set_rough_glass): a dielectric material reflects and refracts about GGX micro-normals; SetRoughnessMap
+    // scales its roughness too, ClearMicrofacet makes it clear glass again
+    void SetRoughGlass(uint32_t material, float roughness) { check(rt_scene_set_rough_glass(s_, material, roughness), "rt_scene_set_rough_glass"); }
     void SetRoughnessMap(uint32_t material, uint32_t image) { check(rt_scene_set_roughness_map(s_, material, image), "rt_scene_set_roughness_map"); }
     void ClearMicrofacet(uint32_t material) { check(rt_scene_clear_microfacet(s_, material), "rt_scene_clear_microfacet"); }
     uint32_t Microfacets(const rt_microfacet** out) const {
@@ -647,7 +650,7 @@ class Renderer {
             uint32_t n_mfacs = 0;
             rt06::check(rt_scene_microfacets(static_cast<const BVH*>(world)->scene, &mfacs, &n_mfacs), "rt_scene_microfacets");
             bool roughness_mapped = false;
-            for (uint32_t i = 0; i < n_mfacs; i++) roughness_mapped = roughness_mapped || mfacs[i].on == RT_MICROFACET_MAPPED;
+            for (uint32_t i = 0; i < n_mfacs; i++) roughness_mapped = roughness_mapped || mfacs[i].on == RT_MICROFACET_MAPPED || mfacs[i].on == RT_MICROFACET_GLASS_MAPPED;
             if (table_says_more || ((n_nmaps || roughness_mapped) && n_tex)) made.SetTextures(tex, n_tex, texels);
             if (n_nmaps) made.SetNormalMaps(nmaps, n_nmaps);
             if (n_mfacs) made.SetMicrofacets(mfacs, n_mfacs);

@@ -185,8 +185,14 @@ class Scene:
         return self
 
     def set_roughness_map(self, material, image):
-        """The green channel of image `image` of the scene scales the roughness of `material`'s record (rt_scene_set_roughness_map; set_microfacet first)."""
+        """The green channel of image `image` of the scene scales the roughness of `material`'s record (rt_scene_set_roughness_map; set_microfacet or, on glass, set_rough_glass first)."""
         check(lib().rt_scene_set_roughness_map(self.h, material, image))
+        return self
+
+    def set_rough_glass(self, material, roughness):
+        """Gives `material`, a Dielectric, a rough-glass record (extension; rt_scene_set_rough_glass): it reflects and refracts about GGX
+        micro-normals of that roughness.  set_roughness_map then scales the roughness by an image's green channel; clear_microfacet makes it clear glass again."""
+        check(lib().rt_scene_set_rough_glass(self.h, material, float(roughness)))
         return self
 
     def clear_microfacet(self, material):
@@ -406,7 +412,7 @@ class Scene:
         mfacs = self.microfacets()            # likewise the microfacet records; the texture table only with a roughness map
         if mfacs is not None:
             w.microfacets = mfacs
-            if table is not None and (mfacs["on"] == capi.MICROFACET_MAPPED).any():
+            if table is not None and np.isin(mfacs["on"], (capi.MICROFACET_MAPPED, capi.MICROFACET_GLASS_MAPPED)).any():
                 w.textures = table
         return w
 
@@ -1306,6 +1312,40 @@ def microfacet_batch(normal, ray_d, roughness, f0, coat, tapes):
 def probe_microfacet(normal, ray_d, roughness, f0, coat, tapes, device=0):
     """rt_probe_microfacet: microfacet_batch on the device, one lane per case"""
     return _microfacet(lambda *args: lib().rt_probe_microfacet(device, *args), normal, ray_d, roughness, f0, coat, tapes)
+
+
+def _rough_glass(fn, normal, ray_d, roughness, ior, tapes):
+    normal, ray_d = (np.ascontiguousarray(x, np.float32).reshape(-1, 3) for x in (normal, ray_d))
+    roughness, ior = (np.ascontiguousarray(x, np.float32).reshape(-1) for x in (roughness, ior))
+    n = len(roughness)
+    if not all(len(x) == n for x in (normal, ray_d, ior, tapes)):
+        raise ValueError("rough glass: every array must have one entry per case")
+    offsets = np.zeros((n, 2), np.uint32)
+    if isinstance(tapes, np.ndarray) and tapes.ndim == 2:   # tapes of one length, as one array: a million cases need no million arrays
+        offsets[:, 1] = tapes.shape[1]
+        offsets[:, 0] = np.arange(n, dtype=np.uint64) * tapes.shape[1]
+        words = [np.ascontiguousarray(tapes, np.uint32).reshape(-1)]
+    else:
+        lengths = np.array([len(t) for t in tapes], np.uint32)
+        offsets[:, 1] = lengths
+        offsets[1:, 0] = np.cumsum(lengths, dtype=np.uint64)[:-1]
+        words = [np.asarray(t, np.uint32) for t in tapes]
+    tape = np.ascontiguousarray(np.concatenate(words + [np.array([0x800001], np.uint32)]), np.uint32)
+    out_dir, weight, path, draws = np.zeros((n, 3), np.float32), np.zeros(n, np.float32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+    check(fn(n, normal, ray_d, roughness, ior, tape, len(tape), offsets, out_dir, weight, path, draws))
+    return out_dir, weight, path, draws
+
+
+def rough_glass_batch(normal, ray_d, roughness, ior, tapes):
+    """rt_rough_glass_batch (host only): the rough-glass rule on n cases — per case the normal, the ray's direction, the roughness, the index of
+    refraction, and tapes[i] = its uniforms as words k in [1, 2^24] (a list of arrays, or one (n, L) array) -> (directions (n, 3), weights (n,), path (n,) of
+    capi.MFAC_*, uniforms consumed (n,))"""
+    return _rough_glass(lib().rt_rough_glass_batch, normal, ray_d, roughness, ior, tapes)
+
+
+def probe_rough_glass(normal, ray_d, roughness, ior, tapes, device=0):
+    """rt_probe_rough_glass: rough_glass_batch on the device, one lane per case"""
+    return _rough_glass(lambda *args: lib().rt_probe_rough_glass(device, *args), normal, ray_d, roughness, ior, tapes)
 
 
 def _noise_value(fn, world, albedo, scale, points):

@@ -39,6 +39,7 @@ NMAP_REPLACED, NMAP_FLAT, NMAP_NO_TANGENT, NMAP_NO_LENGTH, NMAP_FACING, NMAP_NO_
 MICROFACET_DT = np.dtype([("on", "<u4"), ("image", "<u4"), ("roughness", "<f4"), ("specular", "<f4")])   # rt_microfacet, 16 B
 MICROFACET_OFF, MICROFACET_CONSTANT, MICROFACET_MAPPED = 0, 1, 2
 MFAC_SPECULAR, MFAC_BASE, MFAC_ABSORBED, MFAC_BACKSIDE = 1, 2, 3, 4
+MICROFACET_GLASS, MICROFACET_GLASS_MAPPED, MFAC_TRANSMITTED = 4, 6, 5   # rough glass
 WRAP_CLAMP, WRAP_REPEAT = 0, 1
 FILTER_NEAREST, FILTER_BILINEAR = 0, 1
 MAX_IMAGES = 256
@@ -115,6 +116,7 @@ SYMBOLS = [
     "rt_renderer_normal_maps", "rt_renderer_normal_maps_info", "rt_renderer_kernel_normal_map", "rt_multi_renderer_normal_maps", "rt_multi_renderer_normal_maps_info",
     "rt_scene_set_microfacet", "rt_scene_set_roughness_map", "rt_scene_clear_microfacet", "rt_scene_microfacets", "rt_microfacet_batch", "rt_probe_microfacet",
     "rt_renderer_microfacets", "rt_renderer_microfacets_info", "rt_renderer_kernel_microfacet", "rt_multi_renderer_microfacets", "rt_multi_renderer_microfacets_info",
+    "rt_scene_set_rough_glass", "rt_rough_glass_batch", "rt_probe_rough_glass",
 ]
 
 _lib = None
@@ -252,6 +254,9 @@ def lib():
     L.rt_scene_microfacets.argtypes = [C.c_void_p, P(C.c_void_p), P(C.c_uint32)]
     L.rt_microfacet_batch.argtypes = [C.c_size_t, f32p, f32p, f32p, f32p, u32p, u32p, C.c_size_t, u32p, f32p, f32p, u32p, u32p]
     L.rt_probe_microfacet.argtypes = [C.c_int] + L.rt_microfacet_batch.argtypes
+    L.rt_scene_set_rough_glass.argtypes = [C.c_void_p, C.c_uint32, C.c_float]
+    L.rt_rough_glass_batch.argtypes = [C.c_size_t, f32p, f32p, f32p, f32p, u32p, C.c_size_t, u32p, f32p, f32p, u32p, u32p]
+    L.rt_probe_rough_glass.argtypes = [C.c_int] + L.rt_rough_glass_batch.argtypes
     L.rt_renderer_microfacets.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     L.rt_renderer_microfacets_info.argtypes = [C.c_void_p, C.c_uint32 * 2]
     L.rt_renderer_kernel_microfacet.argtypes = [C.c_void_p, P(C.c_uint32)]

@@ -353,7 +353,7 @@ struct rt_renderer {
     bool roughness_map_entry_missing(uint32_t* which) const {
         if (!mf.on) return false;
         for (const rt_microfacet& m : mf.host)
-            if (m.on == RT_MICROFACET_MAPPED && (!tex.on || m.image >= tex.records.size() || tex.records[m.image].width == 0u)) { *which = m.image; return true; }
+            if ((m.on == RT_MICROFACET_MAPPED || m.on == RT_MICROFACET_GLASS_MAPPED) && (!tex.on || m.image >= tex.records.size() || tex.records[m.image].width == 0u)) { *which = m.image; return true; }
         return false;
     }
     // whether a launch is refused for its image materials (§25): one of them names an entry (*which) the renderer does not have
@@ -1310,6 +1310,15 @@ extern "C" int rt_renderer_microfacets(rt_renderer* r, const rt_microfacet* tabl
         if (n != r->scene.dw.n_mats) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: %u records for a world of %u materials", n, r->scene.dw.n_mats);
         for (uint32_t i = 0; i < n; i++) {
             if (table[i].on == RT_MICROFACET_OFF) continue;
+            const bool glass = table[i].on == RT_MICROFACET_GLASS || table[i].on == RT_MICROFACET_GLASS_MAPPED;   // §30: kinds of their own, on dielectrics alone
+            if (glass) {
+                if (r->scene.mat_types[i] != RT_MAT_DIELECTRIC) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: record %u: a rough-glass record (on = %u) belongs on a dielectric alone", i, table[i].on);
+                if (table[i].on == RT_MICROFACET_GLASS_MAPPED && table[i].image >= RT_MAX_IMAGES) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: record %u: a rough-glass record's image index lies in [0, %u)", i, RT_MAX_IMAGES);
+                if (!(std::isfinite(table[i].roughness) && table[i].roughness >= 0.0f && table[i].roughness <= 1.0f)) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: record %u: a rough-glass record's roughness must be finite and in [0, 1]", i);
+                if (table[i].specular != 0.0f) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: record %u: a rough-glass record reads no specular; it is stored as 0", i);
+                n_on++;
+                continue;
+            }
             if (table[i].on > RT_MICROFACET_MAPPED) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: record %u: on is 0 (off), 1 (constant roughness) or 2 (roughness under a map), not %u", i, table[i].on);
             const uint32_t type = r->scene.mat_types[i];
             if (type == RT_MAT_DIELECTRIC || type == RT_MAT_DIFFUSE_LIGHT || type == RT_MAT_ISOTROPIC)
@@ -1325,7 +1334,8 @@ extern "C" int rt_renderer_microfacets(rt_renderer* r, const rt_microfacet* tabl
         next.on = true; next.n_on = n_on; next.host.assign(table, table + n);
         for (rt_microfacet& m : next.host) {   // what no kernel reads is zero, so that equal tables are equal bytes
             if (m.on == RT_MICROFACET_OFF) m = rt_microfacet{RT_MICROFACET_OFF, 0u, 0.0f, 0.0f};
-            if (m.on == RT_MICROFACET_CONSTANT) m.image = 0u;
+            if (m.on == RT_MICROFACET_CONSTANT || m.on == RT_MICROFACET_GLASS) m.image = 0u;
+            if (m.on == RT_MICROFACET_GLASS || m.on == RT_MICROFACET_GLASS_MAPPED) m.specular = 0.0f;
         }
     }
     if (n ? (r->mf.on && r->mf.host.size() == n && std::memcmp(r->mf.host.data(), next.host.data(), (size_t)n * sizeof(rt_microfacet)) == 0) : !r->mf.on) return RT_OK;   // nothing changes, the refinement goes on

@@ -580,13 +580,10 @@ RT_HD float mfac_max(float x, float c) { return x > c ? x : c; }   // a NaN take
 RT_HD float mfac_min(float x, float c) { return x < c ? x : c; }
 // c = texture_value of the record's entry at the hit's (u, v): the green channel scales the roughness
 RT_HD float microfacet_roughness(float roughness, f3 c) { return roughness * c.y; }
-// N = the shading normal, d = the ray's direction, r = the roughness, F0 = the conductor's albedo or — coat — the scalar specular three times; G: Rng, or the
-// probes' tape.  Returns the way out (rt06.h): RT_MFAC_SPECULAR with the direction and the factor of the throughput, or why there is neither.
+// Steps 2 to 7 of the rule up to the micro-normal, shared with rough glass (§30): N = the normal on the viewer's side, v = the unit direction to the viewer,
+// co = dot(N, v) > 0, r = the roughness.  Returns M, a normal of the distribution v sees, and a = the clamped width the masking term takes.
 template <class G>
-RT_HD uint32_t microfacet_scatter(f3 N, f3 d, float r, f3 F0, bool coat, G& g, f3& out_dir, f3& out_weight) {
-    const f3 v = (-d) / sqrtf(dot(d, d));                                   // 1
-    const float co = dot(N, v);
-    if (!(co > 0.0f)) return RT_MFAC_BACKSIDE;
+RT_HD f3 microfacet_visible_normal(f3 N, f3 v, float co, float r, G& g, float& a_out) {
     const float a = mfac_max(r * r, 0x1p-10f);                              // 2
     const float s = N.z >= 0.0f ? 1.0f : -1.0f;                             // 3
     const float k = -1.0f / (s + N.z);
@@ -605,7 +602,23 @@ RT_HD uint32_t microfacet_scatter(f3 N, f3 d, float r, f3 F0, bool coat, G& g, f
     t2 = (1.0f - q) * sqrtf(mfac_max(1.0f - t11, 0.0f)) + q * t2;
     const f3 nh = (T1 * t1 + T2 * t2) + h * sqrtf(mfac_max((1.0f - t11) - t2 * t2, 0.0f));
     const f3 m = normalize(mk3(a * nh.x, a * nh.y, mfac_max(nh.z, 0.0f)));  // 7
-    const f3 M = (T * m.x + B * m.y) + N * m.z;
+    a_out = a;
+    return (T * m.x + B * m.y) + N * m.z;
+}
+// the separable Smith term of a direction whose cosine to the normal is c > 0
+RT_HD float microfacet_g1(float a, float c) {
+    const float c2 = c * c;
+    return 2.0f / (1.0f + sqrtf(1.0f + ((a * a) * mfac_max(1.0f - c2, 0.0f)) / c2));
+}
+// N = the shading normal, d = the ray's direction, r = the roughness, F0 = the conductor's albedo or — coat — the scalar specular three times; G: Rng, or the
+// probes' tape.  Returns the way out (rt06.h): RT_MFAC_SPECULAR with the direction and the factor of the throughput, or why there is neither.
+template <class G>
+RT_HD uint32_t microfacet_scatter(f3 N, f3 d, float r, f3 F0, bool coat, G& g, f3& out_dir, f3& out_weight) {
+    const f3 v = (-d) / sqrtf(dot(d, d));                                   // 1
+    const float co = dot(N, v);
+    if (!(co > 0.0f)) return RT_MFAC_BACKSIDE;
+    float a;
+    const f3 M = microfacet_visible_normal(N, v, co, r, g, a);              // 2 - 7
     const float ch = dot(v, M);
     const float x = 1.0f - mfac_min(mfac_max(ch, 0.0f), 1.0f);
     const float k5 = ((x * x) * (x * x)) * x;
@@ -614,11 +627,46 @@ RT_HD uint32_t microfacet_scatter(f3 N, f3 d, float r, f3 F0, bool coat, G& g, f
     const f3 w = M * (2.0f * ch) - v;                                       // 9
     const float ci = dot(N, w);
     if (!(ci > 0.0f)) return RT_MFAC_ABSORBED;
-    const float ci2 = ci * ci;
-    const float Gm = 2.0f / (1.0f + sqrtf(1.0f + ((a * a) * mfac_max(1.0f - ci2, 0.0f)) / ci2));
+    const float Gm = microfacet_g1(a, ci);
     out_dir = w;
     out_weight = coat ? mk3(Gm) : F * Gm;
     return RT_MFAC_SPECULAR;
+}
+
+// Rough glass (rt06.h: rt_scene_set_rough_glass): the dielectric whose interface is a GGX height field.  The rule is rough_glass_scatter, numbered
+// as rt06.h numbers it; its steps 2 to 7 are rough_glass_faced, which takes the facing (n, eta) as the smooth dielectric's own expressions leave it, so that the
+// shade phase, which has just evaluated them, hands them on and no bit depends on who did.  Out: the direction and the scalar factor of the throughput.
+template <class G>
+RT_HD uint32_t rough_glass_faced(f3 n, float eta, f3 d, float r, G& g, f3& out_dir, float& out_weight) {
+    const f3 v = (-d) / sqrtf(dot(d, d));                                   // 2
+    const float co = dot(n, v);
+    if (!(co > 0.0f)) return RT_MFAC_BASE;
+    float a;
+    const f3 M = microfacet_visible_normal(n, v, co, r, g, a);              // 3
+    const float ch = dot(v, M);
+    const float F = reflectance(mfac_min(mfac_max(ch, 0.0f), 1.0f), eta);   // 4
+    const float k = 1.0f - eta * eta * (1.0f - ch * ch);                    // 5
+    bool mirror = !(k >= 0.0f);
+    if (!mirror) mirror = F > g.next();
+    if (mirror) {                                                           // 6
+        const f3 w = M * (2.0f * ch) - v;
+        const float ci = dot(n, w);
+        if (!(ci > 0.0f)) return RT_MFAC_ABSORBED;
+        out_dir = w; out_weight = microfacet_g1(a, ci);
+        return RT_MFAC_SPECULAR;
+    }
+    const f3 w = refract(-v, M, eta);                                       // 7
+    const float ci = -dot(n, w);
+    if (!(ci > 0.0f)) return RT_MFAC_ABSORBED;
+    out_dir = w; out_weight = microfacet_g1(a, ci);
+    return RT_MFAC_TRANSMITTED;
+}
+template <class G>
+RT_HD uint32_t rough_glass_scatter(f3 N, f3 d, float r, float ior, G& g, f3& out_dir, float& out_weight) {
+    const bool back = dot(d, N) > 0;                                        // 1
+    const f3 n = back ? -N : N;
+    const float eta = back ? ior : 1 / ior;
+    return rough_glass_faced(n, eta, d, r, g, out_dir, out_weight);
 }
 
 // Environment maps (rt06.h: rt_scene_set_environment): what a ray that leaves the world sees.  d = the ray's direction (any length), texels =

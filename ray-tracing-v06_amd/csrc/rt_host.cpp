@@ -1067,8 +1067,22 @@ extern "C" int rt_scene_set_roughness_map(rt_scene* s, uint32_t material, uint32
     if (material >= s->mfacs.size() || s->mfacs[material].on == RT_MICROFACET_OFF)
         return rt_fail(RT_ERR_INVALID, "rt_scene_set_roughness_map: material %u has no microfacet record; give it one with rt_scene_set_microfacet first", material);
     if (image >= RT_MAX_IMAGES) return rt_fail(RT_ERR_INVALID, "rt_scene_set_roughness_map: an image index lies in [0, %u), not %u", RT_MAX_IMAGES, image);
-    s->mfacs[material].on = RT_MICROFACET_MAPPED;
+    const uint32_t on = s->mfacs[material].on;   // §30: a glass record stays a glass record
+    s->mfacs[material].on = (on == RT_MICROFACET_GLASS || on == RT_MICROFACET_GLASS_MAPPED) ? RT_MICROFACET_GLASS_MAPPED : RT_MICROFACET_MAPPED;
     s->mfacs[material].image = image;
+    return RT_OK;
+}
+// rough glass: a record kind of its own, on dielectrics alone
+extern "C" int rt_scene_set_rough_glass(rt_scene* s, uint32_t material, float roughness) {
+    if (!s) return rt_fail(RT_ERR_INVALID, "rt_scene_set_rough_glass: null scene");
+    if (material >= s->mats.size()) return rt_fail(RT_ERR_INVALID, "rt_scene_set_rough_glass: the scene has no material %u", material);
+    if (s->mats[material].type != RT_MAT_DIELECTRIC)
+        return rt_fail(RT_ERR_INVALID, "rt_scene_set_rough_glass: material %u is no dielectric; metals and Lambertian materials take their record from rt_scene_set_microfacet", material);
+    if (!(std::isfinite(roughness) && roughness >= 0.0f && roughness <= 1.0f)) return rt_fail(RT_ERR_INVALID, "rt_scene_set_rough_glass: a roughness must be finite and in [0, 1]");
+    if (s->mfacs.size() <= material) s->mfacs.resize((size_t)material + 1u, rt_microfacet{RT_MICROFACET_OFF, 0u, 0.0f, 0.0f});
+    rt_microfacet& m = s->mfacs[material];
+    if (m.on != RT_MICROFACET_GLASS_MAPPED) m = rt_microfacet{RT_MICROFACET_GLASS, 0u, 0.0f, 0.0f};
+    m.roughness = roughness; m.specular = 0.0f;
     return RT_OK;
 }
 extern "C" int rt_scene_clear_microfacet(rt_scene* s, uint32_t material) {

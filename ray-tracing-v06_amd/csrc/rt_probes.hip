@@ -199,6 +199,22 @@ __global__ void probe_microfacet_kernel(size_t n, const float* normal, const flo
     if (i >= n) return;
     microfacet_case(i, normal, ray_d, roughness, f0, coat, tape, offsets, out_dir, out_weight, out_path, out_draws);
 }
+// the rough-glass rule (rough_glass_scatter) on one case with its tape, likewise
+RT_HD void rough_glass_case(size_t i, const float* normal, const float* ray_d, const float* roughness, const float* ior, const uint32_t* tape, const uint32_t* offsets,
+                            float* out_dir, float* out_weight, uint32_t* out_path, uint32_t* out_draws) {
+    TapeRng g{tape + offsets[2 * i], offsets[2 * i + 1], 0u};
+    f3 dir = mk3(0.0f);
+    float weight = 0.0f;
+    out_path[i] = rough_glass_scatter(ld3(normal + 3 * i), ld3(ray_d + 3 * i), roughness[i], ior[i], g, dir, weight);
+    st3(out_dir + 3 * i, dir); out_weight[i] = weight;
+    out_draws[i] = g.draws;
+}
+__global__ void probe_rough_glass_kernel(size_t n, const float* normal, const float* ray_d, const float* roughness, const float* ior, const uint32_t* tape,
+                                         const uint32_t* offsets, float* out_dir, float* out_weight, uint32_t* out_path, uint32_t* out_draws) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    rough_glass_case(i, normal, ray_d, roughness, ior, tape, offsets, out_dir, out_weight, out_path, out_draws);
+}
 __global__ void probe_radiance_kernel(DeviceWorld w, rt_camera cam, uint32_t width, uint32_t height, uint32_t max_depth,
                                       uint64_t seed, size_t n, const uint32_t* keys, float* out) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -664,6 +680,35 @@ extern "C" int rt_microfacet_batch(size_t count, const float* normal, const floa
                                    size_t tape_len, const uint32_t* offsets, float* out_dir, float* out_weight, uint32_t* out_path, uint32_t* out_draws) {
     if (const int rc = microfacet_args("rt_microfacet_batch", count, normal, ray_d, roughness, f0, coat, tape, tape_len, offsets, out_dir, out_weight, out_path, out_draws)) return rc;
     for (size_t i = 0; i < count; i++) microfacet_case(i, normal, ray_d, roughness, f0, coat, tape, offsets, out_dir, out_weight, out_path, out_draws);
+    return RT_OK;
+}
+// Rough glass: its rule over arrays of cases, on the device and — HOST (no GPU) — here
+static int rough_glass_args(const char* who, size_t count, const float* normal, const float* ray_d, const float* roughness, const float* ior, const uint32_t* tape,
+                            size_t tape_len, const uint32_t* offsets, float* out_dir, float* out_weight, uint32_t* out_path, uint32_t* out_draws) {
+    if (!normal || !ray_d || !roughness || !ior || !tape || !offsets || !out_dir || !out_weight || !out_path || !out_draws)
+        return rt_fail(RT_ERR_INVALID, "%s: null argument", who);
+    if (int rc = check_tape(who, count, tape_len, offsets)) return rc;
+    for (size_t i = 0; i < count; i++)
+        if (!(std::isfinite(roughness[i]) && roughness[i] >= 0.0f && roughness[i] <= 1.0f))
+            return rt_fail(RT_ERR_INVALID, "%s: case %zu: a roughness must be finite and in [0, 1]", who, i);
+    return RT_OK;
+}
+extern "C" int rt_probe_rough_glass(int device, size_t count, const float* normal, const float* ray_d, const float* roughness, const float* ior, const uint32_t* tape,
+                                    size_t tape_len, const uint32_t* offsets, float* out_dir, float* out_weight, uint32_t* out_path, uint32_t* out_draws) {
+    if (const int rc = rough_glass_args("rt_probe_rough_glass", count, normal, ray_d, roughness, ior, tape, tape_len, offsets, out_dir, out_weight, out_path, out_draws)) return rc;
+    if (count == 0) return RT_OK;
+    ProbeRun p(device);
+    auto dn = p.in(normal, 3 * count); auto dd = p.in(ray_d, 3 * count); auto dr = p.in(roughness, count); auto di = p.in(ior, count);
+    const uint32_t no_tape = 0x800001u;   // an empty tape, as rt_probe_microfacet uploads it
+    auto dt = tape_len ? p.in(tape, tape_len) : p.in(&no_tape, 1); auto dof = p.in(offsets, 2 * count);
+    auto od = p.out(out_dir, 3 * count); auto ow = p.out(out_weight, count); auto op = p.out(out_path, count); auto on = p.out(out_draws, count);
+    p.launch(probe_rough_glass_kernel, p.per_case(count), 128, count, dn, dd, dr, di, dt, dof, od, ow, op, on);
+    return p.finish();
+}
+extern "C" int rt_rough_glass_batch(size_t count, const float* normal, const float* ray_d, const float* roughness, const float* ior, const uint32_t* tape, size_t tape_len,
+                                    const uint32_t* offsets, float* out_dir, float* out_weight, uint32_t* out_path, uint32_t* out_draws) {
+    if (const int rc = rough_glass_args("rt_rough_glass_batch", count, normal, ray_d, roughness, ior, tape, tape_len, offsets, out_dir, out_weight, out_path, out_draws)) return rc;
+    for (size_t i = 0; i < count; i++) rough_glass_case(i, normal, ray_d, roughness, ior, tape, offsets, out_dir, out_weight, out_path, out_draws);
     return RT_OK;
 }
 extern "C" int rt_probe_radiance(const rt_render_config* cfg, const rt_camera* cam, const rt_world_flat* world, size_t n,

@@ -268,6 +268,8 @@ __device__ __forceinline__ f3 texture_table_value(const uint4* tt, uint32_t imag
 //      before the scatter branches: a metal is a rough conductor, a Lambertian kind wears a coat whose toss comes before every draw of the base.  A specular or
 //      absorbed hit takes none of the base's draws; a base or backside hit runs the code below as it stands.  The records lie last in the tail, where the bits
 //      above bit 0 of the header's first lane say; that word is read at the hit, through a scalar, and vn_on keeps bit 0 alone.
+//      Rough glass: a dielectric whose record is a glass one runs rough_glass_faced in the dielectric branch, from the facing that branch has
+//      computed; reflected or transmitted, the albedo is scaled by the rule's weight; absorbed is a failed scatter; handed back, the smooth hit runs verbatim.
 // LTREE && ENVL (mode RT_LIGHT_SAMPLING_ENV_TREE): both at once.  The light half tosses once more between the map and mode 16's table (no toss
 //      when the table is empty: n_l == 0 is the map alone), the light density is the mean of the map's and the walk's, and an image-textured Lambertian hit is
 //      sampled as the diffuse hit it is — its albedo is looked up behind the direction, as ever.
@@ -720,7 +722,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                         const uint4* tt = p.scene.blob + p.scene.blob_vec4 + tex_here;
                         const uint4 th = tt[0];
                         const uint32_t nm_at = (uint32_t)__builtin_amdgcn_readfirstlane((int)th.w);
-                        const bool mf_mapped = MFAC && mf_rec.x == RT_MICROFACET_MAPPED;
+                        const bool mf_mapped = MFAC && (mf_rec.x == RT_MICROFACET_MAPPED || mf_rec.x == RT_MICROFACET_GLASS_MAPPED);   // §30: a frosted surface under its map
                         if (nm_at != 0u || mf_mapped) {
                             uint4 nr = make_uint4(0u, 0u, 0u, 0u);
                             if (!MFAC || nm_at != 0u) nr = tt[nm_at + (mat_bits & RT_MAT_INDEX_MASK)];   // (on, image, strength bits, -): per lane, lanes sit on different materials
@@ -797,8 +799,26 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                 if (path_over) {
                     // nothing to sample: the path ends here with what it has collected
                 } else if (is_diel) {
+                    // §30: glass with a rough-glass record (the table admits no other kind on a dielectric) reflects or refracts about a micro-normal, from the
+                    // facing the block above has just left in `normal` and ior_ratio — step 1 of the rule in its own expressions.  Specular or transmitted: the
+                    // rule's direction, the albedo times its weight; absorbed: a failed scatter; base (a grazing or NaN cosine): the smooth hit, verbatim.
+                    // (The smooth hit stands twice so that the forms without MFAC are the statements they were, to the compiler too.)
+                    if constexpr (MFAC) {
+                        bool gl_done = false;
+                        if (mf_rec.x != 0u) {
+                            float gl_weight = 0.0f;
+                            const uint32_t way = rough_glass_faced(normal, ior_ratio, ray.d, mf_rough, rng, scatter_dir, gl_weight);
+                            if (way == RT_MFAC_SPECULAR || way == RT_MFAC_TRANSMITTED) { albedo = albedo * gl_weight; gl_done = true; }
+                            else if (way == RT_MFAC_ABSORBED) { scattered_ok = false; gl_done = true; }
+                        }
+                        if (!gl_done) {
+                            if (must_reflect || reflect_prob > rng.next()) scatter_dir = reflect(unit_dir, normal);
+                            else scatter_dir = refract(unit_dir, normal, ior_ratio);
+                        }
+                    } else {
                     if (must_reflect || reflect_prob > rng.next()) scatter_dir = reflect(unit_dir, normal);
                     else scatter_dir = refract(unit_dir, normal, ior_ratio);
+                    }
                 } else {
                     RT_PT(11);
                     // §29: a material with a microfacet record — a metal as a rough conductor with F0 = its albedo, the Lambertian kinds under a coat — before any

@@ -173,7 +173,9 @@ def load_mtl(path):
     resolved beside the file, options in front of it (-s, -o, ...) are skipped.  `norm`, `map_Bump`, `map_bump` and `bump` name the material's normal map
     (the file is taken as a tangent-space normal map, OpenGL convention, green = +v): "normal_map": path | None and "normal_strength": the `-bm X`
     in front of the name, 1.0 without one; the last such line of a material counts.  The PBR extension's `Pr`, `map_Pr` and `Pm` become
-    "roughness": float | None, "roughness_map": path | None and "metallic": float | None.  Nothing else of MTL is read."""
+    "roughness": float | None, "roughness_map": path | None and "metallic": float | None.  The keywords glass is told by add keys of their own, each
+    present only when the file has the keyword: `Ni` as "ior" (> 0), `d` and `Tr` as "dissolve" in [0, 1] (Tr = 1 - d), `illum` as "illum" (an integer).  Nothing
+    else of MTL is read."""
     import os
     out, current = {}, None
     beside = lambda name: os.path.join(os.path.dirname(os.path.abspath(path)), *name.replace("\\", "/").split("/"))
@@ -214,6 +216,26 @@ def load_mtl(path):
                     if not (np.isfinite(value) and 0.0 <= value <= 1.0):
                         raise ValueError(f"{where}: {parts[0]} must be finite and in [0, 1]")
                     current["roughness" if parts[0] == "Pr" else "metallic"] = value
+            elif parts[0] in ("Ni", "d", "Tr", "illum"):
+                if current is None:
+                    raise ValueError(f"{where}: {parts[0]} before any newmtl")
+                if len(parts) < 2:
+                    raise ValueError(f"{where}: {parts[0]} needs a value")
+                if parts[0] == "illum":
+                    try:
+                        current["illum"] = int(parts[1])
+                    except ValueError:
+                        raise ValueError(f"{where}: illum must be an integer") from None
+                else:
+                    value = float(parts[-1])   # (`d -halo x`: the option is skipped)
+                    if parts[0] == "Ni":
+                        if not (np.isfinite(value) and value > 0.0):
+                            raise ValueError(f"{where}: Ni must be finite and above 0")
+                        current["ior"] = value
+                    else:
+                        if not (np.isfinite(value) and 0.0 <= value <= 1.0):
+                            raise ValueError(f"{where}: {parts[0]} must be finite and in [0, 1]")
+                        current["dissolve"] = value if parts[0] == "d" else 1.0 - value
             elif parts[0] in ("Kd", "map_Kd"):
                 if current is None:
                     raise ValueError(f"{where}: {parts[0]} before any newmtl")

@@ -57,7 +57,9 @@ world's lights together (RT_LIGHT_SAMPLING_ENV_TREE), and sample
 renders each `usemtl` group of the OBJ as a mesh of its own with the image its material's map_Kd names (the scene's texture table): here the
 book's earth sphere (image 0), a floor whose `vt` run to 4 — tiled under --texture-wrap repeat — and a UV-mapped pyramid, both filtered bilinearly.  A material's
 `Pm`, `Pr` and `map_Pr` are applied too: `Pm >= 0.5` makes the group a metal with `Kd` as F0; `Pr` or `map_Pr` gives it a microfacet record — a rough
-conductor on the metal, a coat of specular 0.04 on anything else —, `map_Pr` scaling the roughness by the image's green channel.
+conductor on the metal, a coat of specular 0.04 on anything else —, `map_Pr` scaling the roughness by the image's green channel.  A group whose `d` is below 0.5
+(`Tr` above) or whose `illum` is 4, 6, 7 or 9 is glass of index `Ni`, whatever its `Pm`; `Pr` and `map_Pr` frost it.  --rough-glass R frosts the
+prefab `glass` material of --mesh-material.
 """
 import argparse, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -93,6 +95,7 @@ ap.add_argument("--texture", default=None, action="append", metavar="FILE.ppm|FI
                     "the k-th one replaces the map_Kd of the k-th material group, in the order the OBJ first uses them")
 ap.add_argument("--mtl", action="store_true", help="with --mesh FILE.obj: one mesh per `usemtl` group, each with the image its material's map_Kd names (mtllib files beside the "
                     "OBJ; DESIGN.md §25) or a Lambertian of its Kd; a group without either takes --mesh-material")
+ap.add_argument("--rough-glass", type=float, default=None, metavar="R", help="with --mesh-material glass: frost the glass, a GGX roughness in [0, 1] (DESIGN.md §30)")
 ap.add_argument("--texture-wrap", choices=["clamp", "repeat"], default="clamp", help="the wrap mode of the images --texture / --mtl bring (DESIGN.md §25)")
 ap.add_argument("--texture-filter", choices=["nearest", "bilinear"], default="nearest", help="their filter")
 ap.add_argument("--env", default=None, metavar="FILE.hdr|FILE.npy|FILE.png|FILE.ppm|sky", help="an equirectangular environment map in the place of the scene's background "
@@ -151,8 +154,13 @@ if a.mesh:
         _, _, uvs, uv_faces = mesh_io.load_obj_uvs(a.mesh)
         if uvs is None and a.texture:
             sys.exit(f"--texture: {a.mesh} has no complete set of texture coordinates (`vt` lines and a second index at every face corner)")
+    def frosted(mat):   # --rough-glass: the prefab glass with a rough-glass record
+        if a.rough_glass is not None:
+            scene.set_rough_glass(mat, a.rough_glass)
+        return mat
+
     plain = {"white": lambda: scene.Lambertian((0.73, 0.73, 0.73)), "red": lambda: scene.Lambertian((0.65, 0.05, 0.05)), "metal": lambda: scene.Metal((0.8, 0.85, 0.88), 0.0),
-             "glass": lambda: scene.Dielectric((1, 1, 1), 1.5), "checker": lambda: scene.LambertianTexture((0.2, 0.3, 0.1), (0.9, 0.9, 0.9), abs(a.mesh_scale) / 4 if a.mesh_scale else 1.0),   # four squares across a unit mesh
+             "glass": lambda: frosted(scene.Dielectric((1, 1, 1), 1.5)), "checker": lambda: scene.LambertianTexture((0.2, 0.3, 0.1), (0.9, 0.9, 0.9), abs(a.mesh_scale) / 4 if a.mesh_scale else 1.0),   # four squares across a unit mesh
              "light": lambda: scene.DiffuseLight((4, 4, 4))}[a.mesh_material]
     place = dict(scale=a.mesh_scale, rotate_y=a.mesh_rotate_y, translate=[float(x) for x in a.mesh_translate.split(",")])
     if a.mtl:   # one mesh per material group, in the order the OBJ first uses them
@@ -166,17 +174,25 @@ if a.mesh:
         for k, name in enumerate(groups):
             rows = np.array([i for i, n in enumerate(names) if n == name])
             entry = library.get(name, {"Kd": None, "map_Kd": None})
-            picture = a.texture[k] if a.texture and k < len(a.texture) else entry["map_Kd"]
+            # glass, before everything else: a dissolve below 0.5 or one of the illumination models with refraction (4, 6, 7, 9) makes the group
+            # a white dielectric of index Ni (1.5 when absent or not above 1), whatever its map_Kd and Pm; Pr or map_Pr then frosts it
+            is_glass = entry.get("dissolve", 1.0) < 0.5 or entry.get("illum") in (4, 6, 7, 9)
+            picture = None if is_glass else a.texture[k] if a.texture and k < len(a.texture) else entry["map_Kd"]
             if picture and uvs is None:
                 sys.exit(f"--mtl: material {name!r} has an image and {a.mesh} has no complete set of texture coordinates")
-            mat = image_material(picture) if picture else scene.Lambertian(entry["Kd"]) if entry["Kd"] else plain()
+            ior = entry.get("ior")
+            mat = (scene.Dielectric((1, 1, 1), ior if ior is not None and ior > 1.0 else 1.5) if is_glass else image_material(picture) if picture
+                   else scene.Lambertian(entry["Kd"]) if entry["Kd"] else plain())
             # microfacet surfaces: Pm >= 0.5 makes the group a metal with Kd as F0; Pr or map_Pr gives it a record — a rough conductor on the
             # metal, a coat of specular 0.04 on anything else — and map_Pr scales the roughness by the image's green channel (Pr = 1 when the file has none)
             roughness, roughness_map, metallic = entry.get("roughness"), entry.get("roughness_map"), entry.get("metallic")
-            if metallic is not None and metallic >= 0.5:
+            if metallic is not None and metallic >= 0.5 and not is_glass:
                 mat, picture = scene.Metal(entry["Kd"] or (0.8, 0.85, 0.88), 0.0), None
             if roughness is not None or roughness_map:
-                scene.set_microfacet(mat, 1.0 if roughness is None else roughness, 0.04)
+                if is_glass:
+                    scene.set_rough_glass(mat, 1.0 if roughness is None else roughness)
+                else:
+                    scene.set_microfacet(mat, 1.0 if roughness is None else roughness, 0.04)
                 if roughness_map:
                     if uvs is None:
                         sys.exit(f"--mtl: material {name!r} has a roughness map and {a.mesh} has no complete set of texture coordinates")
@@ -185,7 +201,7 @@ if a.mesh:
             group_uvs = dict(uvs=uvs, uv_faces=uv_faces[rows]) if picture or roughness_map else {}
             added += scene.MakeMesh(vertices, faces[rows], mat, **place, **group_normals, **group_uvs)[1]
             print(json.dumps({"material": name, "triangles": len(rows), "image": picture, "Kd": entry["Kd"], "roughness": roughness, "roughness_map": roughness_map,
-                              "metallic": metallic}), flush=True)
+                              "metallic": metallic, "glass": is_glass}), flush=True)
     else:
         mat = image_material(a.texture[0]) if a.texture else plain()
         first, added = scene.MakeMesh(vertices, faces, mat, **place, normals=normals, normal_faces=normal_faces, uvs=uvs, uv_faces=uv_faces)
