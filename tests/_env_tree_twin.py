@@ -114,10 +114,10 @@ def new_stats():
     return st
 
 
-def radiance(world, cam, width, height, max_depth, seed, gids, samples, sky, light=None, tree=None, tex=None, stats=None):
+def radiance(world, cam, width, height, max_depth, seed, gids, samples, sky, light=None, tree=None, tex=None, stats=None, walk=None):
     """Radiance of sample samples[i] of pixel gids[i] with the miss colour sky(directions): ((n, 3) float32, followed (n,) bool).  light = (tables, u0) alone:
     §24's mixture at Lambertian and checker hits; with tree = table_of(world): §26's at Lambertian, checker and image hits.  _env_light_twin.radiance statement
-    by statement, but for the blocks marked §26."""
+    by statement, but for the blocks marked §26 — and §28: walk, the dict a substituted walk (_nmap_twin.mapped_walk) leaves its (u, v) in."""
     assert cam.type == 0, "the twin restates the pinhole camera"
     assert tree is None or (light is not None and tree.refused is None)   # §26
     gids = np.ascontiguousarray(gids, np.uint32)
@@ -173,6 +173,7 @@ def radiance(world, cam, width, height, max_depth, seed, gids, samples, sky, lig
             r = live[sel]
             if tex is not None:   # §26: the texture coordinates of every hit that goes on, before the arrays are cut down to them
                 tuv = XT.hit_uv(world, tex[0], rays[sel], hit[sel], t[sel], prim[sel], normal[sel])
+                tuv, walked = XT.prefer_walk_uv(tuv, walk, sel)   # §28: a mapped hit's (u, v) is the walk's, from before the map
             o, d, t, normal, mi, mt = o[sel], d[sel], t[sel], normal[sel], mi[sel], mt[sel]
             hit_p = o + d * t[:, None]
             k = len(r)
@@ -230,6 +231,7 @@ def radiance(world, cam, width, height, max_depth, seed, gids, samples, sky, lig
             img = np.nonzero(mt == MAT_IMAGE)[0]   # §26: the albedo of an image hit, behind the direction: the table's entry at the hit's coordinates
             if len(img):
                 albedo[img] = XT.lookup(tex[1], m_albedo2[mi[img]][:, 0].astype(np.int64), tuv[img, 0], tuv[img, 1])
+                XT.count_walk_uv(walk, walked[img].sum())
             if light is not None:   # §24: the densities of the direction under both halves
                 s = np.nonzero(sampled & ok)[0]
                 if len(s):
@@ -262,11 +264,11 @@ def radiance(world, cam, width, height, max_depth, seed, gids, samples, sky, lig
     return out, followed
 
 
-def frame_samples(world, cam, width, height, spp, max_depth, seed, sky, light=None, tree=None, tex=None, first_sample=0, stats=None):
+def frame_samples(world, cam, width, height, spp, max_depth, seed, sky, light=None, tree=None, tex=None, first_sample=0, stats=None, walk=None):
     """(height, width, spp, 3) float32: every sample of every pixel; followed (height, width, spp)"""
     gids = np.repeat(np.arange(width * height, dtype=np.uint32), spp)
     smp = np.tile(np.arange(first_sample, first_sample + spp, dtype=np.uint32), width * height)
-    rad, ok = radiance(world, cam, width, height, max_depth, seed, gids, smp, sky, light, tree, tex, stats)
+    rad, ok = radiance(world, cam, width, height, max_depth, seed, gids, smp, sky, light, tree, tex, stats, walk)
     return rad.reshape(height, width, spp, 3), ok.reshape(height, width, spp)
 
 

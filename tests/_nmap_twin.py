@@ -109,7 +109,11 @@ def mapped_walk(world, vn, uv, nmaps, table, rays, preset=None, info=None):
     """_tri_twin.closest_intersection — behind _smooth_twin's rule when vn, a table of vertex normals, is given — then the normal-map rule on every hit whose
     material's record of nmaps (capi.NORMAL_MAP_DT, one per material) says on: (u, v) by _tex_twin.hit_uv from the normal the walk found, the tangents by the
     kind of surface (a triangle takes its coordinates' whenever the world has a table of them, as the kernels do), the entry of `table` = [(image, wrap,
-    filter), ...].  info (a dict): its 'mapped' (hits on a mapped material) and one count per way out of the rule grow."""
+    filter), ...].  info (a dict): its 'mapped' (hits on a mapped material) and one count per way out of the rule grow, and its 'uv' is what this call hands on
+    to radiance(): (given (k,) bool, uv (k, 2), on a sphere (k,) bool) over the k rays — the (u, v) of every hit it mapped, taken from the normal BEFORE the map
+    replaced it, which the image lookup and the roughness map of that hit share (_tex_twin.prefer_walk_uv) — or None when it mapped no hit."""
+    if info is not None:
+        info["uv"] = None
     if vn is not None and len(vn):
         hit, t, prim, normal = ST.closest_intersection_smooth(world, vn, rays, preset)
     else:
@@ -121,7 +125,6 @@ def mapped_walk(world, vn, uv, nmaps, table, rays, preset=None, info=None):
     rows = np.nonzero((hit != 0) & (nmaps["on"][mi] != 0))[0]
     if len(rows) == 0:
         return hit, t, prim, normal
-    assert not ((prim[rows] < len(prims)) & (mats["type"][mi[rows]] == XT.MAT_IMAGE)).any(), "an image-textured sphere takes its (u, v) from the normal: not this twin's"
     tuv = XT.hit_uv(world, uv, rays[rows], hit[rows], t[rows], prim[rows], normal[rows])
     k = len(rows)
     surface = np.full(k, PLANAR, np.uint32)
@@ -141,6 +144,9 @@ def mapped_walk(world, vn, uv, nmaps, table, rays, preset=None, info=None):
     normal = normal.copy()
     normal[rows] = out
     if info is not None:
+        given, full, on_sphere = np.zeros(len(rays), bool), np.zeros((len(rays), 2), F), np.zeros(len(rays), bool)
+        given[rows], full[rows], on_sphere[rows] = True, tuv, sph
+        info["uv"] = (given, full, on_sphere)
         info["mapped"] = info.get("mapped", 0) + k
         for name, count in counts(path).items():
             info[name] = info.get(name, 0) + count
@@ -151,11 +157,12 @@ def frame_samples(world, cam, width, height, spp, max_depth, seed, sky, vn, uv, 
     """_env_tree_twin.frame_samples — plain (light None) or mode 48 — with the walk replaced by mapped_walk for the duration of the call; nmaps None = no table"""
     saved = TT.closest_intersection
     if nmaps is not None:
+        info = {} if info is None else info   # the walk's (u, v) travel to radiance() in it
         TT.closest_intersection = lambda w, rays, preset=None: mapped_walk(w, vn, uv, nmaps, table, rays, preset, info)
     elif vn is not None and len(vn):
         TT.closest_intersection = lambda w, rays, preset=None: ST.closest_intersection_smooth(w, vn, rays, preset)
     try:
         return VT.frame_samples(world, cam, width, height, spp, max_depth, seed, sky, light=light, tree=tree, tex=(uv if uv is not None and len(uv) else None, table),
-                                first_sample=first_sample, stats=stats)
+                                first_sample=first_sample, stats=stats, walk=info if nmaps is not None else None)
     finally:
         TT.closest_intersection = saved

@@ -163,7 +163,7 @@ def new_stats():
     return st
 
 
-def radiance(world, cam, width, height, max_depth, seed, gids, samples, sky, light=None, tree=None, tex=None, mfacs=None, stats=None):
+def radiance(world, cam, width, height, max_depth, seed, gids, samples, sky, light=None, tree=None, tex=None, mfacs=None, stats=None, walk=None):
     """_mfac_twin.radiance statement by statement, but for the dielectric block, marked §30: a hit on glass whose record is a rough-glass one runs faced() from
     the facing the block has computed; every other glass hit, and one the rule hands back, is the smooth dielectric it was.  ((n, 3) float32, followed (n,) bool)"""
     assert cam.type == 0, "the twin restates the pinhole camera"
@@ -236,7 +236,7 @@ def radiance(world, cam, width, height, max_depth, seed, gids, samples, sky, lig
                         mp = rec["on"][has] == GLASS_MAPPED
                         if mp.any():
                             hm = gl[has][mp]
-                            assert tex is not None and not (prim[hm] < len(prims)).any(), "a roughness map on a sphere takes its (u, v) before the normal map: not this twin's"
+                            assert tex is not None   # (glass takes no normal map: on a sphere too the walk's normal is the one the kernel reads (u, v) from)
                             tuv_g = XT.hit_uv(world, tex[0], rays[hm], hit[hm], t[hm], prim[hm], normal[hm])
                             rough[mp] = rough[mp] * XT.lookup(tex[1], rec["image"][has][mp].astype(np.int64), tuv_g[:, 0], tuv_g[:, 1])[:, 1]
                         det = {}
@@ -279,6 +279,7 @@ def radiance(world, cam, width, height, max_depth, seed, gids, samples, sky, lig
             r = live[sel]
             if tex is not None:
                 tuv = XT.hit_uv(world, tex[0], rays[sel], hit[sel], t[sel], prim[sel], normal[sel])
+                tuv, walked = XT.prefer_walk_uv(tuv, walk, sel)   # §28: a mapped hit's (u, v) is the walk's, from before the map
             o, d, t, normal, mi, mt, prim_sel = o[sel], d[sel], t[sel], normal[sel], mi[sel], mt[sel], prim[sel]
             hit_p = o + d * t[:, None]
             if mfacs is not None and len(r):   # §29: the records' rule, before every draw of the base
@@ -289,7 +290,8 @@ def radiance(world, cam, width, height, max_depth, seed, gids, samples, sky, lig
                     rough = rec["roughness"][has].astype(F)
                     mp = rec["on"][has] == MAPPED
                     if mp.any():
-                        assert tex is not None and not (prim_sel[has][mp] < len(prims)).any(), "a roughness map on a sphere takes its (u, v) before the normal map: not this twin's"
+                        assert tex is not None
+                        XT.count_walk_uv(walk, walked[has][mp].sum())
                         green = XT.lookup(tex[1], rec["image"][has][mp].astype(np.int64), tuv[has][mp, 0], tuv[has][mp, 1])[:, 1]
                         rough[mp] = rough[mp] * green
                     is_coat = mt[has] != MAT_METAL
@@ -309,7 +311,7 @@ def radiance(world, cam, width, height, max_depth, seed, gids, samples, sky, lig
                 keep = ~done
                 r, o, d, t, normal, mi, mt, hit_p = r[keep], o[keep], d[keep], t[keep], normal[keep], mi[keep], mt[keep], hit_p[keep]
                 if tex is not None:
-                    tuv = tuv[keep]
+                    tuv, walked = tuv[keep], walked[keep]
             k = len(r)
             lamb = mt != 1
             sampled = lamb & ((mt != MAT_IMAGE) | both)
@@ -364,6 +366,7 @@ def radiance(world, cam, width, height, max_depth, seed, gids, samples, sky, lig
             img = np.nonzero(mt == MAT_IMAGE)[0]
             if len(img):
                 albedo[img] = XT.lookup(tex[1], m_albedo2[mi[img]][:, 0].astype(np.int64), tuv[img, 0], tuv[img, 1])
+                XT.count_walk_uv(walk, walked[img].sum())
             if light is not None:
                 s = np.nonzero(sampled & ok)[0]
                 if len(s):
@@ -404,6 +407,7 @@ def frame_samples(world, cam, width, height, spp, max_depth, seed, sky, vn, uv, 
     _nmap_twin.frame_samples replaces it (nmaps None = no normal-map table) and the records of mfacs (None = no microfacet table), rough-glass records among them"""
     saved = TT.closest_intersection
     if nmaps is not None:
+        info = {} if info is None else info   # the walk's (u, v) travel to radiance() in it
         TT.closest_intersection = lambda w, rays, preset=None: NT.mapped_walk(w, vn, uv, nmaps, table, rays, preset, info)
     elif vn is not None and len(vn):
         TT.closest_intersection = lambda w, rays, preset=None: ST.closest_intersection_smooth(w, vn, rays, preset)
@@ -411,7 +415,7 @@ def frame_samples(world, cam, width, height, spp, max_depth, seed, sky, vn, uv, 
         gids = np.repeat(np.arange(width * height, dtype=np.uint32), spp)
         smp = np.tile(np.arange(first_sample, first_sample + spp, dtype=np.uint32), width * height)
         tex = (uv if uv is not None and len(uv) else None, table) if table is not None else None
-        rad, ok = radiance(world, cam, width, height, max_depth, seed, gids, smp, sky, light, tree, tex, mfacs, stats)
+        rad, ok = radiance(world, cam, width, height, max_depth, seed, gids, smp, sky, light, tree, tex, mfacs, stats, info if nmaps is not None else None)
         return rad.reshape(height, width, spp, 3), ok.reshape(height, width, spp)
     finally:
         TT.closest_intersection = saved

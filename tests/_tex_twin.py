@@ -133,6 +133,24 @@ def hit_uv(world, uv, rays, hit, t, prim, normal):
     return out
 
 
+def prefer_walk_uv(tuv, walk, sel):
+    """The kernels' order on a mapped hit: (u, v) is computed once, from the normal the walk found, BEFORE the normal map replaces that normal, and
+    the image lookup and the roughness map of the hit take that same (u, v).  walk: the dict _nmap_twin.mapped_walk leaves its (u, v) in — walk["uv"] = (given
+    (k,) bool, uv (k, 2), on a sphere (k,) bool) over the k rays of its last call, or None — or None for a run without a normal-map table; sel: the rows of
+    those rays that tuv = hit_uv(...) stands for.  Returns (tuv with the walk's (u, v) on the rows it gave one for, (len(sel),) bool: such a row on a sphere —
+    the one surface whose hit_uv reads the normal).  walk["after_map"] (a test's switch) keeps hit_uv's, the order the kernels do NOT have."""
+    if not walk or walk.get("uv") is None or walk.get("after_map"):
+        return tuv, np.zeros(len(sel), bool)
+    given, uv, sphere = walk["uv"]
+    return np.where(given[sel][:, None], uv[sel], tuv).astype(F), (given & sphere)[sel]
+
+
+def count_walk_uv(walk, n):
+    """walk's counter of the image and roughness lookups that took the walk's (u, v) on a sphere"""
+    if walk is not None:
+        walk["uv_lookups"] = walk.get("uv_lookups", 0) + int(n)
+
+
 def first_hit_frame(world, uv, table, cam, width, height, spp, seed, stats=None):
     """Every sample of a depth-2 frame of an open world under a constant background whose surfaces are image-textured (a sphere, a parallelogram or a
     triangle; material.albedo2[0] = its image of `table`): a primary miss is the background; a hit scatters as a Lambertian does (one on_unit3 draw; near-zero = a

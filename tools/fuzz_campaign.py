@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Differential fuzz campaign: random worlds (spheres, moving spheres, quads, triangles and meshes, lights, media, textures; every builder; LDS
 and global-memory paths; three cameras) rendered on the GPU and by the CPU oracle, compared bit for bit.
-    python tools/fuzz_campaign.py --seeds 200 [--first 0] [--no-triangles] [--mesh-lights] [--light-tree] [--texture-coords] [--textures] [--env-tree]
+    python tools/fuzz_campaign.py --seeds 200 [--first 0] [--no-triangles] [--mesh-lights] [--light-tree] [--texture-coords] [--textures] [--env-tree] [--surfaces]
 Prints one line per failure and a summary; exit code 1 if anything differed.  The triangles of a world come from a generator of their own, so the rest of a seed's
 world is what it was before the fuzzer made triangles, and --no-triangles renders exactly those earlier worlds.  Importing this file starts nothing:
 world_of_seed() builds a seed's world on the host, without a device.  --mesh-lights (off by default: the recorded campaigns ran without it) also renders every
@@ -9,7 +9,9 @@ world that RT_LIGHT_SAMPLING_MESH accepts in that mode; it draws nothing, so the
  gives random triangles of every world with an image and triangles random texture coordinates from [-0.5, 1.5) — wider than the unit square —,
 drawn from the seed's generator AFTER every other draw of the case, so committed seeds give the worlds, frames and cameras they gave.  --env-tree
 puts every world with quads under the procedural sky as its LAST check — it draws nothing and the scene is not used again — and renders it in light-sampling
-mode 48: both memory forms, and the twin (tests/_env_tree_twin.py) where it follows."""
+mode 48: both memory forms, and the twin (tests/_env_tree_twin.py) where it follows.  --surfaces also renders every world under the inert normal-map and
+microfacet tables of tests/_surface_worlds.py — on a second scene built from the seed, so it draws nothing and leaves the seed's own scene alone — and holds both
+kernel families, in both memory forms, to the oracle's frame the campaign has computed."""
 import argparse, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -41,6 +43,7 @@ def parse_args(argv=None):
     ap.add_argument("--mesh-lights", action="store_true", help="also render the worlds that light-sampling mode 4 (triangle and mesh lights) accepts in that mode: both memory forms, and the twin where it follows")
     ap.add_argument("--textures", action="store_true", help="also render the worlds with an image under a texture table of several random images and random modes: the world's image under clamp / nearest must be the oracle's frame, and under another mode pair both memory forms must agree")
     ap.add_argument("--texture-coords", action="store_true", help="also render the worlds with an image and triangles under a table of random texture coordinates on random triangles: both memory forms must agree, and the identity table must be the oracle's frame")
+    ap.add_argument("--surfaces", action="store_true", help="also render every world under inert normal-map and microfacet tables (flat maps; records that are all off on the materials in use): the NMAP and the MFAC kernel family, both memory forms, must give the oracle's frame; worlds the families refuse (a lane walk, a kernel variant other than 2 and 3) are counted as skipped")
     return ap.parse_args(argv)
 
 
@@ -267,12 +270,46 @@ def textures_check(p, s, w, cam, W, H, spp, depth, variant, rng, ref):
     return bits_equal(frames[0], frames[1]), forms, modes
 
 
+def surfaces_check(p, seed, args, cam, W, H, spp, depth, variant, ref):
+    """The seed's world once more, built afresh (the tables add images and materials to a scene), under tests/_surface_worlds.inert_tables: a normal-map table
+    of flat maps alone (the NMAP family) and with a microfacet table whose records on the materials in use are off (the MFAC family), each in the renderer's own
+    form and in the global-memory form.  Every frame must be `ref`, the oracle's.  None: not applicable (no material in use takes a record, a lane walk, a
+    variant without the families); else (ok, forms)."""
+    import _surface_worlds as SW
+    forms, ok = [], True
+    for family in ("NMAP", "MFAC"):
+        s = world_of_seed(p, seed, not args.no_triangles, args.force_variant)[0]
+        if s.getWorldPtr().traversal != 0 or not SW.takes_a_record(s):
+            return None
+        SW.inert_tables(s, microfacets=family == "MFAC")
+        w = s.getWorldPtr()
+        for env in ({}, {"RT06_FORCE_BIG": "1"}):
+            os.environ.pop("RT06_FORCE_BIG", None)
+            os.environ.update(env)
+            try:
+                r = p.Renderer.MakeRenderer(W, H, spp, depth, cam, w, variant=variant)
+            except p.capi.RtError:
+                return None   # no kernel of the families for the world
+            finally:
+                os.environ.pop("RT06_FORCE_BIG", None)
+            if r.kernel_info()["variant"] not in (2, 3) or not (r.kernel_microfacet() if family == "MFAC" else r.kernel_normal_map()):
+                r.close()
+                return None
+            forms.append((family, r.kernel_form()))
+            r.Render()
+            ok = bits_equal(r.DownloadRenderbuffer(), ref) and ok
+            r.close()
+    return ok, forms
+
+
 def main(argv=None):
     args = parse_args(argv)
     p = G.load_package()
     fails = 0
     t0 = time.time()
     stats = {"lds": 0, "global": 0, "baseline": 0, "xchg": 0, "triangle_worlds": 0, "tri_kernels": 0}
+    if args.surfaces:
+        stats.update({"surface_worlds": 0, "surface_kernels": 0, "surface_skipped": 0})
     for seed in range(args.first, args.first + args.seeds):
         s, kinds, builder, big, rng = world_of_seed(p, seed, not args.no_triangles, args.force_variant)
         W, H = int(rng.integers(17, 120)), int(rng.integers(9, 80))
@@ -374,6 +411,16 @@ def main(argv=None):
                 if not tx[0]:
                     fails += 1
                     print(f"FAIL seed {seed} with a texture table: kinds {kinds} builder {builder} big {big} cam {ck} depth {depth} modes {tx[2]} forms {tx[1]}", flush=True)
+        if args.surfaces and ok:
+            sf = surfaces_check(p, seed, args, cam, W, H, spp, depth, variant, ref) if info["variant"] in (2, 3) and not (big and builder == 3) else None
+            if sf is None:
+                stats["surface_skipped"] += 1
+            else:
+                stats["surface_worlds"] += 1
+                stats["surface_kernels"] += len(sf[1])
+                if not sf[0]:
+                    fails += 1
+                    print(f"FAIL seed {seed} under inert surface tables: kinds {kinds} triangles {s.n_triangles()} builder {builder} big {big} cam {ck} {W}x{H}x{spp} depth {depth} forms {sf[1]}", flush=True)
         if args.env_tree and ok and kinds >= 1 and info["variant"] in (2, 3) and not (big and builder == 3):   # last: it changes the scene's background
             et = env_tree_check(p, s, cam, ck, W, H, depth, variant)
             if et is not None:
