@@ -14,13 +14,13 @@ import ctypes as C
 
 import numpy as np
 
-import _oracle as O
+import _path_twin as PT
 import _smooth_twin as ST
 import _tex_twin as XT
 import _tri_twin as TT
 import _uv_twin as UT
 from _nee2_twin import world_arrays
-from _nee_twin import F, PRIM_MOVING, _Tape
+from _nee_twin import F, PRIM_MOVING, oracle_trace
 
 MAT_LAMBERTIAN, MAT_METAL, MAT_CHECKER, MAT_NOISE, MAT_IMAGE = 0, 1, 3, 6, 7
 
@@ -49,33 +49,17 @@ def world_image(world_flat):
 
 def primary_rays(cam, width, height, spp, seed, first_sample=0):
     """rays (width * height * spp, 7) float32 of samples [first_sample, first_sample + spp) of every pixel, pixel-major: jitter, then the pinhole ray"""
-    assert cam.type == 0
-    gids = np.repeat(np.arange(width * height, dtype=np.uint32), spp)
-    smp = np.tile(np.arange(first_sample, first_sample + spp, dtype=np.uint32), width * height)
-    n = len(gids)
-    tape = _Tape(seed, gids, smp)
-    with np.errstate(all="ignore"):
-        x, y = (gids % np.uint32(width)).astype(F), (gids // np.uint32(width)).astype(F)
-        psx, psy = F(1) / F(width), F(1) / F(height)
-        ndcx = ((x + F(0.5)) * psx) * F(2) - F(1)
-        ndcy = ((y + F(0.5)) * psy) * F(2) - F(1)
-        jx, jy = tape.in_unit2(np.arange(n))
-        sx, sy = ndcx + jx * psx, ndcy + jy * psy
-        co, cu, cv, cw = (np.array(list(v), F) for v in (cam.o, cam.u, cam.v, cam.w))
-        rays = np.zeros((n, 7), F)
-        rays[:, 0:3] = co
-        rays[:, 3:6] = (cw[None, :] + cu[None, :] * sx[:, None]) + cv[None, :] * sy[:, None]
+    _, ray_o, ray_d = PT.primary_rays(cam, width, height, seed, *PT.keys(width, height, spp, first_sample))
+    rays = np.zeros((len(ray_o), 7), F)
+    rays[:, 0:3], rays[:, 3:6] = ray_o, ray_d
     return rays
 
 
-def first_hits(world, rays):
-    """(hit, t, prim, normal) of the world's own walk"""
+def first_hits(world, rays, trace=TT.closest_intersection):
+    """(hit, t, prim, normal) of the world's own walk: `trace` where _tri_twin walks the world, the oracle's elsewhere"""
     if world.kind in (0, 1) and world.traversal == 0:
-        return TT.closest_intersection(world, rays)
-    n = len(rays)
-    hit, t, prim, nrm = np.zeros(n, np.int32), np.zeros(n, F), np.zeros(n, np.int32), np.zeros((n, 3), F)
-    assert O.lib().orc_trace_batch(C.byref(world), n, np.ascontiguousarray(rays, F), hit, t, prim, nrm) == 0
-    return hit, t, prim, nrm
+        return trace(world, rays)
+    return oracle_trace(world, np.ascontiguousarray(rays, F))
 
 
 def checker_value(even, odd, inv_scale, pos):
@@ -122,11 +106,12 @@ def albedo_of_hits(world, rays, hit, t, prim, normal, textured, uv=None, table=N
     return alb
 
 
-def sums(world, cam, width, height, spp, seed, textured, uv=None, table=None, image=None, noise=None, vn=None, first_sample=0, start=None):
+def sums(world, cam, width, height, spp, seed, textured, uv=None, table=None, image=None, noise=None, vn=None, first_sample=0, start=None,
+         trace=TT.closest_intersection):
     """(H, W, 8) float32: (sum Nx, sum Ny, sum Nz, sum t, sum Ar, sum Ag, sum Ab, hits) of samples [first_sample, first_sample + spp), continued from `start`;
     also the fraction of rays that hit"""
     rays = primary_rays(cam, width, height, spp, seed, first_sample)
-    hit, t, prim, normal = first_hits(world, rays)
+    hit, t, prim, normal = first_hits(world, rays, trace)
     alb = albedo_of_hits(world, rays, hit, t, prim, normal, textured, uv, table, image, noise)
     if vn is not None:   # the smooth form changes the normal sum only
         prims, quads, _ = world_arrays(world)

@@ -1,10 +1,10 @@
 """A numpy float32 twin of one whole sample under the map and the light tree together (mode 48) — test infrastructure only.
 
-radiance() is a COPY of _env_light_twin.radiance (the older twins stay untouched) with mode 48's lines marked §26.  With `light` None it is _env_twin.radiance,
-with `light` = (tables, u0) and `tree` None it is _env_light_twin.radiance statement by statement — tests/test_env_tree_cpu.py pins both bit for bit — and with
-`tree` = table_of(world) it is mode 48: a Lambertian, checker or image-textured hit draws c, below 0.5 — and with a light in the table — c2, takes the map below
-0.5 and the table otherwise, and weighs the path by sp / pdf with pdf = 0.5 sp + 0.5 (0.5 pe + 0.5 pl).  The builder, the walk, the choice and the leaf term are
-_light_tree_twin's own, called as they are; the map's rule and density are _env_light_twin's.
+This module owns MapRule, the light rule of the map modes (32 and 48) as tests/_path_twin.py takes it, and its pieces: pick_half, table_point, light_density.
+radiance() is that loop under it.  With `light` None it is _env_twin.radiance, with `light` = (tables, u0) and `tree` None it is _env_light_twin.radiance —
+tests/test_env_tree_cpu.py holds both bit for bit — and with `tree` = table_of(world) it is mode 48: a Lambertian, checker or image-textured hit draws c, below
+0.5 — and with a light in the table — c2, takes the map below 0.5 and the table otherwise, and weighs the path by sp / pdf with pdf = 0.5 sp + 0.5 (0.5 pe +
+0.5 pl).  The builder, the walk, the choice and the leaf term are _light_tree_twin's own, called as they are; the map's draw and density are _env_light_twin's.
 
 Material 7 (an image-textured Lambertian) is FOLLOWED when `tex` = (uv, table) is given — uv: the scene's table of texture coordinates or None, table:
 [(image, wrap, filter), ...] as _tex_twin.lookup takes it — through _tex_twin.hit_uv and _tex_twin.lookup; it is sampled in mode 48 only.  `stats` counts what a
@@ -15,13 +15,13 @@ import numpy as np
 import _env_light_twin as LT
 import _env_twin as ET
 import _light_tree_twin as TR
+import _path_twin as PT
 import _tex_twin as XT
 import _tri_twin as TT
 from _env_light_twin import density_of, draw
-from _env_twin import primary_rays
 from _light_tree_twin import QUAD, SPHERE, TRIANGLE
-from _nee2_twin import MAT_DIFFUSE_LIGHT, world_arrays
-from _nee_twin import F, INV_PI, PRIM_MOVING, dot, near_zero
+from _nee2_twin import world_arrays
+from _nee_twin import F
 
 MODE = 48       # RT_LIGHT_SAMPLING_ENV_TREE
 MAT_IMAGE = XT.MAT_IMAGE
@@ -114,162 +114,83 @@ def new_stats():
     return st
 
 
-def radiance(world, cam, width, height, max_depth, seed, gids, samples, sky, light=None, tree=None, tex=None, stats=None, walk=None):
-    """Radiance of sample samples[i] of pixel gids[i] with the miss colour sky(directions): ((n, 3) float32, followed (n,) bool).  light = (tables, u0) alone:
-    §24's mixture at Lambertian and checker hits; with tree = table_of(world): §26's at Lambertian, checker and image hits.  _env_light_twin.radiance statement
-    by statement, but for the blocks marked §26 — and §28: walk, the dict a substituted walk (_nmap_twin.mapped_walk) leaves its (u, v) in."""
-    assert cam.type == 0, "the twin restates the pinhole camera"
-    assert tree is None or (light is not None and tree.refused is None)   # §26
-    gids = np.ascontiguousarray(gids, np.uint32)
-    samples = np.ascontiguousarray(samples, np.uint32)
-    n = len(gids)
-    prims, quads, mats = world_arrays(world)
-    mat_of_prim = np.concatenate([(prims["mat"] & ~np.uint32(PRIM_MOVING)), quads["mat"]]).astype(np.int64)
-    m_type, m_albedo, m_albedo2, m_param = mats["type"].astype(np.int64), mats["albedo"].astype(F), mats["albedo2"].astype(F), mats["param"].astype(F)
-    both = tree is not None                                   # §26: mode 48
-    n_l = tree.n_l if both else 0                             # §26
-    scatters = (0, 1, 3, MAT_IMAGE) if tex is not None else (0, 1, 3)   # §26: material 7 is followed where its images are known
-    if stats is not None:
-        stats.setdefault("misses_by_bounce", np.zeros(max_depth, np.int64))
-        for key, zero in new_stats().items():
-            stats.setdefault(key, zero)
-    tape, ray_o, ray_d = primary_rays(cam, width, height, seed, gids, samples)
-    rows = np.arange(n)
-    from_light = np.zeros(n, bool)   # §24 (stats only): the ray being traced was drawn from the map
-    with np.errstate(all="ignore"):
-        atten = np.ones((n, 3), F)
-        accum = np.zeros((n, 3), F)
-        out = np.zeros((n, 3), F)
-        followed = np.ones(n, bool)
-        live = rows.copy()
-        for bounce in range(max_depth):
-            if len(live) == 0:
-                break
-            k = len(live)
-            rays = np.zeros((k, 7), F)
-            rays[:, 0:3], rays[:, 3:6] = ray_o[live], ray_d[live]
-            hit, t, prim, normal = TT.closest_intersection(world, rays)
-            o, d = rays[:, 0:3], rays[:, 3:6]
-            miss = hit == 0
+class MapRule:
+    """The light rule of the map modes for _path_twin.radiance: light = (tables, u0) alone is §24's (mode 32: a Lambertian or checker hit is sampled, and its
+    light half is the map's); with tree = table_of(world) it is §26's (mode 48: an image-textured hit is sampled too, and the light half is shared by the map and
+    the table)."""
+
+    def __init__(self, world, light, tree=None):
+        assert tree is None or tree.refused is None
+        self.prims, self.quads, _ = world_arrays(world)
+        self.light, self.tree, self.images = light, tree, tree is not None
+
+    def pick(self, tape, r, sampled, mt, hit_p, new_d, stats):
+        """The draws, in order: c and — mode 48, with a light in the table — c2 (pick_half); the map's x1, x2, a, b (draw), or §20's choice and point
+        (table_point)."""
+        tree, k = self.tree, len(r)
+        to_light, to_env = np.zeros(k, bool), np.zeros(k, bool)   # to_env: light-half draws that go to the map
+        drawn = np.full(k, -1, np.int64)                          # the light of the table a light-half draw went to
+        if sampled.any():
+            if tree is not None:
+                had = tape.cur[r[sampled]].copy()
+                tl, te = pick_half(tape, r[sampled], tree.n_l)
+                to_light[np.nonzero(sampled)[0]], to_env[np.nonzero(sampled)[0]] = tl, te
+                if stats is not None:
+                    stats["second_draws"] += int((tape.cur[r[sampled]] - had == 2).sum())
+                    stats["image_sampled"] += int((mt[sampled] == MAT_IMAGE).sum())
+                    stats["image_light_half"] += int((to_light & (mt == MAT_IMAGE)).sum())
+            else:
+                c = tape.next(r[sampled])
+                to_light[np.nonzero(sampled)[0]] = c < F(0.5)
+                to_env = to_light.copy()
+        if to_env.any():
+            s = np.nonzero(to_env)[0]
+            four = np.stack([tape.next(r[s]) for _ in range(4)], axis=1)
+            new_d[s] = draw(self.light[0], self.light[1], four)[0]
             if stats is not None:
-                stats["light_half_hit"] += int((from_light[live] & ~miss).sum())
-            if miss.any():
-                out[live[miss]] = atten[live[miss]] * np.asarray(sky(d[miss]), F) + accum[live[miss]]
-                if stats is not None:
-                    stats["misses_by_bounce"][bounce] += int(miss.sum())
-            mi = mat_of_prim[np.where(miss, 0, prim)]
-            mt = np.where(miss, -1, m_type[mi])
-            lit = mt == MAT_DIFFUSE_LIGHT   # a light of either kind: emits, never scatters
-            accum[live[lit]] = accum[live[lit]] + atten[live[lit]] * m_albedo[mi[lit]]
-            out[live[lit]] = accum[live[lit]]
-            other = ~miss & ~lit & ~np.isin(mt, scatters)
-            followed[live[other]] = False
-            out[live[other]] = np.nan
-            go = np.isin(mt, scatters)
-            if bounce + 1 >= max_depth:
-                out[live[go]] = accum[live[go]]
-                break
-            sel = np.nonzero(go)[0]
-            r = live[sel]
-            if tex is not None:   # §26: the texture coordinates of every hit that goes on, before the arrays are cut down to them
-                tuv = XT.hit_uv(world, tex[0], rays[sel], hit[sel], t[sel], prim[sel], normal[sel])
-                tuv, walked = XT.prefer_walk_uv(tuv, walk, sel)   # §28: a mapped hit's (u, v) is the walk's, from before the map
-            o, d, t, normal, mi, mt = o[sel], d[sel], t[sel], normal[sel], mi[sel], mt[sel]
-            hit_p = o + d * t[:, None]
-            k = len(r)
-            lamb = mt != 1
-            sampled = lamb & ((mt != MAT_IMAGE) | both)   # §26: an image hit is a diffuse hit; modes 0 and 32 leave it to the cosine lobe alone
-            ok = np.ones(k, bool)
-            new_d = np.zeros((k, 3), F)
-            # §24: the first draw of a Lambertian / checker hit picks the half; the map's half draws x1, x2, a, b and no on-unit vector
-            weight = np.ones(k, F)
-            weighted = np.zeros(k, bool)
-            to_light = np.zeros(k, bool)
-            to_env = np.zeros(k, bool)          # §26: light-half draws that go to the map
-            drawn = np.full(k, -1, np.int64)    # §26: the light of the table a light-half draw went to
-            if light is not None and sampled.any():
-                if both:   # §26: c, then — with a light in the table — c2
-                    had = tape.cur[r[sampled]].copy()
-                    tl, te = pick_half(tape, r[sampled], n_l)
-                    to_light[np.nonzero(sampled)[0]], to_env[np.nonzero(sampled)[0]] = tl, te
-                    if stats is not None:
-                        stats["second_draws"] += int((tape.cur[r[sampled]] - had == 2).sum())
-                        stats["image_sampled"] += int((mt[sampled] == MAT_IMAGE).sum())
-                        stats["image_light_half"] += int((to_light & (mt == MAT_IMAGE)).sum())
-                else:
-                    c = tape.next(r[sampled])
-                    to_light[np.nonzero(sampled)[0]] = c < F(0.5)
-                    to_env = to_light.copy()
-            if to_env.any():
-                s = np.nonzero(to_env)[0]
-                four = np.stack([tape.next(r[s]) for _ in range(4)], axis=1)
-                new_d[s] = draw(light[0], light[1], four)[0]
-                if stats is not None:
-                    stats["light_half"] += len(s)
-                    stats["map_draws"] += len(s) if both else 0
-                    stats["checker_light_half"] += int((mt[s] == 3).sum())
-            to_table = to_light & ~to_env
-            if to_table.any():   # §26: §20's choice and point
-                s = np.nonzero(to_table)[0]
-                drawn[s], new_d[s] = table_point(tape, r[s], tree, prims, quads, hit_p[s], stats)
-            s = np.nonzero(~to_light)[0]
-            if len(s):
-                on_unit = tape.on_unit3(r[s])
-                sl, sm = s[lamb[s]], s[~lamb[s]]
-                new_d[sl] = normal[sl] + on_unit[lamb[s]]
-                ok[sl] = ~near_zero(new_d[sl])
-                dn = dot(normal[sm], d[sm])
-                refl = d[sm] - (normal[sm] * dn[:, None]) * F(2)
-                new_d[sm] = refl + on_unit[~lamb[s]] * m_param[mi[sm]][:, None]
-                ok[sm] = ~((dot(new_d[sm], normal[sm]) < F(0)) | near_zero(new_d[sm]))
-            albedo = m_albedo[mi].copy()
-            chk = np.nonzero(mt == 3)[0]
-            if len(chk):
-                sp = hit_p[chk] * m_param[mi[chk]][:, None]
-                ssum = np.trunc(sp).astype(np.int64).sum(axis=1)
-                albedo[chk] = np.where((ssum % 2 == 0)[:, None], m_albedo[mi[chk]], m_albedo2[mi[chk]])
-            img = np.nonzero(mt == MAT_IMAGE)[0]   # §26: the albedo of an image hit, behind the direction: the table's entry at the hit's coordinates
-            if len(img):
-                albedo[img] = XT.lookup(tex[1], m_albedo2[mi[img]][:, 0].astype(np.int64), tuv[img, 0], tuv[img, 1])
-                XT.count_walk_uv(walk, walked[img].sum())
-            if light is not None:   # §24: the densities of the direction under both halves
-                s = np.nonzero(sampled & ok)[0]
-                if len(s):
-                    dd, nn = new_d[s], normal[s]
-                    len2 = dot(dd, dd)
-                    ln = np.sqrt(len2)
-                    cosn = dot(nn, dd) / ln
-                    pdf_cos = np.where(cosn > F(0), cosn * INV_PI, F(0)).astype(F)
-                    if both:   # §26: pm = 0.5 pe + 0.5 pl by §20's walk (n_l == 0: pe), and the silhouette rule for a drawn sphere
-                        pdf_light, own_lost = light_density(tree, light, prims, quads, hit_p[s], dd, len2, ln, to_table[s], drawn[s], stats)
-                        if stats is not None:
-                            stats["sphere_uncredited"] += int(own_lost.sum())
-                    else:
-                        pdf_light, own_lost = density_of(light[0], light[1], dd), np.zeros(len(s), bool)
-                    pdf = F(0.5) * pdf_cos + F(0.5) * pdf_light
-                    good = ~(pdf_cos == F(0)) & (pdf > F(0)) & ~own_lost
-                    if stats is not None:
-                        stats["below_surface"] += int((pdf_cos == F(0)).sum())
-                    ok[s[~good]] = False
-                    weight[s[good]] = pdf_cos[good] / pdf[good]
-                    weighted[s[good]] = True
-                albedo = np.where(weighted[:, None], albedo * weight[:, None], albedo)
-            out[r[~ok]] = accum[r[~ok]]
-            from_light[r] = to_env
-            r, new_d, hit_p, albedo = r[ok], new_d[ok], hit_p[ok], albedo[ok]
-            atten[r] = atten[r] * albedo
-            ray_d[r] = new_d
-            ray_o[r] = hit_p + new_d * F(0.001)
-            live = r
-    return out, followed
+                stats["light_half"] += len(s)
+                stats["checker_light_half"] += int((mt[s] == 3).sum())
+                if tree is not None:
+                    stats["map_draws"] += len(s)
+        to_table = to_light & ~to_env
+        if to_table.any():
+            s = np.nonzero(to_table)[0]
+            drawn[s], new_d[s] = table_point(tape, r[s], tree, self.prims, self.quads, hit_p[s], stats)
+        return to_light, to_env, (to_table, drawn)
+
+    def density(self, picked, s, hp, dd, len2, ln, pdf_cos, stats):
+        """(the map's density of dd, or pm = 0.5 pe + 0.5 pl by §20's walk; own_lost: the silhouette rule for a drawn sphere)"""
+        if self.tree is not None:
+            pdf_light, own_lost = light_density(self.tree, self.light, self.prims, self.quads, hp, dd, len2, ln, picked[0][s], picked[1][s], stats)
+            if stats is not None:
+                stats["sphere_uncredited"] += int(own_lost.sum())
+        else:
+            pdf_light, own_lost = density_of(self.light[0], self.light[1], dd), np.zeros(len(s), bool)
+        if stats is not None:
+            stats["below_surface"] += int((pdf_cos == F(0)).sum())
+        return pdf_light, own_lost
 
 
-def frame_samples(world, cam, width, height, spp, max_depth, seed, sky, light=None, tree=None, tex=None, first_sample=0, stats=None, walk=None):
+def map_radiance(world, cam, width, height, max_depth, seed, gids, samples, sky, light, tree, tex, mfacs, stats, walk, trace, glass):
+    """the loop of _path_twin under the map's rule (light None: the cosine lobe alone), for this module and the surface twins above it"""
+    assert tree is None or light is not None
+    return PT.radiance(world, cam, width, height, max_depth, seed, gids, samples, trace, sky=sky, rule=MapRule(world, light, tree) if light is not None else None,
+                       tex=tex, mfacs=mfacs, walk=walk, glass=glass, stats=stats)
+
+
+def radiance(world, cam, width, height, max_depth, seed, gids, samples, sky, light=None, tree=None, tex=None, stats=None, walk=None, trace=TT.closest_intersection):
+    """Radiance of sample samples[i] of pixel gids[i] with the miss colour sky(directions): ((n, 3) float32, followed (n,) bool).  light = (tables, u0) alone:
+    §24's mixture at Lambertian and checker hits; with tree = table_of(world): §26's at Lambertian, checker and image hits.  walk: the dict a mapped walk
+    (_nmap_twin.mapped_walk, passed as `trace`) leaves its (u, v) in (§28).  A dielectric hit is not followed."""
+    stats = PT.counters(stats, {"misses_by_bounce": np.zeros(max_depth, np.int64), **new_stats()})
+    return map_radiance(world, cam, width, height, max_depth, seed, gids, samples, sky, light, tree, tex, None, stats, walk, trace, False)
+
+
+def frame_samples(world, cam, width, height, spp, max_depth, seed, sky, light=None, tree=None, tex=None, first_sample=0, stats=None, walk=None,
+                  trace=TT.closest_intersection):
     """(height, width, spp, 3) float32: every sample of every pixel; followed (height, width, spp)"""
-    gids = np.repeat(np.arange(width * height, dtype=np.uint32), spp)
-    smp = np.tile(np.arange(first_sample, first_sample + spp, dtype=np.uint32), width * height)
-    rad, ok = radiance(world, cam, width, height, max_depth, seed, gids, smp, sky, light, tree, tex, stats, walk)
-    return rad.reshape(height, width, spp, 3), ok.reshape(height, width, spp)
+    return PT.frame_samples(lambda g, s: radiance(world, cam, width, height, max_depth, seed, g, s, sky, light, tree, tex, stats, walk, trace), width, height, spp,
+                            first_sample)
 
 
 in_order_sums, resolve = ET.in_order_sums, ET.resolve

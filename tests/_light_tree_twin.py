@@ -1,9 +1,9 @@
 """The numpy float32 twin of one whole sample for light sampling through a light tree, with the light chosen by area (mode 16) — test
 infrastructure only.
 
-tests/_mesh_light_twin.py restates §19 (modes 0, 1, 2 and 4) and stays as it is.  This module has a radiance() of its own that also takes mode 16 =
-RT_LIGHT_SAMPLING_TREE: mode 4's lights, permuted into the leaf order of a median-split tree over their padded boxes.  What mode 16 adds are functions of their
-own, so that a test can hold each to something no kernel shares (tests/test_light_tree_cpu.py):
+tests/_mesh_light_twin.py owns §19 (mode 4's table and the triangle rules).  This module owns mode 16 = RT_LIGHT_SAMPLING_TREE: mode 4's lights, permuted into
+the leaf order of a median-split tree over their padded boxes.  What mode 16 adds are functions of their own, so that a test can hold each to something no
+kernel shares (tests/test_light_tree_cpu.py):
 
     light_boxes(prims, quads, kind, index, M)   the padded box of every light: its vertices' box widened by PAD * M (a sphere: by that + (PAD_SPHERE * (M * M)) / r)
     build_tree(bmin, bmax)                      the builder: (order, lo, hi, skip, leaf) — preorder nodes, leaves in table order
@@ -14,24 +14,24 @@ own, so that a test can hold each to something no kernel shares (tests/test_ligh
     leaf_term(tree, prims, quads, j, ...)       mode 4's pl_j without its division by area_j
     tree_density(...), linear_density(...)      the sum over the walk, and over every light of the same table: equal bit for bit when the walk misses nothing
 
-radiance() below is a COPY of _mesh_light_twin.radiance: all but the lines marked §20 are its text.  tests/test_light_tree_cpu.py pins it before anything is
-compared with it: in modes 0, 1, 2 and 4 it equals _mesh_light_twin on every world, bit for bit.
+It also owns TableRule, the light rule of every table mode (1, 2, 4 and 16) as tests/_path_twin.py takes it: which half a hit takes and the light half's
+point — uniform or by-area choice, then the kind's draws — and the density of the chosen direction, the per-light sum or the tree walk.  radiance() is that
+loop under it; tests/test_light_tree_cpu.py pins it before anything is compared with it: in modes 0, 1, 2 and 4 it equals _mesh_light_twin on every world,
+bit for bit.
 
 Scope: _tri_twin's.
 """
 import numpy as np
 
+import _mesh_light_twin as MT
 import _nee2_twin as T2
 import _nee_twin as T
-import _tri_twin as TT
-from _nee2_twin import QUAD, SPHERE, MAT_DIFFUSE_LIGHT, world_arrays
-from _nee_twin import F, INV_PI, MAX_LIGHTS, MISS, PRIM_MOVING, _Tape, cross, dot, near_zero
-from _tri_twin import closest_intersection, first_hit_sums, kinds
+import _path_twin as PT
+from _mesh_light_twin import MAX_LIGHTS_MESH, TRIANGLE, _tri_hit, _tri_pl, _tri_point, lights_of, triangle_lights  # noqa: F401
+from _nee2_twin import QUAD, SPHERE, world_arrays
+from _nee_twin import F, MAX_LIGHTS, count, dot
+from _tri_twin import closest_intersection, first_hit_sums  # noqa: F401
 
-import _mesh_light_twin as MT
-
-TRIANGLE = 2            # RT_LIGHT_TRIANGLE
-MAX_LIGHTS_MESH = 64    # RT_MAX_LIGHTS_MESH
 MAX_LIGHTS_TREE = 4096  # RT_MAX_LIGHTS_TREE
 PAD = F(2.0 ** -10)           # RT_LIGHT_TREE_PAD
 PAD_SPHERE = F(2.0 ** -18)    # RT_LIGHT_TREE_PAD_SPHERE
@@ -222,25 +222,6 @@ def linear_density(t, prims, quads, hp, dd, len2, ln):
     return total, positive
 
 
-def triangle_lights(quads, mats):
-    """(quad indices, areas): the triangles whose material is a diffuse light, in quad-index order; area = 0.5f * sqrt(dot(n, n)), n = cross(u, v)"""
-    idx = np.array([i for i in range(len(quads)) if quads["kind"][i] == 1 and mats["type"][quads["mat"][i]] == MAT_DIFFUSE_LIGHT], dtype=np.uint32)
-    if len(idx) == 0:
-        return idx, np.zeros(0, F)
-    n = cross(quads["u"][idx].astype(F), quads["v"][idx].astype(F))
-    return idx, (F(0.5) * np.sqrt(dot(n, n))).astype(F)
-
-
-def lights_of(prims, quads, mats, mode):
-    """(kind, index, area) of the light table of `mode`: _tri_twin.lights_of for modes 1 and 2; mode 4: mode 2's table, then the triangle lights"""
-    if mode != 4:
-        return TT.lights_of(prims, quads, mats, mode)
-    kind, index, area = TT.lights_of(prims, quads, mats, 2)
-    t_idx, t_area = triangle_lights(quads, mats)
-    return (np.concatenate([kind, np.full(len(t_idx), TRIANGLE, np.int64)]), np.concatenate([index, t_idx.astype(np.int64)]),
-            np.concatenate([area, t_area]).astype(F))
-
-
 def new_stats(n=MAX_LIGHTS_MESH):
     """(§20: light_samples over a table of n; tree_leaves: leaf visits of the walks; tree_sphere_uncredited: drawn spheres the walk did not credit)
     _nee2_twin's counters with light_samples[i] over a table of 64, and for triangle lights: tri_light_half: light-half draws sent to a triangle light;
@@ -254,274 +235,148 @@ def new_stats(n=MAX_LIGHTS_MESH):
     return st
 
 
-def _tri_point(a, b, Q, u, v, hit_p):
-    """§19's drawn point: a, b (n,) uniforms; Q, u, v (n, 3) or (3,); hit_p (n, 3): the unnormalised direction (n, 3) to the folded point"""
-    a, b = np.asarray(a, F), np.asarray(b, F)
-    Q, u, v = (np.broadcast_to(np.asarray(x, F), hit_p.shape) for x in (Q, u, v))
-    fold = (a + b) > F(1)   # one fp32 add; exactly 1 stays
-    a2 = np.where(fold, F(1) - a, a).astype(F)
-    b2 = np.where(fold, F(1) - b, b).astype(F)
-    return ((Q + u * a2[:, None]) + v * b2[:, None]) - hit_p
+class TableRule:
+    """The light rule of the table modes for _path_twin.radiance: table = (kind, index, area) as a lights_of() lists it (modes 1, 2, 4), or, tree = tree_of(world),
+    the permuted table with the light chosen by area and the density by the walk (mode 16).  A Lambertian or checker hit is sampled."""
+    images = False
 
+    def __init__(self, world, table, tree=None):
+        self.prims, self.quads, _ = world_arrays(world)
+        self.kind, self.index, self.area = (tree.kind, tree.index, tree.area) if tree is not None else table
+        self.tree, self.n_l = tree, len(self.kind)
 
-def _tri_hit(q, o, d):
-    """quad_closest_intersection with RT_QUAD_TRIANGLE of one record on rays (o, d) over a fresh trace's interval: _nee_twin._quad_hit's arithmetic and the
-    kind rule !(alpha + beta <= 1)"""
-    n = np.broadcast_to(q["normal"].astype(F), d.shape)
-    denom = dot(n, d)
-    t = (F(q["D"]) - dot(n, o)) / denom
-    hit = ~(np.abs(denom) < F(1e-8)) & ~(t < F(0)) & ~(t >= MISS)
-    planar = (o + d * t[:, None]) - q["Q"].astype(F)[None, :]
-    w = np.broadcast_to(q["w"].astype(F), d.shape)
-    alpha = dot(w, cross(planar, np.broadcast_to(q["v"].astype(F), d.shape)))
-    beta = dot(w, cross(np.broadcast_to(q["u"].astype(F), d.shape), planar))
-    hit &= (alpha >= F(0)) & (alpha <= F(1)) & (beta >= F(0)) & (beta <= F(1))
-    hit &= (alpha + beta) <= F(1)
-    return hit, t
-
-
-def _tri_pl(q, area, hp, dd, len2, ln):
-    """§19's density of one triangle light (flat record q, area) along rays (hp, dd): (pl_j, hit)"""
-    thit, t = _tri_hit(q, hp, dd)
-    nj = np.broadcast_to(q["normal"].astype(F), dd.shape)
-    pl = ((t * t) * len2) / ((np.abs(dot(dd, nj)) / ln) * F(area))
-    return np.where(thit, pl, F(0)).astype(F), thit
-
-
-def radiance(world, cam, width, height, max_depth, seed, gids, samples, mode=0, stats=None):
-    """Radiance of sample samples[i] of pixel gids[i]: ((n, 3) float32, followed (n,) bool); mode 0 / 1 / 2 / 4 / 16 as rt_renderer_light_sampling_enable takes
-    it.  _mesh_light_twin.radiance statement by statement, but for the lines marked §20 below."""
-    assert cam.type == 0, "the twin restates the pinhole camera"
-    assert mode in (0, 1, 2, 4, 16)   # §20
-    gids = np.ascontiguousarray(gids, np.uint32)
-    samples = np.ascontiguousarray(samples, np.uint32)
-    n = len(gids)
-    prims, quads, mats = world_arrays(world)
-    tree = tree_of(world) if mode == 16 else None   # §20
-    l_kind, l_index, l_area = (tree.kind, tree.index, tree.area) if mode == 16 else lights_of(prims, quads, mats, mode)   # §20: mode 4's lights in leaf order
-    n_l = len(l_kind)
-    if mode:
-        assert 1 <= n_l <= (MAX_LIGHTS_TREE if mode == 16 else MAX_LIGHTS_MESH if mode == 4 else MAX_LIGHTS)   # §20
-        assert mode != 16 or tree.refused is None   # §20
-    mat_of_prim = np.concatenate([(prims["mat"] & ~np.uint32(PRIM_MOVING)), quads["mat"]]).astype(np.int64)
-    m_type, m_albedo, m_albedo2, m_param = mats["type"].astype(np.int64), mats["albedo"].astype(F), mats["albedo2"].astype(F), mats["param"].astype(F)
-
-    if stats is not None:
-        for key, zero in new_stats(max(n_l, MAX_LIGHTS_MESH)).items():   # §20
-            stats.setdefault(key, zero)
-    tape = _Tape(seed, gids, samples)
-    rows = np.arange(n)
-    with np.errstate(all="ignore"):
-        x, y = (gids % np.uint32(width)).astype(F), (gids // np.uint32(width)).astype(F)
-        psx, psy = F(1) / F(width), F(1) / F(height)
-        ndcx = ((x + F(0.5)) * psx) * F(2) - F(1)
-        ndcy = ((y + F(0.5)) * psy) * F(2) - F(1)
-        jx, jy = tape.in_unit2(rows)
-        sx, sy = ndcx + jx * psx, ndcy + jy * psy
-        co, cu, cv, cw = (np.array(list(v), F) for v in (cam.o, cam.u, cam.v, cam.w))
-        ray_o = np.broadcast_to(co, (n, 3)).copy()
-        ray_d = (cw[None, :] + cu[None, :] * sx[:, None]) + cv[None, :] * sy[:, None]
-
-        atten = np.ones((n, 3), F)
-        accum = np.zeros((n, 3), F)
-        out = np.zeros((n, 3), F)
-        followed = np.ones(n, bool)
-        live = rows.copy()
-        for bounce in range(max_depth):
-            if len(live) == 0:
-                break
-            k = len(live)
-            rays = np.zeros((k, 7), F)
-            rays[:, 0:3], rays[:, 3:6] = ray_o[live], ray_d[live]
-            hit, t, prim, normal = closest_intersection(world, rays)   # the one step that is not _nee2_twin's: the walk below, which knows the kind
-            o, d = rays[:, 0:3], rays[:, 3:6]
-            miss = hit == 0
-            if miss.any():
-                dm = d[miss]
-                if world.background == 1:
-                    sky = np.broadcast_to(np.array(list(world.background_color), F), dm.shape)
-                else:
-                    inv = F(1) / np.sqrt(dot(dm, dm))
-                    tt = (dm[:, 1] * inv) * F(0.5) + F(0.5)
-                    a, b = np.array([0.1, 0.2, 0.4], F), np.array([0.9, 0.9, 0.99], F)
-                    sky = a[None, :] + (b - a)[None, :] * tt[:, None]
-                out[live[miss]] = atten[live[miss]] * sky + accum[live[miss]]
-            mi = mat_of_prim[np.where(miss, 0, prim)]
-            mt = np.where(miss, -1, m_type[mi])
-            lit = mt == MAT_DIFFUSE_LIGHT   # a light of either kind: emits, never scatters
-            accum[live[lit]] = accum[live[lit]] + atten[live[lit]] * m_albedo[mi[lit]]
-            out[live[lit]] = accum[live[lit]]
-            other = ~miss & ~lit & ~np.isin(mt, (0, 1, 3))
-            followed[live[other]] = False
-            out[live[other]] = np.nan
-            go = np.isin(mt, (0, 1, 3))
-            if bounce + 1 >= max_depth:
-                out[live[go]] = accum[live[go]]
-                break
-            sel = np.nonzero(go)[0]
-            r = live[sel]
-            o, d, t, normal, mi, mt = o[sel], d[sel], t[sel], normal[sel], mi[sel], mt[sel]
-            hit_p = o + d * t[:, None]
-            k = len(r)
-            lamb = mt != 1
-            ok = np.ones(k, bool)
-            new_d = np.zeros((k, 3), F)
-            weight = np.ones(k, F)
-            weighted = np.zeros(k, bool)
-            to_light = np.zeros(k, bool)
-            drawn = np.full(k, -1, np.int64)   # the light a light-half draw went to
-            if mode and lamb.any():
-                c = tape.next(r[lamb])
-                to_light[np.nonzero(lamb)[0]] = c < F(0.5)
-            if to_light.any():
-                s = np.nonzero(to_light)[0]
-                li = np.zeros(len(s), np.int64)
-                if n_l > 1 and mode == 16:   # §20: by area — the smallest j with c_j > next * A
-                    xs = tape.next(r[s]) * tree.A
-                    li = choose(tree.cdf, xs)
-                    if stats is not None:
-                        stats["index_clamped"] += int((~(tree.A > xs)).sum())
-                elif n_l > 1:
-                    scaled = (tape.next(r[s]) * F(n_l)).astype(np.uint32)
-                    li = np.minimum(scaled, np.uint32(n_l - 1)).astype(np.int64)
-                    if stats is not None:
-                        stats["index_clamped"] += int((scaled >= n_l).sum())
-                drawn[s] = li
+    def pick(self, tape, r, sampled, mt, hit_p, new_d, stats):
+        """The draws, in order: c (below 0.5: the light half); the light — none for one light, next * n_l clamped or, by area, the smallest j with
+        c_j > next * A —; the point: a triangle's two draws folded, a parallelogram's two draws, a sphere's on-unit vector, rejection loop and all."""
+        prims, quads, l_kind, l_index, n_l = self.prims, self.quads, self.kind, self.index, self.n_l
+        to_light = np.zeros(len(r), bool)
+        drawn = np.full(len(r), -1, np.int64)   # the light a light-half draw went to
+        if sampled.any():
+            c = tape.next(r[sampled])
+            to_light[np.nonzero(sampled)[0]] = c < F(0.5)
+        if to_light.any():
+            s = np.nonzero(to_light)[0]
+            li = np.zeros(len(s), np.int64)
+            if n_l > 1 and self.tree is not None:
+                xs = tape.next(r[s]) * self.tree.A
+                li = choose(self.tree.cdf, xs)
+                clamped = ~(self.tree.A > xs)
+            elif n_l > 1:
+                scaled = (tape.next(r[s]) * F(n_l)).astype(np.uint32)
+                li = np.minimum(scaled, np.uint32(n_l - 1)).astype(np.int64)
+                clamped = scaled >= n_l
+            drawn[s] = li
+            if stats is not None:
+                stats["index_clamped"] += int(clamped.sum()) if n_l > 1 else 0
+                stats["light_samples"] += np.bincount(li, minlength=len(stats["light_samples"]))
+                stats["checker_light_half"] += int((mt[s] == 3).sum())
+                count(stats, "sphere_light_half", int((l_kind[li] == SPHERE).sum()))
+            sq_, ss_, st_ = s[l_kind[li] == QUAD], s[l_kind[li] == SPHERE], s[l_kind[li] == TRIANGLE]
+            if len(st_):   # §19: a, b folded into the triangle: a point uniform over its area; no on-unit draw
+                la = tape.next(r[st_])
+                lb = tape.next(r[st_])
+                q = quads[l_index[drawn[st_]]]
+                new_d[st_] = _tri_point(la, lb, q["Q"].astype(F), q["u"].astype(F), q["v"].astype(F), hit_p[st_])
                 if stats is not None:
-                    stats["light_samples"] += np.bincount(li, minlength=len(stats["light_samples"]))   # §20
-                    stats["checker_light_half"] += int((mt[s] == 3).sum())
-                    stats["sphere_light_half"] += int((l_kind[li] == SPHERE).sum())
-                sq_, ss_ = s[l_kind[li] == QUAD], s[l_kind[li] == SPHERE]
-                st_ = s[l_kind[li] == TRIANGLE]   # §19, to the end of the block
-                if len(st_):   # a, b folded into the triangle: a point uniform over its area; no on-unit draw
-                    la = tape.next(r[st_])
-                    lb = tape.next(r[st_])
-                    q = quads[l_index[drawn[st_]]]
-                    new_d[st_] = _tri_point(la, lb, q["Q"].astype(F), q["u"].astype(F), q["v"].astype(F), hit_p[st_])
-                    if stats is not None:
-                        stats["tri_light_half"] += len(st_)
-                        stats["tri_folded"] += int(((la + lb) > F(1)).sum())
-                if len(sq_):   # a, b: a point of the parallelogram
-                    la = tape.next(r[sq_])
-                    lb = tape.next(r[sq_])
-                    q = quads[l_index[drawn[sq_]]]
-                    new_d[sq_] = ((q["Q"].astype(F) + q["u"].astype(F) * la[:, None]) + q["v"].astype(F) * lb[:, None]) - hit_p[sq_]
-                if len(ss_):   # rng_on_unit3, rejection loop and all: a point of the sphere, uniform over its area
-                    u = tape.on_unit3(r[ss_])
-                    sp_ = prims[l_index[drawn[ss_]]]
-                    new_d[ss_] = (sp_["c0"].astype(F) + u * sp_["radius"].astype(F)[:, None]) - hit_p[ss_]
-            s = np.nonzero(~to_light)[0]
-            if len(s):
-                on_unit = tape.on_unit3(r[s])
-                sl, sm = s[lamb[s]], s[~lamb[s]]
-                new_d[sl] = normal[sl] + on_unit[lamb[s]]
-                ok[sl] = ~near_zero(new_d[sl])
-                dn = dot(normal[sm], d[sm])
-                refl = d[sm] - (normal[sm] * dn[:, None]) * F(2)
-                new_d[sm] = refl + on_unit[~lamb[s]] * m_param[mi[sm]][:, None]
-                ok[sm] = ~((dot(new_d[sm], normal[sm]) < F(0)) | near_zero(new_d[sm]))
-            albedo = m_albedo[mi].copy()
-            chk = np.nonzero(mt == 3)[0]
-            if len(chk):
-                sp = hit_p[chk] * m_param[mi[chk]][:, None]
-                ssum = np.trunc(sp).astype(np.int64).sum(axis=1)
-                albedo[chk] = np.where((ssum % 2 == 0)[:, None], m_albedo[mi[chk]], m_albedo2[mi[chk]])
-            if mode:
-                s = np.nonzero(lamb & ok)[0]
-                if len(s):
-                    dd, nn, hp = new_d[s], normal[s], hit_p[s]
-                    len2 = dot(dd, dd)
-                    ln = np.sqrt(len2)
-                    cosn = dot(nn, dd) / ln
-                    pdf_cos = np.where(cosn > F(0), cosn * INV_PI, F(0)).astype(F)
-                    pdf_light = np.zeros(len(s), F)
-                    met = np.zeros(len(s), np.int64)          # lights the direction meets (stats only)
-                    met_sphere = np.zeros(len(s), np.int64)
-                    met_tri = np.zeros(len(s), np.int64)      # §19 (stats only)
-                    own_lost = np.zeros(len(s), bool)         # light-half draws whose own sphere gives !(disc > 0): a failed scatter
-                    if mode == 16:   # §20, to the end of the branch: the walk instead of the loop, terms without their areas, one division by A
-                        credited = np.zeros(len(s), bool)   # drawn spheres whose leaf the walk reached with disc > 0
+                    stats["tri_light_half"] += len(st_)
+                    stats["tri_folded"] += int(((la + lb) > F(1)).sum())
+            if len(sq_):   # a, b: a point of the parallelogram
+                la = tape.next(r[sq_])
+                lb = tape.next(r[sq_])
+                q = quads[l_index[drawn[sq_]]]
+                new_d[sq_] = ((q["Q"].astype(F) + q["u"].astype(F) * la[:, None]) + q["v"].astype(F) * lb[:, None]) - hit_p[sq_]
+            if len(ss_):   # rng_on_unit3, rejection loop and all: a point of the sphere, uniform over its area
+                u = tape.on_unit3(r[ss_])
+                sp_ = prims[l_index[drawn[ss_]]]
+                new_d[ss_] = (sp_["c0"].astype(F) + u * sp_["radius"].astype(F)[:, None]) - hit_p[ss_]
+        return to_light, np.zeros(len(r), bool), (to_light, drawn)
 
-                        def on_leaf(rr, j, term, hit, pos):
-                            met[rr] += hit
-                            if l_kind[j] == TRIANGLE:
-                                met_tri[rr] += hit
-                            if l_kind[j] == SPHERE:
-                                met_sphere[rr] += hit
-                                credited[rr] |= to_light[s][rr] & (drawn[s][rr] == j) & pos
-                            if stats is not None:
-                                stats["tree_leaves"] += len(rr)
+    def density(self, picked, s, hp, dd, len2, ln, pdf_cos, stats):
+        """(pl of the directions dd from hp, own_lost: light-half draws whose own sphere gives !(disc > 0) — a failed scatter): the sum of the lights' pl_j
+        over n_l or, with the tree, the walk's sum of the terms without their areas over A"""
+        prims, quads, l_kind, l_index, l_area, tree = self.prims, self.quads, self.kind, self.index, self.area, self.tree
+        to_light, drawn = picked[0][s], picked[1][s]
+        pdf_light = np.zeros(len(s), F)
+        met = np.zeros(len(s), np.int64)          # lights the direction meets (stats only)
+        met_sphere = np.zeros(len(s), np.int64)
+        met_tri = np.zeros(len(s), np.int64)
+        own_lost = np.zeros(len(s), bool)
+        if tree is not None:   # §20
+            credited = np.zeros(len(s), bool)   # drawn spheres whose leaf the walk reached with disc > 0
 
-                        pdf_light = tree_density(tree, prims, quads, hp, dd, len2, ln, on_leaf)
-                        own_lost = to_light[s] & (drawn[s] >= 0) & (l_kind[np.maximum(drawn[s], 0)] == SPHERE) & ~credited
-                        if stats is not None:
-                            stats["tree_sphere_uncredited"] += int(own_lost.sum())
-                    for j in range(n_l if mode != 16 else 0):   # §20
-                        if l_kind[j] == QUAD:
-                            q = quads[l_index[j]]
-                            qhit, qt = _quad_hit(q, hp, dd)
-                            nj = np.broadcast_to(q["normal"].astype(F), dd.shape)
-                            pl = ((qt * qt) * len2) / ((np.abs(dot(dd, nj)) / ln) * l_area[j])
-                            pdf_light = pdf_light + np.where(qhit, pl, F(0)).astype(F)
-                            met += qhit
-                        elif l_kind[j] == TRIANGLE:   # §19, to the end of the branch
-                            q = quads[l_index[j]]
-                            pl, thit = _tri_pl(q, l_area[j], hp, dd, len2, ln)
-                            pdf_light = pdf_light + pl
-                            met += thit
-                            met_tri += thit
-                            if stats is not None:
-                                stats["tri_own_missed"] += int((to_light[s] & (drawn[s] == j) & ~thit).sum())
-                        else:
-                            pr = prims[l_index[j]]
-                            pl, pos, t1, t2 = T2._sphere_pl(pr["c0"].astype(F), F(pr["radius"]), l_area[j], hp, dd, len2, ln)
-                            pdf_light = pdf_light + pl
-                            front1, front2 = pos & (t1 > F(0)), pos & (t2 > F(0))
-                            own_lost |= to_light[s] & (drawn[s] == j) & ~pos
-                            met += front2
-                            met_sphere += front2
-                            if stats is not None:
-                                mine = to_light[s] & (drawn[s] == j)
-                                stats["both_roots"] += int((front1 & front2).sum())
-                                stats["one_root"] += int((~front1 & front2).sum())
-                                stats["no_root"] += int((pos & ~front2).sum())
-                                ocj = pr["c0"].astype(F)[None, :] - hp
-                                ccj = dot(ocj, ocj) - F(pr["radius"]) * F(pr["radius"])
-                                stats["near_surface"] += int(((ccj >= F(0)) & (ccj < F(0.21) * (F(pr["radius"]) * F(pr["radius"])))).sum())
-                                stats["disc_nonpos_light_half"] += int((mine & ~pos).sum())
-                                stats["far_side_sample"] += int((mine & front1 & front2 & (np.abs(t2 - F(1)) < np.abs(t1 - F(1)))).sum())
-                    pdf_light = pdf_light / (tree.A if mode == 16 else F(n_l))   # §20
-                    pdf = F(0.5) * pdf_cos + F(0.5) * pdf_light
-                    good = ~(pdf_cos == F(0)) & (pdf > F(0)) & ~own_lost
-                    if stats is not None:
-                        stats["below_surface"] += int((to_light[s] & (pdf_cos == F(0))).sum())
-                        stats["light_half_unmet"] += int((to_light[s] & (met == 0)).sum())
-                        stats["cos_one_light"] += int((~to_light[s] & (met == 1)).sum())
-                        stats["cos_many_lights"] += int((~to_light[s] & (met >= 2)).sum())
-                        stats["sphere_and_other"] += int(((met_sphere >= 1) & (met >= 2)).sum())
-                        stats["two_tri_crossings"] += int((met_tri >= 2).sum())   # §19
-                        stats["tri_and_other"] += int(((met_tri >= 1) & (met > met_tri)).sum())   # §19
-                    ok[s[~good]] = False
-                    weight[s[good]] = pdf_cos[good] / pdf[good]
-                    weighted[s[good]] = True
-            albedo = np.where(weighted[:, None], albedo * weight[:, None], albedo)
-            out[r[~ok]] = accum[r[~ok]]
-            r, new_d, hit_p, albedo = r[ok], new_d[ok], hit_p[ok], albedo[ok]
-            atten[r] = atten[r] * albedo
-            ray_d[r] = new_d
-            ray_o[r] = hit_p + new_d * F(0.001)
-            live = r
-    if stats is not None:
-        stats["not_followed"] += int((~followed).sum())
-    return out, followed
+            def on_leaf(rr, j, term, hit, pos):
+                met[rr] += hit
+                if l_kind[j] == TRIANGLE:
+                    met_tri[rr] += hit
+                if l_kind[j] == SPHERE:
+                    met_sphere[rr] += hit
+                    credited[rr] |= to_light[rr] & (drawn[rr] == j) & pos
+                if stats is not None:
+                    stats["tree_leaves"] += len(rr)
+
+            pdf_light = tree_density(tree, prims, quads, hp, dd, len2, ln, on_leaf)
+            own_lost = to_light & (drawn >= 0) & (l_kind[np.maximum(drawn, 0)] == SPHERE) & ~credited
+            if stats is not None:
+                stats["tree_sphere_uncredited"] += int(own_lost.sum())
+        for j in range(self.n_l if tree is None else 0):
+            if l_kind[j] == QUAD:
+                q = quads[l_index[j]]
+                qhit, qt = _quad_hit(q, hp, dd)
+                nj = np.broadcast_to(q["normal"].astype(F), dd.shape)
+                pl = ((qt * qt) * len2) / ((np.abs(dot(dd, nj)) / ln) * l_area[j])
+                pdf_light = pdf_light + np.where(qhit, pl, F(0)).astype(F)
+                met += qhit
+            elif l_kind[j] == TRIANGLE:   # §19
+                pl, thit = _tri_pl(quads[l_index[j]], l_area[j], hp, dd, len2, ln)
+                pdf_light = pdf_light + pl
+                met += thit
+                met_tri += thit
+                if stats is not None:
+                    stats["tri_own_missed"] += int((to_light & (drawn == j) & ~thit).sum())
+            else:   # §17
+                pr = prims[l_index[j]]
+                pl, pos, t1, t2 = T2._sphere_pl(pr["c0"].astype(F), F(pr["radius"]), l_area[j], hp, dd, len2, ln)
+                pdf_light = pdf_light + pl
+                front1, front2 = pos & (t1 > F(0)), pos & (t2 > F(0))
+                own_lost |= to_light & (drawn == j) & ~pos
+                met += front2
+                met_sphere += front2
+                if stats is not None:
+                    mine = to_light & (drawn == j)
+                    stats["both_roots"] += int((front1 & front2).sum())
+                    stats["one_root"] += int((~front1 & front2).sum())
+                    stats["no_root"] += int((pos & ~front2).sum())
+                    ocj = pr["c0"].astype(F)[None, :] - hp
+                    ccj = dot(ocj, ocj) - F(pr["radius"]) * F(pr["radius"])
+                    stats["near_surface"] += int(((ccj >= F(0)) & (ccj < F(0.21) * (F(pr["radius"]) * F(pr["radius"])))).sum())
+                    stats["disc_nonpos_light_half"] += int((mine & ~pos).sum())
+                    stats["far_side_sample"] += int((mine & front1 & front2 & (np.abs(t2 - F(1)) < np.abs(t1 - F(1)))).sum())
+        if stats is not None:
+            stats["below_surface"] += int((to_light & (pdf_cos == F(0))).sum())
+            stats["light_half_unmet"] += int((to_light & (met == 0)).sum())
+            stats["cos_one_light"] += int((~to_light & (met == 1)).sum())
+            stats["cos_many_lights"] += int((~to_light & (met >= 2)).sum())
+            count(stats, "sphere_and_other", int(((met_sphere >= 1) & (met >= 2)).sum()))
+            count(stats, "two_tri_crossings", int((met_tri >= 2).sum()))
+            count(stats, "tri_and_other", int(((met_tri >= 1) & (met > met_tri)).sum()))
+        return pdf_light / (tree.A if tree is not None else F(self.n_l)), own_lost
+
+
+def radiance(world, cam, width, height, max_depth, seed, gids, samples, mode=0, stats=None, trace=closest_intersection):
+    """Radiance of sample samples[i] of pixel gids[i]: ((n, 3) float32, followed (n,) bool); mode 0 / 1 / 2 / 4 / 16 as rt_renderer_light_sampling_enable takes
+    it: mode 16 over tree_of(world), the others as _mesh_light_twin lists their tables; trace: the walk"""
+    if mode != 16:
+        return T2.table_radiance(world, cam, width, height, max_depth, seed, gids, samples, mode, PT.counters(stats, new_stats()), trace, lights_of, (0, 1, 2, 4),
+                                 MAX_LIGHTS_MESH if mode == 4 else MAX_LIGHTS)
+    tree = tree_of(world)
+    assert 1 <= tree.n_l <= MAX_LIGHTS_TREE and tree.refused is None
+    return PT.radiance(world, cam, width, height, max_depth, seed, gids, samples, trace, rule=TableRule(world, None, tree),
+                       stats=PT.counters(stats, new_stats(max(tree.n_l, MAX_LIGHTS_MESH))))
 
 
 def frame_samples(world, cam, width, height, spp, max_depth, seed, mode=0, first_sample=0, stats=None):
     """(height, width, spp, 3) float32: every sample of every pixel; followed (height, width, spp)"""
-    gids = np.repeat(np.arange(width * height, dtype=np.uint32), spp)
-    smp = np.tile(np.arange(first_sample, first_sample + spp, dtype=np.uint32), width * height)
-    rad, ok = radiance(world, cam, width, height, max_depth, seed, gids, smp, mode, stats)
-    return rad.reshape(height, width, spp, 3), ok.reshape(height, width, spp)
+    return PT.frame_samples(lambda g, s: radiance(world, cam, width, height, max_depth, seed, g, s, mode, stats), width, height, spp, first_sample)
 
 
 luminance, in_order_sums, resolve = T.luminance, T.in_order_sums, T.resolve

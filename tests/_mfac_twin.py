@@ -2,26 +2,24 @@
 
 scatter() restates microfacet_scatter of include/rt06.h (rt_scene_set_microfacet) in float32 numpy, every operation rounded on its own, over any tape that
 serves next(rows) and in_unit2(rows): CaseTape (the words of rt_microfacet_batch's cases), RandomTape (fresh uniforms, for the mathematics no kernel shares) or
-_nee_twin's tape of a sample.  radiance() is a COPY of _env_tree_twin.radiance (the older twins stay untouched) with §29's lines marked: the records' rule before
-the scatter branches and — so that a room with a glass ball is followed on every sample — the dielectric of material_scatter.  With no records and no glass it
-is _env_tree_twin.radiance statement by statement; tests/test_microfacets_cpu.py pins that bit for bit.  The oracle does not know the rule: rt_microfacet_batch —
-the kernels' own function on the host — is pinned to scatter() bit for bit before anything is compared with either.
+_nee_twin's tape of a sample.  radiance() is the loop of tests/_path_twin.py under _env_tree_twin's rule with the records given to it — the loop runs scatter()
+before the scatter branches — and with the dielectric of material_scatter followed, so that a room with a glass ball is followed on every sample.  With no
+records and no glass it is _env_tree_twin.radiance; tests/test_microfacets_cpu.py holds that bit for bit.  The oracle does not know the rule:
+rt_microfacet_batch — the kernels' own function on the host — is pinned to scatter() bit for bit before anything is compared with either.
 """
 import numpy as np
 
 import _env_tree_twin as VT
 import _nmap_twin as NT
-import _smooth_twin as ST
+import _path_twin as PT
 import _tex_twin as XT
 import _tri_twin as TT
-from _env_light_twin import density_of, draw
-from _env_twin import primary_rays
-from _nee2_twin import MAT_DIFFUSE_LIGHT, world_arrays
-from _nee_twin import F, INV_PI, PRIM_MOVING, cross, dot, near_zero
+from _nee_twin import F, cross, dot
 
 SPECULAR, BASE, ABSORBED, BACKSIDE = 1, 2, 3, 4
 WAYS = {SPECULAR: "specular", BASE: "base", ABSORBED: "absorbed", BACKSIDE: "backside"}
 OFF, CONSTANT, MAPPED = 0, 1, 2
+GLASS, GLASS_MAPPED = 4, 6   # §30's records, which _rglass_twin follows
 MAT_METAL, MAT_DIELECTRIC, MAT_IMAGE = 1, 2, XT.MAT_IMAGE
 A_MIN = F(2.0 ** -10)
 PAST_END = 0x800001   # what a tape serves past its end: every rejection loop accepts it
@@ -196,235 +194,22 @@ def new_stats():
     return st
 
 
-def radiance(world, cam, width, height, max_depth, seed, gids, samples, sky, light=None, tree=None, tex=None, mfacs=None, stats=None, walk=None):
-    """_env_tree_twin.radiance statement by statement, but for the blocks marked §29: mfacs = one record of capi.MICROFACET_DT per material, or None; a
-    dielectric hit is followed.  ((n, 3) float32, followed (n,) bool)"""
-    assert cam.type == 0, "the twin restates the pinhole camera"
-    assert tree is None or (light is not None and tree.refused is None)
-    gids = np.ascontiguousarray(gids, np.uint32)
-    samples = np.ascontiguousarray(samples, np.uint32)
-    n = len(gids)
-    prims, quads, mats = world_arrays(world)
-    mat_of_prim = np.concatenate([(prims["mat"] & ~np.uint32(PRIM_MOVING)), quads["mat"]]).astype(np.int64)
-    m_type, m_albedo, m_albedo2, m_param = mats["type"].astype(np.int64), mats["albedo"].astype(F), mats["albedo2"].astype(F), mats["param"].astype(F)
-    both = tree is not None
-    n_l = tree.n_l if both else 0
-    scatters = (0, 1, 3, MAT_IMAGE) if tex is not None else (0, 1, 3)
-    if stats is not None:
-        stats.setdefault("misses_by_bounce", np.zeros(max_depth, np.int64))
-        for key, zero in new_stats().items():
-            stats.setdefault(key, zero)
-    tape, ray_o, ray_d = primary_rays(cam, width, height, seed, gids, samples)
-    rows = np.arange(n)
-    from_light = np.zeros(n, bool)
-    with np.errstate(all="ignore"):
-        atten = np.ones((n, 3), F)
-        accum = np.zeros((n, 3), F)
-        out = np.zeros((n, 3), F)
-        followed = np.ones(n, bool)
-        live = rows.copy()
-        for bounce in range(max_depth):
-            if len(live) == 0:
-                break
-            k = len(live)
-            rays = np.zeros((k, 7), F)
-            rays[:, 0:3], rays[:, 3:6] = ray_o[live], ray_d[live]
-            hit, t, prim, normal = TT.closest_intersection(world, rays)
-            o, d = rays[:, 0:3], rays[:, 3:6]
-            miss = hit == 0
-            if stats is not None:
-                stats["light_half_hit"] += int((from_light[live] & ~miss).sum())
-            if miss.any():
-                out[live[miss]] = atten[live[miss]] * np.asarray(sky(d[miss]), F) + accum[live[miss]]
-                if stats is not None:
-                    stats["misses_by_bounce"][bounce] += int(miss.sum())
-            mi = mat_of_prim[np.where(miss, 0, prim)]
-            mt = np.where(miss, -1, m_type[mi])
-            lit = mt == MAT_DIFFUSE_LIGHT
-            accum[live[lit]] = accum[live[lit]] + atten[live[lit]] * m_albedo[mi[lit]]
-            out[live[lit]] = accum[live[lit]]
-            glass = mt == MAT_DIELECTRIC                                     # §29: followed here
-            other = ~miss & ~lit & ~glass & ~np.isin(mt, scatters)
-            followed[live[other]] = False
-            out[live[other]] = np.nan
-            go = np.isin(mt, scatters)
-            if bounce + 1 >= max_depth:
-                out[live[go | glass]] = accum[live[go | glass]]
-                break
-            carried = []   # §29: (rows, new direction, hit point, factor) of the hits that go on without the base's scatter
-            gl = np.nonzero(glass)[0]
-            if len(gl):   # §29: the dielectric of material_scatter: face, ratio, Schlick, one uniform unless the reflection is total
-                rg, dg, ng = live[gl], d[gl], normal[gl]
-                pg = o[gl] + dg * t[gl][:, None]
-                behind = dot(dg, ng) > F(0)
-                ng = np.where(behind[:, None], -ng, ng)
-                ior = m_param[mi[gl]]
-                ratio = np.where(behind, ior, F(1) / ior).astype(F)
-                unit = normalize(dg)
-                cos_t = np.minimum(dot(-unit, ng), F(1))
-                sin_t = np.sqrt(F(1) - cos_t * cos_t)
-                r0 = (F(1) - ratio) / (F(1) + ratio)
-                r0 = r0 * r0
-                x1 = F(1) - cos_t
-                x2 = x1 * x1
-                prob = r0 + (F(1) - r0) * ((x2 * x2) * x1)
-                must = ratio * sin_t > F(1)
-                reflects = must.copy()
-                free = np.nonzero(~must)[0]
-                if len(free):
-                    reflects[free] = prob[free] > tape.next(rg[free])
-                refl = unit - (ng * dot(ng, unit)[:, None]) * F(2)
-                dv = dot(ng, unit)
-                kk = F(1) - (ratio * ratio) * (F(1) - dv * dv)
-                refr = np.where((kk >= F(0))[:, None], unit * ratio[:, None] - ng * (ratio * dv + np.sqrt(kk))[:, None], F(0)).astype(F)
-                carried.append((rg, np.where(reflects[:, None], refl, refr).astype(F), pg, m_albedo[mi[gl]]))
-                if stats is not None:
-                    stats["glass"] += len(gl)
-                    stats["glass_reflected"] += int(reflects.sum())
-            sel = np.nonzero(go)[0]
-            r = live[sel]
-            if tex is not None:
-                tuv = XT.hit_uv(world, tex[0], rays[sel], hit[sel], t[sel], prim[sel], normal[sel])
-                tuv, walked = XT.prefer_walk_uv(tuv, walk, sel)   # §28: a mapped hit's (u, v) is the walk's, from before the map
-            o, d, t, normal, mi, mt, prim_sel = o[sel], d[sel], t[sel], normal[sel], mi[sel], mt[sel], prim[sel]
-            hit_p = o + d * t[:, None]
-            if mfacs is not None and len(r):   # §29: the records' rule, before every draw of the base
-                rec = mfacs[mi]
-                has = np.nonzero(rec["on"] != OFF)[0]
-                done = np.zeros(len(r), bool)
-                if len(has):
-                    rough = rec["roughness"][has].astype(F)
-                    mp = rec["on"][has] == MAPPED
-                    if mp.any():
-                        assert tex is not None
-                        XT.count_walk_uv(walk, walked[has][mp].sum())
-                        green = XT.lookup(tex[1], rec["image"][has][mp].astype(np.int64), tuv[has][mp, 0], tuv[has][mp, 1])[:, 1]
-                        rough[mp] = rough[mp] * green
-                    is_coat = mt[has] != MAT_METAL
-                    f0 = np.where(is_coat[:, None], rec["specular"][has].astype(F)[:, None], m_albedo[mi[has]]).astype(F)
-                    new_w, factor, way = scatter(normal[has], d[has], rough, f0, is_coat, tape, r[has])
-                    spec, gone = way == SPECULAR, way == ABSORBED
-                    done[has] = spec | gone
-                    out[r[has][gone]] = accum[r[has][gone]]
-                    carried.append((r[has][spec], new_w[spec], hit_p[has][spec], factor[spec]))
-                    if stats is not None:
-                        stats["recorded"] += len(has)
-                        stats["coat"] += int(is_coat.sum())
-                        stats["conductor"] += int((~is_coat).sum())
-                        stats["mapped"] += int(mp.sum())
-                        for name, count in counts(way).items():
-                            stats[name] += count
-                keep = ~done
-                r, o, d, t, normal, mi, mt, hit_p = r[keep], o[keep], d[keep], t[keep], normal[keep], mi[keep], mt[keep], hit_p[keep]
-                if tex is not None:
-                    tuv, walked = tuv[keep], walked[keep]
-            k = len(r)
-            lamb = mt != 1
-            sampled = lamb & ((mt != MAT_IMAGE) | both)
-            ok = np.ones(k, bool)
-            new_d = np.zeros((k, 3), F)
-            weight = np.ones(k, F)
-            weighted = np.zeros(k, bool)
-            to_light = np.zeros(k, bool)
-            to_env = np.zeros(k, bool)
-            drawn = np.full(k, -1, np.int64)
-            if light is not None and sampled.any():
-                if both:
-                    had = tape.cur[r[sampled]].copy()
-                    tl, te = VT.pick_half(tape, r[sampled], n_l)
-                    to_light[np.nonzero(sampled)[0]], to_env[np.nonzero(sampled)[0]] = tl, te
-                    if stats is not None:
-                        stats["second_draws"] += int((tape.cur[r[sampled]] - had == 2).sum())
-                        stats["image_sampled"] += int((mt[sampled] == MAT_IMAGE).sum())
-                        stats["image_light_half"] += int((to_light & (mt == MAT_IMAGE)).sum())
-                else:
-                    c = tape.next(r[sampled])
-                    to_light[np.nonzero(sampled)[0]] = c < F(0.5)
-                    to_env = to_light.copy()
-            if to_env.any():
-                s = np.nonzero(to_env)[0]
-                four = np.stack([tape.next(r[s]) for _ in range(4)], axis=1)
-                new_d[s] = draw(light[0], light[1], four)[0]
-                if stats is not None:
-                    stats["light_half"] += len(s)
-                    stats["map_draws"] += len(s) if both else 0
-                    stats["checker_light_half"] += int((mt[s] == 3).sum())
-            to_table = to_light & ~to_env
-            if to_table.any():
-                s = np.nonzero(to_table)[0]
-                drawn[s], new_d[s] = VT.table_point(tape, r[s], tree, prims, quads, hit_p[s], stats)
-            s = np.nonzero(~to_light)[0]
-            if len(s):
-                on_unit = tape.on_unit3(r[s])
-                sl, sm = s[lamb[s]], s[~lamb[s]]
-                new_d[sl] = normal[sl] + on_unit[lamb[s]]
-                ok[sl] = ~near_zero(new_d[sl])
-                dn = dot(normal[sm], d[sm])
-                refl = d[sm] - (normal[sm] * dn[:, None]) * F(2)
-                new_d[sm] = refl + on_unit[~lamb[s]] * m_param[mi[sm]][:, None]
-                ok[sm] = ~((dot(new_d[sm], normal[sm]) < F(0)) | near_zero(new_d[sm]))
-            albedo = m_albedo[mi].copy()
-            chk = np.nonzero(mt == 3)[0]
-            if len(chk):
-                sp = hit_p[chk] * m_param[mi[chk]][:, None]
-                ssum = np.trunc(sp).astype(np.int64).sum(axis=1)
-                albedo[chk] = np.where((ssum % 2 == 0)[:, None], m_albedo[mi[chk]], m_albedo2[mi[chk]])
-            img = np.nonzero(mt == MAT_IMAGE)[0]
-            if len(img):
-                albedo[img] = XT.lookup(tex[1], m_albedo2[mi[img]][:, 0].astype(np.int64), tuv[img, 0], tuv[img, 1])
-                XT.count_walk_uv(walk, walked[img].sum())
-            if light is not None:
-                s = np.nonzero(sampled & ok)[0]
-                if len(s):
-                    dd, nn = new_d[s], normal[s]
-                    len2 = dot(dd, dd)
-                    ln = np.sqrt(len2)
-                    cosn = dot(nn, dd) / ln
-                    pdf_cos = np.where(cosn > F(0), cosn * INV_PI, F(0)).astype(F)
-                    if both:
-                        pdf_light, own_lost = VT.light_density(tree, light, prims, quads, hit_p[s], dd, len2, ln, to_table[s], drawn[s], stats)
-                        if stats is not None:
-                            stats["sphere_uncredited"] += int(own_lost.sum())
-                    else:
-                        pdf_light, own_lost = density_of(light[0], light[1], dd), np.zeros(len(s), bool)
-                    pdf = F(0.5) * pdf_cos + F(0.5) * pdf_light
-                    good = ~(pdf_cos == F(0)) & (pdf > F(0)) & ~own_lost
-                    if stats is not None:
-                        stats["below_surface"] += int((pdf_cos == F(0)).sum())
-                    ok[s[~good]] = False
-                    weight[s[good]] = pdf_cos[good] / pdf[good]
-                    weighted[s[good]] = True
-                albedo = np.where(weighted[:, None], albedo * weight[:, None], albedo)
-            out[r[~ok]] = accum[r[~ok]]
-            from_light[live] = False
-            from_light[r] = to_env
-            carried.append((r[ok], new_d[ok], hit_p[ok], albedo[ok]))
-            r = np.concatenate([c[0] for c in carried])                         # §29: the base's hits and the carried ones go on together
-            new_d, hit_p, albedo = (np.concatenate([c[i] for c in carried]).astype(F) for i in (1, 2, 3))
-            atten[r] = atten[r] * albedo
-            ray_d[r] = new_d
-            ray_o[r] = hit_p + new_d * F(0.001)
-            live = np.sort(r)
-    return out, followed
+def radiance(world, cam, width, height, max_depth, seed, gids, samples, sky, light=None, tree=None, tex=None, mfacs=None, stats=None, walk=None,
+             trace=TT.closest_intersection):
+    """_env_tree_twin.radiance with §29's records — mfacs = one record of capi.MICROFACET_DT per material, or None — and with every dielectric hit followed, so
+    that a room with a glass ball is followed on every sample.  This twin knows no rough glass: a table with such records is _rglass_twin's.
+    ((n, 3) float32, followed (n,) bool)"""
+    assert mfacs is None or not np.isin(mfacs["on"], (GLASS, GLASS_MAPPED)).any(), "rough-glass records: _rglass_twin.radiance"
+    stats = PT.counters(stats, {"misses_by_bounce": np.zeros(max_depth, np.int64), **new_stats()})
+    return VT.map_radiance(world, cam, width, height, max_depth, seed, gids, samples, sky, light, tree, tex, mfacs, stats, walk, trace, True)
 
 
 def frame_samples(world, cam, width, height, spp, max_depth, seed, sky, vn, uv, nmaps, mfacs, table, light=None, tree=None, first_sample=0, stats=None, info=None):
-    """(height, width, spp, 3) float32 and followed (height, width, spp): every sample of every pixel, plain (light None) or in mode 48, with the walk replaced as
-    _nmap_twin.frame_samples replaces it (nmaps None = no normal-map table) and the records of mfacs (None = no microfacet table)"""
-    saved = TT.closest_intersection
-    if nmaps is not None:
-        info = {} if info is None else info   # the walk's (u, v) travel to radiance() in it
-        TT.closest_intersection = lambda w, rays, preset=None: NT.mapped_walk(w, vn, uv, nmaps, table, rays, preset, info)
-    elif vn is not None and len(vn):
-        TT.closest_intersection = lambda w, rays, preset=None: ST.closest_intersection_smooth(w, vn, rays, preset)
-    try:
-        gids = np.repeat(np.arange(width * height, dtype=np.uint32), spp)
-        smp = np.tile(np.arange(first_sample, first_sample + spp, dtype=np.uint32), width * height)
-        tex = (uv if uv is not None and len(uv) else None, table) if table is not None else None
-        rad, ok = radiance(world, cam, width, height, max_depth, seed, gids, smp, sky, light, tree, tex, mfacs, stats, info if nmaps is not None else None)
-        return rad.reshape(height, width, spp, 3), ok.reshape(height, width, spp)
-    finally:
-        TT.closest_intersection = saved
+    """(height, width, spp, 3) float32 and followed (height, width, spp): every sample of every pixel, plain (light None) or in mode 48, over the walk
+    _nmap_twin.walk_of chooses (nmaps None = no normal-map table) and with the records of mfacs (None = no microfacet table)"""
+    trace, walk = NT.walk_of(vn, uv, nmaps, table, info)
+    return PT.frame_samples(lambda g, s: radiance(world, cam, width, height, max_depth, seed, g, s, sky, light, tree, NT.tex_of(uv, table), mfacs, stats, walk, trace),
+                            width, height, spp, first_sample)
 
 
 in_order_sums, resolve = VT.in_order_sums, VT.resolve

@@ -1,9 +1,12 @@
-"""A numpy float32 restatement of one whole sample, with and without light sampling — test infrastructure only.
+"""The ground floor of the numpy float32 twins of one whole sample, and the twin with and without light sampling over quad lights — test
+infrastructure only.
 
+What this module owns: the float32 vector helpers, the tape of a sample's uniforms with the two rejection loops (_Tape), the quad lights of a world, quad::hit
+restated (_quad_hit), the oracle's walk as the twins take one (oracle_trace), the resolve, and the counters of §16.  The sample's path itself — the pixel jitter,
+the pinhole ray, the shade step of sample_world and the light-sampling estimator as rt06.h states it, every operation a float32 operation rounded on its own —
+is tests/_path_twin.py's one loop; radiance() runs it over orc_trace_batch under _light_tree_twin.TableRule on the quad lights.
 What it takes from the oracle: the uniforms of a sample (orc_rng_uniforms, on the stream id one_sample uses) and every closest
-intersection (orc_trace_batch, through _oracle.py).  What it restates: the pixel jitter's rejection loop, the pinhole ray, the shade
-step of sample_world — Lambertian, checker, metal, diffuse light, the sky — and the light-sampling estimator as rt06.h states it,
-every operation a float32 operation rounded on its own.  The per-light quad test of the density step is quad::hit restated here:
+intersection (orc_trace_batch, through _oracle.py).  The per-light quad test of the density step is quad::hit restated here:
 orc_trace_batch tests a world's bounds before its primitives, which the bare test the kernel calls does not.
 
 Scope: pinhole cameras; worlds of spheres and quads with Lambertian, checker, metal and diffuse-light materials.  A sample that meets
@@ -126,170 +129,33 @@ def _quad_hit(q, o, d):
     return hit, t
 
 
+def oracle_trace(world, rays):
+    """every closest intersection of rays (k, 7) by the oracle's orc_trace_batch: (hit, t, prim, normal)"""
+    k = len(rays)
+    hit, t, prim, normal = np.zeros(k, np.int32), np.zeros(k, F), np.zeros(k, np.int32), np.zeros((k, 3), F)
+    assert O.lib().orc_trace_batch(C.byref(world), k, rays, hit, t, prim, normal) == 0
+    return hit, t, prim, normal
+
+
+def count(stats, key, n):
+    """stats[key] += n where the caller's dict keeps that counter"""
+    if key in stats:
+        stats[key] += n
+
+
 def radiance(world, cam, width, height, max_depth, seed, gids, samples, light_sampling=False, stats=None):
     """Radiance of sample samples[i] of pixel gids[i]: ((n, 3) float32, followed (n,) bool).  world: _oracle.World, cam: _oracle.Camera (pinhole).
     stats: a dict of new_stats()'s shape (or an empty one, which is given it) that the run adds its counts to."""
-    assert cam.type == 0, "the twin restates the pinhole camera"
-    gids = np.ascontiguousarray(gids, np.uint32)
-    samples = np.ascontiguousarray(samples, np.uint32)
-    n = len(gids)
-    prims = np.frombuffer((C.c_char * (world.n_prims * O.PRIM_DT.itemsize)).from_address(world.prims), O.PRIM_DT) if world.n_prims else np.zeros(0, O.PRIM_DT)
-    quads = np.frombuffer((C.c_char * (world.n_quads * O.QUAD_DT.itemsize)).from_address(world.quads), O.QUAD_DT) if world.n_quads else np.zeros(0, O.QUAD_DT)
-    mats = np.frombuffer((C.c_char * (world.n_materials * O.MAT_DT.itemsize)).from_address(world.materials), O.MAT_DT)
-    light_idx, light_area = quad_lights(quads, mats)
-    n_l = len(light_idx)
-    if light_sampling:
-        assert 1 <= n_l <= MAX_LIGHTS
-    mat_of_prim = np.concatenate([(prims["mat"] & ~np.uint32(PRIM_MOVING)), quads["mat"]]).astype(np.int64)
-    m_type, m_albedo, m_albedo2, m_param = mats["type"].astype(np.int64), mats["albedo"].astype(F), mats["albedo2"].astype(F), mats["param"].astype(F)
-
-    if stats is not None:
-        for key, zero in new_stats().items():
-            stats.setdefault(key, zero)
-    tape = _Tape(seed, gids, samples)
-    rows = np.arange(n)
-    with np.errstate(all="ignore"):
-        # one_sample: pixel centre in NDC, jitter in a disc of half a pixel, PinholeCamera::sample_ray
-        x, y = (gids % np.uint32(width)).astype(F), (gids // np.uint32(width)).astype(F)
-        psx, psy = F(1) / F(width), F(1) / F(height)
-        ndcx = ((x + F(0.5)) * psx) * F(2) - F(1)
-        ndcy = ((y + F(0.5)) * psy) * F(2) - F(1)
-        jx, jy = tape.in_unit2(rows)
-        sx, sy = ndcx + jx * psx, ndcy + jy * psy
-        co, cu, cv, cw = (np.array(list(v), F) for v in (cam.o, cam.u, cam.v, cam.w))
-        ray_o = np.broadcast_to(co, (n, 3)).copy()
-        ray_d = (cw[None, :] + cu[None, :] * sx[:, None]) + cv[None, :] * sy[:, None]
-
-        atten = np.ones((n, 3), F)
-        accum = np.zeros((n, 3), F)
-        out = np.zeros((n, 3), F)
-        followed = np.ones(n, bool)
-        live = rows.copy()   # samples whose path goes on
-        for bounce in range(max_depth):
-            if len(live) == 0:
-                break
-            k = len(live)
-            rays = np.zeros((k, 7), F)
-            rays[:, 0:3], rays[:, 3:6] = ray_o[live], ray_d[live]
-            hit, t, prim, normal = np.zeros(k, np.int32), np.zeros(k, F), np.zeros(k, np.int32), np.zeros((k, 3), F)
-            assert O.lib().orc_trace_batch(C.byref(world), k, rays, hit, t, prim, normal) == 0
-            o, d = rays[:, 0:3], rays[:, 3:6]
-            # miss: the sky (Renderer.cu:150-151) or the constant background
-            miss = hit == 0
-            if miss.any():
-                dm = d[miss]
-                if world.background == 1:
-                    sky = np.broadcast_to(np.array(list(world.background_color), F), dm.shape)
-                else:
-                    inv = F(1) / np.sqrt(dot(dm, dm))
-                    tt = (dm[:, 1] * inv) * F(0.5) + F(0.5)
-                    a, b = np.array([0.1, 0.2, 0.4], F), np.array([0.9, 0.9, 0.99], F)
-                    sky = a[None, :] + (b - a)[None, :] * tt[:, None]
-                out[live[miss]] = atten[live[miss]] * sky + accum[live[miss]]
-            mi = mat_of_prim[np.where(miss, 0, prim)]
-            mt = np.where(miss, -1, m_type[mi])
-            # a light: emits, never scatters
-            lit = mt == 4
-            accum[live[lit]] = accum[live[lit]] + atten[live[lit]] * m_albedo[mi[lit]]
-            out[live[lit]] = accum[live[lit]]
-            other = ~miss & ~lit & ~np.isin(mt, (0, 1, 3))
-            followed[live[other]] = False
-            out[live[other]] = np.nan
-            go = np.isin(mt, (0, 1, 3))
-            if bounce + 1 >= max_depth:   # the last allowed bounce: whatever it scatters into is never traced
-                out[live[go]] = accum[live[go]]
-                break
-            sel = np.nonzero(go)[0]
-            r = live[sel]
-            o, d, t, normal, mi, mt = o[sel], d[sel], t[sel], normal[sel], mi[sel], mt[sel]
-            hit_p = o + d * t[:, None]
-            k = len(r)
-            lamb = mt != 1
-            ok = np.ones(k, bool)
-            new_d = np.zeros((k, 3), F)
-            weight = np.ones(k, F)
-            weighted = np.zeros(k, bool)
-            to_light = np.zeros(k, bool)
-            if light_sampling and lamb.any():
-                c = tape.next(r[lamb])
-                to_light[np.nonzero(lamb)[0]] = c < F(0.5)
-            if to_light.any():
-                s = np.nonzero(to_light)[0]
-                li = np.zeros(len(s), np.int64)
-                if n_l > 1:
-                    scaled = (tape.next(r[s]) * F(n_l)).astype(np.uint32)
-                    li = np.minimum(scaled, np.uint32(n_l - 1)).astype(np.int64)
-                    if stats is not None:
-                        stats["index_clamped"] += int((scaled >= n_l).sum())
-                la = tape.next(r[s])
-                lb = tape.next(r[s])
-                if stats is not None:
-                    stats["light_samples"] += np.bincount(li, minlength=MAX_LIGHTS)
-                    stats["checker_light_half"] += int((mt[s] == 3).sum())
-                q = quads[light_idx[li]]
-                new_d[s] = ((q["Q"].astype(F) + q["u"].astype(F) * la[:, None]) + q["v"].astype(F) * lb[:, None]) - hit_p[s]
-            s = np.nonzero(~to_light)[0]
-            if len(s):
-                on_unit = tape.on_unit3(r[s])
-                sl, sm = s[lamb[s]], s[~lamb[s]]
-                new_d[sl] = normal[sl] + on_unit[lamb[s]]
-                ok[sl] = ~near_zero(new_d[sl])
-                dn = dot(normal[sm], d[sm])
-                refl = d[sm] - (normal[sm] * dn[:, None]) * F(2)
-                new_d[sm] = refl + on_unit[~lamb[s]] * m_param[mi[sm]][:, None]
-                ok[sm] = ~((dot(new_d[sm], normal[sm]) < F(0)) | near_zero(new_d[sm]))
-            albedo = m_albedo[mi].copy()
-            chk = np.nonzero(mt == 3)[0]
-            if len(chk):   # checker_texture::value: ivec3 truncation of pos * scale, parity of the sum
-                sp = hit_p[chk] * m_param[mi[chk]][:, None]
-                ssum = np.trunc(sp).astype(np.int64).sum(axis=1)
-                albedo[chk] = np.where((ssum % 2 == 0)[:, None], m_albedo[mi[chk]], m_albedo2[mi[chk]])
-            if light_sampling:
-                s = np.nonzero(lamb & ok)[0]
-                if len(s):
-                    dd, nn, hp = new_d[s], normal[s], hit_p[s]
-                    len2 = dot(dd, dd)
-                    ln = np.sqrt(len2)
-                    cosn = dot(nn, dd) / ln
-                    pdf_cos = np.where(cosn > F(0), cosn * INV_PI, F(0)).astype(F)
-                    pdf_light = np.zeros(len(s), F)
-                    met = np.zeros(len(s), np.int64)   # lights the direction meets (stats only)
-                    for j in range(n_l):
-                        q = quads[light_idx[j]]
-                        qhit, qt = _quad_hit(q, hp, dd)
-                        nj = np.broadcast_to(q["normal"].astype(F), dd.shape)
-                        pl = ((qt * qt) * len2) / ((np.abs(dot(dd, nj)) / ln) * light_area[j])
-                        pdf_light = pdf_light + np.where(qhit, pl, F(0)).astype(F)
-                        met += qhit
-                    pdf_light = pdf_light / F(n_l)
-                    pdf = F(0.5) * pdf_cos + F(0.5) * pdf_light
-                    good = ~(pdf_cos == F(0)) & (pdf > F(0))
-                    if stats is not None:
-                        stats["below_surface"] += int((to_light[s] & (pdf_cos == F(0))).sum())
-                        stats["light_half_unmet"] += int((to_light[s] & (met == 0)).sum())
-                        stats["cos_one_light"] += int((~to_light[s] & (met == 1)).sum())
-                        stats["cos_many_lights"] += int((~to_light[s] & (met >= 2)).sum())
-                    ok[s[~good]] = False
-                    weight[s[good]] = pdf_cos[good] / pdf[good]
-                    weighted[s[good]] = True
-            albedo = np.where(weighted[:, None], albedo * weight[:, None], albedo)
-            out[r[~ok]] = accum[r[~ok]]   # a failed scatter keeps what the path has collected
-            r, new_d, hit_p, albedo = r[ok], new_d[ok], hit_p[ok], albedo[ok]
-            atten[r] = atten[r] * albedo
-            ray_d[r] = new_d
-            ray_o[r] = hit_p + new_d * F(0.001)
-            live = r
-    if stats is not None:
-        stats["not_followed"] += int((~followed).sum())
-    return out, followed
+    import _nee2_twin as T2   # (the table, the rule and the loop stand above this module)
+    import _path_twin as PT
+    return T2.table_radiance(world, cam, width, height, max_depth, seed, gids, samples, 1 if light_sampling else 0, PT.counters(stats, new_stats()), oracle_trace,
+                             T2.lights_of, (0, 1))   # mode 1's table: quad_lights() above
 
 
 def frame_samples(world, cam, width, height, spp, max_depth, seed, light_sampling=False, first_sample=0, stats=None):
     """(height, width, spp, 3) float32: every sample of every pixel; followed (height, width, spp)"""
-    gids = np.repeat(np.arange(width * height, dtype=np.uint32), spp)
-    smp = np.tile(np.arange(first_sample, first_sample + spp, dtype=np.uint32), width * height)
-    rad, ok = radiance(world, cam, width, height, max_depth, seed, gids, smp, light_sampling, stats)
-    return rad.reshape(height, width, spp, 3), ok.reshape(height, width, spp)
+    import _path_twin as PT
+    return PT.frame_samples(lambda g, s: radiance(world, cam, width, height, max_depth, seed, g, s, light_sampling, stats), width, height, spp, first_sample)
 
 
 def luminance(rgb):

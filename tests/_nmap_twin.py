@@ -8,7 +8,7 @@ the host — is pinned to this twin bit for bit before anything is compared with
 import numpy as np
 
 import _env_tree_twin as VT
-import _smooth_twin as ST   # (takes _tri_twin's walk as it stands, before anything below substitutes it)
+import _smooth_twin as ST
 import _tex_twin as XT
 import _tri_twin as TT
 import _uv_twin as UT
@@ -153,16 +153,24 @@ def mapped_walk(world, vn, uv, nmaps, table, rays, preset=None, info=None):
     return hit, t, prim, normal
 
 
-def frame_samples(world, cam, width, height, spp, max_depth, seed, sky, vn, uv, nmaps, table, light=None, tree=None, first_sample=0, stats=None, info=None):
-    """_env_tree_twin.frame_samples — plain (light None) or mode 48 — with the walk replaced by mapped_walk for the duration of the call; nmaps None = no table"""
-    saved = TT.closest_intersection
+def walk_of(vn, uv, nmaps, table, info=None):
+    """(trace, walk) as _path_twin.radiance takes them, for a world with these tables: mapped_walk and the dict its (u, v) travel to radiance() in where there is a
+    normal-map table (nmaps None = none), the smooth walk under a table of vertex normals, _tri_twin's flat walk otherwise"""
     if nmaps is not None:
-        info = {} if info is None else info   # the walk's (u, v) travel to radiance() in it
-        TT.closest_intersection = lambda w, rays, preset=None: mapped_walk(w, vn, uv, nmaps, table, rays, preset, info)
-    elif vn is not None and len(vn):
-        TT.closest_intersection = lambda w, rays, preset=None: ST.closest_intersection_smooth(w, vn, rays, preset)
-    try:
-        return VT.frame_samples(world, cam, width, height, spp, max_depth, seed, sky, light=light, tree=tree, tex=(uv if uv is not None and len(uv) else None, table),
-                                first_sample=first_sample, stats=stats, walk=info if nmaps is not None else None)
-    finally:
-        TT.closest_intersection = saved
+        info = {} if info is None else info
+        return (lambda w, rays, preset=None: mapped_walk(w, vn, uv, nmaps, table, rays, preset, info)), info
+    if vn is not None and len(vn):
+        return ST.smooth_walk(vn), None
+    return TT.closest_intersection, None
+
+
+def tex_of(uv, table):
+    """tex as _path_twin.radiance takes it: (the table of texture coordinates or None, the texture table), or None without a texture table"""
+    return (uv if uv is not None and len(uv) else None, table) if table is not None else None
+
+
+def frame_samples(world, cam, width, height, spp, max_depth, seed, sky, vn, uv, nmaps, table, light=None, tree=None, first_sample=0, stats=None, info=None):
+    """_env_tree_twin.frame_samples — plain (light None) or mode 48 — over the walk walk_of() chooses"""
+    trace, walk = walk_of(vn, uv, nmaps, table, info)
+    return VT.frame_samples(world, cam, width, height, spp, max_depth, seed, sky, light=light, tree=tree, tex=tex_of(uv, table), first_sample=first_sample,
+                            stats=stats, walk=walk, trace=trace)

@@ -2,25 +2,22 @@
 
 shading_normal() restates the rule of include/rt06.h (rt_tri_normals) in float32 numpy, every operation rounded on its own: image_value_quad's planar
 coordinates, g = (n0 * ((1 - alpha) - beta) + n1 * alpha) + n2 * beta, the two ways back to the flat normal.  closest_intersection_smooth() is
-_tri_twin.closest_intersection followed by that on triangle hits.  radiance() for modes 0, 1, 2 (_tri_twin), 4 (_mesh_light_twin) and 16 (_light_tree_twin) is
-those modules' own radiance with the walk replaced: their files are not edited, their module-level `closest_intersection` is substituted for the duration of
-the call.  The oracle does not know the rule, so nothing here asks it about one; the twin is pinned before use (tests/test_smooth_normals_cpu.py): with a
+_tri_twin.closest_intersection followed by that on triangle hits.  radiance() for modes 0, 1, 2, 4 and 16 is _light_tree_twin's with that walk passed to it.
+The oracle does not know the rule, so nothing here asks it about one; the twin is pinned before use (tests/test_smooth_normals_cpu.py): with a
 table of zeros it IS _tri_twin, bit for bit, and rt_shading_normal_batch — the kernels' own function on the host — equals shading_normal() bit for bit.
 
 Scope, as the twins have it: pinhole camera, static spheres, Lambertian, checker, metal and light materials, stack traversal.
 """
-import contextlib
-
 import numpy as np
 
 import _light_tree_twin as LT
-import _mesh_light_twin as MT
+import _path_twin as PT
 import _tri_twin as TT
 from _nee2_twin import world_arrays
 from _nee_twin import F, cross, dot
 
 in_order_sums, resolve = TT.in_order_sums, TT.resolve
-_flat_walk = TT.closest_intersection   # the walk itself, taken before any substitution below
+_flat_walk = TT.closest_intersection
 
 
 def table(vn):
@@ -79,39 +76,24 @@ def closest_intersection_smooth(world, vn, rays, preset=None, info=None):
     return hit, t, prim, normal
 
 
-TWIN_OF_MODE = {0: TT, 1: TT, 2: TT, 4: MT, 16: LT}
-
-
-@contextlib.contextmanager
-def _walk(module, vn, info):
-    """module.closest_intersection = the smooth walk, for the duration of the block (the twins call their module-level name)"""
-    saved = module.closest_intersection
-    module.closest_intersection = lambda world, rays, preset=None: closest_intersection_smooth(world, vn, rays, preset, info)
-    try:
-        yield
-    finally:
-        module.closest_intersection = saved
+def smooth_walk(vn, info=None):
+    """closest_intersection_smooth under the table vn as a walk (world, rays[, preset]) -> (hit, t, prim, normal), the way the whole-sample twins take one"""
+    return lambda world, rays, preset=None: closest_intersection_smooth(world, vn, rays, preset, info)
 
 
 def radiance(world, vn, cam, width, height, max_depth, seed, gids, samples, mode=0, info=None):
-    """the mode's own twin's radiance with the walk replaced: ((n, 3) float32, followed (n,) bool)"""
-    module = TWIN_OF_MODE[mode]
-    with _walk(module, vn, info):
-        return module.radiance(world, cam, width, height, max_depth, seed, gids, samples, mode)
+    """_light_tree_twin.radiance (modes 0, 1, 2, 4 and 16) over the smooth walk: ((n, 3) float32, followed (n,) bool)"""
+    return LT.radiance(world, cam, width, height, max_depth, seed, gids, samples, mode, trace=smooth_walk(vn, info))
 
 
 def frame_samples(world, vn, cam, width, height, spp, max_depth, seed, mode=0, first_sample=0, info=None):
     """(height, width, spp, 3) float32: every sample of every pixel; followed (height, width, spp)"""
-    gids = np.repeat(np.arange(width * height, dtype=np.uint32), spp)
-    smp = np.tile(np.arange(first_sample, first_sample + spp, dtype=np.uint32), width * height)
-    rad, ok = radiance(world, vn, cam, width, height, max_depth, seed, gids, smp, mode, info)
-    return rad.reshape(height, width, spp, 3), ok.reshape(height, width, spp)
+    return PT.frame_samples(lambda g, s: radiance(world, vn, cam, width, height, max_depth, seed, g, s, mode, info), width, height, spp, first_sample)
 
 
 def first_hit_sums(world, vn, cam, width, height, spp, seed, first_sample=0):
     """_tri_twin.first_hit_sums with the rule applied to the first hits: (H, W, 5) float32 = (sum Nx, sum Ny, sum Nz, sum t, hits)"""
-    with _walk(TT, vn, None):
-        return TT.first_hit_sums(world, cam, width, height, spp, seed, first_sample)
+    return TT.first_hit_sums(world, cam, width, height, spp, seed, first_sample, trace=smooth_walk(vn))
 
 
 def shading_normal64(Q, u, v, n0, n1, n2, d, hit_p):

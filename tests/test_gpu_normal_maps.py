@@ -8,7 +8,6 @@ import pytest
 import _aov_tex_twin as AT
 import _nmap_twin as NT
 import _nmap_worlds as NW
-import _tri_twin as TT
 import _tri_worlds as TW
 from _common import as_oracle_camera, bits_equal, mismatch_report, pkg
 
@@ -174,15 +173,11 @@ def test_the_feature_pass_carries_the_mapped_normal(p, monkeypatch, as_list, smo
     world = NW.as_oracle_world(scene.getWorldPtr())
     vn, uv, nmaps, table = scene.vertex_normals(), scene.texture_coords(), scene.normal_maps(), NW.room_table()
     assert bool(len(vn)) == smooth
-    info, saved = {}, TT.closest_intersection
+    info = {}
     want = {}
     for name, maps in (("mapped", nmaps), ("unmapped", None)):
-        TT.closest_intersection = (lambda w, rays, preset=None, maps=maps: NT.mapped_walk(w, vn if smooth else None, uv, maps, table, rays, preset, info)) if maps is not None else (
-            lambda w, rays, preset=None: NT.ST.closest_intersection_smooth(w, vn, rays, preset) if smooth else saved(w, rays, preset))
-        try:
-            want[name] = AT.sums(world, as_oracle_camera(NW.camera(p)), W, H, SPP, SEED, True, uv=uv, table=table)[0]
-        finally:
-            TT.closest_intersection = saved
+        trace, _ = NT.walk_of(vn if smooth else None, uv, maps, table, info)
+        want[name] = AT.sums(world, as_oracle_camera(NW.camera(p)), W, H, SPP, SEED, True, uv=uv, table=table, trace=trace)[0]
     assert info["replaced"] > 100 and not bits_equal(want["mapped"][..., 0:3], want["unmapped"][..., 0:3])
     assert bits_equal(want["mapped"][..., 3:8], want["unmapped"][..., 3:8])   # albedo, depth and hits are unchanged
     r = p.Renderer.MakeRenderer(W, H, SPP, DEPTH, NW.camera(p), scene.getWorldPtr(), seed=SEED)
