@@ -468,6 +468,35 @@ int rt_scene_set_rough_glass(rt_scene* s, uint32_t material, float roughness);
  * a tape -> out_dir[3 i ..] (w; zero unless specular or transmitted), out_weight[i] (G; zero likewise), out_path[i] = RT_MFAC_*, out_draws[i].               */
 int rt_rough_glass_batch(size_t count, const float* normal, const float* ray_d, const float* roughness, const float* ior, const uint32_t* tape, size_t tape_len,
                          const uint32_t* offsets, float* out_dir, float* out_weight, uint32_t* out_path, uint32_t* out_draws);
+/* ---- solid glass (not in the reference): a dielectric whose material has an interior record knows inside from outside on parallelograms and
+ * triangles too, and absorbs along the way through it.  One record per material beside the flat world, as the microfacet records are; rt_material and
+ * rt_world_flat keep their sizes.  sigma = the absorption coefficient per unit length and channel.  The rule (interior_hit), for a hit at parameter t of the ray
+ * (o, d) on a dielectric of index ior whose material has a record:
+ *   1  back = dot(d, Ng) > 0, Ng = the stored normal normalize(cross(u, v)) of a parallelogram or triangle before any turning (set_face_normal's own comparison,
+ *      kept), or — on a sphere — the outward normal (hit - centre) / radius, as ever: a negative radius keeps meaning what it means.  The shading normal n stays what
+ *      the shade phase holds by then, the flat or the interpolated normal, facing against the ray.  eta = back ? ior : 1 / ior.  The Schlick toss, reflect, refract
+ *      and the rough-glass rule's steps 2 to 7 take (n, eta) as they take them without a record.
+ *   2  only when back:  len = sqrt(dot(d, d));  dist = t len;  T_c = rt_expf of -(sigma_c dist) per channel;  albedo = albedo T, before the smooth or the rough rule
+ *      touches it (a rough hit's factor is (albedo T) G).  Charged at every back hit, whether it reflects totally, reflects or refracts: the segment that ended there
+ *      was inside.
+ *   3  a dielectric without a record, and every other material, is untouched, draw for draw.
+ * rt_expf, in rt_math.hpp: fp32 + - * /, floor and integer bit operations in one fixed order, no FMA; of +-0 it is 1 exactly, x <= -87 or NaN gives 0, results of x <= 0 lie
+ * in [0, 1].  The winding is trusted: a closed mesh must be wound outward (mesh_io.orient_outward).  Known limit: a segment inside the glass that ends on another
+ * object is not charged; overlapping or nested solids are undefined.  Not done: the eta^2 scaling, normal maps on glass.                                        */
+typedef struct rt_interior { uint32_t on; float sigma[3]; } rt_interior;   /* 16 B, one per material */
+enum { RT_INTERIOR_OFF = 0, RT_INTERIOR_SOLID = 1 };
+/* Gives `material`, an RT_MAT_DIELECTRIC, an interior record.  RT_ERR_INVALID, scene unchanged: no such material; any other type of material; a sigma that is not
+ * finite or is negative.  rt_scene_clear_interior takes it away (no record is no error).  rt_scene_interiors: *out = one record per material (the scene's own
+ * memory, valid until the next call on the scene), *out_n = their number — or NULL, 0 while no material has a record.                                         */
+int rt_scene_set_interior(rt_scene* s, uint32_t material, const float sigma[3]);
+int rt_scene_clear_interior(rt_scene* s, uint32_t material);
+int rt_scene_interiors(const rt_scene* s, const rt_interior** out, uint32_t* out_n);
+/* HOST (no GPU): the rule on `count` cases — per case Ng (3), n (3; the outward normal of a sphere), d (3), t, ior, sigma (3) and sphere[i] != 0 when the hit is on
+ * a sphere (back is then taken on n) -> out_back[i] (0 / 1), out_eta[i], out_T[3 i ..] (ones unless back).                                                    */
+int rt_interior_batch(size_t count, const float* Ng, const float* n, const float* d, const float* t, const float* ior, const float* sigma, const uint32_t* sphere,
+                      uint32_t* out_back, float* out_eta, float* out_T);
+/* HOST: out[i] = rt_expf of x[i]                                                                                                                                  */
+int rt_expf_batch(size_t count, const float* x, float* out);
 
 /* BVH_Handle::Factory::BuildBVH_TopDown -> _build_bvh_rec1 (BVH.cu:166-210):
  * median split on the longest axis, leaf size 1, post-order numbering, root =
@@ -629,9 +658,12 @@ int rt_renderer_kernel_light_tree(rt_renderer* r, uint32_t* out);
 int rt_renderer_kernel_env_light(rt_renderer* r, uint32_t* out);
 /* *out = 1 when the next launch runs an instantiation of the normal-map family, as rt_renderer_kernel_env_light answers for its own */
 int rt_renderer_kernel_normal_map(rt_renderer* r, uint32_t* out);
-/* *out = 1 when the next launch runs an instantiation of the microfacet family: a microfacet table is on.  rt_renderer_kernel_normal_map answers
- * 0 then, whether or not a normal-map table is on too: the microfacet forms read both tables.                                                                 */
+/* *out = 1 when the next launch runs an instantiation of the microfacet family: a microfacet table is on — or an interior table (§32), with or
+ * without a microfacet table, since the solid-glass forms are microfacet forms that read one more table.  rt_renderer_kernel_normal_map answers 0 then, whether
+ * or not a normal-map table is on too: the microfacet forms read both tables.                                                                                 */
 int rt_renderer_kernel_microfacet(rt_renderer* r, uint32_t* out);
+/* *out = 1 when the NEXT launch runs a form of the solid-glass family: an interior table is on (rt_renderer_kernel_microfacet says what else).  */
+int rt_renderer_kernel_interior(rt_renderer* r, uint32_t* out);
 /* Renderer::DownloadRenderbuffer (Renderer.cu:94-96): width*height*4 floats,
  * row-major, row 0 = bottom.  Only valid for world_size == 1.               */
 int rt_renderer_download(rt_renderer* r, float* host_rgba, size_t n_floats);
@@ -932,6 +964,15 @@ int rt_renderer_normal_maps_info(rt_renderer* r, uint32_t out[2]);
 int rt_renderer_microfacets(rt_renderer* r, const rt_microfacet* table, uint32_t n);
 /* out[0] = 1 while a table is on, out[1] = how many of its records are on */
 int rt_renderer_microfacets_info(rt_renderer* r, uint32_t out[2]);
+/* Solid glass (rt_scene_interiors): table = one record per material of the world, or NULL, 0 for off (the default).  While a table is on, plain
+ * launches and those of light-sampling mode 48 run the INTR form of the renderer's kernel (rt_renderer_kernel_interior), whether or not a microfacet, normal-map
+ * or texture table is on; that form reads them all.  Takes effect at the next launch; an unchanged table is a no-op that keeps the refinement, a change discards
+ * the refinement and feature-buffer state.  RT_ERR_INVALID, renderer and kernel unchanged: what rt_renderer_microfacets refuses a renderer for (variants 1, 5, 6;
+ * queue and wide4 walks; bvh_node trees; light-sampling modes 1, 2, 4, 16, 32, which in turn refuse a renderer with a table), a count that is not the world's
+ * number of materials, a record on a material that is no dielectric, an `on` other than 0 or 1, a sigma that is not finite or is negative.                    */
+int rt_renderer_interiors(rt_renderer* r, const rt_interior* table, uint32_t n);
+/* out[0] = 1 while a table is on, out[1] = how many of its records are on */
+int rt_renderer_interiors_info(rt_renderer* r, uint32_t out[2]);
 
 /* ------------------------------------------------------------------ */
 /* Multi-GPU renderer — the same three entry points (Renderer.h:38-46)  */
@@ -973,6 +1014,8 @@ int rt_multi_renderer_normal_maps_info(rt_multi_renderer* m, uint32_t out[2]);
 /* rt_renderer_microfacets on every rank (refused before any rank changes), and rt_renderer_microfacets_info of the ranks.    */
 int rt_multi_renderer_microfacets(rt_multi_renderer* m, const rt_microfacet* table, uint32_t n);
 int rt_multi_renderer_microfacets_info(rt_multi_renderer* m, uint32_t out[2]);
+/* rt_renderer_interiors on every rank (refused before any rank changes).                                                                                        */
+int rt_multi_renderer_interiors(rt_multi_renderer* m, const rt_interior* table, uint32_t n);
 /* Renderer::DownloadRenderbuffer: width*height*4 floats from devices[0].                                                */
 int rt_multi_renderer_download(rt_multi_renderer* m, float* host_rgba, size_t n_floats);
 /* ms of the last render: out[0] host wall-clock of Render(), out[1] slowest rank's kernels (HIP events),
@@ -1024,6 +1067,10 @@ int rt_probe_microfacet(int device, size_t count, const float* normal, const flo
 /* rt_rough_glass_batch on the device, one lane per case                                                                                                       */
 int rt_probe_rough_glass(int device, size_t count, const float* normal, const float* ray_d, const float* roughness, const float* ior, const uint32_t* tape,
                          size_t tape_len, const uint32_t* offsets, float* out_dir, float* out_weight, uint32_t* out_path, uint32_t* out_draws);
+/* rt_interior_batch and rt_expf_batch on the device, one lane per case                                                                                           */
+int rt_probe_interior(int device, size_t count, const float* Ng, const float* n, const float* d, const float* t, const float* ior, const float* sigma,
+                      const uint32_t* sphere, uint32_t* out_back, float* out_eta, float* out_T);
+int rt_probe_expf(int device, size_t count, const float* x, float* out);
 /* rt_noise_value_batch on the device, one lane per point: the tables in global memory, as the renderer holds them                                              */
 int rt_probe_noise_value(int device, const rt_perlin* perlin, const float albedo[3], float scale, const float* points, size_t n, float* out_rgb);
 /* rt_environment_sample_batch on the device, one lane per quadruple: the records and the tables as the renderer holds them in mode RT_LIGHT_SAMPLING_ENV        */

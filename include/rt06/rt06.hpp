@@ -389,6 +389,18 @@ public:
         check(rt_scene_microfacets(s_, out, &n), "rt_scene_microfacets");
         return n;
     }
+    // solid glass (extension; rt_scene_set_interior): a Dielectric whose parallelograms, triangles and meshes know inside from outside by their
+    // winding and absorb exp(-sigma distance) per channel along a segment that ends inside; the table as rt_scene_interiors hands it out
+    void SetInterior(uint32_t material, glm::vec3 sigma = glm::vec3(0.0f)) {
+        const float s3[3] = {sigma.x, sigma.y, sigma.z};
+        check(rt_scene_set_interior(s_, material, s3), "rt_scene_set_interior");
+    }
+    void ClearInterior(uint32_t material) { check(rt_scene_clear_interior(s_, material), "rt_scene_clear_interior"); }
+    uint32_t Interiors(const rt_interior** out) const {
+        uint32_t n = 0;
+        check(rt_scene_interiors(s_, out, &n), "rt_scene_interiors");
+        return n;
+    }
     // child reference of a bvh_node tree: >= 0 node, < 0 primitive
     int32_t tree_ref(const Hittable* h) {
         if (h->kind() == Hittable::NODE) {
@@ -654,6 +666,10 @@ class Renderer {
             if (table_says_more || ((n_nmaps || roughness_mapped) && n_tex)) made.SetTextures(tex, n_tex, texels);
             if (n_nmaps) made.SetNormalMaps(nmaps, n_nmaps);
             if (n_mfacs) made.SetMicrofacets(mfacs, n_mfacs);
+            const rt_interior* interiors = nullptr;       // ... and one with interior records theirs
+            uint32_t n_interiors = 0;
+            rt06::check(rt_scene_interiors(static_cast<const BVH*>(world)->scene, &interiors, &n_interiors), "rt_scene_interiors");
+            if (n_interiors) made.SetInteriors(interiors, n_interiors);
         }
         return made;
     }
@@ -775,6 +791,12 @@ public:
     void SetMicrofacets(const rt_microfacet* table, uint32_t n) {
         if (m.mr) rt06::check(rt_multi_renderer_microfacets(m.mr, table, n), "Renderer::SetMicrofacets");
         else rt06::check(rt_renderer_microfacets(m.r, table, n), "Renderer::SetMicrofacets");
+    }
+    // Solid glass (extension; rt_renderer_interiors): one record per material of the world as SceneBuilder::Interiors hands them out, or
+    // (nullptr, 0) for off; restarts a refinement
+    void SetInteriors(const rt_interior* table, uint32_t n) {
+        if (m.mr) rt06::check(rt_multi_renderer_interiors(m.mr, table, n), "Renderer::SetInteriors");
+        else rt06::check(rt_renderer_interiors(m.r, table, n), "Renderer::SetInteriors");
     }
     void SetTextures(const rt_texture* records, uint32_t n, const uint8_t* texels) {
         if (m.mr) rt06::check(rt_multi_renderer_textures(m.mr, records, n, texels), "Renderer::SetTextures");

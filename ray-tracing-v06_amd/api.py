@@ -205,6 +205,32 @@ class Scene:
         check(lib().rt_scene_microfacets(self.h, C.byref(rec), C.byref(n)))
         return None if n.value == 0 else self._arr(rec.value, n.value, capi.MICROFACET_DT)
 
+    def set_interior(self, material, sigma=None, color=None, at=None):
+        """Makes `material`, a Dielectric, solid glass (extension; rt_scene_set_interior): its parallelograms, triangles and meshes know inside from
+        outside by their winding, and a segment that ends inside it is absorbed by exp(-sigma distance) per channel.  sigma: the absorption coefficient per unit
+        length (one number or three; default 0: facing alone) — or color and at: the tint white light has after `at` units of glass, sigma = -ln(color) / at,
+        computed in double."""
+        if (color is None) != (at is None) or (sigma is not None and color is not None):
+            raise ValueError("set_interior: give sigma, or color and at together")
+        if color is not None:
+            c = np.broadcast_to(np.asarray(color, np.float64), (3,))
+            if not (np.all(c > 0.0) and np.all(c <= 1.0) and float(at) > 0.0):
+                raise ValueError("set_interior: a color lies in (0, 1] per channel and `at` is a positive distance")
+            sigma = -np.log(c) / float(at) + 0.0
+        s3 = np.broadcast_to(np.asarray(0.0 if sigma is None else sigma, np.float64), (3,))
+        check(lib().rt_scene_set_interior(self.h, material, (C.c_float * 3)(*[float(x) for x in s3])))
+        return self
+
+    def clear_interior(self, material):
+        check(lib().rt_scene_clear_interior(self.h, material))
+        return self
+
+    def interiors(self):
+        """The scene's interior table (rt_scene_interiors): one record of capi.INTERIOR_DT per material, or None while no material has a record."""
+        rec, n = C.c_void_p(), C.c_uint32()
+        check(lib().rt_scene_interiors(self.h, C.byref(rec), C.byref(n)))
+        return None if n.value == 0 else self._arr(rec.value, n.value, capi.INTERIOR_DT)
+
     def MakeBox(self, a, b, mat, rotate_y=0.0, translate=(0, 0, 0)):
         """box(a, b, mat) of "The Next Week" as 6 quads, optionally rotate_y(degrees) then translate; returns the first quad index."""
         out = C.c_int32()
@@ -414,6 +440,9 @@ class Scene:
             w.microfacets = mfacs
             if table is not None and np.isin(mfacs["on"], (capi.MICROFACET_MAPPED, capi.MICROFACET_GLASS_MAPPED)).any():
                 w.textures = table
+        interiors = self.interiors()          # likewise the interior records, which need no other table
+        if interiors is not None:
+            w.interiors = interiors
         return w
 
     def _arr(self, ptr, n, dt):
@@ -556,6 +585,13 @@ def _push_normal_maps(fn, handle, table):
     return fn(handle, table.ctypes.data if len(table) else None, len(table))
 
 
+def _push_interiors(fn, handle, table):
+    if table is None:
+        return fn(handle, None, 0)
+    table = np.ascontiguousarray(table, capi.INTERIOR_DT).reshape(-1)
+    return fn(handle, table.ctypes.data if len(table) else None, len(table))
+
+
 def _push_microfacets(fn, handle, table):
     if table is None:
         return fn(handle, None, 0)
@@ -603,6 +639,8 @@ class Renderer:
             r.normal_maps(world.normal_maps)
         if getattr(world, "microfacets", None) is not None:
             r.microfacets(world.microfacets)
+        if getattr(world, "interiors", None) is not None:
+            r.interiors(world.interiors)
         return r
 
     def Render(self):
@@ -781,8 +819,26 @@ class Renderer:
         check(lib().rt_renderer_microfacets_info(self.h, out))
         return {"enabled": bool(out[0]), "records": out[1]}
 
+    def interiors(self, table):
+        """The interior table from the next launch on (rt_renderer_interiors): one record of capi.INTERIOR_DT per material as Scene.interiors()
+        gives it; None = off.  A change restarts the refinement."""
+        check(_push_interiors(lib().rt_renderer_interiors, self.h, table))
+
+    def interiors_info(self):
+        """{'enabled', 'records'} of the renderer's interior table: records = how many materials have one."""
+        out = (C.c_uint32 * 2)()
+        check(lib().rt_renderer_interiors_info(self.h, out))
+        return {"enabled": bool(out[0]), "records": out[1]}
+
+    def kernel_interior(self):
+        """True when the next launch runs the streaming kernel's solid-glass family (rt_renderer_kernel_interior): an interior table is on."""
+        out = C.c_uint32(0)
+        check(lib().rt_renderer_kernel_interior(self.h, C.byref(out)))
+        return bool(out.value)
+
     def kernel_microfacet(self):
-        """True when the next launch runs the streaming kernel's microfacet family (rt_renderer_kernel_microfacet): a microfacet table is on."""
+        """True when the next launch runs the streaming kernel's microfacet family (rt_renderer_kernel_microfacet): a microfacet table is on, or an
+        interior table — the solid-glass forms (kernel_interior) are microfacet forms that read one more table."""
         out = C.c_uint32(0)
         check(lib().rt_renderer_kernel_microfacet(self.h, C.byref(out)))
         return bool(out.value)
@@ -906,6 +962,8 @@ class MultiRenderer:
             m.normal_maps(world.normal_maps)
         if getattr(world, "microfacets", None) is not None:
             m.microfacets(world.microfacets)
+        if getattr(world, "interiors", None) is not None:
+            m.interiors(world.interiors)
         return m
 
     def Render(self):
@@ -952,6 +1010,10 @@ class MultiRenderer:
     def microfacets(self, table):
         """rt_renderer_microfacets on every rank; `table` as Renderer.microfacets takes it."""
         check(_push_microfacets(lib().rt_multi_renderer_microfacets, self.h, table))
+
+    def interiors(self, table):
+        """rt_renderer_interiors on every rank; `table` as Renderer.interiors takes it."""
+        check(_push_interiors(lib().rt_multi_renderer_interiors, self.h, table))
 
     def microfacets_info(self):
         """{'enabled', 'records'} of the ranks' microfacet table (they hold the same one)."""
@@ -1312,6 +1374,47 @@ def microfacet_batch(normal, ray_d, roughness, f0, coat, tapes):
 def probe_microfacet(normal, ray_d, roughness, f0, coat, tapes, device=0):
     """rt_probe_microfacet: microfacet_batch on the device, one lane per case"""
     return _microfacet(lambda *args: lib().rt_probe_microfacet(device, *args), normal, ray_d, roughness, f0, coat, tapes)
+
+
+def _interior(fn, Ng, n, ray_d, t, ior, sigma, sphere):
+    Ng, n, ray_d, sigma = (np.ascontiguousarray(x, np.float32).reshape(-1, 3) for x in (Ng, n, ray_d, sigma))
+    t, ior = (np.ascontiguousarray(x, np.float32).reshape(-1) for x in (t, ior))
+    sphere = np.ascontiguousarray(sphere, np.uint32).reshape(-1)
+    k = len(t)
+    if not all(len(x) == k for x in (Ng, n, ray_d, sigma, ior, sphere)):
+        raise ValueError("interior: every array must have one entry per case")
+    back, eta, T = np.zeros(k, np.uint32), np.zeros(k, np.float32), np.zeros((k, 3), np.float32)
+    check(fn(k, Ng, n, ray_d, t, ior, sigma, sphere, back, eta, T))
+    return back, eta, T
+
+
+def interior_batch(Ng, n, ray_d, t, ior, sigma, sphere):
+    """rt_interior_batch (host only): the solid-glass rule on k cases — per case the stored normal Ng, the shading normal n (a sphere's outward
+    normal), the ray's direction, the hit's parameter t, the index of refraction, sigma (k, 3) and sphere != 0 for a hit on a sphere -> (back (k,) 0 / 1,
+    eta (k,), T (k, 3))"""
+    return _interior(lib().rt_interior_batch, Ng, n, ray_d, t, ior, sigma, sphere)
+
+
+def probe_interior(Ng, n, ray_d, t, ior, sigma, sphere, device=0):
+    """rt_probe_interior: interior_batch on the device, one lane per case"""
+    return _interior(lambda *args: lib().rt_probe_interior(device, *args), Ng, n, ray_d, t, ior, sigma, sphere)
+
+
+def _expf(fn, x):
+    x = np.ascontiguousarray(x, np.float32).reshape(-1)
+    out = np.zeros(len(x), np.float32)
+    check(fn(len(x), x, out))
+    return out
+
+
+def expf_batch(x):
+    """rt_expf_batch (host only): rt_expf of every x, the library's own exponential (rt_math.hpp)"""
+    return _expf(lib().rt_expf_batch, x)
+
+
+def probe_expf(x, device=0):
+    """rt_probe_expf: expf_batch on the device, one lane per value"""
+    return _expf(lambda *args: lib().rt_probe_expf(device, *args), x)
 
 
 def _rough_glass(fn, normal, ray_d, roughness, ior, tapes):

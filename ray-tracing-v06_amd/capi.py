@@ -40,6 +40,8 @@ MICROFACET_DT = np.dtype([("on", "<u4"), ("image", "<u4"), ("roughness", "<f4"),
 MICROFACET_OFF, MICROFACET_CONSTANT, MICROFACET_MAPPED = 0, 1, 2
 MFAC_SPECULAR, MFAC_BASE, MFAC_ABSORBED, MFAC_BACKSIDE = 1, 2, 3, 4
 MICROFACET_GLASS, MICROFACET_GLASS_MAPPED, MFAC_TRANSMITTED = 4, 6, 5   # rough glass
+INTERIOR_DT = np.dtype([("on", "<u4"), ("sigma", "<f4", 3)])   # rt_interior, 16 B
+INTERIOR_OFF, INTERIOR_SOLID = 0, 1
 WRAP_CLAMP, WRAP_REPEAT = 0, 1
 FILTER_NEAREST, FILTER_BILINEAR = 0, 1
 MAX_IMAGES = 256
@@ -117,6 +119,8 @@ SYMBOLS = [
     "rt_scene_set_microfacet", "rt_scene_set_roughness_map", "rt_scene_clear_microfacet", "rt_scene_microfacets", "rt_microfacet_batch", "rt_probe_microfacet",
     "rt_renderer_microfacets", "rt_renderer_microfacets_info", "rt_renderer_kernel_microfacet", "rt_multi_renderer_microfacets", "rt_multi_renderer_microfacets_info",
     "rt_scene_set_rough_glass", "rt_rough_glass_batch", "rt_probe_rough_glass",
+    "rt_scene_set_interior", "rt_scene_clear_interior", "rt_scene_interiors", "rt_interior_batch", "rt_probe_interior", "rt_expf_batch", "rt_probe_expf",
+    "rt_renderer_interiors", "rt_renderer_interiors_info", "rt_renderer_kernel_interior", "rt_multi_renderer_interiors",
 ]
 
 _lib = None
@@ -262,6 +266,17 @@ def lib():
     L.rt_renderer_kernel_microfacet.argtypes = [C.c_void_p, P(C.c_uint32)]
     L.rt_multi_renderer_microfacets.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     L.rt_multi_renderer_microfacets_info.argtypes = [C.c_void_p, C.c_uint32 * 2]
+    L.rt_scene_set_interior.argtypes = [C.c_void_p, C.c_uint32, C.c_float * 3]
+    L.rt_scene_clear_interior.argtypes = [C.c_void_p, C.c_uint32]
+    L.rt_scene_interiors.argtypes = [C.c_void_p, P(C.c_void_p), P(C.c_uint32)]
+    L.rt_interior_batch.argtypes = [C.c_size_t, f32p, f32p, f32p, f32p, f32p, f32p, u32p, u32p, f32p, f32p]
+    L.rt_probe_interior.argtypes = [C.c_int] + L.rt_interior_batch.argtypes
+    L.rt_expf_batch.argtypes = [C.c_size_t, f32p, f32p]
+    L.rt_probe_expf.argtypes = [C.c_int] + L.rt_expf_batch.argtypes
+    L.rt_renderer_interiors.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+    L.rt_renderer_interiors_info.argtypes = [C.c_void_p, C.c_uint32 * 2]
+    L.rt_renderer_kernel_interior.argtypes = [C.c_void_p, P(C.c_uint32)]
+    L.rt_multi_renderer_interiors.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     L.rt_scene_set_background.argtypes = [C.c_void_p, C.c_uint32, vec3]
     L.rt_scene_set_perlin.argtypes = [C.c_void_p, C.c_uint64]
     L.rt_scene_set_image.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]

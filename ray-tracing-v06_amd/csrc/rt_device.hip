@@ -60,6 +60,7 @@ constexpr uint32_t RT_KEY_LTREE = 1u << 12; // the light tree (mode RT_LIGHT_SAM
 constexpr uint32_t RT_KEY_ENVL = 1u << 13;  // environment light sampling (mode RT_LIGHT_SAMPLING_ENV): the ENVL form of an EXT 2 TRI && NEE key; reported by rt_renderer_kernel_env_light
 constexpr uint32_t RT_KEY_NMAP = 1u << 14;  // normal maps (rt_renderer_normal_maps): the NMAP form of an EXT 2 TRI key, plain or with mode 48; reported by rt_renderer_kernel_normal_map
 constexpr uint32_t RT_KEY_MFAC = 1u << 15;  // microfacet surfaces (rt_renderer_microfacets): the MFAC form of an EXT 2 TRI key, plain or with mode 48, which reads the normal-map table too; reported by rt_renderer_kernel_microfacet
+constexpr uint32_t RT_KEY_INTR = 1u << 16;  // solid glass (rt_renderer_interiors): the INTR form of an MFAC key, plain or with mode 48, which reads all three tables; reported by rt_renderer_kernel_interior
 constexpr uint32_t RT_KEY_TRI = 1u << 11;   // the world has triangles: the TRI form of an EXT >= 1 stack-walk or list key, plain or NEE; not one of rt_renderer_kernel_form's fields
 // a stream key read back into render_kernel_stream's template arguments, in stream_key()'s order, then NEE: what rt_renderer_kernel_form reports
 static void stream_key_fields(uint32_t key, uint32_t out[8]) {
@@ -106,13 +107,17 @@ static const void* stream_kernel_for(uint32_t key) {
 #define RT_KERNEL_ENV_TREE(exact, world, ext, big, wide) \
     case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NEE | RT_KEY_LTREE | RT_KEY_ENVL: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, true, true, true, true>)
 #define RT_KERNEL_NORMAL_MAP(exact, world, ext, big, wide) \
-    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NMAP: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, false, true, false, false, false, true>)
+    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NMAP: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, false, true, false, false, false, false, true>)
 #define RT_KERNEL_NORMAL_MAP_ENV_TREE(exact, world, ext, big, wide) \
-    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NEE | RT_KEY_LTREE | RT_KEY_ENVL | RT_KEY_NMAP: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, true, true, true, true, false, true>)
+    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NEE | RT_KEY_LTREE | RT_KEY_ENVL | RT_KEY_NMAP: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, true, true, true, true, false, false, true>)
 #define RT_KERNEL_MICROFACET(exact, world, ext, big, wide) \
-    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_MFAC: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, false, true, false, false, true, true>)
+    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_MFAC: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, false, true, false, false, false, true, true>)
 #define RT_KERNEL_MICROFACET_ENV_TREE(exact, world, ext, big, wide) \
-    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NEE | RT_KEY_LTREE | RT_KEY_ENVL | RT_KEY_MFAC: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, true, true, true, true, true, true>)
+    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NEE | RT_KEY_LTREE | RT_KEY_ENVL | RT_KEY_MFAC: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, true, true, true, true, false, true, true>)
+#define RT_KERNEL_INTERIOR(exact, world, ext, big, wide) \
+    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_MFAC | RT_KEY_INTR: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, false, true, false, false, true, true, true>)
+#define RT_KERNEL_INTERIOR_ENV_TREE(exact, world, ext, big, wide) \
+    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NEE | RT_KEY_LTREE | RT_KEY_ENVL | RT_KEY_MFAC | RT_KEY_INTR: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, true, true, true, true, true, true, true>)
     switch (key) {   // arguments: exact, filter, world, ext, big, wide, tol
         case RT_KEY_XCHG: return reinterpret_cast<const void*>(&render_kernel_xchg<RT_XCHG_BLOCK>);
         RT_KERNEL(true, false, RT_WORLD_BVH_QUEUE, 2, true, true, false); RT_KERNEL(true, false, RT_WORLD_BVH_QUEUE, 1, true, true, false); RT_KERNEL(true, false, RT_WORLD_BVH_QUEUE, 0, true, true, false);
@@ -182,9 +187,23 @@ static const void* stream_kernel_for(uint32_t key) {
         RT_KERNEL_MICROFACET_ENV_TREE(false, RT_WORLD_BVH, 2, true, false); RT_KERNEL_MICROFACET_ENV_TREE(true, RT_WORLD_BVH, 2, true, false);
         RT_KERNEL_MICROFACET_ENV_TREE(true, RT_WORLD_LIST, 2, false, false);
         RT_KERNEL_MICROFACET_ENV_TREE(false, RT_WORLD_BVH, 2, false, false); RT_KERNEL_MICROFACET_ENV_TREE(true, RT_WORLD_BVH, 2, false, false);
+        // solid glass: the microfacet shapes once more, reading the sub-header and the interior records, plain ...
+        RT_KERNEL_INTERIOR(true, RT_WORLD_LIST, 2, true, true);
+        RT_KERNEL_INTERIOR(false, RT_WORLD_BVH, 2, true, true); RT_KERNEL_INTERIOR(true, RT_WORLD_BVH, 2, true, true);
+        RT_KERNEL_INTERIOR(false, RT_WORLD_BVH, 2, true, false); RT_KERNEL_INTERIOR(true, RT_WORLD_BVH, 2, true, false);
+        RT_KERNEL_INTERIOR(true, RT_WORLD_LIST, 2, false, false);
+        RT_KERNEL_INTERIOR(false, RT_WORLD_BVH, 2, false, false); RT_KERNEL_INTERIOR(true, RT_WORLD_BVH, 2, false, false);
+        // ... and under mode 48
+        RT_KERNEL_INTERIOR_ENV_TREE(true, RT_WORLD_LIST, 2, true, true);
+        RT_KERNEL_INTERIOR_ENV_TREE(false, RT_WORLD_BVH, 2, true, true); RT_KERNEL_INTERIOR_ENV_TREE(true, RT_WORLD_BVH, 2, true, true);
+        RT_KERNEL_INTERIOR_ENV_TREE(false, RT_WORLD_BVH, 2, true, false); RT_KERNEL_INTERIOR_ENV_TREE(true, RT_WORLD_BVH, 2, true, false);
+        RT_KERNEL_INTERIOR_ENV_TREE(true, RT_WORLD_LIST, 2, false, false);
+        RT_KERNEL_INTERIOR_ENV_TREE(false, RT_WORLD_BVH, 2, false, false); RT_KERNEL_INTERIOR_ENV_TREE(true, RT_WORLD_BVH, 2, false, false);
         default: return nullptr;
     }
 #undef RT_KERNEL
+#undef RT_KERNEL_INTERIOR
+#undef RT_KERNEL_INTERIOR_ENV_TREE
 #undef RT_KERNEL_MICROFACET
 #undef RT_KERNEL_MICROFACET_ENV_TREE
 #undef RT_KERNEL_NORMAL_MAP
@@ -334,8 +353,11 @@ struct rt_renderer {
     // microfacet surfaces (rt_renderer_microfacets): one record per material as given; the tail carries them last, and the bits above bit 0 of its
     // header's first lane say where.  While on, a plain launch and a mode-48 launch run the MFAC form of their kernel, which reads the normal-map table too.
     struct Microfacets { bool on = false; uint32_t n_on = 0; std::vector<rt_microfacet> host; } mf;
-    struct { uint32_t key = 0; const void* kernel = nullptr; } nm_plain, nm_envt, mf_plain, mf_envt;
-    bool tail_on() const { return vn.on || uv.on || env.on || tex.on || mf.on; }
+    // solid glass (rt_renderer_interiors): one record per material as given; with a table the tail's first lane counts to a sub-header, behind which
+    // the microfacet and the interior records lie.  While on, a plain launch and a mode-48 launch run the INTR form of their kernel, which reads all three tables.
+    struct Interiors { bool on = false; uint32_t n_on = 0; std::vector<rt_interior> host; } in;
+    struct { uint32_t key = 0; const void* kernel = nullptr; } nm_plain, nm_envt, mf_plain, mf_envt, in_plain, in_envt;
+    bool tail_on() const { return vn.on || uv.on || env.on || tex.on || mf.on || in.on; }
     // the NMAP form of the renderer's kernel: the world's own shape at EXT 2 with TRI, plain or with mode 48's bits (0: a world no NMAP form walks)
     uint32_t normal_map_key(bool envt) const {
         if (variant < 2 || variant == 5 || tol || scene.queue || scene.dw.kind == RT_WORLD_NODE_TREE) return 0u;
@@ -395,6 +417,8 @@ struct rt_renderer {
         if (nm.on && mode == RT_LIGHT_SAMPLING_ENV_TREE) { l.kernel = nm_envt.kernel; l.key = nm_envt.key; }
         if (mf.on && !m) { l.kernel = mf_plain.kernel; l.key = mf_plain.key; }   // §29: likewise, and before a normal-map table's form: the MFAC forms read both
         if (mf.on && mode == RT_LIGHT_SAMPLING_ENV_TREE) { l.kernel = mf_envt.kernel; l.key = mf_envt.key; }
+        if (in.on && !m) { l.kernel = in_plain.kernel; l.key = in_plain.key; }   // §32: likewise, and before either of them: the INTR forms read all three
+        if (in.on && mode == RT_LIGHT_SAMPLING_ENV_TREE) { l.kernel = in_envt.kernel; l.key = in_envt.key; }
         l.blob = (im.blob.p ? im.blob : scene.blob).as<uint4>();
         l.blob_vec4 = scene.packed.blob_vec4 + im.table_vec4;
         l.lds_bytes = i ? im.lds_bytes : stream_lds_bytes;
@@ -425,6 +449,18 @@ struct rt_renderer {
         slot_of.key = key; slot_of.kernel = k;
         return RT_OK;
     }
+    // §32: the INTR form of the plain kernel, or of mode 48's, once: the MFAC form's shape with the interior bit beside the microfacet bit
+    int resolve_interior_kernel(bool envt, uint32_t lds_bytes) {
+        auto& slot_of = envt ? in_envt : in_plain;
+        if (slot_of.kernel) return RT_OK;
+        const uint32_t nmap_key = normal_map_key(envt);
+        const uint32_t key = nmap_key ? (nmap_key & ~RT_KEY_NMAP) | RT_KEY_MFAC | RT_KEY_INTR : 0u;
+        const void* k = key ? stream_kernel_for(key) : nullptr;
+        if (!k) return rt_fail(RT_ERR_INVALID, "rt_renderer_interiors: this world's kernel has no form that reads an interior table");
+        HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+        slot_of.key = key; slot_of.kernel = k;
+        return RT_OK;
+    }
     // Image i (0: the plain one; 1 to 4: with the light table of mode 1, 2, 4, 16) from the riders as they stand, into `fresh`: scene | light table | tail
     // (rt_launch_image.hpp has both layouts).  The scene part is copied device to device, the rest uploaded once.  The plain image without a tail gets no buffer.
     int compose(uint32_t i, Image& fresh) const {
@@ -448,6 +484,7 @@ struct rt_renderer {
         rd.textures = tex.on; rd.texture = tex.records.data(); rd.n_textures = tex.records.size(); rd.texture_texels = (uint64_t)reinterpret_cast<uintptr_t>(tex.texels.p);
         if (nm.on) { rd.normal_maps = nm.host.data(); rd.n_normal_maps = nm.host.size(); }
         if (mf.on) { rd.microfacets = mf.host.data(); rd.n_microfacets = mf.host.size(); }
+        if (in.on) { rd.interiors = in.host.data(); rd.n_interiors = in.host.size(); }
         rt_image::append_tail(rest, rd);
         const size_t scene_bytes = (size_t)scene.packed.blob_vec4 * sizeof(uint4);
         HIP_TRY(fresh.blob.alloc(scene_bytes + rest.size() * sizeof(uint4)));
@@ -1053,6 +1090,8 @@ extern "C" int rt_renderer_light_sampling_enable(rt_renderer* r, uint32_t on) {
             return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: the renderer has a normal-map table, and light-sampling mode %u has no kernel that reads one: normal maps render with light sampling off or in mode 48 (take the table away with rt_renderer_normal_maps(NULL, 0) first)", on);
         if (r->mf.on && on != RT_LIGHT_SAMPLING_ENV_TREE)
             return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: the renderer has a microfacet table, and light-sampling mode %u has no kernel that reads one: microfacet surfaces render with light sampling off or in mode 48 (take the table away with rt_renderer_microfacets(NULL, 0) first)", on);
+        if (r->in.on && on != RT_LIGHT_SAMPLING_ENV_TREE)
+            return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: the renderer has an interior table, and light-sampling mode %u has no kernel that reads one: solid glass renders with light sampling off or in mode 48 (take the table away with rt_renderer_interiors(NULL, 0) first)", on);
         if (m->env && r->scene.dw.background != 2u)   // a world of this kind takes the modes of the light tables only, so the message lists them
             return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: mode %u samples the environment map of a world with background mode 2 (rt_scene_set_environment)%s; this world's is %u, for which on must be 0 (off), 1 (quad lights), 2 (quad and sphere lights), 4 (quad, sphere and triangle lights) or 16 (those, through a light tree, chosen by area)", on, m->beside, r->scene.dw.background);
         if (m->env && r->scene.queue)
@@ -1085,6 +1124,8 @@ extern "C" int rt_renderer_light_sampling_enable(rt_renderer* r, uint32_t on) {
             if (const int rc = r->resolve_normal_map_kernel(true, r->launch_on(on).lds_bytes)) return rc;
         if (r->mf.on)   // §29: likewise
             if (const int rc = r->resolve_microfacet_kernel(true, r->launch_on(on).lds_bytes)) return rc;
+        if (r->in.on)   // §32: likewise
+            if (const int rc = r->resolve_interior_kernel(true, r->launch_on(on).lds_bytes)) return rc;
         if (m->env && !r->env.dist_on) {   // the distribution of the map as it stands (a map given while the mode is on brings its own: rt_renderer_environment); an all-black map is refused here
             char who[64];
             std::snprintf(who, sizeof(who), "rt_renderer_light_sampling_enable: mode %u", on);
@@ -1354,6 +1395,55 @@ extern "C" int rt_renderer_microfacets_info(rt_renderer* r, uint32_t out[2]) {
     if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets_info: null argument");
     out[0] = r->mf.on ? 1u : 0u;
     out[1] = r->mf.on ? r->mf.n_on : 0u;
+    return RT_OK;
+}
+
+// Solid glass.  Off: every launch is what it was.  On: the INTR form of the renderer's kernel on images whose tail ends with a sub-header and both
+// record tables.  A refusal leaves the table and the kernel as they were.
+extern "C" int rt_renderer_interiors(rt_renderer* r, const rt_interior* table, uint32_t n) {
+    if (!r) return rt_fail(RT_ERR_INVALID, "rt_renderer_interiors: null renderer");
+    if ((table == nullptr) != (n == 0u)) return rt_fail(RT_ERR_INVALID, "rt_renderer_interiors: a table and its count go together (NULL, 0 turns it off)");
+    uint32_t n_on = 0;
+    if (n) {
+        if (r->variant < 2) return rt_fail(RT_ERR_INVALID, "rt_renderer_interiors: the baseline kernel (variant 1) reads no interior table; use variant 0, 2 or 3");
+        if (r->variant == 5 || r->tol) return rt_fail(RT_ERR_INVALID, "rt_renderer_interiors: kernel variant %u reads no interior table", r->tol ? 6u : 5u);
+        if (r->scene.queue) return rt_fail(RT_ERR_INVALID, "rt_renderer_interiors: a world with a queue or wide4 traversal renders on lane walks that read no interior table (RT_TRAVERSAL_STACK and lists do)");
+        if (r->scene.dw.kind == RT_WORLD_NODE_TREE) return rt_fail(RT_ERR_INVALID, "rt_renderer_interiors: a bvh_node tree renders on a walk that reads no interior table (BVHs walked by the stack and lists do)");
+        if (r->nee.on() && r->nee.mode != RT_LIGHT_SAMPLING_ENV_TREE)
+            return rt_fail(RT_ERR_INVALID, "rt_renderer_interiors: light-sampling mode %u is on, which has no kernel that reads an interior table: solid glass renders with light sampling off or in mode 48", r->nee.mode);
+        if (n != r->scene.dw.n_mats) return rt_fail(RT_ERR_INVALID, "rt_renderer_interiors: %u records for a world of %u materials", n, r->scene.dw.n_mats);
+        for (uint32_t i = 0; i < n; i++) {
+            if (table[i].on == RT_INTERIOR_OFF) continue;
+            if (table[i].on != RT_INTERIOR_SOLID) return rt_fail(RT_ERR_INVALID, "rt_renderer_interiors: record %u: on is 0 (off) or 1 (solid), not %u", i, table[i].on);
+            if (r->scene.mat_types[i] != RT_MAT_DIELECTRIC) return rt_fail(RT_ERR_INVALID, "rt_renderer_interiors: record %u: an interior record belongs on a dielectric alone", i);
+            for (int c = 0; c < 3; c++)
+                if (!(std::isfinite(table[i].sigma[c]) && table[i].sigma[c] >= 0.0f)) return rt_fail(RT_ERR_INVALID, "rt_renderer_interiors: record %u: an absorption coefficient must be finite and >= 0", i);
+            n_on++;
+        }
+    }
+    rt_renderer::Interiors next;
+    if (n) {
+        next.on = true; next.n_on = n_on; next.host.assign(table, table + n);
+        for (rt_interior& m : next.host)   // what no kernel reads is zero, so that equal tables are equal bytes; -0 is 0
+            for (int c = 0; c < 3; c++) m.sigma[c] = m.on == RT_INTERIOR_OFF ? 0.0f : m.sigma[c] + 0.0f;
+    }
+    if (n ? (r->in.on && r->in.host.size() == n && std::memcmp(r->in.host.data(), next.host.data(), (size_t)n * sizeof(rt_interior)) == 0) : !r->in.on) return RT_OK;   // nothing changes, the refinement goes on
+    if (const int rc = wait_last_call(r)) return rc;   // launches already enqueued read the images that are replaced below (sets the device)
+    if (n) {
+        if (const int rc = r->resolve_interior_kernel(false, r->stream_lds_bytes)) return rc;
+        if (r->nee.mode == RT_LIGHT_SAMPLING_ENV_TREE)
+            if (const int rc = r->resolve_interior_kernel(true, r->launch_on(RT_LIGHT_SAMPLING_ENV_TREE).lds_bytes)) return rc;
+    }
+    if (const int rc = r->replace_rider(r->in, next)) return rc;   // (a failure leaves table, images and refinement as they were)
+    r->refine_done = 0;   // samples that crossed the glass by another rule belong to another frame
+    r->aov_done = 0;
+    return RT_OK;
+}
+
+extern "C" int rt_renderer_interiors_info(rt_renderer* r, uint32_t out[2]) {
+    if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_interiors_info: null argument");
+    out[0] = r->in.on ? 1u : 0u;
+    out[1] = r->in.on ? r->in.n_on : 0u;
     return RT_OK;
 }
 
@@ -1653,6 +1743,12 @@ extern "C" int rt_renderer_kernel_normal_map(rt_renderer* r, uint32_t* out) {
 extern "C" int rt_renderer_kernel_microfacet(rt_renderer* r, uint32_t* out) {
     if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_kernel_microfacet: null argument");
     *out = r->variant >= 2 && (r->launch_on(r->nee.mode).key & RT_KEY_MFAC) ? 1u : 0u;
+    return RT_OK;
+}
+// ... and of the solid-glass family, whose forms are microfacet forms too: both queries say 1 of them
+extern "C" int rt_renderer_kernel_interior(rt_renderer* r, uint32_t* out) {
+    if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_kernel_interior: null argument");
+    *out = r->variant >= 2 && (r->launch_on(r->nee.mode).key & RT_KEY_INTR) ? 1u : 0u;
     return RT_OK;
 }
 

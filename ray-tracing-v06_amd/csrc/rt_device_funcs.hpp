@@ -669,6 +669,20 @@ RT_HD uint32_t rough_glass_scatter(f3 N, f3 d, float r, float ior, G& g, f3& out
     return rough_glass_faced(n, eta, d, r, g, out_dir, out_weight);
 }
 
+// Solid glass (rt06.h: rt_scene_set_interior): a dielectric whose material has an interior record knows inside from outside on every kind of
+// surface, and absorbs along the segment that ended inside it.  `back` is the facing as rt06.h's step 1 states it — dot(d, Ng) > 0 on the stored normal of a
+// parallelogram or triangle, the smooth dielectric's own expression on a sphere's outward normal — handed in by who has just evaluated it, so that no bit depends
+// on who did.  Out: eta as the smooth dielectric writes it, and T, the factor of the albedo (ones at a front hit).
+RT_HD void interior_hit(bool back, f3 d, float t, float ior, f3 sigma, float& eta, f3& T) {
+    eta = back ? ior : 1 / ior;                                             // 1
+    T = mk3(1.0f);
+    if (back) {                                                             // 2
+        const float len = sqrtf(dot(d, d));
+        const float dist = t * len;
+        T = mk3(rt_expf(-(sigma.x * dist)), rt_expf(-(sigma.y * dist)), rt_expf(-(sigma.z * dist)));
+    }
+}
+
 // Environment maps (rt06.h: rt_scene_set_environment): what a ray that leaves the world sees.  d = the ray's direction (any length), texels =
 // width x height records (r, g, b, -), row 0 at the top, u0 in [0, 1) = the rotation about y.  image_value's map and constants, the rotation added to u, then
 // image_texel's rule; the clamps are written so that a NaN coordinate lands on texel 0 on host and device alike.  Only + - * / sqrt, comparisons and the two rt_

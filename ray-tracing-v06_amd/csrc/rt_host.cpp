@@ -175,6 +175,8 @@ struct rt_scene {
     mutable std::vector<rt_normal_map> nmap_table;   // what rt_scene_normal_maps last handed out
     std::vector<rt_microfacet> mfacs;    // microfacet surfaces: likewise
     mutable std::vector<rt_microfacet> mfac_table;
+    std::vector<rt_interior> interiors;  // solid glass: likewise
+    mutable std::vector<rt_interior> interior_table;
     std::vector<rt_bvh_node> nodes;     // world nodes (BVH or bvh_node tree)
     std::vector<rt_bvh_node> tree_nodes;  // bvh_node objects created by rt_scene_add_bvh_node
     uint32_t kind = RT_WORLD_LIST;
@@ -1101,6 +1103,36 @@ extern "C" int rt_scene_microfacets(const rt_scene* s, const rt_microfacet** out
     s->mfac_table = s->mfacs;
     s->mfac_table.resize(s->mats.size(), rt_microfacet{RT_MICROFACET_OFF, 0u, 0.0f, 0.0f});
     *out = s->mfac_table.data(); *out_n = (uint32_t)s->mfac_table.size();
+    return RT_OK;
+}
+
+// ---- solid glass ----
+extern "C" int rt_scene_set_interior(rt_scene* s, uint32_t material, const float sigma[3]) {
+    if (!s || !sigma) return rt_fail(RT_ERR_INVALID, "rt_scene_set_interior: null argument");
+    if (material >= s->mats.size()) return rt_fail(RT_ERR_INVALID, "rt_scene_set_interior: the scene has no material %u", material);
+    if (s->mats[material].type != RT_MAT_DIELECTRIC) return rt_fail(RT_ERR_INVALID, "rt_scene_set_interior: material %u is no dielectric; only glass has an inside to absorb in", material);
+    for (int c = 0; c < 3; c++)
+        if (!(std::isfinite(sigma[c]) && sigma[c] >= 0.0f)) return rt_fail(RT_ERR_INVALID, "rt_scene_set_interior: an absorption coefficient must be finite and >= 0");
+    if (s->interiors.size() <= material) s->interiors.resize((size_t)material + 1u, rt_interior{RT_INTERIOR_OFF, {0.0f, 0.0f, 0.0f}});
+    s->interiors[material] = rt_interior{RT_INTERIOR_SOLID, {sigma[0] + 0.0f, sigma[1] + 0.0f, sigma[2] + 0.0f}};   // (-0 is stored as 0)
+    return RT_OK;
+}
+extern "C" int rt_scene_clear_interior(rt_scene* s, uint32_t material) {
+    if (!s) return rt_fail(RT_ERR_INVALID, "rt_scene_clear_interior: null scene");
+    if (material >= s->mats.size()) return rt_fail(RT_ERR_INVALID, "rt_scene_clear_interior: the scene has no material %u", material);
+    if (material < s->interiors.size()) s->interiors[material] = rt_interior{RT_INTERIOR_OFF, {0.0f, 0.0f, 0.0f}};
+    return RT_OK;
+}
+extern "C" int rt_scene_interiors(const rt_scene* s, const rt_interior** out, uint32_t* out_n) {
+    if (!s || !out || !out_n) return rt_fail(RT_ERR_INVALID, "rt_scene_interiors: null argument");
+    *out = nullptr; *out_n = 0u;
+    s->interior_table.clear();
+    bool any = false;
+    for (const rt_interior& m : s->interiors) any = any || m.on != RT_INTERIOR_OFF;
+    if (!any) return RT_OK;
+    s->interior_table = s->interiors;
+    s->interior_table.resize(s->mats.size(), rt_interior{RT_INTERIOR_OFF, {0.0f, 0.0f, 0.0f}});
+    *out = s->interior_table.data(); *out_n = (uint32_t)s->interior_table.size();
     return RT_OK;
 }
 

@@ -91,6 +91,17 @@ RT_HD float rt_logf(float x) {  // x > 0, finite, normal
     float fe = (float)e;
     return fe * 0x1.63p-1f + (fe * -0x1.bd0106p-13f + lm);  // e * ln2 in two words
 }
+// exp(x) for the transmittance of solid glass: x <= 0 is what it is given.  rt_expf(+-0) == 1 exactly; x <= -87 or NaN gives 0, so no denormal
+// is produced (exp(-87) = 1.4 * 2^-126); every result of x <= 0 lies in [0, 1].  Worst error over all fp32 x in [-87, 0]: tools/verify_expf.py.
+RT_HD float rt_expf(float x) {
+    if (!(x > -87.0f)) return 0.0f;
+    float kf = floorf(x * 0x1.715476p+0f + 0.5f);          // nearest multiple of ln 2: |k| <= 126, 7 bits
+    float r = x - kf * 0x1.62e4p-1f;                        // ln 2 in two words (Cody-Waite): the first has 16 bits, so kf times it is exact
+    r = r - kf * 0x1.7f7d1cp-20f;                           // |r| <= ln 2 / 2, a little more at a boundary
+    float p = 1.0f + r * (1.0f + r * (0.5f + r * (0x1.555556p-3f + r * (0x1.555556p-5f + r * (0x1.111112p-7f + r * (0x1.6c16c2p-10f + r * 0x1.a01a02p-13f))))));  // 1/2 ... 1/5040
+    int k = (int)kf;
+    return p * __builtin_bit_cast(float, (uint32_t)(k + 127) << 23);   // 2^k through the exponent bits: k >= -126, and p * 2^k is normal
+}
 RT_HD float rt_sinf(float x) {  // |x| up to a few thousand
     float kf = floorf(x * 0x1.45f306p-1f + 0.5f);          // nearest multiple of pi/2
     int k = (int)kf;

@@ -768,6 +768,64 @@ extern "C" int rt_probe_math(int device, int fn, size_t n, const float* a, const
     p.launch(probe_math_kernel, p.per_case(n), 128, fn, n, da, db, o);
     return p.finish();
 }
+// Solid glass: rt_expf and the rule over arrays of cases, on the device and — HOST (no GPU) — here
+__global__ void probe_expf_kernel(size_t n, const float* x, float* out) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out[i] = rt_expf(x[i]);
+}
+extern "C" int rt_probe_expf(int device, size_t count, const float* x, float* out) {
+    if (!x || !out) return rt_fail(RT_ERR_INVALID, "rt_probe_expf: null argument");
+    if (count == 0) return RT_OK;
+    ProbeRun p(device);
+    auto dx = p.in(x, count);
+    auto o = p.out(out, count);
+    p.launch(probe_expf_kernel, p.per_case(count), 128, count, dx, o);
+    return p.finish();
+}
+extern "C" int rt_expf_batch(size_t count, const float* x, float* out) {
+    if (!x || !out) return rt_fail(RT_ERR_INVALID, "rt_expf_batch: null argument");
+    for (size_t i = 0; i < count; i++) out[i] = rt_expf(x[i]);
+    return RT_OK;
+}
+// one case of the rule: the facing on the stored normal, or — a sphere — on the outward one, then interior_hit
+RT_HD void interior_case(size_t i, const float* Ng, const float* n, const float* d, const float* t, const float* ior, const float* sigma, const uint32_t* sphere,
+                         uint32_t* out_back, float* out_eta, float* out_T) {
+    const f3 dir = ld3(d + 3 * i);
+    const bool back = dot(dir, sphere[i] != 0u ? ld3(n + 3 * i) : ld3(Ng + 3 * i)) > 0;
+    float eta;
+    f3 T;
+    interior_hit(back, dir, t[i], ior[i], ld3(sigma + 3 * i), eta, T);
+    out_back[i] = back ? 1u : 0u; out_eta[i] = eta; st3(out_T + 3 * i, T);
+}
+__global__ void probe_interior_kernel(size_t count, const float* Ng, const float* n, const float* d, const float* t, const float* ior, const float* sigma,
+                                      const uint32_t* sphere, uint32_t* out_back, float* out_eta, float* out_T) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    interior_case(i, Ng, n, d, t, ior, sigma, sphere, out_back, out_eta, out_T);
+}
+static int interior_args(const char* who, const float* Ng, const float* n, const float* d, const float* t, const float* ior, const float* sigma, const uint32_t* sphere,
+                         uint32_t* out_back, float* out_eta, float* out_T) {
+    if (!Ng || !n || !d || !t || !ior || !sigma || !sphere || !out_back || !out_eta || !out_T) return rt_fail(RT_ERR_INVALID, "%s: null argument", who);
+    return RT_OK;
+}
+extern "C" int rt_probe_interior(int device, size_t count, const float* Ng, const float* n, const float* d, const float* t, const float* ior, const float* sigma,
+                                 const uint32_t* sphere, uint32_t* out_back, float* out_eta, float* out_T) {
+    if (const int rc = interior_args("rt_probe_interior", Ng, n, d, t, ior, sigma, sphere, out_back, out_eta, out_T)) return rc;
+    if (count == 0) return RT_OK;
+    ProbeRun p(device);
+    auto dg = p.in(Ng, 3 * count); auto dn = p.in(n, 3 * count); auto dd = p.in(d, 3 * count); auto dt = p.in(t, count); auto di = p.in(ior, count);
+    auto ds = p.in(sigma, 3 * count); auto dk = p.in(sphere, count);
+    auto ob = p.out(out_back, count); auto oe = p.out(out_eta, count); auto oT = p.out(out_T, 3 * count);
+    p.launch(probe_interior_kernel, p.per_case(count), 128, count, dg, dn, dd, dt, di, ds, dk, ob, oe, oT);
+    return p.finish();
+}
+extern "C" int rt_interior_batch(size_t count, const float* Ng, const float* n, const float* d, const float* t, const float* ior, const float* sigma, const uint32_t* sphere,
+                                 uint32_t* out_back, float* out_eta, float* out_T) {
+    if (const int rc = interior_args("rt_interior_batch", Ng, n, d, t, ior, sigma, sphere, out_back, out_eta, out_T)) return rc;
+    for (size_t i = 0; i < count; i++) interior_case(i, Ng, n, d, t, ior, sigma, sphere, out_back, out_eta, out_T);
+    return RT_OK;
+}
 
 // The device half of the math vocabulary (csrc/rt_math.hpp) over arrays: the functions the fixtures tests/golden/glm_*.f32 —
 // generated by the REFERENCE's vendored GLM + glm_utils.h (oracle/ref_glm_probe.cpp) — cover, plus Ray::at / isBackfacing

@@ -270,17 +270,21 @@ __device__ __forceinline__ f3 texture_table_value(const uint4* tt, uint32_t imag
 //      above bit 0 of the header's first lane say; that word is read at the hit, through a scalar, and vn_on keeps bit 0 alone.
 //      Rough glass: a dielectric whose record is a glass one runs rough_glass_faced in the dielectric branch, from the facing that branch has
 //      computed; reflected or transmitted, the albedo is scaled by the rule's weight; absorbed is a failed scatter; handed back, the smooth hit runs verbatim.
+// INTR (rt_renderer_interiors; MFAC only): a dielectric hit whose material has an interior record takes its facing on a parallelogram or triangle
+//      from the stored normal — the comparison set_face_normal makes, kept as q_back — and a back hit scales the albedo by interior_hit's transmittance before
+//      the smooth or rough rule runs.  The tail's first lane then counts the vec4 to a sub-header (to the microfacet records or 0, to the interior records, -, -).
 // LTREE && ENVL (mode RT_LIGHT_SAMPLING_ENV_TREE): both at once.  The light half tosses once more between the map and mode 16's table (no toss
 //      when the table is empty: n_l == 0 is the map alone), the light density is the mean of the map's and the walk's, and an image-textured Lambertian hit is
 //      sampled as the diffuse hit it is — its albedo is looked up behind the direction, as ever.
 template <bool EXACT, bool FILTER, int BLOCK, int WORLD = RT_WORLD_BVH, int EXT = 0, bool BIG = false, bool WIDE = BIG, bool TOL = false, bool NEE = false, bool TRI = false,
-          bool LTREE = false, bool ENVL = false, bool MFAC = false, bool NMAP = false>
+          bool LTREE = false, bool ENVL = false, bool INTR = false, bool MFAC = false, bool NMAP = false>
 // (the second launch bound is hipcc's minimum of waves per SIMD — 6 for 768 threads, what two workgroups per CU are, and all the LDS admits: the register budget is
 //  80, not the 64 of a full SIMD.  The default instantiation took 64 while it needed no more and takes 68 since E23, with no scratch; the occupancy the compiler
 //  reports for it, 8 and now 7, is what its register count would admit, not what the launch gets.)
 __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(StreamParams p) {
     static_assert(!NMAP || (EXT == 2 && TRI), "normal maps: one family of the kernels that read the texture table, plain and with mode 48");
     static_assert(!MFAC || NMAP, "microfacet surfaces: a glossy asset wants its normal map in the same launch, and the roughness map shares the map's (u, v)");
+    static_assert(!INTR || MFAC, "solid glass: one family, the microfacet forms once more, so that a frosted solid is entered and left in the same launch");
     static_assert(!NEE || (EXT >= 1 && WORLD != RT_WORLD_BVH_QUEUE), "light sampling: worlds with quads, walked by the stack or as a list");
     static_assert(!TRI || (EXT >= 1 && WORLD != RT_WORLD_BVH_QUEUE), "triangles: worlds with quads; a lane walk reads the kind from the flat record");
     static_assert(!LTREE || (NEE && TRI), "the light tree: one family, which knows all three kinds of light");
@@ -679,10 +683,16 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                 const f3 hit_p = ray_at(ray, rec_t);
                 f3 normal;
                 uint32_t mat_bits;
+                [[maybe_unused]] bool q_back = false;   // §32, written and read under INTR alone: dot(d, Ng) > 0 on the stored normal of a parallelogram or triangle
                 if (EXT && (uint32_t)rec_code >= p.scene.sphere_codes) {
                     const float4 qs = quads[p.scene.n_quads * 4u + ((uint32_t)rec_code - p.scene.sphere_codes)];   // the quad's shade record
                     normal = mk3(qs.x, qs.y, qs.z);
+                    if constexpr (INTR) {   // §32: the same comparison, kept: the facing of a solid's parallelogram or triangle (it stands twice, as §30's smooth hit does)
+                        q_back = dot(ray.d, normal) > 0;
+                        if (q_back) normal = -normal;
+                    } else {
                     if (dot(ray.d, normal) > 0) normal = -normal;  // the book's set_face_normal: a quad is two-sided
+                    }
                     mat_bits = __float_as_uint(qs.w);
                     if constexpr (TRI) {
                         const uint32_t qi = (uint32_t)rec_code - p.scene.sphere_codes;
@@ -711,7 +721,13 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                 // roughness takes its map's green channel in the block below, which computes the (u, v) when either record needs them
                 uint4 mf_rec = make_uint4(0u, 0u, 0u, 0u);
                 float mf_rough = 0.0f;
-                if constexpr (MFAC) {
+                if constexpr (INTR) {   // §32: the lane counts the vec4 to the sub-header, whose first lane is what the MFAC forms read from the header itself
+                    const uint32_t sub_at = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.scene.blob[p.scene.blob_vec4].x) >> 1;
+                    uint32_t mf_at = 0u;
+                    if (sub_at != 0u) mf_at = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.scene.blob[p.scene.blob_vec4 + sub_at].x);
+                    if (mf_at != 0u) mf_rec = p.scene.blob[p.scene.blob_vec4 + mf_at + (mat_bits & RT_MAT_INDEX_MASK)];
+                    mf_rough = __uint_as_float(mf_rec.z);
+                } else if constexpr (MFAC) {
                     const uint32_t mf_at = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.scene.blob[p.scene.blob_vec4].x) >> 1;
                     if (mf_at != 0u) mf_rec = p.scene.blob[p.scene.blob_vec4 + mf_at + (mat_bits & RT_MAT_INDEX_MASK)];
                     mf_rough = __uint_as_float(mf_rec.z);
@@ -782,9 +798,33 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                 float ior_ratio = 0.0f, reflect_prob = 0.0f;
                 bool must_reflect = false;
                 if (is_diel && !path_over) {
+                    if constexpr (INTR) {
+                        // §32: the interior record of the hit's material, (on, sigma bits x 3), read here alone so that nothing of it lives across the phase.  With a
+                        // record, a parallelogram or triangle takes its facing from the stored normal (q_back; the shading normal already faces the ray and stays),
+                        // a sphere the expression it always took; a back hit ended a segment inside the glass and is charged for it before either rule below.
+                        uint4 in_rec = make_uint4(0u, 0u, 0u, 0u);
+                        const uint32_t sub_at = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.scene.blob[p.scene.blob_vec4].x) >> 1;
+                        if (sub_at != 0u) {
+                            const uint32_t in_at = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.scene.blob[p.scene.blob_vec4 + sub_at].y);
+                            if (in_at != 0u) in_rec = p.scene.blob[p.scene.blob_vec4 + in_at + (mat_bits & RT_MAT_INDEX_MASK)];
+                        }
+                        const bool solid = in_rec.x != 0u;
+                        bool hit_backface;
+                        if (solid && (uint32_t)rec_code >= p.scene.sphere_codes) hit_backface = q_back;
+                        else {
+                            hit_backface = dot(ray.d, normal) > 0;
+                            if (hit_backface) normal = -normal;
+                        }
+                        if (solid) {
+                            f3 in_T;
+                            interior_hit(hit_backface, ray.d, rec_t, mparam, mk3(__uint_as_float(in_rec.y), __uint_as_float(in_rec.z), __uint_as_float(in_rec.w)), ior_ratio, in_T);
+                            if (hit_backface) albedo = albedo * in_T;
+                        } else ior_ratio = hit_backface ? mparam : 1 / mparam;
+                    } else {
                     bool hit_backface = dot(ray.d, normal) > 0;
                     if (hit_backface) normal = -normal;
                     ior_ratio = hit_backface ? mparam : 1 / mparam;
+                    }
                     unit_dir = normalize(ray.d);
                     float cos_theta = fminf(dot(-unit_dir, normal), 1.0f);
                     float sin_theta = sqrtf(1.0f - cos_theta * cos_theta);

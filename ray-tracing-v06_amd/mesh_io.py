@@ -174,8 +174,9 @@ def load_mtl(path):
     (the file is taken as a tangent-space normal map, OpenGL convention, green = +v): "normal_map": path | None and "normal_strength": the `-bm X`
     in front of the name, 1.0 without one; the last such line of a material counts.  The PBR extension's `Pr`, `map_Pr` and `Pm` become
     "roughness": float | None, "roughness_map": path | None and "metallic": float | None.  The keywords glass is told by add keys of their own, each
-    present only when the file has the keyword: `Ni` as "ior" (> 0), `d` and `Tr` as "dissolve" in [0, 1] (Tr = 1 - d), `illum` as "illum" (an integer).  Nothing
-    else of MTL is read."""
+    present only when the file has the keyword: `Ni` as "ior" (> 0), `d` and `Tr` as "dissolve" in [0, 1] (Tr = 1 - d), `illum` as "illum" (an integer).  `Tf r g b` (or `Tf r`), the
+    transmission filter (the tint of solid glass), likewise: "transmission_filter": (r, g, b), each finite and in [0, 1]; its `spectral` and `xyz`
+    forms are not read.  Nothing else of MTL is read."""
     import os
     out, current = {}, None
     beside = lambda name: os.path.join(os.path.dirname(os.path.abspath(path)), *name.replace("\\", "/").split("/"))
@@ -236,6 +237,17 @@ def load_mtl(path):
                         if not (np.isfinite(value) and 0.0 <= value <= 1.0):
                             raise ValueError(f"{where}: {parts[0]} must be finite and in [0, 1]")
                         current["dissolve"] = value if parts[0] == "d" else 1.0 - value
+            elif parts[0] == "Tf":
+                if current is None:
+                    raise ValueError(f"{where}: Tf before any newmtl")
+                if len(parts) >= 2 and parts[1] in ("spectral", "xyz"):
+                    continue
+                if len(parts) not in (2, 4):
+                    raise ValueError(f"{where}: Tf needs one value or three")
+                rgb = tuple(float(x) for x in (parts[1:4] if len(parts) == 4 else parts[1:2] * 3))
+                if not all(np.isfinite(x) and 0.0 <= x <= 1.0 for x in rgb):
+                    raise ValueError(f"{where}: Tf must be finite and in [0, 1]")
+                current["transmission_filter"] = rgb
             elif parts[0] in ("Kd", "map_Kd"):
                 if current is None:
                     raise ValueError(f"{where}: {parts[0]} before any newmtl")
@@ -330,6 +342,58 @@ def icosphere(level):
             nf += [[a, ab, ca], [b, bc, ab], [c, ca, bc], [ab, bc, ca]]
         f = nf
     return np.array(v, np.float32), np.array(f, np.uint32)
+
+
+def _welded(vertices, faces):
+    """the faces over welded vertices — those closer than 1e-6 of the mesh's extent are one, so the seam and the poles of uv_sphere, or an OBJ that repeats a
+    position per texture coordinate, are closed — without the faces that welding leaves degenerate"""
+    v, f = np.asarray(vertices, np.float64).reshape(-1, 3), np.asarray(faces, np.int64).reshape(-1, 3)
+    if len(v) == 0 or len(f) == 0:
+        return f
+    extent = float((v.max(axis=0) - v.min(axis=0)).max())
+    cell = np.round((v - v.min(axis=0)) / (1e-6 * extent)).astype(np.int64) if extent > 0.0 else np.zeros(v.shape, np.int64)
+    f = np.unique(cell, axis=0, return_inverse=True)[1].reshape(-1)[f]
+    return f[(f[:, 0] != f[:, 1]) & (f[:, 1] != f[:, 2]) & (f[:, 2] != f[:, 0])]
+
+
+def _edge_census(vertices, faces):
+    """{(a, b): how many faces run the edge from a to b} over the directed edges of the faces, vertices welded"""
+    f = _welded(vertices, faces)
+    census = {}
+    for a, b in np.concatenate([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]]).tolist():
+        census[(a, b)] = census.get((a, b), 0) + 1
+    return census
+
+
+def signed_volume(vertices, faces):
+    """the volume the faces enclose by the divergence theorem, in double: positive when they are wound counter-clockwise seen from outside"""
+    v, f = np.asarray(vertices, np.float64).reshape(-1, 3), np.asarray(faces, np.int64).reshape(-1, 3)
+    return float(np.einsum("ij,ij->i", v[f[:, 0]], np.cross(v[f[:, 1]], v[f[:, 2]])).sum() / 6.0)
+
+
+def consistently_closed(vertices, faces):
+    """True when every edge is shared by exactly two faces that run it in opposite directions: a closed surface, consistently wound one way or the other"""
+    census = _edge_census(vertices, faces)
+    return len(census) > 0 and all(n == 1 and census.get((b, a), 0) == 1 for (a, b), n in census.items())
+
+
+def closed_outward(vertices, faces):
+    """True when the mesh is closed and consistently wound (consistently_closed) and its signed volume is positive: what the facing rule of solid glass
+     trusts — the stored normal of every face points out of the solid.  Vertices that coincide are one vertex: a seam of duplicated vertices is closed."""
+    return consistently_closed(vertices, faces) and signed_volume(vertices, faces) > 0.0
+
+
+def orient_outward(vertices, faces):
+    """The faces wound outward: as they are when closed_outward holds, every face flipped when the mesh is consistently wound and closed but inside out.
+    Raises ValueError for an open or inconsistently wound mesh, and for one that encloses no volume: such a mesh has no inside, and guessing one is not this
+    function's business."""
+    f = np.asarray(faces).reshape(-1, 3)
+    if not consistently_closed(vertices, f):
+        raise ValueError("orient_outward: the mesh is open or its faces are not consistently wound (every edge must be shared by exactly two faces, in opposite directions)")
+    volume = signed_volume(vertices, f)
+    if volume == 0.0 or not np.isfinite(volume):
+        raise ValueError("orient_outward: the mesh encloses no volume")
+    return f.copy() if volume > 0.0 else np.ascontiguousarray(f[:, ::-1])
 
 
 def from_spec(spec):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Differential fuzz campaign: random worlds (spheres, moving spheres, quads, triangles and meshes, lights, media, textures; every builder; LDS
 and global-memory paths; three cameras) rendered on the GPU and by the CPU oracle, compared bit for bit.
-    python tools/fuzz_campaign.py --seeds 200 [--first 0] [--no-triangles] [--mesh-lights] [--light-tree] [--texture-coords] [--textures] [--env-tree] [--surfaces]
+    python tools/fuzz_campaign.py --seeds 200 [--first 0] [--no-triangles] [--mesh-lights] [--light-tree] [--texture-coords] [--textures] [--env-tree] [--surfaces] [--interiors]
 Prints one line per failure and a summary; exit code 1 if anything differed.  The triangles of a world come from a generator of their own, so the rest of a seed's
 world is what it was before the fuzzer made triangles, and --no-triangles renders exactly those earlier worlds.  Importing this file starts nothing:
 world_of_seed() builds a seed's world on the host, without a device.  --mesh-lights (off by default: the recorded campaigns ran without it) also renders every
@@ -11,7 +11,10 @@ drawn from the seed's generator AFTER every other draw of the case, so committed
 puts every world with quads under the procedural sky as its LAST check — it draws nothing and the scene is not used again — and renders it in light-sampling
 mode 48: both memory forms, and the twin (tests/_env_tree_twin.py) where it follows.  --surfaces also renders every world under the inert normal-map and
 microfacet tables of tests/_surface_worlds.py — on a second scene built from the seed, so it draws nothing and leaves the seed's own scene alone — and holds both
-kernel families, in both memory forms, to the oracle's frame the campaign has computed."""
+kernel families, in both memory forms, to the oracle's frame the campaign has computed.  --interiors builds the seed's world once more with
+glass solids in it — a sphere, a box and a closed mesh, placed, sized and given random interior records by a generator of its own — and holds the INTR family to
+itself (both memory forms; every record off against no table); and, per seed, it renders a second world of static spheres, parallelograms and triangles with such
+solids, built so that tests/_interior_twin.py follows its every sample, and holds both memory forms to the twin on every pixel."""
 import argparse, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -44,6 +47,8 @@ def parse_args(argv=None):
     ap.add_argument("--textures", action="store_true", help="also render the worlds with an image under a texture table of several random images and random modes: the world's image under clamp / nearest must be the oracle's frame, and under another mode pair both memory forms must agree")
     ap.add_argument("--texture-coords", action="store_true", help="also render the worlds with an image and triangles under a table of random texture coordinates on random triangles: both memory forms must agree, and the identity table must be the oracle's frame")
     ap.add_argument("--surfaces", action="store_true", help="also render every world under inert normal-map and microfacet tables (flat maps; records that are all off on the materials in use): the NMAP and the MFAC kernel family, both memory forms, must give the oracle's frame; worlds the families refuse (a lane walk, a kernel variant other than 2 and 3) are counted as skipped")
+    ap.add_argument("--interiors", action="store_true", help="also render every stack-walked or list world with random glass solids under random interior records: the INTR kernel family in both memory forms, every record off "
+                    "against no table, and the twin (tests/_interior_twin.py) where it follows")
     return ap.parse_args(argv)
 
 
@@ -302,6 +307,126 @@ def surfaces_check(p, seed, args, cam, W, H, spp, depth, variant, ref):
     return ok, forms
 
 
+def glass_solids(s, rng):
+    """a glass sphere, a glass box and a closed glass mesh (half the time with vertex normals) into scene s, with random interior records — at least one — and
+    now and then a frosted one, all drawn from rng"""
+    from ray_tracing_v06_amd import mesh_io
+    glass = [s.Dielectric((1, 1, 1), float(rng.choice([1.33, 1.5, 2.4]))) for _ in range(3)]
+    s.MakeSphere((rng.random(3) * 2 - 1) * (4, 1, 4), float(rng.uniform(0.3, 1.2)), glass[0])
+    lo = (rng.random(3) * 2 - 1) * (4, 1, 4)
+    s.MakeBox(lo, lo + rng.uniform(0.3, 2.0, 3), glass[1], rotate_y=float(rng.uniform(0, 90)))
+    v, f = mesh_io.icosphere(int(rng.integers(0, 2))) if rng.random() < 0.7 else mesh_io.tetrahedron()
+    assert mesh_io.closed_outward(v, f)
+    s.MakeMesh(v, f, glass[2], float(rng.uniform(0.4, 1.2)), float(rng.uniform(0, 90)), (rng.random(3) * 2 - 1) * (4, 1, 4),
+               **(dict(normals=mesh_io.vertex_normals(v, f)) if rng.random() < 0.5 else {}))
+    for m in glass:
+        if rng.random() < 0.85:
+            s.set_interior(m, sigma=rng.choice([0.0, 0.1, 1.0, 30.0], 3) * rng.random(3))
+    if rng.random() < 0.3:
+        s.set_rough_glass(glass[int(rng.integers(0, 3))], float(rng.random()))
+    if s.interiors() is None:
+        s.set_interior(glass[1], sigma=(0.5, 0.25, 1.0))
+
+
+def interiors_check(p, seed, args, cam, W, H, spp, depth, variant):
+    """The seed's world once more, built afresh, with glass_solids() in it (a generator of its own: the seed's stays what it is).  The INTR form of the renderer's
+    kernel and its global-memory form must agree, and with every record off the frame must be the frame without a table.  None: not applicable (a lane walk, a
+    variant without the family); else (ok, forms)."""
+    s = world_of_seed(p, seed, not args.no_triangles, args.force_variant)[0]
+    kind = s.getWorldPtr().kind   # (adding to the scene takes its world away until the next build)
+    if s.getWorldPtr().traversal != 0 or kind not in (0, 1):
+        return None
+    glass_solids(s, np.random.default_rng(seed + (32 << 20)))
+    (s.MakeHittableList if kind == 1 else s.BuildBVH_SAH)()
+    w, table = s.getWorldPtr(), s.interiors()
+    sums, forms = [], []
+    for env in ({}, {"RT06_FORCE_BIG": "1"}):
+        os.environ.pop("RT06_FORCE_BIG", None)
+        os.environ.update(env)
+        try:
+            r = p.Renderer.MakeRenderer(W, H, spp, depth, cam, w, variant=variant)
+        except p.capi.RtError:
+            return None   # no kernel of the family for the world
+        finally:
+            os.environ.pop("RT06_FORCE_BIG", None)
+        if r.kernel_info()["variant"] not in (2, 3) or not r.kernel_interior():
+            r.close()
+            return None
+        forms.append(r.kernel_form())
+        r.refine(spp)
+        sums.append(r.refine_sums())
+    r.interiors(np.zeros(len(table), p.capi.INTERIOR_DT))
+    r.refine(spp)
+    off = r.refine_sums()
+    r.interiors(None)
+    r.refine(spp)
+    ok = bits_equal(sums[0], sums[1]) and bits_equal(off, r.refine_sums())
+    r.close()
+    return ok, forms
+
+
+def interiors_twin_world(p, seed):
+    """(scene, pinhole camera, W, H, spp, depth) of a world the twin of tests/_interior_twin.py follows throughout: static spheres, parallelograms, a box and
+    free triangles of Lambertian, metal, glass and — half the time — light materials under a constant background or the gradient, with glass_solids() in it; a
+    BVH by any builder or a list.  The seed's world proper cannot serve: a quarter of its spheres move, and the twin's walk restates static ones."""
+    rng = np.random.default_rng(seed + (33 << 20))
+    s = p.Scene()
+    mats = [s.Lambertian(rng.random(3)), s.Metal(rng.random(3), float(rng.choice([0.0, 0.1, 0.7]))), s.Dielectric((1, 1, 1), float(rng.choice([1.5, 1.33])))]
+    if rng.random() < 0.5:
+        mats.append(s.DiffuseLight(rng.random(3) * float(rng.choice([2.0, 8.0]))))
+    pick = lambda: mats[int(rng.integers(0, len(mats)))]   # noqa: E731
+    for _ in range(int(rng.integers(1, 12))):
+        s.MakeSphere(((rng.random(3) * 2 - 1) * np.array([6, 2, 6])).astype(np.float32), float(rng.choice([0.3, 0.8, 2.5])), pick())
+    for _ in range(int(rng.integers(1, 8))):
+        Q = ((rng.random(3) * 2 - 1) * np.array([6, 3, 6])).astype(np.float32)
+        s.MakeQuad(Q, (rng.standard_normal(3) * 2).astype(np.float32), (rng.standard_normal(3) * 2).astype(np.float32), pick())
+    for _ in range(int(rng.integers(0, 6))):
+        a = ((rng.random(3) * 2 - 1) * np.array([6, 3, 6])).astype(np.float32)
+        s.MakeTriangle(a, a + (rng.standard_normal(3) * 2).astype(np.float32), a + (rng.standard_normal(3) * 2).astype(np.float32), pick())
+    if rng.random() < 0.5:
+        s.MakeSphere((0, -500.0, 0), 498.0, mats[0])
+    if rng.random() < 0.6:
+        s.set_background(tuple(float(x) for x in rng.random(3)))
+    glass_solids(s, rng)
+    [s.BuildBVH_TopDown, s.BuildBVH_SAH, s.BuildBVH_BottomUp, s.MakeHittableList][int(rng.integers(0, 4))]()
+    W, H = int(rng.integers(17, 49)), int(rng.integers(9, 33))
+    eye = ((rng.random(3) * 2 - 1) * np.array([9, 4, 9])).astype(np.float32)
+    cam = p.PinholeCamera(eye, (0, 0, 0), (0, 1, 0), float(rng.uniform(20, 100)), W / H)
+    return s, cam, W, H, int(rng.integers(1, 9)), int(rng.choice([2, 5, 8, 50]))
+
+
+def interiors_twin_check(p, seed):
+    """interiors_twin_world(seed) on the GPU, in the renderer's own form and the global-memory form, against the twin under the whole rule: the sums of every
+    pixel must be the twin's, and the twin must follow every sample (the world is built so).  (ok, forms, pixels held)"""
+    import _interior_twin as IT
+    import _nee_twin as NT
+    import _path_twin as PT
+    import _smooth_twin as ST
+    s, cam, W, H, spp, depth = interiors_twin_world(p, seed)
+    w, table = s.getWorldPtr(), s.interiors()
+    world = as_oracle_world(w)
+    assert not (IT.world_arrays(world)[0]["mat"] & np.uint32(NT.PRIM_MOVING)).any()   # stated, not caught: the walk restates static spheres
+    vn = s.vertex_normals()
+    trace = ST.smooth_walk(vn) if vn is not None and len(vn) else TT.closest_intersection
+    samples, followed = PT.frame_samples(lambda g, k: IT.radiance(world, as_oracle_camera(cam), W, H, depth, 1984, g, k, PT.own_sky(world), table, None, None,
+                                                                 s.microfacets(), None, trace), W, H, spp)
+    want = IT.in_order_sums(samples)
+    ok, forms = bool(followed.all()), []
+    for env in ({}, {"RT06_FORCE_BIG": "1"}):
+        os.environ.pop("RT06_FORCE_BIG", None)
+        os.environ.update(env)
+        try:
+            r = p.Renderer.MakeRenderer(W, H, spp, depth, cam, w, variant=0)
+        finally:
+            os.environ.pop("RT06_FORCE_BIG", None)
+        ok = ok and r.kernel_interior()
+        forms.append(r.kernel_form())
+        r.refine(spp)
+        ok = ok and bits_equal(r.refine_sums(), want)
+        r.close()
+    return ok, forms, W * H
+
+
 def main(argv=None):
     args = parse_args(argv)
     p = G.load_package()
@@ -421,6 +546,20 @@ def main(argv=None):
                 if not sf[0]:
                     fails += 1
                     print(f"FAIL seed {seed} under inert surface tables: kinds {kinds} triangles {s.n_triangles()} builder {builder} big {big} cam {ck} {W}x{H}x{spp} depth {depth} forms {sf[1]}", flush=True)
+        if args.interiors and ok and info["variant"] in (2, 3) and not big:
+            it = interiors_check(p, seed, args, cam, W, H, spp, depth, variant)
+            if it is not None:
+                stats["interior_worlds"] = stats.get("interior_worlds", 0) + 1
+                if not it[0]:
+                    fails += 1
+                    print(f"FAIL seed {seed} with solid glass: kinds {kinds} triangles {s.n_triangles()} builder {builder} cam {ck} {W}x{H}x{spp} depth {depth} forms {it[1]}", flush=True)
+        if args.interiors:   # a world of its own per seed, which the twin follows throughout
+            tw = interiors_twin_check(p, seed)
+            stats["interior_twin_worlds"] = stats.get("interior_twin_worlds", 0) + 1
+            stats["interior_pixels_held_to_the_twin"] = stats.get("interior_pixels_held_to_the_twin", 0) + tw[2]
+            if not tw[0]:
+                fails += 1
+                print(f"FAIL seed {seed}: the solid-glass twin world: forms {tw[1]}", flush=True)
         if args.env_tree and ok and kinds >= 1 and info["variant"] in (2, 3) and not (big and builder == 3):   # last: it changes the scene's background
             et = env_tree_check(p, s, cam, ck, W, H, depth, variant)
             if et is not None:

@@ -59,7 +59,8 @@ book's earth sphere (image 0), a floor whose `vt` run to 4 — tiled under --tex
 `Pm`, `Pr` and `map_Pr` are applied too: `Pm >= 0.5` makes the group a metal with `Kd` as F0; `Pr` or `map_Pr` gives it a microfacet record — a rough
 conductor on the metal, a coat of specular 0.04 on anything else —, `map_Pr` scaling the roughness by the image's green channel.  A group whose `d` is below 0.5
 (`Tr` above) or whose `illum` is 4, 6, 7 or 9 is glass of index `Ni`, whatever its `Pm`; `Pr` and `map_Pr` frost it.  --rough-glass R frosts the
-prefab `glass` material of --mesh-material.
+prefab `glass` material of --mesh-material.  --solid-glass makes such glass solid where its faces close a volume: rays leave it as well as
+enter it, and --glass-tint R,G,B --glass-tint-at D (or the material's `Tf`) colours it by thickness.
 """
 import argparse, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -96,6 +97,12 @@ ap.add_argument("--texture", default=None, action="append", metavar="FILE.ppm|FI
 ap.add_argument("--mtl", action="store_true", help="with --mesh FILE.obj: one mesh per `usemtl` group, each with the image its material's map_Kd names (mtllib files beside the "
                     "OBJ; DESIGN.md §25) or a Lambertian of its Kd; a group without either takes --mesh-material")
 ap.add_argument("--rough-glass", type=float, default=None, metavar="R", help="with --mesh-material glass: frost the glass, a GGX roughness in [0, 1] (DESIGN.md §30)")
+ap.add_argument("--solid-glass", action="store_true", help="with --mesh: the transparent --mtl groups, or the prefab glass of --mesh-material, are solid glass (DESIGN.md §32): they "
+                    "know inside from outside and tint with thickness.  A group is marked only when its faces close a volume and wind consistently (they are turned outward "
+                    "if they wind inward); otherwise a warning, and the group stays the thin glass it was")
+ap.add_argument("--glass-tint", default=None, metavar="R,G,B", help="with --solid-glass: the colour white light has after --glass-tint-at units of the glass (default: the material's "
+                    "`Tf`, or none)")
+ap.add_argument("--glass-tint-at", type=float, default=1.0, metavar="D", help="the thickness at which the glass shows --glass-tint")
 ap.add_argument("--texture-wrap", choices=["clamp", "repeat"], default="clamp", help="the wrap mode of the images --texture / --mtl bring (DESIGN.md §25)")
 ap.add_argument("--texture-filter", choices=["nearest", "bilinear"], default="nearest", help="their filter")
 ap.add_argument("--env", default=None, metavar="FILE.hdr|FILE.npy|FILE.png|FILE.ppm|sky", help="an equirectangular environment map in the place of the scene's background "
@@ -159,6 +166,19 @@ if a.mesh:
             scene.set_rough_glass(mat, a.rough_glass)
         return mat
 
+    def solid(mat, group_faces, what, tf=None):
+        """--solid-glass: (faces wound outward, whether they were turned) and an interior record on `mat` — or a warning and the faces as they are"""
+        if not a.solid_glass:
+            return group_faces, False
+        try:
+            outward = mesh_io.orient_outward(vertices * a.mesh_scale, group_faces)   # (a negative scale turns the winding)
+        except ValueError as e:
+            print(f"warning: --solid-glass: {what} stays thin glass: {e}", file=sys.stderr, flush=True)
+            return group_faces, False
+        tint = [float(x) for x in a.glass_tint.split(",")] if a.glass_tint else tf
+        scene.set_interior(mat, **(dict(color=[min(max(c, 1e-6), 1.0) for c in tint], at=a.glass_tint_at) if tint else {}))
+        return outward, not mesh_io.closed_outward(vertices * a.mesh_scale, group_faces)
+
     plain = {"white": lambda: scene.Lambertian((0.73, 0.73, 0.73)), "red": lambda: scene.Lambertian((0.65, 0.05, 0.05)), "metal": lambda: scene.Metal((0.8, 0.85, 0.88), 0.0),
              "glass": lambda: frosted(scene.Dielectric((1, 1, 1), 1.5)), "checker": lambda: scene.LambertianTexture((0.2, 0.3, 0.1), (0.9, 0.9, 0.9), abs(a.mesh_scale) / 4 if a.mesh_scale else 1.0),   # four squares across a unit mesh
              "light": lambda: scene.DiffuseLight((4, 4, 4))}[a.mesh_material]
@@ -197,13 +217,20 @@ if a.mesh:
                     if uvs is None:
                         sys.exit(f"--mtl: material {name!r} has a roughness map and {a.mesh} has no complete set of texture coordinates")
                     scene.set_roughness_map(mat, scene.add_image(read_image(roughness_map), a.texture_wrap, a.texture_filter))
-            group_normals = dict(normals=normals, normal_faces=normal_faces[rows] if normal_faces is not None else faces[rows]) if normals is not None else {}
-            group_uvs = dict(uvs=uvs, uv_faces=uv_faces[rows]) if picture or roughness_map else {}
-            added += scene.MakeMesh(vertices, faces[rows], mat, **place, **group_normals, **group_uvs)[1]
+            group_faces, turned = solid(mat, faces[rows], f"material {name!r}", entry.get("transmission_filter")) if is_glass else (faces[rows], False)
+            way = (lambda f: f[:, ::-1]) if turned else (lambda f: f)   # a turned face takes its normals and coordinates in the new order too
+            group_normals = dict(normals=normals, normal_faces=way(normal_faces[rows] if normal_faces is not None else faces[rows])) if normals is not None else {}
+            group_uvs = dict(uvs=uvs, uv_faces=way(uv_faces[rows])) if picture or roughness_map else {}
+            added += scene.MakeMesh(vertices, group_faces, mat, **place, **group_normals, **group_uvs)[1]
             print(json.dumps({"material": name, "triangles": len(rows), "image": picture, "Kd": entry["Kd"], "roughness": roughness, "roughness_map": roughness_map,
                               "metallic": metallic, "glass": is_glass}), flush=True)
     else:
         mat = image_material(a.texture[0]) if a.texture else plain()
+        turned = False
+        if a.mesh_material == "glass" and not a.texture:
+            faces, turned = solid(mat, faces, a.mesh)
+        if turned:
+            normal_faces, uv_faces = (None if f is None else f[:, ::-1] for f in (normal_faces, uv_faces))
         first, added = scene.MakeMesh(vertices, faces, mat, **place, normals=normals, normal_faces=normal_faces, uvs=uvs, uv_faces=uv_faces)
     if a.scene == "three_spheres":
         scene.MakeHittableList()   # the prefab's own world kind
