@@ -7,20 +7,17 @@ facing_radiance(): the FACING alone, through the loop of tests/_path_twin.py une
 material has a record and whose stored normal says back, it returns the facing normal negated; the loop's own `behind = dot(d, n) > 0` then takes the rule's
 decision and turns the normal back (negation is exact).  It serves every world that loop follows: smooth and frosted solids, maps, mode 48.
 
-radiance(): the facing AND the absorption, through a short loop of its own — _path_twin takes a glass hit's factor per material and a transmittance is per hit,
-so the unedited loop cannot carry it.  It follows a miss, a light, Lambertian, metal, smooth glass and rough glass of constant roughness, plain or under
-_path_twin's light rules, and nothing else.  With every sigma 0 it equals facing_radiance() bit for bit (tests/test_interiors_cpu.py).  A later refactor folds it
-into the one loop as an argument.
+radiance(): the facing AND the absorption, as the `interiors` argument of that same loop: per glass hit the facing from the stored normal and the factor
+expf(-(sigma * dist)) on the albedo.  With every sigma 0 it equals facing_radiance() bit for bit (tests/test_interiors_cpu.py).
 """
 import numpy as np
 
 import _env_tree_twin as VT
-import _mfac_twin as MT
 import _path_twin as PT
 import _rglass_twin as RG
 import _tri_twin as TT
-from _nee2_twin import MAT_DIFFUSE_LIGHT, world_arrays
-from _nee_twin import F, INV_PI, PRIM_MOVING, count, dot, near_zero
+from _nee2_twin import world_arrays
+from _nee_twin import F, PRIM_MOVING, dot
 
 INTERIOR_DT = np.dtype([("on", "<u4"), ("sigma", "<f4", 3)])
 OFF, SOLID = 0, 1
@@ -78,8 +75,8 @@ def _materials(world):
 
 def solid_walk(trace, interiors, info=None):
     """`trace` with the rule's facing folded into the normal it returns (see the module's text).  info (a dict): 'turned' counts the hits it negated."""
-    def walk(world, rays, preset=None):
-        hit, t, prim, normal = trace(world, rays) if preset is None else trace(world, rays, preset)
+    def walk(world, rays, preset=None, **draws):
+        hit, t, prim, normal = trace(world, rays, **draws) if preset is None else trace(world, rays, preset, **draws)
         prims, quads, _, mat_of_prim = _materials(world)
         rows = np.nonzero((hit != 0) & (prim >= len(prims)))[0]
         rows = rows[interiors["on"][mat_of_prim[prim[rows]]] != OFF]
@@ -102,157 +99,17 @@ def facing_radiance(world, cam, width, height, max_depth, seed, gids, samples, s
 
 def radiance(world, cam, width, height, max_depth, seed, gids, samples, sky, interiors, light=None, tree=None, mfacs=None, stats=None, trace=TT.closest_intersection,
              smooth_tris=None):
-    """Radiance of sample samples[i] of pixel gids[i] under the whole rule: ((n, 3) float32, followed (n,) bool).  trace: the UNWRAPPED walk (flat, or smooth under
-    a table of vertex normals); light, tree: mode 48's, as _rglass_twin takes them; mfacs: rough-glass records of constant roughness are followed, any other
-    record is not; stats: new_stats()'s counters grow.  smooth_tris: per triangle of the world, whether it has vertex normals, for the smooth_back counter."""
-    gids, samples = np.ascontiguousarray(gids, np.uint32), np.ascontiguousarray(samples, np.uint32)
-    n = len(gids)
-    prims, quads, mats, mat_of_prim = _materials(world)
-    n_prims = len(prims)
-    first_tri = n_prims + int((quads["kind"] == 0).sum())
-    m_type, m_albedo, m_param = mats["type"].astype(np.int64), mats["albedo"].astype(F), mats["param"].astype(F)
+    """Radiance of sample samples[i] of pixel gids[i] under the whole rule: ((n, 3) float32, followed (n,) bool) — _path_twin's loop with the records as its
+    `interiors` argument.  trace: the UNWRAPPED walk (flat, or smooth under a table of vertex normals); light, tree: mode 48's, as _rglass_twin takes them; mfacs:
+    the microfacet and rough-glass records (a mapped one needs a texture table, which this signature does not carry); stats: new_stats()'s counters grow.
+    smooth_tris: per triangle of the world, whether it has vertex normals, for the smooth_back counter."""
     rule = VT.MapRule(world, light, tree) if light is not None else None
-    tape, ray_o, ray_d = PT.primary_rays(cam, width, height, seed, gids, samples)
-    with np.errstate(all="ignore"):
-        atten, accum, out = np.ones((n, 3), F), np.zeros((n, 3), F), np.zeros((n, 3), F)
-        followed = np.ones(n, bool)
-        live = np.arange(n)
-        for bounce in range(max_depth):
-            if len(live) == 0:
-                break
-            k = len(live)
-            rays = np.zeros((k, 7), F)
-            rays[:, 0:3], rays[:, 3:6] = ray_o[live], ray_d[live]
-            hit, t, prim, normal = trace(world, rays)
-            o, d = rays[:, 0:3], rays[:, 3:6]
-            miss = hit == 0
-            out[live[miss]] = atten[live[miss]] * np.asarray(sky(d[miss]), F) + accum[live[miss]]
-            mi = mat_of_prim[np.where(miss, 0, prim)]
-            mt = np.where(miss, -1, m_type[mi])
-            lit = mt == MAT_DIFFUSE_LIGHT
-            accum[live[lit]] = accum[live[lit]] + atten[live[lit]] * m_albedo[mi[lit]]
-            out[live[lit]] = accum[live[lit]]
-            go = np.isin(mt, (0, PT.MAT_METAL))
-            through = mt == PT.MAT_DIELECTRIC
-            rec_mf = mfacs[mi] if mfacs is not None else None
-            if rec_mf is not None:   # a record this loop has no rule for: the sample is left out
-                strange = ~miss & (((rec_mf["on"] != MT.OFF) & ~through) | (through & ~np.isin(rec_mf["on"], (MT.OFF, RG.GLASS))))
-                go, through = go & ~strange, through & ~strange
-            other = ~miss & ~lit & ~through & ~go
-            followed[live[other]] = False
-            out[live[other]] = np.nan
-            if bounce + 1 >= max_depth:
-                out[live[go | through]] = accum[live[go | through]]
-                break
-            carried = []
-            gl = np.nonzero(through)[0]
-            if len(gl):
-                rg, dg, ng, tg, pm = live[gl], d[gl], normal[gl], t[gl], prim[gl]
-                pg = o[gl] + dg * tg[:, None]
-                rec = interiors[mi[gl]]
-                solid, flat = rec["on"] != OFF, pm >= n_prims
-                stored = quads["normal"][np.where(flat, pm - n_prims, 0)].astype(F) if len(quads) else np.zeros((len(gl), 3), F)
-                kept = solid & flat                                          # 1: the facing from the stored normal; the shading normal stays
-                back = np.where(kept, dot(dg, stored) > F(0), dot(dg, ng) > F(0))
-                ng = np.where((back & ~kept)[:, None], -ng, ng)
-                ior = m_param[mi[gl]]
-                ratio, T = interior_hit(back, dg, tg, ior, rec["sigma"])
-                charged = solid & back                                       # 2
-                albedo_g = np.where(charged[:, None], m_albedo[mi[gl]] * T, m_albedo[mi[gl]]).astype(F)
-                smooth = np.ones(len(gl), bool)
-                frosted = np.zeros(len(gl), bool)
-                total_rough = np.zeros(len(gl), bool)
-                if mfacs is not None:
-                    has = np.nonzero(mfacs["on"][mi[gl]] == RG.GLASS)[0]
-                    if len(has):
-                        frosted[has] = True
-                        det = {}
-                        new_w, g1, way = RG.faced(ng[has], ratio[has], dg[has], mfacs["roughness"][mi[gl[has]]].astype(F), tape, rg[has], det)
-                        goes, gone = (way == RG.SPECULAR) | (way == RG.TRANSMITTED), way == RG.ABSORBED
-                        smooth[has] = ~(goes | gone)
-                        total_rough[has] = det["total"]
-                        out[rg[has][gone]] = accum[rg[has][gone]]
-                        carried.append((rg[has][goes], new_w[goes], pg[has][goes], (albedo_g[has] * g1[:, None]).astype(F)[goes]))
-                unit = MT.normalize(dg)
-                cos_t = np.minimum(dot(-unit, ng), F(1))
-                sin_t = np.sqrt(F(1) - cos_t * cos_t)
-                r0 = (F(1) - ratio) / (F(1) + ratio)
-                r0 = r0 * r0
-                x1 = F(1) - cos_t
-                x2 = x1 * x1
-                prob = r0 + (F(1) - r0) * ((x2 * x2) * x1)
-                must = ratio * sin_t > F(1)
-                reflects = must.copy()
-                free = np.nonzero(~must & smooth)[0]
-                if len(free):
-                    reflects[free] = prob[free] > tape.next(rg[free])
-                refl = unit - (ng * dot(ng, unit)[:, None]) * F(2)
-                dv = dot(ng, unit)
-                kk = F(1) - (ratio * ratio) * (F(1) - dv * dv)
-                refr = np.where((kk >= F(0))[:, None], unit * ratio[:, None] - ng * (ratio * dv + np.sqrt(kk))[:, None], F(0)).astype(F)
-                carried.append((rg[smooth], np.where(reflects[:, None], refl, refr).astype(F)[smooth], pg[smooth], albedo_g[smooth]))
-                if stats is not None:
-                    tri, quad, sph = solid & flat & (pm >= first_tri), solid & flat & (pm < first_tri), solid & ~flat
-                    for name, sel in (("tri", tri), ("quad", quad), ("sphere", sph)):
-                        stats[name + "_front"] += int((sel & ~back).sum())
-                        stats[name + "_back"] += int((sel & back).sum())
-                    if smooth_tris is not None and len(smooth_tris):
-                        stats["smooth_back"] += int((tri & back & smooth_tris[np.clip(pm - first_tri, 0, len(smooth_tris) - 1)]).sum())
-                    stats["total_inside"] += int((solid & back & ((must & smooth) | total_rough)).sum())
-                    stats["charged"] += int(charged.sum())
-                    stats["frosted_front"] += int((solid & frosted & ~back).sum())
-                    stats["frosted_back"] += int((solid & frosted & back).sum())
-                    stats["unrecorded_mesh"] += int((~solid & flat & (pm >= first_tri)).sum())
-            sel = np.nonzero(go)[0]
-            r = live[sel]
-            o, d, t, normal, mi, mt = o[sel], d[sel], t[sel], normal[sel], mi[sel], mt[sel]
-            hit_p = o + d * t[:, None]
-            k = len(r)
-            lamb = mt != PT.MAT_METAL
-            ok = np.ones(k, bool)
-            new_d = np.zeros((k, 3), F)
-            weight, weighted = np.ones(k, F), np.zeros(k, bool)
-            to_light = np.zeros(k, bool)
-            if rule is not None:
-                sampled = lamb.copy()
-                to_light, _, picked = rule.pick(tape, r, sampled, mt, hit_p, new_d, None)
-            s = np.nonzero(~to_light)[0]
-            if len(s):
-                on_unit = tape.on_unit3(r[s])
-                sl, sm = s[lamb[s]], s[~lamb[s]]
-                new_d[sl] = normal[sl] + on_unit[lamb[s]]
-                ok[sl] = ~near_zero(new_d[sl])
-                dn = dot(normal[sm], d[sm])
-                refl = d[sm] - (normal[sm] * dn[:, None]) * F(2)
-                new_d[sm] = refl + on_unit[~lamb[s]] * m_param[mi[sm]][:, None]
-                ok[sm] = ~((dot(new_d[sm], normal[sm]) < F(0)) | near_zero(new_d[sm]))
-            albedo = m_albedo[mi].copy()
-            if rule is not None:
-                s = np.nonzero(sampled & ok)[0]
-                if len(s):
-                    dd, nn = new_d[s], normal[s]
-                    len2 = dot(dd, dd)
-                    ln = np.sqrt(len2)
-                    cosn = dot(nn, dd) / ln
-                    pdf_cos = np.where(cosn > F(0), cosn * INV_PI, F(0)).astype(F)
-                    pdf_light, own_lost = rule.density(picked, s, hit_p[s], dd, len2, ln, pdf_cos, None)
-                    pdf = F(0.5) * pdf_cos + F(0.5) * pdf_light
-                    good = ~(pdf_cos == F(0)) & (pdf > F(0)) & ~own_lost
-                    ok[s[~good]] = False
-                    weight[s[good]] = pdf_cos[good] / pdf[good]
-                    weighted[s[good]] = True
-                albedo = np.where(weighted[:, None], albedo * weight[:, None], albedo)
-            out[r[~ok]] = accum[r[~ok]]
-            carried.append((r[ok], new_d[ok], hit_p[ok], albedo[ok]))
-            r = np.concatenate([c[0] for c in carried])
-            new_d, hit_p, albedo = (np.concatenate([c[i] for c in carried]).astype(F) for i in (1, 2, 3))
-            atten[r] = atten[r] * albedo
-            ray_d[r] = new_d
-            ray_o[r] = hit_p + new_d * F(0.001)
-            live = np.sort(r)
+    run = None if stats is None else PT.counters(dict(stats), VT.new_stats())   # the light rule counts into its own names; the caller's dict keeps this module's
+    out = PT.radiance(world, cam, width, height, max_depth, seed, gids, samples, trace, sky=sky, rule=rule, mfacs=mfacs, glass=True, stats=run,
+                      interiors=interiors, smooth_tris=smooth_tris)
     if stats is not None:
-        count(stats, "not_followed", int((~followed).sum()))
-    return out, followed
+        stats.update({key: run[key] for key in stats})
+    return out
 
 
 in_order_sums, resolve = VT.in_order_sums, VT.resolve

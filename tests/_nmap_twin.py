@@ -105,7 +105,7 @@ def apply64(m, dpdu, dpdv, normal):
 
 
 # ---- whole samples: the walk every whole-sample twin calls, with the rule behind it --------------------------------------------------------------------------
-def mapped_walk(world, vn, uv, nmaps, table, rays, preset=None, info=None):
+def mapped_walk(world, vn, uv, nmaps, table, rays, preset=None, info=None, **draws):
     """_tri_twin.closest_intersection — behind _smooth_twin's rule when vn, a table of vertex normals, is given — then the normal-map rule on every hit whose
     material's record of nmaps (capi.NORMAL_MAP_DT, one per material) says on: (u, v) by _tex_twin.hit_uv from the normal the walk found, the tangents by the
     kind of surface (a triangle takes its coordinates' whenever the world has a table of them, as the kernels do), the entry of `table` = [(image, wrap,
@@ -115,9 +115,9 @@ def mapped_walk(world, vn, uv, nmaps, table, rays, preset=None, info=None):
     if info is not None:
         info["uv"] = None
     if vn is not None and len(vn):
-        hit, t, prim, normal = ST.closest_intersection_smooth(world, vn, rays, preset)
+        hit, t, prim, normal = ST.closest_intersection_smooth(world, vn, rays, preset, **draws)   # draws: the tape and its rows, for a constant medium (_tri_twin)
     else:
-        hit, t, prim, normal = ST._flat_walk(world, rays, preset)
+        hit, t, prim, normal = ST._flat_walk(world, rays, preset, **draws)
     prims, quads, mats = world_arrays(world)
     first_tri = len(prims) + int((quads["kind"] == 0).sum())
     mat_of_prim = np.concatenate([(prims["mat"] & ~np.uint32(PRIM_MOVING)), quads["mat"]]).astype(np.int64)
@@ -158,7 +158,7 @@ def walk_of(vn, uv, nmaps, table, info=None):
     normal-map table (nmaps None = none), the smooth walk under a table of vertex normals, _tri_twin's flat walk otherwise"""
     if nmaps is not None:
         info = {} if info is None else info
-        return (lambda w, rays, preset=None: mapped_walk(w, vn, uv, nmaps, table, rays, preset, info)), info
+        return (lambda w, rays, preset=None, **draws: mapped_walk(w, vn, uv, nmaps, table, rays, preset, info, **draws)), info
     if vn is not None and len(vn):
         return ST.smooth_walk(vn), None
     return TT.closest_intersection, None

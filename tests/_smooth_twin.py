@@ -52,12 +52,12 @@ def shading_normal(tris, vn, o, d, t):
         return np.where(took[:, None], s, f).astype(F), took, fallback
 
 
-def closest_intersection_smooth(world, vn, rays, preset=None, info=None):
+def closest_intersection_smooth(world, vn, rays, preset=None, info=None, **draws):
     """_tri_twin.closest_intersection, then the rule on the hits whose primitive is a triangle; vn: one record per triangle of the flat world.
     info (a dict): gets added up 'smooth' (hits on triangles with a non-zero record), 'interpolated' and 'fallback2' (of those), and 'fallback1' — every
     triangle hit that `!(l2 > 0)` sends back to the flat normal: all-zero records are the rule's own first case of it, and between three unit normals of one
     record g vanishes only on a set of measure zero, which no rendered frame meets."""
-    hit, t, prim, normal = _flat_walk(world, rays, preset)
+    hit, t, prim, normal = _flat_walk(world, rays, preset, **draws)   # draws: the tape and its rows, for a world with a constant medium (_tri_twin)
     vn = table(vn)
     prims, quads, _ = world_arrays(world)
     first_tri = len(prims) + int((quads["kind"] == 0).sum())
@@ -78,7 +78,7 @@ def closest_intersection_smooth(world, vn, rays, preset=None, info=None):
 
 def smooth_walk(vn, info=None):
     """closest_intersection_smooth under the table vn as a walk (world, rays[, preset]) -> (hit, t, prim, normal), the way the whole-sample twins take one"""
-    return lambda world, rays, preset=None: closest_intersection_smooth(world, vn, rays, preset, info)
+    return lambda world, rays, preset=None, **draws: closest_intersection_smooth(world, vn, rays, preset, info, **draws)
 
 
 def radiance(world, vn, cam, width, height, max_depth, seed, gids, samples, mode=0, info=None):

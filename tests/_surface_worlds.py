@@ -198,11 +198,14 @@ BUILDERS = ("BuildBVH_SAH", "BuildBVH_TopDown", "MakeHittableList")
 STRENGTHS, ROUGHNESSES, SPECULARS = (0.0, 0.5, 1.0, 2.0), (0.0, 0.01, None, 1.0), (0.0, 0.04, 1.0)   # None: a random roughness
 
 
-def random_surface_world(p, seed):
+def random_surface_world(p, seed, live=False):
     """One world of the randomised surface test: at most 24 primitives — spheres, parallelograms, free triangles with or without vertex normals and
     coordinates (mirrored ones included) — plus at most one uv_sphere(8, 4) mesh, materials of the kinds the twin follows (Lambertian, checker, image, metal,
     glass, light), a texture table of 2 to 5 random images under random modes, random records of all three kinds, a random builder, a constant background or
-    the sky map.  Returns (scene, table, camera, recipe); frames are RW x RH at RSPP spp and depth RDEPTH."""
+    the sky map.  live: the same world — the seed's generator is left as it is — plus, from a generator of its own, a noise material under random
+    records on a sphere and a parallelogram, moving spheres of the recorded materials, spheres of constant medium (one about the glass ball), a solid glass box
+    with an interior record, and a camera of a random kind: the twin with `media` follows it.  Returns (scene, table, camera, recipe); frames are RW x RH at
+    RSPP spp and depth RDEPTH."""
     rng = np.random.default_rng(SEED_BASE + seed)
     s = p.Scene()
     table = []
@@ -247,6 +250,7 @@ def random_surface_world(p, seed):
     n_spheres, n_quads, n_tris = int(rng.integers(4, 11)), int(rng.integers(2, 6)), int(rng.integers(2, 9))
     for k in range(n_spheres):   # the first a ball of glass, large enough that rays cross it
         c = ((rng.random(3) * 2 - 1) * np.array([4, 1.5, 4])).astype(F)
+        ball = c if k == 0 else ball
         s.MakeSphere(c, float(rng.choice([0.3, 0.8, 1.4][int(k == 0):])), glass[int(rng.integers(0, 2))] if k == 0 else any_mat())
     s.MakeQuad((-8, -2.2, -8), (16, 0, 0), (0, 0, 16), surface[int(rng.integers(0, len(surface)))])   # a floor, so that paths go on
     s.MakeQuad((-1.5, 5.0, -1.5), (3, 0, 0), (0, 0, 3), s.DiffuseLight((8, 8, 8)))
@@ -278,6 +282,32 @@ def random_surface_world(p, seed):
         c = ((rng.random(3) * 2 - 1) * np.array([3, 1, 3])).astype(F)
         s.MakeMesh(v, f, surface[int(rng.integers(0, len(surface)))], float(rng.uniform(0.8, 1.6)), float(rng.uniform(-180, 180)), c, normals=n,
                    uvs=uv * F(rng.uniform(0.5, 2.0)) - F(rng.uniform(0.0, 0.5)))
+    extra = None
+    if live:
+        lr = np.random.default_rng(SEED_BASE + seed + (33 << 20))
+        s.set_perlin(int(lr.integers(0, 1 << 30)))
+        noise = s.NoiseTexture(float(lr.choice([0.5, 2.0, 4.0])), lr.random(3))
+        if lr.random() < 0.7:
+            s.set_normal_map(noise, int(lr.integers(0, n_img)), float(lr.choice(STRENGTHS)))
+        if lr.random() < 0.7:
+            s.set_microfacet(noise, float(lr.random()), float(lr.choice(SPECULARS)))
+            if lr.random() < 0.5:
+                s.set_roughness_map(noise, int(lr.integers(0, n_img)))
+        place = lambda: ((lr.random(3) * 2 - 1) * np.array([4, 1.5, 4])).astype(F)   # noqa: E731
+        s.MakeSphere(place(), float(lr.choice([0.5, 1.0])), noise)
+        s.MakeQuad(place(), (lr.standard_normal(3) * 1.5).astype(F), (lr.standard_normal(3) * 1.5).astype(F), noise)
+        n_moving = int(lr.integers(1, 4))
+        for _ in range(n_moving):
+            c = place()
+            s.MakeMovingSphere(c, c + (lr.random(3).astype(F) - F(0.5)), float(lr.choice([0.4, 0.9])), surface[int(lr.integers(0, len(surface)))])
+        n_media = int(lr.integers(1, 4))
+        for k in range(n_media):   # the first about the glass ball of the world, the others anywhere: thin haze or a dense ball
+            c = ball if k == 0 else place()
+            s.MakeSphere(c, float(lr.choice([0.6, 1.2, 3.0])), s.Isotropic(lr.random(3), float(lr.choice([0.05, 0.5, 2.0]))))
+        lo = place()
+        s.MakeBox(lo, lo + lr.uniform(0.5, 2.0, 3), glass[0], rotate_y=float(lr.uniform(0, 90)))
+        s.set_interior(glass[0], sigma=lr.choice([0.0, 0.1, 1.0], 3) * lr.random(3))
+        extra = {"moving": n_moving, "media": n_media, "camera": TW.CAMERAS[int(lr.integers(0, 3))]}
     env = bool(rng.random() < 0.5)
     if env:
         s.set_environment(EW.sky_map(), rotate_y=EW.SKY_U0_DEGREES)
@@ -289,8 +319,14 @@ def random_surface_world(p, seed):
     eye = np.array([9 * np.cos(angle), rng.uniform(0.5, 4.0), 9 * np.sin(angle)], F)
     fov = float(rng.uniform(45, 75))
     cam = p.PinholeCamera(eye, (0, 0, 0), (0, 1, 0), fov, RW / RH)
+    if extra is not None and extra["camera"] == "defocus":
+        cam = p.DefocusBlurCamera(eye, (0, 0, 0), (0, 1, 0), fov, RW / RH, float(lr.uniform(0.05, 0.5)), float(lr.uniform(4, 12)))
+    elif extra is not None and extra["camera"] == "motion":
+        cam = p.MotionBlurCamera(eye, (0, 0, 0), (0, 1, 0), fov, RW / RH, 0.0, 1.0)
     recipe = {"seed": seed, "images": [(t[0].shape[1], t[0].shape[0], t[1], t[2]) for t in table], "records": records, "spheres": n_spheres, "quads": n_quads,
               "triangles": shapes, "mesh": mesh, "env": env, "builder": builder, "eye": eye.tolist(), "fov": fov, "frame": (RW, RH, RSPP, RDEPTH)}
+    if extra is not None:
+        recipe["live"] = extra
     return s, table, cam, recipe
 
 

@@ -12,7 +12,8 @@ It is pinned before anything is compared with it (tests/test_triangles_cpu.py): 
 hit, t, primitive and normal on every ray, and radiance() equals orc_radiance_batch (mode 0) and _nee2_twin (modes 1, 2), bit for bit.  After the pins the
 only thing the twin adds is the interior rule.
 
-Scope: _nee_twin's (pinhole cameras; Lambertian, checker, metal and diffuse-light materials) and static spheres; stack traversal.
+Scope: stack traversal; spheres static or moving (the centre at the ray's time); a sphere of RT_MAT_ISOTROPIC as a constant medium when the caller hands the walk
+the tape, as a plain sphere otherwise.  radiance() here follows _nee_twin's materials under the pinhole camera.
 """
 import ctypes as C
 
@@ -24,6 +25,17 @@ import _oracle as O
 import _path_twin as PT
 from _nee2_twin import world_arrays
 from _nee_twin import F, MISS, PRIM_MOVING, cross, dot
+
+
+MAT_ISOTROPIC = 5
+
+
+def _log(x):
+    """the project's deterministic log (orc_math_batch fn 0 = rt_logf)"""
+    x = np.ascontiguousarray(x, F)
+    out = np.zeros(len(x), F)
+    O.lib().orc_math_batch(0, len(x), x, x, out)
+    return out
 
 
 def kinds(quads):
@@ -49,21 +61,61 @@ def _boxes_hit(mn, mx, o, d, maxd):
     return hit != 0, np.where(hit != 0, dist, MISS).astype(F)
 
 
-def _leaf(prims, quads, idx, o, d, rec_t, rec_prim, rec_n, rows):
-    """any_prim_closest_intersection of primitive idx[i] on ray rows[i], against the caller's rec.distance; updates the records in place"""
+def _leaf(prims, quads, idx, o, d, rec_t, rec_prim, rec_n, rows, time=None, media=None):
+    """any_prim_closest_intersection of primitive idx[i] on ray rows[i], against the caller's rec.distance; updates the records in place.  time: the rays' times, for
+    a moving sphere's centre; media = (material types, material params, tape, the tape's row of every ray, info): a sphere of RT_MAT_ISOTROPIC is then the constant
+    medium of prim_closest_intersection (rt_oracle.c:295-322), which draws its uniform from the tape; None: a sphere of any material is a sphere"""
     n_prims = len(prims)
     with np.errstate(all="ignore"):
         sp = idx < n_prims
         if sp.any():
-            r, pr = rows[sp], prims[idx[sp]]
+            r, pr, pi = rows[sp], prims[idx[sp]], idx[sp]
             c, rad = pr["c0"].astype(F), pr["radius"].astype(F)
-            rays = np.ascontiguousarray(np.concatenate([o[r], d[r]], axis=1), F)
-            t = np.zeros(len(r), F)
-            O.lib().orc_sphere_batch(len(r), rays, np.ascontiguousarray(np.concatenate([c, rad[:, None]], axis=1), F), t)
-            ok = ~(t >= rec_t[r])
-            r, t, c, rad = r[ok], t[ok], c[ok], rad[ok]
-            rec_t[r], rec_prim[r] = t, idx[sp][ok]
-            rec_n[r] = ((o[r] + d[r] * t[:, None]) - c) / rad[:, None]
+            mov = (pr["mat"] & np.uint32(PRIM_MOVING)) != 0
+            if mov.any():   # glm::mix(c0, c1, time) = c0 * (1 - time) + c1 * time
+                tm = time[r[mov]][:, None]
+                c[mov] = pr["c0"][mov].astype(F) * (F(1) - tm) + pr["c1"][mov].astype(F) * tm
+            med = np.zeros(len(r), bool)
+            if media is not None:
+                m_type, m_param, tape, tape_rows, info = media
+                mat = (pr["mat"] & ~np.uint32(PRIM_MOVING)).astype(np.int64)
+                med = m_type[mat] == MAT_ISOTROPIC
+            if med.any():
+                rm, cm, radm = r[med], c[med], rad[med]
+                oc = o[rm] - cm
+                a = dot(d[rm], d[rm])
+                hb = dot(d[rm], oc)
+                cc = dot(oc, oc) - radm * radm
+                disc = hb * hb - a * cc
+                sq = np.sqrt(disc)
+                t1, t2 = (-hb - sq) / a, (-hb + sq) / a
+                t_in = np.where(t1 < F(0), F(0), t1).astype(F)
+                t_out = np.where(t2 > rec_t[rm], rec_t[rm], t2).astype(F)
+                draws = np.nonzero(~(disc <= F(0)) & (t_in < t_out))[0]   # a non-empty interval inside the boundary: ONE uniform, whatever becomes of the test
+                if len(draws):
+                    rd = rm[draws]
+                    u = tape.next(tape_rows[rd])
+                    ray_length = np.sqrt(a[draws])
+                    inside = (t_out[draws] - t_in[draws]) * ray_length
+                    hit_distance = (F(-1) / m_param[mat[med][draws]]) * _log(u)
+                    tmed = t_in[draws] + hit_distance / ray_length
+                    ok = ~(hit_distance > inside) & ~(tmed >= rec_t[rd])
+                    rec_t[rd[ok]], rec_prim[rd[ok]] = tmed[ok], pi[med][draws][ok]
+                    rec_n[rd[ok]] = np.array([1, 0, 0], F)
+                    if info is not None:
+                        info["medium_draws"] = info.get("medium_draws", 0) + len(rd)
+                        info["medium_hits"] = info.get("medium_hits", 0) + int(ok.sum())
+                        if "after_medium" in info:   # a test's hook: (tape, the tape's rows that drew, which of the tests accepted)
+                            info["after_medium"](tape, tape_rows[rd], ok)
+                r, pi, c, rad = r[~med], pi[~med], c[~med], rad[~med]
+            if len(r):
+                rays = np.ascontiguousarray(np.concatenate([o[r], d[r]], axis=1), F)
+                t = np.zeros(len(r), F)
+                O.lib().orc_sphere_batch(len(r), rays, np.ascontiguousarray(np.concatenate([c, rad[:, None]], axis=1), F), t)
+                ok = ~(t >= rec_t[r])
+                r, t, c, rad = r[ok], t[ok], c[ok], rad[ok]
+                rec_t[r], rec_prim[r] = t, pi[ok]
+                rec_n[r] = ((o[r] + d[r] * t[:, None]) - c) / rad[:, None]
         qd = ~sp
         if qd.any():
             r, q, ui = rows[qd], quads[idx[qd] - n_prims], idx[qd]
@@ -82,21 +134,28 @@ def _leaf(prims, quads, idx, o, d, rec_t, rec_prim, rec_n, rows):
             rec_n[r] = np.where((dot(dd, nrm) > F(0))[:, None], -nrm, nrm)
 
 
-def closest_intersection(world, rays, preset=None):
+def closest_intersection(world, rays, preset=None, tape=None, rows=None, medium_info=None):
     """Hittable::ClosestIntersection of the flat world on rays (n, 7): (hit int32, t, prim int32, normal), laid out as orc_trace_batch lays them out
-    (a miss: t = the rec.distance it started with, prim = -1, normal = 0).  preset: rec.distance before the walk (default: a fresh record's MISS)."""
-    prims, quads, _ = world_arrays(world)
-    assert not (prims["mat"] & np.uint32(PRIM_MOVING)).any() and world.traversal == 0, "static spheres, stack traversal"
+    (a miss: t = the rec.distance it started with, prim = -1, normal = 0).  preset: rec.distance before the walk (default: a fresh record's MISS).  A moving
+    sphere stands where rays[:, 6], the ray's time, puts it.  tape, rows: the tape of the samples' uniforms and the row of it that serves each ray — given
+    them, a sphere of RT_MAT_ISOTROPIC is a constant medium and draws from its ray's row, in traversal order; a world without a medium never touches the tape.
+    Without them such a sphere is a sphere, as it was before the twin knew media.  medium_info (a dict): 'medium_draws' and 'medium_hits' grow."""
+    prims, quads, mats = world_arrays(world)
+    assert world.traversal == 0, "stack traversal"
     n = len(rays)
+    time = np.ascontiguousarray(rays[:, 6], F)
+    media = None
+    if tape is not None and (mats["type"] == MAT_ISOTROPIC).any():
+        media = (mats["type"].astype(np.int64), mats["param"].astype(F), tape, np.asarray(rows, np.int64), medium_info)
     o, d = np.ascontiguousarray(rays[:, 0:3], F), np.ascontiguousarray(rays[:, 3:6], F)
     rec_t = np.full(n, MISS, F) if preset is None else np.array(preset, F)
     rec_prim, rec_n = np.full(n, -1, np.int64), np.zeros((n, 3), F)
     if world.kind == 1:   # HittableList.cuh:21-34
         bmn, bmx = np.array(list(world.bounds_min), F), np.array(list(world.bounds_max), F)
         inside, _ = _boxes_hit(np.broadcast_to(bmn, (n, 3)), np.broadcast_to(bmx, (n, 3)), o, d, rec_t)
-        rows = np.nonzero(inside)[0]
+        idx = np.nonzero(inside)[0]
         for i in range(world.n_prims + world.n_quads):
-            _leaf(prims, quads, np.full(len(rows), i, np.int64), o, d, rec_t, rec_prim, rec_n, rows)
+            _leaf(prims, quads, np.full(len(idx), i, np.int64), o, d, rec_t, rec_prim, rec_n, idx, time, media)
     else:
         assert world.kind == 0
         nodes = np.frombuffer((C.c_char * (world.n_nodes * O.NODE_DT.itemsize)).from_address(world.nodes), O.NODE_DT)
@@ -105,15 +164,15 @@ def closest_intersection(world, rays, preset=None):
         inside, _ = _boxes_hit(np.broadcast_to(root["min"], (n, 3)), np.broadcast_to(root["max"], (n, 3)), o, d, rec_t)
         stack[inside, 0], head[inside] = world.root, 1
         while True:
-            rows = np.nonzero(head > 0)[0]
-            if len(rows) == 0:
+            live = np.nonzero(head > 0)[0]
+            if len(live) == 0:
                 break
-            head[rows] -= 1
-            node = nodes[stack[rows, head[rows]]]
+            head[live] -= 1
+            node = nodes[stack[live, head[live]]]
             leaf = node["left"] == -1
             if leaf.any():
-                _leaf(prims, quads, node["right"][leaf].astype(np.int64), o, d, rec_t, rec_prim, rec_n, rows[leaf])
-            r = rows[~leaf]
+                _leaf(prims, quads, node["right"][leaf].astype(np.int64), o, d, rec_t, rec_prim, rec_n, live[leaf], time, media)
+            r = live[~leaf]
             if len(r):
                 li, ri = node["left"][~leaf].astype(np.int64), node["right"][~leaf].astype(np.int64)
                 _, ld = _boxes_hit(nodes["min"][li], nodes["max"][li], o[r], d[r], rec_t[r])
@@ -129,8 +188,6 @@ def closest_intersection(world, rays, preset=None):
                 head[r[pn]] += 1
     hit = rec_prim >= 0
     return hit.astype(np.int32), rec_t, rec_prim.astype(np.int32), rec_n
-
-
 
 
 def radiance(world, cam, width, height, max_depth, seed, gids, samples, mode=0, stats=None):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Differential fuzz campaign: random worlds (spheres, moving spheres, quads, triangles and meshes, lights, media, textures; every builder; LDS
 and global-memory paths; three cameras) rendered on the GPU and by the CPU oracle, compared bit for bit.
-    python tools/fuzz_campaign.py --seeds 200 [--first 0] [--no-triangles] [--mesh-lights] [--light-tree] [--texture-coords] [--textures] [--env-tree] [--surfaces] [--interiors]
+    python tools/fuzz_campaign.py --seeds 200 [--first 0] [--no-triangles] [--mesh-lights] [--light-tree] [--texture-coords] [--textures] [--env-tree] [--surfaces [--live]] [--interiors]
 Prints one line per failure and a summary; exit code 1 if anything differed.  The triangles of a world come from a generator of their own, so the rest of a seed's
 world is what it was before the fuzzer made triangles, and --no-triangles renders exactly those earlier worlds.  Importing this file starts nothing:
 world_of_seed() builds a seed's world on the host, without a device.  --mesh-lights (off by default: the recorded campaigns ran without it) also renders every
@@ -47,6 +47,7 @@ def parse_args(argv=None):
     ap.add_argument("--textures", action="store_true", help="also render the worlds with an image under a texture table of several random images and random modes: the world's image under clamp / nearest must be the oracle's frame, and under another mode pair both memory forms must agree")
     ap.add_argument("--texture-coords", action="store_true", help="also render the worlds with an image and triangles under a table of random texture coordinates on random triangles: both memory forms must agree, and the identity table must be the oracle's frame")
     ap.add_argument("--surfaces", action="store_true", help="also render every world under inert normal-map and microfacet tables (flat maps; records that are all off on the materials in use): the NMAP and the MFAC kernel family, both memory forms, must give the oracle's frame; worlds the families refuse (a lane walk, a kernel variant other than 2 and 3) are counted as skipped")
+    ap.add_argument("--live", action="store_true", help="with --surfaces: also render, per seed, a world of tests/_surface_worlds.random_surface_world(seed, live=True) — live normal-map, microfacet, rough-glass and interior records beside a constant medium, a noise material and moving spheres under a random camera kind — in both memory forms against the extended whole-sample twin, which must follow every sample; lane walks and kernel variants other than 2 and 3 are counted as skipped")
     ap.add_argument("--interiors", action="store_true", help="also render every stack-walked or list world with random glass solids under random interior records: the INTR kernel family in both memory forms, every record off "
                     "against no table, and the twin (tests/_interior_twin.py) where it follows")
     return ap.parse_args(argv)
@@ -307,6 +308,31 @@ def surfaces_check(p, seed, args, cam, W, H, spp, depth, variant, ref):
     return ok, forms
 
 
+def live_check(p, seed, variant):
+    """tests/_live_worlds.random_live_sums(seed) on the GPU, in the renderer's own form and the global-memory form, against the extended twin: the
+    sums of every pixel must be the twin's, and the twin must follow every sample.  None: a variant without the families; else (ok, forms, not followed)."""
+    import _live_worlds as LW
+    s, cam, (W, H, spp, depth), want, followed, recipe = LW.random_live_sums(p, seed)
+    ok, forms = bool(followed.all()), []
+    for env in ({}, {"RT06_FORCE_BIG": "1"}):
+        os.environ.pop("RT06_FORCE_BIG", None)
+        os.environ.update(env)
+        try:
+            r = p.Renderer.MakeRenderer(W, H, spp, depth, cam, s.getWorldPtr(), seed=LW.SEED, variant=variant)
+        except p.capi.RtError:
+            return None
+        finally:
+            os.environ.pop("RT06_FORCE_BIG", None)
+        if r.kernel_info()["variant"] not in (2, 3) or not r.kernel_interior():
+            r.close()
+            return None
+        forms.append(r.kernel_form())
+        r.refine(spp)
+        ok = bits_equal(r.refine_sums(), want) and ok
+        r.close()
+    return ok, forms, int((~followed).sum())
+
+
 def glass_solids(s, rng):
     """a glass sphere, a glass box and a closed glass mesh (half the time with vertex normals) into scene s, with random interior records — at least one — and
     now and then a frosted one, all drawn from rng"""
@@ -546,6 +572,17 @@ def main(argv=None):
                 if not sf[0]:
                     fails += 1
                     print(f"FAIL seed {seed} under inert surface tables: kinds {kinds} triangles {s.n_triangles()} builder {builder} big {big} cam {ck} {W}x{H}x{spp} depth {depth} forms {sf[1]}", flush=True)
+        if args.surfaces and args.live:   # a world of its own per seed, which the extended twin follows throughout
+            lv = live_check(p, seed, variant) if w.traversal == 0 and info["variant"] in (2, 3) else None
+            if lv is None:
+                stats["live_skipped"] = stats.get("live_skipped", 0) + 1
+            else:
+                stats["live_worlds"] = stats.get("live_worlds", 0) + 1
+                stats["live_kernels"] = stats.get("live_kernels", 0) + len(lv[1])
+                stats["live_not_followed"] = stats.get("live_not_followed", 0) + lv[2]
+                if not lv[0]:
+                    fails += 1
+                    print(f"FAIL seed {seed}: the live surface world: forms {lv[1]}, {lv[2]} samples not followed", flush=True)
         if args.interiors and ok and info["variant"] in (2, 3) and not big:
             it = interiors_check(p, seed, args, cam, W, H, spp, depth, variant)
             if it is not None:
