@@ -497,6 +497,34 @@ int rt_interior_batch(size_t count, const float* Ng, const float* n, const float
                       uint32_t* out_back, float* out_eta, float* out_T);
 /* HOST: out[i] = rt_expf of x[i]                                                                                                                                  */
 int rt_expf_batch(size_t count, const float* x, float* out);
+/* ---- alpha cutouts (not in the reference): an image mask decides where a parallelogram or triangle is there — leaves, fences, grilles, decals.
+ * One record per material beside the flat world, as the interior records are; rt_material and rt_world_flat keep their sizes.  image = an entry of the scene's
+ * texture table, cutoff in [0, 1].  The rule (cutout_keeps), in the leaf phase, for a candidate hit at parameter t of the ray (o, d) that has passed the
+ * surface's own test against the closest hit so far, on a material whose record is on:
+ *   1  hit_p = o + d t
+ *   2  (u, v) = tri_uv of the triangle's rt_tri_uvs record while the renderer has texture coordinates, the planar coordinates (quad_uv) otherwise and on a
+ *      parallelogram: the functions the shade phase uses for the same surface
+ *   3  c = texture_value(entry[image], u, v), the texture table's rule with the entry's own wrap and filter
+ *   4  the hit is kept iff !(c.green < cutoff): a NaN keeps it.  A candidate turned down leaves the closest hit as it was, and the ray goes on to what lies behind.
+ * The shade phase recomputes hit_p, (u, v) and the texel from the same t with the same functions, so a mask made from the alpha of the material's own map_Kd
+ * agrees with its colour texel for texel.  Deterministic: nothing is drawn, and the order in which a sample consumes its random numbers is untouched.  Known
+ * limits: spheres ignore the record (a sphere test yields one root, and looking through a hole at the sphere's own back needs the second); no stochastic
+ * opacity; the feature pass does not know the rule (rt_renderer_aov_enable refuses a renderer with a table).                                                */
+typedef struct rt_cutout { uint32_t on; uint32_t image; float cutoff; uint32_t reserved; } rt_cutout;   /* 16 B, one per material */
+enum { RT_CUTOUT_OFF = 0, RT_CUTOUT_MASKED = 1 };
+/* Gives `material` a cutout record.  RT_ERR_INVALID, scene unchanged: no such material; an RT_MAT_DIFFUSE_LIGHT (the light tables take a light's whole area as
+ * emitting) or an RT_MAT_ISOTROPIC; a material that has an interior record (a holed solid has no inside — and rt_scene_set_interior refuses a material that
+ * has a cutout); an image index outside [0, RT_MAX_IMAGES); a cutoff that is not finite or lies outside [0, 1].  rt_scene_clear_cutout takes it away (no
+ * record is no error).  rt_scene_cutouts: *out = one record per material (the scene's own memory, valid until the next call on the scene), *out_n = their
+ * number — or NULL, 0 while no material has a record.                                                                                                       */
+int rt_scene_set_cutout(rt_scene* s, uint32_t material, uint32_t image, float cutoff);
+int rt_scene_clear_cutout(rt_scene* s, uint32_t material);
+int rt_scene_cutouts(const rt_scene* s, const rt_cutout** out, uint32_t* out_n);
+/* HOST (no GPU): the rule on `count` cases — the texture table as rt_texture_lookup_batch takes it; per case its surface quads[i] (Q, u, v, w are read), the
+ * triangle's coordinates uv[i] (uv = NULL: the planar coordinates for every case), the ray rays[6 i ..] (o, d), t[i] and material[i], an index into the
+ * n_records records -> out_keep[i] (0 / 1), out_uv[2 i ..] and out_value[i] = c.green (zeros where the record is off: no lookup is made).                      */
+int rt_cutout_batch(const rt_texture* textures, uint32_t n_textures, const uint8_t* texels, size_t count, const rt_quad* quads, const rt_tri_uvs* uv, const float* rays,
+                    const float* t, const rt_cutout* records, uint32_t n_records, const uint32_t* material, uint32_t* out_keep, float* out_uv, float* out_value);
 
 /* BVH_Handle::Factory::BuildBVH_TopDown -> _build_bvh_rec1 (BVH.cu:166-210):
  * median split on the longest axis, leaf size 1, post-order numbering, root =
@@ -664,6 +692,9 @@ int rt_renderer_kernel_normal_map(rt_renderer* r, uint32_t* out);
 int rt_renderer_kernel_microfacet(rt_renderer* r, uint32_t* out);
 /* *out = 1 when the NEXT launch runs a form of the solid-glass family: an interior table is on (rt_renderer_kernel_microfacet says what else).  */
 int rt_renderer_kernel_interior(rt_renderer* r, uint32_t* out);
+/* *out = 1 when the NEXT launch runs a form of the cutout family: a cutout table is on.  Its forms are solid-glass and microfacet forms that
+ * read one more table, so rt_renderer_kernel_interior and rt_renderer_kernel_microfacet answer 1 then too; rt_renderer_kernel_form keeps its nine fields.    */
+int rt_renderer_kernel_cutout(rt_renderer* r, uint32_t* out);
 /* Renderer::DownloadRenderbuffer (Renderer.cu:94-96): width*height*4 floats,
  * row-major, row 0 = bottom.  Only valid for world_size == 1.               */
 int rt_renderer_download(rt_renderer* r, float* host_rgba, size_t n_floats);
@@ -973,6 +1004,18 @@ int rt_renderer_microfacets_info(rt_renderer* r, uint32_t out[2]);
 int rt_renderer_interiors(rt_renderer* r, const rt_interior* table, uint32_t n);
 /* out[0] = 1 while a table is on, out[1] = how many of its records are on */
 int rt_renderer_interiors_info(rt_renderer* r, uint32_t out[2]);
+/* Alpha cutouts (rt_scene_cutouts): table = one record per material of the world, or NULL, 0 for off (the default).  While a table is on, plain
+ * launches and those of light-sampling mode 48 run the CUT form of the renderer's kernel (rt_renderer_kernel_cutout), whether or not an interior, microfacet or
+ * normal-map table is on; that form reads them all.  Takes effect at the next launch; an unchanged table is a no-op that keeps the refinement, a change discards
+ * it.  RT_ERR_INVALID, renderer and kernel unchanged: what rt_renderer_interiors refuses a renderer for (variants 1, 5, 6; queue and wide4 walks; bvh_node
+ * trees; light-sampling modes 1, 2, 4, 16, 32, which in turn refuse a renderer with a table), a renderer without a texture table, feature buffers that are on
+ * (rt_renderer_aov_enable in turn refuses a renderer with a table: the feature pass does not know the rule), a count that is not the world's number of
+ * materials, a record on a light, a medium or a material whose interior record is on, an `on` other than 0 or 1, an image index outside [0, RT_MAX_IMAGES), a
+ * cutoff that is not finite or outside [0, 1].  A record that names an entry the texture table does not hold is refused at the launch, before any kernel
+ * runs: the tables come and go independently.                                                                                                                */
+int rt_renderer_cutouts(rt_renderer* r, const rt_cutout* table, uint32_t n);
+/* out[0] = 1 while a table is on, out[1] = how many of its records are on */
+int rt_renderer_cutouts_info(rt_renderer* r, uint32_t out[2]);
 
 /* ------------------------------------------------------------------ */
 /* Multi-GPU renderer — the same three entry points (Renderer.h:38-46)  */
@@ -1016,6 +1059,9 @@ int rt_multi_renderer_microfacets(rt_multi_renderer* m, const rt_microfacet* tab
 int rt_multi_renderer_microfacets_info(rt_multi_renderer* m, uint32_t out[2]);
 /* rt_renderer_interiors on every rank (refused before any rank changes).                                                                                        */
 int rt_multi_renderer_interiors(rt_multi_renderer* m, const rt_interior* table, uint32_t n);
+/* rt_renderer_cutouts on every rank (refused before any rank changes), and rt_renderer_cutouts_info of the ranks.                                             */
+int rt_multi_renderer_cutouts(rt_multi_renderer* m, const rt_cutout* table, uint32_t n);
+int rt_multi_renderer_cutouts_info(rt_multi_renderer* m, uint32_t out[2]);
 /* Renderer::DownloadRenderbuffer: width*height*4 floats from devices[0].                                                */
 int rt_multi_renderer_download(rt_multi_renderer* m, float* host_rgba, size_t n_floats);
 /* ms of the last render: out[0] host wall-clock of Render(), out[1] slowest rank's kernels (HIP events),
@@ -1071,6 +1117,10 @@ int rt_probe_rough_glass(int device, size_t count, const float* normal, const fl
 int rt_probe_interior(int device, size_t count, const float* Ng, const float* n, const float* d, const float* t, const float* ior, const float* sigma,
                       const uint32_t* sphere, uint32_t* out_back, float* out_eta, float* out_T);
 int rt_probe_expf(int device, size_t count, const float* x, float* out);
+/* rt_cutout_batch on the device, one lane per case: the table as the renderer holds it (one 4-byte record per texel, the entries as vec4)                      */
+int rt_probe_cutout(int device, const rt_texture* textures, uint32_t n_textures, const uint8_t* texels, size_t count, const rt_quad* quads, const rt_tri_uvs* uv,
+                    const float* rays, const float* t, const rt_cutout* records, uint32_t n_records, const uint32_t* material, uint32_t* out_keep, float* out_uv,
+                    float* out_value);
 /* rt_noise_value_batch on the device, one lane per point: the tables in global memory, as the renderer holds them                                              */
 int rt_probe_noise_value(int device, const rt_perlin* perlin, const float albedo[3], float scale, const float* points, size_t n, float* out_rgb);
 /* rt_environment_sample_batch on the device, one lane per quadruple: the records and the tables as the renderer holds them in mode RT_LIGHT_SAMPLING_ENV        */

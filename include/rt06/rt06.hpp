@@ -401,6 +401,15 @@ public:
         check(rt_scene_interiors(s_, out, &n), "rt_scene_interiors");
         return n;
     }
+    // alpha cutouts (extension; rt_scene_set_cutout): image `image` of the scene is the opacity mask of `material` — its parallelograms and
+    // triangles are there only where the mask's green channel is not below `cutoff`; the table as rt_scene_cutouts hands it out
+    void SetCutout(uint32_t material, uint32_t image, float cutoff = 0.5f) { check(rt_scene_set_cutout(s_, material, image, cutoff), "rt_scene_set_cutout"); }
+    void ClearCutout(uint32_t material) { check(rt_scene_clear_cutout(s_, material), "rt_scene_clear_cutout"); }
+    uint32_t Cutouts(const rt_cutout** out) const {
+        uint32_t n = 0;
+        check(rt_scene_cutouts(s_, out, &n), "rt_scene_cutouts");
+        return n;
+    }
     // child reference of a bvh_node tree: >= 0 node, < 0 primitive
     int32_t tree_ref(const Hittable* h) {
         if (h->kind() == Hittable::NODE) {
@@ -663,13 +672,17 @@ class Renderer {
             rt06::check(rt_scene_microfacets(static_cast<const BVH*>(world)->scene, &mfacs, &n_mfacs), "rt_scene_microfacets");
             bool roughness_mapped = false;
             for (uint32_t i = 0; i < n_mfacs; i++) roughness_mapped = roughness_mapped || mfacs[i].on == RT_MICROFACET_MAPPED || mfacs[i].on == RT_MICROFACET_GLASS_MAPPED;
-            if (table_says_more || ((n_nmaps || roughness_mapped) && n_tex)) made.SetTextures(tex, n_tex, texels);
+            const rt_cutout* cutouts = nullptr;           // ... and one with cutout records theirs, and with them the table of their masks
+            uint32_t n_cutouts = 0;
+            rt06::check(rt_scene_cutouts(static_cast<const BVH*>(world)->scene, &cutouts, &n_cutouts), "rt_scene_cutouts");
+            if (table_says_more || ((n_nmaps || roughness_mapped || n_cutouts) && n_tex)) made.SetTextures(tex, n_tex, texels);
             if (n_nmaps) made.SetNormalMaps(nmaps, n_nmaps);
             if (n_mfacs) made.SetMicrofacets(mfacs, n_mfacs);
             const rt_interior* interiors = nullptr;       // ... and one with interior records theirs
             uint32_t n_interiors = 0;
             rt06::check(rt_scene_interiors(static_cast<const BVH*>(world)->scene, &interiors, &n_interiors), "rt_scene_interiors");
             if (n_interiors) made.SetInteriors(interiors, n_interiors);
+            if (n_cutouts) made.SetCutouts(cutouts, n_cutouts);
         }
         return made;
     }
@@ -797,6 +810,12 @@ public:
     void SetInteriors(const rt_interior* table, uint32_t n) {
         if (m.mr) rt06::check(rt_multi_renderer_interiors(m.mr, table, n), "Renderer::SetInteriors");
         else rt06::check(rt_renderer_interiors(m.r, table, n), "Renderer::SetInteriors");
+    }
+    // Alpha cutouts (extension; rt_renderer_cutouts): one record per material of the world as SceneBuilder::Cutouts hands them out, or
+    // (nullptr, 0) for off; the masks are entries of the texture table (SetTextures); restarts a refinement
+    void SetCutouts(const rt_cutout* table, uint32_t n) {
+        if (m.mr) rt06::check(rt_multi_renderer_cutouts(m.mr, table, n), "Renderer::SetCutouts");
+        else rt06::check(rt_renderer_cutouts(m.r, table, n), "Renderer::SetCutouts");
     }
     void SetTextures(const rt_texture* records, uint32_t n, const uint8_t* texels) {
         if (m.mr) rt06::check(rt_multi_renderer_textures(m.mr, records, n, texels), "Renderer::SetTextures");

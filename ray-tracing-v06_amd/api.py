@@ -231,6 +231,23 @@ class Scene:
         check(lib().rt_scene_interiors(self.h, C.byref(rec), C.byref(n)))
         return None if n.value == 0 else self._arr(rec.value, n.value, capi.INTERIOR_DT)
 
+    def set_cutout(self, material, image, cutoff=0.5):
+        """Makes image `image` of the scene (set_image() = 0, add_image() = 1, 2, ...) the opacity mask of `material` (extension; DESIGN.md §34;
+        rt_scene_set_cutout): a parallelogram or triangle of that material is there only where the mask's green channel is not below `cutoff`, and a ray goes
+        through it elsewhere.  Spheres ignore the record; lights, media and materials with an interior record take none."""
+        check(lib().rt_scene_set_cutout(self.h, material, image, float(cutoff)))
+        return self
+
+    def clear_cutout(self, material):
+        check(lib().rt_scene_clear_cutout(self.h, material))
+        return self
+
+    def cutouts(self):
+        """The scene's cutout table (rt_scene_cutouts): one record of capi.CUTOUT_DT per material, or None while no material has a record."""
+        rec, n = C.c_void_p(), C.c_uint32()
+        check(lib().rt_scene_cutouts(self.h, C.byref(rec), C.byref(n)))
+        return None if n.value == 0 else self._arr(rec.value, n.value, capi.CUTOUT_DT)
+
     def MakeBox(self, a, b, mat, rotate_y=0.0, translate=(0, 0, 0)):
         """box(a, b, mat) of "The Next Week" as 6 quads, optionally rotate_y(degrees) then translate; returns the first quad index."""
         out = C.c_int32()
@@ -443,6 +460,11 @@ class Scene:
         interiors = self.interiors()          # likewise the interior records, which need no other table
         if interiors is not None:
             w.interiors = interiors
+        cutouts = self.cutouts()              # likewise the cutout records, and with them the table they name their masks in
+        if cutouts is not None:
+            w.cutouts = cutouts
+            if table is not None:
+                w.textures = table
         return w
 
     def _arr(self, ptr, n, dt):
@@ -592,6 +614,13 @@ def _push_interiors(fn, handle, table):
     return fn(handle, table.ctypes.data if len(table) else None, len(table))
 
 
+def _push_cutouts(fn, handle, table):
+    if table is None:
+        return fn(handle, None, 0)
+    table = np.ascontiguousarray(table, capi.CUTOUT_DT).reshape(-1)
+    return fn(handle, table.ctypes.data if len(table) else None, len(table))
+
+
 def _push_microfacets(fn, handle, table):
     if table is None:
         return fn(handle, None, 0)
@@ -641,6 +670,8 @@ class Renderer:
             r.microfacets(world.microfacets)
         if getattr(world, "interiors", None) is not None:
             r.interiors(world.interiors)
+        if getattr(world, "cutouts", None) is not None:
+            r.cutouts(world.cutouts)
         return r
 
     def Render(self):
@@ -836,6 +867,24 @@ class Renderer:
         check(lib().rt_renderer_kernel_interior(self.h, C.byref(out)))
         return bool(out.value)
 
+    def cutouts(self, table):
+        """The cutout table from the next launch on (rt_renderer_cutouts; DESIGN.md §34): one record of capi.CUTOUT_DT per material as Scene.cutouts() gives it;
+        None = off.  The masks are entries of the renderer's texture table (textures()).  A change restarts the refinement."""
+        check(_push_cutouts(lib().rt_renderer_cutouts, self.h, table))
+
+    def cutouts_info(self):
+        """{'enabled', 'records'} of the renderer's cutout table: records = how many materials have one."""
+        out = (C.c_uint32 * 2)()
+        check(lib().rt_renderer_cutouts_info(self.h, out))
+        return {"enabled": bool(out[0]), "records": out[1]}
+
+    def kernel_cutout(self):
+        """True when the next launch runs the streaming kernel's cutout family (rt_renderer_kernel_cutout): a cutout table is on.  kernel_interior() and
+        kernel_microfacet() are True then too: the cutout forms are those forms, reading one more table."""
+        out = C.c_uint32(0)
+        check(lib().rt_renderer_kernel_cutout(self.h, C.byref(out)))
+        return bool(out.value)
+
     def kernel_microfacet(self):
         """True when the next launch runs the streaming kernel's microfacet family (rt_renderer_kernel_microfacet): a microfacet table is on, or an
         interior table — the solid-glass forms (kernel_interior) are microfacet forms that read one more table."""
@@ -964,6 +1013,8 @@ class MultiRenderer:
             m.microfacets(world.microfacets)
         if getattr(world, "interiors", None) is not None:
             m.interiors(world.interiors)
+        if getattr(world, "cutouts", None) is not None:
+            m.cutouts(world.cutouts)
         return m
 
     def Render(self):
@@ -1014,6 +1065,16 @@ class MultiRenderer:
     def interiors(self, table):
         """rt_renderer_interiors on every rank; `table` as Renderer.interiors takes it."""
         check(_push_interiors(lib().rt_multi_renderer_interiors, self.h, table))
+
+    def cutouts(self, table):
+        """rt_renderer_cutouts on every rank; `table` as Renderer.cutouts takes it."""
+        check(_push_cutouts(lib().rt_multi_renderer_cutouts, self.h, table))
+
+    def cutouts_info(self):
+        """{'enabled', 'records'} of the ranks' cutout table (they hold the same one)."""
+        out = (C.c_uint32 * 2)()
+        check(lib().rt_multi_renderer_cutouts_info(self.h, out))
+        return {"enabled": bool(out[0]), "records": out[1]}
 
     def microfacets_info(self):
         """{'enabled', 'records'} of the ranks' microfacet table (they hold the same one)."""
@@ -1415,6 +1476,34 @@ def expf_batch(x):
 def probe_expf(x, device=0):
     """rt_probe_expf: expf_batch on the device, one lane per value"""
     return _expf(lambda *args: lib().rt_probe_expf(device, *args), x)
+
+
+def _cutout(fn, table, quads, uv, rays, t, records, material):
+    tex, texels = texture_table(table)
+    quads = np.ascontiguousarray(quads, capi.QUAD_DT).reshape(-1)
+    rays, t = np.ascontiguousarray(rays, np.float32).reshape(-1, 6), np.ascontiguousarray(t, np.float32).reshape(-1)
+    records, material = np.ascontiguousarray(records, capi.CUTOUT_DT).reshape(-1), np.ascontiguousarray(material, np.uint32).reshape(-1)
+    k = len(t)
+    if uv is not None:
+        uv = np.ascontiguousarray(np.asarray(uv, np.float32).reshape(-1, 6))
+    if not (len(quads) == len(rays) == len(material) == k and (uv is None or len(uv) == k)):
+        raise ValueError("cutout: every array must have one entry per case")
+    keep, out_uv, value = np.zeros(k, np.uint32), np.zeros((k, 2), np.float32), np.zeros(k, np.float32)
+    check(fn(tex.ctypes.data if len(tex) else None, len(tex), texels.ctypes.data if len(texels) else None, k, quads.ctypes.data if k else None,
+             uv.ctypes.data if uv is not None and k else None, rays, t, records.ctypes.data if len(records) else None, len(records), material, keep, out_uv, value))
+    return keep, out_uv, value
+
+
+def cutout_batch(table, quads, uv, rays, t, records, material):
+    """rt_cutout_batch (host only): the cutout rule on k cases — `table` as Renderer.textures takes it; per case the surface quads[i]
+    (capi.QUAD_DT), its texture coordinates uv[i] ((k, 3, 2); None: the planar coordinates for every case), the ray rays[i] (o, d), the candidate's t[i] and
+    material[i], an index into `records` (capi.CUTOUT_DT) -> (keep (k,) 0 / 1, uv (k, 2), value (k,): the mask's green; zeros where the record is off)"""
+    return _cutout(lib().rt_cutout_batch, table, quads, uv, rays, t, records, material)
+
+
+def probe_cutout(table, quads, uv, rays, t, records, material, device=0):
+    """rt_probe_cutout: cutout_batch on the device, one lane per case"""
+    return _cutout(lambda *args: lib().rt_probe_cutout(device, *args), table, quads, uv, rays, t, records, material)
 
 
 def _rough_glass(fn, normal, ray_d, roughness, ior, tapes):

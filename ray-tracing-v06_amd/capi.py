@@ -42,6 +42,8 @@ MFAC_SPECULAR, MFAC_BASE, MFAC_ABSORBED, MFAC_BACKSIDE = 1, 2, 3, 4
 MICROFACET_GLASS, MICROFACET_GLASS_MAPPED, MFAC_TRANSMITTED = 4, 6, 5   # rough glass
 INTERIOR_DT = np.dtype([("on", "<u4"), ("sigma", "<f4", 3)])   # rt_interior, 16 B
 INTERIOR_OFF, INTERIOR_SOLID = 0, 1
+CUTOUT_DT = np.dtype([("on", "<u4"), ("image", "<u4"), ("cutoff", "<f4"), ("reserved", "<u4")])   # rt_cutout, 16 B
+CUTOUT_OFF, CUTOUT_MASKED = 0, 1
 WRAP_CLAMP, WRAP_REPEAT = 0, 1
 FILTER_NEAREST, FILTER_BILINEAR = 0, 1
 MAX_IMAGES = 256
@@ -121,6 +123,8 @@ SYMBOLS = [
     "rt_scene_set_rough_glass", "rt_rough_glass_batch", "rt_probe_rough_glass",
     "rt_scene_set_interior", "rt_scene_clear_interior", "rt_scene_interiors", "rt_interior_batch", "rt_probe_interior", "rt_expf_batch", "rt_probe_expf",
     "rt_renderer_interiors", "rt_renderer_interiors_info", "rt_renderer_kernel_interior", "rt_multi_renderer_interiors",
+    "rt_scene_set_cutout", "rt_scene_clear_cutout", "rt_scene_cutouts", "rt_cutout_batch", "rt_probe_cutout", "rt_renderer_cutouts", "rt_renderer_cutouts_info",
+    "rt_renderer_kernel_cutout", "rt_multi_renderer_cutouts", "rt_multi_renderer_cutouts_info",
 ]
 
 _lib = None
@@ -277,6 +281,16 @@ def lib():
     L.rt_renderer_interiors_info.argtypes = [C.c_void_p, C.c_uint32 * 2]
     L.rt_renderer_kernel_interior.argtypes = [C.c_void_p, P(C.c_uint32)]
     L.rt_multi_renderer_interiors.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+    L.rt_scene_set_cutout.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float]
+    L.rt_scene_clear_cutout.argtypes = [C.c_void_p, C.c_uint32]
+    L.rt_scene_cutouts.argtypes = [C.c_void_p, P(C.c_void_p), P(C.c_uint32)]
+    L.rt_cutout_batch.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, f32p, f32p, C.c_void_p, C.c_uint32, u32p, u32p, f32p, f32p]
+    L.rt_probe_cutout.argtypes = [C.c_int] + L.rt_cutout_batch.argtypes
+    L.rt_renderer_cutouts.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+    L.rt_renderer_cutouts_info.argtypes = [C.c_void_p, C.c_uint32 * 2]
+    L.rt_renderer_kernel_cutout.argtypes = [C.c_void_p, P(C.c_uint32)]
+    L.rt_multi_renderer_cutouts.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+    L.rt_multi_renderer_cutouts_info.argtypes = [C.c_void_p, C.c_uint32 * 2]
     L.rt_scene_set_background.argtypes = [C.c_void_p, C.c_uint32, vec3]
     L.rt_scene_set_perlin.argtypes = [C.c_void_p, C.c_uint64]
     L.rt_scene_set_image.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]

@@ -61,6 +61,7 @@ constexpr uint32_t RT_KEY_ENVL = 1u << 13;  // environment light sampling (mode 
 constexpr uint32_t RT_KEY_NMAP = 1u << 14;  // normal maps (rt_renderer_normal_maps): the NMAP form of an EXT 2 TRI key, plain or with mode 48; reported by rt_renderer_kernel_normal_map
 constexpr uint32_t RT_KEY_MFAC = 1u << 15;  // microfacet surfaces (rt_renderer_microfacets): the MFAC form of an EXT 2 TRI key, plain or with mode 48, which reads the normal-map table too; reported by rt_renderer_kernel_microfacet
 constexpr uint32_t RT_KEY_INTR = 1u << 16;  // solid glass (rt_renderer_interiors): the INTR form of an MFAC key, plain or with mode 48, which reads all three tables; reported by rt_renderer_kernel_interior
+constexpr uint32_t RT_KEY_CUT = 1u << 17;   // alpha cutouts (rt_renderer_cutouts): the CUT form of an INTR key, plain or with mode 48, which reads all four tables; reported by rt_renderer_kernel_cutout
 constexpr uint32_t RT_KEY_TRI = 1u << 11;   // the world has triangles: the TRI form of an EXT >= 1 stack-walk or list key, plain or NEE; not one of rt_renderer_kernel_form's fields
 // a stream key read back into render_kernel_stream's template arguments, in stream_key()'s order, then NEE: what rt_renderer_kernel_form reports
 static void stream_key_fields(uint32_t key, uint32_t out[8]) {
@@ -107,17 +108,21 @@ static const void* stream_kernel_for(uint32_t key) {
 #define RT_KERNEL_ENV_TREE(exact, world, ext, big, wide) \
     case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NEE | RT_KEY_LTREE | RT_KEY_ENVL: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, true, true, true, true>)
 #define RT_KERNEL_NORMAL_MAP(exact, world, ext, big, wide) \
-    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NMAP: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, false, true, false, false, false, false, true>)
+    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NMAP: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, false, true, false, false, false, false, false, true>)
 #define RT_KERNEL_NORMAL_MAP_ENV_TREE(exact, world, ext, big, wide) \
-    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NEE | RT_KEY_LTREE | RT_KEY_ENVL | RT_KEY_NMAP: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, true, true, true, true, false, false, true>)
+    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NEE | RT_KEY_LTREE | RT_KEY_ENVL | RT_KEY_NMAP: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, true, true, true, true, false, false, false, true>)
 #define RT_KERNEL_MICROFACET(exact, world, ext, big, wide) \
-    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_MFAC: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, false, true, false, false, false, true, true>)
+    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_MFAC: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, false, true, false, false, false, false, true, true>)
 #define RT_KERNEL_MICROFACET_ENV_TREE(exact, world, ext, big, wide) \
-    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NEE | RT_KEY_LTREE | RT_KEY_ENVL | RT_KEY_MFAC: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, true, true, true, true, false, true, true>)
+    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NEE | RT_KEY_LTREE | RT_KEY_ENVL | RT_KEY_MFAC: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, true, true, true, true, false, false, true, true>)
 #define RT_KERNEL_INTERIOR(exact, world, ext, big, wide) \
-    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_MFAC | RT_KEY_INTR: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, false, true, false, false, true, true, true>)
+    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_MFAC | RT_KEY_INTR: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, false, true, false, false, false, true, true, true>)
 #define RT_KERNEL_INTERIOR_ENV_TREE(exact, world, ext, big, wide) \
-    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NEE | RT_KEY_LTREE | RT_KEY_ENVL | RT_KEY_MFAC | RT_KEY_INTR: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, true, true, true, true, true, true, true>)
+    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NEE | RT_KEY_LTREE | RT_KEY_ENVL | RT_KEY_MFAC | RT_KEY_INTR: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, true, true, true, true, false, true, true, true>)
+#define RT_KERNEL_CUTOUT(exact, world, ext, big, wide) \
+    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_MFAC | RT_KEY_INTR | RT_KEY_CUT: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, false, true, false, false, true, true, true, true>)
+#define RT_KERNEL_CUTOUT_ENV_TREE(exact, world, ext, big, wide) \
+    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NEE | RT_KEY_LTREE | RT_KEY_ENVL | RT_KEY_MFAC | RT_KEY_INTR | RT_KEY_CUT: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, true, true, true, true, true, true, true, true>)
     switch (key) {   // arguments: exact, filter, world, ext, big, wide, tol
         case RT_KEY_XCHG: return reinterpret_cast<const void*>(&render_kernel_xchg<RT_XCHG_BLOCK>);
         RT_KERNEL(true, false, RT_WORLD_BVH_QUEUE, 2, true, true, false); RT_KERNEL(true, false, RT_WORLD_BVH_QUEUE, 1, true, true, false); RT_KERNEL(true, false, RT_WORLD_BVH_QUEUE, 0, true, true, false);
@@ -199,9 +204,23 @@ static const void* stream_kernel_for(uint32_t key) {
         RT_KERNEL_INTERIOR_ENV_TREE(false, RT_WORLD_BVH, 2, true, false); RT_KERNEL_INTERIOR_ENV_TREE(true, RT_WORLD_BVH, 2, true, false);
         RT_KERNEL_INTERIOR_ENV_TREE(true, RT_WORLD_LIST, 2, false, false);
         RT_KERNEL_INTERIOR_ENV_TREE(false, RT_WORLD_BVH, 2, false, false); RT_KERNEL_INTERIOR_ENV_TREE(true, RT_WORLD_BVH, 2, false, false);
+        // alpha cutouts: the solid-glass shapes once more, whose leaf phase asks the cutout records before it takes a hit, plain ...
+        RT_KERNEL_CUTOUT(true, RT_WORLD_LIST, 2, true, true);
+        RT_KERNEL_CUTOUT(false, RT_WORLD_BVH, 2, true, true); RT_KERNEL_CUTOUT(true, RT_WORLD_BVH, 2, true, true);
+        RT_KERNEL_CUTOUT(false, RT_WORLD_BVH, 2, true, false); RT_KERNEL_CUTOUT(true, RT_WORLD_BVH, 2, true, false);
+        RT_KERNEL_CUTOUT(true, RT_WORLD_LIST, 2, false, false);
+        RT_KERNEL_CUTOUT(false, RT_WORLD_BVH, 2, false, false); RT_KERNEL_CUTOUT(true, RT_WORLD_BVH, 2, false, false);
+        // ... and under mode 48
+        RT_KERNEL_CUTOUT_ENV_TREE(true, RT_WORLD_LIST, 2, true, true);
+        RT_KERNEL_CUTOUT_ENV_TREE(false, RT_WORLD_BVH, 2, true, true); RT_KERNEL_CUTOUT_ENV_TREE(true, RT_WORLD_BVH, 2, true, true);
+        RT_KERNEL_CUTOUT_ENV_TREE(false, RT_WORLD_BVH, 2, true, false); RT_KERNEL_CUTOUT_ENV_TREE(true, RT_WORLD_BVH, 2, true, false);
+        RT_KERNEL_CUTOUT_ENV_TREE(true, RT_WORLD_LIST, 2, false, false);
+        RT_KERNEL_CUTOUT_ENV_TREE(false, RT_WORLD_BVH, 2, false, false); RT_KERNEL_CUTOUT_ENV_TREE(true, RT_WORLD_BVH, 2, false, false);
         default: return nullptr;
     }
 #undef RT_KERNEL
+#undef RT_KERNEL_CUTOUT
+#undef RT_KERNEL_CUTOUT_ENV_TREE
 #undef RT_KERNEL_INTERIOR
 #undef RT_KERNEL_INTERIOR_ENV_TREE
 #undef RT_KERNEL_MICROFACET
@@ -356,8 +375,11 @@ struct rt_renderer {
     // solid glass (rt_renderer_interiors): one record per material as given; with a table the tail's first lane counts to a sub-header, behind which
     // the microfacet and the interior records lie.  While on, a plain launch and a mode-48 launch run the INTR form of their kernel, which reads all three tables.
     struct Interiors { bool on = false; uint32_t n_on = 0; std::vector<rt_interior> host; } in;
-    struct { uint32_t key = 0; const void* kernel = nullptr; } nm_plain, nm_envt, mf_plain, mf_envt, in_plain, in_envt;
-    bool tail_on() const { return vn.on || uv.on || env.on || tex.on || mf.on || in.on; }
+    // alpha cutouts (rt_renderer_cutouts): one record per material as given, behind the interior records; the sub-header's third lane says where.
+    // While on, a plain launch and a mode-48 launch run the CUT form of their kernel, which reads all four tables, whichever of the others are there.
+    struct Cutouts { bool on = false; uint32_t n_on = 0; std::vector<rt_cutout> host; } cut;
+    struct { uint32_t key = 0; const void* kernel = nullptr; } nm_plain, nm_envt, mf_plain, mf_envt, in_plain, in_envt, cut_plain, cut_envt;
+    bool tail_on() const { return vn.on || uv.on || env.on || tex.on || mf.on || in.on || cut.on; }
     // the NMAP form of the renderer's kernel: the world's own shape at EXT 2 with TRI, plain or with mode 48's bits (0: a world no NMAP form walks)
     uint32_t normal_map_key(bool envt) const {
         if (variant < 2 || variant == 5 || tol || scene.queue || scene.dw.kind == RT_WORLD_NODE_TREE) return 0u;
@@ -376,6 +398,13 @@ struct rt_renderer {
         if (!mf.on) return false;
         for (const rt_microfacet& m : mf.host)
             if ((m.on == RT_MICROFACET_MAPPED || m.on == RT_MICROFACET_GLASS_MAPPED) && (!tex.on || m.image >= tex.records.size() || tex.records[m.image].width == 0u)) { *which = m.image; return true; }
+        return false;
+    }
+    // ... or for its cutout masks (§34): every record that is on names an entry
+    bool cutout_entry_missing(uint32_t* which) const {
+        if (!cut.on) return false;
+        for (const rt_cutout& m : cut.host)
+            if (m.on && (!tex.on || m.image >= tex.records.size() || tex.records[m.image].width == 0u)) { *which = m.image; return true; }
         return false;
     }
     // whether a launch is refused for its image materials (§25): one of them names an entry (*which) the renderer does not have
@@ -419,6 +448,8 @@ struct rt_renderer {
         if (mf.on && mode == RT_LIGHT_SAMPLING_ENV_TREE) { l.kernel = mf_envt.kernel; l.key = mf_envt.key; }
         if (in.on && !m) { l.kernel = in_plain.kernel; l.key = in_plain.key; }   // §32: likewise, and before either of them: the INTR forms read all three
         if (in.on && mode == RT_LIGHT_SAMPLING_ENV_TREE) { l.kernel = in_envt.kernel; l.key = in_envt.key; }
+        if (cut.on && !m) { l.kernel = cut_plain.kernel; l.key = cut_plain.key; }   // §34: likewise, and before all of them: the CUT forms read all four
+        if (cut.on && mode == RT_LIGHT_SAMPLING_ENV_TREE) { l.kernel = cut_envt.kernel; l.key = cut_envt.key; }
         l.blob = (im.blob.p ? im.blob : scene.blob).as<uint4>();
         l.blob_vec4 = scene.packed.blob_vec4 + im.table_vec4;
         l.lds_bytes = i ? im.lds_bytes : stream_lds_bytes;
@@ -461,6 +492,18 @@ struct rt_renderer {
         slot_of.key = key; slot_of.kernel = k;
         return RT_OK;
     }
+    // §34: the CUT form of the plain kernel, or of mode 48's, once: the INTR form's shape with the cutout bit beside the other two
+    int resolve_cutout_kernel(bool envt, uint32_t lds_bytes) {
+        auto& slot_of = envt ? cut_envt : cut_plain;
+        if (slot_of.kernel) return RT_OK;
+        const uint32_t nmap_key = normal_map_key(envt);
+        const uint32_t key = nmap_key ? (nmap_key & ~RT_KEY_NMAP) | RT_KEY_MFAC | RT_KEY_INTR | RT_KEY_CUT : 0u;
+        const void* k = key ? stream_kernel_for(key) : nullptr;
+        if (!k) return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: this world's kernel has no form that reads a cutout table");
+        HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+        slot_of.key = key; slot_of.kernel = k;
+        return RT_OK;
+    }
     // Image i (0: the plain one; 1 to 4: with the light table of mode 1, 2, 4, 16) from the riders as they stand, into `fresh`: scene | light table | tail
     // (rt_launch_image.hpp has both layouts).  The scene part is copied device to device, the rest uploaded once.  The plain image without a tail gets no buffer.
     int compose(uint32_t i, Image& fresh) const {
@@ -485,6 +528,7 @@ struct rt_renderer {
         if (nm.on) { rd.normal_maps = nm.host.data(); rd.n_normal_maps = nm.host.size(); }
         if (mf.on) { rd.microfacets = mf.host.data(); rd.n_microfacets = mf.host.size(); }
         if (in.on) { rd.interiors = in.host.data(); rd.n_interiors = in.host.size(); }
+        if (cut.on) { rd.cutouts = cut.host.data(); rd.n_cutouts = cut.host.size(); }
         rt_image::append_tail(rest, rd);
         const size_t scene_bytes = (size_t)scene.packed.blob_vec4 * sizeof(uint4);
         HIP_TRY(fresh.blob.alloc(scene_bytes + rest.size() * sizeof(uint4)));
@@ -1018,6 +1062,8 @@ static int enqueue_call(rt_renderer* r, void* hip_stream, float* d_out, uint32_t
         return rt_fail(RT_ERR_INVALID, "an image material of the world names image %u and the renderer's texture table has no such entry: give it one with rt_renderer_textures before rendering", k);
     if (uint32_t k = 0u; r->normal_map_entry_missing(&k))   // ... nor on a normal map the table does not hold
         return rt_fail(RT_ERR_INVALID, "a normal map of the world names image %u and the renderer's texture table has no such entry: give it one with rt_renderer_textures before rendering", k);
+    if (uint32_t k = 0u; r->cutout_entry_missing(&k))   // ... nor on a cutout mask it does not hold
+        return rt_fail(RT_ERR_INVALID, "a cutout record of the world names image %u and the renderer's texture table has no such entry: give it one with rt_renderer_textures before rendering", k);
     if (uint32_t k = 0u; r->roughness_map_entry_missing(&k))   // ... nor on a roughness map it does not hold
         return rt_fail(RT_ERR_INVALID, "a roughness map of the world names image %u and the renderer's texture table has no such entry: give it one with rt_renderer_textures before rendering", k);
     HIP_TRY(hipSetDevice(r->cfg.device));
@@ -1092,6 +1138,8 @@ extern "C" int rt_renderer_light_sampling_enable(rt_renderer* r, uint32_t on) {
             return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: the renderer has a microfacet table, and light-sampling mode %u has no kernel that reads one: microfacet surfaces render with light sampling off or in mode 48 (take the table away with rt_renderer_microfacets(NULL, 0) first)", on);
         if (r->in.on && on != RT_LIGHT_SAMPLING_ENV_TREE)
             return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: the renderer has an interior table, and light-sampling mode %u has no kernel that reads one: solid glass renders with light sampling off or in mode 48 (take the table away with rt_renderer_interiors(NULL, 0) first)", on);
+        if (r->cut.on && on != RT_LIGHT_SAMPLING_ENV_TREE)
+            return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: the renderer has a cutout table, and light-sampling mode %u has no kernel that reads one: alpha cutouts render with light sampling off or in mode 48 (take the table away with rt_renderer_cutouts(NULL, 0) first)", on);
         if (m->env && r->scene.dw.background != 2u)   // a world of this kind takes the modes of the light tables only, so the message lists them
             return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: mode %u samples the environment map of a world with background mode 2 (rt_scene_set_environment)%s; this world's is %u, for which on must be 0 (off), 1 (quad lights), 2 (quad and sphere lights), 4 (quad, sphere and triangle lights) or 16 (those, through a light tree, chosen by area)", on, m->beside, r->scene.dw.background);
         if (m->env && r->scene.queue)
@@ -1126,6 +1174,8 @@ extern "C" int rt_renderer_light_sampling_enable(rt_renderer* r, uint32_t on) {
             if (const int rc = r->resolve_microfacet_kernel(true, r->launch_on(on).lds_bytes)) return rc;
         if (r->in.on)   // §32: likewise
             if (const int rc = r->resolve_interior_kernel(true, r->launch_on(on).lds_bytes)) return rc;
+        if (r->cut.on)   // §34: likewise
+            if (const int rc = r->resolve_cutout_kernel(true, r->launch_on(on).lds_bytes)) return rc;
         if (m->env && !r->env.dist_on) {   // the distribution of the map as it stands (a map given while the mode is on brings its own: rt_renderer_environment); an all-black map is refused here
             char who[64];
             std::snprintf(who, sizeof(who), "rt_renderer_light_sampling_enable: mode %u", on);
@@ -1416,6 +1466,7 @@ extern "C" int rt_renderer_interiors(rt_renderer* r, const rt_interior* table, u
             if (table[i].on == RT_INTERIOR_OFF) continue;
             if (table[i].on != RT_INTERIOR_SOLID) return rt_fail(RT_ERR_INVALID, "rt_renderer_interiors: record %u: on is 0 (off) or 1 (solid), not %u", i, table[i].on);
             if (r->scene.mat_types[i] != RT_MAT_DIELECTRIC) return rt_fail(RT_ERR_INVALID, "rt_renderer_interiors: record %u: an interior record belongs on a dielectric alone", i);
+            if (r->cut.on && r->cut.host[i].on != RT_CUTOUT_OFF) return rt_fail(RT_ERR_INVALID, "rt_renderer_interiors: record %u: the material has a cutout record, and a holed solid has no inside", i);
             for (int c = 0; c < 3; c++)
                 if (!(std::isfinite(table[i].sigma[c]) && table[i].sigma[c] >= 0.0f)) return rt_fail(RT_ERR_INVALID, "rt_renderer_interiors: record %u: an absorption coefficient must be finite and >= 0", i);
             n_on++;
@@ -1444,6 +1495,64 @@ extern "C" int rt_renderer_interiors_info(rt_renderer* r, uint32_t out[2]) {
     if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_interiors_info: null argument");
     out[0] = r->in.on ? 1u : 0u;
     out[1] = r->in.on ? r->in.n_on : 0u;
+    return RT_OK;
+}
+
+// Alpha cutouts.  Off: every launch is what it was.  On: the CUT form of the renderer's kernel on images whose tail ends with a sub-header and
+// the record tables, the cutout records last.  A refusal leaves the table and the kernel as they were.  The entries the records name are checked at every
+// launch (enqueue_call), as a normal map's are: the tables come and go independently.
+extern "C" int rt_renderer_cutouts(rt_renderer* r, const rt_cutout* table, uint32_t n) {
+    if (!r) return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: null renderer");
+    if ((table == nullptr) != (n == 0u)) return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: a table and its count go together (NULL, 0 turns it off)");
+    uint32_t n_on = 0;
+    if (n) {
+        if (r->variant < 2) return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: the baseline kernel (variant 1) reads no cutout table; use variant 0, 2 or 3");
+        if (r->variant == 5 || r->tol) return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: kernel variant %u reads no cutout table", r->tol ? 6u : 5u);
+        if (r->scene.queue) return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: a world with a queue or wide4 traversal renders on lane walks that read no cutout table (RT_TRAVERSAL_STACK and lists do)");
+        if (r->scene.dw.kind == RT_WORLD_NODE_TREE) return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: a bvh_node tree renders on a walk that reads no cutout table (BVHs walked by the stack and lists do)");
+        if (r->nee.on() && r->nee.mode != RT_LIGHT_SAMPLING_ENV_TREE)
+            return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: light-sampling mode %u is on, which has no kernel that reads a cutout table: alpha cutouts render with light sampling off or in mode 48", r->nee.mode);
+        if (r->aov_on)
+            return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: feature buffers are on, and the feature pass does not know the cutout rule: its first hits would be the solid cards, and a denoiser guided by them would be wrong without a sign");
+        if (!r->tex.on) return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: the renderer has no texture table to take a mask from: give it one with rt_renderer_textures first");
+        if (n != r->scene.dw.n_mats) return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: %u records for a world of %u materials", n, r->scene.dw.n_mats);
+        for (uint32_t i = 0; i < n; i++) {
+            if (table[i].on == RT_CUTOUT_OFF) continue;
+            if (table[i].on != RT_CUTOUT_MASKED) return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: record %u: on is 0 (off) or 1 (masked), not %u", i, table[i].on);
+            const uint32_t type = r->scene.mat_types[i];
+            if (type == RT_MAT_DIFFUSE_LIGHT || type == RT_MAT_ISOTROPIC)
+                return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: record %u: a light or a medium takes no cutout", i);
+            if (r->in.on && r->in.host[i].on != RT_INTERIOR_OFF) return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: record %u: the material has an interior record, and a holed solid has no inside", i);
+            if (table[i].image >= RT_MAX_IMAGES) return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: record %u: an image index lies in [0, %u)", i, RT_MAX_IMAGES);
+            if (!(std::isfinite(table[i].cutoff) && table[i].cutoff >= 0.0f && table[i].cutoff <= 1.0f)) return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: record %u: a cutoff must be finite and in [0, 1]", i);
+            n_on++;
+        }
+    }
+    rt_renderer::Cutouts next;
+    if (n) {
+        next.on = true; next.n_on = n_on; next.host.assign(table, table + n);
+        for (rt_cutout& m : next.host) {   // what no kernel reads is zero, so that equal tables are equal bytes; -0 is 0
+            m.reserved = 0u;
+            if (m.on == RT_CUTOUT_OFF) m = rt_cutout{RT_CUTOUT_OFF, 0u, 0.0f, 0u}; else m.cutoff = m.cutoff + 0.0f;
+        }
+    }
+    if (n ? (r->cut.on && r->cut.host.size() == n && std::memcmp(r->cut.host.data(), next.host.data(), (size_t)n * sizeof(rt_cutout)) == 0) : !r->cut.on) return RT_OK;   // nothing changes, the refinement goes on
+    if (const int rc = wait_last_call(r)) return rc;   // launches already enqueued read the images that are replaced below (sets the device)
+    if (n) {
+        if (const int rc = r->resolve_cutout_kernel(false, r->stream_lds_bytes)) return rc;
+        if (r->nee.mode == RT_LIGHT_SAMPLING_ENV_TREE)
+            if (const int rc = r->resolve_cutout_kernel(true, r->launch_on(RT_LIGHT_SAMPLING_ENV_TREE).lds_bytes)) return rc;
+    }
+    if (const int rc = r->replace_rider(r->cut, next)) return rc;   // (a failure leaves table, images and refinement as they were)
+    r->refine_done = 0;   // samples that saw the cards whole belong to another frame
+    r->aov_done = 0;
+    return RT_OK;
+}
+
+extern "C" int rt_renderer_cutouts_info(rt_renderer* r, uint32_t out[2]) {
+    if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts_info: null argument");
+    out[0] = r->cut.on ? 1u : 0u;
+    out[1] = r->cut.on ? r->cut.n_on : 0u;
     return RT_OK;
 }
 
@@ -1545,6 +1654,8 @@ static int aov_enable(const char* who, rt_renderer* r, uint32_t max_samples, uin
         return rt_fail(RT_ERR_INVALID, "%s: the baseline kernel (variant 1) cannot refine and keeps no primary-ray records; feature buffers need a streaming variant (0, or 2 to 6)", who);
     if (mode == RT_AOV_PLAIN && r->nm.on)
         return rt_fail(RT_ERR_INVALID, "%s: the renderer has a normal-map table, and the plain feature pass's normals know no normal map: enable the pass in RT_AOV_TEXTURED mode (rt_renderer_aov_enable_mode)", who);
+    if (r->cut.on)
+        return rt_fail(RT_ERR_INVALID, "%s: the renderer has a cutout table, and the feature pass does not know the cutout rule: its first hits would be the solid cards, and a denoiser guided by them would be wrong without a sign (take the table away with rt_renderer_cutouts(NULL, 0) first)", who);
     if (mode == RT_AOV_PLAIN && r->aov_refused)
         return rt_fail(RT_ERR_INVALID, "%s: the world has %s: the feature pass covers spheres and quads with Lambertian, metal, dielectric, checker and light materials", who, r->aov_refused);
     if (mode == RT_AOV_TEXTURED && r->has_medium)   // §27: a medium's first event is an RNG draw, which no trace of the feature pass makes
@@ -1749,6 +1860,12 @@ extern "C" int rt_renderer_kernel_microfacet(rt_renderer* r, uint32_t* out) {
 extern "C" int rt_renderer_kernel_interior(rt_renderer* r, uint32_t* out) {
     if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_kernel_interior: null argument");
     *out = r->variant >= 2 && (r->launch_on(r->nee.mode).key & RT_KEY_INTR) ? 1u : 0u;
+    return RT_OK;
+}
+// ... and of the cutout family, whose forms are solid-glass and microfacet forms too: all three queries say 1 of them
+extern "C" int rt_renderer_kernel_cutout(rt_renderer* r, uint32_t* out) {
+    if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_kernel_cutout: null argument");
+    *out = r->variant >= 2 && (r->launch_on(r->nee.mode).key & RT_KEY_CUT) ? 1u : 0u;
     return RT_OK;
 }
 

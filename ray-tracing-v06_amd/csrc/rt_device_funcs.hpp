@@ -526,6 +526,23 @@ RT_HD f3 texture_value(const uint32_t* texels, uint4 rec, float u, float v) {
     return texture_bilinear(texels, rec, u, v);
 }
 
+// Alpha cutouts (rt06.h: rt_scene_set_cutout): whether a candidate hit at parameter t of `ray` on the parallelogram or triangle (Q, u, v, w) is
+// there.  `entry` = the mask's entry of the texture table, `uvs` = the triangle's six texture coordinates (an rt_tri_uvs record) or nullptr for the planar
+// coordinates.  The point, the coordinates and the texel are what the shade phase computes for the same t with the same functions — ray_at, tri_uv or quad_uv,
+// texture_value — so a mask and a colour image over one surface agree texel for texel.  Kept iff !(green < cutoff): a NaN keeps the hit.  Nothing is drawn.
+// The leaf phase of the CUT kernels, the probe and rt_cutout_batch call this one function, and numpy float32 restates it bit for bit.
+RT_HD bool cutout_keeps(const uint32_t* texels, uint4 entry, float cutoff, f3 Q, f3 u, f3 v, f3 w, const float* uvs, const Ray& ray, float t, float& tu, float& tv, f3& c) {
+    const f3 hit_p = ray_at(ray, t);
+    if (uvs) {
+        const float t0[2] = {uvs[0], uvs[1]}, t1[2] = {uvs[2], uvs[3]}, t2[2] = {uvs[4], uvs[5]};
+        tri_uv(Q, u, v, w, t0, t1, t2, hit_p, tu, tv);
+    } else {
+        quad_uv(Q, u, v, w, hit_p, tu, tv);
+    }
+    c = texture_value(texels, entry, tu, tv);
+    return !(c.y < cutoff);
+}
+
 // Normal maps (rt06.h: rt_scene_set_normal_map): a tangent-space map bends the normal the shade phase has.  Two functions: the directions in
 // which a triangle's texture coordinates grow, and the rule.  The tangents are unnormalised and belong to the lookup's (u, v) before the image flip: on a sphere
 // (n.z, 0, -n.x) and (0, 1, 0) (sphere_uv's phi = atan2(-z, x)), on a parallelogram and on a triangle without coordinates the record's u and v, on a triangle

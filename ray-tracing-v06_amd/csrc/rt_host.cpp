@@ -177,6 +177,8 @@ struct rt_scene {
     mutable std::vector<rt_microfacet> mfac_table;
     std::vector<rt_interior> interiors;  // solid glass: likewise
     mutable std::vector<rt_interior> interior_table;
+    std::vector<rt_cutout> cutouts;      // alpha cutouts: likewise
+    mutable std::vector<rt_cutout> cutout_table;
     std::vector<rt_bvh_node> nodes;     // world nodes (BVH or bvh_node tree)
     std::vector<rt_bvh_node> tree_nodes;  // bvh_node objects created by rt_scene_add_bvh_node
     uint32_t kind = RT_WORLD_LIST;
@@ -1113,6 +1115,8 @@ extern "C" int rt_scene_set_interior(rt_scene* s, uint32_t material, const float
     if (s->mats[material].type != RT_MAT_DIELECTRIC) return rt_fail(RT_ERR_INVALID, "rt_scene_set_interior: material %u is no dielectric; only glass has an inside to absorb in", material);
     for (int c = 0; c < 3; c++)
         if (!(std::isfinite(sigma[c]) && sigma[c] >= 0.0f)) return rt_fail(RT_ERR_INVALID, "rt_scene_set_interior: an absorption coefficient must be finite and >= 0");
+    if (material < s->cutouts.size() && s->cutouts[material].on != RT_CUTOUT_OFF)   // §34
+        return rt_fail(RT_ERR_INVALID, "rt_scene_set_interior: material %u has a cutout record, and a holed solid has no inside (rt_scene_clear_cutout first)", material);
     if (s->interiors.size() <= material) s->interiors.resize((size_t)material + 1u, rt_interior{RT_INTERIOR_OFF, {0.0f, 0.0f, 0.0f}});
     s->interiors[material] = rt_interior{RT_INTERIOR_SOLID, {sigma[0] + 0.0f, sigma[1] + 0.0f, sigma[2] + 0.0f}};   // (-0 is stored as 0)
     return RT_OK;
@@ -1133,6 +1137,40 @@ extern "C" int rt_scene_interiors(const rt_scene* s, const rt_interior** out, ui
     s->interior_table = s->interiors;
     s->interior_table.resize(s->mats.size(), rt_interior{RT_INTERIOR_OFF, {0.0f, 0.0f, 0.0f}});
     *out = s->interior_table.data(); *out_n = (uint32_t)s->interior_table.size();
+    return RT_OK;
+}
+
+// ---- alpha cutouts ----
+extern "C" int rt_scene_set_cutout(rt_scene* s, uint32_t material, uint32_t image, float cutoff) {
+    if (!s) return rt_fail(RT_ERR_INVALID, "rt_scene_set_cutout: null scene");
+    if (material >= s->mats.size()) return rt_fail(RT_ERR_INVALID, "rt_scene_set_cutout: the scene has no material %u", material);
+    if (s->mats[material].type == RT_MAT_DIFFUSE_LIGHT)
+        return rt_fail(RT_ERR_INVALID, "rt_scene_set_cutout: material %u is a light, and the light tables take a light's whole area as emitting", material);
+    if (s->mats[material].type == RT_MAT_ISOTROPIC) return rt_fail(RT_ERR_INVALID, "rt_scene_set_cutout: material %u is a medium, which has no surface to cut", material);
+    if (material < s->interiors.size() && s->interiors[material].on != RT_INTERIOR_OFF)
+        return rt_fail(RT_ERR_INVALID, "rt_scene_set_cutout: material %u has an interior record, and a holed solid has no inside (rt_scene_clear_interior first)", material);
+    if (image >= RT_MAX_IMAGES) return rt_fail(RT_ERR_INVALID, "rt_scene_set_cutout: an image index lies in [0, %u)", RT_MAX_IMAGES);
+    if (!(std::isfinite(cutoff) && cutoff >= 0.0f && cutoff <= 1.0f)) return rt_fail(RT_ERR_INVALID, "rt_scene_set_cutout: a cutoff must be finite and in [0, 1]");
+    if (s->cutouts.size() <= material) s->cutouts.resize((size_t)material + 1u, rt_cutout{RT_CUTOUT_OFF, 0u, 0.0f, 0u});
+    s->cutouts[material] = rt_cutout{RT_CUTOUT_MASKED, image, cutoff + 0.0f, 0u};   // (-0 is stored as 0)
+    return RT_OK;
+}
+extern "C" int rt_scene_clear_cutout(rt_scene* s, uint32_t material) {
+    if (!s) return rt_fail(RT_ERR_INVALID, "rt_scene_clear_cutout: null scene");
+    if (material >= s->mats.size()) return rt_fail(RT_ERR_INVALID, "rt_scene_clear_cutout: the scene has no material %u", material);
+    if (material < s->cutouts.size()) s->cutouts[material] = rt_cutout{RT_CUTOUT_OFF, 0u, 0.0f, 0u};
+    return RT_OK;
+}
+extern "C" int rt_scene_cutouts(const rt_scene* s, const rt_cutout** out, uint32_t* out_n) {
+    if (!s || !out || !out_n) return rt_fail(RT_ERR_INVALID, "rt_scene_cutouts: null argument");
+    *out = nullptr; *out_n = 0u;
+    s->cutout_table.clear();
+    bool any = false;
+    for (const rt_cutout& m : s->cutouts) any = any || m.on != RT_CUTOUT_OFF;
+    if (!any) return RT_OK;
+    s->cutout_table = s->cutouts;
+    s->cutout_table.resize(s->mats.size(), rt_cutout{RT_CUTOUT_OFF, 0u, 0.0f, 0u});
+    *out = s->cutout_table.data(); *out_n = (uint32_t)s->cutout_table.size();
     return RT_OK;
 }
 

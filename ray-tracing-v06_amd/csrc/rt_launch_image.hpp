@@ -43,6 +43,7 @@ template <typename Texture> struct Riders {
     const void* normal_maps = nullptr; size_t n_normal_maps = 0;   // §28: 16 bytes (on, image, strength bits, -) per material; read only beside a texture table
     const void* microfacets = nullptr; size_t n_microfacets = 0;   // §29: 16 bytes (on, image, roughness bits, specular bits) per material; needs no texture table
     const void* interiors = nullptr; size_t n_interiors = 0;       // §32: 16 bytes (on, sigma bits x 3) per material; needs neither table
+    const void* cutouts = nullptr; size_t n_cutouts = 0;           // §34: 16 bytes (on, image, cutoff bits, -) per material; read only beside a texture table
 };
 
 // The tail, appended to `out`: a header (normals follow ? 1 : 0, vec4 from the header to the coordinates or 0, ... to the environment record or 0, ... to the
@@ -56,6 +57,9 @@ template <typename Texture> struct Riders {
 // Interior records (§32): with a table of them the first lane's upper bits count the vec4 to ONE sub-header (vec4 from the header to the microfacet records or 0,
 // vec4 from the header to the interior records, -, -), and both tables lie behind it, the microfacet records first.  Only the INTR forms launch on such a tail, and
 // they know by template that the sub-header is there; without an interior table the tail is byte for byte what it was.
+// Cutout records (§34) lie behind the interior records, and the sub-header's third lane counts the vec4 from the header to them (0 = none).  The sub-header is
+// there when there is an interior table or a cutout table; with cutouts alone its second lane is 0.  Only the CUT forms launch on a tail with cutout records;
+// without them the tail is byte for byte what it was.
 // With everything off it is one zero vec4: the header every kernel reads.
 template <typename Texture> inline void append_tail(std::vector<Vec4>& out, const Riders<Texture>& r) {
     const size_t at = out.size();
@@ -66,9 +70,11 @@ template <typename Texture> inline void append_tail(std::vector<Vec4>& out, cons
     const bool mfacs = r.microfacets && r.n_microfacets;
     const size_t mf_at = tex_at + (r.textures ? 1u + r.n_textures : 0u) + (nmaps ? r.n_normal_maps : 0u);
     const bool intrs = r.interiors && r.n_interiors;
-    const size_t sub_at = mf_at, mf_rec_at = sub_at + (intrs ? 1u : 0u), in_at = mf_rec_at + (mfacs ? r.n_microfacets : 0u);
-    out.resize(at + in_at + (intrs ? r.n_interiors : 0u), Vec4{0u, 0u, 0u, 0u});
-    out[at] = Vec4{(r.normals ? 1u : 0u) | (mfacs || intrs ? (uint32_t)sub_at << 1 : 0u), r.coords ? (uint32_t)uv_at : 0u, r.env ? (uint32_t)env_at : 0u, r.textures ? (uint32_t)tex_at : 0u};
+    const bool cuts = r.cutouts && r.n_cutouts;
+    const bool sub = intrs || cuts;
+    const size_t sub_at = mf_at, mf_rec_at = sub_at + (sub ? 1u : 0u), in_at = mf_rec_at + (mfacs ? r.n_microfacets : 0u), cut_at = in_at + (intrs ? r.n_interiors : 0u);
+    out.resize(at + cut_at + (cuts ? r.n_cutouts : 0u), Vec4{0u, 0u, 0u, 0u});
+    out[at] = Vec4{(r.normals ? 1u : 0u) | (mfacs || sub ? (uint32_t)sub_at << 1 : 0u), r.coords ? (uint32_t)uv_at : 0u, r.env ? (uint32_t)env_at : 0u, r.textures ? (uint32_t)tex_at : 0u};
     if (r.normals) std::memcpy(&out[at + 1u], r.normals, r.n_normal_floats * sizeof(float));
     if (r.coords) std::memcpy(&out[at + uv_at], r.coords, r.n_coord_floats * sizeof(float));
     if (r.env) {
@@ -82,10 +88,9 @@ template <typename Texture> inline void append_tail(std::vector<Vec4>& out, cons
             out[at + tex_at + 1u + k] = Vec4{r.texture[k].width, r.texture[k].height, r.texture[k].wrap | r.texture[k].filter << 8, r.texture[k].first};
     }
     if (mfacs) std::memcpy(&out[at + mf_rec_at], r.microfacets, r.n_microfacets * 16u);
-    if (intrs) {
-        out[at + sub_at] = Vec4{mfacs ? (uint32_t)mf_rec_at : 0u, (uint32_t)in_at, 0u, 0u};
-        std::memcpy(&out[at + in_at], r.interiors, r.n_interiors * 16u);
-    }
+    if (sub) out[at + sub_at] = Vec4{mfacs ? (uint32_t)mf_rec_at : 0u, intrs ? (uint32_t)in_at : 0u, cuts ? (uint32_t)cut_at : 0u, 0u};
+    if (intrs) std::memcpy(&out[at + in_at], r.interiors, r.n_interiors * 16u);
+    if (cuts) std::memcpy(&out[at + cut_at], r.cutouts, r.n_cutouts * 16u);
 }
 
 }   // namespace rt_image

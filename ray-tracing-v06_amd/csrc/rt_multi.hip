@@ -346,6 +346,20 @@ extern "C" int rt_multi_renderer_interiors(rt_multi_renderer* m, const rt_interi
     return RT_OK;
 }
 
+extern "C" int rt_multi_renderer_cutouts(rt_multi_renderer* m, const rt_cutout* table, uint32_t n) {
+    if (!m) return rt_fail(RT_ERR_INVALID, "rt_multi_renderer_cutouts: null renderer");
+    for (rt_renderer* r : m->parts) {   // every rank holds the same world: the first refuses what any would, before any part changes
+        const int rc = rt_renderer_cutouts(r, table, n);
+        if (rc != RT_OK) return rc;
+    }
+    return RT_OK;
+}
+
+extern "C" int rt_multi_renderer_cutouts_info(rt_multi_renderer* m, uint32_t out[2]) {
+    if (!m || !out) return rt_fail(RT_ERR_INVALID, "rt_multi_renderer_cutouts_info: null argument");
+    return rt_renderer_cutouts_info(m->parts[0], out);
+}
+
 extern "C" int rt_multi_renderer_download(rt_multi_renderer* m, float* host_rgba, size_t n_floats) {
     if (!m || !host_rgba) return rt_fail(RT_ERR_INVALID, "rt_multi_renderer_download: null argument");
     const size_t need = (size_t)m->width * m->height * 4;

@@ -531,6 +531,65 @@ extern "C" int rt_normal_map_batch(const rt_texture* records, uint32_t n, const 
     }
     return RT_OK;
 }
+// Alpha cutouts: cutout_keeps over arrays of cases, on the device and — HOST (no GPU) — here.  A case whose material's record is off keeps its hit
+// without a lookup, as the leaf phase does; its (u, v) and value read as zeros.
+RT_HD void cutout_case(size_t i, const uint32_t* texels, const uint4* entries, const rt_quad* quads, const rt_tri_uvs* uv, const float* rays, const float* t,
+                       const rt_cutout* records, const uint32_t* material, uint32_t* out_keep, float* out_uv, float* out_value) {
+    const rt_cutout rec = records[material[i]];
+    float tu = 0.0f, tv = 0.0f;
+    f3 c = mk3(0.0f);
+    bool keep = true;
+    if (rec.on != RT_CUTOUT_OFF) {
+        Ray r;
+        r.o = ld3(rays + 6 * i); r.d = ld3(rays + 6 * i + 3); r.time = 0.0f;
+        keep = cutout_keeps(texels, entries[rec.image], rec.cutoff, ld3(quads[i].Q), ld3(quads[i].u), ld3(quads[i].v), ld3(quads[i].w), uv ? uv[i].t0 : nullptr, r, t[i], tu, tv, c);
+    }
+    out_keep[i] = keep ? 1u : 0u; out_uv[2 * i] = tu; out_uv[2 * i + 1] = tv; out_value[i] = c.y;
+}
+__global__ void probe_cutout_kernel(size_t count, const uint32_t* texels, const uint4* entries, const rt_quad* quads, const rt_tri_uvs* uv, const float* rays, const float* t,
+                                    const rt_cutout* records, const uint32_t* material, uint32_t* out_keep, float* out_uv, float* out_value) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    cutout_case(i, texels, entries, quads, uv, rays, t, records, material, out_keep, out_uv, out_value);
+}
+static int cutout_args(const char* who, const rt_texture* textures, uint32_t n_textures, const uint8_t* texels, size_t count, const rt_quad* quads, const float* rays,
+                       const float* t, const rt_cutout* records, uint32_t n_records, const uint32_t* material, uint32_t* out_keep, float* out_uv, float* out_value,
+                       TextureTable& tab) {
+    if (const int rc = texture_table_args(who, textures, n_textures, texels, nullptr, nullptr, nullptr, 0, nullptr, tab)) return rc;
+    if (count && (!quads || !rays || !t || !records || !material || !out_keep || !out_uv || !out_value)) return rt_fail(RT_ERR_INVALID, "%s: null argument", who);
+    for (uint32_t k = 0; k < n_records; k++) {
+        if (records[k].on == RT_CUTOUT_OFF) continue;
+        if (records[k].on != RT_CUTOUT_MASKED) return rt_fail(RT_ERR_INVALID, "%s: record %u: on is 0 (off) or 1 (masked), not %u", who, k, records[k].on);
+        if (records[k].image >= n_textures || textures[records[k].image].width == 0u) return rt_fail(RT_ERR_INVALID, "%s: record %u: the table has no entry %u", who, k, records[k].image);
+        if (!(std::isfinite(records[k].cutoff) && records[k].cutoff >= 0.0f && records[k].cutoff <= 1.0f)) return rt_fail(RT_ERR_INVALID, "%s: record %u: a cutoff must be finite and in [0, 1]", who, k);
+    }
+    for (size_t i = 0; i < count; i++)
+        if (material[i] >= n_records) return rt_fail(RT_ERR_INVALID, "%s: case %zu: there is no record %u", who, i, material[i]);
+    return RT_OK;
+}
+extern "C" int rt_probe_cutout(int device, const rt_texture* textures, uint32_t n_textures, const uint8_t* texels, size_t count, const rt_quad* quads, const rt_tri_uvs* uv,
+                               const float* rays, const float* t, const rt_cutout* records, uint32_t n_records, const uint32_t* material, uint32_t* out_keep, float* out_uv,
+                               float* out_value) {
+    TextureTable tab;
+    if (const int rc = cutout_args("rt_probe_cutout", textures, n_textures, texels, count, quads, rays, t, records, n_records, material, out_keep, out_uv, out_value, tab)) return rc;
+    if (count == 0) return RT_OK;
+    ProbeRun p(device);
+    auto dw = p.in(tab.dwords.data(), tab.dwords.size());
+    auto en = p.in(tab.entries.data(), tab.entries.size());
+    auto dq = p.in(quads, count);
+    const rt_tri_uvs* du = uv ? p.in(uv, count) : nullptr;
+    auto dr = p.in(rays, 6 * count); auto dt = p.in(t, count); auto dc = p.in(records, n_records); auto dm = p.in(material, count);
+    auto ok = p.out(out_keep, count); auto ouv = p.out(out_uv, 2 * count); auto ov = p.out(out_value, count);
+    p.launch(probe_cutout_kernel, p.per_case(count), 128, count, dw, en, dq, du, dr, dt, dc, dm, ok, ouv, ov);
+    return p.finish();
+}
+extern "C" int rt_cutout_batch(const rt_texture* textures, uint32_t n_textures, const uint8_t* texels, size_t count, const rt_quad* quads, const rt_tri_uvs* uv, const float* rays,
+                               const float* t, const rt_cutout* records, uint32_t n_records, const uint32_t* material, uint32_t* out_keep, float* out_uv, float* out_value) {
+    TextureTable tab;
+    if (const int rc = cutout_args("rt_cutout_batch", textures, n_textures, texels, count, quads, rays, t, records, n_records, material, out_keep, out_uv, out_value, tab)) return rc;
+    for (size_t i = 0; i < count; i++) cutout_case(i, tab.dwords.data(), tab.entries.data(), quads, uv, rays, t, records, material, out_keep, out_uv, out_value);
+    return RT_OK;
+}
 // The marble: the kernels' noise_value() over arrays, on the device and — HOST (no GPU) — here
 extern "C" int rt_probe_noise_value(int device, const rt_perlin* perlin, const float albedo[3], float scale, const float* points, size_t n, float* out_rgb) {
     if (!perlin || !albedo || !points || !out_rgb) return rt_fail(RT_ERR_INVALID, "rt_probe_noise_value: null argument");

@@ -273,11 +273,15 @@ __device__ __forceinline__ f3 texture_table_value(const uint4* tt, uint32_t imag
 // INTR (rt_renderer_interiors; MFAC only): a dielectric hit whose material has an interior record takes its facing on a parallelogram or triangle
 //      from the stored normal — the comparison set_face_normal makes, kept as q_back — and a back hit scales the albedo by interior_hit's transmittance before
 //      the smooth or rough rule runs.  The tail's first lane then counts the vec4 to a sub-header (to the microfacet records or 0, to the interior records, -, -).
+// CUT (rt_renderer_cutouts; INTR only): in the leaf phase a parallelogram or triangle that passes its test, on a material whose cutout record is
+//      on, is taken only if cutout_keeps says so — the mask's texel at the candidate's own (u, v), the first texture lookup inside the traversal.  A candidate
+//      turned down leaves rec_t and rec_code alone, and the lane goes on as after a failed test.  The records lie behind the interior records; the sub-header's
+//      third lane says where, and its second lane is 0 when there is no interior table.  Spheres ignore the record.  Nothing is drawn.
 // LTREE && ENVL (mode RT_LIGHT_SAMPLING_ENV_TREE): both at once.  The light half tosses once more between the map and mode 16's table (no toss
 //      when the table is empty: n_l == 0 is the map alone), the light density is the mean of the map's and the walk's, and an image-textured Lambertian hit is
 //      sampled as the diffuse hit it is — its albedo is looked up behind the direction, as ever.
 template <bool EXACT, bool FILTER, int BLOCK, int WORLD = RT_WORLD_BVH, int EXT = 0, bool BIG = false, bool WIDE = BIG, bool TOL = false, bool NEE = false, bool TRI = false,
-          bool LTREE = false, bool ENVL = false, bool INTR = false, bool MFAC = false, bool NMAP = false>
+          bool LTREE = false, bool ENVL = false, bool CUT = false, bool INTR = false, bool MFAC = false, bool NMAP = false>
 // (the second launch bound is hipcc's minimum of waves per SIMD — 6 for 768 threads, what two workgroups per CU are, and all the LDS admits: the register budget is
 //  80, not the 64 of a full SIMD.  The default instantiation took 64 while it needed no more and takes 68 since E23, with no scratch; the occupancy the compiler
 //  reports for it, 8 and now 7, is what its register count would admit, not what the launch gets.)
@@ -285,6 +289,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
     static_assert(!NMAP || (EXT == 2 && TRI), "normal maps: one family of the kernels that read the texture table, plain and with mode 48");
     static_assert(!MFAC || NMAP, "microfacet surfaces: a glossy asset wants its normal map in the same launch, and the roughness map shares the map's (u, v)");
     static_assert(!INTR || MFAC, "solid glass: one family, the microfacet forms once more, so that a frosted solid is entered and left in the same launch");
+    static_assert(!CUT || INTR, "alpha cutouts: one family, the solid-glass forms once more, so that one launch serves an asset with every kind of record");
     static_assert(!NEE || (EXT >= 1 && WORLD != RT_WORLD_BVH_QUEUE), "light sampling: worlds with quads, walked by the stack or as a list");
     static_assert(!TRI || (EXT >= 1 && WORLD != RT_WORLD_BVH_QUEUE), "triangles: worlds with quads; a lane walk reads the kind from the flat record");
     static_assert(!LTREE || (NEE && TRI), "the light tree: one family, which knows all three kinds of light");
@@ -592,8 +597,37 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void render_kernel_stream(Strea
                         const uint32_t quad_kind = TRI && (code - first_quad) >= p.scene.n_plain_quads ? RT_QUAD_TRIANGLE : RT_QUAD_PARALLELOGRAM;
                         if (quad_closest_intersection(mk3(a0.x, a0.y, a0.z), a0.w, mk3(a1.x, a1.y, a1.z), mk3(a1.w, a2.x, a2.y),
                                                       mk3(a2.z, a2.w, a3.x), mk3(a3.y, a3.z, a3.w), 0u, 0, quad_kind, ray, tmp)) {
-                            rec_t = tmp.distance;
-                            rec_code = (int32_t)(code - first_quad + p.scene.sphere_codes);   // the shade phase's code space
+                            [[maybe_unused]] bool keep = true;
+                            if constexpr (CUT) {
+                                // §34: the cutout record of the candidate's material, (on, image, cutoff bits, -), read here alone; the offsets and the texture
+                                // table's header are the same for every lane and are read through scalars where they are used, none of them kept across the loop
+                                const uint32_t qi = code - first_quad;
+                                const uint32_t cut_mat = __float_as_uint(quads[p.scene.n_quads * 4u + qi].w) & RT_MAT_INDEX_MASK;
+                                uint4 cut_rec = make_uint4(0u, 0u, 0u, 0u);
+                                const uint32_t sub_at = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.scene.blob[p.scene.blob_vec4].x) >> 1;
+                                if (sub_at != 0u) {
+                                    const uint32_t cut_at = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.scene.blob[p.scene.blob_vec4 + sub_at].z);
+                                    if (cut_at != 0u) cut_rec = p.scene.blob[p.scene.blob_vec4 + cut_at + cut_mat];
+                                }
+                                const uint32_t tex_here = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.scene.blob[p.scene.blob_vec4].w);
+                                if (cut_rec.x != 0u && tex_here != 0u) {   // (the host launches no record without its table entry)
+                                    const uint4* tt = p.scene.blob + p.scene.blob_vec4 + tex_here;
+                                    const uint4 th = tt[0];
+                                    const uint64_t texels = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)th.x) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)th.y) << 32;
+                                    const uint32_t uv_here = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.scene.blob[p.scene.blob_vec4].y);
+                                    const float* tr = nullptr;   // §22: a triangle under a table of texture coordinates weighs its vertices' (u, v), as the shade phase will
+                                    if (uv_here != 0u && qi >= p.scene.n_plain_quads)
+                                        tr = reinterpret_cast<const float*>(p.scene.blob + p.scene.blob_vec4 + uv_here) + (size_t)(qi - p.scene.n_plain_quads) * 6u;
+                                    float cut_u, cut_v;
+                                    f3 cut_c;
+                                    keep = cutout_keeps(reinterpret_cast<const uint32_t*>(texels), tt[1u + cut_rec.y], __uint_as_float(cut_rec.z), mk3(a0.x, a0.y, a0.z),
+                                                        mk3(a1.x, a1.y, a1.z), mk3(a1.w, a2.x, a2.y), mk3(a3.y, a3.z, a3.w), tr, ray, tmp.distance, cut_u, cut_v, cut_c);
+                                }
+                            }
+                            if (!CUT || keep) {
+                                rec_t = tmp.distance;
+                                rec_code = (int32_t)(code - first_quad + p.scene.sphere_codes);   // the shade phase's code space
+                            }
                         }
                         if (WORLD == RT_WORLD_LIST) {  // HittableList.cuh:26-30: every object, in order (the quads follow the spheres)
                             if (code + 1u < p.scene.n_prims + p.scene.n_quads) cur = K::LEAF | (code + 1u);

@@ -80,6 +80,31 @@ def read_ppm(path):
 
 def read_png(path):
     """An 8-bit RGB or RGBA PNG without interlacing (alpha dropped) -> uint8 [H][W][3]; all five filter types."""
+    return np.ascontiguousarray(_png_pixels(path)[:, :, :3])
+
+
+def read_png_alpha(path):
+    """The alpha channel of an 8-bit RGBA PNG (as read_png reads it) -> uint8 [H][W], row 0 = top; None for an RGB file, which has none.  What a cutout mask
+    is made of: np.repeat(alpha[:, :, None], 3, axis=2) is an image whose every channel is the opacity."""
+    px = _png_pixels(path)
+    return np.ascontiguousarray(px[:, :, 3]) if px.shape[2] == 4 else None
+
+
+def lattice_mask(width, height, bars_u, bars_v, duty):
+    """A procedural fence for cutouts: uint8 [height][width][3], 255 on bars_u vertical and bars_v horizontal bars spread evenly over the image,
+    0 in the holes between them; `duty` in [0, 1] = the part of each period a bar covers.  Integer arithmetic on texel centres: the same on every machine."""
+    width, height, bars_u, bars_v = int(width), int(height), int(bars_u), int(bars_v)
+    if width <= 0 or height <= 0 or bars_u < 0 or bars_v < 0 or not (0.0 <= float(duty) <= 1.0):
+        raise ValueError("lattice_mask: a positive size, bar counts >= 0 and a duty in [0, 1]")
+    def bars(n, count):   # texel i is on a bar when the phase of its centre within its period, in units of 1 / (2 n), lies below duty
+        phase = ((2 * np.arange(n, dtype=np.int64) + 1) * count) % (2 * n)
+        return phase < int(round(float(duty) * 2 * n)) if count else np.zeros(n, bool)
+    on = bars(width, bars_u)[None, :] | bars(height, bars_v)[:, None]
+    return np.ascontiguousarray(np.repeat((on * np.uint8(255))[:, :, None], 3, axis=2).astype(np.uint8))
+
+
+def _png_pixels(path):
+    """read_png's decoder: uint8 [H][W][3 or 4]"""
     with open(path, "rb") as f:
         data = f.read()
     if data[:8] != b"\x89PNG\r\n\x1a\n":
@@ -136,7 +161,7 @@ def read_png(path):
             raise ValueError(f"{path}: row {y}: unknown filter type {kind}")
         out[y] = cur
         prev = cur
-    return np.ascontiguousarray(out.reshape(h, w, bpp)[:, :, :3])
+    return out.reshape(h, w, bpp)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -176,7 +176,8 @@ def load_mtl(path):
     "roughness": float | None, "roughness_map": path | None and "metallic": float | None.  The keywords glass is told by add keys of their own, each
     present only when the file has the keyword: `Ni` as "ior" (> 0), `d` and `Tr` as "dissolve" in [0, 1] (Tr = 1 - d), `illum` as "illum" (an integer).  `Tf r g b` (or `Tf r`), the
     transmission filter (the tint of solid glass), likewise: "transmission_filter": (r, g, b), each finite and in [0, 1]; its `spectral` and `xyz`
-    forms are not read.  Nothing else of MTL is read."""
+    forms are not read.  `map_d` (the opacity image of an alpha cutout) likewise: "cutout_map": path, resolved beside the file, options in front of
+    the name skipped.  Nothing else of MTL is read."""
     import os
     out, current = {}, None
     beside = lambda name: os.path.join(os.path.dirname(os.path.abspath(path)), *name.replace("\\", "/").split("/"))
@@ -237,6 +238,12 @@ def load_mtl(path):
                         if not (np.isfinite(value) and 0.0 <= value <= 1.0):
                             raise ValueError(f"{where}: {parts[0]} must be finite and in [0, 1]")
                         current["dissolve"] = value if parts[0] == "d" else 1.0 - value
+            elif parts[0] == "map_d":   # §34: the opacity image of a cutout material; options in front of the name (-imfchan, -s, ...) are skipped
+                if current is None:
+                    raise ValueError(f"{where}: map_d before any newmtl")
+                if len(parts) < 2:
+                    raise ValueError(f"{where}: map_d needs a file name")
+                current["cutout_map"] = beside(parts[-1])
             elif parts[0] == "Tf":
                 if current is None:
                     raise ValueError(f"{where}: Tf before any newmtl")

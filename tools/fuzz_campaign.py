@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Differential fuzz campaign: random worlds (spheres, moving spheres, quads, triangles and meshes, lights, media, textures; every builder; LDS
 and global-memory paths; three cameras) rendered on the GPU and by the CPU oracle, compared bit for bit.
-    python tools/fuzz_campaign.py --seeds 200 [--first 0] [--no-triangles] [--mesh-lights] [--light-tree] [--texture-coords] [--textures] [--env-tree] [--surfaces [--live]] [--interiors]
+    python tools/fuzz_campaign.py --seeds 200 [--first 0] [--no-triangles] [--mesh-lights] [--light-tree] [--texture-coords] [--textures] [--env-tree] [--surfaces [--live]] [--interiors] [--cutouts]
 Prints one line per failure and a summary; exit code 1 if anything differed.  The triangles of a world come from a generator of their own, so the rest of a seed's
 world is what it was before the fuzzer made triangles, and --no-triangles renders exactly those earlier worlds.  Importing this file starts nothing:
 world_of_seed() builds a seed's world on the host, without a device.  --mesh-lights (off by default: the recorded campaigns ran without it) also renders every
@@ -14,7 +14,10 @@ microfacet tables of tests/_surface_worlds.py — on a second scene built from t
 kernel families, in both memory forms, to the oracle's frame the campaign has computed.  --interiors builds the seed's world once more with
 glass solids in it — a sphere, a box and a closed mesh, placed, sized and given random interior records by a generator of its own — and holds the INTR family to
 itself (both memory forms; every record off against no table); and, per seed, it renders a second world of static spheres, parallelograms and triangles with such
-solids, built so that tests/_interior_twin.py follows its every sample, and holds both memory forms to the twin on every pixel."""
+solids, built so that tests/_interior_twin.py follows its every sample, and holds both memory forms to the twin on every pixel.  --cutouts
+renders, per seed, such a second world without the solids, with random masks — lattices and random opacities under random wrap modes, filters and cutoffs — on
+random materials of its parallelograms and triangles, half the time with random texture coordinates on a mesh, and holds both memory forms of the CUT family to
+the walk of tests/_cutout_twin.py on every pixel; with every record off the frame must be the frame without a table."""
 import argparse, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -48,6 +51,8 @@ def parse_args(argv=None):
     ap.add_argument("--texture-coords", action="store_true", help="also render the worlds with an image and triangles under a table of random texture coordinates on random triangles: both memory forms must agree, and the identity table must be the oracle's frame")
     ap.add_argument("--surfaces", action="store_true", help="also render every world under inert normal-map and microfacet tables (flat maps; records that are all off on the materials in use): the NMAP and the MFAC kernel family, both memory forms, must give the oracle's frame; worlds the families refuse (a lane walk, a kernel variant other than 2 and 3) are counted as skipped")
     ap.add_argument("--live", action="store_true", help="with --surfaces: also render, per seed, a world of tests/_surface_worlds.random_surface_world(seed, live=True) — live normal-map, microfacet, rough-glass and interior records beside a constant medium, a noise material and moving spheres under a random camera kind — in both memory forms against the extended whole-sample twin, which must follow every sample; lane walks and kernel variants other than 2 and 3 are counted as skipped")
+    ap.add_argument("--cutouts", action="store_true", help="also render, per seed, a world of its own with random masks on random parallelogram and triangle materials: the CUT kernel family in both memory forms against "
+                    "the twin's walk (tests/_cutout_twin.py), every record off against no table")
     ap.add_argument("--interiors", action="store_true", help="also render every stack-walked or list world with random glass solids under random interior records: the INTR kernel family in both memory forms, every record off "
                     "against no table, and the twin (tests/_interior_twin.py) where it follows")
     return ap.parse_args(argv)
@@ -421,6 +426,89 @@ def interiors_twin_world(p, seed):
     return s, cam, W, H, int(rng.integers(1, 9)), int(rng.choice([2, 5, 8, 50]))
 
 
+def cutouts_twin_world(p, seed):
+    """(scene, pinhole camera, W, H, spp, depth) of a world the walk of tests/_cutout_twin.py follows throughout: static spheres, parallelograms, free triangles
+    and a mesh (half the time with texture coordinates wider than the unit square) of Lambertian, metal, glass and — half the time — light materials, with one to
+    three masks on random materials that take one"""
+    from ray_tracing_v06_amd import image_io, mesh_io
+    rng = np.random.default_rng(seed + (34 << 20))
+    s = p.Scene()
+    mats = [s.Lambertian(rng.random(3)), s.Metal(rng.random(3), float(rng.choice([0.0, 0.1, 0.7]))), s.Dielectric((1, 1, 1), float(rng.choice([1.5, 1.33]))),
+            s.Lambertian(rng.random(3)), s.LambertianTexture(rng.random(3), rng.random(3), float(rng.uniform(0.5, 3.0)))]
+    maskable = list(mats)
+    if rng.random() < 0.5:
+        mats.append(s.DiffuseLight(rng.random(3) * float(rng.choice([2.0, 8.0]))))
+    pick = lambda: mats[int(rng.integers(0, len(mats)))]   # noqa: E731
+    for _ in range(int(rng.integers(1, 8))):
+        s.MakeSphere(((rng.random(3) * 2 - 1) * np.array([6, 2, 6])).astype(np.float32), float(rng.choice([0.3, 0.8, 2.5])), pick())
+    for _ in range(int(rng.integers(2, 9))):
+        Q = ((rng.random(3) * 2 - 1) * np.array([6, 3, 6])).astype(np.float32)
+        s.MakeQuad(Q, (rng.standard_normal(3) * 3).astype(np.float32), (rng.standard_normal(3) * 3).astype(np.float32), pick())
+    for _ in range(int(rng.integers(1, 6))):
+        a = ((rng.random(3) * 2 - 1) * np.array([6, 3, 6])).astype(np.float32)
+        s.MakeTriangle(a, a + (rng.standard_normal(3) * 3).astype(np.float32), a + (rng.standard_normal(3) * 3).astype(np.float32), pick())
+    v, f = mesh_io.icosphere(int(rng.integers(0, 2)))
+    s.MakeMesh(v, f, pick(), float(rng.uniform(0.8, 2.5)), float(rng.uniform(0, 90)), (rng.random(3) * 2 - 1) * (4, 1, 4),
+               **(dict(uvs=(rng.random((len(v), 2)) * 2 - 0.5).astype(np.float32)) if rng.random() < 0.5 else {}))
+    if rng.random() < 0.5:
+        s.MakeSphere((0, -500.0, 0), 498.0, mats[0])
+    if rng.random() < 0.6:
+        s.set_background(tuple(float(x) for x in rng.random(3)))
+    for _ in range(int(rng.integers(1, 4))):
+        if rng.random() < 0.5:
+            mask = image_io.lattice_mask(int(rng.integers(1, 33)), int(rng.integers(1, 33)), int(rng.integers(0, 6)), int(rng.integers(0, 6)), float(rng.random()))
+        else:
+            mask = np.repeat(rng.integers(0, 256, (int(rng.integers(1, 9)), int(rng.integers(1, 9)), 1)).astype(np.uint8), 3, axis=2)
+        image = s.add_image(mask, wrap=str(rng.choice(["clamp", "repeat"])), filter=str(rng.choice(["nearest", "bilinear"])))
+        s.set_cutout(maskable[int(rng.integers(0, len(maskable)))], image, float(rng.choice([0.0, 0.25, 0.5, 0.75, 1.0, rng.random()])))
+    [s.BuildBVH_TopDown, s.BuildBVH_SAH, s.BuildBVH_BottomUp, s.MakeHittableList][int(rng.integers(0, 4))]()
+    W, H = int(rng.integers(17, 49)), int(rng.integers(9, 33))
+    eye = ((rng.random(3) * 2 - 1) * np.array([9, 4, 9])).astype(np.float32)
+    cam = p.PinholeCamera(eye, (0, 0, 0), (0, 1, 0), float(rng.uniform(20, 100)), W / H)
+    return s, cam, W, H, int(rng.integers(1, 9)), int(rng.choice([2, 5, 8, 50]))
+
+
+def cutouts_twin_check(p, seed):
+    """cutouts_twin_world(seed) on the GPU, in the renderer's own form and the global-memory form, against the twin's walk under the rule: the sums of every
+    pixel must be the twin's, the twin must follow every sample (the world is built so), and with every record off the frame must be the frame without a
+    table.  (ok, forms, pixels held, candidates the rule turned down)"""
+    import _cutout_twin as CT
+    import _cutout_worlds as CW
+    import _path_twin as PT
+    s, cam, W, H, spp, depth = cutouts_twin_world(p, seed)
+    w, table = s.getWorldPtr(), s.cutouts()
+    world = as_oracle_world(w)
+    uv = s.texture_coords()
+    uv = uv if uv is not None and len(uv) else None
+    images = CW.twin_table(s)
+    stats = CT.new_stats()
+    trace = CT.walk_of(uv, table, images, stats)
+    samples, followed = PT.frame_samples(lambda g, k: PT.radiance(world, as_oracle_camera(cam), W, H, depth, 1984, g, k, trace, sky=PT.own_sky(world), tex=(uv, images),
+                                                                 glass=True), W, H, spp)
+    want = VT.in_order_sums(samples)
+    ok, forms = bool(followed.all()), []
+    for env in ({}, {"RT06_FORCE_BIG": "1"}):
+        os.environ.pop("RT06_FORCE_BIG", None)
+        os.environ.update(env)
+        try:
+            r = p.Renderer.MakeRenderer(W, H, spp, depth, cam, w, variant=0)
+        finally:
+            os.environ.pop("RT06_FORCE_BIG", None)
+        ok = ok and r.kernel_cutout()
+        forms.append(r.kernel_form())
+        r.refine(spp)
+        ok = ok and bits_equal(r.refine_sums(), want)
+        if env:
+            r.cutouts(np.zeros(len(table), p.capi.CUTOUT_DT))
+            r.refine(spp)
+            off = r.refine_sums()
+            r.cutouts(None)
+            r.refine(spp)
+            ok = ok and bits_equal(off, r.refine_sums())
+        r.close()
+    return ok, forms, W * H, stats["rejected"]
+
+
 def interiors_twin_check(p, seed):
     """interiors_twin_world(seed) on the GPU, in the renderer's own form and the global-memory form, against the twin under the whole rule: the sums of every
     pixel must be the twin's, and the twin must follow every sample (the world is built so).  (ok, forms, pixels held)"""
@@ -597,6 +685,14 @@ def main(argv=None):
             if not tw[0]:
                 fails += 1
                 print(f"FAIL seed {seed}: the solid-glass twin world: forms {tw[1]}", flush=True)
+        if args.cutouts:   # likewise
+            tw = cutouts_twin_check(p, seed)
+            stats["cutout_twin_worlds"] = stats.get("cutout_twin_worlds", 0) + 1
+            stats["cutout_pixels_held_to_the_twin"] = stats.get("cutout_pixels_held_to_the_twin", 0) + tw[2]
+            stats["cutout_candidates_turned_down"] = stats.get("cutout_candidates_turned_down", 0) + tw[3]
+            if not tw[0]:
+                fails += 1
+                print(f"FAIL seed {seed}: the cutout twin world: forms {tw[1]}", flush=True)
         if args.env_tree and ok and kinds >= 1 and info["variant"] in (2, 3) and not (big and builder == 3):   # last: it changes the scene's background
             et = env_tree_check(p, s, cam, ck, W, H, depth, variant)
             if et is not None:

@@ -97,6 +97,8 @@ ap.add_argument("--texture", default=None, action="append", metavar="FILE.ppm|FI
 ap.add_argument("--mtl", action="store_true", help="with --mesh FILE.obj: one mesh per `usemtl` group, each with the image its material's map_Kd names (mtllib files beside the "
                     "OBJ; DESIGN.md §25) or a Lambertian of its Kd; a group without either takes --mesh-material")
 ap.add_argument("--rough-glass", type=float, default=None, metavar="R", help="with --mesh-material glass: frost the glass, a GGX roughness in [0, 1] (DESIGN.md §30)")
+ap.add_argument("--cutout-cutoff", type=float, default=0.5, metavar="X", help="with --mesh FILE.obj --mtl: a group whose material has a map_d, or an RGBA map_Kd, is there where the "
+                "mask is not below X (alpha cutouts, DESIGN.md §34; default 0.5)")
 ap.add_argument("--solid-glass", action="store_true", help="with --mesh: the transparent --mtl groups, or the prefab glass of --mesh-material, are solid glass (DESIGN.md §32): they "
                     "know inside from outside and tint with thickness.  A group is marked only when its faces close a volume and wind consistently (they are turned outward "
                     "if they wind inward); otherwise a warning, and the group stays the thin glass it was")
@@ -217,13 +219,28 @@ if a.mesh:
                     if uvs is None:
                         sys.exit(f"--mtl: material {name!r} has a roughness map and {a.mesh} has no complete set of texture coordinates")
                     scene.set_roughness_map(mat, scene.add_image(read_image(roughness_map), a.texture_wrap, a.texture_filter))
-            group_faces, turned = solid(mat, faces[rows], f"material {name!r}", entry.get("transmission_filter")) if is_glass else (faces[rows], False)
+            # alpha cutouts: map_d names the group's opacity image; without one, the alpha channel of an RGBA map_Kd is the mask (R = G = B = alpha),
+            # which then agrees with the colour texel for texel; the group is there where the mask is not below --cutout-cutoff
+            cutout_map, mask = entry.get("cutout_map"), None
+            if cutout_map:
+                mask = read_image(cutout_map)
+            elif picture and picture.lower().endswith(".png"):
+                alpha = image_io.read_png_alpha(picture)
+                if alpha is not None and (alpha != 255).any():
+                    cutout_map, mask = picture + " (alpha)", np.repeat(alpha[:, :, None], 3, axis=2)
+            if mask is not None:
+                if uvs is None:
+                    sys.exit(f"--mtl: material {name!r} has an opacity map and {a.mesh} has no complete set of texture coordinates")
+                scene.set_cutout(mat, scene.add_image(mask, a.texture_wrap, a.texture_filter), a.cutout_cutoff)
+            if is_glass and mask is not None and a.solid_glass:
+                print(f"warning: --solid-glass: material {name!r} stays thin glass: it has an opacity map, and a holed solid has no inside", file=sys.stderr, flush=True)
+            group_faces, turned = solid(mat, faces[rows], f"material {name!r}", entry.get("transmission_filter")) if is_glass and mask is None else (faces[rows], False)
             way = (lambda f: f[:, ::-1]) if turned else (lambda f: f)   # a turned face takes its normals and coordinates in the new order too
             group_normals = dict(normals=normals, normal_faces=way(normal_faces[rows] if normal_faces is not None else faces[rows])) if normals is not None else {}
-            group_uvs = dict(uvs=uvs, uv_faces=way(uv_faces[rows])) if picture or roughness_map else {}
+            group_uvs = dict(uvs=uvs, uv_faces=way(uv_faces[rows])) if picture or roughness_map or mask is not None else {}
             added += scene.MakeMesh(vertices, group_faces, mat, **place, **group_normals, **group_uvs)[1]
             print(json.dumps({"material": name, "triangles": len(rows), "image": picture, "Kd": entry["Kd"], "roughness": roughness, "roughness_map": roughness_map,
-                              "metallic": metallic, "glass": is_glass}), flush=True)
+                              "metallic": metallic, "glass": is_glass, "cutout_map": cutout_map}), flush=True)
     else:
         mat = image_material(a.texture[0]) if a.texture else plain()
         turned = False
