@@ -509,7 +509,7 @@ int rt_expf_batch(size_t count, const float* x, float* out);
  * The shade phase recomputes hit_p, (u, v) and the texel from the same t with the same functions, so a mask made from the alpha of the material's own map_Kd
  * agrees with its colour texel for texel.  Deterministic: nothing is drawn, and the order in which a sample consumes its random numbers is untouched.  Known
  * limits: spheres ignore the record (a sphere test yields one root, and looking through a hole at the sphere's own back needs the second); no stochastic
- * opacity; the feature pass does not know the rule (rt_renderer_aov_enable refuses a renderer with a table).                                                */
+ * opacity; the feature pass knows the rule in mode RT_AOV_FULL alone (modes RT_AOV_PLAIN and RT_AOV_TEXTURED refuse a renderer with a table).                */
 typedef struct rt_cutout { uint32_t on; uint32_t image; float cutoff; uint32_t reserved; } rt_cutout;   /* 16 B, one per material */
 enum { RT_CUTOUT_OFF = 0, RT_CUTOUT_MASKED = 1 };
 /* Gives `material` a cutout record.  RT_ERR_INVALID, scene unchanged: no such material; an RT_MAT_DIFFUSE_LIGHT (the light tables take a light's whole area as
@@ -750,7 +750,7 @@ int rt_renderer_refine_noise(rt_renderer* r, double* out);
  * rt_renderer_refine_reset; afterwards the buffers share its lifecycle (reset, set_camera with other bytes: discarded; set_camera with
  * the same bytes, a Render() between steps: kept).  A sharded renderer accumulates its shard.  RT_ERR_INVALID: a renderer on the
  * baseline kernel (variant 1); a world with a constant medium (its first "hit" draws from the RNG), a noise or an image texture
- * (rt_renderer_aov_enable_mode with RT_AOV_TEXTURED takes the last two).                                                               */
+ * (rt_renderer_aov_enable_mode with RT_AOV_TEXTURED takes the last two, with RT_AOV_FULL all three).                                    */
 int rt_renderer_aov_enable(rt_renderer* r, uint32_t max_samples);
 /* The same with a mode.  RT_AOV_PLAIN is rt_renderer_aov_enable, refusals and messages included.  RT_AOV_TEXTURED also covers the two textured Lambertians; every
  * other material, the normal, the distance and the hit count are as above:
@@ -760,9 +760,21 @@ int rt_renderer_aov_enable(rt_renderer* r, uint32_t max_samples);
  *   (albedo2[0]) of the renderer's texture table, or, without a table, in the world's image.
  * Tables given or taken away later (rt_renderer_textures, _texture_coords, _shading_normals) are followed: they restart the refinement anyway.  A launch whose
  * materials name an entry the renderer does not have is refused before any kernel runs, as without features.  Enabling in either mode restarts the refinement;
- * switching the mode is an enable.  RT_ERR_INVALID: variant 1; a constant medium (the message names RT_MAT_ISOTROPIC); an unknown mode.                        */
+ * switching the mode is an enable.  RT_ERR_INVALID: variant 1; a constant medium (the message names RT_MAT_ISOTROPIC); an unknown mode.
+ * RT_AOV_FULL is RT_AOV_TEXTURED on every world that mode takes, bit for bit, and also follows alpha cutouts and constant media: per sample, in
+ * sample order, the feature trace IS the colour path's first trace.
+ *   Cutouts (lists and stack-walked BVHs, the walks a table is accepted on): a parallelogram or triangle that passes its test, on a material whose rt_cutout
+ *   record is on, is put to the rule of rt_scene_set_cutout at its own (u, v) — rt_tri_uvs' rule while the renderer has texture coordinates, the planar coordinates
+ *   otherwise; a candidate turned down leaves the closest hit as it was and the walk goes on as after a failed test.  rt_renderer_cutouts accepts and removes a
+ *   table while buffers of this mode are on, and restarts colour and features together.
+ *   Media: the trace draws from the sample's own RNG, continued from where the camera's draws left it, so a medium's free path is the one the colour path drew,
+ *   in traversal order.  A first hit inside a medium adds the normal as the trace returns it, (1, 0, 0) — a constant, so that pixels deep in fog agree in the
+ *   filter's normal weight —, its distance, 1, and the isotropic material's albedo.
+ *   Vertex normals and normal maps apply as in RT_AOV_TEXTURED; a miss adds albedo (1, 1, 1) only.
+ * RT_ERR_INVALID in mode RT_AOV_FULL: variant 1; an unknown mode.  At a launch: a cutout, normal-map or image record that names an entry the texture table lacks. */
 #define RT_AOV_PLAIN    0u
 #define RT_AOV_TEXTURED 1u
+#define RT_AOV_FULL     2u
 int rt_renderer_aov_enable_mode(rt_renderer* r, uint32_t max_samples, uint32_t mode);
 /* *out_mode = the mode of the last successful enable; RT_AOV_PLAIN before any */
 int rt_renderer_aov_mode(rt_renderer* r, uint32_t* out_mode);
@@ -1009,7 +1021,7 @@ int rt_renderer_interiors_info(rt_renderer* r, uint32_t out[2]);
  * normal-map table is on; that form reads them all.  Takes effect at the next launch; an unchanged table is a no-op that keeps the refinement, a change discards
  * it.  RT_ERR_INVALID, renderer and kernel unchanged: what rt_renderer_interiors refuses a renderer for (variants 1, 5, 6; queue and wide4 walks; bvh_node
  * trees; light-sampling modes 1, 2, 4, 16, 32, which in turn refuse a renderer with a table), a renderer without a texture table, feature buffers that are on
- * (rt_renderer_aov_enable in turn refuses a renderer with a table: the feature pass does not know the rule), a count that is not the world's number of
+ * in mode RT_AOV_PLAIN or RT_AOV_TEXTURED (which in turn refuse a renderer with a table: only mode RT_AOV_FULL knows the rule), a count that is not the world's number of
  * materials, a record on a light, a medium or a material whose interior record is on, an `on` other than 0 or 1, an image index outside [0, RT_MAX_IMAGES), a
  * cutoff that is not finite or outside [0, 1].  A record that names an entry the texture table does not hold is refused at the launch, before any kernel
  * runs: the tables come and go independently.                                                                                                                */

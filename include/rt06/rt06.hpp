@@ -586,8 +586,10 @@ struct MotionBlurCamera {
 enum class LightSampling : uint32_t { Off = RT_LIGHT_SAMPLING_OFF, Quads = RT_LIGHT_SAMPLING_QUADS, All = RT_LIGHT_SAMPLING_ALL, Mesh = RT_LIGHT_SAMPLING_MESH,
                                       Tree = RT_LIGHT_SAMPLING_TREE, Env = RT_LIGHT_SAMPLING_ENV /* the environment map of a background-2 world */,
                                       EnvTree = RT_LIGHT_SAMPLING_ENV_TREE /* that map and the light tree together, image-textured hits included */ };
-// the modes of Renderer::EnableAOV (RT_AOV_PLAIN, RT_AOV_TEXTURED of rt06.h): Textured also covers noise and image materials
-enum class AovMode { Plain, Textured };
+// the modes of Renderer::EnableAOV (RT_AOV_PLAIN, RT_AOV_TEXTURED, RT_AOV_FULL of rt06.h): Textured also covers noise and image materials, Full
+// also follows alpha cutouts and constant media (§35).  Until §35 the declaration read `enum class AovMode { Plain, Textured }`: Full is appended, so the two
+// older enumerators keep their values and code compiled against them means what it meant.
+enum class AovMode { Plain, Textured, Full };
 
 // ----------------------------------------------------------------------------------------------------
 // Renderer — main/src/Renderer.h:12-47
@@ -750,13 +752,13 @@ public:
     void EnableAOV(uint32_t max_samples = 0) { single("Renderer::EnableAOV"); rt06::check(rt_renderer_aov_enable(m.r, max_samples), "Renderer::EnableAOV"); }
     void EnableAOV(uint32_t max_samples, AovMode mode) {
         single("Renderer::EnableAOV");
-        rt06::check(rt_renderer_aov_enable_mode(m.r, max_samples, mode == AovMode::Textured ? RT_AOV_TEXTURED : RT_AOV_PLAIN), "Renderer::EnableAOV");
+        rt06::check(rt_renderer_aov_enable_mode(m.r, max_samples, mode == AovMode::Full ? RT_AOV_FULL : mode == AovMode::Textured ? RT_AOV_TEXTURED : RT_AOV_PLAIN), "Renderer::EnableAOV");
     }
     AovMode AOVMode() {
         single("Renderer::AOVMode");
         uint32_t mode = RT_AOV_PLAIN;
         rt06::check(rt_renderer_aov_mode(m.r, &mode), "Renderer::AOVMode");
-        return mode == RT_AOV_TEXTURED ? AovMode::Textured : AovMode::Plain;
+        return mode == RT_AOV_FULL ? AovMode::Full : mode == RT_AOV_TEXTURED ? AovMode::Textured : AovMode::Plain;
     }
     // width*height pairs of vec4: (sum Nx, sum Ny, sum Nz, sum t), (sum Ar, sum Ag, sum Ab, hits), unscaled
     void DownloadAOV(glm::vec4* host_dst) {

@@ -537,6 +537,15 @@ def light_sampling_mode(on):
     return int(on)
 
 
+def feature_mode_for(material_types, has_cutouts):
+    """The mode of the feature pass a world asks for, as tools/render.py chooses it: 'full' (RT_AOV_FULL) for a world with a cutout table or a
+    constant medium, 'textured' (§27) for one with a noise or an image material, 'plain' for every other.  material_types: the type of every material."""
+    kinds = {int(k) for k in material_types}
+    if has_cutouts or capi.MAT_ISOTROPIC in kinds:
+        return "full"
+    return "textured" if kinds & {capi.MAT_LAMBERTIAN_NOISE, capi.MAT_LAMBERTIAN_IMAGE} else "plain"
+
+
 def normals_table(table):
     """a table of vertex normals as float32 (n, 9): from Scene.vertex_normals()'s records or an array of shape (n, 9) / (n, 3, 3)"""
     a = np.asarray(table)
@@ -715,19 +724,24 @@ class Renderer:
         check(lib().rt_renderer_refine_noise(self.h, C.byref(out)))
         return out.value
 
-    def enable_aov(self, max_samples=0, textured=False):
+    def enable_aov(self, max_samples=0, textured=False, full=False):
         """Accumulate first-hit feature buffers alongside every refine step from now on (restarts the refinement); max_samples = 0: every sample.
-        textured: mode RT_AOV_TEXTURED, which also covers noise and image materials (the plain mode refuses a world that has one)."""
-        if textured:
+        textured: mode RT_AOV_TEXTURED, which also covers noise and image materials (the plain mode refuses a world that has one).
+        full: mode RT_AOV_FULL, the textured mode that also follows alpha cutouts and constant media.  One mode at a time."""
+        if textured and full:
+            raise ValueError("enable_aov: textured and full are two modes; pass one of them")
+        if full:
+            check(lib().rt_renderer_aov_enable_mode(self.h, max_samples, capi.AOV_FULL))
+        elif textured:
             check(lib().rt_renderer_aov_enable_mode(self.h, max_samples, capi.AOV_TEXTURED))
         else:
             check(lib().rt_renderer_aov_enable(self.h, max_samples))
 
     def aov_mode(self):
-        """'plain' or 'textured': the mode of the last successful enable_aov ('plain' before any)."""
+        """'plain', 'textured' or 'full': the mode of the last successful enable_aov ('plain' before any)."""
         out = C.c_uint32()
         check(lib().rt_renderer_aov_mode(self.h, C.byref(out)))
-        return {capi.AOV_PLAIN: "plain", capi.AOV_TEXTURED: "textured"}[out.value]
+        return {capi.AOV_PLAIN: "plain", capi.AOV_TEXTURED: "textured", capi.AOV_FULL: "full"}[out.value]
 
     def aov_info(self):
         """{'enabled', 'samples', 'bytes'}: whether the feature buffers are on, the samples per pixel they cover, bytes held."""

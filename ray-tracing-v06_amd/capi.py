@@ -47,7 +47,7 @@ CUTOUT_OFF, CUTOUT_MASKED = 0, 1
 WRAP_CLAMP, WRAP_REPEAT = 0, 1
 FILTER_NEAREST, FILTER_BILINEAR = 0, 1
 MAX_IMAGES = 256
-AOV_PLAIN, AOV_TEXTURED = 0, 1
+AOV_PLAIN, AOV_TEXTURED, AOV_FULL = 0, 1, 2
 QUAD_DT = np.dtype([("Q", "<f4", 3), ("D", "<f4"), ("u", "<f4", 3), ("mat", "<u4"), ("v", "<f4", 3), ("kind", "<u4"),
                     ("normal", "<f4", 3), ("pad1", "<f4"), ("w", "<f4", 3), ("pad2", "<f4")])
 

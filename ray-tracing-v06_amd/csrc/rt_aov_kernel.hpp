@@ -29,16 +29,17 @@
 #define RT_AOV_WALK_QUEUE 3   // RT_WORLD_BVH with RT_TRAVERSAL_QUEUE
 #define RT_AOV_WALK_WIDE4 4   // RT_WORLD_BVH with RT_TRAVERSAL_WIDE4
 
-template <int WALK>
-__device__ __forceinline__ bool aov_first_hit(const DeviceWorld& w, const Ray& ray, HitRec& rec, int32_t* lds_i, float* lds_f) {
-    // no RNG: only a constant medium draws during a trace, and a world with one is refused at rt_renderer_aov_enable
+template <int WALK, class Keep = KeepAll>
+__device__ __forceinline__ bool aov_first_hit(const DeviceWorld& w, const Ray& ray, HitRec& rec, int32_t* lds_i, float* lds_f, Rng* rng = nullptr, Keep keep = Keep()) {
+    // modes 0 and 1, no RNG: only a constant medium draws during a trace, and they refuse a world with one; mode RT_AOV_FULL hands in the sample's own (§35),
+    // and on the two walks a cutout table is accepted on, the cutout rule
     const LaneStack<int32_t, (int)RT_AOV_BLOCK> si = {lds_i + threadIdx.x};
     const LaneStack<float, (int)RT_AOV_BLOCK> sf = {lds_f + threadIdx.x};
-    if (WALK == RT_AOV_WALK_LIST) return list_closest_intersection(w, ray, rec, nullptr);
-    if (WALK == RT_AOV_WALK_TREE) return tree_closest_intersection(w, ray, rec, nullptr, si);
-    if (WALK == RT_AOV_WALK_QUEUE) return bvh_closest_intersection_queue(w, ray, rec, nullptr, si, sf);
-    if (WALK == RT_AOV_WALK_WIDE4) return bvh_closest_intersection_wide4(w, ray, rec, nullptr, si);
-    return bvh_closest_intersection(w, ray, rec, nullptr, si);
+    if (WALK == RT_AOV_WALK_LIST) return list_closest_intersection(w, ray, rec, rng, keep);
+    if (WALK == RT_AOV_WALK_TREE) return tree_closest_intersection(w, ray, rec, rng, si);
+    if (WALK == RT_AOV_WALK_QUEUE) return bvh_closest_intersection_queue(w, ray, rec, rng, si, sf);
+    if (WALK == RT_AOV_WALK_WIDE4) return bvh_closest_intersection_wide4(w, ray, rec, rng, si);
+    return bvh_closest_intersection(w, ray, rec, rng, si, keep);
 }
 
 // what the first hit looks like without its lighting: Lambertian / metal: albedo; checker: the texture value at the hit point (the shade
@@ -109,6 +110,29 @@ __device__ __forceinline__ void aov_normal_map(const DeviceWorld& w, const uint4
     normal_map_apply(texture_value(reinterpret_cast<const uint32_t*>(texels), tt[1u + nr.y], tu, tv), __uint_as_float(nr.z), dPdu, dPdv, ray.d, rec.normal);
 }
 
+// Mode RT_AOV_FULL, the Keep of its list and stack walks: the leaf phase of the CUT kernels (rt_stream_kernel.hpp) on the flat world's records.  A
+// parallelogram or triangle that has passed its test, on a material whose cutout record is on, is there iff cutout_keeps says so — the mask's entry of the texture
+// table at the candidate's own (u, v): the triangle's record of the table of texture coordinates while there is one, the planar coordinates otherwise.
+// cut_at = the sub-header's third lane, the vec4 from the tail's header to the records, 0 without a table (wave-uniform, like uv_at and tex_at).
+struct AovCutoutKeep {
+    const uint4* tail;
+    uint32_t uv_at, tex_at, cut_at, first_tri;
+    __device__ __forceinline__ bool operator()(const rt_quad& q, int32_t idx, const Ray& ray, float t) const {
+        if (cut_at == 0u || tex_at == 0u) return true;   // (the host launches no record without its table entry)
+        const uint4 cut_rec = tail[cut_at + q.mat];      // (on, image, cutoff bits, -)
+        if (cut_rec.x == 0u) return true;
+        const uint4* tt = tail + tex_at;
+        const uint4 th = tt[0];
+        const uint64_t texels = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)th.x) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)th.y) << 32;
+        const float* tr = nullptr;
+        if (uv_at != 0u && (uint32_t)idx >= first_tri) tr = reinterpret_cast<const float*>(tail + uv_at) + (size_t)((uint32_t)idx - first_tri) * 6u;
+        float cut_u, cut_v;
+        f3 cut_c;
+        return cutout_keeps(reinterpret_cast<const uint32_t*>(texels), tt[1u + cut_rec.y], __uint_as_float(cut_rec.z), ld3(q.Q), ld3(q.u), ld3(q.v), ld3(q.w), tr, ray, t,
+                            cut_u, cut_v, cut_c);
+    }
+};
+
 // what the feature pass reads of a refine pass (a StreamParams would occupy scalar registers the traversal needs)
 struct AovParams {
     TileMap tm;
@@ -122,9 +146,12 @@ struct AovParams {
 // SMOOTH (aov_kernel_smooth): a hit on a triangle — unified index >= first_tri — takes its normal through shading_normal() from the table's record
 // TEX (aov_kernel_tex / aov_kernel_smooth_tex): the albedo is aov_albedo_tex's; tail = the header of the image's tail, first_tri as above
 // NMAP (aov_kernel_nmap): TEX, and the normal goes through aov_normal_map behind the smooth rule; vn may be null (no table of vertex normals)
-template <int WALK, bool SMOOTH, bool TEX = false, bool NMAP = false>
+// FULL (aov_kernel_full): TEX, and the trace is the colour path's first trace — the lane's Rng starts from the sample's record in prim_rng, as
+//      render_kernel_stream starts a sample, and goes to the walk, so that a constant medium draws what it drew there; with `cutouts` the list and stack walks put
+//      their candidates to the cutout rule; a first hit inside a medium adds the trace's normal (1, 0, 0), its distance, 1 and the isotropic material's albedo
+template <int WALK, bool SMOOTH, bool TEX = false, bool NMAP = false, bool FULL = false>
 __device__ __forceinline__ void aov_body(const AovParams& p, float4* __restrict__ aov, int32_t* lds_i, float* lds_f, const rt_tri_normals* vn, uint32_t first_tri,
-                                         const uint4* tail = nullptr) {
+                                         const uint4* tail = nullptr, [[maybe_unused]] const uint4* prim_rng = nullptr, [[maybe_unused]] uint32_t cutouts = 0u) {
     const uint32_t L = blockIdx.x * RT_AOV_BLOCK + threadIdx.x;
     if (L >= p.tm.n_local_tiles * RT_TILE * RT_TILE) return;
     uint32_t gid;
@@ -137,6 +164,13 @@ __device__ __forceinline__ void aov_body(const AovParams& p, float4* __restrict_
         const uint4 th = tail[0];
         uv_at = (uint32_t)__builtin_amdgcn_readfirstlane((int)th.y); tex_at = (uint32_t)__builtin_amdgcn_readfirstlane((int)th.w);
     }
+    [[maybe_unused]] AovCutoutKeep keep = {tail, uv_at, tex_at, 0u, first_tri};
+    if constexpr (FULL && (WALK == RT_AOV_WALK_LIST || WALK == RT_AOV_WALK_STACK)) {
+        if (cutouts) {   // only a tail with cutout records is known to have the sub-header (rt_launch_image.hpp): the header's first lane counts the vec4 to it
+            const uint32_t sub_at = (uint32_t)__builtin_amdgcn_readfirstlane((int)tail[0].x) >> 1;
+            if (sub_at != 0u) keep.cut_at = (uint32_t)__builtin_amdgcn_readfirstlane((int)tail[sub_at].z);
+        }
+    }
     for (uint32_t s = 0; s < p.n_take; s++) {
         const float4 o = p.prim_o[src], d = p.prim_d[src];
         Ray ray;
@@ -144,8 +178,18 @@ __device__ __forceinline__ void aov_body(const AovParams& p, float4* __restrict_
         HitRec rec;
         rec.distance = RT_MISS_DIST; rec.normal = mk3(0.0f); rec.prim = -1; rec.mat = 0;   // as sample_world starts a trace
         f3 alb = mk3(1.0f);
-        if (aov_first_hit<WALK>(p.world, ray, rec, lds_i, lds_f)) {
-            if constexpr (TEX) alb = aov_albedo_tex(p.world, tail, uv_at, tex_at, first_tri, p.world.mats[rec.mat], ray, rec);
+        bool hit;
+        if constexpr (FULL) {
+            const uint4 rs = prim_rng[src];
+            Rng rng;
+            rng.s0 = rs.x; rng.s1 = rs.y; rng.s2 = rs.z; rng.s3 = rs.w; rng.draws = 0u;
+            if constexpr (WALK == RT_AOV_WALK_LIST || WALK == RT_AOV_WALK_STACK) hit = aov_first_hit<WALK>(p.world, ray, rec, lds_i, lds_f, &rng, keep);
+            else hit = aov_first_hit<WALK>(p.world, ray, rec, lds_i, lds_f, &rng);
+        } else
+        hit = aov_first_hit<WALK>(p.world, ray, rec, lds_i, lds_f);
+        if (hit) {
+            if (FULL && p.world.mats[rec.mat].type == RT_MAT_ISOTROPIC) { const rt_material& m = p.world.mats[rec.mat]; alb = mk3(m.albedo[0], m.albedo[1], m.albedo[2]); }
+            else if constexpr (TEX) alb = aov_albedo_tex(p.world, tail, uv_at, tex_at, first_tri, p.world.mats[rec.mat], ray, rec);
             else alb = aov_albedo(p.world.mats[rec.mat], ray, rec);
             if (SMOOTH && (!NMAP || vn) && (uint32_t)rec.prim >= first_tri) shading_normal_flat(p.world.quads[(uint32_t)rec.prim - p.world.n_prims], vn[(uint32_t)rec.prim - first_tri], ray, rec.distance, rec.normal);
             if constexpr (NMAP) aov_normal_map(p.world, tail, uv_at, tex_at, first_tri, ray, rec);
@@ -197,6 +241,18 @@ __global__ __launch_bounds__(RT_AOV_BLOCK) void aov_kernel_nmap(AovParams p, flo
     __shared__ int32_t lds_i[WALK == RT_AOV_WALK_LIST ? 1u : RT_MAX_STACK * RT_AOV_BLOCK];
     __shared__ float lds_f[1u];
     aov_body<WALK, true, true, true>(p, aov, lds_i, lds_f, vn, first_tri, blob + blob_vec4);
+}
+
+// mode RT_AOV_FULL: one family for the five walks.  Lists and stack-walked BVHs — what a cutout table, vertex normals and a normal map are accepted
+// on — carry the cutout rule and aov_kernel_nmap's normals (vn may be null); the other three walks carry the RNG only.  prim_rng = the pass's RNG records
+// (StreamParams::prim_rng), cutouts = whether the renderer has a cutout table: arguments of these kernels alone.
+template <int WALK>
+__global__ __launch_bounds__(RT_AOV_BLOCK) void aov_kernel_full(AovParams p, float4* __restrict__ aov, const uint4* __restrict__ prim_rng, const rt_tri_normals* __restrict__ vn,
+                                                                const uint4* __restrict__ blob, uint32_t blob_vec4, uint32_t first_tri, uint32_t cutouts) {
+    __shared__ int32_t lds_i[WALK == RT_AOV_WALK_LIST ? 1u : RT_MAX_STACK * RT_AOV_BLOCK];
+    __shared__ float lds_f[WALK == RT_AOV_WALK_QUEUE ? RT_MAX_STACK * RT_AOV_BLOCK : 1u];
+    constexpr bool FLAT = WALK == RT_AOV_WALK_LIST || WALK == RT_AOV_WALK_STACK;
+    aov_body<WALK, FLAT, true, FLAT, true>(p, aov, lds_i, lds_f, vn, first_tri, blob + blob_vec4, prim_rng, cutouts);
 }
 
 // ---------------------------------------------------------------------------------------------

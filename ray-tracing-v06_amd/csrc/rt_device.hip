@@ -251,6 +251,14 @@ static decltype(&aov_kernel_tex<RT_AOV_WALK_STACK>) aov_kernel_tex_for(const Dev
     if (w.traversal == RT_TRAVERSAL_WIDE4) return &aov_kernel_tex<RT_AOV_WALK_WIDE4>;
     return &aov_kernel_tex<RT_AOV_WALK_STACK>;
 }
+// the FULL forms (§35)
+static decltype(&aov_kernel_full<RT_AOV_WALK_STACK>) aov_kernel_full_for(const DeviceWorld& w) {
+    if (w.kind == RT_WORLD_LIST) return &aov_kernel_full<RT_AOV_WALK_LIST>;
+    if (w.kind == RT_WORLD_NODE_TREE) return &aov_kernel_full<RT_AOV_WALK_TREE>;
+    if (w.traversal == RT_TRAVERSAL_QUEUE) return &aov_kernel_full<RT_AOV_WALK_QUEUE>;
+    if (w.traversal == RT_TRAVERSAL_WIDE4) return &aov_kernel_full<RT_AOV_WALK_WIDE4>;
+    return &aov_kernel_full<RT_AOV_WALK_STACK>;
+}
 
 // ---------------------------------------------------------------------------------------------
 // Renderer
@@ -341,7 +349,7 @@ struct rt_renderer {
     DevBuf aov;
     bool aov_on = false;
     uint32_t aov_max = 0, aov_done = 0;
-    uint32_t aov_mode = RT_AOV_PLAIN;    // the mode of the last successful enable: RT_AOV_TEXTURED launches the TEX forms
+    uint32_t aov_mode = RT_AOV_PLAIN;    // the mode of the last successful enable: RT_AOV_TEXTURED launches the TEX forms, RT_AOV_FULL the FULL forms (§35)
     const char* aov_refused = nullptr;   // the first material of the world the plain feature pass does not cover (a medium, a noise or an image texture)
     // light sampling (rt_renderer_light_sampling_enable).  tab[i]: the world's lights as rt_world_light_table gave them at creation for the table modes 1, 2, 4
     // and 16 (or why it gave none; mode 16, §20, with cdf and the tree's nodes).  image[0]: the plain image; image[1 + i]: the image with tab[i]'s table, from
@@ -945,6 +953,11 @@ struct rt_renderer {
         p.pass_first_s = sp.pass_first_s; p.pass_spp = sp.pass_spp; p.n_take = upto - sp.pass_first_s;
         p.prim_o = sp.prim_o; p.prim_d = sp.prim_d;
         const uint32_t first_tri = scene.dw.n_prims + scene.dw.n_quads - scene.n_triangles;
+        if (aov_mode == RT_AOV_FULL) {   // §35: the plain image's tail as in mode 1, the pass's RNG records, and whether that tail holds cutout records
+            const LaunchOn plain = launch_on(RT_LIGHT_SAMPLING_OFF);
+            aov_kernel_full_for(scene.dw)<<<grid, block, 0, st>>>(p, aov.as<float4>(), sp.prim_rng, vn.on ? vn.table.as<rt_tri_normals>() : nullptr, plain.blob, plain.blob_vec4,
+                                                                  first_tri, cut.on ? 1u : 0u);
+        } else
         if (aov_mode == RT_AOV_TEXTURED) {   // §27: the plain image, whose header is zero while no rider is on; every image's tail holds the same tables
             const LaunchOn plain = launch_on(RT_LIGHT_SAMPLING_OFF);
             const uint4* blob = plain.blob;
@@ -1512,7 +1525,7 @@ extern "C" int rt_renderer_cutouts(rt_renderer* r, const rt_cutout* table, uint3
         if (r->scene.dw.kind == RT_WORLD_NODE_TREE) return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: a bvh_node tree renders on a walk that reads no cutout table (BVHs walked by the stack and lists do)");
         if (r->nee.on() && r->nee.mode != RT_LIGHT_SAMPLING_ENV_TREE)
             return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: light-sampling mode %u is on, which has no kernel that reads a cutout table: alpha cutouts render with light sampling off or in mode 48", r->nee.mode);
-        if (r->aov_on)
+        if (r->aov_on && r->aov_mode != RT_AOV_FULL)   // §35: mode 2 follows the table
             return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: feature buffers are on, and the feature pass does not know the cutout rule: its first hits would be the solid cards, and a denoiser guided by them would be wrong without a sign");
         if (!r->tex.on) return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: the renderer has no texture table to take a mask from: give it one with rt_renderer_textures first");
         if (n != r->scene.dw.n_mats) return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: %u records for a world of %u materials", n, r->scene.dw.n_mats);
@@ -1649,12 +1662,12 @@ extern "C" int rt_renderer_refine_noise(rt_renderer* r, double* out) {
 // `who` = the entry point the caller used: rt_renderer_aov_enable keeps its messages
 static int aov_enable(const char* who, rt_renderer* r, uint32_t max_samples, uint32_t mode) {
     if (!r) return rt_fail(RT_ERR_INVALID, "%s: null renderer", who);
-    if (mode > RT_AOV_TEXTURED) return rt_fail(RT_ERR_INVALID, "%s: unknown mode %u (RT_AOV_PLAIN = 0, RT_AOV_TEXTURED = 1)", who, mode);
+    if (mode > RT_AOV_FULL) return rt_fail(RT_ERR_INVALID, "%s: unknown mode %u (RT_AOV_PLAIN = 0, RT_AOV_TEXTURED = 1, RT_AOV_FULL = 2)", who, mode);
     if (r->variant < 2)
         return rt_fail(RT_ERR_INVALID, "%s: the baseline kernel (variant 1) cannot refine and keeps no primary-ray records; feature buffers need a streaming variant (0, or 2 to 6)", who);
     if (mode == RT_AOV_PLAIN && r->nm.on)
         return rt_fail(RT_ERR_INVALID, "%s: the renderer has a normal-map table, and the plain feature pass's normals know no normal map: enable the pass in RT_AOV_TEXTURED mode (rt_renderer_aov_enable_mode)", who);
-    if (r->cut.on)
+    if (r->cut.on && mode != RT_AOV_FULL)   // §35: mode 2 puts its candidates to the rule
         return rt_fail(RT_ERR_INVALID, "%s: the renderer has a cutout table, and the feature pass does not know the cutout rule: its first hits would be the solid cards, and a denoiser guided by them would be wrong without a sign (take the table away with rt_renderer_cutouts(NULL, 0) first)", who);
     if (mode == RT_AOV_PLAIN && r->aov_refused)
         return rt_fail(RT_ERR_INVALID, "%s: the world has %s: the feature pass covers spheres and quads with Lambertian, metal, dielectric, checker and light materials", who, r->aov_refused);

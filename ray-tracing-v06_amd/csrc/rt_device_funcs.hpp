@@ -9,6 +9,7 @@
 #include "rt06.h"
 #include "rt_internal.hpp"
 #include "rt_math.hpp"
+#include <type_traits>
 
 struct DeviceWorld {
     uint32_t kind;
@@ -166,9 +167,22 @@ RT_HD bool shading_normal_flat(const rt_quad& q, const rt_tri_normals& vn, const
     return shading_normal(ld3(q.Q), ld3(q.u), ld3(q.v), ld3(q.w), ld3(vn.n0), ld3(vn.n1), ld3(vn.n2), ray.d, ray_at(ray, t), normal);
 }
 
-__device__ inline bool any_prim_closest_intersection(const DeviceWorld& w, int32_t idx, const Ray& ray, HitRec& rec, Rng* rng) {
+// Declining a candidate: a walk may be given a Keep, asked about every parallelogram or triangle that has just passed its test — keep(q, idx,
+// ray, t) with the record, its unified index and the candidate's distance.  One that is turned down leaves `rec` as it was before the test and counts as a failed
+// test.  KeepAll, the default, is never asked: every caller but the feature pass's third mode compiles to the code it had.
+struct KeepAll {};
+template <class Keep = KeepAll>
+__device__ inline bool any_prim_closest_intersection(const DeviceWorld& w, int32_t idx, const Ray& ray, HitRec& rec, Rng* rng, Keep keep = Keep()) {
     if ((uint32_t)idx >= w.n_prims) {
         const rt_quad& q = w.quads[(uint32_t)idx - w.n_prims];
+        if constexpr (!std::is_same<Keep, KeepAll>::value) {
+            const HitRec before = rec;
+            if (!quad_closest_intersection(mk3(q.Q[0], q.Q[1], q.Q[2]), q.D, mk3(q.u[0], q.u[1], q.u[2]), mk3(q.v[0], q.v[1], q.v[2]),
+                                           mk3(q.normal[0], q.normal[1], q.normal[2]), mk3(q.w[0], q.w[1], q.w[2]), q.mat, idx, q.kind, ray, rec)) return false;
+            if (keep(q, idx, ray, rec.distance)) return true;
+            rec = before;
+            return false;
+        } else
         return quad_closest_intersection(mk3(q.Q[0], q.Q[1], q.Q[2]), q.D, mk3(q.u[0], q.u[1], q.u[2]), mk3(q.v[0], q.v[1], q.v[2]),
                                          mk3(q.normal[0], q.normal[1], q.normal[2]), mk3(q.w[0], q.w[1], q.w[2]), q.mat, idx, q.kind, ray, rec);
     }
@@ -199,8 +213,8 @@ struct LaneStack {
 // BVH::ClosestIntersection, rt_engine/geometry/BVH.cu:54-106 (the live, non-priority-queue branch):
 // root box first; pop; leaf -> primitive; inner -> test BOTH child boxes, order near-first, push far
 // then near iff dist < rec.distance; no re-check at pop.
-template <class S = OwnStack<int32_t>>
-__device__ inline bool bvh_closest_intersection(const DeviceWorld& w, const Ray& ray, HitRec& rec, Rng* rng, S given = S()) {
+template <class S = OwnStack<int32_t>, class Keep = KeepAll>
+__device__ inline bool bvh_closest_intersection(const DeviceWorld& w, const Ray& ray, HitRec& rec, Rng* rng, S given = S(), Keep keep = Keep()) {
     typename S::Local stack;
     S::bind(stack, given);
     int head = 0;
@@ -213,7 +227,7 @@ __device__ inline bool bvh_closest_intersection(const DeviceWorld& w, const Ray&
         const rt_bvh_node& node = w.nodes[idx];
         int32_t left_idx = node.left, right_idx = node.right;
         if (left_idx == -1) {
-            hit_any |= any_prim_closest_intersection(w, right_idx, ray, rec, rng);
+            hit_any |= any_prim_closest_intersection(w, right_idx, ray, rec, rng, keep);
             continue;
         }
         float left_dist = RT_MISS_DIST, right_dist = RT_MISS_DIST;
@@ -318,12 +332,13 @@ __device__ inline bool bvh_closest_intersection_wide4(const DeviceWorld& w, cons
 }
 
 // HittableList::ClosestIntersection, rt_engine/geometry/HittableList.cuh:21-34
-__device__ inline bool list_closest_intersection(const DeviceWorld& w, const Ray& ray, HitRec& rec, Rng* rng) {
+template <class Keep = KeepAll>
+__device__ inline bool list_closest_intersection(const DeviceWorld& w, const Ray& ray, HitRec& rec, Rng* rng, Keep keep = Keep()) {
     float d;
     if (!aabb_intersects(w.bmin, w.bmax, ray, rec.distance, d)) return false;
     bool hit_any = false;
     for (uint32_t i = 0; i < w.n_prims + w.n_quads; i++)
-        if (any_prim_closest_intersection(w, (int32_t)i, ray, rec, rng)) hit_any = true;
+        if (any_prim_closest_intersection(w, (int32_t)i, ray, rec, rng, keep)) hit_any = true;
     return hit_any;
 }
 

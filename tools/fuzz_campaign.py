@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Differential fuzz campaign: random worlds (spheres, moving spheres, quads, triangles and meshes, lights, media, textures; every builder; LDS
 and global-memory paths; three cameras) rendered on the GPU and by the CPU oracle, compared bit for bit.
-    python tools/fuzz_campaign.py --seeds 200 [--first 0] [--no-triangles] [--mesh-lights] [--light-tree] [--texture-coords] [--textures] [--env-tree] [--surfaces [--live]] [--interiors] [--cutouts]
+    python tools/fuzz_campaign.py --seeds 200 [--first 0] [--no-triangles] [--mesh-lights] [--light-tree] [--texture-coords] [--textures] [--env-tree] [--surfaces [--live]] [--interiors] [--cutouts [--aov-full]]
 Prints one line per failure and a summary; exit code 1 if anything differed.  The triangles of a world come from a generator of their own, so the rest of a seed's
 world is what it was before the fuzzer made triangles, and --no-triangles renders exactly those earlier worlds.  Importing this file starts nothing:
 world_of_seed() builds a seed's world on the host, without a device.  --mesh-lights (off by default: the recorded campaigns ran without it) also renders every
@@ -53,6 +53,8 @@ def parse_args(argv=None):
     ap.add_argument("--live", action="store_true", help="with --surfaces: also render, per seed, a world of tests/_surface_worlds.random_surface_world(seed, live=True) — live normal-map, microfacet, rough-glass and interior records beside a constant medium, a noise material and moving spheres under a random camera kind — in both memory forms against the extended whole-sample twin, which must follow every sample; lane walks and kernel variants other than 2 and 3 are counted as skipped")
     ap.add_argument("--cutouts", action="store_true", help="also render, per seed, a world of its own with random masks on random parallelogram and triangle materials: the CUT kernel family in both memory forms against "
                     "the twin's walk (tests/_cutout_twin.py), every record off against no table")
+    ap.add_argument("--aov-full", action="store_true", help="with --cutouts: also accumulate that world's feature buffers in mode RT_AOV_FULL (DESIGN.md §35), in both memory forms, and hold the sums of every "
+                    "pixel to tests/_aov_full_twin.py")
     ap.add_argument("--interiors", action="store_true", help="also render every stack-walked or list world with random glass solids under random interior records: the INTR kernel family in both memory forms, every record off "
                     "against no table, and the twin (tests/_interior_twin.py) where it follows")
     return ap.parse_args(argv)
@@ -509,6 +511,32 @@ def cutouts_twin_check(p, seed):
     return ok, forms, W * H, stats["rejected"]
 
 
+def aov_full_check(p, seed):
+    """cutouts_twin_world(seed) with feature buffers in mode RT_AOV_FULL, in the renderer's own form and the global-memory form: the feature sums of
+    every pixel must be those of tests/_aov_full_twin.py, whose first trace is the cutout walk's.  (ok, pixels held, candidates the rule turned down)"""
+    import _aov_full_twin as FT
+    import _cutout_worlds as CW
+    s, cam, W, H, spp, _ = cutouts_twin_world(p, seed)
+    w, table = s.getWorldPtr(), s.cutouts()
+    uv, vn = s.texture_coords(), s.vertex_normals()
+    stats = FT.new_stats()
+    want = FT.sums(as_oracle_world(w), as_oracle_camera(cam), W, H, spp, 1984, uv=uv if uv is not None and len(uv) else None, cutouts=table, table=CW.twin_table(s),
+                   vn=vn if vn is not None and len(vn) else None, stats=stats)
+    ok = True
+    for env in ({}, {"RT06_FORCE_BIG": "1"}):
+        os.environ.pop("RT06_FORCE_BIG", None)
+        os.environ.update(env)
+        try:
+            r = p.Renderer.MakeRenderer(W, H, spp, 2, cam, w, variant=0)
+        finally:
+            os.environ.pop("RT06_FORCE_BIG", None)
+        r.enable_aov(full=True)
+        r.refine(spp)
+        ok = ok and r.kernel_cutout() and r.aov_mode() == "full" and bits_equal(r.aov_sums(), want)
+        r.close()
+    return ok, W * H, stats["rejected"]
+
+
 def interiors_twin_check(p, seed):
     """interiors_twin_world(seed) on the GPU, in the renderer's own form and the global-memory form, against the twin under the whole rule: the sums of every
     pixel must be the twin's, and the twin must follow every sample (the world is built so).  (ok, forms, pixels held)"""
@@ -693,6 +721,14 @@ def main(argv=None):
             if not tw[0]:
                 fails += 1
                 print(f"FAIL seed {seed}: the cutout twin world: forms {tw[1]}", flush=True)
+        if args.cutouts and args.aov_full:   # the same world under feature buffers
+            fa = aov_full_check(p, seed)
+            stats["aov_full_worlds"] = stats.get("aov_full_worlds", 0) + 1
+            stats["aov_full_pixels_held_to_the_twin"] = stats.get("aov_full_pixels_held_to_the_twin", 0) + fa[1]
+            stats["aov_full_candidates_turned_down"] = stats.get("aov_full_candidates_turned_down", 0) + fa[2]
+            if not fa[0]:
+                fails += 1
+                print(f"FAIL seed {seed}: the feature sums of mode RT_AOV_FULL on the cutout twin world", flush=True)
         if args.env_tree and ok and kinds >= 1 and info["variant"] in (2, 3) and not (big and builder == 3):   # last: it changes the scene's background
             et = env_tree_check(p, s, cam, ck, W, H, depth, variant)
             if et is not None:

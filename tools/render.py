@@ -17,7 +17,8 @@ last refined frame: bit for bit the frame a one-shot render at that sample count
 also accumulates first-hit feature buffers (rt_renderer_aov_enable) while refining.  --denoise writes the edge-aware filtered frame
 (rt_renderer_denoise) next to the refined one, as out_denoised.png; --aov PREFIX writes PREFIX_normal.png (n * 0.5 + 0.5),
 PREFIX_depth.png (nearest white, misses black) and PREFIX_albedo.png.  One GPU; a world with a noise or an image texture takes the textured
-feature mode (rt_renderer_aov_enable_mode, DESIGN.md §27: the albedo is the first hit's marble or texel); worlds with media are refused.
+feature mode (rt_renderer_aov_enable_mode, DESIGN.md §27: the albedo is the first hit's marble or texel), one with alpha cutouts or a constant medium the full mode
+(§35: the feature trace is the colour path's first trace, masks and the medium's draws included).
 
     python tools/render.py --scene cornell_box --spp 64 --light-sampling --out out.png
 
@@ -276,13 +277,13 @@ if a.refine:
          else p.Renderer.MakeRenderer(W, H, step_spp, a.depth, cam, scene.getWorldPtr(), seed=a.seed, device=a.device))
     if light_mode:
         r.light_sampling(light_mode)
-    if a.denoise or a.aov:   # a world with a noise or an image material takes the textured feature mode; every other one the plain mode, as ever
-        import ctypes
+    if a.denoise or a.aov:   # a world with a cutout table or a medium takes the full feature mode, one with a noise or an image material the
+        import ctypes        # textured mode (§27); every other one the plain mode, as ever
         import numpy as np
         flat = scene.getWorldPtr()
         kinds = np.frombuffer((ctypes.c_char * (flat.n_materials * p.capi.MAT_DT.itemsize)).from_address(flat.materials), dtype=p.capi.MAT_DT)["type"]
-        textured = bool(np.isin(kinds, (p.capi.MAT_LAMBERTIAN_NOISE, p.capi.MAT_LAMBERTIAN_IMAGE)).any())
-        r.enable_aov(textured=textured)
+        mode = p.api.feature_mode_for(kinds, scene.cutouts() is not None)
+        r.enable_aov(textured=mode == "textured", full=mode == "full")
     samples, ms = 0, 0.0
     while samples < a.spp:
         n = min(a.refine, a.spp - samples)
