@@ -53,9 +53,11 @@ def first_trace(world, cam, width, height, spp, seed, uv=None, cutouts=None, tab
 
 
 def sums(world, cam, width, height, spp, seed, uv=None, cutouts=None, table=None, image=None, noise=None, vn=None, first_sample=0, start=None, stats=None,
-         fresh_rng=False):
+         fresh_rng=False, nmaps=None):
     """(H, W, 8) float32: (sum Nx, sum Ny, sum Nz, sum t, sum Ar, sum Ag, sum Ab, hits) of samples [first_sample, first_sample + spp), continued from `start` —
-    _aov_tex_twin.sums' layout and order of additions"""
+    _aov_tex_twin.sums' layout and order of additions.  nmaps (one record of capi.NORMAL_MAP_DT per material): the first-hit normal is the mapped normal —
+    _nmap_twin.mapped_walk, the smooth rule and then the map, over the walk first_trace() ran with the tape and its rows (the cutout walk under a cutout table); the
+    albedo's (u, v) on a sphere stays the one of the normal the walk found.  With every record off it is the smooth rule alone."""
     rays, hit, t, prim, normal = first_trace(world, cam, width, height, spp, seed, uv, cutouts, table, first_sample, stats, fresh_rng)
     prims, quads, mats = world_arrays(world)
     alb = AT.albedo_of_hits(world, rays, hit, t, prim, normal, True, uv, table, image, noise)
@@ -64,7 +66,11 @@ def sums(world, cam, width, height, spp, seed, uv=None, cutouts=None, table=None
     mat = (prims["mat"][prim[on_sphere]] & ~np.uint32(AT.PRIM_MOVING)).astype(np.int64)
     iso = mats["type"][mat] == MAT_ISOTROPIC
     alb[on_sphere[iso]] = mats["albedo"][mat[iso]]   # the isotropic hit: the medium's albedo
-    if vn is not None:   # the smooth rule changes the normal sum only
+    if nmaps is not None:
+        import _nmap_twin as NT
+        traced = hit, t, prim, normal
+        normal = NT.mapped_walk(world, vn, uv, nmaps, table, rays, base=lambda *a, **k: traced)[3]
+    elif vn is not None:   # the smooth rule changes the normal sum only
         first_tri = len(prims) + int((quads["kind"] == 0).sum())
         rows = np.nonzero(h & (prim >= first_tri))[0]
         if len(rows):

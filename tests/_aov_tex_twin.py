@@ -73,13 +73,12 @@ def checker_value(even, odd, inv_scale, pos):
 def albedo_of_hits(world, rays, hit, t, prim, normal, textured, uv=None, table=None, image=None, noise=None):
     """the first-hit albedo of every ray (n, 3) float32; a miss is (1, 1, 1)"""
     prims, quads, mats = world_arrays(world)
-    assert not (prims["mat"] & np.uint32(PRIM_MOVING)).any(), "static spheres"
     n = len(rays)
     alb = np.ones((n, 3), F)
     h = np.nonzero(hit != 0)[0]
     on_sphere = prim[h] < len(prims)
     mat = np.zeros(len(h), np.int64)
-    mat[on_sphere] = prims["mat"][prim[h][on_sphere]]
+    mat[on_sphere] = prims["mat"][prim[h][on_sphere]] & ~np.uint32(PRIM_MOVING)   # a moving sphere's material; where it stood at the ray's time is the walk's to know
     mat[~on_sphere] = quads["mat"][prim[h][~on_sphere] - len(prims)]
     mtype = mats["type"][mat]
     with np.errstate(all="ignore"):

@@ -64,10 +64,17 @@ def keeps64(image, wrap, Q, u, v, t0, t1, t2, o, d, t, cutoff):
     return ~(value < np.asarray(cutoff, np.float64)), tuv, value
 
 
-def closest_intersection(world, uv, cutouts, table, rays, preset=None, stats=None, eye=None, tape=None, rows=None, medium_info=None):
+LIVE_COUNTERS = ("hole_then_moving", "hole_then_medium_draw", "hole_then_solid", "kept_image_masked", "kept_mapped_masked", "kept_smooth_masked", "mask_uv_is_shade_uv")
+NOT_TAKEN_BACK, MASK_AT_PLANAR = "a rejected candidate keeps its distance", "the mask is read at the planar coordinates"   # the deliberately wrong walks (`wrong`)
+
+
+def closest_intersection(world, uv, cutouts, table, rays, preset=None, stats=None, eye=None, tape=None, rows=None, medium_info=None, marks=None, wrong=None):
     """_tri_twin.closest_intersection under the rule: (hit int32, t, prim int32, normal).  uv: the renderer's table of texture coordinates or None; cutouts: one
     record of CUTOUT_DT per material; table: the texture table [(image, wrap, filter), ...]; stats: new_stats()'s counters grow; eye: the camera's position —
-    a rejection on a ray that does not start there counts as deep."""
+    a rejection on a ray that does not start there counts as deep.  marks (a dict, with stats): what the walk does not know of the world — 'solid' and 'mapped'
+    (bool per material: an interior record, a normal-map record), 'smooth' (bool per triangle: vertex normals) — under which LIVE_COUNTERS are counted (DESIGN.md
+    §36), and which gets 'masked_image' back: (rows, bool) — the rays of this call whose hit is on a masked image material.  wrong: NOT_TAKEN_BACK or
+    MASK_AT_PLANAR — a walk that is WRONG on purpose, for the tests that show a frame would notice."""
     prims, quads, mats = world_arrays(world)
     assert world.traversal == 0, "stack traversal"
     n, n_prims = len(rays), len(prims)
@@ -86,7 +93,10 @@ def closest_intersection(world, uv, cutouts, table, rays, preset=None, stats=Non
 
     def leaf(idx, at):
         before = rec_t[at].copy(), rec_prim[at].copy(), rec_n[at].copy()
+        cur0 = tape.cur[media[3][at]].copy() if media is not None and marks is not None else None
         TT._leaf(prims, quads, idx, o, d, rec_t, rec_prim, rec_n, at, time, media)
+        if cur0 is not None and stats is not None:   # a medium drew on a ray that had been through a hole
+            stats["hole_then_medium_draw"] = stats.get("hole_then_medium_draw", 0) + int(((tape.cur[media[3][at]] > cur0) & np.isfinite(nearest_hole[at])).sum())
         quad = idx >= n_prims
         took = quad & (rec_prim[at] == idx) & (before[1] != idx)
         took[took] = on_of_quad[idx[took] - n_prims]
@@ -94,7 +104,7 @@ def closest_intersection(world, uv, cutouts, table, rays, preset=None, stats=Non
         if len(c) == 0:
             return
         r, qi = at[c], idx[c] - n_prims
-        under_table = (idx[c] >= first_tri) & (tab is not None)
+        under_table = (idx[c] >= first_tri) & (tab is not None) & (wrong != MASK_AT_PLANAR)
         keep = np.ones(len(c), bool)
         for sel, tuv in ((under_table, True), (~under_table, False)):
             if sel.any():
@@ -114,7 +124,9 @@ def closest_intersection(world, uv, cutouts, table, rays, preset=None, stats=Non
             stats["rejected_deep"] += int((rej & deep[r]).sum())
         back = r[rej]
         nearest_hole[back] = np.minimum(nearest_hole[back], rec_t[back].astype(np.float64))
-        rec_t[back], rec_prim[back], rec_n[back] = before[0][c][rej], before[1][c][rej], before[2][c][rej]   # the hit is taken back: the lane never took it
+        if wrong != NOT_TAKEN_BACK:
+            rec_t[back] = before[0][c][rej]
+        rec_prim[back], rec_n[back] = before[1][c][rej], before[2][c][rej]   # the hit is taken back: the lane never took it
 
     if world.kind == 1:   # HittableList.cuh:21-34
         bmn, bmx = np.array(list(world.bounds_min), F), np.array(list(world.bounds_max), F)
@@ -158,9 +170,46 @@ def closest_intersection(world, uv, cutouts, table, rays, preset=None, stats=Non
         stats["then_farther"] += int((holed & hit & (rec_t.astype(np.float64) > nearest_hole)).sum())
         stats["then_nearer"] += int((holed & hit & ~(rec_t.astype(np.float64) > nearest_hole)).sum())
         stats["then_miss"] += int((holed & ~hit).sum())
+        if marks is not None:
+            _live_counters(world, uv, cutouts, table, rays, stats, marks, holed, hit, rec_t, rec_prim, rec_n, rows, (prims, quads, mats, tab, first_tri, on_of_quad))
     return hit.astype(np.int32), rec_t, rec_prim.astype(np.int32), rec_n
 
 
-def walk_of(uv, cutouts, table, stats=None, eye=None):
+def _live_counters(world, uv, cutouts, table, rays, stats, marks, holed, hit, rec_t, rec_prim, rec_n, rows, arrays):
+    """LIVE_COUNTERS of one finished walk (hole_then_medium_draw is counted leaf by leaf): what lay behind a hole, and what the kept hits on masked surfaces are"""
+    from _nee_twin import PRIM_MOVING
+    prims, quads, mats, tab, first_tri, on_of_quad = arrays
+    n_prims = len(prims)
+
+    def bump(key, which):
+        stats[key] = stats.get(key, 0) + int(np.count_nonzero(which))
+    sphere = hit & (rec_prim < n_prims)
+    flat = hit & ~sphere
+    qi = np.where(flat, rec_prim - n_prims, 0)
+    mat = np.where(sphere, prims["mat"][np.where(sphere, rec_prim, 0)] & ~np.uint32(PRIM_MOVING), quads["mat"][qi]).astype(np.int64) if n_prims else quads["mat"][qi].astype(np.int64)
+    moving = sphere & ((prims["mat"][np.where(sphere, rec_prim, 0)] & np.uint32(PRIM_MOVING)) != 0) if n_prims else sphere
+    bump("hole_then_moving", holed & moving & (rays[:, 6] > F(0.25)))
+    bump("hole_then_solid", holed & hit & np.asarray(marks["solid"], bool)[mat])
+    masked = flat & on_of_quad[qi]
+    image = masked & (mats["type"][mat] == XT.MAT_IMAGE)
+    bump("kept_image_masked", image)
+    bump("kept_mapped_masked", masked & np.asarray(marks["mapped"], bool)[mat])
+    tri = masked & (rec_prim >= first_tri)
+    smooth = np.asarray(marks["smooth"], bool)
+    bump("kept_smooth_masked", tri & smooth[np.where(tri, rec_prim - first_tri, 0)] if len(smooth) else False)
+    marks["masked_image"] = (None if rows is None else np.asarray(rows), image)
+    c = np.nonzero(image)[0]
+    if len(c):   # the rule's (u, v) of the kept hit, once more, beside the (u, v) the shade lookup reads (_tex_twin.hit_uv): the same bits
+        under = (rec_prim[c] >= first_tri) & (tab is not None)
+        rule_uv = np.zeros((len(c), 2), F)
+        for sel, tuv in ((under, True), (~under, False)):
+            if sel.any():
+                k = c[sel]
+                rule_uv[sel] = keeps(table, quads[qi[k]], tab[rec_prim[k] - first_tri] if tuv else None, rays[k, 0:3], rays[k, 3:6], rec_t[k], cutouts, quads["mat"][qi[k]])[1]
+        shade_uv = XT.hit_uv(world, uv, rays[c], hit[c].astype(np.int32), rec_t[c], rec_prim[c].astype(np.int32), rec_n[c])
+        bump("mask_uv_is_shade_uv", (rule_uv.view(np.uint32) == np.ascontiguousarray(shade_uv, F).view(np.uint32)).all(axis=1))
+
+
+def walk_of(uv, cutouts, table, stats=None, eye=None, marks=None, wrong=None):
     """the walk under these tables as _path_twin.radiance takes one: (world, rays[, preset]) -> (hit, t, prim, normal)"""
-    return lambda world, rays, preset=None, **draws: closest_intersection(world, uv, cutouts, table, rays, preset, stats, eye, **draws)
+    return lambda world, rays, preset=None, **draws: closest_intersection(world, uv, cutouts, table, rays, preset, stats, eye, marks=marks, wrong=wrong, **draws)

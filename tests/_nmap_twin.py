@@ -105,19 +105,20 @@ def apply64(m, dpdu, dpdv, normal):
 
 
 # ---- whole samples: the walk every whole-sample twin calls, with the rule behind it --------------------------------------------------------------------------
-def mapped_walk(world, vn, uv, nmaps, table, rays, preset=None, info=None, **draws):
+def mapped_walk(world, vn, uv, nmaps, table, rays, preset=None, info=None, base=None, **draws):
     """_tri_twin.closest_intersection — behind _smooth_twin's rule when vn, a table of vertex normals, is given — then the normal-map rule on every hit whose
     material's record of nmaps (capi.NORMAL_MAP_DT, one per material) says on: (u, v) by _tex_twin.hit_uv from the normal the walk found, the tangents by the
     kind of surface (a triangle takes its coordinates' whenever the world has a table of them, as the kernels do), the entry of `table` = [(image, wrap,
     filter), ...].  info (a dict): its 'mapped' (hits on a mapped material) and one count per way out of the rule grow, and its 'uv' is what this call hands on
     to radiance(): (given (k,) bool, uv (k, 2), on a sphere (k,) bool) over the k rays — the (u, v) of every hit it mapped, taken from the normal BEFORE the map
-    replaced it, which the image lookup and the roughness map of that hit share (_tex_twin.prefer_walk_uv) — or None when it mapped no hit."""
+    replaced it, which the image lookup and the roughness map of that hit share (_tex_twin.prefer_walk_uv) — or None when it mapped no hit.  base: the walk
+    both rules post-process (default: _tri_twin's), as _smooth_twin.closest_intersection_smooth takes it."""
     if info is not None:
         info["uv"] = None
     if vn is not None and len(vn):
-        hit, t, prim, normal = ST.closest_intersection_smooth(world, vn, rays, preset, **draws)   # draws: the tape and its rows, for a constant medium (_tri_twin)
+        hit, t, prim, normal = ST.closest_intersection_smooth(world, vn, rays, preset, base=base, **draws)   # draws: the tape and its rows, for a constant medium (_tri_twin)
     else:
-        hit, t, prim, normal = ST._flat_walk(world, rays, preset, **draws)
+        hit, t, prim, normal = (ST._flat_walk if base is None else base)(world, rays, preset, **draws)
     prims, quads, mats = world_arrays(world)
     first_tri = len(prims) + int((quads["kind"] == 0).sum())
     mat_of_prim = np.concatenate([(prims["mat"] & ~np.uint32(PRIM_MOVING)), quads["mat"]]).astype(np.int64)
@@ -153,15 +154,16 @@ def mapped_walk(world, vn, uv, nmaps, table, rays, preset=None, info=None, **dra
     return hit, t, prim, normal
 
 
-def walk_of(vn, uv, nmaps, table, info=None):
+def walk_of(vn, uv, nmaps, table, info=None, base=None):
     """(trace, walk) as _path_twin.radiance takes them, for a world with these tables: mapped_walk and the dict its (u, v) travel to radiance() in where there is a
-    normal-map table (nmaps None = none), the smooth walk under a table of vertex normals, _tri_twin's flat walk otherwise"""
+    normal-map table (nmaps None = none), the smooth walk under a table of vertex normals, _tri_twin's flat walk otherwise; base: the walk they post-process
+    in its place — _cutout_twin.walk_of(...), the rule in the leaf phase and then smooth normal and map at the hit the walk kept"""
     if nmaps is not None:
         info = {} if info is None else info
-        return (lambda w, rays, preset=None, **draws: mapped_walk(w, vn, uv, nmaps, table, rays, preset, info, **draws)), info
+        return (lambda w, rays, preset=None, **draws: mapped_walk(w, vn, uv, nmaps, table, rays, preset, info, base, **draws)), info
     if vn is not None and len(vn):
-        return ST.smooth_walk(vn), None
-    return TT.closest_intersection, None
+        return ST.smooth_walk(vn, base=base), None
+    return (TT.closest_intersection if base is None else base), None
 
 
 def tex_of(uv, table):

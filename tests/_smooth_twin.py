@@ -52,12 +52,13 @@ def shading_normal(tris, vn, o, d, t):
         return np.where(took[:, None], s, f).astype(F), took, fallback
 
 
-def closest_intersection_smooth(world, vn, rays, preset=None, info=None, **draws):
+def closest_intersection_smooth(world, vn, rays, preset=None, info=None, base=None, **draws):
     """_tri_twin.closest_intersection, then the rule on the hits whose primitive is a triangle; vn: one record per triangle of the flat world.
     info (a dict): gets added up 'smooth' (hits on triangles with a non-zero record), 'interpolated' and 'fallback2' (of those), and 'fallback1' — every
     triangle hit that `!(l2 > 0)` sends back to the flat normal: all-zero records are the rule's own first case of it, and between three unit normals of one
-    record g vanishes only on a set of measure zero, which no rendered frame meets."""
-    hit, t, prim, normal = _flat_walk(world, rays, preset, **draws)   # draws: the tape and its rows, for a world with a constant medium (_tri_twin)
+    record g vanishes only on a set of measure zero, which no rendered frame meets.  base: the walk this one post-processes (default: _tri_twin's) —
+    _cutout_twin.walk_of(...) for a world under a cutout table, whose rule runs in the leaf phase, before the normal of the hit the walk kept."""
+    hit, t, prim, normal = (_flat_walk if base is None else base)(world, rays, preset, **draws)   # draws: the tape and its rows, for a world with a constant medium (_tri_twin)
     vn = table(vn)
     prims, quads, _ = world_arrays(world)
     first_tri = len(prims) + int((quads["kind"] == 0).sum())
@@ -76,9 +77,9 @@ def closest_intersection_smooth(world, vn, rays, preset=None, info=None, **draws
     return hit, t, prim, normal
 
 
-def smooth_walk(vn, info=None):
+def smooth_walk(vn, info=None, base=None):
     """closest_intersection_smooth under the table vn as a walk (world, rays[, preset]) -> (hit, t, prim, normal), the way the whole-sample twins take one"""
-    return lambda world, rays, preset=None, **draws: closest_intersection_smooth(world, vn, rays, preset, info, **draws)
+    return lambda world, rays, preset=None, **draws: closest_intersection_smooth(world, vn, rays, preset, info, base, **draws)
 
 
 def radiance(world, vn, cam, width, height, max_depth, seed, gids, samples, mode=0, info=None):

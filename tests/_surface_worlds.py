@@ -198,14 +198,16 @@ BUILDERS = ("BuildBVH_SAH", "BuildBVH_TopDown", "MakeHittableList")
 STRENGTHS, ROUGHNESSES, SPECULARS = (0.0, 0.5, 1.0, 2.0), (0.0, 0.01, None, 1.0), (0.0, 0.04, 1.0)   # None: a random roughness
 
 
-def random_surface_world(p, seed, live=False):
+def random_surface_world(p, seed, live=False, before_build=None):
     """One world of the randomised surface test: at most 24 primitives — spheres, parallelograms, free triangles with or without vertex normals and
     coordinates (mirrored ones included) — plus at most one uv_sphere(8, 4) mesh, materials of the kinds the twin follows (Lambertian, checker, image, metal,
     glass, light), a texture table of 2 to 5 random images under random modes, random records of all three kinds, a random builder, a constant background or
     the sky map.  live: the same world — the seed's generator is left as it is — plus, from a generator of its own, a noise material under random
     records on a sphere and a parallelogram, moving spheres of the recorded materials, spheres of constant medium (one about the glass ball), a solid glass box
     with an interior record, and a camera of a random kind: the twin with `media` follows it.  Returns (scene, table, camera, recipe); frames are RW x RH at
-    RSPP spp and depth RDEPTH."""
+    RSPP spp and depth RDEPTH.  before_build(s, materials, table), with live: called before the world is built with the scene, a dict of its materials by role
+    and the texture table, to which it may append what it adds to the scene (tests/_live_worlds.random_masks: cutout records); it draws from no
+    generator of this function."""
     rng = np.random.default_rng(SEED_BASE + seed)
     s = p.Scene()
     table = []
@@ -222,8 +224,15 @@ def random_surface_world(p, seed, live=False):
         table.append((img, wrap, filt))
     n_img = len(table)
     pick = lambda: int(rng.integers(0, n_img))   # noqa: E731
+    image_of = {}   # which image each image material names
+
+    def image_material():
+        k = pick()
+        m = s.ImageTexture(k)
+        image_of[m] = k
+        return m
     surface = [s.Lambertian(rng.random(3)), s.Lambertian(rng.random(3)), s.LambertianTexture(rng.random(3), rng.random(3), float(rng.choice([0.5, 1.3]))),
-               s.ImageTexture(pick()), s.ImageTexture(pick()), s.Metal(rng.random(3), float(rng.choice([0.0, 0.3]))), s.Metal(rng.random(3), 0.1)]
+               image_material(), image_material(), s.Metal(rng.random(3), float(rng.choice([0.0, 0.3]))), s.Metal(rng.random(3), 0.1)]
     glass = [s.Dielectric((1, 1, 1), 1.5), s.Dielectric(0.8 + 0.2 * rng.random(3), 1.33)]
     records = {"normal_maps": 0, "microfacets": 0, "roughness_maps": 0, "rough_glass": 0}
     for m in surface:
@@ -308,6 +317,8 @@ def random_surface_world(p, seed, live=False):
         s.MakeBox(lo, lo + lr.uniform(0.5, 2.0, 3), glass[0], rotate_y=float(lr.uniform(0, 90)))
         s.set_interior(glass[0], sigma=lr.choice([0.0, 0.1, 1.0], 3) * lr.random(3))
         extra = {"moving": n_moving, "media": n_media, "camera": TW.CAMERAS[int(lr.integers(0, 3))]}
+        if before_build is not None:
+            extra["masks"] = before_build(s, dict(surface=surface, image_of=image_of, noise=noise, clear=glass[1]), table)
     env = bool(rng.random() < 0.5)
     if env:
         s.set_environment(EW.sky_map(), rotate_y=EW.SKY_U0_DEGREES)

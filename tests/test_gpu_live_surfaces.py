@@ -161,7 +161,14 @@ def test_the_feature_pass_refuses_the_medium_and_runs_on_the_room_without_it(p, 
         assert e.value.code == 1 and r.kernel_form() == form and r.kernel_interior() and r.kernel_microfacet() and r.normal_maps_info()["enabled"]
         assert r.interiors_info() == {"enabled": True, "records": 1} and r.microfacets_info() == {"enabled": True, "records": 4}
     sums = sums_of(r)   # ... and the renderer is as usable as it was
+    assert bits_equal(sums, tw.frame(LW.ALL, "pinhole").sums)
+    r.enable_aov(full=True)   # the third mode follows the medium: it admits the room as it is, and gives the feature twin's sums
+    assert r.aov_mode() == "full" and r.kernel_form() == form and r.kernel_interior() and r.kernel_microfacet() and r.normal_maps_info()["enabled"]
+    r.refine(SPP)
+    full, sums = r.aov_sums(), r.refine_sums()
     r.close()
+    want = LW.feature_sums(tw, "pinhole")
+    assert bits_equal(full, want), mismatch_report(full, want)
     assert bits_equal(sums, tw.frame(LW.ALL, "pinhole").sums)
     dry = LW.run(False, medium=False)
     r = renderer(p, dry, "pinhole")

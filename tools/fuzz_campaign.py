@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Differential fuzz campaign: random worlds (spheres, moving spheres, quads, triangles and meshes, lights, media, textures; every builder; LDS
 and global-memory paths; three cameras) rendered on the GPU and by the CPU oracle, compared bit for bit.
-    python tools/fuzz_campaign.py --seeds 200 [--first 0] [--no-triangles] [--mesh-lights] [--light-tree] [--texture-coords] [--textures] [--env-tree] [--surfaces [--live]] [--interiors] [--cutouts [--aov-full]]
+    python tools/fuzz_campaign.py --seeds 200 [--first 0] [--no-triangles] [--mesh-lights] [--light-tree] [--texture-coords] [--textures] [--env-tree] [--surfaces [--live]] [--interiors] [--cutouts [--live] [--aov-full]]
 Prints one line per failure and a summary; exit code 1 if anything differed.  The triangles of a world come from a generator of their own, so the rest of a seed's
 world is what it was before the fuzzer made triangles, and --no-triangles renders exactly those earlier worlds.  Importing this file starts nothing:
 world_of_seed() builds a seed's world on the host, without a device.  --mesh-lights (off by default: the recorded campaigns ran without it) also renders every
@@ -17,7 +17,10 @@ itself (both memory forms; every record off against no table); and, per seed, it
 solids, built so that tests/_interior_twin.py follows its every sample, and holds both memory forms to the twin on every pixel.  --cutouts
 renders, per seed, such a second world without the solids, with random masks — lattices and random opacities under random wrap modes, filters and cutoffs — on
 random materials of its parallelograms and triangles, half the time with random texture coordinates on a mesh, and holds both memory forms of the CUT family to
-the walk of tests/_cutout_twin.py on every pixel; with every record off the frame must be the frame without a table."""
+the walk of tests/_cutout_twin.py on every pixel; with every record off the frame must be the frame without a table.  --cutouts --live renders,
+per seed, the live world of --surfaces --live under tests/_live_worlds.random_masks(seed) — random masks on materials of every kind that takes one, one image
+material masked by an alpha of its own picture's size and modes — in both memory forms against the composed twin, which must follow every sample, every record
+off against no table, and with --aov-full its feature sums of mode RT_AOV_FULL against the feature twin."""
 import argparse, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -51,7 +54,8 @@ def parse_args(argv=None):
     ap.add_argument("--texture-coords", action="store_true", help="also render the worlds with an image and triangles under a table of random texture coordinates on random triangles: both memory forms must agree, and the identity table must be the oracle's frame")
     ap.add_argument("--surfaces", action="store_true", help="also render every world under inert normal-map and microfacet tables (flat maps; records that are all off on the materials in use): the NMAP and the MFAC kernel family, both memory forms, must give the oracle's frame; worlds the families refuse (a lane walk, a kernel variant other than 2 and 3) are counted as skipped")
     ap.add_argument("--live", action="store_true", help="with --surfaces: also render, per seed, a world of tests/_surface_worlds.random_surface_world(seed, live=True) — live normal-map, microfacet, rough-glass and interior records beside a constant medium, a noise material and moving spheres under a random camera kind — in both memory forms against the extended whole-sample twin, which must follow every sample; lane walks and kernel variants other than 2 and 3 are counted as skipped")
-    ap.add_argument("--cutouts", action="store_true", help="also render, per seed, a world of its own with random masks on random parallelogram and triangle materials: the CUT kernel family in both memory forms against "
+    ap.add_argument("--cutouts", action="store_true", help="with --live: also render, per seed, the live world of --surfaces --live under random masks (tests/_live_worlds.random_masks) against the composed twin, "
+                    "and with --aov-full its feature sums against the feature twin; lane walks and kernel variants other than 2 and 3 are counted as skipped.  Without --live: also render, per seed, a world of its own with random masks on random parallelogram and triangle materials: the CUT kernel family in both memory forms against "
                     "the twin's walk (tests/_cutout_twin.py), every record off against no table")
     ap.add_argument("--aov-full", action="store_true", help="with --cutouts: also accumulate that world's feature buffers in mode RT_AOV_FULL (DESIGN.md §35), in both memory forms, and hold the sums of every "
                     "pixel to tests/_aov_full_twin.py")
@@ -340,6 +344,63 @@ def live_check(p, seed, variant):
     return ok, forms, int((~followed).sum())
 
 
+def live_cutout_check(p, seed, variant, aov_full):
+    """tests/_live_worlds.random_live_sums(seed, masks=True) on the GPU, in the renderer's own form and the global-memory form, against the composed
+    twin — the cutout rule in the leaf phase, then smooth normal and normal map —, which must follow every sample; in the second form every record off against no
+    table; aov_full: the feature sums of mode RT_AOV_FULL in both forms against tests/_aov_full_twin.py under the world's normal-map table.  None: a variant
+    without the family; else (ok, forms, not followed, candidates the rule turned down)."""
+    import _aov_full_twin as FT
+    import _cutout_twin as CT
+    import _live_worlds as LW
+    import _noise_twin as NZ
+    stats = CT.new_stats()
+    s, cam, (W, H, spp, depth), want, followed, recipe = LW.random_live_sums(p, seed, stats, masks=True)
+    w, table = s.getWorldPtr(), s.cutouts()
+    ok, forms = bool(followed.all()), []
+    features = None
+    if aov_full:
+        world, uv, vn = as_oracle_world(w), s.texture_coords(), s.vertex_normals()
+        tab = NZ.tables(world)
+        features = FT.sums(world, as_oracle_camera(cam), W, H, spp, LW.SEED, uv=uv if uv is not None and len(uv) else None, cutouts=table,
+                           table=LW.AT.twin_table(s.textures()), noise=lambda a, k, pts: NZ.value(tab, np.asarray(a, np.float32), np.float32(k), pts),
+                           vn=vn if vn is not None and len(vn) else None, nmaps=s.normal_maps())
+    for env in ({}, {"RT06_FORCE_BIG": "1"}):
+        os.environ.pop("RT06_FORCE_BIG", None)
+        os.environ.update(env)
+        try:
+            r = p.Renderer.MakeRenderer(W, H, spp, depth, cam, w, seed=LW.SEED, variant=variant)
+        except p.capi.RtError:
+            return None
+        finally:
+            os.environ.pop("RT06_FORCE_BIG", None)
+        if r.kernel_info()["variant"] not in (2, 3) or not r.kernel_cutout():
+            r.close()
+            return None
+        forms.append(r.kernel_form())
+        r.refine(spp)
+        ok = bits_equal(r.refine_sums(), want) and ok
+        if aov_full:   # a renderer of its own, so that the colour frames above and below are those of a renderer without feature buffers
+            os.environ.update(env)
+            try:
+                f = p.Renderer.MakeRenderer(W, H, spp, depth, cam, w, seed=LW.SEED, variant=variant)
+            finally:
+                os.environ.pop("RT06_FORCE_BIG", None)
+            f.enable_aov(full=True)
+            f.refine(spp)
+            ok = f.aov_mode() == "full" and f.kernel_cutout() and bits_equal(f.aov_sums(), features) and bits_equal(f.refine_sums(), want) and ok
+            f.close()
+        if env:
+            r.cutouts(np.zeros(len(table), p.capi.CUTOUT_DT))
+            r.refine(spp)
+            off = r.refine_sums()
+            ok = r.kernel_cutout() and ok
+            r.cutouts(None)
+            r.refine(spp)
+            ok = not r.kernel_cutout() and bits_equal(off, r.refine_sums()) and ok
+        r.close()
+    return ok, forms, int((~followed).sum()), stats["rejected"]
+
+
 def glass_solids(s, rng):
     """a glass sphere, a glass box and a closed glass mesh (half the time with vertex normals) into scene s, with random interior records — at least one — and
     now and then a frosted one, all drawn from rng"""
@@ -577,6 +638,8 @@ def main(argv=None):
     stats = {"lds": 0, "global": 0, "baseline": 0, "xchg": 0, "triangle_worlds": 0, "tri_kernels": 0}
     if args.surfaces:
         stats.update({"surface_worlds": 0, "surface_kernels": 0, "surface_skipped": 0})
+    if args.cutouts and args.live:
+        stats.update({"live_cutout_worlds": 0, "live_cutout_not_followed": 0})
     for seed in range(args.first, args.first + args.seeds):
         s, kinds, builder, big, rng = world_of_seed(p, seed, not args.no_triangles, args.force_variant)
         W, H = int(rng.integers(17, 120)), int(rng.integers(9, 80))
@@ -721,6 +784,18 @@ def main(argv=None):
             if not tw[0]:
                 fails += 1
                 print(f"FAIL seed {seed}: the cutout twin world: forms {tw[1]}", flush=True)
+        if args.cutouts and args.live:   # the live world of the seed under random masks
+            lc = live_cutout_check(p, seed, variant, args.aov_full) if w.traversal == 0 and info["variant"] in (2, 3) else None
+            if lc is None:
+                stats["live_cutout_skipped"] = stats.get("live_cutout_skipped", 0) + 1
+            else:
+                stats["live_cutout_worlds"] = stats.get("live_cutout_worlds", 0) + 1
+                stats["live_cutout_kernels"] = stats.get("live_cutout_kernels", 0) + len(lc[1])
+                stats["live_cutout_not_followed"] = stats.get("live_cutout_not_followed", 0) + lc[2]
+                stats["live_cutout_candidates_turned_down"] = stats.get("live_cutout_candidates_turned_down", 0) + lc[3]
+                if not lc[0]:
+                    fails += 1
+                    print(f"FAIL seed {seed}: the live world under masks: forms {lc[1]}, {lc[2]} samples not followed", flush=True)
         if args.cutouts and args.aov_full:   # the same world under feature buffers
             fa = aov_full_check(p, seed)
             stats["aov_full_worlds"] = stats.get("aov_full_worlds", 0) + 1
