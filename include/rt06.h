@@ -162,11 +162,17 @@ enum { RT_TRAVERSAL_STACK = 0, RT_TRAVERSAL_QUEUE = 1, RT_TRAVERSAL_WIDE4 = 2 };
 enum {
     RT_CAM_PINHOLE = 0,  /* PinholeCamera     cu_Cameras.cuh:12-31 */
     RT_CAM_DEFOCUS = 1,  /* DefocusBlurCamera cu_Cameras.cuh:34-65 */
-    RT_CAM_MOTION = 2    /* MotionBlurCamera  cu_Cameras.cuh:68-90 */
+    RT_CAM_MOTION = 2,   /* MotionBlurCamera  cu_Cameras.cuh:68-90 */
+    /* the lens cameras (below; not in the reference): 3 to 15 and 20 and above stay "unknown camera type" */
+    RT_CAM_PERSPECTIVE = 16,
+    RT_CAM_ORTHOGRAPHIC = 17,
+    RT_CAM_FISHEYE = 18,
+    RT_CAM_PANORAMA = 19
 };
 /* Camera POD, passed by value to the kernel like LaunchParams::cam
  * (Renderer.cu:99-108,117).  For PINHOLE/MOTION u,v are pre-scaled by the
- * viewport; for DEFOCUS they are unit vectors and viewport_* are separate.  */
+ * viewport; for DEFOCUS and the lens cameras they are unit vectors and
+ * viewport_* are separate.                                                  */
 typedef struct rt_camera {
     uint32_t type;
     float o[3], u[3], v[3], w[3];
@@ -186,6 +192,57 @@ int rt_camera_defocus(const float lookfrom[3], const float lookat[3], const floa
                       float vfov, float aspect, float aperture, float focus_dist, rt_camera* out);
 int rt_camera_motion(const float lookfrom[3], const float lookat[3], const float up[3],
                      float vfov, float aspect, float time0, float time1, rt_camera* out);
+
+/* ------------------------------------------------------------------ */
+/* lens cameras — a projection, an optional thin lens and an optional shutter on one record.  Not in the reference, whose three
+ * types exclude each other (DefocusBlurCamera has no time, MotionBlurCamera no lens).  The record keeps its 76 bytes:
+ *   o, u, v, w                       the UNIT basis of DefocusBlurCamera's constructor (w = towards lookat, u = normalize(cross(up, w)), v = cross(w, u))
+ *   viewport_width, viewport_height  the projection's two parameters (a, b), below
+ *   lens_radius, focus_dist          the lens; lens_radius == 0: no lens and no lens draw
+ *   t0, t1                           the shutter; t0 == t1: every ray has time t0 and there is no time draw
+ * (a, b):  PERSPECTIVE   tan(vfov / 2) * aspect, tan(vfov / 2)              (what DEFOCUS stores)
+ *          ORTHOGRAPHIC  half width, half height of the view window in world units
+ *          FISHEYE       equidistant; b = radians(fov) / 2 across the image's height, a = b * aspect; sqrt(a^2 + b^2) < pi (the frame's corner stays
+ *                        short of the back pole); no circular mask, every pixel of the rectangle has a ray
+ *          PANORAMA      equirectangular; half horizontal and half vertical span in radians, 0 < a <= pi, 0 < b <= pi / 2; full: (pi, pi / 2)
+ * THE RULE (lens_camera_draw / lens_camera_ray, csrc/rt_device_funcs.hpp), in fp32, every operation rounded on its own (no contraction), + - * / sqrt,
+ * comparisons and the library's rt_sinf only; cos x = sin(x + 0x1.921fb6p+0f), where sin is rt_sinf throughout.  (s, t) = the jittered NDC point of a sample.  Vector expressions are
+ * per component; a sum of three terms is (first + second) + third.
+ *   draws, in this order: the pixel jitter (InUnit<2>); the lens point (la, lb) (InUnit<2>) iff lens_radius > 0; one uniform x iff t0 != t1.
+ *   time = t0 * (1 - x) + t1 * x, or t0.
+ *   off  = (u * la + v * lb) * lens_radius                                   (with a lens)
+ *   PERSPECTIVE without a lens:  ray.o = o,        ray.d = (w + (u * a) * s) + (v * b) * t
+ *   PERSPECTIVE with a lens:     ray.o = o + off,  ray.d = ((w * focus_dist + ((u * a) * focus_dist) * s) + ((v * b) * focus_dist) * t) - off
+ *                                (DefocusBlurCamera::sample_ray's own order, cu_Cameras.cuh:54-64)
+ *   the others:  (o0, d0) from the projection;  ray.o = o0 + off, ray.d = d0 * focus_dist - off  with a lens;  ray.o = o0, ray.d = d0  without
+ *   ORTHOGRAPHIC  o0 = (o + (u * a) * s) + (v * b) * t,  d0 = w
+ *   FISHEYE       x = a * s, y = b * t, th = sqrt(x * x + y * y);  th == 0: d0 = w;  else k = sin(th) / th,
+ *                 d0 = (w * cos th + u * (x * k)) + v * (y * k)
+ *   PANORAMA      ph = a * s, lm = b * t, cl = cos lm;  d0 = (w * (cl * cos ph) + u * (cl * sin(ph))) + v * sin(lm)
+ * Directions are not normalised, as the reference's are not.  Two equivalences, bit for bit in rays and draws: a DEFOCUS record with type = 16 and
+ * t0 = t1 = 0 is that DEFOCUS camera; a PINHOLE (also t0 = t1 = 0) or MOTION record with type = 16, viewport_* = 1, lens_radius = 0 is that camera.
+ * Orientation of a panorama: looking along +x with +y up, u is -z, and a full panorama sees an unrotated environment map texel for texel (the frame's
+ * row 0 is the bottom, the map's row 0 the top).
+ * The constructors take aperture = 2 * lens_radius like rt_camera_defocus; orthographic: the window's full height and its aspect; fisheye: the angle across
+ * the image's height in degrees and the aspect; panorama: the full spans in degrees.  They and, for these four types, rt_renderer_create / _set_camera and
+ * the rt_multi_renderer twins validate: every field finite, a, b > 0, lens_radius >= 0, focus_dist > 0 where there is a lens, the bounds above.  A refused
+ * call changes nothing and names the field.
+ * Rendered by every streaming variant (0, 2 to 6) — their primary rays come from primary_rays_lens_kernel — with feature buffers, refinement, run-ahead, light
+ * sampling and rt_multi_renderer.  Refused by the baseline kernel (variant 1, and worlds only it renders), rt_probe_radiance, rt_probe_camera(_tape). */
+/* ------------------------------------------------------------------ */
+int rt_camera_perspective(const float lookfrom[3], const float lookat[3], const float up[3], float vfov, float aspect,
+                          float aperture, float focus_dist, float time0, float time1, rt_camera* out);
+int rt_camera_orthographic(const float lookfrom[3], const float lookat[3], const float up[3], float height, float aspect,
+                           float aperture, float focus_dist, float time0, float time1, rt_camera* out);
+int rt_camera_fisheye(const float lookfrom[3], const float lookat[3], const float up[3], float fov, float aspect,
+                      float aperture, float focus_dist, float time0, float time1, rt_camera* out);
+int rt_camera_panorama(const float lookfrom[3], const float lookat[3], const float up[3], float hspan_degrees, float vspan_degrees,
+                       float aperture, float focus_dist, float time0, float time1, rt_camera* out);
+/* HOST (no GPU): the camera's rule on given cases, any of the seven types (the old three through camera_sample_ray): st n*2, uniforms from `tape` as
+ * rt_probe_camera_tape takes them (case i draws tape[offsets[2i] ..] for offsets[2i+1] uniforms) -> ray n*7 (o, d, time), uniforms consumed n.  The
+ * pixel jitter is the caller's: (s, t) is given.                                                                                                    */
+int rt_camera_rays_batch(const rt_camera* cam, size_t n, const float* st, const uint32_t* tape, size_t tape_len,
+                         const uint32_t* offsets, float* out_rays, uint32_t* out_draws);
 
 /* ------------------------------------------------------------------ */
 /* scene construction — host side, replaces SphereHandle / newOnDevice /
@@ -621,7 +678,7 @@ int rt_renderer_create(const rt_render_config* cfg, const rt_camera* cam,
 void rt_renderer_destroy(rt_renderer* r);
 
 /* `params.cam = *m.cam;` of Renderer::Render (Renderer.cu:117): the camera of every launch from now on (render, render_async,
- * refine*).  Validated as in rt_renderer_create (NULL, type > RT_CAM_MOTION: RT_ERR_INVALID, renderer unchanged).  The camera travels
+ * refine*).  Validated as in rt_renderer_create (NULL, an unknown type, a bad lens-camera field, a lens camera on the baseline kernel: RT_ERR_INVALID, renderer unchanged).  The camera travels
  * BY VALUE in the kernel arguments, so a launch that is already enqueued keeps the camera it was given.  A camera whose bytes differ
  * from the current one discards the refinement state (samples accumulated -> 0); the same bytes keep it.  The world, the per-pass
  * buffers and the streams are untouched: this is what an animation loop calls instead of destroy + create.                          */
@@ -1159,6 +1216,9 @@ int rt_probe_scatter_tape(int device, size_t n, const rt_material* mats, const f
                           const float* normals, const uint32_t* tape, size_t tape_len, const uint32_t* offsets,
                           int32_t* out_scattered, float* out_rays, float* out_atten, uint32_t* out_draws);
 int rt_probe_camera_tape(int device, const rt_camera* cam, size_t n, const float* st, const uint32_t* tape,
+                         size_t tape_len, const uint32_t* offsets, float* out_rays, uint32_t* out_draws);
+/* the lens cameras' rule (types 16 to 19 only) on the device, one lane per case: what rt_camera_rays_batch computes on the host */
+int rt_probe_camera_lens(int device, const rt_camera* cam, size_t n, const float* st, const uint32_t* tape,
                          size_t tape_len, const uint32_t* offsets, float* out_rays, uint32_t* out_draws);
 /* one full sample (render_kernel body for one s + sample_world,
  * Renderer.cu:139-181,198-204): keys n*2 (pixel gid, sample) -> radiance n*3 */

@@ -581,6 +581,42 @@ struct MotionBlurCamera {
         rt06::check(rt_camera_motion(a, b, c, vfov, aspect_ratio, time0, time1, &cam), "MotionBlurCamera");
     }
 };
+// The lens cameras (extension; rt06.h): one record, a projection with an optional thin lens (aperture > 0) and an optional shutter (time0 != time1).
+// The named constructors validate as the C constructors do and throw what they refuse.
+struct LensCamera {
+    rt_camera cam{};
+    LensCamera() = default;
+    static LensCamera Perspective(glm::vec3 lookfrom, glm::vec3 lookat, glm::vec3 up, float vfov, float aspect_ratio, float aperture = 0.0f, float focus_dist = 1.0f,
+                                  float time0 = 0.0f, float time1 = 0.0f) {
+        return make(rt_camera_perspective, "LensCamera::Perspective", lookfrom, lookat, up, vfov, aspect_ratio, aperture, focus_dist, time0, time1);
+    }
+    // height: the view window's full height in world units
+    static LensCamera Orthographic(glm::vec3 lookfrom, glm::vec3 lookat, glm::vec3 up, float height, float aspect_ratio, float aperture = 0.0f, float focus_dist = 1.0f,
+                                   float time0 = 0.0f, float time1 = 0.0f) {
+        return make(rt_camera_orthographic, "LensCamera::Orthographic", lookfrom, lookat, up, height, aspect_ratio, aperture, focus_dist, time0, time1);
+    }
+    // equidistant; fov: degrees across the image's height
+    static LensCamera Fisheye(glm::vec3 lookfrom, glm::vec3 lookat, glm::vec3 up, float fov, float aspect_ratio, float aperture = 0.0f, float focus_dist = 1.0f,
+                              float time0 = 0.0f, float time1 = 0.0f) {
+        return make(rt_camera_fisheye, "LensCamera::Fisheye", lookfrom, lookat, up, fov, aspect_ratio, aperture, focus_dist, time0, time1);
+    }
+    // equirectangular; the full sphere by default: looking along +x with +y up it is an unrotated environment map
+    static LensCamera Panorama(glm::vec3 lookfrom, glm::vec3 lookat, glm::vec3 up, float hspan_degrees = 360.0f, float vspan_degrees = 180.0f, float aperture = 0.0f,
+                               float focus_dist = 1.0f, float time0 = 0.0f, float time1 = 0.0f) {
+        return make(rt_camera_panorama, "LensCamera::Panorama", lookfrom, lookat, up, hspan_degrees, vspan_degrees, aperture, focus_dist, time0, time1);
+    }
+
+  private:
+    typedef int (*Ctor)(const float[3], const float[3], const float[3], float, float, float, float, float, float, rt_camera*);
+    static LensCamera make(Ctor ctor, const char* what, glm::vec3 lookfrom, glm::vec3 lookat, glm::vec3 up, float p0, float p1, float aperture, float focus_dist,
+                           float time0, float time1) {
+        LensCamera c;
+        float a[3], b[3], d[3];
+        rt06::v3(lookfrom, a); rt06::v3(lookat, b); rt06::v3(up, d);
+        rt06::check(ctor(a, b, d, p0, p1, aperture, focus_dist, time0, time1, &c.cam), what);
+        return c;
+    }
+};
 
 // the modes of Renderer::SetLightSampling (RT_LIGHT_SAMPLING_* of rt06.h)
 enum class LightSampling : uint32_t { Off = RT_LIGHT_SAMPLING_OFF, Quads = RT_LIGHT_SAMPLING_QUADS, All = RT_LIGHT_SAMPLING_ALL, Mesh = RT_LIGHT_SAMPLING_MESH,
@@ -718,6 +754,12 @@ public:
     }
     static Renderer MakeRenderer(uint32_t render_width, uint32_t render_height, uint32_t samples_per_pixel, uint32_t max_depth,
                                  const PinholeCamera* cam, const Hittable* d_world_ptr, uint64_t seed = 1984, int device = 0, uint32_t n_gpus = 1,
+                                 uint32_t variant = 0) {
+        return make(render_width, render_height, samples_per_pixel, max_depth, &cam->cam, d_world_ptr, seed, device, n_gpus, variant);
+    }
+    // a lens camera: kept and read at every Render() / Refine() like the other three; the baseline kernel (variant 1) refuses it
+    static Renderer MakeRenderer(uint32_t render_width, uint32_t render_height, uint32_t samples_per_pixel, uint32_t max_depth,
+                                 const LensCamera* cam, const Hittable* d_world_ptr, uint64_t seed = 1984, int device = 0, uint32_t n_gpus = 1,
                                  uint32_t variant = 0) {
         return make(render_width, render_height, samples_per_pixel, max_depth, &cam->cam, d_world_ptr, seed, device, n_gpus, variant);
     }

@@ -33,6 +33,34 @@ def MotionBlurCamera(lookfrom, lookat, up, vfov, aspect_ratio, time0, time1):
     return c
 
 
+# The lens cameras (rt06.h): a projection with an optional thin lens (aperture > 0) and an optional shutter (time0 != time1) on one record.
+# Rendered by the streaming variants; the baseline kernel (variant 1) refuses them.
+def _lens_camera(ctor, lookfrom, lookat, up, p0, p1, aperture, focus_dist, time0, time1):
+    c = Camera()
+    check(ctor(v3(lookfrom), v3(lookat), v3(up), p0, p1, aperture, focus_dist, time0, time1, C.byref(c)))
+    return c
+
+
+def PerspectiveCamera(lookfrom, lookat, up, vfov, aspect_ratio, aperture=0.0, focus_dist=1.0, time0=0.0, time1=0.0):
+    """rt_camera_perspective: DefocusBlurCamera's basis and viewport, with a shutter."""
+    return _lens_camera(lib().rt_camera_perspective, lookfrom, lookat, up, vfov, aspect_ratio, aperture, focus_dist, time0, time1)
+
+
+def OrthographicCamera(lookfrom, lookat, up, height, aspect_ratio, aperture=0.0, focus_dist=1.0, time0=0.0, time1=0.0):
+    """rt_camera_orthographic: parallel rays along lookat - lookfrom through a window `height` world units tall."""
+    return _lens_camera(lib().rt_camera_orthographic, lookfrom, lookat, up, height, aspect_ratio, aperture, focus_dist, time0, time1)
+
+
+def FisheyeCamera(lookfrom, lookat, up, fov, aspect_ratio, aperture=0.0, focus_dist=1.0, time0=0.0, time1=0.0):
+    """rt_camera_fisheye: equidistant, `fov` degrees across the image's height; no circular mask."""
+    return _lens_camera(lib().rt_camera_fisheye, lookfrom, lookat, up, fov, aspect_ratio, aperture, focus_dist, time0, time1)
+
+
+def PanoramaCamera(lookfrom, lookat, up, hspan_degrees=360.0, vspan_degrees=180.0, aperture=0.0, focus_dist=1.0, time0=0.0, time1=0.0):
+    """rt_camera_panorama: equirectangular; the full sphere by default, oriented like an unrotated environment map when looking along +x with +y up."""
+    return _lens_camera(lib().rt_camera_panorama, lookfrom, lookat, up, hspan_degrees, vspan_degrees, aperture, focus_dist, time0, time1)
+
+
 class Scene:
     """Host scene: what SphereHandle / newOnDevice<Material> / BVH_Handle::Factory / HittableList /
     bvh_node build in the reference, kept as flat arrays."""
@@ -1218,6 +1246,32 @@ def probe_camera_tape(cam, st, tape, offsets, device=0):
     orays = np.zeros((n, 7), np.float32); draws = np.zeros(n, np.uint32)
     check(lib().rt_probe_camera_tape(device, C.byref(cam), n, np.ascontiguousarray(st, np.float32), tape, len(tape),
                                      np.ascontiguousarray(offsets, np.uint32), orays, draws))
+    return orays, draws
+
+
+def _tape_or_one(tape):
+    tape = np.ascontiguousarray(tape, np.uint32)
+    return tape if len(tape) else np.array([0x800001], np.uint32), len(tape)   # an empty tape still needs an address
+
+
+def camera_rays_batch(cam, st, tape, offsets):
+    """rt_camera_rays_batch (HOST, no GPU): the camera's rule, any of the seven types, on given (s, t) with uniforms from `tape` as
+    probe_camera_tape takes them -> rays (n, 7) = (o, d, time), uniforms consumed (n,)"""
+    n = len(st)
+    tape, tape_len = _tape_or_one(tape)
+    orays = np.zeros((n, 7), np.float32); draws = np.zeros(n, np.uint32)
+    check(lib().rt_camera_rays_batch(C.byref(cam), n, np.ascontiguousarray(st, np.float32).reshape(-1), tape, tape_len,
+                                     np.ascontiguousarray(offsets, np.uint32).reshape(-1), orays, draws))
+    return orays, draws
+
+
+def probe_camera_lens(cam, st, tape, offsets, device=0):
+    """rt_probe_camera_lens: camera_rays_batch for a lens camera (types 16 to 19) on the device, one lane per case"""
+    n = len(st)
+    tape, tape_len = _tape_or_one(tape)
+    orays = np.zeros((n, 7), np.float32); draws = np.zeros(n, np.uint32)
+    check(lib().rt_probe_camera_lens(device, C.byref(cam), n, np.ascontiguousarray(st, np.float32).reshape(-1), tape, tape_len,
+                                     np.ascontiguousarray(offsets, np.uint32).reshape(-1), orays, draws))
     return orays, draws
 
 

@@ -125,6 +125,7 @@ SYMBOLS = [
     "rt_renderer_interiors", "rt_renderer_interiors_info", "rt_renderer_kernel_interior", "rt_multi_renderer_interiors",
     "rt_scene_set_cutout", "rt_scene_clear_cutout", "rt_scene_cutouts", "rt_cutout_batch", "rt_probe_cutout", "rt_renderer_cutouts", "rt_renderer_cutouts_info",
     "rt_renderer_kernel_cutout", "rt_multi_renderer_cutouts", "rt_multi_renderer_cutouts_info",
+    "rt_camera_perspective", "rt_camera_orthographic", "rt_camera_fisheye", "rt_camera_panorama", "rt_camera_rays_batch", "rt_probe_camera_lens",
 ]
 
 _lib = None
@@ -198,6 +199,8 @@ def lib():
     L.rt_camera_pinhole.argtypes = [vec3, vec3, vec3, C.c_float, C.c_float, P(Camera)]
     L.rt_camera_defocus.argtypes = [vec3, vec3, vec3, C.c_float, C.c_float, C.c_float, C.c_float, P(Camera)]
     L.rt_camera_motion.argtypes = [vec3, vec3, vec3, C.c_float, C.c_float, C.c_float, C.c_float, P(Camera)]
+    for name in ("rt_camera_perspective", "rt_camera_orthographic", "rt_camera_fisheye", "rt_camera_panorama"):
+        getattr(L, name).argtypes = [vec3, vec3, vec3] + [C.c_float] * 6 + [P(Camera)]
     L.rt_scene_create.argtypes = [P(C.c_void_p)]
     L.rt_scene_destroy.argtypes = [C.c_void_p]
     L.rt_scene_destroy.restype = None
@@ -368,6 +371,8 @@ def lib():
     L.rt_probe_sphere_hit.argtypes = [C.c_int, C.c_size_t, C.c_void_p, f32p, f32p, i32p, f32p, f32p]
     L.rt_probe_scatter_tape.argtypes = [C.c_int, C.c_size_t, C.c_void_p, f32p, f32p, f32p, u32p, C.c_size_t, u32p, i32p, f32p, f32p, u32p]
     L.rt_probe_camera_tape.argtypes = [C.c_int, P(Camera), C.c_size_t, f32p, u32p, C.c_size_t, u32p, f32p, u32p]
+    L.rt_probe_camera_lens.argtypes = [C.c_int, P(Camera), C.c_size_t, f32p, u32p, C.c_size_t, u32p, f32p, u32p]
+    L.rt_camera_rays_batch.argtypes = [P(Camera), C.c_size_t, f32p, u32p, C.c_size_t, u32p, f32p, u32p]
     L.rt_probe_radiance.argtypes = [P(RenderConfig), P(Camera), P(WorldFlat), C.c_size_t, u32p, f32p]
     L.rt_probe_sphere_index.argtypes = [C.c_int, P(Camera), C.c_uint32, C.c_uint32, C.c_size_t, f32p, i32p]
     L.rt_probe_rng.argtypes = [C.c_int, C.c_uint64, C.c_size_t, u32p, C.c_uint32, f32p]

@@ -90,6 +90,16 @@ static uint32_t stream_kernel_key(uint32_t variant, bool tol, const DeviceScene&
     return stream_key(variant == 2, variant == 4, RT_WORLD_BVH);
 }
 
+// The ray generator of a lens camera (types 16 to 19, validated by rt_camera_check): one of primary_rays_lens_kernel's sixteen forms, read off the record
+typedef void (*PrimaryRaysLensKernel)(StreamParams, uint32_t);
+static PrimaryRaysLensKernel primary_rays_lens_kernel_for(const rt_camera& c) {
+#define RT_LENS_FORMS(proj) \
+    primary_rays_lens_kernel<proj, false, false>, primary_rays_lens_kernel<proj, false, true>, primary_rays_lens_kernel<proj, true, false>, primary_rays_lens_kernel<proj, true, true>
+    static const PrimaryRaysLensKernel forms[16] = {RT_LENS_FORMS(0u), RT_LENS_FORMS(1u), RT_LENS_FORMS(2u), RT_LENS_FORMS(3u)};
+#undef RT_LENS_FORMS
+    return forms[((c.type - RT_CAM_PERSPECTIVE) & 3u) * 4u + (lens_camera_has_lens(c) ? 2u : 0u) + (lens_camera_has_shutter(c) ? 1u : 0u)];
+}
+
 // Every shipped instantiation, once, a family per line, in the order the code object has them (a key listed twice does not compile).
 // stream_kernel_key() yields no other key, so the default is never taken.
 static const void* stream_kernel_for(uint32_t key) {
@@ -833,7 +843,9 @@ struct rt_renderer {
             static const uint32_t primary_lds = [] { const char* e = std::getenv("RT06_PRIMARY_LDS"); return e ? (uint32_t)std::atoi(e) : 0u; }();
             for (uint32_t b0 = 0; b0 < tm.n_local_tiles; b0 += 65535u) {   // grid.y = 64-pixel block, at most 65535 per launch
                 const uint32_t nb = std::min(65535u, tm.n_local_tiles - b0);
-                primary_rays_kernel<<<dim3((64u * p.pass_spp + 255u) / 256u, nb), 256, primary_lds, gs>>>(p, b0);
+                const dim3 pgrid((64u * p.pass_spp + 255u) / 256u, nb);
+                if (p.cam.type >= RT_CAM_PERSPECTIVE) hipLaunchKernelGGL(primary_rays_lens_kernel_for(p.cam), pgrid, dim3(256), primary_lds, gs, p, b0);   // this launch's camera: it may change between queued frames
+                else primary_rays_kernel<<<pgrid, 256, primary_lds, gs>>>(p, b0);
                 HIP_TRY(hipGetLastError());
             }
             void* args[] = {&p};
@@ -1001,13 +1013,21 @@ static bool another_renderer_busy(const rt_renderer* self) {
     return false;
 }
 
+// The lens cameras exist in the streaming kernels' ray generator only: the baseline kernel calls camera_sample_ray itself
+static int lens_camera_variant_check(const char* who, uint32_t variant, const rt_camera* cam) {
+    if (cam->type >= RT_CAM_PERSPECTIVE && variant < 2)
+        return rt_fail(RT_ERR_INVALID, "%s: the baseline kernel (variant 1) samples the reference's three cameras inside the kernel and knows no lens camera (type %u): "
+                       "use a streaming variant (0, or 2 to 6) on a world that streams", who, cam->type);
+    return RT_OK;
+}
+
 extern "C" int rt_renderer_create(const rt_render_config* cfg, const rt_camera* cam, const rt_world_flat* world, rt_renderer** out) {
     if (!cfg || !cam || !world || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_create: null argument");
     if (cfg->width == 0 || cfg->height == 0 || cfg->samples_per_pixel == 0)
         return rt_fail(RT_ERR_INVALID, "rt_renderer_create: width, height and samples_per_pixel must be > 0");
     if ((uint64_t)cfg->width * cfg->height > 0x7fffffffull) return rt_fail(RT_ERR_INVALID, "rt_renderer_create: image too large");
     if (cfg->world_size == 0 || cfg->rank >= cfg->world_size) return rt_fail(RT_ERR_INVALID, "rt_renderer_create: bad rank %u / world_size %u", cfg->rank, cfg->world_size);
-    if (cam->type > RT_CAM_MOTION) return rt_fail(RT_ERR_INVALID, "rt_renderer_create: unknown camera type %u", cam->type);
+    if (const int crc = rt_camera_check("rt_renderer_create", cam)) return crc;
     int rc = select_device(cfg->device);
     if (rc != RT_OK) return rc;
     rt_renderer* r = new rt_renderer();
@@ -1047,6 +1067,7 @@ extern "C" int rt_renderer_create(const rt_render_config* cfg, const rt_camera* 
     if (e == hipSuccess) e = r->slot[0].work_counter.alloc(256);
     if (e == hipSuccess) {
         rc = r->plan();
+        if (rc == RT_OK) rc = lens_camera_variant_check("rt_renderer_create", r->variant, cam);
         if (rc != RT_OK) { delete r; return rc; }
     }
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking);
@@ -1123,7 +1144,8 @@ static int download_tile_major(rt_renderer* r, const DevBuf& src, uint32_t fpp, 
 
 extern "C" int rt_renderer_set_camera(rt_renderer* r, const rt_camera* cam) {
     if (!r || !cam) return rt_fail(RT_ERR_INVALID, "rt_renderer_set_camera: null argument");
-    if (cam->type > RT_CAM_MOTION) return rt_fail(RT_ERR_INVALID, "rt_renderer_set_camera: unknown camera type %u", cam->type);
+    if (const int rc = rt_camera_check("rt_renderer_set_camera", cam)) return rc;
+    if (const int rc = lens_camera_variant_check("rt_renderer_set_camera", r->variant, cam)) return rc;
     if (std::memcmp(&r->cam, cam, sizeof(rt_camera)) == 0) return RT_OK;   // the same bytes: nothing moves, the refinement goes on
     r->cam = *cam;          // travels by value in the kernel arguments of the NEXT launch; launches already enqueued keep theirs (those that run ahead too: no drain)
     r->refine_done = 0;     // samples accumulated under another camera belong to another frame

@@ -874,6 +874,78 @@ RT_HD Ray camera_sample_ray(const rt_camera& c, float s, float t, G& rng) {
     return camera_ray(c, s, t, a, b);
 }
 
+// The lens cameras (rt06.h: RT_CAM_PERSPECTIVE .. RT_CAM_PANORAMA): a projection, an optional thin lens and an optional shutter on ONE record.
+// u, v, w are the unit basis, (viewport_width, viewport_height) = the projection's (a, b).  Like sample_ray above in two halves: lens_camera_draw consumes the
+// uniforms (the lens point InUnit<2> iff lens_radius > 0, then one uniform -> time iff t0 != t1), lens_camera_ray is the arithmetic.  Only + - * / sqrt,
+// comparisons and rt_sinf, each rounded on its own; cos x = rt_sinf(x + pi/2) as environment_sample writes it.  Directions are not normalised.
+// proj = type - RT_CAM_PERSPECTIVE and lens = (lens_radius > 0) are arguments so that primary_rays_lens_kernel passes them as constants; the host and the probe
+// pass what the record says.  PERSPECTIVE with a lens keeps DefocusBlurCamera's own expression order (camera_ray above), without one PinholeCamera's: a
+// DEFOCUS record with type 16 and t0 = t1 = 0, and a PINHOLE / MOTION record with type 16, viewport 1 and no lens, give those cameras' rays bit for bit.
+RT_HD bool lens_camera_has_lens(const rt_camera& c) { return c.lens_radius > 0.0f; }
+RT_HD bool lens_camera_has_shutter(const rt_camera& c) { return c.t0 != c.t1; }
+template <class G>
+RT_HD void lens_camera_draw(const rt_camera& c, bool lens, bool shutter, G& rng, float& la, float& lb, float& time) {
+    la = 0.0f; lb = 0.0f;
+    if (lens) rng_in_unit2(rng, la, lb);
+    time = shutter ? mix(c.t0, c.t1, rng.next()) : c.t0;
+}
+RT_HD Ray lens_camera_ray(const rt_camera& c, uint32_t proj, bool lens, float s, float t, float la, float lb, float time) {
+    Ray r;
+    const f3 o = mk3(c.o[0], c.o[1], c.o[2]), u = mk3(c.u[0], c.u[1], c.u[2]);
+    const f3 v = mk3(c.v[0], c.v[1], c.v[2]), w = mk3(c.w[0], c.w[1], c.w[2]);
+    const float a = c.viewport_width, b = c.viewport_height;
+    const float half_pi = 0x1.921fb6p+0f;
+    r.time = time;
+    f3 offset = mk3(0.0f);
+    if (lens) {
+        offset = u * la + v * lb;
+        offset = offset * c.lens_radius;
+    }
+    if (proj == 0u) {
+        if (lens) {   // cu_Cameras.cuh:54-64, term for term
+            const f3 forward = w * c.focus_dist;
+            const f3 hori = u * a * c.focus_dist;
+            const f3 vert = v * b * c.focus_dist;
+            r.o = o + offset;
+            r.d = forward + hori * s + vert * t - offset;
+        } else {      // cu_Cameras.cuh:27-30 with u, v scaled here
+            r.o = o;
+            r.d = w + (u * a) * s + (v * b) * t;
+        }
+        return r;
+    }
+    f3 o0 = o, d0 = w;
+    if (proj == RT_CAM_ORTHOGRAPHIC - RT_CAM_PERSPECTIVE) {
+        o0 = o + (u * a) * s + (v * b) * t;
+    } else if (proj == RT_CAM_FISHEYE - RT_CAM_PERSPECTIVE) {   // equidistant: the angle off the axis is the distance from the centre
+        const float x = a * s, y = b * t;
+        const float theta = sqrtf(x * x + y * y);
+        if (theta != 0.0f) {
+            const float k = rt_sinf(theta) / theta;
+            d0 = w * rt_sinf(theta + half_pi) + u * (x * k) + v * (y * k);
+        }
+    } else {                                                     // equirectangular: longitude a s about v, latitude b t
+        const float phi = a * s, lam = b * t;
+        const float cl = rt_sinf(lam + half_pi);
+        d0 = w * (cl * rt_sinf(phi + half_pi)) + u * (cl * rt_sinf(phi)) + v * rt_sinf(lam);
+    }
+    if (lens) {
+        r.o = o0 + offset;
+        r.d = d0 * c.focus_dist - offset;
+    } else {
+        r.o = o0;
+        r.d = d0;
+    }
+    return r;
+}
+template <class G>
+RT_HD Ray lens_camera_sample_ray(const rt_camera& c, float s, float t, G& rng) {
+    const bool lens = lens_camera_has_lens(c);
+    float la, lb, time;
+    lens_camera_draw(c, lens, lens_camera_has_shutter(c), rng, la, lb, time);
+    return lens_camera_ray(c, c.type - RT_CAM_PERSPECTIVE, lens, s, t, la, lb, time);
+}
+
 // sample_world, main/src/Renderer.cu:139-181.  The emission / background hooks are the reference's own commented
 // placeholders (`accum_radiance`, Renderer.cu:142,152,157,163,179); with no emissive material and background 0 this
 // is exactly the live function.

@@ -90,6 +90,66 @@ extern "C" int rt_camera_motion(const float lookfrom[3], const float lookat[3], 
     return RT_OK;
 }
 
+// the lens cameras (rt06.h): what a record of type 16 to 19 must satisfy; the three reference types pass as they always did
+int rt_camera_check(const char* who, const rt_camera* c) {
+    if (c->type <= RT_CAM_MOTION) return RT_OK;
+    if (c->type < RT_CAM_PERSPECTIVE || c->type > RT_CAM_PANORAMA) return rt_fail(RT_ERR_INVALID, "%s: unknown camera type %u", who, c->type);
+    const struct { const char* name; const float* p; int n; } fields[] = {
+        {"o", c->o, 3}, {"u", c->u, 3}, {"v", c->v, 3}, {"w", c->w, 3}, {"viewport_width", &c->viewport_width, 1}, {"viewport_height", &c->viewport_height, 1},
+        {"lens_radius", &c->lens_radius, 1}, {"focus_dist", &c->focus_dist, 1}, {"t0", &c->t0, 1}, {"t1", &c->t1, 1}};
+    for (const auto& f : fields)
+        for (int k = 0; k < f.n; k++)
+            if (!std::isfinite(f.p[k])) return rt_fail(RT_ERR_INVALID, "%s: camera field %s is not finite", who, f.name);
+    const float a = c->viewport_width, b = c->viewport_height;
+    if (!(a > 0.0f)) return rt_fail(RT_ERR_INVALID, "%s: camera field viewport_width (the projection's first parameter) must be > 0, is %g", who, (double)a);
+    if (!(b > 0.0f)) return rt_fail(RT_ERR_INVALID, "%s: camera field viewport_height (the projection's second parameter) must be > 0, is %g", who, (double)b);
+    if (c->lens_radius < 0.0f) return rt_fail(RT_ERR_INVALID, "%s: camera field lens_radius must be >= 0, is %g", who, (double)c->lens_radius);
+    if (c->lens_radius > 0.0f && !(c->focus_dist > 0.0f))
+        return rt_fail(RT_ERR_INVALID, "%s: camera field focus_dist must be > 0 where there is a lens, is %g", who, (double)c->focus_dist);
+    const double pi = 3.14159265358979323846;
+    if (c->type == RT_CAM_FISHEYE && std::sqrt((double)a * a + (double)b * b) >= pi)
+        return rt_fail(RT_ERR_INVALID, "%s: camera fields viewport_width, viewport_height: a fisheye's corner angle sqrt(a^2 + b^2) = %g must stay below pi", who,
+                       std::sqrt((double)a * a + (double)b * b));
+    // pi and pi / 2 as fp32 holds them: what radians(360) / 2 and radians(180) / 2 give
+    if (c->type == RT_CAM_PANORAMA && a > 0x1.921fb6p+1f) return rt_fail(RT_ERR_INVALID, "%s: camera field viewport_width: a panorama's half horizontal span must be <= pi, is %g", who, (double)a);
+    if (c->type == RT_CAM_PANORAMA && b > 0x1.921fb6p+0f) return rt_fail(RT_ERR_INVALID, "%s: camera field viewport_height: a panorama's half vertical span must be <= pi / 2, is %g", who, (double)b);
+    return RT_OK;
+}
+// one body for the four constructors: rt_camera_defocus's basis, then the projection's (a, b), the lens and the shutter; *out is written only when the record is valid
+static int lens_camera(const char* who, uint32_t type, const float lookfrom[3], const float lookat[3], const float up[3], float vfov, float aspect, bool own_ab, float a,
+                       float b, float aperture, float focus_dist, float time0, float time1, rt_camera* out) {
+    if (!lookfrom || !lookat || !up || !out) return rt_fail(RT_ERR_INVALID, "%s: null argument", who);
+    rt_camera c;
+    camera_basis(lookfrom, lookat, up, vfov, aspect, false, &c);
+    c.type = type;
+    if (own_ab) { c.viewport_width = a; c.viewport_height = b; }
+    c.lens_radius = aperture * 0.5f;
+    c.focus_dist = focus_dist;
+    c.t0 = time0; c.t1 = time1;
+    if (const int rc = rt_camera_check(who, &c)) return rc;
+    *out = c;
+    return RT_OK;
+}
+extern "C" int rt_camera_perspective(const float lookfrom[3], const float lookat[3], const float up[3], float vfov, float aspect, float aperture, float focus_dist,
+                                     float time0, float time1, rt_camera* out) {
+    return lens_camera("rt_camera_perspective", RT_CAM_PERSPECTIVE, lookfrom, lookat, up, vfov, aspect, false, 0.0f, 0.0f, aperture, focus_dist, time0, time1, out);
+}
+extern "C" int rt_camera_orthographic(const float lookfrom[3], const float lookat[3], const float up[3], float height, float aspect, float aperture, float focus_dist,
+                                      float time0, float time1, rt_camera* out) {
+    const float b = height * 0.5f;
+    return lens_camera("rt_camera_orthographic", RT_CAM_ORTHOGRAPHIC, lookfrom, lookat, up, 90.0f, 1.0f, true, b * aspect, b, aperture, focus_dist, time0, time1, out);
+}
+extern "C" int rt_camera_fisheye(const float lookfrom[3], const float lookat[3], const float up[3], float fov, float aspect, float aperture, float focus_dist,
+                                 float time0, float time1, rt_camera* out) {
+    const float b = radians(fov) * 0.5f;
+    return lens_camera("rt_camera_fisheye", RT_CAM_FISHEYE, lookfrom, lookat, up, 90.0f, 1.0f, true, b * aspect, b, aperture, focus_dist, time0, time1, out);
+}
+extern "C" int rt_camera_panorama(const float lookfrom[3], const float lookat[3], const float up[3], float hspan_degrees, float vspan_degrees, float aperture,
+                                  float focus_dist, float time0, float time1, rt_camera* out) {
+    return lens_camera("rt_camera_panorama", RT_CAM_PANORAMA, lookfrom, lookat, up, 90.0f, 1.0f, true, radians(hspan_degrees) * 0.5f, radians(vspan_degrees) * 0.5f,
+                       aperture, focus_dist, time0, time1, out);
+}
+
 // ---------------------------------------------------------------------------------------------
 // aabb — rt_engine/geometry/aabb.cuh (host-side members used by the builders)
 // ---------------------------------------------------------------------------------------------

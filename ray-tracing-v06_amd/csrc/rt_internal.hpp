@@ -6,6 +6,8 @@
 #define RT_TILE 8        // 8x8-pixel tiles: the reference's thread-block shape, Renderer.cu:130
 
 int rt_fail(int code, const char* fmt, ...);
+struct rt_camera;
+int rt_camera_check(const char* who, const rt_camera* cam);   // rt_host.cpp: RT_OK for the three reference types and a valid lens camera (types 16 to 19), else the refusal
 const char* rt_environment_image_refusal(uint32_t width, uint32_t height, const float* rgb);   // rt_host.cpp: why an environment map is refused, or null
 // rt_host.cpp: rt_environment_distribution's tables of a valid image, or why it has none (an all-black map)
 const char* rt_environment_distribution_refusal(uint32_t width, uint32_t height, const float* rgb, float* rowc, float* rowy, float* colc, float* density);

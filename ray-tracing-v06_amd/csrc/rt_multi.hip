@@ -98,6 +98,7 @@ struct rt_multi_renderer {
 extern "C" int rt_multi_renderer_create(const rt_render_config* cfg, const rt_camera* cam, const rt_world_flat* world, uint32_t n_gpus,
                                         const int32_t* devices, rt_multi_renderer** out) {
     if (!cfg || !cam || !world || !out) return rt_fail(RT_ERR_INVALID, "rt_multi_renderer_create: null argument");
+    if (const int rc = rt_camera_check("rt_multi_renderer_create", cam)) return rc;
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0)
         return rt_fail(RT_ERR_NO_DEVICE, "no HIP device available: the HIP path is required, there is no CPU fallback");
@@ -251,7 +252,7 @@ extern "C" int rt_multi_renderer_refine(rt_multi_renderer* m, uint32_t n_samples
 
 extern "C" int rt_multi_renderer_set_camera(rt_multi_renderer* m, const rt_camera* cam) {
     if (!m || !cam) return rt_fail(RT_ERR_INVALID, "rt_multi_renderer_set_camera: null argument");
-    if (cam->type > RT_CAM_MOTION) return rt_fail(RT_ERR_INVALID, "rt_multi_renderer_set_camera: unknown camera type %u", cam->type);   // refused before any part changes
+    if (const int rc = rt_camera_check("rt_multi_renderer_set_camera", cam)) return rc;   // refused before any part changes (and what a part refuses, the first does)
     for (rt_renderer* r : m->parts) {
         const int rc = rt_renderer_set_camera(r, cam);
         if (rc != RT_OK) return rc;

@@ -183,6 +183,18 @@ __global__ void probe_camera_kernel(MakeRng make_rng, rt_camera cam, size_t n, c
     st3(out_rays + 7 * i, r.o); st3(out_rays + 7 * i + 3, r.d); out_rays[7 * i + 6] = r.time;
     draws[i] = g.draws;
 }
+// the camera's rule on one case with its tape: what rt_camera_rays_batch runs on the host (any type) and rt_probe_camera_lens one lane each (a lens camera)
+RT_HD void camera_rays_case(const rt_camera& cam, size_t i, const float* st, const uint32_t* tape, const uint32_t* offsets, float* out_rays, uint32_t* out_draws) {
+    TapeRng g{tape + offsets[2 * i], offsets[2 * i + 1], 0u};
+    const Ray r = cam.type >= RT_CAM_PERSPECTIVE ? lens_camera_sample_ray(cam, st[2 * i], st[2 * i + 1], g) : camera_sample_ray(cam, st[2 * i], st[2 * i + 1], g);
+    st3(out_rays + 7 * i, r.o); st3(out_rays + 7 * i + 3, r.d); out_rays[7 * i + 6] = r.time;
+    out_draws[i] = g.draws;
+}
+__global__ void probe_camera_lens_kernel(rt_camera cam, size_t n, const float* st, const uint32_t* tape, const uint32_t* offsets, float* out_rays, uint32_t* out_draws) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    camera_rays_case(cam, i, st, tape, offsets, out_rays, out_draws);
+}
 // the microfacet rule (microfacet_scatter) on one case with its tape: what rt_microfacet_batch runs on the host and the probe one lane each
 RT_HD void microfacet_case(size_t i, const float* normal, const float* ray_d, const float* roughness, const float* f0, const uint32_t* coat, const uint32_t* tape,
                            const uint32_t* offsets, float* out_dir, float* out_weight, uint32_t* out_path, uint32_t* out_draws) {
@@ -710,6 +722,31 @@ extern "C" int rt_probe_camera_tape(int device, const rt_camera* cam, size_t n, 
     ProbeRun p(device);
     const TapedRng make_rng{p.in(tape, tape_len), p.in(offsets, 2 * n)};
     return camera_cases(p, make_rng, *cam, n, st, out_rays, out_draws);
+}
+// Lens cameras: the rule over arrays of cases, on the device and — HOST (no GPU) — here
+static int camera_rays_args(const char* who, const rt_camera* cam, size_t n, const float* st, const uint32_t* tape, size_t tape_len, const uint32_t* offsets,
+                            float* out_rays, uint32_t* out_draws) {
+    if (!cam || !st || !tape || !offsets || !out_rays || !out_draws) return rt_fail(RT_ERR_INVALID, "%s: null argument", who);
+    if (int rc = rt_camera_check(who, cam)) return rc;
+    return check_tape(who, n, tape_len, offsets);
+}
+extern "C" int rt_probe_camera_lens(int device, const rt_camera* cam, size_t n, const float* st, const uint32_t* tape, size_t tape_len, const uint32_t* offsets,
+                                    float* out_rays, uint32_t* out_draws) {
+    if (const int rc = camera_rays_args("rt_probe_camera_lens", cam, n, st, tape, tape_len, offsets, out_rays, out_draws)) return rc;
+    if (cam->type < RT_CAM_PERSPECTIVE) return rt_fail(RT_ERR_INVALID, "rt_probe_camera_lens: camera type %u is no lens camera (rt_probe_camera_tape probes the reference's three)", cam->type);
+    if (n == 0) return RT_OK;
+    ProbeRun p(device);
+    const uint32_t no_tape = 0x800001u;   // an empty tape, as rt_probe_microfacet uploads it
+    auto s = p.in(st, 2 * n); auto dt = tape_len ? p.in(tape, tape_len) : p.in(&no_tape, 1); auto dof = p.in(offsets, 2 * n);
+    auto r = p.out(out_rays, 7 * n); auto d = p.out(out_draws, n);
+    p.launch(probe_camera_lens_kernel, p.per_case(n), 128, *cam, n, s, dt, dof, r, d);
+    return p.finish();
+}
+extern "C" int rt_camera_rays_batch(const rt_camera* cam, size_t n, const float* st, const uint32_t* tape, size_t tape_len, const uint32_t* offsets, float* out_rays,
+                                    uint32_t* out_draws) {
+    if (const int rc = camera_rays_args("rt_camera_rays_batch", cam, n, st, tape, tape_len, offsets, out_rays, out_draws)) return rc;
+    for (size_t i = 0; i < n; i++) camera_rays_case(*cam, i, st, tape, offsets, out_rays, out_draws);
+    return RT_OK;
 }
 // Microfacet surfaces: the rule over arrays of cases, on the device and — HOST (no GPU) — here
 static int microfacet_args(const char* who, size_t count, const float* normal, const float* ray_d, const float* roughness, const float* f0, const uint32_t* coat,

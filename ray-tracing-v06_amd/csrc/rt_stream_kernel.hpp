@@ -1287,6 +1287,48 @@ __global__ __launch_bounds__(256) void primary_rays_kernel(StreamParams p, uint3
     rt_store_stream(p.prim_rng + n, make_uint4(rng.s0, rng.s1, rng.s2, rng.s3));
 }
 
+// The same pass for a lens camera (rt06.h: types 16 to 19): primary_rays_kernel's index space, padding rule and three records, the ray from
+// lens_camera_ray.  PROJ = type - RT_CAM_PERSPECTIVE, LENS = lens_radius > 0, SHUTTER = t0 != t1 are the host's reading of the camera at launch time, so each of
+// the sixteen forms holds one projection and only the draws it makes.  With LENS the two rejection loops run as one, as in the DEFOCUS branch above.
+template <uint32_t PROJ, bool LENS, bool SHUTTER>
+__global__ __launch_bounds__(256) void primary_rays_lens_kernel(StreamParams p, uint32_t first_blk) {
+    const uint32_t blk = first_blk + blockIdx.y;
+    const uint32_t rem = blockIdx.x * 256u + threadIdx.x;   // index inside the block's 64 * pass_spp samples
+    if (rem >= 64u * p.pass_spp) return;
+    const uint32_t n = blk * (64u * p.pass_spp) + rem;
+    const uint32_t s_local = rem >> 6, pix = rem & 63u;
+    uint32_t x0, y0;
+    const bool ok = block_origin(p.tm, blk, x0, y0);
+    const uint32_t x = x0 + (pix & 7u), y = y0 + (pix >> 3);
+    if (!(ok && x < p.width && y < p.height)) {   // padding pixel: outside the image / past the last tile
+        p.prim_rng[n] = make_uint4(0u, 0u, 0u, 0u);
+        return;
+    }
+    Rng rng;
+    rng.init(p.seed, y * p.width + x, p.pass_first_s + s_local, RT_STREAM_RENDER);
+    float psx, psy, ndcx, ndcy;
+    pixel_ndc(x, y, p.width, p.height, psx, psy, ndcx, ndcy);
+    float jx = 0.0f, jy = 0.0f, la = 0.0f, lb = 0.0f;
+    if (LENS) {
+        uint32_t stage = 0;   // 0: pixel jitter, 1: lens point, 2: done
+        do {
+            const float u = rng.next_signed();
+            const float v = rng.next_signed();
+            if (length2(u, v) < 1.0f) {
+                if (stage == 0u) { jx = u; jy = v; } else { la = u; lb = v; }
+                stage++;
+            }
+        } while (stage < 2u);
+    } else {
+        rng_in_unit2(rng, jx, jy);
+    }
+    const float time = SHUTTER ? mix(p.cam.t0, p.cam.t1, rng.next()) : p.cam.t0;
+    const Ray ray = lens_camera_ray(p.cam, PROJ, LENS, ndcx + jx * psx, ndcy + jy * psy, la, lb, time);
+    rt_store_stream(p.prim_o + n, make_float4(ray.o.x, ray.o.y, ray.o.z, ray.time));
+    rt_store_stream(p.prim_d + n, make_float4(ray.d.x, ray.d.y, ray.d.z, 0.0f));
+    rt_store_stream(p.prim_rng + n, make_uint4(rng.s0, rng.s1, rng.s2, rng.s3));
+}
+
 // The two steps every resolve shares, so that a frame refined in steps and a frame rendered in one call cannot drift apart:
 //   add_pass_samples: the samples of one pass added to a pixel's sum IN SAMPLE ORDER (Renderer.cu:198-204: `radiance += ...`);
 //   resolve_pixel:    mean / clamp / sqrt-gamma / alpha over n_samples (Renderer.cu:206-216).

@@ -62,6 +62,17 @@ conductor on the metal, a coat of specular 0.04 on anything else —, `map_Pr` s
 (`Tr` above) or whose `illum` is 4, 6, 7 or 9 is glass of index `Ni`, whatever its `Pm`; `Pr` and `map_Pr` frost it.  --rough-glass R frosts the
 prefab `glass` material of --mesh-material.  --solid-glass makes such glass solid where its faces close a volume: rays leave it as well as
 enter it, and --glass-tint R,G,B --glass-tint-at D (or the material's `Tf`) colours it by thickness.
+
+    python tools/render.py --scene book2_moving --camera perspective --aperture 0.3 --focus-dist 10 --shutter 0,1 --out out.png
+    python tools/render.py --scene cornell_box --camera orthographic --camera-height 560 --out plan.png
+    python tools/render.py --scene cornell_box --camera panorama --lookfrom 278,278,278 --lookat 279,278,278 --width 512 --height 256 --out probe.hdr
+    python tools/render.py --scene three_spheres --env probe.hdr --out lit.png
+
+replace the prefab camera by a lens camera: perspective (--camera-fov: the vertical field of view, default the prefab's), orthographic
+(--camera-height: the window's height in world units), fisheye (--camera-fov: degrees across the image's height, default 180) or panorama (--camera-span H,V degrees,
+default 360,180), each with an optional lens (--aperture, --focus-dist) and shutter (--shutter T0,T1), from --lookfrom towards --lookat (default: the prefab
+camera's place and direction).  --out FILE.hdr or FILE.npy writes the LINEAR mean radiance (the refinement sums over the sample count, unclamped, no gamma), top
+row first: a panorama looking along +x with +y up written this way loads as an --env map without a flip or a turn — a light probe of one scene lights another.
 """
 import argparse, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -112,16 +123,31 @@ ap.add_argument("--env", default=None, metavar="FILE.hdr|FILE.npy|FILE.png|FILE.
                     "(DESIGN.md §23): Radiance RGBE, a float (H, W, 3) numpy array, an 8-bit picture (mapped to [0, 1]) or the procedural sky")
 ap.add_argument("--env-rotate", type=float, default=0.0, metavar="DEG", help="with --env: turn the map about y")
 ap.add_argument("--env-scale", type=float, default=1.0, metavar="X", help="with --env: multiply the map's radiance, on the host before upload")
-ap.add_argument("--out", default="render.png")
+ap.add_argument("--camera", choices=["perspective", "orthographic", "fisheye", "panorama"], default=None, help="a lens camera in the place of the prefab one (DESIGN.md §37)")
+ap.add_argument("--camera-fov", type=float, default=None, metavar="DEG", help="perspective: the vertical field of view (default: the prefab camera's); fisheye: the angle across the image's height (default 180)")
+ap.add_argument("--camera-height", type=float, default=None, metavar="H", help="orthographic: the view window's height in world units")
+ap.add_argument("--camera-span", default="360,180", metavar="H,V", help="panorama: the horizontal and vertical span in degrees")
+ap.add_argument("--aperture", type=float, default=0.0, metavar="A", help="with --camera: the lens diameter (0: no lens)")
+ap.add_argument("--focus-dist", type=float, default=None, metavar="D", help="with --camera: the distance of the focus surface (default: from --lookfrom to --lookat)")
+ap.add_argument("--shutter", default=None, metavar="T0,T1", help="with --camera: the shutter interval (default: none, every ray at time 0)")
+ap.add_argument("--lookfrom", default=None, metavar="X,Y,Z", help="with --camera: the eye (default: the prefab camera's)")
+ap.add_argument("--lookat", default=None, metavar="X,Y,Z", help="with --camera: the point looked at (default: one unit along the prefab camera's direction)")
+ap.add_argument("--out", default="render.png", help="FILE.png / .ppm / .jpg: the frame; FILE.hdr / .npy: the linear mean radiance, top row first (one GPU)")
 a = ap.parse_args()
 light_mode = {"quads": 1, "all": 2, "mesh": 4, "tree": 16, "env": 32, "env+tree": 48}.get(a.light_sampling_mode, 1 if a.light_sampling else 0)   # RT_LIGHT_SAMPLING_*
 if a.refine < 0 or (a.until is not None and (a.refine == 0 or a.gpus > 1)):
     ap.error("--until needs --refine STEP > 0 and one GPU (the multi-GPU renderer has no noise figure)")
 if (a.denoise or a.aov) and (a.refine == 0 or a.gpus > 1):
     ap.error("--denoise and --aov need --refine STEP > 0 and one GPU (feature buffers accumulate alongside refinement)")
+linear_out = a.out.lower().endswith((".hdr", ".npy"))
+if linear_out:
+    if a.gpus > 1:
+        ap.error("--out FILE.hdr / FILE.npy reads the refinement sums of one GPU")
+    a.refine = a.refine or a.spp   # the sums are the refinement's: one step of --spp samples unless --refine says otherwise
 p = G.load_package()
 from ray_tracing_v06_amd import image_io
 W, H = a.width, a.height
+PREFAB_FOV = {"three_spheres": 90.0, "cornell_box": 40.0, "cornell_lamp": 40.0, "book2_final": 40.0, "book1_final": 20.0, "book2_moving": 20.0}
 if a.scene == "three_spheres":
     scene, cam = p.Scene.three_spheres(), p.PinholeCamera((0, 0, 0), (0, 0, -1), (0, 1, 0), 90.0, W / H)
 elif a.scene in ("cornell_box", "cornell_lamp"):
@@ -132,6 +158,25 @@ elif a.scene == "book1_final":
     scene, cam = p.Scene.book1_final(a.seed), p.DefocusBlurCamera((13, 2, 3), (0, 0, 0), (0, 1, 0), 20.0, W / H, 0.1, 10.0)
 else:
     scene, cam = p.Scene.book2_moving(a.seed), p.MotionBlurCamera((13, 2, 3), (0, 0, 0), (0, 1, 0), 20.0, W / H, 0.0, 1.0)
+if a.camera:   # a lens camera at the prefab camera's place unless --lookfrom / --lookat say otherwise
+    import math
+    vec = lambda text: tuple(float(x) for x in text.split(","))   # noqa: E731
+    eye = vec(a.lookfrom) if a.lookfrom else tuple(cam.o)
+    w = tuple(cam.w) if cam.type == 1 else tuple(c / math.sqrt(sum(x * x for x in cam.w)) for c in cam.w)
+    at = vec(a.lookat) if a.lookat else tuple(e + d for e, d in zip(eye, w))
+    focus = a.focus_dist if a.focus_dist is not None else math.dist(eye, at)
+    t0, t1 = vec(a.shutter) if a.shutter else (0.0, 0.0)
+    lens = (a.aperture, focus, t0, t1)
+    if a.camera == "perspective":
+        cam = p.api.PerspectiveCamera(eye, at, (0, 1, 0), a.camera_fov if a.camera_fov is not None else PREFAB_FOV[a.scene], W / H, *lens)
+    elif a.camera == "orthographic":
+        if a.camera_height is None:
+            sys.exit("--camera orthographic needs --camera-height H, the window's height in world units")
+        cam = p.api.OrthographicCamera(eye, at, (0, 1, 0), a.camera_height, W / H, *lens)
+    elif a.camera == "fisheye":
+        cam = p.api.FisheyeCamera(eye, at, (0, 1, 0), a.camera_fov if a.camera_fov is not None else 180.0, W / H, *lens)
+    else:
+        cam = p.api.PanoramaCamera(eye, at, (0, 1, 0), *vec(a.camera_span), *lens)
 if (a.texture or a.mtl) and not a.mesh:
     sys.exit("--texture needs --mesh FILE.obj" if a.texture else "--mtl needs --mesh FILE.obj")
 if a.mesh:
@@ -310,12 +355,22 @@ else:
 fb = r.DownloadRenderbuffer()
 # .jpg = the reference app's own format (stbi_write_jpg quality 95, FirstApp.cpp:120); .ppm / .png are lossless
 writer = image_io.write_ppm if a.out.endswith(".ppm") else image_io.write_jpg if a.out.endswith((".jpg", ".jpeg")) else image_io.write_png
-writer(a.out, fb)
+if linear_out:   # the mean radiance as it was summed: no clamp, no gamma; the frame's row 0 is the bottom, a picture's and an environment map's the top
+    import numpy as np
+    mean = (r.refine_sums()[::-1, :, 0:3] / np.float32(samples)).astype(np.float32)
+    if a.out.lower().endswith(".npy"):
+        np.save(a.out, mean)
+    else:
+        image_io.write_hdr(a.out, np.where(np.isfinite(mean) & (mean > 0), mean, np.float32(0.0)))   # RGBE holds finite values >= 0
+    writer = image_io.write_png   # --denoise writes its .png beside it
+else:
+    writer(a.out, fb)
 extra = {"aov_mode": r.aov_mode()} if a.denoise or a.aov else {}
 if a.denoise:   # (with --refine only: `time` is imported there)
     t0 = time.perf_counter()
     den = r.denoise()
     stem, ext = os.path.splitext(a.out)
+    ext = ".png" if linear_out else ext
     extra["denoised"] = stem + "_denoised" + ext
     extra["denoise_ms"] = round((time.perf_counter() - t0) * 1e3, 3)   # filter + download, host wall-clock
     writer(extra["denoised"], den)
@@ -331,4 +386,4 @@ if a.aov:
     image_io.write_png(a.aov + "_albedo.png", np.concatenate([f["albedo"], one], axis=2))
     extra["aov"] = [a.aov + s for s in ("_normal.png", "_depth.png", "_albedo.png")]
 print(json.dumps({**extra, "scene": a.scene, "width": W, "height": H, "spp": samples, "max_depth": a.depth, "render_ms": round(ms, 3),
-                  "msamples_per_s": round(W * H * samples / ms / 1e3, 1), "gpus": a.gpus, "light_sampling": light_mode > 0, "light_sampling_mode": light_mode, "out": a.out}))
+                  "msamples_per_s": round(W * H * samples / ms / 1e3, 1), "gpus": a.gpus, "light_sampling": light_mode > 0, "light_sampling_mode": light_mode, "camera": a.camera or "prefab", "out": a.out}))
