@@ -637,32 +637,26 @@ def _push_textures(fn, handle, table):
     return fn(handle, records.ctypes.data if len(records) else None, len(records), texels.ctypes.data if len(texels) else None)
 
 
-def _push_normal_maps(fn, handle, table):
+def _push_records(fn, handle, table, dtype):
+    """a per-material table (normal maps, microfacets, interiors, cutouts) as records of `dtype`; None = off"""
     if table is None:
         return fn(handle, None, 0)
-    table = np.ascontiguousarray(table, capi.NORMAL_MAP_DT).reshape(-1)
+    table = np.ascontiguousarray(table, dtype).reshape(-1)
     return fn(handle, table.ctypes.data if len(table) else None, len(table))
 
 
-def _push_interiors(fn, handle, table):
-    if table is None:
-        return fn(handle, None, 0)
-    table = np.ascontiguousarray(table, capi.INTERIOR_DT).reshape(-1)
-    return fn(handle, table.ctypes.data if len(table) else None, len(table))
+def _info_pair(fn, handle, count):
+    """a table's _info query: {'enabled', count}"""
+    out = (C.c_uint32 * 2)()
+    check(fn(handle, out))
+    return {"enabled": bool(out[0]), count: out[1]}
 
 
-def _push_cutouts(fn, handle, table):
-    if table is None:
-        return fn(handle, None, 0)
-    table = np.ascontiguousarray(table, capi.CUTOUT_DT).reshape(-1)
-    return fn(handle, table.ctypes.data if len(table) else None, len(table))
-
-
-def _push_microfacets(fn, handle, table):
-    if table is None:
-        return fn(handle, None, 0)
-    table = np.ascontiguousarray(table, capi.MICROFACET_DT).reshape(-1)
-    return fn(handle, table.ctypes.data if len(table) else None, len(table))
+def _kernel_has(fn, handle):
+    """a kernel_* query: whether the next launch runs an instantiation of the family"""
+    out = C.c_uint32(0)
+    check(fn(handle, C.byref(out)))
+    return bool(out.value)
 
 
 def _env_image(image):
@@ -828,9 +822,7 @@ class Renderer:
     def light_sampling_info(self):
         """{'enabled', 'lights'}: whether light sampling is on (in any mode: light_sampling_mode() tells which), and the number of lights in the
         mode's table — off: of quad lights; "env": the texels of the map; "env+tree": of the light tree's table, which may be empty — (0: the world cannot be light-sampled)."""
-        out = (C.c_uint32 * 2)()
-        check(lib().rt_renderer_light_sampling_info(self.h, out))
-        return {"enabled": bool(out[0]), "lights": out[1]}
+        return _info_pair(lib().rt_renderer_light_sampling_info, self.h, "lights")
 
     def shading_normals(self, table):
         """Smooth shading from the next launch on (rt_renderer_shading_normals): table = one record of three vertex normals per triangle of
@@ -839,9 +831,7 @@ class Renderer:
 
     def shading_normals_info(self):
         """{'enabled', 'smooth'}: whether a table of vertex normals is on, and how many of its records are not flat."""
-        out = (C.c_uint32 * 2)()
-        check(lib().rt_renderer_shading_normals_info(self.h, out))
-        return {"enabled": bool(out[0]), "smooth": out[1]}
+        return _info_pair(lib().rt_renderer_shading_normals_info, self.h, "smooth")
 
     def texture_coords(self, table):
         """Texture coordinates from the next launch on (rt_renderer_texture_coords): table = one record of three (u, v) per triangle of the
@@ -850,9 +840,7 @@ class Renderer:
 
     def texture_coords_info(self):
         """{'enabled', 'mapped'}: whether a table of texture coordinates is on, and how many of its records are not the identity."""
-        out = (C.c_uint32 * 2)()
-        check(lib().rt_renderer_texture_coords_info(self.h, out))
-        return {"enabled": bool(out[0]), "mapped": out[1]}
+        return _info_pair(lib().rt_renderer_texture_coords_info, self.h, "mapped")
 
     def environment(self, image, u0=0.0):
         """The environment map of a background-2 world from the next launch on (rt_renderer_environment): image (H, W, 3) float, u0 in [0, 1) the
@@ -867,78 +855,60 @@ class Renderer:
     def normal_maps(self, table):
         """The normal-map table from the next launch on (rt_renderer_normal_maps): one record of capi.NORMAL_MAP_DT per material as Scene.normal_maps()
         gives it; None = off.  The images it names are the texture table's (Renderer.textures).  A change restarts the refinement; an unchanged table keeps it."""
-        check(_push_normal_maps(lib().rt_renderer_normal_maps, self.h, table))
+        check(_push_records(lib().rt_renderer_normal_maps, self.h, table, capi.NORMAL_MAP_DT))
 
     def normal_maps_info(self):
         """{'enabled', 'mapped'} of the renderer's normal-map table: mapped = how many materials have a map."""
-        out = (C.c_uint32 * 2)()
-        check(lib().rt_renderer_normal_maps_info(self.h, out))
-        return {"enabled": bool(out[0]), "mapped": out[1]}
+        return _info_pair(lib().rt_renderer_normal_maps_info, self.h, "mapped")
 
     def kernel_normal_map(self):
         """True when the next launch runs the streaming kernel's normal-map family (rt_renderer_kernel_normal_map): a normal-map table is on."""
-        out = C.c_uint32(0)
-        check(lib().rt_renderer_kernel_normal_map(self.h, C.byref(out)))
-        return bool(out.value)
+        return _kernel_has(lib().rt_renderer_kernel_normal_map, self.h)
 
     def microfacets(self, table):
         """The microfacet table from the next launch on (rt_renderer_microfacets): one record of capi.MICROFACET_DT per material as
         Scene.microfacets() gives it; None = off.  A mapped record names its image in the texture table (Renderer.textures).  A change restarts the refinement."""
-        check(_push_microfacets(lib().rt_renderer_microfacets, self.h, table))
+        check(_push_records(lib().rt_renderer_microfacets, self.h, table, capi.MICROFACET_DT))
 
     def microfacets_info(self):
         """{'enabled', 'records'} of the renderer's microfacet table: records = how many materials have one."""
-        out = (C.c_uint32 * 2)()
-        check(lib().rt_renderer_microfacets_info(self.h, out))
-        return {"enabled": bool(out[0]), "records": out[1]}
+        return _info_pair(lib().rt_renderer_microfacets_info, self.h, "records")
 
     def interiors(self, table):
         """The interior table from the next launch on (rt_renderer_interiors): one record of capi.INTERIOR_DT per material as Scene.interiors()
         gives it; None = off.  A change restarts the refinement."""
-        check(_push_interiors(lib().rt_renderer_interiors, self.h, table))
+        check(_push_records(lib().rt_renderer_interiors, self.h, table, capi.INTERIOR_DT))
 
     def interiors_info(self):
         """{'enabled', 'records'} of the renderer's interior table: records = how many materials have one."""
-        out = (C.c_uint32 * 2)()
-        check(lib().rt_renderer_interiors_info(self.h, out))
-        return {"enabled": bool(out[0]), "records": out[1]}
+        return _info_pair(lib().rt_renderer_interiors_info, self.h, "records")
 
     def kernel_interior(self):
         """True when the next launch runs the streaming kernel's solid-glass family (rt_renderer_kernel_interior): an interior table is on."""
-        out = C.c_uint32(0)
-        check(lib().rt_renderer_kernel_interior(self.h, C.byref(out)))
-        return bool(out.value)
+        return _kernel_has(lib().rt_renderer_kernel_interior, self.h)
 
     def cutouts(self, table):
         """The cutout table from the next launch on (rt_renderer_cutouts; DESIGN.md §34): one record of capi.CUTOUT_DT per material as Scene.cutouts() gives it;
         None = off.  The masks are entries of the renderer's texture table (textures()).  A change restarts the refinement."""
-        check(_push_cutouts(lib().rt_renderer_cutouts, self.h, table))
+        check(_push_records(lib().rt_renderer_cutouts, self.h, table, capi.CUTOUT_DT))
 
     def cutouts_info(self):
         """{'enabled', 'records'} of the renderer's cutout table: records = how many materials have one."""
-        out = (C.c_uint32 * 2)()
-        check(lib().rt_renderer_cutouts_info(self.h, out))
-        return {"enabled": bool(out[0]), "records": out[1]}
+        return _info_pair(lib().rt_renderer_cutouts_info, self.h, "records")
 
     def kernel_cutout(self):
         """True when the next launch runs the streaming kernel's cutout family (rt_renderer_kernel_cutout): a cutout table is on.  kernel_interior() and
         kernel_microfacet() are True then too: the cutout forms are those forms, reading one more table."""
-        out = C.c_uint32(0)
-        check(lib().rt_renderer_kernel_cutout(self.h, C.byref(out)))
-        return bool(out.value)
+        return _kernel_has(lib().rt_renderer_kernel_cutout, self.h)
 
     def kernel_microfacet(self):
         """True when the next launch runs the streaming kernel's microfacet family (rt_renderer_kernel_microfacet): a microfacet table is on, or an
         interior table — the solid-glass forms (kernel_interior) are microfacet forms that read one more table."""
-        out = C.c_uint32(0)
-        check(lib().rt_renderer_kernel_microfacet(self.h, C.byref(out)))
-        return bool(out.value)
+        return _kernel_has(lib().rt_renderer_kernel_microfacet, self.h)
 
     def textures_info(self):
         """{'enabled', 'entries'} of the renderer's texture table."""
-        out = (C.c_uint32 * 2)()
-        check(lib().rt_renderer_textures_info(self.h, out))
-        return {"enabled": bool(out[0]), "entries": out[1]}
+        return _info_pair(lib().rt_renderer_textures_info, self.h, "entries")
 
     def environment_info(self):
         """{'enabled', 'width', 'height', 'u0'} of the renderer's environment map."""
@@ -987,21 +957,15 @@ class Renderer:
 
     def kernel_light_tree(self):
         """True when the next launch runs the streaming kernel's light-tree family (rt_renderer_kernel_light_tree): mode "tree" or "env+tree" is on."""
-        out = C.c_uint32(0)
-        check(lib().rt_renderer_kernel_light_tree(self.h, C.byref(out)))
-        return bool(out.value)
+        return _kernel_has(lib().rt_renderer_kernel_light_tree, self.h)
 
     def kernel_env_light(self):
         """True when the next launch runs the streaming kernel's environment-sampling family (rt_renderer_kernel_env_light): mode "env" or "env+tree" is on."""
-        out = C.c_uint32(0)
-        check(lib().rt_renderer_kernel_env_light(self.h, C.byref(out)))
-        return bool(out.value)
+        return _kernel_has(lib().rt_renderer_kernel_env_light, self.h)
 
     def kernel_triangles(self):
         """True when the next launch runs the streaming kernel's triangle family (rt_renderer_kernel_triangles)."""
-        out = C.c_uint32()
-        check(lib().rt_renderer_kernel_triangles(self.h, C.byref(out)))
-        return bool(out.value)
+        return _kernel_has(lib().rt_renderer_kernel_triangles, self.h)
 
     def DownloadRenderbuffer(self):
         out = np.zeros((self.cfg.height, self.cfg.width, 4), dtype=np.float32)
@@ -1092,43 +1056,35 @@ class MultiRenderer:
 
     def normal_maps(self, table):
         """rt_renderer_normal_maps on every rank; `table` as Renderer.normal_maps takes it."""
-        check(_push_normal_maps(lib().rt_multi_renderer_normal_maps, self.h, table))
+        check(_push_records(lib().rt_multi_renderer_normal_maps, self.h, table, capi.NORMAL_MAP_DT))
 
     def normal_maps_info(self):
         """{'enabled', 'mapped'} of the ranks' normal-map table (they hold the same one)."""
-        out = (C.c_uint32 * 2)()
-        check(lib().rt_multi_renderer_normal_maps_info(self.h, out))
-        return {"enabled": bool(out[0]), "mapped": out[1]}
+        return _info_pair(lib().rt_multi_renderer_normal_maps_info, self.h, "mapped")
 
     def microfacets(self, table):
         """rt_renderer_microfacets on every rank; `table` as Renderer.microfacets takes it."""
-        check(_push_microfacets(lib().rt_multi_renderer_microfacets, self.h, table))
+        check(_push_records(lib().rt_multi_renderer_microfacets, self.h, table, capi.MICROFACET_DT))
 
     def interiors(self, table):
         """rt_renderer_interiors on every rank; `table` as Renderer.interiors takes it."""
-        check(_push_interiors(lib().rt_multi_renderer_interiors, self.h, table))
+        check(_push_records(lib().rt_multi_renderer_interiors, self.h, table, capi.INTERIOR_DT))
 
     def cutouts(self, table):
         """rt_renderer_cutouts on every rank; `table` as Renderer.cutouts takes it."""
-        check(_push_cutouts(lib().rt_multi_renderer_cutouts, self.h, table))
+        check(_push_records(lib().rt_multi_renderer_cutouts, self.h, table, capi.CUTOUT_DT))
 
     def cutouts_info(self):
         """{'enabled', 'records'} of the ranks' cutout table (they hold the same one)."""
-        out = (C.c_uint32 * 2)()
-        check(lib().rt_multi_renderer_cutouts_info(self.h, out))
-        return {"enabled": bool(out[0]), "records": out[1]}
+        return _info_pair(lib().rt_multi_renderer_cutouts_info, self.h, "records")
 
     def microfacets_info(self):
         """{'enabled', 'records'} of the ranks' microfacet table (they hold the same one)."""
-        out = (C.c_uint32 * 2)()
-        check(lib().rt_multi_renderer_microfacets_info(self.h, out))
-        return {"enabled": bool(out[0]), "records": out[1]}
+        return _info_pair(lib().rt_multi_renderer_microfacets_info, self.h, "records")
 
     def textures_info(self):
         """{'enabled', 'entries'} of the ranks' texture table (they hold the same one)."""
-        out = (C.c_uint32 * 2)()
-        check(lib().rt_multi_renderer_textures_info(self.h, out))
-        return {"enabled": bool(out[0]), "entries": out[1]}
+        return _info_pair(lib().rt_multi_renderer_textures_info, self.h, "entries")
 
     def DownloadRenderbuffer(self):
         out = np.zeros((self.cfg.height, self.cfg.width, 4), dtype=np.float32)

@@ -63,10 +63,23 @@ constexpr uint32_t RT_KEY_MFAC = 1u << 15;  // microfacet surfaces (rt_renderer_
 constexpr uint32_t RT_KEY_INTR = 1u << 16;  // solid glass (rt_renderer_interiors): the INTR form of an MFAC key, plain or with mode 48, which reads all three tables; reported by rt_renderer_kernel_interior
 constexpr uint32_t RT_KEY_CUT = 1u << 17;   // alpha cutouts (rt_renderer_cutouts): the CUT form of an INTR key, plain or with mode 48, which reads all four tables; reported by rt_renderer_kernel_cutout
 constexpr uint32_t RT_KEY_TRI = 1u << 11;   // the world has triangles: the TRI form of an EXT >= 1 stack-walk or list key, plain or NEE; not one of rt_renderer_kernel_form's fields
-// a stream key read back into render_kernel_stream's template arguments, in stream_key()'s order, then NEE: what rt_renderer_kernel_form reports
+// The one decode of a key.  Field i of stream_key()'s seven, in its order: exact, filter, world, ext, big, wide, tol ...
+constexpr uint32_t stream_key_field(uint32_t key, int i) {
+    constexpr uint32_t shift[7] = {0, 1, 2, 4, 6, 7, 8}, mask[7] = {1, 1, 3, 3, 1, 1, 1};
+    return key >> shift[i] & mask[i];
+}
+// ... the instantiation a key names: the nine low bits as above, then NEE, TRI, LTREE, ENVL, CUT, INTR and MFAC from their bits.  NMAP is on under RT_KEY_MFAC too:
+// every MFAC form (so every INTR and CUT form) reads the normal-map table, and its key does not carry RT_KEY_NMAP (rt_renderer_kernel_normal_map says 0 of it).
+template <uint32_t K> static const void* stream_kernel_of() {
+    return reinterpret_cast<const void*>(&render_kernel_stream<
+        stream_key_field(K, 0) != 0u, stream_key_field(K, 1) != 0u, RT_STREAM_BLOCK, (int)stream_key_field(K, 2), (int)stream_key_field(K, 3), stream_key_field(K, 4) != 0u,
+        stream_key_field(K, 5) != 0u, stream_key_field(K, 6) != 0u, (K & RT_KEY_NEE) != 0u, (K & RT_KEY_TRI) != 0u, (K & RT_KEY_LTREE) != 0u, (K & RT_KEY_ENVL) != 0u,
+        (K & RT_KEY_CUT) != 0u, (K & RT_KEY_INTR) != 0u, (K & RT_KEY_MFAC) != 0u, (K & (RT_KEY_NMAP | RT_KEY_MFAC)) != 0u>);
+}
+// ... and what rt_renderer_kernel_form reports: the seven fields, then NEE
 static void stream_key_fields(uint32_t key, uint32_t out[8]) {
-    out[0] = key & 1u; out[1] = key >> 1 & 1u; out[2] = key >> 2 & 3u; out[3] = key >> 4 & 3u;
-    out[4] = key >> 6 & 1u; out[5] = key >> 7 & 1u; out[6] = key >> 8 & 1u; out[7] = key >> 10 & 1u;
+    for (int i = 0; i < 7; i++) out[i] = stream_key_field(key, i);
+    out[7] = key & RT_KEY_NEE ? 1u : 0u;
 }
 
 // The kernel of a renderer: variant = the resolved one (2 verbatim box tests, 3 fast exact division, 4 filtered predicates, 5 ray exchange), tol = requested
@@ -100,150 +113,62 @@ static PrimaryRaysLensKernel primary_rays_lens_kernel_for(const rt_camera& c) {
     return forms[((c.type - RT_CAM_PERSPECTIVE) & 3u) * 4u + (lens_camera_has_lens(c) ? 2u : 0u) + (lens_camera_has_shutter(c) ? 1u : 0u)];
 }
 
-// Every shipped instantiation, once, a family per line, in the order the code object has them (a key listed twice does not compile).
-// stream_kernel_key() yields no other key, so the default is never taken.
+// Every shipped instantiation, once, in the order the code object has them (a key listed twice does not compile): the exchange kernel, the 26 plain keys, then
+// the feature families, a line each: a family is a set of key bits over one of two shape lists.  stream_kernel_key() yields no other key, so the default is never taken.
+// The sixteen EXT 1 and 2 list and stack-walk shapes (exact, world, ext, big, wide) ...
+#define RT_SHAPES_16(S, bits) \
+    S(true, RT_WORLD_LIST, 2, true, true, bits) S(true, RT_WORLD_LIST, 1, true, true, bits) \
+    S(false, RT_WORLD_BVH, 2, true, true, bits) S(true, RT_WORLD_BVH, 2, true, true, bits) S(false, RT_WORLD_BVH, 1, true, true, bits) S(true, RT_WORLD_BVH, 1, true, true, bits) \
+    S(false, RT_WORLD_BVH, 2, true, false, bits) S(true, RT_WORLD_BVH, 2, true, false, bits) S(false, RT_WORLD_BVH, 1, true, false, bits) S(true, RT_WORLD_BVH, 1, true, false, bits) \
+    S(true, RT_WORLD_LIST, 2, false, false, bits) S(true, RT_WORLD_LIST, 1, false, false, bits) \
+    S(false, RT_WORLD_BVH, 2, false, false, bits) S(true, RT_WORLD_BVH, 2, false, false, bits) S(false, RT_WORLD_BVH, 1, false, false, bits) S(true, RT_WORLD_BVH, 1, false, false, bits)
+// ... and their eight EXT 2 members
+#define RT_SHAPES_8(S, bits) \
+    S(true, RT_WORLD_LIST, 2, true, true, bits) S(false, RT_WORLD_BVH, 2, true, true, bits) S(true, RT_WORLD_BVH, 2, true, true, bits) S(false, RT_WORLD_BVH, 2, true, false, bits) S(true, RT_WORLD_BVH, 2, true, false, bits) \
+    S(true, RT_WORLD_LIST, 2, false, false, bits) S(false, RT_WORLD_BVH, 2, false, false, bits) S(true, RT_WORLD_BVH, 2, false, false, bits)
 static const void* stream_kernel_for(uint32_t key) {
-#define RT_KERNEL(exact, filter, world, ext, big, wide, tol) \
-    case stream_key(exact, filter, world, ext, big, wide, tol): return reinterpret_cast<const void*>(&render_kernel_stream<exact, filter, RT_STREAM_BLOCK, world, ext, big, wide, tol>)
-#define RT_KERNEL_NEE(exact, world, ext, big, wide) \
-    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_NEE: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, true>)
-#define RT_KERNEL_TRI(exact, world, ext, big, wide) \
-    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, false, true>)
-#define RT_KERNEL_TRI_NEE(exact, world, ext, big, wide) \
-    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NEE: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, true, true>)
-#define RT_KERNEL_LIGHT_TREE(exact, world, ext, big, wide) \
-    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NEE | RT_KEY_LTREE: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, true, true, true>)
-#define RT_KERNEL_ENV_LIGHT(exact, world, ext, big, wide) \
-    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NEE | RT_KEY_ENVL: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, true, true, false, true>)
-#define RT_KERNEL_ENV_TREE(exact, world, ext, big, wide) \
-    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NEE | RT_KEY_LTREE | RT_KEY_ENVL: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, true, true, true, true>)
-#define RT_KERNEL_NORMAL_MAP(exact, world, ext, big, wide) \
-    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NMAP: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, false, true, false, false, false, false, false, true>)
-#define RT_KERNEL_NORMAL_MAP_ENV_TREE(exact, world, ext, big, wide) \
-    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NEE | RT_KEY_LTREE | RT_KEY_ENVL | RT_KEY_NMAP: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, true, true, true, true, false, false, false, true>)
-#define RT_KERNEL_MICROFACET(exact, world, ext, big, wide) \
-    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_MFAC: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, false, true, false, false, false, false, true, true>)
-#define RT_KERNEL_MICROFACET_ENV_TREE(exact, world, ext, big, wide) \
-    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NEE | RT_KEY_LTREE | RT_KEY_ENVL | RT_KEY_MFAC: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, true, true, true, true, false, false, true, true>)
-#define RT_KERNEL_INTERIOR(exact, world, ext, big, wide) \
-    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_MFAC | RT_KEY_INTR: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, false, true, false, false, false, true, true, true>)
-#define RT_KERNEL_INTERIOR_ENV_TREE(exact, world, ext, big, wide) \
-    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NEE | RT_KEY_LTREE | RT_KEY_ENVL | RT_KEY_MFAC | RT_KEY_INTR: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, true, true, true, true, false, true, true, true>)
-#define RT_KERNEL_CUTOUT(exact, world, ext, big, wide) \
-    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_MFAC | RT_KEY_INTR | RT_KEY_CUT: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, false, true, false, false, true, true, true, true>)
-#define RT_KERNEL_CUTOUT_ENV_TREE(exact, world, ext, big, wide) \
-    case stream_key(exact, false, world, ext, big, wide, false) | RT_KEY_TRI | RT_KEY_NEE | RT_KEY_LTREE | RT_KEY_ENVL | RT_KEY_MFAC | RT_KEY_INTR | RT_KEY_CUT: return reinterpret_cast<const void*>(&render_kernel_stream<exact, false, RT_STREAM_BLOCK, world, ext, big, wide, false, true, true, true, true, true, true, true, true>)
-    switch (key) {   // arguments: exact, filter, world, ext, big, wide, tol
+#define RT_CASE(key) case (key): return stream_kernel_of<(key)>();
+#define RT_KERNEL(exact, filter, world, ext, big, wide, tol) RT_CASE(stream_key(exact, filter, world, ext, big, wide, tol))
+#define RT_SHAPE(exact, world, ext, big, wide, bits) RT_CASE(stream_key(exact, false, world, ext, big, wide) | (bits))
+#define RT_FAMILY_16(bits) RT_SHAPES_16(RT_SHAPE, bits)
+#define RT_FAMILY_8(bits) RT_SHAPES_8(RT_SHAPE, bits)
+    switch (key) {
         case RT_KEY_XCHG: return reinterpret_cast<const void*>(&render_kernel_xchg<RT_XCHG_BLOCK>);
-        RT_KERNEL(true, false, RT_WORLD_BVH_QUEUE, 2, true, true, false); RT_KERNEL(true, false, RT_WORLD_BVH_QUEUE, 1, true, true, false); RT_KERNEL(true, false, RT_WORLD_BVH_QUEUE, 0, true, true, false);
-        RT_KERNEL(true, false, RT_WORLD_LIST, 2, true, true, false); RT_KERNEL(true, false, RT_WORLD_LIST, 1, true, true, false); RT_KERNEL(true, false, RT_WORLD_NODE_TREE, 0, true, true, false);
-        RT_KERNEL(false, false, RT_WORLD_BVH, 2, true, true, false); RT_KERNEL(true, false, RT_WORLD_BVH, 2, true, true, false); RT_KERNEL(false, false, RT_WORLD_BVH, 1, true, true, false); RT_KERNEL(true, false, RT_WORLD_BVH, 1, true, true, false);
-        RT_KERNEL(false, false, RT_WORLD_BVH, 2, true, false, false); RT_KERNEL(true, false, RT_WORLD_BVH, 2, true, false, false); RT_KERNEL(false, false, RT_WORLD_BVH, 1, true, false, false); RT_KERNEL(true, false, RT_WORLD_BVH, 1, true, false, false);
-        RT_KERNEL(true, false, RT_WORLD_LIST, 2, false, false, false); RT_KERNEL(true, false, RT_WORLD_LIST, 1, false, false, false);
-        RT_KERNEL(false, false, RT_WORLD_BVH, 2, false, false, false); RT_KERNEL(true, false, RT_WORLD_BVH, 2, false, false, false); RT_KERNEL(false, false, RT_WORLD_BVH, 1, false, false, false); RT_KERNEL(true, false, RT_WORLD_BVH, 1, false, false, false);
-        RT_KERNEL(true, false, RT_WORLD_LIST, 0, false, false, false); RT_KERNEL(true, false, RT_WORLD_NODE_TREE, 0, false, false, false);
-        RT_KERNEL(false, false, RT_WORLD_BVH, 0, false, false, true); RT_KERNEL(true, false, RT_WORLD_BVH, 0, false, false, false); RT_KERNEL(false, true, RT_WORLD_BVH, 0, false, false, false); RT_KERNEL(false, false, RT_WORLD_BVH, 0, false, false, false);
-        // light sampling: every EXT >= 1 list and stack-walk family once more (arguments: exact, world, ext, big, wide)
-        RT_KERNEL_NEE(true, RT_WORLD_LIST, 2, true, true); RT_KERNEL_NEE(true, RT_WORLD_LIST, 1, true, true);
-        RT_KERNEL_NEE(false, RT_WORLD_BVH, 2, true, true); RT_KERNEL_NEE(true, RT_WORLD_BVH, 2, true, true); RT_KERNEL_NEE(false, RT_WORLD_BVH, 1, true, true); RT_KERNEL_NEE(true, RT_WORLD_BVH, 1, true, true);
-        RT_KERNEL_NEE(false, RT_WORLD_BVH, 2, true, false); RT_KERNEL_NEE(true, RT_WORLD_BVH, 2, true, false); RT_KERNEL_NEE(false, RT_WORLD_BVH, 1, true, false); RT_KERNEL_NEE(true, RT_WORLD_BVH, 1, true, false);
-        RT_KERNEL_NEE(true, RT_WORLD_LIST, 2, false, false); RT_KERNEL_NEE(true, RT_WORLD_LIST, 1, false, false);
-        RT_KERNEL_NEE(false, RT_WORLD_BVH, 2, false, false); RT_KERNEL_NEE(true, RT_WORLD_BVH, 2, false, false); RT_KERNEL_NEE(false, RT_WORLD_BVH, 1, false, false); RT_KERNEL_NEE(true, RT_WORLD_BVH, 1, false, false);
-        // triangles (§18): the same sixteen families once more, plain and with light sampling (arguments: exact, world, ext, big, wide)
-        RT_KERNEL_TRI(true, RT_WORLD_LIST, 2, true, true); RT_KERNEL_TRI(true, RT_WORLD_LIST, 1, true, true);
-        RT_KERNEL_TRI(false, RT_WORLD_BVH, 2, true, true); RT_KERNEL_TRI(true, RT_WORLD_BVH, 2, true, true); RT_KERNEL_TRI(false, RT_WORLD_BVH, 1, true, true); RT_KERNEL_TRI(true, RT_WORLD_BVH, 1, true, true);
-        RT_KERNEL_TRI(false, RT_WORLD_BVH, 2, true, false); RT_KERNEL_TRI(true, RT_WORLD_BVH, 2, true, false); RT_KERNEL_TRI(false, RT_WORLD_BVH, 1, true, false); RT_KERNEL_TRI(true, RT_WORLD_BVH, 1, true, false);
-        RT_KERNEL_TRI(true, RT_WORLD_LIST, 2, false, false); RT_KERNEL_TRI(true, RT_WORLD_LIST, 1, false, false);
-        RT_KERNEL_TRI(false, RT_WORLD_BVH, 2, false, false); RT_KERNEL_TRI(true, RT_WORLD_BVH, 2, false, false); RT_KERNEL_TRI(false, RT_WORLD_BVH, 1, false, false); RT_KERNEL_TRI(true, RT_WORLD_BVH, 1, false, false);
-        RT_KERNEL_TRI_NEE(true, RT_WORLD_LIST, 2, true, true); RT_KERNEL_TRI_NEE(true, RT_WORLD_LIST, 1, true, true);
-        RT_KERNEL_TRI_NEE(false, RT_WORLD_BVH, 2, true, true); RT_KERNEL_TRI_NEE(true, RT_WORLD_BVH, 2, true, true); RT_KERNEL_TRI_NEE(false, RT_WORLD_BVH, 1, true, true); RT_KERNEL_TRI_NEE(true, RT_WORLD_BVH, 1, true, true);
-        RT_KERNEL_TRI_NEE(false, RT_WORLD_BVH, 2, true, false); RT_KERNEL_TRI_NEE(true, RT_WORLD_BVH, 2, true, false); RT_KERNEL_TRI_NEE(false, RT_WORLD_BVH, 1, true, false); RT_KERNEL_TRI_NEE(true, RT_WORLD_BVH, 1, true, false);
-        RT_KERNEL_TRI_NEE(true, RT_WORLD_LIST, 2, false, false); RT_KERNEL_TRI_NEE(true, RT_WORLD_LIST, 1, false, false);
-        RT_KERNEL_TRI_NEE(false, RT_WORLD_BVH, 2, false, false); RT_KERNEL_TRI_NEE(true, RT_WORLD_BVH, 2, false, false); RT_KERNEL_TRI_NEE(false, RT_WORLD_BVH, 1, false, false); RT_KERNEL_TRI_NEE(true, RT_WORLD_BVH, 1, false, false);
-        // the light tree (§20): the TRI && NEE families once more (arguments: exact, world, ext, big, wide)
-        RT_KERNEL_LIGHT_TREE(true, RT_WORLD_LIST, 2, true, true); RT_KERNEL_LIGHT_TREE(true, RT_WORLD_LIST, 1, true, true);
-        RT_KERNEL_LIGHT_TREE(false, RT_WORLD_BVH, 2, true, true); RT_KERNEL_LIGHT_TREE(true, RT_WORLD_BVH, 2, true, true); RT_KERNEL_LIGHT_TREE(false, RT_WORLD_BVH, 1, true, true); RT_KERNEL_LIGHT_TREE(true, RT_WORLD_BVH, 1, true, true);
-        RT_KERNEL_LIGHT_TREE(false, RT_WORLD_BVH, 2, true, false); RT_KERNEL_LIGHT_TREE(true, RT_WORLD_BVH, 2, true, false); RT_KERNEL_LIGHT_TREE(false, RT_WORLD_BVH, 1, true, false); RT_KERNEL_LIGHT_TREE(true, RT_WORLD_BVH, 1, true, false);
-        RT_KERNEL_LIGHT_TREE(true, RT_WORLD_LIST, 2, false, false); RT_KERNEL_LIGHT_TREE(true, RT_WORLD_LIST, 1, false, false);
-        RT_KERNEL_LIGHT_TREE(false, RT_WORLD_BVH, 2, false, false); RT_KERNEL_LIGHT_TREE(true, RT_WORLD_BVH, 2, false, false); RT_KERNEL_LIGHT_TREE(false, RT_WORLD_BVH, 1, false, false); RT_KERNEL_LIGHT_TREE(true, RT_WORLD_BVH, 1, false, false);
-        // environment light sampling (§24): the EXT 2 families of TRI && NEE once more (arguments: exact, world, ext, big, wide)
-        RT_KERNEL_ENV_LIGHT(true, RT_WORLD_LIST, 2, true, true);
-        RT_KERNEL_ENV_LIGHT(false, RT_WORLD_BVH, 2, true, true); RT_KERNEL_ENV_LIGHT(true, RT_WORLD_BVH, 2, true, true);
-        RT_KERNEL_ENV_LIGHT(false, RT_WORLD_BVH, 2, true, false); RT_KERNEL_ENV_LIGHT(true, RT_WORLD_BVH, 2, true, false);
-        RT_KERNEL_ENV_LIGHT(true, RT_WORLD_LIST, 2, false, false);
-        RT_KERNEL_ENV_LIGHT(false, RT_WORLD_BVH, 2, false, false); RT_KERNEL_ENV_LIGHT(true, RT_WORLD_BVH, 2, false, false);
-        // the map and the light tree together (§26): the same eight once more, LTREE && ENVL (arguments: exact, world, ext, big, wide)
-        RT_KERNEL_ENV_TREE(true, RT_WORLD_LIST, 2, true, true);
-        RT_KERNEL_ENV_TREE(false, RT_WORLD_BVH, 2, true, true); RT_KERNEL_ENV_TREE(true, RT_WORLD_BVH, 2, true, true);
-        RT_KERNEL_ENV_TREE(false, RT_WORLD_BVH, 2, true, false); RT_KERNEL_ENV_TREE(true, RT_WORLD_BVH, 2, true, false);
-        RT_KERNEL_ENV_TREE(true, RT_WORLD_LIST, 2, false, false);
-        RT_KERNEL_ENV_TREE(false, RT_WORLD_BVH, 2, false, false); RT_KERNEL_ENV_TREE(true, RT_WORLD_BVH, 2, false, false);
-        // normal maps: the shapes of the environment-light family, plain ...
-        RT_KERNEL_NORMAL_MAP(true, RT_WORLD_LIST, 2, true, true);
-        RT_KERNEL_NORMAL_MAP(false, RT_WORLD_BVH, 2, true, true); RT_KERNEL_NORMAL_MAP(true, RT_WORLD_BVH, 2, true, true);
-        RT_KERNEL_NORMAL_MAP(false, RT_WORLD_BVH, 2, true, false); RT_KERNEL_NORMAL_MAP(true, RT_WORLD_BVH, 2, true, false);
-        RT_KERNEL_NORMAL_MAP(true, RT_WORLD_LIST, 2, false, false);
-        RT_KERNEL_NORMAL_MAP(false, RT_WORLD_BVH, 2, false, false); RT_KERNEL_NORMAL_MAP(true, RT_WORLD_BVH, 2, false, false);
-        // ... and under mode 48
-        RT_KERNEL_NORMAL_MAP_ENV_TREE(true, RT_WORLD_LIST, 2, true, true);
-        RT_KERNEL_NORMAL_MAP_ENV_TREE(false, RT_WORLD_BVH, 2, true, true); RT_KERNEL_NORMAL_MAP_ENV_TREE(true, RT_WORLD_BVH, 2, true, true);
-        RT_KERNEL_NORMAL_MAP_ENV_TREE(false, RT_WORLD_BVH, 2, true, false); RT_KERNEL_NORMAL_MAP_ENV_TREE(true, RT_WORLD_BVH, 2, true, false);
-        RT_KERNEL_NORMAL_MAP_ENV_TREE(true, RT_WORLD_LIST, 2, false, false);
-        RT_KERNEL_NORMAL_MAP_ENV_TREE(false, RT_WORLD_BVH, 2, false, false); RT_KERNEL_NORMAL_MAP_ENV_TREE(true, RT_WORLD_BVH, 2, false, false);
-        // microfacet surfaces: the same eight shapes, reading both tables, plain ...
-        RT_KERNEL_MICROFACET(true, RT_WORLD_LIST, 2, true, true);
-        RT_KERNEL_MICROFACET(false, RT_WORLD_BVH, 2, true, true); RT_KERNEL_MICROFACET(true, RT_WORLD_BVH, 2, true, true);
-        RT_KERNEL_MICROFACET(false, RT_WORLD_BVH, 2, true, false); RT_KERNEL_MICROFACET(true, RT_WORLD_BVH, 2, true, false);
-        RT_KERNEL_MICROFACET(true, RT_WORLD_LIST, 2, false, false);
-        RT_KERNEL_MICROFACET(false, RT_WORLD_BVH, 2, false, false); RT_KERNEL_MICROFACET(true, RT_WORLD_BVH, 2, false, false);
-        // ... and under mode 48
-        RT_KERNEL_MICROFACET_ENV_TREE(true, RT_WORLD_LIST, 2, true, true);
-        RT_KERNEL_MICROFACET_ENV_TREE(false, RT_WORLD_BVH, 2, true, true); RT_KERNEL_MICROFACET_ENV_TREE(true, RT_WORLD_BVH, 2, true, true);
-        RT_KERNEL_MICROFACET_ENV_TREE(false, RT_WORLD_BVH, 2, true, false); RT_KERNEL_MICROFACET_ENV_TREE(true, RT_WORLD_BVH, 2, true, false);
-        RT_KERNEL_MICROFACET_ENV_TREE(true, RT_WORLD_LIST, 2, false, false);
-        RT_KERNEL_MICROFACET_ENV_TREE(false, RT_WORLD_BVH, 2, false, false); RT_KERNEL_MICROFACET_ENV_TREE(true, RT_WORLD_BVH, 2, false, false);
-        // solid glass: the microfacet shapes once more, reading the sub-header and the interior records, plain ...
-        RT_KERNEL_INTERIOR(true, RT_WORLD_LIST, 2, true, true);
-        RT_KERNEL_INTERIOR(false, RT_WORLD_BVH, 2, true, true); RT_KERNEL_INTERIOR(true, RT_WORLD_BVH, 2, true, true);
-        RT_KERNEL_INTERIOR(false, RT_WORLD_BVH, 2, true, false); RT_KERNEL_INTERIOR(true, RT_WORLD_BVH, 2, true, false);
-        RT_KERNEL_INTERIOR(true, RT_WORLD_LIST, 2, false, false);
-        RT_KERNEL_INTERIOR(false, RT_WORLD_BVH, 2, false, false); RT_KERNEL_INTERIOR(true, RT_WORLD_BVH, 2, false, false);
-        // ... and under mode 48
-        RT_KERNEL_INTERIOR_ENV_TREE(true, RT_WORLD_LIST, 2, true, true);
-        RT_KERNEL_INTERIOR_ENV_TREE(false, RT_WORLD_BVH, 2, true, true); RT_KERNEL_INTERIOR_ENV_TREE(true, RT_WORLD_BVH, 2, true, true);
-        RT_KERNEL_INTERIOR_ENV_TREE(false, RT_WORLD_BVH, 2, true, false); RT_KERNEL_INTERIOR_ENV_TREE(true, RT_WORLD_BVH, 2, true, false);
-        RT_KERNEL_INTERIOR_ENV_TREE(true, RT_WORLD_LIST, 2, false, false);
-        RT_KERNEL_INTERIOR_ENV_TREE(false, RT_WORLD_BVH, 2, false, false); RT_KERNEL_INTERIOR_ENV_TREE(true, RT_WORLD_BVH, 2, false, false);
-        // alpha cutouts: the solid-glass shapes once more, whose leaf phase asks the cutout records before it takes a hit, plain ...
-        RT_KERNEL_CUTOUT(true, RT_WORLD_LIST, 2, true, true);
-        RT_KERNEL_CUTOUT(false, RT_WORLD_BVH, 2, true, true); RT_KERNEL_CUTOUT(true, RT_WORLD_BVH, 2, true, true);
-        RT_KERNEL_CUTOUT(false, RT_WORLD_BVH, 2, true, false); RT_KERNEL_CUTOUT(true, RT_WORLD_BVH, 2, true, false);
-        RT_KERNEL_CUTOUT(true, RT_WORLD_LIST, 2, false, false);
-        RT_KERNEL_CUTOUT(false, RT_WORLD_BVH, 2, false, false); RT_KERNEL_CUTOUT(true, RT_WORLD_BVH, 2, false, false);
-        // ... and under mode 48
-        RT_KERNEL_CUTOUT_ENV_TREE(true, RT_WORLD_LIST, 2, true, true);
-        RT_KERNEL_CUTOUT_ENV_TREE(false, RT_WORLD_BVH, 2, true, true); RT_KERNEL_CUTOUT_ENV_TREE(true, RT_WORLD_BVH, 2, true, true);
-        RT_KERNEL_CUTOUT_ENV_TREE(false, RT_WORLD_BVH, 2, true, false); RT_KERNEL_CUTOUT_ENV_TREE(true, RT_WORLD_BVH, 2, true, false);
-        RT_KERNEL_CUTOUT_ENV_TREE(true, RT_WORLD_LIST, 2, false, false);
-        RT_KERNEL_CUTOUT_ENV_TREE(false, RT_WORLD_BVH, 2, false, false); RT_KERNEL_CUTOUT_ENV_TREE(true, RT_WORLD_BVH, 2, false, false);
+        // the plain keys (arguments: exact, filter, world, ext, big, wide, tol)
+        RT_KERNEL(true, false, RT_WORLD_BVH_QUEUE, 2, true, true, false) RT_KERNEL(true, false, RT_WORLD_BVH_QUEUE, 1, true, true, false) RT_KERNEL(true, false, RT_WORLD_BVH_QUEUE, 0, true, true, false)
+        RT_KERNEL(true, false, RT_WORLD_LIST, 2, true, true, false) RT_KERNEL(true, false, RT_WORLD_LIST, 1, true, true, false) RT_KERNEL(true, false, RT_WORLD_NODE_TREE, 0, true, true, false)
+        RT_KERNEL(false, false, RT_WORLD_BVH, 2, true, true, false) RT_KERNEL(true, false, RT_WORLD_BVH, 2, true, true, false) RT_KERNEL(false, false, RT_WORLD_BVH, 1, true, true, false) RT_KERNEL(true, false, RT_WORLD_BVH, 1, true, true, false)
+        RT_KERNEL(false, false, RT_WORLD_BVH, 2, true, false, false) RT_KERNEL(true, false, RT_WORLD_BVH, 2, true, false, false) RT_KERNEL(false, false, RT_WORLD_BVH, 1, true, false, false) RT_KERNEL(true, false, RT_WORLD_BVH, 1, true, false, false)
+        RT_KERNEL(true, false, RT_WORLD_LIST, 2, false, false, false) RT_KERNEL(true, false, RT_WORLD_LIST, 1, false, false, false)
+        RT_KERNEL(false, false, RT_WORLD_BVH, 2, false, false, false) RT_KERNEL(true, false, RT_WORLD_BVH, 2, false, false, false) RT_KERNEL(false, false, RT_WORLD_BVH, 1, false, false, false) RT_KERNEL(true, false, RT_WORLD_BVH, 1, false, false, false)
+        RT_KERNEL(true, false, RT_WORLD_LIST, 0, false, false, false) RT_KERNEL(true, false, RT_WORLD_NODE_TREE, 0, false, false, false)
+        RT_KERNEL(false, false, RT_WORLD_BVH, 0, false, false, true) RT_KERNEL(true, false, RT_WORLD_BVH, 0, false, false, false) RT_KERNEL(false, true, RT_WORLD_BVH, 0, false, false, false) RT_KERNEL(false, false, RT_WORLD_BVH, 0, false, false, false)
+        // the families.  Light sampling, triangles (§18), both, the light tree (§20); environment light sampling (§24), the map and the tree together (§26);
+        // then the four material tables, each plain and under mode 48: normal maps (§28), microfacet surfaces (§29), solid glass (§32), alpha cutouts (§34)
+        RT_FAMILY_16(RT_KEY_NEE)
+        RT_FAMILY_16(RT_KEY_TRI)
+        RT_FAMILY_16(RT_KEY_TRI | RT_KEY_NEE)
+        RT_FAMILY_16(RT_KEY_TRI | RT_KEY_NEE | RT_KEY_LTREE)
+        RT_FAMILY_8(RT_KEY_TRI | RT_KEY_NEE | RT_KEY_ENVL)
+        RT_FAMILY_8(RT_KEY_TRI | RT_KEY_NEE | RT_KEY_LTREE | RT_KEY_ENVL)
+        RT_FAMILY_8(RT_KEY_TRI | RT_KEY_NMAP)
+        RT_FAMILY_8(RT_KEY_TRI | RT_KEY_NEE | RT_KEY_LTREE | RT_KEY_ENVL | RT_KEY_NMAP)
+        RT_FAMILY_8(RT_KEY_TRI | RT_KEY_MFAC)
+        RT_FAMILY_8(RT_KEY_TRI | RT_KEY_NEE | RT_KEY_LTREE | RT_KEY_ENVL | RT_KEY_MFAC)
+        RT_FAMILY_8(RT_KEY_TRI | RT_KEY_MFAC | RT_KEY_INTR)
+        RT_FAMILY_8(RT_KEY_TRI | RT_KEY_NEE | RT_KEY_LTREE | RT_KEY_ENVL | RT_KEY_MFAC | RT_KEY_INTR)
+        RT_FAMILY_8(RT_KEY_TRI | RT_KEY_MFAC | RT_KEY_INTR | RT_KEY_CUT)
+        RT_FAMILY_8(RT_KEY_TRI | RT_KEY_NEE | RT_KEY_LTREE | RT_KEY_ENVL | RT_KEY_MFAC | RT_KEY_INTR | RT_KEY_CUT)
         default: return nullptr;
     }
+#undef RT_FAMILY_8
+#undef RT_FAMILY_16
+#undef RT_SHAPE
 #undef RT_KERNEL
-#undef RT_KERNEL_CUTOUT
-#undef RT_KERNEL_CUTOUT_ENV_TREE
-#undef RT_KERNEL_INTERIOR
-#undef RT_KERNEL_INTERIOR_ENV_TREE
-#undef RT_KERNEL_MICROFACET
-#undef RT_KERNEL_MICROFACET_ENV_TREE
-#undef RT_KERNEL_NORMAL_MAP
-#undef RT_KERNEL_NORMAL_MAP_ENV_TREE
-#undef RT_KERNEL_ENV_TREE
-#undef RT_KERNEL_ENV_LIGHT
-#undef RT_KERNEL_LIGHT_TREE
-#undef RT_KERNEL_NEE
-#undef RT_KERNEL_TRI
-#undef RT_KERNEL_TRI_NEE
+#undef RT_CASE
 }
+#undef RT_SHAPES_8
+#undef RT_SHAPES_16
 
 // the feature pass's kernel: the world's own traversal, so that a kernel carries one traversal stack
 static decltype(&aov_kernel<RT_AOV_WALK_STACK>) aov_kernel_for(const DeviceWorld& w) {
@@ -299,6 +224,18 @@ static const LightMode* light_mode(uint32_t mode) {   // NULL: off, or no mode
     for (const LightMode& m : LIGHT_MODES) if (m.mode == mode) return &m;
     return nullptr;
 }
+
+// The four per-material tables, a rung each, lowest first: normal maps (§28), microfacet surfaces (§29), solid glass (§32), alpha cutouts (§34).  A rung's form
+// reads its own table and every table below it, so a launch runs the form of the highest rung that is on, plain or under mode 48.  A row: the key bits of the
+// rung's form, and the words its refusals are built from.
+struct FormRung { uint32_t key_bits; const char *api, *a, *table, *surfaces_render, *variant_5_6; };
+enum : uint32_t { RUNG_NMAP, RUNG_MFAC, RUNG_INTR, RUNG_CUT, N_RUNGS };
+static const FormRung FORM_LADDER[N_RUNGS] = {
+    {RT_KEY_NMAP, "rt_renderer_normal_maps", "a", "normal-map table", "normal maps render", "reads no texture table and no normal-map table"},
+    {RT_KEY_MFAC, "rt_renderer_microfacets", "a", "microfacet table", "microfacet surfaces render", "reads no microfacet table"},
+    {RT_KEY_MFAC | RT_KEY_INTR, "rt_renderer_interiors", "an", "interior table", "solid glass renders", "reads no interior table"},
+    {RT_KEY_MFAC | RT_KEY_INTR | RT_KEY_CUT, "rt_renderer_cutouts", "a", "cutout table", "alpha cutouts render", "reads no cutout table"},
+};
 
 struct rt_renderer {
     rt_render_config cfg{};
@@ -373,9 +310,9 @@ struct rt_renderer {
              bool on() const { return mode != RT_LIGHT_SAMPLING_OFF; } } nee;
     // The riders: what every launch image carries in its tail while it is on.  Each setter builds the next state of its rider and hands it to replace_rider().
     // smooth shading (rt_renderer_shading_normals): the table as given (9 floats per triangle of the world) and a flat copy for the feature pass
-    struct { bool on = false; uint32_t n_smooth = 0; std::vector<float> host; OwnedBuf table; } vn;
+    struct { bool on = false; uint32_t n_smooth = 0; std::vector<float> host; OwnedBuf table; uint32_t count() const { return n_smooth; } } vn;
     // texture coordinates (rt_renderer_texture_coords): the table as given (6 floats per triangle of the world)
-    struct { bool on = false; uint32_t n_mapped = 0; std::vector<float> host; } uv;
+    struct { bool on = false; uint32_t n_mapped = 0; std::vector<float> host; uint32_t count() const { return n_mapped; } } uv;
     // the environment map (rt_renderer_environment) of a background-2 world: the image as given (3 floats per texel) and a device buffer of the
     // renderer's own with one float4 per texel; the tail carries only a two-vec4 record that points to it (a 2048 x 1024 map is 32 MiB, and there are up to five images)
     // (§24: while dist_on, the records' fourth lane holds the sampling density and `dist` rowc[H], rowy[H + 1], colc[H W] of rt_environment_distribution)
@@ -383,50 +320,40 @@ struct rt_renderer {
     bool has_medium = false;   // the world has a constant medium (RT_MAT_ISOTROPIC): the modes that sample the map refuse it
     // the texture table (rt_renderer_textures): the entries and the texels as given (3 bytes per texel), and a device buffer of the renderer's own
     // with one dword r | g << 8 | b << 16 per texel, all images back to back; the tail carries (pointer low, pointer high, n, -) and one vec4 per entry
-    struct { bool on = false; std::vector<rt_texture> records; std::vector<uint8_t> host; OwnedBuf texels; } tex;
+    struct { bool on = false; std::vector<rt_texture> records; std::vector<uint8_t> host; OwnedBuf texels; uint32_t count() const { return (uint32_t)records.size(); } } tex;
     // normal maps (rt_renderer_normal_maps): one record per material as given; the tail carries them behind the texture table, whose header points
     // there.  While on, a plain launch and a mode-48 launch run the NMAP form of their kernel (plain / envt, resolved when the table or the mode comes on).
-    struct NormalMaps { bool on = false; uint32_t n_mapped = 0; std::vector<rt_normal_map> host; } nm;
+    struct NormalMaps { bool on = false; uint32_t n_mapped = 0; std::vector<rt_normal_map> host; uint32_t count() const { return n_mapped; } } nm;
     // microfacet surfaces (rt_renderer_microfacets): one record per material as given; the tail carries them last, and the bits above bit 0 of its
     // header's first lane say where.  While on, a plain launch and a mode-48 launch run the MFAC form of their kernel, which reads the normal-map table too.
-    struct Microfacets { bool on = false; uint32_t n_on = 0; std::vector<rt_microfacet> host; } mf;
+    struct Microfacets { bool on = false; uint32_t n_on = 0; std::vector<rt_microfacet> host; uint32_t count() const { return n_on; } } mf;
     // solid glass (rt_renderer_interiors): one record per material as given; with a table the tail's first lane counts to a sub-header, behind which
     // the microfacet and the interior records lie.  While on, a plain launch and a mode-48 launch run the INTR form of their kernel, which reads all three tables.
-    struct Interiors { bool on = false; uint32_t n_on = 0; std::vector<rt_interior> host; } in;
+    struct Interiors { bool on = false; uint32_t n_on = 0; std::vector<rt_interior> host; uint32_t count() const { return n_on; } } in;
     // alpha cutouts (rt_renderer_cutouts): one record per material as given, behind the interior records; the sub-header's third lane says where.
     // While on, a plain launch and a mode-48 launch run the CUT form of their kernel, which reads all four tables, whichever of the others are there.
-    struct Cutouts { bool on = false; uint32_t n_on = 0; std::vector<rt_cutout> host; } cut;
-    struct { uint32_t key = 0; const void* kernel = nullptr; } nm_plain, nm_envt, mf_plain, mf_envt, in_plain, in_envt, cut_plain, cut_envt;
+    struct Cutouts { bool on = false; uint32_t n_on = 0; std::vector<rt_cutout> host; uint32_t count() const { return n_on; } } cut;
+    // the rungs' forms (FORM_LADDER): the key and the kernel of rung g's form, plain [g][0] and under mode 48 [g][1], each from the first time its table and its mode met
+    struct { uint32_t key = 0; const void* kernel = nullptr; } form[N_RUNGS][2];
+    bool rung_on(uint32_t g) const { return g == RUNG_NMAP ? nm.on : g == RUNG_MFAC ? mf.on : g == RUNG_INTR ? in.on : cut.on; }
     bool tail_on() const { return vn.on || uv.on || env.on || tex.on || mf.on || in.on || cut.on; }
-    // the NMAP form of the renderer's kernel: the world's own shape at EXT 2 with TRI, plain or with mode 48's bits (0: a world no NMAP form walks)
-    uint32_t normal_map_key(bool envt) const {
+    // rung g's form of the renderer's kernel: the world's own shape at EXT 2 with TRI and the rung's bits, plain or with mode 48's (0: a world no such form walks)
+    uint32_t form_key(uint32_t g, bool envt) const {
         if (variant < 2 || variant == 5 || tol || scene.queue || scene.dw.kind == RT_WORLD_NODE_TREE) return 0u;
         const uint32_t base = stream_kernel_key(variant, false, scene);
-        return stream_key(base & 1u, false, (int)(base >> 2 & 3u), 2, base >> 6 & 1u, base >> 7 & 1u) | RT_KEY_TRI | RT_KEY_NMAP | (envt ? RT_KEY_NEE | RT_KEY_LTREE | RT_KEY_ENVL : 0u);
+        return stream_key(stream_key_field(base, 0), false, (int)stream_key_field(base, 2), 2, stream_key_field(base, 4), stream_key_field(base, 5)) | RT_KEY_TRI |
+               FORM_LADDER[g].key_bits | (envt ? RT_KEY_NEE | RT_KEY_LTREE | RT_KEY_ENVL : 0u);
     }
-    // whether a launch is refused for its normal maps (§28): one of them names an entry (*which) the renderer's texture table does not have
-    bool normal_map_entry_missing(uint32_t* which) const {
-        if (!nm.on) return false;
-        for (const rt_normal_map& m : nm.host)
-            if (m.on && (!tex.on || m.image >= tex.records.size() || tex.records[m.image].width == 0u)) { *which = m.image; return true; }
+    // whether a launch is refused for a table's records (normal maps §28, roughness maps §29, cutout masks §34): one that is `mapped` names an entry (*which) the
+    // renderer's texture table does not have
+    template <typename Rider, typename Mapped> bool entry_missing(const Rider& rider, Mapped mapped, uint32_t* which) const {
+        if (!rider.on) return false;
+        for (const auto& m : rider.host)
+            if (mapped(m) && (!tex.on || m.image >= tex.records.size() || tex.records[m.image].width == 0u)) { *which = m.image; return true; }
         return false;
     }
-    // ... or for its roughness maps (§29); a table of constant records needs no texture table
-    bool roughness_map_entry_missing(uint32_t* which) const {
-        if (!mf.on) return false;
-        for (const rt_microfacet& m : mf.host)
-            if ((m.on == RT_MICROFACET_MAPPED || m.on == RT_MICROFACET_GLASS_MAPPED) && (!tex.on || m.image >= tex.records.size() || tex.records[m.image].width == 0u)) { *which = m.image; return true; }
-        return false;
-    }
-    // ... or for its cutout masks (§34): every record that is on names an entry
-    bool cutout_entry_missing(uint32_t* which) const {
-        if (!cut.on) return false;
-        for (const rt_cutout& m : cut.host)
-            if (m.on && (!tex.on || m.image >= tex.records.size() || tex.records[m.image].width == 0u)) { *which = m.image; return true; }
-        return false;
-    }
-    // whether a launch is refused for its image materials (§25): one of them names an entry (*which) the renderer does not have
-    bool texture_entry_missing(uint32_t* which) const {
+    // ... or for its image materials (§25): one of them names an index (*which) the renderer does not serve
+    bool image_index_unserved(uint32_t* which) const {
         for (const uint32_t k : scene.image_indices)
             if (tex.on ? (k >= tex.records.size() || tex.records[k].width == 0u) : k != 0u) { *which = k; return true; }
         return false;
@@ -460,14 +387,9 @@ struct rt_renderer {
         LaunchOn l;
         l.kernel = m ? nee.resolved[m - LIGHT_MODES].kernel : stream_kernel;
         l.key = m ? nee.resolved[m - LIGHT_MODES].key : stream_kernel_key(variant, tol, scene);
-        if (nm.on && !m) { l.kernel = nm_plain.kernel; l.key = nm_plain.key; }   // §28: the other modes are refused while a table is on
-        if (nm.on && mode == RT_LIGHT_SAMPLING_ENV_TREE) { l.kernel = nm_envt.kernel; l.key = nm_envt.key; }
-        if (mf.on && !m) { l.kernel = mf_plain.kernel; l.key = mf_plain.key; }   // §29: likewise, and before a normal-map table's form: the MFAC forms read both
-        if (mf.on && mode == RT_LIGHT_SAMPLING_ENV_TREE) { l.kernel = mf_envt.kernel; l.key = mf_envt.key; }
-        if (in.on && !m) { l.kernel = in_plain.kernel; l.key = in_plain.key; }   // §32: likewise, and before either of them: the INTR forms read all three
-        if (in.on && mode == RT_LIGHT_SAMPLING_ENV_TREE) { l.kernel = in_envt.kernel; l.key = in_envt.key; }
-        if (cut.on && !m) { l.kernel = cut_plain.kernel; l.key = cut_plain.key; }   // §34: likewise, and before all of them: the CUT forms read all four
-        if (cut.on && mode == RT_LIGHT_SAMPLING_ENV_TREE) { l.kernel = cut_envt.kernel; l.key = cut_envt.key; }
+        if (!m || mode == RT_LIGHT_SAMPLING_ENV_TREE)   // the form of the highest rung that is on (the other modes are refused while a table is on)
+            for (uint32_t g = N_RUNGS; g-- > 0u;)
+                if (rung_on(g)) { l.kernel = form[g][m ? 1 : 0].kernel; l.key = form[g][m ? 1 : 0].key; break; }
         l.blob = (im.blob.p ? im.blob : scene.blob).as<uint4>();
         l.blob_vec4 = scene.packed.blob_vec4 + im.table_vec4;
         l.lds_bytes = i ? im.lds_bytes : stream_lds_bytes;
@@ -475,49 +397,13 @@ struct rt_renderer {
         l.lights = m && !i ? env.w * env.h : t.refused.empty() ? t.n : 0u;
         return l;
     }
-    // §28: the NMAP form of the plain kernel, or of mode 48's, once: the kernel and its LDS limit
-    int resolve_normal_map_kernel(bool envt, uint32_t lds_bytes) {
-        auto& slot_of = envt ? nm_envt : nm_plain;
+    // Rung g's form of the plain kernel, or of mode 48's, once: the kernel and its LDS limit
+    int resolve_form_kernel(uint32_t g, bool envt, uint32_t lds_bytes) {
+        auto& slot_of = form[g][envt ? 1 : 0];
         if (slot_of.kernel) return RT_OK;
-        const uint32_t key = normal_map_key(envt);
+        const uint32_t key = form_key(g, envt);
         const void* k = key ? stream_kernel_for(key) : nullptr;
-        if (!k) return rt_fail(RT_ERR_INVALID, "rt_renderer_normal_maps: this world's kernel has no form that reads a normal-map table");
-        HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-        slot_of.key = key; slot_of.kernel = k;
-        return RT_OK;
-    }
-    // §29: the MFAC form of the plain kernel, or of mode 48's, once: the NMAP form's shape with the microfacet bit in the normal-map bit's place
-    int resolve_microfacet_kernel(bool envt, uint32_t lds_bytes) {
-        auto& slot_of = envt ? mf_envt : mf_plain;
-        if (slot_of.kernel) return RT_OK;
-        const uint32_t nmap_key = normal_map_key(envt);
-        const uint32_t key = nmap_key ? (nmap_key & ~RT_KEY_NMAP) | RT_KEY_MFAC : 0u;
-        const void* k = key ? stream_kernel_for(key) : nullptr;
-        if (!k) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: this world's kernel has no form that reads a microfacet table");
-        HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-        slot_of.key = key; slot_of.kernel = k;
-        return RT_OK;
-    }
-    // §32: the INTR form of the plain kernel, or of mode 48's, once: the MFAC form's shape with the interior bit beside the microfacet bit
-    int resolve_interior_kernel(bool envt, uint32_t lds_bytes) {
-        auto& slot_of = envt ? in_envt : in_plain;
-        if (slot_of.kernel) return RT_OK;
-        const uint32_t nmap_key = normal_map_key(envt);
-        const uint32_t key = nmap_key ? (nmap_key & ~RT_KEY_NMAP) | RT_KEY_MFAC | RT_KEY_INTR : 0u;
-        const void* k = key ? stream_kernel_for(key) : nullptr;
-        if (!k) return rt_fail(RT_ERR_INVALID, "rt_renderer_interiors: this world's kernel has no form that reads an interior table");
-        HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-        slot_of.key = key; slot_of.kernel = k;
-        return RT_OK;
-    }
-    // §34: the CUT form of the plain kernel, or of mode 48's, once: the INTR form's shape with the cutout bit beside the other two
-    int resolve_cutout_kernel(bool envt, uint32_t lds_bytes) {
-        auto& slot_of = envt ? cut_envt : cut_plain;
-        if (slot_of.kernel) return RT_OK;
-        const uint32_t nmap_key = normal_map_key(envt);
-        const uint32_t key = nmap_key ? (nmap_key & ~RT_KEY_NMAP) | RT_KEY_MFAC | RT_KEY_INTR | RT_KEY_CUT : 0u;
-        const void* k = key ? stream_kernel_for(key) : nullptr;
-        if (!k) return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: this world's kernel has no form that reads a cutout table");
+        if (!k) return rt_fail(RT_ERR_INVALID, "%s: this world's kernel has no form that reads %s %s", FORM_LADDER[g].api, FORM_LADDER[g].a, FORM_LADDER[g].table);
         HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
         slot_of.key = key; slot_of.kernel = k;
         return RT_OK;
@@ -565,12 +451,19 @@ struct rt_renderer {
             if (!i || nee.image[i].blob.p) std::swap(nee.image[i], fresh[i]);
         return RT_OK;
     }
-    // A rider's state replaced by `next` and the images composed anew; on failure the rider gets its old state back, and no image has changed.
+    // A rider's state replaced by `next` and the images composed anew; on failure the rider gets its old state back, and no image and nothing of the refinement
+    // has changed.  On success the refinement and its first hits start anew: samples drawn on the old images belong to another frame.
     template <typename Rider> int replace_rider(Rider& rider, Rider& next) {
         std::swap(rider, next);
         const int rc = recompose();
-        if (rc != RT_OK) std::swap(rider, next);
-        return rc;
+        if (rc != RT_OK) { std::swap(rider, next); return rc; }
+        refine_done = aov_done = 0u;
+        return RT_OK;
+    }
+    // Whether `next` is the state the rider is in: both off, or both on with the same (canonical) host table.  Then nothing changes and the refinement goes on.
+    template <typename Rider> static bool same_table(const Rider& rider, const Rider& next) {
+        if (!next.on || !rider.on) return next.on == rider.on;
+        return rider.host.size() == next.host.size() && std::memcmp(rider.host.data(), next.host.data(), next.host.size() * sizeof(next.host[0])) == 0;
     }
     // denoiser (rt_renderer_denoise): guide records, the two colour buffers the iterations ping-pong, the output frame; allocated at first use
     DevBuf dn_g0, dn_g1, dn_a, dn_b, dn_out;
@@ -1092,13 +985,13 @@ extern "C" void rt_renderer_destroy(rt_renderer* r) {
 static int enqueue_call(rt_renderer* r, void* hip_stream, float* d_out, uint32_t first_s, uint32_t n_s, bool refine, bool run_ahead = false) {
     if (r->scene.dw.background == 2u && !r->env.on)   // never launch with a dangling record
         return rt_fail(RT_ERR_INVALID, "the world's background is an environment map (mode 2) and the renderer has none: give it one with rt_renderer_environment before rendering");
-    if (uint32_t k = 0u; r->texture_entry_missing(&k))   // never launch on an index the table does not hold
+    if (uint32_t k = 0u; r->image_index_unserved(&k))   // never launch on an index the table does not hold
         return rt_fail(RT_ERR_INVALID, "an image material of the world names image %u and the renderer's texture table has no such entry: give it one with rt_renderer_textures before rendering", k);
-    if (uint32_t k = 0u; r->normal_map_entry_missing(&k))   // ... nor on a normal map the table does not hold
+    if (uint32_t k = 0u; r->entry_missing(r->nm, [](const rt_normal_map& m) { return m.on != 0u; }, &k))   // ... nor on a normal map the table does not hold
         return rt_fail(RT_ERR_INVALID, "a normal map of the world names image %u and the renderer's texture table has no such entry: give it one with rt_renderer_textures before rendering", k);
-    if (uint32_t k = 0u; r->cutout_entry_missing(&k))   // ... nor on a cutout mask it does not hold
+    if (uint32_t k = 0u; r->entry_missing(r->cut, [](const rt_cutout& m) { return m.on != RT_CUTOUT_OFF; }, &k))   // ... nor on a cutout mask it does not hold: every record that is on names one
         return rt_fail(RT_ERR_INVALID, "a cutout record of the world names image %u and the renderer's texture table has no such entry: give it one with rt_renderer_textures before rendering", k);
-    if (uint32_t k = 0u; r->roughness_map_entry_missing(&k))   // ... nor on a roughness map it does not hold
+    if (uint32_t k = 0u; r->entry_missing(r->mf, [](const rt_microfacet& m) { return m.on == RT_MICROFACET_MAPPED || m.on == RT_MICROFACET_GLASS_MAPPED; }, &k))   // ... nor on a roughness map it does not hold; constant records need no texture table
         return rt_fail(RT_ERR_INVALID, "a roughness map of the world names image %u and the renderer's texture table has no such entry: give it one with rt_renderer_textures before rendering", k);
     HIP_TRY(hipSetDevice(r->cfg.device));
     hipStream_t st = (hipStream_t)hip_stream;  // NULL is the HIP null stream, as for any HIP launch
@@ -1167,14 +1060,9 @@ extern "C" int rt_renderer_light_sampling_enable(rt_renderer* r, uint32_t on) {
         const rt_renderer::LightTable* t = m->image ? &r->nee.tab[m->image - 1u] : nullptr;
         if (r->variant < 2 || r->variant == 5 || r->tol)
             return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: kernel variant %u has no light-sampling form (the baseline kernel 1, the ray exchange 5 and the tolerance mode 6 do not; use variant 0, 2 or 3)", r->tol ? 6u : r->variant);
-        if (r->nm.on && on != RT_LIGHT_SAMPLING_ENV_TREE)
-            return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: the renderer has a normal-map table, and light-sampling mode %u has no kernel that reads one: normal maps render with light sampling off or in mode 48 (take the table away with rt_renderer_normal_maps(NULL, 0) first)", on);
-        if (r->mf.on && on != RT_LIGHT_SAMPLING_ENV_TREE)
-            return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: the renderer has a microfacet table, and light-sampling mode %u has no kernel that reads one: microfacet surfaces render with light sampling off or in mode 48 (take the table away with rt_renderer_microfacets(NULL, 0) first)", on);
-        if (r->in.on && on != RT_LIGHT_SAMPLING_ENV_TREE)
-            return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: the renderer has an interior table, and light-sampling mode %u has no kernel that reads one: solid glass renders with light sampling off or in mode 48 (take the table away with rt_renderer_interiors(NULL, 0) first)", on);
-        if (r->cut.on && on != RT_LIGHT_SAMPLING_ENV_TREE)
-            return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: the renderer has a cutout table, and light-sampling mode %u has no kernel that reads one: alpha cutouts render with light sampling off or in mode 48 (take the table away with rt_renderer_cutouts(NULL, 0) first)", on);
+        for (uint32_t g = 0; g < N_RUNGS; g++)   // (the lowest rung that is on speaks)
+            if (const FormRung& f = FORM_LADDER[g]; r->rung_on(g) && on != RT_LIGHT_SAMPLING_ENV_TREE)
+                return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: the renderer has %s %s, and light-sampling mode %u has no kernel that reads one: %s with light sampling off or in mode 48 (take the table away with %s(NULL, 0) first)", f.a, f.table, on, f.surfaces_render, f.api);
         if (m->env && r->scene.dw.background != 2u)   // a world of this kind takes the modes of the light tables only, so the message lists them
             return rt_fail(RT_ERR_INVALID, "rt_renderer_light_sampling_enable: mode %u samples the environment map of a world with background mode 2 (rt_scene_set_environment)%s; this world's is %u, for which on must be 0 (off), 1 (quad lights), 2 (quad and sphere lights), 4 (quad, sphere and triangle lights) or 16 (those, through a light tree, chosen by area)", on, m->beside, r->scene.dw.background);
         if (m->env && r->scene.queue)
@@ -1203,14 +1091,9 @@ extern "C" int rt_renderer_light_sampling_enable(rt_renderer* r, uint32_t on) {
             resolved.key = key;
             resolved.kernel = k;
         }
-        if (r->nm.on)   // §28: mode 48's NMAP form, on the image of mode 16's table
-            if (const int rc = r->resolve_normal_map_kernel(true, r->launch_on(on).lds_bytes)) return rc;
-        if (r->mf.on)   // §29: likewise
-            if (const int rc = r->resolve_microfacet_kernel(true, r->launch_on(on).lds_bytes)) return rc;
-        if (r->in.on)   // §32: likewise
-            if (const int rc = r->resolve_interior_kernel(true, r->launch_on(on).lds_bytes)) return rc;
-        if (r->cut.on)   // §34: likewise
-            if (const int rc = r->resolve_cutout_kernel(true, r->launch_on(on).lds_bytes)) return rc;
+        for (uint32_t g = 0; g < N_RUNGS; g++)   // mode 48's form of every rung that is on, on the image of mode 16's table
+            if (r->rung_on(g))
+                if (const int rc = r->resolve_form_kernel(g, true, r->launch_on(on).lds_bytes)) return rc;
         if (m->env && !r->env.dist_on) {   // the distribution of the map as it stands (a map given while the mode is on brings its own: rt_renderer_environment); an all-black map is refused here
             char who[64];
             std::snprintf(who, sizeof(who), "rt_renderer_light_sampling_enable: mode %u", on);
@@ -1233,76 +1116,95 @@ extern "C" int rt_renderer_light_sampling_info(rt_renderer* r, uint32_t out[2]) 
     return RT_OK;
 }
 
+// The table setters.  Each builds the next state of its rider — its own record loop and canonical form (what no kernel reads is zero, so that equal tables are
+// equal bytes) — between a shared beginning and a shared end.
+// The beginning of a per-triangle table's setter (vertex normals, texture coordinates): what it refuses before it reads a record.
+static int triangle_table_refusal(const char* api, const char* what, rt_renderer* r, bool has_table, uint32_t n) {
+    if (!r) return rt_fail(RT_ERR_INVALID, "%s: null renderer", api);
+    if (has_table != (n != 0u)) return rt_fail(RT_ERR_INVALID, "%s: a table and its count go together (NULL, 0 turns it off)", api);
+    if (!n) return RT_OK;
+    if (r->variant < 2) return rt_fail(RT_ERR_INVALID, "%s: the baseline kernel (variant 1) reads no %s; use variant 0, 2 or 3", api, what);
+    if (r->scene.queue) return rt_fail(RT_ERR_INVALID, "%s: a world with a queue or wide4 traversal renders on lane walks that read no %s (RT_TRAVERSAL_STACK and lists do)", api, what);
+    if (r->variant == 5 || r->tol) return rt_fail(RT_ERR_INVALID, "%s: kernel variant %u renders no triangles", api, r->tol ? 6u : 5u);
+    if (n != r->scene.n_triangles) return rt_fail(RT_ERR_INVALID, "%s: %u records for a world of %u triangles", api, n, r->scene.n_triangles);
+    return RT_OK;
+}
+// The beginning of a per-material table's setter (rung g of FORM_LADDER); `extra` holds the setter's own refusals, which come before the count's.
+template <typename Extra> static int material_table_refusal(uint32_t g, rt_renderer* r, bool has_table, uint32_t n, Extra extra) {
+    const FormRung& f = FORM_LADDER[g];
+    if (!r) return rt_fail(RT_ERR_INVALID, "%s: null renderer", f.api);
+    if (has_table != (n != 0u)) return rt_fail(RT_ERR_INVALID, "%s: a table and its count go together (NULL, 0 turns it off)", f.api);
+    if (!n) return RT_OK;
+    if (r->variant < 2) return rt_fail(RT_ERR_INVALID, "%s: the baseline kernel (variant 1) reads no %s; use variant 0, 2 or 3", f.api, f.table);
+    if (r->variant == 5 || r->tol) return rt_fail(RT_ERR_INVALID, "%s: kernel variant %u %s", f.api, r->tol ? 6u : 5u, f.variant_5_6);
+    if (r->scene.queue) return rt_fail(RT_ERR_INVALID, "%s: a world with a queue or wide4 traversal renders on lane walks that read no %s (RT_TRAVERSAL_STACK and lists do)", f.api, f.table);
+    if (r->scene.dw.kind == RT_WORLD_NODE_TREE) return rt_fail(RT_ERR_INVALID, "%s: a bvh_node tree renders on a walk that reads no %s (BVHs walked by the stack and lists do)", f.api, f.table);
+    if (r->nee.on() && r->nee.mode != RT_LIGHT_SAMPLING_ENV_TREE)
+        return rt_fail(RT_ERR_INVALID, "%s: light-sampling mode %u is on, which has no kernel that reads %s %s: %s with light sampling off or in mode 48", f.api, r->nee.mode, f.a, f.table, f.surfaces_render);
+    if (const int rc = extra()) return rc;
+    if (n != r->scene.dw.n_mats) return rt_fail(RT_ERR_INVALID, "%s: %u records for a world of %u materials", f.api, n, r->scene.dw.n_mats);
+    return RT_OK;
+}
+// The end of every table's setter.  Nothing happens if `next` is the state the rider is in.  Else, behind a wait for the launches already enqueued, which read the
+// images that are replaced (it sets the device), the forms of the table's rung are resolved (g; N_RUNGS: a table every kernel reads) and the rider replaced.  A
+// failure leaves table, kernels, images and refinement as they were.
+template <typename Rider> static int install_table(rt_renderer* r, uint32_t g, Rider& rider, Rider& next) {
+    if (rt_renderer::same_table(rider, next)) return RT_OK;
+    if (const int rc = wait_last_call(r)) return rc;
+    if (next.on && g < N_RUNGS) {   // the plain form, and mode 48's while that mode is on
+        if (const int rc = r->resolve_form_kernel(g, false, r->stream_lds_bytes)) return rc;
+        if (r->nee.mode == RT_LIGHT_SAMPLING_ENV_TREE)
+            if (const int rc = r->resolve_form_kernel(g, true, r->launch_on(RT_LIGHT_SAMPLING_ENV_TREE).lds_bytes)) return rc;
+    }
+    return r->replace_rider(rider, next);
+}
+
 // Smooth shading.  Off: every launch is what it was.  On: the same kernels on images whose tail holds the table.
 extern "C" int rt_renderer_shading_normals(rt_renderer* r, const rt_tri_normals* table, uint32_t n) {
-    if (!r) return rt_fail(RT_ERR_INVALID, "rt_renderer_shading_normals: null renderer");
-    if ((table == nullptr) != (n == 0u)) return rt_fail(RT_ERR_INVALID, "rt_renderer_shading_normals: a table and its count go together (NULL, 0 turns it off)");
-    uint32_t n_smooth = 0;
-    if (n) {
-        if (r->variant < 2) return rt_fail(RT_ERR_INVALID, "rt_renderer_shading_normals: the baseline kernel (variant 1) reads no table of vertex normals; use variant 0, 2 or 3");
-        if (r->scene.queue) return rt_fail(RT_ERR_INVALID, "rt_renderer_shading_normals: a world with a queue or wide4 traversal renders on lane walks that read no table of vertex normals (RT_TRAVERSAL_STACK and lists do)");
-        if (r->variant == 5 || r->tol) return rt_fail(RT_ERR_INVALID, "rt_renderer_shading_normals: kernel variant %u renders no triangles", r->tol ? 6u : 5u);
-        if (n != r->scene.n_triangles) return rt_fail(RT_ERR_INVALID, "rt_renderer_shading_normals: %u records for a world of %u triangles", n, r->scene.n_triangles);
-        for (uint32_t i = 0; i < n; i++) {
-            const float* v = table[i].n0;   // nine floats: n0, n1, n2
-            uint32_t n_zero = 0;
-            for (int k = 0; k < 9; k++)
-                if (!std::isfinite(v[k])) return rt_fail(RT_ERR_INVALID, "rt_renderer_shading_normals: record %u: a value that is not finite", i);
-            for (int k = 0; k < 3; k++)
-                if (v[3 * k] == 0.0f && v[3 * k + 1] == 0.0f && v[3 * k + 2] == 0.0f) n_zero++;
-            if (n_zero != 0u && n_zero != 3u) return rt_fail(RT_ERR_INVALID, "rt_renderer_shading_normals: record %u: %u of its three normals are zero (all zero = a flat triangle, or none)", i, n_zero);
-            if (n_zero == 0u) n_smooth++;
-        }
-    }
-    const size_t bytes = (size_t)n * sizeof(rt_tri_normals);
-    if (n ? (r->vn.on && r->vn.host.size() * sizeof(float) == bytes && std::memcmp(r->vn.host.data(), table, bytes) == 0) : !r->vn.on) return RT_OK;   // nothing changes, the refinement goes on
-    if (const int rc = wait_last_call(r)) return rc;   // launches already enqueued read the images that are replaced below
-    r->refine_done = 0;   // samples shaded with other normals belong to another frame
-    r->aov_done = 0;
+    if (const int rc = triangle_table_refusal("rt_renderer_shading_normals", "table of vertex normals", r, table != nullptr, n)) return rc;
     decltype(r->vn) next;   // off, unless a table is given; the other riders stay as they are
-    if (n) {
-        next.on = true; next.n_smooth = n_smooth;
-        next.host.assign(table[0].n0, table[0].n0 + (size_t)n * 9u);
-        HIP_TRY(next.table.upload(next.host.data(), bytes));
+    for (uint32_t i = 0; i < n; i++) {
+        const float* v = table[i].n0;   // nine floats: n0, n1, n2
+        uint32_t n_zero = 0;
+        for (int k = 0; k < 9; k++)
+            if (!std::isfinite(v[k])) return rt_fail(RT_ERR_INVALID, "rt_renderer_shading_normals: record %u: a value that is not finite", i);
+        for (int k = 0; k < 3; k++)
+            if (v[3 * k] == 0.0f && v[3 * k + 1] == 0.0f && v[3 * k + 2] == 0.0f) n_zero++;
+        if (n_zero != 0u && n_zero != 3u) return rt_fail(RT_ERR_INVALID, "rt_renderer_shading_normals: record %u: %u of its three normals are zero (all zero = a flat triangle, or none)", i, n_zero);
+        if (n_zero == 0u) next.n_smooth++;
     }
-    return r->replace_rider(r->vn, next);
+    if (n) { next.on = true; next.host.assign(table[0].n0, table[0].n0 + (size_t)n * 9u); }
+    if (n && !rt_renderer::same_table(r->vn, next)) {   // the feature pass's flat copy, of a table that will be installed
+        HIP_TRY(hipSetDevice(r->cfg.device));
+        HIP_TRY(next.table.upload(next.host.data(), next.host.size() * sizeof(float)));
+    }
+    return install_table(r, N_RUNGS, r->vn, next);
 }
 
 // Texture coordinates, as the normals above: off, every launch is what it was; on, the same kernels on images whose tail holds the table.
 extern "C" int rt_renderer_texture_coords(rt_renderer* r, const rt_tri_uvs* table, uint32_t n) {
-    if (!r) return rt_fail(RT_ERR_INVALID, "rt_renderer_texture_coords: null renderer");
-    if ((table == nullptr) != (n == 0u)) return rt_fail(RT_ERR_INVALID, "rt_renderer_texture_coords: a table and its count go together (NULL, 0 turns it off)");
-    uint32_t n_mapped = 0;
-    if (n) {
-        if (r->variant < 2) return rt_fail(RT_ERR_INVALID, "rt_renderer_texture_coords: the baseline kernel (variant 1) reads no table of texture coordinates; use variant 0, 2 or 3");
-        if (r->scene.queue) return rt_fail(RT_ERR_INVALID, "rt_renderer_texture_coords: a world with a queue or wide4 traversal renders on lane walks that read no table of texture coordinates (RT_TRAVERSAL_STACK and lists do)");
-        if (r->variant == 5 || r->tol) return rt_fail(RT_ERR_INVALID, "rt_renderer_texture_coords: kernel variant %u renders no triangles", r->tol ? 6u : 5u);
-        if (n != r->scene.n_triangles) return rt_fail(RT_ERR_INVALID, "rt_renderer_texture_coords: %u records for a world of %u triangles", n, r->scene.n_triangles);
-        static const float identity[6] = {0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 1.0f};
-        for (uint32_t i = 0; i < n; i++) {
-            const float* v = table[i].t0;   // six floats: t0, t1, t2
-            for (int k = 0; k < 6; k++)
-                if (!std::isfinite(v[k])) return rt_fail(RT_ERR_INVALID, "rt_renderer_texture_coords: record %u: a value that is not finite", i);
-            for (int k = 0; k < 6; k++)
-                if (v[k] != identity[k]) { n_mapped++; break; }
-        }
-    }
-    const size_t bytes = (size_t)n * sizeof(rt_tri_uvs);
-    if (n ? (r->uv.on && r->uv.host.size() * sizeof(float) == bytes && std::memcmp(r->uv.host.data(), table, bytes) == 0) : !r->uv.on) return RT_OK;   // nothing changes, the refinement goes on
-    if (const int rc = wait_last_call(r)) return rc;   // launches already enqueued read the images that are replaced below
-    r->refine_done = 0;   // samples textured through other coordinates belong to another frame
-    r->aov_done = 0;
+    if (const int rc = triangle_table_refusal("rt_renderer_texture_coords", "table of texture coordinates", r, table != nullptr, n)) return rc;
     decltype(r->uv) next;
-    if (n) { next.on = true; next.n_mapped = n_mapped; next.host.assign(table[0].t0, table[0].t0 + (size_t)n * 6u); }
-    return r->replace_rider(r->uv, next);
+    static const float identity[6] = {0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 1.0f};
+    for (uint32_t i = 0; i < n; i++) {
+        const float* v = table[i].t0;   // six floats: t0, t1, t2
+        for (int k = 0; k < 6; k++)
+            if (!std::isfinite(v[k])) return rt_fail(RT_ERR_INVALID, "rt_renderer_texture_coords: record %u: a value that is not finite", i);
+        for (int k = 0; k < 6; k++)
+            if (v[k] != identity[k]) { next.n_mapped++; break; }
+    }
+    if (n) { next.on = true; next.host.assign(table[0].t0, table[0].t0 + (size_t)n * 6u); }
+    return install_table(r, N_RUNGS, r->uv, next);
 }
 
-extern "C" int rt_renderer_texture_coords_info(rt_renderer* r, uint32_t out[2]) {
-    if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_texture_coords_info: null argument");
-    out[0] = r->uv.on ? 1u : 0u;
-    out[1] = r->uv.on ? r->uv.n_mapped : 0u;
+// What a table's _info query answers: whether the rider is on, and how many of its records say something
+template <typename Rider> static int rider_info(const char* api, rt_renderer* r, uint32_t out[2], Rider rt_renderer::* rider) {
+    if (!r || !out) return rt_fail(RT_ERR_INVALID, "%s: null argument", api);
+    out[0] = (r->*rider).on ? 1u : 0u;
+    out[1] = (r->*rider).on ? (r->*rider).count() : 0u;
     return RT_OK;
 }
+extern "C" int rt_renderer_texture_coords_info(rt_renderer* r, uint32_t out[2]) { return rider_info("rt_renderer_texture_coords_info", r, out, &rt_renderer::uv); }
 
 // The environment map of a background-2 world.  The texels live in a buffer of the renderer's own; every image it launches on gets the tail record
 // that points there.  Off, a background-2 renderer refuses to launch (enqueue_call).
@@ -1330,9 +1232,7 @@ extern "C" int rt_renderer_environment(rt_renderer* r, uint32_t width, uint32_t 
         next.host.assign(rgb, rgb + n_texels * 3u);
         if (const int rc = rt_renderer::upload_environment(who, next, sampled)) return rc;
     }
-    r->refine_done = 0;   // samples lit by another sky belong to another frame
-    r->aov_done = 0;
-    return r->replace_rider(r->env, next);
+    return r->replace_rider(r->env, next);   // (samples lit by another sky belong to another frame)
 }
 
 extern "C" int rt_renderer_environment_info(rt_renderer* r, uint32_t out[4]) {
@@ -1364,246 +1264,134 @@ extern "C" int rt_renderer_textures(rt_renderer* r, const rt_texture* records, u
         next.on = true; next.records.assign(records, records + n); next.host.assign(texels, texels + n_texels * 3u);
     }
     if (const int rc = wait_last_call(r)) return rc;   // launches already enqueued read the images and the texels that are replaced below
-    r->refine_done = 0;   // samples textured by other images belong to another frame
-    r->aov_done = 0;
-    return r->replace_rider(r->tex, next);
+    return r->replace_rider(r->tex, next);   // (samples textured by other images belong to another frame)
 }
 
 // Normal maps.  Off: every launch is what it was.  On: the NMAP form of the renderer's kernel on images whose tail holds the records behind the
 // texture table.  The entries the records name are checked at every launch (enqueue_call), as an image material's is: the tables come and go independently.
 extern "C" int rt_renderer_normal_maps(rt_renderer* r, const rt_normal_map* table, uint32_t n) {
-    if (!r) return rt_fail(RT_ERR_INVALID, "rt_renderer_normal_maps: null renderer");
-    if ((table == nullptr) != (n == 0u)) return rt_fail(RT_ERR_INVALID, "rt_renderer_normal_maps: a table and its count go together (NULL, 0 turns it off)");
-    uint32_t n_mapped = 0;
-    if (n) {
-        if (r->variant < 2) return rt_fail(RT_ERR_INVALID, "rt_renderer_normal_maps: the baseline kernel (variant 1) reads no normal-map table; use variant 0, 2 or 3");
-        if (r->variant == 5 || r->tol) return rt_fail(RT_ERR_INVALID, "rt_renderer_normal_maps: kernel variant %u reads no texture table and no normal-map table", r->tol ? 6u : 5u);
-        if (r->scene.queue) return rt_fail(RT_ERR_INVALID, "rt_renderer_normal_maps: a world with a queue or wide4 traversal renders on lane walks that read no normal-map table (RT_TRAVERSAL_STACK and lists do)");
-        if (r->scene.dw.kind == RT_WORLD_NODE_TREE) return rt_fail(RT_ERR_INVALID, "rt_renderer_normal_maps: a bvh_node tree renders on a walk that reads no normal-map table (BVHs walked by the stack and lists do)");
-        if (r->nee.on() && r->nee.mode != RT_LIGHT_SAMPLING_ENV_TREE)
-            return rt_fail(RT_ERR_INVALID, "rt_renderer_normal_maps: light-sampling mode %u is on, which has no kernel that reads a normal-map table: normal maps render with light sampling off or in mode 48", r->nee.mode);
-        if (r->aov_on && r->aov_mode == RT_AOV_PLAIN)
-            return rt_fail(RT_ERR_INVALID, "rt_renderer_normal_maps: the plain feature pass is on, whose normals know no normal map: enable it in RT_AOV_TEXTURED mode (rt_renderer_aov_enable_mode)");
-        if (n != r->scene.dw.n_mats) return rt_fail(RT_ERR_INVALID, "rt_renderer_normal_maps: %u records for a world of %u materials", n, r->scene.dw.n_mats);
-        for (uint32_t i = 0; i < n; i++) {
-            if (!table[i].on) continue;
-            const uint32_t type = r->scene.mat_types[i];
-            if (type == RT_MAT_DIELECTRIC || type == RT_MAT_DIFFUSE_LIGHT || type == RT_MAT_ISOTROPIC)
-                return rt_fail(RT_ERR_INVALID, "rt_renderer_normal_maps: record %u: a dielectric, a light or a medium takes no normal map", i);
-            if (table[i].image >= RT_MAX_IMAGES) return rt_fail(RT_ERR_INVALID, "rt_renderer_normal_maps: record %u: an image index lies in [0, %u)", i, RT_MAX_IMAGES);
-            if (!(std::isfinite(table[i].strength) && table[i].strength >= 0.0f)) return rt_fail(RT_ERR_INVALID, "rt_renderer_normal_maps: record %u: a strength must be finite and >= 0", i);
-            n_mapped++;
-        }
-    }
-    const size_t bytes = (size_t)n * sizeof(rt_normal_map);
-    if (n ? (r->nm.on && r->nm.host.size() == n && std::memcmp(r->nm.host.data(), table, bytes) == 0) : !r->nm.on) return RT_OK;   // nothing changes, the refinement goes on
-    if (const int rc = wait_last_call(r)) return rc;   // launches already enqueued read the images that are replaced below (sets the device)
-    if (n) {
-        if (const int rc = r->resolve_normal_map_kernel(false, r->stream_lds_bytes)) return rc;
-        if (r->nee.mode == RT_LIGHT_SAMPLING_ENV_TREE)
-            if (const int rc = r->resolve_normal_map_kernel(true, r->launch_on(RT_LIGHT_SAMPLING_ENV_TREE).lds_bytes)) return rc;
-    }
-    r->refine_done = 0;   // samples shaded with other normals belong to another frame
-    r->aov_done = 0;
+    if (const int rc = material_table_refusal(RUNG_NMAP, r, table != nullptr, n, [&] {
+            return r->aov_on && r->aov_mode == RT_AOV_PLAIN
+                ? rt_fail(RT_ERR_INVALID, "rt_renderer_normal_maps: the plain feature pass is on, whose normals know no normal map: enable it in RT_AOV_TEXTURED mode (rt_renderer_aov_enable_mode)") : RT_OK;
+        })) return rc;
     rt_renderer::NormalMaps next;
+    for (uint32_t i = 0; i < n; i++) {
+        if (!table[i].on) continue;
+        const uint32_t type = r->scene.mat_types[i];
+        if (type == RT_MAT_DIELECTRIC || type == RT_MAT_DIFFUSE_LIGHT || type == RT_MAT_ISOTROPIC)
+            return rt_fail(RT_ERR_INVALID, "rt_renderer_normal_maps: record %u: a dielectric, a light or a medium takes no normal map", i);
+        if (table[i].image >= RT_MAX_IMAGES) return rt_fail(RT_ERR_INVALID, "rt_renderer_normal_maps: record %u: an image index lies in [0, %u)", i, RT_MAX_IMAGES);
+        if (!(std::isfinite(table[i].strength) && table[i].strength >= 0.0f)) return rt_fail(RT_ERR_INVALID, "rt_renderer_normal_maps: record %u: a strength must be finite and >= 0", i);
+        next.n_mapped++;
+    }
     if (n) {
-        next.on = true; next.n_mapped = n_mapped; next.host.assign(table, table + n);
+        next.on = true; next.host.assign(table, table + n);
         for (rt_normal_map& m : next.host) { m.pad = 0u; if (!m.on) m = rt_normal_map{0u, 0u, 0.0f, 0u}; }
     }
-    return r->replace_rider(r->nm, next);
+    return install_table(r, RUNG_NMAP, r->nm, next);   // (samples shaded with other normals belong to another frame)
 }
 
-extern "C" int rt_renderer_normal_maps_info(rt_renderer* r, uint32_t out[2]) {
-    if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_normal_maps_info: null argument");
-    out[0] = r->nm.on ? 1u : 0u;
-    out[1] = r->nm.on ? r->nm.n_mapped : 0u;
-    return RT_OK;
-}
+extern "C" int rt_renderer_normal_maps_info(rt_renderer* r, uint32_t out[2]) { return rider_info("rt_renderer_normal_maps_info", r, out, &rt_renderer::nm); }
 
 // Microfacet surfaces.  Off: every launch is what it was.  On: the MFAC form of the renderer's kernel on images whose tail ends with the records.
 // The entries mapped records name are checked at every launch (enqueue_call), as a normal map's are: the tables come and go independently.
 extern "C" int rt_renderer_microfacets(rt_renderer* r, const rt_microfacet* table, uint32_t n) {
-    if (!r) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: null renderer");
-    if ((table == nullptr) != (n == 0u)) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: a table and its count go together (NULL, 0 turns it off)");
-    uint32_t n_on = 0;
-    if (n) {
-        if (r->variant < 2) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: the baseline kernel (variant 1) reads no microfacet table; use variant 0, 2 or 3");
-        if (r->variant == 5 || r->tol) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: kernel variant %u reads no microfacet table", r->tol ? 6u : 5u);
-        if (r->scene.queue) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: a world with a queue or wide4 traversal renders on lane walks that read no microfacet table (RT_TRAVERSAL_STACK and lists do)");
-        if (r->scene.dw.kind == RT_WORLD_NODE_TREE) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: a bvh_node tree renders on a walk that reads no microfacet table (BVHs walked by the stack and lists do)");
-        if (r->nee.on() && r->nee.mode != RT_LIGHT_SAMPLING_ENV_TREE)
-            return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: light-sampling mode %u is on, which has no kernel that reads a microfacet table: microfacet surfaces render with light sampling off or in mode 48", r->nee.mode);
-        if (n != r->scene.dw.n_mats) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: %u records for a world of %u materials", n, r->scene.dw.n_mats);
-        for (uint32_t i = 0; i < n; i++) {
-            if (table[i].on == RT_MICROFACET_OFF) continue;
-            const bool glass = table[i].on == RT_MICROFACET_GLASS || table[i].on == RT_MICROFACET_GLASS_MAPPED;   // §30: kinds of their own, on dielectrics alone
-            if (glass) {
-                if (r->scene.mat_types[i] != RT_MAT_DIELECTRIC) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: record %u: a rough-glass record (on = %u) belongs on a dielectric alone", i, table[i].on);
-                if (table[i].on == RT_MICROFACET_GLASS_MAPPED && table[i].image >= RT_MAX_IMAGES) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: record %u: a rough-glass record's image index lies in [0, %u)", i, RT_MAX_IMAGES);
-                if (!(std::isfinite(table[i].roughness) && table[i].roughness >= 0.0f && table[i].roughness <= 1.0f)) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: record %u: a rough-glass record's roughness must be finite and in [0, 1]", i);
-                if (table[i].specular != 0.0f) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: record %u: a rough-glass record reads no specular; it is stored as 0", i);
-                n_on++;
-                continue;
-            }
-            if (table[i].on > RT_MICROFACET_MAPPED) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: record %u: on is 0 (off), 1 (constant roughness) or 2 (roughness under a map), not %u", i, table[i].on);
-            const uint32_t type = r->scene.mat_types[i];
-            if (type == RT_MAT_DIELECTRIC || type == RT_MAT_DIFFUSE_LIGHT || type == RT_MAT_ISOTROPIC)
-                return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: record %u: a dielectric, a light or a medium takes no microfacet record", i);
-            if (table[i].on == RT_MICROFACET_MAPPED && table[i].image >= RT_MAX_IMAGES) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: record %u: an image index lies in [0, %u)", i, RT_MAX_IMAGES);
-            if (!(std::isfinite(table[i].roughness) && table[i].roughness >= 0.0f && table[i].roughness <= 1.0f)) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: record %u: a roughness must be finite and in [0, 1]", i);
-            if (!(std::isfinite(table[i].specular) && table[i].specular >= 0.0f && table[i].specular <= 1.0f)) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: record %u: a specular must be finite and in [0, 1]", i);
-            n_on++;
-        }
-    }
+    if (const int rc = material_table_refusal(RUNG_MFAC, r, table != nullptr, n, [] { return RT_OK; })) return rc;
     rt_renderer::Microfacets next;
+    for (uint32_t i = 0; i < n; i++) {
+        if (table[i].on == RT_MICROFACET_OFF) continue;
+        const bool glass = table[i].on == RT_MICROFACET_GLASS || table[i].on == RT_MICROFACET_GLASS_MAPPED;   // §30: kinds of their own, on dielectrics alone
+        if (glass) {
+            if (r->scene.mat_types[i] != RT_MAT_DIELECTRIC) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: record %u: a rough-glass record (on = %u) belongs on a dielectric alone", i, table[i].on);
+            if (table[i].on == RT_MICROFACET_GLASS_MAPPED && table[i].image >= RT_MAX_IMAGES) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: record %u: a rough-glass record's image index lies in [0, %u)", i, RT_MAX_IMAGES);
+            if (!(std::isfinite(table[i].roughness) && table[i].roughness >= 0.0f && table[i].roughness <= 1.0f)) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: record %u: a rough-glass record's roughness must be finite and in [0, 1]", i);
+            if (table[i].specular != 0.0f) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: record %u: a rough-glass record reads no specular; it is stored as 0", i);
+            next.n_on++;
+            continue;
+        }
+        if (table[i].on > RT_MICROFACET_MAPPED) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: record %u: on is 0 (off), 1 (constant roughness) or 2 (roughness under a map), not %u", i, table[i].on);
+        const uint32_t type = r->scene.mat_types[i];
+        if (type == RT_MAT_DIELECTRIC || type == RT_MAT_DIFFUSE_LIGHT || type == RT_MAT_ISOTROPIC)
+            return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: record %u: a dielectric, a light or a medium takes no microfacet record", i);
+        if (table[i].on == RT_MICROFACET_MAPPED && table[i].image >= RT_MAX_IMAGES) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: record %u: an image index lies in [0, %u)", i, RT_MAX_IMAGES);
+        if (!(std::isfinite(table[i].roughness) && table[i].roughness >= 0.0f && table[i].roughness <= 1.0f)) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: record %u: a roughness must be finite and in [0, 1]", i);
+        if (!(std::isfinite(table[i].specular) && table[i].specular >= 0.0f && table[i].specular <= 1.0f)) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets: record %u: a specular must be finite and in [0, 1]", i);
+        next.n_on++;
+    }
     if (n) {
-        next.on = true; next.n_on = n_on; next.host.assign(table, table + n);
-        for (rt_microfacet& m : next.host) {   // what no kernel reads is zero, so that equal tables are equal bytes
+        next.on = true; next.host.assign(table, table + n);
+        for (rt_microfacet& m : next.host) {
             if (m.on == RT_MICROFACET_OFF) m = rt_microfacet{RT_MICROFACET_OFF, 0u, 0.0f, 0.0f};
             if (m.on == RT_MICROFACET_CONSTANT || m.on == RT_MICROFACET_GLASS) m.image = 0u;
             if (m.on == RT_MICROFACET_GLASS || m.on == RT_MICROFACET_GLASS_MAPPED) m.specular = 0.0f;
         }
     }
-    if (n ? (r->mf.on && r->mf.host.size() == n && std::memcmp(r->mf.host.data(), next.host.data(), (size_t)n * sizeof(rt_microfacet)) == 0) : !r->mf.on) return RT_OK;   // nothing changes, the refinement goes on
-    if (const int rc = wait_last_call(r)) return rc;   // launches already enqueued read the images that are replaced below (sets the device)
-    if (n) {
-        if (const int rc = r->resolve_microfacet_kernel(false, r->stream_lds_bytes)) return rc;
-        if (r->nee.mode == RT_LIGHT_SAMPLING_ENV_TREE)
-            if (const int rc = r->resolve_microfacet_kernel(true, r->launch_on(RT_LIGHT_SAMPLING_ENV_TREE).lds_bytes)) return rc;
-    }
-    r->refine_done = 0;   // samples scattered by another rule belong to another frame
-    r->aov_done = 0;
-    return r->replace_rider(r->mf, next);
+    return install_table(r, RUNG_MFAC, r->mf, next);   // (samples scattered by another rule belong to another frame)
 }
 
-extern "C" int rt_renderer_microfacets_info(rt_renderer* r, uint32_t out[2]) {
-    if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_microfacets_info: null argument");
-    out[0] = r->mf.on ? 1u : 0u;
-    out[1] = r->mf.on ? r->mf.n_on : 0u;
-    return RT_OK;
-}
+extern "C" int rt_renderer_microfacets_info(rt_renderer* r, uint32_t out[2]) { return rider_info("rt_renderer_microfacets_info", r, out, &rt_renderer::mf); }
 
 // Solid glass.  Off: every launch is what it was.  On: the INTR form of the renderer's kernel on images whose tail ends with a sub-header and both
 // record tables.  A refusal leaves the table and the kernel as they were.
 extern "C" int rt_renderer_interiors(rt_renderer* r, const rt_interior* table, uint32_t n) {
-    if (!r) return rt_fail(RT_ERR_INVALID, "rt_renderer_interiors: null renderer");
-    if ((table == nullptr) != (n == 0u)) return rt_fail(RT_ERR_INVALID, "rt_renderer_interiors: a table and its count go together (NULL, 0 turns it off)");
-    uint32_t n_on = 0;
-    if (n) {
-        if (r->variant < 2) return rt_fail(RT_ERR_INVALID, "rt_renderer_interiors: the baseline kernel (variant 1) reads no interior table; use variant 0, 2 or 3");
-        if (r->variant == 5 || r->tol) return rt_fail(RT_ERR_INVALID, "rt_renderer_interiors: kernel variant %u reads no interior table", r->tol ? 6u : 5u);
-        if (r->scene.queue) return rt_fail(RT_ERR_INVALID, "rt_renderer_interiors: a world with a queue or wide4 traversal renders on lane walks that read no interior table (RT_TRAVERSAL_STACK and lists do)");
-        if (r->scene.dw.kind == RT_WORLD_NODE_TREE) return rt_fail(RT_ERR_INVALID, "rt_renderer_interiors: a bvh_node tree renders on a walk that reads no interior table (BVHs walked by the stack and lists do)");
-        if (r->nee.on() && r->nee.mode != RT_LIGHT_SAMPLING_ENV_TREE)
-            return rt_fail(RT_ERR_INVALID, "rt_renderer_interiors: light-sampling mode %u is on, which has no kernel that reads an interior table: solid glass renders with light sampling off or in mode 48", r->nee.mode);
-        if (n != r->scene.dw.n_mats) return rt_fail(RT_ERR_INVALID, "rt_renderer_interiors: %u records for a world of %u materials", n, r->scene.dw.n_mats);
-        for (uint32_t i = 0; i < n; i++) {
-            if (table[i].on == RT_INTERIOR_OFF) continue;
-            if (table[i].on != RT_INTERIOR_SOLID) return rt_fail(RT_ERR_INVALID, "rt_renderer_interiors: record %u: on is 0 (off) or 1 (solid), not %u", i, table[i].on);
-            if (r->scene.mat_types[i] != RT_MAT_DIELECTRIC) return rt_fail(RT_ERR_INVALID, "rt_renderer_interiors: record %u: an interior record belongs on a dielectric alone", i);
-            if (r->cut.on && r->cut.host[i].on != RT_CUTOUT_OFF) return rt_fail(RT_ERR_INVALID, "rt_renderer_interiors: record %u: the material has a cutout record, and a holed solid has no inside", i);
-            for (int c = 0; c < 3; c++)
-                if (!(std::isfinite(table[i].sigma[c]) && table[i].sigma[c] >= 0.0f)) return rt_fail(RT_ERR_INVALID, "rt_renderer_interiors: record %u: an absorption coefficient must be finite and >= 0", i);
-            n_on++;
-        }
-    }
+    if (const int rc = material_table_refusal(RUNG_INTR, r, table != nullptr, n, [] { return RT_OK; })) return rc;
     rt_renderer::Interiors next;
+    for (uint32_t i = 0; i < n; i++) {
+        if (table[i].on == RT_INTERIOR_OFF) continue;
+        if (table[i].on != RT_INTERIOR_SOLID) return rt_fail(RT_ERR_INVALID, "rt_renderer_interiors: record %u: on is 0 (off) or 1 (solid), not %u", i, table[i].on);
+        if (r->scene.mat_types[i] != RT_MAT_DIELECTRIC) return rt_fail(RT_ERR_INVALID, "rt_renderer_interiors: record %u: an interior record belongs on a dielectric alone", i);
+        if (r->cut.on && r->cut.host[i].on != RT_CUTOUT_OFF) return rt_fail(RT_ERR_INVALID, "rt_renderer_interiors: record %u: the material has a cutout record, and a holed solid has no inside", i);
+        for (int c = 0; c < 3; c++)
+            if (!(std::isfinite(table[i].sigma[c]) && table[i].sigma[c] >= 0.0f)) return rt_fail(RT_ERR_INVALID, "rt_renderer_interiors: record %u: an absorption coefficient must be finite and >= 0", i);
+        next.n_on++;
+    }
     if (n) {
-        next.on = true; next.n_on = n_on; next.host.assign(table, table + n);
-        for (rt_interior& m : next.host)   // what no kernel reads is zero, so that equal tables are equal bytes; -0 is 0
+        next.on = true; next.host.assign(table, table + n);
+        for (rt_interior& m : next.host)   // (-0 is 0)
             for (int c = 0; c < 3; c++) m.sigma[c] = m.on == RT_INTERIOR_OFF ? 0.0f : m.sigma[c] + 0.0f;
     }
-    if (n ? (r->in.on && r->in.host.size() == n && std::memcmp(r->in.host.data(), next.host.data(), (size_t)n * sizeof(rt_interior)) == 0) : !r->in.on) return RT_OK;   // nothing changes, the refinement goes on
-    if (const int rc = wait_last_call(r)) return rc;   // launches already enqueued read the images that are replaced below (sets the device)
-    if (n) {
-        if (const int rc = r->resolve_interior_kernel(false, r->stream_lds_bytes)) return rc;
-        if (r->nee.mode == RT_LIGHT_SAMPLING_ENV_TREE)
-            if (const int rc = r->resolve_interior_kernel(true, r->launch_on(RT_LIGHT_SAMPLING_ENV_TREE).lds_bytes)) return rc;
-    }
-    if (const int rc = r->replace_rider(r->in, next)) return rc;   // (a failure leaves table, images and refinement as they were)
-    r->refine_done = 0;   // samples that crossed the glass by another rule belong to another frame
-    r->aov_done = 0;
-    return RT_OK;
+    return install_table(r, RUNG_INTR, r->in, next);   // (samples that crossed the glass by another rule belong to another frame)
 }
 
-extern "C" int rt_renderer_interiors_info(rt_renderer* r, uint32_t out[2]) {
-    if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_interiors_info: null argument");
-    out[0] = r->in.on ? 1u : 0u;
-    out[1] = r->in.on ? r->in.n_on : 0u;
-    return RT_OK;
-}
+extern "C" int rt_renderer_interiors_info(rt_renderer* r, uint32_t out[2]) { return rider_info("rt_renderer_interiors_info", r, out, &rt_renderer::in); }
 
 // Alpha cutouts.  Off: every launch is what it was.  On: the CUT form of the renderer's kernel on images whose tail ends with a sub-header and
 // the record tables, the cutout records last.  A refusal leaves the table and the kernel as they were.  The entries the records name are checked at every
 // launch (enqueue_call), as a normal map's are: the tables come and go independently.
 extern "C" int rt_renderer_cutouts(rt_renderer* r, const rt_cutout* table, uint32_t n) {
-    if (!r) return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: null renderer");
-    if ((table == nullptr) != (n == 0u)) return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: a table and its count go together (NULL, 0 turns it off)");
-    uint32_t n_on = 0;
-    if (n) {
-        if (r->variant < 2) return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: the baseline kernel (variant 1) reads no cutout table; use variant 0, 2 or 3");
-        if (r->variant == 5 || r->tol) return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: kernel variant %u reads no cutout table", r->tol ? 6u : 5u);
-        if (r->scene.queue) return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: a world with a queue or wide4 traversal renders on lane walks that read no cutout table (RT_TRAVERSAL_STACK and lists do)");
-        if (r->scene.dw.kind == RT_WORLD_NODE_TREE) return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: a bvh_node tree renders on a walk that reads no cutout table (BVHs walked by the stack and lists do)");
-        if (r->nee.on() && r->nee.mode != RT_LIGHT_SAMPLING_ENV_TREE)
-            return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: light-sampling mode %u is on, which has no kernel that reads a cutout table: alpha cutouts render with light sampling off or in mode 48", r->nee.mode);
-        if (r->aov_on && r->aov_mode != RT_AOV_FULL)   // §35: mode 2 follows the table
-            return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: feature buffers are on, and the feature pass does not know the cutout rule: its first hits would be the solid cards, and a denoiser guided by them would be wrong without a sign");
-        if (!r->tex.on) return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: the renderer has no texture table to take a mask from: give it one with rt_renderer_textures first");
-        if (n != r->scene.dw.n_mats) return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: %u records for a world of %u materials", n, r->scene.dw.n_mats);
-        for (uint32_t i = 0; i < n; i++) {
-            if (table[i].on == RT_CUTOUT_OFF) continue;
-            if (table[i].on != RT_CUTOUT_MASKED) return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: record %u: on is 0 (off) or 1 (masked), not %u", i, table[i].on);
-            const uint32_t type = r->scene.mat_types[i];
-            if (type == RT_MAT_DIFFUSE_LIGHT || type == RT_MAT_ISOTROPIC)
-                return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: record %u: a light or a medium takes no cutout", i);
-            if (r->in.on && r->in.host[i].on != RT_INTERIOR_OFF) return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: record %u: the material has an interior record, and a holed solid has no inside", i);
-            if (table[i].image >= RT_MAX_IMAGES) return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: record %u: an image index lies in [0, %u)", i, RT_MAX_IMAGES);
-            if (!(std::isfinite(table[i].cutoff) && table[i].cutoff >= 0.0f && table[i].cutoff <= 1.0f)) return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: record %u: a cutoff must be finite and in [0, 1]", i);
-            n_on++;
-        }
-    }
+    if (const int rc = material_table_refusal(RUNG_CUT, r, table != nullptr, n, [&] {
+            if (r->aov_on && r->aov_mode != RT_AOV_FULL)   // §35: mode 2 follows the table
+                return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: feature buffers are on, and the feature pass does not know the cutout rule: its first hits would be the solid cards, and a denoiser guided by them would be wrong without a sign");
+            if (!r->tex.on) return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: the renderer has no texture table to take a mask from: give it one with rt_renderer_textures first");
+            return (int)RT_OK;
+        })) return rc;
     rt_renderer::Cutouts next;
+    for (uint32_t i = 0; i < n; i++) {
+        if (table[i].on == RT_CUTOUT_OFF) continue;
+        if (table[i].on != RT_CUTOUT_MASKED) return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: record %u: on is 0 (off) or 1 (masked), not %u", i, table[i].on);
+        const uint32_t type = r->scene.mat_types[i];
+        if (type == RT_MAT_DIFFUSE_LIGHT || type == RT_MAT_ISOTROPIC)
+            return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: record %u: a light or a medium takes no cutout", i);
+        if (r->in.on && r->in.host[i].on != RT_INTERIOR_OFF) return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: record %u: the material has an interior record, and a holed solid has no inside", i);
+        if (table[i].image >= RT_MAX_IMAGES) return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: record %u: an image index lies in [0, %u)", i, RT_MAX_IMAGES);
+        if (!(std::isfinite(table[i].cutoff) && table[i].cutoff >= 0.0f && table[i].cutoff <= 1.0f)) return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts: record %u: a cutoff must be finite and in [0, 1]", i);
+        next.n_on++;
+    }
     if (n) {
-        next.on = true; next.n_on = n_on; next.host.assign(table, table + n);
-        for (rt_cutout& m : next.host) {   // what no kernel reads is zero, so that equal tables are equal bytes; -0 is 0
+        next.on = true; next.host.assign(table, table + n);
+        for (rt_cutout& m : next.host) {   // (-0 is 0)
             m.reserved = 0u;
             if (m.on == RT_CUTOUT_OFF) m = rt_cutout{RT_CUTOUT_OFF, 0u, 0.0f, 0u}; else m.cutoff = m.cutoff + 0.0f;
         }
     }
-    if (n ? (r->cut.on && r->cut.host.size() == n && std::memcmp(r->cut.host.data(), next.host.data(), (size_t)n * sizeof(rt_cutout)) == 0) : !r->cut.on) return RT_OK;   // nothing changes, the refinement goes on
-    if (const int rc = wait_last_call(r)) return rc;   // launches already enqueued read the images that are replaced below (sets the device)
-    if (n) {
-        if (const int rc = r->resolve_cutout_kernel(false, r->stream_lds_bytes)) return rc;
-        if (r->nee.mode == RT_LIGHT_SAMPLING_ENV_TREE)
-            if (const int rc = r->resolve_cutout_kernel(true, r->launch_on(RT_LIGHT_SAMPLING_ENV_TREE).lds_bytes)) return rc;
-    }
-    if (const int rc = r->replace_rider(r->cut, next)) return rc;   // (a failure leaves table, images and refinement as they were)
-    r->refine_done = 0;   // samples that saw the cards whole belong to another frame
-    r->aov_done = 0;
-    return RT_OK;
+    return install_table(r, RUNG_CUT, r->cut, next);   // (samples that saw the cards whole belong to another frame)
 }
 
-extern "C" int rt_renderer_cutouts_info(rt_renderer* r, uint32_t out[2]) {
-    if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_cutouts_info: null argument");
-    out[0] = r->cut.on ? 1u : 0u;
-    out[1] = r->cut.on ? r->cut.n_on : 0u;
-    return RT_OK;
-}
+extern "C" int rt_renderer_cutouts_info(rt_renderer* r, uint32_t out[2]) { return rider_info("rt_renderer_cutouts_info", r, out, &rt_renderer::cut); }
 
-extern "C" int rt_renderer_textures_info(rt_renderer* r, uint32_t out[2]) {
-    if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_textures_info: null argument");
-    out[0] = r->tex.on ? 1u : 0u;
-    out[1] = r->tex.on ? (uint32_t)r->tex.records.size() : 0u;
-    return RT_OK;
-}
+extern "C" int rt_renderer_textures_info(rt_renderer* r, uint32_t out[2]) { return rider_info("rt_renderer_textures_info", r, out, &rt_renderer::tex); }
 
-extern "C" int rt_renderer_shading_normals_info(rt_renderer* r, uint32_t out[2]) {
-    if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_shading_normals_info: null argument");
-    out[0] = r->vn.on ? 1u : 0u;
-    out[1] = r->vn.on ? r->vn.n_smooth : 0u;
-    return RT_OK;
-}
+extern "C" int rt_renderer_shading_normals_info(rt_renderer* r, uint32_t out[2]) { return rider_info("rt_renderer_shading_normals_info", r, out, &rt_renderer::vn); }
 
 extern "C" int rt_renderer_refine_async(rt_renderer* r, void* hip_stream, float* d_out, uint32_t n_samples) {
     if (!r) return rt_fail(RT_ERR_INVALID, "rt_renderer_refine_async: null renderer");
@@ -1868,48 +1656,22 @@ extern "C" int rt_renderer_kernel_form(rt_renderer* r, uint32_t out[9]) {
     return RT_OK;
 }
 
-// Whether the NEXT launch runs an instantiation of the triangle family: a query of its own, so that rt_renderer_kernel_form's nine outputs stay what they are.
-extern "C" int rt_renderer_kernel_triangles(rt_renderer* r, uint32_t* out) {
-    if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_kernel_triangles: null argument");
-    *out = r->variant >= 2 && (r->launch_on(r->nee.mode).key & RT_KEY_TRI) ? 1u : 0u;
+// Whether the NEXT launch runs an instantiation whose key has `bit`: queries of their own, so that rt_renderer_kernel_form's nine outputs stay what they are.
+// (The baseline kernel has no key; no plain key has a family's bit.)
+static int kernel_has(const char* api, rt_renderer* r, uint32_t* out, uint32_t bit) {
+    if (!r || !out) return rt_fail(RT_ERR_INVALID, "%s: null argument", api);
+    *out = r->variant >= 2 && (r->launch_on(r->nee.mode).key & bit) ? 1u : 0u;
     return RT_OK;
 }
-
-// Whether the NEXT launch runs an instantiation of the environment-sampling family: a query of its own, for the same reason.
-extern "C" int rt_renderer_kernel_env_light(rt_renderer* r, uint32_t* out) {
-    if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_kernel_env_light: null argument");
-    *out = r->launch_on(r->nee.mode).key & RT_KEY_ENVL ? 1u : 0u;   // (no plain key has the bit)
-    return RT_OK;
-}
-extern "C" int rt_renderer_kernel_normal_map(rt_renderer* r, uint32_t* out) {
-    if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_kernel_normal_map: null argument");
-    *out = r->variant >= 2 && (r->launch_on(r->nee.mode).key & RT_KEY_NMAP) ? 1u : 0u;
-    return RT_OK;
-}
-extern "C" int rt_renderer_kernel_microfacet(rt_renderer* r, uint32_t* out) {
-    if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_kernel_microfacet: null argument");
-    *out = r->variant >= 2 && (r->launch_on(r->nee.mode).key & RT_KEY_MFAC) ? 1u : 0u;
-    return RT_OK;
-}
-// ... and of the solid-glass family, whose forms are microfacet forms too: both queries say 1 of them
-extern "C" int rt_renderer_kernel_interior(rt_renderer* r, uint32_t* out) {
-    if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_kernel_interior: null argument");
-    *out = r->variant >= 2 && (r->launch_on(r->nee.mode).key & RT_KEY_INTR) ? 1u : 0u;
-    return RT_OK;
-}
-// ... and of the cutout family, whose forms are solid-glass and microfacet forms too: all three queries say 1 of them
-extern "C" int rt_renderer_kernel_cutout(rt_renderer* r, uint32_t* out) {
-    if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_kernel_cutout: null argument");
-    *out = r->variant >= 2 && (r->launch_on(r->nee.mode).key & RT_KEY_CUT) ? 1u : 0u;
-    return RT_OK;
-}
-
-// Whether the NEXT launch runs an instantiation of the light-tree family: a query of its own, for the same reason.
-extern "C" int rt_renderer_kernel_light_tree(rt_renderer* r, uint32_t* out) {
-    if (!r || !out) return rt_fail(RT_ERR_INVALID, "rt_renderer_kernel_light_tree: null argument");
-    *out = r->launch_on(r->nee.mode).key & RT_KEY_LTREE ? 1u : 0u;   // (no plain key has the bit)
-    return RT_OK;
-}
+extern "C" int rt_renderer_kernel_triangles(rt_renderer* r, uint32_t* out) { return kernel_has("rt_renderer_kernel_triangles", r, out, RT_KEY_TRI); }         // §18
+extern "C" int rt_renderer_kernel_light_tree(rt_renderer* r, uint32_t* out) { return kernel_has("rt_renderer_kernel_light_tree", r, out, RT_KEY_LTREE); }     // §20
+extern "C" int rt_renderer_kernel_env_light(rt_renderer* r, uint32_t* out) { return kernel_has("rt_renderer_kernel_env_light", r, out, RT_KEY_ENVL); }        // §24
+// the rungs of FORM_LADDER: a form says 1 to its own query and to that of every bit its key carries (a cutout form is a solid-glass and a microfacet form too;
+// none of them carries RT_KEY_NMAP, though all read the normal-map table)
+extern "C" int rt_renderer_kernel_normal_map(rt_renderer* r, uint32_t* out) { return kernel_has("rt_renderer_kernel_normal_map", r, out, RT_KEY_NMAP); }     // §28
+extern "C" int rt_renderer_kernel_microfacet(rt_renderer* r, uint32_t* out) { return kernel_has("rt_renderer_kernel_microfacet", r, out, RT_KEY_MFAC); }      // §29
+extern "C" int rt_renderer_kernel_interior(rt_renderer* r, uint32_t* out) { return kernel_has("rt_renderer_kernel_interior", r, out, RT_KEY_INTR); }          // §32
+extern "C" int rt_renderer_kernel_cutout(rt_renderer* r, uint32_t* out) { return kernel_has("rt_renderer_kernel_cutout", r, out, RT_KEY_CUT); }               // §34
 
 extern "C" int rt_renderer_download(rt_renderer* r, float* host_rgba, size_t n_floats) {
     if (!r || !host_rgba) return rt_fail(RT_ERR_INVALID, "rt_renderer_download: null argument");

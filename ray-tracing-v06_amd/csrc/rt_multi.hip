@@ -250,116 +250,57 @@ extern "C" int rt_multi_renderer_refine(rt_multi_renderer* m, uint32_t n_samples
     return rc == RT_OK ? RT_OK : multi_fail_drain(m, rc);
 }
 
+// A setting goes to every part in turn, and the first refusal wins: every rank holds the same world on the same variant, so the first refuses what any would
+// (a mode or a table included), before any part changes.
+template <typename Call> static int on_every_part(const char* api, rt_multi_renderer* m, Call call) {
+    if (!m) return rt_fail(RT_ERR_INVALID, "%s: null renderer", api);
+    for (rt_renderer* r : m->parts)
+        if (const int rc = call(r)) return rc;
+    return RT_OK;
+}
+// A question about a table: every rank holds the same one, so rank 0 answers
+static int rank_0_answers(const char* api, rt_multi_renderer* m, uint32_t* out, int (*info)(rt_renderer*, uint32_t*)) {
+    if (!m || !out || m->parts.empty()) return rt_fail(RT_ERR_INVALID, "%s: null argument", api);
+    return info(m->parts[0], out);
+}
+
 extern "C" int rt_multi_renderer_set_camera(rt_multi_renderer* m, const rt_camera* cam) {
     if (!m || !cam) return rt_fail(RT_ERR_INVALID, "rt_multi_renderer_set_camera: null argument");
     if (const int rc = rt_camera_check("rt_multi_renderer_set_camera", cam)) return rc;   // refused before any part changes (and what a part refuses, the first does)
-    for (rt_renderer* r : m->parts) {
-        const int rc = rt_renderer_set_camera(r, cam);
-        if (rc != RT_OK) return rc;
-    }
-    return RT_OK;
+    return on_every_part("rt_multi_renderer_set_camera", m, [&](rt_renderer* r) { return rt_renderer_set_camera(r, cam); });
 }
-
 extern "C" int rt_multi_renderer_light_sampling_enable(rt_multi_renderer* m, uint32_t on) {
-    if (!m) return rt_fail(RT_ERR_INVALID, "rt_multi_renderer_light_sampling_enable: null renderer");
-    for (rt_renderer* r : m->parts) {   // every rank holds the same world on the same variant: the first refuses what any would (mode included), before any part changes
-        const int rc = rt_renderer_light_sampling_enable(r, on);
-        if (rc != RT_OK) return rc;
-    }
-    return RT_OK;
+    return on_every_part("rt_multi_renderer_light_sampling_enable", m, [&](rt_renderer* r) { return rt_renderer_light_sampling_enable(r, on); });
 }
-
 extern "C" int rt_multi_renderer_shading_normals(rt_multi_renderer* m, const rt_tri_normals* table, uint32_t n) {
-    if (!m) return rt_fail(RT_ERR_INVALID, "rt_multi_renderer_shading_normals: null renderer");
-    for (rt_renderer* r : m->parts) {   // every rank holds the same world on the same variant: the first refuses what any would, before any part changes
-        const int rc = rt_renderer_shading_normals(r, table, n);
-        if (rc != RT_OK) return rc;
-    }
-    return RT_OK;
+    return on_every_part("rt_multi_renderer_shading_normals", m, [&](rt_renderer* r) { return rt_renderer_shading_normals(r, table, n); });
 }
-
 extern "C" int rt_multi_renderer_texture_coords(rt_multi_renderer* m, const rt_tri_uvs* table, uint32_t n) {
-    if (!m) return rt_fail(RT_ERR_INVALID, "rt_multi_renderer_texture_coords: null renderer");
-    for (rt_renderer* r : m->parts) {   // every rank holds the same world on the same variant: the first refuses what any would, before any part changes
-        const int rc = rt_renderer_texture_coords(r, table, n);
-        if (rc != RT_OK) return rc;
-    }
-    return RT_OK;
+    return on_every_part("rt_multi_renderer_texture_coords", m, [&](rt_renderer* r) { return rt_renderer_texture_coords(r, table, n); });
 }
-
 extern "C" int rt_multi_renderer_environment(rt_multi_renderer* m, uint32_t width, uint32_t height, const float* rgb, float u0) {
-    if (!m) return rt_fail(RT_ERR_INVALID, "rt_multi_renderer_environment: null renderer");
-    for (rt_renderer* r : m->parts) {   // every rank holds the same world: the first refuses what any would, before any part changes
-        const int rc = rt_renderer_environment(r, width, height, rgb, u0);
-        if (rc != RT_OK) return rc;
-    }
-    return RT_OK;
+    return on_every_part("rt_multi_renderer_environment", m, [&](rt_renderer* r) { return rt_renderer_environment(r, width, height, rgb, u0); });
 }
-
 extern "C" int rt_multi_renderer_textures(rt_multi_renderer* m, const rt_texture* records, uint32_t n, const uint8_t* texels) {
-    if (!m) return rt_fail(RT_ERR_INVALID, "rt_multi_renderer_textures: null renderer");
-    for (rt_renderer* r : m->parts) {   // every rank holds the same world: the first refuses what any would, before any part changes
-        const int rc = rt_renderer_textures(r, records, n, texels);
-        if (rc != RT_OK) return rc;
-    }
-    return RT_OK;
+    return on_every_part("rt_multi_renderer_textures", m, [&](rt_renderer* r) { return rt_renderer_textures(r, records, n, texels); });
 }
-
-extern "C" int rt_multi_renderer_textures_info(rt_multi_renderer* m, uint32_t out[2]) {   // every rank holds the same table: rank 0 answers
-    if (!m || !out || m->parts.empty()) return rt_fail(RT_ERR_INVALID, "rt_multi_renderer_textures_info: null argument");
-    return rt_renderer_textures_info(m->parts[0], out);
-}
-
 extern "C" int rt_multi_renderer_normal_maps(rt_multi_renderer* m, const rt_normal_map* table, uint32_t n) {
-    if (!m) return rt_fail(RT_ERR_INVALID, "rt_multi_renderer_normal_maps: null renderer");
-    for (rt_renderer* r : m->parts) {   // every rank holds the same world: the first refuses what any would, before any part changes
-        const int rc = rt_renderer_normal_maps(r, table, n);
-        if (rc != RT_OK) return rc;
-    }
-    return RT_OK;
+    return on_every_part("rt_multi_renderer_normal_maps", m, [&](rt_renderer* r) { return rt_renderer_normal_maps(r, table, n); });
 }
-
-extern "C" int rt_multi_renderer_normal_maps_info(rt_multi_renderer* m, uint32_t out[2]) {   // every rank holds the same table: rank 0 answers
-    if (!m || !out || m->parts.empty()) return rt_fail(RT_ERR_INVALID, "rt_multi_renderer_normal_maps_info: null argument");
-    return rt_renderer_normal_maps_info(m->parts[0], out);
-}
-
 extern "C" int rt_multi_renderer_microfacets(rt_multi_renderer* m, const rt_microfacet* table, uint32_t n) {
-    if (!m) return rt_fail(RT_ERR_INVALID, "rt_multi_renderer_microfacets: null renderer");
-    for (rt_renderer* r : m->parts) {   // every rank holds the same world: the first refuses what any would, before any part changes
-        const int rc = rt_renderer_microfacets(r, table, n);
-        if (rc != RT_OK) return rc;
-    }
-    return RT_OK;
+    return on_every_part("rt_multi_renderer_microfacets", m, [&](rt_renderer* r) { return rt_renderer_microfacets(r, table, n); });
 }
-
-extern "C" int rt_multi_renderer_microfacets_info(rt_multi_renderer* m, uint32_t out[2]) {   // every rank holds the same table: rank 0 answers
-    if (!m || !out || m->parts.empty()) return rt_fail(RT_ERR_INVALID, "rt_multi_renderer_microfacets_info: null argument");
-    return rt_renderer_microfacets_info(m->parts[0], out);
-}
-
 extern "C" int rt_multi_renderer_interiors(rt_multi_renderer* m, const rt_interior* table, uint32_t n) {
-    if (!m) return rt_fail(RT_ERR_INVALID, "rt_multi_renderer_interiors: null renderer");
-    for (rt_renderer* r : m->parts) {   // every rank holds the same world: the first refuses what any would, before any part changes
-        const int rc = rt_renderer_interiors(r, table, n);
-        if (rc != RT_OK) return rc;
-    }
-    return RT_OK;
+    return on_every_part("rt_multi_renderer_interiors", m, [&](rt_renderer* r) { return rt_renderer_interiors(r, table, n); });
 }
-
 extern "C" int rt_multi_renderer_cutouts(rt_multi_renderer* m, const rt_cutout* table, uint32_t n) {
-    if (!m) return rt_fail(RT_ERR_INVALID, "rt_multi_renderer_cutouts: null renderer");
-    for (rt_renderer* r : m->parts) {   // every rank holds the same world: the first refuses what any would, before any part changes
-        const int rc = rt_renderer_cutouts(r, table, n);
-        if (rc != RT_OK) return rc;
-    }
-    return RT_OK;
+    return on_every_part("rt_multi_renderer_cutouts", m, [&](rt_renderer* r) { return rt_renderer_cutouts(r, table, n); });
 }
 
-extern "C" int rt_multi_renderer_cutouts_info(rt_multi_renderer* m, uint32_t out[2]) {
-    if (!m || !out) return rt_fail(RT_ERR_INVALID, "rt_multi_renderer_cutouts_info: null argument");
-    return rt_renderer_cutouts_info(m->parts[0], out);
-}
+extern "C" int rt_multi_renderer_textures_info(rt_multi_renderer* m, uint32_t out[2]) { return rank_0_answers("rt_multi_renderer_textures_info", m, out, rt_renderer_textures_info); }
+extern "C" int rt_multi_renderer_normal_maps_info(rt_multi_renderer* m, uint32_t out[2]) { return rank_0_answers("rt_multi_renderer_normal_maps_info", m, out, rt_renderer_normal_maps_info); }
+extern "C" int rt_multi_renderer_microfacets_info(rt_multi_renderer* m, uint32_t out[2]) { return rank_0_answers("rt_multi_renderer_microfacets_info", m, out, rt_renderer_microfacets_info); }
+extern "C" int rt_multi_renderer_cutouts_info(rt_multi_renderer* m, uint32_t out[2]) { return rank_0_answers("rt_multi_renderer_cutouts_info", m, out, rt_renderer_cutouts_info); }
 
 extern "C" int rt_multi_renderer_download(rt_multi_renderer* m, float* host_rgba, size_t n_floats) {
     if (!m || !host_rgba) return rt_fail(RT_ERR_INVALID, "rt_multi_renderer_download: null argument");

@@ -22,7 +22,7 @@ SEED = EW.SEED
 W, H, SPP, DEPTH = 24, 16, 8, 8
 ENV_TREE = 48
 BACKGROUND = IW.BACKGROUND
-FORMS = dict(IW.FORMS)   # one key per RT_KERNEL_CUTOUT(...) line of csrc/rt_device.hip and, once more, per RT_KERNEL_CUTOUT_ENV_TREE(...) line: §32's shapes
+FORMS = dict(IW.FORMS)   # one key per form of the CUTOUT family of csrc/rt_device.hip's kernel table and, once more, of its CUTOUT_ENV_TREE family: §32's shapes
 EYE = (0.0, 2.0, 8.0)
 RECORDS = 3
 

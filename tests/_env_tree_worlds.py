@@ -20,8 +20,8 @@ SEED = EW.SEED
 W, H, SPP, DEPTH = EW.W, EW.H, EW.SPP, EW.DEPTH   # 24 x 16 at 8 spp and depth 6
 ENV_TREE = 48                                     # RT_LIGHT_SAMPLING_ENV_TREE
 
-# The suite's statement of which LTREE && ENVL instantiations of render_kernel_stream exist: one (world, exact, ext, big, wide) key per RT_KERNEL_ENV_TREE(...)
-# line of csrc/rt_device.hip, each with _tri_worlds' recipe (kernel variant, environment) that makes a renderer of a background-2 world resolve to it.
+# The suite's statement of which LTREE && ENVL instantiations of render_kernel_stream exist: one (world, exact, ext, big, wide) key per form of the ENV_TREE family
+# of csrc/rt_device.hip, each with _tri_worlds' recipe (kernel variant, environment) that makes a renderer of a background-2 world resolve to it.
 # tests/test_env_tree_cpu.py holds the list against the source; tests/test_gpu_env_tree.py renders every key and compares it with the twin.
 FORMS = {f: TW.FORMS[f] for f in [(TW.BVH, 0, 2, 0, 0), (TW.BVH, 1, 2, 0, 0), (TW.BVH, 0, 2, 1, 0), (TW.BVH, 1, 2, 1, 0), (TW.BVH, 0, 2, 1, 1), (TW.BVH, 1, 2, 1, 1),
                                   (TW.LIST, 1, 2, 0, 0), (TW.LIST, 1, 2, 1, 1)]}

@@ -91,7 +91,7 @@ SEED = EW.SEED
 W, H, SPP, DEPTH = 24, 16, 8, 8   # a path needs to enter, leave and land
 ENV_TREE = 48
 BACKGROUND = MW.BACKGROUND
-FORMS = dict(MW.FORMS)   # one key per RT_KERNEL_INTERIOR(...) line of csrc/rt_device.hip and, once more, per RT_KERNEL_INTERIOR_ENV_TREE(...) line: §29's shapes
+FORMS = dict(MW.FORMS)   # one key per form of the INTERIOR family of csrc/rt_device.hip's kernel table and, once more, of its INTERIOR_ENV_TREE family: §29's shapes
 OUTSIDE, INSIDE = "outside", "inside"
 BOX = ((6.4, 0.2, 4.4), (8.2, 2.2, 6.2))
 TINT = dict(smooth=((0.9, 0.6, 0.3), 1.0), box=((0.3, 0.8, 0.5), 1.0), ball=((0.8, 0.4, 0.9), 0.8), frosted=((0.95, 0.7, 0.7), 1.0))

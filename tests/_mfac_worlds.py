@@ -102,8 +102,8 @@ W, H, SPP, DEPTH = NW.W, NW.H, NW.SPP, NW.DEPTH   # §28's: 24 x 16 at 8 spp and
 ENV_TREE = 48
 BACKGROUND = NW.BACKGROUND
 
-# The suite's statement of which MFAC instantiations of render_kernel_stream exist: one (world, exact, ext, big, wide) key per RT_KERNEL_MICROFACET(...) line of
-# csrc/rt_device.hip and, the same eight once more, per RT_KERNEL_MICROFACET_ENV_TREE(...) line: the shapes of §28's family, each with _tri_worlds' recipe.
+# The suite's statement of which MFAC instantiations of render_kernel_stream exist: one (world, exact, ext, big, wide) key per form of the MICROFACET family of
+# csrc/rt_device.hip and, the same eight once more, of the MICROFACET_ENV_TREE family: the shapes of §28's family, each with _tri_worlds' recipe.
 # tests/test_microfacets_cpu.py holds the list against the source; tests/test_gpu_microfacets.py renders every key, plain and in mode 48, against the twin.
 FORMS = dict(NW.FORMS)
 

@@ -1,7 +1,7 @@
 """The worlds of the light-sampling tests and the matrix of kernel forms they must reach — test infrastructure only.
 
 FORMS is the suite's statement of which light-sampling instantiations of render_kernel_stream exist: one (world, exact, ext, big, wide) tuple per
-RT_KERNEL_NEE(...) line of csrc/rt_device.hip, each with the recipe — world kind, kernel variant, environment — that makes a renderer resolve to it.
+form of the NEE family of csrc/rt_device.hip's kernel table, each with the recipe — world kind, kernel variant, environment — that makes a renderer resolve to it.
 tests/test_light_sampling_cpu.py holds the set against the source and every world against the conditions it is there for (run(name).stats), without
 a GPU; tests/test_gpu_light_sampling.py renders each form and compares it with the twin's run of its world (tests/_nee_twin.py).
 

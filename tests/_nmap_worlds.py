@@ -108,8 +108,8 @@ W, H, SPP, DEPTH = EW.W, EW.H, EW.SPP, EW.DEPTH   # 24 x 16 at 8 spp and depth 6
 ENV_TREE = 48
 BACKGROUND = (0.55, 0.65, 0.85)
 
-# The suite's statement of which NMAP instantiations of render_kernel_stream exist: one (world, exact, ext, big, wide) key per RT_KERNEL_NORMAL_MAP(...) line of
-# csrc/rt_device.hip and, the same eight once more, per RT_KERNEL_NORMAL_MAP_ENV_TREE(...) line, each with _tri_worlds' recipe (kernel variant, environment) that
+# The suite's statement of which NMAP instantiations of render_kernel_stream exist: one (world, exact, ext, big, wide) key per form of the NORMAL_MAP family of
+# csrc/rt_device.hip and, the same eight once more, of the NORMAL_MAP_ENV_TREE family, each with _tri_worlds' recipe (kernel variant, environment) that
 # makes a renderer with a normal-map table resolve to it.  tests/test_normal_maps_cpu.py holds the list against the source; tests/test_gpu_normal_maps.py renders
 # every key, plain and in mode 48, and compares it with the twin.
 FORMS = {f: TW.FORMS[f] for f in [(TW.BVH, 0, 2, 0, 0), (TW.BVH, 1, 2, 0, 0), (TW.BVH, 0, 2, 1, 0), (TW.BVH, 1, 2, 1, 0), (TW.BVH, 0, 2, 1, 1), (TW.BVH, 1, 2, 1, 1),

@@ -30,8 +30,8 @@ BVH, LIST = "RT_WORLD_BVH", "RT_WORLD_LIST"
 WORLD_ID = {BVH: 0, LIST: 1}   # RT_WORLD_BVH, RT_WORLD_LIST of include/rt06.h
 LDS, NARROW, WIDE = {}, {"RT06_FORCE_BIG": "1"}, {"RT06_FORCE_BIG": "1", "RT06_FORCE_WIDE": "1"}
 
-# The suite's statement of which TRI instantiations of render_kernel_stream exist: one (world, exact, ext, big, wide) key per RT_KERNEL_TRI(...) line of
-# csrc/rt_device.hip — and, the same sixteen keys once more, per RT_KERNEL_TRI_NEE(...) line —, each with the recipe (kernel variant, environment) that makes a
+# The suite's statement of which TRI instantiations of render_kernel_stream exist: one (world, exact, ext, big, wide) key per form of the TRI family of
+# csrc/rt_device.hip — and, the same sixteen keys once more, per form of its TRI_NEE family —, each with the recipe (kernel variant, environment) that makes a
 # renderer of a triangle room resolve to it; ext 2 takes the textured room, a list the room left a HittableList.  tests/test_triangles_cpu.py holds the table against
 # the source, tests/test_gpu_triangles.py renders every key plain and with light sampling and compares it with the twin.
 FORMS = {

@@ -14,6 +14,7 @@ import _env_light_worlds as LW
 import _env_twin as ET
 import _env_worlds as EW
 import _tri_worlds as TW
+import _kernel_table as KT
 from _common import ROOT, as_oracle_camera, as_oracle_world, bits_equal, mismatch_report, pkg
 from _nee_twin import luminance
 
@@ -194,17 +195,13 @@ def test_the_gpu_worlds_exercise_what_they_are_there_for():
 
 # ---- forms ----------------------------------------------------------------------------------------------------------------------------------------------------
 def test_form_list_is_the_set_of_environment_sampling_instantiations():
-    """every RT_KERNEL_ENV_LIGHT(exact, world, ext, big, wide) of stream_kernel_for() has a recipe in the list the GPU tests run, and nothing else has"""
-    src = open(os.path.join(ROOT, "ray-tracing-v06_amd", "csrc", "rt_device.hip")).read()
-    table = src[src.index("switch (key)"):]
-    entries = re.findall(r"RT_KERNEL_ENV_LIGHT\(\s*(true|false)\s*,\s*(RT_WORLD_\w+)\s*,\s*(\d)\s*,\s*(true|false)\s*,\s*(true|false)\s*\)", table)
-    assert len(entries) == table.count("RT_KERNEL_ENV_LIGHT(") == 8   # every use is one the pattern reads; the #define above the switch is not a use
-    shipped = {(world, int(exact == "true"), int(ext), int(big == "true"), int(wide == "true")) for exact, world, ext, big, wide in entries}
-    assert len(shipped) == len(entries)
+    """every form of stream_kernel_for()'s ENV_LIGHT family has a recipe in the list the GPU tests run, and nothing else has"""
+    shipped = KT.family("ENV_LIGHT")
+    assert len(shipped) == KT.count("ENV_LIGHT") == 8   # (the reader raises on a line of the table it cannot read)
     assert shipped == set(LW.FORMS), shipped ^ set(LW.FORMS)
     assert all(f[2] == 2 for f in shipped) and all(LW.FORMS[f] == TW.FORMS[f] for f in LW.FORMS)
-    for macro in ("RT_KERNEL_NEE(", "RT_KERNEL_TRI(", "RT_KERNEL_TRI_NEE(", "RT_KERNEL_LIGHT_TREE("):
-        assert table.count(macro) == 16   # nothing existing moved
+    for family in ("NEE", "TRI", "TRI_NEE", "LIGHT_TREE"):
+        assert KT.count(family) == 16   # nothing existing moved
 
 
 # ---- plumbing ---------------------------------------------------------------------------------------------------------------------------------------------------

@@ -15,6 +15,7 @@ import _env_tree_worlds as VW
 import _env_twin as ET
 import _env_worlds as EW
 import _tri_worlds as TW
+import _kernel_table as KT
 from _common import ROOT, as_oracle_camera, as_oracle_world, bits_equal, pkg
 from _nee2_twin import world_arrays
 from _nee_twin import _Tape, dot, luminance
@@ -214,17 +215,13 @@ def test_the_gpu_worlds_exercise_what_they_are_there_for():
 
 # ---- forms ---------------------------------------------------------------------------------------------------------------------------------------------------
 def test_form_list_is_the_set_of_instantiations_and_the_older_counts_stand():
-    """every RT_KERNEL_ENV_TREE(exact, world, ext, big, wide) of stream_kernel_for() has a recipe in the list the GPU tests run, and nothing else has"""
-    src = open(os.path.join(ROOT, "ray-tracing-v06_amd", "csrc", "rt_device.hip")).read()
-    table = src[src.index("switch (key)"):]
-    entries = re.findall(r"RT_KERNEL_ENV_TREE\(\s*(true|false)\s*,\s*(RT_WORLD_\w+)\s*,\s*(\d)\s*,\s*(true|false)\s*,\s*(true|false)\s*\)", table)
-    assert len(entries) == table.count("RT_KERNEL_ENV_TREE(") == 8   # every use is one the pattern reads; the #define above the switch is not a use
-    shipped = {(world, int(exact == "true"), int(ext), int(big == "true"), int(wide == "true")) for exact, world, ext, big, wide in entries}
-    assert len(shipped) == len(entries)
+    """every form of stream_kernel_for()'s ENV_TREE family has a recipe in the list the GPU tests run, and nothing else has"""
+    shipped = KT.family("ENV_TREE")
+    assert len(shipped) == KT.count("ENV_TREE") == 8   # (the reader raises on a line of the table it cannot read)
     assert shipped == set(VW.FORMS) == set(LW.FORMS), shipped ^ set(VW.FORMS)
     assert all(f[2] == 2 for f in shipped) and all(VW.FORMS[f] == TW.FORMS[f] for f in VW.FORMS)
-    for macro, count in (("RT_KERNEL_NEE(", 16), ("RT_KERNEL_TRI(", 16), ("RT_KERNEL_TRI_NEE(", 16), ("RT_KERNEL_LIGHT_TREE(", 16), ("RT_KERNEL_ENV_LIGHT(", 8)):
-        assert table.count(macro) == count, macro   # nothing existing moved
+    for family, count in (("NEE", 16), ("TRI", 16), ("TRI_NEE", 16), ("LIGHT_TREE", 16), ("ENV_LIGHT", 8)):
+        assert KT.count(family) == count, family   # nothing existing moved
 
 
 # ---- plumbing ------------------------------------------------------------------------------------------------------------------------------------------------

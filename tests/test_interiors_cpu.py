@@ -12,6 +12,7 @@ import _interior_twin as IT
 import _interior_worlds as IW
 import _mfac_worlds as MW
 import _path_twin as PT
+import _kernel_table as KT
 from _common import ROOT, bits_equal, mismatch_report, pkg
 
 F = np.float32
@@ -248,20 +249,15 @@ def test_scene_calls_refusals_and_builders(p):
 
 
 def test_form_list_is_the_set_of_instantiations_and_the_older_counts_stand():
-    """every RT_KERNEL_INTERIOR(...) and RT_KERNEL_INTERIOR_ENV_TREE(...) of stream_kernel_for() has a recipe in the list the GPU tests run, and nothing else has"""
+    """every form of stream_kernel_for()'s INTERIOR and INTERIOR_ENV_TREE families has a recipe in the list the GPU tests run, and nothing else has"""
     import _tri_worlds as TW
-    src = open(os.path.join(ROOT, "ray-tracing-v06_amd", "csrc", "rt_device.hip")).read()
-    table = src[src.index("switch (key)"):]
-    for macro in ("RT_KERNEL_INTERIOR", "RT_KERNEL_INTERIOR_ENV_TREE"):
-        entries = re.findall(macro + r"\(\s*(true|false)\s*,\s*(RT_WORLD_\w+)\s*,\s*(\d)\s*,\s*(true|false)\s*,\s*(true|false)\s*\)", table)
-        assert len(entries) == table.count(macro + "(") == 8
-        shipped = {(world, int(exact == "true"), int(ext), int(big == "true"), int(wide == "true")) for exact, world, ext, big, wide in entries}
-        assert len(shipped) == 8 and shipped == set(IW.FORMS) == set(MW.FORMS), shipped ^ set(IW.FORMS)
+    for family in ("INTERIOR", "INTERIOR_ENV_TREE"):
+        shipped = KT.family(family)
+        assert len(shipped) == KT.count(family) == 8 and shipped == set(IW.FORMS) == set(MW.FORMS), shipped ^ set(IW.FORMS)
     assert all(IW.FORMS[f] == TW.FORMS[f] for f in IW.FORMS)
-    for macro, count in (("RT_KERNEL_NEE(", 16), ("RT_KERNEL_TRI(", 16), ("RT_KERNEL_TRI_NEE(", 16), ("RT_KERNEL_LIGHT_TREE(", 16), ("RT_KERNEL_ENV_LIGHT(", 8),
-                         ("RT_KERNEL_ENV_TREE(", 8), ("RT_KERNEL_NORMAL_MAP(", 8), ("RT_KERNEL_NORMAL_MAP_ENV_TREE(", 8), ("RT_KERNEL_MICROFACET(", 8),
-                         ("RT_KERNEL_MICROFACET_ENV_TREE(", 8)):
-        assert table.count(macro) == count, macro   # nothing existing moved
+    for family, count in (("NEE", 16), ("TRI", 16), ("TRI_NEE", 16), ("LIGHT_TREE", 16), ("ENV_LIGHT", 8), ("ENV_TREE", 8), ("NORMAL_MAP", 8), ("NORMAL_MAP_ENV_TREE", 8),
+                          ("MICROFACET", 8), ("MICROFACET_ENV_TREE", 8)):
+        assert KT.count(family) == count, family   # nothing existing moved
     kernel = open(os.path.join(ROOT, "ray-tracing-v06_amd", "csrc", "rt_stream_kernel.hpp")).read()
     assert "static_assert(!INTR || MFAC" in kernel and "bool INTR = false, bool MFAC = false, bool NMAP = false>" in kernel
     shade = kernel[kernel.index("if (cur == K::SHADE)"):]

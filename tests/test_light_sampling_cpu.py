@@ -16,6 +16,7 @@ import pytest
 import _nee_twin as T
 import _nee_worlds as NW
 import _oracle as O
+import _kernel_table as KT
 from _common import ROOT, as_oracle_world, bits_equal, mismatch_report, pkg
 
 SEED = 1984
@@ -122,13 +123,9 @@ def test_symbols_are_declared_exported_bound_and_mirrored():
 
 
 def test_form_matrix_is_the_set_of_light_sampling_instantiations():
-    """every RT_KERNEL_NEE(exact, world, ext, big, wide) of stream_kernel_for() has a recipe in the matrix the GPU tests run, and nothing else has"""
-    src = open(os.path.join(ROOT, "ray-tracing-v06_amd", "csrc", "rt_device.hip")).read()
-    table = src[src.index("switch (key)"):]
-    entries = re.findall(r"RT_KERNEL_NEE\(\s*(true|false)\s*,\s*(RT_WORLD_\w+)\s*,\s*(\d)\s*,\s*(true|false)\s*,\s*(true|false)\s*\)", table)
-    assert len(entries) == table.count("RT_KERNEL_NEE(") == 16   # every use is one the pattern reads; the #define above the switch is not a use
-    shipped = {(world, int(exact == "true"), int(ext), int(big == "true"), int(wide == "true")) for exact, world, ext, big, wide in entries}
-    assert len(shipped) == len(entries)
+    """every form of stream_kernel_for()'s NEE family has a recipe in the matrix the GPU tests run, and nothing else has"""
+    shipped = KT.family("NEE")
+    assert len(shipped) == KT.count("NEE") == 16   # (the reader raises on a line of the table it cannot read)
     assert shipped == set(NW.FORMS), shipped ^ set(NW.FORMS)
     assert len({NW.form_id(f) for f in NW.FORMS}) == len(NW.FORMS)
     assert all(name in NW.MATRIX_WORLDS for name, _, _ in NW.FORMS.values())

@@ -15,6 +15,7 @@ import _light_tree_twin as LT
 import _light_tree_worlds as LW
 import _mesh_light_twin as MT
 import _tri_worlds as TW
+import _kernel_table as KT
 from _common import ROOT, as_oracle_camera, as_oracle_world, bits_equal, mismatch_report, pkg
 
 F = np.float32
@@ -129,13 +130,9 @@ def test_refusals():
 
 
 def test_the_kernel_table_has_sixteen_light_tree_forms_with_the_triangle_familys_keys():
-    src = open(os.path.join(ROOT, "ray-tracing-v06_amd", "csrc", "rt_device.hip")).read()
-    table = src[src.index("switch (key)"):]
-    assert table.count("RT_KERNEL_LIGHT_TREE(") == 16
-    assert table.count("RT_KERNEL_NEE(") == 16 and table.count("RT_KERNEL_TRI(") == 16 and table.count("RT_KERNEL_TRI_NEE(") == 16
-    keys = set()
-    for exact, world, ext, big, wide in re.findall(r"RT_KERNEL_LIGHT_TREE\((true|false), (RT_WORLD_\w+), (\d), (true|false), (true|false)\)", table):
-        keys.add((world, int(exact == "true"), int(ext), int(big == "true"), int(wide == "true")))
+    assert KT.count("LIGHT_TREE") == 16
+    assert KT.count("NEE") == 16 and KT.count("TRI") == 16 and KT.count("TRI_NEE") == 16
+    keys = KT.family("LIGHT_TREE")
     assert keys == set(TW.FORMS) and len(keys) == 16
 
 

@@ -15,6 +15,7 @@ import _mesh_light_worlds as MW
 import _nee2_worlds as NW2
 import _tri_twin as TT
 import _tri_worlds as TW
+import _kernel_table as KT
 from _common import ROOT, as_oracle_camera, as_oracle_world, bits_equal, mismatch_report, pkg
 
 F = np.float32
@@ -131,9 +132,7 @@ def test_sixty_four_lights_are_accepted_and_refusals():
 
 
 def test_stream_kernel_table_gains_no_instantiation():
-    src = open(os.path.join(ROOT, "ray-tracing-v06_amd", "csrc", "rt_device.hip")).read()
-    table = src[src.index("switch (key)"):]
-    assert table.count("RT_KERNEL_NEE(") == 16 and table.count("RT_KERNEL_TRI_NEE(") == 16
+    assert KT.count("NEE") == 16 and KT.count("TRI_NEE") == 16
 
 
 # ---- pins -------------------------------------------------------------------------------------------------------------------------------------------

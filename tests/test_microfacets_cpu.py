@@ -13,6 +13,7 @@ import pytest
 import _mfac_twin as MT
 import _mfac_worlds as MW
 import _nmap_worlds as NW
+import _kernel_table as KT
 from _common import ROOT, bits_equal, mismatch_report, pkg
 
 F = np.float32
@@ -146,19 +147,14 @@ def test_the_room_takes_every_way_out_and_follows_every_sample():
 
 # ---- 4. the kernel forms and the launch image -----------------------------------------------------------------------------------------------------------------------
 def test_form_list_is_the_set_of_instantiations_and_the_older_counts_stand():
-    """every RT_KERNEL_MICROFACET(...) and RT_KERNEL_MICROFACET_ENV_TREE(...) of stream_kernel_for() has a recipe in the list the GPU tests run, and nothing else has"""
+    """every form of stream_kernel_for()'s MICROFACET and MICROFACET_ENV_TREE families has a recipe in the list the GPU tests run, and nothing else has"""
     import _tri_worlds as TW
-    src = open(os.path.join(ROOT, "ray-tracing-v06_amd", "csrc", "rt_device.hip")).read()
-    table = src[src.index("switch (key)"):]
-    for macro in ("RT_KERNEL_MICROFACET", "RT_KERNEL_MICROFACET_ENV_TREE"):
-        entries = re.findall(macro + r"\(\s*(true|false)\s*,\s*(RT_WORLD_\w+)\s*,\s*(\d)\s*,\s*(true|false)\s*,\s*(true|false)\s*\)", table)
-        assert len(entries) == table.count(macro + "(") == 8
-        shipped = {(world, int(exact == "true"), int(ext), int(big == "true"), int(wide == "true")) for exact, world, ext, big, wide in entries}
-        assert len(shipped) == 8 and shipped == set(MW.FORMS) == set(NW.FORMS), shipped ^ set(MW.FORMS)
+    for family in ("MICROFACET", "MICROFACET_ENV_TREE"):
+        shipped = KT.family(family)
+        assert len(shipped) == KT.count(family) == 8 and shipped == set(MW.FORMS) == set(NW.FORMS), shipped ^ set(MW.FORMS)
     assert all(MW.FORMS[f] == TW.FORMS[f] for f in MW.FORMS)
-    for macro, count in (("RT_KERNEL_NEE(", 16), ("RT_KERNEL_TRI(", 16), ("RT_KERNEL_TRI_NEE(", 16), ("RT_KERNEL_LIGHT_TREE(", 16), ("RT_KERNEL_ENV_LIGHT(", 8),
-                         ("RT_KERNEL_ENV_TREE(", 8), ("RT_KERNEL_NORMAL_MAP(", 8), ("RT_KERNEL_NORMAL_MAP_ENV_TREE(", 8)):
-        assert table.count(macro) == count, macro   # nothing existing moved
+    for family, count in (("NEE", 16), ("TRI", 16), ("TRI_NEE", 16), ("LIGHT_TREE", 16), ("ENV_LIGHT", 8), ("ENV_TREE", 8), ("NORMAL_MAP", 8), ("NORMAL_MAP_ENV_TREE", 8)):
+        assert KT.count(family) == count, family   # nothing existing moved
     kernel = open(os.path.join(ROOT, "ray-tracing-v06_amd", "csrc", "rt_stream_kernel.hpp")).read()
     assert "static_assert(!MFAC || NMAP" in kernel and "bool MFAC = false, bool NMAP = false>" in kernel
 

@@ -9,6 +9,7 @@ import pytest
 import _nmap_twin as NT
 import _nmap_worlds as NW
 import _tex_worlds as XW
+import _kernel_table as KT
 from _common import ROOT, bits_equal, mismatch_report, pkg
 
 F = np.float32
@@ -271,22 +272,16 @@ def test_both_languages_mirror_the_surface(p):
 
 # ---- 5. the kernel forms and the launch image -----------------------------------------------------------------------------------------------------------------------
 def test_form_list_is_the_set_of_instantiations_and_the_older_counts_stand():
-    """every RT_KERNEL_NORMAL_MAP(...) and RT_KERNEL_NORMAL_MAP_ENV_TREE(...) of stream_kernel_for() has a recipe in the list the GPU tests run, and nothing else has"""
-    import re
-
+    """every form of stream_kernel_for()'s NORMAL_MAP and NORMAL_MAP_ENV_TREE families has a recipe in the list the GPU tests run, and nothing else has"""
     import _env_tree_worlds as VW
     import _tri_worlds as TW
-    src = open(os.path.join(ROOT, "ray-tracing-v06_amd", "csrc", "rt_device.hip")).read()
-    table = src[src.index("switch (key)"):]
-    for macro in ("RT_KERNEL_NORMAL_MAP", "RT_KERNEL_NORMAL_MAP_ENV_TREE"):
-        entries = re.findall(macro + r"\(\s*(true|false)\s*,\s*(RT_WORLD_\w+)\s*,\s*(\d)\s*,\s*(true|false)\s*,\s*(true|false)\s*\)", table)
-        assert len(entries) == table.count(macro + "(") == 8   # every use is one the pattern reads; the #define above the switch is not a use
-        shipped = {(world, int(exact == "true"), int(ext), int(big == "true"), int(wide == "true")) for exact, world, ext, big, wide in entries}
-        assert len(shipped) == 8 and shipped == set(NW.FORMS) == set(VW.FORMS), shipped ^ set(NW.FORMS)
+    for family in ("NORMAL_MAP", "NORMAL_MAP_ENV_TREE"):
+        shipped = KT.family(family)
+        assert len(shipped) == KT.count(family) == 8   # (the reader raises on a line of the table it cannot read)
+        assert shipped == set(NW.FORMS) == set(VW.FORMS), shipped ^ set(NW.FORMS)
     assert all(f[2] == 2 for f in NW.FORMS) and all(NW.FORMS[f] == TW.FORMS[f] for f in NW.FORMS)
-    for macro, count in (("RT_KERNEL_NEE(", 16), ("RT_KERNEL_TRI(", 16), ("RT_KERNEL_TRI_NEE(", 16), ("RT_KERNEL_LIGHT_TREE(", 16), ("RT_KERNEL_ENV_LIGHT(", 8),
-                         ("RT_KERNEL_ENV_TREE(", 8)):
-        assert table.count(macro) == count, macro   # nothing existing moved
+    for family, count in (("NEE", 16), ("TRI", 16), ("TRI_NEE", 16), ("LIGHT_TREE", 16), ("ENV_LIGHT", 8), ("ENV_TREE", 8)):
+        assert KT.count(family) == count, family   # nothing existing moved
     kernel = open(os.path.join(ROOT, "ray-tracing-v06_amd", "csrc", "rt_stream_kernel.hpp")).read()
     assert "static_assert(!NMAP || (EXT == 2 && TRI)" in kernel and "bool NMAP = false>" in kernel
 

@@ -10,6 +10,7 @@ import pytest
 import _tri_worlds as TW
 import _uv_twin as UT
 import _uv_worlds as UW
+import _kernel_table as KT
 from _common import ROOT, as_oracle_world, bits_equal, mismatch_report, pkg
 
 F = np.float32
@@ -379,10 +380,8 @@ def test_symbols_and_mirrors(p):
 def test_stream_kernel_table_gains_no_instantiation():
     """the kernel forms held against rt_device.hip without a GPU are what they were: texture coordinates ride on a wave-uniform header, not on a
     template argument"""
-    src = open(os.path.join(ROOT, "ray-tracing-v06_amd", "csrc", "rt_device.hip")).read()
-    table = src[src.index("switch (key)"):]
-    for macro, n in (("RT_KERNEL_NEE(", 16), ("RT_KERNEL_TRI(", 16), ("RT_KERNEL_TRI_NEE(", 16), ("RT_KERNEL_LIGHT_TREE(", 16)):
-        assert table.count(macro) == n, macro
+    for family, n in (("NEE", 16), ("TRI", 16), ("TRI_NEE", 16), ("LIGHT_TREE", 16)):
+        assert KT.count(family) == n, family
     kernel = open(os.path.join(ROOT, "ray-tracing-v06_amd", "csrc", "rt_stream_kernel.hpp")).read()
     head = kernel[kernel.index("template <"):kernel.index("render_kernel_stream(")]
     assert "UV" not in head.rsplit("template <", 1)[1]

@@ -14,6 +14,7 @@ import _nee_twin as T
 import _oracle as O
 import _tri_twin as TT
 import _tri_worlds as TW
+import _kernel_table as KT
 from _common import ROOT, as_oracle_camera, as_oracle_world, bits_equal, mismatch_report, pkg, random_mixed_scene
 from test_light_sampling_cpu import cornell_camera, plain_samples
 
@@ -493,15 +494,10 @@ def test_the_test_room_is_followed_everywhere_and_shows_its_triangles():
 
 
 def test_every_triangle_instantiation_has_a_recipe_in_the_matrix_the_gpu_tests_run():
-    """every RT_KERNEL_TRI(exact, world, ext, big, wide) and every RT_KERNEL_TRI_NEE(...) of stream_kernel_for() is a key of _tri_worlds.FORMS, and nothing else is"""
-    src = open(os.path.join(ROOT, "ray-tracing-v06_amd", "csrc", "rt_device.hip")).read()
-    table = src[src.index("switch (key)"):]
-    args = r"\(\s*(true|false)\s*,\s*(RT_WORLD_\w+)\s*,\s*(\d)\s*,\s*(true|false)\s*,\s*(true|false)\s*\)"
-    for macro in ("RT_KERNEL_TRI", "RT_KERNEL_TRI_NEE"):
-        entries = re.findall(r"\b" + macro + args, table)
-        assert len(entries) == table.count(macro + "(") == 16, macro   # every use is one the pattern reads; the #define above the switch is not a use
-        keys = {(world, int(exact == "true"), int(ext), int(big == "true"), int(wide == "true")) for exact, world, ext, big, wide in entries}
-        assert len(keys) == 16 and keys == set(TW.FORMS), macro
+    """every form of stream_kernel_for()'s TRI family and of its TRI_NEE family is a key of _tri_worlds.FORMS, and nothing else is"""
+    for family in ("TRI", "TRI_NEE"):
+        keys = KT.family(family)
+        assert len(keys) == KT.count(family) == 16 and keys == set(TW.FORMS), family   # (the reader raises on a line of the table it cannot read)
     for (world, exact, ext, big, wide), (variant, env) in TW.FORMS.items():   # the recipes say what stream_kernel_key() makes of them
         assert variant == ({0: 3, 1: 2}[exact] if world == TW.BVH else 0)
         assert env == (TW.LDS, TW.NARROW, TW.WIDE)[big + wide] if world == TW.BVH else env == (TW.NARROW if big else TW.LDS)
